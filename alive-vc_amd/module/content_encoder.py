@@ -29,10 +29,10 @@ class ContentEncoder(PackedNet):
         n, c, t = x.shape
         if c != self.sizes[0] // 2 + 1:
             raise ValueError(f"ContentEncoder expects {self.sizes[0] // 2 + 1} spectrogram bins, got {c}")
+        if x.device.type != "cuda" or self._device.type != "cuda":
+            raise RuntimeError("this network runs on the MI355X only: call .to('cuda') and pass CUDA tensors (no CPU path)")
         if self.generic:
             from . import _generic
-            if x.device.type != "cuda" or self._device.type != "cuda":
-                raise RuntimeError("this network runs on the MI355X only: call .to('cuda') and pass CUDA tensors (no CPU path)")
             y = _generic.content_encoder(self._sd, x, self.sizes[4])
             if out is not None:
                 out.copy_(y)

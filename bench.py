@@ -193,6 +193,28 @@ def guarded(fn):
         return {"error": f"{type(e).__name__}: {e}"[:300]}
 
 
+DUMP_BYTES = 64 * 2**20            # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, wave):
+    """--dump-outputs: what the timed path returned in its last step -- the waveform windows [n, L] -- as float32 .npy, so that two
+    builds can be compared output for output.  When all windows exceed DUMP_BYTES, a fixed sample of whole windows is written
+    (permutation seed 0: the same rows on every run with the same arguments), and their indices beside it as float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n, L = wave.shape
+    rows = min(n, (DUMP_BYTES - 4096) // (L * 4 + 8))
+    assert rows >= 1, f"one window of {L} samples is over the {DUMP_BYTES}-byte budget of --dump-outputs"
+    idx_file = os.path.join(path, "waveform_windows.npy")
+    if rows < n:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:rows].sort().values
+        np.save(idx_file, idx.to(torch.float64).numpy())
+        wave = wave[idx.to(wave.device)]
+    elif os.path.exists(idx_file):                            # (left by an earlier run with a larger batch)
+        os.remove(idx_file)
+    np.save(os.path.join(path, "waveform.npy"), wave.float().cpu().numpy())
+
+
 def timed_steps(fn, reps):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -224,7 +246,12 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="--gpus 1 only: create a world-size-1 process group anyway and run the library-sharded leg with one shard, so "
                          "that RCCL init, the device-tensor collectives and the fences of module/sharded.py execute on a 1-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the waveform windows of the last step (rank 0) to DIR/waveform.npy, float32; "
+                         "over 64 MB, a fixed sample of whole windows, their indices in DIR/waveform_windows.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(launch_ranks(args))
@@ -307,6 +334,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
     assert torch.isfinite(out).all(), "non-finite waveform"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     stats = library.search_stats()                            # of the last timed step's search
 
     # ---- roofline of the scoring kernel ----
