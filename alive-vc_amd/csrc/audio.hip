@@ -38,9 +38,16 @@ __global__ void resample_filter_kernel(int orig, int new_, int width, float* __r
 }
 
 // y[b][m * new + p] = post * sum_j filt[p][j] * (pre * xpad[b][m * orig + j]),  xpad = x shifted by `width` zeros
+// ROWS (alive_resample_rows): pre / post of row b from pre_r / post_r [B]
+template <bool ROWS = false>
 __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, int L, int orig, int new_, int width,
                                                        const float* __restrict__ filt, float pre, float post,
-                                                       float* __restrict__ y, int Lout, bool use_lds) {
+                                                       float* __restrict__ y, int Lout, bool use_lds,
+                                                       const float* __restrict__ pre_r = nullptr, const float* __restrict__ post_r = nullptr) {
+    if constexpr (ROWS) {
+        pre = pre_r[blockIdx.y];
+        post = post_r[blockIdx.y];
+    }
     extern __shared__ float fs_lds[];             // the whole filter bank when it is small (24k <-> 16k: 46 / 48 floats)
     const int taps = 2 * width + orig;
     const float* fs = filt;                       // large banks (44.1k -> 16k: 160 x 475) stay in global memory / L2
@@ -63,6 +70,16 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
         acc = fmaf(f[j], v, acc);
     }
     y[(size_t)b * Lout + o] = acc * post;
+}
+
+// equal rates: torchaudio.functional.gain on the input, then on the output -- (x * pre) * post, row by row
+__global__ __launch_bounds__(256) void gain_rows_kernel(const float* __restrict__ x, int L, const float* __restrict__ pre_r,
+                                                        const float* __restrict__ post_r, float* __restrict__ y) {
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= L) return;
+    const int b = blockIdx.y;
+    const float v = x[(size_t)b * L + o] * pre_r[b];
+    y[(size_t)b * L + o] = v * post_r[b];
 }
 
 __global__ void pcm16_to_float_kernel(const short* __restrict__ in, int64_t n, float* __restrict__ out) {
@@ -107,6 +124,27 @@ extern "C" int alive_resample(const float* x, int B, int L, int orig, int new_, 
     resample_kernel<<<dim3(cdiv(Lout, 256), B), 256, use_lds ? bank : 0, (hipStream_t)stream>>>(
         x, L, orig, new_, width, filt, pre_scale, post_scale, y, Lout, use_lds);
     ALIVE_CHECK_LAUNCH("alive_resample");
+    return ALIVE_OK;
+}
+
+extern "C" int alive_resample_rows(const float* x, int B, int L, int orig, int new_, const float* filt, const float* pre_scale,
+                                   const float* post_scale, float* y, int Lout, void* stream) {
+    ALIVE_CHECK_ARG(x && y && pre_scale && post_scale && B > 0 && L > 0 && orig > 0 && new_ > 0, "alive_resample_rows: bad args");
+    if (orig == new_) {                  // (filt is not read: may be NULL)
+        ALIVE_CHECK_ARG(Lout == L, "alive_resample_rows: equal rates need Lout == L (%d, %d)", Lout, L);
+        gain_rows_kernel<<<dim3(cdiv(L, 256), B), 256, 0, (hipStream_t)stream>>>(x, L, pre_scale, post_scale, y);
+        ALIVE_CHECK_LAUNCH("alive_resample_rows");
+        return ALIVE_OK;
+    }
+    ALIVE_CHECK_ARG(filt != nullptr, "alive_resample_rows: null filter bank");
+    ALIVE_CHECK_ARG(Lout > 0 && Lout <= alive_resample_length(L, orig, new_), "alive_resample_rows: Lout %d exceeds ceil(new*L/orig) = %lld",
+                    Lout, (long long)alive_resample_length(L, orig, new_));
+    const int width = resample_width(orig, new_);
+    const size_t bank = (size_t)new_ * (2 * width + orig) * sizeof(float);
+    const bool use_lds = bank <= 16 * 1024;
+    resample_kernel<true><<<dim3(cdiv(Lout, 256), B), 256, use_lds ? bank : 0, (hipStream_t)stream>>>(
+        x, L, orig, new_, width, filt, 1.0f, 1.0f, y, Lout, use_lds, pre_scale, post_scale);
+    ALIVE_CHECK_LAUNCH("alive_resample_rows");
     return ALIVE_OK;
 }
 

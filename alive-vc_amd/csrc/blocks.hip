@@ -331,7 +331,16 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ X
 // One block per window.  pitch = 12*log2(f0/440) - 9, mean over finite entries, intonation / shift,
 // back to Hz, NaN/inf -> 0, * f0_rate.  log2/exp2 are evaluated in fp64 and rounded once, the closest
 // a device kernel can get to the 1-ulp vector libm of the CPU path.
-__global__ __launch_bounds__(256) void pitch_kernel(float* f0, int T, int mode, float f0_rate, float shift, float inton) {
+// ROWS (alive_pitch_transform_rows): the three parameters of row n from rate_r / shift_r / inton_r [N]
+template <bool ROWS = false>
+__global__ __launch_bounds__(256) void pitch_kernel(float* f0, int T, int mode, float f0_rate, float shift, float inton,
+                                                    const float* __restrict__ rate_r = nullptr, const float* __restrict__ shift_r = nullptr,
+                                                    const float* __restrict__ inton_r = nullptr) {
+    if constexpr (ROWS) {
+        f0_rate = rate_r[blockIdx.x];
+        shift = shift_r[blockIdx.x];
+        inton = inton_r[blockIdx.x];
+    }
     __shared__ double s_sum[256];
     __shared__ int s_cnt[256];
     float* f = f0 + (size_t)blockIdx.x * T;
@@ -600,6 +609,15 @@ extern "C" int alive_pitch_transform(float* f0, int N, int T, int mode, float f0
     ALIVE_CHECK_ARG(f0 && N > 0 && T > 0 && (mode == 0 || mode == 1), "alive_pitch_transform: bad args");
     pitch_kernel<<<N, 256, 0, (hipStream_t)stream>>>(f0, T, mode, f0_rate, pitch_shift, intonation);
     ALIVE_CHECK_LAUNCH("alive_pitch_transform");
+    return ALIVE_OK;
+}
+
+extern "C" int alive_pitch_transform_rows(float* f0, int N, int T, int mode, const float* f0_rate, const float* pitch_shift,
+                                          const float* intonation, void* stream) {
+    ALIVE_CHECK_ARG(f0 && f0_rate && pitch_shift && intonation, "alive_pitch_transform_rows: null pointer");
+    ALIVE_CHECK_ARG(N > 0 && T > 0 && (mode == 0 || mode == 1), "alive_pitch_transform_rows: bad args");
+    pitch_kernel<true><<<N, 256, 0, (hipStream_t)stream>>>(f0, T, mode, 0.0f, 0.0f, 0.0f, f0_rate, pitch_shift, intonation);
+    ALIVE_CHECK_LAUNCH("alive_pitch_transform_rows");
     return ALIVE_OK;
 }
 

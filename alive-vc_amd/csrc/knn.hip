@@ -138,8 +138,10 @@ __global__ __launch_bounds__(256) void lib_pack_kernel(const float* __restrict__
             if (mm < M_pad) {
                 float v = tile[lane][r];
                 if (mm < M) rows[(size_t)mm * D + d0 + lane] = v;
-                float q = (mm < M) ? v / nrm[r] : 0.0f;
-                lib[(size_t)mm * D + d0 + lane] = f32_to_bf16_rn(q);
+                if (lib != nullptr) {              // (alive_library_pack_rows: fp32 rows and norms only)
+                    float q = (mm < M) ? v / nrm[r] : 0.0f;
+                    lib[(size_t)mm * D + d0 + lane] = f32_to_bf16_rn(q);
+                }
             }
         }
         __syncthreads();
@@ -2022,14 +2024,16 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void knn_scan_kernel(const float* 
 // LDS exchange between the four waves and one barrier: no global load after the first.  (Until round 4 every thread re-read the
 // heads of all its lists in every round and the block reduced through an LDS tree: 26 us of dependent L2 round trips for k = 4.)
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+// The body is shared with the grouped search (knn_grouped_merge_kernel): list w of the frame at part[w * stride + t * k + e],
+// the result at out[t_out * k + j].
 template <bool K4>
-__global__ __launch_bounds__(256) void knn_scan_merge_kernel(const float* __restrict__ part_val, const int* __restrict__ part_idx,
-                                                             int nw, int k, int64_t idx_base, float* __restrict__ out_val,
-                                                             int* __restrict__ out_idx) {
+__device__ __forceinline__ void scan_merge_frame(const float* __restrict__ part_val, const int* __restrict__ part_idx, int64_t stride,
+                                                 int nw, int t, int k, int64_t idx_base, float* __restrict__ out_val,
+                                                 int* __restrict__ out_idx, int64_t t_out) {
     constexpr int NL = SCAN_MAX_LISTS / 256;
     __shared__ float sv[2][4];
     __shared__ int si[2][4], sw[2][4];
-    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int head[NL];
     f32x4 pv4[K4 ? NL : 1];
     i32x4 pi4[K4 ? NL : 1];
@@ -2043,14 +2047,14 @@ __global__ __launch_bounds__(256) void knn_scan_merge_kernel(const float* __rest
             const int w = tid + 256 * i;
             if (k == 4) {
                 const bool in = w < nw;
-                pv4[i] = *(const f32x4*)(part_val + (size_t)(in ? w : 0) * 64 + t * 4);
-                pi4[i] = *(const i32x4*)(part_idx + (size_t)(in ? w : 0) * 64 + t * 4);
+                pv4[i] = *(const f32x4*)(part_val + (size_t)(in ? w : 0) * stride + t * 4);
+                pi4[i] = *(const i32x4*)(part_idx + (size_t)(in ? w : 0) * stride + t * 4);
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const bool in = w < nw && e < k;
-                    pv4[i][e] = in ? part_val[(size_t)w * 64 + t * k + e] : -INFINITY;
-                    pi4[i][e] = in ? part_idx[(size_t)w * 64 + t * k + e] : 0x7fffffff;
+                    pv4[i][e] = in ? part_val[(size_t)w * stride + t * k + e] : -INFINITY;
+                    pi4[i][e] = in ? part_idx[(size_t)w * stride + t * k + e] : 0x7fffffff;
                 }
             }
         }
@@ -2069,8 +2073,8 @@ __global__ __launch_bounds__(256) void knn_scan_merge_kernel(const float* __rest
                     v = head[i] == 0 ? pv4[i][0] : (head[i] == 1 ? pv4[i][1] : (head[i] == 2 ? pv4[i][2] : pv4[i][3]));
                     id = head[i] == 0 ? pi4[i][0] : (head[i] == 1 ? pi4[i][1] : (head[i] == 2 ? pi4[i][2] : pi4[i][3]));
                 } else {
-                    v = part_val[(size_t)w * 64 + t * k + head[i]];
-                    id = part_idx[(size_t)w * 64 + t * k + head[i]];
+                    v = part_val[(size_t)w * stride + t * k + head[i]];
+                    id = part_idx[(size_t)w * stride + t * k + head[i]];
                 }
                 if (v > bv || (v == bv && id < bi)) { bv = v; bi = id; bl = i; }
             }
@@ -2093,8 +2097,8 @@ __global__ __launch_bounds__(256) void knn_scan_merge_kernel(const float* __rest
             if (ov > gv || (ov == gv && (unsigned)oi < (unsigned)gi)) { gv = ov; gi = oi; gt = sw[par][q]; }
         }
         if (tid == 0) {
-            out_val[(size_t)t * k + j] = gv;
-            out_idx[(size_t)t * k + j] = (gi == 0x7fffffff || !(gv > -INFINITY)) ? -1 : (int)(idx_base + gi);
+            out_val[(size_t)t_out * k + j] = gv;
+            out_idx[(size_t)t_out * k + j] = (gi == 0x7fffffff || !(gv > -INFINITY)) ? -1 : (int)(idx_base + gi);
         }
         if (gt == tid && bl >= 0) {
 #pragma unroll
@@ -2105,20 +2109,266 @@ __global__ __launch_bounds__(256) void knn_scan_merge_kernel(const float* __rest
     }
 }
 
+template <bool K4>
+__global__ __launch_bounds__(256) void knn_scan_merge_kernel(const float* __restrict__ part_val, const int* __restrict__ part_idx,
+                                                             int nw, int k, int64_t idx_base, float* __restrict__ out_val,
+                                                             int* __restrict__ out_idx) {
+    scan_merge_frame<K4>(part_val, part_idx, 64, nw, blockIdx.x, k, idx_base, out_val, out_idx, blockIdx.x);
+}
+
+// ----------------------------------------------------------------------------------------------
+// grouped exact search (multi-session streaming): row n of the batch searches its own segment of a voice pool
+// ----------------------------------------------------------------------------------------------
+// The streaming scan above for a batch whose rows search DIFFERENT libraries: every voice's fp32 rows are concatenated into
+// one pool, and device arrays seg_lo[N] / seg_len[N] name the segment row n searches (seg_len 0: an inactive slot).  The
+// table may change between replays of a captured graph, so nothing on the host depends on it: every grid is sized from
+// N, T and k alone, and a one-block prologue turns the table into a work list in the workspace --
+//   groups  the rows that search the same segment (one pass over a segment serves all of them);
+//   chunks  a group's frames (its rows x T) cut into runs of GR_F = 64 / k frames: one register pair per lane, lane = frame * k +
+//           slot, exactly the lists of knn_scan_kernel;
+//   slabs   a segment cut into nslab row ranges, nslab chosen so that all items together fill about GR_ITEMS waves.
+// An item is (group, slab, chunk); the items of one slab are consecutive, so the waves that read a slab at the same time are
+// those of its different chunks and re-reads come from L2: each segment in use leaves HBM once per call.  Scores use the
+// arithmetic of knn_scan_kernel / knn_rescore_kernel (frames prepared by src_prep_small_kernel, rows divided by norm_div /
+// div_by, fmaf over d in the same lane partition, the xor-tree wave_sum), and a frame's lists are merged by the body of
+// knn_scan_merge_kernel: val and idx - seg_lo are bitwise what alive_knn_search_strict returns for the segment packed alone.
+constexpr int GR_MAX_ROWS = 1024;       // batch rows one call takes (the prologue keeps its tables in LDS)
+constexpr int GR_ITEMS = SCAN_MAX_LISTS; // target work items per call (= waves launched), and the most lists a frame merges
+constexpr int GR_MIN_SLAB = 4;          // rows per slab at least
+constexpr int GR_BLOCKS = GR_ITEMS / SCAN_WAVES;
+enum { GR_G = 0, GR_LO, GR_LEN, GR_SIZE, GR_MSTART, GR_CHUNKS, GR_NSLAB, GR_BASE, GR_FIELDS };
+
+struct GroupedWs {
+    float* s_f32;
+    unsigned short* s_bf16;
+    int* hdr;        // [0] groups, [1] items
+    int* grp;        // [GR_MAX_ROWS + 1][GR_FIELDS]; grp[G][GR_BASE] = items
+    int* members;    // [N] rows of the batch, grouped
+    int* row_g;      // [N] group of row n (-1: inactive)
+    int* row_rank;   // [N] rank of row n in its group
+    float* pv;
+    int* pi;
+    size_t bytes;
+};
+
+static int64_t grouped_items_cap(int N, int T, int k) {
+    const int64_t chunks = (int64_t)N * ((T + 64 / k - 1) / (64 / k));
+    return chunks > GR_ITEMS ? chunks : GR_ITEMS;
+}
+
+static GroupedWs grouped_ws_layout(void* base, int N, int T, int k) {
+    GroupedWs w{};
+    char* p = (char*)base;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* q = p + off;
+        off = (off + bytes + 255) / 256 * 256;
+        return q;
+    };
+    const int64_t Tt = (int64_t)N * T, items = grouped_items_cap(N, T, k);
+    w.s_f32 = (float*)take(Tt * D * sizeof(float));
+    w.s_bf16 = (unsigned short*)take(Tt * D * sizeof(unsigned short));
+    w.hdr = (int*)take(4 * sizeof(int));
+    w.grp = (int*)take((GR_MAX_ROWS + 1) * GR_FIELDS * sizeof(int));
+    w.members = (int*)take(N * sizeof(int));
+    w.row_g = (int*)take(N * sizeof(int));
+    w.row_rank = (int*)take(N * sizeof(int));
+    w.pv = (float*)take(items * 64 * sizeof(float));
+    w.pi = (int*)take(items * 64 * sizeof(int));
+    w.bytes = off;
+    return w;
+}
+
+// one block: segment table -> groups, members, items.  The rows are few (<= 1024) and the walk is serial where it needs an order.
+__global__ __launch_bounds__(256) void knn_grouped_plan_kernel(const int* __restrict__ seg_lo, const int* __restrict__ seg_len, int N, int T,
+                                                               int64_t P, int k, GroupedWs w) {
+    __shared__ int s_lo[GR_MAX_ROWS], s_len[GR_MAX_ROWS], s_lead[GR_MAX_ROWS];
+    const int tid = threadIdx.x;
+    for (int n = tid; n < N; n += 256) {
+        const int lo = seg_lo[n], len = seg_len[n];
+        // a segment outside the pool or shorter than k is an inactive row (the host-side layers refuse such tables)
+        const bool ok = len > 0 && len >= k && lo >= 0 && (int64_t)lo + len <= P;
+        s_lo[n] = lo;
+        s_len[n] = ok ? len : 0;
+    }
+    __syncthreads();
+    for (int n = tid; n < N; n += 256) {
+        int lead = -1;
+        if (s_len[n] > 0)
+            for (int m = 0; m <= n; ++m)
+                if (s_len[m] == s_len[n] && s_lo[m] == s_lo[n]) { lead = m; break; }
+        s_lead[n] = lead;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int F = 64 / k;
+        int G = 0;
+        for (int n = 0; n < N; ++n) {
+            const int lead = s_lead[n];
+            if (lead < 0) { w.row_g[n] = -1; w.row_rank[n] = 0; continue; }
+            int g;
+            if (lead == n) {
+                g = G++;
+                int* e = w.grp + g * GR_FIELDS;
+                e[GR_G] = g; e[GR_LO] = s_lo[n]; e[GR_LEN] = s_len[n]; e[GR_SIZE] = 0;
+            } else {
+                g = w.row_g[lead];
+            }
+            int* e = w.grp + g * GR_FIELDS;
+            w.row_g[n] = g;
+            w.row_rank[n] = e[GR_SIZE]++;
+        }
+        int mstart = 0, chunks_total = 0;
+        for (int g = 0; g < G; ++g) {
+            int* e = w.grp + g * GR_FIELDS;
+            e[GR_MSTART] = mstart;
+            mstart += e[GR_SIZE];
+            e[GR_CHUNKS] = (e[GR_SIZE] * T + F - 1) / F;
+            chunks_total += e[GR_CHUNKS];
+        }
+        int items = 0;
+        const int per = chunks_total > 0 ? GR_ITEMS / chunks_total : 0;        // slabs per segment that fill GR_ITEMS waves
+        for (int g = 0; g < G; ++g) {
+            int* e = w.grp + g * GR_FIELDS;
+            int nslab = e[GR_LEN] / GR_MIN_SLAB;
+            nslab = nslab < per ? nslab : per;
+            e[GR_NSLAB] = nslab < 1 ? 1 : nslab;
+            e[GR_BASE] = items;
+            items += e[GR_NSLAB] * e[GR_CHUNKS];
+        }
+        w.grp[G * GR_FIELDS + GR_BASE] = items;
+        w.hdr[0] = G;
+        w.hdr[1] = items;
+    }
+    __syncthreads();
+    for (int n = tid; n < N; n += 256) {
+        const int g = w.row_g[n];
+        if (g >= 0) w.members[w.grp[g * GR_FIELDS + GR_MSTART] + w.row_rank[n]] = n;
+    }
+}
+
+// one wave per item (wave-stride loop): the rows of one slab scored against the frames of one chunk, knn_scan_kernel's loop
+__global__ __launch_bounds__(64 * SCAN_WAVES) void knn_grouped_scan_kernel(const float* __restrict__ rows, const float* __restrict__ norms,
+                                                                           int T, int k, GroupedWs w) {
+    const int lane = threadIdx.x & 63;
+    const int nw = gridDim.x * SCAN_WAVES;
+    const int G = w.hdr[0], items = w.hdr[1];
+    const int F = 64 / k;
+    for (int it = blockIdx.x * SCAN_WAVES + (threadIdx.x >> 6); it < items; it += nw) {
+        int a = 0, b = G - 1;                                  // the group of the item: grp[g][GR_BASE] <= it < grp[g + 1][GR_BASE]
+        while (a < b) {
+            const int m = (a + b + 1) >> 1;
+            if (w.grp[m * GR_FIELDS + GR_BASE] <= it) a = m;
+            else b = m - 1;
+        }
+        const int* e = w.grp + a * GR_FIELDS;
+        const int chunks = e[GR_CHUNKS], nslab = e[GR_NSLAB], len = e[GR_LEN], size = e[GR_SIZE];
+        const int r = it - e[GR_BASE];
+        const int slab = r / chunks, c = r - slab * chunks;
+        const int64_t r0 = e[GR_LO] + (int64_t)len * slab / nslab, r1 = e[GR_LO] + (int64_t)len * (slab + 1) / nslab;
+        const int left = size * T - c * F;
+        const int nf = left < F ? left : F;
+        int my_ft = 0;                                         // lane f < nf: the batch frame of chunk frame f
+        if (lane < nf) {
+            const int j = c * F + lane;
+            my_ft = w.members[e[GR_MSTART] + j / T] * T + j % T;
+        }
+        const int my_t = lane / k;
+        const bool live = lane < nf * k;
+        float lv = -INFINITY;
+        int li = 0x7fffffff;
+        f32x4 n0 = {}, n1 = {}, n2 = {};
+        float nnx = 1.0f;
+        if (r0 < r1) {
+            const f32x4* rp = (const f32x4*)(rows + (size_t)r0 * D);
+            n0 = rp[lane]; n1 = rp[lane + 64]; n2 = rp[lane + 128];
+            nnx = norms[r0];
+        }
+        for (int64_t rr = r0; rr < r1; ++rr) {
+            f32x4 q0 = n0, q1 = n1, q2 = n2;
+            const float nn = nnx;
+            if (rr + 1 < r1) {
+                const f32x4* rp = (const f32x4*)(rows + (size_t)(rr + 1) * D);
+                n0 = rp[lane]; n1 = rp[lane + 64]; n2 = rp[lane + 128];
+                nnx = norms[rr + 1];
+            }
+            const NormDiv nd = norm_div(nn);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { q0[j] = div_by(q0[j], nd); q1[j] = div_by(q1[j], nd); q2[j] = div_by(q2[j], nd); }
+            float p = -INFINITY;
+            for (int t = 0; t < nf; ++t) {
+                const int ft = __shfl(my_ft, t);
+                const f32x4* sp = (const f32x4*)(w.s_f32 + (size_t)ft * D);
+                const f32x4 s0 = sp[lane], s1 = sp[lane + 64], s2 = sp[lane + 128];
+                float d = 0.0f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d = fmaf(s0[j], q0[j], d);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d = fmaf(s1[j], q1[j], d);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d = fmaf(s2[j], q2[j], d);
+                d = wave_sum(d);
+                if (live && t == my_t) p = d;
+            }
+            const int ri = (int)rr;
+            const bool before = lv > p || (lv == p && li < ri);
+            const float up_v = __shfl_up(lv, 1);
+            const int up_i = __shfl_up(li, 1);
+            const bool up_before = (lane % k == 0) ? true : (up_v > p || (up_v == p && up_i < ri));
+            if (live && !before) {
+                lv = up_before ? p : up_v;
+                li = up_before ? ri : up_i;
+            }
+        }
+        w.pv[(size_t)it * 64 + lane] = lv;
+        w.pi[(size_t)it * 64 + lane] = li;
+    }
+}
+
+// one block per batch frame: the nslab lists of its chunk -> exact top-k (pool indices); inactive rows get val -inf, idx -1
+template <bool K4>
+__global__ __launch_bounds__(256) void knn_grouped_merge_kernel(int T, int k, GroupedWs w, float* __restrict__ out_val,
+                                                                int* __restrict__ out_idx) {
+    const int64_t ft = blockIdx.x;
+    const int n = (int)(ft / T), t = (int)(ft - (int64_t)n * T);
+    const int g = w.row_g[n];
+    if (g < 0) {
+        if ((int)threadIdx.x < k) {
+            out_val[ft * k + threadIdx.x] = -INFINITY;
+            out_idx[ft * k + threadIdx.x] = -1;
+        }
+        return;
+    }
+    const int* e = w.grp + g * GR_FIELDS;
+    const int F = 64 / k;
+    const int j = w.row_rank[n] * T + t;
+    const int c = j / F, pos = j - c * F;
+    const size_t off = (size_t)(e[GR_BASE] + c) * 64;
+    scan_merge_frame<K4>(w.pv + off, w.pi + off, (int64_t)e[GR_CHUNKS] * 64, e[GR_NSLAB], pos, k, 0, out_val, out_idx, ft);
+}
+
 // ----------------------------------------------------------------------------------------------
 // merge shards + gather + mean + blend.  Block = 32 consecutive frames of one window.
 // ----------------------------------------------------------------------------------------------
 // NPER = candidates per lane in the merge: S * k <= 64 * NPER (2: the usual k <= 8 over up to 16 shards; 8: k up to 64)
-template <int NPER, int KMAX>
+// ROWS (alive_knn_merge_gather_rows, one shard): alpha of window n from alpha_rows[n], 1 - alpha formed in double and rounded
+// once as the host does for the scalar form; a frame without a match (idx -1: an inactive slot of the grouped search) passes
+// its source through.
+template <int NPER, int KMAX, bool ROWS = false>
 __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __restrict__ cand_val,
                                                                const int* __restrict__ cand_idx, int S, int k, float alpha,
                                                                float one_minus, const float* __restrict__ rows, const float* __restrict__ src,
                                                                int T, int64_t Tt, float* __restrict__ out,
-                                                               int* __restrict__ final_idx) {
+                                                               int* __restrict__ final_idx, const double* __restrict__ alpha_rows = nullptr) {
     __shared__ int sel[32][KMAX];
     __shared__ float tile[32][65];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = blockIdx.y;
+    if constexpr (ROWS) {
+        const double a = alpha_rows[n];
+        alpha = (float)a;
+        one_minus = (float)(1.0 - a);
+    }
     const int t0 = blockIdx.x * 32;
     const int nf = (T - t0) < 32 ? (T - t0) : 32;
 
@@ -2189,7 +2439,8 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
             if (f < nf) {
                 size_t o = ((size_t)n * D + d0 + d) * T + t0 + f;
                 float m = tile[f][d];
-                out[o] = m * one_minus + src[o] * alpha;
+                if (ROWS && sel[f][0] < 0) out[o] = src[o];
+                else out[o] = m * one_minus + src[o] * alpha;
             }
         }
         __syncthreads();
@@ -3091,5 +3342,55 @@ extern "C" int alive_dedup_pass(const float* val, const int32_t* idx, int64_t M,
     ALIVE_CHECK_ARG(val && idx && state && undecided && M >= 1 && k >= 1, "alive_dedup_pass: bad arguments");
     dedup_pass_kernel<<<(unsigned)((M + 255) / 256), 256, 0, (hipStream_t)stream>>>(val, idx, M, k, (float)threshold, state, undecided);
     ALIVE_CHECK_LAUNCH("alive_dedup_pass");
+    return ALIVE_OK;
+}
+
+// ---- grouped exact search (multi-session streaming) ----
+extern "C" int alive_library_pack_rows(const float* tokens, int64_t M, int Dd, float* rows_f32, float* norms, void* stream) {
+    ALIVE_CHECK_ARG(tokens && rows_f32 && norms, "alive_library_pack_rows: null pointer");
+    ALIVE_CHECK_ARG(Dd == D, "alive_library_pack_rows: feature dim %d, expected %d", Dd, D);
+    ALIVE_CHECK_ARG(M >= 1 && M < (int64_t)1 << 31, "alive_library_pack_rows: M out of range");
+    const int64_t M_pad = alive_library_padded_rows(M);
+    lib_pack_kernel<<<(unsigned)(M_pad / 64), 256, 0, (hipStream_t)stream>>>(tokens, M, M_pad, nullptr, rows_f32, norms);
+    ALIVE_CHECK_LAUNCH("alive_library_pack_rows");
+    return ALIVE_OK;
+}
+
+extern "C" size_t alive_knn_grouped_workspace_bytes(int N, int T, int k) {
+    if (N < 1 || N > GR_MAX_ROWS || T < 1 || k < 1 || k > KH) return 0;
+    return grouped_ws_layout(nullptr, N, T, k).bytes;
+}
+
+extern "C" int alive_knn_search_grouped(const float* src, int N, int T, const float* rows_f32, const float* norms, int64_t P,
+                                        const int32_t* seg_lo, const int32_t* seg_len, int k, float* out_val, int32_t* out_idx,
+                                        void* ws, void* stream) {
+    ALIVE_CHECK_ARG(src && rows_f32 && norms && seg_lo && seg_len && out_val && out_idx && ws, "alive_knn_search_grouped: null pointer");
+    ALIVE_CHECK_ARG(k >= 1 && k <= KH, "alive_knn_search_grouped: k=%d outside [1,%d]", k, KH);
+    ALIVE_CHECK_ARG(N >= 1 && N <= GR_MAX_ROWS, "alive_knn_search_grouped: N=%d outside [1,%d]", N, GR_MAX_ROWS);
+    ALIVE_CHECK_ARG(T >= 1 && (int64_t)N * T <= (int64_t)1 << 20, "alive_knn_search_grouped: T=%d out of range", T);
+    ALIVE_CHECK_ARG(P >= k && P < (int64_t)1 << 31, "alive_knn_search_grouped: pool of %lld rows (k=%d)", (long long)P, k);
+    const GroupedWs w = grouped_ws_layout(ws, N, T, k);
+    const int64_t Tt = (int64_t)N * T;
+    hipStream_t s = (hipStream_t)stream;
+    src_prep_small_kernel<<<(unsigned)Tt, 256, 0, s>>>(src, T, Tt, w.s_f32, w.s_bf16, nullptr);
+    knn_grouped_plan_kernel<<<1, 256, 0, s>>>(seg_lo, seg_len, N, T, P, k, w);
+    knn_grouped_scan_kernel<<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, T, k, w);
+    if (k <= 4) knn_grouped_merge_kernel<true><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
+    else knn_grouped_merge_kernel<false><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
+    ALIVE_CHECK_LAUNCH("alive_knn_search_grouped");
+    return ALIVE_OK;
+}
+
+extern "C" int alive_knn_merge_gather_rows(const float* cand_val, const int32_t* cand_idx, int k, const double* alpha,
+                                           const float* rows_f32_full, const float* src, int N, int T, float* out,
+                                           int32_t* final_idx, void* stream) {
+    ALIVE_CHECK_ARG(cand_val && cand_idx && alpha && rows_f32_full && src && out, "alive_knn_merge_gather_rows: null pointer");
+    ALIVE_CHECK_ARG(k >= 1 && k <= 8, "alive_knn_merge_gather_rows: k=%d outside [1,8]", k);
+    ALIVE_CHECK_ARG(N > 0 && T > 0, "alive_knn_merge_gather_rows: empty source");
+    const int zs = (int64_t)cdiv(T, 32) * N < 64 ? D / 64 : 1;       // as alive_knn_merge_gather
+    const dim3 g(cdiv(T, 32), N, zs);
+    knn_merge_gather_kernel<2, 8, true><<<g, 256, 0, (hipStream_t)stream>>>(cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T,
+                                                                         (int64_t)N * T, out, final_idx, alpha);
+    ALIVE_CHECK_LAUNCH("alive_knn_merge_gather_rows");
     return ALIVE_OK;
 }

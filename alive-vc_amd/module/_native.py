@@ -71,6 +71,10 @@ PROTOTYPES = {
     "alive_knn_search_fp8_rot_timed": (_I, [_VP, _VP, _F, _I, _I, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_knn_search_fp6": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP]),
     "alive_knn_search_fp6_timed": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "alive_library_pack_rows": (_I, [_VP, _I64, _I, _VP, _VP, _VP]),
+    "alive_knn_grouped_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "alive_knn_search_grouped": (_I, [_VP, _I, _I, _VP, _VP, _I64, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "alive_knn_merge_gather_rows": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP]),
     "alive_dedup_pass": (_I, [_VP, _VP, _I64, _I, _D, _VP, _VP, _VP]),
     "alive_knn_merge_gather": (_I, [_VP, _VP, _I, _I, _D, _VP, _VP, _I, _I, _VP, _VP, _VP]),
     "alive_conv1d": (_I, [C.POINTER(AliveConv), _VP]),
@@ -112,6 +116,7 @@ PROTOTYPES = {
     "alive_resample_length": (_I64, [_I64, _I, _I]),
     "alive_resample_filter": (_I, [_I, _I, _VP, _VP]),
     "alive_resample": (_I, [_VP, _I, _I, _I, _I, _VP, _F, _F, _VP, _I, _VP]),
+    "alive_resample_rows": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _VP]),
     "alive_pcm16_to_float": (_I, [_VP, _I64, _VP, _VP]),
     "alive_float_to_pcm16": (_I, [_VP, _I64, _VP, _VP]),
     "alive_weight_count": (_I, [_I]),
@@ -126,6 +131,7 @@ PROTOTYPES = {
     "alive_decoder_forward": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "alive_decoder_forward_range": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP]),
     "alive_pitch_transform": (_I, [_VP, _I, _I, _I, _F, _F, _F, _VP]),
+    "alive_pitch_transform_rows": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
 }
 
 

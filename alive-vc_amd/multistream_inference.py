@@ -1,0 +1,160 @@
+"""Multi-session streaming CLI: many file-driven sessions converted concurrently, chunk by chunk, through one
+MultiStreamConverter (module/multistream.py) -- one batched device step per tick for all of them.
+
+The sessions file is a JSON list; each entry:
+  {"input": "a.wav",                      the session's input
+   "target": "spk.wav" and / or "lib": "voice_library.pt",   its voice (as -t / -lib of realtime_inference.py)
+   "pitch": 0, "f0_rate": 1, "alpha": 0, "gain": 0, "input_gain": 0,     optional, realtime_inference.py's meanings
+   "start": 0,                            optional: the tick at which the session joins
+   "output": "a_out.wav"}                 optional: default <outdir>/<index>_<input name>.wav
+A session's slot opens at its start tick, gets one chunk per tick while its input lasts and closes after its last chunk.
+Flags shared with realtime_inference.py keep its spelling: -c, -b, -k, -isr, -osr, --no-graph.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from module import audio_io                                     # noqa: E402
+from module.content_encoder import ContentEncoder                # noqa: E402
+from module.decoder import Decoder                               # noqa: E402
+from module.f0_estimator import F0Estimator                      # noqa: E402
+from module.multistream import MultiStreamConverter, VoicePool   # noqa: E402
+from module.spectrogram import spectrogram                       # noqa: E402
+from module.voice_library import VoiceLibrary                    # noqa: E402
+
+SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "start", "output")
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description="Convert many voices concurrently")
+    parser.add_argument('sessions', help="JSON list of sessions (see the module docstring)")
+    parser.add_argument('-o', '--output-dir', default="outputs")
+    parser.add_argument('-d', '--device', default='cuda', choices=['cpu', 'cuda', 'mps'])
+    parser.add_argument('-dep', '--decoder-path', default="decoder.pt")
+    parser.add_argument('-cep', '--content-encoder-path', default="content_encoder.pt")
+    parser.add_argument('-f0ep', '--f0-estimator-path', default="f0_estimator.pt")
+    parser.add_argument('-b', '--buffersize', default=8, type=int)
+    parser.add_argument('-c', '--chunk', default=960, type=int)
+    parser.add_argument('-k', default=4, type=int)
+    parser.add_argument('-isr', '--input-sr', default=16000, type=int)
+    parser.add_argument('-osr', '--output-sr', default=16000, type=int)
+    parser.add_argument('--slots', default=0, type=int, help="session slots of the converter (default: one per session)")
+    parser.add_argument('--no-graph', action='store_true',
+                        help="launch the per-tick device pipeline kernel by kernel instead of replaying one captured hipGraph")
+    return parser
+
+
+def load_sessions(path):
+    """the sessions file -> list of dicts with every key filled in; ValueError on a malformed entry"""
+    with open(path) as f:
+        sessions = json.load(f)
+    if not isinstance(sessions, list) or not sessions:
+        raise ValueError(f"{path}: expected a non-empty JSON list of sessions")
+    base = os.path.dirname(os.path.abspath(path))
+    out = []
+    for i, s in enumerate(sessions):
+        if not isinstance(s, dict) or "input" not in s:
+            raise ValueError(f"session {i}: an object with an \"input\" wav is required")
+        unknown = set(s) - set(SESSION_KEYS)
+        if unknown:
+            raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: {SESSION_KEYS})")
+        if s.get("target") is None and s.get("lib") is None:
+            raise ValueError(f"session {i}: needs a \"target\" wav or a \"lib\" voice library")
+        rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))
+        e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
+                 pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
+                 gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)))
+        if e["start"] < 0:
+            raise ValueError(f"session {i}: start tick {e['start']} < 0")
+        out.append(e)
+    return out
+
+
+def voice_tokens(ce, target, lib, device):
+    """a session's library as realtime_inference.py builds it: the target utterance's frames (every 4th) and / or a library file"""
+    tgt = torch.zeros(1, 768, 0, device=device)
+    if target is not None:
+        wf, sr = audio_io.load(target)
+        wf = audio_io.resample(wf.to(device), sr, 16000)
+        wf = wf / wf.abs().max()
+        tgt = ce(spectrogram(wf[:1]))[:, :, ::4]
+    if lib is not None:
+        VL = VoiceLibrary().to(device)
+        VL.load_state_dict(torch.load(lib, map_location=device))
+        tgt = torch.cat([tgt, VL.tokens], dim=2)
+    return tgt[0].contiguous()
+
+
+def input_pcm(path, input_sr, device):
+    wf, sr = audio_io.load(path)
+    wf = audio_io.resample(wf.mean(dim=0, keepdim=True).to(device), sr, input_sr)[0].cpu()
+    return (wf.numpy() * 32767).astype(np.int16)
+
+
+def run(conv, pcms, starts, chunk, params):
+    """drive `conv` tick by tick: session i occupies slot i (opened with params[i]) from tick starts[i] for len(pcms[i]) // chunk
+    ticks.
+    Returns the emitted int16 chunks of every session, concatenated."""
+    n_chunks = [len(p) // chunk for p in pcms]
+    outs = [[] for _ in pcms]
+    last = max(s + n for s, n in zip(starts, n_chunks))
+    for tick in range(last):
+        feed = {}
+        for i, (s, n) in enumerate(zip(starts, n_chunks)):
+            if tick == s and n > 0:
+                conv.open(i, **params[i])
+            if s <= tick < s + n:
+                j = tick - s
+                feed[i] = pcms[i][j * chunk:(j + 1) * chunk]
+        res = conv.step(feed)
+        for i, o in res.items():
+            if o is not None:
+                outs[i].append(o)
+        for i, (s, n) in enumerate(zip(starts, n_chunks)):
+            if tick == s + n - 1:
+                conv.close(i)
+    return [np.concatenate(o) if o else np.zeros(0, np.int16) for o in outs]
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    sessions = load_sessions(args.sessions)
+    if args.device != 'cuda' or not torch.cuda.is_available():
+        raise SystemExit("Error: this build needs a ROCm device: pass -d cuda on an MI355X host.")
+    device = torch.device('cuda')
+    PE, CE, Dec = F0Estimator().to(device), ContentEncoder().to(device), Decoder().to(device)
+    PE.load_state_dict(torch.load(args.f0_estimator_path, map_location=device))
+    CE.load_state_dict(torch.load(args.content_encoder_path, map_location=device))
+    Dec.load_state_dict(torch.load(args.decoder_path, map_location=device))
+
+    pool, names = VoicePool(device=device), []
+    for s in sessions:
+        name = json.dumps([s["target"], s["lib"]])
+        if name not in pool.segments:
+            pool.add(name, voice_tokens(CE, s["target"], s["lib"], device))
+        names.append(name)
+    slots = max(args.slots, len(sessions))
+    conv = MultiStreamConverter(CE, PE, Dec, pool, slots, chunk=args.chunk, buffersize=args.buffersize, input_sr=args.input_sr,
+                                output_sr=args.output_sr, k=args.k, device=device)
+    params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
+                   input_gain=s["input_gain"]) for n, s in zip(names, sessions)]
+    if not args.no_graph:
+        conv.enable_graph()
+    pcms = [input_pcm(s["input"], args.input_sr, device) for s in sessions]
+    outs = run(conv, pcms, [s["start"] for s in sessions], args.chunk, params)
+    os.makedirs(args.output_dir, exist_ok=True)
+    for i, (s, o) in enumerate(zip(sessions, outs)):
+        path = s["output"] or os.path.join(args.output_dir, f"{i}_{os.path.splitext(os.path.basename(s['input']))[0]}.wav")
+        audio_io.save(path, torch.from_numpy(o.astype(np.float32) / 32768)[None], args.output_sr, "pcm16")
+        print(f"session {i}: {len(o)} samples -> {path}")
+    return outs
+
+
+if __name__ == "__main__":
+    main()

@@ -203,6 +203,29 @@ int alive_knn_merge_gather(const float* cand_val, const int32_t* cand_idx, int n
                            double alpha, const float* rows_f32_full, const float* src,
                            int N, int T, float* out, int32_t* final_idx, void* stream);
 
+/* ---------------------------------------------- grouped search (multi-session streaming) ----
+ * alive_library_pack_rows: the fp32 rows and norms of alive_library_pack alone (bitwise the same norms), for a VOICE POOL:
+ *   every voice's tokens[768][M] packed at its own offset of one rows_f32[P][768] / norms[P] table.
+ * alive_knn_search_grouped: exact top-k (k <= 8) of every frame of src[N][768][T] against the pool segment of its row:
+ *   row n searches rows [seg_lo[n], seg_lo[n] + seg_len[n]) of the pool (seg_lo / seg_len: DEVICE int32[N]); seg_len[n] == 0
+ *   marks an inactive row (its frames get val -inf, idx -1), as does a segment outside the pool or shorter than k.
+ *   out_val / out_idx [N*T][k]: val and idx - seg_lo[n] are bitwise what alive_knn_search_strict returns for the frame against
+ *   the segment packed alone (ties to the lower row); idx is a POOL index, ready for alive_knn_merge_gather(_rows) on rows_f32.
+ *   Every launch is sized from N, T and k: the segment table may change between replays of a captured hipGraph.  Rows that
+ *   search the same segment share one pass over it.  N <= 1024.
+ *   ws: alive_knn_grouped_workspace_bytes(N, T, k) bytes (0: arguments out of range). */
+int alive_library_pack_rows(const float* tokens, int64_t M, int Dd, float* rows_f32, float* norms, void* stream);
+size_t alive_knn_grouped_workspace_bytes(int N, int T, int k);
+int alive_knn_search_grouped(const float* src, int N, int T, const float* rows_f32, const float* norms, int64_t P,
+                             const int32_t* seg_lo, const int32_t* seg_len, int k, float* out_val, int32_t* out_idx,
+                             void* ws, void* stream);
+/* alive_knn_merge_gather with one shard and a per-window alpha: alpha[N] is a DEVICE double array (the scalar form's type;
+ * 1 - alpha is formed the same way), bitwise the scalar form with n_shards = 1 row by row.  A frame whose list starts with
+ * idx -1 (an inactive row of the grouped search) is passed through: out = src.  k <= 8. */
+int alive_knn_merge_gather_rows(const float* cand_val, const int32_t* cand_idx, int k, const double* alpha,
+                                const float* rows_f32_full, const float* src, int N, int T, float* out,
+                                int32_t* final_idx, void* stream);
+
 /* alive_dedup_pass: one pass of the greedy de-duplication of a library (generate_voice_library.py of this build, --dedup):
  * frame i is dropped iff a KEPT earlier frame among its k nearest (val / idx[M][k] = alive_knn_search of the library
  * against itself) has cosine > threshold.  state[M]: 0 undecided, 1 kept, 2 dropped (zero it before the first pass);
@@ -484,6 +507,11 @@ int64_t alive_resample_length(int64_t L, int orig, int new_rate);
 int alive_resample_filter(int orig, int new_rate, float* filt, void* stream);
 int alive_resample(const float* x, int B, int L, int orig, int new_rate, const float* filt, float pre_scale,
                    float post_scale, float* y, int Lout, void* stream);
+/* alive_resample with per-row factors: pre_scale / post_scale are DEVICE float[B] (row b: bitwise alive_resample with
+ * pre_scale[b], post_scale[b]).  orig == new: the gains alone, y = (x * pre) * post (torchaudio.functional.gain twice), Lout == L,
+ * filt not read. */
+int alive_resample_rows(const float* x, int B, int L, int orig, int new_rate, const float* filt, const float* pre_scale,
+                        const float* post_scale, float* y, int Lout, void* stream);
 int alive_pcm16_to_float(const int16_t* in, int64_t n, float* out, void* stream);
 int alive_float_to_pcm16(const float* in, int64_t n, int16_t* out, void* stream);
 
@@ -560,6 +588,10 @@ int alive_decoder_forward(const float* const* w, const float* x, const float* f0
  * and realtime_inference.py:156-163 (mode 1); in place on f0[N][T]. */
 int alive_pitch_transform(float* f0, int N, int T, int mode, float f0_rate, float pitch_shift,
                           float intonation, void* stream);
+/* the same with per-row parameters: f0_rate / pitch_shift / intonation are DEVICE float[N]; row n is bitwise
+ * alive_pitch_transform with that row's values */
+int alive_pitch_transform_rows(float* f0, int N, int T, int mode, const float* f0_rate, const float* pitch_shift,
+                               const float* intonation, void* stream);
 
 #ifdef __cplusplus
 }
