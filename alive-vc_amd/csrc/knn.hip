@@ -3357,7 +3357,7 @@ extern "C" int alive_library_pack_rows(const float* tokens, int64_t M, int Dd, f
 }
 
 extern "C" size_t alive_knn_grouped_workspace_bytes(int N, int T, int k) {
-    if (N < 1 || N > GR_MAX_ROWS || T < 1 || k < 1 || k > KH) return 0;
+    if (N < 1 || N > GR_MAX_ROWS || T < 1 || (int64_t)N * T > (int64_t)1 << 20 || k < 1 || k > KH) return 0;   // as the search
     return grouped_ws_layout(nullptr, N, T, k).bytes;
 }
 

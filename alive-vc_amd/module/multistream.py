@@ -93,11 +93,11 @@ def knn_search_grouped(source, rows, norms, seg_lo, seg_len, k):
     L = nat.lib()
     if not 1 <= k <= MAX_K:
         raise ValueError(f"grouped search: k={k} outside [1, {MAX_K}]")
+    nbytes = L.alive_knn_grouped_workspace_bytes(n, t, k)
+    if nbytes == 0:                                         # (before anything is allocated)
+        raise ValueError(f"grouped search: {n} rows x {t} frames (k={k}) out of range")
     val = torch.empty(n * t, k, dtype=torch.float32, device=source.device)
     idx = torch.empty(n * t, k, dtype=torch.int32, device=source.device)
-    nbytes = L.alive_knn_grouped_workspace_bytes(n, t, k)
-    if nbytes == 0:
-        raise ValueError(f"grouped search: {n} rows x {t} frames (k={k}) out of range")
     ws = _ws.get(nbytes, source.device)
     nat.check(L.alive_knn_search_grouped(nat.ptr(source), n, t, nat.ptr(rows), nat.ptr(norms), rows.shape[0], nat.ptr(seg_lo),
                                          nat.ptr(seg_len), k, nat.ptr(val), nat.ptr(idx), nat.ptr(ws), nat.stream()),

@@ -212,7 +212,7 @@ int alive_knn_merge_gather(const float* cand_val, const int32_t* cand_idx, int n
  *   out_val / out_idx [N*T][k]: val and idx - seg_lo[n] are bitwise what alive_knn_search_strict returns for the frame against
  *   the segment packed alone (ties to the lower row); idx is a POOL index, ready for alive_knn_merge_gather(_rows) on rows_f32.
  *   Every launch is sized from N, T and k: the segment table may change between replays of a captured hipGraph.  Rows that
- *   search the same segment share one pass over it.  N <= 1024.
+ *   search the same segment share one pass over it.  N <= 1024, N * T <= 2^20.
  *   ws: alive_knn_grouped_workspace_bytes(N, T, k) bytes (0: arguments out of range). */
 int alive_library_pack_rows(const float* tokens, int64_t M, int Dd, float* rows_f32, float* norms, void* stream);
 size_t alive_knn_grouped_workspace_bytes(int N, int T, int k);

@@ -26,6 +26,30 @@ def test_grouped_search_abi_refuses_bad_arguments():
     assert rc == -1
 
 
+def test_grouped_workspace_size_refuses_more_frames_than_the_search_takes():
+    """N * T <= 2^20 is the search's limit: one frame more and the size is 0 ("out of range"), not a huge positive size"""
+    L = nat.lib()
+    for k in (1, 4, 8):
+        assert L.alive_knn_grouped_workspace_bytes(1024, 1024, k) > 1024 * 1024 * 768 * 6
+        assert L.alive_knn_grouped_workspace_bytes(1024, 1025, k) == 0
+        assert L.alive_knn_grouped_workspace_bytes(1, 1 << 20, k) > 0
+        assert L.alive_knn_grouped_workspace_bytes(1, (1 << 20) + 1, k) == 0
+        assert L.alive_knn_grouped_workspace_bytes(1024, 4096, k) == 0
+    assert L.alive_knn_grouped_workspace_bytes(1024, 1025, 4) == 0
+
+
+def test_grouped_search_refuses_too_many_frames_before_allocating(monkeypatch):
+    import torch
+    src = torch.empty(1024, 768, 1025, device="meta")                      # (no storage)
+
+    def boom(*a, **kw):
+        raise AssertionError("allocated for a shape the search refuses")
+    monkeypatch.setattr(MS._ws, "get", boom)
+    monkeypatch.setattr(MS.torch, "empty", boom)
+    with pytest.raises(ValueError, match="1024 rows x 1025 frames"):
+        MS.knn_search_grouped(src, None, None, None, None, 4)
+
+
 def test_per_row_edge_abi_refuses_bad_arguments():
     L = nat.lib()
     assert L.alive_library_pack_rows(None, 10, 768, 1, 1, None) == -1 and b"null" in L.alive_last_error()
