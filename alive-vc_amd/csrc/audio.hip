@@ -82,6 +82,62 @@ __global__ __launch_bounds__(256) void gain_rows_kernel(const float* __restrict_
     y[(size_t)b * L + o] = v * post_r[b];
 }
 
+// MULTI (alive_resample_rows_multi): row b at its own rate pair table[pair[b]] = {orig, new, width, offset into filt}, its own
+// lengths len_in[b] / len_out[b] inside rows of ld_in / ld_out floats, and y zero from len_out[b] to ld_out.  The arithmetic of a
+// row is resample_kernel<true>'s (gain_rows_kernel's at orig == new) in the same tap order; the pair is uniform per block
+// (blockIdx.y is the row), so is the choice of LDS or global staging, and staging moves no result.  Device data out of range
+// (a pair index outside the table, an entry whose bank is not inside filt[filt_len], lengths past the row strides) writes a zero
+// row or is clamped: never an access outside x, filt, y.
+__global__ __launch_bounds__(256) void resample_rows_multi_kernel(const float* __restrict__ x, int ld_in, const int* __restrict__ len_in,
+                                                                  const int* __restrict__ pair, const int4* __restrict__ table,
+                                                                  int n_pairs, const float* __restrict__ filt, int64_t filt_len,
+                                                                  int lds_bytes,
+                                                                  const float* __restrict__ pre_r, const float* __restrict__ post_r,
+                                                                  float* __restrict__ y, int ld_out, const int* __restrict__ len_out) {
+    extern __shared__ float fs_lds[];
+    const int b = blockIdx.y;
+    const int pi = pair[b];
+    int4 e = (pi >= 0 && pi < n_pairs) ? table[pi] : make_int4(0, 0, 0, 0);
+    const bool resamples = e.x != e.y;
+    const int64_t bank = (int64_t)e.y * (2 * (int64_t)e.z + e.x);        // floats
+    const bool valid = e.x > 0 && e.y > 0 && (!resamples || (e.z >= 0 && e.w >= 0 && (int64_t)e.w + bank <= filt_len));
+    if (!valid) e = make_int4(1, 1, 0, 0);
+    const int orig = e.x, new_ = e.y, width = e.z;
+    const int taps = 2 * width + orig;
+    const float* fs = filt + e.w;
+    if (valid && resamples && bank * (int64_t)sizeof(float) <= lds_bytes) {          // uniform per block
+        for (int i = threadIdx.x; i < new_ * taps; i += blockDim.x) fs_lds[i] = fs[i];
+        __syncthreads();
+        fs = fs_lds;
+    }
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= ld_out) return;
+    float* yb = y + (size_t)b * ld_out;
+    const int L = min(max(len_in[b], 0), ld_in);
+    const int Lout = valid ? min(len_out[b], ld_out) : 0;
+    if (o >= Lout) {
+        yb[o] = 0.0f;
+        return;
+    }
+    const float pre = pre_r[b], post = post_r[b];
+    const float* xb = x + (size_t)b * ld_in;
+    if (!resamples) {
+        const float v = (o < L) ? xb[o] * pre : 0.0f;
+        yb[o] = v * post;
+        return;
+    }
+    const int m = o / new_, p = o - m * new_;
+    const float* f = fs + p * taps;
+    const int s0 = m * orig - width;
+    float acc = 0.0f;
+    for (int j = 0; j < taps; ++j) {
+        const int s = s0 + j;
+        const float v = (s >= 0 && s < L) ? xb[s] * pre : 0.0f;
+        acc = fmaf(f[j], v, acc);
+    }
+    yb[o] = acc * post;
+}
+
 __global__ void pcm16_to_float_kernel(const short* __restrict__ in, int64_t n, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (float)in[i] / 32768.0f;
@@ -145,6 +201,24 @@ extern "C" int alive_resample_rows(const float* x, int B, int L, int orig, int n
     resample_kernel<true><<<dim3(cdiv(Lout, 256), B), 256, use_lds ? bank : 0, (hipStream_t)stream>>>(
         x, L, orig, new_, width, filt, 1.0f, 1.0f, y, Lout, use_lds, pre_scale, post_scale);
     ALIVE_CHECK_LAUNCH("alive_resample_rows");
+    return ALIVE_OK;
+}
+
+extern "C" int alive_resample_rows_multi(const float* x, int B, int ld_in, const int* len_in, const int* pair, const int* table,
+                                         int n_pairs, const float* filt, int64_t filt_len, int lds_bytes, const float* pre_scale,
+                                         const float* post_scale, float* y, int ld_out, const int* len_out, void* stream) {
+    ALIVE_CHECK_ARG(x && len_in && pair && table && pre_scale && post_scale && y && len_out,
+                    "alive_resample_rows_multi: null pointer");
+    ALIVE_CHECK_ARG(B >= 1 && B <= 1024, "alive_resample_rows_multi: B=%d outside [1, 1024]", B);
+    ALIVE_CHECK_ARG(n_pairs >= 1, "alive_resample_rows_multi: empty pair table (n_pairs=%d)", n_pairs);
+    ALIVE_CHECK_ARG(ld_in > 0 && ld_out > 0, "alive_resample_rows_multi: ld_in=%d, ld_out=%d must be > 0", ld_in, ld_out);
+    ALIVE_CHECK_ARG(filt_len >= 0 && (filt || filt_len == 0), "alive_resample_rows_multi: null filter buffer of %lld floats",
+                    (long long)filt_len);
+    ALIVE_CHECK_ARG(lds_bytes >= 0 && lds_bytes <= 16 * 1024, "alive_resample_rows_multi: lds_bytes=%d outside [0, 16384]", lds_bytes);
+    resample_rows_multi_kernel<<<dim3(cdiv(ld_out, 256), B), 256, lds_bytes, (hipStream_t)stream>>>(
+        x, ld_in, len_in, pair, reinterpret_cast<const int4*>(table), n_pairs, filt, filt_len, lds_bytes, pre_scale, post_scale, y,
+        ld_out, len_out);
+    ALIVE_CHECK_LAUNCH("alive_resample_rows_multi");
     return ALIVE_OK;
 }
 

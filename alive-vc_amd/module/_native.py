@@ -117,6 +117,7 @@ PROTOTYPES = {
     "alive_resample_filter": (_I, [_I, _I, _VP, _VP]),
     "alive_resample": (_I, [_VP, _I, _I, _I, _I, _VP, _F, _F, _VP, _I, _VP]),
     "alive_resample_rows": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _VP]),
+    "alive_resample_rows_multi": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _VP, _I64, _I, _VP, _VP, _VP, _I, _VP, _VP]),
     "alive_pcm16_to_float": (_I, [_VP, _I64, _VP, _VP]),
     "alive_float_to_pcm16": (_I, [_VP, _I64, _VP, _VP]),
     "alive_weight_count": (_I, [_I]),

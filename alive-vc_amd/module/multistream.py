@@ -1,7 +1,10 @@
 """Multi-session streaming: B live voices converted in one batched step per tick (realtime_inference.py:130-183 per slot).
 
-A `MultiStreamConverter` holds B session slots that share the chunk, the ring (buffersize), the sample rates and k.  Each slot has
-its own target voice (a segment of a `VoicePool`), pitch shift, f0 rate, alpha, input / output gain, ring and oscillator phase.
+A `MultiStreamConverter` holds B session slots that share the chunk duration, the ring (buffersize) and k.  Each slot has its own
+target voice (a segment of a `VoicePool`), pitch shift, f0 rate, alpha, input / output gain, ring and oscillator phase, and -- with
+`rates=` declared up front and input_sr == output_sr -- its own sample rate: a session at rate r sends and receives
+chunk * r / input_sr samples per tick, and its ring at 16 kHz has the converter's geometry (session_geometry), so only the two
+resampling edges differ per row (alive_resample_rows_multi: one launch, every row at its own rate pair).
 One tick runs the whole device pipeline once over [B, ring]: the networks see a batch of B rings, the kNN match is the grouped
 exact search (csrc/knn.hip: alive_knn_search_grouped -- row n searches its own pool segment), and the per-user edges read
 per-row device arrays (alive_pitch_transform_rows, alive_knn_merge_gather_rows, alive_resample_rows).  Every per-session
@@ -146,6 +149,87 @@ def resample_rows(x, orig_freq, new_freq, pre_scale, post_scale):
     return y
 
 
+class RateTable:
+    """rate pairs (orig_freq, new_freq) -> the device pair table of alive_resample_rows_multi: int32 [n][4] entries
+    {orig, new, width, offset} (the rates divided by their gcd) and one concatenated filter buffer holding every pair's bank at its
+    offset, each filled by alive_resample_filter (bitwise the bank audio_io.resample and resample_rows use).  lds_bytes is the
+    largest bank of at most 16 KB: the rows at those pairs stage their bank in LDS."""
+
+    def __init__(self, pairs, device="cuda"):
+        L_ = nat.lib()
+        self.device = torch.device(device)
+        self.index, entries, off, lds = {}, [], 0, 0
+        for o, n in pairs:
+            key = audio_io._reduced(o, n)
+            if key in self.index:
+                continue
+            orig, new = key
+            if orig == new:
+                entries.append((1, 1, 0, 0))
+            else:
+                taps = int(L_.alive_resample_taps(orig, new))
+                entries.append((orig, new, (taps - orig) // 2, off))
+                bank = new * taps
+                if bank * 4 <= 16 * 1024:
+                    lds = max(lds, bank * 4)
+                off += bank
+            self.index[key] = len(entries) - 1
+        if not entries:
+            raise ValueError("RateTable: no rate pairs")
+        self.entries = entries
+        self.filt = torch.empty(max(off, 1), dtype=torch.float32, device=self.device)
+        for orig, new, _, o in entries:
+            if orig != new:
+                nat.check(L_.alive_resample_filter(orig, new, self.filt[o].data_ptr(), nat.stream()), "alive_resample_filter")
+        self.filt_len = off
+        self.lds_bytes = lds
+        self.table = torch.tensor(entries, dtype=torch.int32, device=self.device).contiguous()
+        torch.cuda.current_stream(self.device).synchronize()
+
+    def pair(self, orig_freq, new_freq):
+        """the table index of a rate pair"""
+        return self.index[audio_io._reduced(orig_freq, new_freq)]
+
+
+def resample_rows_multi(x, lens_in, pairs, table, lens_out, ld_out, pre, post):
+    """x [B, ld_in], row b resampled at its own pair -> y [B, ld_out]: row b is resample_rows of x[b, :lens_in[b]] at the RateTable
+    pair pairs[b], cut to lens_out[b] samples, and zero after them.  lens_in, pairs, lens_out: device int32 [B]; pre / post: device
+    float32 [B] linear gains.  The caller keeps lens_in[b] <= ld_in and lens_out[b] <= min(ld_out, the pair's resampled length)."""
+    x = x.contiguous()
+    b, ld_in = x.shape
+    y = torch.empty(b, int(ld_out), device=x.device)
+    nat.check(nat.lib().alive_resample_rows_multi(nat.ptr(x), b, ld_in, nat.ptr(lens_in), nat.ptr(pairs), nat.ptr(table.table),
+                                                  len(table.entries), nat.ptr(table.filt), table.filt_len, table.lds_bytes,
+                                                  nat.ptr(pre), nat.ptr(post), nat.ptr(y), int(ld_out), nat.ptr(lens_out), nat.stream()),
+              "alive_resample_rows_multi")
+    return y
+
+
+def _geometry(chunk, buffersize, sr):
+    """realtime_inference.py:122-126 at one rate: (ring length at 16 kHz, frames, internal chunk)"""
+    n = chunk * buffersize
+    return -(-16000 * n // sr), (n * 16000 // sr) // 320, int(chunk * (16000 / sr))
+
+
+def session_geometry(chunk, buffersize, sr, rate):
+    """a session at `rate` in a converter of `chunk` samples at `sr`: its chunk, chunk * rate / sr samples.  ValueError unless
+    that is a whole number of samples and the session's 16 kHz geometry -- the resampled ring length ceil(16000 * ring / rate),
+    the frame count and int(chunk_r * (16000 / rate)) -- is the converter's, each checked on its own."""
+    chunk, buffersize, sr, rate = int(chunk), int(buffersize), int(sr), int(rate)
+    if rate <= 0:
+        raise ValueError(f"sample rate {rate} must be > 0")
+    if (chunk * rate) % sr:
+        raise ValueError(f"a session at {rate} Hz would take chunks of {chunk} * {rate} / {sr} = {chunk * rate / sr:g} samples: "
+                         "not a whole number")
+    c = chunk * rate // sr
+    mine, want = _geometry(c, buffersize, rate), _geometry(chunk, buffersize, sr)
+    for what, a, w in zip(("16 kHz ring length", "frame count", "internal chunk"), mine, want):
+        if a != w:
+            raise ValueError(f"a session at {rate} Hz ({c}-sample chunks) has a {what} of {a}, the converter's is {w}: its "
+                             "geometry must be the converter's")
+    return c
+
+
 def db_scale(db):
     """torchaudio.functional.gain's factor as audio_io.resample forms it (1.0 exactly at 0 dB)"""
     return float(10 ** (db / 20)) if db != 0 else 1.0
@@ -156,11 +240,18 @@ _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain")
 
 class MultiStreamConverter:
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
-                 output_sr=16000, k=4, device="cuda"):
+                 output_sr=16000, k=4, device="cuda", rates=None):
         if not 1 <= int(k) <= MAX_K:
             raise ValueError(f"MultiStreamConverter: k={k} outside [1, {MAX_K}] (the grouped search keeps k <= 8)")
         if int(slots) < 1 or int(slots) > 1024:
             raise ValueError(f"MultiStreamConverter: slots={slots} outside [1, 1024]")
+        rates = sorted({int(r) for r in (rates or ())} | {int(input_sr)})
+        if len(rates) > 1:
+            if input_sr != output_sr:
+                raise ValueError(f"MultiStreamConverter: per-session rates {rates} need input_sr == output_sr (got {input_sr} and "
+                                 f"{output_sr}): a session's chunk could not then last as long as the converter's on both sides, so "
+                                 "its internal chunk and its frame count could not both be the converter's")
+            chunks = {r: session_geometry(chunk, buffersize, input_sr, r) for r in rates}
         self.device = torch.device(device)
         self.ce, self.pe, self.dec = content_encoder.to(device), f0_estimator.to(device), decoder.to(device)
         for net in (self.ce, self.pe, self.dec):
@@ -179,11 +270,35 @@ class MultiStreamConverter:
             raise ValueError(f"ring of {buffersize} x {chunk} samples is {self.frames} frames; the decoder needs >= 5")
         B, dev = self.B, self.device
         self.n = self.chunk * self.buffersize
+        self.rates = tuple(rates)
         # per-slot state: host side
         self.is_open = [False] * B
         self.params = [None] * B
         self.count = [0] * B
-        self.ring = np.zeros((B, self.n), dtype=np.int16)
+        self.rate = [int(input_sr)] * B
+        self.slot_chunk = [self.chunk] * B
+        self._rt = None
+        ld_in = self.n
+        if len(rates) > 1:
+            # the multi-rate edges (alive_resample_rows_multi): every rate's pair into and out of 16 kHz in one table, rings padded
+            # to the longest session ring; row b's lengths and pairs are device arrays written by open / close
+            self._chunks = chunks
+            self._rt = RateTable([(r, 16000) for r in rates] + [(16000, r) for r in rates], dev)
+            self._len16 = _geometry(self.chunk, self.buffersize, input_sr)[0]          # the ring at 16 kHz, every session's
+            self._lw = 320 * (self._len16 // 320)                                     # the decoder's wave: 320 per frame
+            L_ = nat.lib()
+            self._lout = {r: int(L_.alive_resample_length(self._lw, *audio_io._reduced(16000, r))) for r in rates}
+            ld_in = max(c * self.buffersize for c in chunks.values())
+            self._ld_out = max(self._lout.values())
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.len_in = torch.full((B,), self.n, **i32)
+            self.pair_in = torch.full((B,), self._rt.pair(input_sr, 16000), **i32)
+            self.pair_out = torch.full((B,), self._rt.pair(16000, input_sr), **i32)
+            self.len_out = torch.full((B,), self._lout[int(input_sr)], **i32)
+            self._len16_rows = torch.full((B,), self._len16, **i32)
+            self._lw_rows = torch.full((B,), self._lw, **i32)
+        self.ld_in = ld_in
+        self.ring = np.zeros((B, ld_in), dtype=np.int16)
         # per-slot state: device arrays the (captured) step reads
         self.seg_lo = torch.zeros(B, dtype=torch.int32, device=dev)
         self.seg_len = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -197,7 +312,7 @@ class MultiStreamConverter:
         self.out_post = torch.ones(B, dtype=torch.float32, device=dev)
         self.emit = torch.zeros(B, 1, dtype=torch.bool, device=dev)          # the slots whose phase advances this tick
         self.phi = torch.zeros(B, 64, device=dev)
-        self._in = torch.zeros(B, self.n, device=dev)
+        self._in = torch.zeros(B, ld_in, device=dev)
         self._graph = None
         self._graph_pool_version = None
         self.captures = 0
@@ -225,11 +340,28 @@ class MultiStreamConverter:
         self.in_post[slot] = db_scale(p["input_gain"])
         self.out_pre[slot] = db_scale(p["gain"])
 
-    def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0):
-        """start a session in `slot`: empty ring, phase 0"""
+    def _set_rate(self, slot, rate):
+        self.rate[slot] = rate
+        if self._rt is None:
+            return
+        c = self._chunks[rate]
+        self.slot_chunk[slot] = c
+        self.len_in[slot] = c * self.buffersize
+        self.pair_in[slot] = self._rt.pair(rate, 16000)
+        self.pair_out[slot] = self._rt.pair(16000, rate)
+        self.len_out[slot] = self._lout[rate]
+
+    def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None):
+        """start a session in `slot`: empty ring, phase 0.  `rate` (default: the converter's input_sr) is one of the declared
+        `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life"""
         slot = self._slot(slot)
+        rate = int(self.input_sr if rate is None else rate)
+        if rate not in self.rates:
+            raise ValueError(f"slot {slot}: rate {rate} Hz was not declared (rates={list(self.rates)}): pass it in "
+                             "MultiStreamConverter(..., rates=...)")
         p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain)
         self._apply(slot, p)                                  # (validates the voice before anything changes)
+        self._set_rate(slot, rate)
         self.params[slot] = p
         self.is_open[slot] = True
         self.count[slot] = 0
@@ -242,6 +374,8 @@ class MultiStreamConverter:
         slot = self._slot(slot)
         if not self.is_open[slot]:
             raise ValueError(f"slot {slot} is not open")
+        if "rate" in params:
+            raise ValueError(f"slot {slot}: a session's rate is fixed for its life: close the slot and open it at the new rate")
         unknown = set(params) - set(_PARAMS)
         if unknown:
             raise ValueError(f"unknown session settings {sorted(unknown)} (known: {_PARAMS})")
@@ -258,6 +392,7 @@ class MultiStreamConverter:
         self.ring[slot] = 0
         self.seg_len[slot] = 0
         self.phi[slot] = 0.0
+        self._set_rate(slot, int(self.input_sr))             # a closed slot: the converter's own rate, silence
         return self
 
     # ------------------------------------------------------------------ device step
@@ -279,7 +414,11 @@ class MultiStreamConverter:
 
     def _device_step(self, data, phi):
         """data float32 [B, ring] on the device, phi [B, 64] -> (wave [B, L] at output_sr, phi_next [B, 64])"""
-        data = resample_rows(data, self.input_sr, 16000, self.in_pre, self.in_post)
+        if self._rt is None:
+            data = resample_rows(data, self.input_sr, 16000, self.in_pre, self.in_post)
+        else:
+            data = resample_rows_multi(data, self.len_in, self.pair_in, self._rt, self._len16_rows, self._len16, self.in_pre,
+                                       self.in_post)
         spec = spectrogram(data)
         f0, join = self._f0_on_side_stream(spec)
         content = self.ce(spec)
@@ -288,7 +427,13 @@ class MultiStreamConverter:
         join()
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0
-        wave = resample_rows(wave, 16000, self.output_sr, self.out_pre, self.out_post)
+        if self._rt is None:
+            wave = resample_rows(wave, 16000, self.output_sr, self.out_pre, self.out_post)
+        else:
+            if wave.shape[1] != self._lw:
+                raise RuntimeError(f"decoder wave of {wave.shape[1]} samples, the multi-rate edge expects {self._lw}")
+            wave = resample_rows_multi(wave, self._lw_rows, self.pair_out, self._rt, self.len_out, self._ld_out, self.out_pre,
+                                       self.out_post)
         phi_next = torch.where(self.emit, phi_out[:, :, self.end_of_output], torch.zeros_like(phi))
         return wave, phi_next
 
@@ -340,7 +485,10 @@ class MultiStreamConverter:
         return audio_io.float_to_pcm16(self._run()).cpu().numpy()
 
     def step(self, chunks):
-        """{slot: int16 chunk} for EVERY open slot -> {slot: converted centre chunk (int16) or None while its ring fills}"""
+        """{slot: int16 chunk} for EVERY open slot -> {slot: converted centre chunk (int16) or None while its ring fills}.
+        A session at rate r sends and receives chunks of chunk_r = chunk * r / input_sr samples; its output is cut at its own
+        centre, buffersize * chunk_r // 2 +- chunk_r // 2 (realtime_inference.py at that rate), so an odd chunk_r (441 at 44.1 kHz
+        with 160-sample chunks at 16 kHz) returns chunk_r - 1 samples per tick, as the reference does."""
         for s in chunks:
             self._slot(s)
             if not self.is_open[s]:
@@ -351,10 +499,12 @@ class MultiStreamConverter:
         emit = [False] * self.B
         for s, c in chunks.items():
             c = np.asarray(c, dtype=np.int16).reshape(-1)
-            if c.shape[0] != self.chunk:
-                raise ValueError(f"slot {s}: chunk of {c.shape[0]} samples, expected {self.chunk}")
-            self.ring[s, :-self.chunk] = self.ring[s, self.chunk:]
-            self.ring[s, -self.chunk:] = c
+            cs = self.slot_chunk[s]
+            if c.shape[0] != cs:
+                raise ValueError(f"slot {s}: chunk of {c.shape[0]} samples, expected {cs} (the session runs at {self.rate[s]} Hz)")
+            n = cs * self.buffersize
+            self.ring[s, :n - cs] = self.ring[s, cs:n]
+            self.ring[s, n - cs:n] = c
             self.count[s] += 1
             emit[s] = self.count[s] > self.buffersize
         out = {s: None for s in chunks}
@@ -369,8 +519,9 @@ class MultiStreamConverter:
         o = audio_io.float_to_pcm16(self._run()).cpu().numpy()
         if guarded and ops.f16_saturations(reset=True) > 0:
             o = self._repeat_on_bf16(saved_phi)
-        center = self.buffersize * self.chunk // 2
         for s in chunks:
             if emit[s]:
-                out[s] = o[s, center - self.chunk // 2: center + self.chunk // 2].copy()
+                cs = self.slot_chunk[s]
+                center = self.buffersize * cs // 2
+                out[s] = o[s, center - cs // 2: center + cs // 2].copy()
         return out

@@ -6,8 +6,12 @@ The sessions file is a JSON list; each entry:
    "target": "spk.wav" and / or "lib": "voice_library.pt",   its voice (as -t / -lib of realtime_inference.py)
    "pitch": 0, "f0_rate": 1, "alpha": 0, "gain": 0, "input_gain": 0,     optional, realtime_inference.py's meanings
    "start": 0,                            optional: the tick at which the session joins
+   "sr": 48000,                           optional: the session's sample rate (default -isr / -osr)
    "output": "a_out.wav"}                 optional: default <outdir>/<index>_<input name>.wav
 A session's slot opens at its start tick, gets one chunk per tick while its input lasts and closes after its last chunk.
+A session with "sr" has its input resampled to sr on load, is driven at sr in chunks of chunk * sr / isr samples (a whole number,
+with the converter's 16 kHz geometry: module/multistream.py session_geometry), and its output wav is written at sr.  "sr" needs
+-isr == -osr.
 Flags shared with realtime_inference.py keep its spelling: -c, -b, -k, -isr, -osr, --no-graph.
 """
 import argparse
@@ -28,7 +32,7 @@ from module.multistream import MultiStreamConverter, VoicePool   # noqa: E402
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
-SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "start", "output")
+SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "start", "sr", "output")
 
 
 def build_parser():
@@ -69,9 +73,12 @@ def load_sessions(path):
         rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
-                 gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)))
+                 gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
+                 sr=None if s.get("sr") is None else int(s["sr"]))
         if e["start"] < 0:
             raise ValueError(f"session {i}: start tick {e['start']} < 0")
+        if e["sr"] is not None and e["sr"] <= 0:
+            raise ValueError(f"session {i}: sample rate {e['sr']} <= 0")
         out.append(e)
     return out
 
@@ -99,9 +106,10 @@ def input_pcm(path, input_sr, device):
 
 def run(conv, pcms, starts, chunk, params):
     """drive `conv` tick by tick: session i occupies slot i (opened with params[i]) from tick starts[i] for len(pcms[i]) // chunk
-    ticks.
+    ticks; `chunk` is one length for every session or a list of per-session lengths (sessions at their own rates).
     Returns the emitted int16 chunks of every session, concatenated."""
-    n_chunks = [len(p) // chunk for p in pcms]
+    chunks = list(chunk) if isinstance(chunk, (list, tuple)) else [chunk] * len(pcms)
+    n_chunks = [len(p) // c for p, c in zip(pcms, chunks)]
     outs = [[] for _ in pcms]
     last = max(s + n for s, n in zip(starts, n_chunks))
     for tick in range(last):
@@ -110,8 +118,8 @@ def run(conv, pcms, starts, chunk, params):
             if tick == s and n > 0:
                 conv.open(i, **params[i])
             if s <= tick < s + n:
-                j = tick - s
-                feed[i] = pcms[i][j * chunk:(j + 1) * chunk]
+                j, c = tick - s, chunks[i]
+                feed[i] = pcms[i][j * c:(j + 1) * c]
         res = conv.step(feed)
         for i, o in res.items():
             if o is not None:
@@ -125,6 +133,8 @@ def run(conv, pcms, starts, chunk, params):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     sessions = load_sessions(args.sessions)
+    if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
+        raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
         raise SystemExit("Error: this build needs a ROCm device: pass -d cuda on an MI355X host.")
     device = torch.device('cuda')
@@ -140,18 +150,21 @@ def main(argv=None):
             pool.add(name, voice_tokens(CE, s["target"], s["lib"], device))
         names.append(name)
     slots = max(args.slots, len(sessions))
+    in_sr = [s["sr"] or args.input_sr for s in sessions]
+    out_sr = [s["sr"] or args.output_sr for s in sessions]
     conv = MultiStreamConverter(CE, PE, Dec, pool, slots, chunk=args.chunk, buffersize=args.buffersize, input_sr=args.input_sr,
-                                output_sr=args.output_sr, k=args.k, device=device)
+                                output_sr=args.output_sr, k=args.k, device=device, rates=sorted(set(in_sr)))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
-                   input_gain=s["input_gain"]) for n, s in zip(names, sessions)]
+                   input_gain=s["input_gain"], rate=r) for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()
-    pcms = [input_pcm(s["input"], args.input_sr, device) for s in sessions]
-    outs = run(conv, pcms, [s["start"] for s in sessions], args.chunk, params)
+    pcms = [input_pcm(s["input"], r, device) for s, r in zip(sessions, in_sr)]
+    chunks = [args.chunk * r // args.input_sr for r in in_sr]
+    outs = run(conv, pcms, [s["start"] for s in sessions], chunks, params)
     os.makedirs(args.output_dir, exist_ok=True)
-    for i, (s, o) in enumerate(zip(sessions, outs)):
+    for i, (s, o, r) in enumerate(zip(sessions, outs, out_sr)):
         path = s["output"] or os.path.join(args.output_dir, f"{i}_{os.path.splitext(os.path.basename(s['input']))[0]}.wav")
-        audio_io.save(path, torch.from_numpy(o.astype(np.float32) / 32768)[None], args.output_sr, "pcm16")
+        audio_io.save(path, torch.from_numpy(o.astype(np.float32) / 32768)[None], r, "pcm16")
         print(f"session {i}: {len(o)} samples -> {path}")
     return outs
 

@@ -512,6 +512,25 @@ int alive_resample(const float* x, int B, int L, int orig, int new_rate, const f
  * filt not read. */
 int alive_resample_rows(const float* x, int B, int L, int orig, int new_rate, const float* filt, const float* pre_scale,
                         const float* post_scale, float* y, int Lout, void* stream);
+/* alive_resample_rows with a rate pair per row, for a batch of sessions at different rates in one launch (one captured graph).
+ *   x[B][ld_in]: row b holds len_in[b] valid samples.  y[B][ld_out]: row b receives len_out[b] samples; the rest of the row up to
+ *   ld_out is written 0.0f.
+ *   table: DEVICE int32[n_pairs][4], 16-byte aligned, entry {orig, new, width, offset} -- the rates divided by their gcd,
+ *   width = (alive_resample_taps(orig, new) - orig) / 2, and the offset (in floats) of the pair's bank, filled by
+ *   alive_resample_filter(orig, new, filt + offset), in the concatenated buffer filt[filt_len].  An equal-rate entry is {1, 1, 0, 0}
+ *   and reads no bank (filt may be NULL when every entry is equal-rate and filt_len is 0).
+ *   pair, len_in, len_out: DEVICE int32[B]; pre_scale / post_scale: DEVICE float[B].
+ *   Row b is bitwise alive_resample_rows of that row alone at table[pair[b]] with pre_scale[b], post_scale[b] and Lout = len_out[b]
+ *   (at orig == new: the gains alone, (x * pre) * post).  A resampling row whose bank is at most lds_bytes stages it in LDS; pass
+ *   the largest bank of at most 16 KB in the table (any value in [0, 16384] is safe and gives the same result).
+ *   The grid depends on B and ld_out only: one captured launch serves any mix of pairs and lengths written between replays.
+ *   The per-row arrays are device data the host does not read: the caller guarantees len_in[b] <= ld_in and
+ *   len_out[b] <= min(ld_out, alive_resample_length(len_in[b], orig, new)).  Out-of-range device data never leads to an access
+ *   outside x, filt or y: lengths are clamped to the strides, and a row whose pair index or table entry is invalid is written 0.
+ *   B in [1, 1024], n_pairs >= 1, ld_in, ld_out > 0. */
+int alive_resample_rows_multi(const float* x, int B, int ld_in, const int* len_in, const int* pair, const int* table, int n_pairs,
+                              const float* filt, int64_t filt_len, int lds_bytes, const float* pre_scale, const float* post_scale,
+                              float* y, int ld_out, const int* len_out, void* stream);
 int alive_pcm16_to_float(const int16_t* in, int64_t n, float* out, void* stream);
 int alive_float_to_pcm16(const float* in, int64_t n, int16_t* out, void* stream);
 

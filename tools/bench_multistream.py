@@ -3,10 +3,13 @@
 the chunk period); and the grouped search alone: bytes of the segments it reads per tick over its kernel time.
 
 Timing: every tick is bracketed by torch.cuda.synchronize() (the tick itself ends in a device -> host copy), after warm-up
-ticks; the search is timed with events around repeated calls.  Profile in a separate run (rocprofv3 --kernel-trace --stats --
+ticks; the search is timed with events around repeated calls.  --rates spreads the sessions over a list of sample rates
+(session s at rates[s % len]; MultiStreamConverter(rates=...), the per-row multi-rate edges) and adds that batch's tick p50 / p99
+(mixed_<mode>_tick_p50_ms / _p99_ms) next to the single-rate figures of the same B.  Profile in a separate run (rocprofv3 --kernel-trace --stats --
 python tools/bench_multistream.py --quick).  Prints one JSON line per configuration and writes the list to --out.
 
-    python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--out multistream.json]
+    python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
+                                      [--out multistream.json]
 """
 import argparse
 import json
@@ -35,10 +38,12 @@ def make_pool(n_voices, seed=0):
 
 
 def time_ticks(conv, B, chunk, ticks, warmup, seed):
-    pcm = [(synthetic.make_waveform(chunk * 4, seed + s)[0].numpy() * 12000).astype(np.int16) for s in range(B)]
+    """chunk: one length, or a list of per-slot lengths (sessions at their own rates)"""
+    cs = list(chunk) if isinstance(chunk, (list, tuple)) else [chunk] * B
+    pcm = [(synthetic.make_waveform(cs[s] * 4, seed + s)[0].numpy() * 12000).astype(np.int16) for s in range(B)]
     ts = []
     for t in range(warmup + ticks):
-        feed = {s: pcm[s][(t % 4) * chunk:(t % 4 + 1) * chunk] for s in range(B)}
+        feed = {s: pcm[s][(t % 4) * cs[s]:(t % 4 + 1) * cs[s]] for s in range(B)}
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         conv.step(feed)
@@ -70,10 +75,12 @@ def main():
     ap.add_argument("--ticks", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--quick", action="store_true", help="B = 64 at -c 160 -b 16, distinct voices, graph only (profiler runs)")
+    ap.add_argument("--rates", default=None, help="comma-separated session rates: also time a batch spread over them")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     batches = [int(b) for b in args.batches.split(",")]
     configs = [tuple(int(v) for v in c.split("x")) for c in args.configs.split(",")]
+    rates = [int(r) for r in args.rates.split(",")] if args.rates else None
     mixes = ("shared", "distinct")
     if args.quick:
         batches, configs, mixes = [64], [(160, 16)], ("distinct",)
@@ -98,6 +105,18 @@ def main():
                 rec["real_time"] = rec["graph_tick_p99_ms"] < period_ms
                 rec["sessions_served_in_real_time"] = B if rec["real_time"] else 0
                 ms, nbytes = time_search(conv, B)
+                if rates:
+                    rec["rates"] = rates
+                    for mode in (("graph",) if args.quick else ("eager", "graph")):
+                        mixed = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, rates=rates)
+                        for s in range(B):
+                            mixed.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5,
+                                       rate=rates[s % len(rates)])
+                        if mode == "graph":
+                            mixed.enable_graph()
+                        p50, p99 = time_ticks(mixed, B, mixed.slot_chunk, args.ticks, args.warmup + bs + 1, 300)
+                        rec[f"mixed_{mode}_tick_p50_ms"], rec[f"mixed_{mode}_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                        del mixed
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
                 rows.append(rec)
