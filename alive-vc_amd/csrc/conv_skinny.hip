@@ -8,7 +8,6 @@
 // for the tiled kernels: fp32 [Co_pad][K_pad], or 2 / 3 bf16 planes whose sum is the (16- / 24-bit mantissa) weight.
 #include "conv_epilogue.h"
 #include "planes_layout.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -171,9 +170,8 @@ bool alive_conv_skinny_try(const AliveConv* d, hipStream_t s, int* rc) {
     if (d->precision == 0 && (d->K_pad & 15)) return false;
     dim3 g(cdiv(d->Co, 16), cdiv(ncols, 32));
     const bool pw = d->KW == 1 && d->stride == 1 && d->pad_left == 0 && d->Tout <= d->Tin;
-    static const int k16 = getenv("ALIVE_SKINNY_K16") ? atoi(getenv("ALIVE_SKINNY_K16")) : 512;
     const int Kp = d->precision == 0 ? d->K_pad : d->KW * d->Ci_pad;
-    const bool wide = Kp >= k16;
+    const bool wide = Kp >= 512;
 #define SKINNY_LAUNCH(NP_, PW_) do { if (wide) conv_skinny_kernel<NP_, PW_, 16><<<g, 1024, 0, s>>>(*d, ncols); \
                                       else conv_skinny_kernel<NP_, PW_, 8><<<g, 512, 0, s>>>(*d, ncols); } while (0)
     if (d->precision == 0) { if (pw) SKINNY_LAUNCH(0, true); else SKINNY_LAUNCH(0, false); }

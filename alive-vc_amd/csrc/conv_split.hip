@@ -17,12 +17,6 @@
 // of 64x32), v_mfma_f32_32x32x16_bf16.
 #include "conv_epilogue.h"
 #include "planes_layout.h"
-#include <stdlib.h>
-
-#ifndef ALIVE_CONV_ABL
-#define ALIVE_CONV_ABL 0             // ablation bits (timing only, WRONG results): 1 no epilogue, 2 B fragments read once per channel block, 4 no X DMA after the first,
-                                     // 8 weight fragments loaded once, 16 no gelu, 32 FiLM without the interpolation, 64 no transposed plane leave
-#endif
 
 namespace {
 
@@ -41,10 +35,6 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 constexpr int PROW = 64;          // PLANES = true: bytes per LDS row (32 channels bf16, no pad: 16-B chunks swizzled by the row)
 
 // NP = number of bf16 planes per operand: 2 -> 3 MFMAs per product (~2^-16), 3 -> 6 MFMAs per product (~2^-24, fp32-grade)
-// BM = 256: all 256 output channels of the filter's coarsest scale in ONE block -- a wave owns 64 rows x 128 columns (2 x 4 MFMA
-// tiles, 128 accumulator registers, one block per CU).  Against two 128-row blocks per column tile that stages the X tile
-// (global loads, split, LDS writes) once instead of twice, reads every activation fragment for two row tiles instead of one
-// (0.33 instead of 0.67 LDS fragment reads per MFMA) and halves the X traffic from L2 / HBM.
 // PLANES = true (BM = 128, NP = 2; round 3): the activation operand arrives ALREADY split, plane-packed with rows = time
 // (AliveConv.Xp: the k-blocked planes of gemm_planes.hip / planes_layout.h, rows = n * Tin + t), so a 32-channel block of the X
 // tile is ONE run of 144 consecutive 64-B row segments per plane that LDS-DMA copies straight into LDS -- no fp32 loads, no split, no ds_write in the
@@ -61,11 +51,11 @@ constexpr int PROW = 64;          // PLANES = true: bytes per LDS row (32 channe
 // fragment pair the stacked 128-row form would read 1 KB of LDS per MFMA (the LDS peak): NP = 1 runs as the 2 x 2 form of BM = 128 (a B
 // fragment feeds two row tiles; 144 registers, three blocks per CU).
 template <int BM, int NP, bool PLANES = false, bool W22 = false>
-__global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv_split_kernel(AliveConv p, float film_ratio) {
+__global__ __launch_bounds__(256, 2) void conv_split_kernel(AliveConv p, float film_ratio) {
     static_assert(!W22 || BM == 128, "the 2 x 2 wave arrangement is the 128-row tile's");
-    // wave tile: (32 | 64) rows x (128 | 64) columns.  BM = 256 / 128: four waves stacked along the rows; BM = 64: 2 x 2.
+    // wave tile: (32 | 64) rows x (128 | 64) columns.  BM = 128: four waves stacked along the rows; BM = 64: 2 x 2.
     constexpr int NR = W22 ? 2 : (BM >= 128 ? 4 : 2);         // 32-column MFMA tiles per wave
-    constexpr int MR = W22 ? 2 : (BM == 256 ? 2 : 1);         // 32-row MFMA tiles per wave
+    constexpr int MR = W22 ? 2 : 1;                           // 32-row MFMA tiles per wave
 
     // X tile, double buffered: [2 buffers][2 planes][XROWS][PITCH]
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (NP > 1 ? NP : 2) * XPLANE];      // (NP = 1: the epilogue's staging needs the 46 KB)
@@ -96,11 +86,7 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv_split_kernel(Aliv
     }
     bf16x8 a_cur[MR][2][NP], a_nxt[MR][2][NP];    // [row tile][k16 step][plane]
     auto load_A = [&](int cb, int j, bf16x8 (&a)[MR][2][NP]) {
-#ifdef ALIVE_CONV_ABL_SAMEA          // ablation (timing only, WRONG results): every k-step reads the weights of k-step 0 -- the L1 serves them
-        const int kcol = 0 * (j + cb);
-#else
         const int kcol = j * p.Ci_pad + cb * BKC;
-#endif
 #pragma unroll
         for (int mr = 0; mr < MR; ++mr)
 #pragma unroll
@@ -236,31 +222,20 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv_split_kernel(Aliv
     advance();
     if constexpr (!PLANES) store_X(0);
     __syncthreads();
-#ifdef ALIVE_CONV_PRIO
-    __builtin_amdgcn_s_setprio(ALIVE_CONV_PRIO);              // the k-loop of this wave before the epilogue of a co-resident block's
-#endif
     for (int cb = 0; cb < ncb; ++cb) {
         const bool more_cb = cb + 1 < ncb;
-        if (ALIVE_CONV_ABL & 8) pcb = ncb;                     // no further weight loads
         if constexpr (PLANES) {
-            if (more_cb && !(ALIVE_CONV_ABL & 4)) dma_X(cb + 1, (cb + 1) & 1);          // lands under this block's taps; the barrier below waits for it
+            if (more_cb) dma_X(cb + 1, (cb + 1) & 1);          // lands under this block's taps; the barrier below waits for it
         } else {
             if (more_cb) load_X(cb + 1);                       // in flight under this block's taps
         }
         const unsigned char* Xs = smem + (cb & 1) * NP * XPLANE;
-#if ALIVE_CONV_ABL & 2
-        bf16x8 bf[NP][NR];
-#endif
         for (int j = 0; j < p.KW; ++j) {
             if (pcb < ncb) load_A(pcb, pj, a_nx2);
             advance();
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-#if !(ALIVE_CONV_ABL & 2)
                 bf16x8 bf[NP][NR];
-#endif
-                if ((ALIVE_CONV_ABL & 2) && (j > 0 || s2 > 0)) {
-                } else
                 if constexpr (PLANES) {
                     const int rho = wcol + lr + j * p.dil;             // + nn * 32 does not change (row >> 2) & 3
                     const unsigned char* b = Xs + rho * PROW + (((2 * s2 + lh) ^ ((rho >> 2) & 3)) << 4);
@@ -300,18 +275,6 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv_split_kernel(Aliv
         __syncthreads();          // next X tile visible (vmcnt(0) covers the DMA); this one is free to be overwritten one block later
     }
 
-    if (ALIVE_CONV_ABL & 1) {
-        float sx = 0.0f;
-#pragma unroll
-        for (int mr = 0; mr < MR; ++mr)
-#pragma unroll
-            for (int nn = 0; nn < NR; ++nn) sx += acc[mr][nn][lane & 15];
-        if (sx == 12345.678f && p.Y != nullptr) p.Y[0] = sx;
-        return;
-    }
-#ifdef ALIVE_CONV_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     // ---- epilogue: accumulators -> LDS -> cooperative row-wise pass ----
     // Staging the tile through LDS turns the MFMA layout (a lane owns 16 scattered rows of one column) into
     // whole rows: every global access of the epilogue (residual, skip, Y, Z) is a 16-B vector per thread on
@@ -385,28 +348,20 @@ __global__ __launch_bounds__(256, BM == 256 ? 1 : 2) void conv_split_kernel(Aliv
                 if (p.Z != nullptr || p.Zp != nullptr) {
                     const float* fs = Ft + pr * 2 * FILM_NF - f_lo;
                     f32x4 z;
-#if ALIVE_CONV_ABL & 16
-                    const float gv[4] = {v[0], v[1], v[2], v[3]};
-#else
                     const f32x2 g0 = gelu_fast2(f32x2{v[0], v[1]}), g1 = gelu_fast2(f32x2{v[2], v[3]});
                     const float gv[4] = {g0[0], g0[1], g1[0], g1[1]};
-#endif
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-#if ALIVE_CONV_ABL & 32
-                        z[q] = gv[q] * fs[q] + fs[FILM_NF + q];
-#else
                         Lerp lp = lerp_coord(t + q + p.film_t0, film_ratio, p.Lf);
                         float sc = lerp_apply(lp, fs[lp.i0], fs[lp.i1]);
                         float sh = lerp_apply(lp, fs[FILM_NF + lp.i0], fs[FILM_NF + lp.i1]);
                         z[q] = gv[q] * sc + sh;
-#endif
                     }
                     if (p.Z != nullptr) *(f32x4*)(p.Z + o) = z;
                     if (p.Zp != nullptr) *(f32x4*)&Ct[pr * CP + (c4 ^ zsw(pr))] = z;      // in place: this thread's own four values
                 }
             }
-            if (p.Zp != nullptr && !(ALIVE_CONV_ABL & 64)) {
+            if (p.Zp != nullptr) {
                 // transposed leave: thread = (column, 8 channels); 8 lanes write the 128 B of a column's 64 channels per plane
                 __syncthreads();
                 unsigned short* Zp = (unsigned short*)p.Zp;
@@ -548,14 +503,11 @@ int alive_conv_split_launch(const AliveConv* d, float ratio, hipStream_t s) {
                         "output column that reads past the signal (the kernel clamps rows >= Tin instead of zero-filling them)");
     }
     ALIVE_CHECK_ARG(d->Tout <= d->Tin + d->pad_left, "alive_conv1d(split): Tout");
-    // measured (tools/bench_conv256.py, 128 windows x 4500 columns): the 256-row tile is 12 - 37 % SLOWER than two 128-row blocks
+    // measured (128 windows x 4500 columns): a 256-row tile is 12 - 37 % SLOWER than two 128-row blocks
     // (k5 + FiLM + residual 2.11 against 1.72 ms, 1x1 1.15 against 0.84): at one block per CU nothing covers the LDS / L2
-    // latencies of the single wave per SIMD, and no other block's main loop runs under the four epilogue passes.  Off by
-    // default; ALIVE_CONV_TILE256=1 selects it (same results bit for bit).
-    static const bool tile256 = getenv("ALIVE_CONV_TILE256") != nullptr && atoi(getenv("ALIVE_CONV_TILE256")) != 0;
-    static const bool w22 = getenv("ALIVE_CONV_W22") != nullptr && atoi(getenv("ALIVE_CONV_W22")) != 0;      // A/B: 2 x 2 waves (plane input)
+    // latencies of the single wave per SIMD, and no other block's main loop runs under the four epilogue passes.
     if (d->precision == 3) {
-        // plain fp16 (one plane per operand): the 2 x 2 form of the 128-row tile.  Measured (tools/bench_conv256.py, 128 windows x 4500 columns,
+        // plain fp16 (one plane per operand): the 2 x 2 form of the 128-row tile.  Measured (128 windows x 4500 columns,
         // k5 + FiLM + residual + Y / k5 + FiLM / 1x1 + FiLM + Y / k5 + residual + Y): 0.895 / 0.697 / 0.548 / 0.661 ms against the two-plane
         // form's 1.353 / 1.182 / 0.664 / 1.063; as one 256-row block per column tile (256 registers at two blocks per CU, 122 of them
         // spilled in the four epilogue passes) 1.625 / 1.319 / 1.239 / 0.747 -- not instantiated.
@@ -567,13 +519,9 @@ int alive_conv_split_launch(const AliveConv* d, float ratio, hipStream_t s) {
             dim3 g(cdiv(d->Tout, BN), 1, d->N);
             conv_split_kernel<64, 1><<<g, 256, 0, s>>>(*d, ratio);
         }
-    } else if (d->Co > 128 && d->Co % 256 == 0 && d->precision == 1 && tile256 && !d->Xp) {
-        dim3 g(cdiv(d->Tout, BN), d->Co / 256, d->N);
-        conv_split_kernel<256, 2><<<g, 256, 0, s>>>(*d, ratio);
     } else if (d->Co > 64) {
         dim3 g(cdiv(d->Tout, BN), cdiv(d->Co, 128), d->N);
         if (d->precision == 2) conv_split_kernel<128, 3><<<g, 256, 0, s>>>(*d, ratio);
-        else if (d->Xp && w22) conv_split_kernel<128, 2, true, true><<<g, 256, 0, s>>>(*d, ratio);
         else if (d->Xp) conv_split_kernel<128, 2, true><<<g, 256, 0, s>>>(*d, ratio);
         else conv_split_kernel<128, 2><<<g, 256, 0, s>>>(*d, ratio);
     } else {

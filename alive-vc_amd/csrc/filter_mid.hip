@@ -90,7 +90,7 @@ __device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
 // NTT = column tiles of 32 per wave: 4 on the batch path (256-column tiles, 200 outputs), 2 for a signal of a few such tiles (the
 // streaming step: 800 samples = four batch tiles on four CUs, 72 us of a 0.8-ms step): 128-column tiles, 72 outputs, twelve blocks with
 // half the serial chain each.  The halo is then 44 % of a tile -- irrelevant where the chip is empty.
-// H16 (round 5, decoder precision mode 1 with ALIVE_DECODER_BF16_MASK bit 16): the six k5 convs multiply ONE fp16 plane of the modulated
+// H16 (round 5, decoder precision mode 1, group (e)): the six k5 convs multiply ONE fp16 plane of the modulated
 // tensor by ONE fp16 plane of the weights -- a third of the MFMAs, no lo plane in LDS, half the weight registers.  The 1x1 input conv
 // keeps the split form (its operand is the raw residual stream).
 // SWEEP (round 6; H16 only, batch path): a block walks a SEGMENT of a window left to right, 256 NEW columns per tile, and hands every
@@ -491,16 +491,6 @@ __global__ __launch_bounds__(256, 1) void filter_block64_kernel(const float* __r
                 }
                 if (i == NT - 1 && emit) load_weights_step(q + 1, s);     // a[s] is dead: the next conv's weights travel under the rest of the step
                 if (!drain_first) epi_stage(E, it_second, it_emit, it_qf, it_dst, it_t, it_acc, s / 5, s % 5);
-#ifdef ALIVE_FB64_DUP_STAGE           // diagnostic (timing only): one stage's work a second time -- the increment prices the stage
-                if (s % 5 == ALIVE_FB64_DUP_STAGE && it_emit) {
-                    Epi E2 = E;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { asm volatile("" : "+v"(E2.jt[e]), "+v"(E2.je[e]), "+v"(E2.jx[e]), "+v"(E2.jsc[e])); asm volatile("" : "+v"(E2.jsh[e]), "+v"(E2.z[e])); }
-                    epi_stage(E2, false, true, it_qf, it_dst, it_t, it_acc, s / 5, s % 5);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { asm volatile("" :: "v"(E2.jt[e]), "v"(E2.je[e]), "v"(E2.jx[e]), "v"(E2.jsc[e])); asm volatile("" :: "v"(E2.jsh[e]), "v"(E2.z[e])); }
-                }
-#endif
                 __builtin_amdgcn_sched_barrier(0);           // one scheduling region per k-step
             }
             __syncthreads();
@@ -590,10 +580,13 @@ int filter_block64_impl(const float* U, int N, int L, const void* W16, const flo
     ALIVE_CHECK_ARG((double)BL * film_ld / L + 3.0 <= NFP, "alive_filter_block64: tile spans more than %d frames (L %d, frames %d)", NFP, L, film_ld);
     {
         static LdsOptIn optin;
-        hipError_t e = H16 ? optin.ensure({(const void*)filter_block64_kernel<false, 4, H16>, (const void*)filter_block64_kernel<true, 4, H16>,
-                                           (const void*)filter_block64_kernel<true, 2, H16>, (const void*)filter_block64_kernel<false, 4, true, true>}, LDS_BYTES)
-                           : optin.ensure({(const void*)filter_block64_kernel<false, 4, H16>, (const void*)filter_block64_kernel<true, 4, H16>,
-                                           (const void*)filter_block64_kernel<true, 2, H16>}, LDS_BYTES);
+        hipError_t e;
+        if constexpr (H16)
+            e = optin.ensure({(const void*)filter_block64_kernel<true, 4, true>, (const void*)filter_block64_kernel<true, 2, true>,
+                              (const void*)filter_block64_kernel<false, 4, true, true>}, LDS_BYTES);
+        else
+            e = optin.ensure({(const void*)filter_block64_kernel<false, 4, false>, (const void*)filter_block64_kernel<true, 4, false>,
+                              (const void*)filter_block64_kernel<true, 2, false>}, LDS_BYTES);
         if (e != hipSuccess) {
             alive_set_error("alive_filter_block64: cannot reserve %d B of LDS: %s", LDS_BYTES, hipGetErrorString(e));
             return ALIVE_ERR_LAUNCH;
@@ -617,10 +610,9 @@ int filter_block64_impl(const float* U, int N, int L, const void* W16, const flo
     const bool small = (int64_t)tiles * N <= 256;
     filter_block64_kernel<true, 4, H16><<<dim3(small ? tiles : 1, N), 256, LDS_BYTES, (hipStream_t)stream>>>(
         U, L, (const unsigned short*)W16, biases, film, film_rows, Lf, film_off, ratio, t0, f0, film_ld, skip, out, g_stamps64);
-    if constexpr (H16) {
-        // the sweep form (see the kernel): columns [TT, L) in segments walked left to right; ALIVE_FB64_SWEEP=0 keeps the tiled form (A/B)
-        static const bool sweep = !(getenv("ALIVE_FB64_SWEEP") && atoi(getenv("ALIVE_FB64_SWEEP")) == 0);
-        if (sweep && tiles > 1 && !small) {
+    if (tiles > 1 && !small) {
+        if constexpr (H16) {
+            // the sweep form (see the kernel): columns [TT, L) in segments walked left to right
             const int rem = L - TT, t256 = cdiv(rem, BL);
             // segments per window: the fewest chip rounds x (tiles per segment + the warm-up tile)
             int best_s = 1;
@@ -632,13 +624,11 @@ int filter_block64_impl(const float* U, int N, int L, const void* W16, const flo
             const int seg_cols = cdiv(t256, best_s) * BL;
             filter_block64_kernel<false, 4, true, true><<<dim3(cdiv(rem, seg_cols), N), 256, LDS_BYTES, (hipStream_t)stream>>>(
                 U, L, (const unsigned short*)W16, biases, film, film_rows, Lf, film_off, ratio, t0, f0, film_ld, skip, out, g_stamps64, TT, seg_cols);
-            ALIVE_CHECK_LAUNCH("alive_filter_block64");
-            return ALIVE_OK;
+        } else {
+            filter_block64_kernel<false, 4, false><<<dim3(tiles - 1, N), 256, LDS_BYTES, (hipStream_t)stream>>>(
+                U, L, (const unsigned short*)W16, biases, film, film_rows, Lf, film_off, ratio, t0, f0, film_ld, skip, out, g_stamps64);
         }
     }
-    if (tiles > 1 && !small)
-        filter_block64_kernel<false, 4, H16><<<dim3(tiles - 1, N), 256, LDS_BYTES, (hipStream_t)stream>>>(
-            U, L, (const unsigned short*)W16, biases, film, film_rows, Lf, film_off, ratio, t0, f0, film_ld, skip, out, g_stamps64);
     ALIVE_CHECK_LAUNCH("alive_filter_block64");
     return ALIVE_OK;
 }

@@ -465,8 +465,7 @@ int launch_small(const float* U, int N, int L, const float* wpack, const float* 
     const int tiles = cdiv(L, K::TT);
     // the first tile of a window reflects at t = 0 (per-lane fragment addresses); a problem that does not fill the chip runs all its
     // tiles through that form in one launch (filter_mid.hip)
-    static const int force = getenv("ALIVE_FBS_FORCE") ? atoi(getenv("ALIVE_FBS_FORCE")) : 0;      // diagnostic: 1 = every tile through the FIRST form, 2 = never
-    const bool small = force == 1 || (force != 2 && (int64_t)tiles * N <= 256);
+    const bool small = (int64_t)tiles * N <= 256;
     filter_block_small_kernel<C, true, PL><<<dim3(small ? tiles : 1, N), 256, K::LDS, s>>>(U, L, wpack, film, film_rows, Lf, film_off, ratio, t0,
                                                                                      f0, film_ld, skip, out, g_stamps_small);
     if (tiles > 1 && !small)

@@ -606,9 +606,6 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_lw_kernel(AliveGemm p, int
             ldst[i] = ((i >= 2 * NP ? NP : 0) + (q % (8 * NP)) / 8) * PLANE_BYTES + (q % 8) * 1024;
         }
         auto tile_offsets = [&](int tv, unsigned (&o)[NI]) {
-#ifdef ALIVE_LW_ABL_SAMETILE
-            tv = (blockIdx.x & 7) + 8 * (tv & 3);          // timing only: 4 tiles per XCD, everything hits L2
-#endif
             int mt, ct;
             tile_of(tv, n_mt, gw, mt, ct);
             const int64_t c0 = (int64_t)ct * GN;
@@ -659,12 +656,10 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_lw_kernel(AliveGemm p, int
                 const int ts = s + NS;
                 const bool in_tile = ts < nsteps;
                 if (ts == nsteps) walk.reset();
-#ifndef ALIVE_LW_ABL_NODMA
                 if (in_tile || has_next) {
 #pragma unroll
                     for (int i = 0; i < NI; ++i) issue(in_tile ? cur : (cur ^ 1), slot, i);
                 }
-#endif
                 walk.advance(gw);
             }
             if (!has_next) break;
@@ -724,37 +719,22 @@ __global__ __launch_bounds__(512, 1) void gemm_planes_lw_kernel(AliveGemm p, int
             const int slot = (qb + s) % NS;
             const int slot1 = slot + 1 == NS ? 0 : slot + 1;
             mma(fa[0], fb[0], [&](int n) {
-#ifdef ALIVE_LW_ABL_NOREAD
-                if (n == 0 && s == 0) load_frags(slot, 1, fa[1], fb[1]);
-#else
                 if (n == 0) load_frags(slot, 1, fa[1], fb[1]);
-#endif
             });
             __builtin_amdgcn_sched_barrier(0);
             wait_lgkmcnt0();
             __builtin_amdgcn_s_barrier();
-#ifndef ALIVE_LW_ABL_NOREAD
             if (s + 1 < nsteps) load_frags(slot1, 0, fa[0], fb[0]);
-#endif
             __builtin_amdgcn_sched_barrier(0);
             mma(fa[1], fb[1], [&](int) {});
             __builtin_amdgcn_sched_barrier(0);
         }
-#ifdef ALIVE_LW_ABL_NOEPI
-        if (nsteps < 0)
-#endif
         {
             int mt, ct;
             tile_of(v, n_mt, gw, mt, ct);
             gemm_epilogue<NP, ACT>(p, acc, mt * GM, (int64_t)ct * GN, wr, wc, lr, lh, cols, cols_pad, co_pad32, nullptr,
                                    p.Pout != nullptr ? smem + NS * SLOT + w * 2048 : nullptr);
         }
-#ifdef ALIVE_LW_ABL_NOEPI
-        else {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) { asm volatile("" :: "v"(acc[i][0])); asm volatile("" :: "v"(acc[i][1])); }
-        }
-#endif
         if (!has_next) break;
         v = vn;
         qb = (qb + nsteps) % NS;
@@ -958,29 +938,24 @@ extern "C" int alive_gemm_planes(const AliveGemm* d, void* stream) {
                     "alive_gemm_planes: W / P / Pout must be 16-byte aligned");
     ALIVE_CHECK_ARG(!(d->Y || d->residual) || (int64_t)d->N * d->Co * d->T < (1ll << 30),
                     "alive_gemm_planes: fp32 tensor of %lld elements exceeds the 32-bit offsets", (long long)d->N * d->Co * d->T);
-    // variants (A/B switch for tools/bench_gemm_planes.py): 0 = default, 1 = one-tile kernels only, 2 = persistent for both
+    // variants (A/B switch for tools/bench_gemm_planes.py): 0 = default, 1 = one-tile kernels only
     static const int variant = getenv("ALIVE_GEMM_VARIANT") ? atoi(getenv("ALIVE_GEMM_VARIANT")) : 0;
     const int64_t ntiles = (int64_t)cdiv(d->Co, GM) * cdiv((int64_t)d->N * d->T, GN);
     const int nsteps = pad32(d->Ci) / GK;
     // from 2 tiles per CU on (512; 1024 until the loader waves: with them the form pays below four tiles per CU too -- 512 -> 256 x 3
     // planes, 900 tiles: 0.125 -> 0.116 ms)
-    static const int persist_min = getenv("ALIVE_GEMM_PERSIST_MIN") ? atoi(getenv("ALIVE_GEMM_PERSIST_MIN")) : 512;
-    const bool can_persist = ntiles >= persist_min && variant != 1 &&
+    const bool can_persist = ntiles >= 512 && variant != 1 &&
                              (d->b_row == 0 ? (int64_t)d->planes * pad_cols((int64_t)d->N * d->T) * pad32(d->Ci)
                                             : (int64_t)d->planes * d->b_plane) * 2 < (1ll << 32);          // 32-bit DMA offsets
     if (d->planes == 1) {
         // one plane = plain fp16 operands, one MFMA per product (round 5): W and P are single fp16 planes in the k-blocked layout.
         // Stages of 16 KB, four in the ring, two blocks per CU.
-        static const int form1 = getenv("ALIVE_GEMM1_FORM") ? atoi(getenv("ALIVE_GEMM1_FORM")) : 0;      // A/B: ring depth x blocks per CU
-        // K a multiple of 64: the 64-deep step in the two-plane kernel's slots (form 4 forces the 32-deep kernel)
-        if ((pad32(d->Ci) & 63) == 0 && pad32(d->Ci) >= 128 && form1 == 0) {
+        // K a multiple of 64: the 64-deep step in the two-plane kernel's slots
+        if ((pad32(d->Ci) & 63) == 0 && pad32(d->Ci) >= 128) {
             if (d->act == 1) return launch_gemm_act<2, 2, 2, 1, true>(*d, (hipStream_t)stream);
             if (d->act == 2) return launch_gemm_act<2, 2, 2, 2, true>(*d, (hipStream_t)stream);
             return launch_gemm_act<2, 2, 2, 0, true>(*d, (hipStream_t)stream);
         }
-        if (form1 == 1) return launch_gemm<1, 3, 3>(*d, (hipStream_t)stream);
-        if (form1 == 2) return launch_gemm<1, 6, 2>(*d, (hipStream_t)stream);
-        if (form1 == 3) return launch_gemm<1, 2, 4>(*d, (hipStream_t)stream);
         return launch_gemm<1, 4, 2>(*d, (hipStream_t)stream);
     }
     ALIVE_CHECK_ARG(!d->f16s || (d->planes == 2 && d->wscale != nullptr && d->in_unscale > 0.0f && d->act >= 0 && d->act <= 3 &&
@@ -994,7 +969,6 @@ extern "C" int alive_gemm_planes(const AliveGemm* d, void* stream) {
     }
     if (d->planes == 2) {
         // two planes: the one-tile kernel with two blocks per CU (one block's epilogue under the other's MFMAs) beats one persistent block
-        if (can_persist && variant == 2 && nsteps >= 4) return launch_gemm_lw<2, 4>(*d, (hipStream_t)stream);
         return launch_gemm<2, 2, 2>(*d, (hipStream_t)stream);
     }
     if (can_persist && nsteps >= 3) return launch_gemm_lw<3, 3>(*d, (hipStream_t)stream);

@@ -1025,7 +1025,7 @@ typedef int v8i __attribute__((ext_vector_type(8)));
 // of the same frames starts its lists AT tau instead of at -inf -- every entry holds tau with index -1, so rows below it
 // are never admitted and the list floor the certificate reads is tau until real rows replace it.  Without a seed a split's
 // lists warm up from nothing: 16 (1 + ln(n / 16)) admissions per half-list, and every admission in any wave stops the
-// block's matrix pipes at the next barrier (ablation -DALIVE_KNN_ABL_RARE_W=1: the rare path in ONE wave of four costs
+// block's matrix pipes at the next barrier (measured by ablation: the rare path in ONE wave of four costs
 // what it costs in all four).  A row below tau has an fp8 score more than SEED_MARGIN under k rows already seen: it is
 // "outside" in the certificate's sense, with tau as the bound on its score, exactly like a row under a full list's floor.
 // The hand-off is one LOOK at the previous split's flag (no waiting: nothing can hang, an unfinished predecessor just means
@@ -1038,22 +1038,6 @@ constexpr float SEED_MARGIN16_STRICT = 4.5e-3f;                  // strict searc
 constexpr int SEED_MIN_FB = 512;
 constexpr int SEED_MIN_FB6 = 300;                                // fp6 kernel, 384-frame blocks: a little over one round of the chip is enough --
                                                                  // the look at the predecessor's flag never waits, an unfinished one means an unseeded block
-static float seed_margin8() {              // ALIVE_KNN_SEED_MARGIN (cosine units): experiments only
-    static const float m = [] {
-        const char* e = getenv("ALIVE_KNN_SEED_MARGIN");
-        const float v = e ? (float)atof(e) : 0.0f;
-        return v > 0.0f ? v * F8_SCALE * F8_SCALE : SEED_MARGIN8;
-    }();
-    return m;
-}
-static float seed_margin6() {
-    static const float m = [] {
-        const char* e = getenv("ALIVE_KNN_SEED_MARGIN");
-        const float v = e ? (float)atof(e) : 0.0f;
-        return v > 0.0f ? v * F6_SCALE * F6_SCALE : SEED_MARGIN6;
-    }();
-    return m;
-}
 
 template <int FMT, int NCT8>
 __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict__ s_f8,
@@ -1154,10 +1138,9 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
 
     auto load_a = [&](const unsigned char* Ab, int ks) {
         const unsigned char* q = Ab + (ks >> 1) * 4 * PIECE;
-#ifndef ALIVE_KNN6_READ32
         if constexpr (FMT == 2) {
             // Only the 24 code bytes of the 32-byte slot leave the LDS (the kernel moves 120 KB through the LDS per 1 152 MFMA cycles:
-            // 61.0 -> 57.7 ms per launch; -DALIVE_KNN6_READ32 restores the two b128 reads).  A compiler-visible ds_read_b64 of the tile
+            // 61.0 -> 57.7 ms per launch against two b128 reads).  A compiler-visible ds_read_b64 of the tile
             // buffer makes hipcc wait vmcnt(0) for the LDS-DMA in flight, so the 8-byte half goes through asm -- issued
             // BEFORE the visible ds_read_b128 (whose address is tied to the asm): LDS reads of a wave return in order, so the wait
             // hipcc places in front of the fragment's first use (the MFMA takes both halves) covers the asm read too; an unknown
@@ -1170,7 +1153,6 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             const u32x4 lo = *(const __attribute__((address_space(3))) u32x4*)(uintptr_t)off0;
             return v8i{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)h8.x, (int)h8.y, 0, 0};
         }
-#endif
         const u32x4 lo = *(const u32x4*)(q + a_off[ks & 1][0]);
         const u32x4 hi = *(const u32x4*)(q + a_off[ks & 1][1]);
         return v8i{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
@@ -1240,12 +1222,6 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
 
     auto fold_rare = [&](f32x16& acc, int ni, int tile, float mx) {
         if (__builtin_amdgcn_ballot_w64(mx > thr[ni]) == 0) return;
-#ifdef ALIVE_KNN_ABL_NORARE            // ablation build (tools/bench_knn.py): the fold's fast path only -- results are WRONG, timing only
-        return;
-#endif
-#ifdef ALIVE_KNN_ABL_RARE_W            // ablation build: only waves below this number take the rare path (WRONG results): what a trip
-        if (w >= ALIVE_KNN_ABL_RARE_W) return;      // costs the OTHER waves of the block through the per-tile barrier
-#endif
         // Rare path (wave-uniform; by ablation ~1500 cycles with the matrix pipe idle, 15 % of the kernel on the bench batch and
         // 30 % on uncorrelated frames), cut for the common case of ONE admitted row per lane:
         //  * every lane's list minimum and its quarter are known from the register caches, so the quarter is read from LDS
@@ -1320,16 +1296,7 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         const unsigned char* Ab = smem + buf * ABUF8;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; c2[r] = 0.0f; }
-#ifndef ALIVE_KNN6_PD
-#define ALIVE_KNN6_PD 1                 // A fragments requested this many k-steps ahead of their MFMAs
-#endif
-        constexpr int PD6 = ALIVE_KNN6_PD, NA6 = PD6 + 1;
-        // ablation switches (timing only, WRONG results: tools/ab_build.sh x.so knn.hip -DALIVE_KNN6_ABL=<bits>): 1 no LDS-DMA of the next
-        // tile, 2 no fragment reads after the tile's first, 4 no barrier at the end of the tile
-#ifndef ALIVE_KNN6_ABL
-#define ALIVE_KNN6_ABL 0
-#endif
-        constexpr bool ABL_NODMA = (ALIVE_KNN6_ABL & 1) != 0, ABL_NOLDS = (ALIVE_KNN6_ABL & 2) != 0, ABL_NOBAR = (ALIVE_KNN6_ABL & 4) != 0;
+        constexpr int PD6 = 1, NA6 = PD6 + 1;     // A fragments requested this many k-steps ahead of their MFMAs
         v8i a[NA6];
 #pragma unroll
         for (int i = 0; i < PD6; ++i) a[i] = load_a(Ab, i);
@@ -1340,8 +1307,8 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
             c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[(ks) % NA6], bq[0][ks], c0, FMT, FMT, 0, 127, 0, 127); \
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
-            if ((ks) + PD6 < NK64 && !ABL_NOLDS) a[((ks) + PD6) % NA6] = load_a(Ab, (ks) + PD6);                                 \
-            if ((ks) < D / 128 && !ABL_NODMA)                                                                                    \
+            if ((ks) + PD6 < NK64) a[((ks) + PD6) % NA6] = load_a(Ab, (ks) + PD6);                                               \
+            if ((ks) < D / 128)                                                                                                  \
                 __builtin_amdgcn_global_load_lds((gptr_t)(gnext + (ks) * 128), (lptr_t)(lnext + (ks) * 4 * PIECE), 16, 0, 0);    \
             AFTER0;                                                                                                              \
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
@@ -1355,13 +1322,8 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         }
         f32x16 v0, v1, v2;
         auto acc_read = [&](const f32x16& a_, int lo, int hi, f32x16& v) {
-#ifdef ALIVE_KNN_ABL_NOREAD            // ablation (timing only, WRONG results): what the 48 accumulator copies of a tile cost
-#pragma unroll
-            for (int r = lo; r < hi; ++r) v[r] = -INFINITY;
-#else
 #pragma unroll
             for (int r = lo; r < hi; ++r) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v[r]) : "a"(a_[r]));
-#endif
         };
         auto acc_pin = [&]() { asm volatile("" : "+a"(c0), "+a"(c1), "+a"(c2)); };
         K8_STEP3(0, (void)0, (void)0, (void)0) K8_STEP3(1, (void)0, (void)0, (void)0) K8_STEP3(2, (void)0, (void)0, (void)0)
@@ -1375,7 +1337,7 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         K8_STEP3(11, (void)0, (void)0, (void)0)
 #undef K8_STEP3
         acc_pin();
-        if (!ABL_NOBAR) __syncthreads();
+        __syncthreads();
     };
     auto fold_now3 = [&](f32x16& p0, f32x16& p1, f32x16& p2, int tile) {
         mask_ragged(p0, tile);
@@ -1439,7 +1401,6 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
             AFTER1;                                                                                                              \
         }
-#ifndef ALIVE_KNN_FOLD_EARLY
         // The previous tile's accumulators (p0, p1) STAY in their AGPR set until the second half of this tile and are copied out
         // there by explicit v_accvgpr_read, eight at a time behind the MFMAs of steps 6 .. 9 (the gaps of steps 0 .. 5 carry the
         // LDS-DMA pieces), each group pinned behind its MFMA by an empty asm that names the running accumulators.  Left to itself
@@ -1465,14 +1426,6 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         K8_STEP(9, (acc_pin(), pm1 = max8(v1, 0, pm1)), pm1 = max8(v1, 8, pm1))
         K8_STEP(10, (void)0, fold_rare(v0, 0, tile - 1, pm0))
         K8_STEP(11, (void)0, fold_rare(v1, 1, tile - 1, pm1))
-#else   // -DALIVE_KNN_FOLD_EARLY: the form of rounds 2 .. 3 (A/B builds): the fold reads p0 / p1 as plain values in steps 0 .. 3
-        K8_STEP(0, (mask_ragged(p0, tile - 1), pm0 = max8(p0, 0, pm0)), pm0 = max8(p0, 8, pm0))
-        K8_STEP(1, (mask_ragged(p1, tile - 1), pm1 = max8(p1, 0, pm1)), pm1 = max8(p1, 8, pm1))
-        K8_STEP(2, (void)0, fold_rare(p0, 0, tile - 1, pm0))
-        K8_STEP(3, (void)0, fold_rare(p1, 1, tile - 1, pm1))
-        K8_STEP(4, (void)0, (void)0) K8_STEP(5, (void)0, (void)0) K8_STEP(6, (void)0, (void)0) K8_STEP(7, (void)0, (void)0)
-        K8_STEP(8, (void)0, (void)0) K8_STEP(9, (void)0, (void)0) K8_STEP(10, (void)0, (void)0) K8_STEP(11, (void)0, (void)0)
-#endif
 #undef K8_STEP
         // The accumulators are next read by the fold inside the NEXT tile, and hipcc sinks the whole c1 chain down to that use:
         // eight dependent MFMAs back to back behind the barrier, their A fragments parked in AGPRs.  An opaque use pins both
@@ -3237,7 +3190,7 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
         probe_decide_kernel<<<1, 1, 0, s>>>(w.stats, w.probe_n, PROBE_NUM, PROBE_DEN);
     }
     // ---- mode 0: the fp8 / fp6 stage first ----
-    const SeedArgs sa8 = seeds_for(w, p.Tt_pad / ft, p.split, k, f6 ? seed_margin6() : seed_margin8(), ST_SEEDED, s, f6 ? SEED_MIN_FB6 : SEED_MIN_FB);
+    const SeedArgs sa8 = seeds_for(w, p.Tt_pad / ft, p.split, k, f6 ? SEED_MARGIN6 : SEED_MARGIN8, ST_SEEDED, s, f6 ? SEED_MIN_FB6 : SEED_MIN_FB);
     if (g_ev_start) (void)hipEventRecord(g_ev_start, s);             // behind the memset of the seed flags: the events bracket the kernel alone
     if (f6)
         knn_score6_kernel<<<dim3((unsigned)(p.Tt_pad / ft), p.split), 256, lds, s>>>(

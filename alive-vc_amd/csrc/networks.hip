@@ -135,8 +135,7 @@ AliveConv split(AliveConv d) {
 //   (tests/test_gpu_models.py::test_decoder_precision_modes).  The first form
 //   of mode 1 used plane 0 of the bf16 images (8 significand bits): 1.19e-4 on the same fixture -- fp16 costs the same MFMAs and bytes.
 // mode 2: two-plane split bf16 for these too (rounds 1 - 4).  ALIVE_DECODER_PRECISION=2 or alive_decoder_precision(2).
-// ALIVE_DECODER_BF16_MASK (experiments): which of (a) = 1, (b) = 2, (c) = 4, (d: the two transposed convs) = 8, (e) = 16 mode 1 covers
-// (default 23).
+// decoder_bf16_mask(): the groups mode 1 covers, (a) = 1, (b) = 2, (c) = 4, (e) = 16.
 // Sensitivities (oracle with the operands of one group rounded to fp16 | to bf16; 450-frame fixture, waveform RMS 0.66): (a) 1.24e-5 |
 // 1.11e-4, (b) 3.4e-6 | 2.7e-5, (c) 1.3e-6 + 1.2e-6 + 2.0e-7 | 2.2e-5 + 8.3e-6 + 1.3e-6; not adopted: FiLM projections 1.4e-4 | 1.6e-3,
 // input layer 1.2e-4 | 1.5e-3, up convs 1.0e-5 | 8.1e-5 (store bound: nothing to gain); (e) 2.6e-5 | 2.2e-4 -- adopted last, for
@@ -150,8 +149,7 @@ int decoder_precision() {
     return g_decoder_precision;
 }
 int decoder_bf16_mask() {
-    static const int m = getenv("ALIVE_DECODER_BF16_MASK") ? atoi(getenv("ALIVE_DECODER_BF16_MASK")) : 23;
-    return decoder_precision() == 1 ? m : 0;
+    return decoder_precision() == 1 ? 23 : 0;
 }
 
 bool fb64s_enabled() {          // ALIVE_FB64S=0: the 64-channel block on filter_mid.hip's sweep kernel, as before
@@ -742,9 +740,6 @@ int decoder_run(const float* const* w, const float* x_in, const float* f0, const
                                     F_MODE[s] == 0 && !fused256 ? b.Hh : b.U);
             d.up = r;
             if (F_SPLIT[s]) d = split(d);
-            // (experiment, mask bit 8, off: the two transposed convs are bound by their stores -- 170.1 +- 0.3 ms per step either way, and the
-            // fixture error goes 1.40e-5 -> 1.79e-5)
-            if (F_SPLIT[s] && (decoder_bf16_mask() & 8) && (int64_t)N * L > 96) d = plain(d);
             RUN(alive_conv1d(&d, stream));
         }
         L *= r;
