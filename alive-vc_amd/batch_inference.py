@@ -1,0 +1,154 @@
+"""Many-to-many batch conversion CLI: a corpus of files, each converted to a voice of its own, in ONE batched run
+(module/pipeline.py: Converter.convert_many -- the windows of every file form one batch, the kNN match is one pool search).
+
+The jobs file is a JSON list; each entry:
+  {"input": "a.wav",                                        the file to convert
+   "target": "spk.wav" and / or "lib": "voice_library.pt",  its voice (as -t / -lib of inference.py; both: concatenated in
+                                                            inference.py's order, the target's frames first)
+   "pitch": 0, "intonation": 1, "f0_rate": 1, "alpha": 0,   optional, inference.py's -p / -int / -f0 / -a
+   "gain": 1, "normalize": false,                           optional, inference.py's -g / -norm
+   "output": "a_out.wav"}                                   optional: default <outdir>/<index>_<input name>.wav
+Jobs naming the same voice sources share one voice of the pool.  Every file keeps inference.py's edges: loaded, resampled to
+16 kHz, normalised by its maximum, mono mean; the output resampled back to the file's own rate, gain, optional normalisation.
+Each output is bitwise what `inference.py --knn-strict` writes for that file, voice and settings.
+Flags shared with inference.py keep its spelling: -c, -k, -d, -dep, -cep, -f0ep, --window-batch, --pcm16, --no-trim-context.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from module import audio_io                                     # noqa: E402
+from module.multistream import MAX_K                             # noqa: E402
+
+JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "output")
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description="Convert many files, each to its own voice, in one batched run")
+    parser.add_argument('jobs', help="JSON list of jobs (see the module docstring)")
+    parser.add_argument('-o', '--outputs', default="./outputs/")
+    parser.add_argument('-d', '--device', default='cuda')
+    parser.add_argument('-dep', '--decoder-path', default="decoder.pt")
+    parser.add_argument('-cep', '--content-encoder-path', default="content_encoder.pt")
+    parser.add_argument('-f0ep', '--f0-estimator-path', default="f0_estimator.pt")
+    parser.add_argument('-k', default=4, type=int)
+    parser.add_argument('-c', '--chunk', default=48000, type=int)
+    parser.add_argument('--window-batch', default=64, type=int, help="windows per device batch")
+    parser.add_argument('--no-trim-context', action='store_true',
+                        help="run the kNN match and the decoder over all three chunks of every window (same samples)")
+    parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV")
+    return parser
+
+
+def load_jobs(path, k=4):
+    """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder); ValueError on a malformed
+    job, before anything runs on the device"""
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"k={k} outside [1, {MAX_K}] (the pool search's limit)")
+    with open(path) as f:
+        jobs = json.load(f)
+    if not isinstance(jobs, list) or not jobs:
+        raise ValueError(f"{path}: expected a non-empty JSON list of jobs")
+    base = os.path.dirname(os.path.abspath(path))
+    rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))      # noqa: E731
+    out = []
+    for i, j in enumerate(jobs):
+        if not isinstance(j, dict) or "input" not in j:
+            raise ValueError(f"job {i}: an object with an \"input\" wav is required")
+        unknown = set(j) - set(JOB_KEYS)
+        if unknown:
+            raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: {JOB_KEYS})")
+        if j.get("target") is None and j.get("lib") is None:
+            raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
+        e = dict(input=rel(j["input"]), target=rel(j.get("target")), lib=rel(j.get("lib")), output=rel(j.get("output")),
+                 pitch=float(j.get("pitch", 0.0)), intonation=float(j.get("intonation", 1.0)), f0_rate=float(j.get("f0_rate", 1.0)),
+                 alpha=float(j.get("alpha", 0.0)), gain=float(j.get("gain", 1.0)), normalize=bool(j.get("normalize", False)))
+        for key in ("input", "target", "lib"):
+            if e[key] is not None and not os.path.isfile(e[key]):
+                raise ValueError(f"job {i}: {key} {e[key]!r} does not exist")
+        out.append(e)
+    return out
+
+
+def voice_key(job):
+    """jobs with the same voice sources share one pool voice"""
+    return (job["target"], job["lib"])
+
+
+def check_voice_sizes(sizes, k):
+    """sizes: voice key -> vectors; ValueError for a voice shorter than k"""
+    for key, m in sizes.items():
+        if m < k:
+            raise ValueError(f"voice {key}: {m} vectors, fewer than k={k}")
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    device = torch.device(args.device)
+    if device.type != "cuda":
+        raise SystemExit("this build runs on the MI355X only: pass -d cuda")
+    jobs = load_jobs(args.jobs, args.k)
+    # (device work starts here)
+    from module.content_encoder import ContentEncoder
+    from module.decoder import Decoder
+    from module.f0_estimator import F0Estimator
+    from module.multistream import VoicePool
+    from module.pipeline import Converter
+    from module.spectrogram import spectrogram
+    from module.voice_library import VoiceLibrary
+
+    PE, CE, Dec = F0Estimator().to(device), ContentEncoder().to(device), Decoder().to(device)
+    PE.load_state_dict(torch.load(args.f0_estimator_path, map_location=device))
+    CE.load_state_dict(torch.load(args.content_encoder_path, map_location=device))
+    Dec.load_state_dict(torch.load(args.decoder_path, map_location=device))
+    os.makedirs(args.outputs, exist_ok=True)
+
+    voices = {}
+    for job in jobs:                                  # inference.py:86-92 per distinct voice
+        key = voice_key(job)
+        if key in voices:
+            continue
+        tgt = torch.zeros(1, 768, 0, device=device)
+        if job["target"] is not None:
+            wf, sr = audio_io.load(job["target"])
+            wf = audio_io.resample(wf.to(device), sr, 16000)
+            wf = wf / wf.abs().max()
+            tgt = CE(spectrogram(wf[:1]))
+        if job["lib"] is not None:
+            VL = VoiceLibrary().to(device)
+            VL.load_state_dict(torch.load(job["lib"], map_location=device))
+            tgt = torch.cat([tgt, VL.tokens], dim=2)
+        voices[key] = tgt
+    check_voice_sizes({k_: int(t.shape[2]) for k_, t in voices.items()}, args.k)
+    names = {key: f"voice{i}" for i, key in enumerate(voices)}
+    pool = VoicePool({names[key]: t for key, t in voices.items()}, device=device)
+    print(f"{len(jobs)} jobs over {len(voices)} voices ({pool.P} vectors)")
+
+    utts, rates = [], []
+    for job in jobs:
+        wf, sr = audio_io.load(job["input"])
+        wf = audio_io.resample(wf.to(device), sr, 16000)
+        wf = wf / wf.abs().max()
+        utts.append(wf.mean(dim=0, keepdim=True))
+        rates.append(sr)
+    conv = Converter(CE, PE, Dec, device)
+    outs = conv.convert_many(utts, pool, [names[voice_key(j)] for j in jobs], pitch_shift=[j["pitch"] for j in jobs],
+                             intonation=[j["intonation"] for j in jobs], f0_rate=[j["f0_rate"] for j in jobs],
+                             alpha=[j["alpha"] for j in jobs], chunk=args.chunk, k=args.k, window_batch=args.window_batch,
+                             trim_context=not args.no_trim_context)
+    for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
+        out = audio_io.resample(out, 16000, sr, post_gain_db=job["gain"]).cpu()
+        if job["normalize"]:
+            out = out / out.abs().max()
+        path = job["output"] or os.path.join(args.outputs, f"{i}_{os.path.splitext(os.path.basename(job['input']))[0]}.wav")
+        audio_io.save(path, out, sr, "pcm16" if args.pcm16 else "float32")
+        print(f"-> {path}")
+
+
+if __name__ == "__main__":
+    main()

@@ -577,19 +577,41 @@ __device__ __forceinline__ void seeds_publish(const SeedArgs& sa, const float* L
     }
 }
 
-template <bool COLLECT>
+// POOL (alive_knn_search_pool): frame block x of the launch belongs to ONE voice of a pool (PoolBlocks, filled on the device by
+// knn_pool_plan_kernel); the block searches that voice's image (lib + img_off[voice] rows, seg_len[voice] rows) cut into gridDim.y
+// splits, and its lists hold POOL row indices (seg_lo[voice] + row).  Blocks past the plan's count return at once.
+struct PoolBlocks {
+    const int* hdr;        // [PH_BLOCKS]: frame blocks of the plan
+    const int* blk_voice;  // [frame block] voice
+    const int64_t* img_off;
+    const int32_t* seg_lo;
+    const int32_t* seg_len;
+};
+enum { PH_GROUPS = 0, PH_BLOCKS, PH_ITEMS, PH_FAIL, PH_WORDS = 8 };
+
+template <bool COLLECT, bool POOL = false>
 __global__ __launch_bounds__(256, 1) void knn_score_kernel(const unsigned short* __restrict__ s_bf16,
                                                            const unsigned short* __restrict__ lib, int64_t M, int tiles_total,
                                                            int tiles_per_split, int P, float* __restrict__ cand_val,
                                                            int* __restrict__ cand_idx, const int* __restrict__ gate_cnt,
                                                            int gate_lo, int gate_hi, int by_count, const float* __restrict__ thr_in,
-                                                           SeedArgs sa, int caps) {
+                                                           SeedArgs sa, int caps, PoolBlocks pool = PoolBlocks{}) {
     int n_slots = 0x7fffffff;
     {
         int c;
         if (!gate_open(gate_cnt, gate_lo, gate_hi, c)) return;                       // block-uniform
         if (by_count && (int64_t)blockIdx.x * 256 >= c) return;                      // compacted frames: only c of them
         if (by_count) n_slots = c;
+    }
+    int row_base = 0;                                                                // POOL: pool index of the image's row 0
+    if constexpr (POOL) {
+        if ((int)blockIdx.x >= pool.hdr[PH_BLOCKS]) return;                          // block-uniform
+        const int v = pool.blk_voice[blockIdx.x];
+        M = pool.seg_len[v];
+        lib += (size_t)pool.img_off[v] * D;
+        tiles_total = (int)(((M + TILE - 1) / TILE * TILE) / LT);
+        tiles_per_split = (tiles_total + (int)gridDim.y - 1) / (int)gridDim.y;
+        row_base = pool.seg_lo[v];
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* Lv = (float*)(smem + 2 * ABUF);
@@ -765,7 +787,7 @@ __global__ __launch_bounds__(256, 1) void knn_score_kernel(const unsigned short*
                 }
                 if (has) {
                     lv[pos * 512] = mx;
-                    li[pos * 512] = (int)(row0 + (rsel & 3) + 8 * (rsel >> 2) + 4 * lh);
+                    li[pos * 512] = (int)(row0 + (rsel & 3) + 8 * (rsel >> 2) + 4 * lh) + (POOL ? row_base : 0);
                     thr[ni] = fminf(m2, mx);
                 }
                 // retire the inserted value and look for the next candidate of this lane
@@ -1558,7 +1580,18 @@ __device__ __forceinline__ int wave_argbest(float v, int idx) {
 //   * divisions by the norm through div_by (see there), four candidates' wave sums through wave_sum_frames (7 permutes instead of 24,
 //     bitwise the same sums), candidate broadcasts through v_readlane, the final top-k through DPP max / min.
 // Results are bit for bit what they were (same products, same summation trees, same tie-breaks).
-template <int PER>
+// POOL (alive_knn_search_pool): candidates are indexed by SLOT of the pool plan, frame_list = the plan's slot -> frame map (-1: a
+// padding slot, skipped), det_lib = the per-voice bounds, taken for the slot's voice; a frame that fails the certificate is listed
+// in its group's range of the fallback list (PoolRescore) instead of flag_list, which is not written.
+struct PoolRescore {
+    const int* slot_grp;   // [slot] group of the plan
+    const int* grp;        // [group][PG_FIELDS]
+    int* gfail;            // [group] frames of the group that failed the certificate
+    int* fb;               // [slot] fallback list: group g's failing slots at grp[g][PG_SLOT0] + 0 .. gfail[g] - 1
+};
+enum { PG_VOICE = 0, PG_MSTART, PG_SIZE, PG_BLK0, PG_NBLK, PG_CHUNKS, PG_NSLAB, PG_BASE, PG_FBASE, PG_FIELDS };
+
+template <int PER, bool POOL = false>
 __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_idx,
                                                           int P, int kp, const float* __restrict__ s_f32,
                                                           const float* __restrict__ rows, const float* __restrict__ norms,
@@ -1569,7 +1602,8 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
                                                           int list_len, float pre_scale, float sd_prior,
                                                           const float* __restrict__ det_q, const float* __restrict__ det_lib,
                                                           float* __restrict__ thr_list, int collect, float overflow_slack,
-                                                          const unsigned char* __restrict__ force_fail = nullptr) {
+                                                          const unsigned char* __restrict__ force_fail = nullptr,
+                                                          PoolRescore pool = PoolRescore{}) {
     // force_fail (fp6 stage): frames whose fp6 image clipped an element (|x| 2^5 > 7.5) -- their stage scores are off by more than
     // any error statistic of their candidates can show, so they go to the next tier whatever the certificate says
     __shared__ float cs_v[4][64];          // compaction of the selected candidates, one row per wave
@@ -1585,6 +1619,9 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
     }
     if (slot >= Tt || (frame_list != nullptr && slot >= gc)) return;
     const int64_t ft = frame_list != nullptr ? frame_list[slot] : slot;     // frame: source row and output row
+    if constexpr (POOL) {
+        if (ft < 0) return;                                                  // padding slot of the pool plan
+    }
     const int R = P * kp;                  // kp candidates per frame and split: KP (bf16 scoring) or KP8 (fp8 scoring)
     const float* cv = cand_val + (size_t)slot * R;
     const int* ci = cand_idx + (size_t)slot * R;
@@ -1611,7 +1648,8 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
     // Cauchy-Schwarz on the two rounding-error vectors, || q^ - bf16(q^) || (this frame, measured) + || bf16(q^) || *
     // max_R || r^ - bf16(r^) || (this library, measured) + the fp32 accumulation error of 768 exact products (<= 768 * 2^-23
     // * sum |q r| <= 9.3e-5) + the rounding of the rescoring arithmetic itself (< 3e-6): no statistics, no assumption.
-    const float det_bound = det_q != nullptr ? det_q[ft] + 1.004f * det_lib[0] + 1.0e-4f : 0.0f;
+    const float det_bound = det_q != nullptr ? det_q[ft] + 1.004f * det_lib[POOL ? pool.grp[pool.slot_grp[slot] * PG_FIELDS + PG_VOICE] : 0] + 1.0e-4f
+                                             : 0.0f;
     const float prune = !certify ? INFINITY
                                  : (det_q != nullptr ? 2.0f * det_bound : 2.0f * zsig * sd_prior) / pre_scale;     // in prefilter-score units
     if constexpr (PER == 0) {              // R <= 64: one candidate per lane as it stands
@@ -1861,7 +1899,14 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
     if (certify && lane == 0 && (c_cut > -INFINITY || forced)) {
         const float bound = det_q != nullptr ? c_cut * pre_scale + det_bound
                                              : c_cut * pre_scale - err_mu + fmaxf(zsig * err_sd, 2.0f * err_max);
-        if (!(vk > bound) || forced) {
+        if constexpr (POOL) {
+            if (!(vk > bound)) {
+                const int g = pool.slot_grp[slot];
+                const int pos = atomicAdd(pool.gfail + g, 1);
+                pool.fb[pool.grp[g * PG_FIELDS + PG_BLK0] * FT + pos] = (int)slot;
+                atomicAdd(flag_cnt, 1);
+            }
+        } else if (!(vk > bound) || forced) {
             // the frame goes to the next tier; for the collect tier it takes along the threshold below which no row can
             // belong to its top-k: its k-th exact cosine so far minus the slack it was just tested with (stage-score units)
             const int pos = atomicAdd(flag_cnt, 1);
@@ -2825,6 +2870,317 @@ static SeedArgs seeds_for(const SearchWs& w, int64_t fb, int split, int k, float
     return SeedArgs{w.tau, w.tau_flag, k, margin, w.stats + counter};
 }
 
+
+// ----------------------------------------------------------------------------------------------
+// pool search (many-to-many batch conversion): every batch row searches its own voice of a pool at the bf16 MFMA rate
+// ----------------------------------------------------------------------------------------------
+// alive_knn_search_pool is the strict search (bf16 candidate stage, exact rescoring, the DETERMINISTIC certificate, exact scan of
+// the frames that fail it) for a batch whose rows search different voices.  The voice table is device data, so a one-block
+// prologue turns it into a plan on the device and every grid is sized from N, T, k and the pool's dimensions (no host sync, one
+// launch per stage whatever the number of voices):
+//   groups   the rows of one voice (sorted by voice, then row): their frames, row-major, are cut into 256-frame blocks of that voice
+//            alone (knn_pool_gather_kernel compacts them into SLOTS: group g owns slots [blk0 * 256, (blk0 + nblk) * 256));
+//   splits   every voice's image is cut into gridDim.y tile ranges (empty ranges write empty lists);
+//   stage    knn_score_kernel<false, true> (the candidate stage of alive_knn_search_strict on the block's voice image), then
+//            knn_rescore_kernel<PER, true> with the frame's own voice's rounding bound;
+//   fallback the frames that fail the certificate, listed per group, are scanned exactly against their voice's fp32 rows in chunks of
+//            64 / k frames x slabs of the segment (the items of knn_grouped_scan_kernel) and merged by knn_grouped_merge_kernel's body.
+// Every score is the rescoring arithmetic: val and idx - seg_lo[voice[n]] are bitwise alive_knn_search_strict on the voice alone.
+constexpr int POOL_MAX_ROWS = 4096;       // batch rows one call takes (the prologue sorts them in LDS)
+constexpr int POOL_MAX_FRAMES = 1 << 20;  // N * T
+constexpr int POOL_MERGE_BLOCKS = 1024;
+
+struct PoolWs {
+    int* stats;                            // ALIVE_POOL_STATS words, first in the workspace
+    int* hdr;                              // [PH_WORDS]
+    float* s_f32; unsigned short* s_bf16; float* dq;
+    unsigned short* s_c;                   // [S][768] bf16 frames in slot order
+    float* cv; int* ci;                    // [S][P][KP] candidate lists
+    int* slot_frame; int* slot_grp;        // [S]
+    int* grp;                              // [N + 1][PG_FIELDS]
+    int* members;                          // [N] rows sorted by (voice, row); -1 past the active ones
+    int* blk_voice; int* blk_grp;          // [S / 256]
+    int* gfail;                            // [N]
+    int* fb;                               // [S]
+    float* pv; int* pi;                    // [items][64] partial lists of the fallback scan
+    int64_t S;                             // slots: 256 x (frame blocks the plan can need)
+    int P;                                 // library splits of the candidate stage
+    int64_t items;
+    size_t bytes;
+};
+
+static PoolWs pool_ws_layout(void* base, int N, int T, int k, int V, int64_t max_len) {
+    PoolWs w{};
+    const int64_t Tt = (int64_t)N * T;
+    const int64_t gmax = N < V ? N : V;                                 // groups: each adds at most one partial frame block
+    w.S = ((Tt + FT - 1) / FT + gmax) * FT;
+    w.P = make_plan(Tt, max_len).split;
+    const int F = 64 / k;
+    const int64_t chunks = (Tt + F - 1) / F + gmax;
+    w.items = chunks > GR_ITEMS ? chunks : GR_ITEMS;
+    Arena a(base);
+    w.stats = a.take<int>(ALIVE_POOL_STATS);
+    w.hdr = a.take<int>(PH_WORDS);
+    w.s_f32 = a.take<float>((size_t)Tt * D);
+    w.s_bf16 = a.take<unsigned short>((size_t)((Tt + 63) / 64 * 64) * D);
+    w.dq = a.take<float>((size_t)Tt);
+    w.s_c = a.take<unsigned short>((size_t)w.S * D);
+    w.cv = a.take<float>((size_t)w.S * w.P * KP);
+    w.ci = a.take<int>((size_t)w.S * w.P * KP);
+    w.slot_frame = a.take<int>((size_t)w.S);
+    w.slot_grp = a.take<int>((size_t)w.S);
+    w.grp = a.take<int>((size_t)(N + 1) * PG_FIELDS);
+    w.members = a.take<int>((size_t)N);
+    w.blk_voice = a.take<int>((size_t)(w.S / FT));
+    w.blk_grp = a.take<int>((size_t)(w.S / FT));
+    w.gfail = a.take<int>((size_t)N);
+    w.fb = a.take<int>((size_t)w.S);
+    w.pv = a.take<float>((size_t)w.items * 64);
+    w.pi = a.take<int>((size_t)w.items * 64);
+    w.bytes = a.used();
+    return w;
+}
+
+// image of one voice: lib[M_pad][768] = bf16(row / norm), zero rows to M_pad -- alive_library_pack's image of the voice alone
+// (the same division of the same operands: rows and norms of the pool are alive_library_pack_rows')
+__global__ __launch_bounds__(256) void pool_image_kernel(const float* __restrict__ rows, const float* __restrict__ norms, int64_t M,
+                                                         int64_t M_pad, unsigned short* __restrict__ lib) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M_pad * D) return;
+    const int64_t m = i / D;
+    const float q = m < M ? rows[i] / norms[m] : 0.0f;
+    lib[i] = f32_to_bf16_rn(q);
+}
+
+// one block: voice table -> groups (rows sorted by (voice, row) with a bitonic sort in LDS), frame blocks, members
+__global__ __launch_bounds__(1024) void knn_pool_plan_kernel(const int32_t* __restrict__ voice, int N, int T, const int32_t* __restrict__ seg_lo,
+                                                             const int32_t* __restrict__ seg_len, int V, int64_t P, int k, PoolWs w) {
+    __shared__ unsigned long long key[POOL_MAX_ROWS];
+    __shared__ int s_groups;
+    const int tid = threadIdx.x;
+    constexpr unsigned long long NONE = ~0ull;
+    int np = 1;
+    while (np < N) np <<= 1;
+    for (int n = tid; n < np; n += 1024) {
+        unsigned long long kk = NONE;
+        if (n < N) {
+            const int v = voice[n];
+            // a voice outside the table, outside the pool or shorter than k: an inactive row (val -inf, idx -1)
+            if (v >= 0 && v < V && seg_len[v] >= k && seg_lo[v] >= 0 && (int64_t)seg_lo[v] + seg_len[v] <= P)
+                kk = ((unsigned long long)v << 32) | (unsigned)n;
+        }
+        key[n] = kk;
+    }
+    __syncthreads();
+    for (int size = 2; size <= np; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < np; i += 1024) {
+                const int j = i ^ stride;
+                if (j > i) {
+                    const unsigned long long a = key[i], b = key[j];
+                    if ((a > b) == ((i & size) == 0)) { key[i] = b; key[j] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) {
+        int G = 0, blocks = 0;
+        for (int i = 0; i < N && key[i] != NONE;) {
+            const int v = (int)(key[i] >> 32);
+            int j = i + 1;
+            while (j < N && key[j] != NONE && (int)(key[j] >> 32) == v) ++j;
+            int* e = w.grp + G * PG_FIELDS;
+            const int nblk = (int)(((int64_t)(j - i) * T + FT - 1) / FT);
+            e[PG_VOICE] = v; e[PG_MSTART] = i; e[PG_SIZE] = j - i; e[PG_BLK0] = blocks; e[PG_NBLK] = nblk;
+            blocks += nblk;
+            ++G;
+            i = j;
+        }
+        w.hdr[PH_GROUPS] = G;
+        w.hdr[PH_BLOCKS] = blocks;
+        w.hdr[PH_ITEMS] = 0;
+        w.hdr[PH_FAIL] = 0;
+        w.stats[2] = G;
+        w.stats[3] = blocks;
+        s_groups = G;
+    }
+    __syncthreads();
+    for (int i = tid; i < N; i += 1024) w.members[i] = key[i] == NONE ? -1 : (int)(key[i] & 0xffffffffu);
+    const int G = s_groups;
+    __threadfence_block();
+    for (int g = tid; g < G; g += 1024) {
+        const int* e = w.grp + g * PG_FIELDS;
+        w.gfail[g] = 0;
+        for (int b = e[PG_BLK0]; b < e[PG_BLK0] + e[PG_NBLK]; ++b) { w.blk_voice[b] = e[PG_VOICE]; w.blk_grp[b] = g; }
+    }
+}
+
+// one block per slot: slot -> (frame, group), and the frame's bf16 row in slot order (zero rows for the padding slots)
+__global__ __launch_bounds__(128) void knn_pool_gather_kernel(int T, PoolWs w) {
+    const int64_t slot = blockIdx.x;
+    const int64_t b = slot / FT;
+    const int blocks = w.hdr[PH_BLOCKS];
+    int frame = -1, g = -1;
+    if (b < blocks) {
+        g = w.blk_grp[b];
+        const int* e = w.grp + g * PG_FIELDS;
+        const int64_t j = slot - (int64_t)e[PG_BLK0] * FT;
+        if (j < (int64_t)e[PG_SIZE] * T) frame = (int)((int64_t)w.members[e[PG_MSTART] + (int)(j / T)] * T + j % T);
+    }
+    if (threadIdx.x == 0) {
+        w.slot_frame[slot] = frame;
+        w.slot_grp[slot] = g;
+    }
+    if (b >= blocks || threadIdx.x >= 96) return;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (frame >= 0) v = ((const u32x4*)(w.s_bf16 + (size_t)frame * D))[threadIdx.x];
+    ((u32x4*)(w.s_c + (size_t)slot * D))[threadIdx.x] = v;
+}
+
+// frames of inactive rows: val -inf, idx -1 (the grouped search's convention)
+__global__ __launch_bounds__(256) void knn_pool_inactive_kernel(const int32_t* __restrict__ voice, int N, int T, const int32_t* __restrict__ seg_lo,
+                                                                const int32_t* __restrict__ seg_len, int V, int64_t P, int k,
+                                                                float* __restrict__ out_val, int* __restrict__ out_idx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)N * T * k) return;
+    const int v = voice[i / ((int64_t)T * k)];
+    if (v >= 0 && v < V && seg_len[v] >= k && seg_lo[v] >= 0 && (int64_t)seg_lo[v] + seg_len[v] <= P) return;
+    out_val[i] = -INFINITY;
+    out_idx[i] = -1;
+}
+
+// one block: per-group counts of the frames that failed the certificate -> fallback items (grouped-scan slabs x chunks)
+__global__ void knn_pool_fallback_plan_kernel(const int32_t* __restrict__ seg_len, int k, PoolWs w) {
+    if (threadIdx.x != 0) return;
+    const int G = w.hdr[PH_GROUPS], F = 64 / k;
+    int chunks_total = 0, fail = 0;
+    for (int g = 0; g < G; ++g) {
+        int* e = w.grp + g * PG_FIELDS;
+        const int c = w.gfail[g];
+        e[PG_FBASE] = fail;
+        e[PG_CHUNKS] = (c + F - 1) / F;
+        fail += c;
+        chunks_total += e[PG_CHUNKS];
+    }
+    const int per = chunks_total > 0 ? GR_ITEMS / chunks_total : 0;
+    int items = 0;
+    for (int g = 0; g < G; ++g) {
+        int* e = w.grp + g * PG_FIELDS;
+        int nslab = seg_len[e[PG_VOICE]] / GR_MIN_SLAB;
+        nslab = nslab < per ? nslab : per;
+        e[PG_NSLAB] = nslab < 1 ? 1 : nslab;
+        e[PG_BASE] = items;
+        items += e[PG_NSLAB] * e[PG_CHUNKS];
+    }
+    w.grp[G * PG_FIELDS + PG_BASE] = items;
+    w.grp[G * PG_FIELDS + PG_FBASE] = fail;
+    w.hdr[PH_ITEMS] = items;
+    w.hdr[PH_FAIL] = fail;
+    w.stats[1] = fail;
+}
+
+// the largest group m < G with grp[m][field] <= x (groups without items / failing frames share the next group's start)
+__device__ __forceinline__ int pool_group_of(const int* grp, int G, int field, int x) {
+    int a = 0, b = G - 1;
+    while (a < b) {
+        const int m = (a + b + 1) >> 1;
+        if (grp[m * PG_FIELDS + field] <= x) a = m;
+        else b = m - 1;
+    }
+    return a;
+}
+
+// one wave per fallback item: the rows of one slab of the voice against one chunk of its group's failing frames
+// (knn_grouped_scan_kernel's loop and arithmetic; pool row indices)
+__global__ __launch_bounds__(64 * SCAN_WAVES) void knn_pool_scan_kernel(const float* __restrict__ rows, const float* __restrict__ norms,
+                                                                        const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_len,
+                                                                        int k, PoolWs w) {
+    const int lane = threadIdx.x & 63;
+    const int nw = gridDim.x * SCAN_WAVES;
+    const int G = w.hdr[PH_GROUPS], items = w.hdr[PH_ITEMS];
+    const int F = 64 / k;
+    for (int it = blockIdx.x * SCAN_WAVES + (threadIdx.x >> 6); it < items; it += nw) {
+        const int g = pool_group_of(w.grp, G, PG_BASE, it);
+        const int* e = w.grp + g * PG_FIELDS;
+        const int chunks = e[PG_CHUNKS], nslab = e[PG_NSLAB], v = e[PG_VOICE];
+        const int64_t len = seg_len[v], lo = seg_lo[v];
+        const int r = it - e[PG_BASE];
+        const int slab = r / chunks, c = r - slab * chunks;
+        const int64_t r0 = lo + len * slab / nslab, r1 = lo + len * (slab + 1) / nslab;
+        const int left = w.gfail[g] - c * F;
+        const int nf = left < F ? left : F;
+        int my_ft = 0;
+        if (lane < nf) my_ft = w.slot_frame[w.fb[(int64_t)e[PG_BLK0] * FT + c * F + lane]];
+        const int my_t = lane / k;
+        const bool live = lane < nf * k;
+        float lv = -INFINITY;
+        int li = 0x7fffffff;
+        f32x4 n0 = {}, n1 = {}, n2 = {};
+        float nnx = 1.0f;
+        if (r0 < r1) {
+            const f32x4* rp = (const f32x4*)(rows + (size_t)r0 * D);
+            n0 = rp[lane]; n1 = rp[lane + 64]; n2 = rp[lane + 128];
+            nnx = norms[r0];
+        }
+        for (int64_t rr = r0; rr < r1; ++rr) {
+            f32x4 q0 = n0, q1 = n1, q2 = n2;
+            const float nn = nnx;
+            if (rr + 1 < r1) {
+                const f32x4* rp = (const f32x4*)(rows + (size_t)(rr + 1) * D);
+                n0 = rp[lane]; n1 = rp[lane + 64]; n2 = rp[lane + 128];
+                nnx = norms[rr + 1];
+            }
+            const NormDiv nd = norm_div(nn);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { q0[j] = div_by(q0[j], nd); q1[j] = div_by(q1[j], nd); q2[j] = div_by(q2[j], nd); }
+            float p = -INFINITY;
+            for (int t = 0; t < nf; ++t) {
+                const int ft = __shfl(my_ft, t);
+                const f32x4* sp = (const f32x4*)(w.s_f32 + (size_t)ft * D);
+                const f32x4 s0 = sp[lane], s1 = sp[lane + 64], s2 = sp[lane + 128];
+                float d = 0.0f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d = fmaf(s0[j], q0[j], d);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d = fmaf(s1[j], q1[j], d);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d = fmaf(s2[j], q2[j], d);
+                d = wave_sum(d);
+                if (live && t == my_t) p = d;
+            }
+            const int ri = (int)rr;
+            const bool before = lv > p || (lv == p && li < ri);
+            const float up_v = __shfl_up(lv, 1);
+            const int up_i = __shfl_up(li, 1);
+            const bool up_before = (lane % k == 0) ? true : (up_v > p || (up_v == p && up_i < ri));
+            if (live && !before) {
+                lv = up_before ? p : up_v;
+                li = up_before ? ri : up_i;
+            }
+        }
+        w.pv[(size_t)it * 64 + lane] = lv;
+        w.pi[(size_t)it * 64 + lane] = li;
+    }
+}
+
+// block-stride loop over the failing frames: the nslab lists of a frame's chunk -> its exact top-k (overwrites the rescored lists)
+template <bool K4>
+__global__ __launch_bounds__(256) void knn_pool_merge_kernel(int k, PoolWs w, float* __restrict__ out_val, int* __restrict__ out_idx) {
+    const int G = w.hdr[PH_GROUPS], fail = w.hdr[PH_FAIL];
+    const int F = 64 / k;
+    for (int i = blockIdx.x; i < fail; i += gridDim.x) {
+        const int g = pool_group_of(w.grp, G, PG_FBASE, i);
+        const int* e = w.grp + g * PG_FIELDS;
+        const int pos = i - e[PG_FBASE];
+        const int c = pos / F;
+        const int ft = w.slot_frame[w.fb[(int64_t)e[PG_BLK0] * FT + pos]];
+        const size_t off = (size_t)(e[PG_BASE] + c) * 64;
+        scan_merge_frame<K4>(w.pv + off, w.pi + off, (int64_t)e[PG_CHUNKS] * 64, e[PG_NSLAB], pos - c * F, k, 0, out_val, out_idx, ft);
+        __syncthreads();                                    // (the merge's LDS exchange is reused by the next frame)
+    }
+}
+
 }  // namespace
 
 extern "C" int64_t alive_library_padded_rows(int64_t M) { return (M + TILE - 1) / TILE * TILE; }
@@ -3345,5 +3701,104 @@ extern "C" int alive_knn_merge_gather_rows(const float* cand_val, const int32_t*
     knn_merge_gather_kernel<2, 8, true><<<g, 256, 0, (hipStream_t)stream>>>(cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T,
                                                                          (int64_t)N * T, out, final_idx, alpha);
     ALIVE_CHECK_LAUNCH("alive_knn_merge_gather_rows");
+    return ALIVE_OK;
+}
+
+// ---- pool search (many-to-many batch conversion) ----
+extern "C" size_t alive_pool_image_bytes(const int32_t* seg_len, int V, int64_t* img_off) {
+    if (seg_len == nullptr || V < 1) return 0;
+    int64_t rows = 0;
+    for (int v = 0; v < V; ++v) {
+        if (seg_len[v] < 1) return 0;
+        if (img_off != nullptr) img_off[v] = rows;
+        rows += alive_library_padded_rows(seg_len[v]);
+    }
+    return (size_t)rows * D * sizeof(unsigned short);
+}
+
+extern "C" int alive_pool_pack_images(const float* rows_f32, const float* norms, int64_t P, const int32_t* seg_lo, const int32_t* seg_len,
+                                      int V, void* images, float* bounds, void* stream) {
+    ALIVE_CHECK_ARG(rows_f32 && norms && seg_lo && seg_len && images && bounds, "alive_pool_pack_images: null pointer");
+    ALIVE_CHECK_ARG(V >= 1 && P >= 1 && P < ((int64_t)1 << 31), "alive_pool_pack_images: V=%d, P=%lld", V, (long long)P);
+    for (int v = 0; v < V; ++v)
+        ALIVE_CHECK_ARG(seg_len[v] >= 1 && seg_lo[v] >= 0 && (int64_t)seg_lo[v] + seg_len[v] <= P,
+                        "alive_pool_pack_images: voice %d: segment [%d, +%d) outside the pool of %lld rows", v, seg_lo[v], seg_len[v], (long long)P);
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipMemsetAsync(bounds, 0, (size_t)V * sizeof(float), s);
+    int64_t off = 0;
+    for (int v = 0; v < V; ++v) {
+        const int64_t M = seg_len[v], M_pad = alive_library_padded_rows(M);
+        unsigned short* lib = (unsigned short*)images + (size_t)off * D;
+        const float* rows = rows_f32 + (size_t)seg_lo[v] * D;
+        pool_image_kernel<<<(unsigned)((M_pad * D + 255) / 256), 256, 0, s>>>(rows, norms + seg_lo[v], M, M_pad, lib);
+        lib_rounding_bound_kernel<<<(unsigned)((M + 3) / 4), 256, 0, s>>>(lib, rows, norms + seg_lo[v], M, (unsigned*)(bounds + v));
+        off += M_pad;
+    }
+    ALIVE_CHECK_LAUNCH("alive_pool_pack_images");
+    return ALIVE_OK;
+}
+
+static bool pool_args_ok(int N, int T, int k, int V, int64_t P, int64_t max_len) {
+    return N >= 1 && N <= POOL_MAX_ROWS && T >= 1 && (int64_t)N * T <= POOL_MAX_FRAMES && k >= 1 && k <= KH && V >= 1 && P >= 1 &&
+           P < ((int64_t)1 << 31) && max_len >= 1 && max_len <= P;
+}
+
+extern "C" size_t alive_knn_pool_workspace_bytes(int N, int T, int k, int V, int64_t P, int64_t max_len) {
+    if (!pool_args_ok(N, T, k, V, P, max_len)) return 0;
+    return pool_ws_layout(nullptr, N, T, k, V, max_len).bytes;
+}
+
+extern "C" const int* alive_knn_pool_stats(void* ws) { return (const int*)ws; }
+
+extern "C" int alive_knn_search_pool(const float* src, int N, int T, const void* images, const int64_t* img_off, const float* rows_f32,
+                                     const float* norms, const float* bounds, int64_t P, const int32_t* seg_lo, const int32_t* seg_len, int V,
+                                     int64_t max_len, const int32_t* voice, int k, float* out_val, int32_t* out_idx, void* ws, void* stream) {
+    ALIVE_CHECK_ARG(src && images && img_off && rows_f32 && norms && bounds && seg_lo && seg_len && voice && out_val && out_idx && ws,
+                    "alive_knn_search_pool: null pointer");
+    ALIVE_CHECK_ARG(k >= 1 && k <= KH, "alive_knn_search_pool: k=%d outside [1,%d]", k, KH);
+    ALIVE_CHECK_ARG(N >= 1 && N <= POOL_MAX_ROWS, "alive_knn_search_pool: N=%d outside [1,%d]", N, POOL_MAX_ROWS);
+    ALIVE_CHECK_ARG(T >= 1 && (int64_t)N * T <= POOL_MAX_FRAMES, "alive_knn_search_pool: N*T=%lld outside [1,%d]", (long long)N * T,
+                    POOL_MAX_FRAMES);
+    ALIVE_CHECK_ARG(V >= 1 && P >= 1 && P < ((int64_t)1 << 31), "alive_knn_search_pool: V=%d voices, pool of %lld rows", V, (long long)P);
+    ALIVE_CHECK_ARG(max_len >= 1 && max_len <= P, "alive_knn_search_pool: longest voice %lld outside [1, %lld]", (long long)max_len,
+                    (long long)P);
+    if (int rc = lds_optin("alive_knn_search_pool")) return rc;
+    static LdsOptIn optin_pool;
+    if (optin_pool.ensure({(const void*)knn_score_kernel<false, true>}, SCORE_LDS) != hipSuccess) {
+        alive_set_error("alive_knn_search_pool: cannot reserve %d B of LDS", SCORE_LDS);
+        return ALIVE_ERR_LAUNCH;
+    }
+    const PoolWs w = pool_ws_layout(ws, N, T, k, V, max_len);
+    const int64_t Tt = (int64_t)N * T;
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipMemsetAsync(w.stats, 0, ALIVE_POOL_STATS * sizeof(int), s);
+    knn_pool_inactive_kernel<<<(unsigned)((Tt * k + 255) / 256), 256, 0, s>>>(voice, N, T, seg_lo, seg_len, V, P, k, out_val, out_idx);
+    // frames: the strict search's preparation (the same kernel choice by frame count: bitwise the same s_f32 and bound share)
+    if (Tt <= 512) src_prep_small_kernel<<<(unsigned)Tt, 256, 0, s>>>(src, T, Tt, w.s_f32, w.s_bf16, w.dq);
+    else src_prep_kernel<<<(unsigned)((Tt + 63) / 64), 256, 0, s>>>(src, T, Tt, (Tt + 63) / 64 * 64, w.s_f32, w.s_bf16, w.dq);
+    knn_pool_plan_kernel<<<1, 1024, 0, s>>>(voice, N, T, seg_lo, seg_len, V, P, k, w);
+    knn_pool_gather_kernel<<<(unsigned)w.S, 128, 0, s>>>(T, w);
+    const PoolBlocks pb{w.hdr, w.blk_voice, img_off, seg_lo, seg_len};
+    knn_score_kernel<false, true><<<dim3((unsigned)(w.S / FT), w.P), 256, SCORE_LDS, s>>>(
+        w.s_c, (const unsigned short*)images, 0, 0, 0, w.P, w.cv, w.ci, nullptr, 0, 0, 0, nullptr, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, 0,
+        pb);
+    const PoolRescore pr{w.slot_grp, w.grp, w.gfail, w.fb};
+    const int R = w.P * KP;
+#define ALIVE_POOL_RESCORE(PER_)                                                                                                   \
+    knn_rescore_kernel<PER_, true><<<(unsigned)(w.S / 4), 256, 0, s>>>(w.cv, w.ci, w.P, KP, w.s_f32, rows_f32, norms, w.S, 0, k,     \
+                                                                     out_val, out_idx, w.slot_frame, nullptr, 0, 0, w.fb, w.stats, \
+                                                                     CERT_Z, KH, 1.0f, SD_PRIOR16, w.dq, bounds, nullptr, 0, 0.0f, \
+                                                                     nullptr, pr)
+    if (R <= 64) ALIVE_POOL_RESCORE(0);
+    else if (R <= 192) ALIVE_POOL_RESCORE(3);
+    else if (R <= 256) ALIVE_POOL_RESCORE(4);
+    else if (R <= 512) ALIVE_POOL_RESCORE(8);
+    else ALIVE_POOL_RESCORE(16);
+#undef ALIVE_POOL_RESCORE
+    knn_pool_fallback_plan_kernel<<<1, 64, 0, s>>>(seg_len, k, w);
+    knn_pool_scan_kernel<<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, seg_lo, seg_len, k, w);
+    if (k <= 4) knn_pool_merge_kernel<true><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
+    else knn_pool_merge_kernel<false><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
+    ALIVE_CHECK_LAUNCH("alive_knn_search_pool");
     return ALIVE_OK;
 }

@@ -88,6 +88,44 @@ class VoicePool:
             raise ValueError(f"voice pool row {int(torch.nonzero(bad)[0])} has zero or non-finite norm: remove it")
         self.rows, self.norms, self.P, self.segments = rows, norms, P, segs
         self.version += 1
+        self._images = None
+
+    def search_images(self):
+        """The pool search's tables, built on first use for this version of the pool (the streaming path never asks):
+        a dict of the bf16 image buffer, device int64 img_off [V], int32 seg_lo / seg_len [V], float32 bounds [V] (the
+        deterministic certificate's per-voice rounding bound), the voice names in table order, and the longest voice."""
+        if self._images is not None:
+            return self._images
+        L = nat.lib()
+        names = list(self.segments)
+        V = len(names)
+        if V == 0:
+            raise ValueError("the voice pool is empty")
+        lo = np.array([self.segments[n][0] for n in names], dtype=np.int32)
+        ln = np.array([self.segments[n][1] for n in names], dtype=np.int32)
+        off = np.zeros(V, dtype=np.int64)
+        nbytes = L.alive_pool_image_bytes(ln.ctypes.data, V, off.ctypes.data)
+        if nbytes == 0:
+            raise ValueError("voice pool: bad segment table")
+        images = torch.empty(nbytes // 2, dtype=torch.int16, device=self.device)
+        bounds = torch.empty(V, dtype=torch.float32, device=self.device)
+        nat.check(L.alive_pool_pack_images(nat.ptr(self.rows), nat.ptr(self.norms), self.P, lo.ctypes.data, ln.ctypes.data, V,
+                                           nat.ptr(images), nat.ptr(bounds), nat.stream()), "alive_pool_pack_images")
+        dev = self.device
+        self._images = dict(images=images, img_off=torch.from_numpy(off).to(dev), seg_lo=torch.from_numpy(lo).to(dev),
+                            seg_len=torch.from_numpy(ln).to(dev), bounds=bounds, names=names, index={n: i for i, n in enumerate(names)},
+                            max_len=int(ln.max()))
+        return self._images
+
+    def voice_ids(self, names):
+        """voice names (None: an inactive row) -> device int32 [N] indices of the pool search's table"""
+        index = self.search_images()["index"]
+        ids = []
+        for n in names:
+            if n is not None and n not in index:
+                raise ValueError(f"unknown voice {n!r} (the pool holds {sorted(index)})")
+            ids.append(-1 if n is None else index[n])
+        return torch.tensor(ids, dtype=torch.int32, device=self.device)
 
 
 def knn_search_grouped(source, rows, norms, seg_lo, seg_len, k):
@@ -105,6 +143,39 @@ def knn_search_grouped(source, rows, norms, seg_lo, seg_len, k):
     nat.check(L.alive_knn_search_grouped(nat.ptr(source), n, t, nat.ptr(rows), nat.ptr(norms), rows.shape[0], nat.ptr(seg_lo),
                                          nat.ptr(seg_len), k, nat.ptr(val), nat.ptr(idx), nat.ptr(ws), nat.stream()),
               "alive_knn_search_grouped")
+    return val, idx
+
+
+def knn_pool_workspace_bytes(n, t, k, pool):
+    im = pool.search_images()
+    return nat.lib().alive_knn_pool_workspace_bytes(n, t, k, len(im["names"]), pool.P, im["max_len"])
+
+
+def knn_search_pool(source, pool, voice_ids, k, stats=False):
+    """source [N, 768, T], a VoicePool, device int32 voice_ids [N] (-1: inactive) -> (val [N*T, k], idx [N*T, k] pool indices):
+    the strict search of every row against its own voice in one call (csrc/knn.hip: alive_knn_search_pool).  stats=True also
+    returns the call's counters (a host copy: a sync)."""
+    n, d, t = source.shape
+    L = nat.lib()
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"pool search: k={k} outside [1, {MAX_K}]")
+    im = pool.search_images()
+    nbytes = knn_pool_workspace_bytes(n, t, k, pool)
+    if nbytes == 0:                                         # (before anything is allocated)
+        raise ValueError(f"pool search: {n} rows x {t} frames (k={k}) out of range")
+    if voice_ids.dtype != torch.int32 or voice_ids.numel() != n:
+        raise ValueError("pool search: voice_ids must be int32 [N]")
+    source = source.contiguous()
+    val = torch.empty(n * t, k, dtype=torch.float32, device=source.device)
+    idx = torch.empty(n * t, k, dtype=torch.int32, device=source.device)
+    ws = _ws.get(nbytes, source.device)
+    nat.check(L.alive_knn_search_pool(nat.ptr(source), n, t, nat.ptr(im["images"]), nat.ptr(im["img_off"]), nat.ptr(pool.rows),
+                                      nat.ptr(pool.norms), nat.ptr(im["bounds"]), pool.P, nat.ptr(im["seg_lo"]), nat.ptr(im["seg_len"]),
+                                      len(im["names"]), im["max_len"], nat.ptr(voice_ids), k, nat.ptr(val), nat.ptr(idx), nat.ptr(ws),
+                                      nat.stream()), "alive_knn_search_pool")
+    if stats:                                               # knn.hip alive_knn_pool_stats: int[ALIVE_POOL_STATS] at the front of ws
+        c = ws[:32].view(torch.int32).tolist()
+        return val, idx, dict(frames_failed_certificate=c[0], frames_searched_exactly=c[1], voice_groups=c[2], frame_blocks=c[3])
     return val, idx
 
 

@@ -323,6 +323,110 @@ class Converter:
             kw["share_overlap"] = n if ok else None
         return stitch(self.convert_windows(windows, keep_frames=keep, **kw), total, chunk)       # (the guard sits in convert_windows)
 
+    def convert_many(self, utterances, pool, voices, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, alpha=0.0, chunk=48000, k=4,
+                     window_batch=64, trim_context=False):
+        """Many-to-many batch conversion: utterance i (16 kHz, [L] or [1, L], any length) to voice voices[i] of `pool`
+        (module/multistream.py: VoicePool), with per-utterance pitch_shift / intonation / f0_rate / alpha (a scalar applies to
+        every utterance).  Returns one [1, L_i] waveform per utterance.  The windows of ALL utterances form one batch (a network
+        batch may span utterances), and the match is ONE pool search over every window's frames, each window against its own
+        voice (csrc/knn.hip: alive_knn_search_pool).  Utterance i comes out bitwise as `convert` with
+        PackedLibrary(voice, strict=True) makes it alone -- unless the fp16 range guard repeats the batch on bf16 planes: that
+        repeat covers the whole batch, so its composition then matters (ops.Fp16Guard)."""
+        from . import multistream as MS
+        m = len(utterances)
+        voices = list(voices)
+        if len(voices) != m:
+            raise ValueError(f"{m} utterances but {len(voices)} voices")
+        if not 1 <= k <= MS.MAX_K:
+            raise ValueError(f"convert_many: k={k} outside [1, {MS.MAX_K}]")
+
+        def per(x, what):
+            xs = list(x) if isinstance(x, (list, tuple)) else [x] * m
+            if len(xs) != m:
+                raise ValueError(f"{what}: {len(xs)} values for {m} utterances")
+            return [float(v) for v in xs]
+        shifts, inton, rates, alphas = (per(pitch_shift, "pitch_shift"), per(intonation, "intonation"), per(f0_rate, "f0_rate"),
+                                        per(alpha, "alpha"))
+        for name in voices:
+            if pool.segment(name)[1] < k:
+                raise ValueError(f"voice {name!r} has {pool.segment(name)[1]} vectors, fewer than k={k}")
+        wins, totals, counts = [], [], []
+        for u in utterances:
+            u = u.reshape(1, -1).to(self.device, torch.float32)
+            w, total = make_windows(u, chunk)
+            wins.append(w)
+            totals.append(total)
+            counts.append(w.shape[0])
+        windows = torch.cat(wins).contiguous()
+        rep = torch.tensor(counts, device=self.device)
+
+        def rows(vals, dtype):
+            return torch.repeat_interleave(torch.tensor(vals, dtype=dtype, device=self.device), rep).contiguous()
+        params = dict(ids=torch.repeat_interleave(pool.voice_ids(voices), rep).contiguous(), alpha=rows(alphas, torch.float64),
+                      shift=rows(shifts, torch.float32), inton=rows(inton, torch.float32), rate=rows(rates, torch.float32))
+        keep = (chunk // 320, 2 * chunk // 320) if trim_context else None
+        out = ops.Fp16Guard(self._agree_on_saturations()).run(
+            lambda: self._convert_many_windows(windows, pool, params, k, window_batch, keep))
+        res, i = [], 0
+        for c, total in zip(counts, totals):
+            res.append(stitch(out[i:i + c], total, chunk))
+            i += c
+        return res
+
+    def _convert_many_windows(self, windows, pool, p, k, window_batch, keep_frames):
+        """`_convert_windows` (per-window front end) with per-window voice, alpha and pitch parameters"""
+        from . import multistream as MS
+        n, L = windows.shape
+        lf = L // 320
+        rng = None if keep_frames is None else (max(0, keep_frames[0] - TRIM_LEFT), min(lf, keep_frames[1] + TRIM_RIGHT))
+        feat = torch.empty(n, 768, lf, device=windows.device)
+        f0 = torch.empty(n, 1, lf, device=windows.device)
+
+        def batches(fn):
+            cur = torch.cuda.current_stream()
+            side = self._side_streams(windows.device)
+            for j, i in enumerate(range(0, n, window_batch)):
+                if not side:
+                    fn(i)
+                    continue
+                st = side[j % len(side)]
+                st.wait_stream(cur)
+                with torch.cuda.stream(st):
+                    fn(i)
+            for st in side:
+                cur.wait_stream(st)
+
+        def enc(i):
+            sl = slice(i, i + window_batch)
+            if rng is None:
+                ops.front_end(windows[sl], self.ce, self.pe, out=(feat[sl], f0[sl]))
+                return
+            spec = spectrogram(windows[sl])
+            f0[sl] = self.pe.estimate(spec)
+            a, b = max(0, rng[0] - CE_MARGIN), min(lf, rng[1] + CE_MARGIN)
+            fe = torch.zeros(spec.shape[0], 768, lf, device=spec.device)
+            fe[:, :, a:b] = self.ce(spec[:, :, a:b].contiguous())
+            feat[sl] = fe
+        batches(enc)
+        MS.pitch_transform_rows_(f0, 0, p["rate"], p["shift"], p["inton"])
+        src = feat if rng is None else feat[:, :, rng[0]:rng[1]].contiguous()
+        val, idx = MS.knn_search_pool(src, pool, p["ids"], k)
+        matched = MS.merge_gather_rows(val, idx, k, p["alpha"], pool.rows, src)
+        if rng is None:
+            out = torch.empty_like(windows)
+
+            def dec(i):
+                self.dec(matched[i:i + window_batch], f0[i:i + window_batch], out=out[i:i + window_batch])
+            batches(dec)
+            return out
+        out = torch.zeros_like(windows)
+
+        def dec_range(i):
+            out[i:i + window_batch, rng[0] * 320:rng[1] * 320] = self.dec.forward_range(
+                matched[i:i + window_batch], f0[i:i + window_batch], rng[0])
+        batches(dec_range)
+        return out
+
     @staticmethod
     def check_fp16_range():
         """For callers of the LOW-LEVEL ops (ContentEncoder / Decoder objects called directly): raises when a value left fp16's range

@@ -226,6 +226,36 @@ int alive_knn_merge_gather_rows(const float* cand_val, const int32_t* cand_idx, 
                                 const float* rows_f32_full, const float* src, int N, int T, float* out,
                                 int32_t* final_idx, void* stream);
 
+/* ---------------------------------------------- pool search (many-to-many batch conversion) ----
+ * A pool of V voices: fp32 rows_f32[P][768] / norms[P] from alive_library_pack_rows (voice v = rows [seg_lo[v], seg_lo[v] +
+ * seg_len[v])), plus one bf16 IMAGE per voice in the layout of alive_library_pack (padded to alive_library_padded_rows rows),
+ * the images at consecutive tile-aligned offsets of one buffer, and a rounding bound per voice.
+ * alive_pool_image_bytes: bytes of the image buffer for HOST seg_len[V] (0 on a bad table); img_off (HOST int64[V], may be NULL)
+ *   receives each image's first row.
+ * alive_pool_pack_images: fills the images and bounds (DEVICE float[V]: alive_library_rounding_bound of each voice alone), from the
+ *   pool's rows and norms; seg_lo / seg_len are HOST int32[V].  One small launch pair per voice (packing is not on the hot path).
+ * alive_knn_search_pool: exact top-k (1 <= k <= 8) of every frame of src[N][768][T] against the voice of its row: voice[n]
+ *   (DEVICE int32[N]) indexes the DEVICE tables img_off[V] (int64, image rows), seg_lo[V], seg_len[V] and bounds[V].
+ *   out_val / out_idx [N*T][k]: val and idx - seg_lo[voice[n]] are bitwise alive_knn_search_strict on the voice packed alone, and
+ *   so bitwise alive_knn_search_grouped on the same segments (ties to the lower row); idx is a POOL index.  A row whose voice is
+ *   -1, outside the table, or shorter than k gets val -inf, idx -1.  The strict search's stages with a plan built on the device
+ *   (no host sync, one launch per stage whatever V): bf16 candidate stage per (256-frame block of one voice, library split),
+ *   exact rescoring with the deterministic certificate (the frame's own voice's bound), exact fp32 scan of the frames that fail.
+ *   Limits: N <= 4096, N * T <= 2^20, P < 2^31; max_len = the longest voice (sizes the library splits).
+ *   ws: alive_knn_pool_workspace_bytes(N, T, k, V, P, max_len) bytes (0: arguments out of range).
+ * alive_knn_pool_stats: device int[ALIVE_POOL_STATS] inside ws, the last call's counters: [0] frames that failed the certificate,
+ *   [1] frames that ended in the exact scan, [2] voice groups, [3] 256-frame blocks of the candidate stage. */
+#define ALIVE_POOL_STATS 8
+size_t alive_pool_image_bytes(const int32_t* seg_len, int V, int64_t* img_off);
+int alive_pool_pack_images(const float* rows_f32, const float* norms, int64_t P, const int32_t* seg_lo, const int32_t* seg_len,
+                           int V, void* images, float* bounds, void* stream);
+size_t alive_knn_pool_workspace_bytes(int N, int T, int k, int V, int64_t P, int64_t max_len);
+int alive_knn_search_pool(const float* src, int N, int T, const void* images, const int64_t* img_off, const float* rows_f32,
+                          const float* norms, const float* bounds, int64_t P, const int32_t* seg_lo, const int32_t* seg_len,
+                          int V, int64_t max_len, const int32_t* voice, int k, float* out_val, int32_t* out_idx, void* ws,
+                          void* stream);
+const int* alive_knn_pool_stats(void* ws);
+
 /* alive_dedup_pass: one pass of the greedy de-duplication of a library (generate_voice_library.py of this build, --dedup):
  * frame i is dropped iff a KEPT earlier frame among its k nearest (val / idx[M][k] = alive_knn_search of the library
  * against itself) has cosine > threshold.  state[M]: 0 undecided, 1 kept, 2 dropped (zero it before the first pass);

@@ -1,0 +1,114 @@
+"""Many-to-many batch conversion: the pool search against the alternatives on the same batch, and convert_many end to end.
+
+    python tools/bench_many_to_many.py [--reps 3] [--out many_to_many_bench.json]
+
+Batch: bench.synth_windows(64, 10 s) = 384 windows x 450 frames = 172 800 content-encoder frames (ContentEncoder(seed=2)); utterance
+u's 6 windows search voice u % V.  Voices: V in {1, 8, 64} distinct voices of M in {512, 50 000} rows (i.i.d. Gaussian tokens).
+Every time is event-timed on the current stream after one warm-up call, mean of --reps calls:
+  (a) alive_knn_search_pool, one call (module/multistream.py: knn_search_pool);
+  (b) alive_knn_search_grouped, one call on the same segments;
+  (c) a per-voice loop of PackedLibrary(strict=True).search over that voice's windows (libraries packed beforehand);
+  ref alive_knn_search_strict of the whole batch against ONE M-row voice (same FLOPs as (a)).
+End to end at V = 64, M = 50 000: convert_many of the 64 utterances against 64 sequential Converter.convert calls (each with its
+voice's strict PackedLibrary, packed beforehand), trim_context on (the CLI default).
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import torch
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, os.path.join(ROOT, "alive-vc_amd"))
+sys.path.insert(0, ROOT)
+
+import bench                                                      # noqa: E402
+from module import multistream as MS                              # noqa: E402
+from module.common import PackedLibrary                           # noqa: E402
+
+DEV = torch.device("cuda")
+N_UTT, SECONDS, CHUNK, K = 64, 10.0, 48000, 4
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also write the results as JSON to this file")
+    ap.add_argument("--commit", default="", help="source commit to record (default: git rev-parse HEAD, when there is a .git)")
+    args = ap.parse_args()
+    from module.content_encoder import ContentEncoder
+    from module.decoder import Decoder
+    from module.f0_estimator import F0Estimator
+    from module.pipeline import Converter
+    conv = Converter(ContentEncoder(seed=2), F0Estimator(seed=2), Decoder(seed=2), DEV)
+    windows = bench.synth_windows(N_UTT, SECONDS, CHUNK, DEV, seed=300)
+    n = windows.shape[0]
+    per_utt = n // N_UTT
+    feat = torch.empty(n, 768, windows.shape[1] // 320, device=DEV)
+    for i in range(0, n, 64):
+        feat[i:i + 64] = conv.features(windows[i:i + 64])[0]
+    torch.cuda.synchronize()
+    T = feat.shape[2]
+    commit = args.commit or subprocess.run(["git", "rev-parse", "HEAD"], cwd=ROOT, capture_output=True, text=True).stdout.strip()
+    res = dict(commit=commit,
+               batch=dict(windows=n, frames=n * T, k=K), search=[], end_to_end=None)
+    g = torch.Generator(device=DEV).manual_seed(7)
+    for M in (512, 50_000):
+        toks = {f"v{j}": torch.randn(768, M, device=DEV, generator=g) for j in range(64)}
+        one = PackedLibrary(toks["v0"], strict=True)
+        t_ref = timed(lambda: one.search(feat, K), args.reps)
+        for V in (1, 8, 64):
+            pool = MS.VoicePool({f"v{j}": toks[f"v{j}"] for j in range(V)}, device=DEV)
+            names = [f"v{(w // per_utt) % V}" for w in range(n)]
+            ids = pool.voice_ids(names)
+            lo = torch.tensor([pool.segment(x)[0] for x in names], dtype=torch.int32, device=DEV)
+            ln = torch.tensor([pool.segment(x)[1] for x in names], dtype=torch.int32, device=DEV)
+            t_pool = timed(lambda: MS.knn_search_pool(feat, pool, ids, K), args.reps)
+            _, _, st = MS.knn_search_pool(feat, pool, ids, K, stats=True)
+            t_grp = timed(lambda: MS.knn_search_grouped(feat, pool.rows, pool.norms, lo, ln, K), args.reps)
+            libs = [PackedLibrary(toks[f"v{j}"], strict=True) for j in range(V)]
+            rows_of = [torch.tensor([w for w in range(n) if (w // per_utt) % V == j], device=DEV) for j in range(V)]
+            srcs = [feat[r].contiguous() for r in rows_of]
+            t_loop = timed(lambda: [lib.search(s, K) for lib, s in zip(libs, srcs)], args.reps)
+            row = dict(V=V, M=M, pool_ms=round(t_pool, 3), grouped_ms=round(t_grp, 3), per_voice_loop_ms=round(t_loop, 3),
+                       strict_one_voice_ms=round(t_ref, 3), pool_over_strict_one_voice=round(t_pool / t_ref, 3), pool_stats=st)
+            print(json.dumps(row), flush=True)
+            res["search"].append(row)
+    # end to end: 64 utterances, 64 voices of 50 000 rows
+    sig = bench.synth_signals(N_UTT, int(SECONDS * 16000), DEV, 300)
+    toks = {f"v{j}": torch.randn(768, 50_000, device=DEV, generator=g) for j in range(N_UTT)}
+    pool = MS.VoicePool(toks, device=DEV)
+    names = [f"v{u}" for u in range(N_UTT)]
+    utts = [sig[u:u + 1] for u in range(N_UTT)]
+    libs = {x: PackedLibrary(toks[x], strict=True) for x in names}
+
+    def seq():
+        for u, x in zip(utts, names):
+            conv.set_library(libs[x])
+            conv.convert(u, chunk=CHUNK, k=K, trim_context=True)
+    t_many = timed(lambda: conv.convert_many(utts, pool, names, chunk=CHUNK, k=K, trim_context=True), args.reps)
+    t_seq = timed(seq, args.reps)
+    res["end_to_end"] = dict(utterances=N_UTT, voices=N_UTT, M=50_000, convert_many_ms=round(t_many, 2),
+                             sequential_convert_ms=round(t_seq, 2), speedup=round(t_seq / t_many, 2))
+    print(json.dumps(res["end_to_end"]), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
