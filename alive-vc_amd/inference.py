@@ -73,8 +73,6 @@ def main(argv=None):
     device = torch.device(args.device)
     if device.type != "cuda":
         raise SystemExit("this build runs on the MI355X only: pass -d cuda (the reference's spelling for ROCm devices)")
-    if args.world_pitch_estimation:
-        raise SystemExit("-wpe needs pyworld (WORLD), which is outside this build's scope")
 
     PE, CE, Dec = F0Estimator().to(device), ContentEncoder().to(device), Decoder().to(device)
     PE.load_state_dict(torch.load(args.f0_estimator_path, map_location=device))
@@ -106,7 +104,7 @@ def main(argv=None):
         wf = wf.mean(dim=0, keepdim=True)
         print(f"-> {path}")
         out = conv.convert(wf, chunk=args.chunk, k=args.k, alpha=args.alpha, pitch_shift=args.pitch,
-                           intonation=args.intonation, f0_rate=args.f0_rate, window_batch=args.window_batch,
+                           world_pitch=bool(args.world_pitch_estimation), intonation=args.intonation, f0_rate=args.f0_rate, window_batch=args.window_batch,
                            trim_context=not args.no_trim_context,
                            share_overlap=None if args.no_share_overlap else "auto")
         out = audio_io.resample(out, 16000, sr, post_gain_db=args.gain).cpu()      # resample, then gain (:136-137)

@@ -1,6 +1,8 @@
 """Drop-in for the inference-time surface of the reference's module/common.py.
 
   match_features(source, reference, k=4, alpha=0.0)   <- /root/reference/module/common.py:96-109
+  compute_f0_dio(wf, sample_rate=8000, ...)           <- module/common.py:113-130 (pyworld.dio + stonemask, `-wpe`)
+  compute_f0(wf, sample_rate=16000, segment_size=320) <- module/common.py:133-137
 
 runs on the MI355X through libalive_vc.so: fp6- (or fp8- / bf16-) MFMA candidate scoring with
 LDS-staged top-k' lists, exact fp32 rescoring, gather-mean-blend.  The library
@@ -352,3 +354,74 @@ def match_features(source, reference, k=4, alpha=0.0, return_indices=False):
             idxs.append(r[1])
     out = torch.cat(outs, 0)
     return (out, torch.cat(idxs, 0)) if return_indices else out
+
+
+# ---- WORLD pitch estimation (`-wpe`): DIO + StoneMask in fp64 on the device (csrc/world_f0.hip, DESIGN.md "WORLD pitch") ----------
+_world_taps = {}
+_world_ws = nat.Workspace()
+
+
+def _world_taps_for(fs, f0_min, f0_max, device):
+    """DIO's filter taps (built on the host by the library, uploaded once per device and rate)"""
+    key = (int(fs), float(f0_min), float(f0_max), str(device))
+    taps = _world_taps.get(key)
+    if taps is None:
+        L = nat.lib()
+        n = L.alive_world_f0_taps_count(int(fs), float(f0_min), float(f0_max))
+        if n <= 0:
+            raise ValueError(f"WORLD f0: unsupported rate {fs} / f0 range [{f0_min}, {f0_max}]")
+        host = torch.empty(n, dtype=torch.float64)
+        nat.check(L.alive_world_f0_taps(int(fs), float(f0_min), float(f0_max), host.data_ptr()), "alive_world_f0_taps")
+        taps = host.to(device)
+        torch.cuda.current_stream(device).synchronize()         # once per rate: other streams will read it
+        _world_taps[key] = taps
+    return taps
+
+
+def world_f0(x, sample_rate=8000, f0_min=20.0, f0_max=4096.0, frame_period=5.0):
+    """pyworld.stonemask(x, *pyworld.dio(x, sample_rate, f0_floor=f0_min, f0_ceil=f0_max, frame_period=frame_period)) of every
+    row of x [N, L] (float32 on the device), in float64 -> float32 [N, F], F = int(1000 L / sample_rate / frame_period) + 1"""
+    if x.dim() != 2:
+        raise ValueError(f"world_f0 expects [N, L] rows, got {tuple(x.shape)}")
+    x = x.contiguous().float()
+    N, L8 = x.shape
+    lib = nat.lib()
+    args = (int(sample_rate), float(f0_min), float(f0_max), float(frame_period))
+    nbytes = lib.alive_world_f0_workspace_bytes(N, L8, *args)
+    if nbytes == 0:
+        raise ValueError(f"world_f0: unsupported arguments (rows {N}, length {L8}, rate {sample_rate}, f0 [{f0_min}, {f0_max}])")
+    taps = _world_taps_for(sample_rate, f0_min, f0_max, x.device)
+    out = torch.empty(N, lib.alive_world_f0_frames(L8, int(sample_rate), float(frame_period)), device=x.device)
+    ws = _world_ws.get(nbytes, x.device)
+    nat.check(lib.alive_world_f0(nat.ptr(x), N, L8, *args, nat.ptr(taps), nat.ptr(out), nat.ptr(ws), ws.numel(), nat.stream()),
+              "alive_world_f0")
+    return out
+
+
+def linear_resize(x, size):
+    """F.interpolate(x, size, mode='linear') (align_corners=False) of x [..., Lin] on the device, rounded as torch's CPU kernel"""
+    if size <= 0:
+        raise ValueError(f"linear_resize: output size {size} must be positive")
+    shape = x.shape
+    xr = x.reshape(-1, shape[-1]).contiguous().float()
+    y = torch.empty(xr.shape[0], int(size), device=x.device)
+    nat.check(nat.lib().alive_linear_resize(nat.ptr(xr), xr.shape[0], xr.shape[1], nat.ptr(y), int(size), nat.stream()),
+              "alive_linear_resize")
+    return y.reshape(shape[:-1] + (int(size),))
+
+
+def compute_f0_dio(wf, sample_rate=8000, segment_size=256, f0_min=20, f0_max=4096):
+    """reference module/common.py:113-130: wf [L] -> [1, L // segment_size]; wf [N, L] -> [N, 1, L // segment_size]"""
+    if wf.dim() not in (1, 2):
+        raise ValueError(f"compute_f0_dio expects [L] or [N, L], got {tuple(wf.shape)}")
+    rows = wf[None] if wf.dim() == 1 else wf
+    f0 = linear_resize(world_f0(rows, sample_rate, f0_min, f0_max), rows.shape[1] // segment_size)
+    return f0 if wf.dim() == 1 else f0[:, None]
+
+
+def compute_f0(wf, sample_rate=16000, segment_size=320):
+    """reference module/common.py:133-137: wf [N, L] at sample_rate -> f0 [N, 1, L // segment_size] (8-kHz DIO + StoneMask)"""
+    from . import audio_io
+    l = wf.shape[1]
+    wf8 = audio_io.resample(wf, sample_rate, 8000)
+    return linear_resize(compute_f0_dio(wf8, 8000), l // segment_size)

@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .common import PackedLibrary, merge_gather
+from .common import PackedLibrary, compute_f0, merge_gather
 from .content_encoder import ContentEncoder
 from .decoder import Decoder
 from .f0_estimator import F0Estimator
@@ -81,11 +81,27 @@ class Converter:
         self.library = tokens if isinstance(tokens, PackedLibrary) else PackedLibrary(tokens[0].to(self.device))
         return self
 
-    def features(self, windows, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, frames=None, out=None):
+    def features(self, windows, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, frames=None, out=None, world_pitch=False):
         """spectrogram -> f0 (+ per-window pitch transform) and content features   (inference.py:112-128).
         frames = (lo, hi): content features are only needed on [lo, hi) (context trimming): the encoder runs on that range
         plus its own receptive field; the other frames come back as zeros.  f0 always covers the whole window (the pitch
-        transform uses the window's mean pitch, the oscillator accumulates phase from the first frame)."""
+        transform uses the window's mean pitch, the oscillator accumulates phase from the first frame).
+        world_pitch: f0 is WORLD's DIO + StoneMask of each whole window (common.compute_f0, reference inference.py:113-114) and the
+        f0 estimator does not run."""
+        if world_pitch:
+            f0 = ops.pitch_transform_(compute_f0(windows), 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
+            spec = spectrogram(windows)
+            lf = spec.shape[2]
+            if frames is None:
+                feat = self.ce(spec)
+            else:
+                a, b = max(0, frames[0] - CE_MARGIN), min(lf, frames[1] + CE_MARGIN)
+                feat = torch.zeros(spec.shape[0], 768, lf, device=spec.device)
+                feat[:, :, a:b] = self.ce(spec[:, :, a:b].contiguous())
+            if out is not None:
+                out[0].copy_(feat)
+                out[1].copy_(f0)
+            return feat, f0
         if frames is None:                 # the whole window: one fused call, no fp32 spectrogram (ops.front_end, SURVEY 8 f1)
             feat, f0 = ops.front_end(windows, self.ce, self.pe, out=out)     # out = (feat, f0) batch slices to write into
             return feat, ops.pitch_transform_(f0, 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
@@ -205,13 +221,16 @@ class Converter:
         return None                       # one process, one decision (ShardedConverter: max over the ranks)
 
     def _convert_windows(self, windows, k=4, alpha=0.0, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, window_batch=64,
-                         keep_frames=None, share_overlap=None):
+                         keep_frames=None, share_overlap=None, world_pitch=False):
         """windows [n, L] on the device -> waveforms [n, L]; L a multiple of 320.
         Networks run in batches of `window_batch` windows (bounded scratch); the kNN match runs ONCE over the frames
         of all windows, so every library tile streamed from L2 is used by as many frames as possible.
         keep_frames = (a, b): the caller keeps only the output of frames [a, b) of every window (inference.py keeps the
         centre third).  The match is then restricted to the frames that can reach them through the decoder; the kept
-        samples are bitwise the same as without it (the other frames of the window decode from unmatched features)."""
+        samples are bitwise the same as without it (the other frames of the window decode from unmatched features).
+        world_pitch=True: f0 is WORLD's (DIO + StoneMask) of every whole window instead of the f0 estimator's, as `-wpe` does
+        (reference inference.py:113-114); WORLD is not local (mean removal and contour fixing span the window), so overlap
+        sharing is not used with it (the per-window path gives the same samples) and trimming applies to the content only."""
         n, L = windows.shape
         lf = L // 320
         # (the edge blocks of all windows form one launch of n x 30 frame columns: below 96 columns the library would switch
@@ -220,7 +239,7 @@ class Converter:
         rng = None if keep_frames is None else (max(0, keep_frames[0] - TRIM_LEFT), min(lf, keep_frames[1] + TRIM_RIGHT))
         # sharing and trimming together need the trimmed range to consist of interior frames of the signal (it does for the
         # centre third of a 3-chunk window from 46 frames per chunk on); otherwise trimming alone is used -- same samples
-        share_ok = bool(share_overlap) and n * (EDGE + NET_MARGIN) >= 96
+        share_ok = bool(share_overlap) and n * (EDGE + NET_MARGIN) >= 96 and not world_pitch
         if share_ok and (rng is None or (EDGE <= rng[0] and rng[1] <= lf - EDGE and rng[1] - rng[0] >= 5)):
             # share_overlap = windows per signal (make_windows order): front end once per signal, decoder per window
             feat, f0 = self.features_shared(windows, int(share_overlap), k, alpha, frames=rng)
@@ -269,10 +288,11 @@ class Converter:
         def enc(i):
             if rng is None:                                 # the networks write straight into the batch's slices
                 self.features(windows[i:i + window_batch], pitch_shift, intonation, f0_rate,
-                              out=(feat[i:i + window_batch], f0[i:i + window_batch]))
+                              out=(feat[i:i + window_batch], f0[i:i + window_batch]), world_pitch=world_pitch)
                 return
             feat[i:i + window_batch], f0[i:i + window_batch] = self.features(windows[i:i + window_batch], pitch_shift,
-                                                                           intonation, f0_rate, frames=rng)
+                                                                           intonation, f0_rate, frames=rng,
+                                                                           world_pitch=world_pitch)
         batches(enc)
         if rng is None:
             feat = self.match(feat, k, alpha)

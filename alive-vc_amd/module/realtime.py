@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import audio_io, ops
-from .common import PackedLibrary, merge_gather
+from .common import PackedLibrary, compute_f0, merge_gather
 from .spectrogram import spectrogram
 
 
@@ -48,7 +48,7 @@ def reuse_rows(frames):
 class RealtimeConverter:
     def __init__(self, content_encoder, f0_estimator, decoder, library_tokens, device="cuda", chunk=960, buffersize=8,
                  input_sr=16000, output_sr=16000, f0_rate=1.0, pitch=0.0, k=4, alpha=0.0, gain=0.0, input_gain=0.0,
-                 reuse_interior="auto"):
+                 reuse_interior="auto", world_pitch=False):
         self.device = torch.device(device)
         self.ce, self.pe, self.dec = content_encoder.to(device), f0_estimator.to(device), decoder.to(device)
         for net in (self.ce, self.pe, self.dec):
@@ -79,6 +79,13 @@ class RealtimeConverter:
         self._blk = reuse_block(frames, self.shift) if (input_sr == 16000 and chunk % 320 == 0 and
                                                         (chunk * buffersize) % 320 == 0) else None
         fits = self._blk is not None
+        # world_pitch (`-wpe`): f0 is WORLD's DIO + StoneMask of the whole ring (module/common.py compute_f0), whose mean removal
+        # and contour fixing span the ring -- no frame of it can be kept from the previous step, so interior reuse is off
+        self.world_pitch = bool(world_pitch)
+        if reuse_interior is True and self.world_pitch:
+            raise ValueError("interior reuse cannot be combined with world_pitch: WORLD's f0 of a ring depends on the whole ring")
+        if self.world_pitch:
+            fits = False
         if reuse_interior is True and not fits:
             raise ValueError("interior reuse needs input_sr 16000, chunk a multiple of 320 and a ring of at least 70 + chunk / 320 "
                              f"frames (below 96 frames: 33 + chunk / 320 < 96); got {frames} frames: see module/realtime.py")
@@ -98,7 +105,7 @@ class RealtimeConverter:
             return self._device_step_reuse(data, phi)
         data = audio_io.resample(data, self.input_sr, 16000, post_gain_db=self.input_gain)     # resample, then gain (:146-147)
         spec = spectrogram(data)
-        f0, join = self._f0_on_side_stream(spec)
+        f0, join = self._f0_on_side_stream(spec, data)
         content = self.ce(spec)
         val, idx = self.lib.search(content, self.k)
         content = merge_gather(val, idx, 1, self.k, self.alpha, self.lib.rows, content)
@@ -108,7 +115,7 @@ class RealtimeConverter:
         wave = audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain)[0]         # gain, then resample (:173-175)
         return wave, phi_out[:, :, self.end_of_output]
 
-    def _f0_on_side_stream(self, spec):
+    def _f0_on_side_stream(self, spec, data=None):
         """The f0 estimator (+ the pitch transform) needs nothing but the spectrogram and feeds nothing before the decoder: its ~35
         dependent launches run on a side stream beside the content encoder and the match (a step is a chain of ~150 small kernels,
         bound by their latencies, not by the chip).  Returns (f0, join): the f0 tensor -- a persistent buffer per shape (at most
@@ -116,7 +123,9 @@ class RealtimeConverter:
         nothing on the side stream (the estimator's scratch is sized by the eager warm-up steps that precede hipGraph capture:
         enable_graph) -- and the call that makes the current stream wait for it.  The buffer is overwritten by the next call with
         the same shape: `last_f0` of the non-reuse step aliases it and is valid until the next step.  Same kernels, same results;
-        captured into the step's hipGraph as a parallel branch."""
+        captured into the step's hipGraph as a parallel branch.  With world_pitch the branch is WORLD's f0 of the 16-kHz ring
+        `data` instead, and the pitch transform leaves out f0_rate: the reference multiplies only the estimator's f0 by it
+        (realtime_inference.py:153-156)."""
         cur = torch.cuda.current_stream(spec.device)
         if self._side is None:
             self._side = torch.cuda.Stream(device=spec.device)
@@ -129,8 +138,12 @@ class RealtimeConverter:
         side = self._side
         side.wait_stream(cur)                                   # the spectrogram is complete
         with torch.cuda.stream(side):
-            f0 = self.pe.estimate(spec, out=buf)
-            f0 = ops.pitch_transform_(f0, 1, f0_rate=self.f0_rate, pitch_shift=self.pitch)
+            if self.world_pitch:
+                buf.copy_(compute_f0(data))
+                f0 = ops.pitch_transform_(buf, 1, f0_rate=1.0, pitch_shift=self.pitch)
+            else:
+                f0 = self.pe.estimate(spec, out=buf)
+                f0 = ops.pitch_transform_(f0, 1, f0_rate=self.f0_rate, pitch_shift=self.pitch)
         return f0, (lambda: cur.wait_stream(side))
 
     def _front_end(self, data):

@@ -66,8 +66,8 @@ def main(argv=None):
         os.environ["ALIVE_KNN_STRICT"] = "1"              # read by module/common.py when the library is packed
     if args.device != 'cuda' or not torch.cuda.is_available():
         raise SystemExit("Error: this build needs a ROCm device: pass -d cuda on an MI355X host.")
-    if args.fp16 or args.world_pitch_estimation:
-        raise SystemExit("-fp16 (documented deprecated upstream) and -wpe (pyworld) are outside this build's scope")
+    if args.fp16:
+        raise SystemExit("-fp16 (documented deprecated upstream) is outside this build's scope")
     device = torch.device('cuda')
     PE, CE, Dec = F0Estimator().to(device), ContentEncoder().to(device), Decoder().to(device)
     PE.load_state_dict(torch.load(args.f0_estimator_path, map_location=device))
@@ -90,7 +90,8 @@ def main(argv=None):
 
     rt = RealtimeConverter(CE, PE, Dec, tgt.contiguous(), device, chunk=args.chunk, buffersize=args.buffersize,
                            input_sr=args.input_sr, output_sr=args.output_sr, f0_rate=args.f0_rate, pitch=args.pitch,
-                           k=args.k, alpha=args.alpha, gain=args.gain, input_gain=args.input_gain)
+                           k=args.k, alpha=args.alpha, gain=args.gain, input_gain=args.input_gain,
+                           world_pitch=bool(args.world_pitch_estimation))   # -wpe: WORLD f0, -f0 not applied (as the reference)
     if not args.no_graph:
         rt.enable_graph()        # the whole per-chunk device pipeline (~150 launches) captured once, replayed per chunk: same samples
     print("streaming: conversion running (Ctrl-C stops)")

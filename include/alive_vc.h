@@ -642,6 +642,25 @@ int alive_pitch_transform(float* f0, int N, int T, int mode, float f0_rate, floa
 int alive_pitch_transform_rows(float* f0, int N, int T, int mode, const float* f0_rate, const float* pitch_shift,
                                const float* intonation, void* stream);
 
+/* WORLD pitch estimation (`-wpe`): DIO + StoneMask on N rows of L8 samples at fs, in fp64   (reference module/common.py:113-137,
+ * pyworld.dio(x, fs, f0_floor, f0_ceil, channels_in_octave=2, frame_period, speed=1, allowed_range=0.1) then pyworld.stonemask).
+ * Restated from the published algorithm (tools/world_ref.py is the NumPy restatement; parity with pyworld is unpinned).
+ *   alive_world_f0_frames      F = int(1000 L8 / fs / frame_period) + 1 frames per row
+ *   alive_world_f0_taps        HOST call: fills host_taps[alive_world_f0_taps_count(...)] doubles with DIO's filter taps (low cut,
+ *                              then one Nuttall low-pass per band), cosines from the C library; upload once, pass as `taps`
+ *   alive_world_f0             x8 [N][L8] fp32 -> f0_out [N][F] fp32 (0 = unvoiced); workspace of
+ *                              alive_world_f0_workspace_bytes(N, L8, fs, f0_floor, f0_ceil, frame_period) bytes (0: bad args).
+ *                              fs <= 16000; the lowest band's low-pass may have at most 1024 taps (fs / f0_floor <= ~724)
+ *   alive_linear_resize        y [rows][Lout] = torch F.interpolate(x [rows][Lin], Lout, mode='linear', align_corners=False) as
+ *                              torch's CPU kernel rounds it (float32, fused multiply-adds where it fuses)                      */
+int alive_world_f0_frames(int L8, int fs, double frame_period);
+int alive_world_f0_taps_count(int fs, double f0_floor, double f0_ceil);
+int alive_world_f0_taps(int fs, double f0_floor, double f0_ceil, double* host_taps);
+size_t alive_world_f0_workspace_bytes(int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period);
+int alive_world_f0(const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
+                   const double* taps, float* f0_out, void* ws, size_t ws_bytes, void* stream);
+int alive_linear_resize(const float* x, int rows, int Lin, float* y, int Lout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
