@@ -7,10 +7,13 @@ The jobs file is a JSON list; each entry:
                                                             inference.py's order, the target's frames first)
    "pitch": 0, "intonation": 1, "f0_rate": 1, "alpha": 0,   optional, inference.py's -p / -int / -f0 / -a
    "gain": 1, "normalize": false,                           optional, inference.py's -g / -norm
+   "world_pitch": false,                                    optional, a JSON bool: inference.py's -wpe (WORLD's f0 of each
+                                                            window; pitch, intonation and f0_rate apply to it)
    "output": "a_out.wav"}                                   optional: default <outdir>/<index>_<input name>.wav
 Jobs naming the same voice sources share one voice of the pool.  Every file keeps inference.py's edges: loaded, resampled to
 16 kHz, normalised by its maximum, mono mean; the output resampled back to the file's own rate, gain, optional normalisation.
-Each output is bitwise what `inference.py --knn-strict` writes for that file, voice and settings.
+Each output is bitwise what `inference.py --knn-strict` (with `-wpe True` for a WORLD job) writes for that file, voice and
+settings; WORLD and estimator jobs mix freely in one run.
 Flags shared with inference.py keep its spelling: -c, -k, -d, -dep, -cep, -f0ep, --window-batch, --pcm16, --no-trim-context.
 """
 import argparse
@@ -25,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from module import audio_io                                     # noqa: E402
 from module.multistream import MAX_K                             # noqa: E402
 
-JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "output")
+JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "world_pitch", "output")
 
 
 def build_parser():
@@ -65,9 +68,12 @@ def load_jobs(path, k=4):
             raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: {JOB_KEYS})")
         if j.get("target") is None and j.get("lib") is None:
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
+        if not isinstance(j.get("world_pitch", False), bool):
+            raise ValueError(f"job {i}: \"world_pitch\" must be true or false, got {j['world_pitch']!r}")
         e = dict(input=rel(j["input"]), target=rel(j.get("target")), lib=rel(j.get("lib")), output=rel(j.get("output")),
                  pitch=float(j.get("pitch", 0.0)), intonation=float(j.get("intonation", 1.0)), f0_rate=float(j.get("f0_rate", 1.0)),
-                 alpha=float(j.get("alpha", 0.0)), gain=float(j.get("gain", 1.0)), normalize=bool(j.get("normalize", False)))
+                 alpha=float(j.get("alpha", 0.0)), gain=float(j.get("gain", 1.0)), normalize=bool(j.get("normalize", False)),
+                 world_pitch=j.get("world_pitch", False))
         for key in ("input", "target", "lib"):
             if e[key] is not None and not os.path.isfile(e[key]):
                 raise ValueError(f"job {i}: {key} {e[key]!r} does not exist")
@@ -139,7 +145,7 @@ def main(argv=None):
     conv = Converter(CE, PE, Dec, device)
     outs = conv.convert_many(utts, pool, [names[voice_key(j)] for j in jobs], pitch_shift=[j["pitch"] for j in jobs],
                              intonation=[j["intonation"] for j in jobs], f0_rate=[j["f0_rate"] for j in jobs],
-                             alpha=[j["alpha"] for j in jobs], chunk=args.chunk, k=args.k, window_batch=args.window_batch,
+                             alpha=[j["alpha"] for j in jobs], world_pitch=[j["world_pitch"] for j in jobs], chunk=args.chunk, k=args.k, window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)
     for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
         out = audio_io.resample(out, 16000, sr, post_gain_db=job["gain"]).cpu()

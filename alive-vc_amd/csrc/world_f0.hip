@@ -78,9 +78,11 @@ int plan(WfPlan& p, int N, int L, int fs, double f0_floor, double f0_ceil, doubl
 int taps_count(const WfPlan& p) { return p.woff[p.nb - 1] + 4 * p.h[p.nb - 1]; }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) wf_mean_kernel(const float* __restrict__ x, int L, double* __restrict__ mean) {
+__global__ void __launch_bounds__(256) wf_mean_kernel(const float* __restrict__ x, int L, const int32_t* __restrict__ row_on,
+                                                     double* __restrict__ mean) {
     __shared__ double acc[256];
     const int r = blockIdx.x, t = threadIdx.x;
+    if (row_on && !row_on[r]) return;                       // (uniform across the block)
     const float* xr = x + (int64_t)r * L;
     double a = 0.0;
     for (int i = t; i < L; i += 256) a = a + (double)xr[i];
@@ -96,9 +98,10 @@ __global__ void __launch_bounds__(256) wf_mean_kernel(const float* __restrict__ 
 // yl[n] = sum_{j=0}^{2c} lc[j] y[n - (j - c)], n in [-c, Ly + c), y = x - mean on [0, L), -mean at L, 0 elsewhere
 __global__ void __launch_bounds__(256) wf_lowcut_kernel(const float* __restrict__ x, const double* __restrict__ mean,
                                                         const double* __restrict__ lc, int L, int c, int64_t ld,
-                                                        double* __restrict__ yl) {
+                                                        const int32_t* __restrict__ row_on, double* __restrict__ yl) {
     __shared__ double ys[256 + 2 * 400];
     const int r = blockIdx.y, t = threadIdx.x;
+    if (row_on && !row_on[r]) return;
     const int n0 = (int)blockIdx.x * 256 - c;               // first output lag of the block
     const float* xr = x + (int64_t)r * L;
     const double m = mean[r];
@@ -119,13 +122,15 @@ __device__ inline double fine_edge(int e, double a, double b) { return (double)e
 
 // one block per (band, row)
 __global__ void __launch_bounds__(WF_BT) wf_bands_kernel(const double* __restrict__ yl_all, const double* __restrict__ taps,
-                                                         WfPlan p, double* __restrict__ iv_all, int* __restrict__ ni_all) {
+                                                         WfPlan p, const int32_t* __restrict__ row_on, double* __restrict__ iv_all,
+                                                         int* __restrict__ ni_all) {
     __shared__ double ybuf[WF_TILE + WF_MAX_NUTTALL];
     __shared__ double sbuf[WF_TILE + 2];
     __shared__ double ebuf[4][WF_TILE + 3];
     __shared__ int cnt[4][4][4];                // [round][wave][stream]
     __shared__ int tile_n[4];
     const int b = blockIdx.x, r = blockIdx.y, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    if (row_on && !row_on[r]) return;
     const int h = p.h[b], nt = 4 * h, Ly = p.Ly, F = p.F;
     const double fs = (double)p.fs;
     const double* w = taps + p.woff[b];
@@ -260,11 +265,13 @@ __device__ inline double select_best(const double* cand, int64_t bstride, int nb
     return fabs(1.0 - cv / ref) > allowed ? 0.0 : cv;
 }
 
-__global__ void __launch_bounds__(64) wf_select_kernel(WfPlan p, double* __restrict__ iv_all, const int* __restrict__ ni_all,
+__global__ void __launch_bounds__(64) wf_select_kernel(WfPlan p, const int32_t* __restrict__ row_on, double* __restrict__ iv_all,
+                                                       const int* __restrict__ ni_all,
                                                        double* __restrict__ best_all, double* __restrict__ s1_all,
                                                        double* __restrict__ s2_all, double* __restrict__ s3_all,
                                                        int* __restrict__ pi_all, int* __restrict__ ng_all) {
     const int r = blockIdx.x, lane = threadIdx.x, F = p.F, nb = p.nb;
+    if (row_on && !row_on[r]) return;
     double* iv = iv_all + (int64_t)r * nb * 4 * F;
     const int* ni = ni_all + (int64_t)r * nb * 4;
     double* best = best_all + (int64_t)r * F;
@@ -391,11 +398,15 @@ __device__ double fix_f0(const double* mw, const double* dw, int m, int n, doubl
 }
 
 __global__ void __launch_bounds__(128) wf_stone_kernel(const float* __restrict__ x8, WfPlan p, const double* __restrict__ dio_all,
-                                                       float* __restrict__ out) {
+                                                       const int32_t* __restrict__ row_on, float* __restrict__ out) {
     __shared__ double mwin[2][WF_MAX_WIN], dwin[2][WF_MAX_WIN];
     const int r = blockIdx.y, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int f = blockIdx.x * 2 + wv;
     if (f >= p.F) return;
+    if (row_on && !row_on[r]) {                             // an off row: unvoiced, nothing read
+        if (lane == 0) out[(int64_t)r * p.F + f] = 0.0f;
+        return;
+    }
     const int L = p.L;
     const double fs = (double)p.fs;
     const float* x = x8 + (int64_t)r * L;
@@ -505,15 +516,18 @@ extern "C" size_t alive_world_f0_workspace_bytes(int N, int L8, int fs, double f
     return p.total;
 }
 
-extern "C" int alive_world_f0(const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
-                              const double* taps, float* f0_out, void* ws, size_t ws_bytes, void* stream) {
+namespace {
+
+// row_on == nullptr: every row
+int world_f0_launch(const char* who, const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
+                    const double* taps, const int32_t* row_on, float* f0_out, void* ws, size_t ws_bytes, void* stream) {
     WfPlan p;
-    ALIVE_CHECK_ARG(x8 && taps && f0_out && ws, "alive_world_f0: null pointer");
+    ALIVE_CHECK_ARG(x8 && taps && f0_out && ws, "%s: null pointer", who);
     const int pr = plan(p, N, L8, fs, f0_floor, f0_ceil, frame_period);
-    ALIVE_CHECK_ARG(pr == 0, "alive_world_f0: bad args (N %d, L8 %d, fs %d, f0 range [%g, %g], frame period %g; fs <= 16000, at most "
-                    "%d bands, lowest band <= %d taps)", N, L8, fs, f0_floor, f0_ceil, frame_period, WF_MAX_BANDS, WF_MAX_NUTTALL);
-    ALIVE_CHECK_ARG(ws_bytes >= p.total, "alive_world_f0: workspace of %zu bytes, %zu needed", ws_bytes, p.total);
-    ALIVE_CHECK_ARG(2 * p.c + 1 <= 801, "alive_world_f0: low cut of %d taps exceeds 801", 2 * p.c + 1);
+    ALIVE_CHECK_ARG(pr == 0, "%s: bad args (N %d, L8 %d, fs %d, f0 range [%g, %g], frame period %g; fs <= 16000, at most "
+                    "%d bands, lowest band <= %d taps)", who, N, L8, fs, f0_floor, f0_ceil, frame_period, WF_MAX_BANDS, WF_MAX_NUTTALL);
+    ALIVE_CHECK_ARG(ws_bytes >= p.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, p.total);
+    ALIVE_CHECK_ARG(2 * p.c + 1 <= 801, "%s: low cut of %d taps exceeds 801", who, 2 * p.c + 1);
     hipStream_t s = (hipStream_t)stream;
     char* w = (char*)ws;
     double* mean = (double*)(w + p.off_mean);
@@ -524,13 +538,31 @@ extern "C" int alive_world_f0(const float* x8, int N, int L8, int fs, double f0_
     double* s1 = (double*)(w + p.off_s1);
     double* s2 = (double*)(w + p.off_s2);
     double* s3 = (double*)(w + p.off_s3);
-    wf_mean_kernel<<<N, 256, 0, s>>>(x8, L8, mean);
-    wf_lowcut_kernel<<<dim3(cdiv(p.yl_ld, 256), N), 256, 0, s>>>(x8, mean, taps, L8, p.c, p.yl_ld, yl);
-    wf_bands_kernel<<<dim3(p.nb, N), WF_BT, 0, s>>>(yl, taps, p, iv, ni);
-    wf_select_kernel<<<N, 64, 0, s>>>(p, iv, ni, best, s1, s2, s3, (int*)(w + p.off_pi), (int*)(w + p.off_ng));
-    wf_stone_kernel<<<dim3(cdiv(p.F, 2), N), 128, 0, s>>>(x8, p, s3, f0_out);
-    ALIVE_CHECK_LAUNCH("alive_world_f0");
+    wf_mean_kernel<<<N, 256, 0, s>>>(x8, L8, row_on, mean);
+    wf_lowcut_kernel<<<dim3(cdiv(p.yl_ld, 256), N), 256, 0, s>>>(x8, mean, taps, L8, p.c, p.yl_ld, row_on, yl);
+    wf_bands_kernel<<<dim3(p.nb, N), WF_BT, 0, s>>>(yl, taps, p, row_on, iv, ni);
+    wf_select_kernel<<<N, 64, 0, s>>>(p, row_on, iv, ni, best, s1, s2, s3, (int*)(w + p.off_pi), (int*)(w + p.off_ng));
+    wf_stone_kernel<<<dim3(cdiv(p.F, 2), N), 128, 0, s>>>(x8, p, s3, row_on, f0_out);
+    ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
+}
+
+}  // namespace
+
+extern "C" int alive_world_f0(const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
+                              const double* taps, float* f0_out, void* ws, size_t ws_bytes, void* stream) {
+    return world_f0_launch("alive_world_f0", x8, N, L8, fs, f0_floor, f0_ceil, frame_period, taps, nullptr, f0_out, ws, ws_bytes,
+                           stream);
+}
+
+// the rows whose row_on[r] (device int32 [N]) is nonzero: bitwise alive_world_f0 of those rows; the others get 0 (unvoiced) at every
+// frame and touch nothing else.  Every kernel tests the row of its block first, so a captured call serves any mask.
+extern "C" int alive_world_f0_rows(const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
+                                   const double* taps, const int32_t* row_on, float* f0_out, void* ws, size_t ws_bytes,
+                                   void* stream) {
+    ALIVE_CHECK_ARG(row_on, "alive_world_f0_rows: null row mask");
+    return world_f0_launch("alive_world_f0_rows", x8, N, L8, fs, f0_floor, f0_ceil, frame_period, taps, row_on, f0_out, ws,
+                           ws_bytes, stream);
 }
 
 extern "C" int alive_linear_resize(const float* x, int rows, int Lin, float* y, int Lout, void* stream) {

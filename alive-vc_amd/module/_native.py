@@ -143,6 +143,7 @@ PROTOTYPES = {
     "alive_world_f0_taps": (_I, [_I, _D, _D, _VP]),
     "alive_world_f0_workspace_bytes": (_SZ, [_I, _I, _I, _D, _D, _D]),
     "alive_world_f0": (_I, [_VP, _I, _I, _I, _D, _D, _D, _VP, _VP, _VP, _SZ, _VP]),
+    "alive_world_f0_rows": (_I, [_VP, _I, _I, _I, _D, _D, _D, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "alive_linear_resize": (_I, [_VP, _I, _I, _VP, _I, _VP]),
 }
 

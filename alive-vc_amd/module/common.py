@@ -3,6 +3,7 @@
   match_features(source, reference, k=4, alpha=0.0)   <- /root/reference/module/common.py:96-109
   compute_f0_dio(wf, sample_rate=8000, ...)           <- module/common.py:113-130 (pyworld.dio + stonemask, `-wpe`)
   compute_f0(wf, sample_rate=16000, segment_size=320) <- module/common.py:133-137
+  compute_f0_rows(wf, row_on)                         compute_f0 of the rows a device mask switches on (the batched paths)
 
 runs on the MI355X through libalive_vc.so: fp6- (or fp8- / bf16-) MFMA candidate scoring with
 LDS-staged top-k' lists, exact fp32 rescoring, gather-mean-blend.  The library
@@ -398,6 +399,28 @@ def world_f0(x, sample_rate=8000, f0_min=20.0, f0_max=4096.0, frame_period=5.0):
     return out
 
 
+def world_f0_rows(x, row_on, sample_rate=8000, f0_min=20.0, f0_max=4096.0, frame_period=5.0):
+    """world_f0 of the rows of x [N, L] whose row_on[r] (device int32 [N]) is nonzero, bitwise; the other rows come back 0
+    (unvoiced) and cost a block that returns at once.  The mask is read on the device: a captured call serves any mask"""
+    if x.dim() != 2:
+        raise ValueError(f"world_f0_rows expects [N, L] rows, got {tuple(x.shape)}")
+    if row_on.dtype != torch.int32 or row_on.numel() != x.shape[0] or not row_on.is_contiguous():
+        raise ValueError(f"world_f0_rows: row_on must be a contiguous int32 [{x.shape[0]}] mask")
+    x = x.contiguous().float()
+    N, L8 = x.shape
+    lib = nat.lib()
+    args = (int(sample_rate), float(f0_min), float(f0_max), float(frame_period))
+    nbytes = lib.alive_world_f0_workspace_bytes(N, L8, *args)
+    if nbytes == 0:
+        raise ValueError(f"world_f0_rows: unsupported arguments (rows {N}, length {L8}, rate {sample_rate}, f0 [{f0_min}, {f0_max}])")
+    taps = _world_taps_for(sample_rate, f0_min, f0_max, x.device)
+    out = torch.empty(N, lib.alive_world_f0_frames(L8, int(sample_rate), float(frame_period)), device=x.device)
+    ws = _world_ws.get(nbytes, x.device)
+    nat.check(lib.alive_world_f0_rows(nat.ptr(x), N, L8, *args, nat.ptr(taps), nat.ptr(row_on), nat.ptr(out), nat.ptr(ws),
+                                      ws.numel(), nat.stream()), "alive_world_f0_rows")
+    return out
+
+
 def linear_resize(x, size):
     """F.interpolate(x, size, mode='linear') (align_corners=False) of x [..., Lin] on the device, rounded as torch's CPU kernel"""
     if size <= 0:
@@ -425,3 +448,14 @@ def compute_f0(wf, sample_rate=16000, segment_size=320):
     l = wf.shape[1]
     wf8 = audio_io.resample(wf, sample_rate, 8000)
     return linear_resize(compute_f0_dio(wf8, 8000), l // segment_size)
+
+
+def compute_f0_rows(wf, row_on, sample_rate=16000, segment_size=320):
+    """compute_f0 of the rows of wf [N, L] whose row_on[r] (device int32 [N]) is nonzero, bitwise; the other rows are 0.  The
+    16 -> 8 kHz resample and the two resizes run over every row (cheap); DIO + StoneMask only over the rows that are on.  No host
+    synchronisation: capturable once warm (taps, resampling filter and the stream's workspace exist after the first call)"""
+    from . import audio_io
+    l = wf.shape[1]
+    wf8 = audio_io.resample(wf, sample_rate, 8000).contiguous()
+    f0 = linear_resize(world_f0_rows(wf8, row_on, 8000), wf8.shape[1] // 256)
+    return linear_resize(f0[:, None], l // segment_size)

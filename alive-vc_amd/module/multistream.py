@@ -15,13 +15,20 @@ Per slot, as RealtimeConverter.step: the ring fills chunk by chunk, the slot emi
 `buffersize` chunks, and the phase is carried through phi[:, :, end_of_output] -- 0 while the slot fills, reset by `open`.
 Slots that are closed run on silence with an empty segment.  Interior reuse (RealtimeConverter's reuse_interior) is not
 available here.
+
+WORLD pitch (`-wpe` per session): a converter built with world_pitch=True adds one masked WORLD branch over all B rings
+(common.compute_f0_rows: alive_world_f0_rows) on the f0 side stream, after the estimator; a session opened or set with
+world_pitch=True takes that f0 instead of the estimator's, as RealtimeConverter(world_pitch=True) does: WORLD's f0 of its 16-kHz
+ring (after the input resample and gain), the mode-1 transform with its pitch shift, and NOT its f0_rate (the reference
+multiplies only the estimator's f0 by it).  The mask and the per-row choice are device arrays: switching costs no re-capture.
+WORLD needs the whole ring: rings shorter than about 230 ms (-c 160 -b 16 is 160 ms) come out unvoiced.
 """
 import numpy as np
 import torch
 
 from . import _native as nat
 from . import audio_io, ops
-from .common import DIM
+from .common import DIM, compute_f0_rows
 from .realtime import PLANES_MIN_COLS
 from .spectrogram import spectrogram
 
@@ -306,12 +313,12 @@ def db_scale(db):
     return float(10 ** (db / 20)) if db != 0 else 1.0
 
 
-_PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain")
+_PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch")
 
 
 class MultiStreamConverter:
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
-                 output_sr=16000, k=4, device="cuda", rates=None):
+                 output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False):
         if not 1 <= int(k) <= MAX_K:
             raise ValueError(f"MultiStreamConverter: k={k} outside [1, {MAX_K}] (the grouped search keeps k <= 8)")
         if int(slots) < 1 or int(slots) > 1024:
@@ -382,6 +389,13 @@ class MultiStreamConverter:
         self.out_pre = torch.ones(B, dtype=torch.float32, device=dev)       # output gain: before the resampler (:173-175)
         self.out_post = torch.ones(B, dtype=torch.float32, device=dev)
         self.emit = torch.zeros(B, 1, dtype=torch.bool, device=dev)          # the slots whose phase advances this tick
+        # world_pitch: the masked WORLD branch is part of the tick (captured once); per row, world_on selects WORLD's f0 and the
+        # transform's rate is f0_rate_eff: the session's f0_rate, 1.0 on a WORLD row (its f0_rate stays in its params)
+        self.world_pitch = bool(world_pitch)
+        if self.world_pitch:
+            self.world_on = torch.zeros(B, dtype=torch.int32, device=dev)
+            self._world_sel = torch.zeros(B, 1, 1, dtype=torch.bool, device=dev)
+            self.f0_rate_eff = torch.ones(B, dtype=torch.float32, device=dev)
         self.phi = torch.zeros(B, 64, device=dev)
         self._in = torch.zeros(B, ld_in, device=dev)
         self._graph = None
@@ -403,6 +417,11 @@ class MultiStreamConverter:
         lo, m = self.pool.segment(p["voice"])
         if m < self.k:
             raise ValueError(f"voice {p['voice']!r} has {m} vectors, fewer than k={self.k}")
+        world = p["world_pitch"]
+        if not isinstance(world, (bool, np.bool_)):
+            raise ValueError(f"slot {slot}: world_pitch must be a bool, got {world!r}")
+        if world and not self.world_pitch:
+            raise ValueError(f"slot {slot}: world_pitch=True needs a converter built with MultiStreamConverter(..., world_pitch=True)")
         self.seg_lo[slot] = lo
         self.seg_len[slot] = m
         self.alpha[slot] = float(p["alpha"])
@@ -410,6 +429,13 @@ class MultiStreamConverter:
         self.pitch[slot] = float(p["pitch"])
         self.in_post[slot] = db_scale(p["input_gain"])
         self.out_pre[slot] = db_scale(p["gain"])
+        if self.world_pitch:
+            self._set_world(slot, bool(world), float(p["f0_rate"]))
+
+    def _set_world(self, slot, on, f0_rate):
+        self.world_on[slot] = int(on)
+        self._world_sel[slot] = on
+        self.f0_rate_eff[slot] = 1.0 if on else f0_rate
 
     def _set_rate(self, slot, rate):
         self.rate[slot] = rate
@@ -422,15 +448,16 @@ class MultiStreamConverter:
         self.pair_out[slot] = self._rt.pair(16000, rate)
         self.len_out[slot] = self._lout[rate]
 
-    def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None):
+    def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False):
         """start a session in `slot`: empty ring, phase 0.  `rate` (default: the converter's input_sr) is one of the declared
-        `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life"""
+        `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
+        WORLD's f0 of the session's ring instead of the estimator's, f0_rate not applied (needs a world_pitch=True converter)"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
             raise ValueError(f"slot {slot}: rate {rate} Hz was not declared (rates={list(self.rates)}): pass it in "
                              "MultiStreamConverter(..., rates=...)")
-        p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain)
+        p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch)
         self._apply(slot, p)                                  # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -441,7 +468,7 @@ class MultiStreamConverter:
         return self
 
     def set(self, slot, **params):
-        """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain)"""
+        """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch)"""
         slot = self._slot(slot)
         if not self.is_open[slot]:
             raise ValueError(f"slot {slot} is not open")
@@ -463,12 +490,15 @@ class MultiStreamConverter:
         self.ring[slot] = 0
         self.seg_len[slot] = 0
         self.phi[slot] = 0.0
+        if self.world_pitch:
+            self._set_world(slot, False, 1.0)
         self._set_rate(slot, int(self.input_sr))             # a closed slot: the converter's own rate, silence
         return self
 
     # ------------------------------------------------------------------ device step
-    def _f0_on_side_stream(self, spec):
-        """RealtimeConverter._f0_on_side_stream with the per-row pitch transform"""
+    def _f0_on_side_stream(self, spec, data):
+        """RealtimeConverter._f0_on_side_stream with the per-row pitch transform.  world_pitch: after the estimator, the masked
+        WORLD f0 of the 16-kHz rings `data` (rows off: no work), selected per row, then the transform at the effective rates"""
         cur = torch.cuda.current_stream(spec.device)
         if self._side is None:
             self._side = torch.cuda.Stream(device=spec.device)
@@ -480,7 +510,11 @@ class MultiStreamConverter:
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             f0 = self.pe.estimate(spec, out=buf)
-            f0 = pitch_transform_rows_(f0, 1, self.f0_rate, self.pitch, self.intonation)
+            rate = self.f0_rate
+            if self.world_pitch:
+                buf.copy_(torch.where(self._world_sel, compute_f0_rows(data, self.world_on), buf))
+                f0, rate = buf, self.f0_rate_eff
+            f0 = pitch_transform_rows_(f0, 1, rate, self.pitch, self.intonation)
         return f0, (lambda: cur.wait_stream(side))
 
     def _device_step(self, data, phi):
@@ -491,7 +525,7 @@ class MultiStreamConverter:
             data = resample_rows_multi(data, self.len_in, self.pair_in, self._rt, self._len16_rows, self._len16, self.in_pre,
                                        self.in_post)
         spec = spectrogram(data)
-        f0, join = self._f0_on_side_stream(spec)
+        f0, join = self._f0_on_side_stream(spec, data)
         content = self.ce(spec)
         val, idx = knn_search_grouped(content, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k)
         content = merge_gather_rows(val, idx, self.k, self.alpha, self.pool.rows, content)

@@ -7,6 +7,7 @@ and reflect pads), so here all windows of all utterances go through the networks
 """
 import os
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -344,10 +345,10 @@ class Converter:
         return stitch(self.convert_windows(windows, keep_frames=keep, **kw), total, chunk)       # (the guard sits in convert_windows)
 
     def convert_many(self, utterances, pool, voices, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, alpha=0.0, chunk=48000, k=4,
-                     window_batch=64, trim_context=False):
+                     window_batch=64, trim_context=False, world_pitch=False):
         """Many-to-many batch conversion: utterance i (16 kHz, [L] or [1, L], any length) to voice voices[i] of `pool`
-        (module/multistream.py: VoicePool), with per-utterance pitch_shift / intonation / f0_rate / alpha (a scalar applies to
-        every utterance).  Returns one [1, L_i] waveform per utterance.  The windows of ALL utterances form one batch (a network
+        (module/multistream.py: VoicePool), with per-utterance pitch_shift / intonation / f0_rate / alpha / world_pitch (a scalar
+        applies to every utterance; world_pitch: WORLD's f0 of each whole window, as convert(world_pitch=True)).  Returns one [1, L_i] waveform per utterance.  The windows of ALL utterances form one batch (a network
         batch may span utterances), and the match is ONE pool search over every window's frames, each window against its own
         voice (csrc/knn.hip: alive_knn_search_pool).  Utterance i comes out bitwise as `convert` with
         PackedLibrary(voice, strict=True) makes it alone -- unless the fp16 range guard repeats the batch on bf16 planes: that
@@ -367,6 +368,11 @@ class Converter:
             return [float(v) for v in xs]
         shifts, inton, rates, alphas = (per(pitch_shift, "pitch_shift"), per(intonation, "intonation"), per(f0_rate, "f0_rate"),
                                         per(alpha, "alpha"))
+        worlds = list(world_pitch) if isinstance(world_pitch, (list, tuple)) else [world_pitch] * m
+        if len(worlds) != m:
+            raise ValueError(f"world_pitch: {len(worlds)} values for {m} utterances")
+        if not all(isinstance(w, (bool, np.bool_)) for w in worlds):
+            raise ValueError(f"world_pitch: expected bools, got {worlds}")
         for name in voices:
             if pool.segment(name)[1] < k:
                 raise ValueError(f"voice {name!r} has {pool.segment(name)[1]} vectors, fewer than k={k}")
@@ -384,6 +390,10 @@ class Converter:
             return torch.repeat_interleave(torch.tensor(vals, dtype=dtype, device=self.device), rep).contiguous()
         params = dict(ids=torch.repeat_interleave(pool.voice_ids(voices), rep).contiguous(), alpha=rows(alphas, torch.float64),
                       shift=rows(shifts, torch.float32), inton=rows(inton, torch.float32), rate=rows(rates, torch.float32))
+        # the WORLD windows of every window batch (batch-local row indices, on the device before the batches start)
+        on = [bool(w) for w, c in zip(worlds, counts) for _ in range(c)]
+        params["world"] = {i: torch.tensor([j - i for j in range(i, min(i + window_batch, len(on))) if on[j]], dtype=torch.int64,
+                                           device=self.device) for i in range(0, len(on), window_batch) if any(on[i:i + window_batch])}
         keep = (chunk // 320, 2 * chunk // 320) if trim_context else None
         out = ops.Fp16Guard(self._agree_on_saturations()).run(
             lambda: self._convert_many_windows(windows, pool, params, k, window_batch, keep))
@@ -394,7 +404,9 @@ class Converter:
         return res
 
     def _convert_many_windows(self, windows, pool, p, k, window_batch, keep_frames):
-        """`_convert_windows` (per-window front end) with per-window voice, alpha and pitch parameters"""
+        """`_convert_windows` (per-window front end) with per-window voice, alpha and pitch parameters.  p["world"]: window batch
+        start -> its WORLD windows' rows: their f0 (compute_f0 of the gathered whole windows) replaces the estimator's before the
+        per-row transform, which applies each utterance's pitch, intonation and f0 rate (features(world_pitch=True))"""
         from . import multistream as MS
         n, L = windows.shape
         lf = L // 320
@@ -427,7 +439,14 @@ class Converter:
             fe = torch.zeros(spec.shape[0], 768, lf, device=spec.device)
             fe[:, :, a:b] = self.ce(spec[:, :, a:b].contiguous())
             feat[sl] = fe
-        batches(enc)
+
+        def enc_world(i):
+            enc(i)
+            w = p["world"].get(i)
+            if w is not None:                                   # (same stream: after the estimator wrote the batch's f0)
+                sl = slice(i, i + window_batch)
+                f0[sl].index_copy_(0, w, compute_f0(windows[sl].index_select(0, w)))
+        batches(enc_world)
         MS.pitch_transform_rows_(f0, 0, p["rate"], p["shift"], p["inton"])
         src = feat if rng is None else feat[:, :, rng[0]:rng[1]].contiguous()
         val, idx = MS.knn_search_pool(src, pool, p["ids"], k)

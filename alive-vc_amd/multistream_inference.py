@@ -5,6 +5,8 @@ The sessions file is a JSON list; each entry:
   {"input": "a.wav",                      the session's input
    "target": "spk.wav" and / or "lib": "voice_library.pt",   its voice (as -t / -lib of realtime_inference.py)
    "pitch": 0, "f0_rate": 1, "alpha": 0, "gain": 0, "input_gain": 0,     optional, realtime_inference.py's meanings
+   "world_pitch": false,                  optional, a JSON bool: realtime_inference.py's -wpe (WORLD's f0 of the ring; its
+                                          f0_rate is then not applied, as there)
    "start": 0,                            optional: the tick at which the session joins
    "sr": 48000,                           optional: the session's sample rate (default -isr / -osr)
    "output": "a_out.wav"}                 optional: default <outdir>/<index>_<input name>.wav
@@ -12,6 +14,8 @@ A session's slot opens at its start tick, gets one chunk per tick while its inpu
 A session with "sr" has its input resampled to sr on load, is driven at sr in chunks of chunk * sr / isr samples (a whole number,
 with the converter's 16 kHz geometry: module/multistream.py session_geometry), and its output wav is written at sr.  "sr" needs
 -isr == -osr.
+The converter carries the WORLD branch only if some session asks for "world_pitch": a sessions file without it runs as before.
+WORLD needs rings of about 230 ms or more (-c 960 -b 8 is 480 ms): a shorter ring comes out unvoiced.
 Flags shared with realtime_inference.py keep its spelling: -c, -b, -k, -isr, -osr, --no-graph.
 """
 import argparse
@@ -32,7 +36,7 @@ from module.multistream import MultiStreamConverter, VoicePool   # noqa: E402
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
-SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "start", "sr", "output")
+SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "start", "sr", "output")
 
 
 def build_parser():
@@ -70,11 +74,13 @@ def load_sessions(path):
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: {SESSION_KEYS})")
         if s.get("target") is None and s.get("lib") is None:
             raise ValueError(f"session {i}: needs a \"target\" wav or a \"lib\" voice library")
+        if not isinstance(s.get("world_pitch", False), bool):
+            raise ValueError(f"session {i}: \"world_pitch\" must be true or false, got {s['world_pitch']!r}")
         rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
                  gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
-                 sr=None if s.get("sr") is None else int(s["sr"]))
+                 sr=None if s.get("sr") is None else int(s["sr"]), world_pitch=s.get("world_pitch", False))
         if e["start"] < 0:
             raise ValueError(f"session {i}: start tick {e['start']} < 0")
         if e["sr"] is not None and e["sr"] <= 0:
@@ -153,9 +159,10 @@ def main(argv=None):
     in_sr = [s["sr"] or args.input_sr for s in sessions]
     out_sr = [s["sr"] or args.output_sr for s in sessions]
     conv = MultiStreamConverter(CE, PE, Dec, pool, slots, chunk=args.chunk, buffersize=args.buffersize, input_sr=args.input_sr,
-                                output_sr=args.output_sr, k=args.k, device=device, rates=sorted(set(in_sr)))
+                                output_sr=args.output_sr, k=args.k, device=device, rates=sorted(set(in_sr)),
+                                world_pitch=any(s["world_pitch"] for s in sessions))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
-                   input_gain=s["input_gain"], rate=r) for n, s, r in zip(names, sessions, in_sr)]
+                   input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"]) for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()
     pcms = [input_pcm(s["input"], r, device) for s, r in zip(sessions, in_sr)]

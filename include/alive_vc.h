@@ -651,6 +651,9 @@ int alive_pitch_transform_rows(float* f0, int N, int T, int mode, const float* f
  *   alive_world_f0             x8 [N][L8] fp32 -> f0_out [N][F] fp32 (0 = unvoiced); workspace of
  *                              alive_world_f0_workspace_bytes(N, L8, fs, f0_floor, f0_ceil, frame_period) bytes (0: bad args).
  *                              fs <= 16000; the lowest band's low-pass may have at most 1024 taps (fs / f0_floor <= ~724)
+ *   alive_world_f0_rows        alive_world_f0 over the rows whose row_on[r] (DEVICE int32 [N]) is nonzero, bitwise; the other
+ *                              rows get 0 (unvoiced) at every frame and do no other work.  Same plan, workspace and taps; the
+ *                              mask is read on the device, so one captured call serves any mix of rows (a null mask is refused)
  *   alive_linear_resize        y [rows][Lout] = torch F.interpolate(x [rows][Lin], Lout, mode='linear', align_corners=False) as
  *                              torch's CPU kernel rounds it (float32, fused multiply-adds where it fuses)                      */
 int alive_world_f0_frames(int L8, int fs, double frame_period);
@@ -659,6 +662,8 @@ int alive_world_f0_taps(int fs, double f0_floor, double f0_ceil, double* host_ta
 size_t alive_world_f0_workspace_bytes(int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period);
 int alive_world_f0(const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
                    const double* taps, float* f0_out, void* ws, size_t ws_bytes, void* stream);
+int alive_world_f0_rows(const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
+                        const double* taps, const int32_t* row_on, float* f0_out, void* ws, size_t ws_bytes, void* stream);
 int alive_linear_resize(const float* x, int rows, int Lin, float* y, int Lout, void* stream);
 
 #ifdef __cplusplus

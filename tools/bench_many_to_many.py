@@ -10,7 +10,9 @@ Every time is event-timed on the current stream after one warm-up call, mean of 
   (c) a per-voice loop of PackedLibrary(strict=True).search over that voice's windows (libraries packed beforehand);
   ref alive_knn_search_strict of the whole batch against ONE M-row voice (same FLOPs as (a)).
 End to end at V = 64, M = 50 000: convert_many of the 64 utterances against 64 sequential Converter.convert calls (each with its
-voice's strict PackedLibrary, packed beforehand), trim_context on (the CLI default).
+voice's strict PackedLibrary, packed beforehand), trim_context on (the CLI default).  --world 0,0.5,1 also times convert_many with
+that fraction of the utterances on WORLD pitch (spread evenly: utterance u is on WORLD when floor((u + 1) f) > floor(u f)) and
+records world_<f>_ms; --no-search skips the search table.
 """
 import argparse
 import json
@@ -48,6 +50,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the results as JSON to this file")
+    ap.add_argument("--world", default=None, help="comma-separated fractions of the utterances on WORLD pitch (end to end)")
+    ap.add_argument("--no-search", action="store_true", help="skip the search table (end to end only)")
     ap.add_argument("--commit", default="", help="source commit to record (default: git rev-parse HEAD, when there is a .git)")
     args = ap.parse_args()
     from module.content_encoder import ContentEncoder
@@ -67,7 +71,7 @@ def main():
     res = dict(commit=commit,
                batch=dict(windows=n, frames=n * T, k=K), search=[], end_to_end=None)
     g = torch.Generator(device=DEV).manual_seed(7)
-    for M in (512, 50_000):
+    for M in (() if args.no_search else (512, 50_000)):
         toks = {f"v{j}": torch.randn(768, M, device=DEV, generator=g) for j in range(64)}
         one = PackedLibrary(toks["v0"], strict=True)
         t_ref = timed(lambda: one.search(feat, K), args.reps)
@@ -104,6 +108,11 @@ def main():
     t_seq = timed(seq, args.reps)
     res["end_to_end"] = dict(utterances=N_UTT, voices=N_UTT, M=50_000, convert_many_ms=round(t_many, 2),
                              sequential_convert_ms=round(t_seq, 2), speedup=round(t_seq / t_many, 2))
+    for f in (args.world.split(",") if args.world else []):
+        on = [int((u + 1) * float(f)) > int(u * float(f)) for u in range(N_UTT)]
+        t_w = timed(lambda: conv.convert_many(utts, pool, names, chunk=CHUNK, k=K, trim_context=True, world_pitch=on), args.reps)
+        res["end_to_end"][f"world_{f}_ms"] = round(t_w, 2)
+        res["end_to_end"][f"world_{f}_utterances"] = sum(on)
     print(json.dumps(res["end_to_end"]), flush=True)
     if args.out:
         with open(args.out, "w") as f:

@@ -5,11 +5,13 @@ the chunk period); and the grouped search alone: bytes of the segments it reads 
 Timing: every tick is bracketed by torch.cuda.synchronize() (the tick itself ends in a device -> host copy), after warm-up
 ticks; the search is timed with events around repeated calls.  --rates spreads the sessions over a list of sample rates
 (session s at rates[s % len]; MultiStreamConverter(rates=...), the per-row multi-rate edges) and adds that batch's tick p50 / p99
-(mixed_<mode>_tick_p50_ms / _p99_ms) next to the single-rate figures of the same B.  Profile in a separate run (rocprofv3 --kernel-trace --stats --
+(mixed_<mode>_tick_p50_ms / _p99_ms) next to the single-rate figures of the same B.  --world adds the graph tick p50 / p99 of
+the same batch per WORLD setting (world_<setting>_tick_p50_ms / _p99_ms): "off" is a world_pitch=False converter, a number f a
+world_pitch=True converter with sessions s < round(f B) on WORLD (0: the masked branch with every row off).  Profile in a separate run (rocprofv3 --kernel-trace --stats --
 python tools/bench_multistream.py --quick).  Prints one JSON line per configuration and writes the list to --out.
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
-                                      [--out multistream.json]
+                                      [--world off,0,0.5,1] [--voices shared,distinct] [--out multistream.json]
 """
 import argparse
 import json
@@ -76,12 +78,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--quick", action="store_true", help="B = 64 at -c 160 -b 16, distinct voices, graph only (profiler runs)")
     ap.add_argument("--rates", default=None, help="comma-separated session rates: also time a batch spread over them")
+    ap.add_argument("--world", default=None, help="comma-separated WORLD settings: off, or the fraction of sessions on WORLD")
+    ap.add_argument("--voices", default="shared,distinct", help="voice mixes to run: shared, distinct")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     batches = [int(b) for b in args.batches.split(",")]
     configs = [tuple(int(v) for v in c.split("x")) for c in args.configs.split(",")]
     rates = [int(r) for r in args.rates.split(",")] if args.rates else None
-    mixes = ("shared", "distinct")
+    mixes = tuple(args.voices.split(","))
+    worlds = args.world.split(",") if args.world else []
     if args.quick:
         batches, configs, mixes = [64], [(160, 16)], ("distinct",)
     nets = (ContentEncoder(seed=2), F0Estimator(seed=2), Decoder(seed=2))
@@ -117,6 +122,15 @@ def main():
                         p50, p99 = time_ticks(mixed, B, mixed.slot_chunk, args.ticks, args.warmup + bs + 1, 300)
                         rec[f"mixed_{mode}_tick_p50_ms"], rec[f"mixed_{mode}_tick_p99_ms"] = round(p50, 3), round(p99, 3)
                         del mixed
+                for w in worlds:
+                    wc = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, world_pitch=w != "off")
+                    on = 0 if w == "off" else int(round(float(w) * B))
+                    for s in range(B):
+                        wc.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, world_pitch=s < on)
+                    wc.enable_graph()
+                    p50, p99 = time_ticks(wc, B, chunk, args.ticks, args.warmup + bs + 1, 300)
+                    rec[f"world_{w}_tick_p50_ms"], rec[f"world_{w}_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                    del wc
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
                 rows.append(rec)
