@@ -10,12 +10,15 @@ Default workload = BASELINE.json config 3/4 on one GPU: 64 utterances x 10 s (38
 N > 1: `python bench.py --gpus N` launches its own N ranks (torch.distributed.run, one process per GPU,
 before this process has touched a GPU) unless it already runs under a launcher (RANK in the
 environment).  Windows are independent units, so the headline ranks are pure data-parallel replicas over
-disjoint utterance sets ("weak" scaling, no data-path collective).  BASELINE config 4 -- the library cut
-into N row slabs, features all-gathered, per-shard exact top-k all-gathered and merged -- runs as a
-second leg on one fixed global batch, is checked bitwise against the replicated path on every rank and
-is reported as `sharded_knn`, never as `value`.
+disjoint utterance sets ("weak" scaling, no data-path collective).  With `--full`, BASELINE config 4 --
+the library cut into N row slabs, features all-gathered, per-shard exact top-k all-gathered and merged --
+runs as a second leg on one fixed global batch, is checked bitwise against the replicated path on every
+rank and is reported as `sharded_knn`, never as `value`.
 
-Prints ONE JSON line on rank 0.  Secondary legs (`--legs`) sit beside the headline in the same line.
+Prints ONE JSON line on rank 0.  A plain run does what the headline needs and nothing else: set up, warm up,
+time the steps, write `--dump-outputs`, print the line (with the scoring kernel's roofline from the events of
+the timed steps).  `--full` adds everything that takes runs of its own: the networks' roofline passes
+(`roofline_nets`), the CPU-oracle baseline, the secondary legs (`--legs`) and the library-sharded leg.
 """
 import argparse
 import json
@@ -235,23 +238,28 @@ def main():
     ap.add_argument("--chunk", type=int, default=48000)
     ap.add_argument("-k", type=int, default=4)
     ap.add_argument("--window-batch", type=int, default=192)      # (384 windows = 2 batches; 128 / 192 / 256 / 384: 188.4 / 187.4 / 187.4 / 188.5 ms per step, tools/sweep_streams.sh)
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU-oracle leg (0 = skip)")
-    ap.add_argument("--legs", default="all", help="comma list of secondary legs (N = 1): " + ",".join(ALL_LEGS) + " | all | none")
-    ap.add_argument("--no-nets-roofline", action="store_true", help="skip the separate timed passes of the networks (profiling runs: keeps the kernel trace to the steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what takes runs of its own: the networks' roofline passes, the CPU-oracle baseline, "
+                         "the secondary legs (--legs) and, on more than one rank, the library-sharded leg (config 4)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU-oracle leg of --full (0 = skip)")
+    ap.add_argument("--legs", default=None, help="comma list of the secondary legs of --full (N = 1): " + ",".join(ALL_LEGS) + " | all | none (default all)")
+    ap.add_argument("--no-nets-roofline", action="store_true", help="--full without the separate timed passes of the networks")
     ap.add_argument("--stream-steps", type=int, default=1000, help="steps of the streaming leg (BASELINE config 5)")
-    ap.add_argument("--no-shard-library", action="store_true", help="skip the library-sharded leg (config 4) of a multi-GPU run")
+    ap.add_argument("--no-shard-library", action="store_true", help="--full without the library-sharded leg (config 4) of a multi-GPU run")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the real thing); gloo + --same-device only exercise the multi-rank code path on a 1-GPU box")
     ap.add_argument("--same-device", action="store_true", help="test only: every rank uses cuda:0")
     ap.add_argument("--force-dist", action="store_true",
-                    help="--gpus 1 only: create a world-size-1 process group anyway and run the library-sharded leg with one shard, so "
-                         "that RCCL init, the device-tensor collectives and the fences of module/sharded.py execute on a 1-GPU box")
+                    help="--gpus 1 only: create a world-size-1 process group anyway and (with --full) run the library-sharded leg with one "
+                         "shard, so that RCCL init, the device-tensor collectives and the fences of module/sharded.py execute on a 1-GPU box")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the waveform windows of the last step (rank 0) to DIR/waveform.npy, float32; "
                          "over 64 MB, a fixed sample of whole windows, their indices in DIR/waveform_windows.npy")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.legs not in (None, "none") and not args.full:
+        ap.error("--legs chooses among the legs of a --full run")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(launch_ranks(args))
@@ -281,11 +289,12 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
         else:
             dist.init_process_group("gloo")
-    legs = set(ALL_LEGS) if args.legs == "all" else set(x for x in args.legs.split(",") if x and x != "none")
+    legs = set(ALL_LEGS) if args.legs in (None, "all") else set(x for x in args.legs.split(",") if x and x != "none")
     if args.cpu_seconds <= 0:
         legs.discard("cpu_baseline")
-    if rank != 0 or world > 1:
+    if rank != 0 or world > 1 or not args.full:
         legs = set()
+    shard_leg = dist_on and args.full and not args.no_shard_library
 
     from module import _native as nat
     from module.common import PackedLibrary
@@ -300,7 +309,7 @@ def main():
     g = torch.Generator(device=dev).manual_seed(1234)         # same library on every rank
     tokens = torch.randn(768, M, device=dev, generator=g)
     library = PackedLibrary(tokens)
-    if not dist_on or args.no_shard_library:
+    if not shard_leg:
         del tokens
     conv = Converter(ContentEncoder(seed=2), F0Estimator(seed=2), Decoder(seed=2), dev).set_library(library)
     windows = synth_windows(args.utterances, args.seconds, args.chunk, dev, seed=100 + rank)
@@ -424,7 +433,7 @@ def main():
                                 precision_mode=dec_mode, frac_of_split_bf16_peak=round(fl_dec / (ms_dec * 1e-3) / 1e12 / (PEAK_BF16_TFLOPS / 3), 4)),
                 "step": {"ideal_ms": round(ideal_ms, 1), "ms_per_step": round(dt / args.steps * 1e3, 2), "frac": round(ideal_ms / (dt / args.steps * 1e3), 4),
                          "ideal": "kNN 2*768*M*T FLOP at the candidate stage's MFMA peak + decoder at its blended peak (2.5 PF for the plain-fp16 layers, 2.5 PF / 3 for the rest) + front end at its blended peak (2.5 PF / 3 for the fp16-split layers, 2.5 PF / 6 for the rest)"}}
-    roofline_nets = guarded(nets_roofline) if rank == 0 and not args.no_nets_roofline else None
+    roofline_nets = guarded(nets_roofline) if rank == 0 and args.full and not args.no_nets_roofline else None
 
     extra = {}
     # Data dependence of the scoring kernel: the candidate-list path is taken more often when the frames of a wave
@@ -832,7 +841,7 @@ def main():
     del small_tokens
 
     sharded = None
-    if dist_on and not args.no_shard_library:
+    if shard_leg:
         # BASELINE config 4 (never part of `value`): one fixed global batch (same seed on every rank), windows partitioned
         # over the ranks, the library cut into `world` row slabs -- checked bitwise against the replicated path
         from module.sharded import bench_sharded

@@ -419,6 +419,28 @@ def test_realtime_graph_capture_equals_eager(workdir):
     assert np.array_equal(outs["eager"], outs["graph"])
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`python bench.py` without --full sets up, warms up, times the steps, writes --dump-outputs and prints ONE JSON line --
+    none of the passes that take runs of their own (the networks' roofline, the CPU oracle, the secondary legs)"""
+    import json
+    import subprocess
+    import bench
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--library-size", "30000", "--utterances", "3",
+                        "--seconds", "4", "--steps", "2", "--warmup", "1", "--window-batch", "8", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["higher_is_better"] is True and d["unit"] == "frames/s" and d["dtype"]
+    assert d["roofline"]["launches"] > 0 and "achieved_uncorrelated_frames" not in d["roofline"]
+    assert d["roofline_nets"] is None and d["cpu_baseline"] is None
+    assert not set(d) & (set(bench.ALL_LEGS) - {"cpu_baseline"} | {"sharded_knn", "ranks"}), sorted(d)
+    wave = np.load(tmp_path / "waveform.npy")
+    assert wave.dtype == np.float32 and wave.shape[0] == d["config"]["windows_per_step_per_gpu"] and np.isfinite(wave).all()
+
+
 def test_bench_world1_rccl_executes_the_sharded_leg():
     """the RCCL code path on the hardware there is.  `--gpus 1 --force-dist` creates a world-size-1 `nccl`
     (= RCCL) process group: communicator init with device_id, barrier / all_reduce on device tensors (fences, max over
@@ -428,7 +450,7 @@ def test_bench_world1_rccl_executes_the_sharded_leg():
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--backend", "nccl",
                         "--library-size", "30000", "--utterances", "3", "--seconds", "4", "--steps", "1", "--warmup", "1",
-                        "--window-batch", "8", "--legs", "none"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--window-batch", "8", "--full", "--legs", "none"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -450,7 +472,7 @@ def test_bench_two_ranks_gloo_same_device():
     env = dict(os.environ, ALIVE_STREAMS="2")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device",
                         "--library-size", "30000", "--utterances", "3", "--seconds", "4", "--steps", "1", "--warmup", "1",
-                        "--window-batch", "8"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--window-batch", "8", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -165,6 +165,14 @@ def test_cli_flags_match_the_reference():
         assert flag in rt._option_string_actions, flag
 
 
+def test_bench_legs_belong_to_a_full_run():
+    """bench.py without --full measures the headline alone: asking it for a secondary leg is an argument error (before any GPU use)"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", "strict_knn"], capture_output=True, text=True,
+                       timeout=300, cwd=ROOT)
+    assert r.returncode == 2 and "--full" in r.stderr and not r.stdout, (r.returncode, r.stderr[-2000:])
+
+
 def test_shard_bounds_and_window_partition():
     assert shard_bounds(10, 4) == [(0, 3), (3, 6), (6, 8), (8, 10)]
     assert shard_bounds(1_000_000, 8)[7] == (875000, 1000000)
