@@ -29,7 +29,8 @@ import torch
 from . import _native as nat
 from . import audio_io, ops
 from .common import DIM, compute_f0_rows
-from .realtime import PLANES_MIN_COLS
+from .pipeline import prepare_networks
+from .realtime import capture_step, f0_on_side_stream, fp16_guarded, ring_geometry
 from .spectrogram import spectrogram
 
 MAX_K = 8          # the grouped search keeps one register pair per lane and frame (csrc/knn.hip)
@@ -285,8 +286,7 @@ def resample_rows_multi(x, lens_in, pairs, table, lens_out, ld_out, pre, post):
 
 def _geometry(chunk, buffersize, sr):
     """realtime_inference.py:122-126 at one rate: (ring length at 16 kHz, frames, internal chunk)"""
-    n = chunk * buffersize
-    return -(-16000 * n // sr), (n * 16000 // sr) // 320, int(chunk * (16000 / sr))
+    return -(-16000 * chunk * buffersize // sr), ring_geometry(chunk, buffersize, sr, sr)[2], int(chunk * (16000 / sr))
 
 
 def session_geometry(chunk, buffersize, sr, rate):
@@ -331,21 +331,12 @@ class MultiStreamConverter:
                                  "its internal chunk and its frame count could not both be the converter's")
             chunks = {r: session_geometry(chunk, buffersize, input_sr, r) for r in rates}
         self.device = torch.device(device)
-        self.ce, self.pe, self.dec = content_encoder.to(device), f0_estimator.to(device), decoder.to(device)
-        for net in (self.ce, self.pe, self.dec):
-            net.table()
-        self.dec._split_for_this_checkpoint()
+        self.ce, self.pe, self.dec = prepare_networks(content_encoder, f0_estimator, decoder, device)
         self.pool = pool
         self.B, self.k = int(slots), int(k)
         self.chunk, self.buffersize = int(chunk), int(buffersize)
         self.input_sr, self.output_sr = input_sr, output_sr
-        internal_chunk = int(chunk * (16000 / output_sr))                  # realtime_inference.py:122-126
-        center = int(internal_chunk * buffersize) // 2
-        self.end_of_output = center + internal_chunk // 2
-        self.begin_of_output = center - internal_chunk // 2
-        self.frames = (chunk * buffersize * 16000 // input_sr) // 320
-        if self.frames < 5:
-            raise ValueError(f"ring of {buffersize} x {chunk} samples is {self.frames} frames; the decoder needs >= 5")
+        self.begin_of_output, self.end_of_output, self.frames = ring_geometry(chunk, buffersize, input_sr, output_sr)
         B, dev = self.B, self.device
         self.n = self.chunk * self.buffersize
         self.rates = tuple(rates)
@@ -404,7 +395,7 @@ class MultiStreamConverter:
         self._side = None
         self._f0_bufs = {}
         self.last_f0 = None
-        if self._fp16_guarded():
+        if fp16_guarded(self.B * self.frames):
             ops.f16_clear()
 
     # ------------------------------------------------------------------ sessions
@@ -497,25 +488,16 @@ class MultiStreamConverter:
 
     # ------------------------------------------------------------------ device step
     def _f0_on_side_stream(self, spec, data):
-        """RealtimeConverter._f0_on_side_stream with the per-row pitch transform.  world_pitch: after the estimator, the masked
-        WORLD f0 of the 16-kHz rings `data` (rows off: no work), selected per row, then the transform at the effective rates"""
-        cur = torch.cuda.current_stream(spec.device)
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=spec.device)
-        key = (spec.shape[0], spec.shape[2])
-        buf = self._f0_bufs.get(key)
-        if buf is None:
-            buf = self._f0_bufs[key] = torch.empty(spec.shape[0], 1, spec.shape[2], device=spec.device)
-        side = self._side
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
+        """realtime.f0_on_side_stream with the per-row pitch transform.  world_pitch: after the estimator, the masked WORLD f0 of
+        the 16-kHz rings `data` (rows off: no work), selected per row, then the transform at the effective rates"""
+        def body(buf):
             f0 = self.pe.estimate(spec, out=buf)
             rate = self.f0_rate
             if self.world_pitch:
                 buf.copy_(torch.where(self._world_sel, compute_f0_rows(data, self.world_on), buf))
                 f0, rate = buf, self.f0_rate_eff
-            f0 = pitch_transform_rows_(f0, 1, rate, self.pitch, self.intonation)
-        return f0, (lambda: cur.wait_stream(side))
+            return pitch_transform_rows_(f0, 1, rate, self.pitch, self.intonation)
+        return f0_on_side_stream(self, spec, body)
 
     def _device_step(self, data, phi):
         """data float32 [B, ring] on the device, phi [B, 64] -> (wave [B, L] at output_sr, phi_next [B, 64])"""
@@ -544,19 +526,8 @@ class MultiStreamConverter:
 
     def enable_graph(self):
         """capture the per-tick device pipeline over [B, ring] once; replays read the per-slot device arrays"""
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
         saved = self.phi.clone()
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._device_step(self._in, self.phi)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            wave, phi_next = self._device_step(self._in, self.phi)
-            self.phi.copy_(phi_next)
-            self._g_out = wave
+        self._graph, self._g_out = capture_step(self.device, lambda: self._device_step(self._in, self.phi), self.phi)
         self.phi.copy_(saved)
         self._graph_pool_version = self.pool.version
         self.captures += 1
@@ -572,18 +543,9 @@ class MultiStreamConverter:
         self.phi.copy_(phi_next)
         return wave
 
-    def _fp16_guarded(self):
-        """as RealtimeConverter: B x frames >= 96 columns select the plane kernels and with them the fp16 forms"""
-        return self.B * self.frames >= PLANES_MIN_COLS and (ops.encoder_precision(0) != 2 or ops.decoder_precision(0) != 2)
-
     def _repeat_on_bf16(self, saved_phi):
         """RealtimeConverter._repeat_on_bf16 for the whole tick: modes 2, every slot's phase restored, the tick again"""
-        import warnings
-        warnings.warn("an activation left fp16's range in the multi-session streaming step: switching to ALIVE_ENCODER_PRECISION=2 / "
-                      "ALIVE_DECODER_PRECISION=2 (bf16 planes) and converting the tick again", RuntimeWarning)
-        ops.Fp16Guard.fallbacks += 1
-        ops.encoder_precision(2)
-        ops.decoder_precision(2)
+        ops.switch_to_bf16("multi-session streaming step", "tick")
         self.phi.copy_(saved_phi)
         if self._graph is not None:
             self.enable_graph()
@@ -618,7 +580,7 @@ class MultiStreamConverter:
         self.emit.copy_(torch.tensor(emit, device=self.device).view(self.B, 1))
         pcm = torch.from_numpy(self.ring).to(self.device)
         self._in.copy_(audio_io.pcm16_to_float(pcm))
-        guarded = self._fp16_guarded()
+        guarded = fp16_guarded(self.B * self.frames)
         if guarded:
             saved_phi = self.phi.clone()
         o = audio_io.float_to_pcm16(self._run()).cpu().numpy()

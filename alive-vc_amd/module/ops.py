@@ -419,3 +419,15 @@ class Fp16Guard:
             encoder_precision(enc)
             decoder_precision(dec)
         return out
+
+
+def switch_to_bf16(step, unit):
+    """A streaming `step` drove an activation out of fp16's range: both precision modes go to 2 (bf16 planes, fp32's range) for the
+    rest of the process -- a stream that saturates once will do so again, so unlike Fp16Guard's repeat the modes stay -- and the
+    caller converts its `unit` again.  Counted in Fp16Guard.fallbacks."""
+    import warnings
+    warnings.warn("an activation left fp16's range in the %s: switching to ALIVE_ENCODER_PRECISION=2 / "
+                  "ALIVE_DECODER_PRECISION=2 (bf16 planes) and converting the %s again" % (step, unit), RuntimeWarning)
+    Fp16Guard.fallbacks += 1
+    encoder_precision(2)
+    decoder_precision(2)

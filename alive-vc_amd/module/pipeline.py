@@ -67,15 +67,47 @@ def _edge_chunks(n, size):
     return bounds
 
 
+def _signals(windows, group):
+    """the padded signal [m, (group + 2) c] of every `group` consecutive windows (make_windows order, chunk c = a third of the
+    window): the first chunk of each window, then the last two chunks of the last one"""
+    n, L = windows.shape
+    m, c = n // group, L // 3
+    w3 = windows.view(m, group, L)
+    return torch.cat([w3[:, :, :c].reshape(m, group * c), w3[:, -1, c:]], dim=1).contiguous()
+
+
+def _edge_specs(windows):
+    """spectrograms of the two edge blocks of every window, EDGE + NET_MARGIN frames each: frames [0, nl) and [lf - nl, lf),
+    each from a slice of the window with SPEC_MARGIN frames more (those are spoiled by the slice's own reflect padding)"""
+    L = windows.shape[1]
+    nl = EDGE + NET_MARGIN
+    sl = spectrogram(windows[:, :(nl + SPEC_MARGIN) * 320].contiguous())[:, :, :nl].contiguous()
+    sr = spectrogram(windows[:, L - (nl + SPEC_MARGIN) * 320:].contiguous())[:, :, SPEC_MARGIN:].contiguous()
+    return sl, sr
+
+
+def _decoded_range(keep_frames, lf):
+    """the frames [lo, hi) that can reach the kept frames keep_frames of a window of lf frames through the decoder (None: all)"""
+    return None if keep_frames is None else (max(0, keep_frames[0] - TRIM_LEFT), min(lf, keep_frames[1] + TRIM_RIGHT))
+
+
+def prepare_networks(content_encoder, f0_estimator, decoder, device):
+    """the three networks on `device` with their weight tables packed and the decoder's precision mode calibrated for this
+    checkpoint (module/decoder.py) -- now, on the caller's stream: never lazily inside a window batch on a side stream or
+    inside a hipGraph capture"""
+    nets = content_encoder.to(device), f0_estimator.to(device), decoder.to(device)
+    for net in nets:
+        net.table()
+    if torch.device(device).type == "cuda":
+        nets[2]._split_for_this_checkpoint()
+    return nets
+
+
 class Converter:
     def __init__(self, content_encoder: ContentEncoder, f0_estimator: F0Estimator, decoder: Decoder, device="cuda"):
         self.device = torch.device(device)
-        self.ce, self.pe, self.dec = content_encoder.to(device), f0_estimator.to(device), decoder.to(device)
+        self.ce, self.pe, self.dec = prepare_networks(content_encoder, f0_estimator, decoder, device)
         self.library = None
-        for net in (self.ce, self.pe, self.dec):       # pack the weight tables now, on the caller's stream (not lazily
-            net.table()                                # inside the first window batch, which runs on a side stream)
-        if self.device.type == "cuda":
-            self.dec._split_for_this_checkpoint()      # ... and calibrate the decoder's precision mode for this checkpoint (module/decoder.py)
 
     def set_library(self, tokens):
         """tokens [1, 768, M] (voice_library.pt layout) or an already packed PackedLibrary."""
@@ -91,14 +123,7 @@ class Converter:
         f0 estimator does not run."""
         if world_pitch:
             f0 = ops.pitch_transform_(compute_f0(windows), 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
-            spec = spectrogram(windows)
-            lf = spec.shape[2]
-            if frames is None:
-                feat = self.ce(spec)
-            else:
-                a, b = max(0, frames[0] - CE_MARGIN), min(lf, frames[1] + CE_MARGIN)
-                feat = torch.zeros(spec.shape[0], 768, lf, device=spec.device)
-                feat[:, :, a:b] = self.ce(spec[:, :, a:b].contiguous())
+            feat = self._encode(spectrogram(windows), frames)
             if out is not None:
                 out[0].copy_(feat)
                 out[1].copy_(f0)
@@ -109,11 +134,18 @@ class Converter:
         spec = spectrogram(windows)
         f0 = self.pe.estimate(spec, out=None if out is None else out[1])
         f0 = ops.pitch_transform_(f0, 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
+        return self._encode(spec, frames), f0
+
+    def _encode(self, spec, frames=None):
+        """content features of spectrograms [n, 513, lf].  frames = (lo, hi): the encoder runs on [lo - CE_MARGIN, hi + CE_MARGIN)
+        only (its receptive field around the frames that are needed); the frames outside come back as zeros"""
+        if frames is None:
+            return self.ce(spec)
         lf = spec.shape[2]
         a, b = max(0, frames[0] - CE_MARGIN), min(lf, frames[1] + CE_MARGIN)
         feat = torch.zeros(spec.shape[0], 768, lf, device=spec.device)
         feat[:, :, a:b] = self.ce(spec[:, :, a:b].contiguous())
-        return feat, f0
+        return feat
 
     def features_shared(self, windows, group, k=4, alpha=0.0, utt_batch=32, frames=None):
         """(matched content features [n, 768, lf], raw f0 [n, 1, lf]) of n = m * group windows, every `group` consecutive ones
@@ -131,9 +163,7 @@ class Converter:
         if frames is not None:
             return self._features_shared_range(windows, group, k, alpha, utt_batch, frames)
         m = n // group
-        w3 = windows.view(m, group, L)
-        # the padded signal of every group: first chunk of each window, then the last two chunks of the last one
-        sig = torch.cat([w3[:, :, :c].reshape(m, group * c), w3[:, -1, c:]], dim=1).contiguous()      # [m, (group + 2) c]
+        sig = _signals(windows, group)                         # [m, (group + 2) c]
         dev = windows.device
         feat = torch.empty(n, 768, lf, device=dev)
         f0 = torch.empty(n, 1, lf, device=dev)
@@ -141,13 +171,10 @@ class Converter:
         pu = torch.empty(m, 1, (group + 2) * cf, device=dev)
         for i in range(0, m, utt_batch):                       # interior frames: one pass over each signal
             ops.front_end(sig[i:i + utt_batch], self.ce, self.pe, out=(fu[i:i + utt_batch], pu[i:i + utt_batch]))
-        nl = EDGE + NET_MARGIN
         fe = torch.empty(n, 768, 2 * EDGE, device=dev)         # edge frames of every window: [0, EDGE) and [lf - EDGE, lf)
         pe_ = torch.empty(n, 1, 2 * EDGE, device=dev)
         for i, j in _edge_chunks(n, 8 * utt_batch):
-            w = windows[i:j]
-            sl = spectrogram(w[:, :(nl + SPEC_MARGIN) * 320].contiguous())[:, :, :nl].contiguous()
-            sr = spectrogram(w[:, L - (nl + SPEC_MARGIN) * 320:].contiguous())[:, :, SPEC_MARGIN:].contiguous()
+            sl, sr = _edge_specs(windows[i:j])
             fe[i:j, :, :EDGE] = self.ce(sl)[:, :, :EDGE]
             fe[i:j, :, EDGE:] = self.ce(sr)[:, :, NET_MARGIN:]
             pe_[i:j, :, :EDGE] = self.pe.estimate(sl)[:, :, :EDGE]
@@ -177,8 +204,7 @@ class Converter:
             raise ValueError(f"shared front end with a frame range needs {EDGE} <= r0 < r1 <= {lf - EDGE}, got {frames}")
         m = n // group
         nr = r1 - r0
-        w3 = windows.view(m, group, L)
-        sig = torch.cat([w3[:, :, :c].reshape(m, group * c), w3[:, -1, c:]], dim=1).contiguous()      # [m, (group + 2) c]
+        sig = _signals(windows, group)                         # [m, (group + 2) c]
         dev = windows.device
         tu = (group + 2) * cf
         u0, u1 = r0, (group - 1) * cf + r1                      # frames of a signal that some window's range holds
@@ -189,12 +215,9 @@ class Converter:
             spec = spectrogram(sig[i:i + utt_batch])
             pu[i:i + utt_batch] = self.pe.estimate(spec)
             fu[i:i + utt_batch] = self.ce(spec[:, :, a:b].contiguous())[:, :, u0 - a:u1 - a]
-        nl = EDGE + NET_MARGIN
         f0 = torch.empty(n, 1, lf, device=dev)
         for i, j in _edge_chunks(n, 8 * utt_batch):            # f0 of the edge frames of every window
-            w = windows[i:j]
-            sl = spectrogram(w[:, :(nl + SPEC_MARGIN) * 320].contiguous())[:, :, :nl].contiguous()
-            sr = spectrogram(w[:, L - (nl + SPEC_MARGIN) * 320:].contiguous())[:, :, SPEC_MARGIN:].contiguous()
+            sl, sr = _edge_specs(windows[i:j])
             f0[i:j, :, :EDGE] = self.pe.estimate(sl)[:, :, :EDGE]
             f0[i:j, :, lf - EDGE:] = self.pe.estimate(sr)[:, :, NET_MARGIN:]
         nu = u1 - u0
@@ -237,7 +260,7 @@ class Converter:
         # (the edge blocks of all windows form one launch of n x 30 frame columns: below 96 columns the library would switch
         # to its streaming kernels, which round differently from the plane GEMMs the windows themselves run on -- then the
         # per-window front end is used, so that the result never depends on the flag)
-        rng = None if keep_frames is None else (max(0, keep_frames[0] - TRIM_LEFT), min(lf, keep_frames[1] + TRIM_RIGHT))
+        rng = _decoded_range(keep_frames, lf)
         # sharing and trimming together need the trimmed range to consist of interior frames of the signal (it does for the
         # centre third of a 3-chunk window from 46 frames per chunk on); otherwise trimming alone is used -- same samples
         share_ok = bool(share_overlap) and n * (EDGE + NET_MARGIN) >= 96 and not world_pitch
@@ -245,76 +268,67 @@ class Converter:
             # share_overlap = windows per signal (make_windows order): front end once per signal, decoder per window
             feat, f0 = self.features_shared(windows, int(share_overlap), k, alpha, frames=rng)
             f0 = ops.pitch_transform_(f0, 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
-            out = torch.empty_like(windows) if rng is None else torch.zeros_like(windows)
-            cur = torch.cuda.current_stream()
-            side = self._side_streams(windows.device)
+            return self._decode(windows, feat, f0, rng, window_batch)
 
-            def dec_shared(i):
-                if rng is None:
-                    self.dec(feat[i:i + window_batch], f0[i:i + window_batch], out=out[i:i + window_batch])
-                else:       # feat holds frames [rng[0], rng[1]) only; samples outside the range are not kept by the caller
-                    out[i:i + window_batch, rng[0] * 320:rng[1] * 320] = self.dec.forward_range(
-                        feat[i:i + window_batch], f0[i:i + window_batch], rng[0])
-            for j, i in enumerate(range(0, n, window_batch)):
-                st = side[j % len(side)] if side else None
-                if st is None:
-                    dec_shared(i)
-                    continue
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    dec_shared(i)
-            for st in side:
-                cur.wait_stream(st)
-            return out
-        feat = torch.empty(n, 768, lf, device=windows.device)
-        f0 = torch.empty(n, 1, lf, device=windows.device)
-
-        # Window batches are independent before and after the match: they go round-robin onto side streams (scratch is per
-        # stream, module/_native.py::Workspace), so that the tail of one batch's kernels overlaps the next batch's -- the
-        # kernels of a batch differ widely in what bounds them.  Same kernels on the same data: results are unchanged.
-        def batches(fn):
-            cur = torch.cuda.current_stream()
-            side = self._side_streams(windows.device)
-            for j, i in enumerate(range(0, n, window_batch)):
-                if not side:
-                    fn(i)
-                    continue
-                st = side[j % len(side)]
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    fn(i)
-            for st in side:
-                cur.wait_stream(st)
-
-        def enc(i):
+        def encode(i, feat, f0):                            # the pitch transform included (features)
+            b = slice(i, i + window_batch)
             if rng is None:                                 # the networks write straight into the batch's slices
-                self.features(windows[i:i + window_batch], pitch_shift, intonation, f0_rate,
-                              out=(feat[i:i + window_batch], f0[i:i + window_batch]), world_pitch=world_pitch)
-                return
-            feat[i:i + window_batch], f0[i:i + window_batch] = self.features(windows[i:i + window_batch], pitch_shift,
-                                                                           intonation, f0_rate, frames=rng,
-                                                                           world_pitch=world_pitch)
-        batches(enc)
-        if rng is None:
-            feat = self.match(feat, k, alpha)
-        else:
+                self.features(windows[b], pitch_shift, intonation, f0_rate, out=(feat[b], f0[b]), world_pitch=world_pitch)
+            else:
+                feat[b], f0[b] = self.features(windows[b], pitch_shift, intonation, f0_rate, frames=rng, world_pitch=world_pitch)
+
+        def match(feat):                                    # (ShardedConverter overrides self.match)
+            if rng is None:
+                return self.match(feat, k, alpha)
             feat[:, :, rng[0]:rng[1]] = self.match(feat[:, :, rng[0]:rng[1]].contiguous(), k, alpha)
-        if rng is None:
-            out = torch.empty_like(windows)
+            return feat[:, :, rng[0]:rng[1]]
+        return self._convert_per_window(windows, rng, window_batch, encode, match)
 
-            def dec(i):
-                self.dec(feat[i:i + window_batch], f0[i:i + window_batch], out=out[i:i + window_batch])
-            batches(dec)
-            return out
-        # decode the matched range only (the oscillator still accumulates phase over the whole window); samples outside it
-        # are not kept by the caller and stay zero
-        out = torch.zeros_like(windows)
+    def _convert_per_window(self, windows, rng, window_batch, encode, match, transform=None):
+        """The per-window front end of `convert_windows` and `convert_many`: encode(i, feat, f0) writes the content features and
+        the f0 of the window batch that starts at i into feat [n, 768, lf] / f0 [n, 1, lf]; transform(f0) then applies the
+        pitch transform to every window at once (None: encode did); match(feat) returns the matched features of the frames
+        rng = [lo, hi) of every window (of all frames: rng None), ONE match over all windows; the decoder runs per batch."""
+        n, L = windows.shape
+        feat = torch.empty(n, 768, L // 320, device=windows.device)
+        f0 = torch.empty(n, 1, L // 320, device=windows.device)
+        self._window_batches(n, window_batch, windows.device, lambda i: encode(i, feat, f0))
+        if transform is not None:
+            transform(f0)
+        return self._decode(windows, match(feat), f0, rng, window_batch)
 
-        def dec_range(i):
-            out[i:i + window_batch, rng[0] * 320:rng[1] * 320] = self.dec.forward_range(
-                feat[i:i + window_batch, :, rng[0]:rng[1]].contiguous(), f0[i:i + window_batch], rng[0])
-        batches(dec_range)
+    def _decode(self, windows, feat, f0, rng, window_batch):
+        """matched features and transformed f0 of the windows -> output windows [n, L], decoded per window batch.  With a range
+        rng = (lo, hi) feat holds frames [lo, hi) only and only they are decoded (the oscillator still accumulates phase over
+        the whole window); samples outside them are not kept by the caller and stay zero."""
+        out = torch.empty_like(windows) if rng is None else torch.zeros_like(windows)
+
+        def dec(i):
+            b = slice(i, i + window_batch)
+            if rng is None:
+                self.dec(feat[b], f0[b], out=out[b])
+            else:
+                out[b, rng[0] * 320:rng[1] * 320] = self.dec.forward_range(feat[b].contiguous(), f0[b], rng[0])
+        self._window_batches(windows.shape[0], window_batch, windows.device, dec)
         return out
+
+    def _window_batches(self, n, window_batch, device, fn):
+        """fn(i) for the window batches [i, i + window_batch) of n windows.  Window batches are independent before and after the
+        match: they go round-robin onto side streams (scratch is per stream, module/_native.py::Workspace), so that the tail of
+        one batch's kernels overlaps the next batch's -- the kernels of a batch differ widely in what bounds them.  Same kernels
+        on the same data: results are unchanged.  The caller's stream then waits for all of them."""
+        cur = torch.cuda.current_stream()
+        side = self._side_streams(device)
+        for j, i in enumerate(range(0, n, window_batch)):
+            if not side:
+                fn(i)
+                continue
+            st = side[j % len(side)]
+            st.wait_stream(cur)
+            with torch.cuda.stream(st):
+                fn(i)
+        for st in side:
+            cur.wait_stream(st)
 
     def _side_streams(self, device):
         """side streams of the window batches (ALIVE_STREAMS, default 3; 1 = everything on the caller's stream)"""
@@ -394,77 +408,34 @@ class Converter:
         on = [bool(w) for w, c in zip(worlds, counts) for _ in range(c)]
         params["world"] = {i: torch.tensor([j - i for j in range(i, min(i + window_batch, len(on))) if on[j]], dtype=torch.int64,
                                            device=self.device) for i in range(0, len(on), window_batch) if any(on[i:i + window_batch])}
-        keep = (chunk // 320, 2 * chunk // 320) if trim_context else None
+        rng = _decoded_range((chunk // 320, 2 * chunk // 320) if trim_context else None, windows.shape[1] // 320)
+
+        def encode(i, feat, f0):
+            b = slice(i, i + window_batch)
+            if rng is None:
+                ops.front_end(windows[b], self.ce, self.pe, out=(feat[b], f0[b]))
+            else:
+                spec = spectrogram(windows[b])
+                f0[b] = self.pe.estimate(spec)
+                feat[b] = self._encode(spec, rng)
+            w = params["world"].get(i)
+            if w is not None:               # WORLD's f0 of the whole windows replaces the estimator's (same stream: after it)
+                f0[b].index_copy_(0, w, compute_f0(windows[b].index_select(0, w)))
+
+        def transform(f0):                  # each utterance's pitch, intonation and f0 rate (features(world_pitch=True))
+            MS.pitch_transform_rows_(f0, 0, params["rate"], params["shift"], params["inton"])
+
+        def match(feat):
+            src = feat if rng is None else feat[:, :, rng[0]:rng[1]].contiguous()
+            val, idx = MS.knn_search_pool(src, pool, params["ids"], k)
+            return MS.merge_gather_rows(val, idx, k, params["alpha"], pool.rows, src)
         out = ops.Fp16Guard(self._agree_on_saturations()).run(
-            lambda: self._convert_many_windows(windows, pool, params, k, window_batch, keep))
+            lambda: self._convert_per_window(windows, rng, window_batch, encode, match, transform))
         res, i = [], 0
         for c, total in zip(counts, totals):
             res.append(stitch(out[i:i + c], total, chunk))
             i += c
         return res
-
-    def _convert_many_windows(self, windows, pool, p, k, window_batch, keep_frames):
-        """`_convert_windows` (per-window front end) with per-window voice, alpha and pitch parameters.  p["world"]: window batch
-        start -> its WORLD windows' rows: their f0 (compute_f0 of the gathered whole windows) replaces the estimator's before the
-        per-row transform, which applies each utterance's pitch, intonation and f0 rate (features(world_pitch=True))"""
-        from . import multistream as MS
-        n, L = windows.shape
-        lf = L // 320
-        rng = None if keep_frames is None else (max(0, keep_frames[0] - TRIM_LEFT), min(lf, keep_frames[1] + TRIM_RIGHT))
-        feat = torch.empty(n, 768, lf, device=windows.device)
-        f0 = torch.empty(n, 1, lf, device=windows.device)
-
-        def batches(fn):
-            cur = torch.cuda.current_stream()
-            side = self._side_streams(windows.device)
-            for j, i in enumerate(range(0, n, window_batch)):
-                if not side:
-                    fn(i)
-                    continue
-                st = side[j % len(side)]
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    fn(i)
-            for st in side:
-                cur.wait_stream(st)
-
-        def enc(i):
-            sl = slice(i, i + window_batch)
-            if rng is None:
-                ops.front_end(windows[sl], self.ce, self.pe, out=(feat[sl], f0[sl]))
-                return
-            spec = spectrogram(windows[sl])
-            f0[sl] = self.pe.estimate(spec)
-            a, b = max(0, rng[0] - CE_MARGIN), min(lf, rng[1] + CE_MARGIN)
-            fe = torch.zeros(spec.shape[0], 768, lf, device=spec.device)
-            fe[:, :, a:b] = self.ce(spec[:, :, a:b].contiguous())
-            feat[sl] = fe
-
-        def enc_world(i):
-            enc(i)
-            w = p["world"].get(i)
-            if w is not None:                                   # (same stream: after the estimator wrote the batch's f0)
-                sl = slice(i, i + window_batch)
-                f0[sl].index_copy_(0, w, compute_f0(windows[sl].index_select(0, w)))
-        batches(enc_world)
-        MS.pitch_transform_rows_(f0, 0, p["rate"], p["shift"], p["inton"])
-        src = feat if rng is None else feat[:, :, rng[0]:rng[1]].contiguous()
-        val, idx = MS.knn_search_pool(src, pool, p["ids"], k)
-        matched = MS.merge_gather_rows(val, idx, k, p["alpha"], pool.rows, src)
-        if rng is None:
-            out = torch.empty_like(windows)
-
-            def dec(i):
-                self.dec(matched[i:i + window_batch], f0[i:i + window_batch], out=out[i:i + window_batch])
-            batches(dec)
-            return out
-        out = torch.zeros_like(windows)
-
-        def dec_range(i):
-            out[i:i + window_batch, rng[0] * 320:rng[1] * 320] = self.dec.forward_range(
-                matched[i:i + window_batch], f0[i:i + window_batch], rng[0])
-        batches(dec_range)
-        return out
 
     @staticmethod
     def check_fp16_range():

@@ -9,6 +9,7 @@ import torch
 
 from . import audio_io, ops
 from .common import PackedLibrary, compute_f0, merge_gather
+from .pipeline import prepare_networks
 from .spectrogram import spectrogram
 
 
@@ -45,28 +46,81 @@ def reuse_rows(frames):
     return 1 if frames < PLANES_MIN_COLS else -(-PLANES_MIN_COLS // blk)
 
 
+def ring_geometry(chunk, buffersize, input_sr, output_sr):
+    """realtime_inference.py:122-126: (begin_of_output, end_of_output, frames) of a ring of `buffersize` chunks of `chunk`
+    samples at input_sr, converted to output_sr"""
+    internal_chunk = int(chunk * (16000 / output_sr))
+    center = int(internal_chunk * buffersize) // 2
+    frames = (chunk * buffersize * 16000 // input_sr) // 320
+    if frames < 5:
+        raise ValueError(f"ring of {buffersize} x {chunk} samples is {frames} frames; the decoder needs >= 5 "
+                         "(reflection pad 4 on the bottleneck: module/decoder.py:165 of the reference)")
+    return center - internal_chunk // 2, center + internal_chunk // 2, frames
+
+
+def fp16_guarded(cols):
+    """Steps of 96 frame columns or more (rings x frames) run the batch kernels and with them the fp16 forms of the encoder /
+    decoder GEMMs (modes 1): `step()` then reads the saturation counters after every chunk (it has just synchronised for the PCM
+    copy).  Shorter steps -- the reference's defaults -- run the fp32-activation streaming kernels, which write no fp16 plane:
+    nothing to guard."""
+    return cols >= PLANES_MIN_COLS and (ops.encoder_precision(0) != 2 or ops.decoder_precision(0) != 2)
+
+
+def f0_on_side_stream(conv, spec, body):
+    """The f0 estimator (+ the pitch transform) needs nothing but the spectrogram and feeds nothing before the decoder: its ~35
+    dependent launches run on a side stream beside the content encoder and the match (a step is a chain of ~150 small kernels,
+    bound by their latencies, not by the chip).  body(buf) computes the transformed f0 [N, 1, F] of `spec` [N, 513, F] into
+    `buf` on that stream.  Returns (f0, join): the f0 tensor -- `buf` is a persistent buffer per shape (at most four shapes are
+    kept: a converter has one ring geometry and two slice geometries), so that the steady-state step allocates nothing on the
+    side stream (the estimator's scratch is sized by the eager warm-up steps that precede hipGraph capture: capture_step) -- and
+    the call that makes the current stream wait for it.  The buffer is overwritten by the next call with the same shape: a
+    `last_f0` that aliases it is valid until the next step.  Same kernels, same results; captured into the step's hipGraph as
+    a parallel branch.  The side stream and the buffers are the converter's `_side` and `_f0_bufs`."""
+    cur = torch.cuda.current_stream(spec.device)
+    if conv._side is None:
+        conv._side = torch.cuda.Stream(device=spec.device)
+    key = (spec.shape[0], spec.shape[2])
+    buf = conv._f0_bufs.get(key)
+    if buf is None:
+        if len(conv._f0_bufs) >= 4:
+            conv._f0_bufs.pop(next(iter(conv._f0_bufs)))
+        buf = conv._f0_bufs[key] = torch.empty(spec.shape[0], 1, spec.shape[2], device=spec.device)
+    side = conv._side
+    side.wait_stream(cur)                                   # the spectrogram is complete
+    with torch.cuda.stream(side):
+        f0 = body(buf)
+    return f0, (lambda: cur.wait_stream(side))
+
+
+def capture_step(device, step, phi):
+    """Capture one streaming step into a hipGraph: step() -> (wave, phi_next) runs twice eagerly on a side stream first, so that
+    every scratch buffer reaches its steady-state size (the C ABI never allocates or synchronises inside the capture), then once
+    under capture with phi_next copied into `phi`.  Returns (graph, the captured step's wave)."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        wave, phi_next = step()
+        phi.copy_(phi_next)
+    return graph, wave
+
+
 class RealtimeConverter:
     def __init__(self, content_encoder, f0_estimator, decoder, library_tokens, device="cuda", chunk=960, buffersize=8,
                  input_sr=16000, output_sr=16000, f0_rate=1.0, pitch=0.0, k=4, alpha=0.0, gain=0.0, input_gain=0.0,
                  reuse_interior="auto", world_pitch=False):
         self.device = torch.device(device)
-        self.ce, self.pe, self.dec = content_encoder.to(device), f0_estimator.to(device), decoder.to(device)
-        for net in (self.ce, self.pe, self.dec):
-            net.table()                                # weight tables packed up front (never inside a captured step)
-        self.dec._split_for_this_checkpoint()          # precision calibration of this checkpoint, also never inside a capture
+        self.ce, self.pe, self.dec = prepare_networks(content_encoder, f0_estimator, decoder, device)
         self.lib = library_tokens if isinstance(library_tokens, PackedLibrary) else PackedLibrary(library_tokens[0].to(device))
         self.chunk, self.buffersize = chunk, buffersize
         self.input_sr, self.output_sr = input_sr, output_sr
         self.f0_rate, self.pitch, self.k, self.alpha, self.gain, self.input_gain = f0_rate, pitch, k, alpha, gain, input_gain
-        # realtime_inference.py:122-126
-        internal_chunk = int(chunk * (16000 / output_sr))
-        center = int(internal_chunk * buffersize) // 2
-        self.end_of_output = center + internal_chunk // 2
-        self.begin_of_output = center - internal_chunk // 2
-        frames = (chunk * buffersize * 16000 // input_sr) // 320
-        if frames < 5:
-            raise ValueError(f"ring of {buffersize} x {chunk} samples is {frames} frames; the decoder needs >= 5 "
-                             "(reflection pad 4 on the bottleneck: module/decoder.py:165 of the reference)")
+        self.begin_of_output, self.end_of_output, frames = ring_geometry(chunk, buffersize, input_sr, output_sr)
         self.ring = []
         self.phi = 0
         self._graph = None
@@ -92,7 +146,7 @@ class RealtimeConverter:
         self.reuse = bool(fits and reuse_interior in (True, "auto"))
         self._rows = reuse_rows(frames)
         self._cache_valid = False
-        if self._fp16_guarded():
+        if fp16_guarded(frames):
             ops.f16_clear()                # stale counts of earlier work in this process are not this stream's
         if self.reuse:
             self._c_feat = torch.zeros(1, 768, frames, device=self.device)      # matched features of the ring's frames
@@ -104,52 +158,27 @@ class RealtimeConverter:
         if self.reuse:
             return self._device_step_reuse(data, phi)
         data = audio_io.resample(data, self.input_sr, 16000, post_gain_db=self.input_gain)     # resample, then gain (:146-147)
-        spec = spectrogram(data)
-        f0, join = self._f0_on_side_stream(spec, data)
-        content = self.ce(spec)
-        val, idx = self.lib.search(content, self.k)
-        content = merge_gather(val, idx, 1, self.k, self.alpha, self.lib.rows, content)
-        join()
+        content, f0 = self._front_end(spectrogram(data), data)
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0                  # (a view of the per-shape side-stream buffer: valid until the next step)
         wave = audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain)[0]         # gain, then resample (:173-175)
         return wave, phi_out[:, :, self.end_of_output]
 
     def _f0_on_side_stream(self, spec, data=None):
-        """The f0 estimator (+ the pitch transform) needs nothing but the spectrogram and feeds nothing before the decoder: its ~35
-        dependent launches run on a side stream beside the content encoder and the match (a step is a chain of ~150 small kernels,
-        bound by their latencies, not by the chip).  Returns (f0, join): the f0 tensor -- a persistent buffer per shape (at most
-        four shapes are kept: a converter has one ring geometry and two slice geometries), so that the steady-state step allocates
-        nothing on the side stream (the estimator's scratch is sized by the eager warm-up steps that precede hipGraph capture:
-        enable_graph) -- and the call that makes the current stream wait for it.  The buffer is overwritten by the next call with
-        the same shape: `last_f0` of the non-reuse step aliases it and is valid until the next step.  Same kernels, same results;
-        captured into the step's hipGraph as a parallel branch.  With world_pitch the branch is WORLD's f0 of the 16-kHz ring
-        `data` instead, and the pitch transform leaves out f0_rate: the reference multiplies only the estimator's f0 by it
-        (realtime_inference.py:153-156)."""
-        cur = torch.cuda.current_stream(spec.device)
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=spec.device)
-        key = (spec.shape[0], spec.shape[2])
-        buf = self._f0_bufs.get(key)
-        if buf is None:
-            if len(self._f0_bufs) >= 4:
-                self._f0_bufs.pop(next(iter(self._f0_bufs)))
-            buf = self._f0_bufs[key] = torch.empty(spec.shape[0], 1, spec.shape[2], device=spec.device)
-        side = self._side
-        side.wait_stream(cur)                                   # the spectrogram is complete
-        with torch.cuda.stream(side):
+        """f0_on_side_stream with the estimator's f0 and the pitch transform.  With world_pitch the branch is WORLD's f0 of the
+        16-kHz ring `data` instead, and the pitch transform leaves out f0_rate: the reference multiplies only the estimator's f0
+        by it (realtime_inference.py:153-156)."""
+        def body(buf):
             if self.world_pitch:
                 buf.copy_(compute_f0(data))
-                f0 = ops.pitch_transform_(buf, 1, f0_rate=1.0, pitch_shift=self.pitch)
-            else:
-                f0 = self.pe.estimate(spec, out=buf)
-                f0 = ops.pitch_transform_(f0, 1, f0_rate=self.f0_rate, pitch_shift=self.pitch)
-        return f0, (lambda: cur.wait_stream(side))
+                return ops.pitch_transform_(buf, 1, f0_rate=1.0, pitch_shift=self.pitch)
+            f0 = self.pe.estimate(spec, out=buf)
+            return ops.pitch_transform_(f0, 1, f0_rate=self.f0_rate, pitch_shift=self.pitch)
+        return f0_on_side_stream(self, spec, body)
 
-    def _front_end(self, data):
-        """16 kHz ring [1, n] -> (matched content [1, 768, F], transformed f0 [1, 1, F]) for every frame"""
-        spec = spectrogram(data)
-        f0, join = self._f0_on_side_stream(spec)
+    def _front_end(self, spec, data=None):
+        """spectrogram [R, 513, F] (of the 16 kHz ring `data`) -> (matched content [R, 768, F], transformed f0 [R, 1, F])"""
+        f0, join = self._f0_on_side_stream(spec, data)
         content = self.ce(spec)
         val, idx = self.lib.search(content, self.k)
         out = merge_gather(val, idx, 1, self.k, self.alpha, self.lib.rows, content)
@@ -162,7 +191,7 @@ class RealtimeConverter:
         F_, s = self.frames, self.shift
         data = data if self.input_gain == 0 else audio_io.gain(data, self.input_gain)
         if not self._cache_valid:
-            feat, f0 = self._front_end(data)
+            feat, f0 = self._front_end(spectrogram(data))
             self._c_feat.copy_(feat)
             self._c_f0.copy_(f0)
             self._cache_valid = True
@@ -191,12 +220,7 @@ class RealtimeConverter:
         samples = samples.contiguous()
         if self._rows > 1:                                  # identical rows: same kernels as the full ring (see the header)
             samples = samples.expand(self._rows, -1).contiguous()
-        spec = spectrogram(samples)[:, :, f_lo:f_hi].contiguous()
-        f0, join = self._f0_on_side_stream(spec)
-        content = self.ce(spec)
-        val, idx = self.lib.search(content, self.k)
-        out = merge_gather(val, idx, 1, self.k, self.alpha, self.lib.rows, content)
-        join()
+        out, f0 = self._front_end(spectrogram(samples)[:, :, f_lo:f_hi].contiguous())
         return out[:1], f0[:1].clone()                   # (f0 lives in a per-shape buffer the next slice overwrites)
 
     def enable_graph(self):
@@ -205,18 +229,7 @@ class RealtimeConverter:
         n = self.chunk * self.buffersize
         self._g_in = torch.zeros(1, n, device=self.device)
         self._g_phi = torch.zeros(1, 64, device=self.device)
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._device_step(self._g_in, self._g_phi)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            wave, phi_next = self._device_step(self._g_in, self._g_phi)
-            self._g_phi.copy_(phi_next)
-            self._g_out = wave
+        self._graph, self._g_out = capture_step(self.device, lambda: self._device_step(self._g_in, self._g_phi), self._g_phi)
         self._g_phi.zero_()
         self._cache_valid = False          # interior reuse: the captured step is the incremental one; the first real step runs in full
         return self
@@ -253,22 +266,10 @@ class RealtimeConverter:
         self.phi = phi_next
         return wave
 
-    def _fp16_guarded(self):
-        """Rings of 96 frames or more run the batch kernels and with them the fp16 forms of the encoder / decoder GEMMs (modes 1):
-        `step()` then reads the saturation counters after every chunk (it has just synchronised for the PCM copy).  Shorter rings --
-        the reference's defaults -- run the fp32-activation streaming kernels, which write no fp16 plane: nothing to guard."""
-        return self.frames >= PLANES_MIN_COLS and (ops.encoder_precision(0) != 2 or ops.decoder_precision(0) != 2)
-
     def _repeat_on_bf16(self, data, saved_phi):
-        """a chunk drove an activation out of fp16's range: switch the process to precision modes 2 (bf16 planes, fp32's range -- a
-        stream that saturates once will do so again, so the modes stay), restore the phase the chunk started from, drop the frame
-        caches, re-capture the step if it was a hipGraph, and convert the chunk again"""
-        import warnings
-        warnings.warn("an activation left fp16's range in the streaming step: switching to ALIVE_ENCODER_PRECISION=2 / "
-                      "ALIVE_DECODER_PRECISION=2 (bf16 planes) and converting the chunk again", RuntimeWarning)
-        ops.Fp16Guard.fallbacks += 1
-        ops.encoder_precision(2)
-        ops.decoder_precision(2)
+        """a chunk drove an activation out of fp16's range: switch the process to bf16 planes (ops.switch_to_bf16), restore the
+        phase the chunk started from, drop the frame caches, re-capture the step if it was a hipGraph, and convert the chunk again"""
+        ops.switch_to_bf16("streaming step", "chunk")
         self._cache_valid = False
         if getattr(self, "_graph", None) is not None:
             self.enable_graph()
@@ -288,12 +289,12 @@ class RealtimeConverter:
             return None
         data = torch.from_numpy(np.concatenate(self.ring, 0)).to(self.device)
         data = audio_io.pcm16_to_float(data).unsqueeze(0)            # / 32768 on the device (:139-140)
-        guarded = self._fp16_guarded()
+        guarded = fp16_guarded(self.frames)
         if guarded:
             saved_phi = self._g_phi.clone() if getattr(self, "_graph", None) is not None else self.phi
         wave = self.step_device(data, continues=True)                # this ring is the previous one advanced by one chunk
         out = audio_io.float_to_pcm16(wave).cpu().numpy()            # C cast of numpy's astype, no clipping (:180-183)
-        if guarded and ops.f16_saturations(reset=True) > 0:          # (the copy above has synchronised: five 4-byte reads)
+        if guarded and ops.f16_saturations(reset=True) > 0:          # (the copy above has synchronised: six 4-byte reads)
             out = self._repeat_on_bf16(data, saved_phi)
         center = self.buffersize * self.chunk // 2
         return out[center - self.chunk // 2: center + self.chunk // 2]
