@@ -9,9 +9,11 @@ The jobs file is a JSON list; each entry:
    "gain": 1, "normalize": false,                           optional, inference.py's -g / -norm
    "world_pitch": false,                                    optional, a JSON bool: inference.py's -wpe (WORLD's f0 of each
                                                             window; pitch, intonation and f0_rate apply to it)
+   "blend": [{"target": "a.wav", "weight": 2},              instead of "target" / "lib": a weighted mix of 1 to 4 voices, each
+             {"lib": "b.pt", "weight": 1}],                 component a voice source as above (module/multistream.py blend_spec)
    "output": "a_out.wav"}                                   optional: default <outdir>/<index>_<input name>.wav
-Jobs naming the same voice sources share one voice of the pool.  Every file keeps inference.py's edges: loaded, resampled to
-16 kHz, normalised by its maximum, mono mean; the output resampled back to the file's own rate, gain, optional normalisation.
+Jobs and blend components naming the same voice sources share one voice of the pool.  Every file keeps inference.py's edges:
+loaded, resampled to 16 kHz, normalised by its maximum, mono mean; the output resampled back to the file's own rate, gain, optional normalisation.
 Each output is bitwise what `inference.py --knn-strict` (with `-wpe True` for a WORLD job) writes for that file, voice and
 settings; WORLD and estimator jobs mix freely in one run.
 Flags shared with inference.py keep its spelling: -c, -k, -d, -dep, -cep, -f0ep, --window-batch, --pcm16, --no-trim-context.
@@ -26,9 +28,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from module import audio_io                                     # noqa: E402
-from module.multistream import MAX_K                             # noqa: E402
+from module.multistream import MAX_K, blend_sources              # noqa: E402
 
-JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "world_pitch", "output")
+JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "world_pitch", "output",
+            "blend")
 
 
 def build_parser():
@@ -66,24 +69,43 @@ def load_jobs(path, k=4):
         unknown = set(j) - set(JOB_KEYS)
         if unknown:
             raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: {JOB_KEYS})")
-        if j.get("target") is None and j.get("lib") is None:
+        blend = blend_sources(j, f"job {i}", rel) if "blend" in j else None
+        if blend is None and j.get("target") is None and j.get("lib") is None:
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
         if not isinstance(j.get("world_pitch", False), bool):
             raise ValueError(f"job {i}: \"world_pitch\" must be true or false, got {j['world_pitch']!r}")
         e = dict(input=rel(j["input"]), target=rel(j.get("target")), lib=rel(j.get("lib")), output=rel(j.get("output")),
                  pitch=float(j.get("pitch", 0.0)), intonation=float(j.get("intonation", 1.0)), f0_rate=float(j.get("f0_rate", 1.0)),
                  alpha=float(j.get("alpha", 0.0)), gain=float(j.get("gain", 1.0)), normalize=bool(j.get("normalize", False)),
-                 world_pitch=j.get("world_pitch", False))
+                 world_pitch=j.get("world_pitch", False), blend=blend)
         for key in ("input", "target", "lib"):
             if e[key] is not None and not os.path.isfile(e[key]):
                 raise ValueError(f"job {i}: {key} {e[key]!r} does not exist")
+        for c, (tgt, lib, _) in enumerate(blend or ()):
+            for key, f in (("target", tgt), ("lib", lib)):
+                if f is not None and not os.path.isfile(f):
+                    raise ValueError(f"job {i}: blend component {c}: {key} {f!r} does not exist")
         out.append(e)
     return out
 
 
 def voice_key(job):
-    """jobs with the same voice sources share one pool voice"""
+    """jobs (and blend components: (target, lib, weight)) with the same voice sources share one pool voice"""
+    if isinstance(job, tuple):
+        return (job[0], job[1])
     return (job["target"], job["lib"])
+
+
+def voice_keys(job):
+    """the voice sources a job needs: its own, or those of its blend's components"""
+    return [voice_key(c) for c in job["blend"]] if job.get("blend") else [voice_key(job)]
+
+
+def job_voice(job, names):
+    """the job's voice for Converter.convert_many: a pool name, or (name, weight) pairs for a blend"""
+    if job.get("blend"):
+        return [(names[voice_key(c)], c[2]) for c in job["blend"]]
+    return names[voice_key(job)]
 
 
 def check_voice_sizes(sizes, k):
@@ -115,19 +137,19 @@ def main(argv=None):
     os.makedirs(args.outputs, exist_ok=True)
 
     voices = {}
-    for job in jobs:                                  # inference.py:86-92 per distinct voice
-        key = voice_key(job)
+    for key in (key for job in jobs for key in voice_keys(job)):        # inference.py:86-92 per distinct voice
         if key in voices:
             continue
+        target, lib = key
         tgt = torch.zeros(1, 768, 0, device=device)
-        if job["target"] is not None:
-            wf, sr = audio_io.load(job["target"])
+        if target is not None:
+            wf, sr = audio_io.load(target)
             wf = audio_io.resample(wf.to(device), sr, 16000)
             wf = wf / wf.abs().max()
             tgt = CE(spectrogram(wf[:1]))
-        if job["lib"] is not None:
+        if lib is not None:
             VL = VoiceLibrary().to(device)
-            VL.load_state_dict(torch.load(job["lib"], map_location=device))
+            VL.load_state_dict(torch.load(lib, map_location=device))
             tgt = torch.cat([tgt, VL.tokens], dim=2)
         voices[key] = tgt
     check_voice_sizes({k_: int(t.shape[2]) for k_, t in voices.items()}, args.k)
@@ -143,7 +165,7 @@ def main(argv=None):
         utts.append(wf.mean(dim=0, keepdim=True))
         rates.append(sr)
     conv = Converter(CE, PE, Dec, device)
-    outs = conv.convert_many(utts, pool, [names[voice_key(j)] for j in jobs], pitch_shift=[j["pitch"] for j in jobs],
+    outs = conv.convert_many(utts, pool, [job_voice(j, names) for j in jobs], pitch_shift=[j["pitch"] for j in jobs],
                              intonation=[j["intonation"] for j in jobs], f0_rate=[j["f0_rate"] for j in jobs],
                              alpha=[j["alpha"] for j in jobs], world_pitch=[j["world_pitch"] for j in jobs], chunk=args.chunk, k=args.k, window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)

@@ -2352,13 +2352,19 @@ __global__ __launch_bounds__(256) void knn_grouped_merge_kernel(int T, int k, Gr
 // ROWS (alive_knn_merge_gather_rows, one shard): alpha of window n from alpha_rows[n], 1 - alpha formed in double and rounded
 // once as the host does for the scalar form; a frame without a match (idx -1: an inactive slot of the grouped search) passes
 // its source through.
-template <int NPER, int KMAX, bool ROWS = false>
+// LISTS > 1 (alive_knn_blend_gather_rows, with ROWS): output row n owns the list rows first[n] .. first[n+1]-1 (at most LISTS),
+// each a one-shard top-k list [list row * T + t][k] with a weight; phase 1 copies them into the per-list table sel[s], phase 2
+// forms each active list's mean as the one-list form does and sums them weighted, in list order, before the alpha blend.
+template <int NPER, int KMAX, bool ROWS = false, int LISTS = 1>
 __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __restrict__ cand_val,
                                                                const int* __restrict__ cand_idx, int S, int k, float alpha,
                                                                float one_minus, const float* __restrict__ rows, const float* __restrict__ src,
                                                                int T, int64_t Tt, float* __restrict__ out,
-                                                               int* __restrict__ final_idx, const double* __restrict__ alpha_rows = nullptr) {
-    __shared__ int sel[32][KMAX];
+                                                               int* __restrict__ final_idx, const double* __restrict__ alpha_rows = nullptr,
+                                                               const int* __restrict__ first = nullptr, const double* __restrict__ weight = nullptr) {
+    constexpr bool BLEND = LISTS > 1;
+    static_assert(!BLEND || ROWS, "the blend form takes a per-row alpha");
+    __shared__ int sel[LISTS][32][KMAX];
     __shared__ float tile[32][65];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = blockIdx.y;
@@ -2369,6 +2375,61 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
     }
     const int t0 = blockIdx.x * 32;
     const int nf = (T - t0) < 32 ? (T - t0) : 32;
+
+    if constexpr (BLEND) {
+        // phase 1: the lists of row n, frames [t0, t0 + nf) of each are nf * k consecutive entries (a table outside
+        // [0, LISTS] lists per row is clamped: the LDS table never overflows)
+        const int l0 = first[n];
+        const int nl = min(max(first[n + 1] - l0, 0), LISTS);
+        float wgt[LISTS];
+#pragma unroll
+        for (int s = 0; s < LISTS; ++s) wgt[s] = s < nl ? (float)weight[l0 + s] : 0.0f;
+        const int per = nf * k;
+        for (int e = tid; e < nl * per; e += 256) {
+            const int s = e / per, r = e - s * per, f = r / k, j = r - f * k;
+            sel[s][f][j] = cand_idx[((size_t)(l0 + s) * T + t0) * k + r];
+        }
+        __syncthreads();
+
+        // phase 2: as below, with the weighted sum of the active lists' means in place of the one mean
+        const int d_begin = gridDim.z == 1 ? 0 : blockIdx.z * 64, d_end = gridDim.z == 1 ? D : d_begin + 64;
+        for (int d0 = d_begin; d0 < d_end; d0 += 64) {
+            for (int f = wv; f < nf; f += 4) {
+                float b = 0.0f;
+                bool any = false;
+#pragma unroll
+                for (int s = 0; s < LISTS; ++s) {
+                    if (s >= nl) break;
+                    if (sel[s][f][0] < 0) continue;                  // an inactive list contributes nothing
+                    float acc = 0.0f;
+                    for (int j = 0; j < k; ++j) {
+                        int idx = sel[s][f][j];
+                        float r = (idx >= 0) ? rows[(size_t)idx * D + d0 + lane] : __builtin_nanf("");
+                        acc = (j == 0) ? r : acc + r;
+                    }
+                    const float c = wgt[s] * (acc / (float)k);
+                    b = any ? b + c : c;
+                    any = true;
+                }
+                tile[f][lane] = b;
+            }
+            __syncthreads();
+            for (int e = tid; e < 64 * 32; e += 256) {
+                int f = e & 31, d = e >> 5;
+                if (f < nf) {
+                    size_t o = ((size_t)n * D + d0 + d) * T + t0 + f;
+                    bool any = false;
+#pragma unroll
+                    for (int s = 0; s < LISTS; ++s)
+                        if (s < nl && sel[s][f][0] >= 0) any = true;
+                    if (!any) out[o] = src[o];
+                    else out[o] = tile[f][d] * one_minus + src[o] * alpha;
+                }
+            }
+            __syncthreads();
+        }
+        return;
+    }
 
     // phase 1: each wave merges 8 frames; the S*k candidates of a frame sit NPER per lane
     for (int f = wv * 8; f < wv * 8 + 8; ++f) {
@@ -2388,7 +2449,7 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
         if (S == 1) {
             // a single shard: its list IS the merged list (sorted, -1 behind the last valid entry)
             if (lane < k) {
-                sel[f][lane] = id[0];
+                sel[0][f][lane] = id[0];
                 if (final_idx != nullptr && blockIdx.z == 0) final_idx[(size_t)ft * k + lane] = id[0];
             }
             continue;
@@ -2406,7 +2467,7 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
             int win = wave_argbest(bv, bi < 0 ? 0x7fffffff : bi);
             int wi = __shfl(bi, win);
             if (lane == 0) {
-                sel[f][j] = wi;
+                sel[0][f][j] = wi;
                 if (final_idx != nullptr && blockIdx.z == 0) final_idx[(size_t)ft * k + j] = wi;
             }
             if (lane == win) {
@@ -2425,7 +2486,7 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
         for (int f = wv; f < nf; f += 4) {
             float acc = 0.0f;
             for (int j = 0; j < k; ++j) {
-                int idx = sel[f][j];
+                int idx = sel[0][f][j];
                 float r = (idx >= 0) ? rows[(size_t)idx * D + d0 + lane] : __builtin_nanf("");
                 acc = (j == 0) ? r : acc + r;
             }
@@ -2437,7 +2498,7 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
             if (f < nf) {
                 size_t o = ((size_t)n * D + d0 + d) * T + t0 + f;
                 float m = tile[f][d];
-                if (ROWS && sel[f][0] < 0) out[o] = src[o];
+                if (ROWS && sel[0][f][0] < 0) out[o] = src[o];
                 else out[o] = m * one_minus + src[o] * alpha;
             }
         }
@@ -3701,6 +3762,23 @@ extern "C" int alive_knn_merge_gather_rows(const float* cand_val, const int32_t*
     knn_merge_gather_kernel<2, 8, true><<<g, 256, 0, (hipStream_t)stream>>>(cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T,
                                                                          (int64_t)N * T, out, final_idx, alpha);
     ALIVE_CHECK_LAUNCH("alive_knn_merge_gather_rows");
+    return ALIVE_OK;
+}
+
+// Voice blending: output row n mixes the means of its list rows first[n] .. first[n+1]-1 with their weights (the blend form of
+// knn_merge_gather_kernel: same grid forms as alive_knn_merge_gather_rows, a per-list table in LDS).  No allocation, no sync.
+extern "C" int alive_knn_blend_gather_rows(const float* cand_val, const int32_t* cand_idx, int k, const int32_t* first,
+                                           const double* weight, const double* alpha, const float* rows_f32_full, const float* src,
+                                           int N, int T, float* out, void* stream) {
+    ALIVE_CHECK_ARG(cand_val && cand_idx && first && weight && alpha && rows_f32_full && src && out,
+                    "alive_knn_blend_gather_rows: null pointer");
+    ALIVE_CHECK_ARG(k >= 1 && k <= 8, "alive_knn_blend_gather_rows: k=%d outside [1,8]", k);
+    ALIVE_CHECK_ARG(N >= 1 && T >= 1, "alive_knn_blend_gather_rows: N=%d, T=%d: empty source", N, T);
+    const int zs = (int64_t)cdiv(T, 32) * N < 64 ? D / 64 : 1;       // as alive_knn_merge_gather_rows
+    const dim3 g(cdiv(T, 32), N, zs);
+    knn_merge_gather_kernel<2, 8, true, ALIVE_MAX_BLEND><<<g, 256, 0, (hipStream_t)stream>>>(
+        cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T, (int64_t)N * T, out, nullptr, alpha, first, weight);
+    ALIVE_CHECK_LAUNCH("alive_knn_blend_gather_rows");
     return ALIVE_OK;
 }
 

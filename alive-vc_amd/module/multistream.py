@@ -22,6 +22,12 @@ world_pitch=True takes that f0 instead of the estimator's, as RealtimeConverter(
 ring (after the input resample and gain), the mode-1 transform with its pitch shift, and NOT its f0_rate (the reference
 multiplies only the estimator's f0 by it).  The mask and the per-row choice are device arrays: switching costs no re-capture.
 WORLD needs the whole ring: rings shorter than about 230 ms (-c 160 -b 16 is 160 ms) come out unvoiced.
+
+Voice blending: a session's voice may be a weighted mix of up to `blend` voices (blend_spec: the one rule set, shared with
+Converter.convert_many and both CLIs).  A converter built with blend=S > 1 gives slot b the S list rows b*S .. b*S+S-1: the content
+[B, 768, T] is replicated to [B*S, 768, T], the grouped search runs over the list rows' segments (unused rows at seg_len 0) and
+alive_knn_blend_gather_rows replaces merge_gather_rows, mixing each slot's list means with the device weights.  Blends, single
+voices and weights switch between ticks without a re-capture; blend=1 launches exactly the plain tick.
 """
 import numpy as np
 import torch
@@ -34,7 +40,83 @@ from .realtime import capture_step, f0_on_side_stream, fp16_guarded, ring_geomet
 from .spectrogram import spectrogram
 
 MAX_K = 8          # the grouped search keeps one register pair per lane and frame (csrc/knn.hip)
+MAX_BLEND = 4      # voices one blend may mix: lists per output row of alive_knn_blend_gather_rows (ALIVE_MAX_BLEND)
+MAX_ROWS = 1024    # rows of one grouped search (streaming: slots * blend)
+# the pool search's limits (alive_knn_search_pool: N <= 4096, N * T <= 2^20): convert_many searches the list rows of a blended
+# corpus in consecutive pieces within them -- the results are per frame, so the pieces are bitwise one call
+POOL_PIECE_ROWS, POOL_PIECE_FRAMES = 4096, 1 << 20
 _ws = nat.Workspace()
+
+
+def blend_spec(voice, pool=None, k=None, limit=MAX_BLEND):
+    """A voice or a blend -> (names, weights): the ONE place that checks and normalises a blend (both conversion paths and both
+    CLIs call it).  `voice` is a name (the blend {name: 1.0}), a {name: weight} dict or a sequence of (name, weight) pairs: 1 to
+    `limit` (<= MAX_BLEND) distinct names, weights finite, > 0 and not bool, normalised in float64 as w_s / sum(w) in the caller's
+    order (a single voice gets exactly 1.0).  With a pool, every name must be one of its voices with at least k vectors."""
+    if isinstance(voice, str):
+        items = [(voice, 1.0)]
+    elif isinstance(voice, dict):
+        items = list(voice.items())
+    elif isinstance(voice, (list, tuple)):
+        items = []
+        for c in voice:
+            if not isinstance(c, (list, tuple)) or len(c) != 2:
+                raise ValueError(f"a blend component is a (voice, weight) pair, got {c!r}")
+            items.append(tuple(c))
+    else:
+        raise ValueError(f"a voice is a name, a {{name: weight}} dict or (name, weight) pairs, got {voice!r}")
+    limit = min(int(limit), MAX_BLEND)
+    if not items:
+        raise ValueError("a blend needs at least one voice")
+    if len(items) > limit:
+        raise ValueError(f"a blend of {len(items)} voices: at most {limit} (MAX_BLEND = {MAX_BLEND})")
+    names, weights = [], []
+    for name, w in items:
+        if name in names:
+            raise ValueError(f"voice {name!r} appears twice in one blend")
+        if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, float, np.integer, np.floating)):
+            raise ValueError(f"blend weight of {name!r} must be a number, got {w!r}")
+        w = float(w)
+        if not np.isfinite(w) or w <= 0:
+            raise ValueError(f"blend weight of {name!r} must be finite and > 0, got {w!r}")
+        if pool is not None:
+            m = pool.segment(name)[1]
+            if k is not None and m < k:
+                raise ValueError(f"voice {name!r} has {m} vectors, fewer than k={k}")
+        names.append(name)
+        weights.append(w)
+    total = 0.0
+    for w in weights:
+        total += w
+    return tuple(names), tuple(w / total for w in weights)
+
+
+def blend_sources(entry, where, rel):
+    """the "blend" key of a jobs / sessions file entry -> [(target, lib, weight), ...]: each component is a voice source like an
+    entry's own "target" / "lib" (paths through `rel`) with a "weight", checked by blend_spec (the sources are the names);
+    ValueError on a malformed blend, before any device work"""
+    if entry.get("target") is not None or entry.get("lib") is not None:
+        raise ValueError(f"{where}: \"blend\" excludes a top-level \"target\" / \"lib\"")
+    comps = entry["blend"]
+    if not isinstance(comps, list) or not comps:
+        raise ValueError(f"{where}: \"blend\" must be a non-empty list of {{\"target\" / \"lib\", \"weight\"}} objects")
+    out = []
+    for i, c in enumerate(comps):
+        if not isinstance(c, dict):
+            raise ValueError(f"{where}: blend component {i} must be an object, got {c!r}")
+        unknown = set(c) - {"target", "lib", "weight"}
+        if unknown:
+            raise ValueError(f"{where}: blend component {i}: unknown keys {sorted(unknown)} (known: target, lib, weight)")
+        if c.get("target") is None and c.get("lib") is None:
+            raise ValueError(f"{where}: blend component {i} needs a \"target\" wav and / or a \"lib\" voice library")
+        if "weight" not in c:
+            raise ValueError(f"{where}: blend component {i} has no \"weight\"")
+        out.append((rel(c.get("target")), rel(c.get("lib")), c["weight"]))
+    try:
+        blend_spec([((t, lb), w) for t, lb, w in out])
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return out
 
 
 def _tokens_2d(tokens):
@@ -196,6 +278,18 @@ def merge_gather_rows(val, idx, k, alpha, rows, source):
     return out
 
 
+def blend_gather_rows(val, idx, k, first, weight, alpha, rows, source):
+    """the blend of output row n: the weighted sum of the means of its list rows first[n] .. first[n+1]-1 (device int32 [N+1];
+    weight: device float64 [first[N]]; val / idx: [first[N] * T, k] from a grouped or pool search of the list rows), then the
+    per-row alpha (device float64 [N]) as merge_gather_rows (csrc/knn.hip: alive_knn_blend_gather_rows)"""
+    n, d, t = source.shape
+    out = torch.empty_like(source)
+    nat.check(nat.lib().alive_knn_blend_gather_rows(nat.ptr(val), nat.ptr(idx), k, nat.ptr(first), nat.ptr(weight), nat.ptr(alpha),
+                                                    nat.ptr(rows), nat.ptr(source), n, t, nat.ptr(out), nat.stream()),
+              "alive_knn_blend_gather_rows")
+    return out
+
+
 def pitch_transform_rows_(f0, mode, f0_rate, pitch_shift, intonation):
     """in place on f0 [N, 1, T] with device float32 [N] parameters (ops.pitch_transform_ row by row)"""
     n, _, t = f0.shape
@@ -318,11 +412,16 @@ _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pi
 
 class MultiStreamConverter:
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
-                 output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False):
+                 output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1):
         if not 1 <= int(k) <= MAX_K:
             raise ValueError(f"MultiStreamConverter: k={k} outside [1, {MAX_K}] (the grouped search keeps k <= 8)")
-        if int(slots) < 1 or int(slots) > 1024:
-            raise ValueError(f"MultiStreamConverter: slots={slots} outside [1, 1024]")
+        if int(slots) < 1 or int(slots) > MAX_ROWS:
+            raise ValueError(f"MultiStreamConverter: slots={slots} outside [1, {MAX_ROWS}]")
+        if isinstance(blend, (bool, np.bool_)) or not isinstance(blend, (int, np.integer)) or not 1 <= blend <= MAX_BLEND:
+            raise ValueError(f"MultiStreamConverter: blend={blend!r} outside [1, {MAX_BLEND}]")
+        if int(slots) * int(blend) > MAX_ROWS:
+            raise ValueError(f"MultiStreamConverter: slots * blend = {int(slots) * int(blend)} list rows, the grouped search takes "
+                             f"at most {MAX_ROWS}")
         rates = sorted({int(r) for r in (rates or ())} | {int(input_sr)})
         if len(rates) > 1:
             if input_sr != output_sr:
@@ -368,9 +467,14 @@ class MultiStreamConverter:
             self._lw_rows = torch.full((B,), self._lw, **i32)
         self.ld_in = ld_in
         self.ring = np.zeros((B, ld_in), dtype=np.int16)
-        # per-slot state: device arrays the (captured) step reads
-        self.seg_lo = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.seg_len = torch.zeros(B, dtype=torch.int32, device=dev)
+        # per-slot state: device arrays the (captured) step reads.  blend = S > 1: slot b owns the S list rows b*S .. b*S+S-1 of
+        # the grouped search (unused ones at seg_len 0) with their weights; first = [0, S, 2S, ...] is fixed
+        self.S = int(blend)
+        self.seg_lo = torch.zeros(B * self.S, dtype=torch.int32, device=dev)
+        self.seg_len = torch.zeros(B * self.S, dtype=torch.int32, device=dev)
+        if self.S > 1:
+            self.first = torch.arange(0, B * self.S + 1, self.S, dtype=torch.int32, device=dev)
+            self.weight = torch.zeros(B * self.S, dtype=torch.float64, device=dev)
         self.alpha = torch.zeros(B, dtype=torch.float64, device=dev)
         self.f0_rate = torch.ones(B, dtype=torch.float32, device=dev)
         self.pitch = torch.zeros(B, dtype=torch.float32, device=dev)
@@ -405,16 +509,21 @@ class MultiStreamConverter:
         return int(slot)
 
     def _apply(self, slot, p):
-        lo, m = self.pool.segment(p["voice"])
-        if m < self.k:
-            raise ValueError(f"voice {p['voice']!r} has {m} vectors, fewer than k={self.k}")
+        names, weights = blend_spec(p["voice"], self.pool, self.k, self.S)
         world = p["world_pitch"]
         if not isinstance(world, (bool, np.bool_)):
             raise ValueError(f"slot {slot}: world_pitch must be a bool, got {world!r}")
         if world and not self.world_pitch:
             raise ValueError(f"slot {slot}: world_pitch=True needs a converter built with MultiStreamConverter(..., world_pitch=True)")
-        self.seg_lo[slot] = lo
-        self.seg_len[slot] = m
+        segs = [self.pool.segment(n) for n in names]
+        if self.S == 1:
+            self.seg_lo[slot], self.seg_len[slot] = segs[0]
+        else:                                                 # the slot's S list rows, unused ones inactive, in one write each
+            pad = self.S - len(segs)
+            rows = slice(slot * self.S, (slot + 1) * self.S)
+            self.seg_lo[rows] = torch.tensor([lo for lo, _ in segs] + [0] * pad, dtype=torch.int32)
+            self.seg_len[rows] = torch.tensor([m for _, m in segs] + [0] * pad, dtype=torch.int32)
+            self.weight[rows] = torch.tensor(list(weights) + [0.0] * pad, dtype=torch.float64)
         self.alpha[slot] = float(p["alpha"])
         self.f0_rate[slot] = float(p["f0_rate"])
         self.pitch[slot] = float(p["pitch"])
@@ -479,7 +588,7 @@ class MultiStreamConverter:
         self.params[slot] = None
         self.count[slot] = 0
         self.ring[slot] = 0
-        self.seg_len[slot] = 0
+        self.seg_len[slot * self.S:(slot + 1) * self.S] = 0
         self.phi[slot] = 0.0
         if self.world_pitch:
             self._set_world(slot, False, 1.0)
@@ -509,8 +618,14 @@ class MultiStreamConverter:
         spec = spectrogram(data)
         f0, join = self._f0_on_side_stream(spec, data)
         content = self.ce(spec)
-        val, idx = knn_search_grouped(content, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k)
-        content = merge_gather_rows(val, idx, self.k, self.alpha, self.pool.rows, content)
+        if self.S == 1:
+            val, idx = knn_search_grouped(content, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k)
+            content = merge_gather_rows(val, idx, self.k, self.alpha, self.pool.rows, content)
+        else:                                                 # every slot's content once per list row, then the blend
+            b, d, t = content.shape
+            rep = content.unsqueeze(1).expand(b, self.S, d, t).reshape(b * self.S, d, t).contiguous()     # (B = 1: a view)
+            val, idx = knn_search_grouped(rep, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k)
+            content = blend_gather_rows(val, idx, self.k, self.first, self.weight, self.alpha, self.pool.rows, content)
         join()
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0

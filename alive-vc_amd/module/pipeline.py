@@ -366,7 +366,11 @@ class Converter:
         batch may span utterances), and the match is ONE pool search over every window's frames, each window against its own
         voice (csrc/knn.hip: alive_knn_search_pool).  Utterance i comes out bitwise as `convert` with
         PackedLibrary(voice, strict=True) makes it alone -- unless the fp16 range guard repeats the batch on bf16 planes: that
-        repeat covers the whole batch, so its composition then matters (ops.Fp16Guard)."""
+        repeat covers the whole batch, so its composition then matters (ops.Fp16Guard).
+        voices[i] may also be a blend ({name: weight} or (name, weight) pairs, multistream.blend_spec): then every window of the
+        corpus gets one list row per voice of its utterance's blend, the pool search runs over those rows (in pieces within its
+        limits, bitwise one call) and the blend gather mixes each window's lists (alive_knn_blend_gather_rows).  A corpus without a
+        blend of two or more voices launches the plain path."""
         from . import multistream as MS
         m = len(utterances)
         voices = list(voices)
@@ -387,9 +391,8 @@ class Converter:
             raise ValueError(f"world_pitch: {len(worlds)} values for {m} utterances")
         if not all(isinstance(w, (bool, np.bool_)) for w in worlds):
             raise ValueError(f"world_pitch: expected bools, got {worlds}")
-        for name in voices:
-            if pool.segment(name)[1] < k:
-                raise ValueError(f"voice {name!r} has {pool.segment(name)[1]} vectors, fewer than k={k}")
+        specs = [MS.blend_spec(v, pool, k) for v in voices]
+        blended = any(len(names) > 1 for names, _ in specs)
         wins, totals, counts = [], [], []
         for u in utterances:
             u = u.reshape(1, -1).to(self.device, torch.float32)
@@ -402,8 +405,23 @@ class Converter:
 
         def rows(vals, dtype):
             return torch.repeat_interleave(torch.tensor(vals, dtype=dtype, device=self.device), rep).contiguous()
-        params = dict(ids=torch.repeat_interleave(pool.voice_ids(voices), rep).contiguous(), alpha=rows(alphas, torch.float64),
-                      shift=rows(shifts, torch.float32), inton=rows(inton, torch.float32), rate=rows(rates, torch.float32))
+        params = dict(alpha=rows(alphas, torch.float64), shift=rows(shifts, torch.float32), inton=rows(inton, torch.float32),
+                      rate=rows(rates, torch.float32))
+        if not blended:                     # (one-voice blends are their voice: weight 1.0)
+            params["ids"] = torch.repeat_interleave(pool.voice_ids([names[0] for names, _ in specs]), rep).contiguous()
+        else:                               # compact list rows: window w of utterance i owns S_i of them, in blend order
+            owner, lnames, lweights, first = [], [], [], [0]
+            w = 0
+            for (names, weights), c in zip(specs, counts):
+                for _ in range(c):
+                    owner += [w] * len(names)
+                    lnames += names
+                    lweights += weights
+                    first.append(first[-1] + len(names))
+                    w += 1
+            params.update(owner=torch.tensor(owner, dtype=torch.int64, device=self.device), ids=pool.voice_ids(lnames),
+                          first=torch.tensor(first, dtype=torch.int32, device=self.device),
+                          weight=torch.tensor(lweights, dtype=torch.float64, device=self.device))
         # the WORLD windows of every window batch (batch-local row indices, on the device before the batches start)
         on = [bool(w) for w, c in zip(worlds, counts) for _ in range(c)]
         params["world"] = {i: torch.tensor([j - i for j in range(i, min(i + window_batch, len(on))) if on[j]], dtype=torch.int64,
@@ -427,8 +445,16 @@ class Converter:
 
         def match(feat):
             src = feat if rng is None else feat[:, :, rng[0]:rng[1]].contiguous()
-            val, idx = MS.knn_search_pool(src, pool, params["ids"], k)
-            return MS.merge_gather_rows(val, idx, k, params["alpha"], pool.rows, src)
+            if not blended:
+                val, idx = MS.knn_search_pool(src, pool, params["ids"], k)
+                return MS.merge_gather_rows(val, idx, k, params["alpha"], pool.rows, src)
+            src_v = src.index_select(0, params["owner"])
+            R, _, t = src_v.shape
+            step = max(1, min(MS.POOL_PIECE_ROWS, MS.POOL_PIECE_FRAMES // t))
+            pieces = [MS.knn_search_pool(src_v[a:a + step], pool, params["ids"][a:a + step], k) for a in range(0, R, step)]
+            val = pieces[0][0] if len(pieces) == 1 else torch.cat([p[0] for p in pieces])
+            idx = pieces[0][1] if len(pieces) == 1 else torch.cat([p[1] for p in pieces])
+            return MS.blend_gather_rows(val, idx, k, params["first"], params["weight"], params["alpha"], pool.rows, src)
         out = ops.Fp16Guard(self._agree_on_saturations()).run(
             lambda: self._convert_per_window(windows, rng, window_batch, encode, match, transform))
         res, i = [], 0

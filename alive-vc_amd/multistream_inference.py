@@ -7,6 +7,8 @@ The sessions file is a JSON list; each entry:
    "pitch": 0, "f0_rate": 1, "alpha": 0, "gain": 0, "input_gain": 0,     optional, realtime_inference.py's meanings
    "world_pitch": false,                  optional, a JSON bool: realtime_inference.py's -wpe (WORLD's f0 of the ring; its
                                           f0_rate is then not applied, as there)
+   "blend": [{"target": "a.wav", "weight": 2}, {"lib": "b.pt", "weight": 1}],   instead of "target" / "lib": a weighted mix
+                                          of 1 to 4 voices, each component a voice source as above (multistream.blend_spec)
    "start": 0,                            optional: the tick at which the session joins
    "sr": 48000,                           optional: the session's sample rate (default -isr / -osr)
    "output": "a_out.wav"}                 optional: default <outdir>/<index>_<input name>.wav
@@ -15,6 +17,8 @@ A session with "sr" has its input resampled to sr on load, is driven at sr in ch
 with the converter's 16 kHz geometry: module/multistream.py session_geometry), and its output wav is written at sr.  "sr" needs
 -isr == -osr.
 The converter carries the WORLD branch only if some session asks for "world_pitch": a sessions file without it runs as before.
+It is built with blend = the most components of any session's "blend" (1 without one: a file without blends runs as before);
+sessions and blend components naming the same voice sources share one voice of the pool.
 WORLD needs rings of about 230 ms or more (-c 960 -b 8 is 480 ms): a shorter ring comes out unvoiced.
 Flags shared with realtime_inference.py keep its spelling: -c, -b, -k, -isr, -osr, --no-graph.
 """
@@ -32,11 +36,12 @@ from module import audio_io                                     # noqa: E402
 from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
-from module.multistream import MultiStreamConverter, VoicePool   # noqa: E402
+from module.multistream import MultiStreamConverter, VoicePool, blend_sources   # noqa: E402
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
-SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "start", "sr", "output")
+SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "start", "sr", "output",
+                "blend")
 
 
 def build_parser():
@@ -72,21 +77,39 @@ def load_sessions(path):
         unknown = set(s) - set(SESSION_KEYS)
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: {SESSION_KEYS})")
-        if s.get("target") is None and s.get("lib") is None:
+        rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))      # noqa: E731
+        blend = blend_sources(s, f"session {i}", rel) if "blend" in s else None
+        if blend is None and s.get("target") is None and s.get("lib") is None:
             raise ValueError(f"session {i}: needs a \"target\" wav or a \"lib\" voice library")
         if not isinstance(s.get("world_pitch", False), bool):
             raise ValueError(f"session {i}: \"world_pitch\" must be true or false, got {s['world_pitch']!r}")
-        rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
                  gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
-                 sr=None if s.get("sr") is None else int(s["sr"]), world_pitch=s.get("world_pitch", False))
+                 sr=None if s.get("sr") is None else int(s["sr"]), world_pitch=s.get("world_pitch", False), blend=blend)
         if e["start"] < 0:
             raise ValueError(f"session {i}: start tick {e['start']} < 0")
         if e["sr"] is not None and e["sr"] <= 0:
             raise ValueError(f"session {i}: sample rate {e['sr']} <= 0")
         out.append(e)
     return out
+
+
+def voice_name(target, lib):
+    """the pool name of a voice source: sessions and blend components with the same sources share one voice"""
+    return json.dumps([target, lib])
+
+
+def session_voice(s):
+    """the session's voice for MultiStreamConverter.open: a pool name, or (name, weight) pairs for a blend"""
+    if s.get("blend"):
+        return [(voice_name(t, lb), w) for t, lb, w in s["blend"]]
+    return voice_name(s["target"], s["lib"])
+
+
+def blend_size(sessions):
+    """the converter's blend: the most components of any session's blend, 1 for a file without blends"""
+    return max([len(s["blend"]) for s in sessions if s.get("blend")] or [1])
 
 
 def voice_tokens(ce, target, lib, device):
@@ -151,16 +174,16 @@ def main(argv=None):
 
     pool, names = VoicePool(device=device), []
     for s in sessions:
-        name = json.dumps([s["target"], s["lib"]])
-        if name not in pool.segments:
-            pool.add(name, voice_tokens(CE, s["target"], s["lib"], device))
-        names.append(name)
+        for target, lib in ([(t, lb) for t, lb, _ in s["blend"]] if s.get("blend") else [(s["target"], s["lib"])]):
+            if voice_name(target, lib) not in pool.segments:
+                pool.add(voice_name(target, lib), voice_tokens(CE, target, lib, device))
+        names.append(session_voice(s))
     slots = max(args.slots, len(sessions))
     in_sr = [s["sr"] or args.input_sr for s in sessions]
     out_sr = [s["sr"] or args.output_sr for s in sessions]
     conv = MultiStreamConverter(CE, PE, Dec, pool, slots, chunk=args.chunk, buffersize=args.buffersize, input_sr=args.input_sr,
                                 output_sr=args.output_sr, k=args.k, device=device, rates=sorted(set(in_sr)),
-                                world_pitch=any(s["world_pitch"] for s in sessions))
+                                world_pitch=any(s["world_pitch"] for s in sessions), blend=blend_size(sessions))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"]) for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:

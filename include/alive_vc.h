@@ -225,6 +225,21 @@ int alive_knn_search_grouped(const float* src, int N, int T, const float* rows_f
 int alive_knn_merge_gather_rows(const float* cand_val, const int32_t* cand_idx, int k, const double* alpha,
                                 const float* rows_f32_full, const float* src, int N, int T, float* out,
                                 int32_t* final_idx, void* stream);
+/* alive_knn_blend_gather_rows: voice blending.  Output row n (of src / out [N][768][T]) owns the LIST ROWS first[n] ..
+ * first[n+1]-1, at most ALIVE_MAX_BLEND of them (a longer run is cut at ALIVE_MAX_BLEND, a negative one is empty); list row r
+ * is one top-k list per frame, cand_val / cand_idx [first[N] * T][k] as alive_knn_search_grouped or alive_knn_search_pool
+ * return them for the list rows, with weight[r] (normalised by the caller).  Per frame t of row n, in float32 with every
+ * product and sum rounded on its own:
+ *   m_s = (r_0 + ... + r_(k-1)) / k          the mean of list s's rows (alive_knn_merge_gather_rows' mean, bitwise)
+ *   b   = w_0 m_0 + w_1 m_1 + ...            over the ACTIVE lists (first idx >= 0), in list order, left to right
+ *   out = b (1 - alpha[n]) + src alpha[n]    as alive_knn_merge_gather_rows; a frame with no active list: out = src.
+ * One list at weight 1.0 is therefore bitwise alive_knn_merge_gather_rows.  first (int32[N+1]), weight (double[first[N]]),
+ * alpha (double[N]) are DEVICE arrays: the call neither allocates nor synchronises, and a captured hipGraph may replay it
+ * after they change.  k <= 8. */
+#define ALIVE_MAX_BLEND 4
+int alive_knn_blend_gather_rows(const float* cand_val, const int32_t* cand_idx, int k, const int32_t* first,
+                                const double* weight, const double* alpha, const float* rows_f32_full, const float* src,
+                                int N, int T, float* out, void* stream);
 
 /* ---------------------------------------------- pool search (many-to-many batch conversion) ----
  * A pool of V voices: fp32 rows_f32[P][768] / norms[P] from alive_library_pack_rows (voice v = rows [seg_lo[v], seg_lo[v] +

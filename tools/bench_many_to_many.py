@@ -12,7 +12,8 @@ Every time is event-timed on the current stream after one warm-up call, mean of 
 End to end at V = 64, M = 50 000: convert_many of the 64 utterances against 64 sequential Converter.convert calls (each with its
 voice's strict PackedLibrary, packed beforehand), trim_context on (the CLI default).  --world 0,0.5,1 also times convert_many with
 that fraction of the utterances on WORLD pitch (spread evenly: utterance u is on WORLD when floor((u + 1) f) > floor(u f)) and
-records world_<f>_ms; --no-search skips the search table.
+records world_<f>_ms; --blend S also times convert_many with every utterance blending S voices (utterance u: voices u, u + 1, ...
+mod 64, weights 1, 2, ...) and records blend_<S>_ms; --no-search skips the search table.
 """
 import argparse
 import json
@@ -51,6 +52,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the results as JSON to this file")
     ap.add_argument("--world", default=None, help="comma-separated fractions of the utterances on WORLD pitch (end to end)")
+    ap.add_argument("--blend", type=int, default=0, help="also time convert_many with every utterance blending this many voices")
     ap.add_argument("--no-search", action="store_true", help="skip the search table (end to end only)")
     ap.add_argument("--commit", default="", help="source commit to record (default: git rev-parse HEAD, when there is a .git)")
     args = ap.parse_args()
@@ -113,6 +115,12 @@ def main():
         t_w = timed(lambda: conv.convert_many(utts, pool, names, chunk=CHUNK, k=K, trim_context=True, world_pitch=on), args.reps)
         res["end_to_end"][f"world_{f}_ms"] = round(t_w, 2)
         res["end_to_end"][f"world_{f}_utterances"] = sum(on)
+    if args.blend > 1:
+        S = args.blend
+        blends = [[(f"v{(u + s) % N_UTT}", float(s + 1)) for s in range(S)] for u in range(N_UTT)]
+        t_b = timed(lambda: conv.convert_many(utts, pool, blends, chunk=CHUNK, k=K, trim_context=True), args.reps)
+        res["end_to_end"][f"blend_{S}_ms"] = round(t_b, 2)
+        res["end_to_end"][f"blend_{S}_over_plain"] = round(t_b / t_many, 3)
     print(json.dumps(res["end_to_end"]), flush=True)
     if args.out:
         with open(args.out, "w") as f:

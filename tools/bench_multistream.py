@@ -7,11 +7,14 @@ ticks; the search is timed with events around repeated calls.  --rates spreads t
 (session s at rates[s % len]; MultiStreamConverter(rates=...), the per-row multi-rate edges) and adds that batch's tick p50 / p99
 (mixed_<mode>_tick_p50_ms / _p99_ms) next to the single-rate figures of the same B.  --world adds the graph tick p50 / p99 of
 the same batch per WORLD setting (world_<setting>_tick_p50_ms / _p99_ms): "off" is a world_pitch=False converter, a number f a
-world_pitch=True converter with sessions s < round(f B) on WORLD (0: the masked branch with every row off).  Profile in a separate run (rocprofv3 --kernel-trace --stats --
+world_pitch=True converter with sessions s < round(f B) on WORLD (0: the masked branch with every row off).  --blend adds the graph
+tick p50 / p99 of voice blending: blend3_single_* a blend=3 converter whose sessions are single voices, blend2_* / blend3_* every
+session blending 2 / 3 voices (session s: voices s, s + 1, s + 2, weights 1, 2, 3) in a converter of that blend; distinct voices
+only.  Profile in a separate run (rocprofv3 --kernel-trace --stats --
 python tools/bench_multistream.py --quick).  Prints one JSON line per configuration and writes the list to --out.
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
-                                      [--world off,0,0.5,1] [--voices shared,distinct] [--out multistream.json]
+                                      [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--out multistream.json]
 """
 import argparse
 import json
@@ -80,6 +83,7 @@ def main():
     ap.add_argument("--rates", default=None, help="comma-separated session rates: also time a batch spread over them")
     ap.add_argument("--world", default=None, help="comma-separated WORLD settings: off, or the fraction of sessions on WORLD")
     ap.add_argument("--voices", default="shared,distinct", help="voice mixes to run: shared, distinct")
+    ap.add_argument("--blend", action="store_true", help="also time voice blending (blend=3 single voices, 2- and 3-voice blends)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     batches = [int(b) for b in args.batches.split(",")]
@@ -91,7 +95,7 @@ def main():
         batches, configs, mixes = [64], [(160, 16)], ("distinct",)
     nets = (ContentEncoder(seed=2), F0Estimator(seed=2), Decoder(seed=2))
     shared = make_pool(1, 1)
-    distinct = make_pool(max(batches), 2)
+    distinct = make_pool(max(batches) + (2 if args.blend else 0), 2)
     rows = []
     for chunk, bs in configs:
         period_ms = chunk / 16.0
@@ -131,6 +135,17 @@ def main():
                     p50, p99 = time_ticks(wc, B, chunk, args.ticks, args.warmup + bs + 1, 300)
                     rec[f"world_{w}_tick_p50_ms"], rec[f"world_{w}_tick_p99_ms"] = round(p50, 3), round(p99, 3)
                     del wc
+                blends = (("blend3_single", 3, 1), ("blend2", 2, 2), ("blend3", 3, 3)) if args.blend and mix == "distinct" else ()
+                for name, S, n_mix in blends:                  # (distinct voices only: a blend mixes different voices)
+                    bc = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, blend=S)
+                    for s in range(B):
+                        vs = [f"v{s + j}" for j in range(n_mix)]
+                        bc.open(s, vs[0] if n_mix == 1 else [(v, j + 1.0) for j, v in enumerate(vs)], pitch=float(s % 5), f0_rate=0.5)
+                    bc.enable_graph()
+                    p50, p99 = time_ticks(bc, B, chunk, args.ticks, args.warmup + bs + 1, 300)
+                    rec[f"{name}_tick_p50_ms"], rec[f"{name}_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                    rec[f"{name}_real_time"] = p99 < period_ms
+                    del bc
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
                 rows.append(rec)
