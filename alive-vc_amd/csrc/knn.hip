@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256) void rot_codes_kernel(const float* __restrict_
 // dq (optional): || q^ - bf16(q^) ||_2 per frame, rounded up -- the frame's share of the strict certificate's bound
 __global__ __launch_bounds__(256) void src_prep_kernel(const float* __restrict__ src, int T, int64_t Tt, int64_t Tt_pad,
                                                        float* __restrict__ s_f32, unsigned short* __restrict__ s_bf16,
-                                                       float* __restrict__ dq) {
+                                                       float* __restrict__ dq, float* __restrict__ nrm_out = nullptr) {
     __shared__ float red[4][64];
     __shared__ float tile[64][65];
     __shared__ float nrm[64];
@@ -378,6 +378,7 @@ __global__ __launch_bounds__(256) void src_prep_kernel(const float* __restrict__
     red[wv][lane] = ss;
     __syncthreads();
     if (wv == 0) nrm[lane] = sqrtf(red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
+    if (wv == 0 && nrm_out != nullptr && ok) nrm_out[ft] = nrm[lane];          // |q| for the subspace stage (sub_codes_kernel)
     __syncthreads();
     float e2[16];                                     // rounding error of frame f0 + wv + 4 i, this lane's features
 #pragma unroll
@@ -416,7 +417,7 @@ __global__ __launch_bounds__(256) void src_prep_kernel(const float* __restrict__
 // serially with one frame per lane, which for 8 frames is 2 x 192 dependent strided loads per wave
 __global__ __launch_bounds__(256) void src_prep_small_kernel(const float* __restrict__ src, int T, int64_t Tt,
                                                              float* __restrict__ s_f32, unsigned short* __restrict__ s_bf16,
-                                                             float* __restrict__ dq) {
+                                                             float* __restrict__ dq, float* __restrict__ nrm_out = nullptr) {
     __shared__ float red[4];
     __shared__ float ered[4];
     const int64_t ft = blockIdx.x;
@@ -444,6 +445,7 @@ __global__ __launch_bounds__(256) void src_prep_small_kernel(const float* __rest
     }
     __syncthreads();
     const float nrm = sqrtf(red[0] + red[1] + red[2] + red[3]);
+    if (nrm_out != nullptr && tid == 0) nrm_out[ft] = nrm;
     float e2 = 0.0f;
 #pragma unroll
     for (int i = 0; i < D / 256; ++i) {
@@ -1061,12 +1063,13 @@ constexpr int SEED_MIN_FB = 512;
 constexpr int SEED_MIN_FB6 = 300;                                // fp6 kernel, 384-frame blocks: a little over one round of the chip is enough --
                                                                  // the look at the predecessor's flag never waits, an unfinished one means an unseeded block
 
-template <int FMT, int NCT8>
+template <int FMT, int NCT8, int NK = NK64>
 __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict__ s_f8,
                                                 const unsigned char* __restrict__ lib, int64_t M, int tiles_total,
                                                 int tiles_per_split, int P, float* __restrict__ cand_val,
                                                 int* __restrict__ cand_idx, const int* __restrict__ gate_cnt,
-                                                int gate_lo, int gate_hi, SeedArgs sa) {
+                                                int gate_lo, int gate_hi, SeedArgs sa,
+                                                const float* __restrict__ rho = nullptr, const float* __restrict__ gq = nullptr) {
     {
         int c;
         if (!gate_open(gate_cnt, gate_lo, gate_hi, c)) return;                       // block-uniform
@@ -1075,8 +1078,12 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
     constexpr int WF8 = 32 * NCT8;             // frames per wave
     constexpr int FT8 = 4 * WF8;               // frames per block (256 / 384)
     constexpr int LW8 = 4 * 2 * WF8;           // lane-columns per list entry row (two half-waves per frame column)
+    // NK k-steps of 64 features: 12 (K = 768) or 8 (the subspace stage, K = 512: codes of 512 coordinates, rows and frames of KD bytes)
+    constexpr int KD = 64 * NK;                // bytes per row / frame code vector
+    constexpr int NSEG = KD / 128;             // 128-byte segments per row = DMA pieces per wave and tile
+    constexpr int ABUF_ = 4 * NSEG * PIECE;    // bytes per tile buffer
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* Lv = (float*)(smem + 2 * ABUF8);
+    float* Lv = (float*)(smem + 2 * ABUF_);
     int* Li = (int*)(Lv + FT8 * KP8);          // both entry-major: [KH8][LW8 lane-columns]
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1108,21 +1115,21 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
     const int dma_row = 8 * w + (lane >> 3);
     const int dma_chunk = (lane & 7) ^ (lane >> 3);
     auto issue_tile = [&](int tile, int buf) {
-        const unsigned char* g = lib + ((size_t)tile * LT + dma_row) * D + dma_chunk * 16;
-        unsigned char* l = smem + buf * ABUF8 + w * PIECE;
+        const unsigned char* g = lib + ((size_t)tile * LT + dma_row) * KD + dma_chunk * 16;
+        unsigned char* l = smem + buf * ABUF_ + w * PIECE;
 #pragma unroll
-        for (int sg = 0; sg < D / 128; ++sg)
+        for (int sg = 0; sg < NSEG; ++sg)
             __builtin_amdgcn_global_load_lds((gptr_t)(g + sg * 128), (lptr_t)(l + sg * 4 * PIECE), 16, 0, 0);
     };
     if (tile_begin < tile_end) issue_tile(tile_begin, 0);
 
     // stationary B fragments: frame = frame0 + 64 w + 32 ni + lr, features 64 ks + 32 lh .. + 31 (32 bytes)
-    v8i bq[NCT8][NK64];
+    v8i bq[NCT8][NK];
 #pragma unroll
     for (int ni = 0; ni < NCT8; ++ni) {
-        const unsigned char* fp = s_f8 + (size_t)(frame0 + WF8 * w + 32 * ni + lr) * D + 32 * lh;
+        const unsigned char* fp = s_f8 + (size_t)(frame0 + WF8 * w + 32 * ni + lr) * KD + 32 * lh;
 #pragma unroll
-        for (int ks = 0; ks < NK64; ++ks) {
+        for (int ks = 0; ks < NK; ++ks) {
             if constexpr (FMT == 2) {           // 24 of the 32 bytes carry the 32 six-bit codes: no 8-register temporaries
                 const u32x4 lo = *(const u32x4*)(fp + 64 * ks);
                 const uint2 hi = *(const uint2*)(fp + 64 * ks + 16);
@@ -1133,6 +1140,12 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             }
         }
     }
+
+    // subspace stage (NK = 8): a score is x_f . y_r + g_f rho_r (knn_sub6_kernel below); g_f of this lane's frame of column tile ni,
+    // in the stage's score units
+    float gs[NCT8];
+#pragma unroll
+    for (int ni = 0; ni < NCT8; ++ni) gs[ni] = NK == NK64 ? 0.0f : gq[frame0 + WF8 * w + 32 * ni + lr] * (F6_SCALE * F6_SCALE);
 
     // A fragment of k-step ks: row lr, bytes 64 ks + 32 lh .. +31 = chunks c0 = 4 (ks & 1) + 2 lh and c0 + 1 of segment ks >> 1;
     // chunk c of line rr sits at position c ^ rr
@@ -1197,6 +1210,21 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
 #pragma unroll
         for (int r = 0; r < 8; ++r) m = fmaxf(m, acc[lo + r]);
         return m;
+    };
+    // rho of the 16 rows of a lane's accumulator registers in a tile: register r is row 8 (r >> 2) + 4 lh + (r & 3)
+    auto load_rho = [&](int tile, float* rv) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const f32x4 t = *(const f32x4*)(rho + (size_t)tile * LT + 8 * j + 4 * lh);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) rv[4 * j + e] = t[e];
+        }
+    };
+    // the subspace stage's running maximum: 8 registers get their g_f rho_r first (-inf of a masked row stays -inf)
+    auto max8g = [&](f32x16& acc, int lo, float m, int ni, const float* rv) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) acc[lo + r] = fmaf(gs[ni], rv[lo + r], acc[lo + r]);
+        return max8(acc, lo, m);
     };
     // the loop form on accumulators that already carry their register index: admits mx, then the largest score below it, ...
     // while any lane still holds an admitted score
@@ -1310,14 +1338,18 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
     if constexpr (NCT8 == 3) {
     // Three column tiles per wave (the fp6 kernel): 36 MFMAs per tile into (c0, c1, c2); the previous tile's accumulators
     // (p0, p1, p2) are copied out and folded in steps 6 .. 10.  Same pieces as the two-tile form below, one more of each.
-    auto do_tile3 = [&](int tile, f32x16& c0, f32x16& c1, f32x16& c2, f32x16& p0, f32x16& p1, f32x16& p2) {
+    // rv: rho of the previous tile's rows (the subspace stage; ready: loaded one tile earlier), rn: rho of this tile's rows, requested
+    // here and waited for by the barrier at the end of the tile (vmcnt(0) there for the DMA anyway) -- a plain load consumed inside the
+    // tile would make hipcc drain vmcnt, the LDS-DMA pieces just issued included, in the middle of it
+    auto do_tile3 = [&](int tile, f32x16& c0, f32x16& c1, f32x16& c2, f32x16& p0, f32x16& p1, f32x16& p2, float* rv, float* rn) {
         const int buf = (tile - tile_begin) & 1;
         const int next_tile = tile + 1 < tile_end ? tile + 1 : tile;
-        const unsigned char* gnext = lib + ((size_t)next_tile * LT + dma_row) * D + dma_chunk * 16;
-        unsigned char* lnext = smem + (buf ^ 1) * ABUF8 + w * PIECE;
-        const unsigned char* Ab = smem + buf * ABUF8;
+        const unsigned char* gnext = lib + ((size_t)next_tile * LT + dma_row) * KD + dma_chunk * 16;
+        unsigned char* lnext = smem + (buf ^ 1) * ABUF_ + w * PIECE;
+        const unsigned char* Ab = smem + buf * ABUF_;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; c2[r] = 0.0f; }
+        if constexpr (NK != NK64) load_rho(tile, rn);
         constexpr int PD6 = 1, NA6 = PD6 + 1;     // A fragments requested this many k-steps ahead of their MFMAs
         v8i a[NA6];
 #pragma unroll
@@ -1329,8 +1361,8 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
             c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[(ks) % NA6], bq[0][ks], c0, FMT, FMT, 0, 127, 0, 127); \
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
-            if ((ks) + PD6 < NK64) a[((ks) + PD6) % NA6] = load_a(Ab, (ks) + PD6);                                               \
-            if ((ks) < D / 128)                                                                                                  \
+            if ((ks) + PD6 < NK) a[((ks) + PD6) % NA6] = load_a(Ab, (ks) + PD6);                                                 \
+            if ((ks) < NSEG)                                                                                                     \
                 __builtin_amdgcn_global_load_lds((gptr_t)(gnext + (ks) * 128), (lptr_t)(lnext + (ks) * 4 * PIECE), 16, 0, 0);    \
             AFTER0;                                                                                                              \
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
@@ -1349,7 +1381,10 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         };
         auto acc_pin = [&]() { asm volatile("" : "+a"(c0), "+a"(c1), "+a"(c2)); };
         K8_STEP3(0, (void)0, (void)0, (void)0) K8_STEP3(1, (void)0, (void)0, (void)0) K8_STEP3(2, (void)0, (void)0, (void)0)
+        if constexpr (NK == NK64) {
         K8_STEP3(3, (void)0, (void)0, (void)0) K8_STEP3(4, (void)0, (void)0, (void)0) K8_STEP3(5, (void)0, (void)0, acc_pin())
+        }
+        if constexpr (NK == NK64) {
         // (each column tile's copy is folded before the next one is read: one 16-register copy live at a time)
         K8_STEP3(6, acc_read(p0, 0, 8, v0), (acc_pin(), acc_read(p0, 8, 16, v0), mask_ragged(v0, tile - 1)), (acc_pin(), pm0 = max8(v0, 0, pm0)))
         K8_STEP3(7, pm0 = max8(v0, 8, pm0), fold_rare(v0, 0, tile - 1, pm0), (acc_pin(), acc_read(p1, 0, 8, v1)))
@@ -1357,41 +1392,58 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         K8_STEP3(9, fold_rare(v1, 1, tile - 1, pm1), (acc_pin(), acc_read(p2, 0, 8, v2)), (acc_pin(), acc_read(p2, 8, 16, v2), mask_ragged(v2, tile - 1)))
         K8_STEP3(10, (acc_pin(), pm2 = max8(v2, 0, pm2)), pm2 = max8(v2, 8, pm2), fold_rare(v2, 2, tile - 1, pm2))
         K8_STEP3(11, (void)0, (void)0, (void)0)
+        } else {
+        // the subspace stage: 8 k-steps, the 4 DMA pieces in steps 0 .. 3; the previous tile's fold (the same 15 pieces as above) takes
+        // the slots from the second MFMA of step 3 on, its rho (4 x 16 B per lane, requested in front of this tile's DMA pieces) has
+        // had three steps to arrive
+        K8_STEP3(3, acc_pin(), (acc_pin(), acc_read(p0, 0, 8, v0)), (acc_pin(), acc_read(p0, 8, 16, v0), mask_ragged(v0, tile - 1)))
+        K8_STEP3(4, (acc_pin(), pm0 = max8g(v0, 0, pm0, 0, rv)), pm0 = max8g(v0, 8, pm0, 0, rv), fold_rare(v0, 0, tile - 1, pm0))
+        K8_STEP3(5, (acc_pin(), acc_read(p1, 0, 8, v1)), (acc_pin(), acc_read(p1, 8, 16, v1), mask_ragged(v1, tile - 1)), (acc_pin(), pm1 = max8g(v1, 0, pm1, 1, rv)))
+        K8_STEP3(6, pm1 = max8g(v1, 8, pm1, 1, rv), fold_rare(v1, 1, tile - 1, pm1), (acc_pin(), acc_read(p2, 0, 8, v2)))
+        K8_STEP3(7, (acc_pin(), acc_read(p2, 8, 16, v2), mask_ragged(v2, tile - 1)), (acc_pin(), pm2 = max8g(v2, 0, pm2, 2, rv)),
+                 (pm2 = max8g(v2, 8, pm2, 2, rv), fold_rare(v2, 2, tile - 1, pm2)))
+        }
 #undef K8_STEP3
         acc_pin();
         __syncthreads();
     };
-    auto fold_now3 = [&](f32x16& p0, f32x16& p1, f32x16& p2, int tile) {
+    auto fold_now3 = [&](f32x16& p0, f32x16& p1, f32x16& p2, int tile, float* rv) {
         mask_ragged(p0, tile);
         mask_ragged(p1, tile);
         mask_ragged(p2, tile);
+        if constexpr (NK != NK64) {
+            (void)max8g(p0, 0, max8g(p0, 8, -INFINITY, 0, rv), 0, rv);
+            (void)max8g(p1, 0, max8g(p1, 8, -INFINITY, 1, rv), 1, rv);
+            (void)max8g(p2, 0, max8g(p2, 8, -INFINITY, 2, rv), 2, rv);
+        }
         fold_rare(p0, 0, tile, max8(p0, 8, max8(p0, 0, -INFINITY)));
         fold_rare(p1, 1, tile, max8(p1, 8, max8(p1, 0, -INFINITY)));
         fold_rare(p2, 2, tile, max8(p2, 8, max8(p2, 0, -INFINITY)));
     };
     {
         f32x16 A0, A1, A2, B0, B1, B2;
+        float RA[16], RB[16];                  // subspace stage: rho of the tiles in A / B (unused at K = 768)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { B0[r] = -INFINITY; B1[r] = -INFINITY; B2[r] = -INFINITY; }
+        for (int r = 0; r < 16; ++r) { B0[r] = -INFINITY; B1[r] = -INFINITY; B2[r] = -INFINITY; RA[r] = 0.0f; RB[r] = 0.0f; }
         int tile = tile_begin;
         for (; tile + 1 < tile_end; tile += 2) {
-            do_tile3(tile, A0, A1, A2, B0, B1, B2);
-            do_tile3(tile + 1, B0, B1, B2, A0, A1, A2);
+            do_tile3(tile, A0, A1, A2, B0, B1, B2, RB, RA);
+            do_tile3(tile + 1, B0, B1, B2, A0, A1, A2, RA, RB);
         }
         if (tile < tile_end) {
-            do_tile3(tile, A0, A1, A2, B0, B1, B2);
-            fold_now3(A0, A1, A2, tile);
+            do_tile3(tile, A0, A1, A2, B0, B1, B2, RB, RA);
+            fold_now3(A0, A1, A2, tile, RA);
         } else if (tile_begin < tile_end) {
-            fold_now3(B0, B1, B2, tile_end - 1);
+            fold_now3(B0, B1, B2, tile_end - 1, RB);
         }
     }
     } else {
     auto do_tile = [&](int tile, f32x16& c0, f32x16& c1, f32x16& p0, f32x16& p1) {
         const int buf = (tile - tile_begin) & 1;
         const int next_tile = tile + 1 < tile_end ? tile + 1 : tile;
-        const unsigned char* gnext = lib + ((size_t)next_tile * LT + dma_row) * D + dma_chunk * 16;
-        unsigned char* lnext = smem + (buf ^ 1) * ABUF8 + w * PIECE;
-        const unsigned char* Ab = smem + buf * ABUF8;
+        const unsigned char* gnext = lib + ((size_t)next_tile * LT + dma_row) * KD + dma_chunk * 16;
+        unsigned char* lnext = smem + (buf ^ 1) * ABUF_ + w * PIECE;
+        const unsigned char* Ab = smem + buf * ABUF_;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; }
         // hipcc waits lgkmcnt(0) in front of every MFMA that takes an LDS fragment, i.e. for EVERYTHING in flight -- a
@@ -1413,8 +1465,8 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
             c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[(ks) & 1], bq[0][ks], c0, FMT, FMT, 0, 127, 0, 127);              \
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
-            if ((ks) + 1 < NK64) a[((ks) + 1) & 1] = load_a(Ab, (ks) + 1);                                                       \
-            if ((ks) < D / 128) /* the 6 DMA pieces of the next tile go out in the FIRST half of this one: the barrier at its */  \
+            if ((ks) + 1 < NK) a[((ks) + 1) & 1] = load_a(Ab, (ks) + 1);                                                         \
+            if ((ks) < NSEG)    /* the 6 DMA pieces of the next tile go out in the FIRST half of this one: the barrier at its */  \
                                 /* end waits vmcnt(0), and a piece issued in the last step exposes a whole L2 / HBM round trip */ \
                 __builtin_amdgcn_global_load_lds((gptr_t)(gnext + (ks) * 128), (lptr_t)(lnext + (ks) * 4 * PIECE), 16, 0, 0);    \
             AFTER0;                                                                                                              \
@@ -1513,6 +1565,22 @@ __global__ __launch_bounds__(256, 1) void knn_probe6_kernel(const unsigned char*
                                                             int64_t M, int tiles_total, int tiles_per_split, int P,
                                                             float* __restrict__ cand_val, int* __restrict__ cand_idx, const int* __restrict__ gate) {
     knn_score8_body<2, 3>(s_f6, lib, M, tiles_total, tiles_per_split, P, cand_val, cand_idx, gate, 0, 1, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr});
+}
+// The subspace form of the fp6 stage: K = 512.  Every frame the converter searches is q = W h + b (the content encoder's last layer,
+// W 768 x 512), so it lies in span(U) + u with U an orthonormal basis of span(W) and u the unit part of b outside it.  For such a frame
+// and ANY library row, q^ . r^ = x_f . y_r + g_f rho_r exactly (x = U^T q^, y = U^T r^, g = u . q^, rho = u . r^): the codes of the 512
+// coordinates go through the MFMA (8 k-steps instead of 12, 512-byte rows), g_f rho_r is added in fp32 in the fold.  Frames that leave
+// the subspace or clip are flagged by sub_codes_kernel (below); the search gate sends the batch to knn_score6_kernel when there are many.
+constexpr int NK_SUB = 8;
+constexpr int SUB_K = 64 * NK_SUB;                               // 512 coordinates = 512 code bytes per row and frame
+constexpr int SUB6_LDS = 2 * 4 * (SUB_K / 128) * PIECE + FT6 * KP8 * 8;   // 135168 B
+__global__ __launch_bounds__(256, 1) void knn_sub6_kernel(const unsigned char* __restrict__ s_sub, const unsigned char* __restrict__ lib_sub,
+                                                          const float* __restrict__ rho, const float* __restrict__ gq,
+                                                          int64_t M, int tiles_total, int tiles_per_split, int P,
+                                                          float* __restrict__ cand_val, int* __restrict__ cand_idx,
+                                                          const int* __restrict__ gate_cnt, int gate_lo, int gate_hi, SeedArgs sa) {
+    knn_score8_body<2, 3, NK_SUB>(s_sub, lib_sub, M, tiles_total, tiles_per_split, P, cand_val, cand_idx, gate_cnt, gate_lo, gate_hi, sa,
+                                  rho, gq);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -2685,6 +2753,9 @@ constexpr int RESEARCH_MIN = 64;          // frames failing the fp8 certificate:
                                           // frames of the bench batch then cost 111.5 instead of 104.9 ms per search)
 enum { ST_FLAG8 = 0, ST_FLAG16 = 1, ST_PROBE_N = 2, ST_PROBE_FAIL = 3, ST_MODE = 4, ST_FIRST = 5, ST_PROBE_CNT = 6, ST_TIER = 7, ST_FLAGC = 8, ST_SEEDED = 9, ST_SEEDED16 = 10, ST_RESEARCH_MIN = 11, ST_COLLECT_MIN = 12,
        ST_PROBE_SKIPPED = 13,
+       // subspace stage (alive_knn_search_fp6_sub): frames flagged by sub_codes_kernel (out of the subspace or clipped) / of them clipped;
+       // ST_SUB_FORM (written by every subspace search): 1 = the subspace kernel ran, 2 = the plain fp6 kernel (too many flagged frames)
+       ST_SUB_FLAG = 14, ST_SUB_CLIP = 15, ST_SUB_FORM = 20, ST_SUB_GATE = 21,
        // Probe history (round 6), kept in the CALLER'S workspace across calls and never reset by a search: the probe costs 1.8 ms per
        // 172 800-frame search and says the same thing every time a library is searched with frames of one kind.  After two consecutive
        // searches on this workspace (same library size, same frame count: ST_HIST_TAG) in which the probe chose the low-precision stage
@@ -2697,6 +2768,106 @@ constexpr int PROBE_EVERY = 16, PROBE_STREAK = 2;
 // ST_TIER: which path the last search on this workspace took (written by every path, so that the host never has to
 // re-derive the dispatch): 1 = streaming scan, 2 = exact scan of every frame (k > 8), 3 = bf16 first, 4 = fp8 first
 enum { TIER_SCAN = 1, TIER_EXACT_ALL = 2, TIER_BF16 = 3, TIER_FP8 = 4, TIER_FP6 = 5 };
+// ---- operands of the subspace stage (knn_sub6_kernel) ----
+// 32 coordinates (x 2^5) -> the 24 code bytes of a 32-byte slot (to_fp6_kernel's format); true if one of them clips
+__device__ __forceinline__ bool fp6_slot(const float* v, u32x4* o) {
+    unsigned long long acc = 0;
+    int nb = 0, wi = 0;
+    unsigned wd[6];
+    bool clipped = false;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        clipped = clipped || fabsf(v[j]) > 7.75f;
+        acc |= (unsigned long long)fp6_e2m3(v[j]) << nb;
+        nb += 6;
+        if (nb >= 32) { wd[wi++] = (unsigned)acc; acc >>= 32; nb -= 32; }
+    }
+    o[0] = u32x4{wd[0], wd[1], wd[2], wd[3]};
+    o[1] = u32x4{wd[4], wd[5], 0u, 0u};
+    return clipped;
+}
+// rows: y[count][SUB_C] fp32 coordinates of unit rows m0 .. m0 + count - 1 (U^T r^ in 0 .. 511, rho = u . r^ in 512) -> codes [span][512 B]
+// and rho [span] from row m0 on, zeros beyond count; *clip = 1 if any code clipped
+constexpr int SUB_C = 576;                 // coordinates per vector passed in (as the rotated stage's 1x1 conv leaves them); 513 are read
+__global__ __launch_bounds__(256) void lib_sub6_kernel(const float* __restrict__ y, int64_t count, int64_t span, unsigned char* __restrict__ out,
+                                                       float* __restrict__ rho, int* __restrict__ clip) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= span * (SUB_K / 32)) return;
+    const int64_t r = i / (SUB_K / 32);
+    const int grp = (int)(i % (SUB_K / 32));
+    float v[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) v[j] = r < count ? y[(size_t)r * SUB_C + 32 * grp + j] * F6_SCALE : 0.0f;
+    if (fp6_slot(v, (u32x4*)(out + (size_t)r * SUB_K + 32 * grp))) atomicOr(clip, 1);
+    if (grp == 0) rho[r] = r < count ? y[(size_t)r * SUB_C + SUB_K] : 0.0f;
+}
+// frames: y = [U | u]^T src as alive_conv1d leaves it, [N][SUB_C][T], NOT normalised; nrm[Tt] = |q| (src_prep_kernel).  32 frames per
+// block, 8 groups of 32 threads.  Writes the codes of x = U^T q^ ([Tt_pad][512 B]), g = u . q^, and flags a frame (flag = 1, counted)
+// whose unit vector has more than SUB_RES2 of its energy outside the 513 coordinates or whose codes clip.  A zero frame stays
+// unflagged with zero codes (score 0 against every row, as in the plain stage).
+constexpr float SUB_RES2 = 1.0e-5f;        // |q^ - [U u][U u]^T q^|^2 limit: |r| <= 3.2e-3, the score error it adds is r . r^ (encoder frames: ~1e-13)
+__global__ __launch_bounds__(256) void sub_codes_kernel(const float* __restrict__ y, const float* __restrict__ nrm, int T, int64_t Tt,
+                                                        int64_t Tt_pad, unsigned char* __restrict__ out, float* __restrict__ g,
+                                                        unsigned char* __restrict__ flag, int* __restrict__ stats) {
+    __shared__ float ssq[8][32];
+    __shared__ int clp[8][32];
+    const int fl = threadIdx.x & 31, cg = threadIdx.x >> 5;
+    const int64_t f = (int64_t)blockIdx.x * 32 + fl;
+    const bool live = f < Tt;
+    const int64_t ni = live ? f / T : 0, ti = live ? f - ni * T : 0;
+    const float* yb = y + (size_t)ni * SUB_C * T + ti;
+    const float q = live ? nrm[f] : 0.0f;
+    const float inv = q > 0.0f ? 1.0f / q : 0.0f;
+    float v[32];
+    float sy = 0.0f;
+    bool clipped = false;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            v[j] = live ? yb[(size_t)(32 * (cg + 8 * h) + j) * T] * inv : 0.0f;
+            sy = fmaf(v[j], v[j], sy);
+            v[j] *= F6_SCALE;
+        }
+        u32x4 o[2];
+        clipped = fp6_slot(v, o) || clipped;
+        if (f < Tt_pad) {
+            u32x4* dst = (u32x4*)(out + (size_t)f * SUB_K + 32 * (cg + 8 * h));
+            dst[0] = o[0];
+            dst[1] = o[1];
+        }
+    }
+    const float gy = live ? yb[(size_t)SUB_K * T] * inv : 0.0f;
+    if (cg == 0) sy = fmaf(gy, gy, sy);
+    ssq[cg][fl] = sy;
+    clp[cg][fl] = clipped ? 1 : 0;
+    __syncthreads();
+    if (cg == 0 && f < Tt_pad) {
+        float s2 = 0.0f;
+        int cl = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { s2 += ssq[k][fl]; cl |= clp[k][fl]; }
+        const bool out_of_span = q > 0.0f && 1.0f - s2 > SUB_RES2;
+        const bool bad = live && (cl != 0 || out_of_span);
+        g[f] = gy;
+        flag[f] = bad ? 1 : 0;
+        if (bad) atomicAdd(stats + ST_SUB_FLAG, 1);
+        if (live && cl != 0) atomicAdd(stats + ST_SUB_CLIP, 1);
+    }
+}
+// after the probe (ST_MODE final): the gate word of the two fp6 kernels -- 0 none (bf16 first), 1 the subspace kernel, 2 the plain one
+// (more than RESEARCH_MIN flagged frames) -- and, for the subspace kernel, its flagged frames join the forced failures
+__global__ __launch_bounds__(256) void sub_select_kernel(const unsigned char* __restrict__ flag, unsigned char* __restrict__ clip6,
+                                                         int64_t n, int* __restrict__ stats) {
+    const bool sub = stats[ST_SUB_FLAG] <= RESEARCH_MIN;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (sub && i < n && flag[i] != 0) clip6[i] = 1;
+    if (i == 0) {
+        stats[ST_SUB_FORM] = sub ? 1 : 2;
+        stats[ST_SUB_GATE] = stats[ST_MODE] != 0 ? 0 : (sub ? 1 : 2);
+    }
+}
+
 __global__ void stats_init_kernel(int* __restrict__ stats, int tier, int hist_tag = 0) {
     // (the two tier limits are written out with the counters, so that a reader never repeats the constants)
     if (threadIdx.x < ST_HIST_TAG)
@@ -2852,6 +3023,8 @@ struct SearchWs {
     float* thr1; int* list2;               // collect tier: thresholds of the frames in list1; frames that overflowed it
     float* dq;                             // || q^ - bf16(q^) || per frame (strict certificate)
     unsigned char* clip6;                  // fp6 stage: 1 = the frame's fp6 image clipped an element (-> it fails the certificate)
+    unsigned char* sub_f6; float* sub_g; unsigned char* sub_flag;   // subspace stage (its workspace only): frame codes [Tp8][512], g_f,
+    float* sub_nrm;                                                  // 1 = flagged, |q| of each frame
     unsigned short* s_c2h; unsigned short* s_c2l;   // split tier (strict search): both planes of the frames that failed the deterministic certificate
     float* c2v; int* c2i;                  // candidate lists of the collect tiers: [slot][split][caps]
     int rows_t, rows_b;                    // rows per frame they may fill: tier-1 launches (<= fcap frames) / bulk launches
@@ -2861,7 +3034,7 @@ struct SearchWs {
     size_t bytes;
 };
 
-static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split = false) {
+static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split = false, bool sub = false) {
     SearchWs w;
     w.p16 = make_plan(Tt, M);
     w.p8 = make_plan(Tt, M, MAX_SPLIT8);
@@ -2921,6 +3094,11 @@ static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split =
     // (alive_knn_workspace_bytes_strict); they come last, so every other address is the same in both layouts
     w.s_c2h = split ? a.take<unsigned short>((size_t)Tp * D) : nullptr;
     w.s_c2l = split ? a.take<unsigned short>((size_t)Tp * D) : nullptr;
+    // the subspace stage's frame operands exist only in its workspace (alive_knn_workspace_bytes_sub), after everything else
+    w.sub_f6 = sub ? a.take<unsigned char>((size_t)Tp8 * SUB_K) : nullptr;
+    w.sub_g = sub ? a.take<float>((size_t)Tp8) : nullptr;
+    w.sub_nrm = sub ? a.take<float>((size_t)Tp8) : nullptr;
+    w.sub_flag = sub ? a.take<unsigned char>((size_t)Tp8) : nullptr;
     w.bytes = a.used() + 1024;
     return w;
 }
@@ -3296,8 +3474,8 @@ static void knn_exact_launch(const SearchWs& w, const float* rows_f32, const flo
 
 static void src_prep_launch(const SearchWs& w, const float* src, int T, int64_t Tt, hipStream_t s) {
     float* dq = w.det_q != nullptr ? w.dq : nullptr;
-    if (Tt <= 512) src_prep_small_kernel<<<(unsigned)w.p16.Tt_pad, 256, 0, s>>>(src, T, Tt, w.s_f32, w.s_bf16, dq);
-    else src_prep_kernel<<<(unsigned)(w.p16.Tt_pad / 64), 256, 0, s>>>(src, T, Tt, w.p16.Tt_pad, w.s_f32, w.s_bf16, dq);
+    if (Tt <= 512) src_prep_small_kernel<<<(unsigned)w.p16.Tt_pad, 256, 0, s>>>(src, T, Tt, w.s_f32, w.s_bf16, dq, w.sub_nrm);
+    else src_prep_kernel<<<(unsigned)(w.p16.Tt_pad / 64), 256, 0, s>>>(src, T, Tt, w.p16.Tt_pad, w.s_f32, w.s_bf16, dq, w.sub_nrm);
 }
 
 static int check_search_args(const char* what, const void* a, const void* b, int N, int T, int k, int64_t M) {
@@ -3310,11 +3488,12 @@ static int check_search_args(const char* what, const void* a, const void* b, int
 }
 
 static int lds_optin(const char* what) {
-    static LdsOptIn optin8, optin6, optin16, optin_split;
+    static LdsOptIn optin8, optin6, optin16, optin_split, optin_sub;
     hipError_t e = optin8.ensure({(const void*)knn_score8_kernel, (const void*)knn_probe8_kernel}, SCORE8_LDS);
     if (e == hipSuccess) e = optin6.ensure({(const void*)knn_score6_kernel, (const void*)knn_probe6_kernel}, SCORE6_LDS);
     if (e == hipSuccess) e = optin16.ensure({(const void*)knn_score_kernel<false>, (const void*)knn_score_kernel<true>}, SCORE_LDS);
     if (e == hipSuccess) e = optin_split.ensure({(const void*)knn_collect_split_kernel}, SPLIT_LDS);
+    if (e == hipSuccess) e = optin_sub.ensure({(const void*)knn_sub6_kernel}, SUB6_LDS);
     if (e != hipSuccess) {
         alive_set_error("%s: cannot reserve %d B of LDS: %s", what, SCORE_LDS, hipGetErrorString(e));
         return ALIVE_ERR_LAUNCH;
@@ -3356,6 +3535,10 @@ extern "C" size_t alive_knn_workspace_bytes_strict(int64_t Tt, int64_t M) {
     return a > b ? a : b;
 }
 extern "C" size_t alive_knn_workspace_bytes(int64_t Tt, int64_t M) { return alive_knn_workspace_bytes_strict(Tt, M); }
+extern "C" size_t alive_knn_workspace_bytes_sub(int64_t Tt, int64_t M) {       // alive_knn_search_fp6_sub_timed
+    const size_t a = ws_layout(nullptr, Tt, M, 4, false, true).bytes, b = ws_layout(nullptr, Tt, M, ALIVE_MAX_K, false, true).bytes;
+    return a > b ? a : b;
+}
 
 // The collect tier: the frames whose bf16 certificate failed (list1, with the thresholds thr1 the rescoring kernel recorded
 // for them) go through the bf16 scoring kernel once more, in its COLLECT form -- every row whose stage score reaches the
@@ -3553,7 +3736,8 @@ extern "C" int alive_knn_search_timed(const float* src, int N, int T, const void
 static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f8, const void* lib_bf16, const float* rows_f32,
                                const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
                                void* ws, void* stream, hipEvent_t g_ev_start, hipEvent_t g_ev_stop, int fmt = 0,
-                               const float* y_rot = nullptr, float rot_c0 = 0.0f) {
+                               const float* y_rot = nullptr, float rot_c0 = 0.0f, const float* y_sub = nullptr,
+                               const void* lib_sub = nullptr, const float* rho = nullptr) {
     // y_rot != NULL (fp8 only): lib_f8 holds the ROTATED codes of the rows (alive_library_pack_fp8_rot) and y_rot the frames' rotated
     // coordinates [N][576][T]: the frames' codes come from rot_codes_kernel, the stage's error prior is SD_PRIOR8R; everything else --
     // exact rescoring on the original rows, certificates, the bf16 tiers on lib_bf16 -- is the plain search's
@@ -3562,7 +3746,7 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
     const int64_t Tt = (int64_t)N * T;
     if (k > KH)
         return knn_search_impl(src, N, T, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream, g_ev_start, g_ev_stop);
-    const SearchWs w = ws_layout(ws, Tt, M, k);
+    const SearchWs w = ws_layout(ws, Tt, M, k, false, y_sub != nullptr);
     const bool f6 = fmt == 2;
     const SearchPlan& p = f6 ? w.p6 : w.p8;
     const SearchPlan& pp = f6 ? w.pp6 : w.pp;
@@ -3574,13 +3758,16 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
         return knn_scan_launch(src, T, Tt, rows_f32, norms, M, idx_base, k, w.s_f32, w.s_bf16, w.pv, w.pi, out_val, out_idx, w.stats, s, g_ev_start, g_ev_stop);
     if (int rc = lds_optin("alive_knn_search_fp8")) return rc;
     // (history tag: library size, frame count and stage -- a workspace that was last used for another search starts over)
-    const int hist_tag = (int)(((uint64_t)M * 0x9E3779B1u) ^ ((uint64_t)Tt * 0x85EBCA77u) ^ (f6 ? 0x6u : (y_rot != nullptr ? 0x18u : 0x8u))) | 1;
+    const int hist_tag = (int)(((uint64_t)M * 0x9E3779B1u) ^ ((uint64_t)Tt * 0x85EBCA77u) ^
+                               (f6 ? (y_sub != nullptr ? 0x36u : 0x6u) : (y_rot != nullptr ? 0x18u : 0x8u))) | 1;
     stats_init_kernel<<<1, 64, 0, s>>>(w.stats, f6 ? TIER_FP6 : TIER_FP8, w.probe_n > 0 ? hist_tag : 0);
     src_prep_launch(w, src, T, Tt, s);
     if (f6) {
         const int64_t n32 = p.Tt_pad * D / 32;
         (void)hipMemsetAsync(w.clip6, 0, (size_t)p.Tt_pad, s);
         to_fp6_kernel<<<(unsigned)((n32 + 255) / 256), 256, 0, s>>>(w.s_bf16, n32, w.p16.Tt_pad * D / 32, (u32x4*)w.s_f8, w.clip6);
+        if (y_sub != nullptr)
+            sub_codes_kernel<<<(unsigned)(p.Tt_pad / 32), 256, 0, s>>>(y_sub, w.sub_nrm, T, Tt, p.Tt_pad, w.sub_f6, w.sub_g, w.sub_flag, w.stats);
     } else if (y_rot != nullptr) {
         rot_codes_kernel<<<(unsigned)(p.Tt_pad / 32), 256, 0, s>>>(y_rot, Tt, p.Tt_pad, T, 1, rot_c0, w.s_f8);
     } else {
@@ -3606,10 +3793,17 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
                                                                           pre, prior, nullptr, nullptr, nullptr, 0, 0.0f, f6 ? w.clip6 : nullptr);
         probe_decide_kernel<<<1, 1, 0, s>>>(w.stats, w.probe_n, PROBE_NUM, PROBE_DEN);
     }
+    if (y_sub != nullptr) sub_select_kernel<<<(unsigned)((p.Tt_pad + 255) / 256), 256, 0, s>>>(w.sub_flag, w.clip6, p.Tt_pad, w.stats);
     // ---- mode 0: the fp8 / fp6 stage first ----
     const SeedArgs sa8 = seeds_for(w, p.Tt_pad / ft, p.split, k, f6 ? SEED_MARGIN6 : SEED_MARGIN8, ST_SEEDED, s, f6 ? SEED_MIN_FB6 : SEED_MIN_FB);
     if (g_ev_start) (void)hipEventRecord(g_ev_start, s);             // behind the memset of the seed flags: the events bracket the kernel alone
-    if (f6)
+    if (y_sub != nullptr) {            // one of the two runs: the gate word of sub_select_kernel (1 subspace, 2 plain, 0 neither)
+        const int* gate = w.stats + ST_SUB_GATE;
+        knn_sub6_kernel<<<dim3((unsigned)(p.Tt_pad / ft), p.split), 256, SUB6_LDS, s>>>(
+            w.sub_f6, (const unsigned char*)lib_sub, rho, w.sub_g, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, gate, 0, 1, sa8);
+        knn_score6_kernel<<<dim3((unsigned)(p.Tt_pad / ft), p.split), 256, lds, s>>>(
+            w.s_f8, (const unsigned char*)lib_f8, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, gate, 1, 2, sa8);
+    } else if (f6)
         knn_score6_kernel<<<dim3((unsigned)(p.Tt_pad / ft), p.split), 256, lds, s>>>(
             w.s_f8, (const unsigned char*)lib_f8, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, mode, -1, 0, sa8);
     else
@@ -3675,13 +3869,44 @@ extern "C" int alive_knn_search_fp6_timed(const float* src, int N, int T, const 
                                (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 2);
 }
 
-// device pointer (inside ws) to the counters of the last search on this workspace, int[16] (ST_WORDS; slots used today: 0-4, 7-12):
+// The subspace form of the fp6 search (knn_sub6_kernel): y_sub = [U | u]^T src [N][576][T] (alive_conv1d of the frames, unnormalised),
+// lib_sub / rho from alive_library_pack_fp6_sub, lib_f6 the plain fp6 image (the stage falls back to it on the device when more than
+// RESEARCH_MIN frames leave the subspace or clip).  The events bracket both scoring launches; everything behind the stage is the plain
+// fp6 search's.
+extern "C" int alive_knn_search_fp6_sub_timed(const float* src, const float* y_sub, int N, int T, const void* lib_sub, const float* rho,
+                                              const void* lib_f6, const void* lib_bf16, const float* rows_f32, const float* norms, int64_t M,
+                                              int64_t idx_base, int k, float* out_val, int32_t* out_idx, void* ws, void* stream,
+                                              void* ev_start, void* ev_stop) {
+    ALIVE_CHECK_ARG(y_sub && lib_sub && rho, "alive_knn_search_fp6_sub: null subspace operand");
+    return knn_search_fp8_impl(src, N, T, lib_f6, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream,
+                               (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 2, nullptr, 0.0f, y_sub, lib_sub, rho);
+}
+extern "C" int alive_knn_sub_coordinates(void) { return SUB_C; }
+extern "C" size_t alive_library_fp6_sub_bytes(int64_t M) { return (size_t)alive_library_padded_rows(M) * SUB_K; }
+// y_rows: [count][576] fp32 coordinates of the unit rows m0 .. m0 + count - 1 (U^T r^ in 0 .. 511, u . r^ in 512); lib_sub: alive_library_fp6_sub_bytes(M),
+// rho: [M_pad] fp32; *clip (device int, zeroed by the caller) is set when a code clipped (the caller then keeps the plain stage)
+extern "C" int alive_library_pack_fp6_sub(const float* y_rows, int64_t m0, int64_t count, int64_t M, void* lib_sub, float* rho, int* clip,
+                                          void* stream) {
+    ALIVE_CHECK_ARG(y_rows && lib_sub && rho && clip && M >= 1 && m0 >= 0 && count >= 1 && m0 + count <= M && (m0 % 32) == 0,
+                    "alive_library_pack_fp6_sub: bad args (m0 must be a multiple of 32)");
+    const int64_t m_pad = alive_library_padded_rows(M);
+    const int64_t span = m0 + count == M ? m_pad - m0 : count;          // the last chunk also zeroes the padding rows
+    const int64_t n = span * (SUB_K / 32);
+    lib_sub6_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(y_rows, count, span, (unsigned char*)lib_sub + (size_t)m0 * SUB_K,
+                                                                                 rho + m0, clip);
+    ALIVE_CHECK_LAUNCH("alive_library_pack_fp6_sub");
+    return ALIVE_OK;
+}
+
+// device pointer (inside ws) to the counters of the last search on this workspace, int[32] (ST_WORDS; slots used today: 0-4, 7-21):
 //   [0] frames the fp8 certificate sent to the bf16 stage (all frames when the probe chose bf16 first)
 //   [1] frames the bf16 certificate sent on (to the collect tier; [8] of them end in the exact scan)
 //   [2] frames of the probe sample, [3] of which failed the fp8 certificate, [4] 1 = the probe chose bf16 first
 //   [7] the path taken: 1 streaming scan, 2 exact scan of every frame (k > 8), 3 bf16 first, 4 fp8 first
 //   [8] frames the collect tier could not hold (dense clusters) -> exact scan;  [1] then counts the frames sent to the collect tier
 //       (strict search with a lo-plane library: the collect tier IS the split-bf16 pass)
+//   [14] / [15] subspace search: frames flagged by sub_codes_kernel (out of the subspace or clipped) / of them clipped;
+//   [20] / [21] its form and gate word: 1 the subspace kernel, 2 the plain fp6 kernel; [21] = 0: neither ran (bf16 first)
 // (the counters are the first thing in the workspace: their address depends on neither the batch nor k)
 extern "C" const int* alive_knn_search_stats(int N, int T, int64_t M, void* ws) {
     return ws_layout(ws, (int64_t)N * T, M, 4).stats;

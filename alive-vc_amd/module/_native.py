@@ -64,6 +64,11 @@ PROTOTYPES = {
     "alive_knn_search_timed": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_knn_search_fp8_timed": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_library_pack_fp6": (_I, [_VP, _I64, _VP, _VP]),
+    "alive_knn_sub_coordinates": (_I, []),
+    "alive_knn_workspace_bytes_sub": (_SZ, [_I64, _I64]),
+    "alive_library_fp6_sub_bytes": (_SZ, [_I64]),
+    "alive_library_pack_fp6_sub": (_I, [_VP, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
+    "alive_knn_search_fp6_sub_timed": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_knn_rot_coordinates": (_I, []),
     "alive_knn_rot_leading": (_I, []),
     "alive_knn_rot_mixed": (_I, []),

@@ -94,6 +94,8 @@ class PackedLibrary:
                 self.prefilter, self.fp6_declined = "fp8", True
         if self.rot is None and self.prefilter in ("fp8", "fp6"):
             self.lib_f8 = self._pack_stage(self.prefilter)
+        self.sub = None                    # subspace fp6 stage (set_subspace): {"W": packed 1x1 conv weights, "lib": codes, "rho": ...}
+        self.sub_forms = []                # forms built for recent encoders: (weight, its version, bias, its version, form or None)
         self.bound = None
         self.lib_lo = None
         if self.strict:
@@ -156,15 +158,65 @@ class PackedLibrary:
         # the frames' change of basis is a 1x1 conv 768 -> 576 on two bf16 planes (2^-16: far below the stage's 8-bit digits)
         self.rot = {"W": pack_conv_split(W.t().contiguous().unsqueeze(2), 2), "co": rc, "basis": W, "c0": c0}
 
-    def _rotate_frames(self, source):
-        """source [n, 768, t] -> W^T source [n, 576, t] through alive_conv1d (split bf16)"""
+    def use_subspace(self, weight, bias):
+        """set_subspace for the encoder output layer (weight, bias) unless this library already holds its form: the last few forms are
+        kept by the tensors themselves (strong references, so an identity cannot be reused) and their versions, so converters with
+        different encoders that share a library do not repack it on every search"""
+        for f in self.sub_forms:
+            if f[0] is weight and f[1] == weight._version and f[2] is bias and f[3] == bias._version:
+                self.sub = f[4]
+                return self
+        self.set_subspace(weight, bias)
+        self.sub_forms = [(weight, weight._version, bias, bias._version, self.sub)] + self.sub_forms[:3]
+        return self
+
+    def set_subspace(self, weight, bias, chunk=131072):
+        """Search through the subspace form of the fp6 stage (csrc/knn.hip knn_sub6_kernel): frames of the form q = weight h + bias
+        (the content encoder's output_layer, weight [768, 512(, 1)]) are scored on their 512 coordinates in an orthonormal basis U of
+        span(weight) plus g rho along u, the unit part of bias outside span(weight).  A frame that is not of that form is caught on the
+        device and goes to the next tier (or, many of them, the whole batch to the plain fp6 stage): a wrong basis costs time, never
+        results.  Only a plain fp6 library takes the form; the basis is built in float64, the rows' codes by alive_library_pack_fp6_sub.
+        """
+        from ._pack import pack_conv_split
+        if self.prefilter != "fp6" or self.strict or self.rot is not None or self.lib_f8 is None or self.M == 0:
+            self.sub = None
+            return self
+        L = nat.lib()
+        dev = self.rows.device
+        Wt = weight.detach().reshape(DIM, -1).to("cpu", torch.float64)
+        b = bias.detach().reshape(DIM).to("cpu", torch.float64)
+        U = torch.linalg.qr(Wt)[0]                               # [768, 512] orthonormal basis of span(W)
+        bp = b - U @ (U.t() @ b)
+        nb = float(bp.norm())
+        u = bp / nb if nb > 1e-9 * max(1.0, float(b.norm())) else torch.zeros_like(bp)
+        co = L.alive_knn_sub_coordinates()
+        B = torch.zeros(DIM, co, dtype=torch.float64)
+        B[:, :U.shape[1]] = U
+        B[:, 512] = u
+        B = B.float().to(dev)
+        lib = torch.empty(L.alive_library_fp6_sub_bytes(self.M), dtype=torch.uint8, device=dev)
+        rho = torch.empty(L.alive_library_padded_rows(self.M), dtype=torch.float32, device=dev)
+        clip = torch.zeros(1, dtype=torch.int32, device=dev)
+        for s0 in range(0, self.M, chunk):                                                    # (chunk is a multiple of 32)
+            y = ((self.rows[s0:s0 + chunk] / self.norms[s0:s0 + chunk, None]) @ B).contiguous()
+            nat.check(L.alive_library_pack_fp6_sub(nat.ptr(y), s0, y.shape[0], self.M, nat.ptr(lib), nat.ptr(rho), nat.ptr(clip),
+                                                   nat.stream()), "alive_library_pack_fp6_sub")
+        if int(clip.item()) != 0:                  # a row coordinate beyond e2m3's range: keep the plain stage (as _fp6_would_clip)
+            self.sub = None
+            return self
+        self.sub = {"W": pack_conv_split(B.t().contiguous().unsqueeze(2), 2), "co": co, "lib": lib, "rho": rho}
+        return self
+
+    def _rotate_frames(self, source, form=None):
+        """source [n, 768, t] -> W^T source [n, co, t] through alive_conv1d (split bf16): the rotated fp8 stage's basis, or form["W"]"""
         import ctypes as C
+        form = self.rot if form is None else form
         n, d, t = source.shape
-        y = torch.empty(n, self.rot["co"], t, device=source.device)
-        W = self.rot["W"]
+        y = torch.empty(n, form["co"], t, device=source.device)
+        W = form["W"]
         dsc = nat.AliveConv()
         dsc.W, dsc.bias, dsc.X = nat.ptr(W), None, nat.ptr(source)
-        dsc.N, dsc.Ci, dsc.Tin, dsc.Co, dsc.K_pad = n, d, t, self.rot["co"], W.shape[1] * 32
+        dsc.N, dsc.Ci, dsc.Tin, dsc.Co, dsc.K_pad = n, d, t, form["co"], W.shape[1] * 32
         dsc.precision, dsc.Ci_pad = 1, d
         dsc.KW, dsc.stride, dsc.dil, dsc.pad_left, dsc.pad_mode = 1, 1, 1, 0, 0
         dsc.Tout, dsc.up, dsc.act = t, 1, 0
@@ -192,7 +244,9 @@ class PackedLibrary:
         val = torch.empty(n * t, k, dtype=torch.float32, device=source.device)
         idx = torch.empty(n * t, k, dtype=torch.int32, device=source.device)
         split = self.strict and self.lib_lo is not None          # the split-bf16 collect tier needs the frames' two planes as well
-        ws = self._ws.get((L.alive_knn_workspace_bytes_strict if split else L.alive_knn_workspace_bytes_fast)(n * t, self.M), source.device)
+        sub = self.sub is not None and self.prefilter == "fp6" and not self.strict and self.rot is None
+        wsb = L.alive_knn_workspace_bytes_strict if split else (L.alive_knn_workspace_bytes_sub if sub else L.alive_knn_workspace_bytes_fast)
+        ws = self._ws.get(wsb(n * t, self.M), source.device)
         ev = (None, None) if events is None else (events[0].cuda_event, events[1].cuda_event)
         if self.strict:
             nat.check(L.alive_knn_search_strict(nat.ptr(source), n, t, nat.ptr(self.lib_bf16), nat.ptr(self.lib_lo), nat.ptr(self.rows), nat.ptr(self.norms),
@@ -203,6 +257,12 @@ class PackedLibrary:
             nat.check(L.alive_knn_search_fp8_rot_timed(nat.ptr(source), nat.ptr(y), self.rot["c0"], n, t, nat.ptr(self.lib_f8), nat.ptr(self.lib_bf16),
                                                        nat.ptr(self.rows), nat.ptr(self.norms), self.M, self.idx_base, k,
                                                        nat.ptr(val), nat.ptr(idx), nat.ptr(ws), nat.stream(), *ev), "alive_knn_search_fp8_rot")
+        elif sub:
+            y = self._rotate_frames(source, self.sub)
+            nat.check(L.alive_knn_search_fp6_sub_timed(nat.ptr(source), nat.ptr(y), n, t, nat.ptr(self.sub["lib"]), nat.ptr(self.sub["rho"]),
+                                                       nat.ptr(self.lib_f8), nat.ptr(self.lib_bf16), nat.ptr(self.rows), nat.ptr(self.norms),
+                                                       self.M, self.idx_base, k, nat.ptr(val), nat.ptr(idx), nat.ptr(ws), nat.stream(), *ev),
+                      "alive_knn_search_fp6_sub")
         elif self.lib_f8 is not None:
             fn = L.alive_knn_search_fp6_timed if self.prefilter == "fp6" else L.alive_knn_search_fp8_timed
             nat.check(fn(nat.ptr(source), n, t, nat.ptr(self.lib_f8), nat.ptr(self.lib_bf16),
@@ -212,7 +272,7 @@ class PackedLibrary:
             nat.check(L.alive_knn_search_timed(nat.ptr(source), n, t, nat.ptr(self.lib_bf16), nat.ptr(self.rows),
                                                nat.ptr(self.norms), self.M, self.idx_base, k, nat.ptr(val), nat.ptr(idx),
                                                nat.ptr(ws), nat.stream(), *ev), "alive_knn_search")
-        self._last = (n, t, k, ws)
+        self._last = (n, t, k, ws, sub)
         return val, idx
 
 
@@ -226,9 +286,11 @@ class PackedLibrary:
         other.__dict__.pop("search", None)             # an instrumented search (bench.py) stays with the original
         if rotated and self.rot is not None and prefilter == "fp8":
             other._ws, other._last = nat.Workspace(), None
-            other.strict, other.bound, other.lib_lo = False, None, None
+            other.strict, other.bound, other.lib_lo, other.sub, other.sub_forms = False, None, None, None, []
             return other
         was_rot, other.rot = self.rot is not None, None
+        other.sub = self.sub if prefilter == "fp6" else None
+        other.sub_forms = self.sub_forms if prefilter == "fp6" else []
         other.fp6_declined = prefilter == "fp6" and self._fp6_would_clip()
         if other.fp6_declined:
             prefilter = "fp8"
@@ -254,14 +316,16 @@ class PackedLibrary:
         last = getattr(self, "_last", None)
         if last is None:
             return None
-        n, t, k, ws = last
+        n, t, k, ws, sub = last
         torch.cuda.synchronize()
         st = {"prefilter": self.prefilter, "certificate": "deterministic" if self.strict else "statistical"}
         if getattr(self, "rot", None) is not None:
             st["rotated_operands"] = True          # dense bank: the fp8 stage on the bank's own basis (csrc/knn.hip rot_codes_kernel)
         off = nat.lib().alive_knn_search_stats(n, t, self.M, nat.ptr(ws)) - ws.data_ptr()
-        c = ws[off:off + 64].view(torch.int32).tolist()       # int[16]: knn.hip ST_*
+        c = ws[off:off + 128].view(torch.int32).tolist()      # int[32]: knn.hip ST_*
         tier = c[7]                                     # written by the C side on every path (knn.hip: ST_TIER)
+        if sub and tier == 5:                           # subspace form (knn.hip ST_SUB_*): which kernel scored, frames flagged / clipped
+            st.update(stage_form={1: "subspace", 2: "plain"}.get(c[21], "none"), frames_left_subspace=c[14] - c[15], frames_clipped=c[15])
         if tier == 1:
             return dict(st, tier="exact scan of every row (streaming)")
         if tier == 2:

@@ -110,9 +110,23 @@ class Converter:
         self.library = None
 
     def set_library(self, tokens):
-        """tokens [1, 768, M] (voice_library.pt layout) or an already packed PackedLibrary."""
+        """tokens [1, 768, M] (voice_library.pt layout) or an already packed PackedLibrary.  A plain fp6 library gets the subspace form
+        of its candidate stage from the content encoder's output layer (PackedLibrary.set_subspace)."""
         self.library = tokens if isinstance(tokens, PackedLibrary) else PackedLibrary(tokens[0].to(self.device))
+        self._subspace()
         return self
+
+    def _subspace(self):
+        """(re)build the library's subspace basis when the encoder's output layer is not the one it was built from (load_state_dict
+        replaces the tensors)"""
+        lib = self.library
+        if not isinstance(lib, PackedLibrary) or getattr(self.ce, "generic", False):
+            return
+        sd = self.ce._sd
+        w, b = sd.get("output_layer.weight"), sd.get("output_layer.bias")
+        if w is None or b is None or w.shape[0] != 768 or w.shape[1] != 512:
+            return
+        lib.use_subspace(w, b)
 
     def features(self, windows, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, frames=None, out=None, world_pitch=False):
         """spectrogram -> f0 (+ per-window pitch transform) and content features   (inference.py:112-128).
@@ -231,6 +245,7 @@ class Converter:
         return feat, f0
 
     def match(self, feat, k=4, alpha=0.0):
+        self._subspace()
         val, idx = self.library.search(feat, k)
         return merge_gather(val, idx, 1, k, alpha, self.library.rows, feat)
 

@@ -194,6 +194,28 @@ int alive_knn_search_fp6_timed(const float* src, int N, int T,
                                int64_t M, int64_t idx_base, int k,
                                float* out_val, int32_t* out_idx, void* ws, void* stream, void* ev_start, void* ev_stop);
 
+/* The subspace form of the fp6 stage (knn.hip knn_sub6_kernel): the content encoder's frames are q = W h + b with W 768 x 512, so
+ * q^ . r^ = x_f . y_r + g_f rho_r with x = U^T q^, y = U^T r^ (U an orthonormal basis of span(W)), g = u . q^, rho = u . r^ (u the unit
+ * part of b outside span(W)).  The candidate stage scores the 512 coordinates on the fp6 MFMA and adds g_f rho_r in fp32; rescoring,
+ * certificate and the tiers behind it are the plain fp6 search's, on the original rows.
+ *   alive_library_pack_fp6_sub: y_rows [count][alive_knn_sub_coordinates()] fp32 = [U | u]^T r^ of unit rows m0 .. m0 + count - 1
+ *     (m0 a multiple of 32) -> lib_sub (alive_library_fp6_sub_bytes(M)) and rho [M_pad]; *clip (device int, zeroed by the caller) is
+ *     set when a code clipped (the caller keeps the plain stage then).
+ *   alive_knn_search_fp6_sub_timed: y_sub = [U | u]^T src as [N][alive_knn_sub_coordinates()][T] (unnormalised); lib_f6 is the plain
+ *     fp6 image: frames that leave the subspace (or clip) are forced into the next tier, and when more than 64 of a batch do, the
+ *     batch is scored by the plain fp6 kernel instead -- decided on the device, no host sync.  ev_start / ev_stop bracket the
+ *     scoring launches.  Counters (alive_knn_search_stats): [14] frames flagged, [15] of them clipped, [21] which kernel scored
+ *     (1 subspace, 2 plain fp6, 0 neither: the probe chose bf16 first). */
+int alive_knn_sub_coordinates(void);
+size_t alive_knn_workspace_bytes_sub(int64_t Tt, int64_t M);      /* the workspace of alive_knn_search_fp6_sub_timed */
+size_t alive_library_fp6_sub_bytes(int64_t M);
+int alive_library_pack_fp6_sub(const float* y_rows, int64_t m0, int64_t count, int64_t M, void* lib_sub, float* rho, int* clip,
+                               void* stream);
+int alive_knn_search_fp6_sub_timed(const float* src, const float* y_sub, int N, int T, const void* lib_sub, const float* rho,
+                                   const void* lib_f6, const void* lib_bf16, const float* rows_f32, const float* norms, int64_t M,
+                                   int64_t idx_base, int k, float* out_val, int32_t* out_idx, void* ws, void* stream,
+                                   void* ev_start, void* ev_stop);
+
 /* alive_knn_merge_gather: merge n_shards exact top-k lists ([S][Tt][k], e.g.
  * after an RCCL all-gather), pick the global top-k, gather those rows from the
  * full fp32 row table, mean over k, alpha-blend with the source.  n_shards * k <= 512.
