@@ -4105,3 +4105,125 @@ extern "C" int alive_knn_search_pool(const float* src, int N, int T, const void*
     ALIVE_CHECK_LAUNCH("alive_knn_search_pool");
     return ALIVE_OK;
 }
+
+// ---- reserved voice pool: append a voice in place, move segments (live enrolment) ----
+// lib_pack_kernel's rows and norms for tokens read through strides (feature d, token m at tok[d * rs + m * cs]), written at row
+// `at` of a table that is not replaced.  The arithmetic is lib_pack_kernel's to the operation: wave wv adds features wv, wv + 4, ...
+// in that order with fmaf, the four partial sums are added left to right, one sqrtf -- so rows and norms are bitwise those of
+// alive_library_pack_rows on the same tokens, whatever M is (a row's norm depends on its own column alone).  Each new norm is
+// checked here: report[0] counts the rows whose norm is zero or not finite, report[1] keeps the lowest such pool row.
+__global__ void pool_report_init_kernel(int32_t* __restrict__ report) {
+    report[0] = 0;
+    report[1] = INT32_MAX;
+}
+
+__global__ __launch_bounds__(256) void pool_append_kernel(const float* __restrict__ tok, int64_t rs, int64_t cs, int64_t M, int64_t at,
+                                                          float* __restrict__ rows, float* __restrict__ norms,
+                                                          int32_t* __restrict__ report) {
+    __shared__ float red[4][64];
+    __shared__ float tile[64][65];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t m0 = (int64_t)blockIdx.x * 64;
+    const int64_t m = m0 + lane;
+    const bool ok = m < M;
+    const float* col = tok + (ok ? m : 0) * cs;
+    float ss = 0.0f;
+    for (int d = wv; d < D; d += 4) {
+        float v = ok ? col[(int64_t)d * rs] : 0.0f;
+        ss = fmaf(v, v, ss);
+    }
+    red[wv][lane] = ss;
+    __syncthreads();
+    if (wv == 0 && ok) {
+        const float nn = sqrtf(red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
+        norms[at + m] = nn;
+        if (!(nn > 0.0f && nn < __builtin_huge_valf())) {       // zero, NaN or Inf: such a row would match every frame
+            atomicAdd(&report[0], 1);
+            atomicMin(&report[1], (int32_t)(at + m));
+        }
+    }
+    for (int d0 = 0; d0 < D; d0 += 64) {
+        for (int r = wv; r < 64; r += 4) tile[r][lane] = ok ? col[(int64_t)(d0 + r) * rs] : 0.0f;
+        __syncthreads();
+        for (int r = wv; r < 64; r += 4) {      // r = token inside the block, lane = feature
+            const int64_t mm = m0 + r;
+            if (mm < M) rows[(size_t)(at + mm) * D + d0 + lane] = tile[lane][r];
+        }
+        __syncthreads();
+    }
+}
+
+// Move n elements of `base` from src to dst where the ranges may overlap, in ONE launch and without scratch.  With shift =
+// |src - dst|, element i of the range belongs to chain i mod shift: the chain's elements i, i + shift, i + 2 shift, ... are the only
+// ones whose source or destination has its residue, so chains never touch each other's memory and may run in any order on any
+// thread.  Inside a chain the copy is sequential in the safe direction -- ascending when moving down (an element lands on the source
+// of the chain's previous one, already read), descending when moving up -- by ONE thread, whose own loads and stores are ordered.
+// The loop works in groups of 8: all 8 loads, then the 8 stores (a store of the group lands on the source of the element before it,
+// loaded earlier in the group or in the previous one), which keeps 8 loads in flight.  `base` is deliberately not __restrict__.
+// Disjoint ranges (shift >= n) are the case of n chains of one element: a plain parallel copy.  A shift of one row still leaves
+// 192 float4 chains; compaction shifts are whole voices.
+typedef unsigned int pool_u32x4 __attribute__((ext_vector_type(4)));      // 16 bytes moved as one register quad
+
+template <typename T>
+__global__ __launch_bounds__(256) void pool_move_kernel(T* base, int64_t src, int64_t dst, int64_t n) {
+    const int64_t shift = src > dst ? src - dst : dst - src;
+    const int64_t chains = shift < n ? shift : n;
+    const bool down = dst < src;
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < chains; c += (int64_t)gridDim.x * 256) {
+        const int64_t count = (n - c + shift - 1) / shift;          // elements c + j * shift < n
+        const T* s = base + src + c;
+        T* d = base + dst + c;
+        int64_t j = 0;
+        for (; j + 8 <= count; j += 8) {
+            T v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = s[(down ? j + u : count - 1 - j - u) * shift];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) d[(down ? j + u : count - 1 - j - u) * shift] = v[u];
+        }
+        for (; j < count; ++j) {                                     // the chain's last elements, one by one
+            const T v = s[(down ? j : count - 1 - j) * shift];
+            d[(down ? j : count - 1 - j) * shift] = v;
+        }
+    }
+}
+
+template <typename T>
+static void pool_move_launch(T* base, int64_t src, int64_t dst, int64_t n, hipStream_t s) {
+    const int64_t shift = src > dst ? src - dst : dst - src;
+    const int64_t chains = shift < n ? shift : n;
+    const int64_t blocks = (chains + 255) / 256;
+    pool_move_kernel<T><<<(unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)), 256, 0, s>>>(base, src, dst, n);
+}
+
+extern "C" int alive_pool_append(const float* tokens, int64_t row_stride, int64_t col_stride, int64_t M, int Dd, float* rows_f32,
+                                 float* norms, int64_t capacity, int64_t at, int32_t* report, void* stream) {
+    ALIVE_CHECK_ARG(tokens && rows_f32 && norms && report, "alive_pool_append: null pointer");
+    ALIVE_CHECK_ARG(Dd == D, "alive_pool_append: feature dim %d, expected %d", Dd, D);
+    ALIVE_CHECK_ARG(capacity >= 1 && capacity < (int64_t)1 << 31, "alive_pool_append: capacity %lld out of range", (long long)capacity);
+    ALIVE_CHECK_ARG(M >= 1 && at >= 0 && M <= capacity && at <= capacity - M,
+                    "alive_pool_append: rows [%lld, +%lld) outside the table of %lld rows", (long long)at, (long long)M, (long long)capacity);
+    ALIVE_CHECK_ARG(row_stride >= 0 && col_stride >= 0, "alive_pool_append: negative stride (%lld, %lld)", (long long)row_stride,
+                    (long long)col_stride);
+    hipStream_t s = (hipStream_t)stream;
+    pool_report_init_kernel<<<1, 1, 0, s>>>(report);
+    pool_append_kernel<<<(unsigned)((M + 63) / 64), 256, 0, s>>>(tokens, row_stride, col_stride, M, at, rows_f32, norms, report);
+    ALIVE_CHECK_LAUNCH("alive_pool_append");
+    return ALIVE_OK;
+}
+
+extern "C" int alive_pool_move_rows(float* rows_f32, float* norms, int64_t capacity, int64_t src, int64_t dst, int64_t n, void* stream) {
+    ALIVE_CHECK_ARG(rows_f32 && norms, "alive_pool_move_rows: null pointer");
+    ALIVE_CHECK_ARG(((uintptr_t)rows_f32 & 15) == 0, "alive_pool_move_rows: the row table must be 16-byte aligned");
+    ALIVE_CHECK_ARG(capacity >= 1 && capacity < (int64_t)1 << 31, "alive_pool_move_rows: capacity %lld out of range", (long long)capacity);
+    ALIVE_CHECK_ARG(n >= 1 && n <= capacity && src >= 0 && dst >= 0 && src <= capacity - n && dst <= capacity - n,
+                    "alive_pool_move_rows: %lld rows from %lld to %lld outside the table of %lld rows", (long long)n, (long long)src,
+                    (long long)dst, (long long)capacity);
+    if (src == dst) return ALIVE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    constexpr int64_t Q = D / 4;                                 // a row is 192 quads
+    pool_move_launch<pool_u32x4>((pool_u32x4*)rows_f32, src * Q, dst * Q, n * Q, s);      // bytes, not floats: bitwise by construction
+    pool_move_launch<unsigned int>((unsigned int*)norms, src, dst, n, s);
+    ALIVE_CHECK_LAUNCH("alive_pool_move_rows");
+    return ALIVE_OK;
+}

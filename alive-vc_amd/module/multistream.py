@@ -9,7 +9,9 @@ One tick runs the whole device pipeline once over [B, ring]: the networks see a 
 exact search (csrc/knn.hip: alive_knn_search_grouped -- row n searches its own pool segment), and the per-user edges read
 per-row device arrays (alive_pitch_transform_rows, alive_knn_merge_gather_rows, alive_resample_rows).  Every per-session
 value lives in those device arrays, so opening, closing or re-configuring a slot never re-captures the step's hipGraph; the
-launch sizes depend on B alone.  Adding a voice to the pool re-packs the pool: the next tick re-captures.
+launch sizes depend on B alone.  Adding a voice to a default pool re-packs the pool: the next tick re-captures.  On a reserved
+pool (VoicePool(capacity=ROWS): one table for the pool's life) voices are enrolled, grown, removed and compacted between ticks
+without a re-capture: the slots hold their voices, and a tick that finds pool.layout changed rewrites its segment arrays first.
 
 Per slot, as RealtimeConverter.step: the ring fills chunk by chunk, the slot emits None until its ring has held more than
 `buffersize` chunks, and the phase is carried through phi[:, :, end_of_output] -- 0 while the slot fills, reset by `open`.
@@ -130,16 +132,168 @@ def _tokens_2d(tokens):
     return t
 
 
+class RowAllocator:
+    """The host side of a reserved pool: named segments [lo, lo + n) of `capacity` rows.  Plain Python, no device.
+
+    The only state is the segment map; holes are derived from it (the gaps between the segments in address order, the space after
+    the highest one last), so a freed segment is coalesced with its neighbours by construction and there is no free list to keep
+    in step.  Placement is first-fit in address order.  Every method either succeeds or raises and leaves the map as it was.
+
+    `layout` counts the operations that changed some EXISTING segment's (lo, n): extend (in place or moved) and a compact that moved
+    something; add and remove do not.  `hold` / `release` count the users of a segment by label; a held segment cannot be removed."""
+
+    def __init__(self, capacity):
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity < 2 ** 31:
+            raise ValueError(f"a reserved pool holds 1 <= capacity < 2^31 rows (got {capacity!r})")
+        self.capacity = int(capacity)
+        self.segments = {}
+        self.layout = 0
+        self.holds = {}
+
+    def holes(self):
+        """the free ranges [(lo, n), ...] in address order"""
+        out, at = [], 0
+        for lo, n in sorted(self.segments.values()):
+            if lo > at:
+                out.append((at, lo - at))
+            at = lo + n
+        if at < self.capacity:
+            out.append((at, self.capacity - at))
+        return out
+
+    @property
+    def free_rows(self):
+        return self.capacity - sum(n for _, n in self.segments.values())
+
+    @property
+    def largest_hole(self):
+        return max([n for _, n in self.holes()] or [0])
+
+    def _fit(self, n, what):
+        for lo, size in self.holes():
+            if size >= n:
+                return lo
+        raise ValueError(f"{what}: needs {n} rows, the pool of {self.capacity} has {self.free_rows} free and its largest hole is "
+                         f"{self.largest_hole}" + (": compact() would make room" if n <= self.free_rows else ": the pool is too small"))
+
+    def add(self, name, n):
+        """place a new segment of n rows in the first hole that fits -> its first row"""
+        if name in self.segments:
+            raise ValueError(f"voice {name!r} is already in the pool")
+        if n < 1:
+            raise ValueError(f"voice {name!r} is empty")
+        lo = self._fit(n, f"voice {name!r}")
+        self.segments[name] = (lo, n)
+        return lo
+
+    def remove(self, name):
+        if name not in self.segments:
+            raise ValueError(f"unknown voice {name!r} (the pool holds {sorted(self.segments)})")
+        users = self.holds.get(name)
+        if users:
+            raise ValueError(f"voice {name!r} is in use by {', '.join(f'{w} ({c} hold(s))' for w, c in users.items())}: close or "
+                             "re-voice those sessions first")
+        return self.segments.pop(name)
+
+    def hold(self, name, who):
+        """count `who` (a label: a converter) as a user of the segment"""
+        if name not in self.segments:
+            raise ValueError(f"unknown voice {name!r} (the pool holds {sorted(self.segments)})")
+        users = self.holds.setdefault(name, {})
+        users[who] = users.get(who, 0) + 1
+
+    def release(self, name, who):
+        users = self.holds.get(name, {})
+        if users.get(who, 0) < 1:
+            raise ValueError(f"{who} holds no voice {name!r}")
+        users[who] -= 1
+        if users[who] == 0:
+            del users[who]
+        if not users:
+            del self.holds[name]
+
+    def extend(self, name, extra):
+        """grow a segment by `extra` rows -> (old_lo, old_n, new_lo): in place (new_lo == old_lo) when the hole behind it is large
+        enough, else in the first hole that takes the old and the new rows together (the old segment is freed; the caller copies
+        its rows from old_lo to new_lo, two disjoint ranges)"""
+        if name not in self.segments:
+            raise ValueError(f"unknown voice {name!r} (the pool holds {sorted(self.segments)})")
+        if extra < 1:
+            raise ValueError(f"voice {name!r}: nothing to append")
+        lo, n = self.segments[name]
+        end = lo + n
+        behind = min([l for l, _ in self.segments.values() if l >= end] or [self.capacity]) - end
+        new_lo = lo if behind >= extra else self._fit(n + extra, f"voice {name!r} (growing from {n} rows by {extra})")
+        self.segments[name] = (new_lo, n + extra)
+        self.layout += 1
+        return lo, n, new_lo
+
+    def undo_extend(self, name, lo, n):
+        """take back the latest extend of `name` (its new rows were refused)"""
+        self.segments[name] = (lo, n)
+        self.layout -= 1
+
+    def compact(self):
+        """slide every segment down, in address order, until no hole remains between segments -> the moves [(name, src, dst, n),
+        ...] in the order in which they must be made (each destination is free or part of its own source by then; src - dst < n
+        means the two ranges overlap)"""
+        moves, at = [], 0
+        for name, (lo, n) in sorted(self.segments.items(), key=lambda kv: kv[1]):
+            if lo != at:
+                moves.append((name, lo, at, n))
+                self.segments[name] = (at, n)
+            at += n
+        self.layout += bool(moves)
+        return moves
+
+
+def _token_parts(tokens):
+    """a voice's tokens -> the list of its [768, m] parts (a tensor, or a sequence of tensors appended in order)"""
+    parts = [_tokens_2d(t) for t in (tokens if isinstance(tokens, (list, tuple)) else [tokens])]
+    parts = [t for t in parts if t.shape[1] > 0]
+    return parts, sum(int(t.shape[1]) for t in parts)
+
+
 class VoicePool:
     """Named voices tokens[768, M] packed into one fp32 row table rows[P, 768] with norms[P] (the norms bitwise those of
-    PackedLibrary) and a name -> (seg_lo, M) map.  `add` re-packs the pool (a new row table): allowed between ticks, and a
-    MultiStreamConverter that replays a captured step re-captures on its next tick."""
+    PackedLibrary) and a name -> (seg_lo, M) map.
 
-    def __init__(self, voices=None, device="cuda"):
+    Default pool (capacity=None): `add` re-packs the pool (a new row table): allowed between ticks, and a MultiStreamConverter
+    that replays a captured step re-captures on its next tick.
+
+    Reserved pool (capacity=ROWS): rows[ROWS, 768] and norms[ROWS] are allocated once and never replaced (P == ROWS, `version`
+    stays put), so a captured tick keeps serving while voices are enrolled (`add`), grow (`extend`), go (`remove`) and are packed
+    together (`compact`).  Where each voice lies is decided by a RowAllocator; the device work is alive_pool_append (the new rows
+    only, with their norms checked on the device: the host reads two words, never the norms) and alive_pool_move_rows.  `tokens`
+    may be strided (a slice or an every-4th-frame view of an encoder output goes in without a copy) and, for `add` and `extend`, a
+    sequence of such parts.  `layout` counts the operations that changed some EXISTING voice's (seg_lo, seg_len): a converter
+    rewrites its segment arrays when it moved on.  `hold` / `release` count the users of a voice; a held voice cannot be removed.
+
+    Stream order: every operation runs on the CURRENT stream of the calling thread (torch.cuda.current_stream()) and records an
+    event there; neither allocates table-sized memory nor waits for the device, except that `add` / `extend` read the two-word
+    report back.  MultiStreamConverter makes the stream it replays the tick on wait for that event, so an operation issued between
+    two ticks is ordered before the next tick whatever stream it ran on; `step` returns after its tick has completed (it copies
+    the PCM to the host), so an operation issued between two ticks never overtakes the tick before it either."""
+
+    def __init__(self, voices=None, device="cuda", capacity=None):
         self.device = torch.device(device)
-        self._tokens = {}
         self.segments = {}
         self.version = 0
+        self.capacity = None
+        self._images = None
+        if capacity is not None:
+            self._alloc = RowAllocator(capacity)
+            self.capacity = self.P = self._alloc.capacity
+            self.segments = self._alloc.segments
+            self.rows = torch.empty(self.P, DIM, dtype=torch.float32, device=self.device)
+            self.norms = torch.empty(self.P, dtype=torch.float32, device=self.device)
+            self._report = torch.zeros(2, dtype=torch.int32, device=self.device)
+            self.mutations = 0                 # every operation; `order` is the event recorded after the latest one
+            self.order = None
+            for name, tok in (voices or {}).items():
+                self.add(str(name), tok)
+            return
+        self._tokens = {}
         self.rows = self.norms = None
         self.P = 0
         if voices:
@@ -148,9 +302,120 @@ class VoicePool:
             self._pack()
 
     def add(self, name, tokens):
+        if self.capacity is not None:
+            parts, m = _token_parts(tokens)
+            lo = self._alloc.add(str(name), m)                # first fit; raises (rows needed, free rows, largest hole) if none
+            try:
+                self._append(lo, parts)
+            except Exception:
+                self._alloc.remove(str(name))
+                raise
+            self._changed()
+            return self
         self._tokens[str(name)] = _tokens_2d(tokens).to(self.device, torch.float32).contiguous()
         self._pack()
         return self
+
+    # ------------------------------------------------------------------ reserved pool
+    def _reserved(self, what):
+        if self.capacity is None:
+            raise ValueError(f"VoicePool.{what} needs a reserved pool: VoicePool(..., capacity=ROWS)")
+
+    def _changed(self):
+        self.mutations += 1
+        self._images = None
+        self.order = torch.cuda.Event()
+        self.order.record(torch.cuda.current_stream(self.device))
+
+    def _append(self, at, parts):
+        """pack the parts at consecutive rows from `at` (the rows are the caller's to write); ValueError if a new row's norm is zero
+        or not finite -- read from the device's two-word report, not from the norms"""
+        L = nat.lib()
+        for t in parts:
+            if t.device != self.device or t.dtype != torch.float32:
+                t = t.to(self.device, torch.float32)
+            m = int(t.shape[1])
+            nat.check(L.alive_pool_append(t.data_ptr(), t.stride(0), t.stride(1), m, DIM, nat.ptr(self.rows), nat.ptr(self.norms),
+                                          self.P, at, nat.ptr(self._report), nat.stream()), "alive_pool_append")
+            bad, first = self._report.tolist()
+            if bad:
+                raise ValueError(f"voice pool row {first} has zero or non-finite norm ({bad} such row(s) among the new ones): "
+                                 "remove it")
+            at += m
+
+    def _move(self, src, dst, n):
+        nat.check(nat.lib().alive_pool_move_rows(nat.ptr(self.rows), nat.ptr(self.norms), self.P, src, dst, n, nat.stream()),
+                  "alive_pool_move_rows")
+
+    def extend(self, name, tokens):
+        """append rows to a live voice (old rows first): in place when the hole behind it is large enough, else the voice moves to
+        the first hole that takes the old and the new rows together"""
+        self._reserved("extend")
+        parts, extra = _token_parts(tokens)
+        lo, n, new_lo = self._alloc.extend(name, extra)
+        try:
+            self._append(new_lo + n, parts)                   # the new rows first: refused rows leave the voice as it was
+        except Exception:
+            self._alloc.undo_extend(name, lo, n)
+            raise
+        if new_lo != lo:
+            self._move(lo, new_lo, n)                         # (two disjoint ranges: the new hole was free)
+        self._changed()
+        return self
+
+    def remove(self, name):
+        self._reserved("remove")
+        self._alloc.remove(name)                              # raises while a converter holds the voice
+        self._changed()
+        return self
+
+    def compact(self):
+        """slide every voice down until no hole remains between voices.  A voice may move by less than its own length, so a move's
+        source and destination may overlap: alive_pool_move_rows copies chain by chain (the elements one shift apart), each chain
+        in the direction in which an element is read before it is overwritten (csrc/knn.hip: pool_move_kernel)"""
+        self._reserved("compact")
+        moves = self._alloc.compact()
+        for _, src, dst, n in moves:                          # address order: each destination is free, or its own source, by now
+            self._move(src, dst, n)
+        if moves:
+            self._changed()
+        return self
+
+    def hold(self, name, who):
+        """count `who` (a label: a converter) as a user of the voice; `remove` raises while any is left"""
+        self._reserved("hold")
+        self._alloc.hold(name, who)
+
+    def release(self, name, who):
+        self._reserved("release")
+        self._alloc.release(name, who)
+
+    @property
+    def layout(self):
+        self._reserved("layout")
+        return self._alloc.layout
+
+    def holes(self):
+        """the free ranges [(first row, rows), ...] in address order"""
+        self._reserved("holes")
+        return self._alloc.holes()
+
+    @property
+    def free_rows(self):
+        self._reserved("free_rows")
+        return self._alloc.free_rows
+
+    @property
+    def largest_hole(self):
+        self._reserved("largest_hole")
+        return self._alloc.largest_hole
+
+    def tokens(self, name):
+        """the voice's tokens [768, M], bitwise those that went in (a reserved pool keeps no copy: rebuilt from its rows)"""
+        lo, m = self.segment(name)
+        if self.capacity is None:
+            return self._tokens[name]
+        return self.rows[lo:lo + m].t().contiguous()
 
     def segment(self, name):
         if name not in self.segments:
@@ -181,7 +446,8 @@ class VoicePool:
         self._images = None
 
     def search_images(self):
-        """The pool search's tables, built on first use for this version of the pool (the streaming path never asks):
+        """The pool search's tables, built on first use after the pool changed (the streaming path never asks; a reserved pool
+        passes its live voices only, with P its capacity):
         a dict of the bf16 image buffer, device int64 img_off [V], int32 seg_lo / seg_len [V], float32 bounds [V] (the
         deterministic certificate's per-voice rounding bound), the voice names in table order, and the longest voice."""
         if self._images is not None:
@@ -216,6 +482,86 @@ class VoicePool:
                 raise ValueError(f"unknown voice {n!r} (the pool holds {sorted(index)})")
             ids.append(-1 if n is None else index[n])
         return torch.tensor(ids, dtype=torch.int32, device=self.device)
+
+
+def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="cuda"):
+    """A voice's tokens as realtime_inference.py builds its library, as strided [768, m] parts and without a copy: the target
+    utterance `wav` [channels, samples] at `sr` Hz -- resampled to 16 kHz, peak-normalised, first channel, content_encoder(
+    spectrogram(.)), every `every`-th frame (a column-strided view of the encoder's output) -- then the tokens of `lib` (a voice
+    library file, or its tokens [1, 768, M] / [768, M]).  The encoder runs under ops.Fp16Guard, as generate_voice_library.py's."""
+    from .voice_library import VoiceLibrary
+    parts = []
+    if wav is not None:
+        wf = audio_io.resample(wav.to(device), sr, 16000)
+        wf = wf / wf.abs().max()
+        feats = ops.Fp16Guard().run(lambda: content_encoder(spectrogram(wf[:1])))
+        parts.append(feats[0][:, ::every])
+    if lib is not None:
+        if isinstance(lib, (str, bytes)) or hasattr(lib, "__fspath__"):
+            VL = VoiceLibrary().to(device)
+            VL.load_state_dict(torch.load(lib, map_location=device))
+            lib = VL.tokens
+        parts.append(_tokens_2d(lib))
+    if not parts:
+        raise ValueError("a voice needs a target wav and / or a voice library")
+    return parts
+
+
+def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False):
+    """enrol_voice as a generator: the utterance is encoded once, then each next() appends one piece -- `add` for the first, `extend`
+    for the rest -- and yields the voice's row count so far, so that a server can put a tick between the pieces.  If a piece is
+    refused the voice is removed again (when no session holds it yet) and the error propagates."""
+    if pool.capacity is None:
+        raise ValueError("enrol_voice needs a reserved pool: VoicePool(..., capacity=ROWS)")
+    if max_frames is not None and int(max_frames) < 1:
+        raise ValueError(f"max_frames={max_frames!r} must be >= 1")
+    parts = voice_parts(content_encoder, wav, sr, lib, every, pool.device)
+    total = sum(int(t.shape[1]) for t in parts)
+    step = total if max_frames is None else int(max_frames)
+    if compact and pool.largest_hole < min(step, total) <= pool.free_rows:
+        pool.compact()
+    # pieces of at most `step` tokens of the parts laid end to end; a piece that spans two parts is a list of two views
+    pieces, cur, room = [], [], step
+    for t in parts:
+        at, m = 0, int(t.shape[1])
+        while at < m:
+            n = min(room, m - at)
+            cur.append(t[:, at:at + n])
+            at, room = at + n, room - n
+            if room == 0:
+                pieces.append(cur)
+                cur, room = [], step
+    if cur:
+        pieces.append(cur)
+    done = 0
+    try:
+        for i, piece in enumerate(pieces):
+            (pool.add if i == 0 else pool.extend)(name, piece)
+            done += sum(int(t.shape[1]) for t in piece)
+            yield done
+    except ValueError:
+        if done and name in pool.segments:
+            try:
+                pool.remove(name)
+            except ValueError:                                 # a session opened on the part that is there: it stays
+                pass
+        raise
+
+
+def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False):
+    """Enrol a voice into a reserved pool from audio, while sessions run on the pool's other voices: the recipe of voice_parts
+    (multistream_inference.voice_tokens', under ops.Fp16Guard), appended through the strided alive_pool_append -- the encoder's
+    output is never copied or concatenated.  The voice's rows are bitwise those of voice_tokens followed by `add`.
+
+    max_frames: the tokens go in pieces of at most that many, `add` then `extend`s (enrol_steps yields between them).  The content
+    encoder's receptive field spans the whole utterance, so no cut of the AUDIO gives bitwise the frames of one call: the utterance
+    is encoded once and its tokens are appended piece by piece, which is bitwise one call for any max_frames (a row and its norm
+    depend on the row's own token alone).  compact=True: compact the pool first when the first piece fits its free rows but none
+    of its holes.  Returns the voice's row count."""
+    rows = 0
+    for rows in enrol_steps(pool, name, content_encoder, wav, sr, lib, every, max_frames, compact):
+        pass
+    return rows
 
 
 def knn_search_grouped(source, rows, norms, seg_lo, seg_len, k):
@@ -433,6 +779,12 @@ class MultiStreamConverter:
         self.ce, self.pe, self.dec = prepare_networks(content_encoder, f0_estimator, decoder, device)
         self.pool = pool
         self.B, self.k = int(slots), int(k)
+        # a reserved pool (VoicePool(capacity=...)): the slots hold their voices, and the tick follows the pool's layout
+        self._reserved = getattr(pool, "capacity", None) is not None
+        self._label = f"MultiStreamConverter(slots={self.B}) at {id(self):#x}"
+        self._names = [()] * self.B
+        self._seen_layout = pool.layout if self._reserved else None
+        self._seen_mutations = 0
         self.chunk, self.buffersize = int(chunk), int(buffersize)
         self.input_sr, self.output_sr = input_sr, output_sr
         self.begin_of_output, self.end_of_output, self.frames = ring_geometry(chunk, buffersize, input_sr, output_sr)
@@ -515,6 +867,21 @@ class MultiStreamConverter:
             raise ValueError(f"slot {slot}: world_pitch must be a bool, got {world!r}")
         if world and not self.world_pitch:
             raise ValueError(f"slot {slot}: world_pitch=True needs a converter built with MultiStreamConverter(..., world_pitch=True)")
+        self._write_segments(slot, names)
+        if self.S > 1:
+            rows = slice(slot * self.S, (slot + 1) * self.S)
+            self.weight[rows] = torch.tensor(list(weights) + [0.0] * (self.S - len(names)), dtype=torch.float64)
+        self._hold(slot, names)
+        self.alpha[slot] = float(p["alpha"])
+        self.f0_rate[slot] = float(p["f0_rate"])
+        self.pitch[slot] = float(p["pitch"])
+        self.in_post[slot] = db_scale(p["input_gain"])
+        self.out_pre[slot] = db_scale(p["gain"])
+        if self.world_pitch:
+            self._set_world(slot, bool(world), float(p["f0_rate"]))
+
+    def _write_segments(self, slot, names):
+        """the slot's rows of seg_lo / seg_len from where its voices lie in the pool now"""
         segs = [self.pool.segment(n) for n in names]
         if self.S == 1:
             self.seg_lo[slot], self.seg_len[slot] = segs[0]
@@ -523,14 +890,34 @@ class MultiStreamConverter:
             rows = slice(slot * self.S, (slot + 1) * self.S)
             self.seg_lo[rows] = torch.tensor([lo for lo, _ in segs] + [0] * pad, dtype=torch.int32)
             self.seg_len[rows] = torch.tensor([m for _, m in segs] + [0] * pad, dtype=torch.int32)
-            self.weight[rows] = torch.tensor(list(weights) + [0.0] * pad, dtype=torch.float64)
-        self.alpha[slot] = float(p["alpha"])
-        self.f0_rate[slot] = float(p["f0_rate"])
-        self.pitch[slot] = float(p["pitch"])
-        self.in_post[slot] = db_scale(p["input_gain"])
-        self.out_pre[slot] = db_scale(p["gain"])
-        if self.world_pitch:
-            self._set_world(slot, bool(world), float(p["f0_rate"]))
+
+    def _hold(self, slot, names):
+        """the slot now uses `names` (blend components included): on a reserved pool, take a hold on each and release the holds
+        of the voices it used before, so that pool.remove refuses a voice some session still searches"""
+        if self._reserved:
+            for n in names:
+                self.pool.hold(n, self._label)
+            for n in self._names[slot]:
+                self.pool.release(n, self._label)
+        self._names[slot] = tuple(names)
+
+    def _follow_pool(self):
+        """before a tick on a reserved pool: order the tick after the pool's latest operation, whatever stream that ran on, and if
+        some voice moved or grew since the last look (pool.layout) rewrite every open slot's segment rows from its stored voice --
+        device arrays the captured tick reads, so nothing is re-captured"""
+        pool = self.pool
+        if pool.mutations != self._seen_mutations:
+            torch.cuda.current_stream(self.device).wait_event(pool.order)
+            self._seen_mutations = pool.mutations
+        if pool.layout != self._seen_layout:                  # every list row in one write each (closed slots stay inactive)
+            lo, ln = [0] * (self.B * self.S), [0] * (self.B * self.S)
+            for slot in range(self.B):
+                if self.is_open[slot]:
+                    for j, n in enumerate(self._names[slot]):
+                        lo[slot * self.S + j], ln[slot * self.S + j] = pool.segment(n)
+            self.seg_lo.copy_(torch.tensor(lo, dtype=torch.int32))
+            self.seg_len.copy_(torch.tensor(ln, dtype=torch.int32))
+            self._seen_layout = pool.layout
 
     def _set_world(self, slot, on, f0_rate):
         self.world_on[slot] = int(on)
@@ -589,6 +976,7 @@ class MultiStreamConverter:
         self.count[slot] = 0
         self.ring[slot] = 0
         self.seg_len[slot * self.S:(slot + 1) * self.S] = 0
+        self._hold(slot, ())
         self.phi[slot] = 0.0
         if self.world_pitch:
             self._set_world(slot, False, 1.0)
@@ -649,6 +1037,8 @@ class MultiStreamConverter:
         return self
 
     def _run(self):
+        if self._reserved:
+            self._follow_pool()
         if self._graph is not None:
             if self._graph_pool_version != self.pool.version:        # the pool was re-packed: its rows moved
                 self.enable_graph()

@@ -21,6 +21,13 @@ It is built with blend = the most components of any session's "blend" (1 without
 sessions and blend components naming the same voice sources share one voice of the pool.
 WORLD needs rings of about 230 ms or more (-c 960 -b 8 is 480 ms): a shorter ring comes out unvoiced.
 Flags shared with realtime_inference.py keep its spelling: -c, -b, -k, -isr, -osr, --no-graph.
+
+--pool-rows N: a RESERVED pool of N rows (module/multistream.py VoicePool(capacity=N)) instead of one packed before tick 0: each
+voice is enrolled from its sources at the first tick some session needs it (multistream.enrol_voice, while the other sessions
+run) and removed after the last session on it closes, so N need only cover the voices alive at one time (enrol_plan lists the
+enrolments, the removals and the peak).  The pool is compacted when a voice fits its free rows but none of its holes; a voice
+that does not fit ends the run with the pool's `add` error before any audio is written.  The outputs are byte for byte those
+without the flag.
 """
 import argparse
 import json
@@ -36,7 +43,7 @@ from module import audio_io                                     # noqa: E402
 from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
-from module.multistream import MultiStreamConverter, VoicePool, blend_sources   # noqa: E402
+from module.multistream import MultiStreamConverter, VoicePool, blend_sources, enrol_voice   # noqa: E402
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
@@ -58,6 +65,9 @@ def build_parser():
     parser.add_argument('-isr', '--input-sr', default=16000, type=int)
     parser.add_argument('-osr', '--output-sr', default=16000, type=int)
     parser.add_argument('--slots', default=0, type=int, help="session slots of the converter (default: one per session)")
+    parser.add_argument('--pool-rows', default=None, type=int,
+                        help="a reserved voice pool of this many rows: voices are enrolled at the first tick that needs them and "
+                             "removed after their last session (default: every voice is packed before tick 0)")
     parser.add_argument('--no-graph', action='store_true',
                         help="launch the per-tick device pipeline kernel by kernel instead of replaying one captured hipGraph")
     return parser
@@ -112,6 +122,42 @@ def blend_size(sessions):
     return max([len(s["blend"]) for s in sessions if s.get("blend")] or [1])
 
 
+def session_sources(s):
+    """the (target, lib) voice sources a session uses: its own, or its blend's components"""
+    return [(t, lb) for t, lb, _ in s["blend"]] if s.get("blend") else [(s["target"], s["lib"])]
+
+
+def enrol_plan(sessions):
+    """The --pool-rows schedule as pure host logic.  `sessions`: dicts with "start" (its first tick), "ticks" (how many it runs;
+    0: it never opens) and "voices" ({pool name: rows}, blend components included).  A voice is enrolled before the first tick
+    that some session needs it and removed after the last tick of the last session on it (and enrolled again if a later session
+    asks for it after that).  Returns (events, peak): events is the list of (tick, "enrol" | "remove", name) in the order in which
+    they happen -- a tick's enrolments come before its step, its removals after it -- and peak the most rows alive at one time."""
+    first, last = {}, {}
+    live = [s for s in sessions if s["ticks"] > 0]
+    ticks = sorted({s["start"] for s in live} | {s["start"] + s["ticks"] - 1 for s in live})
+    events, rows, users, alive, peak = [], {}, {}, 0, 0
+    for tick in ticks:
+        for s in live:
+            if s["start"] == tick:
+                for name, m in s["voices"].items():
+                    if rows.setdefault(name, m) != m:
+                        raise ValueError(f"voice {name!r} is given {rows[name]} and {m} rows")
+                    if users.get(name, 0) == 0:
+                        events.append((tick, "enrol", name))
+                        alive += m
+                    users[name] = users.get(name, 0) + 1
+        peak = max(peak, alive)
+        for s in live:
+            if s["start"] + s["ticks"] - 1 == tick:
+                for name, m in s["voices"].items():
+                    users[name] -= 1
+                    if users[name] == 0:
+                        events.append((tick, "remove", name))
+                        alive -= m
+    return events, peak
+
+
 def voice_tokens(ce, target, lib, device):
     """a session's library as realtime_inference.py builds it: the target utterance's frames (every 4th) and / or a library file"""
     tgt = torch.zeros(1, 768, 0, device=device)
@@ -133,15 +179,18 @@ def input_pcm(path, input_sr, device):
     return (wf.numpy() * 32767).astype(np.int16)
 
 
-def run(conv, pcms, starts, chunk, params):
+def run(conv, pcms, starts, chunk, params, before=None, after=None):
     """drive `conv` tick by tick: session i occupies slot i (opened with params[i]) from tick starts[i] for len(pcms[i]) // chunk
     ticks; `chunk` is one length for every session or a list of per-session lengths (sessions at their own rates).
+    before(tick) runs ahead of the tick's opens and after(tick) behind its closes (--pool-rows: enrolments and removals).
     Returns the emitted int16 chunks of every session, concatenated."""
     chunks = list(chunk) if isinstance(chunk, (list, tuple)) else [chunk] * len(pcms)
     n_chunks = [len(p) // c for p, c in zip(pcms, chunks)]
     outs = [[] for _ in pcms]
     last = max(s + n for s, n in zip(starts, n_chunks))
     for tick in range(last):
+        if before is not None:
+            before(tick)
         feed = {}
         for i, (s, n) in enumerate(zip(starts, n_chunks)):
             if tick == s and n > 0:
@@ -156,6 +205,8 @@ def run(conv, pcms, starts, chunk, params):
         for i, (s, n) in enumerate(zip(starts, n_chunks)):
             if tick == s + n - 1:
                 conv.close(i)
+        if after is not None:
+            after(tick)
     return [np.concatenate(o) if o else np.zeros(0, np.int16) for o in outs]
 
 
@@ -172,10 +223,10 @@ def main(argv=None):
     CE.load_state_dict(torch.load(args.content_encoder_path, map_location=device))
     Dec.load_state_dict(torch.load(args.decoder_path, map_location=device))
 
-    pool, names = VoicePool(device=device), []
+    pool, names = VoicePool(device=device, capacity=args.pool_rows), []
     for s in sessions:
-        for target, lib in ([(t, lb) for t, lb, _ in s["blend"]] if s.get("blend") else [(s["target"], s["lib"])]):
-            if voice_name(target, lib) not in pool.segments:
+        for target, lib in session_sources(s):
+            if args.pool_rows is None and voice_name(target, lib) not in pool.segments:
                 pool.add(voice_name(target, lib), voice_tokens(CE, target, lib, device))
         names.append(session_voice(s))
     slots = max(args.slots, len(sessions))
@@ -190,7 +241,24 @@ def main(argv=None):
         conv.enable_graph()
     pcms = [input_pcm(s["input"], r, device) for s, r in zip(sessions, in_sr)]
     chunks = [args.chunk * r // args.input_sr for r in in_sr]
-    outs = run(conv, pcms, [s["start"] for s in sessions], chunks, params)
+    before = after = None
+    if args.pool_rows is not None:
+        # the reserved pool: a tick's first sessions on a voice enrol it ahead of their open, its last one's close removes it
+        n_ticks = [len(p) // c for p, c in zip(pcms, chunks)]
+        sources = {voice_name(t, lb): (t, lb) for s in sessions for t, lb in session_sources(s)}
+        events, _ = enrol_plan([dict(start=s["start"], ticks=n, voices={voice_name(t, lb): 1 for t, lb in session_sources(s)})
+                                for s, n in zip(sessions, n_ticks)])
+
+        def before(tick):
+            for name in [n for t, what, n in events if t == tick and what == "enrol"]:
+                target, lib = sources[name]
+                wav, sr = audio_io.load(target) if target is not None else (None, None)
+                enrol_voice(pool, name, CE, wav, sr, lib=lib, compact=True)
+
+        def after(tick):
+            for name in [n for t, what, n in events if t == tick and what == "remove"]:
+                pool.remove(name)
+    outs = run(conv, pcms, [s["start"] for s in sessions], chunks, params, before, after)
     os.makedirs(args.output_dir, exist_ok=True)
     for i, (s, o, r) in enumerate(zip(sessions, outs, out_sr)):
         path = s["output"] or os.path.join(args.output_dir, f"{i}_{os.path.splitext(os.path.basename(s['input']))[0]}.wav")

@@ -263,6 +263,24 @@ int alive_knn_blend_gather_rows(const float* cand_val, const int32_t* cand_idx, 
                                 const double* weight, const double* alpha, const float* rows_f32_full, const float* src,
                                 int N, int T, float* out, void* stream);
 
+/* ---------------------------------------------- reserved voice pool (live enrolment) ----
+ * A table rows_f32[capacity][768] / norms[capacity] that is allocated once and never replaced, so that a captured hipGraph whose
+ * launches hold its two pointers and its row count keeps serving while voices come, grow, move and go.  Both calls run on
+ * `stream`, neither allocates nor synchronises, and both refuse bad arguments (-1, a message, nothing launched).
+ * alive_pool_append: packs M tokens into rows [at, at + M) of the table; feature d of token m is tokens[d * row_stride +
+ *   m * col_stride] (strides in elements, >= 0: a contiguous [768][M] matrix is row_stride = M, col_stride = 1; a column slice or
+ *   an every-4th-frame view of an encoder output goes in as it is).  Rows and norms are bitwise those of alive_library_pack_rows
+ *   on the same tokens: the same four partial sums per row, fmaf order and sqrtf.  Nothing outside [at, at + M) is written;
+ *   at + M > capacity is refused.  Every new norm is checked on the device: report (DEVICE int32[2], reset by the call) receives
+ *   the number of rows whose norm is zero or not finite and the lowest such TABLE row (INT32_MAX: none).
+ * alive_pool_move_rows: moves n rows and their norms from row src to row dst of the table; the ranges may overlap in either
+ *   direction (the bytes are copied, never recomputed).  With shift = |src - dst|, the elements at one residue modulo shift form a
+ *   chain that no other chain reads or writes; one thread walks a chain in the direction in which every element is read before it
+ *   is overwritten.  One launch for the rows (float4 elements) and one for the norms, no scratch. */
+int alive_pool_append(const float* tokens, int64_t row_stride, int64_t col_stride, int64_t M, int Dd, float* rows_f32,
+                      float* norms, int64_t capacity, int64_t at, int32_t* report, void* stream);
+int alive_pool_move_rows(float* rows_f32, float* norms, int64_t capacity, int64_t src, int64_t dst, int64_t n, void* stream);
+
 /* ---------------------------------------------- pool search (many-to-many batch conversion) ----
  * A pool of V voices: fp32 rows_f32[P][768] / norms[P] from alive_library_pack_rows (voice v = rows [seg_lo[v], seg_lo[v] +
  * seg_len[v])), plus one bf16 IMAGE per voice in the layout of alive_library_pack (padded to alive_library_padded_rows rows),

@@ -10,11 +10,18 @@ the same batch per WORLD setting (world_<setting>_tick_p50_ms / _p99_ms): "off" 
 world_pitch=True converter with sessions s < round(f B) on WORLD (0: the masked branch with every row off).  --blend adds the graph
 tick p50 / p99 of voice blending: blend3_single_* a blend=3 converter whose sessions are single voices, blend2_* / blend3_* every
 session blending 2 / 3 voices (session s: voices s, s + 1, s + 2, weights 1, 2, 3) in a converter of that blend; distinct voices
-only.  Profile in a separate run (rocprofv3 --kernel-trace --stats --
+only.  --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
+one more 50 000-row voice added between two ticks, once on a default pool (the add re-packs the pool and the next tick
+re-captures) and once on a reserved pool of 65 x 50 000 rows (VoicePool(capacity=...): alive_pool_append into the table in
+place); per pool the wall time of the add (bracketed by device synchronisation; add_device_ms: events around it), the latency of
+the tick that follows and the p50 / p99 of the 30 steady ticks before it.  On the reserved pool it asserts that the graph was
+captured once, that the row table did not move and that nothing of table size was allocated, and adds the worst compaction: the
+lowest voice is removed and `compact` slides the other 64 down by one voice (compact_wall_ms, tick_after_compact_ms).  Profile in a separate run (rocprofv3 --kernel-trace --stats --
 python tools/bench_multistream.py --quick).  Prints one JSON line per configuration and writes the list to --out.
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--out multistream.json]
+    python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
 """
 import argparse
 import json
@@ -58,6 +65,83 @@ def time_ticks(conv, B, chunk, ticks, warmup, seed):
     return float(np.percentile(ts, 50)), float(np.percentile(ts, 99))
 
 
+def enrol_leg(nets, B=64, chunk=160, bs=16, steady=30, warmup=6):
+    """the cost of one more voice for B running sessions, on a default and on a reserved pool: one record per pool"""
+    def tokens(i):
+        return torch.randn(768, VOICE_ROWS, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1000 + i))
+    pcm = [(synthetic.make_waveform(chunk * 4, 300 + s)[0].numpy() * 12000).astype(np.int16) for s in range(B)]
+
+    def tick(conv, t):
+        feed = {s: pcm[s][(t % 4) * chunk:(t % 4 + 1) * chunk] for s in range(B)}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        conv.step(feed)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    recs = []
+    for kind in ("default", "reserved"):
+        if kind == "reserved":
+            pool = MS.VoicePool(capacity=(B + 1) * VOICE_ROWS)
+            for i in range(B):
+                pool.add(f"v{i}", tokens(i))
+        else:
+            pool = MS.VoicePool({f"v{i}": tokens(i) for i in range(B)})
+        conv = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4)
+        for s in range(B):
+            conv.open(s, f"v{s}", pitch=float(s % 5), f0_rate=0.5)
+        conv.enable_graph()
+        t = 0
+        for _ in range(bs + 1 + warmup):
+            tick(conv, t)
+            t += 1
+        ts = []
+        for _ in range(steady):
+            ts.append(tick(conv, t))
+            t += 1
+        new = tokens(B)
+        table, table_bytes = pool.rows.data_ptr(), pool.rows.numel() * 4
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        t0 = time.perf_counter()
+        a.record()
+        pool.add("new", new)
+        b.record()
+        torch.cuda.synchronize()
+        add_ms = (time.perf_counter() - t0) * 1e3
+        after_ms = tick(conv, t)
+        t += 1
+        grown = torch.cuda.max_memory_allocated() - before
+        later = [tick(conv, t + i) for i in range(5)]
+        rec = {"pool": kind, "B": B, "chunk": chunk, "buffersize": bs, "voice_rows": VOICE_ROWS, "pool_rows": pool.P,
+               "add_wall_ms": round(add_ms, 3), "add_device_ms": round(a.elapsed_time(b), 3), "tick_after_add_ms": round(after_ms, 3),
+               "steady_tick_p50_ms": round(float(np.percentile(ts, 50)), 3), "steady_tick_p99_ms": round(float(np.percentile(ts, 99)), 3),
+               "ticks_after_that_ms": [round(x, 3) for x in later], "captures": conv.captures, "table_moved": pool.rows.data_ptr() != table,
+               "peak_allocation_during_add_and_tick_MB": round(grown / 2 ** 20, 1), "table_MB": round(table_bytes / 2 ** 20, 1)}
+        if kind == "reserved":
+            rec["tick_after_add_within_p99_plus_add"] = after_ms <= rec["steady_tick_p99_ms"] + a.elapsed_time(b)
+            # the worst compaction: session 0 ends, its voice (the lowest) goes, and all 64 others slide down by one voice
+            conv.close(0)
+            pool.remove("v0")
+            conv.open(0, "new", f0_rate=0.5)              # (slot 0 starts again on the new voice: B sessions still feed)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pool.compact()
+            torch.cuda.synchronize()
+            rec["compact_wall_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+            rec["compact_moved_MB"] = round(B * VOICE_ROWS * (768 + 1) * 4 / 2 ** 20, 1)
+            rec["tick_after_compact_ms"] = round(tick(conv, t + 5), 3)
+            assert conv.captures == 1, conv.captures
+            assert not rec["table_moved"] and pool.version == 0
+            assert grown < table_bytes // 8, f"{grown} bytes allocated during the add and the tick after it"
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+        del conv, pool, new
+        torch.cuda.empty_cache()
+    return recs
+
+
 def time_search(conv, B, reps=20):
     """the grouped search alone on the tick's shape: (ms per call, bytes of distinct segments read once)"""
     src = torch.randn(B, 768, conv.frames, device="cuda")
@@ -84,6 +168,8 @@ def main():
     ap.add_argument("--world", default=None, help="comma-separated WORLD settings: off, or the fraction of sessions on WORLD")
     ap.add_argument("--voices", default="shared,distinct", help="voice mixes to run: shared, distinct")
     ap.add_argument("--blend", action="store_true", help="also time voice blending (blend=3 single voices, 2- and 3-voice blends)")
+    ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
+                                                         "default and on a reserved pool")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     batches = [int(b) for b in args.batches.split(",")]
@@ -94,6 +180,12 @@ def main():
     if args.quick:
         batches, configs, mixes = [64], [(160, 16)], ("distinct",)
     nets = (ContentEncoder(seed=2), F0Estimator(seed=2), Decoder(seed=2))
+    if args.enrol:
+        rows = enrol_leg(nets)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(rows, open(args.out, "w"), indent=1)
+        return
     shared = make_pool(1, 1)
     distinct = make_pool(max(batches) + (2 if args.blend else 0), 2)
     rows = []
