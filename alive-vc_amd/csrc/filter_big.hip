@@ -98,11 +98,16 @@ struct Fb256Weights {
 // x 64 columns load each twice -- the second read hits the L1, whose 64 B per clock then bound the k-loop: 505 cycles per k-step
 // against 318, measured), the B fragments are read from LDS by twice as many waves (half of what it delivers), the epilogue's vector
 // work issues from two waves per SIMD.
-template <int C, int RG>
+// UP (C = 64): the store phase applies the ConvTranspose1d(64, 16, 2, 2) behind the block (ups[2]) to the finished tile and writes
+// [16][2 L]; the 64-channel output is never written.  upW [32 rows (co, j)][64], upb [32]: what alive_conv1d takes for that conv; the
+// sums are conv_gemm_kernel's chains term for term (conv.hip: within each 16 k, MFMA step s of lane group q takes k = 4 q + s).
+template <int C, int RG, bool UP = false>
 __global__ __launch_bounds__((Geo<C, RG>::NT), 1) void filter_block256_kernel(const float* __restrict__ U, int L, Fb256Weights wts, const float* __restrict__ film,
                                                                  int film_rows, int Lf, int film_off, float ratio, int t_off, int f_off,
                                                                  int film_ld, const float* __restrict__ skip, float* __restrict__ out,
-                                                                 int tiles, int per_block, int total, unsigned char* __restrict__ ws) {
+                                                                 int tiles, int per_block, int total, unsigned char* __restrict__ ws,
+                                                                 const float* __restrict__ upW, const float* __restrict__ upb) {
+    static_assert(!UP || C == 64, "the folded transposed conv is ups[2]");
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int sm0 = (int)(unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)sm;      // (0: the kernel has no static LDS)
     typedef Geo<C, RG> G;
@@ -403,6 +408,57 @@ __global__ __launch_bounds__((Geo<C, RG>::NT), 1) void filter_block256_kernel(co
             PROF(6);
         }
 
+        if constexpr (UP) {
+            // ---- store phase with ups[2]: a wave holds 32 of the 64 channels, so the tile (h + skip, fp32 [64][BL + 4]) goes through LDS
+            //      once -- over the FiLM tables and both buffers, all dead behind the last conv's barrier (the next tile's contexts live in
+            //      the slots behind them) -- then a thread takes a column: 32 rows x 64 terms, eight 8-byte stores ----
+            constexpr int XS = BL + 4;
+            static_assert(C * XS * 4 <= G::FS_BYTES + 2 * BUFB, "the fp32 tile fits in front of the context slots");
+            if (!warm) {                                    // (block-uniform)
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg)
+#pragma unroll
+                    for (int c = 0; c < CTW; ++c) {
+                        const int col = col0 + 32 * c + n32, t = tbase + col;
+                        const size_t o = ((size_t)n * C + CW * w + 32 * rg + 4 * lh) * L + (t < L ? t : L - 1);
+                        float sk[16];
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) sk[r] = skip != nullptr ? __builtin_nontemporal_load(skip + o + (size_t)(8 * (r >> 2) + (r & 3)) * L) : 0.0f;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            lds_put<float>(sm0 + 4 * ((CW * w + 32 * rg + 4 * lh + 8 * (r >> 2) + (r & 3)) * XS + col), 0,
+                                           skip != nullptr ? h_get(rg, c, r) + sk[r] : h_get(rg, c, r));
+                    }
+                __syncthreads();
+#pragma unroll 1
+                for (int col = tid; col < BL; col += NT) {
+                    const int t = tbase + col;
+                    if (t >= L) break;
+                    float x[C];
+#pragma unroll
+                    for (int ci = 0; ci < C; ++ci) x[ci] = lds_get<float>(sm0 + 4 * col, 4 * ci * XS);
+                    float* o = out + (size_t)n * (C / 4) * 2 * L + 2 * (size_t)t;
+#pragma unroll 1
+                    for (int co = 0; co < C / 4; ++co) {      // (a rolled loop: 128 wave-uniform weights per pass, not 2048 live at once)
+                        f32x2 v;
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const int row = 2 * co + j;
+                            float a = upb[row];
+#pragma unroll
+                            for (int kt = 0; kt < C / 16; ++kt)
+#pragma unroll
+                                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                                    for (int q = 0; q < 4; ++q) a = fmaf(upW[row * C + 16 * kt + 4 * q + s], x[16 * kt + 4 * q + s], a);
+                            v[j] = a;
+                        }
+                        *(f32x2*)(o + (size_t)co * 2 * L) = v;
+                    }
+                }
+            }
+            continue;                                       // (the barrier at the top of the next tile stands between these reads and its writes)
+        }
         // ---- store (+ U-Net skip, decoder.py:191), straight from the residual registers ----
         if (!warm) {
 #pragma unroll
@@ -432,11 +488,12 @@ __global__ __launch_bounds__((Geo<C, RG>::NT), 1) void filter_block256_kernel(co
 #endif
 }
 
-template <int C>
+template <int C, bool UP = false>
 int fb_launch(const char* name, const float* U, int N, int L, const void* const* w16, const float* const* bias, const float* film, int film_rows,
-              int Lf, int film_off, int t0, int f0, int film_ld, const float* skip, float* out, void* ws, int64_t ws_bytes, void* stream) {
+              int Lf, int film_off, int t0, int f0, int film_ld, const float* skip, float* out, void* ws, int64_t ws_bytes, void* stream,
+              const float* upW = nullptr, const float* upb = nullptr) {
     typedef Geo<C, 1> G;                      // (tile, context and table sizes do not depend on RG)
-    ALIVE_CHECK_ARG(U && w16 && bias && film && out, "%s: null pointer", name);
+    ALIVE_CHECK_ARG(U && w16 && bias && film && out && (!UP || (upW && upb)), "%s: null pointer", name);
     ALIVE_CHECK_ARG(N > 0 && L > 2 * CTX && Lf > 0, "%s: bad sizes (L must exceed 32)", name);
     ALIVE_CHECK_ARG(U != out, "%s: in-place not supported (a block's warm-up tile reads columns another block has stored)", name);
     ALIVE_CHECK_ARG(film_ld > 0 && t0 >= 0 && f0 >= 0, "%s: bad frame range", name);
@@ -449,7 +506,7 @@ int fb_launch(const char* name, const float* U, int N, int L, const void* const*
     }
     {
         static LdsOptIn optin;
-        hipError_t e = optin.ensure({(const void*)filter_block256_kernel<C, 2>, (const void*)filter_block256_kernel<C, 1>}, G::LDS_BYTES);
+        hipError_t e = optin.ensure({(const void*)filter_block256_kernel<C, 2, UP>, (const void*)filter_block256_kernel<C, 1, UP>}, G::LDS_BYTES);
         if (e != hipSuccess) {
             alive_set_error("%s: cannot reserve %d B of LDS: %s", name, G::LDS_BYTES, hipGetErrorString(e));
             return ALIVE_ERR_LAUNCH;
@@ -468,11 +525,13 @@ int fb_launch(const char* name, const float* U, int N, int L, const void* const*
     // ALIVE_FB256_WAVES = 4: one wave per SIMD (64 channels x 128 columns each); default: two (32 channels x 128 columns each)
     static const bool two = !(getenv("ALIVE_FB256_WAVES") && atoi(getenv("ALIVE_FB256_WAVES")) == 4);
     if (two)
-        filter_block256_kernel<C, 1><<<blocks, Geo<C, 1>::NT, G::LDS_BYTES, (hipStream_t)stream>>>(U, L, wts, film, film_rows, Lf, film_off, ratio, t0, f0,
-                                                                                                   film_ld, skip, out, tiles, per_block, total, (unsigned char*)ws);
+        filter_block256_kernel<C, 1, UP><<<blocks, Geo<C, 1>::NT, G::LDS_BYTES, (hipStream_t)stream>>>(U, L, wts, film, film_rows, Lf, film_off, ratio, t0,
+                                                                                                       f0, film_ld, skip, out, tiles, per_block, total,
+                                                                                                       (unsigned char*)ws, upW, upb);
     else
-        filter_block256_kernel<C, 2><<<blocks, Geo<C, 2>::NT, G::LDS_BYTES, (hipStream_t)stream>>>(U, L, wts, film, film_rows, Lf, film_off, ratio, t0, f0,
-                                                                                                   film_ld, skip, out, tiles, per_block, total, (unsigned char*)ws);
+        filter_block256_kernel<C, 2, UP><<<blocks, Geo<C, 2>::NT, G::LDS_BYTES, (hipStream_t)stream>>>(U, L, wts, film, film_rows, Lf, film_off, ratio, t0,
+                                                                                                       f0, film_ld, skip, out, tiles, per_block, total,
+                                                                                                       (unsigned char*)ws, upW, upb);
     ALIVE_CHECK_LAUNCH(name);
 #ifdef ALIVE_FB256_PROF
     {
@@ -508,6 +567,16 @@ extern "C" int alive_filter_block64s_fp16(const float* U, int N, int L, const vo
                                           int film_rows, int Lf, int film_off, int t0, int f0, int film_ld, const float* skip, float* out,
                                           void* ws, int64_t ws_bytes, void* stream) {
     return fb_launch<64>("alive_filter_block64s_fp16", U, N, L, w16, bias, film, film_rows, Lf, film_off, t0, f0, film_ld, skip, out, ws, ws_bytes, stream);
+}
+// the same with ups[2] in the store phase: U[N][64][L] -> out[N][16][2 L] = ConvTranspose1d(64, 16, 2, 2)(FilterBlock(U) + skip)
+extern "C" int alive_filter_block64s_fp16_up(const float* U, int N, int L, const void* const* w16, const float* const* bias, const float* film,
+                                             int film_rows, int Lf, int film_off, int t0, int f0, int film_ld, const float* skip, const float* upW,
+                                             const float* upb, float* out, void* ws, int64_t ws_bytes, void* stream) {
+    ALIVE_CHECK_ARG((((uintptr_t)out) & 7) == 0, "alive_filter_block64s_fp16_up: out must be 8-byte aligned");
+    // (below a tile the decoder keeps the launch of its own, which for few columns is alive_conv1d's K-split kernel: other sums)
+    ALIVE_CHECK_ARG(L >= 512, "alive_filter_block64s_fp16_up: a batch form, L must be at least one tile of 512 columns (got %d)", L);
+    return fb_launch<64, true>("alive_filter_block64s_fp16_up", U, N, L, w16, bias, film, film_rows, Lf, film_off, t0, f0, film_ld, skip, out, ws, ws_bytes,
+                               stream, upW, upb);
 }
 
 ALIVE_F16_SAT_GETTER(alive_f16_sat_filter_big)

@@ -33,8 +33,18 @@ extern "C" void alive_debug_set_stamps_small(long long* p) { g_stamps_small = p;
 
 namespace {
 
-constexpr int HALO = 56;
+constexpr int HALO = 56;                // causal reach of the six k5 convs: 4 (1 + 1 + 2 + 2 + 4 + 4)
 constexpr int NCONV = 6;
+// What the store phase emits -- a compile-time choice, so that the plain instantiations keep their registers, LDS and code:
+//   TAIL_NONE  the block's output (+ U-Net skip) [C][L];
+//   TAIL_UP    C = 16: the ConvTranspose1d(16, 8, 2, 2) behind the block (ups[3]) applied to the finished tile, [8][2 L] -- the
+//              16-channel tensor is never written.  The sums are conv_gemm_kernel's chains term for term (conv.hip: the f32 MFMA
+//              16x16x4 is a fmaf chain from the bias in which step s of lane group q takes k = 4 q + s);
+//   TAIL_WAVE  C = 8: source_out Conv1d(8, 1, 7, pad 3) applied to the finished tile, [L] -- source_out_kernel's fmaf chain in
+//              (ci, m) order from b[0], zeros outside [0, L).  The conv is not causal, so a tile recomputes 8 more columns on its left
+//              (HALO 64: h valid on [t0 - 8, t0 + TT)) and emits the samples [t0 - 3, t0 + TT - 3); the tile that holds column L - 1
+//              emits the window's last three as well.
+constexpr int TAIL_NONE = 0, TAIL_UP = 1, TAIL_WAVE = 2;
 constexpr int NFP = 10;                 // FiLM frames a tile may span (1024 columns at 160 per frame = 6.4, + 3 of slack)
 constexpr int NFS = NFP + 1;            // staged frames per channel (i0 <= NFP - 1, i1 = i0 + 1)
 constexpr int PLANE_BATCH = 32768;      // bytes per plane of the batch tiles: BL * ROWB in both configurations
@@ -43,13 +53,14 @@ constexpr int PLANE_BATCH = 32768;      // bytes per plane of the batch tiles: B
 // a signal of a few thousand samples (the streaming step: 1600 / 3200) would be TWO such tiles on two CUs, each walking 8 / 16
 // column tiles per wave and conv -- 50 us of a 0.9-ms step.  There the planes are 8 KB (256 / 512 columns, 2 / 4 column tiles per
 // wave): 8 blocks, a quarter of the chain each.
-template <int C, int PL = PLANE_BATCH>
+template <int C, int PL = PLANE_BATCH, int TAIL = TAIL_NONE>
 struct Cfg {
+    static constexpr int HL = TAIL == TAIL_WAVE ? HALO + 8 : HALO;      // recomputed columns on a tile's left
     static constexpr int PLANE = PL;
     static constexpr int BUF = 2 * PL;                  // hi + lo
     static constexpr int ROWB = 2 * C;                  // bytes per LDS row
     static constexpr int BL = PLANE / ROWB;             // columns per tile incl. halo (batch: 1024 / 2048)
-    static constexpr int TT = BL - HALO;                // output columns per tile
+    static constexpr int TT = BL - HL;                  // output columns per tile
     static constexpr int NT = BL / 128;                 // column tiles of 32 per wave (8 / 16)
     static constexpr int TSTEP = 128 * ROWB;            // a wave's consecutive tiles are four column tiles apart
     static constexpr int G = C / 8;                     // channel groups of 8 (rows 8 g + 4 lh + e) that hold real channels
@@ -68,12 +79,16 @@ __device__ __forceinline__ unsigned pack2s(float a, float b) {
     return __builtin_bit_cast(unsigned, h);
 }
 
-template <int C, bool FIRST, int PL = PLANE_BATCH>
+// tw / tb: weights and bias of the conv a TAIL applies (TAIL_UP: [16 rows (co, j)][16] and [16]; TAIL_WAVE: [8][7] and [1])
+template <int C, bool FIRST, int PL = PLANE_BATCH, int TAIL = TAIL_NONE>
 __global__ __launch_bounds__(256, PL == 16384 ? 2 : 1) void filter_block_small_kernel(const float* __restrict__ U, int L, const float* __restrict__ wpack,
                                                                    const float* __restrict__ film, int film_rows, int Lf, int film_off,
                                                                    float ratio, int t_off, int f_off, int film_ld,
-                                                                   const float* __restrict__ skip, float* __restrict__ out, long long* stamps) {
-    using K = Cfg<C, PL>;
+                                                                   const float* __restrict__ skip, float* __restrict__ out, long long* stamps,
+                                                                   const float* __restrict__ tw, const float* __restrict__ tb) {
+    static_assert(TAIL == TAIL_NONE || (TAIL == TAIL_UP && C == 16) || (TAIL == TAIL_WAVE && C == 8), "TAIL_UP is ups[3], TAIL_WAVE source_out");
+    using K = Cfg<C, PL, TAIL>;
+    constexpr int HALO = K::HL;
     constexpr int PLANE = K::PLANE, BUF = K::BUF;
 #ifdef ALIVE_STAMPS                 // diagnostic build only (tools/ab_build.sh x.so filter_small.hip -DALIVE_STAMPS; tools/stamp_fbs.py)
     long long tsx[12];
@@ -413,6 +428,55 @@ __global__ __launch_bounds__(256, PL == 16384 ? 2 : 1) void filter_block_small_k
         for (int g = 0; g < G; ++g)
 #pragma unroll
             for (int e = 0; e < 4; ++e) Ht[(8 * g + 4 * lh + e) * HP + colw + 128 * i] = h[i][4 * g + e];
+    if constexpr (TAIL == TAIL_UP) {
+        // U8[co][2 t + j] = chain of row (co, j) over x = h + skip of column t; a lane takes a column, a wave's store is one 512-byte run
+        __syncthreads();
+#pragma unroll 1
+        for (int c = tid; c < TT; c += 256) {
+            const int t = t0 + c;
+            if (t >= L) break;
+            float x[C];
+#pragma unroll
+            for (int ci = 0; ci < C; ++ci)
+                x[ci] = Ht[ci * HP + HALO + c] + (skip != nullptr ? skip[((size_t)n * C + ci) * L + t] : 0.0f);
+            float* o = out + (size_t)n * (C / 2) * 2 * L + 2 * (size_t)t;
+#pragma unroll
+            for (int co = 0; co < C / 2; ++co) {
+                f32x2 v;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int row = 2 * co + j;
+                    float a = tb[row];
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) a = fmaf(tw[row * 16 + 4 * q + s], x[4 * q + s], a);
+                    v[j] = a;
+                }
+                *(f32x2*)(o + (size_t)co * 2 * L) = v;
+            }
+        }
+        return;
+    }
+    if constexpr (TAIL == TAIL_WAVE) {
+        __syncthreads();
+        const int lo = t0 - 3 < 0 ? 0 : t0 - 3;
+        const int hi = t0 + TT >= L ? L : t0 + TT - 3;
+#pragma unroll 1
+        for (int t = lo + tid; t < hi; t += 256) {
+            float a = tb[0];
+#pragma unroll
+            for (int ci = 0; ci < C; ++ci)
+#pragma unroll
+                for (int m = 0; m < 7; ++m) {
+                    const int ti = t + m - 3;                          // column ti - tbase of the tile: 58 .. BL + 2 < HP
+                    const float hv = Ht[ci * HP + (ti - tbase)];
+                    a = fmaf(tw[ci * 7 + m], (ti >= 0 && ti < L) ? hv : 0.0f, a);
+                }
+            out[(size_t)n * L + t] = a;
+        }
+        return;
+    }
     // (the skip loads of the whole tile are in flight together; prefetching them under the last conv spills: 64 more registers)
     constexpr int NV = (C * (TT / 4) + 255) / 256;          // vectors of 4 output columns per thread
     f32x4 sk[NV];
@@ -448,13 +512,14 @@ __global__ __launch_bounds__(256, PL == 16384 ? 2 : 1) void filter_block_small_k
 #endif
 }
 
-template <int C, int PL>
+template <int C, int PL, int TAIL = TAIL_NONE>
 int launch_small(const float* U, int N, int L, const float* wpack, const float* film, int film_rows, int Lf, int film_off,
-                 int t0, int f0, int film_ld, const float* skip, float* out, hipStream_t s) {
-    using K = Cfg<C, PL>;
+                 int t0, int f0, int film_ld, const float* skip, float* out, hipStream_t s, const float* tw = nullptr, const float* tb = nullptr) {
+    using K = Cfg<C, PL, TAIL>;
     {
         static LdsOptIn optin;                               // one per instantiation <C, PL>
-        hipError_t e = optin.ensure({(const void*)filter_block_small_kernel<C, false, PL>, (const void*)filter_block_small_kernel<C, true, PL>}, K::LDS);
+        hipError_t e = optin.ensure({(const void*)filter_block_small_kernel<C, false, PL, TAIL>, (const void*)filter_block_small_kernel<C, true, PL, TAIL>},
+                                    K::LDS);
         if (e != hipSuccess) {
             alive_set_error("alive_filter_block_small: cannot reserve %d B of LDS: %s", K::LDS, hipGetErrorString(e));
             return ALIVE_ERR_LAUNCH;
@@ -466,11 +531,11 @@ int launch_small(const float* U, int N, int L, const float* wpack, const float* 
     // the first tile of a window reflects at t = 0 (per-lane fragment addresses); a problem that does not fill the chip runs all its
     // tiles through that form in one launch (filter_mid.hip)
     const bool small = (int64_t)tiles * N <= 256;
-    filter_block_small_kernel<C, true, PL><<<dim3(small ? tiles : 1, N), 256, K::LDS, s>>>(U, L, wpack, film, film_rows, Lf, film_off, ratio, t0,
-                                                                                     f0, film_ld, skip, out, g_stamps_small);
+    filter_block_small_kernel<C, true, PL, TAIL><<<dim3(small ? tiles : 1, N), 256, K::LDS, s>>>(U, L, wpack, film, film_rows, Lf, film_off, ratio,
+                                                                                           t0, f0, film_ld, skip, out, g_stamps_small, tw, tb);
     if (tiles > 1 && !small)
-        filter_block_small_kernel<C, false, PL><<<dim3(tiles - 1, N), 256, K::LDS, s>>>(U, L, wpack, film, film_rows, Lf, film_off, ratio, t0, f0,
-                                                                                  film_ld, skip, out, g_stamps_small);
+        filter_block_small_kernel<C, false, PL, TAIL><<<dim3(tiles - 1, N), 256, K::LDS, s>>>(U, L, wpack, film, film_rows, Lf, film_off, ratio, t0,
+                                                                                        f0, film_ld, skip, out, g_stamps_small, tw, tb);
     ALIVE_CHECK_LAUNCH("alive_filter_block_small");
     return ALIVE_OK;
 }
@@ -513,4 +578,30 @@ extern "C" int alive_filter_block_small_range(const float* U, int N, int C, int 
                             : launch_small<8, PLANE_BATCH>(U, N, L, wpack, film, film_rows, Lf, film_off, t0, f0, film_ld, skip, out, s);
     return tiny ? launch_small<16, 8192>(U, N, L, wpack, film, film_rows, Lf, film_off, t0, f0, film_ld, skip, out, s)
                 : launch_small<16, PLANE_BATCH>(U, N, L, wpack, film, film_rows, Lf, film_off, t0, f0, film_ld, skip, out, s);
+}
+
+// ---- the block with the small conv behind it folded into its store phase (TAIL_UP / TAIL_WAVE): the batch route of the decoder ----
+// Always the 16-KB-plane tiles (two blocks per CU); a column's value does not depend on the tile form.
+extern "C" int alive_filter_block_small_up_range(const float* U, int N, int L, const float* wpack, const float* film, int film_rows, int Lf,
+                                                 int film_off, int t0, int f0, int film_ld, const float* skip, const float* upW,
+                                                 const float* upb, float* out, void* stream) {
+    ALIVE_CHECK_ARG(U && wpack && film && upW && upb && out, "alive_filter_block_small_up: null pointer");
+    ALIVE_CHECK_ARG(N > 0 && L > 16 && Lf > 0, "alive_filter_block_small_up: bad sizes (L must exceed the largest reflect pad, 16)");
+    ALIVE_CHECK_ARG(U != out, "alive_filter_block_small_up: in-place not supported (tiles read a halo of their left neighbour)");
+    ALIVE_CHECK_ARG((L & 3) == 0 && ((((uintptr_t)U) | ((uintptr_t)out) | ((uintptr_t)skip) | ((uintptr_t)wpack)) & 15) == 0,
+                    "alive_filter_block_small_up: L must be a multiple of 4 and U / out / skip / wpack 16-byte aligned");
+    ALIVE_CHECK_ARG(film_ld > 0 && t0 >= 0 && f0 >= 0, "alive_filter_block_small_up: bad frame range");
+    return launch_small<16, 16384, TAIL_UP>(U, N, L, wpack, film, film_rows, Lf, film_off, t0, f0, film_ld, skip, out, (hipStream_t)stream, upW, upb);
+}
+
+extern "C" int alive_filter_block_small_wave_range(const float* U, int N, int L, const float* wpack, const float* film, int film_rows, int Lf,
+                                                   int film_off, int t0, int f0, int film_ld, const float* oW, const float* ob, float* wave,
+                                                   void* stream) {
+    ALIVE_CHECK_ARG(U && wpack && film && oW && ob && wave, "alive_filter_block_small_wave: null pointer");
+    ALIVE_CHECK_ARG(N > 0 && L > 16 && Lf > 0, "alive_filter_block_small_wave: bad sizes (L must exceed the largest reflect pad, 16)");
+    ALIVE_CHECK_ARG(U != wave, "alive_filter_block_small_wave: in-place not supported (tiles read a halo of their left neighbour)");
+    ALIVE_CHECK_ARG((L & 3) == 0 && ((((uintptr_t)U) | ((uintptr_t)wpack)) & 15) == 0,
+                    "alive_filter_block_small_wave: L must be a multiple of 4 and U / wpack 16-byte aligned");
+    ALIVE_CHECK_ARG(film_ld > 0 && t0 >= 0 && f0 >= 0, "alive_filter_block_small_wave: bad frame range");
+    return launch_small<8, 16384, TAIL_WAVE>(U, N, L, wpack, film, film_rows, Lf, film_off, t0, f0, film_ld, nullptr, wave, (hipStream_t)stream, oW, ob);
 }

@@ -156,6 +156,12 @@ bool fb64s_enabled() {          // ALIVE_FB64S=0: the 64-channel block on filter
     static const bool on = !(getenv("ALIVE_FB64S") && atoi(getenv("ALIVE_FB64S")) == 0);
     return on;
 }
+// ALIVE_FINE_FUSE=0: ups[2], ups[3] and source_out as launches of their own behind the 64- / 16- / 8-channel blocks; 1: only ups[2]
+// keeps its launch; default (2): all three in the blocks' store phases.  Same bits every way.
+int fine_fusion_level() {
+    static const int level = getenv("ALIVE_FINE_FUSE") ? atoi(getenv("ALIVE_FINE_FUSE")) : 2;
+    return level;
+}
 bool fb256_enabled() {          // ALIVE_FB256=0: the 256-channel block conv by conv, as in round 5
     static const bool on = !(getenv("ALIVE_FB256") && atoi(getenv("ALIVE_FB256")) == 0);
     return on;
@@ -727,6 +733,11 @@ int decoder_run(const float* const* w, const float* x_in, const float* f0, const
     const float* skips[4] = {b.d2, b.d1, b.d0, nullptr};
     const float* cur = b.m;
     int cin = 256, L = Lf, film_off = 0;
+    // batch path: the 16-channel block's store phase applies ups[3] and the 8-channel block's source_out (filter_small.hip, TAIL_UP /
+    // TAIL_WAVE) -- neither block's own output nor a launch for the two small convs exists then.  The streaming path launches what it did.
+    // With fused64s the 64-channel block applies ups[2] the same way (filter_big.hip, UP).
+    const bool fine = b.Pa != nullptr && fine_fusion_level() >= 1, fine64 = b.Pa != nullptr && fine_fusion_level() >= 2;
+    bool folded = false;            // the transposed conv of this scale ran in the previous block's store phase: its output is `cur`
     for (int s = 0; s < 4; ++s) {
         const int C = F_CH[s], r = F_UP[s];
         // (a) in decoder precision mode 1, batch path: the 256-channel block in one kernel (filter_big.hip), U -> Hh like the finer scales.
@@ -734,7 +745,7 @@ int decoder_run(const float* const* w, const float* x_in, const float* f0, const
         const bool fused256 = F_MODE[s] == 0 && (decoder_bf16_mask() & 1) != 0 && b.Pa != nullptr && fb256_enabled() && L * r >= 128;
         // (e) the same kernel for the 64-channel block (tiles of 512 columns); its input conv goes into the transposed conv too
         const bool fused64s = F_MODE[s] == 1 && (decoder_bf16_mask() & 16) != 0 && b.Pa != nullptr && fb64s_enabled() && L * r >= 512;
-        {   // ConvTranspose1d(cin, C, r, r): rows = (co, j).  Unfused scale: the weights are ups[s] x input_conv (module/_pack.py), the
+        if (!folded) {   // ConvTranspose1d(cin, C, r, r): rows = (co, j).  Unfused scale: the weights are ups[s] x input_conv (module/_pack.py), the
             // output is the block's residual stream itself
             AliveConv d = conv_desc(fused64s ? upWc : upW[s], fused64s ? upbc : upb[s], cur, N, cin, L, C * r, 1, 1, 1, 0, 0, L,
                                     F_MODE[s] == 0 && !fused256 ? b.Hh : b.U);
@@ -743,11 +754,26 @@ int decoder_run(const float* const* w, const float* x_in, const float* f0, const
             RUN(alive_conv1d(&d, stream));
         }
         L *= r;
+        // a block reads U and writes Hh; behind a folded transposed conv its input is where the previous block wrote, and it writes the other
+        const float* blk_in = folded ? cur : b.U;
+        float* blk_out = blk_in == b.U ? b.Hh : b.U;
+        folded = false;
         if (F_MODE[s] != 0) {   // whole FilterBlock (+ skip) in one kernel: U -> Hh
             if (F_MODE[s] == 2) {
                 const float* wpack = t.next();
-                RUN(alive_filter_block_small_range(b.U, N, C, L, wpack, b.film, FILM_ROWS, Lw_frames, film_off, f_begin * (L / Lf), f_begin, Lf,
-                                                   skips[s], b.Hh, stream));
+                if (fine && s == 3) {
+                    const float* oW = t.next(); const float* ob = t.next();
+                    return alive_filter_block_small_wave_range(blk_in, N, L, wpack, b.film, FILM_ROWS, Lw_frames, film_off, f_begin * (L / Lf), f_begin,
+                                                               Lf, oW, ob, wave, stream);
+                }
+                if (fine && s == 2) {
+                    RUN(alive_filter_block_small_up_range(blk_in, N, L, wpack, b.film, FILM_ROWS, Lw_frames, film_off, f_begin * (L / Lf), f_begin, Lf,
+                                                          skips[s], upW[3], upb[3], blk_out, stream));
+                    folded = true;
+                } else {
+                    RUN(alive_filter_block_small_range(blk_in, N, C, L, wpack, b.film, FILM_ROWS, Lw_frames, film_off, f_begin * (L / Lf), f_begin, Lf,
+                                                       skips[s], blk_out, stream));
+                }
             } else {
                 const float* w16 = t.next(); const float* bias = t.next();
                 const void* w6[6]; const float* b6[6];
@@ -756,7 +782,11 @@ int decoder_run(const float* const* w, const float* x_in, const float* f0, const
                     b6[q] = t.next();
                 }
                 // (e) decoder precision mode 1: the block's six k5 convs on one fp16 plane
-                if (fused64s)
+                if (fused64s && fine64) {
+                    RUN(alive_filter_block64s_fp16_up(b.U, N, L, w6, b6, b.film, FILM_ROWS, Lw_frames, film_off, f_begin * (L / Lf), f_begin, Lf, skips[s],
+                                                      upW[2], upb[2], b.Hh, b.Zz, (int64_t)N * 64 * (Lw / 4) * 4, stream));
+                    folded = true;
+                } else if (fused64s)
                     RUN(alive_filter_block64s_fp16(b.U, N, L, w6, b6, b.film, FILM_ROWS, Lw_frames, film_off, f_begin * (L / Lf), f_begin, Lf, skips[s],
                                                    b.Hh, b.Zz, (int64_t)N * 64 * (Lw / 4) * 4, stream));
                 else if ((decoder_bf16_mask() & 16) && b.Pa != nullptr)          // (batch path only, like the other groups)
@@ -767,7 +797,7 @@ int decoder_run(const float* const* w, const float* x_in, const float* f0, const
                                                    skips[s], b.Hh, stream));
             }
             film_off += 6 * 2 * C;
-            cur = b.Hh;
+            cur = blk_out;
             cin = C;
             continue;
         }
@@ -833,7 +863,7 @@ int decoder_run(const float* const* w, const float* x_in, const float* f0, const
         cin = C;
     }
     const float* oW = t.next(); const float* ob = t.next();
-    return alive_filter_source_out(b.Hh, N, Lw, oW, ob, wave, stream);
+    return alive_filter_source_out(cur, N, Lw, oW, ob, wave, stream);
 }
 }  // namespace
 

@@ -103,6 +103,8 @@ PROTOTYPES = {
     "alive_filter_block_small_weights": (_I, [_I]),
     "alive_filter_block_small": (_I, [_VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
     "alive_filter_block_small_range": (_I, [_VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
+    "alive_filter_block_small_up_range": (_I, [_VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "alive_filter_block_small_wave_range": (_I, [_VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "alive_filter_block64_weights": (_I64, []),
     "alive_filter_block64": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
     "alive_filter_block64_range": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
@@ -111,6 +113,7 @@ PROTOTYPES = {
     "alive_filter_block256_fp16": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _I64, _VP]),
     "alive_filter_block64s_workspace_bytes": (_I64, [_I, _I]),
     "alive_filter_block64s_fp16": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _I64, _VP]),
+    "alive_filter_block64s_fp16_up": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "alive_filter_source_in": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_filter_source_out": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP]),
     "alive_dwconv_norm": (_I, [_VP, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _F, _VP, _VP]),

@@ -227,6 +227,54 @@ def filter_block_small(x, sd, prefix, film, film_off, skip=None):
     return out
 
 
+def filter_block_small_range(x, sd, prefix, film, film_off, skip=None, t0=0, f0=0, frames=None):
+    """filter_block_small on a frame range: x holds the samples from t0 on, film the frames from f0 on of a window of `frames` frames"""
+    from ._pack import pack_filter_small
+    x, film, skip = _f(x), _f(film), _f(skip)
+    n, c, l = x.shape
+    w = pack_filter_small(sd, prefix).to(x.device)
+    out = torch.empty_like(x)
+    nat.check(nat.lib().alive_filter_block_small_range(nat.ptr(x), n, c, l, nat.ptr(w), nat.ptr(film), film.shape[1],
+                                                       film.shape[2] if frames is None else frames, film_off, t0, f0, film.shape[2],
+                                                       nat.ptr(skip), nat.ptr(out), nat.stream()), "alive_filter_block_small_range")
+    return out
+
+
+def filter_block_small_up(x, sd, prefix, film, film_off, up_w, up_b, skip=None, t0=0, f0=0, frames=None):
+    """the 16-channel FilterBlock (+ skip) with ConvTranspose1d(16, 8, 2, 2) in its store phase: x[N,16,L] -> [N,8,2L];
+    up_w [16, 8, 2], up_b [8] in the reference layout"""
+    from ._pack import pack_filter_small
+    x, film, skip = _f(x), _f(film), _f(skip)
+    n, c, l = x.shape
+    assert c == 16
+    w = pack_filter_small(sd, prefix).to(x.device)
+    W, b = pack_convT(up_w, up_b)
+    W, b = W.to(x.device), b.to(x.device)
+    assert tuple(W.shape) == (16, 16) and b.numel() == 16
+    out = torch.empty(n, 8, 2 * l, device=x.device)
+    nat.check(nat.lib().alive_filter_block_small_up_range(nat.ptr(x), n, l, nat.ptr(w), nat.ptr(film), film.shape[1],
+                                                          film.shape[2] if frames is None else frames, film_off, t0, f0, film.shape[2],
+                                                          nat.ptr(skip), nat.ptr(W), nat.ptr(b), nat.ptr(out), nat.stream()),
+              "alive_filter_block_small_up_range")
+    return out
+
+
+def filter_block_small_wave(x, sd, prefix, film, film_off, o_w, o_b, t0=0, f0=0, frames=None):
+    """the 8-channel FilterBlock with source_out Conv1d(8, 1, 7) in its store phase: x[N,8,L] -> [N,1,L]"""
+    from ._pack import pack_filter_small
+    x, film = _f(x), _f(film)
+    n, c, l = x.shape
+    assert c == 8
+    w = pack_filter_small(sd, prefix).to(x.device)
+    ow, ob = _f(o_w).reshape(-1).to(x.device), _f(o_b).reshape(-1).to(x.device)
+    out = torch.empty(n, 1, l, device=x.device)
+    nat.check(nat.lib().alive_filter_block_small_wave_range(nat.ptr(x), n, l, nat.ptr(w), nat.ptr(film), film.shape[1],
+                                                            film.shape[2] if frames is None else frames, film_off, t0, f0, film.shape[2],
+                                                            nat.ptr(ow), nat.ptr(ob), nat.ptr(out), nat.stream()),
+              "alive_filter_block_small_wave_range")
+    return out
+
+
 def filter_block64(x, sd, prefix, film, film_off, skip=None, plain=False):
     """fused FilterBlock for C = 64 (split-bf16 MFMA): x[N,64,L], reference-layout weights sd[prefix + ...].
     plain: the six k5 convs on one fp16 plane per operand (alive_filter_block64_range_fp16; decoder precision mode 1)."""
@@ -247,11 +295,12 @@ def filter_block64(x, sd, prefix, film, film_off, skip=None, plain=False):
     return out
 
 
-def filter_block256(x, sd, prefix, film, film_off, skip=None, t0=0, f0=0, frames=None):
+def filter_block256(x, sd, prefix, film, film_off, skip=None, t0=0, f0=0, frames=None, up=None):
     """fused FilterBlock for C = 256 (or 64: alive_filter_block64s_fp16) on plain fp16 operands WITHOUT its 1x1 input conv (the decoder
     composes that into the transposed conv that produces x; csrc/filter_big.hip, decoder precision mode 1): x[N,C,L] = the block's
     residual stream, reference-layout weights sd[prefix + '.blocks.j.c1 / c2 ...'].  t0 / f0 / frames: the window's place in a longer
-    signal (alive_filter_block64_range)."""
+    signal (alive_filter_block64_range).  up = (weight [64, 16, 2], bias [16]), C = 64: ConvTranspose1d(64, 16, 2, 2) in the block's store
+    phase (alive_filter_block64s_fp16_up) -> [N,16,2L]."""
     import ctypes
     from ._pack import pack_conv_split_h
     x, film, skip = _f(x), _f(film), _f(skip)
@@ -269,6 +318,17 @@ def filter_block256(x, sd, prefix, film, film_off, skip=None, t0=0, f0=0, frames
             bs.append(nat.ptr(b))
     nbytes = getattr(nat.lib(), query)(n, l)
     ws_buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    if up is not None:
+        assert c == 64
+        W, b = pack_convT(up[0], up[1])
+        W, b = W.to(x.device), b.to(x.device)
+        assert tuple(W.shape) == (32, 64) and b.numel() == 32
+        out = torch.empty(n, 16, 2 * l, device=x.device)
+        nat.check(nat.lib().alive_filter_block64s_fp16_up(nat.ptr(x), n, l, (ctypes.c_void_p * 6)(*ws), (ctypes.c_void_p * 6)(*bs), nat.ptr(film),
+                                                          film.shape[1], film.shape[2] if frames is None else frames, film_off, t0, f0,
+                                                          film.shape[2], nat.ptr(skip), nat.ptr(W), nat.ptr(b), nat.ptr(out), nat.ptr(ws_buf), nbytes,
+                                                          nat.stream()), "alive_filter_block64s_fp16_up")
+        return out
     out = torch.empty_like(x)
     nat.check(getattr(nat.lib(), entry)(nat.ptr(x), n, l, (ctypes.c_void_p * 6)(*ws), (ctypes.c_void_p * 6)(*bs), nat.ptr(film),
                                                    film.shape[1], film.shape[2] if frames is None else frames, film_off, t0, f0,

@@ -468,6 +468,21 @@ int alive_filter_block_small(const float* U, int N, int C, int L, const float* w
 int alive_filter_block_small_range(const float* U, int N, int C, int L, const float* wpack, const float* film,
                                    int film_rows, int Lf, int film_off, int t0, int f0, int film_ld, const float* skip,
                                    float* out, void* stream);
+/* The two finest blocks with the small conv that follows them folded into the store phase (the decoder's batch route; the tensor in
+ * between is never written, the results are those of the two launches bit for bit):
+ *   alive_filter_block_small_up_range  : C = 16, then ConvTranspose1d(16, 8, 2, 2) (ups[3]) on block + skip:
+ *        U[N][16][L] -> out[N][8][2 L];  upW[16 rows (co, j)][16], upb[16] as module/_pack.py::pack_convT packs them for alive_conv1d;
+ *   alive_filter_block_small_wave_range: C = 8 (no skip), then source_out Conv1d(8, 1, 7, pad 3, zeros outside [0, L)):
+ *        U[N][8][L] -> wave[N][L];  oW[8][7], ob[1] as alive_filter_source_out takes them.
+ * Other arguments as alive_filter_block_small_range (whole window: t0 = f0 = 0, film_ld = Lf); L > 16 and a multiple of 4.
+ * alive_decoder_forward[_range] take this route on the batch path unless the environment has ALIVE_FINE_FUSE=0 (read once), which
+ * puts the launches of the small convs back -- a switch for A/B runs and the equality tests, it selects nothing else. */
+int alive_filter_block_small_up_range(const float* U, int N, int L, const float* wpack, const float* film, int film_rows, int Lf,
+                                      int film_off, int t0, int f0, int film_ld, const float* skip, const float* upW, const float* upb,
+                                      float* out, void* stream);
+int alive_filter_block_small_wave_range(const float* U, int N, int L, const float* wpack, const float* film, int film_rows, int Lf,
+                                        int film_off, int t0, int f0, int film_ld, const float* oW, const float* ob, float* wave,
+                                        void* stream);
 
 /* FilterBlock.forward (decoder.py:137-150) for C = 64 fused into one kernel on the split-bf16 MFMA (filter_mid.hip):
  * activations stay in LDS as two bf16 planes through the input conv and the six modulated k5 convs.
@@ -508,6 +523,13 @@ int64_t alive_filter_block64s_workspace_bytes(int N, int L);
 int alive_filter_block64s_fp16(const float* U, int N, int L, const void* const* w16, const float* const* bias, const float* film,
                                int film_rows, int Lf, int film_off, int t0, int f0, int film_ld, const float* skip, float* out,
                                void* ws, int64_t ws_bytes, void* stream);
+/* the same with the ConvTranspose1d(64, 16, 2, 2) behind the block (ups[2]) in its store phase: U[N][64][L] -> out[N][16][2 L], bit for
+ * bit alive_conv1d(up = 2) on the block's output, which is never written.  upW[32 rows (co, j)][64], upb[32] as
+ * module/_pack.py::pack_convT packs them.  Part of the decoder's batch route like the two entry points in filter_small.hip above
+ * (ALIVE_FINE_FUSE=1 keeps those two and puts this conv back as a launch of its own). */
+int alive_filter_block64s_fp16_up(const float* U, int N, int L, const void* const* w16, const float* const* bias, const float* film,
+                                  int film_rows, int Lf, int film_off, int t0, int f0, int film_ld, const float* skip, const float* upW,
+                                  const float* upb, float* out, void* ws, int64_t ws_bytes, void* stream);
 
 /* The waveform-rate edges of Filter.forward (decoder.py:164,182,186-188,194) as streaming kernels:
  *   alive_filter_source_in : downs[0](source_in(src)):  src[N][Lw] -> d0[N][16][Lw/2]
