@@ -9,6 +9,9 @@ The jobs file is a JSON list; each entry:
    "gain": 1, "normalize": false,                           optional, inference.py's -g / -norm
    "world_pitch": false,                                    optional, a JSON bool: inference.py's -wpe (WORLD's f0 of each
                                                             window; pitch, intonation and f0_rate apply to it)
+   "k": 4,                                                  optional, an integer in 1..8: this job's k (default: -k).  Jobs at
+                                                            different k still share the one batched run (the pool search groups
+                                                            its rows by voice and k); a jobs file without "k" runs as before
    "blend": [{"target": "a.wav", "weight": 2},              instead of "target" / "lib": a weighted mix of 1 to 4 voices, each
              {"lib": "b.pt", "weight": 1}],                 component a voice source as above (module/multistream.py blend_spec)
    "output": "a_out.wav"}                                   optional: default <outdir>/<index>_<input name>.wav
@@ -28,10 +31,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from module import audio_io                                     # noqa: E402
-from module.multistream import MAX_K, blend_sources              # noqa: E402
+from module.multistream import MAX_K, blend_sources, check_k     # noqa: E402
 
 JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "world_pitch", "output",
-            "blend")
+            "blend", "k")
 
 
 def build_parser():
@@ -74,10 +77,11 @@ def load_jobs(path, k=4):
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
         if not isinstance(j.get("world_pitch", False), bool):
             raise ValueError(f"job {i}: \"world_pitch\" must be true or false, got {j['world_pitch']!r}")
+        job_k = check_k(j["k"], f"job {i}: \"k\"") if "k" in j else k
         e = dict(input=rel(j["input"]), target=rel(j.get("target")), lib=rel(j.get("lib")), output=rel(j.get("output")),
                  pitch=float(j.get("pitch", 0.0)), intonation=float(j.get("intonation", 1.0)), f0_rate=float(j.get("f0_rate", 1.0)),
                  alpha=float(j.get("alpha", 0.0)), gain=float(j.get("gain", 1.0)), normalize=bool(j.get("normalize", False)),
-                 world_pitch=j.get("world_pitch", False), blend=blend)
+                 world_pitch=j.get("world_pitch", False), blend=blend, k=job_k)
         for key in ("input", "target", "lib"):
             if e[key] is not None and not os.path.isfile(e[key]):
                 raise ValueError(f"job {i}: {key} {e[key]!r} does not exist")
@@ -113,6 +117,18 @@ def check_voice_sizes(sizes, k):
     for key, m in sizes.items():
         if m < k:
             raise ValueError(f"voice {key}: {m} vectors, fewer than k={k}")
+
+
+def check_job_voice_sizes(jobs, sizes):
+    """every voice a job uses (blend components included) against the job's own k"""
+    for job in jobs:
+        check_voice_sizes({key: sizes[key] for key in voice_keys(job)}, job["k"])
+
+
+def jobs_k(jobs, k):
+    """convert_many's k: the scalar -k when every job runs at it (the uniform path, as before), else the per-job list"""
+    ks = [job["k"] for job in jobs]
+    return k if all(v == k for v in ks) else ks
 
 
 def main(argv=None):
@@ -152,7 +168,7 @@ def main(argv=None):
             VL.load_state_dict(torch.load(lib, map_location=device))
             tgt = torch.cat([tgt, VL.tokens], dim=2)
         voices[key] = tgt
-    check_voice_sizes({k_: int(t.shape[2]) for k_, t in voices.items()}, args.k)
+    check_job_voice_sizes(jobs, {k_: int(t.shape[2]) for k_, t in voices.items()})
     names = {key: f"voice{i}" for i, key in enumerate(voices)}
     pool = VoicePool({names[key]: t for key, t in voices.items()}, device=device)
     print(f"{len(jobs)} jobs over {len(voices)} voices ({pool.P} vectors)")
@@ -167,7 +183,7 @@ def main(argv=None):
     conv = Converter(CE, PE, Dec, device)
     outs = conv.convert_many(utts, pool, [job_voice(j, names) for j in jobs], pitch_shift=[j["pitch"] for j in jobs],
                              intonation=[j["intonation"] for j in jobs], f0_rate=[j["f0_rate"] for j in jobs],
-                             alpha=[j["alpha"] for j in jobs], world_pitch=[j["world_pitch"] for j in jobs], chunk=args.chunk, k=args.k, window_batch=args.window_batch,
+                             alpha=[j["alpha"] for j in jobs], world_pitch=[j["world_pitch"] for j in jobs], chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)
     for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
         out = audio_io.resample(out, 16000, sr, post_gain_db=job["gain"]).cpu()

@@ -1650,14 +1650,16 @@ __device__ __forceinline__ int wave_argbest(float v, int idx) {
 // Results are bit for bit what they were (same products, same summation trees, same tie-breaks).
 // POOL (alive_knn_search_pool): candidates are indexed by SLOT of the pool plan, frame_list = the plan's slot -> frame map (-1: a
 // padding slot, skipped), det_lib = the per-voice bounds, taken for the slot's voice; a frame that fails the certificate is listed
-// in its group's range of the fallback list (PoolRescore) instead of flag_list, which is not written.
+// in its group's range of the fallback list (PoolRescore) instead of flag_list, which is not written.  A group has one k
+// (grp[g][PG_K]: the call's, or its rows' own k of alive_knn_search_pool_k): the k-th stage score, the top-k and the certificate's
+// k-th exact cosine take the group's k, and the lists are written at the stride of the k argument (the call's largest k).
 struct PoolRescore {
     const int* slot_grp;   // [slot] group of the plan
     const int* grp;        // [group][PG_FIELDS]
     int* gfail;            // [group] frames of the group that failed the certificate
     int* fb;               // [slot] fallback list: group g's failing slots at grp[g][PG_SLOT0] + 0 .. gfail[g] - 1
 };
-enum { PG_VOICE = 0, PG_MSTART, PG_SIZE, PG_BLK0, PG_NBLK, PG_CHUNKS, PG_NSLAB, PG_BASE, PG_FBASE, PG_FIELDS };
+enum { PG_VOICE = 0, PG_MSTART, PG_SIZE, PG_BLK0, PG_NBLK, PG_CHUNKS, PG_NSLAB, PG_BASE, PG_FBASE, PG_K, PG_FIELDS };
 
 template <int PER, bool POOL = false>
 __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_idx,
@@ -1687,8 +1689,10 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
     }
     if (slot >= Tt || (frame_list != nullptr && slot >= gc)) return;
     const int64_t ft = frame_list != nullptr ? frame_list[slot] : slot;     // frame: source row and output row
+    const int ko = k;                      // entries per frame of out_val / out_idx
     if constexpr (POOL) {
         if (ft < 0) return;                                                  // padding slot of the pool plan
+        k = pool.grp[pool.slot_grp[slot] * PG_FIELDS + PG_K];                // wave-uniform
     }
     const int R = P * kp;                  // kp candidates per frame and split: KP (bf16 scoring) or KP8 (fp8 scoring)
     const float* cv = cand_val + (size_t)slot * R;
@@ -1860,7 +1864,7 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
         // in all but a z-sigma tail of the statistical mode; joining them makes that tail harmless), without duplicates
         unsigned long long free_mask = ~__builtin_amdgcn_ballot_w64(my_idx >= 0);
         for (int j = 0; j < k; ++j) {
-            const int g = out_idx[(size_t)ft * k + j];
+            const int g = out_idx[(size_t)ft * ko + j];
             if (g < 0) continue;                                       // wave-uniform
             const int el = (int)(g - idx_base);
             if (__builtin_amdgcn_ballot_w64(my_idx == el) != 0) continue;
@@ -1953,8 +1957,8 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
         const int win = winm != 0 ? (int)__builtin_ctzll(winm) : 0;
         const int wi = (wi_u == 0x7fffffffu || wi_u == 0xffffffffu) ? -1 : (int)wi_u;
         if (lane == 0) {
-            out_val[(size_t)ft * k + j] = wv_;
-            out_idx[(size_t)ft * k + j] = (wi < 0 || !(wv_ > -INFINITY)) ? -1 : (int)(idx_base + wi);
+            out_val[(size_t)ft * ko + j] = wv_;
+            out_idx[(size_t)ft * ko + j] = (wi < 0 || !(wv_ > -INFINITY)) ? -1 : (int)(idx_base + wi);
         }
         if (lane == win) my_score = -INFINITY;
         vk = wv_;
@@ -2091,11 +2095,11 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void knn_scan_kernel(const float* 
 // heads of all its lists in every round and the block reduced through an LDS tree: 26 us of dependent L2 round trips for k = 4.)
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 // The body is shared with the grouped search (knn_grouped_merge_kernel): list w of the frame at part[w * stride + t * k + e],
-// the result at out[t_out * k + j].
+// the result at out[t_out * ko + j] (ko >= k: the per-row-k searches write k entries of a frame's ko).
 template <bool K4>
 __device__ __forceinline__ void scan_merge_frame(const float* __restrict__ part_val, const int* __restrict__ part_idx, int64_t stride,
                                                  int nw, int t, int k, int64_t idx_base, float* __restrict__ out_val,
-                                                 int* __restrict__ out_idx, int64_t t_out) {
+                                                 int* __restrict__ out_idx, int64_t t_out, int ko) {
     constexpr int NL = SCAN_MAX_LISTS / 256;
     __shared__ float sv[2][4];
     __shared__ int si[2][4], sw[2][4];
@@ -2163,8 +2167,8 @@ __device__ __forceinline__ void scan_merge_frame(const float* __restrict__ part_
             if (ov > gv || (ov == gv && (unsigned)oi < (unsigned)gi)) { gv = ov; gi = oi; gt = sw[par][q]; }
         }
         if (tid == 0) {
-            out_val[(size_t)t_out * k + j] = gv;
-            out_idx[(size_t)t_out * k + j] = (gi == 0x7fffffff || !(gv > -INFINITY)) ? -1 : (int)(idx_base + gi);
+            out_val[(size_t)t_out * ko + j] = gv;
+            out_idx[(size_t)t_out * ko + j] = (gi == 0x7fffffff || !(gv > -INFINITY)) ? -1 : (int)(idx_base + gi);
         }
         if (gt == tid && bl >= 0) {
 #pragma unroll
@@ -2179,7 +2183,7 @@ template <bool K4>
 __global__ __launch_bounds__(256) void knn_scan_merge_kernel(const float* __restrict__ part_val, const int* __restrict__ part_idx,
                                                              int nw, int k, int64_t idx_base, float* __restrict__ out_val,
                                                              int* __restrict__ out_idx) {
-    scan_merge_frame<K4>(part_val, part_idx, 64, nw, blockIdx.x, k, idx_base, out_val, out_idx, blockIdx.x);
+    scan_merge_frame<K4>(part_val, part_idx, 64, nw, blockIdx.x, k, idx_base, out_val, out_idx, blockIdx.x, k);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -2189,7 +2193,9 @@ __global__ __launch_bounds__(256) void knn_scan_merge_kernel(const float* __rest
 // one pool, and device arrays seg_lo[N] / seg_len[N] name the segment row n searches (seg_len 0: an inactive slot).  The
 // table may change between replays of a captured graph, so nothing on the host depends on it: every grid is sized from
 // N, T and k alone, and a one-block prologue turns the table into a work list in the workspace --
-//   groups  the rows that search the same segment (one pass over a segment serves all of them);
+//   groups  the rows that search the same segment at the same k (one pass over a segment serves all of them; k is the call's, or
+//           -- alive_knn_search_grouped_k -- row n's own k_row[n] <= k_max: every group is uniform in k, so the scan and the merge
+//           run with the group's k whatever the other rows use, and two rows on one segment at different k take two passes);
 //   chunks  a group's frames (its rows x T) cut into runs of GR_F = 64 / k frames: one register pair per lane, lane = frame * k +
 //           slot, exactly the lists of knn_scan_kernel;
 //   slabs   a segment cut into nslab row ranges, nslab chosen so that all items together fill about GR_ITEMS waves.
@@ -2202,7 +2208,7 @@ constexpr int GR_MAX_ROWS = 1024;       // batch rows one call takes (the prolog
 constexpr int GR_ITEMS = SCAN_MAX_LISTS; // target work items per call (= waves launched), and the most lists a frame merges
 constexpr int GR_MIN_SLAB = 4;          // rows per slab at least
 constexpr int GR_BLOCKS = GR_ITEMS / SCAN_WAVES;
-enum { GR_G = 0, GR_LO, GR_LEN, GR_SIZE, GR_MSTART, GR_CHUNKS, GR_NSLAB, GR_BASE, GR_FIELDS };
+enum { GR_G = 0, GR_LO, GR_LEN, GR_SIZE, GR_MSTART, GR_CHUNKS, GR_NSLAB, GR_BASE, GR_K, GR_FIELDS };
 
 struct GroupedWs {
     float* s_f32;
@@ -2217,6 +2223,7 @@ struct GroupedWs {
     size_t bytes;
 };
 
+// (k: the largest k of the call.  A group of `size` rows at k' <= k has ceil(size T / (64 / k')) <= size ceil(T / (64 / k)) chunks.)
 static int64_t grouped_items_cap(int N, int T, int k) {
     const int64_t chunks = (int64_t)N * ((T + 64 / k - 1) / (64 / k));
     return chunks > GR_ITEMS ? chunks : GR_ITEMS;
@@ -2246,28 +2253,30 @@ static GroupedWs grouped_ws_layout(void* base, int N, int T, int k) {
 }
 
 // one block: segment table -> groups, members, items.  The rows are few (<= 1024) and the walk is serial where it needs an order.
-__global__ __launch_bounds__(256) void knn_grouped_plan_kernel(const int* __restrict__ seg_lo, const int* __restrict__ seg_len, int N, int T,
-                                                               int64_t P, int k, GroupedWs w) {
-    __shared__ int s_lo[GR_MAX_ROWS], s_len[GR_MAX_ROWS], s_lead[GR_MAX_ROWS];
+// k_row (may be null: every row at k): row n's own k, 1 <= k_row[n] <= k; a row outside that range is inactive.
+__global__ __launch_bounds__(256) void knn_grouped_plan_kernel(const int* __restrict__ seg_lo, const int* __restrict__ seg_len,
+                                                               const int* __restrict__ k_row, int N, int T, int64_t P, int k, GroupedWs w) {
+    __shared__ int s_lo[GR_MAX_ROWS], s_len[GR_MAX_ROWS], s_lead[GR_MAX_ROWS], s_k[GR_MAX_ROWS];
     const int tid = threadIdx.x;
     for (int n = tid; n < N; n += 256) {
         const int lo = seg_lo[n], len = seg_len[n];
-        // a segment outside the pool or shorter than k is an inactive row (the host-side layers refuse such tables)
-        const bool ok = len > 0 && len >= k && lo >= 0 && (int64_t)lo + len <= P;
+        const int kn = k_row != nullptr ? k_row[n] : k;
+        // a segment outside the pool or shorter than the row's k is an inactive row (the host-side layers refuse such tables)
+        const bool ok = kn >= 1 && kn <= k && len > 0 && len >= kn && lo >= 0 && (int64_t)lo + len <= P;
         s_lo[n] = lo;
         s_len[n] = ok ? len : 0;
+        s_k[n] = kn;
     }
     __syncthreads();
     for (int n = tid; n < N; n += 256) {
         int lead = -1;
         if (s_len[n] > 0)
             for (int m = 0; m <= n; ++m)
-                if (s_len[m] == s_len[n] && s_lo[m] == s_lo[n]) { lead = m; break; }
+                if (s_len[m] == s_len[n] && s_lo[m] == s_lo[n] && s_k[m] == s_k[n]) { lead = m; break; }
         s_lead[n] = lead;
     }
     __syncthreads();
     if (tid == 0) {
-        const int F = 64 / k;
         int G = 0;
         for (int n = 0; n < N; ++n) {
             const int lead = s_lead[n];
@@ -2276,7 +2285,7 @@ __global__ __launch_bounds__(256) void knn_grouped_plan_kernel(const int* __rest
             if (lead == n) {
                 g = G++;
                 int* e = w.grp + g * GR_FIELDS;
-                e[GR_G] = g; e[GR_LO] = s_lo[n]; e[GR_LEN] = s_len[n]; e[GR_SIZE] = 0;
+                e[GR_G] = g; e[GR_LO] = s_lo[n]; e[GR_LEN] = s_len[n]; e[GR_SIZE] = 0; e[GR_K] = s_k[n];
             } else {
                 g = w.row_g[lead];
             }
@@ -2289,6 +2298,7 @@ __global__ __launch_bounds__(256) void knn_grouped_plan_kernel(const int* __rest
             int* e = w.grp + g * GR_FIELDS;
             e[GR_MSTART] = mstart;
             mstart += e[GR_SIZE];
+            const int F = 64 / e[GR_K];
             e[GR_CHUNKS] = (e[GR_SIZE] * T + F - 1) / F;
             chunks_total += e[GR_CHUNKS];
         }
@@ -2315,11 +2325,10 @@ __global__ __launch_bounds__(256) void knn_grouped_plan_kernel(const int* __rest
 
 // one wave per item (wave-stride loop): the rows of one slab scored against the frames of one chunk, knn_scan_kernel's loop
 __global__ __launch_bounds__(64 * SCAN_WAVES) void knn_grouped_scan_kernel(const float* __restrict__ rows, const float* __restrict__ norms,
-                                                                           int T, int k, GroupedWs w) {
+                                                                           int T, GroupedWs w) {
     const int lane = threadIdx.x & 63;
     const int nw = gridDim.x * SCAN_WAVES;
     const int G = w.hdr[0], items = w.hdr[1];
-    const int F = 64 / k;
     for (int it = blockIdx.x * SCAN_WAVES + (threadIdx.x >> 6); it < items; it += nw) {
         int a = 0, b = G - 1;                                  // the group of the item: grp[g][GR_BASE] <= it < grp[g + 1][GR_BASE]
         while (a < b) {
@@ -2328,6 +2337,7 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void knn_grouped_scan_kernel(const
             else b = m - 1;
         }
         const int* e = w.grp + a * GR_FIELDS;
+        const int k = e[GR_K], F = 64 / k;                     // the group's k (wave-uniform)
         const int chunks = e[GR_CHUNKS], nslab = e[GR_NSLAB], len = e[GR_LEN], size = e[GR_SIZE];
         const int r = it - e[GR_BASE];
         const int slab = r / chunks, c = r - slab * chunks;
@@ -2391,8 +2401,11 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void knn_grouped_scan_kernel(const
     }
 }
 
-// one block per batch frame: the nslab lists of its chunk -> exact top-k (pool indices); inactive rows get val -inf, idx -1
-template <bool K4>
+// one block per batch frame: the nslab lists of its chunk -> exact top-k (pool indices); inactive rows get val -inf, idx -1.
+// MODE MERGE_GEN / MERGE_K4: scan_merge_frame<false / true> (every group at the call's k); MERGE_ROW: per-row k -- the frame's
+// group's k picks the body the uniform call takes at that k (block-uniform), and the entries behind it get val -inf, idx -1.
+enum { MERGE_GEN = 0, MERGE_K4 = 1, MERGE_ROW = 2 };
+template <int MODE>
 __global__ __launch_bounds__(256) void knn_grouped_merge_kernel(int T, int k, GroupedWs w, float* __restrict__ out_val,
                                                                 int* __restrict__ out_idx) {
     const int64_t ft = blockIdx.x;
@@ -2406,11 +2419,21 @@ __global__ __launch_bounds__(256) void knn_grouped_merge_kernel(int T, int k, Gr
         return;
     }
     const int* e = w.grp + g * GR_FIELDS;
-    const int F = 64 / k;
+    const int kg = MODE == MERGE_ROW ? e[GR_K] : k;
+    const int F = 64 / kg;
     const int j = w.row_rank[n] * T + t;
     const int c = j / F, pos = j - c * F;
     const size_t off = (size_t)(e[GR_BASE] + c) * 64;
-    scan_merge_frame<K4>(w.pv + off, w.pi + off, (int64_t)e[GR_CHUNKS] * 64, e[GR_NSLAB], pos, k, 0, out_val, out_idx, ft);
+    if constexpr (MODE == MERGE_ROW) {
+        if ((int)threadIdx.x >= kg && (int)threadIdx.x < k) {
+            out_val[ft * k + threadIdx.x] = -INFINITY;
+            out_idx[ft * k + threadIdx.x] = -1;
+        }
+        if (kg <= 4) scan_merge_frame<true>(w.pv + off, w.pi + off, (int64_t)e[GR_CHUNKS] * 64, e[GR_NSLAB], pos, kg, 0, out_val, out_idx, ft, k);
+        else scan_merge_frame<false>(w.pv + off, w.pi + off, (int64_t)e[GR_CHUNKS] * 64, e[GR_NSLAB], pos, kg, 0, out_val, out_idx, ft, k);
+    } else {
+        scan_merge_frame<MODE == MERGE_K4>(w.pv + off, w.pi + off, (int64_t)e[GR_CHUNKS] * 64, e[GR_NSLAB], pos, kg, 0, out_val, out_idx, ft, k);
+    }
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -2423,13 +2446,16 @@ __global__ __launch_bounds__(256) void knn_grouped_merge_kernel(int T, int k, Gr
 // LISTS > 1 (alive_knn_blend_gather_rows, with ROWS): output row n owns the list rows first[n] .. first[n+1]-1 (at most LISTS),
 // each a one-shard top-k list [list row * T + t][k] with a weight; phase 1 copies them into the per-list table sel[s], phase 2
 // forms each active list's mean as the one-list form does and sums them weighted, in list order, before the alpha blend.
+// k_rows (with ROWS; alive_knn_merge_gather_rows_k / alive_knn_blend_gather_rows_k): output row n's own k = k_rows[n], its lists
+// (a blend's lists all use their owner's k) read at stride k = k_max; a k_rows[n] outside [1, k_max] passes the row's source through.
 template <int NPER, int KMAX, bool ROWS = false, int LISTS = 1>
 __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __restrict__ cand_val,
                                                                const int* __restrict__ cand_idx, int S, int k, float alpha,
                                                                float one_minus, const float* __restrict__ rows, const float* __restrict__ src,
                                                                int T, int64_t Tt, float* __restrict__ out,
                                                                int* __restrict__ final_idx, const double* __restrict__ alpha_rows = nullptr,
-                                                               const int* __restrict__ first = nullptr, const double* __restrict__ weight = nullptr) {
+                                                               const int* __restrict__ first = nullptr, const double* __restrict__ weight = nullptr,
+                                                               const int* __restrict__ k_rows = nullptr) {
     constexpr bool BLEND = LISTS > 1;
     static_assert(!BLEND || ROWS, "the blend form takes a per-row alpha");
     __shared__ int sel[LISTS][32][KMAX];
@@ -2440,6 +2466,15 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
         const double a = alpha_rows[n];
         alpha = (float)a;
         one_minus = (float)(1.0 - a);
+    }
+    const int ks = k;                                   // entries per frame of a list as it lies in memory
+    bool dead = false;                                  // per-row k out of range: the row passes its source through
+    if constexpr (ROWS) {
+        if (k_rows != nullptr) {
+            const int kn = k_rows[n];
+            dead = kn < 1 || kn > ks;
+            k = dead ? 1 : kn;
+        }
     }
     const int t0 = blockIdx.x * 32;
     const int nf = (T - t0) < 32 ? (T - t0) : 32;
@@ -2455,7 +2490,7 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
         const int per = nf * k;
         for (int e = tid; e < nl * per; e += 256) {
             const int s = e / per, r = e - s * per, f = r / k, j = r - f * k;
-            sel[s][f][j] = cand_idx[((size_t)(l0 + s) * T + t0) * k + r];
+            sel[s][f][j] = cand_idx[((size_t)(l0 + s) * T + t0 + f) * ks + j];
         }
         __syncthreads();
 
@@ -2490,7 +2525,7 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
 #pragma unroll
                     for (int s = 0; s < LISTS; ++s)
                         if (s < nl && sel[s][f][0] >= 0) any = true;
-                    if (!any) out[o] = src[o];
+                    if (!any || dead) out[o] = src[o];
                     else out[o] = tile[f][d] * one_minus + src[o] * alpha;
                 }
             }
@@ -2510,16 +2545,14 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
             int e = j * 64 + lane;
             bool in = e < S * k;
             int s = in ? e / k : 0, kk = in ? e % k : 0;
-            size_t o = ((size_t)s * Tt + ft) * k + kk;
+            size_t o = ((size_t)s * Tt + ft) * ks + kk;
             id[j] = in ? cand_idx[o] : -1;
             v[j] = (in && id[j] >= 0) ? cand_val[o] : -INFINITY;
         }
         if (S == 1) {
             // a single shard: its list IS the merged list (sorted, -1 behind the last valid entry)
-            if (lane < k) {
-                sel[0][f][lane] = id[0];
-                if (final_idx != nullptr && blockIdx.z == 0) final_idx[(size_t)ft * k + lane] = id[0];
-            }
+            if (lane < k) sel[0][f][lane] = id[0];
+            if (lane < ks && final_idx != nullptr && blockIdx.z == 0) final_idx[(size_t)ft * ks + lane] = (lane < k && !dead) ? id[0] : -1;
             continue;
         }
         for (int j = 0; j < k; ++j) {
@@ -2536,7 +2569,7 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
             int wi = __shfl(bi, win);
             if (lane == 0) {
                 sel[0][f][j] = wi;
-                if (final_idx != nullptr && blockIdx.z == 0) final_idx[(size_t)ft * k + j] = wi;
+                if (final_idx != nullptr && blockIdx.z == 0) final_idx[(size_t)ft * ks + j] = wi;
             }
             if (lane == win) {
 #pragma unroll
@@ -2566,7 +2599,7 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
             if (f < nf) {
                 size_t o = ((size_t)n * D + d0 + d) * T + t0 + f;
                 float m = tile[f][d];
-                if (ROWS && sel[0][f][0] < 0) out[o] = src[o];
+                if (ROWS && (sel[0][f][0] < 0 || dead)) out[o] = src[o];
                 else out[o] = m * one_minus + src[o] * alpha;
             }
         }
@@ -3117,7 +3150,9 @@ static SeedArgs seeds_for(const SearchWs& w, int64_t fb, int split, int k, float
 // the frames that fail it) for a batch whose rows search different voices.  The voice table is device data, so a one-block
 // prologue turns it into a plan on the device and every grid is sized from N, T, k and the pool's dimensions (no host sync, one
 // launch per stage whatever the number of voices):
-//   groups   the rows of one voice (sorted by voice, then row): their frames, row-major, are cut into 256-frame blocks of that voice
+//   groups   the rows of one voice at one k (sorted by voice, then k, then row; k is the call's, or -- alive_knn_search_pool_k -- row
+//            n's own k_row[n] <= k_max, so every group and every block is uniform in k and a voice searched at two k forms two
+//            groups): their frames, row-major, are cut into 256-frame blocks of that voice
 //            alone (knn_pool_gather_kernel compacts them into SLOTS: group g owns slots [blk0 * 256, (blk0 + nblk) * 256));
 //   splits   every voice's image is cut into gridDim.y tile ranges (empty ranges write empty lists);
 //   stage    knn_score_kernel<false, true> (the candidate stage of alive_knn_search_strict on the block's voice image), then
@@ -3148,13 +3183,14 @@ struct PoolWs {
     size_t bytes;
 };
 
-static PoolWs pool_ws_layout(void* base, int N, int T, int k, int V, int64_t max_len) {
+// kinds: the values of k one voice may be searched at in one call (1: every row at k; k: rows at their own k in [1, k])
+static PoolWs pool_ws_layout(void* base, int N, int T, int k, int V, int64_t max_len, int kinds = 1) {
     PoolWs w{};
     const int64_t Tt = (int64_t)N * T;
-    const int64_t gmax = N < V ? N : V;                                 // groups: each adds at most one partial frame block
+    const int64_t gmax = N < (int64_t)V * kinds ? N : (int64_t)V * kinds;   // groups: each adds at most one partial frame block
     w.S = ((Tt + FT - 1) / FT + gmax) * FT;
     w.P = make_plan(Tt, max_len).split;
-    const int F = 64 / k;
+    const int F = 64 / k;                                               // (a group at k' <= k has chunks of 64 / k' >= F frames)
     const int64_t chunks = (Tt + F - 1) / F + gmax;
     w.items = chunks > GR_ITEMS ? chunks : GR_ITEMS;
     Arena a(base);
@@ -3191,9 +3227,20 @@ __global__ __launch_bounds__(256) void pool_image_kernel(const float* __restrict
     lib[i] = f32_to_bf16_rn(q);
 }
 
-// one block: voice table -> groups (rows sorted by (voice, row) with a bitonic sort in LDS), frame blocks, members
-__global__ __launch_bounds__(1024) void knn_pool_plan_kernel(const int32_t* __restrict__ voice, int N, int T, const int32_t* __restrict__ seg_lo,
-                                                             const int32_t* __restrict__ seg_len, int V, int64_t P, int k, PoolWs w) {
+// a row of the pool search is active: its voice in the table, inside the pool and at least as long as the row's k (k_row null:
+// every row at k; else row n at k_row[n], which must lie in [1, k]) -> the row's k, 0 for an inactive row
+__device__ __forceinline__ int pool_row_k(int n, const int32_t* voice, const int32_t* k_row, const int32_t* seg_lo, const int32_t* seg_len,
+                                          int V, int64_t P, int k) {
+    const int v = voice[n];
+    const int kn = k_row != nullptr ? k_row[n] : k;
+    const bool ok = kn >= 1 && kn <= k && v >= 0 && v < V && seg_len[v] >= kn && seg_lo[v] >= 0 && (int64_t)seg_lo[v] + seg_len[v] <= P;
+    return ok ? kn : 0;
+}
+
+// one block: voice table -> groups (rows sorted by (voice, k, row) with a bitonic sort in LDS), frame blocks, members
+__global__ __launch_bounds__(1024) void knn_pool_plan_kernel(const int32_t* __restrict__ voice, const int32_t* __restrict__ k_row, int N, int T,
+                                                             const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_len, int V,
+                                                             int64_t P, int k, PoolWs w) {
     __shared__ unsigned long long key[POOL_MAX_ROWS];
     __shared__ int s_groups;
     const int tid = threadIdx.x;
@@ -3203,10 +3250,9 @@ __global__ __launch_bounds__(1024) void knn_pool_plan_kernel(const int32_t* __re
     for (int n = tid; n < np; n += 1024) {
         unsigned long long kk = NONE;
         if (n < N) {
-            const int v = voice[n];
-            // a voice outside the table, outside the pool or shorter than k: an inactive row (val -inf, idx -1)
-            if (v >= 0 && v < V && seg_len[v] >= k && seg_lo[v] >= 0 && (int64_t)seg_lo[v] + seg_len[v] <= P)
-                kk = ((unsigned long long)v << 32) | (unsigned)n;
+            // a voice outside the table, outside the pool or shorter than the row's k: an inactive row (val -inf, idx -1)
+            const int kn = pool_row_k(n, voice, k_row, seg_lo, seg_len, V, P, k);
+            if (kn > 0) kk = ((unsigned long long)voice[n] << 36) | ((unsigned long long)kn << 32) | (unsigned)n;      // (kn <= 8)
         }
         key[n] = kk;
     }
@@ -3226,12 +3272,13 @@ __global__ __launch_bounds__(1024) void knn_pool_plan_kernel(const int32_t* __re
     if (tid == 0) {
         int G = 0, blocks = 0;
         for (int i = 0; i < N && key[i] != NONE;) {
-            const int v = (int)(key[i] >> 32);
+            const unsigned long long vk = key[i] >> 32;
+            const int v = (int)(vk >> 4);
             int j = i + 1;
-            while (j < N && key[j] != NONE && (int)(key[j] >> 32) == v) ++j;
+            while (j < N && key[j] != NONE && (key[j] >> 32) == vk) ++j;
             int* e = w.grp + G * PG_FIELDS;
             const int nblk = (int)(((int64_t)(j - i) * T + FT - 1) / FT);
-            e[PG_VOICE] = v; e[PG_MSTART] = i; e[PG_SIZE] = j - i; e[PG_BLK0] = blocks; e[PG_NBLK] = nblk;
+            e[PG_VOICE] = v; e[PG_K] = (int)(vk & 15); e[PG_MSTART] = i; e[PG_SIZE] = j - i; e[PG_BLK0] = blocks; e[PG_NBLK] = nblk;
             blocks += nblk;
             ++G;
             i = j;
@@ -3277,26 +3324,25 @@ __global__ __launch_bounds__(128) void knn_pool_gather_kernel(int T, PoolWs w) {
     ((u32x4*)(w.s_c + (size_t)slot * D))[threadIdx.x] = v;
 }
 
-// frames of inactive rows: val -inf, idx -1 (the grouped search's convention)
-__global__ __launch_bounds__(256) void knn_pool_inactive_kernel(const int32_t* __restrict__ voice, int N, int T, const int32_t* __restrict__ seg_lo,
-                                                                const int32_t* __restrict__ seg_len, int V, int64_t P, int k,
-                                                                float* __restrict__ out_val, int* __restrict__ out_idx) {
+// frames of inactive rows: val -inf, idx -1 (the grouped search's convention); per-row k: so are the entries behind a row's own k
+__global__ __launch_bounds__(256) void knn_pool_inactive_kernel(const int32_t* __restrict__ voice, const int32_t* __restrict__ k_row, int N, int T,
+                                                                const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_len, int V,
+                                                                int64_t P, int k, float* __restrict__ out_val, int* __restrict__ out_idx) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)N * T * k) return;
-    const int v = voice[i / ((int64_t)T * k)];
-    if (v >= 0 && v < V && seg_len[v] >= k && seg_lo[v] >= 0 && (int64_t)seg_lo[v] + seg_len[v] <= P) return;
+    if ((int)(i % k) < pool_row_k((int)(i / ((int64_t)T * k)), voice, k_row, seg_lo, seg_len, V, P, k)) return;
     out_val[i] = -INFINITY;
     out_idx[i] = -1;
 }
 
 // one block: per-group counts of the frames that failed the certificate -> fallback items (grouped-scan slabs x chunks)
-__global__ void knn_pool_fallback_plan_kernel(const int32_t* __restrict__ seg_len, int k, PoolWs w) {
+__global__ void knn_pool_fallback_plan_kernel(const int32_t* __restrict__ seg_len, PoolWs w) {
     if (threadIdx.x != 0) return;
-    const int G = w.hdr[PH_GROUPS], F = 64 / k;
+    const int G = w.hdr[PH_GROUPS];
     int chunks_total = 0, fail = 0;
     for (int g = 0; g < G; ++g) {
         int* e = w.grp + g * PG_FIELDS;
-        const int c = w.gfail[g];
+        const int c = w.gfail[g], F = 64 / e[PG_K];
         e[PG_FBASE] = fail;
         e[PG_CHUNKS] = (c + F - 1) / F;
         fail += c;
@@ -3334,14 +3380,14 @@ __device__ __forceinline__ int pool_group_of(const int* grp, int G, int field, i
 // (knn_grouped_scan_kernel's loop and arithmetic; pool row indices)
 __global__ __launch_bounds__(64 * SCAN_WAVES) void knn_pool_scan_kernel(const float* __restrict__ rows, const float* __restrict__ norms,
                                                                         const int32_t* __restrict__ seg_lo, const int32_t* __restrict__ seg_len,
-                                                                        int k, PoolWs w) {
+                                                                        PoolWs w) {
     const int lane = threadIdx.x & 63;
     const int nw = gridDim.x * SCAN_WAVES;
     const int G = w.hdr[PH_GROUPS], items = w.hdr[PH_ITEMS];
-    const int F = 64 / k;
     for (int it = blockIdx.x * SCAN_WAVES + (threadIdx.x >> 6); it < items; it += nw) {
         const int g = pool_group_of(w.grp, G, PG_BASE, it);
         const int* e = w.grp + g * PG_FIELDS;
+        const int k = e[PG_K], F = 64 / k;                     // the group's k (wave-uniform)
         const int chunks = e[PG_CHUNKS], nslab = e[PG_NSLAB], v = e[PG_VOICE];
         const int64_t len = seg_len[v], lo = seg_lo[v];
         const int r = it - e[PG_BASE];
@@ -3404,18 +3450,24 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void knn_pool_scan_kernel(const fl
 }
 
 // block-stride loop over the failing frames: the nslab lists of a frame's chunk -> its exact top-k (overwrites the rescored lists)
-template <bool K4>
+// (MODE as knn_grouped_merge_kernel: MERGE_ROW takes the body the uniform call takes at the group's k; k: the lists' stride)
+template <int MODE>
 __global__ __launch_bounds__(256) void knn_pool_merge_kernel(int k, PoolWs w, float* __restrict__ out_val, int* __restrict__ out_idx) {
     const int G = w.hdr[PH_GROUPS], fail = w.hdr[PH_FAIL];
-    const int F = 64 / k;
     for (int i = blockIdx.x; i < fail; i += gridDim.x) {
         const int g = pool_group_of(w.grp, G, PG_FBASE, i);
         const int* e = w.grp + g * PG_FIELDS;
+        const int kg = MODE == MERGE_ROW ? e[PG_K] : k, F = 64 / kg;
         const int pos = i - e[PG_FBASE];
         const int c = pos / F;
         const int ft = w.slot_frame[w.fb[(int64_t)e[PG_BLK0] * FT + pos]];
         const size_t off = (size_t)(e[PG_BASE] + c) * 64;
-        scan_merge_frame<K4>(w.pv + off, w.pi + off, (int64_t)e[PG_CHUNKS] * 64, e[PG_NSLAB], pos - c * F, k, 0, out_val, out_idx, ft);
+        if constexpr (MODE == MERGE_ROW) {
+            if (kg <= 4) scan_merge_frame<true>(w.pv + off, w.pi + off, (int64_t)e[PG_CHUNKS] * 64, e[PG_NSLAB], pos - c * F, kg, 0, out_val, out_idx, ft, k);
+            else scan_merge_frame<false>(w.pv + off, w.pi + off, (int64_t)e[PG_CHUNKS] * 64, e[PG_NSLAB], pos - c * F, kg, 0, out_val, out_idx, ft, k);
+        } else {
+            scan_merge_frame<MODE == MERGE_K4>(w.pv + off, w.pi + off, (int64_t)e[PG_CHUNKS] * 64, e[PG_NSLAB], pos - c * F, kg, 0, out_val, out_idx, ft, k);
+        }
         __syncthreads();                                    // (the merge's LDS exchange is reused by the next frame)
     }
 }
@@ -3956,55 +4008,103 @@ extern "C" size_t alive_knn_grouped_workspace_bytes(int N, int T, int k) {
     return grouped_ws_layout(nullptr, N, T, k).bytes;
 }
 
-extern "C" int alive_knn_search_grouped(const float* src, int N, int T, const float* rows_f32, const float* norms, int64_t P,
-                                        const int32_t* seg_lo, const int32_t* seg_len, int k, float* out_val, int32_t* out_idx,
-                                        void* ws, void* stream) {
-    ALIVE_CHECK_ARG(src && rows_f32 && norms && seg_lo && seg_len && out_val && out_idx && ws, "alive_knn_search_grouped: null pointer");
-    ALIVE_CHECK_ARG(k >= 1 && k <= KH, "alive_knn_search_grouped: k=%d outside [1,%d]", k, KH);
-    ALIVE_CHECK_ARG(N >= 1 && N <= GR_MAX_ROWS, "alive_knn_search_grouped: N=%d outside [1,%d]", N, GR_MAX_ROWS);
-    ALIVE_CHECK_ARG(T >= 1 && (int64_t)N * T <= (int64_t)1 << 20, "alive_knn_search_grouped: T=%d out of range", T);
-    ALIVE_CHECK_ARG(P >= k && P < (int64_t)1 << 31, "alive_knn_search_grouped: pool of %lld rows (k=%d)", (long long)P, k);
+// both grouped entry points: k_row null = every row at k (alive_knn_search_grouped), else k = k_max and row n at k_row[n]
+static int search_grouped(const char* who, const float* src, int N, int T, const float* rows_f32, const float* norms, int64_t P,
+                          const int32_t* seg_lo, const int32_t* seg_len, const int32_t* k_row, int k, float* out_val, int32_t* out_idx,
+                          void* ws, void* stream) {
+    ALIVE_CHECK_ARG(src && rows_f32 && norms && seg_lo && seg_len && out_val && out_idx && ws, "%s: null pointer", who);
+    ALIVE_CHECK_ARG(k >= 1 && k <= KH, "%s: k=%d outside [1,%d]", who, k, KH);
+    ALIVE_CHECK_ARG(N >= 1 && N <= GR_MAX_ROWS, "%s: N=%d outside [1,%d]", who, N, GR_MAX_ROWS);
+    ALIVE_CHECK_ARG(T >= 1 && (int64_t)N * T <= (int64_t)1 << 20, "%s: T=%d out of range", who, T);
+    ALIVE_CHECK_ARG(P >= (k_row ? 1 : k) && P < (int64_t)1 << 31, "%s: pool of %lld rows (k=%d)", who, (long long)P, k);
     const GroupedWs w = grouped_ws_layout(ws, N, T, k);
     const int64_t Tt = (int64_t)N * T;
     hipStream_t s = (hipStream_t)stream;
     src_prep_small_kernel<<<(unsigned)Tt, 256, 0, s>>>(src, T, Tt, w.s_f32, w.s_bf16, nullptr);
-    knn_grouped_plan_kernel<<<1, 256, 0, s>>>(seg_lo, seg_len, N, T, P, k, w);
-    knn_grouped_scan_kernel<<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, T, k, w);
-    if (k <= 4) knn_grouped_merge_kernel<true><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
-    else knn_grouped_merge_kernel<false><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
-    ALIVE_CHECK_LAUNCH("alive_knn_search_grouped");
+    knn_grouped_plan_kernel<<<1, 256, 0, s>>>(seg_lo, seg_len, k_row, N, T, P, k, w);
+    knn_grouped_scan_kernel<<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, T, w);
+    if (k_row != nullptr) knn_grouped_merge_kernel<MERGE_ROW><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
+    else if (k <= 4) knn_grouped_merge_kernel<MERGE_K4><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
+    else knn_grouped_merge_kernel<MERGE_GEN><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
+    ALIVE_CHECK_LAUNCH(who);
+    return ALIVE_OK;
+}
+
+extern "C" int alive_knn_search_grouped(const float* src, int N, int T, const float* rows_f32, const float* norms, int64_t P,
+                                        const int32_t* seg_lo, const int32_t* seg_len, int k, float* out_val, int32_t* out_idx,
+                                        void* ws, void* stream) {
+    return search_grouped("alive_knn_search_grouped", src, N, T, rows_f32, norms, P, seg_lo, seg_len, nullptr, k, out_val, out_idx, ws, stream);
+}
+
+// per-row k: the workspace and every grid from N, T and k_max; k_row is read by the plan kernel when the call runs
+extern "C" size_t alive_knn_grouped_k_workspace_bytes(int N, int T, int k_max) { return alive_knn_grouped_workspace_bytes(N, T, k_max); }
+
+extern "C" int alive_knn_search_grouped_k(const float* src, int N, int T, const float* rows_f32, const float* norms, int64_t P,
+                                          const int32_t* seg_lo, const int32_t* seg_len, const int32_t* k_row, int k_max, float* out_val,
+                                          int32_t* out_idx, void* ws, void* stream) {
+    ALIVE_CHECK_ARG(k_row, "alive_knn_search_grouped_k: null pointer");
+    return search_grouped("alive_knn_search_grouped_k", src, N, T, rows_f32, norms, P, seg_lo, seg_len, k_row, k_max, out_val, out_idx, ws,
+                          stream);
+}
+
+// both one-shard row gathers: k_row null = every row at k (alive_knn_merge_gather_rows), else lists at stride k = k_max, row n at k_row[n]
+static int merge_gather_rows(const char* who, const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k, const double* alpha,
+                             const float* rows_f32_full, const float* src, int N, int T, float* out, int32_t* final_idx, void* stream) {
+    ALIVE_CHECK_ARG(cand_val && cand_idx && alpha && rows_f32_full && src && out, "%s: null pointer", who);
+    ALIVE_CHECK_ARG(k >= 1 && k <= 8, "%s: k=%d outside [1,8]", who, k);
+    ALIVE_CHECK_ARG(N > 0 && T > 0, "%s: empty source", who);
+    const int zs = (int64_t)cdiv(T, 32) * N < 64 ? D / 64 : 1;       // as alive_knn_merge_gather
+    const dim3 g(cdiv(T, 32), N, zs);
+    knn_merge_gather_kernel<2, 8, true><<<g, 256, 0, (hipStream_t)stream>>>(cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T,
+                                                                         (int64_t)N * T, out, final_idx, alpha, nullptr, nullptr, k_row);
+    ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
 }
 
 extern "C" int alive_knn_merge_gather_rows(const float* cand_val, const int32_t* cand_idx, int k, const double* alpha,
                                            const float* rows_f32_full, const float* src, int N, int T, float* out,
                                            int32_t* final_idx, void* stream) {
-    ALIVE_CHECK_ARG(cand_val && cand_idx && alpha && rows_f32_full && src && out, "alive_knn_merge_gather_rows: null pointer");
-    ALIVE_CHECK_ARG(k >= 1 && k <= 8, "alive_knn_merge_gather_rows: k=%d outside [1,8]", k);
-    ALIVE_CHECK_ARG(N > 0 && T > 0, "alive_knn_merge_gather_rows: empty source");
-    const int zs = (int64_t)cdiv(T, 32) * N < 64 ? D / 64 : 1;       // as alive_knn_merge_gather
-    const dim3 g(cdiv(T, 32), N, zs);
-    knn_merge_gather_kernel<2, 8, true><<<g, 256, 0, (hipStream_t)stream>>>(cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T,
-                                                                         (int64_t)N * T, out, final_idx, alpha);
-    ALIVE_CHECK_LAUNCH("alive_knn_merge_gather_rows");
-    return ALIVE_OK;
+    return merge_gather_rows("alive_knn_merge_gather_rows", cand_val, cand_idx, nullptr, k, alpha, rows_f32_full, src, N, T, out, final_idx,
+                             stream);
+}
+
+extern "C" int alive_knn_merge_gather_rows_k(const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k_max,
+                                             const double* alpha, const float* rows_f32_full, const float* src, int N, int T, float* out,
+                                             int32_t* final_idx, void* stream) {
+    ALIVE_CHECK_ARG(k_row, "alive_knn_merge_gather_rows_k: null pointer");
+    return merge_gather_rows("alive_knn_merge_gather_rows_k", cand_val, cand_idx, k_row, k_max, alpha, rows_f32_full, src, N, T, out,
+                             final_idx, stream);
 }
 
 // Voice blending: output row n mixes the means of its list rows first[n] .. first[n+1]-1 with their weights (the blend form of
 // knn_merge_gather_kernel: same grid forms as alive_knn_merge_gather_rows, a per-list table in LDS).  No allocation, no sync.
-extern "C" int alive_knn_blend_gather_rows(const float* cand_val, const int32_t* cand_idx, int k, const int32_t* first,
-                                           const double* weight, const double* alpha, const float* rows_f32_full, const float* src,
-                                           int N, int T, float* out, void* stream) {
-    ALIVE_CHECK_ARG(cand_val && cand_idx && first && weight && alpha && rows_f32_full && src && out,
-                    "alive_knn_blend_gather_rows: null pointer");
-    ALIVE_CHECK_ARG(k >= 1 && k <= 8, "alive_knn_blend_gather_rows: k=%d outside [1,8]", k);
-    ALIVE_CHECK_ARG(N >= 1 && T >= 1, "alive_knn_blend_gather_rows: N=%d, T=%d: empty source", N, T);
+static int blend_gather_rows(const char* who, const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k,
+                             const int32_t* first, const double* weight, const double* alpha, const float* rows_f32_full, const float* src,
+                             int N, int T, float* out, void* stream) {
+    ALIVE_CHECK_ARG(cand_val && cand_idx && first && weight && alpha && rows_f32_full && src && out, "%s: null pointer", who);
+    ALIVE_CHECK_ARG(k >= 1 && k <= 8, "%s: k=%d outside [1,8]", who, k);
+    ALIVE_CHECK_ARG(N >= 1 && T >= 1, "%s: N=%d, T=%d: empty source", who, N, T);
     const int zs = (int64_t)cdiv(T, 32) * N < 64 ? D / 64 : 1;       // as alive_knn_merge_gather_rows
     const dim3 g(cdiv(T, 32), N, zs);
     knn_merge_gather_kernel<2, 8, true, ALIVE_MAX_BLEND><<<g, 256, 0, (hipStream_t)stream>>>(
-        cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T, (int64_t)N * T, out, nullptr, alpha, first, weight);
-    ALIVE_CHECK_LAUNCH("alive_knn_blend_gather_rows");
+        cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T, (int64_t)N * T, out, nullptr, alpha, first, weight, k_row);
+    ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
+}
+
+extern "C" int alive_knn_blend_gather_rows(const float* cand_val, const int32_t* cand_idx, int k, const int32_t* first,
+                                           const double* weight, const double* alpha, const float* rows_f32_full, const float* src,
+                                           int N, int T, float* out, void* stream) {
+    return blend_gather_rows("alive_knn_blend_gather_rows", cand_val, cand_idx, nullptr, k, first, weight, alpha, rows_f32_full, src, N, T,
+                             out, stream);
+}
+
+extern "C" int alive_knn_blend_gather_rows_k(const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k_max,
+                                             const int32_t* first, const double* weight, const double* alpha, const float* rows_f32_full,
+                                             const float* src, int N, int T, float* out, void* stream) {
+    ALIVE_CHECK_ARG(k_row, "alive_knn_blend_gather_rows_k: null pointer");
+    return blend_gather_rows("alive_knn_blend_gather_rows_k", cand_val, cand_idx, k_row, k_max, first, weight, alpha, rows_f32_full, src, N,
+                             T, out, stream);
 }
 
 // ---- pool search (many-to-many batch conversion) ----
@@ -4051,35 +4151,41 @@ extern "C" size_t alive_knn_pool_workspace_bytes(int N, int T, int k, int V, int
     return pool_ws_layout(nullptr, N, T, k, V, max_len).bytes;
 }
 
+// per-row k: a voice may be searched at up to k_max values of k, each a group of its own (at most min(N, k_max V) groups)
+extern "C" size_t alive_knn_pool_k_workspace_bytes(int N, int T, int k_max, int V, int64_t P, int64_t max_len) {
+    if (!pool_args_ok(N, T, k_max, V, P, max_len)) return 0;
+    return pool_ws_layout(nullptr, N, T, k_max, V, max_len, k_max).bytes;
+}
+
 extern "C" const int* alive_knn_pool_stats(void* ws) { return (const int*)ws; }
 
-extern "C" int alive_knn_search_pool(const float* src, int N, int T, const void* images, const int64_t* img_off, const float* rows_f32,
-                                     const float* norms, const float* bounds, int64_t P, const int32_t* seg_lo, const int32_t* seg_len, int V,
-                                     int64_t max_len, const int32_t* voice, int k, float* out_val, int32_t* out_idx, void* ws, void* stream) {
+// both pool entry points: k_row null = every row at k (alive_knn_search_pool), else k = k_max and row n at k_row[n]
+static int search_pool(const char* who, const float* src, int N, int T, const void* images, const int64_t* img_off, const float* rows_f32,
+                       const float* norms, const float* bounds, int64_t P, const int32_t* seg_lo, const int32_t* seg_len, int V,
+                       int64_t max_len, const int32_t* voice, const int32_t* k_row, int k, float* out_val, int32_t* out_idx, void* ws,
+                       void* stream) {
     ALIVE_CHECK_ARG(src && images && img_off && rows_f32 && norms && bounds && seg_lo && seg_len && voice && out_val && out_idx && ws,
-                    "alive_knn_search_pool: null pointer");
-    ALIVE_CHECK_ARG(k >= 1 && k <= KH, "alive_knn_search_pool: k=%d outside [1,%d]", k, KH);
-    ALIVE_CHECK_ARG(N >= 1 && N <= POOL_MAX_ROWS, "alive_knn_search_pool: N=%d outside [1,%d]", N, POOL_MAX_ROWS);
-    ALIVE_CHECK_ARG(T >= 1 && (int64_t)N * T <= POOL_MAX_FRAMES, "alive_knn_search_pool: N*T=%lld outside [1,%d]", (long long)N * T,
-                    POOL_MAX_FRAMES);
-    ALIVE_CHECK_ARG(V >= 1 && P >= 1 && P < ((int64_t)1 << 31), "alive_knn_search_pool: V=%d voices, pool of %lld rows", V, (long long)P);
-    ALIVE_CHECK_ARG(max_len >= 1 && max_len <= P, "alive_knn_search_pool: longest voice %lld outside [1, %lld]", (long long)max_len,
-                    (long long)P);
-    if (int rc = lds_optin("alive_knn_search_pool")) return rc;
+                    "%s: null pointer", who);
+    ALIVE_CHECK_ARG(k >= 1 && k <= KH, "%s: k=%d outside [1,%d]", who, k, KH);
+    ALIVE_CHECK_ARG(N >= 1 && N <= POOL_MAX_ROWS, "%s: N=%d outside [1,%d]", who, N, POOL_MAX_ROWS);
+    ALIVE_CHECK_ARG(T >= 1 && (int64_t)N * T <= POOL_MAX_FRAMES, "%s: N*T=%lld outside [1,%d]", who, (long long)N * T, POOL_MAX_FRAMES);
+    ALIVE_CHECK_ARG(V >= 1 && P >= 1 && P < ((int64_t)1 << 31), "%s: V=%d voices, pool of %lld rows", who, V, (long long)P);
+    ALIVE_CHECK_ARG(max_len >= 1 && max_len <= P, "%s: longest voice %lld outside [1, %lld]", who, (long long)max_len, (long long)P);
+    if (int rc = lds_optin(who)) return rc;
     static LdsOptIn optin_pool;
     if (optin_pool.ensure({(const void*)knn_score_kernel<false, true>}, SCORE_LDS) != hipSuccess) {
-        alive_set_error("alive_knn_search_pool: cannot reserve %d B of LDS", SCORE_LDS);
+        alive_set_error("%s: cannot reserve %d B of LDS", who, SCORE_LDS);
         return ALIVE_ERR_LAUNCH;
     }
-    const PoolWs w = pool_ws_layout(ws, N, T, k, V, max_len);
+    const PoolWs w = pool_ws_layout(ws, N, T, k, V, max_len, k_row != nullptr ? k : 1);
     const int64_t Tt = (int64_t)N * T;
     hipStream_t s = (hipStream_t)stream;
     (void)hipMemsetAsync(w.stats, 0, ALIVE_POOL_STATS * sizeof(int), s);
-    knn_pool_inactive_kernel<<<(unsigned)((Tt * k + 255) / 256), 256, 0, s>>>(voice, N, T, seg_lo, seg_len, V, P, k, out_val, out_idx);
+    knn_pool_inactive_kernel<<<(unsigned)((Tt * k + 255) / 256), 256, 0, s>>>(voice, k_row, N, T, seg_lo, seg_len, V, P, k, out_val, out_idx);
     // frames: the strict search's preparation (the same kernel choice by frame count: bitwise the same s_f32 and bound share)
     if (Tt <= 512) src_prep_small_kernel<<<(unsigned)Tt, 256, 0, s>>>(src, T, Tt, w.s_f32, w.s_bf16, w.dq);
     else src_prep_kernel<<<(unsigned)((Tt + 63) / 64), 256, 0, s>>>(src, T, Tt, (Tt + 63) / 64 * 64, w.s_f32, w.s_bf16, w.dq);
-    knn_pool_plan_kernel<<<1, 1024, 0, s>>>(voice, N, T, seg_lo, seg_len, V, P, k, w);
+    knn_pool_plan_kernel<<<1, 1024, 0, s>>>(voice, k_row, N, T, seg_lo, seg_len, V, P, k, w);
     knn_pool_gather_kernel<<<(unsigned)w.S, 128, 0, s>>>(T, w);
     const PoolBlocks pb{w.hdr, w.blk_voice, img_off, seg_lo, seg_len};
     knn_score_kernel<false, true><<<dim3((unsigned)(w.S / FT), w.P), 256, SCORE_LDS, s>>>(
@@ -4087,6 +4193,7 @@ extern "C" int alive_knn_search_pool(const float* src, int N, int T, const void*
         pb);
     const PoolRescore pr{w.slot_grp, w.grp, w.gfail, w.fb};
     const int R = w.P * KP;
+    // (the kernel takes each frame's k from its group; the k argument is the stride of the lists)
 #define ALIVE_POOL_RESCORE(PER_)                                                                                                   \
     knn_rescore_kernel<PER_, true><<<(unsigned)(w.S / 4), 256, 0, s>>>(w.cv, w.ci, w.P, KP, w.s_f32, rows_f32, norms, w.S, 0, k,     \
                                                                      out_val, out_idx, w.slot_frame, nullptr, 0, 0, w.fb, w.stats, \
@@ -4098,12 +4205,29 @@ extern "C" int alive_knn_search_pool(const float* src, int N, int T, const void*
     else if (R <= 512) ALIVE_POOL_RESCORE(8);
     else ALIVE_POOL_RESCORE(16);
 #undef ALIVE_POOL_RESCORE
-    knn_pool_fallback_plan_kernel<<<1, 64, 0, s>>>(seg_len, k, w);
-    knn_pool_scan_kernel<<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, seg_lo, seg_len, k, w);
-    if (k <= 4) knn_pool_merge_kernel<true><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
-    else knn_pool_merge_kernel<false><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
-    ALIVE_CHECK_LAUNCH("alive_knn_search_pool");
+    knn_pool_fallback_plan_kernel<<<1, 64, 0, s>>>(seg_len, w);
+    knn_pool_scan_kernel<<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, seg_lo, seg_len, w);
+    if (k_row != nullptr) knn_pool_merge_kernel<MERGE_ROW><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
+    else if (k <= 4) knn_pool_merge_kernel<MERGE_K4><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
+    else knn_pool_merge_kernel<MERGE_GEN><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
+    ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
+}
+
+extern "C" int alive_knn_search_pool(const float* src, int N, int T, const void* images, const int64_t* img_off, const float* rows_f32,
+                                     const float* norms, const float* bounds, int64_t P, const int32_t* seg_lo, const int32_t* seg_len, int V,
+                                     int64_t max_len, const int32_t* voice, int k, float* out_val, int32_t* out_idx, void* ws, void* stream) {
+    return search_pool("alive_knn_search_pool", src, N, T, images, img_off, rows_f32, norms, bounds, P, seg_lo, seg_len, V, max_len, voice,
+                       nullptr, k, out_val, out_idx, ws, stream);
+}
+
+extern "C" int alive_knn_search_pool_k(const float* src, int N, int T, const void* images, const int64_t* img_off, const float* rows_f32,
+                                       const float* norms, const float* bounds, int64_t P, const int32_t* seg_lo, const int32_t* seg_len,
+                                       int V, int64_t max_len, const int32_t* voice, const int32_t* k_row, int k_max, float* out_val,
+                                       int32_t* out_idx, void* ws, void* stream) {
+    ALIVE_CHECK_ARG(k_row, "alive_knn_search_pool_k: null pointer");
+    return search_pool("alive_knn_search_pool_k", src, N, T, images, img_off, rows_f32, norms, bounds, P, seg_lo, seg_len, V, max_len, voice,
+                       k_row, k_max, out_val, out_idx, ws, stream);
 }
 
 // ---- reserved voice pool: append a voice in place, move segments (live enrolment) ----

@@ -81,12 +81,18 @@ PROTOTYPES = {
     "alive_knn_search_grouped": (_I, [_VP, _I, _I, _VP, _VP, _I64, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
     "alive_knn_merge_gather_rows": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP]),
     "alive_knn_blend_gather_rows": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
+    "alive_knn_grouped_k_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "alive_knn_search_grouped_k": (_I, [_VP, _I, _I, _VP, _VP, _I64, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "alive_knn_merge_gather_rows_k": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP]),
+    "alive_knn_blend_gather_rows_k": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
     "alive_pool_append": (_I, [_VP, _I64, _I64, _I64, _I, _VP, _VP, _I64, _I64, _VP, _VP]),
     "alive_pool_move_rows": (_I, [_VP, _VP, _I64, _I64, _I64, _I64, _VP]),
     "alive_pool_image_bytes": (_SZ, [_VP, _I, _VP]),
     "alive_pool_pack_images": (_I, [_VP, _VP, _I64, _VP, _VP, _I, _VP, _VP, _VP]),
     "alive_knn_pool_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I64, _I64]),
     "alive_knn_search_pool": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _I, _I64, _VP, _I, _VP, _VP, _VP, _VP]),
+    "alive_knn_pool_k_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I64, _I64]),
+    "alive_knn_search_pool_k": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _I, _I64, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
     "alive_knn_pool_stats": (_VP, [_VP]),
     "alive_dedup_pass": (_I, [_VP, _VP, _I64, _I, _D, _VP, _VP, _VP]),
     "alive_knn_merge_gather": (_I, [_VP, _VP, _I, _I, _D, _VP, _VP, _I, _I, _VP, _VP, _VP]),

@@ -1,7 +1,8 @@
 """Multi-session streaming: B live voices converted in one batched step per tick (realtime_inference.py:130-183 per slot).
 
-A `MultiStreamConverter` holds B session slots that share the chunk duration, the ring (buffersize) and k.  Each slot has its own
-target voice (a segment of a `VoicePool`), pitch shift, f0 rate, alpha, input / output gain, ring and oscillator phase, and -- with
+A `MultiStreamConverter` holds B session slots that share the chunk duration and the ring (buffersize).  Each slot has its own
+target voice (a segment of a `VoicePool`), pitch shift, f0 rate, alpha, input / output gain, ring and oscillator phase, -- in a
+converter built with k_max= -- its own k (see "Per-session k" below), and -- with
 `rates=` declared up front and input_sr == output_sr -- its own sample rate: a session at rate r sends and receives
 chunk * r / input_sr samples per tick, and its ring at 16 kHz has the converter's geometry (session_geometry), so only the two
 resampling edges differ per row (alive_resample_rows_multi: one launch, every row at its own rate pair).
@@ -30,6 +31,13 @@ Converter.convert_many and both CLIs).  A converter built with blend=S > 1 gives
 [B, 768, T] is replicated to [B*S, 768, T], the grouped search runs over the list rows' segments (unused rows at seg_len 0) and
 alive_knn_blend_gather_rows replaces merge_gather_rows, mixing each slot's list means with the device weights.  Blends, single
 voices and weights switch between ticks without a re-capture; blend=1 launches exactly the plain tick.
+
+Per-session k: a converter built with k_max=K (k <= K <= 8) keeps a device array k_rows [B] (a closed slot: the converter's k) and
+runs the per-row-k entry points (alive_knn_search_grouped_k, alive_knn_merge_gather_rows_k / alive_knn_blend_gather_rows_k, lists
+at stride K): open(..., k=) and set(slot, k=) write one word, so a change of k between ticks never re-captures, and a session at k
+comes out bitwise as in a converter whose uniform k is that k.  k is part of the search's group key: sessions on one voice at
+different k take one pass over the voice per k.  With blend=S the slot's k is repeated onto its S list rows for the search.
+k_max=None (the default) is the uniform converter, launch for launch.
 """
 import numpy as np
 import torch
@@ -582,6 +590,27 @@ def knn_search_grouped(source, rows, norms, seg_lo, seg_len, k):
     return val, idx
 
 
+def knn_search_grouped_k(source, rows, norms, seg_lo, seg_len, k_row, k_max):
+    """knn_search_grouped with a k per row: device int32 k_row [N], 1 <= k_row[n] <= k_max -> (val, idx) [N*T, k_max]; row n's
+    first k_row[n] entries per frame are bitwise knn_search_grouped at that k, the rest -inf / -1 (alive_knn_search_grouped_k)"""
+    n, d, t = source.shape
+    L = nat.lib()
+    if not 1 <= k_max <= MAX_K:
+        raise ValueError(f"grouped search: k_max={k_max} outside [1, {MAX_K}]")
+    if k_row.dtype != torch.int32 or k_row.numel() != n:
+        raise ValueError("grouped search: k_row must be int32 [N]")
+    nbytes = L.alive_knn_grouped_k_workspace_bytes(n, t, k_max)
+    if nbytes == 0:                                         # (before anything is allocated)
+        raise ValueError(f"grouped search: {n} rows x {t} frames (k_max={k_max}) out of range")
+    val = torch.empty(n * t, k_max, dtype=torch.float32, device=source.device)
+    idx = torch.empty(n * t, k_max, dtype=torch.int32, device=source.device)
+    ws = _ws.get(nbytes, source.device)
+    nat.check(L.alive_knn_search_grouped_k(nat.ptr(source), n, t, nat.ptr(rows), nat.ptr(norms), rows.shape[0], nat.ptr(seg_lo),
+                                           nat.ptr(seg_len), nat.ptr(k_row), k_max, nat.ptr(val), nat.ptr(idx), nat.ptr(ws),
+                                           nat.stream()), "alive_knn_search_grouped_k")
+    return val, idx
+
+
 def knn_pool_workspace_bytes(n, t, k, pool):
     im = pool.search_images()
     return nat.lib().alive_knn_pool_workspace_bytes(n, t, k, len(im["names"]), pool.P, im["max_len"])
@@ -613,6 +642,60 @@ def knn_search_pool(source, pool, voice_ids, k, stats=False):
         c = ws[:32].view(torch.int32).tolist()
         return val, idx, dict(frames_failed_certificate=c[0], frames_searched_exactly=c[1], voice_groups=c[2], frame_blocks=c[3])
     return val, idx
+
+
+def knn_search_pool_k(source, pool, voice_ids, k_row, k_max):
+    """knn_search_pool with a k per row: device int32 k_row [N], 1 <= k_row[n] <= k_max -> (val, idx) [N*T, k_max]; row n's first
+    k_row[n] entries per frame are bitwise knn_search_pool at that k, the rest -inf / -1 (alive_knn_search_pool_k)"""
+    n, d, t = source.shape
+    L = nat.lib()
+    if not 1 <= k_max <= MAX_K:
+        raise ValueError(f"pool search: k_max={k_max} outside [1, {MAX_K}]")
+    im = pool.search_images()
+    nbytes = L.alive_knn_pool_k_workspace_bytes(n, t, k_max, len(im["names"]), pool.P, im["max_len"])
+    if nbytes == 0:                                         # (before anything is allocated)
+        raise ValueError(f"pool search: {n} rows x {t} frames (k_max={k_max}) out of range")
+    if voice_ids.dtype != torch.int32 or voice_ids.numel() != n:
+        raise ValueError("pool search: voice_ids must be int32 [N]")
+    if k_row.dtype != torch.int32 or k_row.numel() != n:
+        raise ValueError("pool search: k_row must be int32 [N]")
+    source = source.contiguous()
+    val = torch.empty(n * t, k_max, dtype=torch.float32, device=source.device)
+    idx = torch.empty(n * t, k_max, dtype=torch.int32, device=source.device)
+    ws = _ws.get(nbytes, source.device)
+    nat.check(L.alive_knn_search_pool_k(nat.ptr(source), n, t, nat.ptr(im["images"]), nat.ptr(im["img_off"]), nat.ptr(pool.rows),
+                                        nat.ptr(pool.norms), nat.ptr(im["bounds"]), pool.P, nat.ptr(im["seg_lo"]),
+                                        nat.ptr(im["seg_len"]), len(im["names"]), im["max_len"], nat.ptr(voice_ids), nat.ptr(k_row),
+                                        k_max, nat.ptr(val), nat.ptr(idx), nat.ptr(ws), nat.stream()), "alive_knn_search_pool_k")
+    return val, idx
+
+
+def merge_gather_rows_k(val, idx, k_row, k_max, alpha, rows, source):
+    """merge_gather_rows with a k per row (device int32 k_row [N]); val / idx [N*T, k_max] from a per-row-k search"""
+    n, d, t = source.shape
+    out = torch.empty_like(source)
+    nat.check(nat.lib().alive_knn_merge_gather_rows_k(nat.ptr(val), nat.ptr(idx), nat.ptr(k_row), k_max, nat.ptr(alpha), nat.ptr(rows),
+                                                      nat.ptr(source), n, t, nat.ptr(out), None, nat.stream()),
+              "alive_knn_merge_gather_rows_k")
+    return out
+
+
+def blend_gather_rows_k(val, idx, k_row, k_max, first, weight, alpha, rows, source):
+    """blend_gather_rows with a k per OUTPUT row (device int32 k_row [N]): every list of a blend uses its owner's k; val / idx
+    [first[N] * T, k_max] from a per-row-k search whose k_row repeats the owner's k on each of its list rows"""
+    n, d, t = source.shape
+    out = torch.empty_like(source)
+    nat.check(nat.lib().alive_knn_blend_gather_rows_k(nat.ptr(val), nat.ptr(idx), nat.ptr(k_row), k_max, nat.ptr(first),
+                                                      nat.ptr(weight), nat.ptr(alpha), nat.ptr(rows), nat.ptr(source), n, t,
+                                                      nat.ptr(out), nat.stream()), "alive_knn_blend_gather_rows_k")
+    return out
+
+
+def check_k(k, what="k", hi=MAX_K):
+    """a k of the batched paths: an int (not a bool) in [1, hi] -> int; ValueError otherwise"""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= hi:
+        raise ValueError(f"{what}={k!r}: expected an integer in [1, {hi}]")
+    return int(k)
 
 
 def merge_gather_rows(val, idx, k, alpha, rows, source):
@@ -753,14 +836,18 @@ def db_scale(db):
     return float(10 ** (db / 20)) if db != 0 else 1.0
 
 
-_PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch")
+_PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k")
 
 
 class MultiStreamConverter:
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
-                 output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1):
+                 output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None):
         if not 1 <= int(k) <= MAX_K:
             raise ValueError(f"MultiStreamConverter: k={k} outside [1, {MAX_K}] (the grouped search keeps k <= 8)")
+        if k_max is not None:
+            k_max = check_k(k_max, "MultiStreamConverter: k_max")
+            if k_max < int(k):
+                raise ValueError(f"MultiStreamConverter: k_max={k_max} is below the converter's k={int(k)}")
         if int(slots) < 1 or int(slots) > MAX_ROWS:
             raise ValueError(f"MultiStreamConverter: slots={slots} outside [1, {MAX_ROWS}]")
         if isinstance(blend, (bool, np.bool_)) or not isinstance(blend, (int, np.integer)) or not 1 <= blend <= MAX_BLEND:
@@ -779,6 +866,7 @@ class MultiStreamConverter:
         self.ce, self.pe, self.dec = prepare_networks(content_encoder, f0_estimator, decoder, device)
         self.pool = pool
         self.B, self.k = int(slots), int(k)
+        self.k_max = k_max                 # None: every session at k (the uniform entry points); K: sessions at their own k <= K
         # a reserved pool (VoicePool(capacity=...)): the slots hold their voices, and the tick follows the pool's layout
         self._reserved = getattr(pool, "capacity", None) is not None
         self._label = f"MultiStreamConverter(slots={self.B}) at {id(self):#x}"
@@ -827,6 +915,9 @@ class MultiStreamConverter:
         if self.S > 1:
             self.first = torch.arange(0, B * self.S + 1, self.S, dtype=torch.int32, device=dev)
             self.weight = torch.zeros(B * self.S, dtype=torch.float64, device=dev)
+        if self.k_max is not None:         # the slot's k, and (blend) the same on each of its list rows for the search
+            self.k_rows = torch.full((B,), self.k, dtype=torch.int32, device=dev)
+            self.k_lists = self.k_rows if self.S == 1 else torch.full((B * self.S,), self.k, dtype=torch.int32, device=dev)
         self.alpha = torch.zeros(B, dtype=torch.float64, device=dev)
         self.f0_rate = torch.ones(B, dtype=torch.float32, device=dev)
         self.pitch = torch.zeros(B, dtype=torch.float32, device=dev)
@@ -860,8 +951,23 @@ class MultiStreamConverter:
             raise ValueError(f"slot {slot!r} out of range [0, {self.B})")
         return int(slot)
 
+    def _session_k(self, slot, k):
+        """a session's k (None: the converter's) against the converter's k_max"""
+        if k is None:
+            return self.k
+        if self.k_max is None:
+            if isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_)) and int(k) == self.k:
+                return self.k
+            raise ValueError(f"slot {slot}: k={k!r} differs from the converter's k={self.k}: a per-session k needs a converter built "
+                             "with MultiStreamConverter(..., k_max=K), k <= K <= 8")
+        k = check_k(k, f"slot {slot}: k")
+        if k > self.k_max:
+            raise ValueError(f"slot {slot}: k={k} is above the converter's k_max={self.k_max}")
+        return k
+
     def _apply(self, slot, p):
-        names, weights = blend_spec(p["voice"], self.pool, self.k, self.S)
+        k = self._session_k(slot, p["k"])
+        names, weights = blend_spec(p["voice"], self.pool, k, self.S)
         world = p["world_pitch"]
         if not isinstance(world, (bool, np.bool_)):
             raise ValueError(f"slot {slot}: world_pitch must be a bool, got {world!r}")
@@ -872,6 +978,10 @@ class MultiStreamConverter:
             rows = slice(slot * self.S, (slot + 1) * self.S)
             self.weight[rows] = torch.tensor(list(weights) + [0.0] * (self.S - len(names)), dtype=torch.float64)
         self._hold(slot, names)
+        if self.k_max is not None:
+            self.k_rows[slot] = k
+            if self.S > 1:
+                self.k_lists[slot * self.S:(slot + 1) * self.S] = k
         self.alpha[slot] = float(p["alpha"])
         self.f0_rate[slot] = float(p["f0_rate"])
         self.pitch[slot] = float(p["pitch"])
@@ -935,8 +1045,9 @@ class MultiStreamConverter:
         self.pair_out[slot] = self._rt.pair(16000, rate)
         self.len_out[slot] = self._lout[rate]
 
-    def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False):
-        """start a session in `slot`: empty ring, phase 0.  `rate` (default: the converter's input_sr) is one of the declared
+    def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None):
+        """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
+        a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
         WORLD's f0 of the session's ring instead of the estimator's, f0_rate not applied (needs a world_pitch=True converter)"""
         slot = self._slot(slot)
@@ -944,7 +1055,8 @@ class MultiStreamConverter:
         if rate not in self.rates:
             raise ValueError(f"slot {slot}: rate {rate} Hz was not declared (rates={list(self.rates)}): pass it in "
                              "MultiStreamConverter(..., rates=...)")
-        p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch)
+        p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch,
+                 k=k)
         self._apply(slot, p)                                  # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -955,7 +1067,7 @@ class MultiStreamConverter:
         return self
 
     def set(self, slot, **params):
-        """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch)"""
+        """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k)"""
         slot = self._slot(slot)
         if not self.is_open[slot]:
             raise ValueError(f"slot {slot} is not open")
@@ -976,6 +1088,10 @@ class MultiStreamConverter:
         self.count[slot] = 0
         self.ring[slot] = 0
         self.seg_len[slot * self.S:(slot + 1) * self.S] = 0
+        if self.k_max is not None:                           # (the slot stays inactive: its segments are empty)
+            self.k_rows[slot] = self.k
+            if self.S > 1:
+                self.k_lists[slot * self.S:(slot + 1) * self.S] = self.k
         self._hold(slot, ())
         self.phi[slot] = 0.0
         if self.world_pitch:
@@ -1006,14 +1122,24 @@ class MultiStreamConverter:
         spec = spectrogram(data)
         f0, join = self._f0_on_side_stream(spec, data)
         content = self.ce(spec)
+        K = self.k_max
         if self.S == 1:
-            val, idx = knn_search_grouped(content, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k)
-            content = merge_gather_rows(val, idx, self.k, self.alpha, self.pool.rows, content)
+            if K is None:
+                val, idx = knn_search_grouped(content, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k)
+                content = merge_gather_rows(val, idx, self.k, self.alpha, self.pool.rows, content)
+            else:                                             # every session at its own k (device array k_rows)
+                val, idx = knn_search_grouped_k(content, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k_rows, K)
+                content = merge_gather_rows_k(val, idx, self.k_rows, K, self.alpha, self.pool.rows, content)
         else:                                                 # every slot's content once per list row, then the blend
             b, d, t = content.shape
             rep = content.unsqueeze(1).expand(b, self.S, d, t).reshape(b * self.S, d, t).contiguous()     # (B = 1: a view)
-            val, idx = knn_search_grouped(rep, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k)
-            content = blend_gather_rows(val, idx, self.k, self.first, self.weight, self.alpha, self.pool.rows, content)
+            if K is None:
+                val, idx = knn_search_grouped(rep, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k)
+                content = blend_gather_rows(val, idx, self.k, self.first, self.weight, self.alpha, self.pool.rows, content)
+            else:
+                val, idx = knn_search_grouped_k(rep, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k_lists, K)
+                content = blend_gather_rows_k(val, idx, self.k_rows, K, self.first, self.weight, self.alpha, self.pool.rows,
+                                              content)
         join()
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0

@@ -385,13 +385,23 @@ class Converter:
         voices[i] may also be a blend ({name: weight} or (name, weight) pairs, multistream.blend_spec): then every window of the
         corpus gets one list row per voice of its utterance's blend, the pool search runs over those rows (in pieces within its
         limits, bitwise one call) and the blend gather mixes each window's lists (alive_knn_blend_gather_rows).  A corpus without a
-        blend of two or more voices launches the plain path."""
+        blend of two or more voices launches the plain path.
+        k may be a list with one value per utterance (1 <= k_i <= 8; every voice of utterance i needs at least k_i vectors): the
+        match then runs the per-row-k entry points at k_max = max(k) (alive_knn_search_pool_k, alive_knn_merge_gather_rows_k /
+        alive_knn_blend_gather_rows_k; the pool search groups its rows by voice and k), and utterance i is bitwise `convert` alone
+        at k_i.  A scalar k launches the uniform path."""
         from . import multistream as MS
         m = len(utterances)
         voices = list(voices)
         if len(voices) != m:
             raise ValueError(f"{m} utterances but {len(voices)} voices")
-        if not 1 <= k <= MS.MAX_K:
+        ks = None                           # per-utterance k: a list; a scalar takes the uniform entry points
+        if isinstance(k, (list, tuple)):
+            if len(k) != m:
+                raise ValueError(f"k: {len(k)} values for {m} utterances")
+            ks = [MS.check_k(v, f"convert_many: k[{i}]") for i, v in enumerate(k)]
+            k = max(ks)                     # k_max: the stride of the lists
+        elif not 1 <= k <= MS.MAX_K:
             raise ValueError(f"convert_many: k={k} outside [1, {MS.MAX_K}]")
 
         def per(x, what):
@@ -406,7 +416,7 @@ class Converter:
             raise ValueError(f"world_pitch: {len(worlds)} values for {m} utterances")
         if not all(isinstance(w, (bool, np.bool_)) for w in worlds):
             raise ValueError(f"world_pitch: expected bools, got {worlds}")
-        specs = [MS.blend_spec(v, pool, k) for v in voices]
+        specs = [MS.blend_spec(v, pool, k if ks is None else ks[i]) for i, v in enumerate(voices)]
         blended = any(len(names) > 1 for names, _ in specs)
         wins, totals, counts = [], [], []
         for u in utterances:
@@ -422,6 +432,8 @@ class Converter:
             return torch.repeat_interleave(torch.tensor(vals, dtype=dtype, device=self.device), rep).contiguous()
         params = dict(alpha=rows(alphas, torch.float64), shift=rows(shifts, torch.float32), inton=rows(inton, torch.float32),
                       rate=rows(rates, torch.float32))
+        if ks is not None:                  # each window's k; the blended search repeats it on the window's list rows (below)
+            params["k"] = rows(ks, torch.int32)
         if not blended:                     # (one-voice blends are their voice: weight 1.0)
             params["ids"] = torch.repeat_interleave(pool.voice_ids([names[0] for names, _ in specs]), rep).contiguous()
         else:                               # compact list rows: window w of utterance i owns S_i of them, in blend order
@@ -437,6 +449,8 @@ class Converter:
             params.update(owner=torch.tensor(owner, dtype=torch.int64, device=self.device), ids=pool.voice_ids(lnames),
                           first=torch.tensor(first, dtype=torch.int32, device=self.device),
                           weight=torch.tensor(lweights, dtype=torch.float64, device=self.device))
+            if ks is not None:
+                params["k_lists"] = params["k"].index_select(0, params["owner"]).contiguous()
         # the WORLD windows of every window batch (batch-local row indices, on the device before the batches start)
         on = [bool(w) for w, c in zip(worlds, counts) for _ in range(c)]
         params["world"] = {i: torch.tensor([j - i for j in range(i, min(i + window_batch, len(on))) if on[j]], dtype=torch.int64,
@@ -461,15 +475,25 @@ class Converter:
         def match(feat):
             src = feat if rng is None else feat[:, :, rng[0]:rng[1]].contiguous()
             if not blended:
-                val, idx = MS.knn_search_pool(src, pool, params["ids"], k)
-                return MS.merge_gather_rows(val, idx, k, params["alpha"], pool.rows, src)
+                if ks is None:
+                    val, idx = MS.knn_search_pool(src, pool, params["ids"], k)
+                    return MS.merge_gather_rows(val, idx, k, params["alpha"], pool.rows, src)
+                val, idx = MS.knn_search_pool_k(src, pool, params["ids"], params["k"], k)
+                return MS.merge_gather_rows_k(val, idx, params["k"], k, params["alpha"], pool.rows, src)
             src_v = src.index_select(0, params["owner"])
             R, _, t = src_v.shape
             step = max(1, min(MS.POOL_PIECE_ROWS, MS.POOL_PIECE_FRAMES // t))
-            pieces = [MS.knn_search_pool(src_v[a:a + step], pool, params["ids"][a:a + step], k) for a in range(0, R, step)]
+            if ks is None:
+                pieces = [MS.knn_search_pool(src_v[a:a + step], pool, params["ids"][a:a + step], k) for a in range(0, R, step)]
+            else:
+                pieces = [MS.knn_search_pool_k(src_v[a:a + step], pool, params["ids"][a:a + step],
+                                               params["k_lists"][a:a + step].contiguous(), k) for a in range(0, R, step)]
             val = pieces[0][0] if len(pieces) == 1 else torch.cat([p[0] for p in pieces])
             idx = pieces[0][1] if len(pieces) == 1 else torch.cat([p[1] for p in pieces])
-            return MS.blend_gather_rows(val, idx, k, params["first"], params["weight"], params["alpha"], pool.rows, src)
+            if ks is None:
+                return MS.blend_gather_rows(val, idx, k, params["first"], params["weight"], params["alpha"], pool.rows, src)
+            return MS.blend_gather_rows_k(val, idx, params["k"], k, params["first"], params["weight"], params["alpha"], pool.rows,
+                                          src)
         out = ops.Fp16Guard(self._agree_on_saturations()).run(
             lambda: self._convert_per_window(windows, rng, window_batch, encode, match, transform))
         res, i = [], 0

@@ -7,6 +7,7 @@ The sessions file is a JSON list; each entry:
    "pitch": 0, "f0_rate": 1, "alpha": 0, "gain": 0, "input_gain": 0,     optional, realtime_inference.py's meanings
    "world_pitch": false,                  optional, a JSON bool: realtime_inference.py's -wpe (WORLD's f0 of the ring; its
                                           f0_rate is then not applied, as there)
+   "k": 4,                                optional, an integer in 1..8: the session's own k (default: -k)
    "blend": [{"target": "a.wav", "weight": 2}, {"lib": "b.pt", "weight": 1}],   instead of "target" / "lib": a weighted mix
                                           of 1 to 4 voices, each component a voice source as above (multistream.blend_spec)
    "start": 0,                            optional: the tick at which the session joins
@@ -19,6 +20,8 @@ with the converter's 16 kHz geometry: module/multistream.py session_geometry), a
 The converter carries the WORLD branch only if some session asks for "world_pitch": a sessions file without it runs as before.
 It is built with blend = the most components of any session's "blend" (1 without one: a file without blends runs as before);
 sessions and blend components naming the same voice sources share one voice of the pool.
+It is built with k_max = the largest "k" only if some session's "k" differs from -k (converter_k_max): a file without "k" runs as
+before.  Sessions on one voice at different k take one pass over that voice per k.
 WORLD needs rings of about 230 ms or more (-c 960 -b 8 is 480 ms): a shorter ring comes out unvoiced.
 Flags shared with realtime_inference.py keep its spelling: -c, -b, -k, -isr, -osr, --no-graph.
 
@@ -43,12 +46,12 @@ from module import audio_io                                     # noqa: E402
 from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
-from module.multistream import MultiStreamConverter, VoicePool, blend_sources, enrol_voice   # noqa: E402
+from module.multistream import MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice   # noqa: E402
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
 SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "start", "sr", "output",
-                "blend")
+                "blend", "k")
 
 
 def build_parser():
@@ -73,8 +76,10 @@ def build_parser():
     return parser
 
 
-def load_sessions(path):
-    """the sessions file -> list of dicts with every key filled in; ValueError on a malformed entry"""
+def load_sessions(path, k=4):
+    """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`); ValueError on a
+    malformed entry"""
+    k = check_k(k, "-k")
     with open(path) as f:
         sessions = json.load(f)
     if not isinstance(sessions, list) or not sessions:
@@ -93,10 +98,11 @@ def load_sessions(path):
             raise ValueError(f"session {i}: needs a \"target\" wav or a \"lib\" voice library")
         if not isinstance(s.get("world_pitch", False), bool):
             raise ValueError(f"session {i}: \"world_pitch\" must be true or false, got {s['world_pitch']!r}")
+        sess_k = check_k(s["k"], f"session {i}: \"k\"") if "k" in s else k
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
                  gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
-                 sr=None if s.get("sr") is None else int(s["sr"]), world_pitch=s.get("world_pitch", False), blend=blend)
+                 sr=None if s.get("sr") is None else int(s["sr"]), world_pitch=s.get("world_pitch", False), blend=blend, k=sess_k)
         if e["start"] < 0:
             raise ValueError(f"session {i}: start tick {e['start']} < 0")
         if e["sr"] is not None and e["sr"] <= 0:
@@ -120,6 +126,13 @@ def session_voice(s):
 def blend_size(sessions):
     """the converter's blend: the most components of any session's blend, 1 for a file without blends"""
     return max([len(s["blend"]) for s in sessions if s.get("blend")] or [1])
+
+
+def converter_k_max(sessions, k):
+    """MultiStreamConverter's k_max: None (the uniform converter, as before) unless some session's k differs from the default
+    `k`; then the largest k in use, the default included"""
+    ks = [s.get("k", k) for s in sessions]
+    return None if all(v == k for v in ks) else max(ks + [k])
 
 
 def session_sources(s):
@@ -212,7 +225,7 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    sessions = load_sessions(args.sessions)
+    sessions = load_sessions(args.sessions, args.k)
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -234,9 +247,11 @@ def main(argv=None):
     out_sr = [s["sr"] or args.output_sr for s in sessions]
     conv = MultiStreamConverter(CE, PE, Dec, pool, slots, chunk=args.chunk, buffersize=args.buffersize, input_sr=args.input_sr,
                                 output_sr=args.output_sr, k=args.k, device=device, rates=sorted(set(in_sr)),
-                                world_pitch=any(s["world_pitch"] for s in sessions), blend=blend_size(sessions))
+                                world_pitch=any(s["world_pitch"] for s in sessions), blend=blend_size(sessions),
+                                k_max=converter_k_max(sessions, args.k))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
-                   input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"]) for n, s, r in zip(names, sessions, in_sr)]
+                   input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"])
+              for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()
     pcms = [input_pcm(s["input"], r, device) for s, r in zip(sessions, in_sr)]

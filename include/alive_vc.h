@@ -263,6 +263,33 @@ int alive_knn_blend_gather_rows(const float* cand_val, const int32_t* cand_idx, 
                                 const double* weight, const double* alpha, const float* rows_f32_full, const float* src,
                                 int N, int T, float* out, void* stream);
 
+/* ---------------------------------------------- per-row k (a k per session / utterance in the batched paths) ----
+ * The four calls above with a k per row: k_row (DEVICE int32[N], read when the kernels run) in place of the scalar, 1 <= k_row[n]
+ * <= k_max <= 8.  Every grid and the workspace are sized from N, T and k_max alone, so a captured hipGraph may replay them after
+ * k_row changed.  Lists are [N*T][k_max] (read and written at stride k_max).
+ * alive_knn_search_grouped_k: for row n the first k_row[n] entries of each frame are bitwise what alive_knn_search_grouped returns
+ *   for that row at k = k_row[n], whatever the other rows use; the rest are val -inf, idx -1.  A row is inactive (every entry
+ *   -inf / -1) when k_row[n] lies outside [1, k_max], or under alive_knn_search_grouped's rules with the row's own k: a segment
+ *   shorter than k_row[n] (one shorter than k_max but not than k_row[n] is searched).  k is part of the group key: rows that search
+ *   the same segment AT THE SAME k share one pass over it, so two rows on one segment at different k take two passes.  With
+ *   k_row[n] == k_max for every n the call is bitwise alive_knn_search_grouped at k = k_max.  N <= 1024, N * T <= 2^20.
+ *   ws: alive_knn_grouped_k_workspace_bytes(N, T, k_max) bytes (0: arguments out of range).
+ * alive_knn_merge_gather_rows_k: alive_knn_merge_gather_rows with the mean (r_0 + ... + r_(k-1)) / (float)k over k = k_row[n] of
+ *   row n (same order, bitwise the scalar form at that k); final_idx [N*T][k_max] (may be NULL), -1 behind a row's k.  A row
+ *   whose k_row[n] lies outside [1, k_max] is passed through (out = src), like a frame whose list starts with idx -1.
+ * alive_knn_blend_gather_rows_k: alive_knn_blend_gather_rows with k_row per OUTPUT row (int32[N]): every list of a blend uses
+ *   its owner's k, so the search's k_row repeats it on each of the row's list rows. */
+size_t alive_knn_grouped_k_workspace_bytes(int N, int T, int k_max);
+int alive_knn_search_grouped_k(const float* src, int N, int T, const float* rows_f32, const float* norms, int64_t P,
+                               const int32_t* seg_lo, const int32_t* seg_len, const int32_t* k_row, int k_max, float* out_val,
+                               int32_t* out_idx, void* ws, void* stream);
+int alive_knn_merge_gather_rows_k(const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k_max,
+                                  const double* alpha, const float* rows_f32_full, const float* src, int N, int T, float* out,
+                                  int32_t* final_idx, void* stream);
+int alive_knn_blend_gather_rows_k(const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k_max,
+                                  const int32_t* first, const double* weight, const double* alpha, const float* rows_f32_full,
+                                  const float* src, int N, int T, float* out, void* stream);
+
 /* ---------------------------------------------- reserved voice pool (live enrolment) ----
  * A table rows_f32[capacity][768] / norms[capacity] that is allocated once and never replaced, so that a captured hipGraph whose
  * launches hold its two pointers and its row count keeps serving while voices come, grow, move and go.  Both calls run on
@@ -309,6 +336,20 @@ int alive_knn_search_pool(const float* src, int N, int T, const void* images, co
                           const float* norms, const float* bounds, int64_t P, const int32_t* seg_lo, const int32_t* seg_len,
                           int V, int64_t max_len, const int32_t* voice, int k, float* out_val, int32_t* out_idx, void* ws,
                           void* stream);
+/* alive_knn_search_pool_k: alive_knn_search_pool with a k per row (k_row: DEVICE int32[N], 1 <= k_row[n] <= k_max <= 8, read when
+ *   the kernels run).  out_val / out_idx [N*T][k_max]: the first k_row[n] entries of each frame of row n are bitwise
+ *   alive_knn_search_pool at k = k_row[n], the rest val -inf, idx -1; a row is inactive when k_row[n] lies outside [1, k_max] or its
+ *   voice is -1, outside the table or shorter than k_row[n] (a voice shorter than k_max but not than the row's k is searched).  The
+ *   plan sorts the rows by (voice, k): every 256-frame block has one voice and one k, the candidate stage does not depend on k, and
+ *   the rescoring, the certificate (the k-th exact cosine) and the exact scan take the block's k -- a voice searched at two values of
+ *   k forms two groups of blocks.  Grids and workspace from N, T, k_max and the pool's dimensions.  With k_row[n] == k_max for every
+ *   n the call is bitwise alive_knn_search_pool at k = k_max.
+ *   ws: alive_knn_pool_k_workspace_bytes(N, T, k_max, V, P, max_len) bytes (room for min(N, k_max V) groups; 0: out of range). */
+size_t alive_knn_pool_k_workspace_bytes(int N, int T, int k_max, int V, int64_t P, int64_t max_len);
+int alive_knn_search_pool_k(const float* src, int N, int T, const void* images, const int64_t* img_off, const float* rows_f32,
+                            const float* norms, const float* bounds, int64_t P, const int32_t* seg_lo, const int32_t* seg_len,
+                            int V, int64_t max_len, const int32_t* voice, const int32_t* k_row, int k_max, float* out_val,
+                            int32_t* out_idx, void* ws, void* stream);
 const int* alive_knn_pool_stats(void* ws);
 
 /* alive_dedup_pass: one pass of the greedy de-duplication of a library (generate_voice_library.py of this build, --dedup):

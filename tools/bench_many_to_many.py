@@ -13,7 +13,10 @@ End to end at V = 64, M = 50 000: convert_many of the 64 utterances against 64 s
 voice's strict PackedLibrary, packed beforehand), trim_context on (the CLI default).  --world 0,0.5,1 also times convert_many with
 that fraction of the utterances on WORLD pitch (spread evenly: utterance u is on WORLD when floor((u + 1) f) > floor(u f)) and
 records world_<f>_ms; --blend S also times convert_many with every utterance blending S voices (utterance u: voices u, u + 1, ...
-mod 64, weights 1, 2, ...) and records blend_<S>_ms; --no-search skips the search table.
+mod 64, weights 1, 2, ...) and records blend_<S>_ms; --mixed-k also times convert_many with a k per utterance (the per-row-k entry points): every utterance at
+k = 4 (k_list_uniform4_ms, next to convert_many_ms: the same corpus through the uniform entry points), an even mix of k = 1, 2, 4, 8
+on the 64 distinct voices (k_list_mixed_ms) and the same mix with all utterances on ONE voice (k_list_mixed_one_voice_ms, next to
+one_voice_ms at k = 4: the pool search then runs one group of frame blocks per k); --no-search skips the search table.
 """
 import argparse
 import json
@@ -53,6 +56,7 @@ def main():
     ap.add_argument("--out", default=None, help="also write the results as JSON to this file")
     ap.add_argument("--world", default=None, help="comma-separated fractions of the utterances on WORLD pitch (end to end)")
     ap.add_argument("--blend", type=int, default=0, help="also time convert_many with every utterance blending this many voices")
+    ap.add_argument("--mixed-k", action="store_true", help="also time convert_many with a k per utterance (uniform 4; 1, 2, 4, 8)")
     ap.add_argument("--no-search", action="store_true", help="skip the search table (end to end only)")
     ap.add_argument("--commit", default="", help="source commit to record (default: git rev-parse HEAD, when there is a .git)")
     args = ap.parse_args()
@@ -121,6 +125,16 @@ def main():
         t_b = timed(lambda: conv.convert_many(utts, pool, blends, chunk=CHUNK, k=K, trim_context=True), args.reps)
         res["end_to_end"][f"blend_{S}_ms"] = round(t_b, 2)
         res["end_to_end"][f"blend_{S}_over_plain"] = round(t_b / t_many, 3)
+    if args.mixed_k:
+        mix = [(1, 2, 4, 8)[u % 4] for u in range(N_UTT)]
+        kw = dict(chunk=CHUNK, trim_context=True)
+        e = res["end_to_end"]
+        e["k_list_uniform4_ms"] = round(timed(lambda: conv.convert_many(utts, pool, names, k=[K] * N_UTT, **kw), args.reps), 2)
+        e["k_list_mixed_ms"] = round(timed(lambda: conv.convert_many(utts, pool, names, k=mix, **kw), args.reps), 2)
+        one = ["v0"] * N_UTT
+        e["one_voice_ms"] = round(timed(lambda: conv.convert_many(utts, pool, one, k=K, **kw), args.reps), 2)
+        e["k_list_mixed_one_voice_ms"] = round(timed(lambda: conv.convert_many(utts, pool, one, k=mix, **kw), args.reps), 2)
+        e["k_list_uniform4_over_scalar"] = round(e["k_list_uniform4_ms"] / t_many, 3)
     print(json.dumps(res["end_to_end"]), flush=True)
     if args.out:
         with open(args.out, "w") as f:

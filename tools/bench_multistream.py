@@ -10,7 +10,9 @@ the same batch per WORLD setting (world_<setting>_tick_p50_ms / _p99_ms): "off" 
 world_pitch=True converter with sessions s < round(f B) on WORLD (0: the masked branch with every row off).  --blend adds the graph
 tick p50 / p99 of voice blending: blend3_single_* a blend=3 converter whose sessions are single voices, blend2_* / blend3_* every
 session blending 2 / 3 voices (session s: voices s, s + 1, s + 2, weights 1, 2, 3) in a converter of that blend; distinct voices
-only.  --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
+only.  --mixed-k adds the graph tick p50 / p99 of the per-session k (MultiStreamConverter(k_max=8), the per-row-k entry points):
+kmax8_uniform4_* every session at k = 4 through them (next to graph_tick_*: the same batch through the uniform entry points),
+kmax8_mixed_* session s at k = (1, 2, 4, 8)[s % 4] -- on the shared voice that is one pass over the voice per k.  --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
 one more 50 000-row voice added between two ticks, once on a default pool (the add re-packs the pool and the next tick
 re-captures) and once on a reserved pool of 65 x 50 000 rows (VoicePool(capacity=...): alive_pool_append into the table in
 place); per pool the wall time of the add (bracketed by device synchronisation; add_device_ms: events around it), the latency of
@@ -20,7 +22,7 @@ lowest voice is removed and `compact` slides the other 64 down by one voice (com
 python tools/bench_multistream.py --quick).  Prints one JSON line per configuration and writes the list to --out.
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
-                                      [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--out multistream.json]
+                                      [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--out multistream.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
 """
 import argparse
@@ -168,6 +170,8 @@ def main():
     ap.add_argument("--world", default=None, help="comma-separated WORLD settings: off, or the fraction of sessions on WORLD")
     ap.add_argument("--voices", default="shared,distinct", help="voice mixes to run: shared, distinct")
     ap.add_argument("--blend", action="store_true", help="also time voice blending (blend=3 single voices, 2- and 3-voice blends)")
+    ap.add_argument("--mixed-k", action="store_true", help="also time a k_max=8 converter: every session at k = 4, and an even "
+                                                           "mix of k = 1, 2, 4, 8")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
                                                          "default and on a reserved pool")
     ap.add_argument("--out", default=None)
@@ -238,6 +242,15 @@ def main():
                     rec[f"{name}_tick_p50_ms"], rec[f"{name}_tick_p99_ms"] = round(p50, 3), round(p99, 3)
                     rec[f"{name}_real_time"] = p99 < period_ms
                     del bc
+                for name, ks in ((("kmax8_uniform4", (4,)), ("kmax8_mixed", (1, 2, 4, 8))) if args.mixed_k else ()):
+                    kc = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, k_max=8)
+                    for s in range(B):
+                        kc.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, k=ks[s % len(ks)])
+                    kc.enable_graph()
+                    p50, p99 = time_ticks(kc, B, chunk, args.ticks, args.warmup + bs + 1, 300)
+                    rec[f"{name}_tick_p50_ms"], rec[f"{name}_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                    rec[f"{name}_real_time"] = p99 < period_ms
+                    del kc
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
                 rows.append(rec)
