@@ -12,6 +12,12 @@ The jobs file is a JSON list; each entry:
    "k": 4,                                                  optional, an integer in 1..8: this job's k (default: -k).  Jobs at
                                                             different k still share the one batched run (the pool search groups
                                                             its rows by voice and k); a jobs file without "k" runs as before
+   "auto_pitch": false,                                     optional, a JSON bool (default: --auto-pitch): the pitch shift follows
+                                                            the target voice's register (convert_many(auto_pitch=)): the voice's
+                                                            mean pitch minus this file's, measured on the device; "pitch" is then
+                                                            an offset on top.  A jobs file without it runs as before
+   "register_hz": 180,                                      optional: declares the register (mean f0 in Hz) of a voice given by
+                                                            "lib" alone; a "target" wav's register is measured when it is encoded
    "blend": [{"target": "a.wav", "weight": 2},              instead of "target" / "lib": a weighted mix of 1 to 4 voices, each
              {"lib": "b.pt", "weight": 1}],                 component a voice source as above (module/multistream.py blend_spec)
    "output": "a_out.wav"}                                   optional: default <outdir>/<index>_<input name>.wav
@@ -34,7 +40,7 @@ from module import audio_io                                     # noqa: E402
 from module.multistream import MAX_K, blend_sources, check_k     # noqa: E402
 
 JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "world_pitch", "output",
-            "blend", "k")
+            "blend", "k", "auto_pitch", "register_hz")
 
 
 def build_parser():
@@ -50,13 +56,39 @@ def build_parser():
     parser.add_argument('--window-batch', default=64, type=int, help="windows per device batch")
     parser.add_argument('--no-trim-context', action='store_true',
                         help="run the kNN match and the decoder over all three chunks of every window (same samples)")
+    parser.add_argument('--auto-pitch', action='store_true',
+                        help="jobs follow their target voice's register unless their \"auto_pitch\" says otherwise")
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV")
     return parser
 
 
-def load_jobs(path, k=4):
-    """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder); ValueError on a malformed
-    job, before anything runs on the device"""
+def register_hz_of(entry, where):
+    """an entry's "register_hz" (None without one): a number > 0, for a voice given by "lib" alone"""
+    hz = entry.get("register_hz")
+    if hz is None:
+        return None
+    if isinstance(hz, bool) or not isinstance(hz, (int, float)) or not 0 < hz < float("inf"):
+        raise ValueError(f"{where}: \"register_hz\" must be a number > 0, got {hz!r}")
+    if "blend" in entry or entry.get("target") is not None or entry.get("lib") is None:
+        raise ValueError(f"{where}: \"register_hz\" declares the register of a voice given by \"lib\" alone (a \"target\" wav's is "
+                         "measured; a blend's comes from its voices)")
+    return float(hz)
+
+
+def declared_registers(jobs):
+    """{voice key: Hz} of the jobs' "register_hz"; ValueError if two jobs declare different ones for one voice"""
+    out = {}
+    for i, j in enumerate(jobs):
+        if j.get("register_hz") is not None:
+            key = voice_key(j)
+            if out.setdefault(key, j["register_hz"]) != j["register_hz"]:
+                raise ValueError(f"job {i}: \"register_hz\" {j['register_hz']} but an earlier job gave this voice {out[key]}")
+    return out
+
+
+def load_jobs(path, k=4, auto_pitch=False):
+    """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder; "auto_pitch": default
+    `auto_pitch`); ValueError on a malformed job, before anything runs on the device"""
     if not 1 <= k <= MAX_K:
         raise ValueError(f"k={k} outside [1, {MAX_K}] (the pool search's limit)")
     with open(path) as f:
@@ -77,11 +109,14 @@ def load_jobs(path, k=4):
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
         if not isinstance(j.get("world_pitch", False), bool):
             raise ValueError(f"job {i}: \"world_pitch\" must be true or false, got {j['world_pitch']!r}")
+        if not isinstance(j.get("auto_pitch", False), bool):
+            raise ValueError(f"job {i}: \"auto_pitch\" must be true or false, got {j['auto_pitch']!r}")
         job_k = check_k(j["k"], f"job {i}: \"k\"") if "k" in j else k
         e = dict(input=rel(j["input"]), target=rel(j.get("target")), lib=rel(j.get("lib")), output=rel(j.get("output")),
                  pitch=float(j.get("pitch", 0.0)), intonation=float(j.get("intonation", 1.0)), f0_rate=float(j.get("f0_rate", 1.0)),
                  alpha=float(j.get("alpha", 0.0)), gain=float(j.get("gain", 1.0)), normalize=bool(j.get("normalize", False)),
-                 world_pitch=j.get("world_pitch", False), blend=blend, k=job_k)
+                 world_pitch=j.get("world_pitch", False), blend=blend, k=job_k,
+                 auto_pitch=j.get("auto_pitch", bool(auto_pitch)), register_hz=register_hz_of(j, f"job {i}"))
         for key in ("input", "target", "lib"):
             if e[key] is not None and not os.path.isfile(e[key]):
                 raise ValueError(f"job {i}: {key} {e[key]!r} does not exist")
@@ -136,12 +171,14 @@ def main(argv=None):
     device = torch.device(args.device)
     if device.type != "cuda":
         raise SystemExit("this build runs on the MI355X only: pass -d cuda")
-    jobs = load_jobs(args.jobs, args.k)
+    jobs = load_jobs(args.jobs, args.k, args.auto_pitch)
+    auto = any(j["auto_pitch"] for j in jobs)           # only then are the voices' registers measured or declared
+    declared = declared_registers(jobs) if auto else {}
     # (device work starts here)
     from module.content_encoder import ContentEncoder
     from module.decoder import Decoder
     from module.f0_estimator import F0Estimator
-    from module.multistream import VoicePool
+    from module.multistream import VoicePool, measure_register, pitch_hz
     from module.pipeline import Converter
     from module.spectrogram import spectrogram
     from module.voice_library import VoiceLibrary
@@ -152,7 +189,7 @@ def main(argv=None):
     Dec.load_state_dict(torch.load(args.decoder_path, map_location=device))
     os.makedirs(args.outputs, exist_ok=True)
 
-    voices = {}
+    voices, registers = {}, {}
     for key in (key for job in jobs for key in voice_keys(job)):        # inference.py:86-92 per distinct voice
         if key in voices:
             continue
@@ -163,14 +200,19 @@ def main(argv=None):
             wf = audio_io.resample(wf.to(device), sr, 16000)
             wf = wf / wf.abs().max()
             tgt = CE(spectrogram(wf[:1]))
+            if auto:                                                    # the voice's register, on the audio the encoder saw
+                registers[key] = measure_register(PE, wf[:1].contiguous())
         if lib is not None:
             VL = VoiceLibrary().to(device)
             VL.load_state_dict(torch.load(lib, map_location=device))
             tgt = torch.cat([tgt, VL.tokens], dim=2)
         voices[key] = tgt
+        if key in declared:
+            registers[key] = (pitch_hz(declared[key]), 1.0)
     check_job_voice_sizes(jobs, {k_: int(t.shape[2]) for k_, t in voices.items()})
     names = {key: f"voice{i}" for i, key in enumerate(voices)}
-    pool = VoicePool({names[key]: t for key, t in voices.items()}, device=device)
+    pool = VoicePool({names[key]: t for key, t in voices.items()}, device=device,
+                     registers={names[key]: r for key, r in registers.items()})
     print(f"{len(jobs)} jobs over {len(voices)} voices ({pool.P} vectors)")
 
     utts, rates = [], []
@@ -183,7 +225,8 @@ def main(argv=None):
     conv = Converter(CE, PE, Dec, device)
     outs = conv.convert_many(utts, pool, [job_voice(j, names) for j in jobs], pitch_shift=[j["pitch"] for j in jobs],
                              intonation=[j["intonation"] for j in jobs], f0_rate=[j["f0_rate"] for j in jobs],
-                             alpha=[j["alpha"] for j in jobs], world_pitch=[j["world_pitch"] for j in jobs], chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
+                             alpha=[j["alpha"] for j in jobs], world_pitch=[j["world_pitch"] for j in jobs],
+                             auto_pitch=[j["auto_pitch"] for j in jobs] if auto else False, chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)
     for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
         out = audio_io.resample(out, 16000, sr, post_gain_db=job["gain"]).cpu()

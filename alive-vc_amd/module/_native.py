@@ -155,6 +155,9 @@ PROTOTYPES = {
     "alive_decoder_forward_range": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP]),
     "alive_pitch_transform": (_I, [_VP, _I, _I, _I, _F, _F, _F, _VP]),
     "alive_pitch_transform_rows": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "alive_pitch_stats_groups": (_I, [_VP, _I, _I, _I, _I, _VP, _I, _VP, _VP]),
+    "alive_pitch_shift_groups": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "alive_pitch_follow_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP]),
     "alive_world_f0_frames": (_I, [_I, _I, _D]),
     "alive_world_f0_taps_count": (_I, [_I, _D, _D]),
     "alive_world_f0_taps": (_I, [_I, _D, _D, _VP]),

@@ -38,6 +38,18 @@ at stride K): open(..., k=) and set(slot, k=) write one word, so a change of k b
 comes out bitwise as in a converter whose uniform k is that k.  k is part of the search's group key: sessions on one voice at
 different k take one pass over the voice per k.  With blend=S the slot's k is repeated onto its S list rows for the search.
 k_max=None (the default) is the uniform converter, launch for launch.
+
+Auto pitch: a converter built with auto_pitch=True keeps, per slot, the target voice's register (`target`, from the pool's voice
+registers: VoicePool.register, a blend's weighted mean) and a running estimate of the SOURCE's register, reg_state [B, 2] = (S, W) in
+fp64 on the device: on every emitting tick alive_pitch_follow_rows, between the f0 and the transform on the f0 side stream, adds the
+ring's voiced pitch (after f0_rate, what the mode-1 transform forms) to S and the voiced count to W, both forgotten at `decay` per tick,
+and writes shift_eff = pitch + W / (W + prior) * (target - S / W) for the sessions opened or set with auto_pitch=True, `pitch` bit for
+bit for the others; the transform reads shift_eff.  `pitch` thus becomes an offset on top of the automatic shift, which grows smoothly
+from 0 as voiced speech arrives (no threshold, no jump).  decay = 2^(-tick / auto_pitch_half_life) (None: never forget) and prior =
+auto_pitch_prior seconds of voiced speech * 50 frames/s * buffersize (a frame stays in the ring for buffersize ticks and is counted
+every time); the defaults, 10 s and 0.5 s, are design choices, not tuned on data.  The state belongs to the session like phi: open and
+close zero it, set(voice=) rewrites the target only (the source has not changed), enable_graph and the bf16 repeat save and restore it.
+Everything is device arrays: toggling never re-captures, and a converter built without auto_pitch launches exactly what it did.
 """
 import numpy as np
 import torch
@@ -127,6 +139,13 @@ def blend_sources(entry, where, rel):
     except ValueError as e:
         raise ValueError(f"{where}: {e}") from None
     return out
+
+
+def pitch_hz(hz):
+    """the pitch 12 log2(hz / 440) - 9 of a frequency as the kernels form it (the quotient in float32, log2 in float64 rounded once to
+    float32, the rest in float32), as a host float"""
+    x = np.float32(hz) / np.float32(440.0)
+    return float(np.float32(12.0) * np.float32(np.log2(np.float64(x))) - np.float32(9.0))
 
 
 def _tokens_2d(tokens):
@@ -281,11 +300,18 @@ class VoicePool:
     event there; neither allocates table-sized memory nor waits for the device, except that `add` / `extend` read the two-word
     report back.  MultiStreamConverter makes the stream it replays the tick on wait for that event, so an operation issued between
     two ticks is ordered before the next tick whatever stream it ran on; `step` returns after its tick has completed (it copies
-    the PCM to the host), so an operation issued between two ticks never overtakes the tick before it either."""
+    the PCM to the host), so an operation issued between two ticks never overtakes the tick before it either.
 
-    def __init__(self, voices=None, device="cuda", capacity=None):
+    Registers (auto pitch): a voice may carry the register of its speaker as host floats (sum of voiced pitch, voiced frames) in the
+    unit of pitch_stats_groups; `register(name)` is their quotient, the mean pitch.  `add` sets it, `extend` merges by adding sums
+    and counts, `set_register` declares one (a voice without audio, such as a voice library); it goes with its voice -- `remove`
+    drops it with the voice, and no operation on the pool (re-packing, moves, compact, another voice's removal) loses or changes
+    the register of a voice that stays."""
+
+    def __init__(self, voices=None, device="cuda", capacity=None, registers=None):
         self.device = torch.device(device)
         self.segments = {}
+        self.registers = {}                    # name -> (sum of voiced pitch, voiced frames), host floats
         self.version = 0
         self.capacity = None
         self._images = None
@@ -299,7 +325,7 @@ class VoicePool:
             self.mutations = 0                 # every operation; `order` is the event recorded after the latest one
             self.order = None
             for name, tok in (voices or {}).items():
-                self.add(str(name), tok)
+                self.add(str(name), tok, (registers or {}).get(name))
             return
         self._tokens = {}
         self.rows = self.norms = None
@@ -308,8 +334,64 @@ class VoicePool:
             for name, tok in voices.items():
                 self._tokens[str(name)] = _tokens_2d(tok).to(self.device, torch.float32).contiguous()
             self._pack()
+            for name, reg in (registers or {}).items():
+                self.set_register(str(name), register=reg)
 
-    def add(self, name, tokens):
+    # ------------------------------------------------------------------ registers (auto pitch)
+    @staticmethod
+    def _check_register(name, register):
+        try:
+            s, c = (float(v) for v in register)
+        except (TypeError, ValueError):
+            raise ValueError(f"voice {name!r}: a register is (sum of voiced pitch, voiced frames), got {register!r}") from None
+        if not (np.isfinite(s) and np.isfinite(c) and c >= 0):
+            raise ValueError(f"voice {name!r}: a register needs a finite sum and a finite count >= 0, got {register!r}")
+        return s, c
+
+    def _merge_register(self, name, register):
+        """add a checked (sum, count) to the voice's register (None: nothing)"""
+        if register is not None:
+            s0, c0 = self.registers.get(name, (0.0, 0.0))
+            self.registers[name] = (s0 + register[0], c0 + register[1])
+
+    def set_register(self, name, hz=None, register=None):
+        """declare the voice's register: its mean f0 in Hz (stored as one voiced frame at pitch_hz(hz)), or a measured
+        (sum of voiced pitch, voiced frames) as pitch_stats_groups returns it; both None: the voice has none any more"""
+        self.segment(name)
+        if hz is not None and register is not None:
+            raise ValueError(f"voice {name!r}: set_register takes hz= or register=, not both")
+        if hz is not None:
+            if isinstance(hz, (bool, np.bool_)) or not isinstance(hz, (int, float, np.integer, np.floating)) or not (
+                    np.isfinite(hz) and hz > 0):
+                raise ValueError(f"voice {name!r}: register hz={hz!r} must be a finite number > 0")
+            register = (pitch_hz(hz), 1.0)
+        if register is None:
+            self.registers.pop(name, None)
+        else:
+            self.registers[name] = self._check_register(name, register)
+        return self
+
+    def register(self, name):
+        """the voice's mean pitch (12 log2(f0 / 440) - 9 averaged over its voiced frames, a float), or None if it carries none"""
+        self.segment(name)
+        s, c = self.registers.get(name, (0.0, 0.0))
+        return s / c if c > 0 else None
+
+    def blend_register(self, names, weights):
+        """the target register of a voice or blend (blend_spec's names and float64-normalised weights, in the caller's order): the
+        weighted mean of the voices' registers; ValueError naming the first voice that has none"""
+        total = 0.0
+        for n, w in zip(names, weights):
+            r = self.register(n)
+            if r is None:
+                raise ValueError(f"auto pitch: voice {n!r} has no register: enrol it with f0_estimator=, pass register= to add / "
+                                 "extend, or declare one with set_register")
+            total += w * r
+        return total
+
+    def add(self, name, tokens, register=None):
+        if register is not None:
+            register = self._check_register(name, register)
         if self.capacity is not None:
             parts, m = _token_parts(tokens)
             lo = self._alloc.add(str(name), m)                # first fit; raises (rows needed, free rows, largest hole) if none
@@ -318,10 +400,13 @@ class VoicePool:
             except Exception:
                 self._alloc.remove(str(name))
                 raise
+            self._merge_register(str(name), register)
             self._changed()
             return self
         self._tokens[str(name)] = _tokens_2d(tokens).to(self.device, torch.float32).contiguous()
         self._pack()
+        self.registers.pop(str(name), None)                   # (a voice added again under its name: the new speaker's)
+        self._merge_register(str(name), register)
         return self
 
     # ------------------------------------------------------------------ reserved pool
@@ -355,10 +440,12 @@ class VoicePool:
         nat.check(nat.lib().alive_pool_move_rows(nat.ptr(self.rows), nat.ptr(self.norms), self.P, src, dst, n, nat.stream()),
                   "alive_pool_move_rows")
 
-    def extend(self, name, tokens):
+    def extend(self, name, tokens, register=None):
         """append rows to a live voice (old rows first): in place when the hole behind it is large enough, else the voice moves to
-        the first hole that takes the old and the new rows together"""
+        the first hole that takes the old and the new rows together.  register: the new audio's (sum, count), added to the voice's"""
         self._reserved("extend")
+        if register is not None:
+            register = self._check_register(name, register)
         parts, extra = _token_parts(tokens)
         lo, n, new_lo = self._alloc.extend(name, extra)
         try:
@@ -368,12 +455,14 @@ class VoicePool:
             raise
         if new_lo != lo:
             self._move(lo, new_lo, n)                         # (two disjoint ranges: the new hole was free)
+        self._merge_register(name, register)
         self._changed()
         return self
 
     def remove(self, name):
         self._reserved("remove")
         self._alloc.remove(name)                              # raises while a converter holds the voice
+        self.registers.pop(name, None)
         self._changed()
         return self
 
@@ -492,18 +581,34 @@ class VoicePool:
         return torch.tensor(ids, dtype=torch.int32, device=self.device)
 
 
-def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="cuda"):
+def measure_register(f0_estimator, wf16, world_pitch=False):
+    """the register (sum of voiced pitch, voiced frames) of 16 kHz audio wf16 [1, L] on the device, as host floats: the f0 estimator's
+    f0 of its spectrogram (world_pitch: WORLD's f0 of the audio) through alive_pitch_stats_groups, one group, every frame.  One
+    host read: for enrolment, never inside a tick."""
+    def f0():
+        return compute_f0(wf16) if world_pitch else f0_estimator.estimate(spectrogram(wf16))
+    f = ops.Fp16Guard().run(f0)
+    first = torch.tensor([0, f.shape[0]], dtype=torch.int32, device=f.device)
+    s, c = pitch_stats_groups(f, first)[0].tolist()
+    return s, c
+
+
+def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="cuda", f0_estimator=None, world_pitch=False):
     """A voice's tokens as realtime_inference.py builds its library, as strided [768, m] parts and without a copy: the target
     utterance `wav` [channels, samples] at `sr` Hz -- resampled to 16 kHz, peak-normalised, first channel, content_encoder(
     spectrogram(.)), every `every`-th frame (a column-strided view of the encoder's output) -- then the tokens of `lib` (a voice
-    library file, or its tokens [1, 768, M] / [768, M]).  The encoder runs under ops.Fp16Guard, as generate_voice_library.py's."""
+    library file, or its tokens [1, 768, M] / [768, M]).  The encoder runs under ops.Fp16Guard, as generate_voice_library.py's.
+    f0_estimator= (auto pitch): returns (parts, register) instead, the register measured on the same 16 kHz audio the encoder saw
+    (measure_register; world_pitch: with WORLD's f0), None without a target wav.  Without it the call is what it was."""
     from .voice_library import VoiceLibrary
-    parts = []
+    parts, register = [], None
     if wav is not None:
         wf = audio_io.resample(wav.to(device), sr, 16000)
         wf = wf / wf.abs().max()
         feats = ops.Fp16Guard().run(lambda: content_encoder(spectrogram(wf[:1])))
         parts.append(feats[0][:, ::every])
+        if f0_estimator is not None:
+            register = measure_register(f0_estimator, wf[:1].contiguous(), world_pitch)
     if lib is not None:
         if isinstance(lib, (str, bytes)) or hasattr(lib, "__fspath__"):
             VL = VoiceLibrary().to(device)
@@ -512,18 +617,24 @@ def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="c
         parts.append(_tokens_2d(lib))
     if not parts:
         raise ValueError("a voice needs a target wav and / or a voice library")
-    return parts
+    return parts if f0_estimator is None else (parts, register)
 
 
-def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False):
+def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False, f0_estimator=None,
+                world_pitch=False):
     """enrol_voice as a generator: the utterance is encoded once, then each next() appends one piece -- `add` for the first, `extend`
     for the rest -- and yields the voice's row count so far, so that a server can put a tick between the pieces.  If a piece is
-    refused the voice is removed again (when no session holds it yet) and the error propagates."""
+    refused the voice is removed again (when no session holds it yet) and the error propagates.  f0_estimator=: the utterance's
+    register is measured too (voice_parts) and stored with the first piece."""
     if pool.capacity is None:
         raise ValueError("enrol_voice needs a reserved pool: VoicePool(..., capacity=ROWS)")
     if max_frames is not None and int(max_frames) < 1:
         raise ValueError(f"max_frames={max_frames!r} must be >= 1")
-    parts = voice_parts(content_encoder, wav, sr, lib, every, pool.device)
+    register = None
+    if f0_estimator is None:
+        parts = voice_parts(content_encoder, wav, sr, lib, every, pool.device)
+    else:
+        parts, register = voice_parts(content_encoder, wav, sr, lib, every, pool.device, f0_estimator, world_pitch)
     total = sum(int(t.shape[1]) for t in parts)
     step = total if max_frames is None else int(max_frames)
     if compact and pool.largest_hole < min(step, total) <= pool.free_rows:
@@ -544,7 +655,10 @@ def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
     done = 0
     try:
         for i, piece in enumerate(pieces):
-            (pool.add if i == 0 else pool.extend)(name, piece)
+            if i == 0:
+                pool.add(name, piece) if register is None else pool.add(name, piece, register)
+            else:
+                pool.extend(name, piece)
             done += sum(int(t.shape[1]) for t in piece)
             yield done
     except ValueError:
@@ -556,7 +670,8 @@ def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
         raise
 
 
-def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False):
+def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False, f0_estimator=None,
+                world_pitch=False):
     """Enrol a voice into a reserved pool from audio, while sessions run on the pool's other voices: the recipe of voice_parts
     (multistream_inference.voice_tokens', under ops.Fp16Guard), appended through the strided alive_pool_append -- the encoder's
     output is never copied or concatenated.  The voice's rows are bitwise those of voice_tokens followed by `add`.
@@ -565,9 +680,10 @@ def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
     encoder's receptive field spans the whole utterance, so no cut of the AUDIO gives bitwise the frames of one call: the utterance
     is encoded once and its tokens are appended piece by piece, which is bitwise one call for any max_frames (a row and its norm
     depend on the row's own token alone).  compact=True: compact the pool first when the first piece fits its free rows but none
-    of its holes.  Returns the voice's row count."""
+    of its holes.  f0_estimator= (auto pitch): the voice also gets its register, measured on the same audio (voice_parts).
+    Returns the voice's row count."""
     rows = 0
-    for rows in enrol_steps(pool, name, content_encoder, wav, sr, lib, every, max_frames, compact):
+    for rows in enrol_steps(pool, name, content_encoder, wav, sr, lib, every, max_frames, compact, f0_estimator, world_pitch):
         pass
     return rows
 
@@ -727,6 +843,41 @@ def pitch_transform_rows_(f0, mode, f0_rate, pitch_shift, intonation):
     return f0
 
 
+def pitch_stats_groups(f0, first, t_lo=0, t_hi=None, out=None):
+    """f0 [N, 1, T] or [N, T], device int32 first [G + 1] -> device float64 [G, 2]: (sum of voiced pitch, voiced frames) over
+    frames [t_lo, t_hi) (default: all) of rows first[g] .. first[g + 1] - 1, in fp64 in a fixed order (alive_pitch_stats_groups)"""
+    if f0.dtype != torch.float32 or not f0.is_contiguous():
+        raise ValueError("pitch_stats_groups: f0 must be contiguous float32")
+    if first.dtype != torch.int32 or first.dim() != 1 or first.numel() < 2:
+        raise ValueError("pitch_stats_groups: first must be int32 [G + 1]")
+    n, t = f0.shape[0], f0.shape[-1]
+    g = first.numel() - 1
+    stats = torch.empty(g, 2, dtype=torch.float64, device=f0.device) if out is None else out
+    nat.check(nat.lib().alive_pitch_stats_groups(nat.ptr(f0), n, t, int(t_lo), int(t if t_hi is None else t_hi), nat.ptr(first), g,
+                                                 nat.ptr(stats), nat.stream()), "alive_pitch_stats_groups")
+    return stats
+
+
+def pitch_shift_groups(stats, first, n, offset, auto_on, target):
+    """the offline shift of every row, device float32 [n]: group g's offset[g], plus target[g] - (float)(sum / count) on an auto
+    group with voiced frames (alive_pitch_shift_groups); offset / target: device float32 [G], auto_on: device int32 [G]"""
+    g = first.numel() - 1
+    out = torch.empty(n, dtype=torch.float32, device=stats.device)
+    nat.check(nat.lib().alive_pitch_shift_groups(nat.ptr(stats), nat.ptr(first), g, n, nat.ptr(offset), nat.ptr(auto_on),
+                                                 nat.ptr(target), nat.ptr(out), nat.stream()), "alive_pitch_shift_groups")
+    return out
+
+
+def pitch_follow_rows_(f0, f0_rate, offset, auto_on, target, emit, decay, prior, state, shift_out):
+    """the streaming register update of every row of f0 [N, 1, T], in place on state (float64 [N, 2]) and shift_out (float32 [N]):
+    alive_pitch_follow_rows.  emit: device bool / uint8 [N] (or [N, 1])"""
+    n, t = f0.shape[0], f0.shape[-1]
+    nat.check(nat.lib().alive_pitch_follow_rows(nat.ptr(f0), n, t, nat.ptr(f0_rate), nat.ptr(offset), nat.ptr(auto_on),
+                                                nat.ptr(target), nat.ptr(emit), float(decay), float(prior), nat.ptr(state),
+                                                nat.ptr(shift_out), nat.stream()), "alive_pitch_follow_rows")
+    return shift_out
+
+
 def resample_rows(x, orig_freq, new_freq, pre_scale, post_scale):
     """x [B, L] -> [B, L'] at new_freq with per-row linear gains (device float32 [B]): audio_io.resample row by row, the gains
     as 10^(dB/20); at equal rates the gains alone"""
@@ -831,17 +982,34 @@ def session_geometry(chunk, buffersize, sr, rate):
     return c
 
 
+def auto_constants(tick_seconds, buffersize, half_life=10.0, prior_seconds=0.5):
+    """(decay, prior) of alive_pitch_follow_rows for a converter whose tick lasts tick_seconds: decay = 2^(-tick / half_life), 1 for
+    half_life None (never forget); prior = prior_seconds of voiced speech * 50 frames/s * buffersize, because every frame stays in
+    the ring for buffersize ticks and is counted each time.  The defaults are design choices, not measurements."""
+    decay = 1.0 if half_life is None else float(2.0 ** (-float(tick_seconds) / float(half_life)))
+    return decay, float(prior_seconds) * 50.0 * int(buffersize)
+
+
 def db_scale(db):
     """torchaudio.functional.gain's factor as audio_io.resample forms it (1.0 exactly at 0 dB)"""
     return float(10 ** (db / 20)) if db != 0 else 1.0
 
 
-_PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k")
+_PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch")
 
 
 class MultiStreamConverter:
+    auto_pitch = False                 # (set per converter in __init__: whether the tick carries the auto-pitch kernel)
+
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
-                 output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None):
+                 output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
+                 auto_pitch_half_life=10.0, auto_pitch_prior=0.5):
+        if not isinstance(auto_pitch, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: auto_pitch must be a bool, got {auto_pitch!r}")
+        if auto_pitch_half_life is not None and not (np.isfinite(auto_pitch_half_life) and auto_pitch_half_life > 0):
+            raise ValueError(f"MultiStreamConverter: auto_pitch_half_life={auto_pitch_half_life!r} must be > 0 seconds, or None")
+        if not (np.isfinite(auto_pitch_prior) and auto_pitch_prior >= 0):
+            raise ValueError(f"MultiStreamConverter: auto_pitch_prior={auto_pitch_prior!r} must be >= 0 seconds")
         if not 1 <= int(k) <= MAX_K:
             raise ValueError(f"MultiStreamConverter: k={k} outside [1, {MAX_K}] (the grouped search keeps k <= 8)")
         if k_max is not None:
@@ -934,6 +1102,16 @@ class MultiStreamConverter:
             self.world_on = torch.zeros(B, dtype=torch.int32, device=dev)
             self._world_sel = torch.zeros(B, 1, 1, dtype=torch.bool, device=dev)
             self.f0_rate_eff = torch.ones(B, dtype=torch.float32, device=dev)
+        # auto_pitch: the follow kernel is part of the tick (captured once); per row, auto_on selects pitch + the automatic shift
+        # towards `target`, and the transform reads shift_eff.  reg_state is the session's running source register, like phi
+        self.auto_pitch = bool(auto_pitch)
+        if self.auto_pitch:
+            self.auto_decay, self.auto_prior = auto_constants(self.chunk / input_sr, self.buffersize, auto_pitch_half_life,
+                                                              auto_pitch_prior)
+            self.auto_on = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.target = torch.zeros(B, dtype=torch.float32, device=dev)
+            self.reg_state = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+            self.shift_eff = torch.zeros(B, dtype=torch.float32, device=dev)
         self.phi = torch.zeros(B, 64, device=dev)
         self._in = torch.zeros(B, ld_in, device=dev)
         self._graph = None
@@ -973,6 +1151,16 @@ class MultiStreamConverter:
             raise ValueError(f"slot {slot}: world_pitch must be a bool, got {world!r}")
         if world and not self.world_pitch:
             raise ValueError(f"slot {slot}: world_pitch=True needs a converter built with MultiStreamConverter(..., world_pitch=True)")
+        auto = p.get("auto_pitch", False)
+        if not isinstance(auto, (bool, np.bool_)):
+            raise ValueError(f"slot {slot}: auto_pitch must be a bool, got {auto!r}")
+        if auto and not self.auto_pitch:
+            raise ValueError(f"slot {slot}: auto_pitch=True needs a converter built with MultiStreamConverter(..., auto_pitch=True)")
+        if auto:                                              # (raises for a voice without a register, before anything changes)
+            try:
+                target = self.pool.blend_register(names, weights)
+            except ValueError as e:
+                raise ValueError(f"slot {slot}: {e}") from None
         self._write_segments(slot, names)
         if self.S > 1:
             rows = slice(slot * self.S, (slot + 1) * self.S)
@@ -989,6 +1177,9 @@ class MultiStreamConverter:
         self.out_pre[slot] = db_scale(p["gain"])
         if self.world_pitch:
             self._set_world(slot, bool(world), float(p["f0_rate"]))
+        if self.auto_pitch:
+            self.auto_on[slot] = int(bool(auto))
+            self.target[slot] = target if auto else 0.0
 
     def _write_segments(self, slot, names):
         """the slot's rows of seg_lo / seg_len from where its voices lie in the pool now"""
@@ -1045,18 +1236,21 @@ class MultiStreamConverter:
         self.pair_out[slot] = self._rt.pair(16000, rate)
         self.len_out[slot] = self._lout[rate]
 
-    def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None):
+    def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None,
+             auto_pitch=False):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
-        WORLD's f0 of the session's ring instead of the estimator's, f0_rate not applied (needs a world_pitch=True converter)"""
+        WORLD's f0 of the session's ring instead of the estimator's, f0_rate not applied (needs a world_pitch=True converter).
+        auto_pitch=True (needs an auto_pitch=True converter and a register on every voice of the session): the pitch shift follows
+        the target voice's register, and `pitch` is an offset on top of it"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
             raise ValueError(f"slot {slot}: rate {rate} Hz was not declared (rates={list(self.rates)}): pass it in "
                              "MultiStreamConverter(..., rates=...)")
         p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch,
-                 k=k)
+                 k=k, auto_pitch=auto_pitch)
         self._apply(slot, p)                                  # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -1064,10 +1258,14 @@ class MultiStreamConverter:
         self.count[slot] = 0
         self.ring[slot] = 0
         self.phi[slot] = 0.0
+        if self.auto_pitch:
+            self.reg_state[slot] = 0.0                        # a new source: nothing heard yet
         return self
 
     def set(self, slot, **params):
-        """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k)"""
+        """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch).
+        The running source register is kept: a new voice changes the target only, and auto_pitch=True after False resumes from
+        what the session had heard while it was on (nothing, if it never was)"""
         slot = self._slot(slot)
         if not self.is_open[slot]:
             raise ValueError(f"slot {slot} is not open")
@@ -1096,6 +1294,10 @@ class MultiStreamConverter:
         self.phi[slot] = 0.0
         if self.world_pitch:
             self._set_world(slot, False, 1.0)
+        if self.auto_pitch:
+            self.auto_on[slot] = 0
+            self.target[slot] = 0.0
+            self.reg_state[slot] = 0.0
         self._set_rate(slot, int(self.input_sr))             # a closed slot: the converter's own rate, silence
         return self
 
@@ -1109,7 +1311,11 @@ class MultiStreamConverter:
             if self.world_pitch:
                 buf.copy_(torch.where(self._world_sel, compute_f0_rows(data, self.world_on), buf))
                 f0, rate = buf, self.f0_rate_eff
-            return pitch_transform_rows_(f0, 1, rate, self.pitch, self.intonation)
+            shift = self.pitch
+            if self.auto_pitch:                               # the sessions' running registers -> this tick's shifts
+                shift = pitch_follow_rows_(f0, rate, self.pitch, self.auto_on, self.target, self.emit, self.auto_decay,
+                                           self.auto_prior, self.reg_state, self.shift_eff)
+            return pitch_transform_rows_(f0, 1, rate, shift, self.intonation)
         return f0_on_side_stream(self, spec, body)
 
     def _device_step(self, data, phi):
@@ -1156,8 +1362,11 @@ class MultiStreamConverter:
     def enable_graph(self):
         """capture the per-tick device pipeline over [B, ring] once; replays read the per-slot device arrays"""
         saved = self.phi.clone()
+        saved_reg = self.reg_state.clone() if self.auto_pitch else None      # (capture_step runs the step three times)
         self._graph, self._g_out = capture_step(self.device, lambda: self._device_step(self._in, self.phi), self.phi)
         self.phi.copy_(saved)
+        if saved_reg is not None:
+            self.reg_state.copy_(saved_reg)
         self._graph_pool_version = self.pool.version
         self.captures += 1
         return self
@@ -1174,10 +1383,13 @@ class MultiStreamConverter:
         self.phi.copy_(phi_next)
         return wave
 
-    def _repeat_on_bf16(self, saved_phi):
-        """RealtimeConverter._repeat_on_bf16 for the whole tick: modes 2, every slot's phase restored, the tick again"""
+    def _repeat_on_bf16(self, saved_phi, saved_reg=None):
+        """RealtimeConverter._repeat_on_bf16 for the whole tick: modes 2, every slot's phase (and running register) restored, the
+        tick again"""
         ops.switch_to_bf16("multi-session streaming step", "tick")
         self.phi.copy_(saved_phi)
+        if saved_reg is not None:
+            self.reg_state.copy_(saved_reg)
         if self._graph is not None:
             self.enable_graph()
         return audio_io.float_to_pcm16(self._run()).cpu().numpy()
@@ -1214,9 +1426,10 @@ class MultiStreamConverter:
         guarded = fp16_guarded(self.B * self.frames)
         if guarded:
             saved_phi = self.phi.clone()
+            saved_reg = self.reg_state.clone() if self.auto_pitch else None
         o = audio_io.float_to_pcm16(self._run()).cpu().numpy()
         if guarded and ops.f16_saturations(reset=True) > 0:
-            o = self._repeat_on_bf16(saved_phi)
+            o = self._repeat_on_bf16(saved_phi, saved_reg)
         for s in chunks:
             if emit[s]:
                 cs = self.slot_chunk[s]

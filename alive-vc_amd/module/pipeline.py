@@ -374,7 +374,7 @@ class Converter:
         return stitch(self.convert_windows(windows, keep_frames=keep, **kw), total, chunk)       # (the guard sits in convert_windows)
 
     def convert_many(self, utterances, pool, voices, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, alpha=0.0, chunk=48000, k=4,
-                     window_batch=64, trim_context=False, world_pitch=False):
+                     window_batch=64, trim_context=False, world_pitch=False, auto_pitch=False):
         """Many-to-many batch conversion: utterance i (16 kHz, [L] or [1, L], any length) to voice voices[i] of `pool`
         (module/multistream.py: VoicePool), with per-utterance pitch_shift / intonation / f0_rate / alpha / world_pitch (a scalar
         applies to every utterance; world_pitch: WORLD's f0 of each whole window, as convert(world_pitch=True)).  Returns one [1, L_i] waveform per utterance.  The windows of ALL utterances form one batch (a network
@@ -389,7 +389,14 @@ class Converter:
         k may be a list with one value per utterance (1 <= k_i <= 8; every voice of utterance i needs at least k_i vectors): the
         match then runs the per-row-k entry points at k_max = max(k) (alive_knn_search_pool_k, alive_knn_merge_gather_rows_k /
         alive_knn_blend_gather_rows_k; the pool search groups its rows by voice and k), and utterance i is bitwise `convert` alone
-        at k_i.  A scalar k launches the uniform path."""
+        at k_i.  A scalar k launches the uniform path.
+        auto_pitch (a bool, or one per utterance): utterance i's shift follows its target voice's register (VoicePool.register; a
+        blend: the weighted mean of its voices'; ValueError for a voice without one): its source register is the mean voiced pitch
+        of the raw f0 (the estimator's or WORLD's, before intonation and rate) over the centre third of each of its windows --
+        frames [chunk // 320, 2 * chunk // 320), every original frame once -- from ONE alive_pitch_stats_groups call with a group
+        per utterance, and its shift is pitch_shift[i] + (target - that mean) (alive_pitch_shift_groups), pitch_shift[i] alone if
+        nothing is voiced.  A group's sums depend on its own rows only and are added in a fixed order, so an utterance converts
+        bitwise the same alone and inside any corpus.  A corpus without an auto utterance launches the present path."""
         from . import multistream as MS
         m = len(utterances)
         voices = list(voices)
@@ -416,7 +423,13 @@ class Converter:
             raise ValueError(f"world_pitch: {len(worlds)} values for {m} utterances")
         if not all(isinstance(w, (bool, np.bool_)) for w in worlds):
             raise ValueError(f"world_pitch: expected bools, got {worlds}")
+        autos = list(auto_pitch) if isinstance(auto_pitch, (list, tuple)) else [auto_pitch] * m
+        if len(autos) != m:
+            raise ValueError(f"auto_pitch: {len(autos)} values for {m} utterances")
+        if not all(isinstance(a, (bool, np.bool_)) for a in autos):
+            raise ValueError(f"auto_pitch: expected bools, got {autos}")
         specs = [MS.blend_spec(v, pool, k if ks is None else ks[i]) for i, v in enumerate(voices)]
+        targets = [pool.blend_register(*spec) if a else 0.0 for spec, a in zip(specs, autos)]      # (raises: a voice without one)
         blended = any(len(names) > 1 for names, _ in specs)
         wins, totals, counts = [], [], []
         for u in utterances:
@@ -434,6 +447,14 @@ class Converter:
                       rate=rows(rates, torch.float32))
         if ks is not None:                  # each window's k; the blended search repeats it on the window's list rows (below)
             params["k"] = rows(ks, torch.int32)
+        if any(autos):                      # one group per utterance: its windows' rows, its offset, whether it is on, its target
+            first = [0]
+            for c in counts:
+                first.append(first[-1] + c)
+            params["auto"] = dict(first=torch.tensor(first, dtype=torch.int32, device=self.device),
+                                  offset=torch.tensor(shifts, dtype=torch.float32, device=self.device),
+                                  on=torch.tensor([int(bool(a)) for a in autos], dtype=torch.int32, device=self.device),
+                                  target=torch.tensor(targets, dtype=torch.float32, device=self.device))
         if not blended:                     # (one-voice blends are their voice: weight 1.0)
             params["ids"] = torch.repeat_interleave(pool.voice_ids([names[0] for names, _ in specs]), rep).contiguous()
         else:                               # compact list rows: window w of utterance i owns S_i of them, in blend order
@@ -470,7 +491,11 @@ class Converter:
                 f0[b].index_copy_(0, w, compute_f0(windows[b].index_select(0, w)))
 
         def transform(f0):                  # each utterance's pitch, intonation and f0 rate (features(world_pitch=True))
-            MS.pitch_transform_rows_(f0, 0, params["rate"], params["shift"], params["inton"])
+            shift, au = params["shift"], params.get("auto")
+            if au is not None:              # the auto utterances' shifts from the raw f0 of their windows' centre thirds
+                stats = MS.pitch_stats_groups(f0, au["first"], chunk // 320, 2 * chunk // 320)
+                shift = MS.pitch_shift_groups(stats, au["first"], f0.shape[0], au["offset"], au["on"], au["target"])
+            MS.pitch_transform_rows_(f0, 0, params["rate"], shift, params["inton"])
 
         def match(feat):
             src = feat if rng is None else feat[:, :, rng[0]:rng[1]].contiguous()

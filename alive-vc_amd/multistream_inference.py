@@ -8,6 +8,10 @@ The sessions file is a JSON list; each entry:
    "world_pitch": false,                  optional, a JSON bool: realtime_inference.py's -wpe (WORLD's f0 of the ring; its
                                           f0_rate is then not applied, as there)
    "k": 4,                                optional, an integer in 1..8: the session's own k (default: -k)
+   "auto_pitch": false,                   optional, a JSON bool (default: --auto-pitch): the pitch shift follows the target
+                                          voice's register (module/multistream.py "Auto pitch"); "pitch" is then an offset on top
+   "register_hz": 180,                    optional: declares the register (mean f0 in Hz) of a voice given by "lib" alone, which
+                                          has no audio to measure it on; a "target" wav's register is measured at enrolment
    "blend": [{"target": "a.wav", "weight": 2}, {"lib": "b.pt", "weight": 1}],   instead of "target" / "lib": a weighted mix
                                           of 1 to 4 voices, each component a voice source as above (multistream.blend_spec)
    "start": 0,                            optional: the tick at which the session joins
@@ -22,6 +26,8 @@ It is built with blend = the most components of any session's "blend" (1 without
 sessions and blend components naming the same voice sources share one voice of the pool.
 It is built with k_max = the largest "k" only if some session's "k" differs from -k (converter_k_max): a file without "k" runs as
 before.  Sessions on one voice at different k take one pass over that voice per k.
+The converter carries the auto-pitch kernel, and the voices are given registers (measured with the f0 estimator on the target wavs),
+only if some session is on auto pitch: a file without "auto_pitch", run without --auto-pitch, runs as before.
 WORLD needs rings of about 230 ms or more (-c 960 -b 8 is 480 ms): a shorter ring comes out unvoiced.
 Flags shared with realtime_inference.py keep its spelling: -c, -b, -k, -isr, -osr, --no-graph.
 
@@ -46,12 +52,13 @@ from module import audio_io                                     # noqa: E402
 from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
-from module.multistream import MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice   # noqa: E402
+from module.multistream import (MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
+                                measure_register)
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
 SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "start", "sr", "output",
-                "blend", "k")
+                "blend", "k", "auto_pitch", "register_hz")
 
 
 def build_parser():
@@ -71,14 +78,40 @@ def build_parser():
     parser.add_argument('--pool-rows', default=None, type=int,
                         help="a reserved voice pool of this many rows: voices are enrolled at the first tick that needs them and "
                              "removed after their last session (default: every voice is packed before tick 0)")
+    parser.add_argument('--auto-pitch', action='store_true',
+                        help="sessions follow their target voice's register unless their \"auto_pitch\" says otherwise")
     parser.add_argument('--no-graph', action='store_true',
                         help="launch the per-tick device pipeline kernel by kernel instead of replaying one captured hipGraph")
     return parser
 
 
-def load_sessions(path, k=4):
-    """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`); ValueError on a
-    malformed entry"""
+def register_hz_of(entry, where):
+    """an entry's "register_hz" (None without one): a number > 0, for a voice given by "lib" alone"""
+    hz = entry.get("register_hz")
+    if hz is None:
+        return None
+    if isinstance(hz, bool) or not isinstance(hz, (int, float)) or not 0 < hz < float("inf"):
+        raise ValueError(f"{where}: \"register_hz\" must be a number > 0, got {hz!r}")
+    if "blend" in entry or entry.get("target") is not None or entry.get("lib") is None:
+        raise ValueError(f"{where}: \"register_hz\" declares the register of a voice given by \"lib\" alone (a \"target\" wav's is "
+                         "measured; a blend's comes from its voices)")
+    return float(hz)
+
+
+def declared_registers(entries, name_of):
+    """{voice name: Hz} of the entries' "register_hz"; ValueError if two entries declare different ones for one voice"""
+    out = {}
+    for i, e in enumerate(entries):
+        if e.get("register_hz") is not None:
+            name = name_of(e)
+            if out.setdefault(name, e["register_hz"]) != e["register_hz"]:
+                raise ValueError(f"entry {i}: \"register_hz\" {e['register_hz']} but an earlier entry gave this voice {out[name]}")
+    return out
+
+
+def load_sessions(path, k=4, auto_pitch=False):
+    """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
+    `auto_pitch`); ValueError on a malformed entry"""
     k = check_k(k, "-k")
     with open(path) as f:
         sessions = json.load(f)
@@ -98,11 +131,14 @@ def load_sessions(path, k=4):
             raise ValueError(f"session {i}: needs a \"target\" wav or a \"lib\" voice library")
         if not isinstance(s.get("world_pitch", False), bool):
             raise ValueError(f"session {i}: \"world_pitch\" must be true or false, got {s['world_pitch']!r}")
+        if not isinstance(s.get("auto_pitch", False), bool):
+            raise ValueError(f"session {i}: \"auto_pitch\" must be true or false, got {s['auto_pitch']!r}")
         sess_k = check_k(s["k"], f"session {i}: \"k\"") if "k" in s else k
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
                  gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
-                 sr=None if s.get("sr") is None else int(s["sr"]), world_pitch=s.get("world_pitch", False), blend=blend, k=sess_k)
+                 sr=None if s.get("sr") is None else int(s["sr"]), world_pitch=s.get("world_pitch", False), blend=blend, k=sess_k,
+                 auto_pitch=s.get("auto_pitch", bool(auto_pitch)), register_hz=register_hz_of(s, f"session {i}"))
         if e["start"] < 0:
             raise ValueError(f"session {i}: start tick {e['start']} < 0")
         if e["sr"] is not None and e["sr"] <= 0:
@@ -186,6 +222,18 @@ def voice_tokens(ce, target, lib, device):
     return tgt[0].contiguous()
 
 
+def voice_tokens_register(ce, pe, target, lib, device):
+    """voice_tokens and the voice's register (sum of voiced pitch, voiced frames), measured with the f0 estimator on the same 16 kHz
+    audio the content encoder sees (multistream.measure_register); None for a voice without a target wav"""
+    register = None
+    if target is not None:
+        wf, sr = audio_io.load(target)
+        wf = audio_io.resample(wf.to(device), sr, 16000)
+        wf = wf / wf.abs().max()
+        register = measure_register(pe, wf[:1].contiguous())
+    return voice_tokens(ce, target, lib, device), register
+
+
 def input_pcm(path, input_sr, device):
     wf, sr = audio_io.load(path)
     wf = audio_io.resample(wf.mean(dim=0, keepdim=True).to(device), sr, input_sr)[0].cpu()
@@ -225,7 +273,7 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    sessions = load_sessions(args.sessions, args.k)
+    sessions = load_sessions(args.sessions, args.k, args.auto_pitch)
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -236,11 +284,20 @@ def main(argv=None):
     CE.load_state_dict(torch.load(args.content_encoder_path, map_location=device))
     Dec.load_state_dict(torch.load(args.decoder_path, map_location=device))
 
+    # auto pitch: only then are the voices' registers measured (with the f0 estimator) or declared ("register_hz")
+    auto = any(s["auto_pitch"] for s in sessions)
+    declared = declared_registers(sessions, lambda s: voice_name(s["target"], s["lib"])) if auto else {}
     pool, names = VoicePool(device=device, capacity=args.pool_rows), []
     for s in sessions:
         for target, lib in session_sources(s):
-            if args.pool_rows is None and voice_name(target, lib) not in pool.segments:
-                pool.add(voice_name(target, lib), voice_tokens(CE, target, lib, device))
+            name = voice_name(target, lib)
+            if args.pool_rows is None and name not in pool.segments:
+                if auto:
+                    pool.add(name, *voice_tokens_register(CE, PE, target, lib, device))
+                    if name in declared:
+                        pool.set_register(name, hz=declared[name])
+                else:
+                    pool.add(name, voice_tokens(CE, target, lib, device))
         names.append(session_voice(s))
     slots = max(args.slots, len(sessions))
     in_sr = [s["sr"] or args.input_sr for s in sessions]
@@ -248,9 +305,9 @@ def main(argv=None):
     conv = MultiStreamConverter(CE, PE, Dec, pool, slots, chunk=args.chunk, buffersize=args.buffersize, input_sr=args.input_sr,
                                 output_sr=args.output_sr, k=args.k, device=device, rates=sorted(set(in_sr)),
                                 world_pitch=any(s["world_pitch"] for s in sessions), blend=blend_size(sessions),
-                                k_max=converter_k_max(sessions, args.k))
+                                k_max=converter_k_max(sessions, args.k), auto_pitch=auto)
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
-                   input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"])
+                   input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"])
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()
@@ -268,7 +325,9 @@ def main(argv=None):
             for name in [n for t, what, n in events if t == tick and what == "enrol"]:
                 target, lib = sources[name]
                 wav, sr = audio_io.load(target) if target is not None else (None, None)
-                enrol_voice(pool, name, CE, wav, sr, lib=lib, compact=True)
+                enrol_voice(pool, name, CE, wav, sr, lib=lib, compact=True, f0_estimator=PE if auto else None)
+                if name in declared:
+                    pool.set_register(name, hz=declared[name])
 
         def after(tick):
             for name in [n for t, what, n in events if t == tick and what == "remove"]:

@@ -760,6 +760,32 @@ int alive_pitch_transform(float* f0, int N, int T, int mode, float f0_rate, floa
 int alive_pitch_transform_rows(float* f0, int N, int T, int mode, const float* f0_rate, const float* pitch_shift,
                                const float* intonation, void* stream);
 
+/* Auto pitch (csrc/pitch_auto.hip): the source's register measured on the device and turned into a shift towards the target voice's.
+ * "pitch" is 12*log2(f0/440) - 9 as alive_pitch_transform forms it (log2 in fp64, rounded once to float32); a frame is voiced when that
+ * value is finite (0, NaN and inf are unvoiced, inference.py:121).  All pointers are DEVICE pointers; no call allocates, synchronises
+ * or reads anything on the host (graph-capturable).  Sums are fp64 in a fixed order (per row: alive_pitch_transform's tree; then the
+ * rows of a group in index order), no floating-point atomics: bitwise reproducible, and a group's result does not depend on the other
+ * groups of the call.
+ *   alive_pitch_stats_groups   stats[g] = (sum of voiced pitch, voiced count as a double) over frames [t_lo, t_hi) of rows
+ *                              first[g] .. first[g+1]-1 of f0[N][T] (first: int32 [G+1]); empty and all-unvoiced groups give (0, 0)
+ *   alive_pitch_shift_groups   shift_out[r] for the rows r of group g: offset[g], plus on a group with auto_on[g] != 0 and a voiced
+ *                              count > 0 the float32 (target[g] - (float)(sum / count)); offset / target: float [G], auto_on: int32 [G].
+ *                              shift_out [N] then feeds alive_pitch_transform_rows (mode 0)
+ *   alive_pitch_follow_rows    the streaming update, row n of f0[N][T] (f0_rate, offset, target: float [N]; auto_on: int32 [N]; emit:
+ *                              bytes [N]; state: double [N][2] = (S, W)):
+ *                                auto_on[n] == 0: shift_out[n] = offset[n] bit for bit, state[n] untouched;
+ *                                else, if emit[n] != 0, with p_t = pitch(f0[n][t] * f0_rate[n]) (what mode 1 forms before the shift):
+ *                                  S <- decay * S + sum of voiced p_t,  W <- decay * W + voiced count   (emit[n] == 0: state stays)
+ *                                then shift_out[n] = offset[n] + (float)(W / (W + prior) * (target[n] - S / W)), the automatic part
+ *                                exactly 0 when W == 0.  0 <= decay <= 1, prior >= 0 (a pseudo-count of voiced frames).
+ *                              alive_pitch_transform_rows(mode 1, f0_rate, shift_out, ...) then runs unchanged */
+int alive_pitch_stats_groups(const float* f0, int N, int T, int t_lo, int t_hi, const int* first, int G, double* stats, void* stream);
+int alive_pitch_shift_groups(const double* stats, const int* first, int G, int N, const float* offset, const int* auto_on,
+                             const float* target, float* shift_out, void* stream);
+int alive_pitch_follow_rows(const float* f0, int N, int T, const float* f0_rate, const float* offset, const int* auto_on,
+                            const float* target, const unsigned char* emit, double decay, double prior, double* state,
+                            float* shift_out, void* stream);
+
 /* WORLD pitch estimation (`-wpe`): DIO + StoneMask on N rows of L8 samples at fs, in fp64   (reference module/common.py:113-137,
  * pyworld.dio(x, fs, f0_floor, f0_ceil, channels_in_octave=2, frame_period, speed=1, allowed_range=0.1) then pyworld.stonemask).
  * Restated from the published algorithm (tools/world_ref.py is the NumPy restatement; parity with pyworld is unpinned).

@@ -12,7 +12,10 @@ tick p50 / p99 of voice blending: blend3_single_* a blend=3 converter whose sess
 session blending 2 / 3 voices (session s: voices s, s + 1, s + 2, weights 1, 2, 3) in a converter of that blend; distinct voices
 only.  --mixed-k adds the graph tick p50 / p99 of the per-session k (MultiStreamConverter(k_max=8), the per-row-k entry points):
 kmax8_uniform4_* every session at k = 4 through them (next to graph_tick_*: the same batch through the uniform entry points),
-kmax8_mixed_* session s at k = (1, 2, 4, 8)[s % 4] -- on the shared voice that is one pass over the voice per k.  --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
+kmax8_mixed_* session s at k = (1, 2, 4, 8)[s % 4] -- on the shared voice that is one pass over the voice per k.  --auto-pitch adds
+the graph tick p50 / p99 of an auto_pitch=True converter with every session on auto pitch (auto_pitch_tick_*: one more small launch on
+the f0 side stream, alive_pitch_follow_rows; voice v_i is declared a register of 110 + 10 (i % 12) Hz) next to graph_tick_* of the same
+batch.  --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
 one more 50 000-row voice added between two ticks, once on a default pool (the add re-packs the pool and the next tick
 re-captures) and once on a reserved pool of 65 x 50 000 rows (VoicePool(capacity=...): alive_pool_append into the table in
 place); per pool the wall time of the add (bracketed by device synchronisation; add_device_ms: events around it), the latency of
@@ -22,7 +25,8 @@ lowest voice is removed and `compact` slides the other 64 down by one voice (com
 python tools/bench_multistream.py --quick).  Prints one JSON line per configuration and writes the list to --out.
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
-                                      [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--out multistream.json]
+                                      [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch]
+                                      [--out multistream.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
 """
 import argparse
@@ -172,6 +176,7 @@ def main():
     ap.add_argument("--blend", action="store_true", help="also time voice blending (blend=3 single voices, 2- and 3-voice blends)")
     ap.add_argument("--mixed-k", action="store_true", help="also time a k_max=8 converter: every session at k = 4, and an even "
                                                            "mix of k = 1, 2, 4, 8")
+    ap.add_argument("--auto-pitch", action="store_true", help="also time an auto_pitch=True converter, every session on auto pitch")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
                                                          "default and on a reserved pool")
     ap.add_argument("--out", default=None)
@@ -192,6 +197,10 @@ def main():
         return
     shared = make_pool(1, 1)
     distinct = make_pool(max(batches) + (2 if args.blend else 0), 2)
+    if args.auto_pitch:                                        # (host floats beside the voices: nothing else changes)
+        for pool in (shared, distinct):
+            for i, name in enumerate(pool.segments):
+                pool.set_register(name, hz=110.0 + 10.0 * (i % 12))
     rows = []
     for chunk, bs in configs:
         period_ms = chunk / 16.0
@@ -251,6 +260,15 @@ def main():
                     rec[f"{name}_tick_p50_ms"], rec[f"{name}_tick_p99_ms"] = round(p50, 3), round(p99, 3)
                     rec[f"{name}_real_time"] = p99 < period_ms
                     del kc
+                if args.auto_pitch:
+                    ac = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, auto_pitch=True)
+                    for s in range(B):
+                        ac.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, auto_pitch=True)
+                    ac.enable_graph()
+                    p50, p99 = time_ticks(ac, B, chunk, args.ticks, args.warmup + bs + 1, 300)
+                    rec["auto_pitch_tick_p50_ms"], rec["auto_pitch_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                    rec["auto_pitch_real_time"] = p99 < period_ms
+                    del ac
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
                 rows.append(rec)
