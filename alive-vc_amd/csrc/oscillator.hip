@@ -34,7 +34,8 @@ __host__ __device__ inline int osc_pieces(int N, int Lf, int seg) { return ((int
 
 // x / 16000 correctly rounded, as one multiply and two fmas: q = x * rc, then one residual correction.  For this
 // divisor the result equals the IEEE quotient for EVERY fp32 x in [2^-24, 2^24) -- checked exhaustively on the GPU
-// (tests/test_gpu_ops.py::test_div16000_is_the_ieee_quotient); other sample rates take the IEEE sequence.
+// (tests/test_gpu_ops.py::test_div16000_is_the_ieee_quotient); other sample rates take the IEEE sequence
+// (22050 and 48000 against the CPU quotient: tests/test_gpu_oscillator.py::test_other_segment_lengths_and_rates).
 __device__ __forceinline__ float div_rate(float x, float sample_rate) {
     if (sample_rate == 16000.0f) {
         const float rc = 6.25e-5f;
@@ -220,6 +221,10 @@ extern "C" int alive_oscillator_range(const float* amps, const float* f0, const 
     const int Lw = Lf * seg;
     ALIVE_CHECK_ARG(crop0 >= 0 && crop0 < Lw, "alive_oscillator: crop0 %d outside [0,%d)", crop0, Lw);
     ALIVE_CHECK_ARG(phi_out == nullptr || (phi_col >= 0 && phi_col < Lw), "alive_oscillator: phi_col outside wave");
+    // only the range's own samples are synthesised: a phi_col outside them would leave phi_out unwritten
+    ALIVE_CHECK_ARG(phi_out == nullptr || (phi_col >= f_begin * seg && phi_col < (f_begin + n_frames) * seg),
+                    "alive_oscillator: phi_col %d outside the frame range's samples [%d, %d)", phi_col, f_begin * seg,
+                    (f_begin + n_frames) * seg);
     const int Q = osc_pieces(N, Lf, seg);
     OscGeom g{H, Lf, seg, Lw, (float)Lf / (float)Lw, sample_rate, Q, seg / Q};
     Arena a(ws);

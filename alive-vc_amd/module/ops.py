@@ -191,17 +191,29 @@ def argmax_channels(x):
     return out
 
 
-def oscillator(amps, f0, phi=None, crop0=0, phi_col=None, seg=320, sample_rate=16000.0):
-    """amps[N,H,Lf] (already exp'd), f0[N,1,Lf] -> wave[N,1,Lf*seg], phi_out[N,H] at phi_col (or None)."""
+def oscillator(amps, f0, phi=None, crop0=0, phi_col=None, seg=320, sample_rate=16000.0, f_begin=0, n_frames=None):
+    """amps[N,H,Lf] (already exp'd), f0[N,1,Lf] -> wave[N,1,Lf*seg], phi_out[N,H] at phi_col (or None).
+    n_frames given: the frames [f_begin, f_begin + n_frames) of the window only through alive_oscillator_range -- amps[N,H,n_frames]
+    and wave[N,1,n_frames*seg] hold that range, f0 stays the whole window (crop0 / phi_col are columns of the window)."""
     amps, f0 = _f(amps), _f(f0)
-    n, h, lf = amps.shape
-    wave = torch.empty(n, 1, lf * seg, device=amps.device)
+    n, h, la = amps.shape
+    lf = f0.shape[-1]
+    wave = torch.empty(n, 1, la * seg, device=amps.device)
     phi_in = None if phi is None else _f(phi.reshape(n, h))
     phi_out = None if phi_col is None else torch.empty(n, h, device=amps.device)
     L = nat.lib()
     ws = _ws.get(L.alive_oscillator_workspace_bytes(n, h, lf), amps.device)
-    rc = L.alive_oscillator(nat.ptr(amps), nat.ptr(f0), nat.ptr(phi_in), n, h, lf, seg, sample_rate, crop0,
-                            0 if phi_col is None else phi_col, nat.ptr(wave), nat.ptr(phi_out), nat.ptr(ws), nat.stream())
+    col = 0 if phi_col is None else phi_col
+    if n_frames is None:
+        if f_begin != 0 or la != lf:
+            raise ValueError(f"oscillator: amps hold {la} frames, f0 {lf} (a frame range needs n_frames)")
+        rc = L.alive_oscillator(nat.ptr(amps), nat.ptr(f0), nat.ptr(phi_in), n, h, lf, seg, sample_rate, crop0, col,
+                                nat.ptr(wave), nat.ptr(phi_out), nat.ptr(ws), nat.stream())
+    else:
+        if la != n_frames:
+            raise ValueError(f"oscillator: amps hold {la} frames, the range {n_frames}")
+        rc = L.alive_oscillator_range(nat.ptr(amps), nat.ptr(f0), nat.ptr(phi_in), n, h, lf, seg, sample_rate, crop0, col,
+                                      f_begin, n_frames, nat.ptr(wave), nat.ptr(phi_out), nat.ptr(ws), nat.stream())
     nat.check(rc, "alive_oscillator")
     return wave, phi_out
 

@@ -620,7 +620,8 @@ int alive_oscillator(const float* amps, const float* f0, const float* phi_in, in
                      int seg, float sample_rate, int crop0, int phi_col,
                      float* wave, float* phi_out, void* ws, void* stream);
 /* the frames [f_begin, f_begin + n_frames) of the window only: amps[N][H][n_frames], wave[N][n_frames*seg]; f0 and the
- * phase accumulation cover the whole window, so the samples are bitwise those of alive_oscillator */
+ * phase accumulation cover the whole window, so the samples are bitwise those of alive_oscillator.  crop0 and phi_col are
+ * columns of the window; with a phi_out, phi_col must lie inside the range's samples [f_begin*seg, (f_begin+n_frames)*seg) */
 int alive_oscillator_range(const float* amps, const float* f0, const float* phi_in, int N, int H, int Lf,
                            int seg, float sample_rate, int crop0, int phi_col, int f_begin, int n_frames,
                            float* wave, float* phi_out, void* ws, void* stream);
