@@ -50,6 +50,21 @@ auto_pitch_prior seconds of voiced speech * 50 frames/s * buffersize (a frame st
 every time); the defaults, 10 s and 0.5 s, are design choices, not tuned on data.  The state belongs to the session like phi: open and
 close zero it, set(voice=) rewrites the target only (the source has not changed), enable_graph and the bf16 repeat save and restore it.
 Everything is device arrays: toggling never re-captures, and a converter built without auto_pitch launches exactly what it did.
+
+Input gate: a converter built with gate=True decides on the device, every tick, which sessions hear something (csrc/gate.hip).  Right
+after the input resample, alive_gate_rows takes the mean square of every 16 kHz ring over the detection window [begin_of_output,
+min(ring, end_of_output + gate_lookahead)) -- the chunk about to be emitted plus a lookahead, one chunk's duration by default, a
+converter constant because it is baked into the captured launch -- and runs, for the sessions opened or set with gate_db=, a hold state
+machine against the session's threshold: gate_state [B, 2] = (hold_left, was_open), like phi the session's own (open and close zero it,
+so a gated session's first chunk fades in; enable_graph and the bf16 repeat save and restore it).  Its outputs steer the rest of the
+tick: g0 / g1, the gains at the two ends of the emitted chunk, which alive_gate_apply_rows turns into a linear fade (or +0.0, or nothing)
+on the final waves; seg_len_eff, the search's segment lengths with a row closed at BOTH ends at 0 -- the grouped search does no work for
+it and the merge passes it through; a fading chunk is still searched, so what fades is the converted voice, never the source --;
+world_eff, WORLD's row mask without the skipped rows; and follow, which replaces emit for the auto-pitch follower, so a session's
+register learns from open ticks only.  The encoders and the decoder still run over all B rows.  gate_db is dBFS of the 16 kHz ring after
+the input gain (thr = 10^(dB/10) as a mean square, float64 on the host), gate_hold seconds rounded up to ticks.  Everything is device
+arrays: toggling and retuning never re-capture, and a converter built without gate launches exactly what it did.  gate_open() reads
+the per-slot open flags of the last tick back; seg_len_eff stays an attribute.
 """
 import numpy as np
 import torch
@@ -878,6 +893,54 @@ def pitch_follow_rows_(f0, f0_rate, offset, auto_on, target, emit, decay, prior,
     return shift_out
 
 
+def gate_thr_ms(gate_db):
+    """a gate threshold in dBFS -> the mean square alive_gate_rows compares with: 10^(dB / 10) in float64.  ValueError unless it is
+    a finite number (not a bool)"""
+    if isinstance(gate_db, (bool, np.bool_)) or not isinstance(gate_db, (int, float, np.integer, np.floating)) or not np.isfinite(
+            gate_db):
+        raise ValueError(f"gate_db={gate_db!r} must be a finite number of dBFS, or None for no gate")
+    return 10.0 ** (float(gate_db) / 10.0)
+
+
+def gate_hold_ticks(gate_hold, tick_seconds):
+    """a gate's hold in seconds -> ticks: ceil(hold / tick).  ValueError unless it is a finite number >= 0 (not a bool)"""
+    if isinstance(gate_hold, (bool, np.bool_)) or not isinstance(gate_hold, (int, float, np.integer, np.floating)) or not (
+            np.isfinite(gate_hold) and gate_hold >= 0):
+        raise ValueError(f"gate_hold={gate_hold!r} must be a finite number of seconds >= 0")
+    ticks = int(np.ceil(float(gate_hold) / float(tick_seconds)))
+    if ticks >= 2 ** 31:
+        raise ValueError(f"gate_hold={gate_hold!r} is {ticks} ticks: too long")
+    return ticks
+
+
+def gate_window(begin_of_output, end_of_output, ring16, lookahead):
+    """the detection window of a ring of ring16 samples at 16 kHz: [begin_of_output, min(ring16, end_of_output + lookahead))"""
+    return int(begin_of_output), min(int(ring16), int(end_of_output) + int(lookahead))
+
+
+def gate_rows(x, w_lo, w_hi, gate_on, thr_ms, hold_ticks, emit, world_on, S, seg_len, state, g0, g1, seg_len_eff, follow,
+              world_eff, ms_out=None):
+    """alive_gate_rows on x [N, ld] (the 16 kHz rings): this tick's decision of every row into g0, g1, seg_len_eff, follow,
+    world_eff (world_on / world_eff: both None without a WORLD branch), state updated in place.  ms_out: float64 [N] or None"""
+    n, ld = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("gate_rows: x must be contiguous float32 [N, ld]")
+    nat.check(nat.lib().alive_gate_rows(nat.ptr(x), n, ld, int(w_lo), int(w_hi), nat.ptr(gate_on), nat.ptr(thr_ms),
+                                        nat.ptr(hold_ticks), nat.ptr(emit), nat.ptr(world_on), int(S), nat.ptr(seg_len),
+                                        nat.ptr(state), nat.ptr(g0), nat.ptr(g1), nat.ptr(seg_len_eff), nat.ptr(follow),
+                                        nat.ptr(world_eff), nat.ptr(ms_out), nat.stream()), "alive_gate_rows")
+
+
+def gate_apply_rows_(y, span_lo, span_len, g0, g1):
+    """alive_gate_apply_rows in place on y [N, ld]: every row's span times its ramp from g0 to g1"""
+    n, ld = y.shape
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError("gate_apply_rows_: y must be contiguous float32 [N, ld]")
+    nat.check(nat.lib().alive_gate_apply_rows(nat.ptr(y), n, ld, nat.ptr(span_lo), nat.ptr(span_len), nat.ptr(g0), nat.ptr(g1),
+                                              nat.stream()), "alive_gate_apply_rows")
+    return y
+
+
 def resample_rows(x, orig_freq, new_freq, pre_scale, post_scale):
     """x [B, L] -> [B, L'] at new_freq with per-row linear gains (device float32 [B]): audio_io.resample row by row, the gains
     as 10^(dB/20); at equal rates the gains alone"""
@@ -995,15 +1058,21 @@ def db_scale(db):
     return float(10 ** (db / 20)) if db != 0 else 1.0
 
 
-_PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch")
+_PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold")
 
 
 class MultiStreamConverter:
     auto_pitch = False                 # (set per converter in __init__: whether the tick carries the auto-pitch kernel)
+    gate = False                       # (likewise: whether the tick carries the two gate kernels)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
-                 auto_pitch_half_life=10.0, auto_pitch_prior=0.5):
+                 auto_pitch_half_life=10.0, auto_pitch_prior=0.5, gate=False, gate_lookahead=None):
+        if not isinstance(gate, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: gate must be a bool, got {gate!r}")
+        if gate_lookahead is not None and (isinstance(gate_lookahead, (bool, np.bool_)) or not isinstance(
+                gate_lookahead, (int, float, np.integer, np.floating)) or not (np.isfinite(gate_lookahead) and gate_lookahead >= 0)):
+            raise ValueError(f"MultiStreamConverter: gate_lookahead={gate_lookahead!r} must be >= 0 seconds, or None (one chunk)")
         if not isinstance(auto_pitch, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: auto_pitch must be a bool, got {auto_pitch!r}")
         if auto_pitch_half_life is not None and not (np.isfinite(auto_pitch_half_life) and auto_pitch_half_life > 0):
@@ -1112,6 +1181,26 @@ class MultiStreamConverter:
             self.target = torch.zeros(B, dtype=torch.float32, device=dev)
             self.reg_state = torch.zeros(B, 2, dtype=torch.float64, device=dev)
             self.shift_eff = torch.zeros(B, dtype=torch.float32, device=dev)
+        # gate: the two gate kernels are part of the tick (captured once); per row, gate_on switches the session's gate, and the tick
+        # reads seg_len_eff / world_eff / follow where it read seg_len / world_on / emit.  gate_state is the session's, like phi
+        self.gate = bool(gate)
+        if self.gate:
+            self.tick_seconds = self.chunk / input_sr
+            self.gate_lookahead = self.tick_seconds if gate_lookahead is None else float(gate_lookahead)
+            self._gate_look16 = int(round(self.gate_lookahead * 16000))
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.gate_on = torch.zeros(B, **i32)
+            self.thr_ms = torch.zeros(B, dtype=torch.float64, device=dev)
+            self.hold_ticks = torch.zeros(B, **i32)
+            self.gate_state = torch.zeros(B, 2, **i32)
+            self.g0 = torch.ones(B, dtype=torch.float32, device=dev)
+            self.g1 = torch.ones(B, dtype=torch.float32, device=dev)
+            self.seg_len_eff = torch.zeros(B * self.S, **i32)
+            self.follow = torch.zeros(B, 1, dtype=torch.bool, device=dev)
+            self.world_eff = torch.zeros(B, **i32) if self.world_pitch else None
+            lo, ln = self._span(self.chunk)                # the emitted centre span of step(), per session rate (_set_rate)
+            self.span_lo = torch.full((B,), lo, **i32)
+            self.span_len = torch.full((B,), ln, **i32)
         self.phi = torch.zeros(B, 64, device=dev)
         self._in = torch.zeros(B, ld_in, device=dev)
         self._graph = None
@@ -1143,8 +1232,27 @@ class MultiStreamConverter:
             raise ValueError(f"slot {slot}: k={k} is above the converter's k_max={self.k_max}")
         return k
 
+    def _span(self, cs):
+        """the span of a session's output wave that step() emits, for chunks of cs samples: (first sample, length)"""
+        return self.buffersize * cs // 2 - cs // 2, 2 * (cs // 2)
+
+    def _session_gate(self, slot, p):
+        """a session's gate settings -> (on, thr_ms, hold_ticks), checked against the converter"""
+        db, hold = p.get("gate_db"), p.get("gate_hold", 0.2)
+        try:
+            ticks = gate_hold_ticks(hold, self.chunk / self.input_sr)
+            if db is None:
+                return 0, 0.0, 0
+            thr = gate_thr_ms(db)
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+        if not self.gate:
+            raise ValueError(f"slot {slot}: gate_db={db!r} needs a converter built with MultiStreamConverter(..., gate=True)")
+        return 1, thr, ticks
+
     def _apply(self, slot, p):
         k = self._session_k(slot, p["k"])
+        gate = self._session_gate(slot, p)
         names, weights = blend_spec(p["voice"], self.pool, k, self.S)
         world = p["world_pitch"]
         if not isinstance(world, (bool, np.bool_)):
@@ -1180,6 +1288,8 @@ class MultiStreamConverter:
         if self.auto_pitch:
             self.auto_on[slot] = int(bool(auto))
             self.target[slot] = target if auto else 0.0
+        if self.gate:
+            self.gate_on[slot], self.thr_ms[slot], self.hold_ticks[slot] = gate
 
     def _write_segments(self, slot, names):
         """the slot's rows of seg_lo / seg_len from where its voices lie in the pool now"""
@@ -1230,6 +1340,8 @@ class MultiStreamConverter:
         if self._rt is None:
             return
         c = self._chunks[rate]
+        if self.gate:
+            self.span_lo[slot], self.span_len[slot] = self._span(c)
         self.slot_chunk[slot] = c
         self.len_in[slot] = c * self.buffersize
         self.pair_in[slot] = self._rt.pair(rate, 16000)
@@ -1237,20 +1349,22 @@ class MultiStreamConverter:
         self.len_out[slot] = self._lout[rate]
 
     def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None,
-             auto_pitch=False):
+             auto_pitch=False, gate_db=None, gate_hold=0.2):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
         WORLD's f0 of the session's ring instead of the estimator's, f0_rate not applied (needs a world_pitch=True converter).
         auto_pitch=True (needs an auto_pitch=True converter and a register on every voice of the session): the pitch shift follows
-        the target voice's register, and `pitch` is an offset on top of it"""
+        the target voice's register, and `pitch` is an offset on top of it.  gate_db (needs a gate=True converter): the session's
+        input gate, a threshold in dBFS on its 16 kHz ring after the input gain (None: no gate); gate_hold: the seconds (>= 0) it
+        stays open after the last loud tick.  A gated session starts closed: its first chunk fades in"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
             raise ValueError(f"slot {slot}: rate {rate} Hz was not declared (rates={list(self.rates)}): pass it in "
                              "MultiStreamConverter(..., rates=...)")
         p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch,
-                 k=k, auto_pitch=auto_pitch)
+                 k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold)
         self._apply(slot, p)                                  # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -1260,10 +1374,13 @@ class MultiStreamConverter:
         self.phi[slot] = 0.0
         if self.auto_pitch:
             self.reg_state[slot] = 0.0                        # a new source: nothing heard yet
+        if self.gate:
+            self.gate_state[slot] = 0                         # closed, no hold: the first emitted chunk fades in
         return self
 
     def set(self, slot, **params):
-        """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch).
+        """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
+        gate_db, gate_hold; the gate's state is kept).
         The running source register is kept: a new voice changes the target only, and auto_pitch=True after False resumes from
         what the session had heard while it was on (nothing, if it never was)"""
         slot = self._slot(slot)
@@ -1298,8 +1415,21 @@ class MultiStreamConverter:
             self.auto_on[slot] = 0
             self.target[slot] = 0.0
             self.reg_state[slot] = 0.0
+        if self.gate:
+            self.gate_on[slot] = 0
+            self.thr_ms[slot] = 0.0
+            self.hold_ticks[slot] = 0
+            self.gate_state[slot] = 0
         self._set_rate(slot, int(self.input_sr))             # a closed slot: the converter's own rate, silence
         return self
+
+    def gate_open(self):
+        """the per-slot open flags after the latest tick, a list of B bools: a gated session's gate (False before its first emitting
+        tick), True for an open session without a gate, False for a closed slot.  One host read"""
+        if not self.gate:
+            raise ValueError("gate_open needs a converter built with MultiStreamConverter(..., gate=True)")
+        on, was = self.gate_on.tolist(), self.gate_state[:, 1].tolist()
+        return [bool(self.is_open[b] and (was[b] if on[b] else True)) for b in range(self.B)]
 
     # ------------------------------------------------------------------ device step
     def _f0_on_side_stream(self, spec, data):
@@ -1309,11 +1439,12 @@ class MultiStreamConverter:
             f0 = self.pe.estimate(spec, out=buf)
             rate = self.f0_rate
             if self.world_pitch:
-                buf.copy_(torch.where(self._world_sel, compute_f0_rows(data, self.world_on), buf))
+                buf.copy_(torch.where(self._world_sel, compute_f0_rows(data, self.world_eff if self.gate else self.world_on), buf))
                 f0, rate = buf, self.f0_rate_eff
             shift = self.pitch
             if self.auto_pitch:                               # the sessions' running registers -> this tick's shifts
-                shift = pitch_follow_rows_(f0, rate, self.pitch, self.auto_on, self.target, self.emit, self.auto_decay,
+                emit = self.follow if self.gate else self.emit      # (a gated session's register learns from open ticks only)
+                shift = pitch_follow_rows_(f0, rate, self.pitch, self.auto_on, self.target, emit, self.auto_decay,
                                            self.auto_prior, self.reg_state, self.shift_eff)
             return pitch_transform_rows_(f0, 1, rate, shift, self.intonation)
         return f0_on_side_stream(self, spec, body)
@@ -1325,25 +1456,32 @@ class MultiStreamConverter:
         else:
             data = resample_rows_multi(data, self.len_in, self.pair_in, self._rt, self._len16_rows, self._len16, self.in_pre,
                                        self.in_post)
+        seg_len = self.seg_len
+        if self.gate:                                         # this tick's live rows, before the f0 side stream forks off
+            w_lo, w_hi = gate_window(self.begin_of_output, self.end_of_output, data.shape[1], self._gate_look16)
+            gate_rows(data, w_lo, w_hi, self.gate_on, self.thr_ms, self.hold_ticks, self.emit,
+                      self.world_on if self.world_pitch else None, self.S, self.seg_len, self.gate_state, self.g0, self.g1,
+                      self.seg_len_eff, self.follow, self.world_eff)
+            seg_len = self.seg_len_eff
         spec = spectrogram(data)
         f0, join = self._f0_on_side_stream(spec, data)
         content = self.ce(spec)
         K = self.k_max
         if self.S == 1:
             if K is None:
-                val, idx = knn_search_grouped(content, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k)
+                val, idx = knn_search_grouped(content, self.pool.rows, self.pool.norms, self.seg_lo, seg_len, self.k)
                 content = merge_gather_rows(val, idx, self.k, self.alpha, self.pool.rows, content)
             else:                                             # every session at its own k (device array k_rows)
-                val, idx = knn_search_grouped_k(content, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k_rows, K)
+                val, idx = knn_search_grouped_k(content, self.pool.rows, self.pool.norms, self.seg_lo, seg_len, self.k_rows, K)
                 content = merge_gather_rows_k(val, idx, self.k_rows, K, self.alpha, self.pool.rows, content)
         else:                                                 # every slot's content once per list row, then the blend
             b, d, t = content.shape
             rep = content.unsqueeze(1).expand(b, self.S, d, t).reshape(b * self.S, d, t).contiguous()     # (B = 1: a view)
             if K is None:
-                val, idx = knn_search_grouped(rep, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k)
+                val, idx = knn_search_grouped(rep, self.pool.rows, self.pool.norms, self.seg_lo, seg_len, self.k)
                 content = blend_gather_rows(val, idx, self.k, self.first, self.weight, self.alpha, self.pool.rows, content)
             else:
-                val, idx = knn_search_grouped_k(rep, self.pool.rows, self.pool.norms, self.seg_lo, self.seg_len, self.k_lists, K)
+                val, idx = knn_search_grouped_k(rep, self.pool.rows, self.pool.norms, self.seg_lo, seg_len, self.k_lists, K)
                 content = blend_gather_rows_k(val, idx, self.k_rows, K, self.first, self.weight, self.alpha, self.pool.rows,
                                               content)
         join()
@@ -1356,6 +1494,8 @@ class MultiStreamConverter:
                 raise RuntimeError(f"decoder wave of {wave.shape[1]} samples, the multi-rate edge expects {self._lw}")
             wave = resample_rows_multi(wave, self._lw_rows, self.pair_out, self._rt, self.len_out, self._ld_out, self.out_pre,
                                        self.out_post)
+        if self.gate:
+            gate_apply_rows_(wave, self.span_lo, self.span_len, self.g0, self.g1)
         phi_next = torch.where(self.emit, phi_out[:, :, self.end_of_output], torch.zeros_like(phi))
         return wave, phi_next
 
@@ -1363,10 +1503,13 @@ class MultiStreamConverter:
         """capture the per-tick device pipeline over [B, ring] once; replays read the per-slot device arrays"""
         saved = self.phi.clone()
         saved_reg = self.reg_state.clone() if self.auto_pitch else None      # (capture_step runs the step three times)
+        saved_gate = self.gate_state.clone() if self.gate else None
         self._graph, self._g_out = capture_step(self.device, lambda: self._device_step(self._in, self.phi), self.phi)
         self.phi.copy_(saved)
         if saved_reg is not None:
             self.reg_state.copy_(saved_reg)
+        if saved_gate is not None:
+            self.gate_state.copy_(saved_gate)
         self._graph_pool_version = self.pool.version
         self.captures += 1
         return self
@@ -1383,13 +1526,15 @@ class MultiStreamConverter:
         self.phi.copy_(phi_next)
         return wave
 
-    def _repeat_on_bf16(self, saved_phi, saved_reg=None):
-        """RealtimeConverter._repeat_on_bf16 for the whole tick: modes 2, every slot's phase (and running register) restored, the
-        tick again"""
+    def _repeat_on_bf16(self, saved_phi, saved_reg=None, saved_gate=None):
+        """RealtimeConverter._repeat_on_bf16 for the whole tick: modes 2, every slot's phase (and running register, and gate state)
+        restored, the tick again"""
         ops.switch_to_bf16("multi-session streaming step", "tick")
         self.phi.copy_(saved_phi)
         if saved_reg is not None:
             self.reg_state.copy_(saved_reg)
+        if saved_gate is not None:
+            self.gate_state.copy_(saved_gate)
         if self._graph is not None:
             self.enable_graph()
         return audio_io.float_to_pcm16(self._run()).cpu().numpy()
@@ -1427,9 +1572,10 @@ class MultiStreamConverter:
         if guarded:
             saved_phi = self.phi.clone()
             saved_reg = self.reg_state.clone() if self.auto_pitch else None
+            saved_gate = self.gate_state.clone() if self.gate else None
         o = audio_io.float_to_pcm16(self._run()).cpu().numpy()
         if guarded and ops.f16_saturations(reset=True) > 0:
-            o = self._repeat_on_bf16(saved_phi, saved_reg)
+            o = self._repeat_on_bf16(saved_phi, saved_reg, saved_gate)
         for s in chunks:
             if emit[s]:
                 cs = self.slot_chunk[s]

@@ -3,6 +3,11 @@
 int16 chunk in -> ring of `buffersize` chunks -> spectrogram / content encoder / f0 / kNN /
 decoder over the whole ring (exactly what the reference recomputes per step) -> centre chunk out
 as int16, with the oscillator phase carried through phi[:, :, end_of_output].
+
+Input gate (`-thr`): RealtimeConverter(gate_db=DB, gate_hold=S) runs the two gate kernels of the multi-session path (csrc/gate.hip,
+module/multistream.py "Input gate") at N = 1: alive_gate_rows on the 16 kHz ring after the input gain, alive_gate_apply_rows on the
+final wave.  It mutes only: the single-library search has no row mask and runs on.  The gate's state lives beside the phase: `reset`
+and `enable_graph` zero it, the bf16 repeat restores it.  Without gate_db the converter launches what it did.
 """
 import numpy as np
 import torch
@@ -113,8 +118,14 @@ def capture_step(device, step, phi):
 class RealtimeConverter:
     def __init__(self, content_encoder, f0_estimator, decoder, library_tokens, device="cuda", chunk=960, buffersize=8,
                  input_sr=16000, output_sr=16000, f0_rate=1.0, pitch=0.0, k=4, alpha=0.0, gain=0.0, input_gain=0.0,
-                 reuse_interior="auto", world_pitch=False):
+                 reuse_interior="auto", world_pitch=False, gate_db=None, gate_hold=0.2, gate_lookahead=None):
         self.device = torch.device(device)
+        self.gate = gate_db is not None
+        if self.gate:                      # (checked before anything is built)
+            from .multistream import gate_hold_ticks, gate_thr_ms
+            thr, ticks = gate_thr_ms(gate_db), gate_hold_ticks(gate_hold, chunk / input_sr)
+            if gate_lookahead is not None and not (np.isfinite(gate_lookahead) and gate_lookahead >= 0):
+                raise ValueError(f"RealtimeConverter: gate_lookahead={gate_lookahead!r} must be >= 0 seconds, or None (one chunk)")
         self.ce, self.pe, self.dec = prepare_networks(content_encoder, f0_estimator, decoder, device)
         self.lib = library_tokens if isinstance(library_tokens, PackedLibrary) else PackedLibrary(library_tokens[0].to(device))
         self.chunk, self.buffersize = chunk, buffersize
@@ -125,6 +136,24 @@ class RealtimeConverter:
         self.phi = 0
         self._graph = None
         self.last_f0 = None
+        if self.gate:
+            # the multi-session gate at one row: an always-emitting session with one (unused) list row; _gate_state = (hold_left,
+            # was_open) is the stream's, like the phase
+            dev, i32 = self.device, dict(dtype=torch.int32, device=self.device)
+            self.gate_db, self.gate_hold = float(gate_db), float(gate_hold)
+            self._gate_look16 = int(round((chunk / input_sr if gate_lookahead is None else float(gate_lookahead)) * 16000))
+            self._gate_on = torch.ones(1, **i32)
+            self._gate_thr = torch.tensor([thr], dtype=torch.float64, device=dev)
+            self._gate_hold = torch.tensor([ticks], **i32)
+            self._gate_emit = torch.ones(1, dtype=torch.bool, device=dev)
+            self._gate_seg = torch.zeros(1, **i32)
+            self._gate_seg_eff = torch.zeros(1, **i32)
+            self._gate_follow = torch.zeros(1, dtype=torch.bool, device=dev)
+            self._gate_state = torch.zeros(1, 2, **i32)
+            self._g0 = torch.ones(1, device=dev)
+            self._g1 = torch.ones(1, device=dev)
+            self._span_lo = torch.tensor([buffersize * chunk // 2 - chunk // 2], **i32)
+            self._span_len = torch.tensor([2 * (chunk // 2)], **i32)
         self._side = None                  # side stream of the f0 estimator (see _f0_on_side_stream)
         self._f0_bufs = {}
         # interior reuse: only where it is exact -- no resampling in front (the ring IS the 16 kHz signal), a shift of whole
@@ -158,11 +187,28 @@ class RealtimeConverter:
         if self.reuse:
             return self._device_step_reuse(data, phi)
         data = audio_io.resample(data, self.input_sr, 16000, post_gain_db=self.input_gain)     # resample, then gain (:146-147)
+        self._gate_decide(data)
         content, f0 = self._front_end(spectrogram(data), data)
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0                  # (a view of the per-shape side-stream buffer: valid until the next step)
-        wave = audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain)[0]         # gain, then resample (:173-175)
+        wave = self._gate_edge(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain))[0]   # gain, then resample
         return wave, phi_out[:, :, self.end_of_output]
+
+    def _gate_decide(self, data):
+        """gate on: this step's decision from the 16 kHz ring `data` [1, L] (alive_gate_rows at one row) into _g0 / _g1"""
+        if self.gate:
+            from .multistream import gate_rows, gate_window
+            data = data.contiguous()
+            w_lo, w_hi = gate_window(self.begin_of_output, self.end_of_output, data.shape[1], self._gate_look16)
+            gate_rows(data, w_lo, w_hi, self._gate_on, self._gate_thr, self._gate_hold, self._gate_emit, None, 1, self._gate_seg,
+                      self._gate_state, self._g0, self._g1, self._gate_seg_eff, self._gate_follow, None)
+
+    def _gate_edge(self, wave):
+        """gate on: the fade (or the mute) on the emitted span of the final wave [1, L], in place"""
+        if self.gate:
+            from .multistream import gate_apply_rows_
+            wave = gate_apply_rows_(wave.contiguous(), self._span_lo, self._span_len, self._g0, self._g1)
+        return wave
 
     def _f0_on_side_stream(self, spec, data=None):
         """f0_on_side_stream with the estimator's f0 and the pitch transform.  With world_pitch the branch is WORLD's f0 of the
@@ -190,6 +236,7 @@ class RealtimeConverter:
         step's ring, `shift` frames further right.  Bitwise the full computation (tests/test_gpu_cli.py)."""
         F_, s = self.frames, self.shift
         data = data if self.input_gain == 0 else audio_io.gain(data, self.input_gain)
+        self._gate_decide(data)
         if not self._cache_valid:
             feat, f0 = self._front_end(spectrogram(data))
             self._c_feat.copy_(feat)
@@ -211,7 +258,7 @@ class RealtimeConverter:
             self._c_f0[:, :, a:].copy_(f0[:, :, margin:])
         wave, phi_out = self.dec(self._c_feat, f0=self._c_f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = self._c_f0
-        wave = audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain)[0]
+        wave = self._gate_edge(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain))[0]
         return wave, phi_out[:, :, self.end_of_output]
 
     def _front_end_slice(self, samples, f_lo, f_hi):
@@ -231,6 +278,8 @@ class RealtimeConverter:
         self._g_phi = torch.zeros(1, 64, device=self.device)
         self._graph, self._g_out = capture_step(self.device, lambda: self._device_step(self._g_in, self._g_phi), self._g_phi)
         self._g_phi.zero_()
+        if self.gate:
+            self._gate_state.zero_()       # (capture_step ran the step three times)
         self._cache_valid = False          # interior reuse: the captured step is the incremental one; the first real step runs in full
         return self
 
@@ -242,7 +291,15 @@ class RealtimeConverter:
         self._cache_valid = False
         if getattr(self, "_graph", None) is not None:
             self._g_phi.zero_()
+        if self.gate:
+            self._gate_state.zero_()
         return self
+
+    def gate_open(self):
+        """whether the gate was open at the end of the latest step (one host read)"""
+        if not self.gate:
+            raise ValueError("gate_open needs a converter built with RealtimeConverter(..., gate_db=DB)")
+        return bool(self._gate_state[0, 1].item())
 
     def step_device(self, ring_f32, continues=False):
         """ring float32 [1, buffersize*chunk] already on the device -> wave [L] (device); phase carried internally.
@@ -266,9 +323,10 @@ class RealtimeConverter:
         self.phi = phi_next
         return wave
 
-    def _repeat_on_bf16(self, data, saved_phi):
+    def _repeat_on_bf16(self, data, saved_phi, saved_gate=None):
         """a chunk drove an activation out of fp16's range: switch the process to bf16 planes (ops.switch_to_bf16), restore the
-        phase the chunk started from, drop the frame caches, re-capture the step if it was a hipGraph, and convert the chunk again"""
+        phase (and the gate state) the chunk started from, drop the frame caches, re-capture the step if it was a hipGraph, and
+        convert the chunk again"""
         ops.switch_to_bf16("streaming step", "chunk")
         self._cache_valid = False
         if getattr(self, "_graph", None) is not None:
@@ -276,6 +334,8 @@ class RealtimeConverter:
             self._g_phi.copy_(saved_phi)
         else:
             self.phi = saved_phi
+        if saved_gate is not None:
+            self._gate_state.copy_(saved_gate)
         wave = self.step_device(data, continues=False)
         return audio_io.float_to_pcm16(wave).cpu().numpy()
 
@@ -292,9 +352,10 @@ class RealtimeConverter:
         guarded = fp16_guarded(self.frames)
         if guarded:
             saved_phi = self._g_phi.clone() if getattr(self, "_graph", None) is not None else self.phi
+            saved_gate = self._gate_state.clone() if self.gate else None
         wave = self.step_device(data, continues=True)                # this ring is the previous one advanced by one chunk
         out = audio_io.float_to_pcm16(wave).cpu().numpy()            # C cast of numpy's astype, no clipping (:180-183)
         if guarded and ops.f16_saturations(reset=True) > 0:          # (the copy above has synchronised: six 4-byte reads)
-            out = self._repeat_on_bf16(data, saved_phi)
+            out = self._repeat_on_bf16(data, saved_phi, saved_gate)
         center = self.buffersize * self.chunk // 2
         return out[center - self.chunk // 2: center + self.chunk // 2]

@@ -12,6 +12,9 @@ The sessions file is a JSON list; each entry:
                                           voice's register (module/multistream.py "Auto pitch"); "pitch" is then an offset on top
    "register_hz": 180,                    optional: declares the register (mean f0 in Hz) of a voice given by "lib" alone, which
                                           has no audio to measure it on; a "target" wav's register is measured at enrolment
+   "gate_db": -40, "gate_hold": 0.2,      optional: the session's input gate (module/multistream.py "Input gate"): a threshold in
+                                          dBFS on its 16 kHz ring after the input gain (null: no gate; default -thr) and the
+                                          seconds it stays open after the last loud tick (default --gate-hold)
    "blend": [{"target": "a.wav", "weight": 2}, {"lib": "b.pt", "weight": 1}],   instead of "target" / "lib": a weighted mix
                                           of 1 to 4 voices, each component a voice source as above (multistream.blend_spec)
    "start": 0,                            optional: the tick at which the session joins
@@ -28,6 +31,8 @@ It is built with k_max = the largest "k" only if some session's "k" differs from
 before.  Sessions on one voice at different k take one pass over that voice per k.
 The converter carries the auto-pitch kernel, and the voices are given registers (measured with the f0 estimator on the target wavs),
 only if some session is on auto pitch: a file without "auto_pitch", run without --auto-pitch, runs as before.
+The converter carries the two gate kernels only if some session ends up gated ("gate_db", or -thr): a file without the keys, run
+without -thr, runs as before.
 WORLD needs rings of about 230 ms or more (-c 960 -b 8 is 480 ms): a shorter ring comes out unvoiced.
 Flags shared with realtime_inference.py keep its spelling: -c, -b, -k, -isr, -osr, --no-graph.
 
@@ -53,12 +58,13 @@ from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
 from module.multistream import (MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
-                                measure_register)
+                                gate_hold_ticks, gate_thr_ms, measure_register)
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
 SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "start", "sr", "output",
                 "blend", "k", "auto_pitch", "register_hz")
+GATE_KEYS = ("gate_db", "gate_hold")     # taken per session too; a loaded session carries them only when it is gated
 
 
 def build_parser():
@@ -80,6 +86,11 @@ def build_parser():
                              "removed after their last session (default: every voice is packed before tick 0)")
     parser.add_argument('--auto-pitch', action='store_true',
                         help="sessions follow their target voice's register unless their \"auto_pitch\" says otherwise")
+    parser.add_argument('-thr', '--gate-db', default=None, type=float,
+                        help="input gate: sessions mute (and skip their search) below this level in dBFS unless their \"gate_db\" "
+                             "says otherwise (default: no gate)")
+    parser.add_argument('--gate-hold', default=0.2, type=float,
+                        help="seconds a gate stays open after the last loud tick (default 0.2; a session's \"gate_hold\" overrides)")
     parser.add_argument('--no-graph', action='store_true',
                         help="launch the per-tick device pipeline kernel by kernel instead of replaying one captured hipGraph")
     return parser
@@ -109,10 +120,25 @@ def declared_registers(entries, name_of):
     return out
 
 
-def load_sessions(path, k=4, auto_pitch=False):
+def session_gate(s, where, gate_db=None, gate_hold=0.2):
+    """an entry's gate -> (gate_db, gate_hold), or None for a session without a gate: "gate_db" (default `gate_db`; a JSON null
+    switches the gate off) a finite number, "gate_hold" (default `gate_hold`) a finite number >= 0; ValueError otherwise"""
+    db, hold = s.get("gate_db", gate_db), s.get("gate_hold", gate_hold)
+    try:
+        gate_hold_ticks(hold, 1.0)
+        if db is not None:
+            gate_thr_ms(db)
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return None if db is None else (float(db), float(hold))
+
+
+def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
-    `auto_pitch`); ValueError on a malformed entry"""
+    `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
+    neither, so a file without the keys loads to what it did; ValueError on a malformed entry"""
     k = check_k(k, "-k")
+    session_gate({}, "-thr / --gate-hold", gate_db, gate_hold)
     with open(path) as f:
         sessions = json.load(f)
     if not isinstance(sessions, list) or not sessions:
@@ -122,9 +148,10 @@ def load_sessions(path, k=4, auto_pitch=False):
     for i, s in enumerate(sessions):
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
-        unknown = set(s) - set(SESSION_KEYS)
+        unknown = set(s) - set(SESSION_KEYS) - set(GATE_KEYS)
         if unknown:
-            raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: {SESSION_KEYS})")
+            raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: {SESSION_KEYS + GATE_KEYS})")
+        gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))      # noqa: E731
         blend = blend_sources(s, f"session {i}", rel) if "blend" in s else None
         if blend is None and s.get("target") is None and s.get("lib") is None:
@@ -143,6 +170,8 @@ def load_sessions(path, k=4, auto_pitch=False):
             raise ValueError(f"session {i}: start tick {e['start']} < 0")
         if e["sr"] is not None and e["sr"] <= 0:
             raise ValueError(f"session {i}: sample rate {e['sr']} <= 0")
+        if gate is not None:
+            e["gate_db"], e["gate_hold"] = gate
         out.append(e)
     return out
 
@@ -273,7 +302,7 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    sessions = load_sessions(args.sessions, args.k, args.auto_pitch)
+    sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold)
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -305,9 +334,11 @@ def main(argv=None):
     conv = MultiStreamConverter(CE, PE, Dec, pool, slots, chunk=args.chunk, buffersize=args.buffersize, input_sr=args.input_sr,
                                 output_sr=args.output_sr, k=args.k, device=device, rates=sorted(set(in_sr)),
                                 world_pitch=any(s["world_pitch"] for s in sessions), blend=blend_size(sessions),
-                                k_max=converter_k_max(sessions, args.k), auto_pitch=auto)
+                                k_max=converter_k_max(sessions, args.k), auto_pitch=auto,
+                                **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
-                   input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"])
+                   input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
+                   **{g: s[g] for g in GATE_KEYS if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()

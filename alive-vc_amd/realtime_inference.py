@@ -50,6 +50,11 @@ def build_parser():
     parser.add_argument('-fp16', default=False, type=bool)
     parser.add_argument('-lib', '--voice-library-path', default="NONE")
     parser.add_argument('-wpe', '--world-pitch-estimation', default=False, type=bool)
+    parser.add_argument('-thr', '--threshold', default=None, type=float,
+                        help="input gate: mute the output while the input stays below this level in dBFS, measured on the 16 kHz "
+                             "ring after -ig, with a fade at both edges (default: no gate)")
+    parser.add_argument('--gate-hold', default=0.2, type=float,
+                        help="seconds the gate stays open after the last chunk above -thr (default 0.2; this build only)")
     parser.add_argument('-isr', '--input-sr', default=16000, type=int)
     parser.add_argument('-osr', '--output-sr', default=16000, type=int)
     parser.add_argument('-lsr', '--loopback-sr', default=16000, type=int)
@@ -91,7 +96,8 @@ def main(argv=None):
     rt = RealtimeConverter(CE, PE, Dec, tgt.contiguous(), device, chunk=args.chunk, buffersize=args.buffersize,
                            input_sr=args.input_sr, output_sr=args.output_sr, f0_rate=args.f0_rate, pitch=args.pitch,
                            k=args.k, alpha=args.alpha, gain=args.gain, input_gain=args.input_gain,
-                           world_pitch=bool(args.world_pitch_estimation))   # -wpe: WORLD f0, -f0 not applied (as the reference)
+                           world_pitch=bool(args.world_pitch_estimation),   # -wpe: WORLD f0, -f0 not applied (as the reference)
+                           **(dict(gate_db=args.threshold, gate_hold=args.gate_hold) if args.threshold is not None else {}))
     if not args.no_graph:
         rt.enable_graph()        # the whole per-chunk device pipeline (~150 launches) captured once, replayed per chunk: same samples
     print("streaming: conversion running (Ctrl-C stops)")

@@ -787,6 +787,35 @@ int alive_pitch_follow_rows(const float* f0, int N, int T, const float* f0_rate,
                             const float* target, const unsigned char* emit, double decay, double prior, double* state,
                             float* shift_out, void* stream);
 
+/* Input gate of the streaming paths (csrc/gate.hip): which rows are live this tick, decided on the device, and the output edge.
+ * All pointers are DEVICE pointers; no call allocates, synchronises or reads anything on the host; the grids depend on N and the
+ * strides alone (graph-capturable: a captured call serves any settings).  No floating-point atomics.
+ *   alive_gate_rows         one block per row n of x[N][ld] (the 16 kHz rings after the input resample and gain).  Per row: gate_on
+ *                           int32, thr_ms double (the threshold as a mean square), hold_ticks int32, emit bytes, world_on int32 (may
+ *                           be NULL, then world_eff must be NULL too); S list rows per row with seg_len int32 [N*S]; state int32
+ *                           [N][2] = (hold_left, was_open).  ms = (sum of x[n][t]^2, t in [w_lo, w_hi)) / (w_hi - w_lo) in fp64 in a
+ *                           fixed order (thread tid: t = w_lo + tid, + 256, ...; then a pairwise tree over the 256 partial sums):
+ *                           bitwise reproducible, and the same for a row alone and in any batch.
+ *                             gate_on[n] == 0 or emit[n] == 0: g0 = g1 = 1, seg_len_eff = seg_len, follow = emit, world_eff =
+ *                               world_on, state[n] untouched (ms_out[n] = 0);
+ *                             else loud = ms >= thr_ms[n].  loud: left = hold_ticks[n], open = 1.  Not loud: open = left > 0, then
+ *                               left = max(left - 1, 0) -- the gate stays open for exactly hold_ticks ticks after the last loud one.
+ *                               g0 = was_open, g1 = open, was_open <- open; skip = g0 == 0 && g1 == 0 (closed at both ends of the
+ *                               chunk); seg_len_eff[n*S + s] = skip ? 0 : seg_len[n*S + s]; world_eff = world_on && !skip; follow =
+ *                               open (emit is nonzero here).
+ *                           Outputs: g0, g1 float [N]; seg_len_eff int32 [N*S]; follow bytes [N]; world_eff int32 [N] or NULL; ms_out
+ *                           double [N] or NULL (the level, for tests and meters).  0 <= w_lo < w_hi <= ld.
+ *   alive_gate_apply_rows   in place on y[N][ld] (the final waves): for i in [0, span_len[n]) with 0 <= span_lo[n] + i < ld,
+ *                           y[n][span_lo[n] + i] *= g0[n] + (g1[n] - g0[n]) * ((float)(i + 1) / (float)span_len[n]) in float32, every
+ *                           operation rounded on its own.  A row with g0 == g1 == 1 is not touched (no load, no store); a row with
+ *                           g0 == g1 == 0 gets +0.0f stored over its span without a load (a NaN there does not leak); samples outside
+ *                           the span are never written.  N <= 65535. */
+int alive_gate_rows(const float* x, int N, int ld, int w_lo, int w_hi, const int* gate_on, const double* thr_ms,
+                    const int* hold_ticks, const unsigned char* emit, const int* world_on, int S, const int* seg_len, int* state,
+                    float* g0, float* g1, int* seg_len_eff, unsigned char* follow, int* world_eff, double* ms_out, void* stream);
+int alive_gate_apply_rows(float* y, int N, int ld, const int* span_lo, const int* span_len, const float* g0, const float* g1,
+                          void* stream);
+
 /* WORLD pitch estimation (`-wpe`): DIO + StoneMask on N rows of L8 samples at fs, in fp64   (reference module/common.py:113-137,
  * pyworld.dio(x, fs, f0_floor, f0_ceil, channels_in_octave=2, frame_period, speed=1, allowed_range=0.1) then pyworld.stonemask).
  * Restated from the published algorithm (tools/world_ref.py is the NumPy restatement; parity with pyworld is unpinned).

@@ -15,7 +15,12 @@ kmax8_uniform4_* every session at k = 4 through them (next to graph_tick_*: the 
 kmax8_mixed_* session s at k = (1, 2, 4, 8)[s % 4] -- on the shared voice that is one pass over the voice per k.  --auto-pitch adds
 the graph tick p50 / p99 of an auto_pitch=True converter with every session on auto pitch (auto_pitch_tick_*: one more small launch on
 the f0 side stream, alive_pitch_follow_rows; voice v_i is declared a register of 110 + 10 (i % 12) Hz) next to graph_tick_* of the same
-batch.  --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
+batch.  --gated adds, per fraction f, the graph tick p50 / p99 of a gate=True converter (the input gate: csrc/gate.hip) whose sessions all
+carry a -40 dB gate, sessions s < round(f B) fed digital silence (their gates stay closed: no search for them) and the others the usual
+speech-level signal (their gates stay open), and the event-timed grouped search over the segment lengths that tick left in seg_len_eff
+(gated_<f>_tick_p50_ms / _p99_ms / _search_ms / _live_rows); and the gate=False converter a second time (gate_off_again_tick_*): the
+spread between its two measurements is the yardstick for the gate's overhead at fraction 0.
+--enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
 one more 50 000-row voice added between two ticks, once on a default pool (the add re-packs the pool and the next tick
 re-captures) and once on a reserved pool of 65 x 50 000 rows (VoicePool(capacity=...): alive_pool_append into the table in
 place); per pool the wall time of the add (bracketed by device synchronisation; add_device_ms: events around it), the latency of
@@ -26,7 +31,7 @@ python tools/bench_multistream.py --quick).  Prints one JSON line per configurat
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch]
-                                      [--out multistream.json]
+                                      [--gated 0,0.5,1] [--out multistream.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
 """
 import argparse
@@ -55,10 +60,10 @@ def make_pool(n_voices, seed=0):
     return MS.VoicePool({f"v{i}": torch.randn(768, VOICE_ROWS, device="cuda", generator=g) for i in range(n_voices)})
 
 
-def time_ticks(conv, B, chunk, ticks, warmup, seed):
-    """chunk: one length, or a list of per-slot lengths (sessions at their own rates)"""
+def time_ticks(conv, B, chunk, ticks, warmup, seed, silent=0):
+    """chunk: one length, or a list of per-slot lengths (sessions at their own rates); sessions s < silent send digital silence"""
     cs = list(chunk) if isinstance(chunk, (list, tuple)) else [chunk] * B
-    pcm = [(synthetic.make_waveform(cs[s] * 4, seed + s)[0].numpy() * 12000).astype(np.int16) for s in range(B)]
+    pcm = [(synthetic.make_waveform(cs[s] * 4, seed + s)[0].numpy() * (0 if s < silent else 12000)).astype(np.int16) for s in range(B)]
     ts = []
     for t in range(warmup + ticks):
         feed = {s: pcm[s][(t % 4) * cs[s]:(t % 4 + 1) * cs[s]] for s in range(B)}
@@ -148,18 +153,20 @@ def enrol_leg(nets, B=64, chunk=160, bs=16, steady=30, warmup=6):
     return recs
 
 
-def time_search(conv, B, reps=20):
-    """the grouped search alone on the tick's shape: (ms per call, bytes of distinct segments read once)"""
+def time_search(conv, B, reps=20, seg_len=None):
+    """the grouped search alone on the tick's shape: (ms per call, bytes of distinct segments read once).  seg_len: the segment
+    lengths to search with (default: the converter's; a gated converter's seg_len_eff has its closed rows at 0)"""
+    seg_len = conv.seg_len if seg_len is None else seg_len
     src = torch.randn(B, 768, conv.frames, device="cuda")
     for _ in range(3):
-        MS.knn_search_grouped(src, conv.pool.rows, conv.pool.norms, conv.seg_lo, conv.seg_len, conv.k)
+        MS.knn_search_grouped(src, conv.pool.rows, conv.pool.norms, conv.seg_lo, seg_len, conv.k)
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
     for _ in range(reps):
-        MS.knn_search_grouped(src, conv.pool.rows, conv.pool.norms, conv.seg_lo, conv.seg_len, conv.k)
+        MS.knn_search_grouped(src, conv.pool.rows, conv.pool.norms, conv.seg_lo, seg_len, conv.k)
     b.record()
     torch.cuda.synchronize()
-    segs = {(int(lo), int(ln)) for lo, ln in zip(conv.seg_lo.tolist(), conv.seg_len.tolist()) if ln > 0}
+    segs = {(int(lo), int(ln)) for lo, ln in zip(conv.seg_lo.tolist(), seg_len.tolist()) if ln > 0}
     return a.elapsed_time(b) / reps, sum(ln for _, ln in segs) * (768 + 1) * 4
 
 
@@ -177,6 +184,8 @@ def main():
     ap.add_argument("--mixed-k", action="store_true", help="also time a k_max=8 converter: every session at k = 4, and an even "
                                                            "mix of k = 1, 2, 4, 8")
     ap.add_argument("--auto-pitch", action="store_true", help="also time an auto_pitch=True converter, every session on auto pitch")
+    ap.add_argument("--gated", default=None, help="comma-separated fractions: also time a gate=True converter, every session behind "
+                                                  "a -40 dB gate and that fraction of them fed digital silence")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
                                                          "default and on a reserved pool")
     ap.add_argument("--out", default=None)
@@ -186,6 +195,7 @@ def main():
     rates = [int(r) for r in args.rates.split(",")] if args.rates else None
     mixes = tuple(args.voices.split(","))
     worlds = args.world.split(",") if args.world else []
+    gated = args.gated.split(",") if args.gated else []
     if args.quick:
         batches, configs, mixes = [64], [(160, 16)], ("distinct",)
     nets = (ContentEncoder(seed=2), F0Estimator(seed=2), Decoder(seed=2))
@@ -269,6 +279,27 @@ def main():
                     rec["auto_pitch_tick_p50_ms"], rec["auto_pitch_tick_p99_ms"] = round(p50, 3), round(p99, 3)
                     rec["auto_pitch_real_time"] = p99 < period_ms
                     del ac
+                for f in gated:
+                    gc = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, gate=True)
+                    silent = int(round(float(f) * B))
+                    for s in range(B):
+                        gc.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, gate_db=-40.0)
+                    gc.enable_graph()
+                    p50, p99 = time_ticks(gc, B, chunk, args.ticks, args.warmup + bs + 1, 300, silent=silent)
+                    rec[f"gated_{f}_tick_p50_ms"], rec[f"gated_{f}_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                    live = sum(gc.gate_open())
+                    assert live == B - silent and gc.captures == 1, (live, B, silent, gc.captures)
+                    rec[f"gated_{f}_live_rows"] = live
+                    rec[f"gated_{f}_search_ms"] = round(time_search(gc, B, seg_len=gc.seg_len_eff)[0], 4)
+                    del gc
+                if gated:                                      # the gate=False converter once more: the run-to-run spread
+                    again = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4)
+                    for s in range(B):
+                        again.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5)
+                    again.enable_graph()
+                    p50, p99 = time_ticks(again, B, chunk, args.ticks, args.warmup + bs + 1, 300)
+                    rec["gate_off_again_tick_p50_ms"], rec["gate_off_again_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                    del again
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
                 rows.append(rec)
