@@ -6,7 +6,10 @@ The reference fills 512 fixed slots with one random content frame from each of u
 MI355X, takes --frames-per-clip frames per clip, is seedable, and writes any M (--num-tokens,
 default 512 so the file stays loadable by the reference's VoiceLibrary()).  --dedup COS drops frames whose cosine
 to an earlier kept frame exceeds COS (silence and sustained vowels fill real corpora with near-duplicates that only
-dilute a k = 4 match); the scan is the library's own kNN kernel run against itself.
+dilute a k = 4 match); the scan is the library's own kNN kernel run against itself.  --codebook SIZE then condenses the filled
+slots to SIZE centroid rows by k-means (module/codebook.py; --seed seeds its init) and writes tokens [1, 768, SIZE]: --num-tokens
+100000 --frames-per-clip 8 --dedup 0.98 --codebook 512 is a whole-corpus library that the reference's VoiceLibrary() loads.  What a
+codebook does to conversion quality on real voices is not measured.
 """
 import argparse
 import glob
@@ -100,8 +103,13 @@ def main(argv=None):
     parser.add_argument('--seed', default=None, type=int)
     parser.add_argument('--dedup', default=None, type=float, metavar="COS",
                         help="drop a frame when an earlier frame of the library has cosine similarity above COS")
+    parser.add_argument('--codebook', default=None, type=int, metavar="SIZE",
+                        help="condense the frames that were collected (after --dedup) to SIZE centroid rows by k-means")
+    parser.add_argument('--codebook-iters', default=10, type=int, metavar="N", help="k-means iterations at most (default 10)")
     parser.add_argument('-d', '--device', default='cuda')
     args = parser.parse_args(argv)
+    if args.codebook is not None and args.codebook < 1:
+        parser.error("--codebook must be >= 1")
     rng = random.Random(args.seed)
     device = torch.device(args.device)
     CE = ContentEncoder().to(device)
@@ -130,6 +138,16 @@ def main(argv=None):
         print(f"dedup: {filled - kept.shape[1]} of {filled} frames have an earlier neighbour above cos {args.dedup}")
         VL.tokens = torch.cat([kept, VL.tokens[0, :, filled:]], 1).unsqueeze(0).contiguous()
         filled = kept.shape[1]
+    if args.codebook is not None:
+        from module.codebook import build_codebook
+        st = {}
+        book = build_codebook(VL.tokens[0, :, :filled].to(device), args.codebook, iters=args.codebook_iters,
+                              seed=0 if args.seed is None else args.seed, stats=st)
+        if st:
+            print(f"codebook: {filled} frames -> {book.shape[1]} centroids in {st['iterations']} iterations "
+                  f"({st['empty_clusters']} clusters without members, mean best cosine {st['objective'][-1] / filled:.4f})")
+        VL.tokens = book.cpu().unsqueeze(0).contiguous()
+        filled = book.shape[1]
     print(f"saving ({filled} of {VL.tokens.shape[2]} slots from data)")
     torch.save(VL.state_dict(), args.voice_library_path)
     print("done")

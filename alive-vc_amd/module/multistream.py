@@ -608,13 +608,16 @@ def measure_register(f0_estimator, wf16, world_pitch=False):
     return s, c
 
 
-def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="cuda", f0_estimator=None, world_pitch=False):
+def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="cuda", f0_estimator=None, world_pitch=False,
+                codebook=None, codebook_iters=10, codebook_seed=0):
     """A voice's tokens as realtime_inference.py builds its library, as strided [768, m] parts and without a copy: the target
     utterance `wav` [channels, samples] at `sr` Hz -- resampled to 16 kHz, peak-normalised, first channel, content_encoder(
     spectrogram(.)), every `every`-th frame (a column-strided view of the encoder's output) -- then the tokens of `lib` (a voice
     library file, or its tokens [1, 768, M] / [768, M]).  The encoder runs under ops.Fp16Guard, as generate_voice_library.py's.
     f0_estimator= (auto pitch): returns (parts, register) instead, the register measured on the same 16 kHz audio the encoder saw
-    (measure_register; world_pitch: with WORLD's f0), None without a target wav.  Without it the call is what it was."""
+    (measure_register; world_pitch: with WORLD's f0), None without a target wav.  Without it the call is what it was.
+    codebook=SIZE: the parts are condensed together, once, to one part of SIZE centroid rows (module/codebook.py build_codebook with
+    codebook_iters and codebook_seed; a voice of SIZE rows or fewer stays as it is); the register is measured on the audio as before."""
     from .voice_library import VoiceLibrary
     parts, register = [], None
     if wav is not None:
@@ -632,24 +635,32 @@ def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="c
         parts.append(_tokens_2d(lib))
     if not parts:
         raise ValueError("a voice needs a target wav and / or a voice library")
+    if codebook is not None:
+        from .codebook import build_codebook, check_size
+        check_size(codebook)
+        if sum(int(t.shape[1]) for t in parts) > codebook:
+            whole = torch.cat([t.to(device, torch.float32) for t in parts], dim=1)
+            parts = [build_codebook(whole, codebook, iters=codebook_iters, seed=codebook_seed)]
     return parts if f0_estimator is None else (parts, register)
 
 
 def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False, f0_estimator=None,
-                world_pitch=False):
+                world_pitch=False, codebook=None, codebook_iters=10, codebook_seed=0):
     """enrol_voice as a generator: the utterance is encoded once, then each next() appends one piece -- `add` for the first, `extend`
     for the rest -- and yields the voice's row count so far, so that a server can put a tick between the pieces.  If a piece is
     refused the voice is removed again (when no session holds it yet) and the error propagates.  f0_estimator=: the utterance's
-    register is measured too (voice_parts) and stored with the first piece."""
+    register is measured too (voice_parts) and stored with the first piece.  codebook=SIZE: the voice is condensed to SIZE centroids
+    first (voice_parts), and the centroids are appended in pieces."""
     if pool.capacity is None:
         raise ValueError("enrol_voice needs a reserved pool: VoicePool(..., capacity=ROWS)")
     if max_frames is not None and int(max_frames) < 1:
         raise ValueError(f"max_frames={max_frames!r} must be >= 1")
     register = None
+    cb = {} if codebook is None else dict(codebook=codebook, codebook_iters=codebook_iters, codebook_seed=codebook_seed)
     if f0_estimator is None:
-        parts = voice_parts(content_encoder, wav, sr, lib, every, pool.device)
+        parts = voice_parts(content_encoder, wav, sr, lib, every, pool.device, **cb)
     else:
-        parts, register = voice_parts(content_encoder, wav, sr, lib, every, pool.device, f0_estimator, world_pitch)
+        parts, register = voice_parts(content_encoder, wav, sr, lib, every, pool.device, f0_estimator, world_pitch, **cb)
     total = sum(int(t.shape[1]) for t in parts)
     step = total if max_frames is None else int(max_frames)
     if compact and pool.largest_hole < min(step, total) <= pool.free_rows:
@@ -686,7 +697,7 @@ def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
 
 
 def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False, f0_estimator=None,
-                world_pitch=False):
+                world_pitch=False, codebook=None, codebook_iters=10, codebook_seed=0):
     """Enrol a voice into a reserved pool from audio, while sessions run on the pool's other voices: the recipe of voice_parts
     (multistream_inference.voice_tokens', under ops.Fp16Guard), appended through the strided alive_pool_append -- the encoder's
     output is never copied or concatenated.  The voice's rows are bitwise those of voice_tokens followed by `add`.
@@ -696,9 +707,12 @@ def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
     is encoded once and its tokens are appended piece by piece, which is bitwise one call for any max_frames (a row and its norm
     depend on the row's own token alone).  compact=True: compact the pool first when the first piece fits its free rows but none
     of its holes.  f0_estimator= (auto pitch): the voice also gets its register, measured on the same audio (voice_parts).
+    codebook=SIZE (with codebook_iters, codebook_seed): the voice goes in as its SIZE-row codebook (module/codebook.py), bitwise
+    `add(name, build_codebook(tokens, SIZE))`; `compact=` is about the pool's holes and has nothing to do with it.
     Returns the voice's row count."""
     rows = 0
-    for rows in enrol_steps(pool, name, content_encoder, wav, sr, lib, every, max_frames, compact, f0_estimator, world_pitch):
+    for rows in enrol_steps(pool, name, content_encoder, wav, sr, lib, every, max_frames, compact, f0_estimator, world_pitch,
+                            codebook, codebook_iters, codebook_seed):
         pass
     return rows
 

@@ -15,6 +15,9 @@ The sessions file is a JSON list; each entry:
    "gate_db": -40, "gate_hold": 0.2,      optional: the session's input gate (module/multistream.py "Input gate"): a threshold in
                                           dBFS on its 16 kHz ring after the input gain (null: no gate; default -thr) and the
                                           seconds it stays open after the last loud tick (default --gate-hold)
+   "codebook": 4096,                      optional, an integer >= 1 or null (default: --codebook): the session's voice is condensed to
+                                          that many centroid rows by k-means when it is packed or enrolled (module/codebook.py); a
+                                          voice of that many rows or fewer stays as it is.  A codebook's rows are means: use k 1 or 2
    "blend": [{"target": "a.wav", "weight": 2}, {"lib": "b.pt", "weight": 1}],   instead of "target" / "lib": a weighted mix
                                           of 1 to 4 voices, each component a voice source as above (multistream.blend_spec)
    "start": 0,                            optional: the tick at which the session joins
@@ -33,6 +36,9 @@ The converter carries the auto-pitch kernel, and the voices are given registers 
 only if some session is on auto pitch: a file without "auto_pitch", run without --auto-pitch, runs as before.
 The converter carries the two gate kernels only if some session ends up gated ("gate_db", or -thr): a file without the keys, run
 without -thr, runs as before.
+The voices are condensed only for sessions with a "codebook" (or under --codebook): a file without the key, run without the flag, runs
+as before.  The size is part of the voice's pool name: sessions on the same sources at different sizes get different voices; a blend's
+components are each condensed to the session's size.
 WORLD needs rings of about 230 ms or more (-c 960 -b 8 is 480 ms): a shorter ring comes out unvoiced.
 Flags shared with realtime_inference.py keep its spelling: -c, -b, -k, -isr, -osr, --no-graph.
 
@@ -65,6 +71,7 @@ from module.voice_library import VoiceLibrary                    # noqa: E402
 SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "start", "sr", "output",
                 "blend", "k", "auto_pitch", "register_hz")
 GATE_KEYS = ("gate_db", "gate_hold")     # taken per session too; a loaded session carries them only when it is gated
+CODEBOOK_KEYS = ("codebook",)            # taken per session too; a loaded session carries it only when its voice is condensed
 
 
 def build_parser():
@@ -91,6 +98,9 @@ def build_parser():
                              "says otherwise (default: no gate)")
     parser.add_argument('--gate-hold', default=0.2, type=float,
                         help="seconds a gate stays open after the last loud tick (default 0.2; a session's \"gate_hold\" overrides)")
+    parser.add_argument('--codebook', default=None, type=int, metavar="SIZE",
+                        help="condense every session's voice to SIZE centroid rows by k-means unless its \"codebook\" says otherwise "
+                             "(default: the voices as they are)")
     parser.add_argument('--no-graph', action='store_true',
                         help="launch the per-tick device pipeline kernel by kernel instead of replaying one captured hipGraph")
     return parser
@@ -133,11 +143,24 @@ def session_gate(s, where, gate_db=None, gate_hold=0.2):
     return None if db is None else (float(db), float(hold))
 
 
-def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2):
+def session_codebook(s, where, codebook=None):
+    """an entry's "codebook" (default `codebook`) -> an integer >= 1, or None for a voice that stays as it is (a JSON null switches
+    the default off); ValueError otherwise"""
+    size = s.get("codebook", codebook)
+    if size is None:
+        return None
+    if isinstance(size, bool) or not isinstance(size, int) or size < 1:
+        raise ValueError(f"{where}: \"codebook\" must be an integer >= 1 or null, got {size!r}")
+    return size
+
+
+def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
-    neither, so a file without the keys loads to what it did; ValueError on a malformed entry"""
+    neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
+    condensed; ValueError on a malformed entry"""
     k = check_k(k, "-k")
+    session_codebook({}, "--codebook", codebook)
     session_gate({}, "-thr / --gate-hold", gate_db, gate_hold)
     with open(path) as f:
         sessions = json.load(f)
@@ -148,10 +171,11 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2):
     for i, s in enumerate(sessions):
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
-        unknown = set(s) - set(SESSION_KEYS) - set(GATE_KEYS)
+        unknown = set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(CODEBOOK_KEYS)
         if unknown:
-            raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: {SESSION_KEYS + GATE_KEYS})")
+            raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: {SESSION_KEYS + GATE_KEYS + CODEBOOK_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
+        size = session_codebook(s, f"session {i}", codebook)
         rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))      # noqa: E731
         blend = blend_sources(s, f"session {i}", rel) if "blend" in s else None
         if blend is None and s.get("target") is None and s.get("lib") is None:
@@ -172,20 +196,23 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2):
             raise ValueError(f"session {i}: sample rate {e['sr']} <= 0")
         if gate is not None:
             e["gate_db"], e["gate_hold"] = gate
+        if size is not None:
+            e["codebook"] = size
         out.append(e)
     return out
 
 
-def voice_name(target, lib):
-    """the pool name of a voice source: sessions and blend components with the same sources share one voice"""
-    return json.dumps([target, lib])
+def voice_name(target, lib, codebook=None):
+    """the pool name of a voice source: sessions and blend components with the same sources share one voice -- at the same codebook
+    size: the size is part of the name (none: the name it always had)"""
+    return json.dumps([target, lib] if codebook is None else [target, lib, codebook])
 
 
 def session_voice(s):
     """the session's voice for MultiStreamConverter.open: a pool name, or (name, weight) pairs for a blend"""
     if s.get("blend"):
-        return [(voice_name(t, lb), w) for t, lb, w in s["blend"]]
-    return voice_name(s["target"], s["lib"])
+        return [(voice_name(t, lb, s.get("codebook")), w) for t, lb, w in s["blend"]]
+    return voice_name(s["target"], s["lib"], s.get("codebook"))
 
 
 def blend_size(sessions):
@@ -251,6 +278,14 @@ def voice_tokens(ce, target, lib, device):
     return tgt[0].contiguous()
 
 
+def condensed(tokens, codebook):
+    """the voice's tokens [768, M] as they go into the pool: its `codebook`-row codebook (None: as they are)"""
+    if codebook is None:
+        return tokens
+    from module.codebook import build_codebook
+    return build_codebook(tokens, codebook)
+
+
 def voice_tokens_register(ce, pe, target, lib, device):
     """voice_tokens and the voice's register (sum of voiced pitch, voiced frames), measured with the f0 estimator on the same 16 kHz
     audio the content encoder sees (multistream.measure_register); None for a voice without a target wav"""
@@ -302,7 +337,7 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold)
+    sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook)
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -315,18 +350,19 @@ def main(argv=None):
 
     # auto pitch: only then are the voices' registers measured (with the f0 estimator) or declared ("register_hz")
     auto = any(s["auto_pitch"] for s in sessions)
-    declared = declared_registers(sessions, lambda s: voice_name(s["target"], s["lib"])) if auto else {}
+    declared = declared_registers(sessions, lambda s: voice_name(s["target"], s["lib"], s.get("codebook"))) if auto else {}
     pool, names = VoicePool(device=device, capacity=args.pool_rows), []
     for s in sessions:
         for target, lib in session_sources(s):
-            name = voice_name(target, lib)
+            name = voice_name(target, lib, s.get("codebook"))
             if args.pool_rows is None and name not in pool.segments:
                 if auto:
-                    pool.add(name, *voice_tokens_register(CE, PE, target, lib, device))
+                    tokens, register = voice_tokens_register(CE, PE, target, lib, device)
+                    pool.add(name, condensed(tokens, s.get("codebook")), register)
                     if name in declared:
                         pool.set_register(name, hz=declared[name])
                 else:
-                    pool.add(name, voice_tokens(CE, target, lib, device))
+                    pool.add(name, condensed(voice_tokens(CE, target, lib, device), s.get("codebook")))
         names.append(session_voice(s))
     slots = max(args.slots, len(sessions))
     in_sr = [s["sr"] or args.input_sr for s in sessions]
@@ -348,15 +384,16 @@ def main(argv=None):
     if args.pool_rows is not None:
         # the reserved pool: a tick's first sessions on a voice enrol it ahead of their open, its last one's close removes it
         n_ticks = [len(p) // c for p, c in zip(pcms, chunks)]
-        sources = {voice_name(t, lb): (t, lb) for s in sessions for t, lb in session_sources(s)}
-        events, _ = enrol_plan([dict(start=s["start"], ticks=n, voices={voice_name(t, lb): 1 for t, lb in session_sources(s)})
+        sources = {voice_name(t, lb, s.get("codebook")): (t, lb, s.get("codebook")) for s in sessions for t, lb in session_sources(s)}
+        events, _ = enrol_plan([dict(start=s["start"], ticks=n,
+                                     voices={voice_name(t, lb, s.get("codebook")): 1 for t, lb in session_sources(s)})
                                 for s, n in zip(sessions, n_ticks)])
 
         def before(tick):
             for name in [n for t, what, n in events if t == tick and what == "enrol"]:
-                target, lib = sources[name]
+                target, lib, size = sources[name]
                 wav, sr = audio_io.load(target) if target is not None else (None, None)
-                enrol_voice(pool, name, CE, wav, sr, lib=lib, compact=True, f0_estimator=PE if auto else None)
+                enrol_voice(pool, name, CE, wav, sr, lib=lib, compact=True, f0_estimator=PE if auto else None, codebook=size)
                 if name in declared:
                     pool.set_register(name, hz=declared[name])
 

@@ -816,6 +816,30 @@ int alive_gate_rows(const float* x, int N, int ld, int w_lo, int w_hi, const int
 int alive_gate_apply_rows(float* y, int N, int ld, const int* span_lo, const int* span_len, const float* g0, const float* g1,
                           void* stream);
 
+/* Voice codebooks (csrc/codebook.hip; module/codebook.py build_codebook): the device passes of one k-means iteration over a voice's
+ * rows that are not the search.  The assignment of a row is the strict search's top-1 against the centroids (alive_knn_search_strict)
+ * and the inverted index a stable sort of the assignment; both are the caller's.  All pointers are DEVICE pointers; no call allocates,
+ * copies or synchronises; argument errors return -1 with a message and launch nothing.  No floating-point atomics: every result is
+ * bitwise the same run to run, and bitwise tools/codebook_ref.py's.  1 <= C <= M < 2^31, 768 columns.
+ *   alive_codebook_workspace_bytes   scratch of alive_codebook_update for M rows and C lists (0: arguments out of range): the plan of
+ *                                    the launch plus the chunk sums of split lists, at most about 2 M / 512 slots of 768 doubles.
+ *   alive_codebook_update            centroids[c][:] <- the mean of rows[order[i]][:], i in [seg_off[c], seg_off[c + 1]), for every list
+ *                                    that is not empty; an empty list's centroid is not written.  order int32 [M]: the rows of list 0,
+ *                                    then of list 1, ..., each list in ascending row index; seg_off int32 [C + 1].  Per column, in fp64:
+ *                                    a list is cut into chunks of 512 rows, each chunk summed from +0.0 in list order, the chunk sums
+ *                                    added from +0.0 in chunk order, the total divided by the count and rounded to fp32 once.  A wave
+ *                                    takes one chunk (a lane 12 columns as three 16-byte loads); a list of one chunk is finished by its
+ *                                    wave, the others by a second launch.  rows and centroids 16-byte aligned; Dd must be 768.  A list
+ *                                    whose boundaries fall or leave [0, M] counts as empty, a row index outside [0, M) is skipped.
+ *   alive_codebook_stats             *objective <- the fp64 sum of val[M] (thread t of 1024 adds val[t], val[t + 1024], ... in turn from
+ *                                    +0.0, then acc[i] += acc[i + o] for o = 512, ..., 1); *moved <- the number of m with assign[m] !=
+ *                                    prev[m], or M when prev is NULL.  One block. */
+size_t alive_codebook_workspace_bytes(int64_t M, int64_t C);
+int alive_codebook_update(const float* rows, int64_t M, int Dd, const int32_t* order, const int32_t* seg_off, int64_t C,
+                          float* centroids, void* ws, void* stream);
+int alive_codebook_stats(const int32_t* assign, const int32_t* prev, const float* val, int64_t M, double* objective, int64_t* moved,
+                         void* stream);
+
 /* WORLD pitch estimation (`-wpe`): DIO + StoneMask on N rows of L8 samples at fs, in fp64   (reference module/common.py:113-137,
  * pyworld.dio(x, fs, f0_floor, f0_ceil, channels_in_octave=2, frame_period, speed=1, allowed_range=0.1) then pyworld.stonemask).
  * Restated from the published algorithm (tools/world_ref.py is the NumPy restatement; parity with pyworld is unpinned).
