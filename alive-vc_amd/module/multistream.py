@@ -65,6 +65,22 @@ register learns from open ticks only.  The encoders and the decoder still run ov
 the input gain (thr = 10^(dB/10) as a mean square, float64 on the host), gate_hold seconds rounded up to ticks.  Everything is device
 arrays: toggling and retuning never re-capture, and a converter built without gate launches exactly what it did.  gate_open() reads
 the per-slot open flags of the last tick back; seg_len_eff stays an attribute.
+
+Seam crossfade: every tick re-decodes the whole ring and emits its centre span, so successive chunks are cut from two independent
+decodes and butted together.  A converter built with crossfade=True (csrc/seam.hip) blends the head of each emitted chunk with the
+previous tick's own continuation: that tick's wave went on for 3.5 chunks beyond what it emitted, and its samples [span_lo + shift,
+span_lo + shift + X) are its prediction of what this tick emits as [span_lo, span_lo + X), from the same carried phase (the oscillator
+refers theta to begin_of_output).  alive_seam_rows keeps those X samples per session (`tail` [B, widest span], `stored` [B]: how many
+are valid) and fades from them into the current decode: no future input is waited for, so no latency is added.  shift is the ring's
+advance per tick in the session's own samples, its chunk -- NOT the span length: at 44.1 kHz under 160-sample ticks the chunk is 441
+and the span 440, so the time-aligned tail starts at span_lo + 441.  The call sits after the output resample and BEFORE the gate's
+edge: the tail is always saved from the un-gated converted wave, and the gate's ramp applies on top of the crossfaded head; a tick
+whose search the gate skipped (g0 = g1 = 0) decoded the passed-through source, so it leaves stored = 0 and the chunk on which the gate
+reopens is not faded from it.  crossfade_ms is per session (open / set; X = round(ms * rate / 1000) in xlen [B], at most the session's
+span); tail and stored are the session's, like phi: open and close zero stored, enable_graph and the bf16 repeat save and restore
+both.  It needs input_sr == output_sr (otherwise the ring's advance is not a whole number of output samples).  Everything is device
+arrays: toggling and retuning never re-capture, and a converter built without crossfade launches exactly what it did.  seam_db() reads
+the latest tick's 10 log10(sum (c - t)^2 / sum c^2) per slot back: how far the two decodes disagree, not how it sounds.
 """
 import numpy as np
 import torch
@@ -955,6 +971,61 @@ def gate_apply_rows_(y, span_lo, span_len, g0, g1):
     return y
 
 
+def seam_rows_(y, span_lo, shift, xlen, emit, tail, stored, g0=None, g1=None, stats=None):
+    """alive_seam_rows in place on y [N, ld]: every emitting row's head faded from its tail, the tail of the next tick saved.
+    tail float32 [N, ld_tail] and stored int32 [N] are the rows' state; g0 / g1: the gate's gains, or both None; stats: float64
+    [N, 2] or None"""
+    n, ld = y.shape
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError("seam_rows_: y must be contiguous float32 [N, ld]")
+    if tail.dtype != torch.float32 or not tail.is_contiguous() or tail.dim() != 2 or tail.shape[0] != n:
+        raise ValueError("seam_rows_: tail must be contiguous float32 [N, ld_tail]")
+    nat.check(nat.lib().alive_seam_rows(nat.ptr(y), n, ld, nat.ptr(span_lo), nat.ptr(shift), nat.ptr(xlen), nat.ptr(emit),
+                                        nat.ptr(g0), nat.ptr(g1), nat.ptr(tail), tail.shape[1], nat.ptr(stored), nat.ptr(stats),
+                                        nat.stream()), "alive_seam_rows")
+    return y
+
+
+def wave_length(frames, rate):
+    """the samples of a converter's final wave: the decoder's 320 per frame at 16 kHz, resampled to `rate`"""
+    orig, new = audio_io._reduced(16000, rate)
+    return 320 * int(frames) if orig == new else int(nat.lib().alive_resample_length(320 * int(frames), orig, new))
+
+
+def stats_db(stats):
+    """alive_seam_rows' (d2, e2) pairs -> 10 log10(d2 / e2) each; nan for a row that did not fade (or whose head was all zero)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return [float(10.0 * np.log10(np.float64(d2) / np.float64(e2))) if e2 > 0 else float("nan") for d2, e2 in stats]
+
+
+def check_crossfade_ms(crossfade_ms):
+    """a crossfade in milliseconds as a float, None for off.  ValueError unless it is None or a finite number > 0 (not a bool)"""
+    if crossfade_ms is None:
+        return None
+    if isinstance(crossfade_ms, (bool, np.bool_)) or not isinstance(crossfade_ms, (int, float, np.integer, np.floating)) or not (
+            np.isfinite(crossfade_ms) and crossfade_ms > 0):
+        raise ValueError(f"crossfade_ms={crossfade_ms!r} must be a finite number of milliseconds > 0, or None for no crossfade")
+    return float(crossfade_ms)
+
+
+def seam_geometry(chunk_r, buffersize, rate, crossfade_ms, row_len):
+    """a session's crossfade -> (span_lo, shift, X) of alive_seam_rows: span_lo the first sample step() emits of its wave of
+    row_len samples, shift = chunk_r (the ring's advance per tick in the session's samples -- not the span length, 2 * (chunk_r //
+    2)), X = round(crossfade_ms * rate / 1000), 0 for crossfade_ms None (off).  ValueError unless crossfade_ms is a finite number
+    > 0 (not a bool) with 1 <= X <= the span length and span_lo + shift + X <= row_len"""
+    chunk_r, buffersize, rate, row_len = int(chunk_r), int(buffersize), int(rate), int(row_len)
+    lo, span = buffersize * chunk_r // 2 - chunk_r // 2, 2 * (chunk_r // 2)
+    if check_crossfade_ms(crossfade_ms) is None:
+        return lo, chunk_r, 0
+    x = int(round(float(crossfade_ms) * rate / 1000.0))
+    x_max = min(span, row_len - lo - chunk_r)
+    if not 1 <= x <= x_max:
+        ms_max = max(x_max, 0) * 1000.0 / rate
+        raise ValueError(f"crossfade_ms={crossfade_ms!r} is {x} samples at {rate} Hz; a session with {chunk_r}-sample chunks in a "
+                         f"wave of {row_len} takes 1 to {max(x_max, 0)} (the largest crossfade_ms that fits is {ms_max:g})")
+    return lo, chunk_r, x
+
+
 def resample_rows(x, orig_freq, new_freq, pre_scale, post_scale):
     """x [B, L] -> [B, L'] at new_freq with per-row linear gains (device float32 [B]): audio_io.resample row by row, the gains
     as 10^(dB/20); at equal rates the gains alone"""
@@ -1072,16 +1143,23 @@ def db_scale(db):
     return float(10 ** (db / 20)) if db != 0 else 1.0
 
 
-_PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold")
+_PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold",
+           "crossfade_ms")
 
 
 class MultiStreamConverter:
     auto_pitch = False                 # (set per converter in __init__: whether the tick carries the auto-pitch kernel)
     gate = False                       # (likewise: whether the tick carries the two gate kernels)
+    crossfade = False                  # (likewise: whether the tick carries the seam kernel)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
-                 auto_pitch_half_life=10.0, auto_pitch_prior=0.5, gate=False, gate_lookahead=None):
+                 auto_pitch_half_life=10.0, auto_pitch_prior=0.5, gate=False, gate_lookahead=None, crossfade=False):
+        if not isinstance(crossfade, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: crossfade must be a bool, got {crossfade!r}")
+        if crossfade and input_sr != output_sr:
+            raise ValueError(f"MultiStreamConverter: crossfade=True needs input_sr == output_sr (got {input_sr} and {output_sr}): "
+                             "the ring's advance per tick is otherwise not a whole number of output samples")
         if not isinstance(gate, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: gate must be a bool, got {gate!r}")
         if gate_lookahead is not None and (isinstance(gate_lookahead, (bool, np.bool_)) or not isinstance(
@@ -1215,6 +1293,22 @@ class MultiStreamConverter:
             lo, ln = self._span(self.chunk)                # the emitted centre span of step(), per session rate (_set_rate)
             self.span_lo = torch.full((B,), lo, **i32)
             self.span_len = torch.full((B,), ln, **i32)
+        # crossfade: the seam kernel is part of the tick (captured once); per row, xlen is the session's crossfade in samples (0:
+        # off) and shift its chunk.  tail / stored are the session's, like phi
+        self.crossfade = bool(crossfade)
+        if self.crossfade:
+            self._row_len = {r: self._wave_len(r) for r in rates}      # the samples of a session's final wave, per rate
+            i32 = dict(dtype=torch.int32, device=dev)
+            spans = [self._span(self._chunk_at(r)) for r in rates]
+            self.xlen = torch.zeros(B, **i32)
+            self.shift = torch.full((B,), self.chunk, **i32)
+            self.stored = torch.zeros(B, **i32)
+            self.tail = torch.zeros(B, max(ln for _, ln in spans), dtype=torch.float32, device=dev)
+            self.seam_stats = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+            if not self.gate:
+                lo, ln = self._span(self.chunk)
+                self.span_lo = torch.full((B,), lo, **i32)
+                self.span_len = torch.full((B,), ln, **i32)
         self.phi = torch.zeros(B, 64, device=dev)
         self._in = torch.zeros(B, ld_in, device=dev)
         self._graph = None
@@ -1250,6 +1344,33 @@ class MultiStreamConverter:
         """the span of a session's output wave that step() emits, for chunks of cs samples: (first sample, length)"""
         return self.buffersize * cs // 2 - cs // 2, 2 * (cs // 2)
 
+    def _chunk_at(self, rate):
+        """the chunk of a session at a declared rate"""
+        return self.chunk if self._rt is None else self._chunks[int(rate)]
+
+    def _wave_len(self, rate):
+        """the samples of the final wave of a session at a declared rate: 320 per frame at 16 kHz, resampled to the rate"""
+        if self._rt is not None:
+            return self._lout[int(rate)]
+        return wave_length(self.frames, self.output_sr)
+
+    def _session_seam(self, slot, p, rate=None):
+        """a session's crossfade -> X in samples at its rate (0: off), checked against the converter"""
+        ms = p.get("crossfade_ms")
+        try:
+            if check_crossfade_ms(ms) is None:
+                return 0
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+        if not self.crossfade:
+            raise ValueError(f"slot {slot}: crossfade_ms={ms!r} needs a converter built with MultiStreamConverter(..., "
+                             "crossfade=True)")
+        rate = int(self.rate[slot] if rate is None else rate)
+        try:
+            return seam_geometry(self._chunk_at(rate), self.buffersize, rate, ms, self._row_len[rate])[2]
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+
     def _session_gate(self, slot, p):
         """a session's gate settings -> (on, thr_ms, hold_ticks), checked against the converter"""
         db, hold = p.get("gate_db"), p.get("gate_hold", 0.2)
@@ -1264,9 +1385,10 @@ class MultiStreamConverter:
             raise ValueError(f"slot {slot}: gate_db={db!r} needs a converter built with MultiStreamConverter(..., gate=True)")
         return 1, thr, ticks
 
-    def _apply(self, slot, p):
+    def _apply(self, slot, p, rate=None):
         k = self._session_k(slot, p["k"])
         gate = self._session_gate(slot, p)
+        xlen = self._session_seam(slot, p, rate)
         names, weights = blend_spec(p["voice"], self.pool, k, self.S)
         world = p["world_pitch"]
         if not isinstance(world, (bool, np.bool_)):
@@ -1304,6 +1426,8 @@ class MultiStreamConverter:
             self.target[slot] = target if auto else 0.0
         if self.gate:
             self.gate_on[slot], self.thr_ms[slot], self.hold_ticks[slot] = gate
+        if self.crossfade:
+            self.xlen[slot] = xlen
 
     def _write_segments(self, slot, names):
         """the slot's rows of seg_lo / seg_len from where its voices lie in the pool now"""
@@ -1354,8 +1478,10 @@ class MultiStreamConverter:
         if self._rt is None:
             return
         c = self._chunks[rate]
-        if self.gate:
+        if self.gate or self.crossfade:
             self.span_lo[slot], self.span_len[slot] = self._span(c)
+        if self.crossfade:
+            self.shift[slot] = c
         self.slot_chunk[slot] = c
         self.len_in[slot] = c * self.buffersize
         self.pair_in[slot] = self._rt.pair(rate, 16000)
@@ -1363,7 +1489,7 @@ class MultiStreamConverter:
         self.len_out[slot] = self._lout[rate]
 
     def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None,
-             auto_pitch=False, gate_db=None, gate_hold=0.2):
+             auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
@@ -1371,15 +1497,17 @@ class MultiStreamConverter:
         auto_pitch=True (needs an auto_pitch=True converter and a register on every voice of the session): the pitch shift follows
         the target voice's register, and `pitch` is an offset on top of it.  gate_db (needs a gate=True converter): the session's
         input gate, a threshold in dBFS on its 16 kHz ring after the input gain (None: no gate); gate_hold: the seconds (>= 0) it
-        stays open after the last loud tick.  A gated session starts closed: its first chunk fades in"""
+        stays open after the last loud tick.  A gated session starts closed: its first chunk fades in.  crossfade_ms (needs a
+        crossfade=True converter): the milliseconds over which the head of every chunk is faded in from the previous tick's
+        continuation (None: a hard cut), at most the session's emitted span; the first chunk has nothing to fade from"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
             raise ValueError(f"slot {slot}: rate {rate} Hz was not declared (rates={list(self.rates)}): pass it in "
                              "MultiStreamConverter(..., rates=...)")
         p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch,
-                 k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold)
-        self._apply(slot, p)                                  # (validates the voice before anything changes)
+                 k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold, crossfade_ms=crossfade_ms)
+        self._apply(slot, p, rate)                            # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
         self.is_open[slot] = True
@@ -1390,11 +1518,14 @@ class MultiStreamConverter:
             self.reg_state[slot] = 0.0                        # a new source: nothing heard yet
         if self.gate:
             self.gate_state[slot] = 0                         # closed, no hold: the first emitted chunk fades in
+        if self.crossfade:
+            self.stored[slot] = 0                             # never fade from another session's tail
         return self
 
     def set(self, slot, **params):
         """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
-        gate_db, gate_hold; the gate's state is kept).
+        gate_db, gate_hold, crossfade_ms; the gate's state and the saved tail are kept: a longer crossfade fades over what the tail
+        holds this tick and in full from the next).
         The running source register is kept: a new voice changes the target only, and auto_pitch=True after False resumes from
         what the session had heard while it was on (nothing, if it never was)"""
         slot = self._slot(slot)
@@ -1434,6 +1565,9 @@ class MultiStreamConverter:
             self.thr_ms[slot] = 0.0
             self.hold_ticks[slot] = 0
             self.gate_state[slot] = 0
+        if self.crossfade:
+            self.xlen[slot] = 0
+            self.stored[slot] = 0
         self._set_rate(slot, int(self.input_sr))             # a closed slot: the converter's own rate, silence
         return self
 
@@ -1444,6 +1578,13 @@ class MultiStreamConverter:
             raise ValueError("gate_open needs a converter built with MultiStreamConverter(..., gate=True)")
         on, was = self.gate_on.tolist(), self.gate_state[:, 1].tolist()
         return [bool(self.is_open[b] and (was[b] if on[b] else True)) for b in range(self.B)]
+
+    def seam_db(self):
+        """the seam statistic of the latest tick, a list of B floats: 10 log10(sum (c - t)^2 / sum c^2) over the faded head of each
+        slot, c the tick's own decode and t the previous tick's continuation; nan for a slot that did not fade.  One host read"""
+        if not self.crossfade:
+            raise ValueError("seam_db needs a converter built with MultiStreamConverter(..., crossfade=True)")
+        return stats_db(self.seam_stats.tolist())
 
     # ------------------------------------------------------------------ device step
     def _f0_on_side_stream(self, spec, data):
@@ -1508,6 +1649,11 @@ class MultiStreamConverter:
                 raise RuntimeError(f"decoder wave of {wave.shape[1]} samples, the multi-rate edge expects {self._lw}")
             wave = resample_rows_multi(wave, self._lw_rows, self.pair_out, self._rt, self.len_out, self._ld_out, self.out_pre,
                                        self.out_post)
+        if self.crossfade:                                    # before the gate's edge: the tail is the un-gated converted wave
+            if wave.shape[1] != max(self._row_len.values()):
+                raise RuntimeError(f"final wave of {wave.shape[1]} samples, the crossfade expects {max(self._row_len.values())}")
+            seam_rows_(wave, self.span_lo, self.shift, self.xlen, self.emit, self.tail, self.stored,
+                       self.g0 if self.gate else None, self.g1 if self.gate else None, self.seam_stats)
         if self.gate:
             gate_apply_rows_(wave, self.span_lo, self.span_len, self.g0, self.g1)
         phi_next = torch.where(self.emit, phi_out[:, :, self.end_of_output], torch.zeros_like(phi))
@@ -1518,8 +1664,10 @@ class MultiStreamConverter:
         saved = self.phi.clone()
         saved_reg = self.reg_state.clone() if self.auto_pitch else None      # (capture_step runs the step three times)
         saved_gate = self.gate_state.clone() if self.gate else None
+        saved_seam = self._seam_state()
         self._graph, self._g_out = capture_step(self.device, lambda: self._device_step(self._in, self.phi), self.phi)
         self.phi.copy_(saved)
+        self._seam_restore(saved_seam)
         if saved_reg is not None:
             self.reg_state.copy_(saved_reg)
         if saved_gate is not None:
@@ -1527,6 +1675,15 @@ class MultiStreamConverter:
         self._graph_pool_version = self.pool.version
         self.captures += 1
         return self
+
+    def _seam_state(self):
+        """a copy of the sessions' tails and how much of them is valid (None without crossfade)"""
+        return (self.tail.clone(), self.stored.clone()) if self.crossfade else None
+
+    def _seam_restore(self, saved):
+        if saved is not None:
+            self.tail.copy_(saved[0])
+            self.stored.copy_(saved[1])
 
     def _run(self):
         if self._reserved:
@@ -1540,15 +1697,16 @@ class MultiStreamConverter:
         self.phi.copy_(phi_next)
         return wave
 
-    def _repeat_on_bf16(self, saved_phi, saved_reg=None, saved_gate=None):
-        """RealtimeConverter._repeat_on_bf16 for the whole tick: modes 2, every slot's phase (and running register, and gate state)
-        restored, the tick again"""
+    def _repeat_on_bf16(self, saved_phi, saved_reg=None, saved_gate=None, saved_seam=None):
+        """RealtimeConverter._repeat_on_bf16 for the whole tick: modes 2, every slot's phase (and running register, gate state and
+        crossfade tail) restored, the tick again"""
         ops.switch_to_bf16("multi-session streaming step", "tick")
         self.phi.copy_(saved_phi)
         if saved_reg is not None:
             self.reg_state.copy_(saved_reg)
         if saved_gate is not None:
             self.gate_state.copy_(saved_gate)
+        self._seam_restore(saved_seam)
         if self._graph is not None:
             self.enable_graph()
         return audio_io.float_to_pcm16(self._run()).cpu().numpy()
@@ -1587,9 +1745,10 @@ class MultiStreamConverter:
             saved_phi = self.phi.clone()
             saved_reg = self.reg_state.clone() if self.auto_pitch else None
             saved_gate = self.gate_state.clone() if self.gate else None
+            saved_seam = self._seam_state()
         o = audio_io.float_to_pcm16(self._run()).cpu().numpy()
         if guarded and ops.f16_saturations(reset=True) > 0:
-            o = self._repeat_on_bf16(saved_phi, saved_reg, saved_gate)
+            o = self._repeat_on_bf16(saved_phi, saved_reg, saved_gate, saved_seam)
         for s in chunks:
             if emit[s]:
                 cs = self.slot_chunk[s]

@@ -8,6 +8,12 @@ Input gate (`-thr`): RealtimeConverter(gate_db=DB, gate_hold=S) runs the two gat
 module/multistream.py "Input gate") at N = 1: alive_gate_rows on the 16 kHz ring after the input gain, alive_gate_apply_rows on the
 final wave.  It mutes only: the single-library search has no row mask and runs on.  The gate's state lives beside the phase: `reset`
 and `enable_graph` zero it, the bf16 repeat restores it.  Without gate_db the converter launches what it did.
+
+Seam crossfade (`-xf`): RealtimeConverter(crossfade_ms=MS) runs alive_seam_rows (csrc/seam.hip, module/multistream.py "Seam
+crossfade") at one row between the output resample and the gate's edge: the head of every chunk is faded in from the previous step's
+continuation of itself.  It needs input_sr == output_sr.  The saved tail lives beside the phase: `reset`, `enable_graph` and a
+`step_device(continues=False)` drop it (the ring is then unrelated to the previous one), the bf16 repeat restores it.  Without
+crossfade_ms the converter launches what it did.
 """
 import numpy as np
 import torch
@@ -118,8 +124,16 @@ def capture_step(device, step, phi):
 class RealtimeConverter:
     def __init__(self, content_encoder, f0_estimator, decoder, library_tokens, device="cuda", chunk=960, buffersize=8,
                  input_sr=16000, output_sr=16000, f0_rate=1.0, pitch=0.0, k=4, alpha=0.0, gain=0.0, input_gain=0.0,
-                 reuse_interior="auto", world_pitch=False, gate_db=None, gate_hold=0.2, gate_lookahead=None):
+                 reuse_interior="auto", world_pitch=False, gate_db=None, gate_hold=0.2, gate_lookahead=None,
+                 crossfade_ms=None):
         self.device = torch.device(device)
+        self.crossfade = crossfade_ms is not None
+        if self.crossfade:                 # (checked before anything is built)
+            from .multistream import check_crossfade_ms
+            check_crossfade_ms(crossfade_ms)
+            if input_sr != output_sr:
+                raise ValueError(f"RealtimeConverter: crossfade_ms needs input_sr == output_sr (got {input_sr} and {output_sr}): "
+                                 "the ring's advance per step is otherwise not a whole number of output samples")
         self.gate = gate_db is not None
         if self.gate:                      # (checked before anything is built)
             from .multistream import gate_hold_ticks, gate_thr_ms
@@ -154,6 +168,21 @@ class RealtimeConverter:
             self._g1 = torch.ones(1, device=dev)
             self._span_lo = torch.tensor([buffersize * chunk // 2 - chunk // 2], **i32)
             self._span_len = torch.tensor([2 * (chunk // 2)], **i32)
+        if self.crossfade:
+            # the multi-session crossfade at one row: an always-emitting session; _seam_tail / _seam_stored are the stream's, like
+            # the phase
+            from .multistream import seam_geometry, wave_length
+            dev, i32 = self.device, dict(dtype=torch.int32, device=self.device)
+            self.crossfade_ms = float(crossfade_ms)
+            self._row_len = wave_length(frames, output_sr)
+            lo, shift, x = seam_geometry(chunk, buffersize, output_sr, crossfade_ms, self._row_len)
+            self._seam_lo = torch.tensor([lo], **i32)
+            self._seam_shift = torch.tensor([shift], **i32)
+            self._seam_x = torch.tensor([x], **i32)
+            self._seam_emit = torch.ones(1, dtype=torch.bool, device=dev)
+            self._seam_tail = torch.zeros(1, 2 * (chunk // 2), device=dev)
+            self._seam_stored = torch.zeros(1, **i32)
+            self._seam_stats = torch.zeros(1, 2, dtype=torch.float64, device=dev)
         self._side = None                  # side stream of the f0 estimator (see _f0_on_side_stream)
         self._f0_bufs = {}
         # interior reuse: only where it is exact -- no resampling in front (the ring IS the 16 kHz signal), a shift of whole
@@ -191,7 +220,7 @@ class RealtimeConverter:
         content, f0 = self._front_end(spectrogram(data), data)
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0                  # (a view of the per-shape side-stream buffer: valid until the next step)
-        wave = self._gate_edge(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain))[0]   # gain, then resample
+        wave = self._gate_edge(self._seam(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain)))[0]   # gain, then resample
         return wave, phi_out[:, :, self.end_of_output]
 
     def _gate_decide(self, data):
@@ -208,6 +237,18 @@ class RealtimeConverter:
         if self.gate:
             from .multistream import gate_apply_rows_
             wave = gate_apply_rows_(wave.contiguous(), self._span_lo, self._span_len, self._g0, self._g1)
+        return wave
+
+    def _seam(self, wave):
+        """crossfade on: the head of the emitted span of the final wave [1, L] faded in from the previous step's continuation, in
+        place, and this step's continuation saved (alive_seam_rows at one row; before the gate's edge, with its gains)"""
+        if self.crossfade:
+            from .multistream import seam_rows_
+            if wave.shape[1] != self._row_len:
+                raise RuntimeError(f"final wave of {wave.shape[1]} samples, the crossfade expects {self._row_len}")
+            wave = seam_rows_(wave.contiguous(), self._seam_lo, self._seam_shift, self._seam_x, self._seam_emit, self._seam_tail,
+                              self._seam_stored, self._g0 if self.gate else None, self._g1 if self.gate else None,
+                              self._seam_stats)
         return wave
 
     def _f0_on_side_stream(self, spec, data=None):
@@ -258,7 +299,7 @@ class RealtimeConverter:
             self._c_f0[:, :, a:].copy_(f0[:, :, margin:])
         wave, phi_out = self.dec(self._c_feat, f0=self._c_f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = self._c_f0
-        wave = self._gate_edge(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain))[0]
+        wave = self._gate_edge(self._seam(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain)))[0]
         return wave, phi_out[:, :, self.end_of_output]
 
     def _front_end_slice(self, samples, f_lo, f_hi):
@@ -280,6 +321,8 @@ class RealtimeConverter:
         self._g_phi.zero_()
         if self.gate:
             self._gate_state.zero_()       # (capture_step ran the step three times)
+        if self.crossfade:
+            self._seam_stored.zero_()
         self._cache_valid = False          # interior reuse: the captured step is the incremental one; the first real step runs in full
         return self
 
@@ -293,7 +336,17 @@ class RealtimeConverter:
             self._g_phi.zero_()
         if self.gate:
             self._gate_state.zero_()
+        if self.crossfade:
+            self._seam_stored.zero_()
         return self
+
+    def seam_db(self):
+        """the seam statistic of the latest step: 10 log10(sum (c - t)^2 / sum c^2) over the faded head, c the step's own decode and
+        t the previous step's continuation; nan if the step did not fade (one host read)"""
+        if not self.crossfade:
+            raise ValueError("seam_db needs a converter built with RealtimeConverter(..., crossfade_ms=MS)")
+        from .multistream import stats_db
+        return stats_db(self._seam_stats.tolist())[0]
 
     def gate_open(self):
         """whether the gate was open at the end of the latest step (one host read)"""
@@ -307,9 +360,15 @@ class RealtimeConverter:
         Contract of interior reuse (on when the ring geometry allows, see `reuse_block`): the matched features and f0 of the
         ring's interior frames are carried over from the previous call, which is only right when `ring_f32` IS the previous
         ring advanced by exactly one chunk.  The caller says so with `continues=True` (`step()` does: it owns the ring);
-        the default treats the ring as unrelated to the previous one and recomputes the whole front end."""
+        the default treats the ring as unrelated to the previous one and recomputes the whole front end -- and, with a crossfade,
+        drops the saved tail: the previous wave's continuation says nothing about an unrelated ring."""
         if not continues:
             self._cache_valid = False
+            if self.crossfade:
+                self._seam_stored.zero_()
+        return self._step_device(ring_f32)
+
+    def _step_device(self, ring_f32):
         if getattr(self, "_graph", None) is not None:
             if self.reuse and not self._cache_valid:             # fills the frame caches the captured (incremental) step reads
                 wave, phi_next = self._device_step(ring_f32, self._g_phi)
@@ -323,10 +382,10 @@ class RealtimeConverter:
         self.phi = phi_next
         return wave
 
-    def _repeat_on_bf16(self, data, saved_phi, saved_gate=None):
+    def _repeat_on_bf16(self, data, saved_phi, saved_gate=None, saved_seam=None):
         """a chunk drove an activation out of fp16's range: switch the process to bf16 planes (ops.switch_to_bf16), restore the
-        phase (and the gate state) the chunk started from, drop the frame caches, re-capture the step if it was a hipGraph, and
-        convert the chunk again"""
+        phase (and the gate state, and the crossfade's tail) the chunk started from, drop the frame caches, re-capture the step if it
+        was a hipGraph, and convert the chunk again -- the whole front end, but crossfaded as the first attempt would have been"""
         ops.switch_to_bf16("streaming step", "chunk")
         self._cache_valid = False
         if getattr(self, "_graph", None) is not None:
@@ -336,7 +395,10 @@ class RealtimeConverter:
             self.phi = saved_phi
         if saved_gate is not None:
             self._gate_state.copy_(saved_gate)
-        wave = self.step_device(data, continues=False)
+        if saved_seam is not None:
+            self._seam_tail.copy_(saved_seam[0])
+            self._seam_stored.copy_(saved_seam[1])
+        wave = self._step_device(data)                  # (not step_device(continues=False), which would drop the restored tail)
         return audio_io.float_to_pcm16(wave).cpu().numpy()
 
     def step(self, data_int16: np.ndarray):
@@ -353,9 +415,10 @@ class RealtimeConverter:
         if guarded:
             saved_phi = self._g_phi.clone() if getattr(self, "_graph", None) is not None else self.phi
             saved_gate = self._gate_state.clone() if self.gate else None
+            saved_seam = (self._seam_tail.clone(), self._seam_stored.clone()) if self.crossfade else None
         wave = self.step_device(data, continues=True)                # this ring is the previous one advanced by one chunk
         out = audio_io.float_to_pcm16(wave).cpu().numpy()            # C cast of numpy's astype, no clipping (:180-183)
         if guarded and ops.f16_saturations(reset=True) > 0:          # (the copy above has synchronised: six 4-byte reads)
-            out = self._repeat_on_bf16(data, saved_phi, saved_gate)
+            out = self._repeat_on_bf16(data, saved_phi, saved_gate, saved_seam)
         center = self.buffersize * self.chunk // 2
         return out[center - self.chunk // 2: center + self.chunk // 2]

@@ -15,6 +15,9 @@ The sessions file is a JSON list; each entry:
    "gate_db": -40, "gate_hold": 0.2,      optional: the session's input gate (module/multistream.py "Input gate"): a threshold in
                                           dBFS on its 16 kHz ring after the input gain (null: no gate; default -thr) and the
                                           seconds it stays open after the last loud tick (default --gate-hold)
+   "crossfade_ms": 10,                    optional, a number of milliseconds > 0 or null (default: --crossfade): the head of every
+                                          chunk of the session is faded in from the previous tick's continuation over that long
+                                          (module/multistream.py "Seam crossfade"; at most the session's chunk; needs -isr == -osr)
    "codebook": 4096,                      optional, an integer >= 1 or null (default: --codebook): the session's voice is condensed to
                                           that many centroid rows by k-means when it is packed or enrolled (module/codebook.py); a
                                           voice of that many rows or fewer stays as it is.  A codebook's rows are means: use k 1 or 2
@@ -36,6 +39,8 @@ The converter carries the auto-pitch kernel, and the voices are given registers 
 only if some session is on auto pitch: a file without "auto_pitch", run without --auto-pitch, runs as before.
 The converter carries the two gate kernels only if some session ends up gated ("gate_db", or -thr): a file without the keys, run
 without -thr, runs as before.
+The converter carries the seam kernel only if some session ends up with a crossfade ("crossfade_ms", or --crossfade): a file without
+the key, run without the flag, runs as before.
 The voices are condensed only for sessions with a "codebook" (or under --codebook): a file without the key, run without the flag, runs
 as before.  The size is part of the voice's pool name: sessions on the same sources at different sizes get different voices; a blend's
 components are each condensed to the session's size.
@@ -64,13 +69,14 @@ from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
 from module.multistream import (MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
-                                gate_hold_ticks, gate_thr_ms, measure_register)
+                                check_crossfade_ms, gate_hold_ticks, gate_thr_ms, measure_register)
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
 SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "start", "sr", "output",
                 "blend", "k", "auto_pitch", "register_hz")
 GATE_KEYS = ("gate_db", "gate_hold")     # taken per session too; a loaded session carries them only when it is gated
+SEAM_KEYS = ("crossfade_ms",)            # taken per session too; a loaded session carries it only when it crossfades
 CODEBOOK_KEYS = ("codebook",)            # taken per session too; a loaded session carries it only when its voice is condensed
 
 
@@ -98,6 +104,9 @@ def build_parser():
                              "says otherwise (default: no gate)")
     parser.add_argument('--gate-hold', default=0.2, type=float,
                         help="seconds a gate stays open after the last loud tick (default 0.2; a session's \"gate_hold\" overrides)")
+    parser.add_argument('--crossfade', default=None, type=float, metavar="MS",
+                        help="seam crossfade: sessions fade the head of every chunk in from the previous tick's continuation over "
+                             "MS milliseconds unless their \"crossfade_ms\" says otherwise (default: hard cuts)")
     parser.add_argument('--codebook', default=None, type=int, metavar="SIZE",
                         help="condense every session's voice to SIZE centroid rows by k-means unless its \"codebook\" says otherwise "
                              "(default: the voices as they are)")
@@ -143,6 +152,15 @@ def session_gate(s, where, gate_db=None, gate_hold=0.2):
     return None if db is None else (float(db), float(hold))
 
 
+def session_crossfade(s, where, crossfade_ms=None):
+    """an entry's "crossfade_ms" (default `crossfade_ms`) -> a float > 0, or None for a session with hard cuts (a JSON null switches
+    the default off); ValueError otherwise"""
+    try:
+        return check_crossfade_ms(s.get("crossfade_ms", crossfade_ms))
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+
+
 def session_codebook(s, where, codebook=None):
     """an entry's "codebook" (default `codebook`) -> an integer >= 1, or None for a voice that stays as it is (a JSON null switches
     the default off); ValueError otherwise"""
@@ -154,14 +172,15 @@ def session_codebook(s, where, codebook=None):
     return size
 
 
-def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None):
+def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None, crossfade_ms=None):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
-    condensed; ValueError on a malformed entry"""
+    condensed, and "crossfade_ms" (default `crossfade_ms`) only on a session that crossfades; ValueError on a malformed entry"""
     k = check_k(k, "-k")
     session_codebook({}, "--codebook", codebook)
     session_gate({}, "-thr / --gate-hold", gate_db, gate_hold)
+    session_crossfade({}, "--crossfade", crossfade_ms)
     with open(path) as f:
         sessions = json.load(f)
     if not isinstance(sessions, list) or not sessions:
@@ -171,10 +190,12 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     for i, s in enumerate(sessions):
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
-        unknown = set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(CODEBOOK_KEYS)
+        unknown = set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(CODEBOOK_KEYS)
         if unknown:
-            raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: {SESSION_KEYS + GATE_KEYS + CODEBOOK_KEYS})")
+            raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + CODEBOOK_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
+        xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
         rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))      # noqa: E731
         blend = blend_sources(s, f"session {i}", rel) if "blend" in s else None
@@ -196,6 +217,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             raise ValueError(f"session {i}: sample rate {e['sr']} <= 0")
         if gate is not None:
             e["gate_db"], e["gate_hold"] = gate
+        if xf is not None:
+            e["crossfade_ms"] = xf
         if size is not None:
             e["codebook"] = size
         out.append(e)
@@ -337,7 +360,8 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook)
+    sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook,
+                             args.crossfade)
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -371,10 +395,11 @@ def main(argv=None):
                                 output_sr=args.output_sr, k=args.k, device=device, rates=sorted(set(in_sr)),
                                 world_pitch=any(s["world_pitch"] for s in sessions), blend=blend_size(sessions),
                                 k_max=converter_k_max(sessions, args.k), auto_pitch=auto,
-                                **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}))
+                                **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}),
+                                **(dict(crossfade=True) if any("crossfade_ms" in s for s in sessions) else {}))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
-                   **{g: s[g] for g in GATE_KEYS if g in s})
+                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()

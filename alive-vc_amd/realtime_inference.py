@@ -55,6 +55,9 @@ def build_parser():
                              "ring after -ig, with a fade at both edges (default: no gate)")
     parser.add_argument('--gate-hold', default=0.2, type=float,
                         help="seconds the gate stays open after the last chunk above -thr (default 0.2; this build only)")
+    parser.add_argument('-xf', '--crossfade', default=None, type=float, metavar="MS",
+                        help="seam crossfade: fade the head of every chunk in from the previous step's continuation over MS "
+                             "milliseconds, at most one chunk (default: hard cuts; needs -isr == -osr; this build only)")
     parser.add_argument('-isr', '--input-sr', default=16000, type=int)
     parser.add_argument('-osr', '--output-sr', default=16000, type=int)
     parser.add_argument('-lsr', '--loopback-sr', default=16000, type=int)
@@ -97,7 +100,8 @@ def main(argv=None):
                            input_sr=args.input_sr, output_sr=args.output_sr, f0_rate=args.f0_rate, pitch=args.pitch,
                            k=args.k, alpha=args.alpha, gain=args.gain, input_gain=args.input_gain,
                            world_pitch=bool(args.world_pitch_estimation),   # -wpe: WORLD f0, -f0 not applied (as the reference)
-                           **(dict(gate_db=args.threshold, gate_hold=args.gate_hold) if args.threshold is not None else {}))
+                           **(dict(gate_db=args.threshold, gate_hold=args.gate_hold) if args.threshold is not None else {}),
+                           **(dict(crossfade_ms=args.crossfade) if args.crossfade is not None else {}))
     if not args.no_graph:
         rt.enable_graph()        # the whole per-chunk device pipeline (~150 launches) captured once, replayed per chunk: same samples
     print("streaming: conversion running (Ctrl-C stops)")

@@ -816,6 +816,29 @@ int alive_gate_rows(const float* x, int N, int ld, int w_lo, int w_hi, const int
 int alive_gate_apply_rows(float* y, int N, int ld, const int* span_lo, const int* span_len, const float* g0, const float* g1,
                           void* stream);
 
+/* Seam crossfade of the streaming paths (csrc/seam.hip): the head of every emitted chunk blended with the previous tick's continuation.
+ * All pointers are DEVICE pointers; the call does not allocate, synchronise or read anything on the host; the grid depends on N alone
+ * (graph-capturable: a captured call serves any settings).  No floating-point atomics.
+ *   alive_seam_rows   one block per row n of y[N][ld] (the final waves, after the output resample, before alive_gate_apply_rows), in
+ *                     place.  Per row: span_lo int32 (the first emitted sample), shift int32 (the ring's advance per tick in samples
+ *                     of y: the session's chunk, NOT the span length -- 441 against 440 at 44.1 kHz with 160-sample ticks), xlen int32
+ *                     (X, the crossfade in samples; 0: off), emit bytes; the row's state tail[N][ld_tail] float and stored[N] int32
+ *                     (how many samples of the tail are valid).  g0 / g1: both NULL, or the two gains of alive_gate_rows.
+ *                       emit[n] == 0: y, tail, stored untouched, stats[n] = {0, 0};
+ *                       X == 0: y untouched, stored[n] = 0, stats[n] = {0, 0};
+ *                       a row whose regions do not fit (span_lo < 0, X < 0, X > ld_tail, X > shift, span_lo + shift + X > ld): the
+ *                         same; nothing outside [0, ld) or [0, ld_tail) is ever read or written;
+ *                       else Xe = min(X, max(stored[n], 0)) and, for i < Xe with t = tail[n][i], c = y[n][span_lo + i]:
+ *                         y[n][span_lo + i] = t + (c - t) * ((float)(i + 1) / (float)(Xe + 1)) in float32, every operation rounded on
+ *                         its own (the weight never reaches 0 or 1); then tail[n][i] = y[n][span_lo + shift + i] for i < X, and
+ *                         stored[n] = X -- or 0 where g0 and g1 are given and both 0 for the row: the gate skipped that tick's
+ *                         search, so what it decoded is the passed-through source and must not be faded from.
+ *                     stats double [N][2] or NULL: {sum over i < Xe of ((double)c - (double)t)^2, sum of (double)c^2} of the UNFADED
+ *                     head, in fp64 in a fixed order (thread tid: i = tid, tid + 256, ...; then a pairwise tree over the 256 partial
+ *                     sums): bitwise reproducible, and the same for a row alone and in any batch.  N, ld, ld_tail > 0. */
+int alive_seam_rows(float* y, int N, int ld, const int* span_lo, const int* shift, const int* xlen, const unsigned char* emit,
+                    const float* g0, const float* g1, float* tail, int ld_tail, int* stored, double* stats, void* stream);
+
 /* Voice codebooks (csrc/codebook.hip; module/codebook.py build_codebook): the device passes of one k-means iteration over a voice's
  * rows that are not the search.  The assignment of a row is the strict search's top-1 against the centroids (alive_knn_search_strict)
  * and the inverted index a stable sort of the assignment; both are the caller's.  All pointers are DEVICE pointers; no call allocates,

@@ -20,6 +20,11 @@ carry a -40 dB gate, sessions s < round(f B) fed digital silence (their gates st
 speech-level signal (their gates stay open), and the event-timed grouped search over the segment lengths that tick left in seg_len_eff
 (gated_<f>_tick_p50_ms / _p99_ms / _search_ms / _live_rows); and the gate=False converter a second time (gate_off_again_tick_*): the
 spread between its two measurements is the yardstick for the gate's overhead at fraction 0.
+--crossfade adds the graph tick p50 / p99 of a crossfade=True converter with every session crossfading over 10 ms (crossfade_tick_*:
+one more launch of one block per session, alive_seam_rows, csrc/seam.hip), the seam statistic of its last tick over the sessions
+(crossfade_seam_db_min / _median / _max: 10 log10 of how far two successive decodes disagree over the faded head -- on SYNTHETIC weights
+and synthetic input, so it says nothing about how a trained model sounds), and the converter built without crossfade a second time
+(crossfade_off_again_tick_*): the spread between its two measurements is the yardstick for the crossfade's cost.
 --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
 one more 50 000-row voice added between two ticks, once on a default pool (the add re-packs the pool and the next tick
 re-captures) and once on a reserved pool of 65 x 50 000 rows (VoicePool(capacity=...): alive_pool_append into the table in
@@ -31,7 +36,7 @@ python tools/bench_multistream.py --quick).  Prints one JSON line per configurat
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch]
-                                      [--gated 0,0.5,1] [--out multistream.json]
+                                      [--gated 0,0.5,1] [--crossfade] [--out multistream.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
 """
 import argparse
@@ -186,6 +191,8 @@ def main():
     ap.add_argument("--auto-pitch", action="store_true", help="also time an auto_pitch=True converter, every session on auto pitch")
     ap.add_argument("--gated", default=None, help="comma-separated fractions: also time a gate=True converter, every session behind "
                                                   "a -40 dB gate and that fraction of them fed digital silence")
+    ap.add_argument("--crossfade", action="store_true", help="also time a crossfade=True converter, every session crossfading over "
+                                                             "10 ms, and the plain converter a second time")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
                                                          "default and on a reserved pool")
     ap.add_argument("--out", default=None)
@@ -299,6 +306,25 @@ def main():
                     again.enable_graph()
                     p50, p99 = time_ticks(again, B, chunk, args.ticks, args.warmup + bs + 1, 300)
                     rec["gate_off_again_tick_p50_ms"], rec["gate_off_again_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                    del again
+                if args.crossfade:
+                    xc = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, crossfade=True)
+                    for s in range(B):
+                        xc.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, crossfade_ms=10.0)
+                    xc.enable_graph()
+                    p50, p99 = time_ticks(xc, B, chunk, args.ticks, args.warmup + bs + 1, 300)
+                    rec["crossfade_tick_p50_ms"], rec["crossfade_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                    db = np.array(xc.seam_db())
+                    assert np.isfinite(db).all() and xc.captures == 1, (db, xc.captures)
+                    rec["crossfade_seam_db_min"], rec["crossfade_seam_db_median"], rec["crossfade_seam_db_max"] = (
+                        round(float(db.min()), 2), round(float(np.median(db)), 2), round(float(db.max()), 2))
+                    del xc
+                    again = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4)
+                    for s in range(B):
+                        again.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5)
+                    again.enable_graph()
+                    p50, p99 = time_ticks(again, B, chunk, args.ticks, args.warmup + bs + 1, 300)
+                    rec["crossfade_off_again_tick_p50_ms"], rec["crossfade_off_again_tick_p99_ms"] = round(p50, 3), round(p99, 3)
                     del again
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
