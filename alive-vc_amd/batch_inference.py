@@ -18,6 +18,10 @@ The jobs file is a JSON list; each entry:
                                                             an offset on top.  A jobs file without it runs as before
    "register_hz": 180,                                      optional: declares the register (mean f0 in Hz) of a voice given by
                                                             "lib" alone; a "target" wav's register is measured when it is encoded
+   "limit_db": -1,                                          optional, a number of dBFS <= 0 or null (default: -lim): the output
+                                                            limiter (module/multistream.py limit_waves) on the device after the
+                                                            gain, at the file's own rate, before "normalize": no sample exceeds
+                                                            the ceiling.  A jobs file without it, run without -lim, runs as before
    "blend": [{"target": "a.wav", "weight": 2},              instead of "target" / "lib": a weighted mix of 1 to 4 voices, each
              {"lib": "b.pt", "weight": 1}],                 component a voice source as above (module/multistream.py blend_spec)
    "output": "a_out.wav"}                                   optional: default <outdir>/<index>_<input name>.wav
@@ -41,6 +45,7 @@ from module.multistream import MAX_K, blend_sources, check_k     # noqa: E402
 
 JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "world_pitch", "output",
             "blend", "k", "auto_pitch", "register_hz")
+LIMIT_KEYS = ("limit_db",)               # taken per job too; a loaded job carries it only when it is limited
 
 
 def build_parser():
@@ -58,6 +63,13 @@ def build_parser():
                         help="run the kNN match and the decoder over all three chunks of every window (same samples)")
     parser.add_argument('--auto-pitch', action='store_true',
                         help="jobs follow their target voice's register unless their \"auto_pitch\" says otherwise")
+    parser.add_argument('-lim', '--limit', default=None, type=float, metavar="DB",
+                        help="output limiter: no output sample exceeds this ceiling in dBFS (<= 0), so the 16-bit edge never wraps; the "
+                             "gain starts to fall --limit-lookahead before a peak unless a job's \"limit_db\" says otherwise (default: no limiter)")
+    parser.add_argument('--limit-lookahead', default=5.0, type=float, metavar="MS",
+                        help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5)")
+    parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
+                        help="milliseconds the limiter's gain stays down after a peak (default 20)")
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV")
     return parser
 
@@ -86,9 +98,23 @@ def declared_registers(jobs):
     return out
 
 
-def load_jobs(path, k=4, auto_pitch=False):
+def job_limit(j, where, limit_db=None, lookahead_ms=5.0, hold_ms=20.0):
+    """an entry's "limit_db" (default `limit_db`; a JSON null switches the default off) -> a float <= 0, or None for a job without a
+    limiter; ValueError otherwise (the two times are those of the flags, checked with it)"""
+    from module.multistream import check_limit
+    db = j.get("limit_db", limit_db)
+    try:
+        check_limit(db, lookahead_ms, hold_ms)
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return None if db is None else float(db)
+
+
+def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold_ms=20.0):
     """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder; "auto_pitch": default
-    `auto_pitch`); ValueError on a malformed job, before anything runs on the device"""
+    `auto_pitch`); a limited job ("limit_db", default `limit_db`) also carries "limit_db", a job without a limiter does not, so a
+    file without the key loads to what it did; ValueError on a malformed job, before anything runs on the device"""
+    job_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, lookahead_ms, hold_ms)
     if not 1 <= k <= MAX_K:
         raise ValueError(f"k={k} outside [1, {MAX_K}] (the pool search's limit)")
     with open(path) as f:
@@ -101,9 +127,9 @@ def load_jobs(path, k=4, auto_pitch=False):
     for i, j in enumerate(jobs):
         if not isinstance(j, dict) or "input" not in j:
             raise ValueError(f"job {i}: an object with an \"input\" wav is required")
-        unknown = set(j) - set(JOB_KEYS)
+        unknown = set(j) - set(JOB_KEYS) - set(LIMIT_KEYS)
         if unknown:
-            raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: {JOB_KEYS})")
+            raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: {JOB_KEYS + LIMIT_KEYS})")
         blend = blend_sources(j, f"job {i}", rel) if "blend" in j else None
         if blend is None and j.get("target") is None and j.get("lib") is None:
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
@@ -117,6 +143,9 @@ def load_jobs(path, k=4, auto_pitch=False):
                  alpha=float(j.get("alpha", 0.0)), gain=float(j.get("gain", 1.0)), normalize=bool(j.get("normalize", False)),
                  world_pitch=j.get("world_pitch", False), blend=blend, k=job_k,
                  auto_pitch=j.get("auto_pitch", bool(auto_pitch)), register_hz=register_hz_of(j, f"job {i}"))
+        lim = job_limit(j, f"job {i}", limit_db, lookahead_ms, hold_ms)
+        if lim is not None:
+            e["limit_db"] = lim
         for key in ("input", "target", "lib"):
             if e[key] is not None and not os.path.isfile(e[key]):
                 raise ValueError(f"job {i}: {key} {e[key]!r} does not exist")
@@ -171,14 +200,14 @@ def main(argv=None):
     device = torch.device(args.device)
     if device.type != "cuda":
         raise SystemExit("this build runs on the MI355X only: pass -d cuda")
-    jobs = load_jobs(args.jobs, args.k, args.auto_pitch)
+    jobs = load_jobs(args.jobs, args.k, args.auto_pitch, args.limit, args.limit_lookahead, args.limit_hold)
     auto = any(j["auto_pitch"] for j in jobs)           # only then are the voices' registers measured or declared
     declared = declared_registers(jobs) if auto else {}
     # (device work starts here)
     from module.content_encoder import ContentEncoder
     from module.decoder import Decoder
     from module.f0_estimator import F0Estimator
-    from module.multistream import VoicePool, measure_register, pitch_hz
+    from module.multistream import VoicePool, limit_waves, measure_register, pitch_hz
     from module.pipeline import Converter
     from module.spectrogram import spectrogram
     from module.voice_library import VoiceLibrary
@@ -229,7 +258,10 @@ def main(argv=None):
                              auto_pitch=[j["auto_pitch"] for j in jobs] if auto else False, chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)
     for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
-        out = audio_io.resample(out, 16000, sr, post_gain_db=job["gain"]).cpu()
+        out = audio_io.resample(out, 16000, sr, post_gain_db=job["gain"])
+        if job.get("limit_db") is not None:                             # on the device, before the normalisation and the save
+            out = limit_waves(out, None, job["limit_db"], args.limit_lookahead, args.limit_hold, sr)
+        out = out.cpu()
         if job["normalize"]:
             out = out / out.abs().max()
         path = job["output"] or os.path.join(args.outputs, f"{i}_{os.path.splitext(os.path.basename(job['input']))[0]}.wav")

@@ -62,6 +62,13 @@ def build_parser():
                         help="always run spectrogram / f0 estimator / content encoder / kNN match per window as the reference does; by "
                              "default long utterances run them once per utterance with the windows assembled from it (same samples "
                              "either way; this build only)")
+    parser.add_argument('-lim', '--limit', default=None, type=float, metavar="DB",
+                        help="output limiter: no output sample exceeds this ceiling in dBFS (<= 0), so the 16-bit edge never wraps; the "
+                             "gain starts to fall --limit-lookahead before a peak (default: no limiter; this build only)")
+    parser.add_argument('--limit-lookahead', default=5.0, type=float, metavar="MS",
+                        help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5)")
+    parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
+                        help="milliseconds the limiter's gain stays down after a peak (default 20)")
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV (this build only)")
     return parser
 
@@ -73,6 +80,9 @@ def main(argv=None):
     device = torch.device(args.device)
     if device.type != "cuda":
         raise SystemExit("this build runs on the MI355X only: pass -d cuda (the reference's spelling for ROCm devices)")
+    if args.limit is not None:
+        from module.multistream import check_limit, limit_waves
+        check_limit(args.limit, args.limit_lookahead, args.limit_hold)       # (before anything is loaded)
 
     PE, CE, Dec = F0Estimator().to(device), ContentEncoder().to(device), Decoder().to(device)
     PE.load_state_dict(torch.load(args.f0_estimator_path, map_location=device))
@@ -107,7 +117,10 @@ def main(argv=None):
                            world_pitch=bool(args.world_pitch_estimation), intonation=args.intonation, f0_rate=args.f0_rate, window_batch=args.window_batch,
                            trim_context=not args.no_trim_context,
                            share_overlap=None if args.no_share_overlap else "auto")
-        out = audio_io.resample(out, 16000, sr, post_gain_db=args.gain).cpu()      # resample, then gain (:136-137)
+        out = audio_io.resample(out, 16000, sr, post_gain_db=args.gain)            # resample, then gain (:136-137)
+        if args.limit is not None:                # on the device, at the file's own rate, before -norm and the save
+            out = limit_waves(out, None, args.limit, args.limit_lookahead, args.limit_hold, sr)
+        out = out.cpu()
         if args.normalize:
             out = out / out.abs().max()
         file_name = f"{i}_{os.path.splitext(os.path.basename(path))[0]}"

@@ -161,6 +161,8 @@ PROTOTYPES = {
     "alive_gate_rows": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_gate_apply_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "alive_seam_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
+    "alive_limit_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
+    "alive_limit_waves": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP]),
     "alive_codebook_workspace_bytes": (_SZ, [_I64, _I64]),
     "alive_codebook_update": (_I, [_VP, _I64, _I, _VP, _VP, _I64, _VP, _VP, _VP]),
     "alive_codebook_stats": (_I, [_VP, _VP, _VP, _I64, _VP, _VP, _VP]),

@@ -81,6 +81,25 @@ span); tail and stored are the session's, like phi: open and close zero stored, 
 both.  It needs input_sr == output_sr (otherwise the ring's advance is not a whole number of output samples).  Everything is device
 arrays: toggling and retuning never re-capture, and a converter built without crossfade launches exactly what it did.  seam_db() reads
 the latest tick's 10 log10(sum (c - t)^2 / sum c^2) per slot back: how far the two decodes disagree, not how it sounds.
+
+Limiter: every path ends in alive_float_to_pcm16, which keeps the low 16 bits: a sample outside [-1, 1) wraps to the other end of the
+scale.  A converter built with limiter=True (csrc/limit.hip) runs alive_limit_rows LAST in the tick, after the seam and the gate's edge,
+on what is emitted: for the sessions opened or set with limit_db= (dBFS <= 0; c = min(10^(dB / 20), 32767 / 32768)) the span is
+multiplied by g[i], the fp64 mean over k = i - L + 1 .. i of m[k] = min over [k - H, k + L - 1] of the required gains a[j] = c /
+max(|y[j]|, c), and clamped to +-c.  Every window that enters g[i] contains i, so no emitted sample exceeds c whatever the neighbours
+are; the gain ramps down over L = limit_lookahead_ms, holds for H = limit_hold_ms and ramps back over L.  The lookahead is taken from the
+tick's own wave one chunk on (limit_shift: where the next tick's span will come from -- 441 against 440 samples at 44.1 kHz), so no
+latency is added; the next tick's decode differs a little from that prediction, so the gain may step a little at a seam -- the bound
+does not depend on it.  limit_hist [B, round(limit_history * fastest rate)] holds the required gains of each session's latest emitted
+samples (L - 1 + H must fit: limit_geometry names the largest value that does); it is the session's, like phi: open and close set it to
+1.0, set keeps it, a tick on which the session's limiter is off sets it to 1.0, enable_graph and the bf16 repeat save and restore it
+(with _seam_state).  The seam's saved tail lies beyond the span and stays un-limited; the gate's zeros ask for nothing (the lookahead
+lies beyond the span, where the gate's edge does not reach: a muted chunk stays zeros, though limit_db() may report a reduction).  Unlike the
+seam it works with input_sr != output_sr (the lookahead is then one tick's advance at output_sr on, never less than the span).
+Everything is device arrays: toggling and retuning never re-capture, and a converter built without limiter launches exactly what it
+did.  limit_db() reads the latest tick's 20 log10(smallest gain) per slot back (0.0: untouched).  limit_waves is the offline form
+(alive_limit_waves), bitwise the streaming one run tick by tick over the same signal.  The defaults (-1 dBFS when asked for, 5 ms,
+20 ms) are design choices: with no trained weights, how they sound is unmeasured.
 """
 import numpy as np
 import torch
@@ -986,6 +1005,134 @@ def seam_rows_(y, span_lo, shift, xlen, emit, tail, stored, g0=None, g1=None, st
     return y
 
 
+def limit_rows_(y, span_lo, span_len, shift, look, hold, ceil, emit, hist, gmin=None):
+    """alive_limit_rows in place on y [N, ld]: every emitting row's span limited to its ceiling with its lookahead taken one chunk on,
+    hist float32 [N, ld_hist] (the rows' state: the required gains of the latest emitted samples) moved on.  gmin: float32 [N] or
+    None"""
+    n, ld = y.shape
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError("limit_rows_: y must be contiguous float32 [N, ld]")
+    if hist.dtype != torch.float32 or not hist.is_contiguous() or hist.dim() != 2 or hist.shape[0] != n:
+        raise ValueError("limit_rows_: hist must be contiguous float32 [N, ld_hist]")
+    nat.check(nat.lib().alive_limit_rows(nat.ptr(y), n, ld, nat.ptr(span_lo), nat.ptr(span_len), nat.ptr(shift), nat.ptr(look),
+                                         nat.ptr(hold), nat.ptr(ceil), nat.ptr(emit), nat.ptr(hist), hist.shape[1], nat.ptr(gmin),
+                                         nat.stream()), "alive_limit_rows")
+    return y
+
+
+def limit_waves_rows(y, lens, look, hold, ceil, gmin=None):
+    """alive_limit_waves: y float32 [N, ld], device int32 lens [N], one look / hold in samples, device float32 ceil [N] -> a new
+    tensor, row n's first lens[n] samples limited as one signal, the rest copied.  gmin: float32 [N] or None"""
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.dim() != 2:
+        raise ValueError("limit_waves_rows: y must be contiguous float32 [N, ld]")
+    n, ld = y.shape
+    out = torch.empty_like(y)
+    nat.check(nat.lib().alive_limit_waves(nat.ptr(out), nat.ptr(y), n, ld, nat.ptr(lens), int(look), int(hold), nat.ptr(ceil),
+                                          nat.ptr(gmin), nat.stream()), "alive_limit_waves")
+    return out
+
+
+LIMIT_TILE, LIMIT_MAX_HIST = 1024, 3072        # ALIVE_LIMIT_TILE, ALIVE_LIMIT_MAX_HIST (include/alive_vc.h)
+LIMIT_CEIL_MAX = 32767.0 / 32768.0             # the largest float sample that alive_float_to_pcm16 does not wrap
+
+
+def _number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def check_limit(limit_db, lookahead_ms=5.0, hold_ms=20.0):
+    """a limiter's settings -> (ceiling, lookahead_ms, hold_ms) as floats, None for limit_db None (off; the two times are still
+    checked).  ValueError unless limit_db is None or a finite number <= 0 (not a bool), limit_lookahead_ms a finite number > 0 and
+    limit_hold_ms a finite number >= 0.  The ceiling is min(10^(dB / 20), 32767 / 32768): 0 dB still never wraps"""
+    if not _number(lookahead_ms) or not (np.isfinite(lookahead_ms) and lookahead_ms > 0):
+        raise ValueError(f"limit_lookahead_ms={lookahead_ms!r} must be a finite number of milliseconds > 0")
+    if not _number(hold_ms) or not (np.isfinite(hold_ms) and hold_ms >= 0):
+        raise ValueError(f"limit_hold_ms={hold_ms!r} must be a finite number of milliseconds >= 0")
+    if limit_db is None:
+        return None
+    if not _number(limit_db) or not (np.isfinite(limit_db) and limit_db <= 0):
+        raise ValueError(f"limit_db={limit_db!r} must be a finite number of dBFS <= 0, or None for no limiter")
+    return min(10.0 ** (float(limit_db) / 20.0), LIMIT_CEIL_MAX), float(lookahead_ms), float(hold_ms)
+
+
+def limit_samples(lookahead_ms, hold_ms, rate):
+    """(L, H) in samples at `rate`: L = max(1, round(lookahead_ms * rate / 1000)), H = round(hold_ms * rate / 1000)"""
+    return max(1, int(round(float(lookahead_ms) * rate / 1000.0))), int(round(float(hold_ms) * rate / 1000.0))
+
+
+def limit_geometry(chunk_r, buffersize, rate, limit_db, lookahead_ms, hold_ms, row_len, ld_hist, shift=None):
+    """a session's limiter -> (span_lo, shift, L, H, c) of alive_limit_rows: span_lo the first sample step() emits of its wave of
+    row_len samples, shift the ring's advance per tick in the session's samples (default chunk_r), L and H as limit_samples forms
+    them, c the ceiling; L = H = 0 and c = 1 for limit_db None (off).  ValueError (check_limit's, or one that names the largest value
+    that fits) unless L <= chunk_r, span_lo + shift + L - 1 <= row_len and L - 1 + H <= ld_hist, the width of the history"""
+    chunk_r, buffersize, rate, row_len, ld_hist = int(chunk_r), int(buffersize), int(rate), int(row_len), int(ld_hist)
+    shift = chunk_r if shift is None else int(shift)
+    lo = buffersize * chunk_r // 2 - chunk_r // 2
+    checked = check_limit(limit_db, lookahead_ms, hold_ms)
+    if checked is None:
+        return lo, shift, 0, 0, 1.0
+    c, look_ms, hold_ms_ = checked
+    L, H = limit_samples(look_ms, hold_ms_, rate)
+    l_max = min(chunk_r, row_len - lo - shift + 1, ld_hist + 1)
+    if L > l_max:
+        ms_max = max(l_max, 0) * 1000.0 / rate
+        raise ValueError(f"limit_lookahead_ms={lookahead_ms!r} is {L} samples at {rate} Hz; a session with {chunk_r}-sample chunks in "
+                         f"a wave of {row_len} and a history of {ld_hist} takes 1 to {max(l_max, 0)} (the largest "
+                         f"limit_lookahead_ms that fits is {ms_max:g})")
+    h_max = ld_hist - (L - 1)
+    if H > h_max:
+        raise ValueError(f"limit_hold_ms={hold_ms!r} is {H} samples at {rate} Hz; beside a lookahead of {L} a history of {ld_hist} "
+                         f"takes 0 to {h_max} (the largest limit_hold_ms that fits is {h_max * 1000.0 / rate:g})")
+    return lo, shift, L, H, c
+
+
+def limit_history_width(limit_history, rate):
+    """the width of the limiter's history, round(limit_history * rate) samples at the fastest declared rate.  ValueError unless it is
+    a finite number of seconds > 0 (not a bool) and the width lies in [1, LIMIT_MAX_HIST]"""
+    if not _number(limit_history) or not (np.isfinite(limit_history) and limit_history > 0):
+        raise ValueError(f"limit_history={limit_history!r} must be a finite number of seconds > 0")
+    width = int(round(float(limit_history) * int(rate)))
+    if not 1 <= width <= LIMIT_MAX_HIST:
+        raise ValueError(f"limit_history={limit_history!r} is {width} samples at {int(rate)} Hz; the limiter keeps 1 to "
+                         f"{LIMIT_MAX_HIST} (the largest limit_history that fits is {LIMIT_MAX_HIST / int(rate):g})")
+    return width
+
+
+def gmin_db(gmin):
+    """alive_limit_rows' smallest gains -> 20 log10(g) each: 0.0 for an untouched row, -inf for a gain of 0"""
+    with np.errstate(divide="ignore"):
+        return [float(20.0 * np.log10(np.float64(g))) if g != 1.0 else 0.0 for g in gmin]
+
+
+def limit_waves(wave, lens=None, limit_db=-1.0, lookahead_ms=5.0, hold_ms=20.0, rate=16000, return_gain=False):
+    """The offline limiter: wave float32 [N, ld] (or [ld]) on the device at `rate` Hz -> a new tensor of its shape, row n's first
+    lens[n] samples (default: the whole row) limited as one signal to limit_db (a number, or one per row; None: the row is copied),
+    the rest copied (alive_limit_waves; bitwise what a streaming session's limiter makes of the same signal).  ValueError as
+    check_limit, and unless L - 1 + H <= LIMIT_MAX_HIST.  return_gain=True: also the smallest gain per row as dB (one host read)"""
+    one = wave.dim() == 1
+    y = (wave[None] if one else wave).contiguous()
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError(f"limit_waves: wave must be float32 [N, ld] or [ld], got {tuple(wave.shape)} {wave.dtype}")
+    n, ld = y.shape
+    dbs = list(limit_db) if isinstance(limit_db, (list, tuple)) else [limit_db] * n
+    if len(dbs) != n:
+        raise ValueError(f"limit_waves: {len(dbs)} limit_db for {n} rows")
+    ceils = [check_limit(db, lookahead_ms, hold_ms) for db in dbs]
+    L, H = limit_samples(lookahead_ms, hold_ms, rate)
+    if L - 1 + H > LIMIT_MAX_HIST:
+        raise ValueError(f"limit_waves: a lookahead of {L} and a hold of {H} samples at {rate} Hz: L - 1 + H is at most "
+                         f"{LIMIT_MAX_HIST} (the largest limit_hold_ms that fits is {(LIMIT_MAX_HIST - L + 1) * 1000.0 / rate:g})")
+    lens = [ld] * n if lens is None else [int(v) for v in lens]
+    if len(lens) != n:
+        raise ValueError(f"limit_waves: {len(lens)} lens for {n} rows")
+    dev = y.device
+    ceil = torch.tensor([0.0 if c is None else c[0] for c in ceils], dtype=torch.float32, device=dev)     # (0: the row is copied)
+    gmin = torch.empty(n, dtype=torch.float32, device=dev) if return_gain else None
+    out = limit_waves_rows(y, torch.tensor(lens, dtype=torch.int32, device=dev), L, H, ceil, gmin)
+    out = out[0] if one else out
+    return (out, gmin_db(gmin.tolist())) if return_gain else out
+
+
 def wave_length(frames, rate):
     """the samples of a converter's final wave: the decoder's 320 per frame at 16 kHz, resampled to `rate`"""
     orig, new = audio_io._reduced(16000, rate)
@@ -1144,17 +1291,26 @@ def db_scale(db):
 
 
 _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold",
-           "crossfade_ms")
+           "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms")
 
 
 class MultiStreamConverter:
     auto_pitch = False                 # (set per converter in __init__: whether the tick carries the auto-pitch kernel)
     gate = False                       # (likewise: whether the tick carries the two gate kernels)
     crossfade = False                  # (likewise: whether the tick carries the seam kernel)
+    limiter = False                    # (likewise: whether the tick carries the limiter kernel)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
-                 auto_pitch_half_life=10.0, auto_pitch_prior=0.5, gate=False, gate_lookahead=None, crossfade=False):
+                 auto_pitch_half_life=10.0, auto_pitch_prior=0.5, gate=False, gate_lookahead=None, crossfade=False,
+                 limiter=False, limit_history=0.05):
+        if not isinstance(limiter, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: limiter must be a bool, got {limiter!r}")
+        if limiter:                        # (checked before anything is built)
+            try:
+                ld_hist = limit_history_width(limit_history, max([int(r) for r in (rates or ())] + [int(output_sr)]))
+            except ValueError as e:
+                raise ValueError(f"MultiStreamConverter: {e}") from None
         if not isinstance(crossfade, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: crossfade must be a bool, got {crossfade!r}")
         if crossfade and input_sr != output_sr:
@@ -1309,6 +1465,22 @@ class MultiStreamConverter:
                 lo, ln = self._span(self.chunk)
                 self.span_lo = torch.full((B,), lo, **i32)
                 self.span_len = torch.full((B,), ln, **i32)
+        # limiter: the limiter kernel is part of the tick (captured once), last, on what is emitted; per row, look is the session's
+        # lookahead in samples (0: off), hold its hold, ceil its ceiling.  limit_hist is the session's, like phi
+        self.limiter = bool(limiter)
+        if self.limiter:
+            i32 = dict(dtype=torch.int32, device=dev)
+            self._limit_len = {r: self._wave_len(r) for r in rates}    # the samples of a session's final wave, per rate
+            self.look = torch.zeros(B, **i32)
+            self.hold = torch.zeros(B, **i32)
+            self.ceil = torch.ones(B, dtype=torch.float32, device=dev)
+            self.limit_hist = torch.ones(B, ld_hist, dtype=torch.float32, device=dev)
+            self.limit_gmin = torch.ones(B, dtype=torch.float32, device=dev)
+            self.limit_shift = torch.full((B,), self._limit_shift(self.chunk), **i32)
+            if not (self.gate or self.crossfade):
+                lo, ln = self._span(self.chunk)
+                self.span_lo = torch.full((B,), lo, **i32)
+                self.span_len = torch.full((B,), ln, **i32)
         self.phi = torch.zeros(B, 64, device=dev)
         self._in = torch.zeros(B, ld_in, device=dev)
         self._graph = None
@@ -1371,6 +1543,32 @@ class MultiStreamConverter:
         except ValueError as e:
             raise ValueError(f"slot {slot}: {e}") from None
 
+    def _limit_shift(self, cs):
+        """the ring's advance per tick in samples of a session's final wave, for chunks of cs samples: cs where input_sr ==
+        output_sr; otherwise the advance at output_sr, but never less than the span (step() cuts cs samples whatever output_sr is)"""
+        if self.input_sr == self.output_sr:
+            return cs
+        return max(cs, int(round(cs * self.output_sr / self.input_sr)))
+
+    def _session_limit(self, slot, p, rate=None):
+        """a session's limiter -> (L, H, c) at its rate ((0, 0, 1.0): off), checked against the converter"""
+        db, look, hold = p.get("limit_db"), p.get("limit_lookahead_ms", 5.0), p.get("limit_hold_ms", 20.0)
+        try:
+            if check_limit(db, look, hold) is None:
+                return 0, 0, 1.0
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+        if not self.limiter:
+            raise ValueError(f"slot {slot}: limit_db={db!r} needs a converter built with MultiStreamConverter(..., limiter=True)")
+        rate = int(self.rate[slot] if rate is None else rate)
+        cs = self._chunk_at(rate)
+        out_rate = rate if self._rt is not None else int(self.output_sr)
+        try:
+            return limit_geometry(cs, self.buffersize, out_rate, db, look, hold, self._limit_len[rate], self.limit_hist.shape[1],
+                                  self._limit_shift(cs))[2:]
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+
     def _session_gate(self, slot, p):
         """a session's gate settings -> (on, thr_ms, hold_ticks), checked against the converter"""
         db, hold = p.get("gate_db"), p.get("gate_hold", 0.2)
@@ -1389,6 +1587,7 @@ class MultiStreamConverter:
         k = self._session_k(slot, p["k"])
         gate = self._session_gate(slot, p)
         xlen = self._session_seam(slot, p, rate)
+        limit = self._session_limit(slot, p, rate)
         names, weights = blend_spec(p["voice"], self.pool, k, self.S)
         world = p["world_pitch"]
         if not isinstance(world, (bool, np.bool_)):
@@ -1428,6 +1627,8 @@ class MultiStreamConverter:
             self.gate_on[slot], self.thr_ms[slot], self.hold_ticks[slot] = gate
         if self.crossfade:
             self.xlen[slot] = xlen
+        if self.limiter:
+            self.look[slot], self.hold[slot], self.ceil[slot] = limit
 
     def _write_segments(self, slot, names):
         """the slot's rows of seg_lo / seg_len from where its voices lie in the pool now"""
@@ -1478,10 +1679,12 @@ class MultiStreamConverter:
         if self._rt is None:
             return
         c = self._chunks[rate]
-        if self.gate or self.crossfade:
+        if self.gate or self.crossfade or self.limiter:
             self.span_lo[slot], self.span_len[slot] = self._span(c)
         if self.crossfade:
             self.shift[slot] = c
+        if self.limiter:
+            self.limit_shift[slot] = self._limit_shift(c)
         self.slot_chunk[slot] = c
         self.len_in[slot] = c * self.buffersize
         self.pair_in[slot] = self._rt.pair(rate, 16000)
@@ -1489,7 +1692,8 @@ class MultiStreamConverter:
         self.len_out[slot] = self._lout[rate]
 
     def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None,
-             auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None):
+             auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0,
+             limit_hold_ms=20.0):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
@@ -1499,14 +1703,18 @@ class MultiStreamConverter:
         input gate, a threshold in dBFS on its 16 kHz ring after the input gain (None: no gate); gate_hold: the seconds (>= 0) it
         stays open after the last loud tick.  A gated session starts closed: its first chunk fades in.  crossfade_ms (needs a
         crossfade=True converter): the milliseconds over which the head of every chunk is faded in from the previous tick's
-        continuation (None: a hard cut), at most the session's emitted span; the first chunk has nothing to fade from"""
+        continuation (None: a hard cut), at most the session's emitted span; the first chunk has nothing to fade from.  limit_db
+        (needs a limiter=True converter): the session's output limiter, a ceiling in dBFS <= 0 that no emitted sample exceeds (None:
+        no limiter, the int16 edge wraps); limit_lookahead_ms: how long before a peak the gain starts to fall (and after the hold,
+        how long it takes to come back), at most the session's chunk; limit_hold_ms: how long the gain stays down after a peak"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
             raise ValueError(f"slot {slot}: rate {rate} Hz was not declared (rates={list(self.rates)}): pass it in "
                              "MultiStreamConverter(..., rates=...)")
         p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch,
-                 k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold, crossfade_ms=crossfade_ms)
+                 k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold, crossfade_ms=crossfade_ms, limit_db=limit_db,
+                 limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms)
         self._apply(slot, p, rate)                            # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -1520,12 +1728,15 @@ class MultiStreamConverter:
             self.gate_state[slot] = 0                         # closed, no hold: the first emitted chunk fades in
         if self.crossfade:
             self.stored[slot] = 0                             # never fade from another session's tail
+        if self.limiter:
+            self._limit_reset(slot)                           # a new stream: no peak behind it
         return self
 
     def set(self, slot, **params):
         """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
-        gate_db, gate_hold, crossfade_ms; the gate's state and the saved tail are kept: a longer crossfade fades over what the tail
-        holds this tick and in full from the next).
+        gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms, limit_hold_ms; the gate's state, the saved tail and the
+        limiter's history are kept: a longer crossfade fades over what the tail holds this tick and in full from the next, and a
+        limiter switched on or retuned sees the required gains of the samples already emitted).
         The running source register is kept: a new voice changes the target only, and auto_pitch=True after False resumes from
         what the session had heard while it was on (nothing, if it never was)"""
         slot = self._slot(slot)
@@ -1568,6 +1779,11 @@ class MultiStreamConverter:
         if self.crossfade:
             self.xlen[slot] = 0
             self.stored[slot] = 0
+        if self.limiter:
+            self.look[slot] = 0
+            self.hold[slot] = 0
+            self.ceil[slot] = 1.0
+            self._limit_reset(slot)
         self._set_rate(slot, int(self.input_sr))             # a closed slot: the converter's own rate, silence
         return self
 
@@ -1578,6 +1794,17 @@ class MultiStreamConverter:
             raise ValueError("gate_open needs a converter built with MultiStreamConverter(..., gate=True)")
         on, was = self.gate_on.tolist(), self.gate_state[:, 1].tolist()
         return [bool(self.is_open[b] and (was[b] if on[b] else True)) for b in range(self.B)]
+
+    def _limit_reset(self, slot):
+        self.limit_hist[slot] = 1.0
+        self.limit_gmin[slot] = 1.0
+
+    def limit_db(self):
+        """how far the limiter turned each slot down in the latest tick, a list of B floats: 20 log10 of the smallest gain of the
+        slot's emitted span; 0.0 for a slot that was not touched (or does not limit, or did not emit yet).  One host read"""
+        if not self.limiter:
+            raise ValueError("limit_db needs a converter built with MultiStreamConverter(..., limiter=True)")
+        return gmin_db(self.limit_gmin.tolist())
 
     def seam_db(self):
         """the seam statistic of the latest tick, a list of B floats: 10 log10(sum (c - t)^2 / sum c^2) over the faded head of each
@@ -1656,6 +1883,11 @@ class MultiStreamConverter:
                        self.g0 if self.gate else None, self.g1 if self.gate else None, self.seam_stats)
         if self.gate:
             gate_apply_rows_(wave, self.span_lo, self.span_len, self.g0, self.g1)
+        if self.limiter:                                      # last: the limiter sees what is emitted (the seam's tail stays un-limited)
+            if wave.shape[1] != max(self._limit_len.values()):
+                raise RuntimeError(f"final wave of {wave.shape[1]} samples, the limiter expects {max(self._limit_len.values())}")
+            limit_rows_(wave, self.span_lo, self.span_len, self.limit_shift, self.look, self.hold, self.ceil, self.emit,
+                        self.limit_hist, self.limit_gmin)
         phi_next = torch.where(self.emit, phi_out[:, :, self.end_of_output], torch.zeros_like(phi))
         return wave, phi_next
 
@@ -1677,13 +1909,21 @@ class MultiStreamConverter:
         return self
 
     def _seam_state(self):
-        """a copy of the sessions' tails and how much of them is valid (None without crossfade)"""
-        return (self.tail.clone(), self.stored.clone()) if self.crossfade else None
+        """a copy of the sessions' tails and how much of them is valid (None without crossfade) -- and, in a limiter converter, of
+        the limiter's histories and latest gains: (tail, stored, limit_hist, limit_gmin), the absent halves None"""
+        if not (self.crossfade or self.limiter):
+            return None
+        seam = (self.tail.clone(), self.stored.clone()) if self.crossfade else (None, None)
+        return seam + ((self.limit_hist.clone(), self.limit_gmin.clone()) if self.limiter else (None, None))
 
     def _seam_restore(self, saved):
         if saved is not None:
-            self.tail.copy_(saved[0])
-            self.stored.copy_(saved[1])
+            if saved[0] is not None:
+                self.tail.copy_(saved[0])
+                self.stored.copy_(saved[1])
+            if len(saved) > 2 and saved[2] is not None:
+                self.limit_hist.copy_(saved[2])
+                self.limit_gmin.copy_(saved[3])
 
     def _run(self):
         if self._reserved:

@@ -14,6 +14,12 @@ crossfade") at one row between the output resample and the gate's edge: the head
 continuation of itself.  It needs input_sr == output_sr.  The saved tail lives beside the phase: `reset`, `enable_graph` and a
 `step_device(continues=False)` drop it (the ring is then unrelated to the previous one), the bf16 repeat restores it.  Without
 crossfade_ms the converter launches what it did.
+
+Output limiter (`-lim`): RealtimeConverter(limit_db=DB, limit_lookahead_ms=MS, limit_hold_ms=MS) runs alive_limit_rows (csrc/limit.hip,
+module/multistream.py "Limiter") at one row, last, on the emitted span of the final wave: no emitted sample exceeds the ceiling, so the
+int16 edge never wraps.  It works on both step forms and with input_sr != output_sr.  The history of required gains lives beside the
+phase: `reset`, `enable_graph` and a `step_device(continues=False)` set it to 1.0, the bf16 repeat restores it.  Without limit_db the
+converter launches what it did.
 """
 import numpy as np
 import torch
@@ -122,11 +128,18 @@ def capture_step(device, step, phi):
 
 
 class RealtimeConverter:
+    limiter = False                    # (set per converter in __init__: whether the step carries the limiter kernel)
+
     def __init__(self, content_encoder, f0_estimator, decoder, library_tokens, device="cuda", chunk=960, buffersize=8,
                  input_sr=16000, output_sr=16000, f0_rate=1.0, pitch=0.0, k=4, alpha=0.0, gain=0.0, input_gain=0.0,
                  reuse_interior="auto", world_pitch=False, gate_db=None, gate_hold=0.2, gate_lookahead=None,
-                 crossfade_ms=None):
+                 crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0, limit_hold_ms=20.0, limit_history=0.05):
         self.device = torch.device(device)
+        self.limiter = limit_db is not None
+        if self.limiter:                   # (checked before anything is built)
+            from .multistream import check_limit, limit_history_width
+            check_limit(limit_db, limit_lookahead_ms, limit_hold_ms)
+            limit_width = limit_history_width(limit_history, output_sr)
         self.crossfade = crossfade_ms is not None
         if self.crossfade:                 # (checked before anything is built)
             from .multistream import check_crossfade_ms
@@ -183,6 +196,24 @@ class RealtimeConverter:
             self._seam_tail = torch.zeros(1, 2 * (chunk // 2), device=dev)
             self._seam_stored = torch.zeros(1, **i32)
             self._seam_stats = torch.zeros(1, 2, dtype=torch.float64, device=dev)
+        if self.limiter:
+            # the multi-session limiter at one row: an always-emitting session; _limit_hist is the stream's, like the phase
+            from .multistream import limit_geometry, wave_length
+            dev, i32 = self.device, dict(dtype=torch.int32, device=self.device)
+            self.limit_db_, self.limit_lookahead_ms, self.limit_hold_ms = float(limit_db), float(limit_lookahead_ms), float(limit_hold_ms)
+            self._limit_len = wave_length(frames, output_sr)
+            shift = chunk if input_sr == output_sr else max(chunk, int(round(chunk * output_sr / input_sr)))
+            lo, shift, look, hold, c = limit_geometry(chunk, buffersize, output_sr, limit_db, limit_lookahead_ms, limit_hold_ms,
+                                                      self._limit_len, limit_width, shift)
+            self._limit_lo = torch.tensor([lo], **i32)
+            self._limit_span = torch.tensor([2 * (chunk // 2)], **i32)
+            self._limit_shift = torch.tensor([shift], **i32)
+            self._limit_look = torch.tensor([look], **i32)
+            self._limit_hold = torch.tensor([hold], **i32)
+            self._limit_ceil = torch.tensor([c], dtype=torch.float32, device=dev)
+            self._limit_emit = torch.ones(1, dtype=torch.bool, device=dev)
+            self._limit_hist = torch.ones(1, limit_width, device=dev)
+            self._limit_gmin = torch.ones(1, device=dev)
         self._side = None                  # side stream of the f0 estimator (see _f0_on_side_stream)
         self._f0_bufs = {}
         # interior reuse: only where it is exact -- no resampling in front (the ring IS the 16 kHz signal), a shift of whole
@@ -220,7 +251,7 @@ class RealtimeConverter:
         content, f0 = self._front_end(spectrogram(data), data)
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0                  # (a view of the per-shape side-stream buffer: valid until the next step)
-        wave = self._gate_edge(self._seam(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain)))[0]   # gain, then resample
+        wave = self._limit(self._gate_edge(self._seam(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain))))[0]   # gain, then resample
         return wave, phi_out[:, :, self.end_of_output]
 
     def _gate_decide(self, data):
@@ -250,6 +281,30 @@ class RealtimeConverter:
                               self._seam_stored, self._g0 if self.gate else None, self._g1 if self.gate else None,
                               self._seam_stats)
         return wave
+
+    def _limit(self, wave):
+        """limiter on: the emitted span of the final wave [1, L] limited to the ceiling, in place, its lookahead taken one chunk on
+        (alive_limit_rows at one row; last, after the gate's edge)"""
+        if self.limiter:
+            from .multistream import limit_rows_
+            if wave.shape[1] != self._limit_len:
+                raise RuntimeError(f"final wave of {wave.shape[1]} samples, the limiter expects {self._limit_len}")
+            wave = limit_rows_(wave.contiguous(), self._limit_lo, self._limit_span, self._limit_shift, self._limit_look,
+                               self._limit_hold, self._limit_ceil, self._limit_emit, self._limit_hist, self._limit_gmin)
+        return wave
+
+    def _limit_reset(self):
+        if self.limiter:
+            self._limit_hist.fill_(1.0)
+            self._limit_gmin.fill_(1.0)
+
+    def limit_db(self):
+        """how far the limiter turned the latest step down: 20 log10 of the smallest gain of its emitted span; 0.0: untouched (one
+        host read)"""
+        if not self.limiter:
+            raise ValueError("limit_db needs a converter built with RealtimeConverter(..., limit_db=DB)")
+        from .multistream import gmin_db
+        return gmin_db(self._limit_gmin.tolist())[0]
 
     def _f0_on_side_stream(self, spec, data=None):
         """f0_on_side_stream with the estimator's f0 and the pitch transform.  With world_pitch the branch is WORLD's f0 of the
@@ -299,7 +354,7 @@ class RealtimeConverter:
             self._c_f0[:, :, a:].copy_(f0[:, :, margin:])
         wave, phi_out = self.dec(self._c_feat, f0=self._c_f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = self._c_f0
-        wave = self._gate_edge(self._seam(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain)))[0]
+        wave = self._limit(self._gate_edge(self._seam(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain))))[0]
         return wave, phi_out[:, :, self.end_of_output]
 
     def _front_end_slice(self, samples, f_lo, f_hi):
@@ -323,6 +378,7 @@ class RealtimeConverter:
             self._gate_state.zero_()       # (capture_step ran the step three times)
         if self.crossfade:
             self._seam_stored.zero_()
+        self._limit_reset()
         self._cache_valid = False          # interior reuse: the captured step is the incremental one; the first real step runs in full
         return self
 
@@ -338,6 +394,7 @@ class RealtimeConverter:
             self._gate_state.zero_()
         if self.crossfade:
             self._seam_stored.zero_()
+        self._limit_reset()
         return self
 
     def seam_db(self):
@@ -366,6 +423,7 @@ class RealtimeConverter:
             self._cache_valid = False
             if self.crossfade:
                 self._seam_stored.zero_()
+            self._limit_reset()
         return self._step_device(ring_f32)
 
     def _step_device(self, ring_f32):
@@ -382,7 +440,7 @@ class RealtimeConverter:
         self.phi = phi_next
         return wave
 
-    def _repeat_on_bf16(self, data, saved_phi, saved_gate=None, saved_seam=None):
+    def _repeat_on_bf16(self, data, saved_phi, saved_gate=None, saved_seam=None, saved_limit=None):
         """a chunk drove an activation out of fp16's range: switch the process to bf16 planes (ops.switch_to_bf16), restore the
         phase (and the gate state, and the crossfade's tail) the chunk started from, drop the frame caches, re-capture the step if it
         was a hipGraph, and convert the chunk again -- the whole front end, but crossfaded as the first attempt would have been"""
@@ -398,6 +456,9 @@ class RealtimeConverter:
         if saved_seam is not None:
             self._seam_tail.copy_(saved_seam[0])
             self._seam_stored.copy_(saved_seam[1])
+        if saved_limit is not None:
+            self._limit_hist.copy_(saved_limit[0])
+            self._limit_gmin.copy_(saved_limit[1])
         wave = self._step_device(data)                  # (not step_device(continues=False), which would drop the restored tail)
         return audio_io.float_to_pcm16(wave).cpu().numpy()
 
@@ -416,9 +477,10 @@ class RealtimeConverter:
             saved_phi = self._g_phi.clone() if getattr(self, "_graph", None) is not None else self.phi
             saved_gate = self._gate_state.clone() if self.gate else None
             saved_seam = (self._seam_tail.clone(), self._seam_stored.clone()) if self.crossfade else None
+            saved_limit = (self._limit_hist.clone(), self._limit_gmin.clone()) if self.limiter else None
         wave = self.step_device(data, continues=True)                # this ring is the previous one advanced by one chunk
         out = audio_io.float_to_pcm16(wave).cpu().numpy()            # C cast of numpy's astype, no clipping (:180-183)
         if guarded and ops.f16_saturations(reset=True) > 0:          # (the copy above has synchronised: six 4-byte reads)
-            out = self._repeat_on_bf16(data, saved_phi, saved_gate, saved_seam)
+            out = self._repeat_on_bf16(data, saved_phi, saved_gate, saved_seam, saved_limit)
         center = self.buffersize * self.chunk // 2
         return out[center - self.chunk // 2: center + self.chunk // 2]

@@ -18,6 +18,11 @@ The sessions file is a JSON list; each entry:
    "crossfade_ms": 10,                    optional, a number of milliseconds > 0 or null (default: --crossfade): the head of every
                                           chunk of the session is faded in from the previous tick's continuation over that long
                                           (module/multistream.py "Seam crossfade"; at most the session's chunk; needs -isr == -osr)
+   "limit_db": -1, "limit_lookahead_ms": 5, "limit_hold_ms": 20,     optional: the session's output limiter (module/multistream.py
+                                          "Limiter"): a ceiling in dBFS <= 0 that no emitted sample exceeds (null: no limiter;
+                                          default -lim), the milliseconds over which the gain falls ahead of a peak (at most the
+                                          session's chunk; default --limit-lookahead) and those it stays down after one (default
+                                          --limit-hold)
    "codebook": 4096,                      optional, an integer >= 1 or null (default: --codebook): the session's voice is condensed to
                                           that many centroid rows by k-means when it is packed or enrolled (module/codebook.py); a
                                           voice of that many rows or fewer stays as it is.  A codebook's rows are means: use k 1 or 2
@@ -41,6 +46,8 @@ The converter carries the two gate kernels only if some session ends up gated ("
 without -thr, runs as before.
 The converter carries the seam kernel only if some session ends up with a crossfade ("crossfade_ms", or --crossfade): a file without
 the key, run without the flag, runs as before.
+The converter carries the limiter kernel only if some session ends up limited ("limit_db", or -lim): a file without the key, run
+without the flag, runs as before.
 The voices are condensed only for sessions with a "codebook" (or under --codebook): a file without the key, run without the flag, runs
 as before.  The size is part of the voice's pool name: sessions on the same sources at different sizes get different voices; a blend's
 components are each condensed to the session's size.
@@ -69,7 +76,7 @@ from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
 from module.multistream import (MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
-                                check_crossfade_ms, gate_hold_ticks, gate_thr_ms, measure_register)
+                                check_crossfade_ms, check_limit, gate_hold_ticks, gate_thr_ms, measure_register)
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
@@ -77,6 +84,7 @@ SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "
                 "blend", "k", "auto_pitch", "register_hz")
 GATE_KEYS = ("gate_db", "gate_hold")     # taken per session too; a loaded session carries them only when it is gated
 SEAM_KEYS = ("crossfade_ms",)            # taken per session too; a loaded session carries it only when it crossfades
+LIMIT_KEYS = ("limit_db", "limit_lookahead_ms", "limit_hold_ms")      # likewise; a loaded session carries them only when it limits
 CODEBOOK_KEYS = ("codebook",)            # taken per session too; a loaded session carries it only when its voice is condensed
 
 
@@ -107,6 +115,13 @@ def build_parser():
     parser.add_argument('--crossfade', default=None, type=float, metavar="MS",
                         help="seam crossfade: sessions fade the head of every chunk in from the previous tick's continuation over "
                              "MS milliseconds unless their \"crossfade_ms\" says otherwise (default: hard cuts)")
+    parser.add_argument('-lim', '--limit', default=None, type=float, metavar="DB",
+                        help="output limiter: no emitted sample exceeds this ceiling in dBFS (<= 0), so the 16-bit edge never wraps; the "
+                             "gain starts to fall --limit-lookahead before a peak unless a session's \"limit_db\" says otherwise (default: no limiter)")
+    parser.add_argument('--limit-lookahead', default=5.0, type=float, metavar="MS",
+                        help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5; a session's \"limit_lookahead_ms\" overrides)")
+    parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
+                        help="milliseconds the limiter's gain stays down after a peak (default 20; a session's \"limit_hold_ms\" overrides)")
     parser.add_argument('--codebook', default=None, type=int, metavar="SIZE",
                         help="condense every session's voice to SIZE centroid rows by k-means unless its \"codebook\" says otherwise "
                              "(default: the voices as they are)")
@@ -161,6 +176,18 @@ def session_crossfade(s, where, crossfade_ms=None):
         raise ValueError(f"{where}: {e}") from None
 
 
+def session_limit(s, where, limit_db=None, lookahead_ms=5.0, hold_ms=20.0):
+    """an entry's limiter -> (limit_db, limit_lookahead_ms, limit_hold_ms) as floats, or None for a session without one: "limit_db"
+    (default `limit_db`; a JSON null switches the limiter off) a finite number <= 0, "limit_lookahead_ms" (default `lookahead_ms`) a
+    finite number > 0, "limit_hold_ms" (default `hold_ms`) a finite number >= 0; ValueError otherwise"""
+    db, look, hold = s.get("limit_db", limit_db), s.get("limit_lookahead_ms", lookahead_ms), s.get("limit_hold_ms", hold_ms)
+    try:
+        checked = check_limit(db, look, hold)
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return None if checked is None else (float(db), checked[1], checked[2])
+
+
 def session_codebook(s, where, codebook=None):
     """an entry's "codebook" (default `codebook`) -> an integer >= 1, or None for a voice that stays as it is (a JSON null switches
     the default off); ValueError otherwise"""
@@ -172,15 +199,19 @@ def session_codebook(s, where, codebook=None):
     return size
 
 
-def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None, crossfade_ms=None):
+def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None, crossfade_ms=None, limit_db=None,
+                  limit_lookahead_ms=5.0, limit_hold_ms=20.0):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
-    condensed, and "crossfade_ms" (default `crossfade_ms`) only on a session that crossfades; ValueError on a malformed entry"""
+    condensed, "crossfade_ms" (default `crossfade_ms`) only on a session that crossfades, and "limit_db" / "limit_lookahead_ms" /
+    "limit_hold_ms" (defaults `limit_db`, `limit_lookahead_ms`, `limit_hold_ms`) only on a session that limits; ValueError on a
+    malformed entry"""
     k = check_k(k, "-k")
     session_codebook({}, "--codebook", codebook)
     session_gate({}, "-thr / --gate-hold", gate_db, gate_hold)
     session_crossfade({}, "--crossfade", crossfade_ms)
+    session_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, limit_lookahead_ms, limit_hold_ms)
     with open(path) as f:
         sessions = json.load(f)
     if not isinstance(sessions, list) or not sessions:
@@ -190,13 +221,14 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     for i, s in enumerate(sessions):
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
-        unknown = set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(CODEBOOK_KEYS)
+        unknown = set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(CODEBOOK_KEYS)
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + CODEBOOK_KEYS})")
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + CODEBOOK_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
+        lim = session_limit(s, f"session {i}", limit_db, limit_lookahead_ms, limit_hold_ms)
         rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))      # noqa: E731
         blend = blend_sources(s, f"session {i}", rel) if "blend" in s else None
         if blend is None and s.get("target") is None and s.get("lib") is None:
@@ -219,6 +251,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             e["gate_db"], e["gate_hold"] = gate
         if xf is not None:
             e["crossfade_ms"] = xf
+        if lim is not None:
+            e["limit_db"], e["limit_lookahead_ms"], e["limit_hold_ms"] = lim
         if size is not None:
             e["codebook"] = size
         out.append(e)
@@ -361,7 +395,7 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook,
-                             args.crossfade)
+                             args.crossfade, args.limit, args.limit_lookahead, args.limit_hold)
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -396,10 +430,11 @@ def main(argv=None):
                                 world_pitch=any(s["world_pitch"] for s in sessions), blend=blend_size(sessions),
                                 k_max=converter_k_max(sessions, args.k), auto_pitch=auto,
                                 **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}),
-                                **(dict(crossfade=True) if any("crossfade_ms" in s for s in sessions) else {}))
+                                **(dict(crossfade=True) if any("crossfade_ms" in s for s in sessions) else {}),
+                                **(dict(limiter=True) if any("limit_db" in s for s in sessions) else {}))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
-                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS if g in s})
+                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()

@@ -58,6 +58,13 @@ def build_parser():
     parser.add_argument('-xf', '--crossfade', default=None, type=float, metavar="MS",
                         help="seam crossfade: fade the head of every chunk in from the previous step's continuation over MS "
                              "milliseconds, at most one chunk (default: hard cuts; needs -isr == -osr; this build only)")
+    parser.add_argument('-lim', '--limit', default=None, type=float, metavar="DB",
+                        help="output limiter: no emitted sample exceeds this ceiling in dBFS (<= 0), so the 16-bit edge never wraps; the "
+                             "gain starts to fall --limit-lookahead before a peak (default: no limiter; this build only)")
+    parser.add_argument('--limit-lookahead', default=5.0, type=float, metavar="MS",
+                        help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5)")
+    parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
+                        help="milliseconds the limiter's gain stays down after a peak (default 20)")
     parser.add_argument('-isr', '--input-sr', default=16000, type=int)
     parser.add_argument('-osr', '--output-sr', default=16000, type=int)
     parser.add_argument('-lsr', '--loopback-sr', default=16000, type=int)
@@ -101,7 +108,9 @@ def main(argv=None):
                            k=args.k, alpha=args.alpha, gain=args.gain, input_gain=args.input_gain,
                            world_pitch=bool(args.world_pitch_estimation),   # -wpe: WORLD f0, -f0 not applied (as the reference)
                            **(dict(gate_db=args.threshold, gate_hold=args.gate_hold) if args.threshold is not None else {}),
-                           **(dict(crossfade_ms=args.crossfade) if args.crossfade is not None else {}))
+                           **(dict(crossfade_ms=args.crossfade) if args.crossfade is not None else {}),
+                           **(dict(limit_db=args.limit, limit_lookahead_ms=args.limit_lookahead, limit_hold_ms=args.limit_hold)
+                              if args.limit is not None else {}))
     if not args.no_graph:
         rt.enable_graph()        # the whole per-chunk device pipeline (~150 launches) captured once, replayed per chunk: same samples
     print("streaming: conversion running (Ctrl-C stops)")

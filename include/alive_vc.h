@@ -839,6 +839,46 @@ int alive_gate_apply_rows(float* y, int N, int ld, const int* span_lo, const int
 int alive_seam_rows(float* y, int N, int ld, const int* span_lo, const int* shift, const int* xlen, const unsigned char* emit,
                     const float* g0, const float* g1, float* tail, int ld_tail, int* stored, double* stats, void* stream);
 
+/* Limiter (csrc/limit.hip): a lookahead peak limiter in front of the int16 edge (alive_float_to_pcm16 wraps whatever leaves [-1, 1)).
+ * All pointers are DEVICE pointers; no call allocates, synchronises or reads anything on the host; the grids depend on N and ld alone
+ * (graph-capturable: a captured call serves any settings).  No floating-point atomics; every store is a plain vector store.
+ * With ceiling c (0 < c <= 1), lookahead L >= 1 and hold H >= 0 samples, P = L - 1 + H, for stream index i of the emitted signal y:
+ *     a[j]   = c / fmaxf(|y[j]|, c)                   the required gain: exactly 1.0f where |y[j]| <= c, 1 for a NaN, 0 for an inf
+ *     m[k]   = min a[k - H .. k + L - 1]
+ *     g[i]   = (float)(sum over k = i - L + 1 .. i, ascending, in double from 0.0, of (double)m[k] / (double)L)
+ *     out[i] = fminf(fmaxf(y[i] * g[i], -c), c)       float32, every operation rounded on its own
+ * Every window that enters g[i] contains i: g[i] <= a[i] and |out[i]| <= c whatever the neighbours are.  A NaN or infinite sample comes
+ * out as -c (inf * 0 is a NaN, and fminf(fmaxf(NaN, -c), c) = -c); no other sample becomes non-finite.  Bitwise tools/limit_ref.py.
+ *   alive_limit_rows    streaming, in place, one block per row n of y[N][ld] (the final waves, after alive_seam_rows and
+ *                       alive_gate_apply_rows).  Per row: span_lo, span_len int32 (the emitted span), shift int32 (the ring's advance
+ *                       per tick in samples of y: the session's chunk, NOT the span length), look int32 (L; 0: off), hold int32 (H),
+ *                       ceil float (c), emit bytes; the row's state hist[N][ld_hist] float: the required gains of its last ld_hist
+ *                       emitted samples, the latest last (a new stream starts from 1.0f).  For i in [0, span_len) the past comes from
+ *                       hist, the present is y[n][span_lo + i] and the future, stream index span_len + j, is y[n][span_lo + shift + j],
+ *                       j < L - 1: where the next tick's span will come from.
+ *                         emit[n] == 0: y, hist and gmin[n] untouched;
+ *                         look == 0, a ceiling outside (0, 1], or a row whose regions do not fit (look < 0, hold < 0, span_lo < 0,
+ *                           span_len < 0, span_len > shift, L > shift, span_lo + shift + L - 1 > ld, P > ld_hist): y untouched, hist
+ *                           row = 1.0f, gmin[n] = 1.0f; nothing outside [0, ld) or [0, ld_hist) is ever read or written;
+ *                         else only [span_lo, span_lo + span_len) of y is written, and hist becomes the last ld_hist values of (hist,
+ *                           a[0 .. span_len)).
+ *                       gmin float [N] or NULL: the smallest g of the row's span this tick (1.0f: nothing was reduced).
+ *                       N, ld > 0; 0 < ld_hist <= ALIVE_LIMIT_MAX_HIST.
+ *   alive_limit_waves   offline, stateless, OUT OF PLACE: out[N][ld] from y[N][ld]; row n's first len[n] samples (int32, clamped to
+ *                       [0, ld]) are limited as one signal with a = 1 outside it, the rest of the row is copied; one look / hold for
+ *                       the call, ceil float [N] (a row whose ceiling is outside (0, 1] is copied whole).  The grid is tiles of
+ *                       ALIVE_LIMIT_TILE samples x rows; a tile's halo is another tile's output range, so an `out` that overlaps `y` is
+ *                       refused.  gmin float [N] or NULL: the smallest g of the row (1.0f first, then an integer atomic min on the
+ *                       float's bits: every g is >= +0, so the order of the bits is the order of the values and the result does not
+ *                       depend on the order).  0 < N <= 65535, ld > 0, look >= 1, hold >= 0, look - 1 + hold <= ALIVE_LIMIT_MAX_HIST.
+ *                       Bitwise alive_limit_rows run tick by tick over the same signal. */
+#define ALIVE_LIMIT_TILE 1024
+#define ALIVE_LIMIT_MAX_HIST 3072
+int alive_limit_rows(float* y, int N, int ld, const int* span_lo, const int* span_len, const int* shift, const int* look,
+                     const int* hold, const float* ceil, const unsigned char* emit, float* hist, int ld_hist, float* gmin, void* stream);
+int alive_limit_waves(float* out, const float* y, int N, int ld, const int* len, int look, int hold, const float* ceil, float* gmin,
+                      void* stream);
+
 /* Voice codebooks (csrc/codebook.hip; module/codebook.py build_codebook): the device passes of one k-means iteration over a voice's
  * rows that are not the search.  The assignment of a row is the strict search's top-1 against the centroids (alive_knn_search_strict)
  * and the inverted index a stable sort of the assignment; both are the caller's.  All pointers are DEVICE pointers; no call allocates,

@@ -25,6 +25,11 @@ one more launch of one block per session, alive_seam_rows, csrc/seam.hip), the s
 (crossfade_seam_db_min / _median / _max: 10 log10 of how far two successive decodes disagree over the faded head -- on SYNTHETIC weights
 and synthetic input, so it says nothing about how a trained model sounds), and the converter built without crossfade a second time
 (crossfade_off_again_tick_*): the spread between its two measurements is the yardstick for the crossfade's cost.
+--limit adds the graph tick p50 / p99 of a limiter=True converter with every session limiting at -12 dBFS with the default 5 ms lookahead
+and 20 ms hold (limit_tick_*: one more launch of one block per session, alive_limit_rows, csrc/limit.hip), how far the limiter turned
+the sessions down in its last tick (limit_db_min / _median / _max: 20 log10 of the smallest gain, on SYNTHETIC weights and input), and
+the converter built without the limiter a second time (limit_off_again_tick_*): the spread between its two measurements is the
+yardstick for the limiter's cost.
 --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
 one more 50 000-row voice added between two ticks, once on a default pool (the add re-packs the pool and the next tick
 re-captures) and once on a reserved pool of 65 x 50 000 rows (VoicePool(capacity=...): alive_pool_append into the table in
@@ -36,7 +41,7 @@ python tools/bench_multistream.py --quick).  Prints one JSON line per configurat
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch]
-                                      [--gated 0,0.5,1] [--crossfade] [--out multistream.json]
+                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--out multistream.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
 """
 import argparse
@@ -193,6 +198,8 @@ def main():
                                                   "a -40 dB gate and that fraction of them fed digital silence")
     ap.add_argument("--crossfade", action="store_true", help="also time a crossfade=True converter, every session crossfading over "
                                                              "10 ms, and the plain converter a second time")
+    ap.add_argument("--limit", action="store_true", help="also time a limiter=True converter, every session limiting at -12 dBFS, "
+                                                         "and the plain converter a second time")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
                                                          "default and on a reserved pool")
     ap.add_argument("--out", default=None)
@@ -325,6 +332,25 @@ def main():
                     again.enable_graph()
                     p50, p99 = time_ticks(again, B, chunk, args.ticks, args.warmup + bs + 1, 300)
                     rec["crossfade_off_again_tick_p50_ms"], rec["crossfade_off_again_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                    del again
+                if args.limit:
+                    lc = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, limiter=True)
+                    for s in range(B):
+                        lc.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, limit_db=-12.0)
+                    lc.enable_graph()
+                    p50, p99 = time_ticks(lc, B, chunk, args.ticks, args.warmup + bs + 1, 300)
+                    rec["limit_tick_p50_ms"], rec["limit_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                    db = np.array(lc.limit_db())
+                    assert not np.isnan(db).any() and lc.captures == 1, (db, lc.captures)
+                    rec["limit_db_min"], rec["limit_db_median"], rec["limit_db_max"] = (
+                        round(float(db.min()), 2), round(float(np.median(db)), 2), round(float(db.max()), 2))
+                    del lc
+                    again = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4)
+                    for s in range(B):
+                        again.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5)
+                    again.enable_graph()
+                    p50, p99 = time_ticks(again, B, chunk, args.ticks, args.warmup + bs + 1, 300)
+                    rec["limit_off_again_tick_p50_ms"], rec["limit_off_again_tick_p99_ms"] = round(p50, 3), round(p99, 3)
                     del again
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
