@@ -140,13 +140,13 @@ __global__ __launch_bounds__(256) void resample_rows_multi_kernel(const float* _
 
 __global__ void pcm16_to_float_kernel(const short* __restrict__ in, int64_t n, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (float)in[i] / 32768.0f;
+    if (i < n) out[i] = alive_pcm16_as_float(in[i]);
 }
 
 // numpy's float32 -> int16 astype on the reference's hosts: truncate toward zero to int32, keep the low 16 bits (no clip)
 __global__ void float_to_pcm16_kernel(const float* __restrict__ in, int64_t n, short* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (short)(int)(in[i] * 32768.0f);
+    if (i < n) out[i] = alive_float_as_pcm16(in[i]);
 }
 
 }  // namespace

@@ -149,6 +149,11 @@ __device__ __forceinline__ float lerp_apply(const Lerp& l, float a, float b) {
     return fmaf(l.w0, a, l.w1 * b);
 }
 
+// the int16 edges, one expression each for every kernel that converts (audio.hip's flat forms, ring.hip's per-row forms).
+// float -> int16 is numpy's astype on the reference's hosts: truncate toward zero to int32, keep the low 16 bits (no clip)
+__device__ __forceinline__ float alive_pcm16_as_float(short s) { return (float)s / 32768.0f; }
+__device__ __forceinline__ short alive_float_as_pcm16(float v) { return (short)(int)(v * 32768.0f); }
+
 __device__ __forceinline__ unsigned short f32_to_bf16_rn(float f) {
     unsigned u = __float_as_uint(f);
     if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);  // NaN stays NaN

@@ -100,6 +100,30 @@ Everything is device arrays: toggling and retuning never re-capture, and a conve
 did.  limit_db() reads the latest tick's 20 log10(smallest gain) per slot back (0.0: untouched).  limit_waves is the offline form
 (alive_limit_waves), bitwise the streaming one run tick by tick over the same signal.  The defaults (-1 dBFS when asked for, 5 ms,
 20 ms) are design choices: with no trained weights, how they sound is unmeasured.
+
+Sparse ticks: a dense converter wants a chunk from every open slot on every tick (step raises otherwise) and keeps the rings on the
+host: it uploads every whole ring and downloads every whole wave per tick.  A converter built with sparse=True (csrc/ring.hip) gives
+every session its own clock.  step(chunks) takes the chunks of ANY subset of the open slots; an open slot without one is absent this
+tick and nothing of it moves: its ring and count, phi, reg_state, gate_state, tail and stored, limit_hist and limit_gmin.  It is not a
+key of the result and costs no search (its list rows run at segment length 0, as rows the gate skipped; it is off in WORLD's row mask);
+the encoders and the decoder still run over all B rows, and what they compute for an absent row is discarded.  The contract: a
+session's emitted stream depends only on the sequence of chunks it supplied, bit for bit -- not on the ticks they arrived in, nor on
+what the other sessions did.  An absent tick is a STALL of the session: its latency to the wall clock grows by one tick, no audio is
+lost or repeated (no concealment audio is made up for it; a chunk that was lost and should advance the session's clock is a chunk of
+zeros).  step({}), or a tick on which no present slot emits, does no network work; present filling slots still have their chunk pushed.
+The rings live on the device, int16 [B, ld_in] in time order (ring_dev; `ring` is None, rings() reads them back): the chunks go up
+through one pinned staging buffer [B, longest chunk] in one copy, present and emit in a second small one, and alive_ring_push_rows --
+once per tick, OUTSIDE the captured step and outside what the bf16 repeat runs again, so a repeated tick starts from the input it
+started from and the ring is pushed once -- advances the present rows in place, rewrites their rows of the float input _in (bitwise
+alive_pcm16_to_float of the ring a dense converter would hold) and forms the tick's masked row arrays seg_len_tick / world_tick (seg_len
+/ world_on on present rows, 0 on absent ones; after _follow_pool has brought seg_len up to date), which the tick reads where a dense one
+reads seg_len / world_on -- with a gate they are alive_gate_rows' inputs, whose emit == 0 branch passes the zeros on.  emit[b] is
+"present and past filling", so the kernels that leave a row's state alone at emit == 0 (alive_pitch_follow_rows, alive_gate_rows,
+alive_seam_rows, alive_limit_rows) do so for an absent row, and phi_next keeps phi where emit is 0 (a filling slot's phi is 0 anyway).
+After the step alive_emit_rows cuts the emitting rows' spans (_span of the slot's chunk: 440 of 441 at 44.1 kHz) into one int16
+[B, widest span] array, the only thing copied back.  open and close zero the slot's device ring and its row of _in.  With every session
+present every tick a sparse converter emits what the dense one emits, byte for byte; a converter built without sparse launches exactly
+what it did, `ring`, _in and the ValueError for a missing slot included.
 """
 import numpy as np
 import torch
@@ -990,6 +1014,47 @@ def gate_apply_rows_(y, span_lo, span_len, g0, g1):
     return y
 
 
+def ring_push_rows_(ring, chunks, chunk_len, ring_len, present, x, seg_len=None, seg_len_tick=None, S=1, world_on=None,
+                    world_tick=None):
+    """alive_ring_push_rows in place: the rows with present != 0 have their int16 ring [N, ld] (time order) advanced by their chunk
+    (chunks int16 [N, ld_chunk], chunk_len / ring_len int32 [N]) and their row of x float32 [N, ld_x] rewritten from it; the others
+    are not touched.  seg_len -> seg_len_tick (int32 [N * S]) and world_on -> world_tick (int32 [N]): the tick's masked row arrays,
+    zero on an absent row (each pair both given or both None)"""
+    if ring.dim() != 2 or ring.dtype != torch.int16 or not ring.is_contiguous():
+        raise ValueError("ring_push_rows_: ring must be contiguous int16 [N, ld]")
+    n, ld = ring.shape
+    if chunks.dtype != torch.int16 or chunks.dim() != 2 or chunks.shape[0] != n or not chunks.is_contiguous():
+        raise ValueError("ring_push_rows_: chunks must be contiguous int16 [N, ld_chunk]")
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != n or not x.is_contiguous():
+        raise ValueError("ring_push_rows_: x must be contiguous float32 [N, ld_x]")
+    if present.numel() != n or present.element_size() != 1:
+        raise ValueError("ring_push_rows_: present must be [N] bytes")
+    for name, t, size in (("chunk_len", chunk_len, n), ("ring_len", ring_len, n), ("seg_len", seg_len, n * int(S)),
+                          ("seg_len_tick", seg_len_tick, n * int(S)), ("world_on", world_on, n), ("world_tick", world_tick, n)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != size):
+            raise ValueError(f"ring_push_rows_: {name} must be int32 [{size}]")
+    if (seg_len is None) != (seg_len_tick is None) or (world_on is None) != (world_tick is None):
+        raise ValueError("ring_push_rows_: seg_len / seg_len_tick and world_on / world_tick are given in pairs")
+    nat.check(nat.lib().alive_ring_push_rows(nat.ptr(ring), n, ld, nat.ptr(chunks), chunks.shape[1], nat.ptr(chunk_len),
+                                             nat.ptr(ring_len), nat.ptr(present), nat.ptr(x), x.shape[1], int(S), nat.ptr(seg_len),
+                                             nat.ptr(seg_len_tick), nat.ptr(world_on), nat.ptr(world_tick), nat.stream()),
+              "alive_ring_push_rows")
+    return ring
+
+
+def emit_rows_(wave, span_lo, span_len, take, out):
+    """alive_emit_rows: out int16 [N, ld_out] <- the spans [span_lo, span_lo + span_len) of the taken rows (take: [N] bytes) of wave
+    float32 [N, ld] as alive_float_to_pcm16 forms them, zeros everywhere else"""
+    n, ld = wave.shape
+    if wave.dtype != torch.float32 or not wave.is_contiguous():
+        raise ValueError("emit_rows_: wave must be contiguous float32 [N, ld]")
+    if out.dtype != torch.int16 or out.dim() != 2 or out.shape[0] != n or take.numel() != n or take.element_size() != 1:
+        raise ValueError("emit_rows_: out must be int16 [N, ld_out], take [N] bytes")
+    nat.check(nat.lib().alive_emit_rows(nat.ptr(wave), n, ld, nat.ptr(span_lo), nat.ptr(span_len), nat.ptr(take), nat.ptr(out),
+                                        out.shape[1], nat.stream()), "alive_emit_rows")
+    return out
+
+
 def seam_rows_(y, span_lo, shift, xlen, emit, tail, stored, g0=None, g1=None, stats=None):
     """alive_seam_rows in place on y [N, ld]: every emitting row's head faded from its tail, the tail of the next tick saved.
     tail float32 [N, ld_tail] and stored int32 [N] are the rows' state; g0 / g1: the gate's gains, or both None; stats: float64
@@ -1299,11 +1364,14 @@ class MultiStreamConverter:
     gate = False                       # (likewise: whether the tick carries the two gate kernels)
     crossfade = False                  # (likewise: whether the tick carries the seam kernel)
     limiter = False                    # (likewise: whether the tick carries the limiter kernel)
+    sparse = False                     # (likewise: whether the rings live on the device and sessions may sit ticks out)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
                  auto_pitch_half_life=10.0, auto_pitch_prior=0.5, gate=False, gate_lookahead=None, crossfade=False,
-                 limiter=False, limit_history=0.05):
+                 limiter=False, limit_history=0.05, sparse=False):
+        if not isinstance(sparse, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: sparse must be a bool, got {sparse!r}")
         if not isinstance(limiter, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: limiter must be a bool, got {limiter!r}")
         if limiter:                        # (checked before anything is built)
@@ -1411,7 +1479,8 @@ class MultiStreamConverter:
         self.in_post = torch.ones(B, dtype=torch.float32, device=dev)       # input gain: after the resampler (:146-147)
         self.out_pre = torch.ones(B, dtype=torch.float32, device=dev)       # output gain: before the resampler (:173-175)
         self.out_post = torch.ones(B, dtype=torch.float32, device=dev)
-        self.emit = torch.zeros(B, 1, dtype=torch.bool, device=dev)          # the slots whose phase advances this tick
+        if not sparse:                     # the slots whose phase advances this tick (sparse: a row of the flags array, below)
+            self.emit = torch.zeros(B, 1, dtype=torch.bool, device=dev)
         # world_pitch: the masked WORLD branch is part of the tick (captured once); per row, world_on selects WORLD's f0 and the
         # transform's rate is f0_rate_eff: the session's f0_rate, 1.0 on a WORLD row (its f0_rate stays in its params)
         self.world_pitch = bool(world_pitch)
@@ -1483,6 +1552,33 @@ class MultiStreamConverter:
                 self.span_len = torch.full((B,), ln, **i32)
         self.phi = torch.zeros(B, 64, device=dev)
         self._in = torch.zeros(B, ld_in, device=dev)
+        # sparse: the rings live on the device in time order (ring_dev; `ring` is gone, rings() reads them back), one push per tick
+        # moves the present rows on and writes _in and the tick's masked row arrays, which the tick reads where it read seg_len /
+        # world_on; the emitted spans are cut on the device into _pcm.  present and emit are the two rows of one flags array: one copy
+        self.sparse = bool(sparse)
+        if self.sparse:
+            i32 = dict(dtype=torch.int32, device=dev)
+            cs = [self._chunk_at(r) for r in rates]
+            up8 = lambda v: -(-int(v) // 8) * 8                                       # noqa: E731  (strides of whole 16-byte groups)
+            self.ring = None
+            self.ring_dev = torch.zeros(B, up8(ld_in), dtype=torch.int16, device=dev)
+            self._stage = torch.zeros(B, up8(max(cs)), dtype=torch.int16).pin_memory()
+            self._chunks_dev = torch.zeros(B, up8(max(cs)), dtype=torch.int16, device=dev)
+            self._flags_host = torch.zeros(2, B, dtype=torch.bool).pin_memory()
+            self._flags = torch.zeros(2, B, dtype=torch.bool, device=dev)
+            self.present, self.emit = self._flags[0], self._flags[1].view(B, 1)
+            self._staged = None                            # the event after the latest upload from the two pinned buffers
+            self.chunk_len = torch.full((B,), self.chunk, **i32)
+            self.ring_len = torch.full((B,), self.n, **i32)
+            self.seg_len_tick = torch.zeros(B * self.S, **i32)
+            self.world_tick = torch.zeros(B, **i32) if self.world_pitch else None
+            if not (self.gate or self.crossfade or self.limiter):
+                lo, ln = self._span(self.chunk)
+                self.span_lo = torch.full((B,), lo, **i32)
+                self.span_len = torch.full((B,), ln, **i32)
+            self._pcm = torch.zeros(B, up8(max(self._span(c)[1] for c in cs)), dtype=torch.int16, device=dev)
+            self._pcm_host = torch.zeros(self._pcm.shape, dtype=torch.int16).pin_memory()
+            self.pushes = 0                                # (how many ticks pushed the rings: one per step with a chunk)
         self._graph = None
         self._graph_pool_version = None
         self.captures = 0
@@ -1679,8 +1775,10 @@ class MultiStreamConverter:
         if self._rt is None:
             return
         c = self._chunks[rate]
-        if self.gate or self.crossfade or self.limiter:
+        if self.gate or self.crossfade or self.limiter or self.sparse:
             self.span_lo[slot], self.span_len[slot] = self._span(c)
+        if self.sparse:
+            self.chunk_len[slot], self.ring_len[slot] = c, c * self.buffersize
         if self.crossfade:
             self.shift[slot] = c
         if self.limiter:
@@ -1720,7 +1818,7 @@ class MultiStreamConverter:
         self.params[slot] = p
         self.is_open[slot] = True
         self.count[slot] = 0
-        self.ring[slot] = 0
+        self._zero_ring(slot)
         self.phi[slot] = 0.0
         if self.auto_pitch:
             self.reg_state[slot] = 0.0                        # a new source: nothing heard yet
@@ -1757,7 +1855,7 @@ class MultiStreamConverter:
         self.is_open[slot] = False
         self.params[slot] = None
         self.count[slot] = 0
-        self.ring[slot] = 0
+        self._zero_ring(slot)
         self.seg_len[slot * self.S:(slot + 1) * self.S] = 0
         if self.k_max is not None:                           # (the slot stays inactive: its segments are empty)
             self.k_rows[slot] = self.k
@@ -1786,6 +1884,19 @@ class MultiStreamConverter:
             self._limit_reset(slot)
         self._set_rate(slot, int(self.input_sr))             # a closed slot: the converter's own rate, silence
         return self
+
+    def _zero_ring(self, slot):
+        if self.sparse:                                       # the device ring and the slot's row of the float input
+            self.ring_dev[slot] = 0
+            self._in[slot] = 0.0
+        else:
+            self.ring[slot] = 0
+
+    def rings(self):
+        """a sparse converter's rings, int16 [B, ld_in] in time order (what `ring` holds in a dense one).  One host read"""
+        if not self.sparse:
+            raise ValueError("rings needs a converter built with MultiStreamConverter(..., sparse=True): a dense one has `ring`")
+        return self.ring_dev[:, :self.ld_in].cpu().numpy()
 
     def gate_open(self):
         """the per-slot open flags after the latest tick, a list of B bools: a gated session's gate (False before its first emitting
@@ -1821,7 +1932,8 @@ class MultiStreamConverter:
             f0 = self.pe.estimate(spec, out=buf)
             rate = self.f0_rate
             if self.world_pitch:
-                buf.copy_(torch.where(self._world_sel, compute_f0_rows(data, self.world_eff if self.gate else self.world_on), buf))
+                world_on = self.world_eff if self.gate else (self.world_tick if self.sparse else self.world_on)
+                buf.copy_(torch.where(self._world_sel, compute_f0_rows(data, world_on), buf))
                 f0, rate = buf, self.f0_rate_eff
             shift = self.pitch
             if self.auto_pitch:                               # the sessions' running registers -> this tick's shifts
@@ -1838,11 +1950,13 @@ class MultiStreamConverter:
         else:
             data = resample_rows_multi(data, self.len_in, self.pair_in, self._rt, self._len16_rows, self._len16, self.in_pre,
                                        self.in_post)
-        seg_len = self.seg_len
+        # (sparse: the push's masked arrays, zero on the rows that sent nothing this tick, stand in for seg_len / world_on)
+        seg_len = self.seg_len_tick if self.sparse else self.seg_len
         if self.gate:                                         # this tick's live rows, before the f0 side stream forks off
             w_lo, w_hi = gate_window(self.begin_of_output, self.end_of_output, data.shape[1], self._gate_look16)
+            world_on = (self.world_tick if self.sparse else self.world_on) if self.world_pitch else None
             gate_rows(data, w_lo, w_hi, self.gate_on, self.thr_ms, self.hold_ticks, self.emit,
-                      self.world_on if self.world_pitch else None, self.S, self.seg_len, self.gate_state, self.g0, self.g1,
+                      world_on, self.S, seg_len, self.gate_state, self.g0, self.g1,
                       self.seg_len_eff, self.follow, self.world_eff)
             seg_len = self.seg_len_eff
         spec = spectrogram(data)
@@ -1888,7 +2002,9 @@ class MultiStreamConverter:
                 raise RuntimeError(f"final wave of {wave.shape[1]} samples, the limiter expects {max(self._limit_len.values())}")
             limit_rows_(wave, self.span_lo, self.span_len, self.limit_shift, self.look, self.hold, self.ceil, self.emit,
                         self.limit_hist, self.limit_gmin)
-        phi_next = torch.where(self.emit, phi_out[:, :, self.end_of_output], torch.zeros_like(phi))
+        # a row that does not emit: 0 -- a filling slot's phase is 0 anyway -- and in a sparse converter its own phase, which is that
+        # same 0 while it fills and stands still on a tick it sat out
+        phi_next = torch.where(self.emit, phi_out[:, :, self.end_of_output], phi if self.sparse else torch.zeros_like(phi))
         return wave, phi_next
 
     def enable_graph(self):
@@ -1940,6 +2056,11 @@ class MultiStreamConverter:
     def _repeat_on_bf16(self, saved_phi, saved_reg=None, saved_gate=None, saved_seam=None):
         """RealtimeConverter._repeat_on_bf16 for the whole tick: modes 2, every slot's phase (and running register, gate state and
         crossfade tail) restored, the tick again"""
+        return audio_io.float_to_pcm16(self._repeat_wave(saved_phi, saved_reg, saved_gate, saved_seam)).cpu().numpy()
+
+    def _repeat_wave(self, saved_phi, saved_reg=None, saved_gate=None, saved_seam=None):
+        """the repeated tick's waves on the device.  The tick reads _in, which the repeat leaves as it is: a sparse converter's rings
+        were pushed before the first attempt and are not pushed again"""
         ops.switch_to_bf16("multi-session streaming step", "tick")
         self.phi.copy_(saved_phi)
         if saved_reg is not None:
@@ -1949,13 +2070,79 @@ class MultiStreamConverter:
         self._seam_restore(saved_seam)
         if self._graph is not None:
             self.enable_graph()
-        return audio_io.float_to_pcm16(self._run()).cpu().numpy()
+        return self._run()
+
+    def _chunk_of(self, s, c):
+        """a slot's chunk as a flat int16 array of the slot's chunk length (ValueError otherwise)"""
+        c = np.asarray(c, dtype=np.int16).reshape(-1)
+        cs = self.slot_chunk[s]
+        if c.shape[0] != cs:
+            raise ValueError(f"slot {s}: chunk of {c.shape[0]} samples, expected {cs} (the session runs at {self.rate[s]} Hz)")
+        return c
+
+    def _emit_spans(self, wave):
+        """the emitting rows' spans of the tick's waves as int16, cut on the device: one [B, widest span] copy to the host"""
+        emit_rows_(wave, self.span_lo, self.span_len, self.emit, self._pcm)
+        self._pcm_host.copy_(self._pcm, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return self._pcm_host.numpy()
+
+    def _step_sparse(self, chunks):
+        """step() of a sparse converter: any subset of the open slots"""
+        taken = {}
+        for s, c in chunks.items():
+            self._slot(s)
+            if not self.is_open[s]:
+                raise ValueError(f"a chunk for slot {s}, which is not open")
+            taken[int(s)] = self._chunk_of(s, c)
+        out = {s: None for s in chunks}
+        if not taken:                                         # nobody sent anything: nothing moves
+            return out
+        if self._staged is not None:
+            self._staged.synchronize()                        # (the pinned buffers are free again: the latest upload has been made)
+        stage, flags = self._stage.numpy(), self._flags_host.numpy()
+        flags[:] = False
+        for s, c in taken.items():
+            stage[s, :c.shape[0]] = c
+            self.count[s] += 1
+            flags[0, s] = True
+            flags[1, s] = self.count[s] > self.buffersize
+        emit = flags[1].copy()
+        if self._reserved:
+            self._follow_pool()                               # seg_len as the pool lies now, before the push masks it
+        self._chunks_dev.copy_(self._stage, non_blocking=True)
+        self._flags.copy_(self._flags_host, non_blocking=True)
+        self._staged = torch.cuda.Event()
+        self._staged.record(torch.cuda.current_stream(self.device))
+        # once per tick, outside the captured step and outside what the bf16 repeat runs again
+        ring_push_rows_(self.ring_dev, self._chunks_dev, self.chunk_len, self.ring_len, self.present, self._in, self.seg_len,
+                        self.seg_len_tick, self.S, self.world_on if self.world_pitch else None, self.world_tick)
+        self.pushes += 1
+        if not emit.any():                                    # the present rings moved on; no network work
+            return out
+        guarded = fp16_guarded(self.B * self.frames)
+        if guarded:
+            saved_phi = self.phi.clone()
+            saved_reg = self.reg_state.clone() if self.auto_pitch else None
+            saved_gate = self.gate_state.clone() if self.gate else None
+            saved_seam = self._seam_state()
+        o = self._emit_spans(self._run())
+        if guarded and ops.f16_saturations(reset=True) > 0:
+            o = self._emit_spans(self._repeat_wave(saved_phi, saved_reg, saved_gate, saved_seam))
+        for s in taken:
+            if emit[s]:
+                out[s] = o[s, :2 * (self.slot_chunk[s] // 2)].copy()
+        return out
 
     def step(self, chunks):
         """{slot: int16 chunk} for EVERY open slot -> {slot: converted centre chunk (int16) or None while its ring fills}.
         A session at rate r sends and receives chunks of chunk_r = chunk * r / input_sr samples; its output is cut at its own
         centre, buffersize * chunk_r // 2 +- chunk_r // 2 (realtime_inference.py at that rate), so an odd chunk_r (441 at 44.1 kHz
-        with 160-sample chunks at 16 kHz) returns chunk_r - 1 samples per tick, as the reference does."""
+        with 160-sample chunks at 16 kHz) returns chunk_r - 1 samples per tick, as the reference does.
+        A sparse converter takes the chunks of ANY subset of its open slots: a slot without one sits the tick out (nothing of it
+        moves, it is not a key of the result), see "Sparse ticks" in the module docstring."""
+        if self.sparse:
+            return self._step_sparse(chunks)
         for s in chunks:
             self._slot(s)
             if not self.is_open[s]:
@@ -1965,10 +2152,8 @@ class MultiStreamConverter:
             raise ValueError(f"open slots {missing} supplied no chunk this tick")
         emit = [False] * self.B
         for s, c in chunks.items():
-            c = np.asarray(c, dtype=np.int16).reshape(-1)
+            c = self._chunk_of(s, c)
             cs = self.slot_chunk[s]
-            if c.shape[0] != cs:
-                raise ValueError(f"slot {s}: chunk of {c.shape[0]} samples, expected {cs} (the session runs at {self.rate[s]} Hz)")
             n = cs * self.buffersize
             self.ring[s, :n - cs] = self.ring[s, cs:n]
             self.ring[s, n - cs:n] = c

@@ -29,6 +29,9 @@ The sessions file is a JSON list; each entry:
    "blend": [{"target": "a.wav", "weight": 2}, {"lib": "b.pt", "weight": 1}],   instead of "target" / "lib": a weighted mix
                                           of 1 to 4 voices, each component a voice source as above (multistream.blend_spec)
    "start": 0,                            optional: the tick at which the session joins
+   "stall": [12, 13, 40],                 optional, a list of distinct integers >= 0: ticks, counted from tick 0 of the run, at which
+                                          the session supplies nothing (a late client; module/multistream.py "Sparse ticks").  Its
+                                          remaining input moves later by one tick per stall, and its slot closes after its last chunk
    "sr": 48000,                           optional: the session's sample rate (default -isr / -osr)
    "output": "a_out.wav"}                 optional: default <outdir>/<index>_<input name>.wav
 A session's slot opens at its start tick, gets one chunk per tick while its input lasts and closes after its last chunk.
@@ -53,6 +56,10 @@ as before.  The size is part of the voice's pool name: sessions on the same sour
 components are each condensed to the session's size.
 WORLD needs rings of about 230 ms or more (-c 960 -b 8 is 480 ms): a shorter ring comes out unvoiced.
 Flags shared with realtime_inference.py keep its spelling: -c, -b, -k, -isr, -osr, --no-graph.
+
+The converter is built sparse (rings on the device, sessions may sit ticks out) only under --sparse or if some session has a
+"stall": a file without the key, run without the flag, runs as before.  A stalled session's output is byte for byte what it is
+without the stalls, and --sparse alone writes byte for byte what a run without it writes.
 
 --pool-rows N: a RESERVED pool of N rows (module/multistream.py VoicePool(capacity=N)) instead of one packed before tick 0: each
 voice is enrolled from its sources at the first tick some session needs it (multistream.enrol_voice, while the other sessions
@@ -86,6 +93,7 @@ GATE_KEYS = ("gate_db", "gate_hold")     # taken per session too; a loaded sessi
 SEAM_KEYS = ("crossfade_ms",)            # taken per session too; a loaded session carries it only when it crossfades
 LIMIT_KEYS = ("limit_db", "limit_lookahead_ms", "limit_hold_ms")      # likewise; a loaded session carries them only when it limits
 CODEBOOK_KEYS = ("codebook",)            # taken per session too; a loaded session carries it only when its voice is condensed
+STALL_KEYS = ("stall",)                  # a loaded session carries it only when its entry has the key (the converter is then sparse)
 
 
 def build_parser():
@@ -125,6 +133,9 @@ def build_parser():
     parser.add_argument('--codebook', default=None, type=int, metavar="SIZE",
                         help="condense every session's voice to SIZE centroid rows by k-means unless its \"codebook\" says otherwise "
                              "(default: the voices as they are)")
+    parser.add_argument('--sparse', action='store_true',
+                        help="build the converter sparse: the rings live on the device and a session may sit ticks out (implied by a "
+                             "session's \"stall\")")
     parser.add_argument('--no-graph', action='store_true',
                         help="launch the per-tick device pipeline kernel by kernel instead of replaying one captured hipGraph")
     return parser
@@ -199,14 +210,38 @@ def session_codebook(s, where, codebook=None):
     return size
 
 
+def session_stall(s, where):
+    """an entry's "stall" -> the sorted tuple of its ticks, or None for a session without the key (a JSON null counts as none): a list
+    of distinct integers >= 0 (no bools, no floats); ValueError otherwise.  Host only"""
+    stall = s.get("stall")
+    if stall is None:
+        return None
+    if not isinstance(stall, list) or any(isinstance(t, bool) or not isinstance(t, int) or t < 0 for t in stall):
+        raise ValueError(f"{where}: \"stall\" must be a list of distinct integers >= 0 (ticks of the run), got {stall!r}")
+    if len(set(stall)) != len(stall):
+        raise ValueError(f"{where}: \"stall\" names a tick twice: {stall!r}")
+    return tuple(sorted(stall))
+
+
+def supply_ticks(start, n_chunks, stall=None):
+    """the ticks at which a session that joins at tick `start` supplies its n_chunks chunks, in order: every tick from `start` on
+    that is not one of its `stall` ticks (without stalls: start .. start + n_chunks - 1).  Host only"""
+    stall, out, tick = set(stall or ()), [], int(start)
+    while len(out) < n_chunks:
+        if tick not in stall:
+            out.append(tick)
+        tick += 1
+    return out
+
+
 def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None, crossfade_ms=None, limit_db=None,
                   limit_lookahead_ms=5.0, limit_hold_ms=20.0):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
     condensed, "crossfade_ms" (default `crossfade_ms`) only on a session that crossfades, and "limit_db" / "limit_lookahead_ms" /
-    "limit_hold_ms" (defaults `limit_db`, `limit_lookahead_ms`, `limit_hold_ms`) only on a session that limits; ValueError on a
-    malformed entry"""
+    "limit_hold_ms" (defaults `limit_db`, `limit_lookahead_ms`, `limit_hold_ms`) only on a session that limits, and "stall" (a sorted
+    tuple of ticks) only on a session whose entry has the key; ValueError on a malformed entry"""
     k = check_k(k, "-k")
     session_codebook({}, "--codebook", codebook)
     session_gate({}, "-thr / --gate-hold", gate_db, gate_hold)
@@ -221,10 +256,10 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     for i, s in enumerate(sessions):
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
-        unknown = set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(CODEBOOK_KEYS)
+        unknown = set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(CODEBOOK_KEYS) - set(STALL_KEYS)
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + CODEBOOK_KEYS})")
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + CODEBOOK_KEYS + STALL_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
@@ -238,6 +273,7 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
         if not isinstance(s.get("auto_pitch", False), bool):
             raise ValueError(f"session {i}: \"auto_pitch\" must be true or false, got {s['auto_pitch']!r}")
         sess_k = check_k(s["k"], f"session {i}: \"k\"") if "k" in s else k
+        stall = session_stall(s, f"session {i}")
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
                  gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
@@ -255,6 +291,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             e["limit_db"], e["limit_lookahead_ms"], e["limit_hold_ms"] = lim
         if size is not None:
             e["codebook"] = size
+        if stall is not None:
+            e["stall"] = stall
         out.append(e)
     return out
 
@@ -361,15 +399,21 @@ def input_pcm(path, input_sr, device):
     return (wf.numpy() * 32767).astype(np.int16)
 
 
-def run(conv, pcms, starts, chunk, params, before=None, after=None):
+def run(conv, pcms, starts, chunk, params, before=None, after=None, stalls=None):
     """drive `conv` tick by tick: session i occupies slot i (opened with params[i]) from tick starts[i] for len(pcms[i]) // chunk
     ticks; `chunk` is one length for every session or a list of per-session lengths (sessions at their own rates).
     before(tick) runs ahead of the tick's opens and after(tick) behind its closes (--pool-rows: enrolments and removals).
+    stalls (a sparse converter): per session the ticks at which it supplies nothing, or None; it then supplies its chunks at
+    supply_ticks(start, chunks, stall) and its slot closes after the last of them.
     Returns the emitted int16 chunks of every session, concatenated."""
     chunks = list(chunk) if isinstance(chunk, (list, tuple)) else [chunk] * len(pcms)
     n_chunks = [len(p) // c for p, c in zip(pcms, chunks)]
     outs = [[] for _ in pcms]
-    last = max(s + n for s, n in zip(starts, n_chunks))
+    supply = [{t: j for j, t in enumerate(supply_ticks(s, n, st))}
+              for s, n, st in zip(starts, n_chunks, stalls or [None] * len(pcms))]
+    # a session's last tick; one without a single chunk never opens and counts as before: up to its start, "closed" the tick before
+    ends = [max(sup) if sup else s - 1 for sup, s in zip(supply, starts)]
+    last = max(e + 1 for e in ends)
     for tick in range(last):
         if before is not None:
             before(tick)
@@ -377,15 +421,15 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None):
         for i, (s, n) in enumerate(zip(starts, n_chunks)):
             if tick == s and n > 0:
                 conv.open(i, **params[i])
-            if s <= tick < s + n:
-                j, c = tick - s, chunks[i]
+            if tick in supply[i]:
+                j, c = supply[i][tick], chunks[i]
                 feed[i] = pcms[i][j * c:(j + 1) * c]
         res = conv.step(feed)
         for i, o in res.items():
             if o is not None:
                 outs[i].append(o)
-        for i, (s, n) in enumerate(zip(starts, n_chunks)):
-            if tick == s + n - 1:
+        for i, e in enumerate(ends):
+            if tick == e:
                 conv.close(i)
         if after is not None:
             after(tick)
@@ -431,7 +475,8 @@ def main(argv=None):
                                 k_max=converter_k_max(sessions, args.k), auto_pitch=auto,
                                 **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}),
                                 **(dict(crossfade=True) if any("crossfade_ms" in s for s in sessions) else {}),
-                                **(dict(limiter=True) if any("limit_db" in s for s in sessions) else {}))
+                                **(dict(limiter=True) if any("limit_db" in s for s in sessions) else {}),
+                                **(dict(sparse=True) if args.sparse or any("stall" in s for s in sessions) else {}))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
                    **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS if g in s})
@@ -444,6 +489,8 @@ def main(argv=None):
     if args.pool_rows is not None:
         # the reserved pool: a tick's first sessions on a voice enrol it ahead of their open, its last one's close removes it
         n_ticks = [len(p) // c for p, c in zip(pcms, chunks)]
+        # (a stalled session occupies its slot, and holds its voices, until its last chunk: its stalls lengthen its life)
+        n_ticks = [supply_ticks(s["start"], n, s.get("stall"))[-1] - s["start"] + 1 if n else 0 for s, n in zip(sessions, n_ticks)]
         sources = {voice_name(t, lb, s.get("codebook")): (t, lb, s.get("codebook")) for s in sessions for t, lb in session_sources(s)}
         events, _ = enrol_plan([dict(start=s["start"], ticks=n,
                                      voices={voice_name(t, lb, s.get("codebook")): 1 for t, lb in session_sources(s)})
@@ -460,7 +507,9 @@ def main(argv=None):
         def after(tick):
             for name in [n for t, what, n in events if t == tick and what == "remove"]:
                 pool.remove(name)
-    outs = run(conv, pcms, [s["start"] for s in sessions], chunks, params, before, after)
+    stalls = [s.get("stall") for s in sessions]
+    outs = run(conv, pcms, [s["start"] for s in sessions], chunks, params, before, after,
+               **(dict(stalls=stalls) if any(st is not None for st in stalls) else {}))
     os.makedirs(args.output_dir, exist_ok=True)
     for i, (s, o, r) in enumerate(zip(sessions, outs, out_sr)):
         path = s["output"] or os.path.join(args.output_dir, f"{i}_{os.path.splitext(os.path.basename(s['input']))[0]}.wav")

@@ -879,6 +879,32 @@ int alive_limit_rows(float* y, int N, int ld, const int* span_lo, const int* spa
 int alive_limit_waves(float* out, const float* y, int N, int ld, const int* len, int look, int hold, const float* ceil, float* gmin,
                       void* stream);
 
+/* The device edge of a sparse multi-session converter (csrc/ring.hip): the sessions' int16 rings kept on the device, and the emitted
+ * spans cut there.  All pointers are DEVICE pointers; no call allocates, synchronises or reads anything on the host; the grids depend
+ * on N and the strides alone (graph-capturable: a captured call serves any lengths and masks).  No atomics.
+ *   alive_ring_push_rows   one block per row n.  ring int16 [N][ld] holds each row's last ring_len[n] samples in TIME ORDER; chunks int16
+ *                          [N][ld_chunk] holds this tick's chunk_len[n] new samples of the rows with present[n] != 0 (bytes).  Such a
+ *                          row's ring becomes ring[n][cl:rl] ++ chunks[n][0:cl], advanced in place (tile by tile, every tile read
+ *                          before it is written), and x[n][j] = (float)ring[n][j] / 32768.0f for j < rl -- bitwise
+ *                          alive_pcm16_to_float of the new ring -- with x[n][rl:ld_x] = 0.0f.  A row with present[n] == 0, or whose
+ *                          lengths do not fit (cl < 0, cl > rl, cl > ld_chunk, rl > ld, rl > ld_x), is ABSENT: its ring and its row of x
+ *                          are neither read nor written.  The same launch writes the tick's masked row arrays: seg_len_tick[n*S + s]
+ *                          = seg_len[n*S + s] on a row that takes part and 0 on an absent one (int32 [N*S]; both NULL or neither), and
+ *                          world_tick[n] from world_on[n] likewise (int32 [N]; both NULL or neither).  16-byte accesses on rows whose
+ *                          cl and rl are multiples of 8 when ring, chunks and x are 16-byte aligned and ld, ld_chunk and ld_x multiples
+ *                          of 8; scalar ones otherwise, with the same result.  N, ld, ld_chunk, ld_x, S > 0, N * S < 2^31.
+ *   alive_emit_rows        out[n][i] = (short)(int)(wave[n][span_lo[n] + i] * 32768.0f) for i < span_len[n] on the rows with take[n]
+ *                          != 0 (bytes) -- bitwise alive_float_to_pcm16 of those samples; the rest of every row of out int16
+ *                          [N][ld_out], and every row not taken, is 0.  The spans are device data the host does not read: a row whose
+ *                          span does not fit (span_lo < 0, span_len < 0, span_lo + span_len > ld, span_len > ld_out) is written as
+ *                          zeros, and nothing outside [0, ld) or [0, ld_out) is ever read or written.  wave float [N][ld].
+ *                          0 < N <= 65535, ld > 0, 0 < ld_out < 2^30. */
+int alive_ring_push_rows(int16_t* ring, int N, int ld, const int16_t* chunks, int ld_chunk, const int* chunk_len, const int* ring_len,
+                         const unsigned char* present, float* x, int ld_x, int S, const int* seg_len, int* seg_len_tick,
+                         const int* world_on, int* world_tick, void* stream);
+int alive_emit_rows(const float* wave, int N, int ld, const int* span_lo, const int* span_len, const unsigned char* take, int16_t* out,
+                    int ld_out, void* stream);
+
 /* Voice codebooks (csrc/codebook.hip; module/codebook.py build_codebook): the device passes of one k-means iteration over a voice's
  * rows that are not the search.  The assignment of a row is the strict search's top-1 against the centroids (alive_knn_search_strict)
  * and the inverted index a stable sort of the assignment; both are the caller's.  All pointers are DEVICE pointers; no call allocates,

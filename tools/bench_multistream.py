@@ -38,11 +38,19 @@ the tick that follows and the p50 / p99 of the 30 steady ticks before it.  On th
 captured once, that the row table did not move and that nothing of table size was allocated, and adds the worst compaction: the
 lowest voice is removed and `compact` slides the other 64 down by one voice (compact_wall_ms, tick_after_compact_ms).  Profile in a separate run (rocprofv3 --kernel-trace --stats --
 python tools/bench_multistream.py --quick).  Prints one JSON line per configuration and writes the list to --out.
+--sparse runs the sparse-ticks leg ALONE (MultiStreamConverter(sparse=True): the rings on the device, csrc/ring.hip), graph mode, k = 4.
+All present: B = 128 and B = 1024 sessions on one shared 50 000-row voice at -c 160 -b 16 (16 kHz sessions) and at -c 960 -b 8 with 48 kHz
+sessions, the dense and the sparse converter ALTERNATED in one process, two runs each (dense_tick_* / sparse_tick_* lists: the spread
+between the two runs of one side is the yardstick for the difference between the sides), and beside them the bytes each converter
+copies per tick in each direction, computed from its shapes.  Half absent: B = 64 distinct voices at -c 160 -b 16, the sparse converter
+with every session present against sessions present on alternate ticks (even slots on even ticks, odd on odd): the tick, and the
+grouped search alone, event-timed, over the segment lengths that tick left in seg_len_tick.
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch]
                                       [--gated 0,0.5,1] [--crossfade] [--limit] [--out multistream.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
+    python tools/bench_multistream.py --sparse [--batches 128,1024] [--ticks 40] [--out profiles/multistream_sparse_bench.json]
 """
 import argparse
 import json
@@ -70,13 +78,14 @@ def make_pool(n_voices, seed=0):
     return MS.VoicePool({f"v{i}": torch.randn(768, VOICE_ROWS, device="cuda", generator=g) for i in range(n_voices)})
 
 
-def time_ticks(conv, B, chunk, ticks, warmup, seed, silent=0):
-    """chunk: one length, or a list of per-slot lengths (sessions at their own rates); sessions s < silent send digital silence"""
+def time_ticks(conv, B, chunk, ticks, warmup, seed, silent=0, present=None):
+    """chunk: one length, or a list of per-slot lengths (sessions at their own rates); sessions s < silent send digital silence;
+    present(t, s) (a sparse converter): whether session s sends a chunk on tick t (default: every session, every tick)"""
     cs = list(chunk) if isinstance(chunk, (list, tuple)) else [chunk] * B
     pcm = [(synthetic.make_waveform(cs[s] * 4, seed + s)[0].numpy() * (0 if s < silent else 12000)).astype(np.int16) for s in range(B)]
     ts = []
     for t in range(warmup + ticks):
-        feed = {s: pcm[s][(t % 4) * cs[s]:(t % 4 + 1) * cs[s]] for s in range(B)}
+        feed = {s: pcm[s][(t % 4) * cs[s]:(t % 4 + 1) * cs[s]] for s in range(B) if present is None or present(t, s)}
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         conv.step(feed)
@@ -163,6 +172,60 @@ def enrol_leg(nets, B=64, chunk=160, bs=16, steady=30, warmup=6):
     return recs
 
 
+def sparse_leg(nets, batches=(128, 1024), ticks=40, warmup=6):
+    """dense against sparse with every session present, alternated, two runs each; then half the sessions absent: one record per
+    configuration"""
+    recs = []
+    shared = make_pool(1, 1)
+    for chunk, bs, rate in ((160, 16, 16000), (960, 8, 48000)):
+        for B in batches:
+            rec = {"leg": "all_present", "chunk": chunk, "buffersize": bs, "session_rate": rate, "B": B, "voices": "shared",
+                   "voice_rows": VOICE_ROWS, "chunk_period_ms": chunk / 16.0, "dense_tick_p50_ms": [], "dense_tick_p99_ms": [],
+                   "sparse_tick_p50_ms": [], "sparse_tick_p99_ms": []}
+            for run in range(2):
+                for side in ("dense", "sparse"):
+                    conv = MS.MultiStreamConverter(*nets, shared, B, chunk=chunk, buffersize=bs, k=4, rates=[rate],
+                                                   sparse=side == "sparse")
+                    for s in range(B):
+                        conv.open(s, "v0", pitch=float(s % 5), f0_rate=0.5, rate=rate)
+                    conv.enable_graph()
+                    p50, p99 = time_ticks(conv, B, conv.slot_chunk, ticks, warmup + bs + 1, 300)
+                    rec[f"{side}_tick_p50_ms"].append(round(p50, 3))
+                    rec[f"{side}_tick_p99_ms"].append(round(p99, 3))
+                    assert conv.captures == 1, conv.captures
+                    if run == 0:                           # what the tick copies, from the converter's own shapes
+                        wave = conv._wave_len(rate)
+                        up = conv._chunks_dev.numel() * 2 + conv._flags.numel() if conv.sparse else B * conv.ld_in * 2 + B
+                        down = conv._pcm.numel() * 2 if conv.sparse else B * wave * 2
+                        rec[f"{side}_bytes_up_per_tick"], rec[f"{side}_bytes_down_per_tick"] = int(up), int(down)
+                    del conv
+                    torch.cuda.empty_cache()
+            rec["bytes_the_sessions_sent_per_tick"] = B * chunk * rate // 16000 * 2
+            print(json.dumps(rec), flush=True)
+            recs.append(rec)
+    del shared
+    torch.cuda.empty_cache()
+    B, chunk, bs = 64, 160, 16
+    pool = make_pool(B, 2)
+    rec = {"leg": "half_absent", "chunk": chunk, "buffersize": bs, "B": B, "voices": "distinct", "voice_rows": VOICE_ROWS}
+    for name, present, fill in (("all_present", None, bs + 1), ("alternating", lambda t, s: (t + s) % 2 == 0, 2 * (bs + 1))):
+        conv = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, sparse=True)
+        for s in range(B):
+            conv.open(s, f"v{s}", pitch=float(s % 5), f0_rate=0.5)
+        conv.enable_graph()
+        p50, p99 = time_ticks(conv, B, chunk, ticks, warmup + fill, 300, present=present)
+        live = int((conv.seg_len_tick > 0).sum())
+        assert live == (B if present is None else B // 2) and conv.captures == 1, (live, conv.captures)
+        ms, nbytes = time_search(conv, B, seg_len=conv.seg_len_tick)
+        rec.update({f"{name}_tick_p50_ms": round(p50, 3), f"{name}_tick_p99_ms": round(p99, 3), f"{name}_live_rows": live,
+                    f"{name}_search_ms": round(ms, 4), f"{name}_search_bytes": nbytes})
+        del conv
+        torch.cuda.empty_cache()
+    print(json.dumps(rec), flush=True)
+    recs.append(rec)
+    return recs
+
+
 def time_search(conv, B, reps=20, seg_len=None):
     """the grouped search alone on the tick's shape: (ms per call, bytes of distinct segments read once).  seg_len: the segment
     lengths to search with (default: the converter's; a gated converter's seg_len_eff has its closed rows at 0)"""
@@ -182,7 +245,7 @@ def time_search(conv, B, reps=20, seg_len=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="1,8,32,64,128")
+    ap.add_argument("--batches", default=None, help="comma-separated batch sizes (default 1,8,32,64,128; with --sparse 128,1024)")
     ap.add_argument("--configs", default="160x16,960x8")
     ap.add_argument("--ticks", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=6)
@@ -202,9 +265,11 @@ def main():
                                                          "and the plain converter a second time")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
                                                          "default and on a reserved pool")
+    ap.add_argument("--sparse", action="store_true", help="the sparse-ticks leg alone: dense against sparse(=True) converters, "
+                                                          "alternated, and half the sessions absent")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    batches = [int(b) for b in args.batches.split(",")]
+    batches = [int(b) for b in (args.batches or ("128,1024" if args.sparse else "1,8,32,64,128")).split(",")]
     configs = [tuple(int(v) for v in c.split("x")) for c in args.configs.split(",")]
     rates = [int(r) for r in args.rates.split(",")] if args.rates else None
     mixes = tuple(args.voices.split(","))
@@ -213,6 +278,12 @@ def main():
     if args.quick:
         batches, configs, mixes = [64], [(160, 16)], ("distinct",)
     nets = (ContentEncoder(seed=2), F0Estimator(seed=2), Decoder(seed=2))
+    if args.sparse:
+        rows = sparse_leg(nets, batches, args.ticks, args.warmup)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(rows, open(args.out, "w"), indent=1)
+        return
     if args.enrol:
         rows = enrol_leg(nets)
         if args.out:
