@@ -140,6 +140,22 @@ def gemm_planes(P, n, t, weight, bias=None, planes=2, act=None, post_add=None, c
     return Y, Po
 
 
+def gemm_planes_raw(P, n, t, ci, co, W, bias=None, planes=2, act=None, post_add=None, ch_scale=None, residual=None,
+                    Y=None, Pout=None, Y2=None, y_split=0, b_plane=0, b_win=0, b_row=0, b_cblk=0, b_blk=0):
+    """alive_gemm_planes on caller-owned memory (tests): P is a raw operand buffer read through the placement fields (AliveGemm.b_plane /
+    b_win / b_row / b_cblk / b_blk; all 0: the standard k-blocked image of to_planes), W an already packed weight (pack_conv_split, or
+    slab 2 of pack_conv_split_h for planes = 1), Y / Y2 / Pout the tensors to write into.  act: a name of ACT, or the integer of
+    AliveGemm.act (4: magnitudes of row pairs into Pout)."""
+    b, post_add, ch_scale, residual = map(_f, (bias, post_add, ch_scale, residual))
+    d = nat.AliveGemm()
+    d.W, d.bias, d.P = nat.ptr(W), nat.ptr(b), nat.ptr(P)
+    d.N, d.T, d.Ci, d.Co, d.planes, d.act = n, t, ci, co, planes, act if isinstance(act, int) else ACT[act]
+    d.post_add, d.ch_scale, d.residual = map(nat.ptr, (post_add, ch_scale, residual))
+    d.Y, d.Pout, d.Y2, d.y_split = nat.ptr(Y), nat.ptr(Pout), nat.ptr(Y2), y_split
+    d.b_plane, d.b_win, d.b_row, d.b_cblk, d.b_blk = b_plane, b_win, b_row, b_cblk, b_blk
+    nat.check(nat.lib().alive_gemm_planes(C.byref(d), nat.stream()), "alive_gemm_planes")
+
+
 def gemm_planes_argmax(P, n, t, weight, bias=None, planes=3):
     """argmax over the output channels of a 1x1 conv without storing its output (AliveGemm.act = 3 + alive_argmax_merge):
     float indices [n, 1, t] like F0Estimator.estimate."""

@@ -220,10 +220,16 @@ def test_pitch_transform(mode):
     torch.testing.assert_close(got.cpu(), ref, rtol=3e-6, atol=1e-5)
 
 
-@pytest.mark.parametrize("L", [1600, 2560, 144000])
-def test_spectrogram(L):
+@pytest.mark.parametrize("N,L", [
+    pytest.param(2, 1600, id="1600"), pytest.param(2, 2560, id="2560"), pytest.param(2, 144000, id="144000"),
+    (48, 648),        # 96 columns: exactly the batch-path threshold; T = 2, the reflect pad with L barely above 640
+    (3, 10248),       # T = 32; L a multiple of 8 but not of 320
+    (2, 15364),       # L % 8 != 0: the conv fallback at batch scale
+    (5, 6400),        # 100 columns: one ragged tile with four row changes inside it
+])
+def test_spectrogram(N, L):
     from module.spectrogram import spectrogram
-    wav = torch.cat([synthetic.make_waveform(L, 9), synthetic.make_waveform(L, 10)], 0)
+    wav = torch.cat([synthetic.make_waveform(L, 9 + i) for i in range(N)], 0)
     ref = O.spectrogram(wav)
     got = spectrogram(wav.to(DEV)).cpu()
     assert got.shape == ref.shape
