@@ -497,7 +497,10 @@ int fb_launch(const char* name, const float* U, int N, int L, const void* const*
     ALIVE_CHECK_ARG(N > 0 && L > 2 * CTX && Lf > 0, "%s: bad sizes (L must exceed 32)", name);
     ALIVE_CHECK_ARG(U != out, "%s: in-place not supported (a block's warm-up tile reads columns another block has stored)", name);
     ALIVE_CHECK_ARG(film_ld > 0 && t0 >= 0 && f0 >= 0, "%s: bad frame range", name);
-    ALIVE_CHECK_ARG(128.0 * film_ld / L + 3.0 <= G::NFS, "%s: 128 columns span more than %d frames (L %d, frames %d)", name, G::NFS - 3, L, film_ld);
+    // (a wave's table holds the frames of its 128 columns; a window shorter than that has only L of them, all the others are clamped to
+    // the last one: L = 33 with 4 frames is within the table)
+    ALIVE_CHECK_ARG((L < 128 ? (double)L : 128.0) * film_ld / L + 3.0 <= G::NFS, "%s: 128 columns span more than %d frames (L %d, frames %d)", name,
+                    G::NFS - 3, L, film_ld);
     Fb256Weights wts;
     for (int q = 0; q < NCONV; ++q) {
         ALIVE_CHECK_ARG(w16[q] && bias[q], "%s: null weights", name);
