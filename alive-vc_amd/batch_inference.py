@@ -22,6 +22,11 @@ The jobs file is a JSON list; each entry:
                                                             limiter (module/multistream.py limit_waves) on the device after the
                                                             gain, at the file's own rate, before "normalize": no sample exceeds
                                                             the ceiling.  A jobs file without it, run without -lim, runs as before
+   "envelope": 0.7,                                         optional, a number in [0, 1] or null (default: -env): how far the converted
+                                                            voice follows the source's loudness contour (module/multistream.py
+                                                            follow_envelope), at 16 kHz before the output resample and the gain; 0 or
+                                                            null: the decoder's own level.  A jobs file without it, run without -env,
+                                                            runs as before
    "blend": [{"target": "a.wav", "weight": 2},              instead of "target" / "lib": a weighted mix of 1 to 4 voices, each
              {"lib": "b.pt", "weight": 1}],                 component a voice source as above (module/multistream.py blend_spec)
    "output": "a_out.wav"}                                   optional: default <outdir>/<index>_<input name>.wav
@@ -45,6 +50,7 @@ from module.multistream import MAX_K, blend_sources, check_k     # noqa: E402
 
 JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "world_pitch", "output",
             "blend", "k", "auto_pitch", "register_hz")
+ENVELOPE_KEYS = ("envelope",)            # likewise; a loaded job carries it only when it follows (an amount above 0)
 LIMIT_KEYS = ("limit_db",)               # taken per job too; a loaded job carries it only when it is limited
 
 
@@ -70,6 +76,16 @@ def build_parser():
                         help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5)")
     parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
                         help="milliseconds the limiter's gain stays down after a peak (default 20)")
+    parser.add_argument('-env', '--envelope', default=0.0, type=float, metavar="A",
+                        help="envelope follow: the converted voices take on their sources' loudness contours by this amount, 0 (off, the "
+                             "default) to 1, unless a job's \"envelope\" says otherwise (module/multistream.py follow_envelope).  It can lift samples above full "
+                             "scale: use -lim beside it")
+    parser.add_argument('--envelope-floor', default=-60.0, type=float, metavar="DB",
+                        help="the level under which the envelope follow stops telling the two signals apart (default -60)")
+    parser.add_argument('--envelope-range', default=12.0, type=float, metavar="DB",
+                        help="the most the envelope follow turns a frame up or down (default 12)")
+    parser.add_argument('--envelope-radius', default=1, type=int, metavar="FRAMES",
+                        help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV")
     return parser
 
@@ -110,11 +126,27 @@ def job_limit(j, where, limit_db=None, lookahead_ms=5.0, hold_ms=20.0):
     return None if db is None else float(db)
 
 
-def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold_ms=20.0):
+def job_envelope(j, where, envelope=0.0, floor_db=-60.0, range_db=12.0, radius=1):
+    """an entry's "envelope" (default `envelope`; a JSON null or 0 switches the default off) -> the amount as a float in (0, 1], or
+    None for a job that does not follow; ValueError otherwise (the three tuning values are those of the flags, checked with it)"""
+    from module.multistream import check_envelope
+    a = j.get("envelope", envelope)
+    try:
+        a = check_envelope(0.0 if a is None else a, floor_db, range_db, radius)[0]
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return a if a > 0 else None
+
+
+def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0,
+              envelope_range_db=12.0, envelope_radius=1):
     """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder; "auto_pitch": default
     `auto_pitch`); a limited job ("limit_db", default `limit_db`) also carries "limit_db", a job without a limiter does not, so a
-    file without the key loads to what it did; ValueError on a malformed job, before anything runs on the device"""
+    file without the key loads to what it did; likewise "envelope" (default `envelope`) only on a job that follows at an amount above
+    0; ValueError on a malformed job, before anything runs on the device"""
     job_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, lookahead_ms, hold_ms)
+    env = (envelope_floor_db, envelope_range_db, envelope_radius)
+    job_envelope({}, "-env / --envelope-floor / --envelope-range / --envelope-radius", envelope, *env)
     if not 1 <= k <= MAX_K:
         raise ValueError(f"k={k} outside [1, {MAX_K}] (the pool search's limit)")
     with open(path) as f:
@@ -127,9 +159,9 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
     for i, j in enumerate(jobs):
         if not isinstance(j, dict) or "input" not in j:
             raise ValueError(f"job {i}: an object with an \"input\" wav is required")
-        unknown = set(j) - set(JOB_KEYS) - set(LIMIT_KEYS)
+        unknown = set(j) - set(JOB_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS)
         if unknown:
-            raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: {JOB_KEYS + LIMIT_KEYS})")
+            raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: {JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS})")
         blend = blend_sources(j, f"job {i}", rel) if "blend" in j else None
         if blend is None and j.get("target") is None and j.get("lib") is None:
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
@@ -146,6 +178,9 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
         lim = job_limit(j, f"job {i}", limit_db, lookahead_ms, hold_ms)
         if lim is not None:
             e["limit_db"] = lim
+        amount = job_envelope(j, f"job {i}", envelope, *env)
+        if amount is not None:
+            e["envelope"] = amount
         for key in ("input", "target", "lib"):
             if e[key] is not None and not os.path.isfile(e[key]):
                 raise ValueError(f"job {i}: {key} {e[key]!r} does not exist")
@@ -200,14 +235,15 @@ def main(argv=None):
     device = torch.device(args.device)
     if device.type != "cuda":
         raise SystemExit("this build runs on the MI355X only: pass -d cuda")
-    jobs = load_jobs(args.jobs, args.k, args.auto_pitch, args.limit, args.limit_lookahead, args.limit_hold)
+    jobs = load_jobs(args.jobs, args.k, args.auto_pitch, args.limit, args.limit_lookahead, args.limit_hold, args.envelope,
+                     args.envelope_floor, args.envelope_range, args.envelope_radius)
     auto = any(j["auto_pitch"] for j in jobs)           # only then are the voices' registers measured or declared
     declared = declared_registers(jobs) if auto else {}
     # (device work starts here)
     from module.content_encoder import ContentEncoder
     from module.decoder import Decoder
     from module.f0_estimator import F0Estimator
-    from module.multistream import VoicePool, limit_waves, measure_register, pitch_hz
+    from module.multistream import VoicePool, follow_envelope, limit_waves, measure_register, pitch_hz
     from module.pipeline import Converter
     from module.spectrogram import spectrogram
     from module.voice_library import VoiceLibrary
@@ -258,6 +294,8 @@ def main(argv=None):
                              auto_pitch=[j["auto_pitch"] for j in jobs] if auto else False, chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)
     for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
+        if job.get("envelope"):                                         # at 16 kHz, against the source the converter saw
+            out = follow_envelope(out, utts[i], None, job["envelope"], args.envelope_floor, args.envelope_range, args.envelope_radius)
         out = audio_io.resample(out, 16000, sr, post_gain_db=job["gain"])
         if job.get("limit_db") is not None:                             # on the device, before the normalisation and the save
             out = limit_waves(out, None, job["limit_db"], args.limit_lookahead, args.limit_hold, sr)

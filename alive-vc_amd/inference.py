@@ -69,6 +69,16 @@ def build_parser():
                         help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5)")
     parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
                         help="milliseconds the limiter's gain stays down after a peak (default 20)")
+    parser.add_argument('-env', '--envelope', default=0.0, type=float, metavar="A",
+                        help="envelope follow: the converted voice takes on the source's loudness contour by this amount, 0 (off, the "
+                             "default) to 1 (module/multistream.py follow_envelope; this build only).  It can lift samples above full "
+                             "scale: use -lim beside it")
+    parser.add_argument('--envelope-floor', default=-60.0, type=float, metavar="DB",
+                        help="the level under which the envelope follow stops telling the two signals apart (default -60)")
+    parser.add_argument('--envelope-range', default=12.0, type=float, metavar="DB",
+                        help="the most the envelope follow turns a frame up or down (default 12)")
+    parser.add_argument('--envelope-radius', default=1, type=int, metavar="FRAMES",
+                        help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV (this build only)")
     return parser
 
@@ -83,6 +93,10 @@ def main(argv=None):
     if args.limit is not None:
         from module.multistream import check_limit, limit_waves
         check_limit(args.limit, args.limit_lookahead, args.limit_hold)       # (before anything is loaded)
+    env = (args.envelope_floor, args.envelope_range, args.envelope_radius)
+    if args.envelope != 0:
+        from module.multistream import check_envelope, follow_envelope
+        check_envelope(args.envelope, *env)                                  # (before anything is loaded)
 
     PE, CE, Dec = F0Estimator().to(device), ContentEncoder().to(device), Decoder().to(device)
     PE.load_state_dict(torch.load(args.f0_estimator_path, map_location=device))
@@ -117,6 +131,8 @@ def main(argv=None):
                            world_pitch=bool(args.world_pitch_estimation), intonation=args.intonation, f0_rate=args.f0_rate, window_batch=args.window_batch,
                            trim_context=not args.no_trim_context,
                            share_overlap=None if args.no_share_overlap else "auto")
+        if args.envelope > 0:                     # at 16 kHz, against the normalised mono source the converter saw
+            out = follow_envelope(out, wf, None, args.envelope, *env)
         out = audio_io.resample(out, 16000, sr, post_gain_db=args.gain)            # resample, then gain (:136-137)
         if args.limit is not None:                # on the device, at the file's own rate, before -norm and the save
             out = limit_waves(out, None, args.limit, args.limit_lookahead, args.limit_hold, sr)

@@ -163,6 +163,7 @@ PROTOTYPES = {
     "alive_seam_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     "alive_limit_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     "alive_limit_waves": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP]),
+    "alive_envelope_waves": (_I, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _D, _D, _D, _VP, _VP]),
     "alive_ring_push_rows": (_I, [_VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "alive_emit_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I, _VP]),
     "alive_codebook_workspace_bytes": (_SZ, [_I64, _I64]),

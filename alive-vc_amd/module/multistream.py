@@ -124,6 +124,23 @@ After the step alive_emit_rows cuts the emitting rows' spans (_span of the slot'
 [B, widest span] array, the only thing copied back.  open and close zero the slot's device ring and its row of _in.  With every session
 present every tick a sparse converter emits what the dense one emits, byte for byte; a converter built without sparse launches exactly
 what it did, `ring`, _in and the ValueError for a missing slot included.
+
+Envelope follow: the decoder sets the level of every frame from the matched features and f0; nothing carries the speaker's own loudness
+across.  A converter built with envelope=True (csrc/envelope.hip) runs alive_envelope_waves right after the decoder, before the output
+resample: for the sessions opened or set with envelope=A (the amount, 0 < A <= 1) the decoder's 16 kHz wave y is multiplied by a gain
+that moves its smoothed frame level towards that of the 16 kHz ring x the gate also sees, which lies beside it sample for sample:
+per 320-sample frame the mean squares of x and y over 2 R + 1 frames, rc = sqrt((Px / Cn + e) / (Py / Cn + e)) kept inside
++-envelope_range_db, G = 1 + A (rc - 1), interpolated linearly between the frame centres -- all in fp64 in a fixed order
+(tools/envelope_ref.py restates it bit for bit).  The tick re-decodes the whole ring, so the envelope is a stateless function of two
+rows: nothing is carried across ticks, the bf16 repeat or a capture, and a row that sat a tick out is recomputed from its unchanged
+ring.  The result goes to a buffer allocated once (the captured graph replays into the same memory); the seam, the gate's edge and the
+limiter sit downstream and see the enveloped wave.  The amounts are a device array: toggling and retuning never re-capture, a converter
+built without envelope launches exactly what it did, and one whose sessions are all at 0 emits byte-identical streams.  The frame grid
+is ring-relative, as the decoder's own frames are: with chunks that are no multiple of 320 samples at 16 kHz it moves against the signal
+from tick to tick, so two successive decodes get slightly different gains at a seam -- smoothed over 2 R + 1 frames, interpolated, and
+faded by crossfade.  The gain can lift a sample above 1.0: use the limiter beside it.  envelope_db() reads the latest tick's smallest
+and largest frame gain per slot back.  follow_envelope is the offline form (the same call over whole utterances).  The defaults (R = 1:
+60 ms, floor -60 dB, range 12 dB) are design choices: with no trained weights, how they sound is unmeasured.
 """
 import numpy as np
 import torch
@@ -1198,6 +1215,81 @@ def limit_waves(wave, lens=None, limit_db=-1.0, lookahead_ms=5.0, hold_ms=20.0, 
     return (out, gmin_db(gmin.tolist())) if return_gain else out
 
 
+ENVELOPE_TILE, ENVELOPE_MAX_RADIUS = 16, 4      # ALIVE_ENVELOPE_TILE, ALIVE_ENVELOPE_MAX_RADIUS (include/alive_vc.h)
+ENVELOPE_HOP = 320                              # the decoder's frame at 16 kHz
+
+
+def envelope_waves_(out, y, x, lens, amount, hop, radius, floor_ms, g_lo, g_hi, gain_minmax=None):
+    """alive_envelope_waves into out [N, ld_y]: y float32 [N, ld_y] times the gain that moves its frame levels towards those of x
+    float32 [N, ld_x], row n over its first lens[n] samples (device int32 [N], or None: the whole row) at amount[n] (device float32
+    [N]; a row whose amount is not in (0, 1] is copied).  gain_minmax: float32 [N, 2] or None.  out must not overlap y or x"""
+    for name, t in (("out", out), ("y", y), ("x", x)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+            raise ValueError(f"envelope_waves_: {name} must be contiguous float32 [N, ld]")
+    n, ld_y = y.shape
+    if out.shape != y.shape or x.shape[0] != n:
+        raise ValueError(f"envelope_waves_: out {tuple(out.shape)}, y {tuple(y.shape)} and x {tuple(x.shape)} do not belong together")
+    nat.check(nat.lib().alive_envelope_waves(nat.ptr(out), nat.ptr(y), ld_y, nat.ptr(x), x.shape[1], n, nat.ptr(lens),
+                                             nat.ptr(amount), int(hop), int(radius), float(floor_ms), float(g_lo), float(g_hi),
+                                             nat.ptr(gain_minmax), nat.stream()), "alive_envelope_waves")
+    return out
+
+
+def check_envelope(amount, floor_db=-60.0, range_db=12.0, radius=1):
+    """an envelope follower's settings -> (amount, floor_ms, g_lo, g_hi, radius): the amount as a float, the floor as a mean square
+    10^(floor_db / 10) and the range 10^(-+range_db / 20) in float64.  ValueError unless amount is a finite number in [0, 1] (not a
+    bool; 0: off), floor_db a finite number in [-3000, 3000], range_db a finite number in [0, 6000] (so that the floor is above 0 and
+    the range finite in float64), and radius
+    an integer in [0, ENVELOPE_MAX_RADIUS]"""
+    if not _number(amount) or not (np.isfinite(amount) and 0 <= amount <= 1):
+        raise ValueError(f"envelope={amount!r} must be a finite number in [0, 1] (0: the converted level as it is)")
+    if not _number(floor_db) or not (np.isfinite(floor_db) and -3000 <= floor_db <= 3000):
+        raise ValueError(f"envelope_floor_db={floor_db!r} must be a finite number of dB in [-3000, 3000] (its mean square is above 0)")
+    if not _number(range_db) or not (np.isfinite(range_db) and 0 <= range_db <= 6000):
+        raise ValueError(f"envelope_range_db={range_db!r} must be a finite number of dB >= 0 (at most 6000)")
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= ENVELOPE_MAX_RADIUS:
+        raise ValueError(f"envelope_radius={radius!r} must be an integer in [0, {ENVELOPE_MAX_RADIUS}] (frames on each side)")
+    return (float(amount), float(10.0 ** (float(floor_db) / 10.0)), float(10.0 ** (-float(range_db) / 20.0)),
+            float(10.0 ** (float(range_db) / 20.0)), int(radius))
+
+
+def minmax_db(minmax):
+    """alive_envelope_waves' smallest and largest frame gains -> (20 log10 min, 20 log10 max) per row: (0.0, 0.0) for a row that
+    does not follow"""
+    return [(float(20.0 * np.log10(np.float64(lo))) if lo != 1.0 else 0.0, float(20.0 * np.log10(np.float64(hi))) if hi != 1.0 else 0.0)
+            for lo, hi in minmax]
+
+
+def follow_envelope(wave, source, lens=None, amount=1.0, floor_db=-60.0, range_db=12.0, radius=1):
+    """The offline envelope follow: wave float32 [N, ld] (or [ld]) on the device, the conversion of `source` float32 [N, ld_x] (or
+    [ld_x]) that lies beside it sample for sample at 16 kHz -> a new tensor of wave's shape, row n's first lens[n] samples (default:
+    as many as both rows hold) at the source's loudness contour, the rest copied (alive_envelope_waves).  amount: a number in [0, 1],
+    or one per row (0: the row is copied).  ValueError as check_envelope"""
+    one = wave.dim() == 1
+    y = (wave[None] if one else wave).contiguous()
+    x = (source[None] if source.dim() == 1 else source).contiguous()
+    if y.dim() != 2 or y.dtype != torch.float32 or x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] != y.shape[0]:
+        raise ValueError(f"follow_envelope: wave and source must be float32 [N, ld] or [ld] with the same N, got "
+                         f"{tuple(wave.shape)} {wave.dtype} and {tuple(source.shape)} {source.dtype}")
+    if x.device != y.device:
+        raise ValueError(f"follow_envelope: wave on {y.device}, source on {x.device}")
+    n, ld = y.shape
+    amounts = list(amount) if isinstance(amount, (list, tuple)) else [amount] * n
+    if len(amounts) != n:
+        raise ValueError(f"follow_envelope: {len(amounts)} amounts for {n} rows")
+    checked = [check_envelope(a, floor_db, range_db, radius) for a in amounts]
+    _, floor_ms, g_lo, g_hi, radius = checked[0]
+    cap = min(ld, x.shape[1])
+    lens = [cap] * n if lens is None else [int(v) for v in lens]
+    if len(lens) != n:
+        raise ValueError(f"follow_envelope: {len(lens)} lens for {n} rows")
+    dev = y.device
+    out = envelope_waves_(torch.empty_like(y), y, x, torch.tensor(lens, dtype=torch.int32, device=dev),
+                          torch.tensor([c[0] for c in checked], dtype=torch.float32, device=dev), ENVELOPE_HOP, radius, floor_ms,
+                          g_lo, g_hi)
+    return out[0] if one else out
+
+
 def wave_length(frames, rate):
     """the samples of a converter's final wave: the decoder's 320 per frame at 16 kHz, resampled to `rate`"""
     orig, new = audio_io._reduced(16000, rate)
@@ -1356,7 +1448,7 @@ def db_scale(db):
 
 
 _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold",
-           "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms")
+           "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope")
 
 
 class MultiStreamConverter:
@@ -1365,11 +1457,20 @@ class MultiStreamConverter:
     crossfade = False                  # (likewise: whether the tick carries the seam kernel)
     limiter = False                    # (likewise: whether the tick carries the limiter kernel)
     sparse = False                     # (likewise: whether the rings live on the device and sessions may sit ticks out)
+    envelope = False                   # (likewise: whether the tick carries the envelope kernel)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
                  auto_pitch_half_life=10.0, auto_pitch_prior=0.5, gate=False, gate_lookahead=None, crossfade=False,
-                 limiter=False, limit_history=0.05, sparse=False):
+                 limiter=False, limit_history=0.05, sparse=False, envelope=False, envelope_floor_db=-60.0,
+                 envelope_range_db=12.0, envelope_radius=1):
+        if not isinstance(envelope, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: envelope must be a bool, got {envelope!r}")
+        if envelope:                       # (checked before anything is built)
+            try:
+                env = check_envelope(0.0, envelope_floor_db, envelope_range_db, envelope_radius)
+            except ValueError as e:
+                raise ValueError(f"MultiStreamConverter: {e}") from None
         if not isinstance(sparse, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: sparse must be a bool, got {sparse!r}")
         if not isinstance(limiter, (bool, np.bool_)):
@@ -1550,6 +1651,15 @@ class MultiStreamConverter:
                 lo, ln = self._span(self.chunk)
                 self.span_lo = torch.full((B,), lo, **i32)
                 self.span_len = torch.full((B,), ln, **i32)
+        # envelope: the envelope kernel is part of the tick (captured once), right after the decoder; per row, env_amount is the
+        # session's amount (0: copied).  No state: the kernel is a function of the tick's ring and wave.  _env_out is allocated once,
+        # by the first tick
+        self.envelope = bool(envelope)
+        if self.envelope:
+            self._env = env[1:]                                # (floor_ms, g_lo, g_hi, radius)
+            self.env_amount = torch.zeros(B, dtype=torch.float32, device=dev)
+            self.env_minmax = torch.ones(B, 2, dtype=torch.float32, device=dev)
+            self._env_out = None
         self.phi = torch.zeros(B, 64, device=dev)
         self._in = torch.zeros(B, ld_in, device=dev)
         # sparse: the rings live on the device in time order (ring_dev; `ring` is gone, rings() reads them back), one push per tick
@@ -1665,6 +1775,17 @@ class MultiStreamConverter:
         except ValueError as e:
             raise ValueError(f"slot {slot}: {e}") from None
 
+    def _session_envelope(self, slot, p):
+        """a session's envelope amount (None: 0), checked against the converter"""
+        a = p.get("envelope", 0.0)
+        try:
+            a = check_envelope(0.0 if a is None else a)[0]
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+        if a > 0 and not self.envelope:
+            raise ValueError(f"slot {slot}: envelope={a!r} needs a converter built with MultiStreamConverter(..., envelope=True)")
+        return a
+
     def _session_gate(self, slot, p):
         """a session's gate settings -> (on, thr_ms, hold_ticks), checked against the converter"""
         db, hold = p.get("gate_db"), p.get("gate_hold", 0.2)
@@ -1684,6 +1805,7 @@ class MultiStreamConverter:
         gate = self._session_gate(slot, p)
         xlen = self._session_seam(slot, p, rate)
         limit = self._session_limit(slot, p, rate)
+        env = self._session_envelope(slot, p)
         names, weights = blend_spec(p["voice"], self.pool, k, self.S)
         world = p["world_pitch"]
         if not isinstance(world, (bool, np.bool_)):
@@ -1725,6 +1847,8 @@ class MultiStreamConverter:
             self.xlen[slot] = xlen
         if self.limiter:
             self.look[slot], self.hold[slot], self.ceil[slot] = limit
+        if self.envelope:
+            self.env_amount[slot] = env
 
     def _write_segments(self, slot, names):
         """the slot's rows of seg_lo / seg_len from where its voices lie in the pool now"""
@@ -1791,7 +1915,7 @@ class MultiStreamConverter:
 
     def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None,
              auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0,
-             limit_hold_ms=20.0):
+             limit_hold_ms=20.0, envelope=0.0):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
@@ -1804,7 +1928,9 @@ class MultiStreamConverter:
         continuation (None: a hard cut), at most the session's emitted span; the first chunk has nothing to fade from.  limit_db
         (needs a limiter=True converter): the session's output limiter, a ceiling in dBFS <= 0 that no emitted sample exceeds (None:
         no limiter, the int16 edge wraps); limit_lookahead_ms: how long before a peak the gain starts to fall (and after the hold,
-        how long it takes to come back), at most the session's chunk; limit_hold_ms: how long the gain stays down after a peak"""
+        how long it takes to come back), at most the session's chunk; limit_hold_ms: how long the gain stays down after a peak.
+        envelope (above 0: needs an envelope=True converter): how far the converted wave follows the loudness contour of the session's
+        input, from 0 (the decoder's own level) to 1 (the source's smoothed frame level, within the converter's range)"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
@@ -1812,7 +1938,7 @@ class MultiStreamConverter:
                              "MultiStreamConverter(..., rates=...)")
         p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch,
                  k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold, crossfade_ms=crossfade_ms, limit_db=limit_db,
-                 limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms)
+                 limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms, envelope=envelope)
         self._apply(slot, p, rate)                            # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -1832,7 +1958,7 @@ class MultiStreamConverter:
 
     def set(self, slot, **params):
         """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
-        gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms, limit_hold_ms; the gate's state, the saved tail and the
+        gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms, limit_hold_ms, envelope; the gate's state, the saved tail and the
         limiter's history are kept: a longer crossfade fades over what the tail holds this tick and in full from the next, and a
         limiter switched on or retuned sees the required gains of the samples already emitted).
         The running source register is kept: a new voice changes the target only, and auto_pitch=True after False resumes from
@@ -1882,6 +2008,9 @@ class MultiStreamConverter:
             self.hold[slot] = 0
             self.ceil[slot] = 1.0
             self._limit_reset(slot)
+        if self.envelope:
+            self.env_amount[slot] = 0.0
+            self.env_minmax[slot] = 1.0
         self._set_rate(slot, int(self.input_sr))             # a closed slot: the converter's own rate, silence
         return self
 
@@ -1916,6 +2045,23 @@ class MultiStreamConverter:
         if not self.limiter:
             raise ValueError("limit_db needs a converter built with MultiStreamConverter(..., limiter=True)")
         return gmin_db(self.limit_gmin.tolist())
+
+    def envelope_db(self):
+        """how far the envelope moved each slot in the latest tick, a list of B pairs: 20 log10 of the smallest and of the largest
+        frame gain over the slot's whole ring; (0.0, 0.0) for a slot that does not follow.  One host read"""
+        if not self.envelope:
+            raise ValueError("envelope_db needs a converter built with MultiStreamConverter(..., envelope=True)")
+        return minmax_db(self.env_minmax.tolist())
+
+    def _follow(self, wave, data):
+        """the decoder's 16 kHz waves [B, L] at the loudness contour of the 16 kHz rings `data`, row by row at the sessions' amounts,
+        into the buffer allocated once"""
+        wave, data = wave.contiguous(), data.contiguous()
+        if self._env_out is None or self._env_out.shape != wave.shape:
+            self._env_out = torch.empty_like(wave)
+        floor_ms, g_lo, g_hi, radius = self._env
+        return envelope_waves_(self._env_out, wave, data, None, self.env_amount, ENVELOPE_HOP, radius, floor_ms, g_lo, g_hi,
+                               self.env_minmax)
 
     def seam_db(self):
         """the seam statistic of the latest tick, a list of B floats: 10 log10(sum (c - t)^2 / sum c^2) over the faded head of each
@@ -1983,6 +2129,8 @@ class MultiStreamConverter:
         join()
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0
+        if self.envelope:                                     # the decoder's level -> the source's contour, before all downstream
+            wave = self._follow(wave, data)
         if self._rt is None:
             wave = resample_rows(wave, 16000, self.output_sr, self.out_pre, self.out_post)
         else:

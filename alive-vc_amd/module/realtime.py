@@ -20,6 +20,11 @@ module/multistream.py "Limiter") at one row, last, on the emitted span of the fi
 int16 edge never wraps.  It works on both step forms and with input_sr != output_sr.  The history of required gains lives beside the
 phase: `reset`, `enable_graph` and a `step_device(continues=False)` set it to 1.0, the bf16 repeat restores it.  Without limit_db the
 converter launches what it did.
+
+Envelope follow (`-env`): RealtimeConverter(envelope=A, envelope_floor_db=, envelope_range_db=, envelope_radius=) runs
+alive_envelope_waves (csrc/envelope.hip, module/multistream.py "Envelope follow") at one row right after the decoder, on both step forms:
+the decoder's 16 kHz wave takes on the loudness contour of the 16 kHz ring the gate also sees, by the amount A in (0, 1].  It is a
+stateless function of the step's ring and wave: nothing is kept between steps.  Without it (A = 0) the converter launches what it did.
 """
 import numpy as np
 import torch
@@ -129,12 +134,17 @@ def capture_step(device, step, phi):
 
 class RealtimeConverter:
     limiter = False                    # (set per converter in __init__: whether the step carries the limiter kernel)
+    envelope = False                   # (likewise: whether the step carries the envelope kernel)
 
     def __init__(self, content_encoder, f0_estimator, decoder, library_tokens, device="cuda", chunk=960, buffersize=8,
                  input_sr=16000, output_sr=16000, f0_rate=1.0, pitch=0.0, k=4, alpha=0.0, gain=0.0, input_gain=0.0,
                  reuse_interior="auto", world_pitch=False, gate_db=None, gate_hold=0.2, gate_lookahead=None,
-                 crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0, limit_hold_ms=20.0, limit_history=0.05):
+                 crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0, limit_hold_ms=20.0, limit_history=0.05,
+                 envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0, envelope_radius=1):
         self.device = torch.device(device)
+        from .multistream import check_envelope
+        env = check_envelope(0.0 if envelope is None else envelope, envelope_floor_db, envelope_range_db, envelope_radius)
+        self.envelope = env[0] > 0         # (checked before anything is built)
         self.limiter = limit_db is not None
         if self.limiter:                   # (checked before anything is built)
             from .multistream import check_limit, limit_history_width
@@ -214,6 +224,12 @@ class RealtimeConverter:
             self._limit_emit = torch.ones(1, dtype=torch.bool, device=dev)
             self._limit_hist = torch.ones(1, limit_width, device=dev)
             self._limit_gmin = torch.ones(1, device=dev)
+        if self.envelope:
+            # the multi-session envelope follow at one row; no state: a function of the step's ring and wave.  _env_out is allocated
+            # once, by the first step
+            self._env = env[1:]                # (floor_ms, g_lo, g_hi, radius)
+            self._env_amount = torch.tensor([env[0]], dtype=torch.float32, device=self.device)
+            self._env_out = None
         self._side = None                  # side stream of the f0 estimator (see _f0_on_side_stream)
         self._f0_bufs = {}
         # interior reuse: only where it is exact -- no resampling in front (the ring IS the 16 kHz signal), a shift of whole
@@ -251,6 +267,7 @@ class RealtimeConverter:
         content, f0 = self._front_end(spectrogram(data), data)
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0                  # (a view of the per-shape side-stream buffer: valid until the next step)
+        wave = self._follow(wave, data)
         wave = self._limit(self._gate_edge(self._seam(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain))))[0]   # gain, then resample
         return wave, phi_out[:, :, self.end_of_output]
 
@@ -280,6 +297,18 @@ class RealtimeConverter:
             wave = seam_rows_(wave.contiguous(), self._seam_lo, self._seam_shift, self._seam_x, self._seam_emit, self._seam_tail,
                               self._seam_stored, self._g0 if self.gate else None, self._g1 if self.gate else None,
                               self._seam_stats)
+        return wave
+
+    def _follow(self, wave, data):
+        """envelope on: the decoder's 16 kHz wave [1, L] at the loudness contour of the 16 kHz ring `data` [1, L16], into the buffer
+        allocated once (alive_envelope_waves at one row; right after the decoder, before the output resample)"""
+        if self.envelope:
+            from .multistream import ENVELOPE_HOP, envelope_waves_
+            wave, data = wave.contiguous(), data.contiguous()
+            if self._env_out is None or self._env_out.shape != wave.shape:
+                self._env_out = torch.empty_like(wave)
+            floor_ms, g_lo, g_hi, radius = self._env
+            wave = envelope_waves_(self._env_out, wave, data, None, self._env_amount, ENVELOPE_HOP, radius, floor_ms, g_lo, g_hi)
         return wave
 
     def _limit(self, wave):
@@ -354,6 +383,7 @@ class RealtimeConverter:
             self._c_f0[:, :, a:].copy_(f0[:, :, margin:])
         wave, phi_out = self.dec(self._c_feat, f0=self._c_f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = self._c_f0
+        wave = self._follow(wave, data)
         wave = self._limit(self._gate_edge(self._seam(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain))))[0]
         return wave, phi_out[:, :, self.end_of_output]
 

@@ -23,6 +23,9 @@ The sessions file is a JSON list; each entry:
                                           default -lim), the milliseconds over which the gain falls ahead of a peak (at most the
                                           session's chunk; default --limit-lookahead) and those it stays down after one (default
                                           --limit-hold)
+   "envelope": 0.7,                       optional, a number in [0, 1] or null (default: -env): how far the session's converted voice
+                                          follows the loudness contour of its input (module/multistream.py "Envelope follow"); 0 or
+                                          null: the decoder's own level
    "codebook": 4096,                      optional, an integer >= 1 or null (default: --codebook): the session's voice is condensed to
                                           that many centroid rows by k-means when it is packed or enrolled (module/codebook.py); a
                                           voice of that many rows or fewer stays as it is.  A codebook's rows are means: use k 1 or 2
@@ -51,6 +54,8 @@ The converter carries the seam kernel only if some session ends up with a crossf
 the key, run without the flag, runs as before.
 The converter carries the limiter kernel only if some session ends up limited ("limit_db", or -lim): a file without the key, run
 without the flag, runs as before.
+The converter carries the envelope kernel only if some session ends up following ("envelope" above 0, or -env): a file without the
+key, run without the flag, runs as before.
 The voices are condensed only for sessions with a "codebook" (or under --codebook): a file without the key, run without the flag, runs
 as before.  The size is part of the voice's pool name: sessions on the same sources at different sizes get different voices; a blend's
 components are each condensed to the session's size.
@@ -83,7 +88,7 @@ from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
 from module.multistream import (MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
-                                check_crossfade_ms, check_limit, gate_hold_ticks, gate_thr_ms, measure_register)
+                                check_crossfade_ms, check_envelope, check_limit, gate_hold_ticks, gate_thr_ms, measure_register)
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
@@ -92,6 +97,7 @@ SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "
 GATE_KEYS = ("gate_db", "gate_hold")     # taken per session too; a loaded session carries them only when it is gated
 SEAM_KEYS = ("crossfade_ms",)            # taken per session too; a loaded session carries it only when it crossfades
 LIMIT_KEYS = ("limit_db", "limit_lookahead_ms", "limit_hold_ms")      # likewise; a loaded session carries them only when it limits
+ENVELOPE_KEYS = ("envelope",)            # likewise; a loaded session carries it only when it follows (an amount above 0)
 CODEBOOK_KEYS = ("codebook",)            # taken per session too; a loaded session carries it only when its voice is condensed
 STALL_KEYS = ("stall",)                  # a loaded session carries it only when its entry has the key (the converter is then sparse)
 
@@ -130,6 +136,16 @@ def build_parser():
                         help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5; a session's \"limit_lookahead_ms\" overrides)")
     parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
                         help="milliseconds the limiter's gain stays down after a peak (default 20; a session's \"limit_hold_ms\" overrides)")
+    parser.add_argument('-env', '--envelope', default=0.0, type=float, metavar="A",
+                        help="envelope follow: the sessions' converted voices take on their inputs' loudness contours by this amount, 0 (off, the "
+                             "default) to 1, unless their \"envelope\" says otherwise (module/multistream.py \"Envelope follow\").  It can "
+                             "lift samples above full scale: use -lim beside it")
+    parser.add_argument('--envelope-floor', default=-60.0, type=float, metavar="DB",
+                        help="the level under which the envelope follow stops telling the two signals apart (default -60)")
+    parser.add_argument('--envelope-range', default=12.0, type=float, metavar="DB",
+                        help="the most the envelope follow turns a frame up or down (default 12)")
+    parser.add_argument('--envelope-radius', default=1, type=int, metavar="FRAMES",
+                        help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
     parser.add_argument('--codebook', default=None, type=int, metavar="SIZE",
                         help="condense every session's voice to SIZE centroid rows by k-means unless its \"codebook\" says otherwise "
                              "(default: the voices as they are)")
@@ -199,6 +215,17 @@ def session_limit(s, where, limit_db=None, lookahead_ms=5.0, hold_ms=20.0):
     return None if checked is None else (float(db), checked[1], checked[2])
 
 
+def session_envelope(s, where, envelope=0.0, floor_db=-60.0, range_db=12.0, radius=1):
+    """an entry's "envelope" (default `envelope`; a JSON null or 0 switches the default off) -> the amount as a float in (0, 1], or
+    None for a session that does not follow; ValueError otherwise (the three tuning values are those of the flags, checked with it)"""
+    a = s.get("envelope", envelope)
+    try:
+        a = check_envelope(0.0 if a is None else a, floor_db, range_db, radius)[0]
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return a if a > 0 else None
+
+
 def session_codebook(s, where, codebook=None):
     """an entry's "codebook" (default `codebook`) -> an integer >= 1, or None for a voice that stays as it is (a JSON null switches
     the default off); ValueError otherwise"""
@@ -235,18 +262,22 @@ def supply_ticks(start, n_chunks, stall=None):
 
 
 def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None, crossfade_ms=None, limit_db=None,
-                  limit_lookahead_ms=5.0, limit_hold_ms=20.0):
+                  limit_lookahead_ms=5.0, limit_hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0,
+                  envelope_radius=1):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
     condensed, "crossfade_ms" (default `crossfade_ms`) only on a session that crossfades, and "limit_db" / "limit_lookahead_ms" /
-    "limit_hold_ms" (defaults `limit_db`, `limit_lookahead_ms`, `limit_hold_ms`) only on a session that limits, and "stall" (a sorted
+    "limit_hold_ms" (defaults `limit_db`, `limit_lookahead_ms`, `limit_hold_ms`) only on a session that limits, "envelope" (default
+    `envelope`) only on a session that follows at an amount above 0, and "stall" (a sorted
     tuple of ticks) only on a session whose entry has the key; ValueError on a malformed entry"""
     k = check_k(k, "-k")
     session_codebook({}, "--codebook", codebook)
     session_gate({}, "-thr / --gate-hold", gate_db, gate_hold)
     session_crossfade({}, "--crossfade", crossfade_ms)
     session_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, limit_lookahead_ms, limit_hold_ms)
+    env = (envelope_floor_db, envelope_range_db, envelope_radius)
+    session_envelope({}, "-env / --envelope-floor / --envelope-range / --envelope-radius", envelope, *env)
     with open(path) as f:
         sessions = json.load(f)
     if not isinstance(sessions, list) or not sessions:
@@ -256,14 +287,16 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     for i, s in enumerate(sessions):
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
-        unknown = set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(CODEBOOK_KEYS) - set(STALL_KEYS)
+        unknown = (set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(CODEBOOK_KEYS)
+                   - set(STALL_KEYS))
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + CODEBOOK_KEYS + STALL_KEYS})")
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
         lim = session_limit(s, f"session {i}", limit_db, limit_lookahead_ms, limit_hold_ms)
+        amount = session_envelope(s, f"session {i}", envelope, *env)
         rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))      # noqa: E731
         blend = blend_sources(s, f"session {i}", rel) if "blend" in s else None
         if blend is None and s.get("target") is None and s.get("lib") is None:
@@ -289,6 +322,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             e["crossfade_ms"] = xf
         if lim is not None:
             e["limit_db"], e["limit_lookahead_ms"], e["limit_hold_ms"] = lim
+        if amount is not None:
+            e["envelope"] = amount
         if size is not None:
             e["codebook"] = size
         if stall is not None:
@@ -439,7 +474,8 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None, stalls=None)
 def main(argv=None):
     args = build_parser().parse_args(argv)
     sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook,
-                             args.crossfade, args.limit, args.limit_lookahead, args.limit_hold)
+                             args.crossfade, args.limit, args.limit_lookahead, args.limit_hold, args.envelope, args.envelope_floor,
+                             args.envelope_range, args.envelope_radius)
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -476,10 +512,12 @@ def main(argv=None):
                                 **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}),
                                 **(dict(crossfade=True) if any("crossfade_ms" in s for s in sessions) else {}),
                                 **(dict(limiter=True) if any("limit_db" in s for s in sessions) else {}),
+                                **(dict(envelope=True, envelope_floor_db=args.envelope_floor, envelope_range_db=args.envelope_range,
+                                        envelope_radius=args.envelope_radius) if any("envelope" in s for s in sessions) else {}),
                                 **(dict(sparse=True) if args.sparse or any("stall" in s for s in sessions) else {}))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
-                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS if g in s})
+                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()

@@ -65,6 +65,16 @@ def build_parser():
                         help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5)")
     parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
                         help="milliseconds the limiter's gain stays down after a peak (default 20)")
+    parser.add_argument('-env', '--envelope', default=0.0, type=float, metavar="A",
+                        help="envelope follow: the converted voice takes on the source's loudness contour by this amount, 0 (off, the "
+                             "default) to 1 (module/multistream.py \"Envelope follow\"; this build only).  It can lift samples above full "
+                             "scale: use -lim beside it")
+    parser.add_argument('--envelope-floor', default=-60.0, type=float, metavar="DB",
+                        help="the level under which the envelope follow stops telling the two signals apart (default -60)")
+    parser.add_argument('--envelope-range', default=12.0, type=float, metavar="DB",
+                        help="the most the envelope follow turns a frame up or down (default 12)")
+    parser.add_argument('--envelope-radius', default=1, type=int, metavar="FRAMES",
+                        help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
     parser.add_argument('-isr', '--input-sr', default=16000, type=int)
     parser.add_argument('-osr', '--output-sr', default=16000, type=int)
     parser.add_argument('-lsr', '--loopback-sr', default=16000, type=int)
@@ -110,7 +120,9 @@ def main(argv=None):
                            **(dict(gate_db=args.threshold, gate_hold=args.gate_hold) if args.threshold is not None else {}),
                            **(dict(crossfade_ms=args.crossfade) if args.crossfade is not None else {}),
                            **(dict(limit_db=args.limit, limit_lookahead_ms=args.limit_lookahead, limit_hold_ms=args.limit_hold)
-                              if args.limit is not None else {}))
+                              if args.limit is not None else {}),
+                           **(dict(envelope=args.envelope, envelope_floor_db=args.envelope_floor, envelope_range_db=args.envelope_range,
+                                   envelope_radius=args.envelope_radius) if args.envelope else {}))
     if not args.no_graph:
         rt.enable_graph()        # the whole per-chunk device pipeline (~150 launches) captured once, replayed per chunk: same samples
     print("streaming: conversion running (Ctrl-C stops)")

@@ -905,6 +905,40 @@ int alive_ring_push_rows(int16_t* ring, int N, int ld, const int16_t* chunks, in
 int alive_emit_rows(const float* wave, int N, int ld, const int* span_lo, const int* span_len, const unsigned char* take, int16_t* out,
                     int ld_out, void* stream);
 
+/* Envelope follow (csrc/envelope.hip): the converted wave y takes on the loudness contour of the source x that lies beside it sample
+ * for sample (both at 16 kHz: the streaming ring and the decoder's wave of a tick; an utterance and its conversion).  Stateless and OUT
+ * OF PLACE: out[N][ld_y] from y[N][ld_y] and x[N][ld_x].  All pointers are DEVICE pointers; the call allocates nothing, synchronises
+ * nothing and reads nothing on the host; the grid depends on N, ld_y and hop alone (graph-capturable: a captured call serves any amounts
+ * and lengths).  No floating-point atomics; every store is a plain vector store.
+ * Per row, with n = len[row] clamped to [0, min(ld_y, ld_x)] (len NULL: ld_y, clamped likewise), frames of `hop` samples,
+ * F = ceil(n / hop), R = radius, m = amount[row], e = floor_ms (a mean square) and the range [g_lo, g_hi], everything in fp64 with
+ * every operation rounded on its own:
+ *     Sx[f], Sy[f]  sums of squares over [f hop, min((f + 1) hop, n)) in one fixed order: 256 accumulators, accumulator a adds
+ *                   v[f hop + a + 256 j]^2 for ascending j from 0.0 (a missing sample adds +0.0); s[l] = (acc[4l] + acc[4l + 1]) +
+ *                   (acc[4l + 2] + acc[4l + 3]) for l < 64; then s[l] = s[l] + s[l + o] for l < o, o = 32, 16, .., 1; the sum is s[0]
+ *     Px, Py        sums of Sx[t] / Sy[t] over t = a .. b ascending from 0.0, a = max(f - R, 0), b = min(f + R, F - 1)
+ *     Cn            (double)(min((b + 1) hop, n) - a hop)
+ *     q             (Px / Cn + e) / (Py / Cn + e);   rc = min(max(sqrt(q), g_lo), g_hi) if q is finite, else 1.0
+ *     G[f]          1.0 + (double)m * (rc - 1.0)
+ *     g[i]          G[0] for i < hop / 2; G[F - 1] for i >= hop / 2 + (F - 1) hop; otherwise G[f] + (G[f + 1] - G[f]) * w with
+ *                   f = (i - hop / 2) / hop and w = (double)((i - hop / 2) - f hop) / (double)hop
+ *     out[i]        (float)((double)y[i] * g[i]) for i < n; y[i] for i >= n
+ * A row whose amount is not in (0, 1] (0, a NaN, 1.5) or whose n is 0 is copied bit for bit.  A NaN in either signal, or an inf in x,
+ * makes q non-finite in the frames within R of it: those stay at G = 1 and no other frame changes (an inf in y alone gives q = 0, so
+ * g_lo, and the sample stays infinite).  A row's result does not depend on N, on the other rows or on the tiling.  Bitwise
+ * tools/envelope_ref.py.
+ *   The grid is tiles of ALIVE_ENVELOPE_TILE frames x rows, 256 threads; a tile recomputes the frame sums of radius + 1 frames on each
+ *   side, so an `out` that overlaps y or x is refused (a tile's halo is another tile's output).
+ *   gain_minmax float [N][2] or NULL: the row's smallest and largest G[f] over f < F as floats, (1, 1) for a copied row (filled with
+ *   (+inf, 0) first, then integer atomic min / max on the floats' bits: every G is > 0, so the order of the bits is the order of the
+ *   values and the result does not depend on the order).
+ *   0 < N <= 65535; ld_y, ld_x > 0; hop even in [2, 1024]; 0 <= radius <= ALIVE_ENVELOPE_MAX_RADIUS; floor_ms > 0;
+ *   0 < g_lo <= 1 <= g_hi; all three finite. */
+#define ALIVE_ENVELOPE_TILE 16
+#define ALIVE_ENVELOPE_MAX_RADIUS 4
+int alive_envelope_waves(float* out, const float* y, int ld_y, const float* x, int ld_x, int N, const int* len, const float* amount,
+                         int hop, int radius, double floor_ms, double g_lo, double g_hi, float* gain_minmax, void* stream);
+
 /* Voice codebooks (csrc/codebook.hip; module/codebook.py build_codebook): the device passes of one k-means iteration over a voice's
  * rows that are not the search.  The assignment of a row is the strict search's top-1 against the centroids (alive_knn_search_strict)
  * and the inverted index a stable sort of the assignment; both are the caller's.  All pointers are DEVICE pointers; no call allocates,

@@ -30,6 +30,11 @@ and 20 ms hold (limit_tick_*: one more launch of one block per session, alive_li
 the sessions down in its last tick (limit_db_min / _median / _max: 20 log10 of the smallest gain, on SYNTHETIC weights and input), and
 the converter built without the limiter a second time (limit_off_again_tick_*): the spread between its two measurements is the
 yardstick for the limiter's cost.
+--envelope adds the graph tick p50 / p99 of an envelope=True converter with every session following at amount 1 (envelope_tick_*: one
+more launch pair after the decoder, alive_envelope_waves, csrc/envelope.hip) beside the plain converter, both alive in the one process
+and timed in alternating rounds (envelope_off_tick_*; the medians over the rounds, and the spread of the plain converter's rounds as the
+yardstick), the call's own time by device events around 200 back-to-back eager calls at the tick's shapes (envelope_call_us, its fill
+launch included) with the 12 B L bytes it moves (envelope_call_bytes), and the gains of the last tick (envelope_db_min / _max).
 --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
 one more 50 000-row voice added between two ticks, once on a default pool (the add re-packs the pool and the next tick
 re-captures) and once on a reserved pool of 65 x 50 000 rows (VoicePool(capacity=...): alive_pool_append into the table in
@@ -48,7 +53,7 @@ grouped search alone, event-timed, over the segment lengths that tick left in se
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch]
-                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--out multistream.json]
+                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--out multistream.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
     python tools/bench_multistream.py --sparse [--batches 128,1024] [--ticks 40] [--out profiles/multistream_sparse_bench.json]
 """
@@ -263,6 +268,8 @@ def main():
                                                              "10 ms, and the plain converter a second time")
     ap.add_argument("--limit", action="store_true", help="also time a limiter=True converter, every session limiting at -12 dBFS, "
                                                          "and the plain converter a second time")
+    ap.add_argument("--envelope", action="store_true", help="also time an envelope=True converter, every session following at amount "
+                                                            "1, against the plain converter in alternating rounds, and the call alone")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
                                                          "default and on a reserved pool")
     ap.add_argument("--sparse", action="store_true", help="the sparse-ticks leg alone: dense against sparse(=True) converters, "
@@ -423,6 +430,40 @@ def main():
                     p50, p99 = time_ticks(again, B, chunk, args.ticks, args.warmup + bs + 1, 300)
                     rec["limit_off_again_tick_p50_ms"], rec["limit_off_again_tick_p99_ms"] = round(p50, 3), round(p99, 3)
                     del again
+                if args.envelope:
+                    both = {}
+                    for name, kw, sess in (("envelope_off", {}, {}), ("envelope", dict(envelope=True), dict(envelope=1.0))):
+                        c = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, **kw)
+                        for s in range(B):
+                            c.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, **sess)
+                        c.enable_graph()
+                        both[name] = c
+                    times = {name: [] for name in both}
+                    for _ in range(5):                         # alternating rounds in the one process
+                        for name, c in both.items():
+                            times[name].append(time_ticks(c, B, chunk, args.ticks, args.warmup + bs + 1, 300))
+                    for name, ts in times.items():
+                        rec[f"{name}_tick_p50_ms"] = round(float(np.median([t[0] for t in ts])), 3)
+                        rec[f"{name}_tick_p99_ms"] = round(float(np.median([t[1] for t in ts])), 3)
+                        rec[f"{name}_tick_p50_rounds_ms"] = [round(t[0], 3) for t in ts]
+                    ec = both["envelope"]
+                    db = np.array(ec.envelope_db())
+                    assert np.isfinite(db).all() and ec.captures == 1, (db, ec.captures)
+                    rec["envelope_db_min"], rec["envelope_db_max"] = round(float(db[:, 0].min()), 2), round(float(db[:, 1].max()), 2)
+                    ld = ec._env_out.shape[1]
+                    g = torch.Generator(device="cuda").manual_seed(5)
+                    y, x = (torch.randn(B, ld, device="cuda", generator=g) * 0.1 for _ in range(2))
+                    for _ in range(10):
+                        ec._follow(y, x)
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    for _ in range(200):
+                        ec._follow(y, x)
+                    b.record()
+                    torch.cuda.synchronize()
+                    rec["envelope_call_us"] = round(a.elapsed_time(b) * 1e3 / 200, 2)
+                    rec["envelope_call_bytes"] = 12 * B * ld
+                    del both, ec
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
                 rows.append(rec)
