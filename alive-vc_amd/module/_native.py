@@ -166,6 +166,7 @@ PROTOTYPES = {
     "alive_envelope_waves": (_I, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _D, _D, _D, _VP, _VP]),
     "alive_ring_push_rows": (_I, [_VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "alive_emit_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I, _VP]),
+    "alive_conceal_rows": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP]),
     "alive_codebook_workspace_bytes": (_SZ, [_I64, _I64]),
     "alive_codebook_update": (_I, [_VP, _I64, _I, _VP, _VP, _I64, _VP, _VP, _VP]),
     "alive_codebook_stats": (_I, [_VP, _VP, _VP, _I64, _VP, _VP, _VP]),

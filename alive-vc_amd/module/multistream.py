@@ -109,8 +109,8 @@ key of the result and costs no search (its list rows run at segment length 0, as
 the encoders and the decoder still run over all B rows, and what they compute for an absent row is discarded.  The contract: a
 session's emitted stream depends only on the sequence of chunks it supplied, bit for bit -- not on the ticks they arrived in, nor on
 what the other sessions did.  An absent tick is a STALL of the session: its latency to the wall clock grows by one tick, no audio is
-lost or repeated (no concealment audio is made up for it; a chunk that was lost and should advance the session's clock is a chunk of
-zeros).  step({}), or a tick on which no present slot emits, does no network work; present filling slots still have their chunk pushed.
+lost or repeated (no concealment audio is made up for it; a chunk that was LOST and should advance the session's clock is named in step(...,
+lost=): see "Lost chunks" below).  step({}), or a tick on which no present slot emits, does no network work; present filling slots still have their chunk pushed.
 The rings live on the device, int16 [B, ld_in] in time order (ring_dev; `ring` is None, rings() reads them back): the chunks go up
 through one pinned staging buffer [B, longest chunk] in one copy, present and emit in a second small one, and alive_ring_push_rows --
 once per tick, OUTSIDE the captured step and outside what the bf16 repeat runs again, so a repeated tick starts from the input it
@@ -141,6 +141,27 @@ from tick to tick, so two successive decodes get slightly different gains at a s
 faded by crossfade.  The gain can lift a sample above 1.0: use the limiter beside it.  envelope_db() reads the latest tick's smallest
 and largest frame gain per slot back.  follow_envelope is the offline form (the same call over whole utterances).  The defaults (R = 1:
 60 ms, floor -60 dB, range 12 dB) are design choices: with no trained weights, how they sound is unmeasured.
+
+Lost chunks: a stall costs nothing, but a server meets another event more often: a chunk that never arrives while the session's clock
+must go on.  Pushing zeros for it puts 10 ms of digital silence with two hard edges into voiced speech, and the hole is re-encoded on
+every one of the buffersize ticks it spends in the ring.  A sparse converter built with conceal=True (csrc/conceal.hip) fills the hole
+at the input edge instead, by waveform substitution in the style of G.711 Appendix I: step(chunks, lost=[slots]) names the open slots
+whose chunk did not arrive; their clock advances exactly as if a chunk had been supplied (count, ring, phase, emission; they are keys of
+the result).  alive_conceal_rows, launched in front of alive_ring_push_rows on the same stream -- outside the captured step and outside
+what the bf16 repeat runs again -- writes the made-up chunk into the uploaded chunk buffer and the push moves it into the ring: at the
+first lost chunk of a run it finds the pitch period P in the ring's newest samples (lags of 60 - 400 Hz, normalised correlation over
+20 ms in exact integer sums, the lowest lag on a tie) and keeps the last period as the run's template, its last quarter faded into the
+period before; every lost chunk repeats the template at full level for conceal_hold_ms and then fades it to exact zeros over
+conceal_fade_ms (the ring, which by then holds made-up samples, is never searched again during the run); the first chunk that arrives
+again has its first conceal_recover_ms faded in from the continuation.  The state is the session's: _conceal_state [B, 2] = (samples
+made up so far in this run, P) and conceal_tmpl; open and close clear it, an absent tick leaves it standing.  The networks see a
+plausible continuation and nothing after the push changes.  A session opened or set with conceal=False that loses a chunk gets zeros.
+The host mirrors which slots are in a run: a tick with no lost and no recovering slot launches exactly what it did, and a converter
+built without conceal allocates nothing new, launches exactly what it did and refuses lost=.  A session needs a ring of at least max(W +
+Lmax, 2 Lmax) samples (587 at 16 kHz: -c 160 -b 4 just fits).  Everything is device arrays: toggling never re-captures.
+conceal_state() reads the per-slot (run samples, period) back.  tools/conceal_ref.py restates the arithmetic bit for bit.  The defaults
+(10 ms, 50 ms, 5 ms) are design choices: with no trained weights, what this does to perceived quality is unmeasured.  Concealment audio
+for a STALL, concealing in feature space, jitter buffers and a voicing decision (the best lag is always used) are not part of it.
 """
 import numpy as np
 import torch
@@ -1059,6 +1080,69 @@ def ring_push_rows_(ring, chunks, chunk_len, ring_len, present, x, seg_len=None,
     return ring
 
 
+CONCEAL_MAX_SPAN, CONCEAL_QMAX = 4096, 1 << 30      # ALIVE_CONCEAL_MAX_SPAN, ALIVE_CONCEAL_QMAX (include/alive_vc.h)
+
+
+def conceal_rows_(ring, ring_len, chunks, chunk_len, present, lost, on, consts, state, tmpl):
+    """alive_conceal_rows in place on chunks int16 [N, ld_chunk]: the rows with lost != 0 get their made-up chunk, the present rows in
+    a run (state[n, 0] > 0) have the head of their chunk faded in from the continuation; ring int16 [N, ld] is read only.  present /
+    lost / on: [N] bytes; consts int32 [6, N]: lag_lo, lag_hi, window, hold, fade, recover per row; state int32 [N, 2] and tmpl int16
+    [N, ld_tmpl] are the rows' state"""
+    if ring.dim() != 2 or ring.dtype != torch.int16 or not ring.is_contiguous():
+        raise ValueError("conceal_rows_: ring must be contiguous int16 [N, ld]")
+    n, ld = ring.shape
+    if chunks.dtype != torch.int16 or chunks.dim() != 2 or chunks.shape[0] != n or not chunks.is_contiguous():
+        raise ValueError("conceal_rows_: chunks must be contiguous int16 [N, ld_chunk]")
+    if tmpl.dtype != torch.int16 or tmpl.dim() != 2 or tmpl.shape[0] != n or not tmpl.is_contiguous():
+        raise ValueError("conceal_rows_: tmpl must be contiguous int16 [N, ld_tmpl]")
+    for name, t in (("present", present), ("lost", lost), ("on", on)):
+        if t.numel() != n or t.element_size() != 1:
+            raise ValueError(f"conceal_rows_: {name} must be [N] bytes")
+    for name, t, shape in (("chunk_len", chunk_len, (n,)), ("ring_len", ring_len, (n,)), ("consts", consts, (6, n)),
+                           ("state", state, (n, 2))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"conceal_rows_: {name} must be contiguous int32 {list(shape)}")
+    c = [consts[i].data_ptr() for i in range(6)]
+    nat.check(nat.lib().alive_conceal_rows(nat.ptr(ring), n, ld, nat.ptr(ring_len), nat.ptr(chunks), chunks.shape[1], nat.ptr(chunk_len),
+                                           nat.ptr(present), nat.ptr(lost), nat.ptr(on), c[0], c[1], c[2], c[3], c[4], c[5],
+                                           nat.ptr(state), nat.ptr(tmpl), tmpl.shape[1], nat.stream()), "alive_conceal_rows")
+    return chunks
+
+
+def check_conceal_ms(hold_ms=10.0, fade_ms=50.0, recover_ms=5.0):
+    """the concealment's three durations as floats.  ValueError unless each is a finite number of milliseconds >= 0 (not a bool)"""
+    out = []
+    for name, v in (("conceal_hold_ms", hold_ms), ("conceal_fade_ms", fade_ms), ("conceal_recover_ms", recover_ms)):
+        if not _number(v) or not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"{name}={v!r} must be a finite number of milliseconds >= 0")
+        out.append(float(v))
+    return tuple(out)
+
+
+def conceal_geometry(rate, chunk_len, ring_len, hold_ms=10.0, fade_ms=50.0, recover_ms=5.0, check=True):
+    """a session's concealment constants in its own samples -> (lag_lo, lag_hi, window, hold, fade, recover), the rows of
+    alive_conceal_rows' consts: lags of 60 - 400 Hz (rate // 400 .. ceil(rate / 60)), a 20 ms window (rate // 50), hold =
+    round(hold_ms rate / 1000), fade = max(1, round(fade_ms rate / 1000)), recover = min(round(recover_ms rate / 1000), chunk_len).
+    check: ValueError (naming both numbers) unless the ring holds need = max(window + lag_hi, 2 lag_hi) samples and need fits the
+    kernel's CONCEAL_MAX_SPAN"""
+    hold_ms, fade_ms, recover_ms = check_conceal_ms(hold_ms, fade_ms, recover_ms)
+    r, cl, rl = int(rate), int(chunk_len), int(ring_len)
+    lo, hi, w = r // 400, -(-r // 60), r // 50
+    hold, fade = int(round(hold_ms * r / 1000.0)), max(1, int(round(fade_ms * r / 1000.0)))
+    rec = min(int(round(recover_ms * r / 1000.0)), cl)
+    if max(hold, fade) > CONCEAL_QMAX:
+        raise ValueError(f"conceal_hold_ms={hold_ms!r} / conceal_fade_ms={fade_ms!r} are {hold} / {fade} samples at {r} Hz: at most "
+                         f"{CONCEAL_QMAX}")
+    need = max(w + hi, 2 * hi)
+    if check and (lo < 1 or need > CONCEAL_MAX_SPAN):
+        raise ValueError(f"concealment at {r} Hz would search {need} samples (lags {lo} .. {hi}): the kernel takes lags >= 1 and at "
+                         f"most {CONCEAL_MAX_SPAN} samples")
+    if check and rl < need:
+        raise ValueError(f"concealment at {r} Hz needs a ring of at least {need} samples (a 20 ms window of {w} and the longest lag of "
+                         f"{hi}); the session's ring holds {rl} ({cl}-sample chunks): use a larger buffersize, or conceal=False")
+    return lo, hi, w, hold, fade, rec
+
+
 def emit_rows_(wave, span_lo, span_len, take, out):
     """alive_emit_rows: out int16 [N, ld_out] <- the spans [span_lo, span_lo + span_len) of the taken rows (take: [N] bytes) of wave
     float32 [N, ld] as alive_float_to_pcm16 forms them, zeros everywhere else"""
@@ -1448,7 +1532,7 @@ def db_scale(db):
 
 
 _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold",
-           "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope")
+           "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope", "conceal")
 
 
 class MultiStreamConverter:
@@ -1458,12 +1542,24 @@ class MultiStreamConverter:
     limiter = False                    # (likewise: whether the tick carries the limiter kernel)
     sparse = False                     # (likewise: whether the rings live on the device and sessions may sit ticks out)
     envelope = False                   # (likewise: whether the tick carries the envelope kernel)
+    conceal = False                    # (likewise: whether lost chunks are concealed in front of the ring push; needs sparse)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
                  auto_pitch_half_life=10.0, auto_pitch_prior=0.5, gate=False, gate_lookahead=None, crossfade=False,
                  limiter=False, limit_history=0.05, sparse=False, envelope=False, envelope_floor_db=-60.0,
-                 envelope_range_db=12.0, envelope_radius=1):
+                 envelope_range_db=12.0, envelope_radius=1, conceal=False, conceal_hold_ms=10.0, conceal_fade_ms=50.0,
+                 conceal_recover_ms=5.0):
+        if not isinstance(conceal, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: conceal must be a bool, got {conceal!r}")
+        if conceal:                        # (checked before anything is built)
+            if not (isinstance(sparse, (bool, np.bool_)) and sparse):
+                raise ValueError("MultiStreamConverter: conceal=True needs sparse=True: lost chunks are concealed in the device rings "
+                                 "of a sparse converter")
+            try:
+                conceal_ms = check_conceal_ms(conceal_hold_ms, conceal_fade_ms, conceal_recover_ms)
+            except ValueError as e:
+                raise ValueError(f"MultiStreamConverter: {e}") from None
         if not isinstance(envelope, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: envelope must be a bool, got {envelope!r}")
         if envelope:                       # (checked before anything is built)
@@ -1674,8 +1770,9 @@ class MultiStreamConverter:
             self.ring_dev = torch.zeros(B, up8(ld_in), dtype=torch.int16, device=dev)
             self._stage = torch.zeros(B, up8(max(cs)), dtype=torch.int16).pin_memory()
             self._chunks_dev = torch.zeros(B, up8(max(cs)), dtype=torch.int16, device=dev)
-            self._flags_host = torch.zeros(2, B, dtype=torch.bool).pin_memory()
-            self._flags = torch.zeros(2, B, dtype=torch.bool, device=dev)
+            rows = 3 if conceal else 2                     # (conceal: `lost`, a third row of the same copy)
+            self._flags_host = torch.zeros(rows, B, dtype=torch.bool).pin_memory()
+            self._flags = torch.zeros(rows, B, dtype=torch.bool, device=dev)
             self.present, self.emit = self._flags[0], self._flags[1].view(B, 1)
             self._staged = None                            # the event after the latest upload from the two pinned buffers
             self.chunk_len = torch.full((B,), self.chunk, **i32)
@@ -1689,6 +1786,23 @@ class MultiStreamConverter:
             self._pcm = torch.zeros(B, up8(max(self._span(c)[1] for c in cs)), dtype=torch.int16, device=dev)
             self._pcm_host = torch.zeros(self._pcm.shape, dtype=torch.int16).pin_memory()
             self.pushes = 0                                # (how many ticks pushed the rings: one per step with a chunk)
+        # conceal: alive_conceal_rows runs in front of the push on the ticks that have a lost or a recovering slot (the host mirrors
+        # which slots are in a run: _conceal_run); per row, conceal_on switches the session's concealment and _conceal_consts holds
+        # its lags, window and durations in its own samples.  _conceal_state / conceal_tmpl are the session's, like phi
+        self.conceal = bool(conceal)
+        if self.conceal:
+            self._conceal_ms = conceal_ms
+            self.lost = self._flags[2]
+            geo = {r: conceal_geometry(r, self._chunk_at(r), self._chunk_at(r) * self.buffersize, *conceal_ms, check=False)
+                   for r in rates}
+            self._conceal_closed = torch.tensor(geo[int(input_sr)], dtype=torch.int32)
+            self.conceal_on = torch.zeros(B, dtype=torch.bool, device=dev)
+            self._conceal_consts = self._conceal_closed.view(6, 1).repeat(1, B).to(dev).contiguous()
+            self._conceal_state = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+            self.conceal_tmpl = torch.zeros(B, -(-max(g[1] for g in geo.values()) // 8) * 8, dtype=torch.int16, device=dev)
+            self._conceal_run = [False] * B
+            self._conceal_host = [False] * B               # (the sessions' switches, for the mirror)
+            self.conceals = 0                              # (how many ticks launched alive_conceal_rows)
         self._graph = None
         self._graph_pool_version = None
         self.captures = 0
@@ -1786,6 +1900,38 @@ class MultiStreamConverter:
             raise ValueError(f"slot {slot}: envelope={a!r} needs a converter built with MultiStreamConverter(..., envelope=True)")
         return a
 
+    def _session_conceal(self, slot, p, rate=None):
+        """a session's concealment -> (on, consts) at its rate, None in a converter without conceal; checked against the converter.
+        conceal None: the converter's (on in a conceal=True converter)"""
+        v = p.get("conceal")
+        if v is not None and not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"slot {slot}: conceal must be a bool or None, got {v!r}")
+        if not self.conceal:
+            if v:
+                raise ValueError(f"slot {slot}: conceal=True needs a converter built with MultiStreamConverter(..., sparse=True, "
+                                 "conceal=True)")
+            return None
+        on = True if v is None else bool(v)
+        rate = int(self.rate[slot] if rate is None else rate)
+        cs = self._chunk_at(rate)
+        try:
+            return on, conceal_geometry(rate, cs, cs * self.buffersize, *self._conceal_ms, check=on)
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+
+    def _conceal_clear(self, slot):
+        """the slot is in no run any more: the device state and the host's mirror"""
+        if self.conceal:
+            self._conceal_state[slot] = 0
+            self._conceal_run[slot] = False
+
+    def conceal_state(self):
+        """the concealment runs after the latest tick, a list of B pairs (samples made up so far in the run, its period in samples);
+        (0, 0) for a slot that is in no run, or closed.  One host read"""
+        if not self.conceal:
+            raise ValueError("conceal_state needs a converter built with MultiStreamConverter(..., sparse=True, conceal=True)")
+        return [(q, P) if self.is_open[b] and q > 0 else (0, 0) for b, (q, P) in enumerate(self._conceal_state.tolist())]
+
     def _session_gate(self, slot, p):
         """a session's gate settings -> (on, thr_ms, hold_ticks), checked against the converter"""
         db, hold = p.get("gate_db"), p.get("gate_hold", 0.2)
@@ -1806,6 +1952,7 @@ class MultiStreamConverter:
         xlen = self._session_seam(slot, p, rate)
         limit = self._session_limit(slot, p, rate)
         env = self._session_envelope(slot, p)
+        con = self._session_conceal(slot, p, rate)
         names, weights = blend_spec(p["voice"], self.pool, k, self.S)
         world = p["world_pitch"]
         if not isinstance(world, (bool, np.bool_)):
@@ -1849,6 +1996,9 @@ class MultiStreamConverter:
             self.look[slot], self.hold[slot], self.ceil[slot] = limit
         if self.envelope:
             self.env_amount[slot] = env
+        if self.conceal:
+            self.conceal_on[slot], self._conceal_host[slot] = con[0], con[0]
+            self._conceal_consts[:, slot] = torch.tensor(con[1], dtype=torch.int32)
 
     def _write_segments(self, slot, names):
         """the slot's rows of seg_lo / seg_len from where its voices lie in the pool now"""
@@ -1915,7 +2065,7 @@ class MultiStreamConverter:
 
     def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None,
              auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0,
-             limit_hold_ms=20.0, envelope=0.0):
+             limit_hold_ms=20.0, envelope=0.0, conceal=None):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
@@ -1930,7 +2080,10 @@ class MultiStreamConverter:
         no limiter, the int16 edge wraps); limit_lookahead_ms: how long before a peak the gain starts to fall (and after the hold,
         how long it takes to come back), at most the session's chunk; limit_hold_ms: how long the gain stays down after a peak.
         envelope (above 0: needs an envelope=True converter): how far the converted wave follows the loudness contour of the session's
-        input, from 0 (the decoder's own level) to 1 (the source's smoothed frame level, within the converter's range)"""
+        input, from 0 (the decoder's own level) to 1 (the source's smoothed frame level, within the converter's range).
+        conceal (None: the converter's, on in a conceal=True converter; True needs one): whether the session's lost chunks (step(...,
+        lost=)) are concealed by waveform substitution; False: they are chunks of zeros.  The session's ring must hold the search:
+        ValueError otherwise"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
@@ -1938,7 +2091,7 @@ class MultiStreamConverter:
                              "MultiStreamConverter(..., rates=...)")
         p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch,
                  k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold, crossfade_ms=crossfade_ms, limit_db=limit_db,
-                 limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms, envelope=envelope)
+                 limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms, envelope=envelope, conceal=conceal)
         self._apply(slot, p, rate)                            # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -1954,11 +2107,12 @@ class MultiStreamConverter:
             self.stored[slot] = 0                             # never fade from another session's tail
         if self.limiter:
             self._limit_reset(slot)                           # a new stream: no peak behind it
+        self._conceal_clear(slot)                             # a new stream: no run behind it
         return self
 
     def set(self, slot, **params):
         """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
-        gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms, limit_hold_ms, envelope; the gate's state, the saved tail and the
+        gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms, limit_hold_ms, envelope, conceal; the gate's state, the saved tail and the
         limiter's history are kept: a longer crossfade fades over what the tail holds this tick and in full from the next, and a
         limiter switched on or retuned sees the required gains of the samples already emitted).
         The running source register is kept: a new voice changes the target only, and auto_pitch=True after False resumes from
@@ -2011,6 +2165,10 @@ class MultiStreamConverter:
         if self.envelope:
             self.env_amount[slot] = 0.0
             self.env_minmax[slot] = 1.0
+        if self.conceal:
+            self.conceal_on[slot], self._conceal_host[slot] = False, False
+            self._conceal_consts[:, slot] = self._conceal_closed
+            self._conceal_clear(slot)
         self._set_rate(slot, int(self.input_sr))             # a closed slot: the converter's own rate, silence
         return self
 
@@ -2235,7 +2393,26 @@ class MultiStreamConverter:
         torch.cuda.current_stream(self.device).synchronize()
         return self._pcm_host.numpy()
 
-    def _step_sparse(self, chunks):
+    def _lost_slots(self, chunks, lost):
+        """step()'s `lost` -> the sorted list of its slots: open slots whose chunk did not arrive, none of them a key of `chunks`;
+        ValueError otherwise, and for any lost slot in a converter built without conceal.  Host only"""
+        lost = list(lost) if lost is not None else []
+        if not lost:
+            return []
+        if not self.conceal:
+            raise ValueError("step(..., lost=) needs a converter built with MultiStreamConverter(..., sparse=True, conceal=True): "
+                             "without one a lost chunk is a chunk of zeros")
+        out = set()
+        for s in lost:
+            s = self._slot(s)
+            if not self.is_open[s]:
+                raise ValueError(f"a lost chunk for slot {s}, which is not open")
+            if s in chunks:
+                raise ValueError(f"slot {s} is named in both chunks and lost: its chunk arrived or it did not")
+            out.add(s)
+        return sorted(out)
+
+    def _step_sparse(self, chunks, lost=()):
         """step() of a sparse converter: any subset of the open slots"""
         taken = {}
         for s, c in chunks.items():
@@ -2243,8 +2420,9 @@ class MultiStreamConverter:
             if not self.is_open[s]:
                 raise ValueError(f"a chunk for slot {s}, which is not open")
             taken[int(s)] = self._chunk_of(s, c)
-        out = {s: None for s in chunks}
-        if not taken:                                         # nobody sent anything: nothing moves
+        lost = self._lost_slots(taken, lost)
+        out = {s: None for s in list(chunks) + lost}
+        if not taken and not lost:                            # nobody sent anything: nothing moves
             return out
         if self._staged is not None:
             self._staged.synchronize()                        # (the pinned buffers are free again: the latest upload has been made)
@@ -2255,6 +2433,16 @@ class MultiStreamConverter:
             self.count[s] += 1
             flags[0, s] = True
             flags[1, s] = self.count[s] > self.buffersize
+        conceal = bool(lost)                                  # does this tick have a lost or a recovering slot?
+        for s in taken:
+            if self.conceal and self._conceal_run[s]:         # the first chunk after a run: faded in on the device
+                conceal, self._conceal_run[s] = True, False
+        for s in lost:                                        # the clock goes on as if a chunk had come: the device makes one up
+            stage[s, :self.slot_chunk[s]] = 0                 # (zeros if the session does not conceal)
+            self.count[s] += 1
+            flags[0, s] = flags[2, s] = True
+            flags[1, s] = self.count[s] > self.buffersize
+            self._conceal_run[s] = self._conceal_host[s]
         emit = flags[1].copy()
         if self._reserved:
             self._follow_pool()                               # seg_len as the pool lies now, before the push masks it
@@ -2263,6 +2451,10 @@ class MultiStreamConverter:
         self._staged = torch.cuda.Event()
         self._staged.record(torch.cuda.current_stream(self.device))
         # once per tick, outside the captured step and outside what the bf16 repeat runs again
+        if conceal:                                           # the lost rows' chunks are made up, the recovering rows' heads faded in
+            conceal_rows_(self.ring_dev, self.ring_len, self._chunks_dev, self.chunk_len, self.present, self.lost, self.conceal_on,
+                          self._conceal_consts, self._conceal_state, self.conceal_tmpl)
+            self.conceals += 1
         ring_push_rows_(self.ring_dev, self._chunks_dev, self.chunk_len, self.ring_len, self.present, self._in, self.seg_len,
                         self.seg_len_tick, self.S, self.world_on if self.world_pitch else None, self.world_tick)
         self.pushes += 1
@@ -2277,20 +2469,23 @@ class MultiStreamConverter:
         o = self._emit_spans(self._run())
         if guarded and ops.f16_saturations(reset=True) > 0:
             o = self._emit_spans(self._repeat_wave(saved_phi, saved_reg, saved_gate, saved_seam))
-        for s in taken:
+        for s in list(taken) + lost:
             if emit[s]:
                 out[s] = o[s, :2 * (self.slot_chunk[s] // 2)].copy()
         return out
 
-    def step(self, chunks):
+    def step(self, chunks, lost=()):
         """{slot: int16 chunk} for EVERY open slot -> {slot: converted centre chunk (int16) or None while its ring fills}.
         A session at rate r sends and receives chunks of chunk_r = chunk * r / input_sr samples; its output is cut at its own
         centre, buffersize * chunk_r // 2 +- chunk_r // 2 (realtime_inference.py at that rate), so an odd chunk_r (441 at 44.1 kHz
         with 160-sample chunks at 16 kHz) returns chunk_r - 1 samples per tick, as the reference does.
         A sparse converter takes the chunks of ANY subset of its open slots: a slot without one sits the tick out (nothing of it
-        moves, it is not a key of the result), see "Sparse ticks" in the module docstring."""
+        moves, it is not a key of the result), see "Sparse ticks" in the module docstring.
+        lost (a sparse converter built with conceal=True): open slots whose chunk did not arrive while their clock must go on; they
+        advance exactly as if a chunk had been supplied and are keys of the result, see "Lost chunks" there."""
         if self.sparse:
-            return self._step_sparse(chunks)
+            return self._step_sparse(chunks, lost)
+        self._lost_slots(chunks, lost)                        # (a dense converter has no conceal: any lost slot is refused)
         for s in chunks:
             self._slot(s)
             if not self.is_open[s]:

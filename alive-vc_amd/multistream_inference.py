@@ -35,6 +35,12 @@ The sessions file is a JSON list; each entry:
    "stall": [12, 13, 40],                 optional, a list of distinct integers >= 0: ticks, counted from tick 0 of the run, at which
                                           the session supplies nothing (a late client; module/multistream.py "Sparse ticks").  Its
                                           remaining input moves later by one tick per stall, and its slot closes after its last chunk
+   "lose": [20, 21],                      optional, a list of distinct integers >= 0: ticks, counted from tick 0 of the run, at which
+                                          the session's next input chunk is consumed and DROPPED: it never arrives, but the session's
+                                          clock goes on (module/multistream.py "Lost chunks"), so the output keeps its length -- this is
+                                          not a stall.  A tick named in both "lose" and "stall" is an error
+   "conceal": true,                       optional, a JSON bool (default: on in a concealing converter): whether the session's lost
+                                          chunks are concealed by waveform substitution; false: they are chunks of zeros
    "sr": 48000,                           optional: the session's sample rate (default -isr / -osr)
    "output": "a_out.wav"}                 optional: default <outdir>/<index>_<input name>.wav
 A session's slot opens at its start tick, gets one chunk per tick while its input lasts and closes after its last chunk.
@@ -66,6 +72,10 @@ The converter is built sparse (rings on the device, sessions may sit ticks out) 
 "stall": a file without the key, run without the flag, runs as before.  A stalled session's output is byte for byte what it is
 without the stalls, and --sparse alone writes byte for byte what a run without it writes.
 
+The converter conceals lost chunks (and is then sparse) only under --conceal or if some session has a "lose" or a true "conceal": a
+file without the keys, run without the flag, runs as before; "lose": [] and --conceal alone write byte for byte what a run without
+them writes.  --conceal-hold / --conceal-fade / --conceal-recover set the three durations for all sessions.
+
 --pool-rows N: a RESERVED pool of N rows (module/multistream.py VoicePool(capacity=N)) instead of one packed before tick 0: each
 voice is enrolled from its sources at the first tick some session needs it (multistream.enrol_voice, while the other sessions
 run) and removed after the last session on it closes, so N need only cover the voices alive at one time (enrol_plan lists the
@@ -88,7 +98,8 @@ from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
 from module.multistream import (MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
-                                check_crossfade_ms, check_envelope, check_limit, gate_hold_ticks, gate_thr_ms, measure_register)
+                                check_conceal_ms, check_crossfade_ms, check_envelope, check_limit, gate_hold_ticks, gate_thr_ms,
+                                measure_register)
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
@@ -100,6 +111,8 @@ LIMIT_KEYS = ("limit_db", "limit_lookahead_ms", "limit_hold_ms")      # likewise
 ENVELOPE_KEYS = ("envelope",)            # likewise; a loaded session carries it only when it follows (an amount above 0)
 CODEBOOK_KEYS = ("codebook",)            # taken per session too; a loaded session carries it only when its voice is condensed
 STALL_KEYS = ("stall",)                  # a loaded session carries it only when its entry has the key (the converter is then sparse)
+LOSE_KEYS = ("lose",)                    # likewise (the converter is then sparse and conceals)
+CONCEAL_KEYS = ("conceal",)              # likewise: the session's own switch
 
 
 def build_parser():
@@ -152,6 +165,15 @@ def build_parser():
     parser.add_argument('--sparse', action='store_true',
                         help="build the converter sparse: the rings live on the device and a session may sit ticks out (implied by a "
                              "session's \"stall\")")
+    parser.add_argument('--conceal', action='store_true',
+                        help="build the converter sparse and concealing: a session's lost chunks (\"lose\") are filled by waveform "
+                             "substitution unless its \"conceal\" says otherwise (implied by a session's \"lose\")")
+    parser.add_argument('--conceal-hold', default=10.0, type=float, metavar="MS",
+                        help="milliseconds a concealed loss repeats the last pitch period at full level (default 10)")
+    parser.add_argument('--conceal-fade', default=50.0, type=float, metavar="MS",
+                        help="milliseconds over which a longer loss then fades to silence (default 50)")
+    parser.add_argument('--conceal-recover', default=5.0, type=float, metavar="MS",
+                        help="milliseconds over which the first chunk after a loss is faded in from the concealment (default 5)")
     parser.add_argument('--no-graph', action='store_true',
                         help="launch the per-tick device pipeline kernel by kernel instead of replaying one captured hipGraph")
     return parser
@@ -250,6 +272,30 @@ def session_stall(s, where):
     return tuple(sorted(stall))
 
 
+def session_lose(s, where):
+    """an entry's "lose" -> the sorted tuple of its ticks, or None for a session without the key (a JSON null counts as none): a list
+    of distinct integers >= 0 (no bools, no floats), none of them one of its "stall" ticks; ValueError otherwise.  Host only"""
+    lose = s.get("lose")
+    if lose is None:
+        return None
+    if not isinstance(lose, list) or any(isinstance(t, bool) or not isinstance(t, int) or t < 0 for t in lose):
+        raise ValueError(f"{where}: \"lose\" must be a list of distinct integers >= 0 (ticks of the run), got {lose!r}")
+    if len(set(lose)) != len(lose):
+        raise ValueError(f"{where}: \"lose\" names a tick twice: {lose!r}")
+    both = sorted(set(lose) & set(session_stall(s, where) or ()))
+    if both:
+        raise ValueError(f"{where}: ticks {both} are named in both \"lose\" and \"stall\": a tick's chunk is late or it is lost")
+    return tuple(sorted(lose))
+
+
+def session_conceal(s, where):
+    """an entry's "conceal" -> a bool, or None for a session without the key (a JSON null counts as none); ValueError otherwise"""
+    v = s.get("conceal")
+    if v is not None and not isinstance(v, bool):
+        raise ValueError(f"{where}: \"conceal\" must be true or false, got {v!r}")
+    return v
+
+
 def supply_ticks(start, n_chunks, stall=None):
     """the ticks at which a session that joins at tick `start` supplies its n_chunks chunks, in order: every tick from `start` on
     that is not one of its `stall` ticks (without stalls: start .. start + n_chunks - 1).  Host only"""
@@ -263,14 +309,19 @@ def supply_ticks(start, n_chunks, stall=None):
 
 def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None, crossfade_ms=None, limit_db=None,
                   limit_lookahead_ms=5.0, limit_hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0,
-                  envelope_radius=1):
+                  envelope_radius=1, conceal_hold_ms=10.0, conceal_fade_ms=50.0, conceal_recover_ms=5.0):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
     condensed, "crossfade_ms" (default `crossfade_ms`) only on a session that crossfades, and "limit_db" / "limit_lookahead_ms" /
     "limit_hold_ms" (defaults `limit_db`, `limit_lookahead_ms`, `limit_hold_ms`) only on a session that limits, "envelope" (default
     `envelope`) only on a session that follows at an amount above 0, and "stall" (a sorted
-    tuple of ticks) only on a session whose entry has the key; ValueError on a malformed entry"""
+    tuple of ticks) only on a session whose entry has the key, as "lose" (a sorted tuple of ticks) and "conceal" (a bool); ValueError on
+    a malformed entry"""
+    try:
+        check_conceal_ms(conceal_hold_ms, conceal_fade_ms, conceal_recover_ms)
+    except ValueError as e:
+        raise ValueError(f"--conceal-hold / --conceal-fade / --conceal-recover: {e}") from None
     k = check_k(k, "-k")
     session_codebook({}, "--codebook", codebook)
     session_gate({}, "-thr / --gate-hold", gate_db, gate_hold)
@@ -288,10 +339,10 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
         unknown = (set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(CODEBOOK_KEYS)
-                   - set(STALL_KEYS))
+                   - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS))
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS})")
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
@@ -307,6 +358,7 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             raise ValueError(f"session {i}: \"auto_pitch\" must be true or false, got {s['auto_pitch']!r}")
         sess_k = check_k(s["k"], f"session {i}: \"k\"") if "k" in s else k
         stall = session_stall(s, f"session {i}")
+        lose, con = session_lose(s, f"session {i}"), session_conceal(s, f"session {i}")
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
                  gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
@@ -328,6 +380,10 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             e["codebook"] = size
         if stall is not None:
             e["stall"] = stall
+        if lose is not None:
+            e["lose"] = lose
+        if con is not None:
+            e["conceal"] = con
         out.append(e)
     return out
 
@@ -434,12 +490,14 @@ def input_pcm(path, input_sr, device):
     return (wf.numpy() * 32767).astype(np.int16)
 
 
-def run(conv, pcms, starts, chunk, params, before=None, after=None, stalls=None):
+def run(conv, pcms, starts, chunk, params, before=None, after=None, stalls=None, loses=None):
     """drive `conv` tick by tick: session i occupies slot i (opened with params[i]) from tick starts[i] for len(pcms[i]) // chunk
     ticks; `chunk` is one length for every session or a list of per-session lengths (sessions at their own rates).
     before(tick) runs ahead of the tick's opens and after(tick) behind its closes (--pool-rows: enrolments and removals).
     stalls (a sparse converter): per session the ticks at which it supplies nothing, or None; it then supplies its chunks at
     supply_ticks(start, chunks, stall) and its slot closes after the last of them.
+    loses (a concealing converter): per session the ticks at which the chunk it would supply is consumed and dropped (step's lost=),
+    or None; a tick at which the session supplies nothing anyway counts for nothing.
     Returns the emitted int16 chunks of every session, concatenated."""
     chunks = list(chunk) if isinstance(chunk, (list, tuple)) else [chunk] * len(pcms)
     n_chunks = [len(p) // c for p, c in zip(pcms, chunks)]
@@ -452,14 +510,17 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None, stalls=None)
     for tick in range(last):
         if before is not None:
             before(tick)
-        feed = {}
+        feed, lost = {}, []
         for i, (s, n) in enumerate(zip(starts, n_chunks)):
             if tick == s and n > 0:
                 conv.open(i, **params[i])
             if tick in supply[i]:
                 j, c = supply[i][tick], chunks[i]
-                feed[i] = pcms[i][j * c:(j + 1) * c]
-        res = conv.step(feed)
+                if loses is not None and loses[i] is not None and tick in loses[i]:
+                    lost.append(i)
+                else:
+                    feed[i] = pcms[i][j * c:(j + 1) * c]
+        res = conv.step(feed, lost) if lost else conv.step(feed)
         for i, o in res.items():
             if o is not None:
                 outs[i].append(o)
@@ -475,7 +536,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook,
                              args.crossfade, args.limit, args.limit_lookahead, args.limit_hold, args.envelope, args.envelope_floor,
-                             args.envelope_range, args.envelope_radius)
+                             args.envelope_range, args.envelope_radius, args.conceal_hold, args.conceal_fade, args.conceal_recover)
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -505,6 +566,7 @@ def main(argv=None):
     slots = max(args.slots, len(sessions))
     in_sr = [s["sr"] or args.input_sr for s in sessions]
     out_sr = [s["sr"] or args.output_sr for s in sessions]
+    conceal = args.conceal or any("lose" in s or s.get("conceal") for s in sessions)      # (a concealing converter is sparse)
     conv = MultiStreamConverter(CE, PE, Dec, pool, slots, chunk=args.chunk, buffersize=args.buffersize, input_sr=args.input_sr,
                                 output_sr=args.output_sr, k=args.k, device=device, rates=sorted(set(in_sr)),
                                 world_pitch=any(s["world_pitch"] for s in sessions), blend=blend_size(sessions),
@@ -514,10 +576,12 @@ def main(argv=None):
                                 **(dict(limiter=True) if any("limit_db" in s for s in sessions) else {}),
                                 **(dict(envelope=True, envelope_floor_db=args.envelope_floor, envelope_range_db=args.envelope_range,
                                         envelope_radius=args.envelope_radius) if any("envelope" in s for s in sessions) else {}),
-                                **(dict(sparse=True) if args.sparse or any("stall" in s for s in sessions) else {}))
+                                **(dict(sparse=True) if args.sparse or conceal or any("stall" in s for s in sessions) else {}),
+                                **(dict(conceal=True, conceal_hold_ms=args.conceal_hold, conceal_fade_ms=args.conceal_fade,
+                                        conceal_recover_ms=args.conceal_recover) if conceal else {}))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
-                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS if g in s})
+                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CONCEAL_KEYS if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()
@@ -546,8 +610,10 @@ def main(argv=None):
             for name in [n for t, what, n in events if t == tick and what == "remove"]:
                 pool.remove(name)
     stalls = [s.get("stall") for s in sessions]
+    loses = [s.get("lose") for s in sessions]
     outs = run(conv, pcms, [s["start"] for s in sessions], chunks, params, before, after,
-               **(dict(stalls=stalls) if any(st is not None for st in stalls) else {}))
+               **(dict(stalls=stalls) if any(st is not None for st in stalls) else {}),
+               **(dict(loses=loses) if any(ls is not None for ls in loses) else {}))
     os.makedirs(args.output_dir, exist_ok=True)
     for i, (s, o, r) in enumerate(zip(sessions, outs, out_sr)):
         path = s["output"] or os.path.join(args.output_dir, f"{i}_{os.path.splitext(os.path.basename(s['input']))[0]}.wav")

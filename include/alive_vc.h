@@ -905,6 +905,45 @@ int alive_ring_push_rows(int16_t* ring, int N, int ld, const int16_t* chunks, in
 int alive_emit_rows(const float* wave, int N, int ld, const int* span_lo, const int* span_len, const unsigned char* take, int16_t* out,
                     int ld_out, void* stream);
 
+/* Lost-chunk concealment at the input edge of a sparse multi-session converter (csrc/conceal.hip): waveform substitution in the style
+ * of G.711 Appendix I on the sessions' int16 rings.  Called in FRONT of alive_ring_push_rows, on the same stream, on a tick that has a
+ * lost or a recovering row.  All pointers are DEVICE pointers; the call allocates nothing, synchronises nothing and reads nothing on
+ * the host; the grid depends on N alone (graph-capturable: a captured call serves any flags, lengths and constants).  No atomics;
+ * every store is a plain vector-memory store.  Bitwise tools/conceal_ref.py.
+ *   alive_conceal_rows   one block per row n.  ring int16 [N][ld] (READ ONLY) holds each row's last ring_len[n] samples in time order;
+ *                        chunks int16 [N][ld_chunk] is the uploaded chunk buffer, rewritten IN PLACE over chunk_len[n] samples;
+ *                        present / lost / on are bytes [N]; lag_lo, lag_hi, window, hold, fade, recover int32 [N] are the row's
+ *                        constants in its own samples; state int32 [N][2] = (q: samples made up so far in this run, P: the run's
+ *                        period), tmpl int16 [N][ld_tmpl] the run's template.  With cl = chunk_len[n], rl = ring_len[n], W = window[n]:
+ *                          present[n] == 0                 absent (a stall): nothing of the row is read or written
+ *                          lost[n] == 0 and q == 0         neither lost nor recovering: nothing is read or written
+ *                          lost[n] != 0, on[n] == 0        chunk[0:cl] = 0, state = (0, 0)
+ *                          lost[n] != 0, on[n] != 0        if q == 0, the period and the template are taken, ONCE per run: for every lag
+ *                              l in [lag_lo, lag_hi], C(l) = sum_i a[i] ring[rl - W + i - l] and E(l) = sum_i ring[rl - W + i - l]^2 over
+ *                              i < W with a[i] = ring[rl - W + i], exact in int64; score = (double)C * (double)C / (double)E if C > 0 and
+ *                              E > 0, else 0; P = the lag of the largest score, the lowest lag on a tie (a silent ring: lag_lo);
+ *                              t[j] = ring[rl - P + j] for j < P, and over its last V = P / 4 samples, m = 1 .. V, j = P - V + m - 1:
+ *                              t[j] = rint(a + (double)((b - a) m) / (double)(V + 1)), a = ring[rl - P + j], b = ring[rl - 2 P + j];
+ *                              t -> tmpl[n][0:P].  If q > 0 the template is read back from tmpl and the ring is not read at all.
+ *                              Then chunk[i] = (int16)rint((double)t[(q + i) mod P] * att(q + i)) for i < cl, with att(k) = 0 if d <= 0,
+ *                              1 if d >= fade, else (double)d / (double)fade, d = hold + fade - k; state = (min(q + cl, QMAX), P)
+ *                          lost[n] == 0, q > 0             recovering: for i < rec = min(recover[n], cl), s = (double)t[(q + i) mod P] *
+ *                              att(q + i) and chunk[i] = rint(s + (((double)chunk[i] - s) * (double)(i + 1)) / (double)(rec + 1)),
+ *                              clamped to int16; the rest of the chunk is untouched; state = (0, 0)
+ *                        every fp64 operation rounded on its own.  A row whose lengths do not fit (cl < 1, cl > ld_chunk, cl > rl, rl >
+ *                        ld), whose constants are out of range (lag_lo < 1, lag_hi < lag_lo, lag_hi > ld_tmpl, W < 1, fade < 1, hold <
+ *                        0, recover < 0, hold or fade > QMAX), whose ring is shorter than need = max(W + lag_hi, 2 lag_hi), whose need
+ *                        exceeds ALIVE_CONCEAL_MAX_SPAN (the samples staged in LDS), or whose state no run leaves behind (q < 0; q > 0
+ *                        with P outside [1, lag_hi]) is LEFT ALONE; device data never leads outside a row.  16-byte stores on rows
+ *                        whose cl is a multiple of 8 when chunks is 16-byte aligned and ld_chunk a multiple of 8; scalar ones
+ *                        otherwise, with the same result.  N, ld, ld_tmpl > 0, 0 < ld_chunk < 2^30. */
+#define ALIVE_CONCEAL_MAX_SPAN 4096
+#define ALIVE_CONCEAL_QMAX (1 << 30)
+int alive_conceal_rows(const int16_t* ring, int N, int ld, const int* ring_len, int16_t* chunks, int ld_chunk, const int* chunk_len,
+                       const unsigned char* present, const unsigned char* lost, const unsigned char* on, const int* lag_lo,
+                       const int* lag_hi, const int* window, const int* hold, const int* fade, const int* recover, int* state,
+                       int16_t* tmpl, int ld_tmpl, void* stream);
+
 /* Envelope follow (csrc/envelope.hip): the converted wave y takes on the loudness contour of the source x that lies beside it sample
  * for sample (both at 16 kHz: the streaming ring and the decoder's wave of a tick; an utterance and its conversion).  Stateless and OUT
  * OF PLACE: out[N][ld_y] from y[N][ld_y] and x[N][ld_x].  All pointers are DEVICE pointers; the call allocates nothing, synchronises

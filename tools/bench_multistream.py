@@ -50,12 +50,22 @@ between the two runs of one side is the yardstick for the difference between the
 copies per tick in each direction, computed from its shapes.  Half absent: B = 64 distinct voices at -c 160 -b 16, the sparse converter
 with every session present against sessions present on alternate ticks (even slots on even ticks, odd on odd): the tick, and the
 grouped search alone, event-timed, over the segment lengths that tick left in seg_len_tick.
+--conceal runs the lost-chunk leg ALONE (MultiStreamConverter(sparse=True, conceal=True): csrc/conceal.hip), graph mode, k = 4, B = 128
+and B = 1024 sessions on one shared 50 000-row voice at -c 160 -b 16: a conceal=False sparse converter (conceal_off_tick_*) and
+conceal=True converters with 0 %, 5 % and 100 % of the sessions losing EVERY tick (conceal_0_ / conceal_5_ / conceal_100_tick_*; a
+session that loses every tick is in one long run: the period is searched on its first lost chunk only), ALTERNATED in one process, two
+runs each: the spread between the two conceal_off runs is the yardstick, and the 0 % converter launches what conceal_off launches.
+Beside them the calls alone on the converter's own arrays, by device events around 200 back-to-back eager calls: alive_conceal_rows
+with every row lost and its state cleared before each call (conceal_call_search_us: every session's FIRST lost chunk, the period
+search, the worst case; the clearing fill is timed alone and taken off), with every row in a run (conceal_call_run_us) and
+alive_ring_push_rows with every row present (push_call_us).
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch]
                                       [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--out multistream.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
     python tools/bench_multistream.py --sparse [--batches 128,1024] [--ticks 40] [--out profiles/multistream_sparse_bench.json]
+    python tools/bench_multistream.py --conceal [--batches 128,1024] [--ticks 40] [--out profiles/multistream_conceal_bench.json]
 """
 import argparse
 import json
@@ -83,21 +93,89 @@ def make_pool(n_voices, seed=0):
     return MS.VoicePool({f"v{i}": torch.randn(768, VOICE_ROWS, device="cuda", generator=g) for i in range(n_voices)})
 
 
-def time_ticks(conv, B, chunk, ticks, warmup, seed, silent=0, present=None):
+def time_ticks(conv, B, chunk, ticks, warmup, seed, silent=0, present=None, lost=None):
     """chunk: one length, or a list of per-slot lengths (sessions at their own rates); sessions s < silent send digital silence;
-    present(t, s) (a sparse converter): whether session s sends a chunk on tick t (default: every session, every tick)"""
+    present(t, s) (a sparse converter): whether session s sends a chunk on tick t (default: every session, every tick);
+    lost(t, s) (a concealing converter): whether session s's chunk of tick t is lost (default: none)"""
     cs = list(chunk) if isinstance(chunk, (list, tuple)) else [chunk] * B
     pcm = [(synthetic.make_waveform(cs[s] * 4, seed + s)[0].numpy() * (0 if s < silent else 12000)).astype(np.int16) for s in range(B)]
     ts = []
     for t in range(warmup + ticks):
         feed = {s: pcm[s][(t % 4) * cs[s]:(t % 4 + 1) * cs[s]] for s in range(B) if present is None or present(t, s)}
+        gone = [s for s in feed if lost(t, s)] if lost is not None else []
+        for s in gone:
+            del feed[s]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        conv.step(feed)
+        conv.step(feed, gone) if gone else conv.step(feed)
         torch.cuda.synchronize()
         if t >= warmup:
             ts.append((time.perf_counter() - t0) * 1e3)
     return float(np.percentile(ts, 50)), float(np.percentile(ts, 99))
+
+
+def time_calls(fn, reps=200):
+    """microseconds per call of fn, by device events around `reps` back-to-back calls"""
+    for _ in range(10):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps
+
+
+def conceal_leg(nets, batches=(128, 1024), ticks=40, warmup=6):
+    """a conceal=False sparse converter against conceal=True ones with 0 %, 5 % and 100 % of the sessions losing every tick, alternated,
+    two runs each; then the conceal call and the push alone: one record per B"""
+    recs = []
+    shared = make_pool(1, 1)
+    chunk, bs = 160, 16
+    sides = (("conceal_off", False, 0.0), ("conceal_0", True, 0.0), ("conceal_5", True, 0.05), ("conceal_100", True, 1.0))
+    for B in batches:
+        rec = {"leg": "conceal", "chunk": chunk, "buffersize": bs, "B": B, "voices": "shared", "voice_rows": VOICE_ROWS,
+               "chunk_period_ms": chunk / 16.0}
+        for name, _, _ in sides:
+            rec[f"{name}_tick_p50_ms"], rec[f"{name}_tick_p99_ms"] = [], []
+        for run in range(2):
+            for name, conceal, frac in sides:
+                conv = MS.MultiStreamConverter(*nets, shared, B, chunk=chunk, buffersize=bs, k=4, sparse=True, conceal=conceal)
+                for s in range(B):
+                    conv.open(s, "v0", pitch=float(s % 5), f0_rate=0.5)
+                conv.enable_graph()
+                losing = int(round(frac * B))
+                fill = warmup + bs + 1                         # the losses start once the rings are full of speech
+                p50, p99 = time_ticks(conv, B, chunk, ticks, fill, 300, lost=(lambda t, s: t >= bs + 1 and s < losing) if losing else None)
+                rec[f"{name}_tick_p50_ms"].append(round(p50, 3))
+                rec[f"{name}_tick_p99_ms"].append(round(p99, 3))
+                assert conv.captures == 1, conv.captures
+                if conceal:
+                    assert conv.conceals == (ticks + warmup if losing else 0), (conv.conceals, losing)
+                    rec[f"{name}_sessions_losing"] = losing
+                if name == "conceal_100" and run == 1:         # the calls alone, on this converter's own arrays and full rings
+                    st, flags = conv._conceal_state, conv._flags
+                    def call():                                # noqa: E306
+                        MS.conceal_rows_(conv.ring_dev, conv.ring_len, conv._chunks_dev, conv.chunk_len, conv.present, conv.lost,
+                                         conv.conceal_on, conv._conceal_consts, st, conv.conceal_tmpl)
+                    flags[0], flags[2] = True, True            # every row present and lost
+                    fill_us = time_calls(lambda: st.zero_())
+                    both_us = time_calls(lambda: (st.zero_(), call()))
+                    assert int((st[:, 0] == chunk).sum()) == B and int((st[:, 1] >= 40).sum()) == B
+                    rec["conceal_call_search_us"] = round(both_us - fill_us, 2)
+                    rec["conceal_call_run_us"] = round(time_calls(call), 2)
+                    flags[2] = False
+                    rec["push_call_us"] = round(time_calls(lambda: MS.ring_push_rows_(
+                        conv.ring_dev, conv._chunks_dev, conv.chunk_len, conv.ring_len, conv.present, conv._in, conv.seg_len,
+                        conv.seg_len_tick, conv.S)), 2)
+                del conv
+                torch.cuda.empty_cache()
+        lo, hi = min(rec["conceal_off_tick_p50_ms"]), max(rec["conceal_off_tick_p50_ms"])
+        rec["conceal_0_inside_the_spread_of_conceal_off"] = all(lo <= v <= hi for v in rec["conceal_0_tick_p50_ms"])
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+    return recs
 
 
 def enrol_leg(nets, B=64, chunk=160, bs=16, steady=30, warmup=6):
@@ -274,9 +352,12 @@ def main():
                                                          "default and on a reserved pool")
     ap.add_argument("--sparse", action="store_true", help="the sparse-ticks leg alone: dense against sparse(=True) converters, "
                                                           "alternated, and half the sessions absent")
+    ap.add_argument("--conceal", action="store_true", help="the lost-chunk leg alone: a conceal=False sparse converter against "
+                                                           "conceal=True ones with 0, 5 and 100 %% of the sessions losing every tick, "
+                                                           "alternated, and the conceal call and the push alone")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    batches = [int(b) for b in (args.batches or ("128,1024" if args.sparse else "1,8,32,64,128")).split(",")]
+    batches = [int(b) for b in (args.batches or ("128,1024" if args.sparse or args.conceal else "1,8,32,64,128")).split(",")]
     configs = [tuple(int(v) for v in c.split("x")) for c in args.configs.split(",")]
     rates = [int(r) for r in args.rates.split(",")] if args.rates else None
     mixes = tuple(args.voices.split(","))
@@ -285,6 +366,12 @@ def main():
     if args.quick:
         batches, configs, mixes = [64], [(160, 16)], ("distinct",)
     nets = (ContentEncoder(seed=2), F0Estimator(seed=2), Decoder(seed=2))
+    if args.conceal:
+        rows = conceal_leg(nets, batches, args.ticks, args.warmup)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(rows, open(args.out, "w"), indent=1)
+        return
     if args.sparse:
         rows = sparse_leg(nets, batches, args.ticks, args.warmup)
         if args.out:
