@@ -18,6 +18,12 @@ The jobs file is a JSON list; each entry:
                                                             an offset on top.  A jobs file without it runs as before
    "register_hz": 180,                                      optional: declares the register (mean f0 in Hz) of a voice given by
                                                             "lib" alone; a "target" wav's register is measured when it is encoded
+   "auto_range": false,                                     optional, a JSON bool (default: --auto-range): the file's pitch
+                                                            excursions are scaled around its own mean pitch so that its standard
+                                                            deviation meets the target voice's (convert_many(auto_range=)), on top of
+                                                            "intonation".  A jobs file without it runs as before
+   "range_st": 2.5,                                         optional, beside "register_hz": declares the pitch range (standard
+                                                            deviation in semitones) of a voice given by "lib" alone
    "limit_db": -1,                                          optional, a number of dBFS <= 0 or null (default: -lim): the output
                                                             limiter (module/multistream.py limit_waves) on the device after the
                                                             gain, at the file's own rate, before "normalize": no sample exceeds
@@ -52,6 +58,7 @@ JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha",
             "blend", "k", "auto_pitch", "register_hz")
 ENVELOPE_KEYS = ("envelope",)            # likewise; a loaded job carries it only when it follows (an amount above 0)
 LIMIT_KEYS = ("limit_db",)               # taken per job too; a loaded job carries it only when it is limited
+RANGE_KEYS = ("auto_range", "range_st")  # a loaded job carries "auto_range" only when it is on, "range_st" only when its entry has it
 
 
 def build_parser():
@@ -69,6 +76,8 @@ def build_parser():
                         help="run the kNN match and the decoder over all three chunks of every window (same samples)")
     parser.add_argument('--auto-pitch', action='store_true',
                         help="jobs follow their target voice's register unless their \"auto_pitch\" says otherwise")
+    parser.add_argument('--auto-range', action='store_true',
+                        help="jobs match their target voice's pitch range unless their \"auto_range\" says otherwise")
     parser.add_argument('-lim', '--limit', default=None, type=float, metavar="DB",
                         help="output limiter: no output sample exceeds this ceiling in dBFS (<= 0), so the 16-bit edge never wraps; the "
                              "gain starts to fall --limit-lookahead before a peak unless a job's \"limit_db\" says otherwise (default: no limiter)")
@@ -101,6 +110,32 @@ def register_hz_of(entry, where):
         raise ValueError(f"{where}: \"register_hz\" declares the register of a voice given by \"lib\" alone (a \"target\" wav's is "
                          "measured; a blend's comes from its voices)")
     return float(hz)
+
+
+def range_st_of(entry, where):
+    """an entry's "range_st" (None without one): a number of semitones > 0, for a voice given by "lib" alone, beside "register_hz"""
+    st = entry.get("range_st")
+    if st is None:
+        return None
+    if isinstance(st, bool) or not isinstance(st, (int, float)) or not 0 < st < float("inf"):
+        raise ValueError(f"{where}: \"range_st\" must be a number of semitones > 0, got {st!r}")
+    if "blend" in entry or entry.get("target") is not None or entry.get("lib") is None:
+        raise ValueError(f"{where}: \"range_st\" declares the pitch range of a voice given by \"lib\" alone (a \"target\" wav's is "
+                         "measured; a blend's comes from its voices)")
+    if entry.get("register_hz") is None:
+        raise ValueError(f"{where}: \"range_st\" goes beside \"register_hz\": a range is declared around a declared register")
+    return float(st)
+
+
+def declared_ranges(jobs):
+    """{voice key: semitones} of the jobs' "range_st"; ValueError if two jobs declare different ones for one voice"""
+    out = {}
+    for i, j in enumerate(jobs):
+        if j.get("range_st") is not None:
+            key = voice_key(j)
+            if out.setdefault(key, j["range_st"]) != j["range_st"]:
+                raise ValueError(f"job {i}: \"range_st\" {j['range_st']} but an earlier job gave this voice {out[key]}")
+    return out
 
 
 def declared_registers(jobs):
@@ -139,11 +174,12 @@ def job_envelope(j, where, envelope=0.0, floor_db=-60.0, range_db=12.0, radius=1
 
 
 def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0,
-              envelope_range_db=12.0, envelope_radius=1):
+              envelope_range_db=12.0, envelope_radius=1, auto_range=False):
     """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder; "auto_pitch": default
     `auto_pitch`); a limited job ("limit_db", default `limit_db`) also carries "limit_db", a job without a limiter does not, so a
     file without the key loads to what it did; likewise "envelope" (default `envelope`) only on a job that follows at an amount above
-    0; ValueError on a malformed job, before anything runs on the device"""
+    0, "auto_range" (default `auto_range`) only on a job that is on and "range_st" only where the entry has it; ValueError on a
+    malformed job, before anything runs on the device"""
     job_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, lookahead_ms, hold_ms)
     env = (envelope_floor_db, envelope_range_db, envelope_radius)
     job_envelope({}, "-env / --envelope-floor / --envelope-range / --envelope-radius", envelope, *env)
@@ -159,9 +195,9 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
     for i, j in enumerate(jobs):
         if not isinstance(j, dict) or "input" not in j:
             raise ValueError(f"job {i}: an object with an \"input\" wav is required")
-        unknown = set(j) - set(JOB_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS)
+        unknown = set(j) - set(JOB_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(RANGE_KEYS)
         if unknown:
-            raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: {JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS})")
+            raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: {JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS})")
         blend = blend_sources(j, f"job {i}", rel) if "blend" in j else None
         if blend is None and j.get("target") is None and j.get("lib") is None:
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
@@ -169,6 +205,8 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
             raise ValueError(f"job {i}: \"world_pitch\" must be true or false, got {j['world_pitch']!r}")
         if not isinstance(j.get("auto_pitch", False), bool):
             raise ValueError(f"job {i}: \"auto_pitch\" must be true or false, got {j['auto_pitch']!r}")
+        if not isinstance(j.get("auto_range", False), bool):
+            raise ValueError(f"job {i}: \"auto_range\" must be true or false, got {j['auto_range']!r}")
         job_k = check_k(j["k"], f"job {i}: \"k\"") if "k" in j else k
         e = dict(input=rel(j["input"]), target=rel(j.get("target")), lib=rel(j.get("lib")), output=rel(j.get("output")),
                  pitch=float(j.get("pitch", 0.0)), intonation=float(j.get("intonation", 1.0)), f0_rate=float(j.get("f0_rate", 1.0)),
@@ -181,6 +219,11 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
         amount = job_envelope(j, f"job {i}", envelope, *env)
         if amount is not None:
             e["envelope"] = amount
+        if j.get("auto_range", bool(auto_range)):
+            e["auto_range"] = True
+        range_st = range_st_of(j, f"job {i}")
+        if range_st is not None:
+            e["range_st"] = range_st
         for key in ("input", "target", "lib"):
             if e[key] is not None and not os.path.isfile(e[key]):
                 raise ValueError(f"job {i}: {key} {e[key]!r} does not exist")
@@ -236,9 +279,12 @@ def main(argv=None):
     if device.type != "cuda":
         raise SystemExit("this build runs on the MI355X only: pass -d cuda")
     jobs = load_jobs(args.jobs, args.k, args.auto_pitch, args.limit, args.limit_lookahead, args.limit_hold, args.envelope,
-                     args.envelope_floor, args.envelope_range, args.envelope_radius)
-    auto = any(j["auto_pitch"] for j in jobs)           # only then are the voices' registers measured or declared
+                     args.envelope_floor, args.envelope_range, args.envelope_radius, args.auto_range)
+    on_auto = any(j["auto_pitch"] for j in jobs)
+    ranged = any("auto_range" in j for j in jobs)
+    auto = on_auto or ranged                            # only then are the voices' registers (and ranges) measured or declared
     declared = declared_registers(jobs) if auto else {}
+    declared_st = declared_ranges(jobs) if ranged else {}
     # (device work starts here)
     from module.content_encoder import ContentEncoder
     from module.decoder import Decoder
@@ -273,7 +319,8 @@ def main(argv=None):
             tgt = torch.cat([tgt, VL.tokens], dim=2)
         voices[key] = tgt
         if key in declared:
-            registers[key] = (pitch_hz(declared[key]), 1.0)
+            p0 = pitch_hz(declared[key])
+            registers[key] = (p0, 1.0) if key not in declared_st else (p0, 1.0, p0 * p0 + declared_st[key] * declared_st[key])
     check_job_voice_sizes(jobs, {k_: int(t.shape[2]) for k_, t in voices.items()})
     names = {key: f"voice{i}" for i, key in enumerate(voices)}
     pool = VoicePool({names[key]: t for key, t in voices.items()}, device=device,
@@ -291,7 +338,8 @@ def main(argv=None):
     outs = conv.convert_many(utts, pool, [job_voice(j, names) for j in jobs], pitch_shift=[j["pitch"] for j in jobs],
                              intonation=[j["intonation"] for j in jobs], f0_rate=[j["f0_rate"] for j in jobs],
                              alpha=[j["alpha"] for j in jobs], world_pitch=[j["world_pitch"] for j in jobs],
-                             auto_pitch=[j["auto_pitch"] for j in jobs] if auto else False, chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
+                             auto_pitch=[j["auto_pitch"] for j in jobs] if on_auto else False,
+                             **(dict(auto_range=["auto_range" in j for j in jobs]) if ranged else {}), chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)
     for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
         if job.get("envelope"):                                         # at 16 kHz, against the source the converter saw

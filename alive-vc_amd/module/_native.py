@@ -158,6 +158,10 @@ PROTOTYPES = {
     "alive_pitch_stats_groups": (_I, [_VP, _I, _I, _I, _I, _VP, _I, _VP, _VP]),
     "alive_pitch_shift_groups": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "alive_pitch_follow_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP]),
+    "alive_pitch_stats2_groups": (_I, [_VP, _I, _I, _I, _I, _VP, _I, _VP, _VP]),
+    "alive_pitch_range_groups": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _D, _VP, _VP, _VP, _VP]),
+    "alive_pitch_follow2_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _D, _D, _D, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "alive_pitch_transform_rows_centred": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_gate_rows": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_gate_apply_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "alive_seam_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP]),

@@ -51,6 +51,16 @@ every time); the defaults, 10 s and 0.5 s, are design choices, not tuned on data
 close zero it, set(voice=) rewrites the target only (the source has not changed), enable_graph and the bf16 repeat save and restore it.
 Everything is device arrays: toggling never re-captures, and a converter built without auto_pitch launches exactly what it did.
 
+Pitch range: a converter built with pitch_range=True carries the second moment too.  reg_state is [B, 3] = (S, W, Q), Q the decayed sum
+of squared pitch; alive_pitch_follow2_rows stands where alive_pitch_follow_rows stood and alive_pitch_transform_rows_centred where
+alive_pitch_transform_rows stood, captured once.  A session follows when it is on auto_pitch, on auto_range, or at an intonation other
+than 1.  With m = S / W, v = Q / W - m^2 and a = W / (W + prior), its frames become p' = m + (p - m) * I_eff + shift_eff, where I_eff =
+1 + a * (intonation * r - 1) and r = clamp(target_sd / sqrt(v), 1 / pitch_range_max, pitch_range_max) on an auto_range session (target_sd
+from VoicePool.blend_range), 1 otherwise: with auto_pitch beside it, the mean-variance transform of log-f0, grown from the identity with
+the evidence.  Half-life and prior are auto pitch's.  A session at intonation=1, auto_range=False is bitwise the session of a plain
+converter, an auto_pitch-only session bitwise that of an auto_pitch=True converter, and a converter built without pitch_range launches
+exactly what it did.  pitch_range_state() reads the running mean, standard deviation and effective intonation back.
+
 Input gate: a converter built with gate=True decides on the device, every tick, which sessions hear something (csrc/gate.hip).  Right
 after the input resample, alive_gate_rows takes the mean square of every 16 kHz ring over the detection window [begin_of_output,
 min(ring, end_of_output + gate_lookahead)) -- the chunk about to be emitted plus a lookahead, one chunk's duration by default, a
@@ -393,6 +403,18 @@ def _token_parts(tokens):
     return parts, sum(int(t.shape[1]) for t in parts)
 
 
+class Register(tuple):
+    """a measured register (sum of voiced pitch, voiced frames) that also carries the sum of squared pitch as `.sumsq`: it compares
+    and unpacks as the 2-tuple it always was, and VoicePool.add / extend / set_register read the third sum from it"""
+    def __new__(cls, s, c, sumsq):
+        self = super().__new__(cls, (s, c))
+        self.sumsq = sumsq
+        return self
+
+    def __getnewargs__(self):              # (pickle and copy rebuild it through __new__)
+        return self[0], self[1], self.sumsq
+
+
 class VoicePool:
     """Named voices tokens[768, M] packed into one fp32 row table rows[P, 768] with norms[P] (the norms bitwise those of
     PackedLibrary) and a name -> (seg_lo, M) map.
@@ -418,12 +440,18 @@ class VoicePool:
     unit of pitch_stats_groups; `register(name)` is their quotient, the mean pitch.  `add` sets it, `extend` merges by adding sums
     and counts, `set_register` declares one (a voice without audio, such as a voice library); it goes with its voice -- `remove`
     drops it with the voice, and no operation on the pool (re-packing, moves, compact, another voice's removal) loses or changes
-    the register of a voice that stays."""
+    the register of a voice that stays.
+
+    Ranges (pitch range): beside its register a voice may carry the sum of its squared voiced pitch (`ranges`), from which
+    `pitch_range(name)` is the standard deviation in semitones.  A register given as (sum, count, sumsq) -- or as the Register that
+    measure_register returns -- carries it, a 2-tuple does not; a voice keeps a range only while every piece merged into its
+    register brought one.  It travels and goes with the register."""
 
     def __init__(self, voices=None, device="cuda", capacity=None, registers=None):
         self.device = torch.device(device)
         self.segments = {}
         self.registers = {}                    # name -> (sum of voiced pitch, voiced frames), host floats
+        self.ranges = {}                       # name -> sum of squared voiced pitch, for the voices that carry a second moment
         self.version = 0
         self.capacity = None
         self._images = None
@@ -452,35 +480,66 @@ class VoicePool:
     # ------------------------------------------------------------------ registers (auto pitch)
     @staticmethod
     def _check_register(name, register):
+        """-> (sum, count) or (sum, count, sumsq) as floats"""
         try:
-            s, c = (float(v) for v in register)
+            vals = tuple(float(v) for v in register)
+            if isinstance(register, Register):
+                vals += (float(register.sumsq),)
+            if len(vals) not in (2, 3):
+                raise ValueError
         except (TypeError, ValueError):
             raise ValueError(f"voice {name!r}: a register is (sum of voiced pitch, voiced frames), got {register!r}") from None
+        s, c = vals[:2]
         if not (np.isfinite(s) and np.isfinite(c) and c >= 0):
             raise ValueError(f"voice {name!r}: a register needs a finite sum and a finite count >= 0, got {register!r}")
-        return s, c
+        if len(vals) == 3 and not (np.isfinite(vals[2]) and vals[2] >= 0):
+            raise ValueError(f"voice {name!r}: a register's sum of squares must be finite and >= 0, got {register!r}")
+        return vals
 
     def _merge_register(self, name, register):
-        """add a checked (sum, count) to the voice's register (None: nothing)"""
+        """add a checked (sum, count[, sumsq]) to the voice's register (None: nothing).  The voice carries a range afterwards only
+        if the piece brought a sum of squares and what the voice had before (if anything) did too"""
         if register is not None:
             s0, c0 = self.registers.get(name, (0.0, 0.0))
+            had = name in self.registers
             self.registers[name] = (s0 + register[0], c0 + register[1])
+            if len(register) == 3 and (not had or name in self.ranges):
+                self.ranges[name] = self.ranges.get(name, 0.0) + register[2]
+            else:
+                self.ranges.pop(name, None)
 
-    def set_register(self, name, hz=None, register=None):
+    def set_register(self, name, hz=None, register=None, range_st=None):
         """declare the voice's register: its mean f0 in Hz (stored as one voiced frame at pitch_hz(hz)), or a measured
-        (sum of voiced pitch, voiced frames) as pitch_stats_groups returns it; both None: the voice has none any more"""
+        (sum of voiced pitch, voiced frames) as pitch_stats_groups returns it -- or (sum, count, sumsq) as pitch_stats2_groups does;
+        both None: the voice has none any more.  range_st (with hz=, or alone on a voice that has a register): the standard
+        deviation of its pitch in semitones, stored as the sum of squares count * (mean^2 + range_st^2)"""
         self.segment(name)
         if hz is not None and register is not None:
             raise ValueError(f"voice {name!r}: set_register takes hz= or register=, not both")
+        if range_st is not None:
+            if isinstance(range_st, (bool, np.bool_)) or not isinstance(range_st, (int, float, np.integer, np.floating)) or not (
+                    np.isfinite(range_st) and range_st > 0):
+                raise ValueError(f"voice {name!r}: range_st={range_st!r} must be a finite number of semitones > 0")
+            if register is not None:
+                raise ValueError(f"voice {name!r}: set_register takes range_st= with hz= or alone, not with register=")
+            if hz is None:
+                if self.register(name) is None:
+                    raise ValueError(f"voice {name!r}: range_st= needs hz= or a voice that has a register")
+                s, c = self.registers[name]
+                self.ranges[name] = c * ((s / c) * (s / c) + float(range_st) * float(range_st))
+                return self
         if hz is not None:
             if isinstance(hz, (bool, np.bool_)) or not isinstance(hz, (int, float, np.integer, np.floating)) or not (
                     np.isfinite(hz) and hz > 0):
                 raise ValueError(f"voice {name!r}: register hz={hz!r} must be a finite number > 0")
             register = (pitch_hz(hz), 1.0)
-        if register is None:
-            self.registers.pop(name, None)
-        else:
-            self.registers[name] = self._check_register(name, register)
+            if range_st is not None:
+                register += (register[0] * register[0] + float(range_st) * float(range_st),)
+        if register is not None:
+            register = self._check_register(name, register)   # (raises before the voice's own is touched)
+        self.registers.pop(name, None)
+        self.ranges.pop(name, None)
+        self._merge_register(name, register)
         return self
 
     def register(self, name):
@@ -501,6 +560,29 @@ class VoicePool:
             total += w * r
         return total
 
+    def pitch_range(self, name):
+        """the standard deviation of the voice's pitch in semitones (a float; 0.0 when its second moment leaves no variance), or
+        None if it carries no second moment"""
+        self.segment(name)
+        s, c = self.registers.get(name, (0.0, 0.0))
+        if not c > 0 or name not in self.ranges:
+            return None
+        m = s / c
+        v = self.ranges[name] / c - m * m
+        return float(np.sqrt(v)) if v > 0 else 0.0
+
+    def blend_range(self, names, weights):
+        """the target range of a voice or blend (blend_spec's names and weights): the weighted mean of the voices' standard
+        deviations; ValueError naming the first voice that has none"""
+        total = 0.0
+        for n, w in zip(names, weights):
+            r = self.pitch_range(n)
+            if r is None:
+                raise ValueError(f"auto range: voice {n!r} has no pitch range: enrol it with f0_estimator=, pass register=(sum, count, "
+                                 "sumsq) to add / extend, or declare one with set_register(..., range_st=)")
+            total += w * r
+        return total
+
     def add(self, name, tokens, register=None):
         if register is not None:
             register = self._check_register(name, register)
@@ -518,6 +600,7 @@ class VoicePool:
         self._tokens[str(name)] = _tokens_2d(tokens).to(self.device, torch.float32).contiguous()
         self._pack()
         self.registers.pop(str(name), None)                   # (a voice added again under its name: the new speaker's)
+        self.ranges.pop(str(name), None)
         self._merge_register(str(name), register)
         return self
 
@@ -575,6 +658,7 @@ class VoicePool:
         self._reserved("remove")
         self._alloc.remove(name)                              # raises while a converter holds the voice
         self.registers.pop(name, None)
+        self.ranges.pop(name, None)
         self._changed()
         return self
 
@@ -695,14 +779,15 @@ class VoicePool:
 
 def measure_register(f0_estimator, wf16, world_pitch=False):
     """the register (sum of voiced pitch, voiced frames) of 16 kHz audio wf16 [1, L] on the device, as host floats: the f0 estimator's
-    f0 of its spectrogram (world_pitch: WORLD's f0 of the audio) through alive_pitch_stats_groups, one group, every frame.  One
-    host read: for enrolment, never inside a tick."""
+    f0 of its spectrogram (world_pitch: WORLD's f0 of the audio) through alive_pitch_stats2_groups, one group, every frame: a
+    Register, the 2-tuple it always was (bitwise alive_pitch_stats_groups') with the sum of squares as `.sumsq`.  One host read: for
+    enrolment, never inside a tick."""
     def f0():
         return compute_f0(wf16) if world_pitch else f0_estimator.estimate(spectrogram(wf16))
     f = ops.Fp16Guard().run(f0)
     first = torch.tensor([0, f.shape[0]], dtype=torch.int32, device=f.device)
-    s, c = pitch_stats_groups(f, first)[0].tolist()
-    return s, c
+    s, c, q = pitch_stats2_groups(f, first)[0].tolist()
+    return Register(s, c, q)
 
 
 def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="cuda", f0_estimator=None, world_pitch=False,
@@ -1002,6 +1087,73 @@ def pitch_follow_rows_(f0, f0_rate, offset, auto_on, target, emit, decay, prior,
                                                 nat.ptr(target), nat.ptr(emit), float(decay), float(prior), nat.ptr(state),
                                                 nat.ptr(shift_out), nat.stream()), "alive_pitch_follow_rows")
     return shift_out
+
+
+def pitch_stats2_groups(f0, first, t_lo=0, t_hi=None, out=None):
+    """pitch_stats_groups with the sum of squares: device float64 [G, 3] = (sum, count, sum of squares), the first two bitwise
+    pitch_stats_groups' (alive_pitch_stats2_groups)"""
+    if f0.dtype != torch.float32 or not f0.is_contiguous():
+        raise ValueError("pitch_stats2_groups: f0 must be contiguous float32")
+    if first.dtype != torch.int32 or first.dim() != 1 or first.numel() < 2:
+        raise ValueError("pitch_stats2_groups: first must be int32 [G + 1]")
+    n, t = f0.shape[0], f0.shape[-1]
+    g = first.numel() - 1
+    stats = torch.empty(g, 3, dtype=torch.float64, device=f0.device) if out is None else out
+    nat.check(nat.lib().alive_pitch_stats2_groups(nat.ptr(f0), n, t, int(t_lo), int(t if t_hi is None else t_hi), nat.ptr(first), g,
+                                                  nat.ptr(stats), nat.stream()), "alive_pitch_stats2_groups")
+    return stats
+
+
+def pitch_range_groups(stats3, first, n, inton, range_on, target_sd, range_max=2.0):
+    """the offline intonation, centre and centre switch of every row, device (float32 [n], float32 [n], int32 [n]): a group with
+    range_on and voiced frames gets inton * clamp(target_sd / its own sd) around its own mean, every other group its inton and no
+    centre (alive_pitch_range_groups); inton: device float32 [G], target_sd: device float64 [G], range_on: device int32 [G]"""
+    g = first.numel() - 1
+    dev = stats3.device
+    i_out = torch.empty(n, dtype=torch.float32, device=dev)
+    c_out = torch.empty(n, dtype=torch.float32, device=dev)
+    on_out = torch.empty(n, dtype=torch.int32, device=dev)
+    nat.check(nat.lib().alive_pitch_range_groups(nat.ptr(stats3), nat.ptr(first), g, n, nat.ptr(inton), nat.ptr(range_on),
+                                                 nat.ptr(target_sd), float(range_max), nat.ptr(i_out), nat.ptr(c_out),
+                                                 nat.ptr(on_out), nat.stream()), "alive_pitch_range_groups")
+    return i_out, c_out, on_out
+
+
+def pitch_follow2_rows_(f0, f0_rate, offset, auto_on, target, inton, range_on, target_sd, emit, decay, prior, range_max, state3,
+                        shift_out, inton_out, centre_out, centre_on_out):
+    """pitch_follow_rows_ on state3 (float64 [N, 3] = (S, W, Q)), in place on it and on the four outputs (float32 [N] x 3, int32
+    [N]): alive_pitch_follow2_rows"""
+    n, t = f0.shape[0], f0.shape[-1]
+    nat.check(nat.lib().alive_pitch_follow2_rows(nat.ptr(f0), n, t, nat.ptr(f0_rate), nat.ptr(offset), nat.ptr(auto_on),
+                                                 nat.ptr(target), nat.ptr(inton), nat.ptr(range_on), nat.ptr(target_sd),
+                                                 nat.ptr(emit), float(decay), float(prior), float(range_max), nat.ptr(state3),
+                                                 nat.ptr(shift_out), nat.ptr(inton_out), nat.ptr(centre_out),
+                                                 nat.ptr(centre_on_out), nat.stream()), "alive_pitch_follow2_rows")
+    return shift_out, inton_out, centre_out, centre_on_out
+
+
+def pitch_transform_rows_centred_(f0, mode, f0_rate, pitch_shift, intonation, centre, centre_on):
+    """pitch_transform_rows_ with a centre per row (device float32 [N]) where centre_on (device int32 [N]) is set; a row with
+    centre_on == 0 is bitwise pitch_transform_rows_ (alive_pitch_transform_rows_centred)"""
+    n, t = f0.shape[0], f0.shape[-1]
+    nat.check(nat.lib().alive_pitch_transform_rows_centred(nat.ptr(f0), n, t, mode, nat.ptr(f0_rate), nat.ptr(pitch_shift),
+                                                           nat.ptr(intonation), nat.ptr(centre), nat.ptr(centre_on), nat.stream()),
+              "alive_pitch_transform_rows_centred")
+    return f0
+
+
+def check_range_max(range_max, what="pitch_range_max"):
+    if isinstance(range_max, (bool, np.bool_)) or not isinstance(range_max, (int, float, np.integer, np.floating)) or not (
+            np.isfinite(range_max) and range_max >= 1):
+        raise ValueError(f"{what}={range_max!r} must be a finite number >= 1")
+    return float(range_max)
+
+
+def check_intonation(intonation, what="intonation"):
+    if isinstance(intonation, (bool, np.bool_)) or not isinstance(intonation, (int, float, np.integer, np.floating)) or not (
+            np.isfinite(intonation) and intonation >= 0):
+        raise ValueError(f"{what}={intonation!r} must be a finite number >= 0")
+    return float(intonation)
 
 
 def gate_thr_ms(gate_db):
@@ -1532,11 +1684,12 @@ def db_scale(db):
 
 
 _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold",
-           "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope", "conceal")
+           "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope", "conceal", "intonation", "auto_range")
 
 
 class MultiStreamConverter:
     auto_pitch = False                 # (set per converter in __init__: whether the tick carries the auto-pitch kernel)
+    pitch_range = False                # (likewise: whether that kernel is the three-moment follower and the transform the centred one)
     gate = False                       # (likewise: whether the tick carries the two gate kernels)
     crossfade = False                  # (likewise: whether the tick carries the seam kernel)
     limiter = False                    # (likewise: whether the tick carries the limiter kernel)
@@ -1549,7 +1702,13 @@ class MultiStreamConverter:
                  auto_pitch_half_life=10.0, auto_pitch_prior=0.5, gate=False, gate_lookahead=None, crossfade=False,
                  limiter=False, limit_history=0.05, sparse=False, envelope=False, envelope_floor_db=-60.0,
                  envelope_range_db=12.0, envelope_radius=1, conceal=False, conceal_hold_ms=10.0, conceal_fade_ms=50.0,
-                 conceal_recover_ms=5.0):
+                 conceal_recover_ms=5.0, pitch_range=False, pitch_range_max=2.0):
+        if not isinstance(pitch_range, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: pitch_range must be a bool, got {pitch_range!r}")
+        try:
+            pitch_range_max = check_range_max(pitch_range_max)
+        except ValueError as e:
+            raise ValueError(f"MultiStreamConverter: {e}") from None
         if not isinstance(conceal, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: conceal must be a bool, got {conceal!r}")
         if conceal:                        # (checked before anything is built)
@@ -1687,14 +1846,25 @@ class MultiStreamConverter:
             self.f0_rate_eff = torch.ones(B, dtype=torch.float32, device=dev)
         # auto_pitch: the follow kernel is part of the tick (captured once); per row, auto_on selects pitch + the automatic shift
         # towards `target`, and the transform reads shift_eff.  reg_state is the session's running source register, like phi
-        self.auto_pitch = bool(auto_pitch)
+        # pitch_range: the follower is alive_pitch_follow2_rows on reg_state [B, 3] = (S, W, Q) and the transform the centred one;
+        # per row, `intonation` scales the excursions around the running mean and range_on maps the running standard deviation onto
+        # target_sd.  Such a converter serves auto_pitch sessions too: everything that carries reg_state carries its third column
+        self.pitch_range = bool(pitch_range)
+        self.auto_pitch = bool(auto_pitch) or self.pitch_range
         if self.auto_pitch:
             self.auto_decay, self.auto_prior = auto_constants(self.chunk / input_sr, self.buffersize, auto_pitch_half_life,
                                                               auto_pitch_prior)
             self.auto_on = torch.zeros(B, dtype=torch.int32, device=dev)
             self.target = torch.zeros(B, dtype=torch.float32, device=dev)
-            self.reg_state = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+            self.reg_state = torch.zeros(B, 3 if self.pitch_range else 2, dtype=torch.float64, device=dev)
             self.shift_eff = torch.zeros(B, dtype=torch.float32, device=dev)
+        if self.pitch_range:
+            self.range_max = pitch_range_max
+            self.range_on = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.target_sd = torch.zeros(B, dtype=torch.float64, device=dev)
+            self.inton_eff = torch.ones(B, dtype=torch.float32, device=dev)
+            self.centre = torch.zeros(B, dtype=torch.float32, device=dev)
+            self.centre_on = torch.zeros(B, dtype=torch.int32, device=dev)
         # gate: the two gate kernels are part of the tick (captured once); per row, gate_on switches the session's gate, and the tick
         # reads seg_len_eff / world_eff / follow where it read seg_len / world_on / emit.  gate_state is the session's, like phi
         self.gate = bool(gate)
@@ -1969,6 +2139,21 @@ class MultiStreamConverter:
                 target = self.pool.blend_register(names, weights)
             except ValueError as e:
                 raise ValueError(f"slot {slot}: {e}") from None
+        inton, ranged = p.get("intonation", 1.0), p.get("auto_range", False)
+        try:
+            inton = check_intonation(inton)
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+        if not isinstance(ranged, (bool, np.bool_)):
+            raise ValueError(f"slot {slot}: auto_range must be a bool, got {ranged!r}")
+        if (inton != 1.0 or ranged) and not self.pitch_range:
+            raise ValueError(f"slot {slot}: intonation={inton!r} / auto_range={bool(ranged)!r} need a converter built with "
+                             "MultiStreamConverter(..., pitch_range=True)")
+        if ranged:                                            # (raises for a voice without a range, before anything changes)
+            try:
+                target_sd = self.pool.blend_range(names, weights)
+            except ValueError as e:
+                raise ValueError(f"slot {slot}: {e}") from None
         self._write_segments(slot, names)
         if self.S > 1:
             rows = slice(slot * self.S, (slot + 1) * self.S)
@@ -1988,6 +2173,10 @@ class MultiStreamConverter:
         if self.auto_pitch:
             self.auto_on[slot] = int(bool(auto))
             self.target[slot] = target if auto else 0.0
+        if self.pitch_range:
+            self.intonation[slot] = inton
+            self.range_on[slot] = int(bool(ranged))
+            self.target_sd[slot] = target_sd if ranged else 0.0
         if self.gate:
             self.gate_on[slot], self.thr_ms[slot], self.hold_ticks[slot] = gate
         if self.crossfade:
@@ -2065,7 +2254,7 @@ class MultiStreamConverter:
 
     def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None,
              auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0,
-             limit_hold_ms=20.0, envelope=0.0, conceal=None):
+             limit_hold_ms=20.0, envelope=0.0, conceal=None, intonation=1.0, auto_range=False):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
@@ -2083,7 +2272,11 @@ class MultiStreamConverter:
         input, from 0 (the decoder's own level) to 1 (the source's smoothed frame level, within the converter's range).
         conceal (None: the converter's, on in a conceal=True converter; True needs one): whether the session's lost chunks (step(...,
         lost=)) are concealed by waveform substitution; False: they are chunks of zeros.  The session's ring must hold the search:
-        ValueError otherwise"""
+        ValueError otherwise.
+        intonation (other than 1: needs a pitch_range=True converter): a finite factor >= 0 on the session's pitch excursions around
+        its running mean pitch, growing from 1 with the evidence as the automatic shift does.  auto_range=True (needs such a converter
+        and a range on every voice of the session): the factor is multiplied by target sd / running source sd, within [1 /
+        pitch_range_max, pitch_range_max] -- with auto_pitch, the mean-variance transform of log-f0"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
@@ -2091,7 +2284,8 @@ class MultiStreamConverter:
                              "MultiStreamConverter(..., rates=...)")
         p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch,
                  k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold, crossfade_ms=crossfade_ms, limit_db=limit_db,
-                 limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms, envelope=envelope, conceal=conceal)
+                 limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms, envelope=envelope, conceal=conceal,
+                 intonation=intonation, auto_range=auto_range)
         self._apply(slot, p, rate)                            # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -2112,7 +2306,7 @@ class MultiStreamConverter:
 
     def set(self, slot, **params):
         """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
-        gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms, limit_hold_ms, envelope, conceal; the gate's state, the saved tail and the
+        intonation, auto_range, gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms, limit_hold_ms, envelope, conceal; the gate's state, the saved tail and the
         limiter's history are kept: a longer crossfade fades over what the tail holds this tick and in full from the next, and a
         limiter switched on or retuned sees the required gains of the samples already emitted).
         The running source register is kept: a new voice changes the target only, and auto_pitch=True after False resumes from
@@ -2149,6 +2343,10 @@ class MultiStreamConverter:
             self.auto_on[slot] = 0
             self.target[slot] = 0.0
             self.reg_state[slot] = 0.0
+        if self.pitch_range:
+            self.intonation[slot] = 1.0
+            self.range_on[slot] = 0
+            self.target_sd[slot] = 0.0
         if self.gate:
             self.gate_on[slot] = 0
             self.thr_ms[slot] = 0.0
@@ -2228,6 +2426,22 @@ class MultiStreamConverter:
             raise ValueError("seam_db needs a converter built with MultiStreamConverter(..., crossfade=True)")
         return stats_db(self.seam_stats.tolist())
 
+    def pitch_range_state(self):
+        """per slot, (mean, sd, intonation): the running mean pitch and standard deviation (semitones) of the session's source as
+        its (S, W, Q) give them -- None, None before any voiced frame or on a session that does not follow -- and the effective
+        intonation of the latest tick (1.0 where the transform ran uncentred).  One host read"""
+        if not self.pitch_range:
+            raise ValueError("pitch_range_state needs a converter built with MultiStreamConverter(..., pitch_range=True)")
+        out = []
+        for (S, W, Q), i in zip(self.reg_state.tolist(), self.inton_eff.tolist()):
+            if W == 0:
+                out.append((None, None, i))
+                continue
+            m = S / W
+            v = Q / W - m * m
+            out.append((m, float(np.sqrt(v)) if v > 0 else 0.0, i))
+        return out
+
     # ------------------------------------------------------------------ device step
     def _f0_on_side_stream(self, spec, data):
         """realtime.f0_on_side_stream with the per-row pitch transform.  world_pitch: after the estimator, the masked WORLD f0 of
@@ -2240,6 +2454,12 @@ class MultiStreamConverter:
                 buf.copy_(torch.where(self._world_sel, compute_f0_rows(data, world_on), buf))
                 f0, rate = buf, self.f0_rate_eff
             shift = self.pitch
+            if self.pitch_range:                              # running (S, W, Q) -> this tick's shifts, intonations and centres
+                emit = self.follow if self.gate else self.emit
+                pitch_follow2_rows_(f0, rate, self.pitch, self.auto_on, self.target, self.intonation, self.range_on, self.target_sd,
+                                    emit, self.auto_decay, self.auto_prior, self.range_max, self.reg_state, self.shift_eff,
+                                    self.inton_eff, self.centre, self.centre_on)
+                return pitch_transform_rows_centred_(f0, 1, rate, self.shift_eff, self.inton_eff, self.centre, self.centre_on)
             if self.auto_pitch:                               # the sessions' running registers -> this tick's shifts
                 emit = self.follow if self.gate else self.emit      # (a gated session's register learns from open ticks only)
                 shift = pitch_follow_rows_(f0, rate, self.pitch, self.auto_on, self.target, emit, self.auto_decay,
@@ -2319,8 +2539,12 @@ class MultiStreamConverter:
         saved_reg = self.reg_state.clone() if self.auto_pitch else None      # (capture_step runs the step three times)
         saved_gate = self.gate_state.clone() if self.gate else None
         saved_seam = self._seam_state()
+        # (the follower's outputs too: pitch_range_state() reads inton_eff, and they are the latest tick's until the next one)
+        saved_outs = [(a, a.clone()) for a in (self.shift_eff, self.inton_eff, self.centre, self.centre_on)] if self.pitch_range else []
         self._graph, self._g_out = capture_step(self.device, lambda: self._device_step(self._in, self.phi), self.phi)
         self.phi.copy_(saved)
+        for a, v in saved_outs:
+            a.copy_(v)
         self._seam_restore(saved_seam)
         if saved_reg is not None:
             self.reg_state.copy_(saved_reg)

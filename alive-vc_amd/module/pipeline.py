@@ -374,7 +374,8 @@ class Converter:
         return stitch(self.convert_windows(windows, keep_frames=keep, **kw), total, chunk)       # (the guard sits in convert_windows)
 
     def convert_many(self, utterances, pool, voices, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, alpha=0.0, chunk=48000, k=4,
-                     window_batch=64, trim_context=False, world_pitch=False, auto_pitch=False):
+                     window_batch=64, trim_context=False, world_pitch=False, auto_pitch=False, auto_range=False,
+                     pitch_range_max=2.0):
         """Many-to-many batch conversion: utterance i (16 kHz, [L] or [1, L], any length) to voice voices[i] of `pool`
         (module/multistream.py: VoicePool), with per-utterance pitch_shift / intonation / f0_rate / alpha / world_pitch (a scalar
         applies to every utterance; world_pitch: WORLD's f0 of each whole window, as convert(world_pitch=True)).  Returns one [1, L_i] waveform per utterance.  The windows of ALL utterances form one batch (a network
@@ -396,7 +397,14 @@ class Converter:
         frames [chunk // 320, 2 * chunk // 320), every original frame once -- from ONE alive_pitch_stats_groups call with a group
         per utterance, and its shift is pitch_shift[i] + (target - that mean) (alive_pitch_shift_groups), pitch_shift[i] alone if
         nothing is voiced.  A group's sums depend on its own rows only and are added in a fixed order, so an utterance converts
-        bitwise the same alone and inside any corpus.  A corpus without an auto utterance launches the present path."""
+        bitwise the same alone and inside any corpus.  A corpus without an auto utterance launches the present path.
+        auto_range (a bool, or one per utterance): utterance i's pitch excursions are scaled so that its own standard deviation meets
+        its target voice's (VoicePool.pitch_range; a blend: the weighted mean; ValueError for a voice without one).  ONE
+        alive_pitch_stats2_groups call over the same centre thirds gives each utterance's mean m and variance v; its intonation
+        becomes intonation[i] * clamp(target sd / sqrt(v), 1 / pitch_range_max, pitch_range_max) (alive_pitch_range_groups) and its
+        frames are scaled around m -- its OWN mean over all its windows, not each window's -- by
+        alive_pitch_transform_rows_centred; the shift stays what it is.  Utterances with the flag off keep the per-window
+        arithmetic in the same launch, bitwise; a corpus without an auto-range utterance launches the present path."""
         from . import multistream as MS
         m = len(utterances)
         voices = list(voices)
@@ -428,8 +436,15 @@ class Converter:
             raise ValueError(f"auto_pitch: {len(autos)} values for {m} utterances")
         if not all(isinstance(a, (bool, np.bool_)) for a in autos):
             raise ValueError(f"auto_pitch: expected bools, got {autos}")
+        ranged = list(auto_range) if isinstance(auto_range, (list, tuple)) else [auto_range] * m
+        if len(ranged) != m:
+            raise ValueError(f"auto_range: {len(ranged)} values for {m} utterances")
+        if not all(isinstance(a, (bool, np.bool_)) for a in ranged):
+            raise ValueError(f"auto_range: expected bools, got {ranged}")
+        pitch_range_max = MS.check_range_max(pitch_range_max, "convert_many: pitch_range_max")
         specs = [MS.blend_spec(v, pool, k if ks is None else ks[i]) for i, v in enumerate(voices)]
         targets = [pool.blend_register(*spec) if a else 0.0 for spec, a in zip(specs, autos)]      # (raises: a voice without one)
+        target_sds = [pool.blend_range(*spec) if a else 0.0 for spec, a in zip(specs, ranged)]     # (likewise)
         blended = any(len(names) > 1 for names, _ in specs)
         wins, totals, counts = [], [], []
         for u in utterances:
@@ -447,7 +462,7 @@ class Converter:
                       rate=rows(rates, torch.float32))
         if ks is not None:                  # each window's k; the blended search repeats it on the window's list rows (below)
             params["k"] = rows(ks, torch.int32)
-        if any(autos):                      # one group per utterance: its windows' rows, its offset, whether it is on, its target
+        if any(autos) or any(ranged):       # one group per utterance: its windows' rows, its offset, whether it is on, its target
             first = [0]
             for c in counts:
                 first.append(first[-1] + c)
@@ -455,6 +470,10 @@ class Converter:
                                   offset=torch.tensor(shifts, dtype=torch.float32, device=self.device),
                                   on=torch.tensor([int(bool(a)) for a in autos], dtype=torch.int32, device=self.device),
                                   target=torch.tensor(targets, dtype=torch.float32, device=self.device))
+        if any(ranged):                     # the same groups: each utterance's own intonation, whether it is on, its target range
+            params["range"] = dict(inton=torch.tensor(inton, dtype=torch.float32, device=self.device),
+                                   on=torch.tensor([int(bool(a)) for a in ranged], dtype=torch.int32, device=self.device),
+                                   sd=torch.tensor(target_sds, dtype=torch.float64, device=self.device))
         if not blended:                     # (one-voice blends are their voice: weight 1.0)
             params["ids"] = torch.repeat_interleave(pool.voice_ids([names[0] for names, _ in specs]), rep).contiguous()
         else:                               # compact list rows: window w of utterance i owns S_i of them, in blend order
@@ -491,7 +510,16 @@ class Converter:
                 f0[b].index_copy_(0, w, compute_f0(windows[b].index_select(0, w)))
 
         def transform(f0):                  # each utterance's pitch, intonation and f0 rate (features(world_pitch=True))
-            shift, au = params["shift"], params.get("auto")
+            shift, au, rg = params["shift"], params.get("auto"), params.get("range")
+            if rg is not None:              # three sums in one call; its first two columns are the auto-pitch call's, bit for bit
+                stats3 = MS.pitch_stats2_groups(f0, au["first"], chunk // 320, 2 * chunk // 320)
+                if any(autos):
+                    shift = MS.pitch_shift_groups(stats3[:, :2].contiguous(), au["first"], f0.shape[0], au["offset"], au["on"],
+                                                  au["target"])
+                it, centre, centre_on = MS.pitch_range_groups(stats3, au["first"], f0.shape[0], rg["inton"], rg["on"], rg["sd"],
+                                                              pitch_range_max)
+                MS.pitch_transform_rows_centred_(f0, 0, params["rate"], shift, it, centre, centre_on)
+                return
             if au is not None:              # the auto utterances' shifts from the raw f0 of their windows' centre thirds
                 stats = MS.pitch_stats_groups(f0, au["first"], chunk // 320, 2 * chunk // 320)
                 shift = MS.pitch_shift_groups(stats, au["first"], f0.shape[0], au["offset"], au["on"], au["target"])

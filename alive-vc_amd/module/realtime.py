@@ -135,13 +135,23 @@ def capture_step(device, step, phi):
 class RealtimeConverter:
     limiter = False                    # (set per converter in __init__: whether the step carries the limiter kernel)
     envelope = False                   # (likewise: whether the step carries the envelope kernel)
+    pitch_range = False                # (likewise: whether the f0 branch runs the pitch-range follower and the centred transform)
 
     def __init__(self, content_encoder, f0_estimator, decoder, library_tokens, device="cuda", chunk=960, buffersize=8,
                  input_sr=16000, output_sr=16000, f0_rate=1.0, pitch=0.0, k=4, alpha=0.0, gain=0.0, input_gain=0.0,
                  reuse_interior="auto", world_pitch=False, gate_db=None, gate_hold=0.2, gate_lookahead=None,
                  crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0, limit_hold_ms=20.0, limit_history=0.05,
-                 envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0, envelope_radius=1):
+                 envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0, envelope_radius=1, intonation=1.0,
+                 intonation_half_life=10.0, intonation_prior=0.5):
         self.device = torch.device(device)
+        from .multistream import check_intonation
+        self.intonation = check_intonation(1.0 if intonation is None else intonation, "RealtimeConverter: intonation")
+        self.pitch_range = self.intonation != 1.0           # (checked before anything is built)
+        if self.pitch_range:
+            if intonation_half_life is not None and not (np.isfinite(intonation_half_life) and intonation_half_life > 0):
+                raise ValueError(f"RealtimeConverter: intonation_half_life={intonation_half_life!r} must be > 0 seconds, or None")
+            if not (np.isfinite(intonation_prior) and intonation_prior >= 0):
+                raise ValueError(f"RealtimeConverter: intonation_prior={intonation_prior!r} must be >= 0 seconds")
         from .multistream import check_envelope
         env = check_envelope(0.0 if envelope is None else envelope, envelope_floor_db, envelope_range_db, envelope_radius)
         self.envelope = env[0] > 0         # (checked before anything is built)
@@ -230,6 +240,23 @@ class RealtimeConverter:
             self._env = env[1:]                # (floor_ms, g_lo, g_hi, radius)
             self._env_amount = torch.tensor([env[0]], dtype=torch.float32, device=self.device)
             self._env_out = None
+        if self.pitch_range:
+            # the multi-session pitch range at one row: an always-emitting session without auto pitch or auto range (there is no
+            # pool); _reg_state = (S, W, Q) is the stream's, like the phase
+            from .multistream import auto_constants
+            dev, i32, f32 = self.device, dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float32, device=self.device)
+            self._range_decay, self._range_prior = auto_constants(chunk / input_sr, buffersize, intonation_half_life,
+                                                                  intonation_prior)
+            self._reg_state = torch.zeros(1, 3, dtype=torch.float64, device=dev)
+            self._range_rate = torch.tensor([1.0 if world_pitch else f0_rate], **f32)
+            self._range_pitch = torch.tensor([pitch], **f32)
+            self._range_inton = torch.tensor([self.intonation], **f32)
+            self._range_off = torch.zeros(1, **i32)            # (auto_on and range_on: both off)
+            self._range_zero = torch.zeros(1, **f32)
+            self._range_sd = torch.zeros(1, dtype=torch.float64, device=dev)
+            self._range_emit = torch.ones(1, dtype=torch.bool, device=dev)
+            self._shift_eff, self._inton_eff = torch.zeros(1, **f32), torch.ones(1, **f32)
+            self._centre, self._centre_on = torch.zeros(1, **f32), torch.zeros(1, **i32)
         self._side = None                  # side stream of the f0 estimator (see _f0_on_side_stream)
         self._f0_bufs = {}
         # interior reuse: only where it is exact -- no resampling in front (the ring IS the 16 kHz signal), a shift of whole
@@ -244,6 +271,13 @@ class RealtimeConverter:
         if reuse_interior is True and self.world_pitch:
             raise ValueError("interior reuse cannot be combined with world_pitch: WORLD's f0 of a ring depends on the whole ring")
         if self.world_pitch:
+            fits = False
+        # intonation: every frame is scaled around the running mean of the step that transforms it, so a carried frame would keep an
+        # earlier step's centre -- interior reuse is off
+        if reuse_interior is True and self.pitch_range:
+            raise ValueError("interior reuse cannot be combined with intonation: the carried f0 frames were transformed around an "
+                             "earlier step's centre")
+        if self.pitch_range:
             fits = False
         if reuse_interior is True and not fits:
             raise ValueError("interior reuse needs input_sr 16000, chunk a multiple of 320 and a ring of at least 70 + chunk / 320 "
@@ -339,11 +373,24 @@ class RealtimeConverter:
         """f0_on_side_stream with the estimator's f0 and the pitch transform.  With world_pitch the branch is WORLD's f0 of the
         16-kHz ring `data` instead, and the pitch transform leaves out f0_rate: the reference multiplies only the estimator's f0
         by it (realtime_inference.py:153-156)."""
+        def ranged(f0):                    # the multi-session follower and centred transform at one row
+            from .multistream import pitch_follow2_rows_, pitch_transform_rows_centred_
+            emit = self._gate_follow if self.gate else self._range_emit     # (a gated stream's state learns from open ticks only)
+            pitch_follow2_rows_(f0, self._range_rate, self._range_pitch, self._range_off, self._range_zero, self._range_inton,
+                                self._range_off, self._range_sd, emit, self._range_decay, self._range_prior, 1.0,
+                                self._reg_state, self._shift_eff, self._inton_eff, self._centre, self._centre_on)
+            return pitch_transform_rows_centred_(f0, 1, self._range_rate, self._shift_eff, self._inton_eff, self._centre,
+                                                 self._centre_on)
+
         def body(buf):
             if self.world_pitch:
                 buf.copy_(compute_f0(data))
+                if self.pitch_range:
+                    return ranged(buf)
                 return ops.pitch_transform_(buf, 1, f0_rate=1.0, pitch_shift=self.pitch)
             f0 = self.pe.estimate(spec, out=buf)
+            if self.pitch_range:
+                return ranged(f0)
             return ops.pitch_transform_(f0, 1, f0_rate=self.f0_rate, pitch_shift=self.pitch)
         return f0_on_side_stream(self, spec, body)
 
@@ -406,6 +453,8 @@ class RealtimeConverter:
         self._g_phi.zero_()
         if self.gate:
             self._gate_state.zero_()       # (capture_step ran the step three times)
+        if self.pitch_range:
+            self._reg_state.zero_()
         if self.crossfade:
             self._seam_stored.zero_()
         self._limit_reset()
@@ -422,6 +471,8 @@ class RealtimeConverter:
             self._g_phi.zero_()
         if self.gate:
             self._gate_state.zero_()
+        if self.pitch_range:
+            self._reg_state.zero_()
         if self.crossfade:
             self._seam_stored.zero_()
         self._limit_reset()
@@ -470,7 +521,7 @@ class RealtimeConverter:
         self.phi = phi_next
         return wave
 
-    def _repeat_on_bf16(self, data, saved_phi, saved_gate=None, saved_seam=None, saved_limit=None):
+    def _repeat_on_bf16(self, data, saved_phi, saved_gate=None, saved_seam=None, saved_limit=None, saved_reg=None):
         """a chunk drove an activation out of fp16's range: switch the process to bf16 planes (ops.switch_to_bf16), restore the
         phase (and the gate state, and the crossfade's tail) the chunk started from, drop the frame caches, re-capture the step if it
         was a hipGraph, and convert the chunk again -- the whole front end, but crossfaded as the first attempt would have been"""
@@ -483,6 +534,8 @@ class RealtimeConverter:
             self.phi = saved_phi
         if saved_gate is not None:
             self._gate_state.copy_(saved_gate)
+        if saved_reg is not None:          # (after enable_graph, which zeroes it)
+            self._reg_state.copy_(saved_reg)
         if saved_seam is not None:
             self._seam_tail.copy_(saved_seam[0])
             self._seam_stored.copy_(saved_seam[1])
@@ -508,9 +561,10 @@ class RealtimeConverter:
             saved_gate = self._gate_state.clone() if self.gate else None
             saved_seam = (self._seam_tail.clone(), self._seam_stored.clone()) if self.crossfade else None
             saved_limit = (self._limit_hist.clone(), self._limit_gmin.clone()) if self.limiter else None
+            saved_reg = self._reg_state.clone() if self.pitch_range else None
         wave = self.step_device(data, continues=True)                # this ring is the previous one advanced by one chunk
         out = audio_io.float_to_pcm16(wave).cpu().numpy()            # C cast of numpy's astype, no clipping (:180-183)
         if guarded and ops.f16_saturations(reset=True) > 0:          # (the copy above has synchronised: six 4-byte reads)
-            out = self._repeat_on_bf16(data, saved_phi, saved_gate, saved_seam, saved_limit)
+            out = self._repeat_on_bf16(data, saved_phi, saved_gate, saved_seam, saved_limit, saved_reg)
         center = self.buffersize * self.chunk // 2
         return out[center - self.chunk // 2: center + self.chunk // 2]

@@ -12,6 +12,12 @@ The sessions file is a JSON list; each entry:
                                           voice's register (module/multistream.py "Auto pitch"); "pitch" is then an offset on top
    "register_hz": 180,                    optional: declares the register (mean f0 in Hz) of a voice given by "lib" alone, which
                                           has no audio to measure it on; a "target" wav's register is measured at enrolment
+   "intonation": 1.0,                     optional, a number >= 0 (default: -int): the session's pitch excursions around its running
+                                          mean pitch are scaled by it (module/multistream.py "Pitch range")
+   "auto_range": false,                   optional, a JSON bool (default: --auto-range): the excursions are also scaled so that the
+                                          source's running standard deviation meets the target voice's
+   "range_st": 2.5,                       optional, beside "register_hz": declares the pitch range (standard deviation in semitones)
+                                          of a voice given by "lib" alone; a "target" wav's range is measured at enrolment
    "gate_db": -40, "gate_hold": 0.2,      optional: the session's input gate (module/multistream.py "Input gate"): a threshold in
                                           dBFS on its 16 kHz ring after the input gain (null: no gate; default -thr) and the
                                           seconds it stays open after the last loud tick (default --gate-hold)
@@ -54,6 +60,9 @@ It is built with k_max = the largest "k" only if some session's "k" differs from
 before.  Sessions on one voice at different k take one pass over that voice per k.
 The converter carries the auto-pitch kernel, and the voices are given registers (measured with the f0 estimator on the target wavs),
 only if some session is on auto pitch: a file without "auto_pitch", run without --auto-pitch, runs as before.
+The converter is built with pitch_range=True, and the voices are given registers and ranges, only if some session ends up at an
+"intonation" other than 1 or on "auto_range" (or under -int / --auto-range): a file without the keys, run without the flags, runs as
+before.
 The converter carries the two gate kernels only if some session ends up gated ("gate_db", or -thr): a file without the keys, run
 without -thr, runs as before.
 The converter carries the seam kernel only if some session ends up with a crossfade ("crossfade_ms", or --crossfade): a file without
@@ -98,8 +107,8 @@ from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
 from module.multistream import (MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
-                                check_conceal_ms, check_crossfade_ms, check_envelope, check_limit, gate_hold_ticks, gate_thr_ms,
-                                measure_register)
+                                check_conceal_ms, check_crossfade_ms, check_envelope, check_intonation, check_limit,
+                                gate_hold_ticks, gate_thr_ms, measure_register)
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
 
@@ -113,6 +122,8 @@ CODEBOOK_KEYS = ("codebook",)            # taken per session too; a loaded sessi
 STALL_KEYS = ("stall",)                  # a loaded session carries it only when its entry has the key (the converter is then sparse)
 LOSE_KEYS = ("lose",)                    # likewise (the converter is then sparse and conceals)
 CONCEAL_KEYS = ("conceal",)              # likewise: the session's own switch
+RANGE_KEYS = ("intonation", "auto_range")    # a loaded session carries "intonation" only when it is not 1, "auto_range" only when on
+RANGE_ST_KEYS = ("range_st",)            # a loaded session carries it only when its entry has the key
 
 
 def build_parser():
@@ -134,6 +145,11 @@ def build_parser():
                              "removed after their last session (default: every voice is packed before tick 0)")
     parser.add_argument('--auto-pitch', action='store_true',
                         help="sessions follow their target voice's register unless their \"auto_pitch\" says otherwise")
+    parser.add_argument('-int', '--intonation', default=1.0, type=float,
+                        help="sessions scale their pitch excursions around their running mean pitch by this factor unless their "
+                             "\"intonation\" says otherwise (default 1: off)")
+    parser.add_argument('--auto-range', action='store_true',
+                        help="sessions match their target voice's pitch range unless their \"auto_range\" says otherwise")
     parser.add_argument('-thr', '--gate-db', default=None, type=float,
                         help="input gate: sessions mute (and skip their search) below this level in dBFS unless their \"gate_db\" "
                              "says otherwise (default: no gate)")
@@ -190,6 +206,44 @@ def register_hz_of(entry, where):
         raise ValueError(f"{where}: \"register_hz\" declares the register of a voice given by \"lib\" alone (a \"target\" wav's is "
                          "measured; a blend's comes from its voices)")
     return float(hz)
+
+
+def range_st_of(entry, where):
+    """an entry's "range_st" (None without one): a number of semitones > 0, for a voice given by "lib" alone"""
+    st = entry.get("range_st")
+    if st is None:
+        return None
+    if isinstance(st, bool) or not isinstance(st, (int, float)) or not 0 < st < float("inf"):
+        raise ValueError(f"{where}: \"range_st\" must be a number of semitones > 0, got {st!r}")
+    if "blend" in entry or entry.get("target") is not None or entry.get("lib") is None:
+        raise ValueError(f"{where}: \"range_st\" declares the pitch range of a voice given by \"lib\" alone (a \"target\" wav's is "
+                         "measured; a blend's comes from its voices)")
+    if entry.get("register_hz") is None:
+        raise ValueError(f"{where}: \"range_st\" goes beside \"register_hz\": a range is declared around a declared register")
+    return float(st)
+
+
+def declared_ranges(entries, name_of):
+    """{voice name: semitones} of the entries' "range_st"; ValueError if two entries declare different ones for one voice"""
+    out = {}
+    for i, e in enumerate(entries):
+        if e.get("range_st") is not None:
+            name = name_of(e)
+            if out.setdefault(name, e["range_st"]) != e["range_st"]:
+                raise ValueError(f"entry {i}: \"range_st\" {e['range_st']} but an earlier entry gave this voice {out[name]}")
+    return out
+
+
+def session_range(s, where, intonation=1.0, auto_range=False):
+    """an entry's pitch range settings -> (intonation, auto_range): "intonation" (default `intonation`) a finite number >= 0,
+    "auto_range" (default `auto_range`) a JSON bool; ValueError otherwise"""
+    it, on = s.get("intonation", intonation), s.get("auto_range", bool(auto_range))
+    if not isinstance(on, bool):
+        raise ValueError(f"{where}: \"auto_range\" must be true or false, got {on!r}")
+    try:
+        return check_intonation(it, "\"intonation\""), on
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
 
 
 def declared_registers(entries, name_of):
@@ -309,15 +363,17 @@ def supply_ticks(start, n_chunks, stall=None):
 
 def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None, crossfade_ms=None, limit_db=None,
                   limit_lookahead_ms=5.0, limit_hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0,
-                  envelope_radius=1, conceal_hold_ms=10.0, conceal_fade_ms=50.0, conceal_recover_ms=5.0):
+                  envelope_radius=1, conceal_hold_ms=10.0, conceal_fade_ms=50.0, conceal_recover_ms=5.0, intonation=1.0,
+                  auto_range=False):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
     condensed, "crossfade_ms" (default `crossfade_ms`) only on a session that crossfades, and "limit_db" / "limit_lookahead_ms" /
     "limit_hold_ms" (defaults `limit_db`, `limit_lookahead_ms`, `limit_hold_ms`) only on a session that limits, "envelope" (default
     `envelope`) only on a session that follows at an amount above 0, and "stall" (a sorted
-    tuple of ticks) only on a session whose entry has the key, as "lose" (a sorted tuple of ticks) and "conceal" (a bool); ValueError on
-    a malformed entry"""
+    tuple of ticks) only on a session whose entry has the key, as "lose" (a sorted tuple of ticks) and "conceal" (a bool); "intonation"
+    (default `intonation`) only on a session whose factor is not 1, "auto_range" (default `auto_range`) only on one that is on, and
+    "range_st" only where the entry has it; ValueError on a malformed entry"""
     try:
         check_conceal_ms(conceal_hold_ms, conceal_fade_ms, conceal_recover_ms)
     except ValueError as e:
@@ -329,6 +385,7 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     session_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, limit_lookahead_ms, limit_hold_ms)
     env = (envelope_floor_db, envelope_range_db, envelope_radius)
     session_envelope({}, "-env / --envelope-floor / --envelope-range / --envelope-radius", envelope, *env)
+    session_range({}, "-int / --auto-range", intonation, auto_range)
     with open(path) as f:
         sessions = json.load(f)
     if not isinstance(sessions, list) or not sessions:
@@ -339,10 +396,10 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
         unknown = (set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(CODEBOOK_KEYS)
-                   - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS))
+                   - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS) - set(RANGE_KEYS) - set(RANGE_ST_KEYS))
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS})")
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
@@ -359,6 +416,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
         sess_k = check_k(s["k"], f"session {i}: \"k\"") if "k" in s else k
         stall = session_stall(s, f"session {i}")
         lose, con = session_lose(s, f"session {i}"), session_conceal(s, f"session {i}")
+        inton, ranged = session_range(s, f"session {i}", intonation, auto_range)
+        range_st = range_st_of(s, f"session {i}")
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
                  gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
@@ -384,6 +443,12 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             e["lose"] = lose
         if con is not None:
             e["conceal"] = con
+        if inton != 1.0:
+            e["intonation"] = inton
+        if ranged:
+            e["auto_range"] = True
+        if range_st is not None:
+            e["range_st"] = range_st
         out.append(e)
     return out
 
@@ -536,7 +601,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook,
                              args.crossfade, args.limit, args.limit_lookahead, args.limit_hold, args.envelope, args.envelope_floor,
-                             args.envelope_range, args.envelope_radius, args.conceal_hold, args.conceal_fade, args.conceal_recover)
+                             args.envelope_range, args.envelope_radius, args.conceal_hold, args.conceal_fade, args.conceal_recover,
+                             args.intonation, args.auto_range)
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -548,8 +614,14 @@ def main(argv=None):
     Dec.load_state_dict(torch.load(args.decoder_path, map_location=device))
 
     # auto pitch: only then are the voices' registers measured (with the f0 estimator) or declared ("register_hz")
-    auto = any(s["auto_pitch"] for s in sessions)
-    declared = declared_registers(sessions, lambda s: voice_name(s["target"], s["lib"], s.get("codebook"))) if auto else {}
+    # pitch range: likewise the converter is built with pitch_range=True, and the voices measured, only if some session needs it
+    wants_range = any("intonation" in s or "auto_range" in s for s in sessions)
+    ranged = any("auto_range" in s for s in sessions)
+    on_auto = any(s["auto_pitch"] for s in sessions)
+    auto = on_auto or ranged                            # (the voices' registers, and with them their ranges, are measured)
+    name_of = lambda s: voice_name(s["target"], s["lib"], s.get("codebook"))      # noqa: E731
+    declared = declared_registers(sessions, name_of) if auto else {}
+    declared_st = declared_ranges(sessions, name_of) if ranged else {}
     pool, names = VoicePool(device=device, capacity=args.pool_rows), []
     for s in sessions:
         for target, lib in session_sources(s):
@@ -559,7 +631,7 @@ def main(argv=None):
                     tokens, register = voice_tokens_register(CE, PE, target, lib, device)
                     pool.add(name, condensed(tokens, s.get("codebook")), register)
                     if name in declared:
-                        pool.set_register(name, hz=declared[name])
+                        pool.set_register(name, hz=declared[name], range_st=declared_st.get(name))
                 else:
                     pool.add(name, condensed(voice_tokens(CE, target, lib, device), s.get("codebook")))
         names.append(session_voice(s))
@@ -570,7 +642,8 @@ def main(argv=None):
     conv = MultiStreamConverter(CE, PE, Dec, pool, slots, chunk=args.chunk, buffersize=args.buffersize, input_sr=args.input_sr,
                                 output_sr=args.output_sr, k=args.k, device=device, rates=sorted(set(in_sr)),
                                 world_pitch=any(s["world_pitch"] for s in sessions), blend=blend_size(sessions),
-                                k_max=converter_k_max(sessions, args.k), auto_pitch=auto,
+                                k_max=converter_k_max(sessions, args.k), auto_pitch=on_auto,
+                                **(dict(pitch_range=True) if wants_range else {}),
                                 **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}),
                                 **(dict(crossfade=True) if any("crossfade_ms" in s for s in sessions) else {}),
                                 **(dict(limiter=True) if any("limit_db" in s for s in sessions) else {}),
@@ -581,7 +654,7 @@ def main(argv=None):
                                         conceal_recover_ms=args.conceal_recover) if conceal else {}))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
-                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CONCEAL_KEYS if g in s})
+                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CONCEAL_KEYS + RANGE_KEYS if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()
@@ -604,7 +677,7 @@ def main(argv=None):
                 wav, sr = audio_io.load(target) if target is not None else (None, None)
                 enrol_voice(pool, name, CE, wav, sr, lib=lib, compact=True, f0_estimator=PE if auto else None, codebook=size)
                 if name in declared:
-                    pool.set_register(name, hz=declared[name])
+                    pool.set_register(name, hz=declared[name], range_st=declared_st.get(name))
 
         def after(tick):
             for name in [n for t, what, n in events if t == tick and what == "remove"]:

@@ -75,6 +75,9 @@ def build_parser():
                         help="the most the envelope follow turns a frame up or down (default 12)")
     parser.add_argument('--envelope-radius', default=1, type=int, metavar="FRAMES",
                         help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
+    parser.add_argument('-int', '--intonation', default=1.0, type=float,
+                        help="scale the pitch excursions around the stream's running mean pitch by this factor, as inference.py's -int "
+                             "does around a window's mean (default 1: off; module/multistream.py \"Pitch range\"; this build only)")
     parser.add_argument('-isr', '--input-sr', default=16000, type=int)
     parser.add_argument('-osr', '--output-sr', default=16000, type=int)
     parser.add_argument('-lsr', '--loopback-sr', default=16000, type=int)
@@ -122,7 +125,8 @@ def main(argv=None):
                            **(dict(limit_db=args.limit, limit_lookahead_ms=args.limit_lookahead, limit_hold_ms=args.limit_hold)
                               if args.limit is not None else {}),
                            **(dict(envelope=args.envelope, envelope_floor_db=args.envelope_floor, envelope_range_db=args.envelope_range,
-                                   envelope_radius=args.envelope_radius) if args.envelope else {}))
+                                   envelope_radius=args.envelope_radius) if args.envelope else {}),
+                           **(dict(intonation=args.intonation) if args.intonation != 1.0 else {}))
     if not args.no_graph:
         rt.enable_graph()        # the whole per-chunk device pipeline (~150 launches) captured once, replayed per chunk: same samples
     print("streaming: conversion running (Ctrl-C stops)")

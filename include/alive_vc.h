@@ -787,6 +787,41 @@ int alive_pitch_follow_rows(const float* f0, int N, int T, const float* f0_rate,
                             const float* target, const unsigned char* emit, double decay, double prior, double* state,
                             float* shift_out, void* stream);
 
+/* Pitch range (csrc/pitch_auto.hip): the second moment of the same pitch.  The conventions of "Auto pitch" hold: DEVICE pointers, no
+ * allocation or host read (graph-capturable), fp64 sums in the same fixed order.  Every fp64 operation is one of + - * / sqrt, rounded on
+ * its own, so a host restatement in the same order (tools/pitch_range_ref.py) agrees bit for bit.  The range factor of a group or row is
+ *   r = clamp(target_sd / sqrt(v), 1 / range_max, range_max),  r = 1 when v <= 0, target_sd <= 0 or either is not finite,
+ * with v the variance of the voiced pitch; range_max is finite and >= 1.
+ *   alive_pitch_stats2_groups  stats3[g] = (sum, count, sum of squares); components 0 and 1 are bitwise alive_pitch_stats_groups'
+ *   alive_pitch_range_groups   the offline counterpart of alive_pitch_shift_groups (inton: float [G]; target_sd: double [G]; range_on: int32 [G]):
+ *                              a group with range_on[g] != 0 and count > 0 has m = sum / count, v = sumsq / count - m * m, and its rows
+ *                              get inton_out = (float)((double)inton[g] * r), centre_out = (float)m, centre_on_out = 1; every other
+ *                              group's rows get inton_out = inton[g] bit for bit, centre_out = 0, centre_on_out = 0
+ *   alive_pitch_follow2_rows   alive_pitch_follow_rows on state3: double [N][3] = (S, W, Q) (inton: float [N]; target_sd: double [N]; range_on:
+ *                              int32 [N]).  Row n follows when auto_on[n], or range_on[n], or inton[n] != 1; a row that does not writes
+ *                              shift_out = offset[n] bit for bit, inton_out = 1, centre_out = 0, centre_on_out = 0 and leaves its state.
+ *                              A following row with emit[n] != 0 updates S and W as alive_pitch_follow_rows does (bitwise) and
+ *                              Q <- decay * Q + sum of voiced p_t^2.  Then, when W != 0: a = W / (W + prior), m = S / W,
+ *                              v = Q / W - m * m, r as above (1 when range_on[n] == 0), I = (double)inton[n] * r,
+ *                              inton_out = (float)(1 + a * (I - 1)), centre_out = (float)m, centre_on_out = (inton_out != 1), and on an
+ *                              auto_on row shift_out = offset[n] + (float)(a * (target[n] - m)) (alive_pitch_follow_rows' expression);
+ *                              any other row, and every row at W == 0, gives shift_out = offset[n]; W == 0 also gives inton_out = 1,
+ *                              centre_on_out = 0: the automatic parts grow from exactly 0
+ *   alive_pitch_transform_rows_centred   in place on f0[N][T]; centre: float [N], centre_on: int32 [N].  A row with centre_on[n] == 0 is
+ *                              bitwise that row of alive_pitch_transform_rows in the same mode; a row with centre_on[n] != 0 gets
+ *                              p = c + (p - c) * inton + shift in float32, each operation rounded, in either mode (f0_rate before in
+ *                              mode 1, after in mode 0; NaN and inf -> 0) */
+int alive_pitch_stats2_groups(const float* f0, int N, int T, int t_lo, int t_hi, const int* first, int G, double* stats3, void* stream);
+int alive_pitch_range_groups(const double* stats3, const int* first, int G, int N, const float* inton, const int* range_on,
+                             const double* target_sd, double range_max, float* inton_out, float* centre_out, int* centre_on_out,
+                             void* stream);
+int alive_pitch_follow2_rows(const float* f0, int N, int T, const float* f0_rate, const float* offset, const int* auto_on,
+                             const float* target, const float* inton, const int* range_on, const double* target_sd,
+                             const unsigned char* emit, double decay, double prior, double range_max, double* state3, float* shift_out,
+                             float* inton_out, float* centre_out, int* centre_on_out, void* stream);
+int alive_pitch_transform_rows_centred(float* f0, int N, int T, int mode, const float* f0_rate, const float* shift, const float* inton,
+                                       const float* centre, const int* centre_on, void* stream);
+
 /* Input gate of the streaming paths (csrc/gate.hip): which rows are live this tick, decided on the device, and the output edge.
  * All pointers are DEVICE pointers; no call allocates, synchronises or reads anything on the host; the grids depend on N and the
  * strides alone (graph-capturable: a captured call serves any settings).  No floating-point atomics.

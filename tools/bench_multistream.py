@@ -15,7 +15,11 @@ kmax8_uniform4_* every session at k = 4 through them (next to graph_tick_*: the 
 kmax8_mixed_* session s at k = (1, 2, 4, 8)[s % 4] -- on the shared voice that is one pass over the voice per k.  --auto-pitch adds
 the graph tick p50 / p99 of an auto_pitch=True converter with every session on auto pitch (auto_pitch_tick_*: one more small launch on
 the f0 side stream, alive_pitch_follow_rows; voice v_i is declared a register of 110 + 10 (i % 12) Hz) next to graph_tick_* of the same
-batch.  --gated adds, per fraction f, the graph tick p50 / p99 of a gate=True converter (the input gate: csrc/gate.hip) whose sessions all
+batch.  --pitch-range adds the graph tick p50 / p99 of a pitch_range=True converter with every session on auto pitch, auto range and an
+intonation of 1.2 (pitch_range_tick_*: alive_pitch_follow2_rows in place of alive_pitch_follow_rows and the centred transform in place
+of the plain one; voice v_i is also declared a range of 1.5 + 0.25 (i % 8) semitones) between two measurements of the auto_pitch=True
+converter with every session on auto pitch (pr_auto_pitch_tick_*, pr_auto_pitch_again_tick_*): the spread between those two is the
+yardstick for the difference.  --gated adds, per fraction f, the graph tick p50 / p99 of a gate=True converter (the input gate: csrc/gate.hip) whose sessions all
 carry a -40 dB gate, sessions s < round(f B) fed digital silence (their gates stay closed: no search for them) and the others the usual
 speech-level signal (their gates stay open), and the event-timed grouped search over the segment lengths that tick left in seg_len_eff
 (gated_<f>_tick_p50_ms / _p99_ms / _search_ms / _live_rows); and the gate=False converter a second time (gate_off_again_tick_*): the
@@ -61,7 +65,7 @@ search, the worst case; the clearing fill is timed alone and taken off), with ev
 alive_ring_push_rows with every row present (push_call_us).
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
-                                      [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch]
+                                      [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch] [--pitch-range]
                                       [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--out multistream.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
     python tools/bench_multistream.py --sparse [--batches 128,1024] [--ticks 40] [--out profiles/multistream_sparse_bench.json]
@@ -340,6 +344,9 @@ def main():
     ap.add_argument("--mixed-k", action="store_true", help="also time a k_max=8 converter: every session at k = 4, and an even "
                                                            "mix of k = 1, 2, 4, 8")
     ap.add_argument("--auto-pitch", action="store_true", help="also time an auto_pitch=True converter, every session on auto pitch")
+    ap.add_argument("--pitch-range", action="store_true", help="also time a pitch_range=True converter, every session on auto pitch, "
+                    "auto range and an intonation of 1.2, against an auto_pitch=True converter with every session on auto pitch, and that "
+                    "one once more for the run-to-run spread")
     ap.add_argument("--gated", default=None, help="comma-separated fractions: also time a gate=True converter, every session behind "
                                                   "a -40 dB gate and that fraction of them fed digital silence")
     ap.add_argument("--crossfade", action="store_true", help="also time a crossfade=True converter, every session crossfading over "
@@ -386,10 +393,11 @@ def main():
         return
     shared = make_pool(1, 1)
     distinct = make_pool(max(batches) + (2 if args.blend else 0), 2)
-    if args.auto_pitch:                                        # (host floats beside the voices: nothing else changes)
+    if args.auto_pitch or args.pitch_range:                    # (host floats beside the voices: nothing else changes)
         for pool in (shared, distinct):
             for i, name in enumerate(pool.segments):
-                pool.set_register(name, hz=110.0 + 10.0 * (i % 12))
+                pool.set_register(name, hz=110.0 + 10.0 * (i % 12),
+                                  **(dict(range_st=1.5 + 0.25 * (i % 8)) if args.pitch_range else {}))
     rows = []
     for chunk, bs in configs:
         period_ms = chunk / 16.0
@@ -458,6 +466,19 @@ def main():
                     rec["auto_pitch_tick_p50_ms"], rec["auto_pitch_tick_p99_ms"] = round(p50, 3), round(p99, 3)
                     rec["auto_pitch_real_time"] = p99 < period_ms
                     del ac
+                if args.pitch_range:                           # the same box, the same run: auto pitch only, pitch range, auto pitch again
+                    for name, kw, sess in (("pr_auto_pitch", dict(auto_pitch=True), dict(auto_pitch=True)),
+                                           ("pitch_range", dict(pitch_range=True), dict(auto_pitch=True, auto_range=True, intonation=1.2)),
+                                           ("pr_auto_pitch_again", dict(auto_pitch=True), dict(auto_pitch=True))):
+                        pc = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, **kw)
+                        for s in range(B):
+                            pc.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, **sess)
+                        pc.enable_graph()
+                        p50, p99 = time_ticks(pc, B, chunk, args.ticks, args.warmup + bs + 1, 300)
+                        rec[f"{name}_tick_p50_ms"], rec[f"{name}_tick_p99_ms"] = round(p50, 3), round(p99, 3)
+                        assert pc.captures == 1
+                        del pc
+                    rec["pitch_range_real_time"] = rec["pitch_range_tick_p99_ms"] < period_ms
                 for f in gated:
                     gc = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, gate=True)
                     silent = int(round(float(f) * B))
