@@ -33,6 +33,12 @@ The jobs file is a JSON list; each entry:
                                                             follow_envelope), at 16 kHz before the output resample and the gain; 0 or
                                                             null: the decoder's own level.  A jobs file without it, run without -env,
                                                             runs as before
+   "pitch_track": true,                                     optional, a JSON bool or {"weight": 1, "jump": 12} (default: -pt with
+                                                            --track-weight / --track-jump): the file's f0 is the Viterbi path over
+                                                            the f0 estimator's class scores of each window instead of their argmax
+                                                            (convert_many(pitch_track=); inference.py's -pt).  Not with
+                                                            "world_pitch".  --track-lo / --track-hi / --track-band hold for the
+                                                            whole run.  A jobs file without it, run without -pt, runs as before
    "blend": [{"target": "a.wav", "weight": 2},              instead of "target" / "lib": a weighted mix of 1 to 4 voices, each
              {"lib": "b.pt", "weight": 1}],                 component a voice source as above (module/multistream.py blend_spec)
    "output": "a_out.wav"}                                   optional: default <outdir>/<index>_<input name>.wav
@@ -51,13 +57,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from module import audio_io                                     # noqa: E402
+from module import audio_io, common                             # noqa: E402
 from module.multistream import MAX_K, blend_sources, check_k     # noqa: E402
 
 JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "world_pitch", "output",
             "blend", "k", "auto_pitch", "register_hz")
 ENVELOPE_KEYS = ("envelope",)            # likewise; a loaded job carries it only when it follows (an amount above 0)
 LIMIT_KEYS = ("limit_db",)               # taken per job too; a loaded job carries it only when it is limited
+TRACK_KEYS = ("pitch_track",)            # a loaded job carries it only when it tracks: {"weight": W, "jump": J}
 RANGE_KEYS = ("auto_range", "range_st")  # a loaded job carries "auto_range" only when it is on, "range_st" only when its entry has it
 
 
@@ -96,6 +103,7 @@ def build_parser():
     parser.add_argument('--envelope-radius', default=1, type=int, metavar="FRAMES",
                         help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV")
+    common.add_track_arguments(parser)      # (-pt: jobs track unless their "pitch_track" says otherwise)
     return parser
 
 
@@ -173,13 +181,39 @@ def job_envelope(j, where, envelope=0.0, floor_db=-60.0, range_db=12.0, radius=1
     return a if a > 0 else None
 
 
+def job_track(j, where, pitch_track=False, weight=common.TRACK_WEIGHT, jump=common.TRACK_JUMP):
+    """an entry's "pitch_track" (default `pitch_track`): true, false or {"weight": W, "jump": J} (defaults `weight`, `jump`) ->
+    {"weight": W, "jump": J} as floats, or None for a job that does not track; ValueError otherwise, and together with
+    "world_pitch" """
+    v = j.get("pitch_track", bool(pitch_track))
+    try:
+        base = dict(weight=common.track_param("weight", weight), jump=common.track_param("jump", jump))
+        if isinstance(v, dict):
+            unknown = set(v) - {"weight", "jump"}
+            if unknown:
+                raise ValueError(f"\"pitch_track\": unknown keys {sorted(unknown)} (weight, jump; lo, hi and band are flags of the run)")
+            base.update({key: common.track_param(key, val) for key, val in v.items()})
+        elif not isinstance(v, bool):
+            raise ValueError(f"\"pitch_track\" must be true, false or an object with weight / jump, got {v!r}")
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    if v is False:
+        return None
+    if j.get("world_pitch", False):
+        raise ValueError(f"{where}: \"pitch_track\" cannot be combined with \"world_pitch\"")
+    return base
+
+
 def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0,
-              envelope_range_db=12.0, envelope_radius=1, auto_range=False):
+              envelope_range_db=12.0, envelope_radius=1, auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT,
+              track_jump=common.TRACK_JUMP):
     """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder; "auto_pitch": default
     `auto_pitch`); a limited job ("limit_db", default `limit_db`) also carries "limit_db", a job without a limiter does not, so a
     file without the key loads to what it did; likewise "envelope" (default `envelope`) only on a job that follows at an amount above
-    0, "auto_range" (default `auto_range`) only on a job that is on and "range_st" only where the entry has it; ValueError on a
-    malformed job, before anything runs on the device"""
+    0, "auto_range" (default `auto_range`) only on a job that is on, "range_st" only where the entry has it and "pitch_track"
+    (default `pitch_track` at `track_weight` / `track_jump`) only on a job that tracks; ValueError on a malformed job, before anything
+    runs on the device"""
+    job_track({}, "-pt / --track-weight / --track-jump", pitch_track, track_weight, track_jump)
     job_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, lookahead_ms, hold_ms)
     env = (envelope_floor_db, envelope_range_db, envelope_radius)
     job_envelope({}, "-env / --envelope-floor / --envelope-range / --envelope-radius", envelope, *env)
@@ -195,9 +229,10 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
     for i, j in enumerate(jobs):
         if not isinstance(j, dict) or "input" not in j:
             raise ValueError(f"job {i}: an object with an \"input\" wav is required")
-        unknown = set(j) - set(JOB_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(RANGE_KEYS)
+        unknown = set(j) - set(JOB_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(RANGE_KEYS) - set(TRACK_KEYS)
         if unknown:
-            raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: {JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS})")
+            raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: "
+                             f"{JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS + TRACK_KEYS})")
         blend = blend_sources(j, f"job {i}", rel) if "blend" in j else None
         if blend is None and j.get("target") is None and j.get("lib") is None:
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
@@ -221,6 +256,9 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
             e["envelope"] = amount
         if j.get("auto_range", bool(auto_range)):
             e["auto_range"] = True
+        track = job_track(j, f"job {i}", pitch_track, track_weight, track_jump)
+        if track is not None:
+            e["pitch_track"] = track
         range_st = range_st_of(j, f"job {i}")
         if range_st is not None:
             e["range_st"] = range_st
@@ -278,8 +316,13 @@ def main(argv=None):
     device = torch.device(args.device)
     if device.type != "cuda":
         raise SystemExit("this build runs on the MI355X only: pass -d cuda")
+    try:
+        tw, tj, lo, hi, band = common.track_arguments(args)             # (before anything is loaded)
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
     jobs = load_jobs(args.jobs, args.k, args.auto_pitch, args.limit, args.limit_lookahead, args.limit_hold, args.envelope,
-                     args.envelope_floor, args.envelope_range, args.envelope_radius, args.auto_range)
+                     args.envelope_floor, args.envelope_range, args.envelope_radius, args.auto_range, args.pitch_track, tw, tj)
+    tracked = any("pitch_track" in j for j in jobs)
     on_auto = any(j["auto_pitch"] for j in jobs)
     ranged = any("auto_range" in j for j in jobs)
     auto = on_auto or ranged                            # only then are the voices' registers (and ranges) measured or declared
@@ -339,7 +382,9 @@ def main(argv=None):
                              intonation=[j["intonation"] for j in jobs], f0_rate=[j["f0_rate"] for j in jobs],
                              alpha=[j["alpha"] for j in jobs], world_pitch=[j["world_pitch"] for j in jobs],
                              auto_pitch=[j["auto_pitch"] for j in jobs] if on_auto else False,
-                             **(dict(auto_range=["auto_range" in j for j in jobs]) if ranged else {}), chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
+                             **(dict(auto_range=["auto_range" in j for j in jobs]) if ranged else {}),
+                             **(dict(pitch_track=[dict(j["pitch_track"], lo=lo, hi=hi, band=band) if "pitch_track" in j else None
+                                                  for j in jobs]) if tracked else {}), chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)
     for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
         if job.get("envelope"):                                         # at 16 kHz, against the source the converter saw

@@ -454,7 +454,8 @@ namespace {
 // the networks behind their input layers: b.x holds input_layer(spec) (content_encoder.py:22 / f0_estimator.py:23), t stands behind
 // the input layer's two table entries
 int ce_body(Table& t, EncBuffers& b, int N, int T, float* out, void* stream);
-int pe_body(Table& t, EncBuffers& b, int N, int T, float* f0, void* stream);
+// logits: nullptr, or the [N][4096][T] tensor that takes the classifier's product instead of the argmax (f0 is not written then)
+int pe_body(Table& t, EncBuffers& b, int N, int T, float* f0, void* stream, float* logits = nullptr);
 }  // namespace
 
 extern "C" size_t alive_content_encoder_workspace_bytes(int N, int T) { return enc_layout(nullptr, N, T, CE_C, CE_H, 0).bytes; }
@@ -487,8 +488,17 @@ extern "C" int alive_f0_estimate(const float* const* w, const float* spec, int N
     RUN(pw_conv(inW, inb, spec, b.Pa, N, T, BINS, PE_C, 3, 0, nullptr, b.x, stream));
     return pe_body(t, b, N, T, f0, stream);
 }
+// F0Estimator.forward through the same kernels: the classifier's product stored instead of reduced (pitch tracking reads it)
+extern "C" int alive_f0_logits(const float* const* w, const float* spec, int N, int T, float* logits, void* ws, void* stream) {
+    ALIVE_CHECK_ARG(w && spec && logits && ws && N > 0 && T > 0, "alive_f0_logits: bad args");
+    Table t(w);
+    EncBuffers b = enc_layout(ws, N, T, PE_C, PE_H, PE_OUT);
+    const float* inW = t.next(); const float* inb = t.next();
+    RUN(pw_conv(inW, inb, spec, b.Pa, N, T, BINS, PE_C, 3, 0, nullptr, b.x, stream));
+    return pe_body(t, b, N, T, nullptr, stream, logits);
+}
 namespace {
-int pe_body(Table& t, EncBuffers& b, int N, int T, float* f0, void* stream) {
+int pe_body(Table& t, EncBuffers& b, int N, int T, float* f0, void* stream, float* logits) {
     for (int i = 0; i < 4; ++i) {
         ConvNeXtW cw(t, false);
         RUN(convnext_layer(cw, b.x, b.y, b.h, b.Pa, b.Ph, N, PE_C, PE_H, T, nullptr, 0, 0, 0, 3, stream));
@@ -505,6 +515,10 @@ int pe_body(Table& t, EncBuffers& b, int N, int T, float* f0, void* stream) {
         gm.W = (const float*)((const unsigned short*)oW + (size_t)3 * ((PE_OUT + 15) & ~15) * ((PE_C + 31) & ~31));
         gm.bias = ob; gm.P = b.Pa; gm.N = N; gm.T = T; gm.Ci = PE_C; gm.Co = PE_OUT; gm.planes = 2; gm.act = 3;
         gm.f16s = 1; gm.wscale = ows; gm.in_unscale = 1.0f / F16S_ACT_SCALE;
+        if (logits != nullptr) {                            // the same GEMM, its product stored (alive_f0_logits)
+            gm.act = 0; gm.Y = logits;
+            return alive_gemm_planes(&gm, stream);
+        }
         gm.arg_val = b.lg;
         gm.arg_idx = (int32_t*)(b.lg + (size_t)nblk * cols);
         RUN(alive_gemm_planes(&gm, stream));
@@ -519,13 +533,18 @@ int pe_body(Table& t, EncBuffers& b, int N, int T, float* f0, void* stream) {
         AliveGemm g;
         memset(&g, 0, sizeof(g));
         g.W = oW; g.bias = ob; g.P = b.Pa; g.N = N; g.T = T; g.Ci = PE_C; g.Co = PE_OUT; g.planes = 3; g.act = 3;
+        if (logits != nullptr) {
+            g.act = 0; g.Y = logits;
+            return alive_gemm_planes(&g, stream);
+        }
         g.arg_val = b.lg;
         g.arg_idx = (int32_t*)(b.lg + (size_t)nblk * cols);
         RUN(alive_gemm_planes(&g, stream));
         return alive_argmax_merge(g.arg_val, g.arg_idx, nblk, cols, f0, stream);
     } else {
         RUN(alive_channel_norm(b.x, N, PE_C, T, g, of, NORM_EPS, b.y, stream));
-        RUN(pw_conv(oW, ob, b.y, b.Pa, N, T, PE_C, PE_OUT, 3, 0, nullptr, b.lg, stream));
+        RUN(pw_conv(oW, ob, b.y, b.Pa, N, T, PE_C, PE_OUT, 3, 0, nullptr, logits != nullptr ? logits : b.lg, stream));
+        if (logits != nullptr) return ALIVE_OK;
     }
     return alive_argmax_channels(b.lg, N, PE_OUT, T, f0, stream);
 }

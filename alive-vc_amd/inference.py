@@ -16,7 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from module import audio_io                                     # noqa: E402
+from module import audio_io, common                             # noqa: E402
 from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
@@ -80,6 +80,7 @@ def build_parser():
     parser.add_argument('--envelope-radius', default=1, type=int, metavar="FRAMES",
                         help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV (this build only)")
+    common.add_track_arguments(parser)
     return parser
 
 
@@ -97,6 +98,11 @@ def main(argv=None):
     if args.envelope != 0:
         from module.multistream import check_envelope, follow_envelope
         check_envelope(args.envelope, *env)                                  # (before anything is loaded)
+    track = None
+    if args.pitch_track:
+        if args.world_pitch_estimation:
+            raise SystemExit("-pt cannot be combined with -wpe: the tracker decodes the f0 estimator's class scores")
+        track = dict(zip(("weight", "jump", "lo", "hi", "band"), common.track_arguments(args)))      # (before anything is loaded)
 
     PE, CE, Dec = F0Estimator().to(device), ContentEncoder().to(device), Decoder().to(device)
     PE.load_state_dict(torch.load(args.f0_estimator_path, map_location=device))
@@ -130,7 +136,7 @@ def main(argv=None):
         out = conv.convert(wf, chunk=args.chunk, k=args.k, alpha=args.alpha, pitch_shift=args.pitch,
                            world_pitch=bool(args.world_pitch_estimation), intonation=args.intonation, f0_rate=args.f0_rate, window_batch=args.window_batch,
                            trim_context=not args.no_trim_context,
-                           share_overlap=None if args.no_share_overlap else "auto")
+                           share_overlap=None if args.no_share_overlap else "auto", **({} if track is None else dict(pitch_track=track)))
         if args.envelope > 0:                     # at 16 kHz, against the normalised mono source the converter saw
             out = follow_envelope(out, wf, None, args.envelope, *env)
         out = audio_io.resample(out, 16000, sr, post_gain_db=args.gain)            # resample, then gain (:136-137)

@@ -4,6 +4,7 @@
   compute_f0_dio(wf, sample_rate=8000, ...)           <- module/common.py:113-130 (pyworld.dio + stonemask, `-wpe`)
   compute_f0(wf, sample_rate=16000, segment_size=320) <- module/common.py:133-137
   compute_f0_rows(wf, row_on)                         compute_f0 of the rows a device mask switches on (the batched paths)
+  pitch_track(lo=50, hi=1100, band=2.0, device=)      the tables of the pitch tracker (F0Estimator.estimate(track=); no counterpart)
 
 runs on the MI355X through libalive_vc.so: fp6- (or fp8- / bf16-) MFMA candidate scoring with
 LDS-staged top-k' lists, exact fp32 rescoring, gather-mean-blend.  The library
@@ -483,6 +484,130 @@ def world_f0_rows(x, row_on, sample_rate=8000, f0_min=20.0, f0_max=4096.0, frame
     nat.check(lib.alive_world_f0_rows(nat.ptr(x), N, L8, *args, nat.ptr(taps), nat.ptr(row_on), nat.ptr(out), nat.ptr(ws),
                                       ws.numel(), nat.stream()), "alive_world_f0_rows")
     return out
+
+
+# ---- pitch tracking: a Viterbi path over the f0 estimator's class scores (csrc/f0_track.hip, DESIGN.md "Pitch tracking") -----------
+TRACK_LO, TRACK_HI, TRACK_BAND, TRACK_WEIGHT, TRACK_JUMP = 50, 1100, 2.0, 1.0, 12.0
+TRACK_MAX_STATES = 4000                         # ALIVE_F0_TRACK_MAX_STATES: two fp64 score columns in 64 KB of LDS
+_track_ws = nat.Workspace()
+
+
+def pitch_track_tables(lo=TRACK_LO, hi=TRACK_HI, band=TRACK_BAND):
+    """(semis float64 [S], band_lo int32 [S], band_hi int32 [S]) in NumPy: semis[i] = 12 log2(lo + i); band_lo / band_hi the first /
+    last state j with |semis[i] - semis[j]| <= band.  The device reads these very bits (no log2 runs there)."""
+    import numpy as np
+    if isinstance(lo, bool) or isinstance(hi, bool) or int(lo) != lo or int(hi) != hi:
+        raise ValueError(f"pitch track: lo and hi must be integers (classes in Hz), got {lo!r}, {hi!r}")
+    lo, hi = int(lo), int(hi)
+    if not 1 <= lo <= hi <= 4095:
+        raise ValueError(f"pitch track: needs 1 <= lo <= hi <= 4095 (class 0 is not a state), got lo {lo}, hi {hi}")
+    if hi - lo + 1 > TRACK_MAX_STATES:
+        raise ValueError(f"pitch track: {hi - lo + 1} states, at most {TRACK_MAX_STATES} (two fp64 score columns in 64 KB of LDS)")
+    if isinstance(band, bool) or not isinstance(band, (int, float)) or not (band >= 0.0 and band < float("inf")):
+        raise ValueError(f"pitch track: band must be a finite number of semitones >= 0, got {band!r}")
+    s = 12.0 * np.log2(np.arange(lo, hi + 1, dtype=np.float64))
+    n = s.size
+    blo, bhi = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+    for i0 in range(0, n, 256):                 # (semis ascends, so a band is one run of states)
+        near = np.abs(s[i0:i0 + 256, None] - s[None, :]) <= float(band)
+        blo[i0:i0 + 256] = near.argmax(axis=1)
+        bhi[i0:i0 + 256] = n - 1 - near[:, ::-1].argmax(axis=1)
+    return s, blo, bhi
+
+
+def track_param(name, v):
+    """a tracker weight / jump from the host: a finite float >= 0"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (v >= 0.0 and v < float("inf")):
+        raise ValueError(f"pitch track: {name} must be a finite number >= 0 (in the units of the class scores), got {v!r}")
+    return float(v)
+
+
+def track_options(value, what="pitch_track"):
+    """pitch_track=None | False | True | dict(weight=, jump=, lo=, hi=, band=) -> None, or the dict with every key filled in and checked"""
+    if value is None or value is False:
+        return None
+    if value is True:
+        value = {}
+    if not isinstance(value, dict):
+        raise ValueError(f"{what}: expected None, a bool or a dict of weight / jump / lo / hi / band, got {value!r}")
+    unknown = set(value) - {"weight", "jump", "lo", "hi", "band"}
+    if unknown:
+        raise ValueError(f"{what}: unknown keys {sorted(unknown)} (weight, jump, lo, hi, band)")
+    o = dict(weight=TRACK_WEIGHT, jump=TRACK_JUMP, lo=TRACK_LO, hi=TRACK_HI, band=TRACK_BAND)
+    o.update(value)
+    o["weight"], o["jump"] = track_param("weight", o["weight"]), track_param("jump", o["jump"])
+    return o
+
+
+class PitchTrack:
+    """the pitch tracker's converter-wide constants: the state classes lo .. hi, the band in semitones and their tables on `device`"""
+
+    def __init__(self, lo=TRACK_LO, hi=TRACK_HI, band=TRACK_BAND, device="cuda"):
+        s, blo, bhi = pitch_track_tables(lo, hi, band)          # (refuses before it touches the device)
+        self.lo, self.hi, self.band, self.states = int(lo), int(hi), float(band), int(s.size)
+        self.device = torch.device(device)
+        self.semis = torch.from_numpy(s).to(self.device)
+        self.band_lo, self.band_hi = torch.from_numpy(blo).to(self.device), torch.from_numpy(bhi).to(self.device)
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()    # once: other streams will read the tables
+
+    def rows(self, logits, f0, on=None, weight=TRACK_WEIGHT, jump=TRACK_JUMP, changed=None):
+        """alive_f0_track_rows: logits [N, C, T] fp32 -> the tracked classes over f0 [N, 1, T] (or [N, T]) in place, for the rows whose
+        on[r] (device int32 [N]; None: every row) is nonzero.  weight / jump: host scalars, or device float64 [N]; changed: a device
+        int32 [N] that receives, per row that is on, the number of frames that differ from what f0 held on entry.  No host
+        synchronisation and, with device arrays, no allocation once the stream's workspace exists: capturable"""
+        if logits.dim() != 3 or logits.dtype != torch.float32 or not logits.is_contiguous():
+            raise ValueError(f"pitch track: logits must be a contiguous fp32 [N, C, T] tensor, got {tuple(logits.shape)}")
+        n, c, t = logits.shape
+        if f0.dtype != torch.float32 or not f0.is_contiguous() or f0.numel() != n * t or f0.shape[0] != n or f0.shape[-1] != t:
+            raise ValueError(f"pitch track: f0 must be a contiguous fp32 [{n}, 1, {t}] tensor, got {tuple(f0.shape)}")
+        if self.hi >= c:
+            raise ValueError(f"pitch track: classes [{self.lo}, {self.hi}] outside the {c} class scores")
+        per_row = []
+        for name, v in (("weight", weight), ("jump", jump)):
+            if not torch.is_tensor(v):
+                v = torch.full((n,), track_param(name, v), dtype=torch.float64, device=logits.device)
+            elif v.dtype != torch.float64 or v.numel() != n or not v.is_contiguous():
+                raise ValueError(f"pitch track: {name} must be a contiguous float64 [{n}] device array")
+            per_row.append(v)
+        for name, v in (("on", on), ("changed", changed)):
+            if v is not None and (v.dtype != torch.int32 or v.numel() != n or not v.is_contiguous()):
+                raise ValueError(f"pitch track: {name} must be a contiguous int32 [{n}] device array")
+        L = nat.lib()
+        ws = _track_ws.get(L.alive_f0_track_workspace_bytes(n, t, self.states), logits.device)
+        nat.check(L.alive_f0_track_rows(nat.ptr(logits), n, c, t, self.lo, self.states, nat.ptr(self.semis), nat.ptr(self.band_lo),
+                                        nat.ptr(self.band_hi), nat.ptr(on), nat.ptr(per_row[0]), nat.ptr(per_row[1]), nat.ptr(f0),
+                                        nat.ptr(changed), nat.ptr(ws), nat.stream()), "alive_f0_track_rows")
+        return f0
+
+
+def pitch_track(lo=TRACK_LO, hi=TRACK_HI, band=TRACK_BAND, device="cuda"):
+    """the tracker object F0Estimator.estimate(track=) takes: state classes lo .. hi (Hz), band in semitones, tables on `device`"""
+    return PitchTrack(lo, hi, band, device)
+
+
+def add_track_arguments(parser):
+    """the pitch tracker's flags, the same in every CLI: -pt and --track-weight / --track-jump / --track-lo / --track-hi / --track-band"""
+    parser.add_argument('-pt', '--pitch-track', action='store_true',
+                        help="pitch tracking: f0 is the Viterbi path over the f0 estimator's class scores instead of their per-frame "
+                             "argmax (octave outliers of single frames are smoothed away; default: off; not with -wpe; this build only)")
+    parser.add_argument('--track-weight', default=TRACK_WEIGHT, type=float, metavar="W",
+                        help="pitch tracking: cost per semitone moved between two frames inside --track-band, in the units of the "
+                             f"class scores (default {TRACK_WEIGHT})")
+    parser.add_argument('--track-jump', default=TRACK_JUMP, type=float, metavar="J",
+                        help=f"pitch tracking: flat cost of any other move (default {TRACK_JUMP})")
+    parser.add_argument('--track-lo', default=TRACK_LO, type=int, metavar="HZ", help=f"pitch tracking: the lowest class (default {TRACK_LO})")
+    parser.add_argument('--track-hi', default=TRACK_HI, type=int, metavar="HZ",
+                        help=f"pitch tracking: the highest class, at most {TRACK_MAX_STATES} classes in all (default {TRACK_HI})")
+    parser.add_argument('--track-band', default=TRACK_BAND, type=float, metavar="SEMITONES",
+                        help=f"pitch tracking: the moves that cost by the semitone (default {TRACK_BAND})")
+
+
+def track_arguments(args):
+    """the parsed flags -> (weight, jump, lo, hi, band), checked before anything is loaded"""
+    pitch_track_tables(args.track_lo, args.track_hi, args.track_band)
+    return (track_param("--track-weight", args.track_weight), track_param("--track-jump", args.track_jump), int(args.track_lo),
+            int(args.track_hi), float(args.track_band))
 
 
 def linear_resize(x, size):

@@ -172,15 +172,29 @@ Lmax, 2 Lmax) samples (587 at 16 kHz: -c 160 -b 4 just fits).  Everything is dev
 conceal_state() reads the per-slot (run samples, period) back.  tools/conceal_ref.py restates the arithmetic bit for bit.  The defaults
 (10 ms, 50 ms, 5 ms) are design choices: with no trained weights, what this does to perceived quality is unmeasured.  Concealment audio
 for a STALL, concealing in feature space, jitter buffers and a voicing decision (the best lag is always used) are not part of it.
+
+Pitch tracking: the estimator's f0 is an independent argmax per frame, so one frame whose octave partner scores a little higher sends
+the oscillator up an octave for 20 ms.  A converter built with pitch_track=True (csrc/f0_track.hip) has the f0 branch store the
+estimator's class scores (F0Estimator.logits, into a buffer allocated once per shape), take their argmax as before and, for the sessions
+opened or set with pitch_track=True, overwrite the row with the Viterbi path over its scores: states are the classes track_lo ..
+track_hi, a move costs track_weight per semitone inside track_band semitones and track_jump flat otherwise, in fp64 in the units of the
+scores (tools/pitch_track_ref.py restates it bit for bit).  It runs before the WORLD select, the followers and the transform: auto pitch
+and pitch range learn from the tracked contour.  The ring is decoded again every tick and the emitted chunk lies 3.5 chunks inside it,
+so the tracker is a stateless fixed-lag smoother: nothing is carried across ticks, the bf16 repeat or a capture, and a row that sat a
+tick out is decoded again from its unchanged ring.  on, weight and jump are device arrays: toggling and retuning never re-capture, a
+converter built without pitch_track allocates nothing, launches exactly what it did and refuses pitch_track=True; not together with
+world_pitch on one session.  Class 0 is not a state: a tracked row never emits f0 = 0.  pitch_track_changed() reads back how many
+frames of each ring the tracker moved.  The defaults (1.0, 12.0, 2.0 semitones, 50 .. 1100 Hz) are design choices in logit units: with
+no trained weights, what tracking does to perceived quality is unmeasured.
 """
 import numpy as np
 import torch
 
 from . import _native as nat
-from . import audio_io, ops
+from . import audio_io, common, ops
 from .common import DIM, compute_f0_rows
 from .pipeline import prepare_networks
-from .realtime import capture_step, f0_on_side_stream, fp16_guarded, ring_geometry
+from .realtime import capture_step, f0_on_side_stream, fp16_guarded, ring_geometry, track_logits_buf
 from .spectrogram import spectrogram
 
 MAX_K = 8          # the grouped search keeps one register pair per lane and frame (csrc/knn.hip)
@@ -777,13 +791,26 @@ class VoicePool:
         return torch.tensor(ids, dtype=torch.int32, device=self.device)
 
 
-def measure_register(f0_estimator, wf16, world_pitch=False):
+def _track_call(pitch_track, world_pitch, device):
+    """enrolment's pitch_track= -> the keywords of F0Estimator.estimate ({} without it); not together with world_pitch"""
+    o = common.track_options(pitch_track)
+    if o is None:
+        return {}
+    if world_pitch:
+        raise ValueError("pitch_track cannot be combined with world_pitch: the tracker decodes the estimator's class scores")
+    return dict(track=common.pitch_track(o["lo"], o["hi"], o["band"], device), track_weight=o["weight"], track_jump=o["jump"])
+
+
+def measure_register(f0_estimator, wf16, world_pitch=False, pitch_track=None):
     """the register (sum of voiced pitch, voiced frames) of 16 kHz audio wf16 [1, L] on the device, as host floats: the f0 estimator's
     f0 of its spectrogram (world_pitch: WORLD's f0 of the audio) through alive_pitch_stats2_groups, one group, every frame: a
     Register, the 2-tuple it always was (bitwise alive_pitch_stats_groups') with the sum of squares as `.sumsq`.  One host read: for
-    enrolment, never inside a tick."""
+    enrolment, never inside a tick.  pitch_track (True, or dict(weight=, jump=, lo=, hi=, band=)): the register and the range are measured
+    on the tracked contour (F0Estimator.estimate(track=)), as a session with pitch_track hears its source."""
+    track = _track_call(pitch_track, world_pitch, wf16.device)
+
     def f0():
-        return compute_f0(wf16) if world_pitch else f0_estimator.estimate(spectrogram(wf16))
+        return compute_f0(wf16) if world_pitch else f0_estimator.estimate(spectrogram(wf16), **track)
     f = ops.Fp16Guard().run(f0)
     first = torch.tensor([0, f.shape[0]], dtype=torch.int32, device=f.device)
     s, c, q = pitch_stats2_groups(f, first)[0].tolist()
@@ -791,13 +818,14 @@ def measure_register(f0_estimator, wf16, world_pitch=False):
 
 
 def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="cuda", f0_estimator=None, world_pitch=False,
-                codebook=None, codebook_iters=10, codebook_seed=0):
+                codebook=None, codebook_iters=10, codebook_seed=0, pitch_track=None):
     """A voice's tokens as realtime_inference.py builds its library, as strided [768, m] parts and without a copy: the target
     utterance `wav` [channels, samples] at `sr` Hz -- resampled to 16 kHz, peak-normalised, first channel, content_encoder(
     spectrogram(.)), every `every`-th frame (a column-strided view of the encoder's output) -- then the tokens of `lib` (a voice
     library file, or its tokens [1, 768, M] / [768, M]).  The encoder runs under ops.Fp16Guard, as generate_voice_library.py's.
     f0_estimator= (auto pitch): returns (parts, register) instead, the register measured on the same 16 kHz audio the encoder saw
-    (measure_register; world_pitch: with WORLD's f0), None without a target wav.  Without it the call is what it was.
+    (measure_register; world_pitch: with WORLD's f0; pitch_track: on the tracked contour), None without a target wav.  Without it
+    the call is what it was.
     codebook=SIZE: the parts are condensed together, once, to one part of SIZE centroid rows (module/codebook.py build_codebook with
     codebook_iters and codebook_seed; a voice of SIZE rows or fewer stays as it is); the register is measured on the audio as before."""
     from .voice_library import VoiceLibrary
@@ -808,7 +836,7 @@ def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="c
         feats = ops.Fp16Guard().run(lambda: content_encoder(spectrogram(wf[:1])))
         parts.append(feats[0][:, ::every])
         if f0_estimator is not None:
-            register = measure_register(f0_estimator, wf[:1].contiguous(), world_pitch)
+            register = measure_register(f0_estimator, wf[:1].contiguous(), world_pitch, pitch_track)
     if lib is not None:
         if isinstance(lib, (str, bytes)) or hasattr(lib, "__fspath__"):
             VL = VoiceLibrary().to(device)
@@ -827,7 +855,7 @@ def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="c
 
 
 def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False, f0_estimator=None,
-                world_pitch=False, codebook=None, codebook_iters=10, codebook_seed=0):
+                world_pitch=False, codebook=None, codebook_iters=10, codebook_seed=0, pitch_track=None):
     """enrol_voice as a generator: the utterance is encoded once, then each next() appends one piece -- `add` for the first, `extend`
     for the rest -- and yields the voice's row count so far, so that a server can put a tick between the pieces.  If a piece is
     refused the voice is removed again (when no session holds it yet) and the error propagates.  f0_estimator=: the utterance's
@@ -842,7 +870,8 @@ def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
     if f0_estimator is None:
         parts = voice_parts(content_encoder, wav, sr, lib, every, pool.device, **cb)
     else:
-        parts, register = voice_parts(content_encoder, wav, sr, lib, every, pool.device, f0_estimator, world_pitch, **cb)
+        parts, register = voice_parts(content_encoder, wav, sr, lib, every, pool.device, f0_estimator, world_pitch,
+                                      pitch_track=pitch_track, **cb)
     total = sum(int(t.shape[1]) for t in parts)
     step = total if max_frames is None else int(max_frames)
     if compact and pool.largest_hole < min(step, total) <= pool.free_rows:
@@ -879,7 +908,7 @@ def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
 
 
 def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False, f0_estimator=None,
-                world_pitch=False, codebook=None, codebook_iters=10, codebook_seed=0):
+                world_pitch=False, codebook=None, codebook_iters=10, codebook_seed=0, pitch_track=None):
     """Enrol a voice into a reserved pool from audio, while sessions run on the pool's other voices: the recipe of voice_parts
     (multistream_inference.voice_tokens', under ops.Fp16Guard), appended through the strided alive_pool_append -- the encoder's
     output is never copied or concatenated.  The voice's rows are bitwise those of voice_tokens followed by `add`.
@@ -888,13 +917,14 @@ def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
     encoder's receptive field spans the whole utterance, so no cut of the AUDIO gives bitwise the frames of one call: the utterance
     is encoded once and its tokens are appended piece by piece, which is bitwise one call for any max_frames (a row and its norm
     depend on the row's own token alone).  compact=True: compact the pool first when the first piece fits its free rows but none
-    of its holes.  f0_estimator= (auto pitch): the voice also gets its register, measured on the same audio (voice_parts).
+    of its holes.  f0_estimator= (auto pitch): the voice also gets its register, measured on the same audio (voice_parts; with
+    pitch_track= on the tracked contour).
     codebook=SIZE (with codebook_iters, codebook_seed): the voice goes in as its SIZE-row codebook (module/codebook.py), bitwise
     `add(name, build_codebook(tokens, SIZE))`; `compact=` is about the pool's holes and has nothing to do with it.
     Returns the voice's row count."""
     rows = 0
     for rows in enrol_steps(pool, name, content_encoder, wav, sr, lib, every, max_frames, compact, f0_estimator, world_pitch,
-                            codebook, codebook_iters, codebook_seed):
+                            codebook, codebook_iters, codebook_seed, pitch_track):
         pass
     return rows
 
@@ -1684,7 +1714,8 @@ def db_scale(db):
 
 
 _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold",
-           "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope", "conceal", "intonation", "auto_range")
+           "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope", "conceal", "intonation", "auto_range",
+           "pitch_track", "track_weight", "track_jump")
 
 
 class MultiStreamConverter:
@@ -1696,13 +1727,22 @@ class MultiStreamConverter:
     sparse = False                     # (likewise: whether the rings live on the device and sessions may sit ticks out)
     envelope = False                   # (likewise: whether the tick carries the envelope kernel)
     conceal = False                    # (likewise: whether lost chunks are concealed in front of the ring push; needs sparse)
+    pitch_track = False                # (likewise: whether the f0 branch stores the class scores and carries the tracker kernel)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
                  auto_pitch_half_life=10.0, auto_pitch_prior=0.5, gate=False, gate_lookahead=None, crossfade=False,
                  limiter=False, limit_history=0.05, sparse=False, envelope=False, envelope_floor_db=-60.0,
                  envelope_range_db=12.0, envelope_radius=1, conceal=False, conceal_hold_ms=10.0, conceal_fade_ms=50.0,
-                 conceal_recover_ms=5.0, pitch_range=False, pitch_range_max=2.0):
+                 conceal_recover_ms=5.0, pitch_range=False, pitch_range_max=2.0, pitch_track=False, track_lo=50, track_hi=1100,
+                 track_band=2.0):
+        if not isinstance(pitch_track, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: pitch_track must be a bool, got {pitch_track!r}")
+        if pitch_track:                    # (checked before anything is built)
+            try:
+                common.pitch_track_tables(track_lo, track_hi, track_band)
+            except ValueError as e:
+                raise ValueError(f"MultiStreamConverter: {e}") from None
         if not isinstance(pitch_range, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: pitch_range must be a bool, got {pitch_range!r}")
         try:
@@ -1865,6 +1905,17 @@ class MultiStreamConverter:
             self.inton_eff = torch.ones(B, dtype=torch.float32, device=dev)
             self.centre = torch.zeros(B, dtype=torch.float32, device=dev)
             self.centre_on = torch.zeros(B, dtype=torch.int32, device=dev)
+        # pitch_track: the f0 branch stores the class scores and the tracker kernel is part of the tick (captured once); per row,
+        # track_on selects the Viterbi path over the scores instead of their argmax, at the session's weight and jump.  No state: the
+        # whole ring is decoded again every tick.  The logits buffer is allocated once per shape, by the first tick
+        self.pitch_track = bool(pitch_track)
+        if self.pitch_track:
+            self._track = common.pitch_track(track_lo, track_hi, track_band, dev)
+            self.track_on = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.track_weight = torch.full((B,), common.TRACK_WEIGHT, dtype=torch.float64, device=dev)
+            self.track_jump = torch.full((B,), common.TRACK_JUMP, dtype=torch.float64, device=dev)
+            self.track_changed = torch.zeros(B, dtype=torch.int32, device=dev)
+            self._track_bufs = {}
         # gate: the two gate kernels are part of the tick (captured once); per row, gate_on switches the session's gate, and the tick
         # reads seg_len_eff / world_eff / follow where it read seg_len / world_on / emit.  gate_state is the session's, like phi
         self.gate = bool(gate)
@@ -2102,6 +2153,31 @@ class MultiStreamConverter:
             raise ValueError("conceal_state needs a converter built with MultiStreamConverter(..., sparse=True, conceal=True)")
         return [(q, P) if self.is_open[b] and q > 0 else (0, 0) for b, (q, P) in enumerate(self._conceal_state.tolist())]
 
+    def _session_track(self, slot, p):
+        """a session's tracker settings -> (on, weight, jump), checked against the converter"""
+        on = p.get("pitch_track", False)
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"slot {slot}: pitch_track must be a bool, got {on!r}")
+        try:
+            w, j = (common.track_param("track_weight", p.get("track_weight", common.TRACK_WEIGHT)),
+                    common.track_param("track_jump", p.get("track_jump", common.TRACK_JUMP)))
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+        if on and not self.pitch_track:
+            raise ValueError(f"slot {slot}: pitch_track=True needs a converter built with MultiStreamConverter(..., pitch_track=True)")
+        if on and p.get("world_pitch", False):
+            raise ValueError(f"slot {slot}: pitch_track cannot be combined with world_pitch: the tracker decodes the estimator's "
+                             "class scores")
+        return int(bool(on)), w, j
+
+    def pitch_track_changed(self):
+        """how many frames of each slot's ring the tracker moved off the per-frame argmax in the latest tick, a list of B ints; 0 for
+        a slot that does not track (or is closed).  One host read"""
+        if not self.pitch_track:
+            raise ValueError("pitch_track_changed needs a converter built with MultiStreamConverter(..., pitch_track=True)")
+        moved = self.track_changed.tolist()
+        return [moved[b] if self.is_open[b] and self.params[b].get("pitch_track", False) else 0 for b in range(self.B)]
+
     def _session_gate(self, slot, p):
         """a session's gate settings -> (on, thr_ms, hold_ticks), checked against the converter"""
         db, hold = p.get("gate_db"), p.get("gate_hold", 0.2)
@@ -2123,6 +2199,7 @@ class MultiStreamConverter:
         limit = self._session_limit(slot, p, rate)
         env = self._session_envelope(slot, p)
         con = self._session_conceal(slot, p, rate)
+        track = self._session_track(slot, p)
         names, weights = blend_spec(p["voice"], self.pool, k, self.S)
         world = p["world_pitch"]
         if not isinstance(world, (bool, np.bool_)):
@@ -2170,6 +2247,10 @@ class MultiStreamConverter:
         self.out_pre[slot] = db_scale(p["gain"])
         if self.world_pitch:
             self._set_world(slot, bool(world), float(p["f0_rate"]))
+        if self.pitch_track:
+            self.track_on[slot], self.track_weight[slot], self.track_jump[slot] = track
+            if not track[0]:
+                self.track_changed[slot] = 0
         if self.auto_pitch:
             self.auto_on[slot] = int(bool(auto))
             self.target[slot] = target if auto else 0.0
@@ -2254,7 +2335,8 @@ class MultiStreamConverter:
 
     def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None,
              auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0,
-             limit_hold_ms=20.0, envelope=0.0, conceal=None, intonation=1.0, auto_range=False):
+             limit_hold_ms=20.0, envelope=0.0, conceal=None, intonation=1.0, auto_range=False, pitch_track=False, track_weight=1.0,
+             track_jump=12.0):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
@@ -2276,7 +2358,11 @@ class MultiStreamConverter:
         intonation (other than 1: needs a pitch_range=True converter): a finite factor >= 0 on the session's pitch excursions around
         its running mean pitch, growing from 1 with the evidence as the automatic shift does.  auto_range=True (needs such a converter
         and a range on every voice of the session): the factor is multiplied by target sd / running source sd, within [1 /
-        pitch_range_max, pitch_range_max] -- with auto_pitch, the mean-variance transform of log-f0"""
+        pitch_range_max, pitch_range_max] -- with auto_pitch, the mean-variance transform of log-f0.
+        pitch_track=True (needs a pitch_track=True converter; not together with world_pitch): the session's f0 is the Viterbi path over
+        the estimator's class scores of its ring instead of their per-frame argmax, at track_weight per semitone moved inside the
+        converter's band and track_jump for any other move (both >= 0, in the units of the scores); the followers and the transform see
+        the tracked contour"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
@@ -2285,7 +2371,8 @@ class MultiStreamConverter:
         p = dict(voice=voice, pitch=pitch, f0_rate=f0_rate, alpha=alpha, gain=gain, input_gain=input_gain, world_pitch=world_pitch,
                  k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold, crossfade_ms=crossfade_ms, limit_db=limit_db,
                  limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms, envelope=envelope, conceal=conceal,
-                 intonation=intonation, auto_range=auto_range)
+                 intonation=intonation, auto_range=auto_range, pitch_track=pitch_track, track_weight=track_weight,
+                 track_jump=track_jump)
         self._apply(slot, p, rate)                            # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -2306,7 +2393,8 @@ class MultiStreamConverter:
 
     def set(self, slot, **params):
         """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
-        intonation, auto_range, gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms, limit_hold_ms, envelope, conceal; the gate's state, the saved tail and the
+        intonation, auto_range, pitch_track, track_weight, track_jump, gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms,
+        limit_hold_ms, envelope, conceal; the gate's state, the saved tail and the
         limiter's history are kept: a longer crossfade fades over what the tail holds this tick and in full from the next, and a
         limiter switched on or retuned sees the required gains of the samples already emitted).
         The running source register is kept: a new voice changes the target only, and auto_pitch=True after False resumes from
@@ -2339,6 +2427,9 @@ class MultiStreamConverter:
         self.phi[slot] = 0.0
         if self.world_pitch:
             self._set_world(slot, False, 1.0)
+        if self.pitch_track:
+            self.track_on[slot], self.track_changed[slot] = 0, 0
+            self.track_weight[slot], self.track_jump[slot] = common.TRACK_WEIGHT, common.TRACK_JUMP
         if self.auto_pitch:
             self.auto_on[slot] = 0
             self.target[slot] = 0.0
@@ -2445,9 +2536,16 @@ class MultiStreamConverter:
     # ------------------------------------------------------------------ device step
     def _f0_on_side_stream(self, spec, data):
         """realtime.f0_on_side_stream with the per-row pitch transform.  world_pitch: after the estimator, the masked WORLD f0 of
-        the 16-kHz rings `data` (rows off: no work), selected per row, then the transform at the effective rates"""
+        the 16-kHz rings `data` (rows off: no work), selected per row, then the transform at the effective rates.  pitch_track: the
+        estimator stores its class scores, their argmax goes to the buffer as without it, and the tracker overwrites the rows that are
+        on -- before the WORLD select, the followers and the transform"""
         def body(buf):
-            f0 = self.pe.estimate(spec, out=buf)
+            if self.pitch_track:
+                f0 = self.pe.estimate(spec, out=buf, track=self._track, track_on=self.track_on, track_weight=self.track_weight,
+                                      track_jump=self.track_jump, logits_out=track_logits_buf(self, spec, self.pe),
+                                      changed=self.track_changed)
+            else:
+                f0 = self.pe.estimate(spec, out=buf)
             rate = self.f0_rate
             if self.world_pitch:
                 world_on = self.world_eff if self.gate else (self.world_tick if self.sparse else self.world_on)
@@ -2486,6 +2584,11 @@ class MultiStreamConverter:
         spec = spectrogram(data)
         f0, join = self._f0_on_side_stream(spec, data)
         content = self.ce(spec)
+        if self.pitch_track:
+            # the f0 branch ends before the search is launched: the grouped scan fills the chip exactly once, and tracker blocks that
+            # are resident while it is placed put part of its blocks out of step with the rest (measured: 38.2 -> 41 - 45 ms at B = 128,
+            # -c 960 -b 8, for a tracker call of 0.6 ms; DESIGN.md 5.4 "Pitch tracking")
+            join()
         K = self.k_max
         if self.S == 1:
             if K is None:

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from . import common
 from .common import PackedLibrary, compute_f0, merge_gather
 from .content_encoder import ContentEncoder
 from .decoder import Decoder
@@ -128,13 +129,36 @@ class Converter:
             return
         lib.use_subspace(w, b)
 
-    def features(self, windows, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, frames=None, out=None, world_pitch=False):
+    def _pitch_track(self, lo, hi, band):
+        """the tracker tables of (lo, hi, band) on this converter's device, built once"""
+        cache = self.__dict__.setdefault("_pitch_tracks", {})
+        key = (int(lo), int(hi), float(band))
+        if key not in cache:
+            cache[key] = common.pitch_track(lo, hi, band, self.device)
+        return cache[key]
+
+    def features(self, windows, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, frames=None, out=None, world_pitch=False,
+                 pitch_track=None):
         """spectrogram -> f0 (+ per-window pitch transform) and content features   (inference.py:112-128).
         frames = (lo, hi): content features are only needed on [lo, hi) (context trimming): the encoder runs on that range
         plus its own receptive field; the other frames come back as zeros.  f0 always covers the whole window (the pitch
         transform uses the window's mean pitch, the oscillator accumulates phase from the first frame).
         world_pitch: f0 is WORLD's DIO + StoneMask of each whole window (common.compute_f0, reference inference.py:113-114) and the
-        f0 estimator does not run."""
+        f0 estimator does not run.
+        pitch_track (common.track_options): the f0 of each whole window is the Viterbi path over the estimator's class scores
+        (F0Estimator.estimate(track=), csrc/f0_track.hip) instead of their per-frame argmax, before the pitch transform."""
+        if pitch_track is not None:
+            if world_pitch:
+                raise ValueError("pitch_track cannot be combined with world_pitch: the tracker decodes the estimator's class scores")
+            o = pitch_track
+            spec = spectrogram(windows)
+            f0 = self.pe.estimate(spec, out=None if out is None else out[1], track=self._pitch_track(o["lo"], o["hi"], o["band"]),
+                                  track_weight=o["weight"], track_jump=o["jump"])
+            f0 = ops.pitch_transform_(f0, 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
+            feat = self._encode(spec, frames)
+            if out is not None:
+                out[0].copy_(feat)
+            return feat, f0
         if world_pitch:
             f0 = ops.pitch_transform_(compute_f0(windows), 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
             feat = self._encode(spectrogram(windows), frames)
@@ -260,7 +284,7 @@ class Converter:
         return None                       # one process, one decision (ShardedConverter: max over the ranks)
 
     def _convert_windows(self, windows, k=4, alpha=0.0, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, window_batch=64,
-                         keep_frames=None, share_overlap=None, world_pitch=False):
+                         keep_frames=None, share_overlap=None, world_pitch=False, pitch_track=None):
         """windows [n, L] on the device -> waveforms [n, L]; L a multiple of 320.
         Networks run in batches of `window_batch` windows (bounded scratch); the kNN match runs ONCE over the frames
         of all windows, so every library tile streamed from L2 is used by as many frames as possible.
@@ -269,7 +293,15 @@ class Converter:
         samples are bitwise the same as without it (the other frames of the window decode from unmatched features).
         world_pitch=True: f0 is WORLD's (DIO + StoneMask) of every whole window instead of the f0 estimator's, as `-wpe` does
         (reference inference.py:113-114); WORLD is not local (mean removal and contour fixing span the window), so overlap
-        sharing is not used with it (the per-window path gives the same samples) and trimming applies to the content only."""
+        sharing is not used with it (the per-window path gives the same samples) and trimming applies to the content only.
+        pitch_track=True | dict(weight=, jump=, lo=, hi=, band=): the f0 of every whole window is the Viterbi path over the
+        estimator's class scores (features); it rides where world_pitch does -- per-window front end, no overlap sharing, f0
+        over the whole window also with keep_frames -- and cannot be combined with it."""
+        pitch_track = common.track_options(pitch_track)
+        if pitch_track is not None and world_pitch:
+            raise ValueError("pitch_track cannot be combined with world_pitch: the tracker decodes the estimator's class scores")
+        if pitch_track is not None:
+            self._pitch_track(pitch_track["lo"], pitch_track["hi"], pitch_track["band"])        # (refuses a bad range before any launch)
         n, L = windows.shape
         lf = L // 320
         # (the edge blocks of all windows form one launch of n x 30 frame columns: below 96 columns the library would switch
@@ -278,7 +310,7 @@ class Converter:
         rng = _decoded_range(keep_frames, lf)
         # sharing and trimming together need the trimmed range to consist of interior frames of the signal (it does for the
         # centre third of a 3-chunk window from 46 frames per chunk on); otherwise trimming alone is used -- same samples
-        share_ok = bool(share_overlap) and n * (EDGE + NET_MARGIN) >= 96 and not world_pitch
+        share_ok = bool(share_overlap) and n * (EDGE + NET_MARGIN) >= 96 and not world_pitch and pitch_track is None
         if share_ok and (rng is None or (EDGE <= rng[0] and rng[1] <= lf - EDGE and rng[1] - rng[0] >= 5)):
             # share_overlap = windows per signal (make_windows order): front end once per signal, decoder per window
             feat, f0 = self.features_shared(windows, int(share_overlap), k, alpha, frames=rng)
@@ -288,9 +320,11 @@ class Converter:
         def encode(i, feat, f0):                            # the pitch transform included (features)
             b = slice(i, i + window_batch)
             if rng is None:                                 # the networks write straight into the batch's slices
-                self.features(windows[b], pitch_shift, intonation, f0_rate, out=(feat[b], f0[b]), world_pitch=world_pitch)
+                self.features(windows[b], pitch_shift, intonation, f0_rate, out=(feat[b], f0[b]), world_pitch=world_pitch,
+                              pitch_track=pitch_track)
             else:
-                feat[b], f0[b] = self.features(windows[b], pitch_shift, intonation, f0_rate, frames=rng, world_pitch=world_pitch)
+                feat[b], f0[b] = self.features(windows[b], pitch_shift, intonation, f0_rate, frames=rng, world_pitch=world_pitch,
+                                               pitch_track=pitch_track)
 
         def match(feat):                                    # (ShardedConverter overrides self.match)
             if rng is None:
@@ -375,7 +409,7 @@ class Converter:
 
     def convert_many(self, utterances, pool, voices, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, alpha=0.0, chunk=48000, k=4,
                      window_batch=64, trim_context=False, world_pitch=False, auto_pitch=False, auto_range=False,
-                     pitch_range_max=2.0):
+                     pitch_range_max=2.0, pitch_track=None):
         """Many-to-many batch conversion: utterance i (16 kHz, [L] or [1, L], any length) to voice voices[i] of `pool`
         (module/multistream.py: VoicePool), with per-utterance pitch_shift / intonation / f0_rate / alpha / world_pitch (a scalar
         applies to every utterance; world_pitch: WORLD's f0 of each whole window, as convert(world_pitch=True)).  Returns one [1, L_i] waveform per utterance.  The windows of ALL utterances form one batch (a network
@@ -404,7 +438,13 @@ class Converter:
         becomes intonation[i] * clamp(target sd / sqrt(v), 1 / pitch_range_max, pitch_range_max) (alive_pitch_range_groups) and its
         frames are scaled around m -- its OWN mean over all its windows, not each window's -- by
         alive_pitch_transform_rows_centred; the shift stays what it is.  Utterances with the flag off keep the per-window
-        arithmetic in the same launch, bitwise; a corpus without an auto-range utterance launches the present path."""
+        arithmetic in the same launch, bitwise; a corpus without an auto-range utterance launches the present path.
+        pitch_track (None / a bool / dict(weight=, jump=), or one per utterance): utterance i's f0 is the Viterbi path over the
+        estimator's class scores of each of its whole windows, as convert(pitch_track=...) of it alone (lo, hi and band are call-wide:
+        the tracked utterances must agree on them; not together with world_pitch).  Per window batch, the class scores of the tracked
+        windows are stored (F0Estimator.logits) and alive_f0_track_rows overwrites their f0 rows, each with its utterance's weight
+        and jump, before the transform -- auto pitch and auto range measure the tracked contour.  A row's path depends on its own
+        scores only; a corpus without a tracked utterance launches the present path."""
         from . import multistream as MS
         m = len(utterances)
         voices = list(voices)
@@ -431,6 +471,18 @@ class Converter:
             raise ValueError(f"world_pitch: {len(worlds)} values for {m} utterances")
         if not all(isinstance(w, (bool, np.bool_)) for w in worlds):
             raise ValueError(f"world_pitch: expected bools, got {worlds}")
+        tracks = list(pitch_track) if isinstance(pitch_track, (list, tuple)) else [pitch_track] * m
+        if len(tracks) != m:
+            raise ValueError(f"pitch_track: {len(tracks)} values for {m} utterances")
+        tracks = [common.track_options(t, f"convert_many: pitch_track[{i}]") for i, t in enumerate(tracks)]
+        if any(t is not None and w for t, w in zip(tracks, worlds)):
+            raise ValueError("pitch_track cannot be combined with world_pitch on the same utterance")
+        tracker = None
+        if any(t is not None for t in tracks):
+            wide = {(t["lo"], t["hi"], t["band"]) for t in tracks if t is not None}
+            if len(wide) != 1:
+                raise ValueError(f"pitch_track: lo, hi and band are call-wide, the tracked utterances ask for {sorted(wide)}")
+            tracker = self._pitch_track(*wide.pop())
         autos = list(auto_pitch) if isinstance(auto_pitch, (list, tuple)) else [auto_pitch] * m
         if len(autos) != m:
             raise ValueError(f"auto_pitch: {len(autos)} values for {m} utterances")
@@ -495,6 +547,25 @@ class Converter:
         on = [bool(w) for w, c in zip(worlds, counts) for _ in range(c)]
         params["world"] = {i: torch.tensor([j - i for j in range(i, min(i + window_batch, len(on))) if on[j]], dtype=torch.int64,
                                            device=self.device) for i in range(0, len(on), window_batch) if any(on[i:i + window_batch])}
+        # the tracked windows of every window batch, with their rows' weight and jump.  The class scores of the selected windows are
+        # stored: when they are fewer than the 96 frame columns of the plane path, the whole batch is selected and the mask picks
+        # the rows (the scores then come from the same kernels as the f0 of the batch)
+        params["track"] = {}
+        if tracker is not None:
+            per_win = [t for t, c in zip(tracks, counts) for _ in range(c)]
+            lf_ = windows.shape[1] // 320
+            for i in range(0, len(per_win), window_batch):
+                part = per_win[i:i + window_batch]
+                sel = [j for j, t in enumerate(part) if t is not None]
+                if not sel:
+                    continue
+                if len(sel) * lf_ < 96:
+                    sel = list(range(len(part)))
+                params["track"][i] = dict(
+                    sel=torch.tensor(sel, dtype=torch.int64, device=self.device),
+                    on=torch.tensor([int(part[j] is not None) for j in sel], dtype=torch.int32, device=self.device),
+                    weight=torch.tensor([part[j]["weight"] if part[j] else 0.0 for j in sel], dtype=torch.float64, device=self.device),
+                    jump=torch.tensor([part[j]["jump"] if part[j] else 0.0 for j in sel], dtype=torch.float64, device=self.device))
         rng = _decoded_range((chunk // 320, 2 * chunk // 320) if trim_context else None, windows.shape[1] // 320)
 
         def encode(i, feat, f0):
@@ -508,6 +579,11 @@ class Converter:
             w = params["world"].get(i)
             if w is not None:               # WORLD's f0 of the whole windows replaces the estimator's (same stream: after it)
                 f0[b].index_copy_(0, w, compute_f0(windows[b].index_select(0, w)))
+            tr = params["track"].get(i)
+            if tr is not None:              # the tracked windows' paths replace the argmax (same stream: after it)
+                sub = f0[b].index_select(0, tr["sel"])
+                tracker.rows(self.pe.logits(spectrogram(windows[b].index_select(0, tr["sel"]))), sub, tr["on"], tr["weight"], tr["jump"])
+                f0[b].index_copy_(0, tr["sel"], sub)
 
         def transform(f0):                  # each utterance's pitch, intonation and f0 rate (features(world_pitch=True))
             shift, au, rg = params["shift"], params.get("auto"), params.get("range")

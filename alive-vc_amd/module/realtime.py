@@ -29,7 +29,7 @@ stateless function of the step's ring and wave: nothing is kept between steps.  
 import numpy as np
 import torch
 
-from . import audio_io, ops
+from . import audio_io, common, ops
 from .common import PackedLibrary, compute_f0, merge_gather
 from .pipeline import prepare_networks
 from .spectrogram import spectrogram
@@ -114,6 +114,18 @@ def f0_on_side_stream(conv, spec, body):
     return f0, (lambda: cur.wait_stream(side))
 
 
+def track_logits_buf(conv, spec, pe):
+    """the buffer that takes the class scores [N, classes, F] of `spec` [N, 513, F] in a tracking converter: allocated once per shape
+    (the converter's `_track_bufs`; at most four shapes are kept, as for the f0 buffers), by the eager steps that precede a capture"""
+    key = (spec.shape[0], spec.shape[2])
+    buf = conv._track_bufs.get(key)
+    if buf is None:
+        if len(conv._track_bufs) >= 4:
+            conv._track_bufs.pop(next(iter(conv._track_bufs)))
+        buf = conv._track_bufs[key] = torch.empty(spec.shape[0], pe.sizes[3], spec.shape[2], device=spec.device)
+    return buf
+
+
 def capture_step(device, step, phi):
     """Capture one streaming step into a hipGraph: step() -> (wave, phi_next) runs twice eagerly on a side stream first, so that
     every scratch buffer reaches its steady-state size (the C ABI never allocates or synchronises inside the capture), then once
@@ -136,14 +148,24 @@ class RealtimeConverter:
     limiter = False                    # (set per converter in __init__: whether the step carries the limiter kernel)
     envelope = False                   # (likewise: whether the step carries the envelope kernel)
     pitch_range = False                # (likewise: whether the f0 branch runs the pitch-range follower and the centred transform)
+    pitch_track = False                # (likewise: whether the f0 branch stores the class scores and runs the tracker kernel)
 
     def __init__(self, content_encoder, f0_estimator, decoder, library_tokens, device="cuda", chunk=960, buffersize=8,
                  input_sr=16000, output_sr=16000, f0_rate=1.0, pitch=0.0, k=4, alpha=0.0, gain=0.0, input_gain=0.0,
                  reuse_interior="auto", world_pitch=False, gate_db=None, gate_hold=0.2, gate_lookahead=None,
                  crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0, limit_hold_ms=20.0, limit_history=0.05,
                  envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0, envelope_radius=1, intonation=1.0,
-                 intonation_half_life=10.0, intonation_prior=0.5):
+                 intonation_half_life=10.0, intonation_prior=0.5, pitch_track=None):
         self.device = torch.device(device)
+        track = common.track_options(pitch_track, "RealtimeConverter: pitch_track")
+        self.pitch_track = track is not None                # (checked before anything is built)
+        if self.pitch_track:
+            if world_pitch:
+                raise ValueError("RealtimeConverter: pitch_track cannot be combined with world_pitch: the tracker decodes the "
+                                 "estimator's class scores")
+            if reuse_interior is True:
+                raise ValueError("interior reuse cannot be combined with pitch_track: a frame's tracked class depends on the whole ring")
+            common.pitch_track_tables(track["lo"], track["hi"], track["band"])
         from .multistream import check_intonation
         self.intonation = check_intonation(1.0 if intonation is None else intonation, "RealtimeConverter: intonation")
         self.pitch_range = self.intonation != 1.0           # (checked before anything is built)
@@ -257,6 +279,17 @@ class RealtimeConverter:
             self._range_emit = torch.ones(1, dtype=torch.bool, device=dev)
             self._shift_eff, self._inton_eff = torch.zeros(1, **f32), torch.ones(1, **f32)
             self._centre, self._centre_on = torch.zeros(1, **f32), torch.zeros(1, **i32)
+        if self.pitch_track:
+            # the multi-session tracker at one row; no state: the whole ring is decoded again every step.  The logits buffer is
+            # allocated once per shape, by the first step
+            dev = self.device
+            self._track = common.pitch_track(track["lo"], track["hi"], track["band"], dev)
+            self.track_weight, self.track_jump = track["weight"], track["jump"]
+            self._track_on = torch.ones(1, dtype=torch.int32, device=dev)
+            self._track_weight = torch.tensor([track["weight"]], dtype=torch.float64, device=dev)
+            self._track_jump = torch.tensor([track["jump"]], dtype=torch.float64, device=dev)
+            self._track_changed = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._track_bufs = {}
         self._side = None                  # side stream of the f0 estimator (see _f0_on_side_stream)
         self._f0_bufs = {}
         # interior reuse: only where it is exact -- no resampling in front (the ring IS the 16 kHz signal), a shift of whole
@@ -278,6 +311,9 @@ class RealtimeConverter:
             raise ValueError("interior reuse cannot be combined with intonation: the carried f0 frames were transformed around an "
                              "earlier step's centre")
         if self.pitch_range:
+            fits = False
+        # pitch_track: a frame's tracked class depends on the whole ring (the path is decoded again every step) -- interior reuse is off
+        if self.pitch_track:
             fits = False
         if reuse_interior is True and not fits:
             raise ValueError("interior reuse needs input_sr 16000, chunk a multiple of 320 and a ring of at least 70 + chunk / 320 "
@@ -369,6 +405,12 @@ class RealtimeConverter:
         from .multistream import gmin_db
         return gmin_db(self._limit_gmin.tolist())[0]
 
+    def pitch_track_changed(self):
+        """how many frames of the ring the tracker moved off the per-frame argmax in the latest step (one host read)"""
+        if not self.pitch_track:
+            raise ValueError("pitch_track_changed needs a converter built with RealtimeConverter(..., pitch_track=True)")
+        return int(self._track_changed.tolist()[0])
+
     def _f0_on_side_stream(self, spec, data=None):
         """f0_on_side_stream with the estimator's f0 and the pitch transform.  With world_pitch the branch is WORLD's f0 of the
         16-kHz ring `data` instead, and the pitch transform leaves out f0_rate: the reference multiplies only the estimator's f0
@@ -388,7 +430,12 @@ class RealtimeConverter:
                 if self.pitch_range:
                     return ranged(buf)
                 return ops.pitch_transform_(buf, 1, f0_rate=1.0, pitch_shift=self.pitch)
-            f0 = self.pe.estimate(spec, out=buf)
+            if self.pitch_track:               # the class scores stored, their argmax, then the Viterbi path over it
+                f0 = self.pe.estimate(spec, out=buf, track=self._track, track_on=self._track_on, track_weight=self._track_weight,
+                                      track_jump=self._track_jump, logits_out=track_logits_buf(self, spec, self.pe),
+                                      changed=self._track_changed)
+            else:
+                f0 = self.pe.estimate(spec, out=buf)
             if self.pitch_range:
                 return ranged(f0)
             return ops.pitch_transform_(f0, 1, f0_rate=self.f0_rate, pitch_shift=self.pitch)

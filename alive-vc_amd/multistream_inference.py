@@ -18,6 +18,11 @@ The sessions file is a JSON list; each entry:
                                           source's running standard deviation meets the target voice's
    "range_st": 2.5,                       optional, beside "register_hz": declares the pitch range (standard deviation in semitones)
                                           of a voice given by "lib" alone; a "target" wav's range is measured at enrolment
+   "pitch_track": true,                   optional, a JSON bool (default: -pt): the session's f0 is the Viterbi path over the f0
+                                          estimator's class scores of its ring instead of their per-frame argmax
+                                          (module/multistream.py "Pitch tracking"); not with "world_pitch"
+   "track_weight": 1, "track_jump": 12,   optional, numbers >= 0 (defaults: --track-weight / --track-jump): the tracker's cost per
+                                          semitone moved inside the band and its flat cost of any other move
    "gate_db": -40, "gate_hold": 0.2,      optional: the session's input gate (module/multistream.py "Input gate"): a threshold in
                                           dBFS on its 16 kHz ring after the input gain (null: no gate; default -thr) and the
                                           seconds it stays open after the last loud tick (default --gate-hold)
@@ -63,6 +68,8 @@ only if some session is on auto pitch: a file without "auto_pitch", run without 
 The converter is built with pitch_range=True, and the voices are given registers and ranges, only if some session ends up at an
 "intonation" other than 1 or on "auto_range" (or under -int / --auto-range): a file without the keys, run without the flags, runs as
 before.
+The converter stores the class scores and carries the tracker kernel only if some session ends up tracking ("pitch_track", or -pt): a
+file without the key, run without the flag, runs as before.  --track-lo / --track-hi / --track-band hold for the whole converter.
 The converter carries the two gate kernels only if some session ends up gated ("gate_db", or -thr): a file without the keys, run
 without -thr, runs as before.
 The converter carries the seam kernel only if some session ends up with a crossfade ("crossfade_ms", or --crossfade): a file without
@@ -102,7 +109,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from module import audio_io                                     # noqa: E402
+from module import audio_io, common                             # noqa: E402
 from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
@@ -123,6 +130,7 @@ STALL_KEYS = ("stall",)                  # a loaded session carries it only when
 LOSE_KEYS = ("lose",)                    # likewise (the converter is then sparse and conceals)
 CONCEAL_KEYS = ("conceal",)              # likewise: the session's own switch
 RANGE_KEYS = ("intonation", "auto_range")    # a loaded session carries "intonation" only when it is not 1, "auto_range" only when on
+TRACK_KEYS = ("pitch_track", "track_weight", "track_jump")      # a loaded session carries them only when it tracks
 RANGE_ST_KEYS = ("range_st",)            # a loaded session carries it only when its entry has the key
 
 
@@ -192,6 +200,7 @@ def build_parser():
                         help="milliseconds over which the first chunk after a loss is faded in from the concealment (default 5)")
     parser.add_argument('--no-graph', action='store_true',
                         help="launch the per-tick device pipeline kernel by kernel instead of replaying one captured hipGraph")
+    common.add_track_arguments(parser)      # (-pt: sessions track unless their "pitch_track" says otherwise)
     return parser
 
 
@@ -244,6 +253,25 @@ def session_range(s, where, intonation=1.0, auto_range=False):
         return check_intonation(it, "\"intonation\""), on
     except ValueError as e:
         raise ValueError(f"{where}: {e}") from None
+
+
+def session_track(s, where, pitch_track=False, weight=common.TRACK_WEIGHT, jump=common.TRACK_JUMP):
+    """an entry's tracker settings -> (weight, jump) as floats, or None for a session that does not track: "pitch_track" (default
+    `pitch_track`) a JSON bool, "track_weight" / "track_jump" (defaults `weight`, `jump`) numbers >= 0; ValueError otherwise, and
+    together with "world_pitch" """
+    on = s.get("pitch_track", bool(pitch_track))
+    if not isinstance(on, bool):
+        raise ValueError(f"{where}: \"pitch_track\" must be true or false, got {on!r}")
+    try:
+        w, j = (common.track_param("\"track_weight\"", s.get("track_weight", weight)),
+                common.track_param("\"track_jump\"", s.get("track_jump", jump)))
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    if not on:
+        return None
+    if s.get("world_pitch", False):
+        raise ValueError(f"{where}: \"pitch_track\" cannot be combined with \"world_pitch\"")
+    return w, j
 
 
 def declared_registers(entries, name_of):
@@ -364,7 +392,7 @@ def supply_ticks(start, n_chunks, stall=None):
 def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None, crossfade_ms=None, limit_db=None,
                   limit_lookahead_ms=5.0, limit_hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0,
                   envelope_radius=1, conceal_hold_ms=10.0, conceal_fade_ms=50.0, conceal_recover_ms=5.0, intonation=1.0,
-                  auto_range=False):
+                  auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT, track_jump=common.TRACK_JUMP):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
@@ -373,7 +401,9 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     `envelope`) only on a session that follows at an amount above 0, and "stall" (a sorted
     tuple of ticks) only on a session whose entry has the key, as "lose" (a sorted tuple of ticks) and "conceal" (a bool); "intonation"
     (default `intonation`) only on a session whose factor is not 1, "auto_range" (default `auto_range`) only on one that is on, and
-    "range_st" only where the entry has it; ValueError on a malformed entry"""
+    "range_st" only where the entry has it; "pitch_track" (true), "track_weight" and "track_jump" (defaults `pitch_track`,
+    `track_weight`, `track_jump`) only on a session that tracks; ValueError on a malformed entry"""
+    session_track({}, "-pt / --track-weight / --track-jump", pitch_track, track_weight, track_jump)
     try:
         check_conceal_ms(conceal_hold_ms, conceal_fade_ms, conceal_recover_ms)
     except ValueError as e:
@@ -396,10 +426,10 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
         unknown = (set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(CODEBOOK_KEYS)
-                   - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS) - set(RANGE_KEYS) - set(RANGE_ST_KEYS))
+                   - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS) - set(RANGE_KEYS) - set(RANGE_ST_KEYS) - set(TRACK_KEYS))
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS})")
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS + TRACK_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
@@ -418,6 +448,7 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
         lose, con = session_lose(s, f"session {i}"), session_conceal(s, f"session {i}")
         inton, ranged = session_range(s, f"session {i}", intonation, auto_range)
         range_st = range_st_of(s, f"session {i}")
+        track = session_track(s, f"session {i}", pitch_track, track_weight, track_jump)
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
                  gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
@@ -449,6 +480,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             e["auto_range"] = True
         if range_st is not None:
             e["range_st"] = range_st
+        if track is not None:
+            e["pitch_track"], (e["track_weight"], e["track_jump"]) = True, track
         out.append(e)
     return out
 
@@ -599,10 +632,14 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None, stalls=None,
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    try:
+        tw, tj, lo, hi, band = common.track_arguments(args)             # (before anything is loaded)
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
     sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook,
                              args.crossfade, args.limit, args.limit_lookahead, args.limit_hold, args.envelope, args.envelope_floor,
                              args.envelope_range, args.envelope_radius, args.conceal_hold, args.conceal_fade, args.conceal_recover,
-                             args.intonation, args.auto_range)
+                             args.intonation, args.auto_range, args.pitch_track, tw, tj)
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -644,6 +681,8 @@ def main(argv=None):
                                 world_pitch=any(s["world_pitch"] for s in sessions), blend=blend_size(sessions),
                                 k_max=converter_k_max(sessions, args.k), auto_pitch=on_auto,
                                 **(dict(pitch_range=True) if wants_range else {}),
+                                **(dict(pitch_track=True, track_lo=lo, track_hi=hi, track_band=band)
+                                   if any("pitch_track" in s for s in sessions) else {}),
                                 **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}),
                                 **(dict(crossfade=True) if any("crossfade_ms" in s for s in sessions) else {}),
                                 **(dict(limiter=True) if any("limit_db" in s for s in sessions) else {}),
@@ -654,7 +693,8 @@ def main(argv=None):
                                         conceal_recover_ms=args.conceal_recover) if conceal else {}))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
-                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CONCEAL_KEYS + RANGE_KEYS if g in s})
+                   **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CONCEAL_KEYS + RANGE_KEYS + TRACK_KEYS
+                      if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()

@@ -13,7 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from module import audio_io                                     # noqa: E402
+from module import audio_io, common                             # noqa: E402
 from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
@@ -78,6 +78,7 @@ def build_parser():
     parser.add_argument('-int', '--intonation', default=1.0, type=float,
                         help="scale the pitch excursions around the stream's running mean pitch by this factor, as inference.py's -int "
                              "does around a window's mean (default 1: off; module/multistream.py \"Pitch range\"; this build only)")
+    common.add_track_arguments(parser)
     parser.add_argument('-isr', '--input-sr', default=16000, type=int)
     parser.add_argument('-osr', '--output-sr', default=16000, type=int)
     parser.add_argument('-lsr', '--loopback-sr', default=16000, type=int)
@@ -96,6 +97,11 @@ def main(argv=None):
         raise SystemExit("Error: this build needs a ROCm device: pass -d cuda on an MI355X host.")
     if args.fp16:
         raise SystemExit("-fp16 (documented deprecated upstream) is outside this build's scope")
+    track = None
+    if args.pitch_track:
+        if args.world_pitch_estimation:
+            raise SystemExit("-pt cannot be combined with -wpe: the tracker decodes the f0 estimator's class scores")
+        track = dict(zip(("weight", "jump", "lo", "hi", "band"), common.track_arguments(args)))      # (before anything is loaded)
     device = torch.device('cuda')
     PE, CE, Dec = F0Estimator().to(device), ContentEncoder().to(device), Decoder().to(device)
     PE.load_state_dict(torch.load(args.f0_estimator_path, map_location=device))
@@ -126,7 +132,8 @@ def main(argv=None):
                               if args.limit is not None else {}),
                            **(dict(envelope=args.envelope, envelope_floor_db=args.envelope_floor, envelope_range_db=args.envelope_range,
                                    envelope_radius=args.envelope_radius) if args.envelope else {}),
-                           **(dict(intonation=args.intonation) if args.intonation != 1.0 else {}))
+                           **(dict(intonation=args.intonation) if args.intonation != 1.0 else {}),
+                           **({} if track is None else dict(pitch_track=track)))
     if not args.no_graph:
         rt.enable_graph()        # the whole per-chunk device pipeline (~150 launches) captured once, replayed per chunk: same samples
     print("streaming: conversion running (Ctrl-C stops)")

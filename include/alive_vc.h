@@ -711,6 +711,32 @@ size_t alive_f0_estimate_workspace_bytes(int N, int T);
 int alive_f0_estimate(const float* const* w, const float* spec, int N, int T,
                       float* f0, void* ws, void* stream);
 
+/* F0Estimator.forward through the fused kernels: spec -> the class scores logits[N][4096][T] that alive_f0_estimate reduces in its
+ * classifier's epilogue, stored instead.  Same operands per branch (fp32 below 96 frame columns, fp16 split planes or three bf16
+ * planes above), so alive_argmax_channels(logits) is bitwise alive_f0_estimate.  ws: alive_f0_estimate_workspace_bytes(N, T). */
+int alive_f0_logits(const float* const* w, const float* spec, int N, int T, float* logits, void* ws, void* stream);
+
+/* Pitch tracking: a Viterbi path over class scores instead of the per-frame argmax (tools/pitch_track_ref.py is the NumPy
+ * restatement, bit for bit).  States i = 0 .. S - 1 stand for the classes lo + i (1 <= lo, lo + S <= C, S <= ALIVE_F0_TRACK_MAX_STATES:
+ * two fp64 score columns in 64 KB of LDS).  HOST tables, uploaded once: semis[i] = 12 log2(lo + i) and band_lo[i] / band_hi[i], the
+ * first / last state j with |semis[i] - semis[j]| <= band.  Per row: weight >= 0 (cost per semitone moved inside the band) and
+ * jump >= 0 (flat cost of any other move), in the units of the scores (raw logits serve: the path is invariant to a per-frame
+ * constant).  With x[t][i] = (double) logits[n][lo + i][t] (NaN -> -FLT_MAX, else clamped to +-FLT_MAX), e[t][i] = x[t][i] -
+ * max_j x[t][j] (the frame's scores below its best one, so that an all-NaN or all-equal frame is e = 0 and the path passes through
+ * it instead of -FLT_MAX rounding every earlier score away) and D[0] = e[0]:
+ *   g = max_j D[t-1][j] - jump;  a = max_{j in band of i} (D[t-1][j] - weight |semis[i] - semis[j]|);  D[t][i] = e[t][i] + max(a, g)
+ * (a wins a tie with g; every max keeps its lowest index); the path is traced back from the lowest argmax of D[T-1] and
+ * f0[n][t] = (float)(lo + p[t]).  fp64 + - * abs and compares only.
+ *   on       DEVICE int32 [N] or NULL (every row): a row with on[n] == 0 does nothing and its f0 row is untouched
+ *   changed  DEVICE int32 [N] or NULL: the number of frames whose tracked class differs from what f0 held on entry
+ *   ws       alive_f0_track_workspace_bytes(N, T, S) bytes (back pointers, uint16 per row, frame and state; 0: bad args)
+ * One block per row, sequential over the frames; no host synchronisation, no allocation, no floating-point atomics. */
+#define ALIVE_F0_TRACK_MAX_STATES 4000
+size_t alive_f0_track_workspace_bytes(int N, int T, int S);
+int alive_f0_track_rows(const float* logits, int N, int C, int T, int lo, int S, const double* semis, const int32_t* band_lo,
+                        const int32_t* band_hi, const int32_t* on, const double* weight, const double* jump, float* f0,
+                        int32_t* changed, void* ws, void* stream);
+
 /* Arithmetic of the decoder's two largest groups of GEMMs on the batch path (more than 96 columns; the streaming kernels are not
  * affected): (a) the six k = 5 convs of the 256-channel FilterBlock (decoder.py:128-134 at the Filter's coarsest scale), (b) the two
  * pointwise convs of the feature extractor's four AdaptiveConvNeXt1d layers (common.py:74-82), (c) the norm-FiLM projection, the two

@@ -39,6 +39,12 @@ more launch pair after the decoder, alive_envelope_waves, csrc/envelope.hip) bes
 and timed in alternating rounds (envelope_off_tick_*; the medians over the rounds, and the spread of the plain converter's rounds as the
 yardstick), the call's own time by device events around 200 back-to-back eager calls at the tick's shapes (envelope_call_us, its fill
 launch included) with the 12 B L bytes it moves (envelope_call_bytes), and the gains of the last tick (envelope_db_min / _max).
+--pitch-track adds the graph tick p50 / p99 of a pitch_track=True converter with no session tracking (track_none_tick_*: the class
+scores stored, their argmax, and the tracker's blocks returning at once) and with every session tracking at the defaults
+(track_all_tick_*: alive_f0_track_rows over every ring, csrc/f0_track.hip) beside the converter built without it (track_off_tick_*),
+all three alive in the one process and timed in alternating rounds (the medians over the rounds; the spread of track_off's rounds is
+the yardstick), the tracker call alone by device events around 200 back-to-back eager calls on the last tick's scores
+(track_call_us), and how many frames it moved in the last tick (track_changed_mean, on SYNTHETIC weights and input).
 --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
 one more 50 000-row voice added between two ticks, once on a default pool (the add re-packs the pool and the next tick
 re-captures) and once on a reserved pool of 65 x 50 000 rows (VoicePool(capacity=...): alive_pool_append into the table in
@@ -66,7 +72,7 @@ alive_ring_push_rows with every row present (push_call_us).
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch] [--pitch-range]
-                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--out multistream.json]
+                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--pitch-track] [--out multistream.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
     python tools/bench_multistream.py --sparse [--batches 128,1024] [--ticks 40] [--out profiles/multistream_sparse_bench.json]
     python tools/bench_multistream.py --conceal [--batches 128,1024] [--ticks 40] [--out profiles/multistream_conceal_bench.json]
@@ -355,6 +361,8 @@ def main():
                                                          "and the plain converter a second time")
     ap.add_argument("--envelope", action="store_true", help="also time an envelope=True converter, every session following at amount "
                                                             "1, against the plain converter in alternating rounds, and the call alone")
+    ap.add_argument("--pitch-track", action="store_true", help="also time a pitch_track=True converter with no session and with "
+                    "every session tracking, beside the plain converter in alternating rounds")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
                                                          "default and on a reserved pool")
     ap.add_argument("--sparse", action="store_true", help="the sparse-ticks leg alone: dense against sparse(=True) converters, "
@@ -572,6 +580,31 @@ def main():
                     rec["envelope_call_us"] = round(a.elapsed_time(b) * 1e3 / 200, 2)
                     rec["envelope_call_bytes"] = 12 * B * ld
                     del both, ec
+                if args.pitch_track:
+                    three = {}
+                    for name, kw, sess in (("track_off", {}, {}), ("track_none", dict(pitch_track=True), {}),
+                                           ("track_all", dict(pitch_track=True), dict(pitch_track=True))):
+                        c = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, **kw)
+                        for s in range(B):
+                            c.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, **sess)
+                        c.enable_graph()
+                        three[name] = c
+                    times = {name: [] for name in three}
+                    for _ in range(5):                         # alternating rounds in the one process
+                        for name, c in three.items():
+                            times[name].append(time_ticks(c, B, chunk, args.ticks, args.warmup + bs + 1, 300))
+                    for name, ts in times.items():
+                        rec[f"{name}_tick_p50_ms"] = round(float(np.median([t[0] for t in ts])), 3)
+                        rec[f"{name}_tick_p99_ms"] = round(float(np.median([t[1] for t in ts])), 3)
+                        rec[f"{name}_tick_p50_rounds_ms"] = [round(t[0], 3) for t in ts]
+                    tc = three["track_all"]
+                    assert tc.captures == 1 and three["track_none"].pitch_track_changed() == [0] * B
+                    rec["track_changed_mean"] = round(float(np.mean(tc.pitch_track_changed())), 2)
+                    lg = next(iter(tc._track_bufs.values()))
+                    f0 = torch.zeros(B, 1, lg.shape[2], device="cuda")
+                    rec["track_frames"], rec["track_states"] = int(lg.shape[2]), tc._track.states
+                    rec["track_call_us"] = round(time_calls(lambda: tc._track.rows(lg, f0, tc.track_on, tc.track_weight, tc.track_jump)), 2)
+                    del three, tc
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
                 rows.append(rec)
