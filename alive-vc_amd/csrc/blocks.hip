@@ -87,6 +87,50 @@ __global__ __launch_bounds__(256) void dwconv_norm_kernel(
 // per-sample scale / shift rows of the adaptive form are read coalesced) and leaves through an LDS transpose as bf16
 // planes (k-blocked, planes_layout.h): HBM sees x once and the planes once.
 constexpr int NPT = 512;                 // 8 waves: channels are split over the waves
+// the last pass of both dw conv + norm kernels: fp32 tile [nc][TW + 1] holding the channels c0 .. c0 + nc - 1 (nc a multiple of 32) ->
+// k-blocked planes (planes_layout.h).  thread = (k-block, column, 8-channel chunk of the block); 4 TW consecutive threads write
+// TW x 64 B = one contiguous run
+template <int NP, int TW>
+__device__ __forceinline__ void dwnorm_tile_to_planes(const float* tile, int C, int T, int n, int t0, unsigned short* __restrict__ P,
+                                                      int64_t cols_pad, float f16_scale, int c0, int nc) {
+    constexpr int PT = TW + 1;
+    const int chunks = nc / 8;
+    for (int item = threadIdx.x; item < TW * chunks; item += NPT) {
+        const int cl = (item >> 2) % TW, ck = (item / (4 * TW)) * 4 + (item & 3);
+        if (t0 + cl >= T) continue;
+        float vv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) vv[e] = tile[(ck * 8 + e) * PT + cl];
+        const bool f16s = NP == 2 && f16_scale != 0.0f;
+        if (f16s) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) vv[e] *= f16_scale;
+        }
+        const int64_t col = (int64_t)n * T + t0 + cl;
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) {
+            u32x4 o4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+                const bf16x2_t hp = {(__bf16)vv[2 * e], (__bf16)vv[2 * e + 1]};
+                const unsigned h = (NP == 1 || f16s) ? pack_f16x2(vv[2 * e], vv[2 * e + 1]) : __builtin_bit_cast(unsigned, hp);     // NP = 1: one fp16 plane
+                o4[e] = h;
+                if (f16s) {
+                    typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+                    const f16x2_t hv = __builtin_bit_cast(f16x2_t, h);
+                    vv[2 * e] -= (float)hv[0];
+                    vv[2 * e + 1] -= (float)hv[1];
+                } else {
+                    vv[2 * e] -= __uint_as_float(h << 16);
+                    vv[2 * e + 1] -= __uint_as_float(h & 0xffff0000u);
+                }
+            }
+            *(u32x4*)(P + planes_at(pl, col, c0 + ck * 8, cols_pad, C)) = o4;
+        }
+    }
+}
+
 // TW = columns per tile: 64 (a wave row is one channel) or 32 (a wave row is two channels; halves the LDS tile so that two
 // blocks share a CU at C = 512 -- with one block of 8 waves per CU the passes are latency-bound)
 template <int NP, int TW>
@@ -174,42 +218,137 @@ __global__ __launch_bounds__(NPT) void dwconv_norm_planes_kernel(
         tile[c * PT + tl] = ok ? v * g + o : 0.0f;
     }
     __syncthreads();
-    // pass 4: [C][col] -> k-blocked planes (planes_layout.h): thread = (k-block, column, 8-channel chunk of the block); 4 TW
-    // consecutive threads write TW x 64 B = one contiguous run
-    const int chunks = C / 8;
-    for (int item = threadIdx.x; item < TW * chunks; item += NPT) {
-        const int cl = (item >> 2) % TW, ck = (item / (4 * TW)) * 4 + (item & 3);
-        if (t0 + cl >= T) continue;
-        float vv[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) vv[e] = tile[(ck * 8 + e) * PT + cl];
-        const bool f16s = NP == 2 && f16_scale != 0.0f;
-        if (f16s) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) vv[e] *= f16_scale;
+    dwnorm_tile_to_planes<NP, TW>(tile, C, T, n, t0, P, cols_pad, f16_scale, 0, C);   // pass 4
+}
+
+// ---- the same kernel with the thread's channel column in registers (C = NI x NR: every width the three networks run) ----
+// A thread of the kernel above owns one column and the channels crow, crow + NR, ...: NI = C / NR values, 32 at C = 512 (TW = 32) and at
+// C = 256 (TW = 64).  They stay in y[NI] from the conv to the affine, so the statistics and the normalisation touch no LDS: an element
+// is written to LDS once (the affine's result) and read once (the split), and the tile, needed for that transpose alone, is half as
+// high (34 KB at C = 512: three blocks per CU instead of two).  Same thread <-> element mapping, same order of every sum, same
+// division, same split: the planes are bitwise those of the kernel above (tests/test_gpu_dwnorm_planes.py).  The scale / shift
+// rows of the adaptive form are walked by offset (NR x T per step).  Per launch at 128 x 450 (tools/bench_dwnorm.py):
+// profiles/r09_dwnorm_ab.json.
+template <int NP, int TW, int NI>
+__global__ __launch_bounds__(NPT) void dwconv_norm_planes_reg_kernel(
+    const float* __restrict__ X, int C, int T, const float* __restrict__ dw_w, const float* __restrict__ dw_b, int dw,
+    int affine_mode, const float* __restrict__ gain, const float* __restrict__ offset, const float* __restrict__ cond,
+    int cond_rows, int scale_row, int shift_row, float eps, unsigned short* __restrict__ P, int64_t cols_pad, float f16_scale) {
+    extern __shared__ float tile[];                      // [C / 2][TW + 1]
+    constexpr int CPW = 64 / TW;
+    constexpr int NR = NPT / 64 * CPW;
+    __shared__ float red[NR][TW];
+    constexpr int PT = TW + 1;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int tl = lane % TW, crow = wv * CPW + lane / TW;
+    const int n = blockIdx.y, t0 = blockIdx.x * TW;
+    const int t = t0 + tl;
+    const bool ok = t < T;
+    const size_t cstep = (size_t)NR * T;                 // one channel step of this thread, in elements of x or cond
+    const float* xc = X + ((size_t)n * C + crow) * T;    // row crow of window n
+    // A wave holds CPW channels, so the taps and the bias are wave-uniform: they are fetched by scalar loads from a wave-uniform index
+    // (both channels of a TW = 32 wave, then a select by lane half) -- as per-lane loads they were 8 of the 15 vector loads of an
+    // element.  (gain / offset stay per-lane loads: scalar loads between the LDS stores of pass 3 cost more than they save, both
+    // count on lgkmcnt.)
+    const int cu = __builtin_amdgcn_readfirstlane(wv) * CPW;
+    const bool hi = CPW == 2 && lane >= TW;
+    auto per_channel = [&](const float* __restrict__ p, int i, int stride, int j) -> float {
+        const float a = p[(cu + i * NR) * stride + j];
+        if constexpr (CPW == 2) {
+            const float b = p[(cu + 1 + i * NR) * stride + j];
+            return hi ? b : a;
         }
-        const int64_t col = (int64_t)n * T + t0 + cl;
+        return a;
+    };
+    // pass 1: depthwise conv (zero pad 3) -> registers, running sum
+    float y[NI];
+    float s = 0.0f;
+    if (dw && t0 >= 3 && t0 + TW + 3 <= T) {             // interior tile (block-uniform): no tap leaves the window
+        const float* xt = xc + t - 3;
 #pragma unroll
-        for (int pl = 0; pl < NP; ++pl) {
-            u32x4 o4;
+        for (int i = 0; i < NI; ++i) {
+            float v = per_channel(dw_b, i, 1, 0);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-                const bf16x2_t hp = {(__bf16)vv[2 * e], (__bf16)vv[2 * e + 1]};
-                const unsigned h = (NP == 1 || f16s) ? pack_f16x2(vv[2 * e], vv[2 * e + 1]) : __builtin_bit_cast(unsigned, hp);     // NP = 1: one fp16 plane
-                o4[e] = h;
-                if (f16s) {
-                    typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-                    const f16x2_t hv = __builtin_bit_cast(f16x2_t, h);
-                    vv[2 * e] -= (float)hv[0];
-                    vv[2 * e + 1] -= (float)hv[1];
-                } else {
-                    vv[2 * e] -= __uint_as_float(h << 16);
-                    vv[2 * e + 1] -= __uint_as_float(h & 0xffff0000u);
+            for (int j = 0; j < 7; ++j) v = fmaf(per_channel(dw_w, i, 7, j), xt[j], v);
+            y[i] = v;
+            s += v;
+            xt += cstep;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            float v = 0.0f;
+            if (dw) {
+                const float bias = per_channel(dw_b, i, 1, 0);
+                if (ok) v = bias;
+#pragma unroll
+                for (int j = 0; j < 7; ++j) {
+                    const int ti = t + j - 3;
+                    const float wj = per_channel(dw_w, i, 7, j);
+                    const float xv = (ok && ti >= 0 && ti < T) ? xc[ti] : 0.0f;
+                    if (ok) v = fmaf(wj, xv, v);
                 }
+            } else if (ok) {
+                v = xc[t];
             }
-            *(u32x4*)(P + planes_at(pl, col, ck * 8, cols_pad, C)) = o4;
+            y[i] = v;
+            s += v;
+            xc += cstep;
         }
+    }
+    red[crow][tl] = s;
+    __syncthreads();
+    float mean = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) mean += red[i][tl];
+    mean = mean / (float)C;
+    // pass 2: centred sum of squares
+    float ss = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const float d = y[i] - mean;
+        ss = fmaf(d, d, ss);
+    }
+    __syncthreads();                                     // every thread has read the sums
+    red[crow][tl] = ok ? ss : 0.0f;
+    __syncthreads();
+    float var = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) var += red[i][tl];
+    const float sigma = sqrtf(var / (float)(C - 1)) + eps;
+    // pass 3: normalise + affine, in place in the registers.  v * g + o is a multiply and an add, rounded separately, as the kernel
+    // above compiles it (-ffp-contract=off); the intrinsics pin that form
+    if (affine_mode == 0) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const float v = (y[i] - mean) / sigma;
+            y[i] = ok ? __fadd_rn(__fmul_rn(v, gain[crow + i * NR]), offset[crow + i * NR]) : 0.0f;
+        }
+    } else {
+        size_t so = ((size_t)n * cond_rows + scale_row + crow) * T + t, ho = ((size_t)n * cond_rows + shift_row + crow) * T + t;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const float v = (y[i] - mean) / sigma;
+            float g = 1.0f, o = 0.0f;
+            if (ok) {
+                g = cond[so];
+                o = cond[ho];
+            }
+            y[i] = ok ? __fadd_rn(__fmul_rn(v, g), o) : 0.0f;
+            so += cstep;
+            ho += cstep;
+        }
+    }
+    // pass 4: the lower and the upper half of the channels (a thread's first and second NI / 2) leave through ONE half-height tile, one
+    // after the other: half the LDS per block, so that three blocks share a CU and cover each other's load phases
+    float* tp = tile + crow * PT + tl;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (h) __syncthreads();                          // the first half has been read
+#pragma unroll
+        for (int i = 0; i < NI / 2; ++i) tp[i * NR * PT] = y[h * (NI / 2) + i];
+        __syncthreads();
+        dwnorm_tile_to_planes<NP, TW>(tile, C, T, n, t0, P, cols_pad, f16_scale, h * (C / 2), C / 2);
     }
 }
 
@@ -411,40 +550,64 @@ extern "C" int alive_dwconv_norm(const float* X, int N, int C, int T, const floa
 
 // dw conv (or none: dw_w == NULL) + (Adaptive)ChannelNorm with plane-packed output; C a multiple of 32
 namespace {
+// the register-resident kernel serves C = NI x NR with NI in {8, 16, 32}: 512 at TW = 32, 64 / 128 / 256 at TW = 64
+template <int NP, int TW>
+const void* dnp_reg_kernel(int ni) {
+    if (ni == 32) return (const void*)dwconv_norm_planes_reg_kernel<NP, TW, 32>;
+    if constexpr (TW == 64) {
+        if (ni == 16) return (const void*)dwconv_norm_planes_reg_kernel<NP, TW, 16>;
+        if (ni == 8) return (const void*)dwconv_norm_planes_reg_kernel<NP, TW, 8>;
+    }
+    return nullptr;
+}
+template <int NP, int TW>
+const void* dnp_kernel(int ni, bool ref) {
+    const void* k = ref ? nullptr : dnp_reg_kernel<NP, TW>(ni);
+    return k != nullptr ? k : (const void*)dwconv_norm_planes_kernel<NP, TW>;
+}
+
+// ref: always the LDS-resident kernel (alive_dwconv_norm_planes_ref, the tests' bitwise comparison)
 int dwconv_norm_planes_impl(const float* X, int N, int C, int T, const float* dw_w, const float* dw_b,
                             int affine_mode, const float* gain, const float* offset, const float* cond,
                             int cond_rows, int scale_row, int shift_row, float eps, int planes, float f16_scale, void* P,
-                            void* stream) {
+                            void* stream, bool ref = false) {
     ALIVE_CHECK_ARG(X && P && N > 0 && C > 1 && T > 0, "alive_dwconv_norm_planes: bad args");
     ALIVE_CHECK_ARG((dw_w == nullptr) == (dw_b == nullptr), "alive_dwconv_norm_planes: dw_w and dw_b go together");
     ALIVE_CHECK_ARG(affine_mode == 0 ? (gain && offset) : (cond != nullptr), "alive_dwconv_norm_planes: affine params");
     ALIVE_CHECK_ARG((C & 31) == 0 && planes >= 1 && planes <= 3, "alive_dwconv_norm_planes: C %d must be a multiple of 32, planes 1, 2 or 3", C);
     const int tw = C > 256 ? 32 : 64;                    // <= 68 KB of LDS per block: two blocks per CU
-    const size_t lds = (size_t)C * (tw + 1) * sizeof(float);
+    size_t lds = (size_t)C * (tw + 1) * sizeof(float);
     ALIVE_CHECK_ARG(lds <= 150 * 1024, "alive_dwconv_norm_planes: C %d does not fit the LDS tile", C);
     const int64_t cols = (int64_t)N * T, cols_pad = (cols + 127) / 128 * 128;
     {
         static LdsOptIn optin;
-        hipError_t e = optin.ensure({(const void*)dwconv_norm_planes_kernel<2, 32>, (const void*)dwconv_norm_planes_kernel<3, 32>,
-                                     (const void*)dwconv_norm_planes_kernel<2, 64>, (const void*)dwconv_norm_planes_kernel<3, 64>,
-                                     (const void*)dwconv_norm_planes_kernel<1, 32>, (const void*)dwconv_norm_planes_kernel<1, 64>}, 150 * 1024);
+        hipError_t e = optin.ensure({dnp_kernel<1, 32>(0, true), dnp_kernel<2, 32>(0, true), dnp_kernel<3, 32>(0, true),
+                                     dnp_kernel<1, 64>(0, true), dnp_kernel<2, 64>(0, true), dnp_kernel<3, 64>(0, true),
+                                     dnp_kernel<1, 32>(32, false), dnp_kernel<2, 32>(32, false), dnp_kernel<3, 32>(32, false),
+                                     dnp_kernel<1, 64>(32, false), dnp_kernel<2, 64>(32, false), dnp_kernel<3, 64>(32, false),
+                                     dnp_kernel<1, 64>(16, false), dnp_kernel<2, 64>(16, false), dnp_kernel<3, 64>(16, false),
+                                     dnp_kernel<1, 64>(8, false), dnp_kernel<2, 64>(8, false), dnp_kernel<3, 64>(8, false)}, 150 * 1024);
         if (e != hipSuccess) {
             alive_set_error("alive_dwconv_norm_planes: cannot reserve LDS: %s", hipGetErrorString(e));
             return ALIVE_ERR_LAUNCH;
         }
     }
-    dim3 g(cdiv(T, tw), N);
-#define LAUNCH_DNP(NP_, TW_)                                                                                                   \
-    dwconv_norm_planes_kernel<NP_, TW_><<<g, NPT, lds, (hipStream_t)stream>>>(X, C, T, dw_w, dw_b, dw_w != nullptr, affine_mode, gain, \
-                                                                             offset, cond, cond_rows, scale_row, shift_row, eps,  \
-                                                                             (unsigned short*)P, cols_pad, f16_scale)
-    if (planes == 1 && tw == 32) LAUNCH_DNP(1, 32);         // one fp16 plane: the input of a plain GEMM (alive_gemm_planes, planes = 1)
-    else if (planes == 1) LAUNCH_DNP(1, 64);
-    else if (planes == 2 && tw == 32) LAUNCH_DNP(2, 32);
-    else if (planes == 3 && tw == 32) LAUNCH_DNP(3, 32);
-    else if (planes == 2) LAUNCH_DNP(2, 64);
-    else LAUNCH_DNP(3, 64);
-#undef LAUNCH_DNP
+    const int nr = tw == 32 ? 16 : 8;                    // the kernels' NR
+    const int ni = C % nr == 0 ? C / nr : 0;
+    const void* k;
+    if (planes == 1) k = tw == 32 ? dnp_kernel<1, 32>(ni, ref) : dnp_kernel<1, 64>(ni, ref);     // one fp16 plane: the input of a plain GEMM
+    else if (planes == 2) k = tw == 32 ? dnp_kernel<2, 32>(ni, ref) : dnp_kernel<2, 64>(ni, ref);
+    else k = tw == 32 ? dnp_kernel<3, 32>(ni, ref) : dnp_kernel<3, 64>(ni, ref);
+    if (!ref && dnp_reg_kernel<1, 64>(tw == 32 && ni != 32 ? 0 : ni) != nullptr) lds /= 2;      // the register-resident kernel: a half-height tile
+    const int dw = dw_w != nullptr;
+    unsigned short* Pp = (unsigned short*)P;
+    void* args[] = {&X, &C, &T, &dw_w, &dw_b, (void*)&dw, &affine_mode, &gain, &offset, &cond, &cond_rows, &scale_row, &shift_row,
+                    &eps, &Pp, (void*)&cols_pad, &f16_scale};
+    hipError_t e = hipLaunchKernel(k, dim3(cdiv(T, tw), N), dim3(NPT), args, lds, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        alive_set_error("alive_dwconv_norm_planes: launch failed: %s", hipGetErrorString(e));
+        return ALIVE_ERR_LAUNCH;
+    }
     ALIVE_CHECK_LAUNCH("alive_dwconv_norm_planes");
     return ALIVE_OK;
 }
@@ -465,6 +628,16 @@ extern "C" int alive_dwconv_norm_planes_f16s(const float* X, int N, int C, int T
     ALIVE_CHECK_ARG(scale > 0.0f, "alive_dwconv_norm_planes_f16s: scale must be a positive power of two");
     return dwconv_norm_planes_impl(X, N, C, T, dw_w, dw_b, affine_mode, gain, offset, cond, cond_rows, scale_row, shift_row, eps, 2, scale,
                                    P, stream);
+}
+
+// test-only: the LDS-resident kernel at every shape; f16_scale != 0 (planes = 2) selects the fp16 split form
+extern "C" int alive_dwconv_norm_planes_ref(const float* X, int N, int C, int T, const float* dw_w, const float* dw_b,
+                                            int affine_mode, const float* gain, const float* offset, const float* cond,
+                                            int cond_rows, int scale_row, int shift_row, float eps, int planes, void* P,
+                                            void* stream, float f16_scale) {
+    ALIVE_CHECK_ARG(f16_scale == 0.0f || (f16_scale > 0.0f && planes == 2), "alive_dwconv_norm_planes_ref: the fp16 split form has two planes");
+    return dwconv_norm_planes_impl(X, N, C, T, dw_w, dw_b, affine_mode, gain, offset, cond, cond_rows, scale_row, shift_row, eps, planes,
+                                   f16_scale, P, stream, true);
 }
 
 extern "C" int alive_channel_norm(const float* X, int N, int C, int T, const float* gain, const float* offset, float eps,

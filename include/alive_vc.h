@@ -588,7 +588,7 @@ int alive_dwconv_norm(const float* X, int N, int C, int T, const float* dw_w, co
                       const float* cond, int cond_rows, int scale_row, int shift_row,
                       float eps, float* Y, void* stream);
 /* the same with plane-packed output for alive_gemm_planes (dw_w == dw_b == NULL: the norm alone); one pass over memory:
- * the [C][64 columns] tile stays in LDS between the conv, the statistics, the affine and the split.  C a multiple of 32. */
+ * a block's [C][32 or 64 columns] tile stays on chip between the conv, the statistics, the affine and the split.  C a multiple of 32. */
 int alive_dwconv_norm_planes(const float* X, int N, int C, int T, const float* dw_w, const float* dw_b,
                              int affine_mode, const float* gain, const float* offset,
                              const float* cond, int cond_rows, int scale_row, int shift_row,
@@ -599,6 +599,13 @@ int alive_dwconv_norm_planes_f16s(const float* X, int N, int C, int T, const flo
                                   int affine_mode, const float* gain, const float* offset,
                                   const float* cond, int cond_rows, int scale_row, int shift_row,
                                   float eps, float scale, void* P, void* stream);
+/* TEST ONLY: the two entry points above always through the kernel that keeps the tile in LDS from the conv on.  The widths the networks
+ * run (C = 64, 128, 256, 512) otherwise take a kernel that holds each thread's channels in registers; its planes are bitwise the same.
+ * f16_scale != 0 (planes = 2): the fp16 split form with that scale. */
+int alive_dwconv_norm_planes_ref(const float* X, int N, int C, int T, const float* dw_w, const float* dw_b,
+                                 int affine_mode, const float* gain, const float* offset,
+                                 const float* cond, int cond_rows, int scale_row, int shift_row,
+                                 float eps, int planes, void* P, void* stream, float f16_scale);
 /* z = gelu(h) * interp(film[scale_row + c]) + interp(film[shift_row + c])  (decoder.py:112-117,130-132: F.gelu, then the FiLM of a
  * ModulatedCausalConv1d with F.interpolate(mode='linear')), the arithmetic of alive_conv1d's second output.  H [N][C][L];
  * film [N][film_rows][film_ld] holds the frames from f0 on of a window of Lf frames, t0 = first sample of H in the window at this
