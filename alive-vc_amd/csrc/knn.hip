@@ -3964,6 +3964,28 @@ extern "C" const int* alive_knn_search_stats(int N, int T, int64_t M, void* ws) 
     return ws_layout(ws, (int64_t)N * T, M, 4).stats;
 }
 
+// debug (tests/test_gpu_knn_stage.py): where the first stage's buffers sit in the workspace of a search of Tt frames against M rows at
+// this k (sub != 0: the subspace search's workspace) and how its three stages cut the work -- read off ws_layout / make_plan, host only:
+//   out[0 .. 7]   byte offsets from the workspace base of s_bf16, s_f8, clip6, sub_f6, sub_g (-1 without sub), cv, ci; [7] bytes
+//   out[8 .. 19]  Tt_pad, tiles_total, tiles_per_split, P of p16 (bf16 stage), p8 (fp8), p6 (fp6 / subspace)
+//   out[20 .. 24] KP, KP8 (candidates per frame and split: bf16 / block-scaled), FT, FT6 (frames per block), LT (rows per tile)
+extern "C" int alive_debug_knn_stage_view(int64_t Tt, int64_t M, int k, int sub, int64_t* out, int n_out) {
+    ALIVE_CHECK_ARG(out && n_out >= 25 && Tt >= 1 && M >= 1 && k >= 1 && k <= ALIVE_MAX_K, "alive_debug_knn_stage_view: bad args");
+    const SearchWs w = ws_layout(nullptr, Tt, M, k, false, sub != 0);
+    auto off = [](const void* p) { return p != nullptr ? (int64_t)(intptr_t)p : (int64_t)-1; };
+    const int64_t head[8] = {off(w.s_bf16), off(w.s_f8), off(w.clip6), off(w.sub_f6), off(w.sub_g), off(w.cv), off(w.ci), (int64_t)w.bytes};
+    for (int i = 0; i < 8; ++i) out[i] = head[i];
+    const SearchPlan* plans[3] = {&w.p16, &w.p8, &w.p6};
+    for (int i = 0; i < 3; ++i) {
+        out[8 + 4 * i] = plans[i]->Tt_pad;
+        out[9 + 4 * i] = plans[i]->tiles_total;
+        out[10 + 4 * i] = plans[i]->tiles_per_split;
+        out[11 + 4 * i] = plans[i]->P;
+    }
+    out[20] = KP; out[21] = KP8; out[22] = FT; out[23] = FT6; out[24] = LT;
+    return ALIVE_OK;
+}
+
 extern "C" int alive_knn_merge_gather(const float* cand_val, const int32_t* cand_idx, int n_shards, int k, double alpha,
                                       const float* rows_f32_full, const float* src, int N, int T, float* out,
                                       int32_t* final_idx, void* stream) {

@@ -61,6 +61,7 @@ PROTOTYPES = {
     "alive_library_pack_fp8": (_I, [_VP, _I64, _VP, _VP]),
     "alive_knn_search_fp8": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP]),
     "alive_knn_search_stats": (_VP, [_I, _I, _I64, _VP]),
+    "alive_debug_knn_stage_view": (_I, [_I64, _I64, _I, _I, _VP, _I]),
     "alive_knn_search_timed": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_knn_search_fp8_timed": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_library_pack_fp6": (_I, [_VP, _I64, _VP, _VP]),

@@ -138,6 +138,14 @@ int alive_knn_search_fp8(const float* src, int N, int T,
                          int64_t M, int64_t idx_base, int k,
                          float* out_val, int32_t* out_idx, void* ws, void* stream);
 const int* alive_knn_search_stats(int N, int T, int64_t M, void* ws);
+/* Debug (the candidate-stage tests): where the first stage's buffers sit in the workspace of a search of Tt frames against M rows at
+ * this k (sub != 0: the workspace of alive_knn_search_fp6_sub_timed) and the plans of its three stages; host arithmetic only.
+ *   out[0 .. 6]   byte offsets from the workspace base: frames as bf16 [Tt_pad][768], the frames' fp8 / fp6 codes, the per-frame fp6
+ *                 clip flags, the subspace codes [.][512] and g (-1 without sub), candidate values, candidate indices;  out[7] bytes
+ *   out[8 .. 19]  Tt_pad, tiles_total, tiles_per_split, P (library splits) of the bf16, the fp8 and the fp6 / subspace stage
+ *   out[20 .. 24] candidates per frame and split (bf16 stage, block-scaled stages), frames per block (256-frame kernels, fp6
+ *                 kernels), library rows per tile.  Candidates are [frame][P][candidates per split].  n_out >= 25. */
+int alive_debug_knn_stage_view(int64_t Tt, int64_t M, int k, int sub, int64_t* out, int n_out);
 
 /* Measurement forms (bench.py): the same searches; ev_start / ev_stop are hipEvent_t handles (or NULL) recorded on `stream`
  * immediately before / after the first-stage scoring kernel of the whole batch -- the dominant kernel of the path. */
