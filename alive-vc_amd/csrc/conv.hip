@@ -26,7 +26,7 @@ constexpr int A_LD = BK + 4;   // 20 floats = 80 B rows: keeps b128 reads 16-B a
 
 // YPL: Y is also written as two k-blocked bf16 planes (AliveConv.Yp) -- an instantiation of its own, like UPV
 template <int BM, int BN, int WM, int WN, bool UPV = false, bool YPL = false>
-__global__ __launch_bounds__(256) void conv_gemm_kernel(AliveConv p, unsigned kw_magic, float film_ratio) {
+__global__ __launch_bounds__(256) void conv_gemm_kernel(AliveConv p, unsigned kw_magic, unsigned kw_shift, float film_ratio) {
     constexpr int TM = BM / WM, TN = BN / WN;
     constexpr int MR = TM / 16, NR = TN / 16;
     constexpr int B_LD = BN + 4;
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(AliveConv p, unsigned kw
             int ci, j;
             if (p.KW == 1) { ci = k; j = 0; }
             else if (kw_magic == 0) { ci = 0; j = k; }          // single input channel (DFT frames, source_in)
-            else { ci = (int)(((unsigned)k * kw_magic) >> 20); j = k - ci * p.KW; }
+            else { ci = (int)(((unsigned)k * kw_magic) >> kw_shift); j = k - ci * p.KW; }      // exact floor(k / KW), k < 32768 (host, below)
             int tin = tin_base + j * p.dil;
             if (tin < 0 && p.pad_mode != 0) tin = -tin;
             if (tin >= p.Tin && p.pad_mode == 2) tin = 2 * (p.Tin - 1) - tin;
@@ -277,6 +277,8 @@ extern "C" int alive_conv1d(const AliveConv* d, void* stream) {
     ALIVE_CHECK_ARG(d->pad_mode >= 0 && d->pad_mode <= 2, "alive_conv1d: pad_mode");
     if (d->pad_mode != 0) ALIVE_CHECK_ARG(d->pad_left < d->Tin, "alive_conv1d: reflect pad %d needs Tin > pad (Tin %d)", d->pad_left, d->Tin);
     if (d->Z || d->Zp) ALIVE_CHECK_ARG(d->film && d->Lf > 0, "alive_conv1d: Z needs film");
+    ALIVE_CHECK_ARG(d->film_ld != 0 || (d->film_t0 == 0 && d->film_f0 == 0), "alive_conv1d: film_t0 %d / film_f0 %d without a frame range (film_ld 0)",
+                    d->film_t0, d->film_f0);
     if (d->precision == 3)
         ALIVE_CHECK_ARG((int64_t)d->N * d->Tout > 96, "alive_conv1d: precision 3 (plain fp16) is a batch form: more than 96 columns, got %lld",
                         (long long)d->N * d->Tout);
@@ -288,22 +290,29 @@ extern "C" int alive_conv1d(const AliveConv* d, void* stream) {
     if (d->precision >= 1)
         return alive_conv_split_launch(d, (d->Z || d->Zp) ? (float)(d->film_ld ? d->film_ld : d->Lf) / (float)d->Tout : 0.0f, (hipStream_t)stream);
     ALIVE_CHECK_ARG(d->film_ld == 0, "alive_conv1d: a film frame range needs the split kernel (precision 1 / 2)");
-    const unsigned magic = d->Ci == 1 ? 0u : (unsigned)(((1u << 20) + d->KW - 1) / d->KW);
+    // (channel, tap) of a reduction index: k / KW = (k * ceil(2^s / KW)) >> s on 32-bit registers.  The product must not wrap
+    // (k < 32768: magic <= 2^17) and s must be large enough for every k (k * (magic * KW - 2^s) < 2^s): s = 18 for KW 2 .. 3, 19 for
+    // 4 .. 7, 20 for 8 .. 16 meets both for every k < 32768 (tests/test_host_conv_operands.py walks them all).  With s = 20 for every KW
+    // the product wrapped from k = 4096 KW on for KW <= 7, and the channels from 4096 up were read from channel 0 on.  A multiply-high
+    // by ceil(2^32 / KW) is exact too, but cost the 64-row tile 1.2 % (41.11 against 40.62 us per launch of 64 x 64 x k5, dilation 2,
+    // 2 x 700 columns; this form: 39.93).
+    const unsigned shift = d->KW < 4 ? 18u : d->KW < 8 ? 19u : 20u;
+    const unsigned magic = d->Ci == 1 ? 0u : (unsigned)(((1u << shift) + d->KW - 1) / d->KW);
     const float ratio = d->Z ? (float)d->Lf / (float)d->Tout : 0.0f;
     hipStream_t s = (hipStream_t)stream;
     if (d->Co > 64) {
         dim3 g(cdiv(d->Tout, 128), cdiv(d->Co, 128), d->N);
-        conv_gemm_kernel<128, 128, 2, 2><<<g, 256, 0, s>>>(*d, magic, ratio);
+        conv_gemm_kernel<128, 128, 2, 2><<<g, 256, 0, s>>>(*d, magic, shift, ratio);
     } else if (d->Co > 16) {
         dim3 g(cdiv(d->Tout, 128), cdiv(d->Co, 64), d->N);
-        if (d->Yp) conv_gemm_kernel<64, 128, 1, 4, false, true><<<g, 256, 0, s>>>(*d, magic, ratio);
-        else conv_gemm_kernel<64, 128, 1, 4><<<g, 256, 0, s>>>(*d, magic, ratio);
+        if (d->Yp) conv_gemm_kernel<64, 128, 1, 4, false, true><<<g, 256, 0, s>>>(*d, magic, shift, ratio);
+        else conv_gemm_kernel<64, 128, 1, 4><<<g, 256, 0, s>>>(*d, magic, shift, ratio);
     } else {
         dim3 g(cdiv(d->Tout, 256), 1, d->N);
         if ((d->up == 2 || d->up == 4) && d->act == 0 && !d->post_add && !d->ch_scale)
-            conv_gemm_kernel<16, 256, 1, 4, true><<<g, 256, 0, s>>>(*d, magic, ratio);      // vector stores of the transposed conv
+            conv_gemm_kernel<16, 256, 1, 4, true><<<g, 256, 0, s>>>(*d, magic, shift, ratio);      // vector stores of the transposed conv
         else
-            conv_gemm_kernel<16, 256, 1, 4><<<g, 256, 0, s>>>(*d, magic, ratio);
+            conv_gemm_kernel<16, 256, 1, 4><<<g, 256, 0, s>>>(*d, magic, shift, ratio);
     }
     ALIVE_CHECK_LAUNCH("alive_conv1d");
     return ALIVE_OK;

@@ -21,12 +21,15 @@ def _f(t):
 
 def conv1d(x, weight, bias=None, stride=1, dilation=1, pad_left=0, pad_mode=0, out_len=None, act=None,
            post_add=None, ch_scale=None, residual=None, skip=None, film=None, film_scale_row=0, film_shift_row=0,
-           want_raw=True, transposed=False, precision="fp32", x_planes=None, z_planes=False, y_planes=False):
+           want_raw=True, transposed=False, precision="fp32", x_planes=None, z_planes=False, y_planes=False,
+           film_t0=0, film_f0=0, film_ld=0, film_lf=None):
     """Generic Conv1d / ConvTranspose1d(k == stride) through alive_conv1d.
     Returns (Y, Z): raw output (or None) and the gelu+FiLM modulated second output (or None).
     x_planes: the plane-packed form of x (to_planes(x, 2)) -- the split kernel then stages its input by LDS-DMA (AliveConv.Xp);
     z_planes: Z comes back plane-packed (AliveConv.Zp; a uint8 buffer like to_planes gives) instead of fp32;
-    y_planes: the exact kernel also writes Y as planes (AliveConv.Yp) -- True / 2: two bf16 planes, 1: one fp16 plane; returned in Z's place."""
+    y_planes: the exact kernel also writes Y as planes (AliveConv.Yp) -- True / 2: two bf16 planes, 1: one fp16 plane; returned in Z's place.
+    film_t0 / film_f0 / film_ld: AliveConv's frame-range fields, passed straight through: x holds the samples from film_t0 on of a
+    window of film_lf frames (AliveConv.Lf, which a range's film tensor cannot tell), film the frames [film_f0, film_f0 + film_ld)."""
     x = _f(x)
     n, ci, tin = x.shape
     keep = []
@@ -34,7 +37,12 @@ def conv1d(x, weight, bias=None, stride=1, dilation=1, pad_left=0, pad_mode=0, o
     planes = 3 if precision == "bf16x6" else 2
     if split and transposed:
         r = weight.shape[2]
-        W, b = pack_convT_split(weight, bias)
+        if precision == "bf16x3":
+            W, b = pack_convT_split(weight, bias)
+        else:                                                   # the rows (co, j) as a 1x1 conv, packed for the asked precision
+            a = weight.permute(1, 2, 0).reshape(weight.shape[1] * r, ci, 1)
+            W = pack_conv_split_h(a)[2].contiguous() if precision == "fp16" else pack_conv_split(a, planes)
+            b = bias.float().repeat_interleave(r).contiguous()
         co_rows, kw, up = weight.shape[1] * r, 1, r
         stride_, tout = 1, tin
         co_out = weight.shape[1]
@@ -74,8 +82,9 @@ def conv1d(x, weight, bias=None, stride=1, dilation=1, pad_left=0, pad_mode=0, o
             Z = torch.empty(nat.lib().alive_planes_bytes(n * tout, co_out, 1 if precision == "fp16" else 2), dtype=torch.uint8, device=x.device)
         else:
             Z = torch.empty(n, co_out, tout, device=x.device)
-        d.film, d.film_rows, d.Lf = nat.ptr(film), film.shape[1], film.shape[2]
+        d.film, d.film_rows, d.Lf = nat.ptr(film), film.shape[1], (film.shape[2] if film_lf is None else film_lf)
         d.film_scale_row, d.film_shift_row = film_scale_row, film_shift_row
+    d.film_t0, d.film_f0, d.film_ld = film_t0, film_f0, film_ld
     d.Y = nat.ptr(Y)
     if z_planes:
         d.Zp = nat.ptr(Z)

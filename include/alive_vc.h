@@ -411,7 +411,7 @@ typedef struct AliveConv {
     /* FiLM of a frame RANGE of a longer window (alive_decoder_forward_range): this conv's columns start at sample
      * film_t0 of the window (at its own rate) and `film` holds the frames [film_f0, film_f0 + film_ld) only, row pitch
      * film_ld; Lf stays the window's frame count, so the interpolation coordinates are those of the whole window.
-     * film_ld == 0: film covers the whole window (film_t0 = film_f0 = 0, pitch Lf).  Split kernel only. */
+     * film_ld == 0: film covers the whole window (film_t0 = film_f0 = 0, pitch Lf; anything else is refused).  Split kernel only. */
     int film_t0, film_f0, film_ld;
     /* Plane-packed operands of the split kernel (precision 1, Co > 64; round 3).  Format = "plane-packed activations" below:
      * P[plane][C_pad/32][cols_pad][32] bf16 (row = n * T + t), 2 planes, plane stride = cols_pad * C_pad, cols_pad = N * T
