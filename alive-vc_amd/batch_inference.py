@@ -28,6 +28,12 @@ The jobs file is a JSON list; each entry:
                                                             limiter (module/multistream.py limit_waves) on the device after the
                                                             gain, at the file's own rate, before "normalize": no sample exceeds
                                                             the ceiling.  A jobs file without it, run without -lim, runs as before
+   "lufs": -23,                                             optional, a number of LUFS in (-70, 0] or null (default: -lufs): the
+                                                            file is brought to this integrated loudness (ITU-R BS.1770-4;
+                                                            module/multistream.py normalize_loudness) by one gain within
+                                                            --loudness-max-db dB, on the device after the gain, at the file's own
+                                                            rate, before "limit_db" and "normalize".  A jobs file without it, run
+                                                            without -lufs, runs as before
    "envelope": 0.7,                                         optional, a number in [0, 1] or null (default: -env): how far the converted
                                                             voice follows the source's loudness contour (module/multistream.py
                                                             follow_envelope), at 16 kHz before the output resample and the gain; 0 or
@@ -64,6 +70,7 @@ JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha",
             "blend", "k", "auto_pitch", "register_hz")
 ENVELOPE_KEYS = ("envelope",)            # likewise; a loaded job carries it only when it follows (an amount above 0)
 LIMIT_KEYS = ("limit_db",)               # taken per job too; a loaded job carries it only when it is limited
+LOUDNESS_KEYS = ("lufs",)                # likewise; a loaded job carries it only when it is normalised
 TRACK_KEYS = ("pitch_track",)            # a loaded job carries it only when it tracks: {"weight": W, "jump": J}
 RANGE_KEYS = ("auto_range", "range_st")  # a loaded job carries "auto_range" only when it is on, "range_st" only when its entry has it
 
@@ -92,6 +99,12 @@ def build_parser():
                         help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5)")
     parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
                         help="milliseconds the limiter's gain stays down after a peak (default 20)")
+    parser.add_argument('-lufs', '--lufs', default=None, type=float, metavar="L",
+                        help="loudness normalisation: every output file is brought to this integrated loudness in LUFS (ITU-R BS.1770-4, "
+                             "-70 < L <= 0, e.g. -23 or -16) by one gain unless a job's \"lufs\" says otherwise, after the gain and before "
+                             "the limiter and \"normalize\" (default: the level is left alone)")
+    parser.add_argument('--loudness-max-db', default=12.0, type=float, metavar="DB",
+                        help="the most the loudness normalisation turns a file up or down (default 12)")
     parser.add_argument('-env', '--envelope', default=0.0, type=float, metavar="A",
                         help="envelope follow: the converted voices take on their sources' loudness contours by this amount, 0 (off, the "
                              "default) to 1, unless a job's \"envelope\" says otherwise (module/multistream.py follow_envelope).  It can lift samples above full "
@@ -169,6 +182,18 @@ def job_limit(j, where, limit_db=None, lookahead_ms=5.0, hold_ms=20.0):
     return None if db is None else float(db)
 
 
+def job_loudness(j, where, lufs=None, max_db=12.0):
+    """an entry's "lufs" (default `lufs`; a JSON null switches the default off) -> a float in (-70, 0], or None for a job whose level
+    is left alone; ValueError otherwise (the largest gain is the flag's, checked with it)"""
+    from module.multistream import check_loudness
+    target = j.get("lufs", lufs)
+    try:
+        check_loudness(target, max_db)
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return None if target is None else float(target)
+
+
 def job_envelope(j, where, envelope=0.0, floor_db=-60.0, range_db=12.0, radius=1):
     """an entry's "envelope" (default `envelope`; a JSON null or 0 switches the default off) -> the amount as a float in (0, 1], or
     None for a job that does not follow; ValueError otherwise (the three tuning values are those of the flags, checked with it)"""
@@ -206,15 +231,17 @@ def job_track(j, where, pitch_track=False, weight=common.TRACK_WEIGHT, jump=comm
 
 def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0,
               envelope_range_db=12.0, envelope_radius=1, auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT,
-              track_jump=common.TRACK_JUMP):
+              track_jump=common.TRACK_JUMP, lufs=None, loudness_max_db=12.0):
     """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder; "auto_pitch": default
     `auto_pitch`); a limited job ("limit_db", default `limit_db`) also carries "limit_db", a job without a limiter does not, so a
     file without the key loads to what it did; likewise "envelope" (default `envelope`) only on a job that follows at an amount above
     0, "auto_range" (default `auto_range`) only on a job that is on, "range_st" only where the entry has it and "pitch_track"
-    (default `pitch_track` at `track_weight` / `track_jump`) only on a job that tracks; ValueError on a malformed job, before anything
+    (default `pitch_track` at `track_weight` / `track_jump`) only on a job that tracks and "lufs" (default `lufs`) only on a job that
+    is normalised; ValueError on a malformed job, before anything
     runs on the device"""
     job_track({}, "-pt / --track-weight / --track-jump", pitch_track, track_weight, track_jump)
     job_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, lookahead_ms, hold_ms)
+    job_loudness({}, "-lufs / --loudness-max-db", lufs, loudness_max_db)
     env = (envelope_floor_db, envelope_range_db, envelope_radius)
     job_envelope({}, "-env / --envelope-floor / --envelope-range / --envelope-radius", envelope, *env)
     if not 1 <= k <= MAX_K:
@@ -229,10 +256,11 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
     for i, j in enumerate(jobs):
         if not isinstance(j, dict) or "input" not in j:
             raise ValueError(f"job {i}: an object with an \"input\" wav is required")
-        unknown = set(j) - set(JOB_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(RANGE_KEYS) - set(TRACK_KEYS)
+        unknown = (set(j) - set(JOB_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(RANGE_KEYS) - set(TRACK_KEYS)
+                   - set(LOUDNESS_KEYS))
         if unknown:
             raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS + TRACK_KEYS})")
+                             f"{JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS + TRACK_KEYS + LOUDNESS_KEYS})")
         blend = blend_sources(j, f"job {i}", rel) if "blend" in j else None
         if blend is None and j.get("target") is None and j.get("lib") is None:
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
@@ -251,6 +279,9 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
         lim = job_limit(j, f"job {i}", limit_db, lookahead_ms, hold_ms)
         if lim is not None:
             e["limit_db"] = lim
+        target = job_loudness(j, f"job {i}", lufs, loudness_max_db)
+        if target is not None:
+            e["lufs"] = target
         amount = job_envelope(j, f"job {i}", envelope, *env)
         if amount is not None:
             e["envelope"] = amount
@@ -321,7 +352,8 @@ def main(argv=None):
     except ValueError as e:
         raise SystemExit(str(e)) from None
     jobs = load_jobs(args.jobs, args.k, args.auto_pitch, args.limit, args.limit_lookahead, args.limit_hold, args.envelope,
-                     args.envelope_floor, args.envelope_range, args.envelope_radius, args.auto_range, args.pitch_track, tw, tj)
+                     args.envelope_floor, args.envelope_range, args.envelope_radius, args.auto_range, args.pitch_track, tw, tj,
+                     args.lufs, args.loudness_max_db)
     tracked = any("pitch_track" in j for j in jobs)
     on_auto = any(j["auto_pitch"] for j in jobs)
     ranged = any("auto_range" in j for j in jobs)
@@ -332,7 +364,7 @@ def main(argv=None):
     from module.content_encoder import ContentEncoder
     from module.decoder import Decoder
     from module.f0_estimator import F0Estimator
-    from module.multistream import VoicePool, follow_envelope, limit_waves, measure_register, pitch_hz
+    from module.multistream import VoicePool, follow_envelope, limit_waves, measure_register, normalize_loudness, pitch_hz
     from module.pipeline import Converter
     from module.spectrogram import spectrogram
     from module.voice_library import VoiceLibrary
@@ -390,6 +422,8 @@ def main(argv=None):
         if job.get("envelope"):                                         # at 16 kHz, against the source the converter saw
             out = follow_envelope(out, utts[i], None, job["envelope"], args.envelope_floor, args.envelope_range, args.envelope_radius)
         out = audio_io.resample(out, 16000, sr, post_gain_db=job["gain"])
+        if job.get("lufs") is not None:                                 # on the device, at the file's own rate, ahead of the limiter
+            out = normalize_loudness(out, None, job["lufs"], int(sr), args.loudness_max_db)
         if job.get("limit_db") is not None:                             # on the device, before the normalisation and the save
             out = limit_waves(out, None, job["limit_db"], args.limit_lookahead, args.limit_hold, sr)
         out = out.cpu()

@@ -69,6 +69,12 @@ def build_parser():
                         help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5)")
     parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
                         help="milliseconds the limiter's gain stays down after a peak (default 20)")
+    parser.add_argument('-lufs', '--lufs', default=None, type=float, metavar="L",
+                        help="loudness normalisation: every output file is brought to this integrated loudness in LUFS (ITU-R BS.1770-4, "
+                             "-70 < L <= 0, e.g. -23 or -16) by one gain, after the output gain and before -lim and -norm (default: the "
+                             "level is left alone; this build only).  It can lift samples above full scale: use -lim beside it")
+    parser.add_argument('--loudness-max-db', default=12.0, type=float, metavar="DB",
+                        help="the most the loudness normalisation turns a file up or down (default 12)")
     parser.add_argument('-env', '--envelope', default=0.0, type=float, metavar="A",
                         help="envelope follow: the converted voice takes on the source's loudness contour by this amount, 0 (off, the "
                              "default) to 1 (module/multistream.py follow_envelope; this build only).  It can lift samples above full "
@@ -94,6 +100,9 @@ def main(argv=None):
     if args.limit is not None:
         from module.multistream import check_limit, limit_waves
         check_limit(args.limit, args.limit_lookahead, args.limit_hold)       # (before anything is loaded)
+    if args.lufs is not None:
+        from module.multistream import check_loudness, normalize_loudness
+        check_loudness(args.lufs, args.loudness_max_db)                      # (before anything is loaded)
     env = (args.envelope_floor, args.envelope_range, args.envelope_radius)
     if args.envelope != 0:
         from module.multistream import check_envelope, follow_envelope
@@ -140,6 +149,8 @@ def main(argv=None):
         if args.envelope > 0:                     # at 16 kHz, against the normalised mono source the converter saw
             out = follow_envelope(out, wf, None, args.envelope, *env)
         out = audio_io.resample(out, 16000, sr, post_gain_db=args.gain)            # resample, then gain (:136-137)
+        if args.lufs is not None:                 # on the device, at the file's own rate: the long-term level, ahead of the limiter
+            out = normalize_loudness(out, None, args.lufs, int(sr), args.loudness_max_db)
         if args.limit is not None:                # on the device, at the file's own rate, before -norm and the save
             out = limit_waves(out, None, args.limit, args.limit_lookahead, args.limit_hold, sr)
         out = out.cpu()

@@ -172,7 +172,11 @@ PROTOTYPES = {
     "alive_seam_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     "alive_limit_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     "alive_limit_waves": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP]),
-    "alive_envelope_waves": (_I, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _D, _D, _D, _VP, _VP]),
+    "alive_loudness_workspace_bytes": (_SZ, [_I, _I]),
+    "alive_loudness_measure_waves": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _D, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "alive_loudness_apply_waves": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _D, _VP, _VP]),
+    "alive_loudness_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "alive_envelope_waves": (_I,[_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _D, _D, _D, _VP, _VP]),
     "alive_ring_push_rows": (_I, [_VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "alive_emit_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I, _VP]),
     "alive_conceal_rows": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP]),

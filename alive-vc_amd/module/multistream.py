@@ -186,7 +186,30 @@ converter built without pitch_track allocates nothing, launches exactly what it 
 world_pitch on one session.  Class 0 is not a state: a tracked row never emits f0 = 0.  pitch_track_changed() reads back how many
 frames of each ring the tracker moved.  The defaults (1.0, 12.0, 2.0 semitones, 50 .. 1100 Hz) are design choices in logit units: with
 no trained weights, what tracking does to perceived quality is unmeasured.
+
+Loudness: every path leaves the converted voice at the level of the library rows it selected.  measure_loudness / normalize_loudness
+(csrc/loudness.hip) are the integrated loudness of ITU-R BS.1770-4 / EBU R 128 for one channel -- K-weighting, 400-ms blocks every 100
+ms, the absolute gate at -70 LUFS and the relative one 10 LU below the gated mean -- and the one gain per row that brings it to a
+target, within +-max_gain_db; rows at mixed rates go through one call.  The K-weighting recurrence runs in tiles of one 100-ms
+sub-block, every tile an independent lane run twice, with one short serial carry per row in between (include/alive_vc.h).  A converter
+built with loudness=True runs alive_loudness_rows in the tick AFTER the gate's edge and BEFORE the limiter, on what is emitted: for the
+sessions opened or set with lufs=L the span goes through the session's K-weighting filter at its own output rate into a running
+loudness -- per completed 400-ms block z, S = S d + z and W = W d + 1 with d = 2^(-0.1 / loudness_half_life), for the blocks above the
+absolute gate and, once the mean is trusted (W >= P = 10 loudness_prior), above S / W - 10 LU: a talker who drops by more than 10 LU is
+taken for a pause until W has decayed below the prior, then believed -- and is multiplied by a gain that ramps linearly over the span
+from the previous tick's to G = 1 + min(W / P, 1) (r - 1), r = sqrt(z_t W / S) within +-loudness_max_db, moved by at most
+loudness_slew_db dB per second.  The state (loud_state [B, 16]: the filter's, the open sub-block, the last three sub-blocks, S, W and
+the gain) is the session's, like phi: open and close start it over, set keeps it, a tick on which the session's lufs is off starts it
+over, a row that does not emit (filling, stalled) leaves it standing, enable_graph and the bf16 repeat save and restore it (with
+_seam_state).  Everything is device arrays: toggling and retuning never re-capture; a converter built without loudness allocates
+nothing, launches exactly what it did and refuses lufs=.  It works with input_sr != output_sr and with per-session rates (the filter
+and the sub-block are the session's own rate's).  loudness() reads the running loudness and the gain per slot back.  The gain can lift
+a sample above full scale: use the limiter beside it.  tools/loudness_ref.py restates everything bit for bit.  The defaults (half-life
+3 s, prior 1 s, gate -70 LUFS, +-12 dB, 6 dB/s) are design choices, not tuned: with no trained weights, how they sound is unmeasured.
 """
+import functools
+import math
+
 import numpy as np
 import torch
 
@@ -1481,6 +1504,209 @@ def limit_waves(wave, lens=None, limit_db=-1.0, lookahead_ms=5.0, hold_ms=20.0, 
     return (out, gmin_db(gmin.tolist())) if return_gain else out
 
 
+LOUDNESS_STATE, LOUDNESS_PARAMS = 16, 6         # ALIVE_LOUDNESS_STATE, ALIVE_LOUDNESS_PARAMS (include/alive_vc.h)
+LOUDNESS_GATE_LUFS = -70.0                      # the standard's absolute gate
+_loudness_ws = nat.Workspace()
+
+
+def loudness_hop(rate):
+    """the samples of a 100-ms sub-block at `rate` Hz: (rate + 5) // 10"""
+    return (int(rate) + 5) // 10
+
+
+def _loudness_biquad(f0, Q, fs, Vh=None):
+    K = math.tan(math.pi * f0 / fs)
+    a0 = 1.0 + K / Q + K * K
+    a1, a2 = 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0
+    if Vh is None:
+        return 1.0, -2.0, 1.0, a1, a2
+    Vb = Vh ** 0.4996667741545416
+    return (Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0, a1, a2
+
+
+@functools.lru_cache(maxsize=None)
+def loudness_filter(rate):
+    """the K-weighting at `rate` Hz as the kernels take it: (coef, ap), coef = (b0, b1, b2, a1, a2) of the shelf then of the
+    high-pass (the usual re-derivation of the standard's 48-kHz filter, in Python floats), ap the 16 entries of AP row by row: column k
+    of AP is the state left after loudness_hop(rate) zero samples from unit state k, by the kernels' own recurrence"""
+    fs = float(int(rate))
+    coef = (_loudness_biquad(1681.974450955533, 0.7071752369554196, fs, 10.0 ** (3.999843853973347 / 20.0))
+            + _loudness_biquad(38.13547087602444, 0.5003270373238773, fs))
+    b0, b1, b2, a1, a2, d0, d1, d2, e1, e2 = coef
+    cols = []
+    for k in range(4):
+        z = [1.0 if i == k else 0.0 for i in range(4)]
+        for _ in range(loudness_hop(rate)):                   # (v = 0.0: the products stay in, as the kernels keep them)
+            o1 = b0 * 0.0 + z[0]
+            z[0] = (b1 * 0.0 - a1 * o1) + z[1]
+            z[1] = b2 * 0.0 - a2 * o1
+            o2 = d0 * o1 + z[2]
+            z[2] = (d1 * o1 - e1 * o2) + z[3]
+            z[3] = d2 * o1 - e2 * o2
+        cols.append(z)
+    return coef, tuple(cols[k][r] for r in range(4) for k in range(4))
+
+
+def loudness_z(level):
+    """the mean square of a loudness in LUFS: 10^((L + 0.691) / 10)"""
+    return 10.0 ** ((float(level) + 0.691) / 10.0)
+
+
+def loudness_lufs(z):
+    """-0.691 + 10 log10(z) on the host; -inf for 0"""
+    return -0.691 + 10.0 * math.log10(z) if z > 0 else -math.inf
+
+
+def check_loudness(target_lufs, max_gain_db=12.0):
+    """a loudness target -> (z_t, gmax) as floats, None for target_lufs None (off; max_gain_db is still checked).  ValueError unless
+    target_lufs is None or a finite number (not a bool) with -70 < target_lufs <= 0, and max_gain_db a finite number >= 0: the gain
+    stays within +-max_gain_db"""
+    if not _number(max_gain_db) or not (np.isfinite(max_gain_db) and max_gain_db >= 0):
+        raise ValueError(f"loudness max gain {max_gain_db!r} must be a finite number of dB >= 0")
+    if target_lufs is None:
+        return None
+    if not _number(target_lufs) or not (np.isfinite(target_lufs) and LOUDNESS_GATE_LUFS < target_lufs <= 0):
+        raise ValueError(f"lufs={target_lufs!r} must be a finite number of LUFS in (-70, 0], or None for no loudness normalisation")
+    return loudness_z(target_lufs), 10.0 ** (float(max_gain_db) / 20.0)
+
+
+def check_loudness_stream(half_life=3.0, prior=1.0, gate_lufs=LOUDNESS_GATE_LUFS, max_db=12.0, slew_db=6.0):
+    """a converter's loudness settings -> (d, P, z_abs, gmax, slew_db) as floats: d = 2^(-0.1 / half_life) per 100-ms sub-block, P = 10
+    * prior blocks.  ValueError unless half_life is a finite number of seconds > 0, prior one >= 0, gate_lufs finite and <= -20,
+    max_db finite >= 0 and slew_db finite > 0 dB per second (none of them a bool)"""
+    if not _number(half_life) or not (np.isfinite(half_life) and half_life > 0):
+        raise ValueError(f"loudness_half_life={half_life!r} must be a finite number of seconds > 0")
+    if not _number(prior) or not (np.isfinite(prior) and prior >= 0):
+        raise ValueError(f"loudness_prior={prior!r} must be a finite number of seconds >= 0")
+    if not _number(gate_lufs) or not (np.isfinite(gate_lufs) and gate_lufs <= -20):
+        raise ValueError(f"loudness_gate_lufs={gate_lufs!r} must be a finite number of LUFS <= -20")
+    if not _number(max_db) or not (np.isfinite(max_db) and max_db >= 0):
+        raise ValueError(f"loudness_max_db={max_db!r} must be a finite number of dB >= 0")
+    if not _number(slew_db) or not (np.isfinite(slew_db) and slew_db > 0):
+        raise ValueError(f"loudness_slew_db={slew_db!r} must be a finite number of dB per second > 0")
+    return (2.0 ** (-0.1 / float(half_life)), 10.0 * float(prior), loudness_z(gate_lufs), 10.0 ** (float(max_db) / 20.0),
+            float(slew_db))
+
+
+def loudness_slew(slew_db, n, rate):
+    """the factor a session's gain may move by in one tick that emits n samples at `rate` Hz: 10^(slew_db (n / rate) / 20)"""
+    return 10.0 ** (float(slew_db) * (int(n) / float(rate)) / 20.0)
+
+
+def loudness_rows_(y, span_lo, span_len, emit, on, hop, coef, par, state):
+    """alive_loudness_rows in place on y [N, ld]: every emitting row whose `on` is set has its span K-weighted into its running
+    loudness and multiplied by the slewed gain towards its target; state float64 [N, LOUDNESS_STATE] moved on.  coef float64 [N, 10],
+    par float64 [N, LOUDNESS_PARAMS], hop int32 [N], emit / on one byte per row"""
+    n, ld = y.shape
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError("loudness_rows_: y must be contiguous float32 [N, ld]")
+    for name, t, w in (("coef", coef, 10), ("par", par, LOUDNESS_PARAMS), ("state", state, LOUDNESS_STATE)):
+        if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != (n, w):
+            raise ValueError(f"loudness_rows_: {name} must be contiguous float64 [N, {w}]")
+    for name, t in (("emit", emit), ("on", on)):
+        if t.element_size() != 1 or t.numel() != n:
+            raise ValueError(f"loudness_rows_: {name} must hold one byte per row")
+    nat.check(nat.lib().alive_loudness_rows(nat.ptr(y), n, ld, nat.ptr(span_lo), nat.ptr(span_len), nat.ptr(emit), nat.ptr(on),
+                                            nat.ptr(hop), nat.ptr(coef), nat.ptr(par), nat.ptr(state), nat.stream()),
+              "alive_loudness_rows")
+    return y
+
+
+def measure_loudness_rows(y, lens, hop, coef, ap, z_abs, max_tiles):
+    """alive_loudness_measure_waves: y float32 [N, ld], device int32 lens / hop [N], float64 coef [N, 10] and ap [N, 16] -> device
+    (zI float64 [N], c1 int32 [N], c2 int32 [N]); max_tiles: the most sub-blocks a row has (a row with more is not measured)"""
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.dim() != 2:
+        raise ValueError("measure_loudness_rows: y must be contiguous float32 [N, ld]")
+    n, ld = y.shape
+    dev = y.device
+    max_tiles = max(int(max_tiles), 1)
+    L = nat.lib()
+    nbytes = L.alive_loudness_workspace_bytes(n, max_tiles)
+    ws = _loudness_ws.get(max(nbytes, 8), dev)
+    zI = torch.empty(n, dtype=torch.float64, device=dev)
+    c1, c2 = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    nat.check(L.alive_loudness_measure_waves(nat.ptr(y), n, ld, nat.ptr(lens), nat.ptr(hop), nat.ptr(coef), nat.ptr(ap), float(z_abs),
+                                             max_tiles, nat.ptr(zI), nat.ptr(c1), nat.ptr(c2), nat.ptr(ws), ws.numel(), nat.stream()),
+              "alive_loudness_measure_waves")
+    return zI, c1, c2
+
+
+def apply_loudness_rows(y, lens, zI, c2, z_t, gmax, gain=None):
+    """alive_loudness_apply_waves: a new tensor, row n's first lens[n] samples times min(max(sqrt(z_t[n] / zI[n]), 1 / gmax), gmax)
+    (1 where c2[n] == 0), the rest copied; a row whose z_t is a NaN is copied bit for bit.  gain: float64 [N] or None"""
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.dim() != 2:
+        raise ValueError("apply_loudness_rows: y must be contiguous float32 [N, ld]")
+    n, ld = y.shape
+    out = torch.empty_like(y)
+    nat.check(nat.lib().alive_loudness_apply_waves(nat.ptr(out), nat.ptr(y), n, ld, nat.ptr(lens), nat.ptr(zI), nat.ptr(c2),
+                                                   nat.ptr(z_t), float(gmax), nat.ptr(gain), nat.stream()),
+              "alive_loudness_apply_waves")
+    return out
+
+
+def _loudness_inputs(what, wave, lens, rate):
+    """the shared front of measure_loudness / normalize_loudness: (one, y, lens list, device lens, hop, coef, ap, max_tiles)"""
+    one = wave.dim() == 1
+    y = (wave[None] if one else wave).contiguous()
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError(f"{what}: wave must be float32 [N, ld] or [ld], got {tuple(wave.shape)} {wave.dtype}")
+    n, ld = y.shape
+    lens = [ld] * n if lens is None else [int(v) for v in lens]
+    if len(lens) != n:
+        raise ValueError(f"{what}: {len(lens)} lens for {n} rows")
+    rates = list(rate) if isinstance(rate, (list, tuple)) else [rate] * n
+    if len(rates) != n:
+        raise ValueError(f"{what}: {len(rates)} rates for {n} rows")
+    for r in rates:
+        if not isinstance(r, (int, np.integer)) or isinstance(r, (bool, np.bool_)) or not 1000 <= int(r) <= 768000:
+            raise ValueError(f"{what}: rate={r!r} must be a whole number of Hz in [1000, 768000]")
+    dev = y.device
+    filt = [loudness_filter(int(r)) for r in rates]
+    hops = [loudness_hop(r) for r in rates]
+    tiles = max([min(max(v, 0), ld) // h for v, h in zip(lens, hops)] + [1])
+    return (one, y, lens, torch.tensor(lens, dtype=torch.int32, device=dev), torch.tensor(hops, dtype=torch.int32, device=dev),
+            torch.tensor([f[0] for f in filt], dtype=torch.float64, device=dev),
+            torch.tensor([f[1] for f in filt], dtype=torch.float64, device=dev), tiles)
+
+
+def measure_loudness(wave, lens=None, rate=16000):
+    """The integrated loudness of ITU-R BS.1770-4 (one channel, two-pass gating) of wave float32 [N, ld] (or [ld]) on the device: row
+    n's first lens[n] samples (default: the whole row) at `rate` Hz (a number, or one per row) -> (LUFS per row, -inf where nothing
+    passed the gates -- fewer than 400 ms, or silence --, the blocks above the absolute gate per row, the blocks above both gates
+    per row), three lists (a float and two ints for a 1-d wave).  One host read"""
+    one, y, _, lens_d, hop, coef, ap, tiles = _loudness_inputs("measure_loudness", wave, lens, rate)
+    zI, c1, c2 = measure_loudness_rows(y, lens_d, hop, coef, ap, loudness_z(LOUDNESS_GATE_LUFS), tiles)
+    zI, c1, c2 = zI.tolist(), c1.tolist(), c2.tolist()
+    out = [loudness_lufs(z) if c else -math.inf for z, c in zip(zI, c2)]
+    return (out[0], c1[0], c2[0]) if one else (out, c1, c2)
+
+
+def normalize_loudness(wave, lens, target_lufs, rate, max_gain_db=12.0, return_gain=False):
+    """Loudness normalisation: wave float32 [N, ld] (or [ld]) on the device -> a new tensor of its shape, row n's first lens[n] samples
+    (None: the whole row) at `rate` Hz (a number, or one per row) times the one gain that brings their integrated loudness to
+    target_lufs (a number, or one per row; None: the row is copied bit for bit), within +-max_gain_db; the rest of the row is copied.
+    A row nothing of which passes the gates keeps its level (gain 1).  The gain can lift a sample above full scale: limit_waves
+    belongs behind it.  ValueError as check_loudness.  return_gain=True: also the gain per row in dB (one host read; no host read
+    otherwise)"""
+    one, y, _, lens_d, hop, coef, ap, tiles = _loudness_inputs("normalize_loudness", wave, lens, rate)
+    n = y.shape[0]
+    targets = list(target_lufs) if isinstance(target_lufs, (list, tuple)) else [target_lufs] * n
+    if len(targets) != n:
+        raise ValueError(f"normalize_loudness: {len(targets)} target_lufs for {n} rows")
+    checked = [check_loudness(t, max_gain_db) for t in targets]
+    gmax = 10.0 ** (float(max_gain_db) / 20.0)
+    dev = y.device
+    zI, _, c2 = measure_loudness_rows(y, lens_d, hop, coef, ap, loudness_z(LOUDNESS_GATE_LUFS), tiles)
+    z_t = torch.tensor([math.nan if c is None else c[0] for c in checked], dtype=torch.float64, device=dev)
+    gain = torch.empty(n, dtype=torch.float64, device=dev) if return_gain else None
+    out = apply_loudness_rows(y, lens_d, zI, c2, z_t, gmax, gain)
+    out = out[0] if one else out
+    if not return_gain:
+        return out
+    db = [20.0 * math.log10(g) for g in gain.tolist()]
+    return out, (db[0] if one else db)
+
+
 ENVELOPE_TILE, ENVELOPE_MAX_RADIUS = 16, 4      # ALIVE_ENVELOPE_TILE, ALIVE_ENVELOPE_MAX_RADIUS (include/alive_vc.h)
 ENVELOPE_HOP = 320                              # the decoder's frame at 16 kHz
 
@@ -1715,7 +1941,7 @@ def db_scale(db):
 
 _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold",
            "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope", "conceal", "intonation", "auto_range",
-           "pitch_track", "track_weight", "track_jump")
+           "pitch_track", "track_weight", "track_jump", "lufs")
 
 
 class MultiStreamConverter:
@@ -1728,6 +1954,7 @@ class MultiStreamConverter:
     envelope = False                   # (likewise: whether the tick carries the envelope kernel)
     conceal = False                    # (likewise: whether lost chunks are concealed in front of the ring push; needs sparse)
     pitch_track = False                # (likewise: whether the f0 branch stores the class scores and carries the tracker kernel)
+    loud = False                       # (likewise: whether the tick carries the loudness kernel; loudness() is the read-back)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
@@ -1735,7 +1962,16 @@ class MultiStreamConverter:
                  limiter=False, limit_history=0.05, sparse=False, envelope=False, envelope_floor_db=-60.0,
                  envelope_range_db=12.0, envelope_radius=1, conceal=False, conceal_hold_ms=10.0, conceal_fade_ms=50.0,
                  conceal_recover_ms=5.0, pitch_range=False, pitch_range_max=2.0, pitch_track=False, track_lo=50, track_hi=1100,
-                 track_band=2.0):
+                 track_band=2.0, loudness=False, loudness_half_life=3.0, loudness_prior=1.0, loudness_gate_lufs=LOUDNESS_GATE_LUFS,
+                 loudness_max_db=12.0, loudness_slew_db=6.0):
+        if not isinstance(loudness, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: loudness must be a bool, got {loudness!r}")
+        if loudness:                       # (checked before anything is built)
+            try:
+                loud = check_loudness_stream(loudness_half_life, loudness_prior, loudness_gate_lufs, loudness_max_db,
+                                             loudness_slew_db)
+            except ValueError as e:
+                raise ValueError(f"MultiStreamConverter: {e}") from None
         if not isinstance(pitch_track, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: pitch_track must be a bool, got {pitch_track!r}")
         if pitch_track:                    # (checked before anything is built)
@@ -2024,6 +2260,23 @@ class MultiStreamConverter:
             self._conceal_run = [False] * B
             self._conceal_host = [False] * B               # (the sessions' switches, for the mirror)
             self.conceals = 0                              # (how many ticks launched alive_conceal_rows)
+        # loudness: the loudness kernel is part of the tick (captured once), after the gate's edge and before the limiter; per row,
+        # loud_on switches the session's normalisation, loud_hop / loud_coef are its rate's sub-block and K-weighting and loud_par its
+        # (z_abs, z_t, d, P, gmax, qs).  loud_state is the session's, like phi
+        self.loud = bool(loudness)
+        if self.loud:
+            self._loud = loud                                  # (d, P, z_abs, gmax, slew_db)
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.loud_on = torch.zeros(B, dtype=torch.bool, device=dev)
+            self.loud_hop = torch.full((B,), loudness_hop(self._out_rate(int(input_sr))), **i32)
+            self.loud_coef = torch.zeros(B, 10, dtype=torch.float64, device=dev)
+            self.loud_par = torch.zeros(B, LOUDNESS_PARAMS, dtype=torch.float64, device=dev)
+            self.loud_state = torch.zeros(B, LOUDNESS_STATE, dtype=torch.float64, device=dev)
+            self.loud_state[:, 12] = 1.0
+            if not (self.gate or self.crossfade or self.limiter or self.sparse):
+                lo, ln = self._span(self.chunk)
+                self.span_lo = torch.full((B,), lo, **i32)
+                self.span_len = torch.full((B,), ln, **i32)
         self._graph = None
         self._graph_pool_version = None
         self.captures = 0
@@ -2109,6 +2362,45 @@ class MultiStreamConverter:
                                   self._limit_shift(cs))[2:]
         except ValueError as e:
             raise ValueError(f"slot {slot}: {e}") from None
+
+    def _out_rate(self, rate):
+        """the rate of the final wave of a session at a declared rate: its own with per-session rates, else output_sr"""
+        return int(rate) if self._rt is not None else int(self.output_sr)
+
+    def _session_loudness(self, slot, p, rate=None):
+        """a session's loudness target -> (on, hop, coef, par) at its rate (on False: off), checked against the converter"""
+        target = p.get("lufs")
+        try:
+            checked = check_loudness(target)
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+        if checked is None:
+            return False, 0, None, None
+        if not self.loud:
+            raise ValueError(f"slot {slot}: lufs={target!r} needs a converter built with MultiStreamConverter(..., loudness=True)")
+        rate = int(self.rate[slot] if rate is None else rate)
+        fs = self._out_rate(rate)
+        d, P, z_abs, gmax, slew = self._loud
+        n = self._span(self._chunk_at(rate))[1]
+        return True, loudness_hop(fs), loudness_filter(fs)[0], (z_abs, checked[0], d, P, gmax, loudness_slew(slew, n, fs))
+
+    def _loud_reset(self, slot):
+        self.loud_state[slot] = 0.0
+        self.loud_state[slot, 12] = 1.0
+
+    def loudness(self):
+        """the sessions' running loudness after the latest tick, a list of B pairs (LUFS, gain in dB): the running loudness S / W of
+        what the session emitted BEFORE the gain (-inf before its first counted block) and the gain the latest tick ended at; (-inf,
+        0.0) for a slot that does not normalise (or is closed).  One host read"""
+        if not self.loud:
+            raise ValueError("loudness needs a converter built with MultiStreamConverter(..., loudness=True)")
+        out = []
+        for b, st in enumerate(self.loud_state.tolist()):
+            if not (self.is_open[b] and self.params[b].get("lufs") is not None):
+                out.append((-math.inf, 0.0))
+                continue
+            out.append((loudness_lufs(st[10] / st[11]) if st[11] > 0 else -math.inf, 20.0 * math.log10(st[12]) if st[12] > 0 else 0.0))
+        return out
 
     def _session_envelope(self, slot, p):
         """a session's envelope amount (None: 0), checked against the converter"""
@@ -2200,6 +2492,7 @@ class MultiStreamConverter:
         env = self._session_envelope(slot, p)
         con = self._session_conceal(slot, p, rate)
         track = self._session_track(slot, p)
+        loud = self._session_loudness(slot, p, rate)
         names, weights = blend_spec(p["voice"], self.pool, k, self.S)
         world = p["world_pitch"]
         if not isinstance(world, (bool, np.bool_)):
@@ -2266,6 +2559,12 @@ class MultiStreamConverter:
             self.look[slot], self.hold[slot], self.ceil[slot] = limit
         if self.envelope:
             self.env_amount[slot] = env
+        if self.loud:
+            self.loud_on[slot] = loud[0]
+            if loud[0]:
+                self.loud_hop[slot] = loud[1]
+                self.loud_coef[slot] = torch.tensor(loud[2], dtype=torch.float64)
+                self.loud_par[slot] = torch.tensor(loud[3], dtype=torch.float64)
         if self.conceal:
             self.conceal_on[slot], self._conceal_host[slot] = con[0], con[0]
             self._conceal_consts[:, slot] = torch.tensor(con[1], dtype=torch.int32)
@@ -2319,7 +2618,7 @@ class MultiStreamConverter:
         if self._rt is None:
             return
         c = self._chunks[rate]
-        if self.gate or self.crossfade or self.limiter or self.sparse:
+        if self.gate or self.crossfade or self.limiter or self.sparse or self.loud:
             self.span_lo[slot], self.span_len[slot] = self._span(c)
         if self.sparse:
             self.chunk_len[slot], self.ring_len[slot] = c, c * self.buffersize
@@ -2336,7 +2635,7 @@ class MultiStreamConverter:
     def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None,
              auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0,
              limit_hold_ms=20.0, envelope=0.0, conceal=None, intonation=1.0, auto_range=False, pitch_track=False, track_weight=1.0,
-             track_jump=12.0):
+             track_jump=12.0, lufs=None):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
@@ -2362,7 +2661,9 @@ class MultiStreamConverter:
         pitch_track=True (needs a pitch_track=True converter; not together with world_pitch): the session's f0 is the Viterbi path over
         the estimator's class scores of its ring instead of their per-frame argmax, at track_weight per semitone moved inside the
         converter's band and track_jump for any other move (both >= 0, in the units of the scores); the followers and the transform see
-        the tracked contour"""
+        the tracked contour.
+        lufs (needs a loudness=True converter): the session's loudness target in LUFS, -70 < lufs <= 0 (None: the session's level is
+        left alone): what the session emits is brought to it by a running BS.1770 loudness and a slewed gain, ahead of the limiter"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
@@ -2372,7 +2673,7 @@ class MultiStreamConverter:
                  k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold, crossfade_ms=crossfade_ms, limit_db=limit_db,
                  limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms, envelope=envelope, conceal=conceal,
                  intonation=intonation, auto_range=auto_range, pitch_track=pitch_track, track_weight=track_weight,
-                 track_jump=track_jump)
+                 track_jump=track_jump, lufs=lufs)
         self._apply(slot, p, rate)                            # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -2388,13 +2689,15 @@ class MultiStreamConverter:
             self.stored[slot] = 0                             # never fade from another session's tail
         if self.limiter:
             self._limit_reset(slot)                           # a new stream: no peak behind it
+        if self.loud:
+            self._loud_reset(slot)                            # a new stream: nothing heard yet, the gain at 1
         self._conceal_clear(slot)                             # a new stream: no run behind it
         return self
 
     def set(self, slot, **params):
         """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
         intonation, auto_range, pitch_track, track_weight, track_jump, gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms,
-        limit_hold_ms, envelope, conceal; the gate's state, the saved tail and the
+        limit_hold_ms, envelope, conceal, lufs; the gate's state, the saved tail, the running loudness with its gain and the
         limiter's history are kept: a longer crossfade fades over what the tail holds this tick and in full from the next, and a
         limiter switched on or retuned sees the required gains of the samples already emitted).
         The running source register is kept: a new voice changes the target only, and auto_pitch=True after False resumes from
@@ -2454,6 +2757,9 @@ class MultiStreamConverter:
         if self.envelope:
             self.env_amount[slot] = 0.0
             self.env_minmax[slot] = 1.0
+        if self.loud:
+            self.loud_on[slot] = False
+            self._loud_reset(slot)
         if self.conceal:
             self.conceal_on[slot], self._conceal_host[slot] = False, False
             self._conceal_consts[:, slot] = self._conceal_closed
@@ -2626,6 +2932,9 @@ class MultiStreamConverter:
                        self.g0 if self.gate else None, self.g1 if self.gate else None, self.seam_stats)
         if self.gate:
             gate_apply_rows_(wave, self.span_lo, self.span_len, self.g0, self.g1)
+        if self.loud:                                         # the long-term level: behind the gate's edge, ahead of the limiter
+            loudness_rows_(wave, self.span_lo, self.span_len, self.emit, self.loud_on, self.loud_hop, self.loud_coef, self.loud_par,
+                           self.loud_state)
         if self.limiter:                                      # last: the limiter sees what is emitted (the seam's tail stays un-limited)
             if wave.shape[1] != max(self._limit_len.values()):
                 raise RuntimeError(f"final wave of {wave.shape[1]} samples, the limiter expects {max(self._limit_len.values())}")
@@ -2659,11 +2968,13 @@ class MultiStreamConverter:
 
     def _seam_state(self):
         """a copy of the sessions' tails and how much of them is valid (None without crossfade) -- and, in a limiter converter, of
-        the limiter's histories and latest gains: (tail, stored, limit_hist, limit_gmin), the absent halves None"""
-        if not (self.crossfade or self.limiter):
+        the limiter's histories and latest gains, and in a loudness converter of the loudness states: (tail, stored, limit_hist,
+        limit_gmin, loud_state), the absent parts None"""
+        if not (self.crossfade or self.limiter or self.loud):
             return None
         seam = (self.tail.clone(), self.stored.clone()) if self.crossfade else (None, None)
-        return seam + ((self.limit_hist.clone(), self.limit_gmin.clone()) if self.limiter else (None, None))
+        seam = seam + ((self.limit_hist.clone(), self.limit_gmin.clone()) if self.limiter else (None, None))
+        return seam + (self.loud_state.clone() if self.loud else None,)
 
     def _seam_restore(self, saved):
         if saved is not None:
@@ -2673,6 +2984,8 @@ class MultiStreamConverter:
             if len(saved) > 2 and saved[2] is not None:
                 self.limit_hist.copy_(saved[2])
                 self.limit_gmin.copy_(saved[3])
+            if len(saved) > 4 and saved[4] is not None:
+                self.loud_state.copy_(saved[4])
 
     def _run(self):
         if self._reserved:

@@ -34,6 +34,9 @@ The sessions file is a JSON list; each entry:
                                           default -lim), the milliseconds over which the gain falls ahead of a peak (at most the
                                           session's chunk; default --limit-lookahead) and those it stays down after one (default
                                           --limit-hold)
+   "lufs": -23,                           optional, a number of LUFS in (-70, 0] or null (default: -lufs): what the session emits is
+                                          brought to this loudness by a running ITU-R BS.1770 measurement and a slewed gain, ahead of
+                                          the limiter (module/multistream.py "Loudness"); null: the session's level is left alone
    "envelope": 0.7,                       optional, a number in [0, 1] or null (default: -env): how far the session's converted voice
                                           follows the loudness contour of its input (module/multistream.py "Envelope follow"); 0 or
                                           null: the decoder's own level
@@ -76,6 +79,9 @@ The converter carries the seam kernel only if some session ends up with a crossf
 the key, run without the flag, runs as before.
 The converter carries the limiter kernel only if some session ends up limited ("limit_db", or -lim): a file without the key, run
 without the flag, runs as before.
+The converter carries the loudness kernel only if some session ends up normalised ("lufs", or -lufs): a file without the key, run
+without the flag, runs as before.  --loudness-half-life / --loudness-prior / --loudness-gate / --loudness-max-db / --loudness-slew hold
+for the whole converter.
 The converter carries the envelope kernel only if some session ends up following ("envelope" above 0, or -env): a file without the
 key, run without the flag, runs as before.
 The voices are condensed only for sessions with a "codebook" (or under --codebook): a file without the key, run without the flag, runs
@@ -115,6 +121,7 @@ from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
 from module.multistream import (MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
                                 check_conceal_ms, check_crossfade_ms, check_envelope, check_intonation, check_limit,
+                                check_loudness, check_loudness_stream,
                                 gate_hold_ticks, gate_thr_ms, measure_register)
 from module.spectrogram import spectrogram                       # noqa: E402
 from module.voice_library import VoiceLibrary                    # noqa: E402
@@ -125,6 +132,7 @@ GATE_KEYS = ("gate_db", "gate_hold")     # taken per session too; a loaded sessi
 SEAM_KEYS = ("crossfade_ms",)            # taken per session too; a loaded session carries it only when it crossfades
 LIMIT_KEYS = ("limit_db", "limit_lookahead_ms", "limit_hold_ms")      # likewise; a loaded session carries them only when it limits
 ENVELOPE_KEYS = ("envelope",)            # likewise; a loaded session carries it only when it follows (an amount above 0)
+LOUDNESS_KEYS = ("lufs",)                # likewise; a loaded session carries it only when it is normalised
 CODEBOOK_KEYS = ("codebook",)            # taken per session too; a loaded session carries it only when its voice is condensed
 STALL_KEYS = ("stall",)                  # a loaded session carries it only when its entry has the key (the converter is then sparse)
 LOSE_KEYS = ("lose",)                    # likewise (the converter is then sparse and conceals)
@@ -173,6 +181,20 @@ def build_parser():
                         help="milliseconds over which the limiter's gain falls ahead of a peak and recovers after the hold (default 5; a session's \"limit_lookahead_ms\" overrides)")
     parser.add_argument('--limit-hold', default=20.0, type=float, metavar="MS",
                         help="milliseconds the limiter's gain stays down after a peak (default 20; a session's \"limit_hold_ms\" overrides)")
+    parser.add_argument('-lufs', '--lufs', default=None, type=float, metavar="L",
+                        help="loudness normalisation: what every session emits is brought to this loudness in LUFS (ITU-R BS.1770, -70 < L "
+                             "<= 0) by a running measurement and a slewed gain, ahead of the limiter, unless its \"lufs\" says otherwise "
+                             "(module/multistream.py \"Loudness\"; default: the level is left alone)")
+    parser.add_argument('--loudness-half-life', default=3.0, type=float, metavar="S",
+                        help="seconds after which a 400-ms block counts half in a session's running loudness (default 3)")
+    parser.add_argument('--loudness-prior', default=1.0, type=float, metavar="S",
+                        help="seconds of counted blocks until a session's running loudness is trusted in full (default 1)")
+    parser.add_argument('--loudness-gate', default=-70.0, type=float, metavar="LUFS",
+                        help="the absolute gate under which a block is not counted (default -70)")
+    parser.add_argument('--loudness-max-db', default=12.0, type=float, metavar="DB",
+                        help="the most the loudness gain turns a session up or down (default 12)")
+    parser.add_argument('--loudness-slew', default=6.0, type=float, metavar="DB",
+                        help="the most the loudness gain moves per second, in dB (default 6)")
     parser.add_argument('-env', '--envelope', default=0.0, type=float, metavar="A",
                         help="envelope follow: the sessions' converted voices take on their inputs' loudness contours by this amount, 0 (off, the "
                              "default) to 1, unless their \"envelope\" says otherwise (module/multistream.py \"Envelope follow\").  It can "
@@ -319,6 +341,17 @@ def session_limit(s, where, limit_db=None, lookahead_ms=5.0, hold_ms=20.0):
     return None if checked is None else (float(db), checked[1], checked[2])
 
 
+def session_loudness(s, where, lufs=None):
+    """an entry's "lufs" (default `lufs`; a JSON null switches the default off) -> a float in (-70, 0], or None for a session whose
+    level is left alone; ValueError otherwise"""
+    target = s.get("lufs", lufs)
+    try:
+        check_loudness(target)
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return None if target is None else float(target)
+
+
 def session_envelope(s, where, envelope=0.0, floor_db=-60.0, range_db=12.0, radius=1):
     """an entry's "envelope" (default `envelope`; a JSON null or 0 switches the default off) -> the amount as a float in (0, 1], or
     None for a session that does not follow; ValueError otherwise (the three tuning values are those of the flags, checked with it)"""
@@ -392,7 +425,7 @@ def supply_ticks(start, n_chunks, stall=None):
 def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None, crossfade_ms=None, limit_db=None,
                   limit_lookahead_ms=5.0, limit_hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0,
                   envelope_radius=1, conceal_hold_ms=10.0, conceal_fade_ms=50.0, conceal_recover_ms=5.0, intonation=1.0,
-                  auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT, track_jump=common.TRACK_JUMP):
+                  auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT, track_jump=common.TRACK_JUMP, lufs=None):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
@@ -402,7 +435,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     tuple of ticks) only on a session whose entry has the key, as "lose" (a sorted tuple of ticks) and "conceal" (a bool); "intonation"
     (default `intonation`) only on a session whose factor is not 1, "auto_range" (default `auto_range`) only on one that is on, and
     "range_st" only where the entry has it; "pitch_track" (true), "track_weight" and "track_jump" (defaults `pitch_track`,
-    `track_weight`, `track_jump`) only on a session that tracks; ValueError on a malformed entry"""
+    `track_weight`, `track_jump`) only on a session that tracks; "lufs" (default `lufs`) only on a session that is normalised;
+    ValueError on a malformed entry"""
     session_track({}, "-pt / --track-weight / --track-jump", pitch_track, track_weight, track_jump)
     try:
         check_conceal_ms(conceal_hold_ms, conceal_fade_ms, conceal_recover_ms)
@@ -416,6 +450,7 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     env = (envelope_floor_db, envelope_range_db, envelope_radius)
     session_envelope({}, "-env / --envelope-floor / --envelope-range / --envelope-radius", envelope, *env)
     session_range({}, "-int / --auto-range", intonation, auto_range)
+    session_loudness({}, "-lufs", lufs)
     with open(path) as f:
         sessions = json.load(f)
     if not isinstance(sessions, list) or not sessions:
@@ -426,15 +461,17 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
         unknown = (set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(CODEBOOK_KEYS)
-                   - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS) - set(RANGE_KEYS) - set(RANGE_ST_KEYS) - set(TRACK_KEYS))
+                   - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS) - set(RANGE_KEYS) - set(RANGE_ST_KEYS) - set(TRACK_KEYS)
+                   - set(LOUDNESS_KEYS))
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS + TRACK_KEYS})")
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS + TRACK_KEYS + LOUDNESS_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
         lim = session_limit(s, f"session {i}", limit_db, limit_lookahead_ms, limit_hold_ms)
         amount = session_envelope(s, f"session {i}", envelope, *env)
+        target = session_loudness(s, f"session {i}", lufs)
         rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))      # noqa: E731
         blend = blend_sources(s, f"session {i}", rel) if "blend" in s else None
         if blend is None and s.get("target") is None and s.get("lib") is None:
@@ -466,6 +503,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             e["limit_db"], e["limit_lookahead_ms"], e["limit_hold_ms"] = lim
         if amount is not None:
             e["envelope"] = amount
+        if target is not None:
+            e["lufs"] = target
         if size is not None:
             e["codebook"] = size
         if stall is not None:
@@ -639,7 +678,13 @@ def main(argv=None):
     sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook,
                              args.crossfade, args.limit, args.limit_lookahead, args.limit_hold, args.envelope, args.envelope_floor,
                              args.envelope_range, args.envelope_radius, args.conceal_hold, args.conceal_fade, args.conceal_recover,
-                             args.intonation, args.auto_range, args.pitch_track, tw, tj)
+                             args.intonation, args.auto_range, args.pitch_track, tw, tj, args.lufs)
+    loud = dict(loudness_half_life=args.loudness_half_life, loudness_prior=args.loudness_prior, loudness_gate_lufs=args.loudness_gate,
+                loudness_max_db=args.loudness_max_db, loudness_slew_db=args.loudness_slew)
+    try:
+        check_loudness_stream(*loud.values())                           # (before anything is loaded)
+    except ValueError as e:
+        raise SystemExit(f"Error: {e}") from None
     if any(s["sr"] is not None for s in sessions) and args.input_sr != args.output_sr:
         raise SystemExit(f"Error: sessions with their own \"sr\" need -isr == -osr (got {args.input_sr} and {args.output_sr})")
     if args.device != 'cuda' or not torch.cuda.is_available():
@@ -686,6 +731,7 @@ def main(argv=None):
                                 **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}),
                                 **(dict(crossfade=True) if any("crossfade_ms" in s for s in sessions) else {}),
                                 **(dict(limiter=True) if any("limit_db" in s for s in sessions) else {}),
+                                **(dict(loudness=True, **loud) if any("lufs" in s for s in sessions) else {}),
                                 **(dict(envelope=True, envelope_floor_db=args.envelope_floor, envelope_range_db=args.envelope_range,
                                         envelope_radius=args.envelope_radius) if any("envelope" in s for s in sessions) else {}),
                                 **(dict(sparse=True) if args.sparse or conceal or any("stall" in s for s in sessions) else {}),
@@ -694,7 +740,7 @@ def main(argv=None):
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
                    **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CONCEAL_KEYS + RANGE_KEYS + TRACK_KEYS
-                      if g in s})
+                      + LOUDNESS_KEYS if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()

@@ -955,6 +955,66 @@ int alive_limit_rows(float* y, int N, int ld, const int* span_lo, const int* spa
 int alive_limit_waves(float* out, const float* y, int N, int ld, const int* len, int look, int hold, const float* ceil, float* gmin,
                       void* stream);
 
+/* Loudness (csrc/loudness.hip): programme loudness after ITU-R BS.1770-4 / EBU R 128 for one channel, measured and normalised per file
+ * (offline) and per session (streaming, between alive_gate_apply_rows and alive_limit_rows).  All pointers are DEVICE pointers; no call
+ * allocates, synchronises or reads anything on the host; the grids depend on N, ld and max_tiles alone (graph-capturable: a captured
+ * call serves any settings).  No atomics; every store is a plain vector store.  Everything is fp64 with every operation rounded on its
+ * own; the device uses only + - * / sqrt and compares, and every 10^x, 2^x and tan is the host's: bitwise tools/loudness_ref.py.
+ * K-weighting at rate fs, coef = (b0, b1, b2, a1, a2) of the shelf then of the high-pass, 10 doubles per row, the usual re-derivation of
+ * the standard's 48-kHz filter:
+ *     shelf      f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196; K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ *                Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2; b0 = (Vh + Vb K / Q + K^2) / a0, b1 = 2 (K^2 - Vh) / a0,
+ *                b2 = (Vh - Vb K / Q + K^2) / a0, a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0
+ *     high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773; b = (1, -2, 1), a1 and a2 as above
+ * Both run in transposed direct form II, the high-pass fed the shelf's o; a non-finite input sample counts as 0.0:
+ *     o = b0 v + z1;   z1 = (b1 v - a1 o) + z2;   z2 = b2 v - a2 o
+ * With H = hop = (fs + 5) / 10 samples per 100-ms sub-block, q[j] is the sum of the squared filter output p over sub-block j (acc = acc
+ * + p p in sample order from 0.0) and block b is z[b] = (((q[b] + q[b + 1]) + q[b + 2]) + q[b + 3]) / (double)(4 H); samples past the
+ * last whole sub-block are not measured.  z_abs = 10^((gate + 0.691) / 10), z_t = 10^((target + 0.691) / 10).
+ *   alive_loudness_workspace_bytes   scratch of alive_loudness_measure_waves for N rows of at most max_tiles sub-blocks: 9 doubles
+ *                       per tile (0: arguments out of range).
+ *   alive_loudness_measure_waves   offline, stateless.  y float [N][ld]; per row len (int32, clamped to [0, ld]), hop (int32), coef
+ *                       double [N][10] and ap double [N][16]: mixed rates are allowed in one call.  THE FILTER RUNS IN TILES: a tile
+ *                       is a sub-block (hop samples), every tile is one lane.  e[j] is the 4-state left by the recurrence over tile j
+ *                       from zero state; ap[r * 4 + k] = AP[r][k], column k of AP the state left after hop zero samples from unit
+ *                       state k (the host's, by the same recurrence); s[0] = 0 and
+ *                           s[j + 1][r] = (((AP[r][0] s[j][0] + AP[r][1] s[j][1]) + AP[r][2] s[j][2]) + AP[r][3] s[j][3]) + e[j][r];
+ *                       q[j] comes from the recurrence over tile j started from s[j].  Then, with nb = len / hop and all sums
+ *                       ascending from 0.0: pass 1 sums z[b] over the blocks with z[b] > z_abs and counts them, c1; rel = 0.1 (sum1 /
+ *                       c1); pass 2 sums over the blocks with z[b] > z_abs and z[b] > rel and counts them, c2; zI = sum2 / c2, or 0.0
+ *                       where c2 == 0 (fewer than four sub-blocks, or silence).  A row with hop < 1 or nb > max_tiles is not
+ *                       measured (c1 = c2 = 0).  0 < N <= 65535; ld, max_tiles > 0; 0 < z_abs, finite; workspace_bytes at least
+ *                       alive_loudness_workspace_bytes(N, max_tiles).
+ *   alive_loudness_apply_waves   offline, OUT OF PLACE (an `out` that overlaps y is refused): g = min(max(sqrt(z_t[n] / zI[n]), 1 /
+ *                       gmax), gmax), g = 1 where c2[n] == 0; out[i] = (float)((double)y[i] g) for i < len[n], the rest of the row is
+ *                       copied.  A row whose z_t is a NaN is copied bit for bit.  gain double [N] or NULL: g per row (1 for a copied
+ *                       row).  0 < N <= 65535, ld > 0, 1 <= gmax, finite.
+ *   alive_loudness_rows   streaming, in place, one block per row n of y[N][ld].  Per row: span_lo, span_len int32 (the emitted span, n =
+ *                       span_len), emit and on bytes, hop int32, coef double [10], par double [ALIVE_LOUDNESS_PARAMS] = (z_abs, z_t, d,
+ *                       P, gmax, qs) with d = 2^(-0.1 / half life), P = 10 * the prior in seconds (blocks) and qs = 10^(slew (n / fs) /
+ *                       20); the row's state double [ALIVE_LOUDNESS_STATE] = (the four filter states, acc, cnt, the last three q oldest
+ *                       first, nsub, S, W, g, 0, 0, 0), a new stream starting from zeros with g = 1.
+ *                         emit[n] == 0: y and the state untouched;
+ *                         on[n] == 0, or a row whose regions do not fit (hop < 1, span_lo < 0, span_len < 1, span_lo + span_len > ld):
+ *                           y untouched, the state back to its start; nothing outside [0, ld) is ever read or written;
+ *                         else, for i ascending over the span: filter, acc = acc + p p, cnt = cnt + 1, and when cnt >= hop:
+ *                           nsub = min(nsub + 1, 4); z = (((q0 + q1) + q2) + acc) / (double)(4 H); S = S d, W = W d; if nsub == 4 and z
+ *                           > z_abs and (W < P or z W > 0.1 S): S = S + z, W = W + 1; (q0, q1, q2) = (q1, q2, acc), acc = cnt = 0.
+ *                           Then G = 1 if W == 0, else r = min(max(sqrt(z_t / (S / W)), 1 / gmax), gmax), a = min(W / P, 1), G = 1 + a
+ *                           (r - 1); G = min(max(G, g / qs), g qs); y[span_lo + i] = (float)((double)y[span_lo + i] (g + (G - g)
+ *                           ((double)(i + 1) / (double)n))); g = G.
+ *                       The relative gate is tested against the running mean only while that mean is trusted (W >= P).  N, ld > 0. */
+#define ALIVE_LOUDNESS_STATE 16
+#define ALIVE_LOUDNESS_PARAMS 6
+size_t alive_loudness_workspace_bytes(int N, int max_tiles);
+int alive_loudness_measure_waves(const float* y, int N, int ld, const int* len, const int* hop, const double* coef, const double* ap,
+                                 double z_abs, int max_tiles, double* zI, int* c1, int* c2, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int alive_loudness_apply_waves(float* out, const float* y, int N, int ld, const int* len, const double* zI, const int* c2,
+                               const double* z_t, double gmax, double* gain, void* stream);
+int alive_loudness_rows(float* y, int N, int ld, const int* span_lo, const int* span_len, const unsigned char* emit,
+                        const unsigned char* on, const int* hop, const double* coef, const double* par, double* state, void* stream);
+
 /* The device edge of a sparse multi-session converter (csrc/ring.hip): the sessions' int16 rings kept on the device, and the emitted
  * spans cut there.  All pointers are DEVICE pointers; no call allocates, synchronises or reads anything on the host; the grids depend
  * on N and the strides alone (graph-capturable: a captured call serves any lengths and masks).  No atomics.

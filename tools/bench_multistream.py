@@ -39,6 +39,14 @@ more launch pair after the decoder, alive_envelope_waves, csrc/envelope.hip) bes
 and timed in alternating rounds (envelope_off_tick_*; the medians over the rounds, and the spread of the plain converter's rounds as the
 yardstick), the call's own time by device events around 200 back-to-back eager calls at the tick's shapes (envelope_call_us, its fill
 launch included) with the 12 B L bytes it moves (envelope_call_bytes), and the gains of the last tick (envelope_db_min / _max).
+--loudness adds the graph tick p50 / p99 of a loudness=True converter with every session normalised to -23 LUFS (loudness_tick_*: one
+more launch between the gate's edge and the limiter, alive_loudness_rows, csrc/loudness.hip) beside the plain converter, both alive in
+the one process and timed in alternating rounds (loudness_off_tick_*; the medians over the rounds, and the spread of the plain
+converter's rounds as the yardstick), the call's own time by device events around 200 back-to-back eager calls on the converter's own
+arrays (loudness_call_us, spans of loudness_span samples) and the gains of the last tick (loudness_gain_db_min / _max, on SYNTHETIC
+weights).
+--loudness-offline runs the offline loudness leg ALONE: alive_loudness_measure_waves (measure_us) and measure + apply, what
+normalize_loudness launches (measure_apply_us), over 64 rows of 10 s and 8 rows of 60 s at 48 kHz, by device events around 20 calls.
 --pitch-track adds the graph tick p50 / p99 of a pitch_track=True converter with no session tracking (track_none_tick_*: the class
 scores stored, their argmax, and the tracker's blocks returning at once) and with every session tracking at the defaults
 (track_all_tick_*: alive_f0_track_rows over every ring, csrc/f0_track.hip) beside the converter built without it (track_off_tick_*),
@@ -72,7 +80,9 @@ alive_ring_push_rows with every row present (push_call_us).
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch] [--pitch-range]
-                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--pitch-track] [--out multistream.json]
+                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--loudness] [--pitch-track]
+                                      [--out multistream.json]
+    python tools/bench_multistream.py --loudness-offline [--out loudness_offline.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
     python tools/bench_multistream.py --sparse [--batches 128,1024] [--ticks 40] [--out profiles/multistream_sparse_bench.json]
     python tools/bench_multistream.py --conceal [--batches 128,1024] [--ticks 40] [--out profiles/multistream_conceal_bench.json]
@@ -135,6 +145,34 @@ def time_calls(fn, reps=200):
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) * 1e3 / reps
+
+
+def loudness_offline_leg(shapes=((64, 10.0), (8, 60.0)), rate=48000):
+    """measure_loudness_rows alone and measure + apply (what normalize_loudness launches) over N rows of `seconds` at `rate` Hz,
+    device time per call: one record per shape"""
+    recs = []
+    coef, ap = MS.loudness_filter(rate)
+    hop_ = MS.loudness_hop(rate)
+    for n, seconds in shapes:
+        ld = int(seconds * rate)
+        y = torch.randn(n, ld, device="cuda", generator=torch.Generator(device="cuda").manual_seed(7)) * 0.1
+        lens = torch.full((n,), ld, dtype=torch.int32, device="cuda")
+        hop = torch.full((n,), hop_, dtype=torch.int32, device="cuda")
+        coefs = torch.tensor([coef] * n, dtype=torch.float64, device="cuda")
+        aps = torch.tensor([ap] * n, dtype=torch.float64, device="cuda")
+        z_t = torch.full((n,), MS.loudness_z(-23.0), dtype=torch.float64, device="cuda")
+        z_abs, tiles = MS.loudness_z(MS.LOUDNESS_GATE_LUFS), ld // hop_
+
+        def both():
+            zI, _, c2 = MS.measure_loudness_rows(y, lens, hop, coefs, aps, z_abs, tiles)
+            return MS.apply_loudness_rows(y, lens, zI, c2, z_t, 4.0)
+        rec = dict(rows=n, seconds=seconds, rate=rate, tiles_per_row=tiles,
+                   measure_us=round(time_calls(lambda: MS.measure_loudness_rows(y, lens, hop, coefs, aps, z_abs, tiles), 20), 1),
+                   measure_apply_us=round(time_calls(both, 20), 1), bytes_read_once=4 * n * ld)
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+        del y
+    return recs
 
 
 def conceal_leg(nets, batches=(128, 1024), ticks=40, warmup=6):
@@ -361,6 +399,10 @@ def main():
                                                          "and the plain converter a second time")
     ap.add_argument("--envelope", action="store_true", help="also time an envelope=True converter, every session following at amount "
                                                             "1, against the plain converter in alternating rounds, and the call alone")
+    ap.add_argument("--loudness", action="store_true", help="also time a loudness=True converter, every session normalised to -23 LUFS, "
+                    "alternated with a plain one, and the loudness call alone")
+    ap.add_argument("--loudness-offline", action="store_true", help="the offline loudness leg alone: measure_loudness and "
+                    "normalize_loudness over 64 rows of 10 s at 48 kHz, and over 8 rows of 60 s")
     ap.add_argument("--pitch-track", action="store_true", help="also time a pitch_track=True converter with no session and with "
                     "every session tracking, beside the plain converter in alternating rounds")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
@@ -389,6 +431,12 @@ def main():
         return
     if args.sparse:
         rows = sparse_leg(nets, batches, args.ticks, args.warmup)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(rows, open(args.out, "w"), indent=1)
+        return
+    if args.loudness_offline:
+        rows = loudness_offline_leg()
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             json.dump(rows, open(args.out, "w"), indent=1)
@@ -580,6 +628,35 @@ def main():
                     rec["envelope_call_us"] = round(a.elapsed_time(b) * 1e3 / 200, 2)
                     rec["envelope_call_bytes"] = 12 * B * ld
                     del both, ec
+                if args.loudness:
+                    both = {}
+                    for name, kw, sess in (("loudness_off", {}, {}), ("loudness", dict(loudness=True), dict(lufs=-23.0))):
+                        c = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, **kw)
+                        for s in range(B):
+                            c.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, **sess)
+                        c.enable_graph()
+                        both[name] = c
+                    times = {name: [] for name in both}
+                    for _ in range(5):                         # alternating rounds in the one process
+                        for name, c in both.items():
+                            times[name].append(time_ticks(c, B, chunk, args.ticks, args.warmup + bs + 1, 300))
+                    for name, ts in times.items():
+                        rec[f"{name}_tick_p50_ms"] = round(float(np.median([t[0] for t in ts])), 3)
+                        rec[f"{name}_tick_p99_ms"] = round(float(np.median([t[1] for t in ts])), 3)
+                        rec[f"{name}_tick_p50_rounds_ms"] = [round(t[0], 3) for t in ts]
+                    lc = both["loudness"]
+                    read = lc.loudness()
+                    assert lc.captures == 1 and all(np.isfinite(g) for _, g in read), (read, lc.captures)
+                    rec["loudness_gain_db_min"], rec["loudness_gain_db_max"] = (round(min(g for _, g in read), 2),
+                                                                                round(max(g for _, g in read), 2))
+                    lo, ln = lc._span(chunk)
+                    y = torch.randn(B, lo + ln + 64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5)) * 0.1
+                    emit = torch.ones(B, dtype=torch.bool, device="cuda")
+                    state = lc.loud_state.clone()
+                    rec["loudness_call_us"] = round(time_calls(lambda: MS.loudness_rows_(y, lc.span_lo, lc.span_len, emit, lc.loud_on,
+                                                                                        lc.loud_hop, lc.loud_coef, lc.loud_par, state)), 2)
+                    rec["loudness_span"] = ln
+                    del both, lc
                 if args.pitch_track:
                     three = {}
                     for name, kw, sess in (("track_off", {}, {}), ("track_none", dict(pitch_track=True), {}),
