@@ -251,26 +251,34 @@ def pitch_transform_(f0, mode, f0_rate=1.0, pitch_shift=0.0, intonation=1.0):
     return f0
 
 
-def filter_block_small(x, sd, prefix, film, film_off, skip=None):
+def _out_like(x, out):
+    """the output of a FilterBlock call: a new tensor, or the caller's (a test's, pre-filled)"""
+    if out is None:
+        return torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == torch.float32 and out.device == x.device and out.is_contiguous()
+    return out
+
+
+def filter_block_small(x, sd, prefix, film, film_off, skip=None, out=None):
     """fused FilterBlock for C in (8, 16): x[N,C,L], reference-layout weights sd[prefix + ...], film[N,rows,Lf]."""
     from ._pack import pack_filter_small
     x, film, skip = _f(x), _f(film), _f(skip)
     n, c, l = x.shape
     w = pack_filter_small(sd, prefix).to(x.device)
     assert w.numel() == nat.lib().alive_filter_block_small_weights(c)
-    out = torch.empty_like(x)
+    out = _out_like(x, out)
     nat.check(nat.lib().alive_filter_block_small(nat.ptr(x), n, c, l, nat.ptr(w), nat.ptr(film), film.shape[1], film.shape[2],
                                                  film_off, nat.ptr(skip), nat.ptr(out), nat.stream()), "alive_filter_block_small")
     return out
 
 
-def filter_block_small_range(x, sd, prefix, film, film_off, skip=None, t0=0, f0=0, frames=None):
+def filter_block_small_range(x, sd, prefix, film, film_off, skip=None, t0=0, f0=0, frames=None, out=None):
     """filter_block_small on a frame range: x holds the samples from t0 on, film the frames from f0 on of a window of `frames` frames"""
     from ._pack import pack_filter_small
     x, film, skip = _f(x), _f(film), _f(skip)
     n, c, l = x.shape
     w = pack_filter_small(sd, prefix).to(x.device)
-    out = torch.empty_like(x)
+    out = _out_like(x, out)
     nat.check(nat.lib().alive_filter_block_small_range(nat.ptr(x), n, c, l, nat.ptr(w), nat.ptr(film), film.shape[1],
                                                        film.shape[2] if frames is None else frames, film_off, t0, f0, film.shape[2],
                                                        nat.ptr(skip), nat.ptr(out), nat.stream()), "alive_filter_block_small_range")
@@ -312,23 +320,21 @@ def filter_block_small_wave(x, sd, prefix, film, film_off, o_w, o_b, t0=0, f0=0,
     return out
 
 
-def filter_block64(x, sd, prefix, film, film_off, skip=None, plain=False):
+def filter_block64(x, sd, prefix, film, film_off, skip=None, plain=False, t0=0, f0=0, frames=None, out=None):
     """fused FilterBlock for C = 64 (split-bf16 MFMA): x[N,64,L], reference-layout weights sd[prefix + ...].
-    plain: the six k5 convs on one fp16 plane per operand (alive_filter_block64_range_fp16; decoder precision mode 1)."""
+    plain: the six k5 convs on one fp16 plane per operand (alive_filter_block64_range_fp16; decoder precision mode 1).
+    t0 / f0 / frames: x holds the samples from t0 on, film the frames from f0 on of a window of `frames` frames (alive_filter_block64_range)."""
     from ._pack import pack_filter_mid
     x, film, skip = _f(x), _f(film), _f(skip)
     n, c, l = x.shape
     w, b = pack_filter_mid(sd, prefix)
     w, b = w.to(x.device), b.to(x.device)
     assert w.numel() == nat.lib().alive_filter_block64_weights()
-    out = torch.empty_like(x)
-    if plain:
-        nat.check(nat.lib().alive_filter_block64_range_fp16(nat.ptr(x), n, l, nat.ptr(w), nat.ptr(b), nat.ptr(film), film.shape[1], film.shape[2],
-                                                            film_off, 0, 0, film.shape[2], nat.ptr(skip), nat.ptr(out), nat.stream()),
-                  "alive_filter_block64_range_fp16")
-        return out
-    nat.check(nat.lib().alive_filter_block64(nat.ptr(x), n, l, nat.ptr(w), nat.ptr(b), nat.ptr(film), film.shape[1], film.shape[2],
-                                             film_off, nat.ptr(skip), nat.ptr(out), nat.stream()), "alive_filter_block64")
+    out = _out_like(x, out)
+    entry = "alive_filter_block64_range_fp16" if plain else "alive_filter_block64_range"
+    nat.check(getattr(nat.lib(), entry)(nat.ptr(x), n, l, nat.ptr(w), nat.ptr(b), nat.ptr(film), film.shape[1],
+                                        film.shape[2] if frames is None else frames, film_off, t0, f0, film.shape[2], nat.ptr(skip),
+                                        nat.ptr(out), nat.stream()), entry)
     return out
 
 

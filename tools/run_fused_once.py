@@ -1,6 +1,6 @@
-"""one seeded launch of a fused FilterBlock, digest of the output: python tools/run_fused_once.py C L N
+"""one seeded launch of a fused FilterBlock, sha256 of the output's bytes: python tools/run_fused_once.py C L N
 (the tile form is chosen by ALIVE_FB64_NT / ALIVE_FBS_PLANE: equal digests across forms = equal bits)"""
-import sys, os, torch
+import hashlib, sys, os, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "alive-vc_amd"))
 from module import ops
 c, l, n = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
@@ -17,4 +17,4 @@ fused = ops.filter_block64 if c == 64 else ops.filter_block_small
 out = fused(x, {k: v.cuda() for k, v in sd.items()}, "n", film, 5, skip=skip)
 torch.cuda.synchronize()
 assert torch.isfinite(out).all()
-print("digest %08x" % (int(out.view(torch.int32).to(torch.int64).sum().item()) & 0xffffffff))
+print("digest " + hashlib.sha256(out.cpu().contiguous().numpy().tobytes()).hexdigest())       # (of the bytes in order: a sum would not see a permutation)
