@@ -102,8 +102,9 @@ __device__ __forceinline__ unsigned split_step(float& a, float& b, bool count = 
 // ---- epilogue, straight from the accumulators (shared by the one-tile and the persistent kernel) ----
 // stage: wave-private LDS (NP x 8 KB: [plane][64 columns][64 channels] bf16) for the plane-packed output, or nullptr.  With it
 // the planes leave as 16-byte pieces, 64 lanes covering 16 columns x the 64 B of a k-block (the tile is written to LDS in the
-// accumulator layout -- 8 B per lane, 16-B chunk index XOR-ed with column & 7 -- and read back transposed); without it a lane
-// stores its 8-byte pieces directly, one per column and store instruction: 64 separate 64-B lines touched per instruction.
+// accumulator layout -- 8 B per lane, 16-B chunk index XOR-ed with column & 7 -- and read back transposed).  stage_small: the
+// persistent kernel's 2-KB form of the same.  Every launch with Pout passes one of the two (a third path, 8-byte stores straight
+// from the lanes, could not be reached by any dispatch and is gone).
 // By ablation (tools/experiments/README.md) the epilogue was 41 % of a 512 -> 1536 + GELU -> planes layer.
 template <int NP, int ACT, bool F16S = false>
 __device__ __forceinline__ void gemm_epilogue(const AliveGemm& p, f32x16 (&acc)[2][2], int m0, int64_t c0, int wr, int wc, int lr,
@@ -311,23 +312,6 @@ __device__ __forceinline__ void gemm_epilogue(const AliveGemm& p, f32x16 (&acc)[
                         const int row0 = m0 + wr * 64 + ti * 32 + chunk * 8;
                         // (64 lanes: 16 columns x the 64 B of one k-block -- one contiguous 1-KB run of the k-blocked planes)
                         if (col < cols && row0 < co_pad32) *(u32x4*)(Po + planes_at(pl, col, row0, cols_pad, co_pad32)) = v;
-                    }
-                }
-            } else if (p.Pout != nullptr && cok[tj]) {
-                // plane-packed output for the next GEMM: 4 consecutive channels of one column -> 8 B per plane
-                unsigned short* Po = (unsigned short*)p.Pout;
-                const int64_t col = c0 + wc * 64 + tj * 32 + lr;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int row = rbase + 8 * g;
-                    if (row >= co_pad32) continue;
-                    float q[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) q[e] = (full_rows || row + e < p.Co) ? vv[4 * g + e] * pscale : 0.0f;
-#pragma unroll
-                    for (int pl = 0; pl < NP; ++pl) {
-                        const unsigned h01 = split_step<NP, F16S>(q[0], q[1]), h23 = split_step<NP, F16S>(q[2], q[3]);
-                        *(uint2*)(Po + planes_at(pl, col, row, cols_pad, co_pad32)) = make_uint2(h01, h23);
                     }
                 }
             }

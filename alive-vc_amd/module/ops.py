@@ -150,11 +150,15 @@ def gemm_planes(P, n, t, weight, bias=None, planes=2, act=None, post_add=None, c
 
 
 def gemm_planes_raw(P, n, t, ci, co, W, bias=None, planes=2, act=None, post_add=None, ch_scale=None, residual=None,
-                    Y=None, Pout=None, Y2=None, y_split=0, b_plane=0, b_win=0, b_row=0, b_cblk=0, b_blk=0):
+                    Y=None, Pout=None, Y2=None, y_split=0, b_plane=0, b_win=0, b_row=0, b_cblk=0, b_blk=0,
+                    f16s=False, wscale=None, in_unscale=0.0, pout_scale=0.0, arg_val=None, arg_idx=None):
     """alive_gemm_planes on caller-owned memory (tests): P is a raw operand buffer read through the placement fields (AliveGemm.b_plane /
     b_win / b_row / b_cblk / b_blk; all 0: the standard k-blocked image of to_planes), W an already packed weight (pack_conv_split, or
     slab 2 of pack_conv_split_h for planes = 1), Y / Y2 / Pout the tensors to write into.  act: a name of ACT, or the integer of
-    AliveGemm.act (4: magnitudes of row pairs into Pout)."""
+    AliveGemm.act (3: argmax candidates into arg_val [blocks of 64 rows][n t] fp32 / arg_idx int32; 4: magnitudes of row pairs into Pout).
+    f16s: W and P are fp16 (hi, lo) pairs of a power-of-two multiple of the values (slabs 3 - 4 of pack_conv_split_f16s and its scalar as
+    wscale; in_unscale = 1 / the multiple of P, pout_scale = the multiple of Pout).  A contiguous fp32 `residual` is passed as it is,
+    so Y may be the same tensor."""
     b, post_add, ch_scale, residual = map(_f, (bias, post_add, ch_scale, residual))
     d = nat.AliveGemm()
     d.W, d.bias, d.P = nat.ptr(W), nat.ptr(b), nat.ptr(P)
@@ -162,7 +166,17 @@ def gemm_planes_raw(P, n, t, ci, co, W, bias=None, planes=2, act=None, post_add=
     d.post_add, d.ch_scale, d.residual = map(nat.ptr, (post_add, ch_scale, residual))
     d.Y, d.Pout, d.Y2, d.y_split = nat.ptr(Y), nat.ptr(Pout), nat.ptr(Y2), y_split
     d.b_plane, d.b_win, d.b_row, d.b_cblk, d.b_blk = b_plane, b_win, b_row, b_cblk, b_blk
+    d.f16s, d.wscale, d.in_unscale, d.pout_scale = int(bool(f16s)), nat.ptr(wscale), in_unscale, pout_scale
+    d.arg_val, d.arg_idx = nat.ptr(arg_val), nat.ptr(arg_idx)
     nat.check(nat.lib().alive_gemm_planes(C.byref(d), nat.stream()), "alive_gemm_planes")
+
+
+def argmax_merge(arg_val, arg_idx, n, t):
+    """alive_argmax_merge over the candidates [blocks][n t] of an act = 3 GEMM: float indices [n, 1, t]"""
+    out = torch.empty(n, 1, t, device=arg_val.device)
+    nat.check(nat.lib().alive_argmax_merge(nat.ptr(arg_val), nat.ptr(arg_idx), arg_val.shape[0], n * t, nat.ptr(out), nat.stream()),
+              "alive_argmax_merge")
+    return out
 
 
 def gemm_planes_argmax(P, n, t, weight, bias=None, planes=3):
