@@ -418,7 +418,7 @@ __global__ __launch_bounds__(256) void argmax_small_kernel(const float* __restri
     int besti = 0x7fffffff;
     for (int c = tid; c < C; c += 256) {
         float v = Xn[(size_t)c * T];
-        if (v > best || (v != v && best == best)) { best = v; besti = c; }
+        if (argmax_takes(v, c, best, besti)) { best = v; besti = c; }
     }
     bv[tid] = best;
     bi[tid] = besti;
@@ -427,8 +427,7 @@ __global__ __launch_bounds__(256) void argmax_small_kernel(const float* __restri
         if (tid < o) {
             float v = bv[tid + o];
             int vi = bi[tid + o];
-            bool take = (v > bv[tid]) || (v == bv[tid] && vi < bi[tid]) || (v != v && bv[tid] == bv[tid]);
-            if (take) { bv[tid] = v; bi[tid] = vi; }
+            if (argmax_takes(v, vi, bv[tid], bi[tid])) { bv[tid] = v; bi[tid] = vi; }
         }
         __syncthreads();
     }
@@ -448,7 +447,7 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ X
     if (ok) {
         for (int c = wv; c < C; c += 4) {
             float v = Xn[(size_t)c * T + t];
-            if (v > best || (v != v && best == best)) { best = v; besti = c; }   // first max; NaN wins like ATen
+            if (argmax_takes(v, c, best, besti)) { best = v; besti = c; }        // first max; NaN wins like ATen (common.h)
         }
     }
     bv[wv][lane] = best;
@@ -460,8 +459,7 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ X
         for (int w = 1; w < 4; ++w) {
             float v = bv[w][lane];
             int vi = bi[w][lane];
-            bool take = (v > b) || (v == b && vi < i) || (v != v && b == b);
-            if (take) { b = v; i = vi; }
+            if (argmax_takes(v, vi, b, i)) { b = v; i = vi; }
         }
         out[(size_t)n * T + t] = (float)i;
     }

@@ -121,6 +121,16 @@ __device__ __forceinline__ f32x16 mfma_f16(bf16x8 a, bf16x8 b, f32x16 c) {      
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
+// The order of argmax candidates, one rule for every site that keeps or merges them (blocks.hip: the per-thread loops and the merges of
+// both argmax kernels; gemm_planes.hip: the act = 3 epilogue and alive_argmax_merge).  (v, vi) replaces (b, i) when v is the larger
+// value; when v is a NaN and b is not (a NaN is the maximum, like ATen); and, among equal values and among NaNs, when vi is the lower
+// index.  The empty candidate is (-inf, 0x7fffffff): it loses to every real one, so a column of -inf gives its first channel, 0.
+// The answer does not depend on which thread, lane, wave or block a channel belongs to, nor on the order of the merges.
+__device__ __forceinline__ bool argmax_takes(float v, int vi, float b, int i) {
+    const bool vn = v != v, bn = b != b;
+    return vn ? (!bn || vi < i) : (!bn && (v > b || (v == b && vi < i)));
+}
+
 // exact-erf GELU in the association order of ATen's CPU kernel: (0.5*x) * (1 + erf(x/sqrt2))
 __device__ __forceinline__ float gelu_erf(float x) {
     return (0.5f * x) * (1.0f + erff(x * 0.70710678118654752440f));

@@ -121,7 +121,7 @@ __device__ __forceinline__ void gemm_epilogue(const AliveGemm& p, f32x16 (&acc)[
         // cross-lane exchange; value = accumulator + bias, bitwise what the Y path would have stored.
         float bv[2] = {-INFINITY, -INFINITY};
         int bi[2] = {0x7fffffff, 0x7fffffff};
-        auto take = [](float v, int vi, float b, int i) { return (v > b) || (v == b && vi < i) || (v != v && b == b); };
+        auto take = [](float v, int vi, float b, int i) { return argmax_takes(v, vi, b, i); };
 #pragma unroll
         for (int ti = 0; ti < 2; ++ti) {
             const int rbase = m0 + wr * 64 + ti * 32 + 4 * lh;
@@ -863,7 +863,7 @@ __global__ __launch_bounds__(256) void argmax_merge_kernel(const float* __restri
     for (int k = 1; k < nblk; ++k) {
         const float v = val[(size_t)k * cols + col];
         const int vi = idx[(size_t)k * cols + col];
-        if ((v > b) || (v == b && vi < i) || (v != v && b == b)) { b = v; i = vi; }
+        if (argmax_takes(v, vi, b, i)) { b = v; i = vi; }
     }
     out[col] = (float)i;
 }

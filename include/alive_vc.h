@@ -470,9 +470,9 @@ typedef struct AliveGemm {
     int b_cblk;
     int64_t b_blk;
     /* act == 3: the [Co][cols] product is never stored.  Each 64-row block of the GEMM leaves, per column, its largest
-     * value (bias included) and the row it sits in -- arg_val / arg_idx [ceil(Co/64)][N*T], first row on ties, NaN wins
-     * like ATen -- and alive_argmax_merge reduces the blocks: F0Estimator.estimate (f0_estimator.py:30-34) without the
-     * 4096-class logits tensor. */
+     * value (bias included) and the row it sits in -- arg_val / arg_idx [ceil(Co/64)][N*T], the rule of
+     * alive_argmax_channels below -- and alive_argmax_merge reduces the blocks: F0Estimator.estimate
+     * (f0_estimator.py:30-34) without the 4096-class logits tensor. */
     float* arg_val;
     int32_t* arg_idx;
     /* Round 5 (the front end without an fp32 spectrogram).  Fields appended: a zeroed struct of the old size means "off".
@@ -623,7 +623,8 @@ int alive_gelu_film(const float* H, int N, int C, int L, const float* film, int 
 /* ChannelNorm alone (f0_estimator.py:25) */
 int alive_channel_norm(const float* X, int N, int C, int T, const float* gain, const float* offset,
                        float eps, float* Y, void* stream);
-/* argmax over channels -> float (f0_estimator.py:33) */
+/* argmax over channels -> float (f0_estimator.py:33), torch.argmax's answer on every column: a NaN is the maximum; among equal values,
+ * and among NaNs, the lowest channel wins; a column of -inf gives 0.  The act == 3 GEMM with alive_argmax_merge follows the same rule. */
 int alive_argmax_channels(const float* X, int N, int C, int T, float* out, void* stream);
 
 /* HarmonicOscillator.forward after to_amps/exp (decoder.py:79-100).
