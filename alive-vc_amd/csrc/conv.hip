@@ -255,10 +255,10 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(AliveConv p, unsigned kw
 
 }  // namespace
 
-int alive_conv_split_launch(const AliveConv* d, float ratio, hipStream_t s);
+int alive_conv_split_launch(const AliveConv* d, float ratio, hipStream_t s, bool allow_up);
 bool alive_conv_skinny_try(const AliveConv* d, hipStream_t s, int* rc);
 
-extern "C" int alive_conv1d(const AliveConv* d, void* stream) {
+static int conv1d_impl(const AliveConv* d, void* stream, bool allow_up) {
     ALIVE_CHECK_ARG(d && d->W && (d->X || d->Xp), "alive_conv1d: null W/X");
     ALIVE_CHECK_ARG(d->N > 0 && d->Ci > 0 && d->Co > 0 && d->Tin > 0 && d->Tout > 0, "alive_conv1d: bad sizes");
     ALIVE_CHECK_ARG(d->KW >= 1 && (d->KW <= 16 || d->Ci == 1) && d->stride >= 1 && d->dil >= 1 && d->up >= 1, "alive_conv1d: bad geometry");
@@ -288,7 +288,8 @@ extern "C" int alive_conv1d(const AliveConv* d, void* stream) {
         if (d->film_ld == 0 && !d->Xp && !d->Zp && alive_conv_skinny_try(d, (hipStream_t)stream, &rc)) return rc;      // few columns (streaming)
     }
     if (d->precision >= 1)
-        return alive_conv_split_launch(d, (d->Z || d->Zp) ? (float)(d->film_ld ? d->film_ld : d->Lf) / (float)d->Tout : 0.0f, (hipStream_t)stream);
+        return alive_conv_split_launch(d, (d->Z || d->Zp) ? (float)(d->film_ld ? d->film_ld : d->Lf) / (float)d->Tout : 0.0f, (hipStream_t)stream,
+                                       allow_up);
     ALIVE_CHECK_ARG(d->film_ld == 0, "alive_conv1d: a film frame range needs the split kernel (precision 1 / 2)");
     // (channel, tap) of a reduction index: k / KW = (k * ceil(2^s / KW)) >> s on 32-bit registers.  The product must not wrap
     // (k < 32768: magic <= 2^17) and s must be large enough for every k (k * (magic * KW - 2^s) < 2^s): s = 18 for KW 2 .. 3, 19 for
@@ -317,5 +318,9 @@ extern "C" int alive_conv1d(const AliveConv* d, void* stream) {
     ALIVE_CHECK_LAUNCH("alive_conv1d");
     return ALIVE_OK;
 }
+
+extern "C" int alive_conv1d(const AliveConv* d, void* stream) { return conv1d_impl(d, stream, true); }
+// test only: the same dispatch without the stationary-input form of conv_up.hip (the tiled kernel it is compared with bit for bit)
+extern "C" int alive_conv1d_tiled(const AliveConv* d, void* stream) { return conv1d_impl(d, stream, false); }
 
 ALIVE_F16_SAT_GETTER(alive_f16_sat_conv)

@@ -475,7 +475,10 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(AliveConv p, float f
 
 }  // namespace
 
-int alive_conv_split_launch(const AliveConv* d, float ratio, hipStream_t s) {
+bool alive_conv_up_try(const AliveConv* d, hipStream_t s, int* rc);      // conv_up.hip
+
+// allow_up = false (alive_conv1d_tiled, test only): never the stationary-input form of conv_up.hip
+int alive_conv_split_launch(const AliveConv* d, float ratio, hipStream_t s, bool allow_up) {
     ALIVE_CHECK_ARG(d->stride == 1, "alive_conv1d(split): stride must be 1");
     ALIVE_CHECK_ARG(d->Ci_pad % BKC == 0 && d->Ci_pad >= d->Ci, "alive_conv1d(split): Ci_pad %d for Ci %d", d->Ci_pad, d->Ci);
     ALIVE_CHECK_ARG(d->KW <= 8 && (d->KW - 1) * d->dil <= XROWS - BN, "alive_conv1d(split): halo (KW-1)*dil = %d exceeds %d",
@@ -503,6 +506,12 @@ int alive_conv_split_launch(const AliveConv* d, float ratio, hipStream_t s) {
                         "output column that reads past the signal (the kernel clamps rows >= Tin instead of zero-filling them)");
     }
     ALIVE_CHECK_ARG(d->Tout <= d->Tin + d->pad_left, "alive_conv1d(split): Tout");
+    // the transposed convs of the decoder's coarse scales (KW == 1, up > 1, Ci <= 256, only a bias, a grid of at least 512 blocks of
+    // 64 columns): the input tile staged once per block instead of once per 128 rows (conv_up.hip); same bits
+    {
+        int rc;
+        if (allow_up && alive_conv_up_try(d, s, &rc)) return rc;
+    }
     // measured (128 windows x 4500 columns): a 256-row tile is 12 - 37 % SLOWER than two 128-row blocks
     // (k5 + FiLM + residual 2.11 against 1.72 ms, 1x1 1.15 against 0.84): at one block per CU nothing covers the LDS / L2
     // latencies of the single wave per SIMD, and no other block's main loop runs under the four epilogue passes.

@@ -138,7 +138,9 @@ AliveConv split(AliveConv d) {
 // decoder_bf16_mask(): the groups mode 1 covers, (a) = 1, (b) = 2, (c) = 4, (e) = 16.
 // Sensitivities (oracle with the operands of one group rounded to fp16 | to bf16; 450-frame fixture, waveform RMS 0.66): (a) 1.24e-5 |
 // 1.11e-4, (b) 3.4e-6 | 2.7e-5, (c) 1.3e-6 + 1.2e-6 + 2.0e-7 | 2.2e-5 + 8.3e-6 + 1.3e-6; not adopted: FiLM projections 1.4e-4 | 1.6e-3,
-// input layer 1.2e-4 | 1.5e-3, up convs 1.0e-5 | 8.1e-5 (store bound: nothing to gain); (e) 2.6e-5 | 2.2e-4 -- adopted last, for
+// input layer 1.2e-4 | 1.5e-3, up convs 1.0e-5 | 8.1e-5 (nothing to gain from fewer MFMAs: on the tiled kernel the two coarse ones ran at
+// 1.0 / 1.9 TB/s of their input + output bytes, held back by the input tile staged once per 128 rows and a barrier every 24 MFMAs, not by the
+// stores; staged once per block they run at 1.9 / 2.9 TB/s and ARE store bound -- conv_up.hip); (e) 2.6e-5 | 2.2e-4 -- adopted last, for
 // 3.7 ms per step (the block is vector-issue bound, but a k-step with one MFMA instead of three is 30 % shorter).
 int g_decoder_precision = 0;      // 0: not decided yet (environment, else 1)
 int decoder_precision() {

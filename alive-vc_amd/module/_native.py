@@ -98,6 +98,9 @@ PROTOTYPES = {
     "alive_dedup_pass": (_I, [_VP, _VP, _I64, _I, _D, _VP, _VP, _VP]),
     "alive_knn_merge_gather": (_I, [_VP, _VP, _I, _I, _D, _VP, _VP, _I, _I, _VP, _VP, _VP]),
     "alive_conv1d": (_I, [C.POINTER(AliveConv), _VP]),
+    "alive_conv1d_tiled": (_I, [C.POINTER(AliveConv), _VP]),   # test only
+    "alive_conv_up_launches": (_I, [_I]),                      # test only
+    "alive_conv_up_min_blocks": (_I, [_I]),                    # test only
     "alive_decoder_precision": (_I, [_I]),
     "alive_encoder_precision": (_I, [_I]),
     "alive_f16_saturations": (_I, [_I]),

@@ -429,6 +429,15 @@ typedef struct AliveConv {
     int yp_planes;         /* 0 / 2: two bf16 planes (the bits of alive_to_planes(Y, 2)); 1: ONE fp16 plane (alive_to_planes(Y, 1)) */
 } AliveConv;
 int alive_conv1d(const AliveConv* desc, void* stream);
+/* TEST ONLY.  A transposed conv on split bf16 (precision 1, KW 1, stride 1, up > 1, no padding) with Ci a multiple of 32 up to 256
+ * and only a bias takes a kernel that stages the input tile once per (window, 64 columns) and walks all rows under it
+ * (csrc/conv_up.hip) when N * ceil(Tout / 64) >= 512; its output is bitwise that of the tiled kernel.  alive_conv1d_tiled is
+ * alive_conv1d without that form; alive_conv_up_launches returns how many launches took it so far (reset != 0: and clears the count);
+ * alive_conv_up_min_blocks(b) sets that threshold of 512 blocks for the process (b > 0: to b, so that a test reaches the kernel with
+ * a small shape; b < 0: back to 512; b == 0: query) and returns the value in force.  The product never calls it. */
+int alive_conv1d_tiled(const AliveConv* desc, void* stream);
+int alive_conv_up_launches(int reset);
+int alive_conv_up_min_blocks(int blocks);
 
 /* ---- plane-packed activations: the frame-rate GEMMs of the ConvNeXt stacks --------------------------
  * The 1x1 convs of ContentEncoder / F0Estimator / FeatureExtractor (content_encoder.py:22-25,
