@@ -117,6 +117,15 @@ __device__ __forceinline__ unsigned pack_f16x2(float a, float b, bool count = tr
     const f16x2_t h = {(_Float16)a, (_Float16)b};
     return __builtin_bit_cast(unsigned, h);
 }
+// ---- split-bf16 operands: v ~= hi + lo with hi = bf16(v), lo = bf16(v - hi), two values per 32-bit word (the first in the low half) ----
+__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+    bf16x2_t h = {(__bf16)a, (__bf16)b};
+    return __builtin_bit_cast(unsigned, h);
+}
+__device__ __forceinline__ unsigned pack_bf16x2_lo(float a, float b, unsigned hi) {       // the lo pair of (a, b), given hi = pack_bf16x2(a, b)
+    return pack_bf16x2(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
+}
 __device__ __forceinline__ f32x16 mfma_f16(bf16x8 a, bf16x8 b, f32x16 c) {      // the operand registers hold fp16 bits
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }

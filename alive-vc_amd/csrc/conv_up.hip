@@ -39,7 +39,6 @@ constexpr int UPLANE = (UCI_MAX / UKC) * UCB;    // bytes per plane
 constexpr int UP_MIN_BLOCKS = 512;
 std::atomic<int> g_up_min_blocks{UP_MIN_BLOCKS};      // (alive_conv_up_min_blocks: the tests reach the kernel with small shapes)
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 std::atomic<int> g_up_launches{0};
@@ -101,12 +100,8 @@ __global__ __launch_bounds__(256, 2) void conv_up_kernel(AliveConv p, unsigned i
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float x0 = ok ? x[u][2 * e] : 0.0f, x1 = ok ? x[u][2 * e + 1] : 0.0f;
-                        bf16x2_t hp = {(__bf16)x0, (__bf16)x1};
-                        const unsigned h = __builtin_bit_cast(unsigned, hp);
-                        const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-                        bf16x2_t lp = {(__bf16)r0, (__bf16)r1};
-                        hv[e] = h;
-                        lv[e] = __builtin_bit_cast(unsigned, lp);
+                        hv[e] = pack_bf16x2(x0, x1);
+                        lv[e] = pack_bf16x2_lo(x0, x1, hv[e]);
                     }
                     *(u32x4*)(dst + (cb0 + u) * UCB) = hv;
                     *(u32x4*)(dst + (cb0 + u) * UCB + UPLANE) = lv;

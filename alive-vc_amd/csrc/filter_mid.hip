@@ -46,7 +46,6 @@
 // comes back wrong -- deterministically for some tiles, run to run for others.  hipcc 7.2 inserts the documented wait states for
 // the first read only.  Eight more wait states between the chains (s_nop below), or reading the accumulator at once, make every
 // launch exact (tools/stress_filter_block.py: 0 of 100 differ; -DALIVE_FB64_NO_CHAIN_GAP reproduces the failure).
-#include "conv_epilogue.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -56,6 +55,7 @@
 #ifndef ALIVE_FILTER_MID_NO_SLP
 #error "filter_mid.hip must be compiled with -fno-slp-vectorize -DALIVE_FILTER_MID_NO_SLP (see csrc/Makefile)"
 #endif
+#include "filter_pipeline.h"           // the pieces shared with filter_small.hip
 
 static long long* g_stamps64 = nullptr;
 
@@ -80,11 +80,6 @@ constexpr int TSTEP = 2 * TROW;         // a wave's consecutive tiles are two co
 constexpr int GUARD = 16 * ROWB;        // 2 KB in front of the plane buffers
 constexpr int LDS_BYTES = GUARD + 2 * BUF + NCONV * C * NFS * 8 + BL * 8;     // 162816 B
 
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    bf16x2_t h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
 __device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
 
 // NTT = column tiles of 32 per wave: 4 on the batch path (256-column tiles, 200 outputs), 2 for a signal of a few such tiles (the
@@ -189,23 +184,15 @@ __global__ __launch_bounds__(256, 1) void filter_block64_kernel(const float* __r
             fc = fc < 0 ? 0 : (fc < film_ld ? fc : film_ld - 1);
             fv[k] = film[((size_t)n * film_rows + film_off + q * 2 * C + sel * C + c) * film_ld + fc];
         }
-        if (part == 0) {   // F.interpolate coordinates of this thread's column, relative to the staged FiLM frames (i1 = i0 + 1: the table
-            // repeats the window's last frame, which is what the clamp of upsample_linear1d reads there)
-            const int tc = t < 0 ? 0 : (t < L ? t : L - 1);
-            const Lerp lp = lerp_coord(tc + t_off, ratio, Lf);
-            int i0 = lp.i0 - f_lo;
-            i0 = i0 < NFP - 1 ? i0 : NFP - 1;
-            Xc[col] = make_uint2((unsigned)(i0 * 8), __float_as_uint(lp.w1));
-        }
+        if (part == 0) Xc[col] = film_column_coord<NFP>(t, L, t_off, ratio, Lf, f_lo);
 #pragma unroll
         for (int ck = 0; ck < CPT / 8; ++ck) {
             u32x4 hi, lo;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float x0 = ok ? v[ck * 8 + 2 * e] : 0.0f, x1 = ok ? v[ck * 8 + 2 * e + 1] : 0.0f;
-                const unsigned h = pack2(x0, x1);
-                hi[e] = h;
-                lo[e] = pack2(x0 - __uint_as_float(h << 16), x1 - __uint_as_float(h & 0xffff0000u));
+                hi[e] = pack_bf16x2(x0, x1);
+                lo[e] = pack_bf16x2_lo(x0, x1, hi[e]);
             }
             unsigned char* dst = bufZ + col * ROWB + (((part * (CPT / 8) + ck) ^ swz(col)) << 4);
             *(u32x4*)dst = hi;
@@ -239,97 +226,24 @@ __global__ __launch_bounds__(256, 1) void filter_block64_kernel(const float* __r
     const uint2* xcw = Xc + colw;
     const unsigned char* fsw = (const unsigned char*)(Fs + (32 * rg + 4 * lh) * NFS);
 
-    // FiLM operands of one channel group (4 channels) of a column: (scale, shift) at frames i0 and i0 + 1
-    struct FilmG {
-        f32x2 a0[4], a1[4];
-    };
-    // The epilogue of one column tile (an "item"): v = chain result (+ residual, c2) -> GELU -> FiLM of the next conv's input ->
-    // re-split -> LDS planes, per channel group g in five stages of four independent chains each
-    struct Epi {
-        int off;
-        float w0, w1;
-        FilmG F[2];
-        float z[4], jt[4], je[4], jsc[4], jsh[4], jx[4];
-    };
-    auto film_fetch = [&](int qf, int off, int g, FilmG& F) {
-        const unsigned char* f = fsw + qf * (C * NFS * 8) + off;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const f32x2* fp = (const f32x2*)(f + ((8 * g + e) * NFS) * 8);
-            F.a0[e] = fp[0];
-            F.a1[e] = fp[1];
-        }
-    };
-    auto epi_begin = [&](Epi& E, int qf, int t) {
-        const uint2 xc = xcw[64 * t];
-        E.off = (int)xc.x;
-        E.w1 = __uint_as_float(xc.y);
-        E.w0 = 1.0f - E.w1;
-        film_fetch(qf, E.off, 0, E.F[0]);
-    };
-    // second: the item is a c2 result (v = chain + residual stream, which it replaces); emit: a next conv exists (FiLM rows qf)
-    // and takes the modulated planes at dstp
+    // the epilogue of a column tile in stages (filter_pipeline.h); here: this wave's FiLM rows, Xc column, residual row and planes
+    auto epi_begin = [&](Epi& E, int qf, int t) { ::epi_begin<C, NFS>(E, fsw, qf, xcw[64 * t]); };
     auto epi_stage = [&](Epi& E, bool second, bool emit, int qf, unsigned char* dstp, int t, const f32x16& accv, int g, int st) {
-        const FilmG& Fg = E.F[g & 1];
         if (st == 0) {
-            if (emit && g + 1 < 4) film_fetch(qf, E.off, g + 1, E.F[(g + 1) & 1]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float x = accv[4 * g + e];                 // one v_accvgpr_read per element (8 cycles beside an MFMA): kept for stage 3
-                if (second) {
-                    x = x + h[t][4 * g + e];
-                    h[t][4 * g + e] = x;
-                }
-                E.jx[e] = x;
-                E.jt[e] = __builtin_amdgcn_rcpf(fmaf(fabsf(x), 0.3275911f * 0.70710678118654752440f, 1.0f));
-                const float xs = x * 0.84932180028801904272f;         // exp(-x^2 / 2) = exp2(-(x sqrt(log2(e) / 2))^2)
-                E.je[e] = __builtin_amdgcn_exp2f(-(xs * xs));
-            }
-            // (the empty asm pins a stage's results to its own scheduling region: pure arithmetic otherwise sinks to its consumer's)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(E.jt[e]), "+v"(E.je[e]), "+v"(E.jx[e]));
+            epi_stage0<C, NFS, 4>(E, fsw, second, emit, qf, h[t], accv, g);
         } else if (!emit) {
-        } else if (st == 1) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                E.jsc[e] = fmaf(E.w0, Fg.a0[e][0], E.w1 * Fg.a1[e][0]);        // fma(w0, a, round(w1 * b)): ATen's linear interp
-                E.jsh[e] = fmaf(E.w0, Fg.a0[e][1], E.w1 * Fg.a1[e][1]);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(E.jsc[e]), "+v"(E.jsh[e]));
-        } else if (st == 2) {          // erf by Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7), like gelu_fast
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float p = fmaf(1.061405429f, E.jt[e], -1.453152027f);
-                p = fmaf(p, E.jt[e], 1.421413741f);
-                p = fmaf(p, E.jt[e], -0.284496736f);
-                p = fmaf(p, E.jt[e], 0.254829592f);
-                E.jt[e] = p * E.jt[e];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(E.jt[e]));
-        } else if (st == 3) {          // x (1 + sign(x) erf|x / sqrt 2|) = x + |x| erf_abs = 2 gelu(x); jsc is half the FiLM scale
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float erf_abs = fmaf(-E.jt[e], E.je[e], 1.0f);
-                E.z[e] = fmaf(fmaf(fabsf(E.jx[e]), erf_abs, E.jx[e]), E.jsc[e], E.jsh[e]);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(E.z[e]));
+        } else if (st < 4) {
+            epi_stage13(E, g, st);
         } else {
-            const float* z = E.z;
             unsigned char* p = dstp + st_off[g] + t * TSTEP;
             if constexpr (H16) {
                 // one fp16 plane, saturating; saturations are counted in the tile's OUTPUT columns only: the halo columns are its
                 // neighbour's outputs, and left of their dependency cone they hold arbitrary values
                 const bool cnt = SWEEP ? !warm : colw + 64 * t >= HALO;
+                const float* z = E.z;
                 *(uint2*)p = make_uint2(pack_f16x2(z[0], z[1], cnt), pack_f16x2(z[2], z[3], cnt));
             } else {
-                const unsigned h01 = pack2(z[0], z[1]), h23 = pack2(z[2], z[3]);
-                const unsigned l01 = pack2(z[0] - __uint_as_float(h01 << 16), z[1] - __uint_as_float(h01 & 0xffff0000u));
-                const unsigned l23 = pack2(z[2] - __uint_as_float(h23 << 16), z[3] - __uint_as_float(h23 & 0xffff0000u));
-                *(uint2*)p = make_uint2(h01, h23);
-                *(uint2*)(p + PLANE) = make_uint2(l01, l23);
+                epi_store_split(E, p, PLANE);
             }
         }
     };
@@ -571,12 +485,9 @@ template <bool H16>
 int filter_block64_impl(const float* U, int N, int L, const void* W16, const float* biases, const float* film,
                         int film_rows, int Lf, int film_off, int t0, int f0, int film_ld, const float* skip,
                         float* out, void* stream) {
-    ALIVE_CHECK_ARG(U && W16 && biases && film && out, "alive_filter_block64: null pointer");
-    ALIVE_CHECK_ARG(N > 0 && L > 16 && Lf > 0, "alive_filter_block64: bad sizes (L must exceed the largest reflect pad, 16)");
-    ALIVE_CHECK_ARG(U != out, "alive_filter_block64: in-place not supported (tiles read a halo of their left neighbour)");
-    ALIVE_CHECK_ARG((L & 3) == 0 && ((((uintptr_t)out) | ((uintptr_t)skip)) & 15) == 0,
-                    "alive_filter_block64: L must be a multiple of 4 and out / skip 16-byte aligned");
-    ALIVE_CHECK_ARG(film_ld > 0 && t0 >= 0 && f0 >= 0, "alive_filter_block64: bad frame range");
+    if (int rc = filter_block_check_args("alive_filter_block64", U && W16 && biases && film && out, U, out, N, L, Lf,
+                                         (uintptr_t)out | (uintptr_t)skip, "out / skip", film_ld, t0, f0))
+        return rc;
     ALIVE_CHECK_ARG((double)BL * film_ld / L + 3.0 <= NFP, "alive_filter_block64: tile spans more than %d frames (L %d, frames %d)", NFP, L, film_ld);
     {
         static LdsOptIn optin;

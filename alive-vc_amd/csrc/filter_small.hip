@@ -20,13 +20,13 @@
 //   * C = 16: the two 16-byte halves of a row are swapped by (column >> 3) & 1, which makes the 32-lane fragment reads conflict-free.
 // Parity: the block's outputs move from "bit for bit an fp32 fmaf chain" to the split-bf16 error of the 64- and 256-channel scales
 // (unit tests: 4e-5 relative instead of 5e-6; the decoder fixtures' waveform RMS error is unchanged at 1.1e-4, bar 1e-3).
-#include "conv_epilogue.h"
 #include <type_traits>
 #include <stdlib.h>
 
 #ifndef ALIVE_FILTER_MID_NO_SLP
 #error "filter_small.hip must be compiled with the flags of filter_mid.hip: -fno-slp-vectorize -DALIVE_FILTER_MID_NO_SLP -mllvm -amdgpu-sched-strategy=max-ilp (see csrc/Makefile)"
 #endif
+#include "filter_pipeline.h"           // the pieces shared with filter_mid.hip
 
 static long long* g_stamps_small = nullptr;
 extern "C" void alive_debug_set_stamps_small(long long* p) { g_stamps_small = p; }
@@ -72,12 +72,6 @@ struct Cfg {
     static constexpr int WFLOATS = 7 * 32 + (W_IN + NCONV * W_K5) / 2;       // fp32 biases [7][32], then the bf16 weights
     static constexpr int LDS = GUARD + 2 * BUF + NCONV * C * NFS * 8 + BL * 8;
 };
-
-__device__ __forceinline__ unsigned pack2s(float a, float b) {
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    bf16x2_t h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
 
 // tw / tb: weights and bias of the conv a TAIL applies (TAIL_UP: [16 rows (co, j)][16] and [16]; TAIL_WAVE: [8][7] and [1])
 template <int C, bool FIRST, int PL = PLANE_BATCH, int TAIL = TAIL_NONE>
@@ -147,21 +141,15 @@ __global__ __launch_bounds__(256, PL == 16384 ? 2 : 1) void filter_block_small_k
 #pragma unroll
         for (int j = 0; j < NCOL; ++j) {
             const int col = tid + 256 * j;
-            int tc = tbase + col;
-            tc = tc < 0 ? 0 : (tc < L ? tc : L - 1);
-            const Lerp lp = lerp_coord(tc + t_off, ratio, Lf);
-            int i0 = lp.i0 - f_lo;
-            i0 = i0 < NFP - 1 ? i0 : NFP - 1;
-            Xc[col] = make_uint2((unsigned)(i0 * 8), __float_as_uint(lp.w1));
+            Xc[col] = film_column_coord<NFP>(tbase + col, L, t_off, ratio, Lf, f_lo);
 #pragma unroll
             for (int ck = 0; ck < C / 8; ++ck) {
                 u32x4 hi, lo;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float x0 = v[j][ck * 8 + 2 * e], x1 = v[j][ck * 8 + 2 * e + 1];
-                    const unsigned h = pack2s(x0, x1);
-                    hi[e] = h;
-                    lo[e] = pack2s(x0 - __uint_as_float(h << 16), x1 - __uint_as_float(h & 0xffff0000u));
+                    hi[e] = pack_bf16x2(x0, x1);
+                    lo[e] = pack_bf16x2_lo(x0, x1, hi[e]);
                 }
                 unsigned char* dst = bufZ + col * ROWB + ((ck ^ hsw(col)) << 4);
                 *(u32x4*)dst = hi;
@@ -188,87 +176,13 @@ __global__ __launch_bounds__(256, PL == 16384 ? 2 : 1) void filter_block_small_k
     const uint2* xcw = Xc + colw;
     const unsigned char* fsw = (const unsigned char*)(Fs + 4 * lh * NFS);
 
-    struct FilmG {
-        f32x2 a0[4], a1[4];
-    };
-    struct Epi {
-        int off;
-        float w0, w1;
-        FilmG F[2];
-        float z[4], jt[4], je[4], jsc[4], jsh[4], jx[4];
-    };
-    auto film_fetch = [&](int qf, int off, int g, FilmG& F) {
-        const unsigned char* f = fsw + qf * (C * NFS * 8) + off;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const f32x2* fp = (const f32x2*)(f + ((8 * g + e) * NFS) * 8);
-            F.a0[e] = fp[0];
-            F.a1[e] = fp[1];
-        }
-    };
-    auto epi_begin = [&](Epi& E, int qf, int t) {
-        const uint2 xc = xcw[128 * t];
-        E.off = (int)xc.x;
-        E.w1 = __uint_as_float(xc.y);
-        E.w0 = 1.0f - E.w1;
-        film_fetch(qf, E.off, 0, E.F[0]);
-    };
-    // one stage (st = 0..4) of the epilogue of channel group g of a tile ("item"); see filter_mid.hip for the staging
+    // the epilogue of a column tile in stages (filter_pipeline.h); here: this wave's FiLM rows, Xc column, residual row and planes
+    auto epi_begin = [&](Epi& E, int qf, int t) { ::epi_begin<C, NFS>(E, fsw, qf, xcw[128 * t]); };
     auto epi_stage = [&](Epi& E, bool second, bool emit, int qf, unsigned char* dstp, int t, const f32x16& accv, int g, int st) {
-        const FilmG& Fg = E.F[g & 1];
-        if (st == 0) {
-            if (emit && g + 1 < G) film_fetch(qf, E.off, g + 1, E.F[(g + 1) & 1]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float x = accv[4 * g + e];
-                if (second) {
-                    x = x + h[t][4 * g + e];
-                    h[t][4 * g + e] = x;
-                }
-                E.jx[e] = x;
-                E.jt[e] = __builtin_amdgcn_rcpf(fmaf(fabsf(x), 0.3275911f * 0.70710678118654752440f, 1.0f));
-                const float xs = x * 0.84932180028801904272f;
-                E.je[e] = __builtin_amdgcn_exp2f(-(xs * xs));
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(E.jt[e]), "+v"(E.je[e]), "+v"(E.jx[e]));
-        } else if (!emit) {
-        } else if (st == 1) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                E.jsc[e] = fmaf(E.w0, Fg.a0[e][0], E.w1 * Fg.a1[e][0]);        // fma(w0, a, round(w1 * b)): ATen's linear interp
-                E.jsh[e] = fmaf(E.w0, Fg.a0[e][1], E.w1 * Fg.a1[e][1]);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(E.jsc[e]), "+v"(E.jsh[e]));
-        } else if (st == 2) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float p = fmaf(1.061405429f, E.jt[e], -1.453152027f);
-                p = fmaf(p, E.jt[e], 1.421413741f);
-                p = fmaf(p, E.jt[e], -0.284496736f);
-                p = fmaf(p, E.jt[e], 0.254829592f);
-                E.jt[e] = p * E.jt[e];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(E.jt[e]));
-        } else if (st == 3) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float erf_abs = fmaf(-E.jt[e], E.je[e], 1.0f);
-                E.z[e] = fmaf(fmaf(fabsf(E.jx[e]), erf_abs, E.jx[e]), E.jsc[e], E.jsh[e]);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(E.z[e]));
-        } else {
-            const float* z = E.z;
-            const unsigned h01 = pack2s(z[0], z[1]), h23 = pack2s(z[2], z[3]);
-            const unsigned l01 = pack2s(z[0] - __uint_as_float(h01 << 16), z[1] - __uint_as_float(h01 & 0xffff0000u));
-            const unsigned l23 = pack2s(z[2] - __uint_as_float(h23 << 16), z[3] - __uint_as_float(h23 & 0xffff0000u));
-            unsigned char* p = dstp + st_off[g] + t * TSTEP;
-            *(uint2*)p = make_uint2(h01, h23);
-            *(uint2*)(p + PLANE) = make_uint2(l01, l23);
-        }
+        if (st == 0) epi_stage0<C, NFS, G>(E, fsw, second, emit, qf, h[t], accv, g);
+        else if (!emit) return;
+        else if (st < 4) epi_stage13(E, g, st);
+        else epi_store_split(E, dstp + st_off[g] + t * TSTEP, PLANE);
     };
 
     // weights of the k5 convs: k-step s covers k = 16 s .. 16 s + 15 (k = tap * C + ci), lane half lh the second eight of them
@@ -554,13 +468,12 @@ extern "C" int alive_filter_block_small(const float* U, int N, int C, int L, con
 extern "C" int alive_filter_block_small_range(const float* U, int N, int C, int L, const float* wpack, const float* film,
                                               int film_rows, int Lf, int film_off, int t0, int f0, int film_ld,
                                               const float* skip, float* out, void* stream) {
-    ALIVE_CHECK_ARG(U && wpack && film && out, "alive_filter_block_small: null pointer");
-    ALIVE_CHECK_ARG(N > 0 && L > 16 && Lf > 0, "alive_filter_block_small: bad sizes (L must exceed the largest reflect pad, 16)");
-    ALIVE_CHECK_ARG(C == 8 || C == 16, "alive_filter_block_small: C must be 8 or 16, got %d", C);
-    ALIVE_CHECK_ARG(U != out, "alive_filter_block_small: in-place not supported (tiles read a halo of their left neighbour)");
-    ALIVE_CHECK_ARG((L & 3) == 0 && ((((uintptr_t)U) | ((uintptr_t)out) | ((uintptr_t)skip) | ((uintptr_t)wpack)) & 15) == 0,
-                    "alive_filter_block_small: L must be a multiple of 4 and U / out / skip / wpack 16-byte aligned");
-    ALIVE_CHECK_ARG(film_ld > 0 && t0 >= 0 && f0 >= 0, "alive_filter_block_small: bad frame range");
+    // (C keeps its place in the order of the checks -- third, behind null pointers and sizes, which the helper reports before
+    //  anything else: a call that is wrong in several arguments hears the same message as before)
+    ALIVE_CHECK_ARG(!(U && wpack && film && out && N > 0 && L > 16 && Lf > 0) || C == 8 || C == 16, "alive_filter_block_small: C must be 8 or 16, got %d", C);
+    if (int rc = filter_block_check_args("alive_filter_block_small", U && wpack && film && out, U, out, N, L, Lf,
+                                         (uintptr_t)U | (uintptr_t)out | (uintptr_t)skip | (uintptr_t)wpack, "U / out / skip / wpack", film_ld, t0, f0))
+        return rc;
     // a signal that would be a handful of batch tiles runs on 8-KB planes (see Cfg)
     static const int pl_env = getenv("ALIVE_FBS_PLANE") ? atoi(getenv("ALIVE_FBS_PLANE")) : 0;
     const int big_tiles = cdiv(L, (C == 8 ? Cfg<8>::TT : Cfg<16>::TT)) * N;
@@ -585,23 +498,17 @@ extern "C" int alive_filter_block_small_range(const float* U, int N, int C, int 
 extern "C" int alive_filter_block_small_up_range(const float* U, int N, int L, const float* wpack, const float* film, int film_rows, int Lf,
                                                  int film_off, int t0, int f0, int film_ld, const float* skip, const float* upW,
                                                  const float* upb, float* out, void* stream) {
-    ALIVE_CHECK_ARG(U && wpack && film && upW && upb && out, "alive_filter_block_small_up: null pointer");
-    ALIVE_CHECK_ARG(N > 0 && L > 16 && Lf > 0, "alive_filter_block_small_up: bad sizes (L must exceed the largest reflect pad, 16)");
-    ALIVE_CHECK_ARG(U != out, "alive_filter_block_small_up: in-place not supported (tiles read a halo of their left neighbour)");
-    ALIVE_CHECK_ARG((L & 3) == 0 && ((((uintptr_t)U) | ((uintptr_t)out) | ((uintptr_t)skip) | ((uintptr_t)wpack)) & 15) == 0,
-                    "alive_filter_block_small_up: L must be a multiple of 4 and U / out / skip / wpack 16-byte aligned");
-    ALIVE_CHECK_ARG(film_ld > 0 && t0 >= 0 && f0 >= 0, "alive_filter_block_small_up: bad frame range");
+    if (int rc = filter_block_check_args("alive_filter_block_small_up", U && wpack && film && upW && upb && out, U, out, N, L, Lf,
+                                         (uintptr_t)U | (uintptr_t)out | (uintptr_t)skip | (uintptr_t)wpack, "U / out / skip / wpack", film_ld, t0, f0))
+        return rc;
     return launch_small<16, 16384, TAIL_UP>(U, N, L, wpack, film, film_rows, Lf, film_off, t0, f0, film_ld, skip, out, (hipStream_t)stream, upW, upb);
 }
 
 extern "C" int alive_filter_block_small_wave_range(const float* U, int N, int L, const float* wpack, const float* film, int film_rows, int Lf,
                                                    int film_off, int t0, int f0, int film_ld, const float* oW, const float* ob, float* wave,
                                                    void* stream) {
-    ALIVE_CHECK_ARG(U && wpack && film && oW && ob && wave, "alive_filter_block_small_wave: null pointer");
-    ALIVE_CHECK_ARG(N > 0 && L > 16 && Lf > 0, "alive_filter_block_small_wave: bad sizes (L must exceed the largest reflect pad, 16)");
-    ALIVE_CHECK_ARG(U != wave, "alive_filter_block_small_wave: in-place not supported (tiles read a halo of their left neighbour)");
-    ALIVE_CHECK_ARG((L & 3) == 0 && ((((uintptr_t)U) | ((uintptr_t)wpack)) & 15) == 0,
-                    "alive_filter_block_small_wave: L must be a multiple of 4 and U / wpack 16-byte aligned");
-    ALIVE_CHECK_ARG(film_ld > 0 && t0 >= 0 && f0 >= 0, "alive_filter_block_small_wave: bad frame range");
+    if (int rc = filter_block_check_args("alive_filter_block_small_wave", U && wpack && film && oW && ob && wave, U, wave, N, L, Lf,
+                                         (uintptr_t)U | (uintptr_t)wpack, "U / wpack", film_ld, t0, f0))
+        return rc;
     return launch_small<8, 16384, TAIL_WAVE>(U, N, L, wpack, film, film_rows, Lf, film_off, t0, f0, film_ld, nullptr, wave, (hipStream_t)stream, oW, ob);
 }

@@ -71,11 +71,6 @@ struct StepWalk {
     }
 };
 
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    bf16x2_t h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
 // the plane format of an NP-plane operand: NP = 1 is ONE fp16 plane (plain operands, round 5), NP >= 2 split bf16 planes
 template <int NP>
 __device__ __forceinline__ unsigned pack_plane2(float a, float b, bool count = true) { return NP == 1 ? pack_f16x2(a, b, count) : pack_bf16x2(a, b); }
