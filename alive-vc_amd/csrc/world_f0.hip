@@ -16,6 +16,7 @@
 // restatement's on the same input and the same taps (alive_world_f0_taps computes them on the host with the C library's cos).
 #include "common.h"
 #include <math.h>
+#include <string.h>
 #include <vector>
 
 namespace {
@@ -417,7 +418,9 @@ __global__ void __launch_bounds__(128) wf_stone_kernel(const float* __restrict__
         const double hw = 3.0 / f0 / 2.0;
         const int rr = mround(hw * fs), m = rr * 2 + 1;
         const double wl = (double)(rr * 2 + 1) / fs;
-        const int n = (int)pow(2.0, 2.0 + (int)(log(hw * fs + WF_SAFE) / WF_LOG2));
+        // WORLD's (int)pow(2.0, 2.0 + (int)(...)) as a shift: the device pow(2.0, 11.0) lies below 2048 and truncated to 2047, the
+        // DFT length of every frame with f0 in (40, 46.875] Hz at 16 kHz
+        const int n = 1 << (2 + (int)(log(hw * fs + WF_SAFE) / WF_LOG2));
         const int basic = mround((tpos + (double)(-rr) / fs) * fs + 0.001);
         double* mw = mwin[wv];
         double* dw = dwin[wv];
@@ -518,11 +521,12 @@ extern "C" size_t alive_world_f0_workspace_bytes(int N, int L8, int fs, double f
 
 namespace {
 
-// row_on == nullptr: every row
+// row_on == nullptr: every row.  stages: how many of the five launches to issue (5: all; fewer only from alive_world_f0_stages)
 int world_f0_launch(const char* who, const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
-                    const double* taps, const int32_t* row_on, float* f0_out, void* ws, size_t ws_bytes, void* stream) {
+                    const double* taps, const int32_t* row_on, float* f0_out, void* ws, size_t ws_bytes, int stages, void* stream) {
     WfPlan p;
     ALIVE_CHECK_ARG(x8 && taps && f0_out && ws, "%s: null pointer", who);
+    ALIVE_CHECK_ARG(stages >= 1 && stages <= 5, "%s: %d stages (1 .. 5)", who, stages);
     const int pr = plan(p, N, L8, fs, f0_floor, f0_ceil, frame_period);
     ALIVE_CHECK_ARG(pr == 0, "%s: bad args (N %d, L8 %d, fs %d, f0 range [%g, %g], frame period %g; fs <= 16000, at most "
                     "%d bands, lowest band <= %d taps)", who, N, L8, fs, f0_floor, f0_ceil, frame_period, WF_MAX_BANDS, WF_MAX_NUTTALL);
@@ -539,10 +543,11 @@ int world_f0_launch(const char* who, const float* x8, int N, int L8, int fs, dou
     double* s2 = (double*)(w + p.off_s2);
     double* s3 = (double*)(w + p.off_s3);
     wf_mean_kernel<<<N, 256, 0, s>>>(x8, L8, row_on, mean);
-    wf_lowcut_kernel<<<dim3(cdiv(p.yl_ld, 256), N), 256, 0, s>>>(x8, mean, taps, L8, p.c, p.yl_ld, row_on, yl);
-    wf_bands_kernel<<<dim3(p.nb, N), WF_BT, 0, s>>>(yl, taps, p, row_on, iv, ni);
-    wf_select_kernel<<<N, 64, 0, s>>>(p, row_on, iv, ni, best, s1, s2, s3, (int*)(w + p.off_pi), (int*)(w + p.off_ng));
-    wf_stone_kernel<<<dim3(cdiv(p.F, 2), N), 128, 0, s>>>(x8, p, s3, row_on, f0_out);
+    if (stages >= 2) wf_lowcut_kernel<<<dim3(cdiv(p.yl_ld, 256), N), 256, 0, s>>>(x8, mean, taps, L8, p.c, p.yl_ld, row_on, yl);
+    if (stages >= 3) wf_bands_kernel<<<dim3(p.nb, N), WF_BT, 0, s>>>(yl, taps, p, row_on, iv, ni);
+    if (stages >= 4)
+        wf_select_kernel<<<N, 64, 0, s>>>(p, row_on, iv, ni, best, s1, s2, s3, (int*)(w + p.off_pi), (int*)(w + p.off_ng));
+    if (stages >= 5) wf_stone_kernel<<<dim3(cdiv(p.F, 2), N), 128, 0, s>>>(x8, p, s3, row_on, f0_out);
     ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
 }
@@ -552,7 +557,36 @@ int world_f0_launch(const char* who, const float* x8, int N, int L8, int fs, dou
 extern "C" int alive_world_f0(const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
                               const double* taps, float* f0_out, void* ws, size_t ws_bytes, void* stream) {
     return world_f0_launch("alive_world_f0", x8, N, L8, fs, f0_floor, f0_ceil, frame_period, taps, nullptr, f0_out, ws, ws_bytes,
-                           stream);
+                           5, stream);
+}
+
+// TEST ONLY: alive_world_f0 stopped after the first `stages` of its five launches (mean, low cut, bands, select, StoneMask); the
+// buffers of the later stages and, below 5, f0_out are not touched.  alive_world_f0_layout says where the buffers are.
+extern "C" int alive_world_f0_stages(const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
+                                     const double* taps, float* f0_out, void* ws, size_t ws_bytes, int stages, void* stream) {
+    return world_f0_launch("alive_world_f0_stages", x8, N, L8, fs, f0_floor, f0_ceil, frame_period, taps, nullptr, f0_out, ws,
+                           ws_bytes, stages, stream);
+}
+
+// TEST ONLY, host arithmetic: the plan of a call as int64 words (include/alive_vc.h lists them); the count written, or plan()'s
+// negative code, or -10 for a missing / short `out`
+extern "C" int alive_world_f0_layout(int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period, int64_t* out,
+                                     int n_out) {
+    WfPlan p;
+    const int pr = plan(p, N, L8, fs, f0_floor, f0_ceil, frame_period);
+    if (pr != 0) return pr;
+    const int n = 16 + 3 * p.nb;
+    if (!out || n_out < n) return -10;
+    const int64_t head[16] = {p.F, p.nb, p.c, p.Ly, p.yl_ld, (int64_t)p.total, (int64_t)p.off_mean, (int64_t)p.off_yl,
+                              (int64_t)p.off_iv, (int64_t)p.off_ni, (int64_t)p.off_best, (int64_t)p.off_s1, (int64_t)p.off_s2,
+                              (int64_t)p.off_s3, (int64_t)p.off_pi, (int64_t)p.off_ng};
+    for (int i = 0; i < 16; ++i) out[i] = head[i];
+    for (int b = 0; b < p.nb; ++b) {
+        out[16 + b] = p.h[b];
+        out[16 + p.nb + b] = p.woff[b];
+        memcpy(&out[16 + 2 * p.nb + b], &p.bound[b], sizeof(double));
+    }
+    return n;
 }
 
 // the rows whose row_on[r] (device int32 [N]) is nonzero: bitwise alive_world_f0 of those rows; the others get 0 (unvoiced) at every
@@ -562,7 +596,7 @@ extern "C" int alive_world_f0_rows(const float* x8, int N, int L8, int fs, doubl
                                    void* stream) {
     ALIVE_CHECK_ARG(row_on, "alive_world_f0_rows: null row mask");
     return world_f0_launch("alive_world_f0_rows", x8, N, L8, fs, f0_floor, f0_ceil, frame_period, taps, row_on, f0_out, ws,
-                           ws_bytes, stream);
+                           ws_bytes, 5, stream);
 }
 
 extern "C" int alive_linear_resize(const float* x, int rows, int Lin, float* y, int Lout, void* stream) {

@@ -193,6 +193,8 @@ PROTOTYPES = {
     "alive_world_f0": (_I, [_VP, _I, _I, _I, _D, _D, _D, _VP, _VP, _VP, _SZ, _VP]),
     "alive_world_f0_rows": (_I, [_VP, _I, _I, _I, _D, _D, _D, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "alive_linear_resize": (_I, [_VP, _I, _I, _VP, _I, _VP]),
+    "alive_world_f0_stages": (_I, [_VP, _I, _I, _I, _D, _D, _D, _VP, _VP, _VP, _SZ, _I, _VP]),   # test only
+    "alive_world_f0_layout": (_I, [_I, _I, _I, _D, _D, _D, _VP, _I]),                            # test only
 }
 
 

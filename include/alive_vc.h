@@ -1171,6 +1171,18 @@ int alive_world_f0(const float* x8, int N, int L8, int fs, double f0_floor, doub
 int alive_world_f0_rows(const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
                         const double* taps, const int32_t* row_on, float* f0_out, void* ws, size_t ws_bytes, void* stream);
 int alive_linear_resize(const float* x, int rows, int Lin, float* y, int Lout, void* stream);
+/* TEST ONLY.  alive_world_f0_stages is alive_world_f0 (the same launcher) stopped after the first `stages` (1 .. 5) of its five
+ * launches: mean, low cut, bands, select + FixF0Contour, StoneMask; buffers of later stages, and f0_out below 5, are not touched.
+ * alive_world_f0_layout is host arithmetic on the same plan: it writes 16 + 3 nb int64 words and returns that count (a negative
+ * code where the plan refuses the arguments, -10 for a missing or short `out`; at most 16 + 3 * 32 words):
+ *   out[0 .. 5]    F, nb (bands), c (low-cut half width), Ly = L8 + 1, yl_ld = Ly + 2c, total (= alive_world_f0_workspace_bytes)
+ *   out[6 .. 15]   byte offsets in the workspace: mean f64 [N], yl f64 [N][yl_ld] (lag n at n + c), iv f64 [N][nb][4][F] (the
+ *                  streams' interp1 values; select overwrites stream 0 with the band's candidate), ni i32 [N][nb][4] (interval
+ *                  counts), best / s1 / s2 / s3 f64 [N][F] (best band, FixF0Contour steps 1, 2 and 3-4), pos / neg i32 [N][F]
+ *   out[16 ..]     h[nb] (band half delay; 4h taps), woff[nb] (offset of the band's taps in the table), bound[nb] (bits of the f64) */
+int alive_world_f0_stages(const float* x8, int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period,
+                          const double* taps, float* f0_out, void* ws, size_t ws_bytes, int stages, void* stream);
+int alive_world_f0_layout(int N, int L8, int fs, double f0_floor, double f0_ceil, double frame_period, int64_t* out, int n_out);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,8 @@ agrees to rounding.
   dio(x, fs, ...)        -> (f0, t)          pyworld.dio with f0_floor / f0_ceil / channels_in_octave / frame_period / allowed_range
   stonemask(x, f0, t, fs) -> refined f0       pyworld.stonemask
   dio_stonemask_rows(X, fs, f0_floor, f0_ceil) -> float32 [N, F]   the pair on every row of X (float32 [N, L] at fs)
+  dio_stages(X, fs, ...)  -> per row what every stage of the kernels leaves behind (mean, low cut, streams, candidates, contour steps)
+  stonemask_margin(x, fs, t, f0) -> how far StoneMask's frame is from taking another branch on a value it computes
 """
 import math
 
@@ -78,11 +80,11 @@ def _row_means(X):
     return acc[:, 0]
 
 
-def filtered_signals(X, fs, f0_floor, f0_ceil):
-    """DIO's band signals: float64 [N, L] -> list per band of [N, L + 1]"""
+def lowcut_signals(X, fs, f0_floor, f0_ceil):
+    """DIO's mean and low-cut signal: float64 [N, L] -> (mean [N], yl [N, L + 1 + 2c], yl[:, n + c] the lag n in [-c, L + 1 + c))"""
     N, L = X.shape
     Ly = L + 1
-    lc, bl = taps(fs, f0_floor, f0_ceil)
+    lc, _ = taps(fs, f0_floor, f0_ceil)
     c = (len(lc) - 1) // 2
     mean = _row_means(X) / Ly
     y = np.zeros((N, Ly))
@@ -95,6 +97,14 @@ def filtered_signals(X, fs, f0_floor, f0_ceil):
     for j in range(2 * c + 1):                # lag k = j - c: yl[n] += lc[k] * y[n - k]
         k = j - c
         yl = yl + lc[j] * yp[:, c - k:c - k + Ly + 2 * c]
+    return mean, yl
+
+
+def band_signals(yl, L, fs, f0_floor, f0_ceil):
+    """the Nuttall low-pass of every band on the low-cut signal -> list per band of [N, L + 1]"""
+    N, Ly = yl.shape[0], L + 1
+    lc, bl = taps(fs, f0_floor, f0_ceil)
+    c = (len(lc) - 1) // 2
     out = []
     for h, w in bl:
         pad = max(0, 2 * h - c)
@@ -106,6 +116,12 @@ def filtered_signals(X, fs, f0_floor, f0_ceil):
             s = s + w[j] * ylp[:, o:o + Ly]
         out.append(s)
     return out
+
+
+def filtered_signals(X, fs, f0_floor, f0_ceil):
+    """DIO's band signals: float64 [N, L] -> list per band of [N, L + 1]"""
+    _, yl = lowcut_signals(X, fs, f0_floor, f0_ceil)
+    return band_signals(yl, X.shape[1], fs, f0_floor, f0_ceil)
 
 
 def _zero_crossing(s, fs):
@@ -125,16 +141,23 @@ def _interp1(x, y, xi):
     return y[k - 1] + s * (y[k] - y[k - 1])
 
 
-def _candidates(s, fs, boundary, f0_floor, f0_ceil, t):
+def _streams(s, fs, t):
+    """the four event streams of a band signal (negative / positive crossings, peaks, dips): per stream the interval count and,
+    from two intervals on, interp1 of the intervals at the frame times (None below two: nothing to interpolate)"""
     neg = _zero_crossing(s, fs)
     pos = _zero_crossing(-s, fs)
     d = (-s[:-1]) - (-s[1:])
     peak = _zero_crossing(d, fs)
     dip = _zero_crossing(-d, fs)
+    ni = [len(a) for a, _ in (neg, pos, peak, dip)]
+    return ni, [_interp1(a, b, t) if len(a) >= 2 else None for a, b in (neg, pos, peak, dip)]
+
+
+def _candidates(s, fs, boundary, f0_floor, f0_ceil, t, streams=None):
+    ni, iv = _streams(s, fs, t) if streams is None else streams
     F = len(t)
-    if min(len(neg[0]), len(pos[0]), len(peak[0]), len(dip[0])) <= 2:
+    if min(ni) <= 2:
         return np.zeros(F), np.full(F, K_MAX)
-    iv = [_interp1(a, b, t) for a, b in (neg, pos, peak, dip)]
     cand = (((iv[0] + iv[1]) + iv[2]) + iv[3]) / 4.0
     dv = [v - cand for v in iv]
     score = np.sqrt((((dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2]) + dv[3] * dv[3]) / 3.0)
@@ -153,12 +176,21 @@ def _select_best(cur, past, cands, j, allowed_range):
     return 0.0 if abs(1.0 - best / ref) > allowed_range else best
 
 
+def voice_range(frame_period, f0_floor):
+    return int(0.5 + 1000.0 / frame_period / f0_floor) * 2 + 1
+
+
 def fix_f0_contour(best, cands, frame_period, f0_floor, allowed_range):
     """FixF0Contour's four steps; every frame stays 0 when there are no more frames than the voice range"""
+    return fix_f0_contour_steps(best, cands, frame_period, f0_floor, allowed_range)[2]
+
+
+def fix_f0_contour_steps(best, cands, frame_period, f0_floor, allowed_range):
+    """(step 1, step 2, steps 3-4) of FixF0Contour; (None, None, zeros) when there are no more frames than the voice range"""
     F = len(best)
-    vr = int(0.5 + 1000.0 / frame_period / f0_floor) * 2 + 1
+    vr = voice_range(frame_period, f0_floor)
     if F <= vr:
-        return np.zeros(F)
+        return None, None, np.zeros(F)
     base = best.copy()
     base[:vr] = 0.0
     base[F - vr:] = 0.0
@@ -190,22 +222,31 @@ def fix_f0_contour(best, cands, frame_period, f0_floor, allowed_range):
             s4[j - 1] = _select_best(s4[j], s4[j + 1], cands, j - 1, allowed_range)
             if s4[j - 1] == 0:
                 break
-    return s4
+    return s1, s2, s4
 
 
-def dio_rows(X, fs, f0_floor=20.0, f0_ceil=4096.0, frame_period=5.0, allowed_range=0.1):
-    """pyworld.dio on every row of X (float64 [N, L]) -> (f0 [N, F], t [F])"""
+def dio_stages(X, fs, f0_floor=20.0, f0_ceil=4096.0, frame_period=5.0, allowed_range=0.1):
+    """DIO on every row of X (float64 [N, L]) with what each stage of csrc/world_f0.hip leaves behind: a dict per row of
+         mean, yl [L + 1 + 2c]           the row's mean and its low-cut signal at every lag (stages 1, 2)
+         ni [bands][4], iv [bands][4]    per band and stream the interval count and the F interp1 values (None where ni < 2) (stage 3)
+         cand [bands][F]                 the band's candidate, 0 where refused (stage 4)
+         best, s1, s2 [F]                the best band and FixF0Contour's steps 1 and 2 (s1, s2 None when F <= the voice range)
+         f0 [F]                          the contour after steps 3-4"""
     X = np.atleast_2d(np.asarray(X, dtype=np.float64))
     N, L = X.shape
     F = n_frames(L, fs, frame_period)
     t = np.arange(F) * frame_period / 1000.0
     bnd = bands(f0_floor, f0_ceil)
-    sig = filtered_signals(X, fs, f0_floor, f0_ceil)
-    out = np.zeros((N, F))
+    mean, yl = lowcut_signals(X, fs, f0_floor, f0_ceil)
+    sig = band_signals(yl, L, fs, f0_floor, f0_ceil)
+    rows = []
     for r in range(N):
-        cands, scores = [], []
+        cands, scores, nis, ivs = [], [], [], []
         for b, s in zip(bnd, sig):
-            c, sc = _candidates(s[r], float(fs), b, f0_floor, f0_ceil, t)
+            ni, iv = _streams(s[r], float(fs), t)
+            c, sc = _candidates(s[r], float(fs), b, f0_floor, f0_ceil, t, (ni, iv))
+            nis.append(ni)
+            ivs.append(iv)
             cands.append(c)
             scores.append(sc / (c + K_SAFE))
         best = cands[0].copy()
@@ -214,8 +255,16 @@ def dio_rows(X, fs, f0_floor=20.0, f0_ceil=4096.0, frame_period=5.0, allowed_ran
             better = low > sc
             low = np.where(better, sc, low)
             best = np.where(better, c, best)
-        out[r] = fix_f0_contour(best, cands, frame_period, f0_floor, allowed_range)
-    return out, t
+        s1, s2, f0 = fix_f0_contour_steps(best, cands, frame_period, f0_floor, allowed_range)
+        rows.append(dict(mean=mean[r], yl=yl[r], ni=np.array(nis, dtype=np.int64), iv=ivs, cand=np.stack(cands), best=best, s1=s1,
+                         s2=s2, f0=f0))
+    return rows, t
+
+
+def dio_rows(X, fs, f0_floor=20.0, f0_ceil=4096.0, frame_period=5.0, allowed_range=0.1):
+    """pyworld.dio on every row of X (float64 [N, L]) -> (f0 [N, F], t [F])"""
+    rows, t = dio_stages(X, fs, f0_floor, f0_ceil, frame_period, allowed_range)
+    return np.stack([row["f0"] for row in rows]), t
 
 
 def dio(x, fs, f0_floor=50.0, f0_ceil=800.0, frame_period=5.0, allowed_range=0.1):
@@ -245,7 +294,8 @@ def _fix_f0(seg_main, seg_diff, n, fs, f0, harmonics):
     return num / den if den != 0.0 else 0.0       # a window without energy (WORLD divides 0 by 0 here): no refinement
 
 
-def _refined(x, fs, t, f0):
+def _refined(x, fs, t, f0, margins=None):
+    """StoneMask of one frame; `margins` (a list) collects the relative margin of every decision taken on a computed value"""
     if f0 <= K_FLOOR_STONEMASK or f0 > fs / 12.0:
         return 0.0
     hw = 3.0 / f0 / 2.0
@@ -264,11 +314,30 @@ def _refined(x, fs, t, f0):
     seg = x[np.clip(bi - 1, 0, len(x) - 1)]
     main, diff = seg * win, seg * dwin
     tent = _fix_f0(main, diff, n, fs, f0, 2)
+    if margins is not None:
+        margins += [abs(tent) / f0, abs(tent - f0 * 2) / (f0 * 2)]
     if tent <= 0.0 or tent > f0 * 2:
         tent = 0.0
     else:
+        if margins is not None:
+            for i in range(6):
+                v = tent * n / fs * (i + 1)
+                margins.append(abs(v - (math.floor(v) + 0.5)) / v)
         tent = _fix_f0(main, diff, n, fs, tent, 6)
+    if margins is not None:
+        margins.append(abs(abs(tent - f0) - f0 * 0.2) / f0)
     return f0 if abs(tent - f0) > f0 * 0.2 else tent
+
+
+def stonemask_margin(x, fs, t, f0):
+    """How far StoneMask's frame at time t with DIO's f0 is from taking another branch on a value it computes, as the smallest
+    relative margin of: tent <= 0 (|tent| / f0); tent > 2 f0; each of the second pass's six bins f0 n / fs (i + 1) from a
+    half-integer (relative to the bin); |tent - f0| against 0.2 f0 (relative to f0).  inf for a frame the f0 gates leave unvoiced:
+    those are taken on DIO's f0 itself.  An implementation whose computed values agree to well below the margin takes the same
+    branches."""
+    margins = []
+    _refined(np.asarray(x, dtype=np.float64), float(fs), t, f0, margins)
+    return min(margins) if margins else math.inf
 
 
 def stonemask(x, f0, t, fs):
