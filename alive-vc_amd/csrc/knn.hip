@@ -3986,6 +3986,49 @@ extern "C" int alive_debug_knn_stage_view(int64_t Tt, int64_t M, int k, int sub,
     return ALIVE_OK;
 }
 
+// debug (tests/test_gpu_knn_cert.py): knn_rescore_kernel through rescore_launch / pool_rescore_launch on the caller's buffers.  What
+// the kernel indexes with is checked here as far as the host can see it (sizes and pointers); the contents of cand_idx, frame_list,
+// out_idx and the pool plan stay on the device and are the caller's to check.
+static int debug_rescore_check(const char* who, const AliveRescoreArgs* a, bool pool) {
+    ALIVE_CHECK_ARG(a && a->cand_val && a->cand_idx && a->s_f32 && a->rows && a->norms && a->out_val && a->out_idx, "%s: null pointer", who);
+    ALIVE_CHECK_ARG(a->k >= 1 && a->k <= KH, "%s: k=%d outside [1,%d]", who, a->k, KH);
+    ALIVE_CHECK_ARG(a->P >= 1 && a->kp >= 1 && (int64_t)a->P * a->kp <= 1024, "%s: P=%d x kp=%d outside [1,1024] candidates", who, a->P, a->kp);
+    ALIVE_CHECK_ARG(a->list_len == 8 || a->list_len == 16, "%s: list_len=%d is neither 8 nor 16", who, a->list_len);
+    ALIVE_CHECK_ARG(a->M >= 1 && a->M < ((int64_t)1 << 31) && a->frames >= 1 && a->Tt >= 1 && a->Tt < ((int64_t)1 << 31),
+                    "%s: M=%lld rows, %lld frames, Tt=%lld", who, (long long)a->M, (long long)a->frames, (long long)a->Tt);
+    ALIVE_CHECK_ARG(a->frame_list != nullptr || a->Tt <= a->frames, "%s: Tt=%lld slots over %lld frames without a frame_list", who,
+                    (long long)a->Tt, (long long)a->frames);
+    const bool certify = a->flag_list != nullptr && a->collect == 0;
+    ALIVE_CHECK_ARG((a->flag_list != nullptr) == (a->flag_cnt != nullptr), "%s: flag_list and flag_cnt go together", who);
+    ALIVE_CHECK_ARG((a->collect == 0 || a->collect == 1) && (a->collect == 0 || a->flag_list != nullptr), "%s: collect=%d needs a flag_list", who, a->collect);
+    ALIVE_CHECK_ARG(a->thr_list == nullptr || a->flag_list != nullptr, "%s: thr_list without a flag_list", who);
+    ALIVE_CHECK_ARG(!certify || (a->P * a->kp) % a->list_len == 0, "%s: %d candidates are not whole lists of %d", who, a->P * a->kp, a->list_len);
+    ALIVE_CHECK_ARG((a->det_q != nullptr) == (a->det_lib != nullptr), "%s: det_q and det_lib go together", who);
+    ALIVE_CHECK_ARG(a->pre_scale > 0.0f && a->zsig >= 0.0f && a->sd_prior >= 0.0f && a->overflow_slack >= 0.0f, "%s: bad scale, z, prior or slack", who);
+    if (a->gate_lo == GATE_BOOL) ALIVE_CHECK_ARG(a->gate_cnt != nullptr, "%s: an on / off gate without its word", who);
+    else ALIVE_CHECK_ARG(a->gate_lo <= a->gate_hi, "%s: gate (%d, %d] is empty", who, a->gate_lo, a->gate_hi);
+    if (pool) ALIVE_CHECK_ARG(certify && a->frame_list != nullptr && a->gate_lo != GATE_BOOL, "%s: the pool form certifies the slots of a plan", who);
+    return ALIVE_OK;
+}
+
+extern "C" int alive_debug_knn_rescore(const AliveRescoreArgs* a, void* stream) {
+    if (int rc = debug_rescore_check("alive_debug_knn_rescore", a, false)) return rc;
+    rescore_launch((unsigned)((a->Tt + 3) / 4), (hipStream_t)stream, a->cand_val, a->cand_idx, a->P, a->kp, a->s_f32, a->rows, a->norms, a->Tt,
+                   a->idx_base, a->k, a->out_val, a->out_idx, a->frame_list, a->gate_cnt, a->gate_lo, a->gate_hi, a->flag_list, a->flag_cnt,
+                   a->zsig, a->list_len, a->pre_scale, a->sd_prior, a->det_q, a->det_lib, a->thr_list, a->collect, a->overflow_slack,
+                   a->force_fail);
+    ALIVE_CHECK_LAUNCH("alive_debug_knn_rescore");
+    return ALIVE_OK;
+}
+
+// (alive_debug_knn_rescore_pool stands behind the pool search, whose launcher it shares)
+
+extern "C" int alive_debug_knn_pool_fields(int32_t* out, int n_out) {
+    ALIVE_CHECK_ARG(out && n_out >= 4, "alive_debug_knn_pool_fields: bad args");
+    out[0] = PG_FIELDS; out[1] = PG_VOICE; out[2] = PG_BLK0; out[3] = PG_K;
+    return ALIVE_OK;
+}
+
 extern "C" int alive_knn_merge_gather(const float* cand_val, const int32_t* cand_idx, int n_shards, int k, double alpha,
                                       const float* rows_f32_full, const float* src, int N, int T, float* out,
                                       int32_t* final_idx, void* stream) {
@@ -4181,6 +4224,17 @@ extern "C" size_t alive_knn_pool_k_workspace_bytes(int N, int T, int k_max, int 
 
 extern "C" const int* alive_knn_pool_stats(void* ws) { return (const int*)ws; }
 
+// the pool form of rescore_launch: the same choice of PER; `rest` ends in the PoolRescore
+template <typename... A>
+static void pool_rescore_launch(unsigned grid, hipStream_t s, const float* cv, const int* ci, int P, int kp, A... rest) {
+    const int R = P * kp;
+    if (R <= 64) knn_rescore_kernel<0, true><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+    else if (R <= 192) knn_rescore_kernel<3, true><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+    else if (R <= 256) knn_rescore_kernel<4, true><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+    else if (R <= 512) knn_rescore_kernel<8, true><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+    else knn_rescore_kernel<16, true><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+}
+
 // both pool entry points: k_row null = every row at k (alive_knn_search_pool), else k = k_max and row n at k_row[n]
 static int search_pool(const char* who, const float* src, int N, int T, const void* images, const int64_t* img_off, const float* rows_f32,
                        const float* norms, const float* bounds, int64_t P, const int32_t* seg_lo, const int32_t* seg_len, int V,
@@ -4214,19 +4268,9 @@ static int search_pool(const char* who, const float* src, int N, int T, const vo
         w.s_c, (const unsigned short*)images, 0, 0, 0, w.P, w.cv, w.ci, nullptr, 0, 0, 0, nullptr, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, 0,
         pb);
     const PoolRescore pr{w.slot_grp, w.grp, w.gfail, w.fb};
-    const int R = w.P * KP;
     // (the kernel takes each frame's k from its group; the k argument is the stride of the lists)
-#define ALIVE_POOL_RESCORE(PER_)                                                                                                   \
-    knn_rescore_kernel<PER_, true><<<(unsigned)(w.S / 4), 256, 0, s>>>(w.cv, w.ci, w.P, KP, w.s_f32, rows_f32, norms, w.S, 0, k,     \
-                                                                     out_val, out_idx, w.slot_frame, nullptr, 0, 0, w.fb, w.stats, \
-                                                                     CERT_Z, KH, 1.0f, SD_PRIOR16, w.dq, bounds, nullptr, 0, 0.0f, \
-                                                                     nullptr, pr)
-    if (R <= 64) ALIVE_POOL_RESCORE(0);
-    else if (R <= 192) ALIVE_POOL_RESCORE(3);
-    else if (R <= 256) ALIVE_POOL_RESCORE(4);
-    else if (R <= 512) ALIVE_POOL_RESCORE(8);
-    else ALIVE_POOL_RESCORE(16);
-#undef ALIVE_POOL_RESCORE
+    pool_rescore_launch((unsigned)(w.S / 4), s, w.cv, w.ci, w.P, KP, w.s_f32, rows_f32, norms, w.S, 0, k, out_val, out_idx, w.slot_frame,
+                        nullptr, 0, 0, w.fb, w.stats, CERT_Z, KH, 1.0f, SD_PRIOR16, w.dq, bounds, nullptr, 0, 0.0f, nullptr, pr);
     knn_pool_fallback_plan_kernel<<<1, 64, 0, s>>>(seg_len, w);
     knn_pool_scan_kernel<<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, seg_lo, seg_len, w);
     if (k_row != nullptr) knn_pool_merge_kernel<MERGE_ROW><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
@@ -4250,6 +4294,20 @@ extern "C" int alive_knn_search_pool_k(const float* src, int N, int T, const voi
     ALIVE_CHECK_ARG(k_row, "alive_knn_search_pool_k: null pointer");
     return search_pool("alive_knn_search_pool_k", src, N, T, images, img_off, rows_f32, norms, bounds, P, seg_lo, seg_len, V, max_len, voice,
                        k_row, k_max, out_val, out_idx, ws, stream);
+}
+
+// debug (tests/test_gpu_knn_cert.py): the pool form of alive_debug_knn_rescore, through the pool search's own launcher
+extern "C" int alive_debug_knn_rescore_pool(const AliveRescoreArgs* a, const int32_t* slot_grp, const int32_t* grp, int32_t* gfail,
+                                            int32_t* fb, int groups, void* stream) {
+    if (int rc = debug_rescore_check("alive_debug_knn_rescore_pool", a, true)) return rc;
+    ALIVE_CHECK_ARG(slot_grp && grp && gfail && fb && groups >= 1, "alive_debug_knn_rescore_pool: null pointer or no group");
+    const PoolRescore pr{slot_grp, grp, gfail, fb};
+    pool_rescore_launch((unsigned)((a->Tt + 3) / 4), (hipStream_t)stream, a->cand_val, a->cand_idx, a->P, a->kp, a->s_f32, a->rows, a->norms,
+                        a->Tt, a->idx_base, a->k, a->out_val, a->out_idx, a->frame_list, a->gate_cnt, a->gate_lo, a->gate_hi, a->flag_list,
+                        a->flag_cnt, a->zsig, a->list_len, a->pre_scale, a->sd_prior, a->det_q, a->det_lib, a->thr_list, a->collect,
+                        a->overflow_slack, a->force_fail, pr);
+    ALIVE_CHECK_LAUNCH("alive_debug_knn_rescore_pool");
+    return ALIVE_OK;
 }
 
 // ---- reserved voice pool: append a voice in place, move segments (live enrolment) ----

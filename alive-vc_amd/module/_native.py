@@ -42,6 +42,19 @@ class AliveGemm(C.Structure):
     ]
 
 
+class AliveRescoreArgs(C.Structure):     # test only (alive_debug_knn_rescore)
+    _fields_ = [
+        ("cand_val", C.c_void_p), ("cand_idx", C.c_void_p), ("P", C.c_int), ("kp", C.c_int),
+        ("s_f32", C.c_void_p), ("rows", C.c_void_p), ("norms", C.c_void_p),
+        ("M", C.c_int64), ("frames", C.c_int64), ("Tt", C.c_int64), ("idx_base", C.c_int64), ("k", C.c_int),
+        ("out_val", C.c_void_p), ("out_idx", C.c_void_p), ("frame_list", C.c_void_p), ("gate_cnt", C.c_void_p),
+        ("gate_lo", C.c_int), ("gate_hi", C.c_int), ("flag_list", C.c_void_p), ("flag_cnt", C.c_void_p),
+        ("zsig", C.c_float), ("list_len", C.c_int), ("pre_scale", C.c_float), ("sd_prior", C.c_float),
+        ("det_q", C.c_void_p), ("det_lib", C.c_void_p), ("thr_list", C.c_void_p),
+        ("collect", C.c_int), ("overflow_slack", C.c_float), ("force_fail", C.c_void_p),
+    ]
+
+
 _VP, _I, _I64, _F, _D, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); mirrors include/alive_vc.h one to one
@@ -62,6 +75,9 @@ PROTOTYPES = {
     "alive_knn_search_fp8": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP]),
     "alive_knn_search_stats": (_VP, [_I, _I, _I64, _VP]),
     "alive_debug_knn_stage_view": (_I, [_I64, _I64, _I, _I, _VP, _I]),
+    "alive_debug_knn_rescore": (_I, [C.POINTER(AliveRescoreArgs), _VP]),                              # test only
+    "alive_debug_knn_rescore_pool": (_I, [C.POINTER(AliveRescoreArgs), _VP, _VP, _VP, _VP, _I, _VP]),  # test only
+    "alive_debug_knn_pool_fields": (_I, [_VP, _I]),                                                   # test only
     "alive_knn_search_timed": (_I, [_VP, _I, _I, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_knn_search_fp8_timed": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_library_pack_fp6": (_I, [_VP, _I64, _VP, _VP]),

@@ -147,6 +147,47 @@ const int* alive_knn_search_stats(int N, int T, int64_t M, void* ws);
  *                 kernels), library rows per tile.  Candidates are [frame][P][candidates per split].  n_out >= 25. */
 int alive_debug_knn_stage_view(int64_t Tt, int64_t M, int k, int sub, int64_t* out, int n_out);
 
+/* TEST ONLY (tests/test_gpu_knn_cert.py): the rescoring kernel that ends every search, launched by the searches' own dispatcher on
+ * the caller's device buffers -- every argument the searches forward, under the names of knn_rescore_kernel (csrc/knn.hip), plus the
+ * sizes the entry validates against.  The grid covers Tt slots, four per block.  Certify mode: flag_list != NULL and collect == 0.
+ * Checked before the launch: 1 <= k <= 8, P * kp <= 1024, list_len 8 or 16, in certify mode P * kp a multiple of list_len,
+ * gate_lo == -2 (on / off word) only with a gate_cnt, otherwise gate_lo <= gate_hi, a frame_list or Tt <= frames, det_q and det_lib
+ * together, collect and thr_list only with a flag_list, a flag_cnt with every flag_list.  Host memory is not read by the kernels and
+ * device memory is not read by the entries: what the index arrays hold is the caller's to check. */
+typedef struct AliveRescoreArgs {
+    const float* cand_val;       /* [Tt][P][kp] stage scores, in units of 1 / pre_scale */
+    const int32_t* cand_idx;     /* [Tt][P][kp] library rows; -1 empty, -2 an overflowed collect list */
+    int P, kp;
+    const float* s_f32;          /* [frames][768] */
+    const float* rows;           /* [M][768] */
+    const float* norms;          /* [M] */
+    int64_t M, frames, Tt, idx_base;
+    int k;                       /* entries per frame of out_val / out_idx */
+    float* out_val;              /* [frames][k] */
+    int32_t* out_idx;
+    const int32_t* frame_list;   /* [Tt] slot -> frame, or NULL: slot = frame */
+    const int32_t* gate_cnt;
+    int gate_lo, gate_hi;
+    int32_t* flag_list;          /* [Tt] */
+    int32_t* flag_cnt;
+    float zsig;
+    int list_len;
+    float pre_scale, sd_prior;
+    const float* det_q;          /* [frames] or NULL */
+    const float* det_lib;        /* [1], pool form [voices] */
+    float* thr_list;             /* [Tt] or NULL */
+    int collect;
+    float overflow_slack;
+    const unsigned char* force_fail;   /* [frames] or NULL; not used by the pool form */
+} AliveRescoreArgs;
+int alive_debug_knn_rescore(const AliveRescoreArgs* a, void* stream);
+/* the pool search's form (certify mode only, a frame_list required): slots of a plan, frame_list its slot -> frame map (-1: padding), group g's failing
+ * slots listed at fb[grp[g][blk0] * 256 + 0 .. gfail[g] - 1], flag_cnt counts them all, flag_list only switches the certificate on. */
+int alive_debug_knn_rescore_pool(const AliveRescoreArgs* a, const int32_t* slot_grp, const int32_t* grp, int32_t* gfail, int32_t* fb,
+                                 int groups, void* stream);
+/* layout of a grp record: out[0 .. 3] = words per group, index of the voice, of the first 256-slot block, of the group's k */
+int alive_debug_knn_pool_fields(int32_t* out, int n_out);
+
 /* Measurement forms (bench.py): the same searches; ev_start / ev_stop are hipEvent_t handles (or NULL) recorded on `stream`
  * immediately before / after the first-stage scoring kernel of the whole batch -- the dominant kernel of the path. */
 int alive_knn_search_timed(const float* src, int N, int T,
