@@ -45,6 +45,12 @@ The jobs file is a JSON list; each entry:
                                                             (convert_many(pitch_track=); inference.py's -pt).  Not with
                                                             "world_pitch".  --track-lo / --track-hi / --track-band hold for the
                                                             whole run.  A jobs file without it, run without -pt, runs as before
+   "voicing": true,                                         optional, a JSON bool or {"on": 0.6, "off": 0.45, "floor_db": -60} (default:
+                                                            -vd with --voicing-on / --voicing-off / --voicing-floor): the file's f0
+                                                            is 0 on the frames whose source is not periodic (convert_many(voicing=);
+                                                            inference.py's -vd).  Not with "world_pitch".  --voicing-lo /
+                                                            --voicing-hi hold for the whole run.  A jobs file without it, run
+                                                            without -vd, runs as before
    "blend": [{"target": "a.wav", "weight": 2},              instead of "target" / "lib": a weighted mix of 1 to 4 voices, each
              {"lib": "b.pt", "weight": 1}],                 component a voice source as above (module/multistream.py blend_spec)
    "output": "a_out.wav"}                                   optional: default <outdir>/<index>_<input name>.wav
@@ -72,6 +78,7 @@ ENVELOPE_KEYS = ("envelope",)            # likewise; a loaded job carries it onl
 LIMIT_KEYS = ("limit_db",)               # taken per job too; a loaded job carries it only when it is limited
 LOUDNESS_KEYS = ("lufs",)                # likewise; a loaded job carries it only when it is normalised
 TRACK_KEYS = ("pitch_track",)            # a loaded job carries it only when it tracks: {"weight": W, "jump": J}
+VOICING_KEYS = ("voicing",)              # a loaded job carries it only when it decides: {"on": R, "off": R, "floor_db": DB}
 RANGE_KEYS = ("auto_range", "range_st")  # a loaded job carries "auto_range" only when it is on, "range_st" only when its entry has it
 
 
@@ -117,6 +124,7 @@ def build_parser():
                         help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV")
     common.add_track_arguments(parser)      # (-pt: jobs track unless their "pitch_track" says otherwise)
+    common.add_voicing_arguments(parser)    # (-vd: jobs decide unless their "voicing" says otherwise)
     return parser
 
 
@@ -229,16 +237,39 @@ def job_track(j, where, pitch_track=False, weight=common.TRACK_WEIGHT, jump=comm
     return base
 
 
+def job_voicing(j, where, voicing=False, on=common.VOICING_ON, off=common.VOICING_OFF, floor_db=common.VOICING_FLOOR_DB):
+    """an entry's "voicing" (default `voicing`): true, false or {"on": R, "off": R, "floor_db": DB} (defaults `on`, `off`, `floor_db`)
+    -> {"on": R, "off": R, "floor_db": DB} as floats, or None for a job that does not decide; ValueError otherwise, and together with
+    "world_pitch" """
+    v = j.get("voicing", bool(voicing))
+    base = dict(on=on, off=off, floor_db=floor_db)
+    if isinstance(v, dict):
+        unknown = set(v) - set(base)
+        if unknown:
+            raise ValueError(f"{where}: \"voicing\": unknown keys {sorted(unknown)} (on, off, floor_db; lo and hi are flags of the run)")
+        base.update(v)
+    elif not isinstance(v, bool):
+        raise ValueError(f"{where}: \"voicing\" must be true, false or an object with on / off / floor_db, got {v!r}")
+    o = common.voicing_options(base, where)
+    if v is False:
+        return None
+    if j.get("world_pitch", False):
+        raise ValueError(f"{where}: \"voicing\" cannot be combined with \"world_pitch\"")
+    return {key: o[key] for key in ("on", "off", "floor_db")}
+
+
 def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0,
               envelope_range_db=12.0, envelope_radius=1, auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT,
-              track_jump=common.TRACK_JUMP, lufs=None, loudness_max_db=12.0):
+              track_jump=common.TRACK_JUMP, lufs=None, loudness_max_db=12.0, voicing=False, voicing_on=common.VOICING_ON,
+              voicing_off=common.VOICING_OFF, voicing_floor_db=common.VOICING_FLOOR_DB):
     """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder; "auto_pitch": default
     `auto_pitch`); a limited job ("limit_db", default `limit_db`) also carries "limit_db", a job without a limiter does not, so a
     file without the key loads to what it did; likewise "envelope" (default `envelope`) only on a job that follows at an amount above
     0, "auto_range" (default `auto_range`) only on a job that is on, "range_st" only where the entry has it and "pitch_track"
     (default `pitch_track` at `track_weight` / `track_jump`) only on a job that tracks and "lufs" (default `lufs`) only on a job that
-    is normalised; ValueError on a malformed job, before anything
-    runs on the device"""
+    is normalised and "voicing" (default `voicing` at `voicing_on` / `voicing_off` / `voicing_floor_db`) only on a job that decides;
+    ValueError on a malformed job, before anything runs on the device"""
+    job_voicing({}, "-vd / --voicing-on / --voicing-off / --voicing-floor", voicing, voicing_on, voicing_off, voicing_floor_db)
     job_track({}, "-pt / --track-weight / --track-jump", pitch_track, track_weight, track_jump)
     job_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, lookahead_ms, hold_ms)
     job_loudness({}, "-lufs / --loudness-max-db", lufs, loudness_max_db)
@@ -257,10 +288,10 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
         if not isinstance(j, dict) or "input" not in j:
             raise ValueError(f"job {i}: an object with an \"input\" wav is required")
         unknown = (set(j) - set(JOB_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(RANGE_KEYS) - set(TRACK_KEYS)
-                   - set(LOUDNESS_KEYS))
+                   - set(LOUDNESS_KEYS) - set(VOICING_KEYS))
         if unknown:
             raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS + TRACK_KEYS + LOUDNESS_KEYS})")
+                             f"{JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS + TRACK_KEYS + LOUDNESS_KEYS + VOICING_KEYS})")
         blend = blend_sources(j, f"job {i}", rel) if "blend" in j else None
         if blend is None and j.get("target") is None and j.get("lib") is None:
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
@@ -290,6 +321,9 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
         track = job_track(j, f"job {i}", pitch_track, track_weight, track_jump)
         if track is not None:
             e["pitch_track"] = track
+        decide = job_voicing(j, f"job {i}", voicing, voicing_on, voicing_off, voicing_floor_db)
+        if decide is not None:
+            e["voicing"] = decide
         range_st = range_st_of(j, f"job {i}")
         if range_st is not None:
             e["range_st"] = range_st
@@ -349,12 +383,14 @@ def main(argv=None):
         raise SystemExit("this build runs on the MI355X only: pass -d cuda")
     try:
         tw, tj, lo, hi, band = common.track_arguments(args)             # (before anything is loaded)
+        common.voicing_arguments(args)                                  # (likewise: --voicing-lo / --voicing-hi and the defaults)
     except ValueError as e:
         raise SystemExit(str(e)) from None
     jobs = load_jobs(args.jobs, args.k, args.auto_pitch, args.limit, args.limit_lookahead, args.limit_hold, args.envelope,
                      args.envelope_floor, args.envelope_range, args.envelope_radius, args.auto_range, args.pitch_track, tw, tj,
-                     args.lufs, args.loudness_max_db)
+                     args.lufs, args.loudness_max_db, args.voicing, args.voicing_on, args.voicing_off, args.voicing_floor)
     tracked = any("pitch_track" in j for j in jobs)
+    deciding = any("voicing" in j for j in jobs)
     on_auto = any(j["auto_pitch"] for j in jobs)
     ranged = any("auto_range" in j for j in jobs)
     auto = on_auto or ranged                            # only then are the voices' registers (and ranges) measured or declared
@@ -416,7 +452,9 @@ def main(argv=None):
                              auto_pitch=[j["auto_pitch"] for j in jobs] if on_auto else False,
                              **(dict(auto_range=["auto_range" in j for j in jobs]) if ranged else {}),
                              **(dict(pitch_track=[dict(j["pitch_track"], lo=lo, hi=hi, band=band) if "pitch_track" in j else None
-                                                  for j in jobs]) if tracked else {}), chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
+                                                  for j in jobs]) if tracked else {}),
+                             **(dict(voicing=[dict(j["voicing"], lo=args.voicing_lo, hi=args.voicing_hi) if "voicing" in j else None
+                                              for j in jobs]) if deciding else {}), chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)
     for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
         if job.get("envelope"):                                         # at 16 kHz, against the source the converter saw

@@ -87,6 +87,7 @@ def build_parser():
                         help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV (this build only)")
     common.add_track_arguments(parser)
+    common.add_voicing_arguments(parser)
     return parser
 
 
@@ -112,6 +113,12 @@ def main(argv=None):
         if args.world_pitch_estimation:
             raise SystemExit("-pt cannot be combined with -wpe: the tracker decodes the f0 estimator's class scores")
         track = dict(zip(("weight", "jump", "lo", "hi", "band"), common.track_arguments(args)))      # (before anything is loaded)
+    try:
+        voicing = common.voicing_arguments(args)                             # (before anything is loaded)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if voicing is not None and args.world_pitch_estimation:
+        raise SystemExit("-vd cannot be combined with -wpe: WORLD makes its own voicing decision")
 
     PE, CE, Dec = F0Estimator().to(device), ContentEncoder().to(device), Decoder().to(device)
     PE.load_state_dict(torch.load(args.f0_estimator_path, map_location=device))
@@ -145,7 +152,8 @@ def main(argv=None):
         out = conv.convert(wf, chunk=args.chunk, k=args.k, alpha=args.alpha, pitch_shift=args.pitch,
                            world_pitch=bool(args.world_pitch_estimation), intonation=args.intonation, f0_rate=args.f0_rate, window_batch=args.window_batch,
                            trim_context=not args.no_trim_context,
-                           share_overlap=None if args.no_share_overlap else "auto", **({} if track is None else dict(pitch_track=track)))
+                           share_overlap=None if args.no_share_overlap else "auto", **({} if track is None else dict(pitch_track=track)),
+                           **({} if voicing is None else dict(voicing={k: voicing[k] for k in common.VOICING_KEYS})))
         if args.envelope > 0:                     # at 16 kHz, against the normalised mono source the converter saw
             out = follow_envelope(out, wf, None, args.envelope, *env)
         out = audio_io.resample(out, 16000, sr, post_gain_db=args.gain)            # resample, then gain (:136-137)

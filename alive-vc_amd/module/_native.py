@@ -174,6 +174,8 @@ PROTOTYPES = {
     "alive_f0_logits": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP]),
     "alive_f0_track_workspace_bytes": (_SZ, [_I, _I, _I]),
     "alive_f0_track_rows": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "alive_voicing_workspace_bytes": (_SZ, [_I, _I]),
+    "alive_voicing_rows": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_decoder_workspace_bytes": (_SZ, [_I, _I]),
     "alive_decoder_forward": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "alive_decoder_forward_range": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP]),

@@ -5,6 +5,7 @@
   compute_f0(wf, sample_rate=16000, segment_size=320) <- module/common.py:133-137
   compute_f0_rows(wf, row_on)                         compute_f0 of the rows a device mask switches on (the batched paths)
   pitch_track(lo=50, hi=1100, band=2.0, device=)      the tables of the pitch tracker (F0Estimator.estimate(track=); no counterpart)
+  voicing_options(v, where="")                        the checked settings of the voicing decision (ops.voicing_rows_; no counterpart)
 
 runs on the MI355X through libalive_vc.so: fp6- (or fp8- / bf16-) MFMA candidate scoring with
 LDS-staged top-k' lists, exact fp32 rescoring, gather-mean-blend.  The library
@@ -608,6 +609,86 @@ def track_arguments(args):
     pitch_track_tables(args.track_lo, args.track_hi, args.track_band)
     return (track_param("--track-weight", args.track_weight), track_param("--track-jump", args.track_jump), int(args.track_lo),
             int(args.track_hi), float(args.track_band))
+
+
+# ---- voicing: f0 = 0 on aperiodic frames, by a correlation detector on the 16 kHz source (csrc/voicing.hip, DESIGN.md "Voicing") ----
+VOICING_ON, VOICING_OFF, VOICING_FLOOR_DB = 0.6, 0.45, -60.0
+VOICING_LO, VOICING_HI, VOICING_WINDOW_MS, VOICING_BRIDGE, VOICING_MIN_RUN = 50, 500, 40, 1, 2
+VOICING_MAX_WINDOW, VOICING_MAX_LAG = 4096, 1600      # ALIVE_VOICING_MAX_WINDOW, ALIVE_VOICING_MAX_LAG: a frame's samples fit 64 KB of LDS
+VOICING_KEYS = ("on", "off", "floor_db", "lo", "hi", "window_ms", "bridge", "min_run")
+
+
+def voicing_floor_e(floor_db, hop=320):
+    """the silence floor as the energy of one frame of int16-grid samples: 10^(dB / 10) * hop * 2^30 in float64"""
+    return 10.0 ** (float(floor_db) / 10.0) * float(hop) * float(2 ** 30)
+
+
+def voicing_options(v, where=""):
+    """voicing=None | False | True | dict(on=, off=, floor_db=, lo=, hi=, window_ms=, bridge=, min_run=) -> None, or the dict with
+    every key filled in and checked, plus what the kernel takes: lag_lo = ceil(16000 / hi), lag_hi = floor(16000 / lo),
+    W = round(16 window_ms) and floor_e = voicing_floor_e(floor_db)"""
+    import math
+    what = f"{where}: voicing" if where else "voicing"
+    if v is None or v is False:
+        return None
+    if v is True:
+        v = {}
+    if not isinstance(v, dict):
+        raise ValueError(f"{what}: expected None, a bool or a dict of {' / '.join(VOICING_KEYS)}, got {v!r}")
+    unknown = set(v) - set(VOICING_KEYS)
+    if unknown:
+        raise ValueError(f"{what}: unknown keys {sorted(unknown)} ({', '.join(VOICING_KEYS)})")
+    o = dict(on=VOICING_ON, off=VOICING_OFF, floor_db=VOICING_FLOOR_DB, lo=VOICING_LO, hi=VOICING_HI, window_ms=VOICING_WINDOW_MS,
+             bridge=VOICING_BRIDGE, min_run=VOICING_MIN_RUN)
+    o.update(v)
+    for key in ("on", "off", "floor_db", "lo", "hi", "window_ms"):
+        x = o[key]
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
+            raise ValueError(f"{what}: {key} must be a finite number, got {x!r}")
+    for key in ("bridge", "min_run"):
+        x = o[key]
+        if isinstance(x, bool) or not isinstance(x, int) or x < 0:
+            raise ValueError(f"{what}: {key} must be an integer number of frames >= 0, got {x!r}")
+    if not 0.0 < o["off"] <= o["on"] <= 1.0:
+        raise ValueError(f"{what}: needs 0 < off <= on <= 1, got off {o['off']!r}, on {o['on']!r}")
+    if not 0.0 < o["lo"] < o["hi"] <= 4000.0:
+        raise ValueError(f"{what}: needs 0 < lo < hi <= 4000 (Hz), got lo {o['lo']!r}, hi {o['hi']!r}")
+    lag_lo, lag_hi = int(math.ceil(16000.0 / o["hi"])), int(math.floor(16000.0 / o["lo"]))
+    if lag_lo > lag_hi:
+        raise ValueError(f"{what}: no whole lag of the 16 kHz signal lies between lo {o['lo']!r} and hi {o['hi']!r} Hz")
+    if lag_hi > VOICING_MAX_LAG:
+        raise ValueError(f"{what}: lo {o['lo']!r} Hz is a lag of {lag_hi} samples, at most {VOICING_MAX_LAG} (lo >= 10 Hz)")
+    W = int(round(16.0 * o["window_ms"]))
+    if not 1 <= W <= VOICING_MAX_WINDOW:
+        raise ValueError(f"{what}: window_ms {o['window_ms']!r} is {W} samples, needs 1 <= W <= {VOICING_MAX_WINDOW}")
+    o.update(on=float(o["on"]), off=float(o["off"]), floor_db=float(o["floor_db"]), lag_lo=lag_lo, lag_hi=lag_hi, W=W,
+             floor_e=voicing_floor_e(o["floor_db"]))
+    return o
+
+
+def add_voicing_arguments(parser):
+    """the voicing decision's flags, the same in every CLI that takes them: -vd and --voicing-on / -off / -floor / -lo / -hi"""
+    parser.add_argument('-vd', '--voicing', action='store_true',
+                        help="voicing decision: f0 = 0 on the frames whose 16 kHz source is not periodic (breath, fricatives, pauses), "
+                             "by a correlation detector of its own, after the f0 estimator or -pt and before the pitch transform "
+                             "(default: off; not with -wpe, which decides for itself; this build only)")
+    parser.add_argument('--voicing-on', default=VOICING_ON, type=float, metavar="R",
+                        help=f"voicing decision: a frame whose best normalised correlation reaches this turns voiced (default {VOICING_ON})")
+    parser.add_argument('--voicing-off', default=VOICING_OFF, type=float, metavar="R",
+                        help=f"voicing decision: a frame under this turns unvoiced; between the two the state stays (default {VOICING_OFF})")
+    parser.add_argument('--voicing-floor', default=VOICING_FLOOR_DB, type=float, metavar="DB",
+                        help=f"voicing decision: a 20 ms frame whose level is under this is unvoiced (dBFS, default {VOICING_FLOOR_DB})")
+    parser.add_argument('--voicing-lo', default=VOICING_LO, type=float, metavar="HZ",
+                        help=f"voicing decision: the lowest pitch whose period is tried (default {VOICING_LO})")
+    parser.add_argument('--voicing-hi', default=VOICING_HI, type=float, metavar="HZ",
+                        help=f"voicing decision: the highest pitch whose period is tried (default {VOICING_HI})")
+
+
+def voicing_arguments(args):
+    """the parsed flags -> the checked options (voicing_options) when -vd is set, else None; refuses before anything is loaded"""
+    o = voicing_options(dict(on=args.voicing_on, off=args.voicing_off, floor_db=args.voicing_floor, lo=args.voicing_lo,
+                             hi=args.voicing_hi), "-vd")
+    return o if args.voicing else None
 
 
 def linear_resize(x, size):

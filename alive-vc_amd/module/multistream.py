@@ -187,6 +187,20 @@ world_pitch on one session.  Class 0 is not a state: a tracked row never emits f
 frames of each ring the tracker moved.  The defaults (1.0, 12.0, 2.0 semitones, 50 .. 1100 Hz) are design choices in logit units: with
 no trained weights, what tracking does to perceived quality is unmeasured.
 
+Voicing: the estimator's argmax never says "unvoiced" (class 0 is not trained), so the oscillator drives its harmonics through every
+breath, fricative and pause, and the followers learn a register from them.  A converter built with voicing=True (csrc/voicing.hip)
+has the f0 branch run a periodicity detector of its own on the 16 kHz ring, after the estimator or the tracker and before the WORLD
+select, the followers and the transform: per frame the best normalised cross-correlation r over the lags of voicing_lo .. voicing_hi Hz
+in a window of voicing_window_ms, on samples quantised to the int16 grid so that every sum is an exact integer (tools/voicing_ref.py
+restates it bit for bit); per row a hysteresis between the session's voicing_on and voicing_off, a silence floor voicing_floor_db,
+gaps of at most voicing_bridge frames bridged and runs under voicing_min_run frames dropped; the f0 of every other frame becomes 0,
+which everything downstream already reads as unvoiced.  Sessions opened or set with voicing=True decide; toggling and retuning never
+re-capture.  The detector is stateless over the ring, like the tracker: nothing is carried across ticks, the bf16 repeat or a capture.
+A converter built without voicing allocates nothing, launches exactly what it did and refuses voicing=True; not together with
+world_pitch on one session (WORLD decides for itself).  voicing_state() reads back, per slot, the voiced frames of the ring, the
+frames set to 0 and r of the emitted centre frame.  The defaults (0.6, 0.45, -60 dB, 50 .. 500 Hz, 40 ms, 1, 2) are design choices:
+with no trained weights, what the decision does to perceived quality is unmeasured.
+
 Loudness: every path leaves the converted voice at the level of the library rows it selected.  measure_loudness / normalize_loudness
 (csrc/loudness.hip) are the integrated loudness of ITU-R BS.1770-4 / EBU R 128 for one channel -- K-weighting, 400-ms blocks every 100
 ms, the absolute gate at -70 LUFS and the relative one 10 LU below the gated mean -- and the one gain per row that brings it to a
@@ -824,16 +838,24 @@ def _track_call(pitch_track, world_pitch, device):
     return dict(track=common.pitch_track(o["lo"], o["hi"], o["band"], device), track_weight=o["weight"], track_jump=o["jump"])
 
 
-def measure_register(f0_estimator, wf16, world_pitch=False, pitch_track=None):
+def measure_register(f0_estimator, wf16, world_pitch=False, pitch_track=None, voicing=None):
     """the register (sum of voiced pitch, voiced frames) of 16 kHz audio wf16 [1, L] on the device, as host floats: the f0 estimator's
     f0 of its spectrogram (world_pitch: WORLD's f0 of the audio) through alive_pitch_stats2_groups, one group, every frame: a
     Register, the 2-tuple it always was (bitwise alive_pitch_stats_groups') with the sum of squares as `.sumsq`.  One host read: for
     enrolment, never inside a tick.  pitch_track (True, or dict(weight=, jump=, lo=, hi=, band=)): the register and the range are measured
-    on the tracked contour (F0Estimator.estimate(track=)), as a session with pitch_track hears its source."""
+    on the tracked contour (F0Estimator.estimate(track=)), as a session with pitch_track hears its source.  voicing (True, or a dict
+    of common.voicing_options' keys): on the frames the voicing decision finds voiced (ops.voicing_rows_), as a session with voicing
+    hears its source; not together with world_pitch."""
     track = _track_call(pitch_track, world_pitch, wf16.device)
+    voicing = common.voicing_options(voicing)
+    if voicing is not None and world_pitch:
+        raise ValueError("voicing cannot be combined with world_pitch: WORLD makes its own voicing decision")
 
     def f0():
-        return compute_f0(wf16) if world_pitch else f0_estimator.estimate(spectrogram(wf16), **track)
+        if world_pitch:
+            return compute_f0(wf16)
+        f = f0_estimator.estimate(spectrogram(wf16), **track)
+        return f if voicing is None else ops.voicing_rows_(f, wf16.contiguous(), voicing)
     f = ops.Fp16Guard().run(f0)
     first = torch.tensor([0, f.shape[0]], dtype=torch.int32, device=f.device)
     s, c, q = pitch_stats2_groups(f, first)[0].tolist()
@@ -841,13 +863,13 @@ def measure_register(f0_estimator, wf16, world_pitch=False, pitch_track=None):
 
 
 def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="cuda", f0_estimator=None, world_pitch=False,
-                codebook=None, codebook_iters=10, codebook_seed=0, pitch_track=None):
+                codebook=None, codebook_iters=10, codebook_seed=0, pitch_track=None, voicing=None):
     """A voice's tokens as realtime_inference.py builds its library, as strided [768, m] parts and without a copy: the target
     utterance `wav` [channels, samples] at `sr` Hz -- resampled to 16 kHz, peak-normalised, first channel, content_encoder(
     spectrogram(.)), every `every`-th frame (a column-strided view of the encoder's output) -- then the tokens of `lib` (a voice
     library file, or its tokens [1, 768, M] / [768, M]).  The encoder runs under ops.Fp16Guard, as generate_voice_library.py's.
     f0_estimator= (auto pitch): returns (parts, register) instead, the register measured on the same 16 kHz audio the encoder saw
-    (measure_register; world_pitch: with WORLD's f0; pitch_track: on the tracked contour), None without a target wav.  Without it
+    (measure_register; world_pitch: with WORLD's f0; pitch_track: on the tracked contour; voicing: on the voiced frames), None without a target wav.  Without it
     the call is what it was.
     codebook=SIZE: the parts are condensed together, once, to one part of SIZE centroid rows (module/codebook.py build_codebook with
     codebook_iters and codebook_seed; a voice of SIZE rows or fewer stays as it is); the register is measured on the audio as before."""
@@ -859,7 +881,7 @@ def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="c
         feats = ops.Fp16Guard().run(lambda: content_encoder(spectrogram(wf[:1])))
         parts.append(feats[0][:, ::every])
         if f0_estimator is not None:
-            register = measure_register(f0_estimator, wf[:1].contiguous(), world_pitch, pitch_track)
+            register = measure_register(f0_estimator, wf[:1].contiguous(), world_pitch, pitch_track, voicing)
     if lib is not None:
         if isinstance(lib, (str, bytes)) or hasattr(lib, "__fspath__"):
             VL = VoiceLibrary().to(device)
@@ -878,7 +900,7 @@ def voice_parts(content_encoder, wav=None, sr=None, lib=None, every=4, device="c
 
 
 def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False, f0_estimator=None,
-                world_pitch=False, codebook=None, codebook_iters=10, codebook_seed=0, pitch_track=None):
+                world_pitch=False, codebook=None, codebook_iters=10, codebook_seed=0, pitch_track=None, voicing=None):
     """enrol_voice as a generator: the utterance is encoded once, then each next() appends one piece -- `add` for the first, `extend`
     for the rest -- and yields the voice's row count so far, so that a server can put a tick between the pieces.  If a piece is
     refused the voice is removed again (when no session holds it yet) and the error propagates.  f0_estimator=: the utterance's
@@ -894,7 +916,7 @@ def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
         parts = voice_parts(content_encoder, wav, sr, lib, every, pool.device, **cb)
     else:
         parts, register = voice_parts(content_encoder, wav, sr, lib, every, pool.device, f0_estimator, world_pitch,
-                                      pitch_track=pitch_track, **cb)
+                                      pitch_track=pitch_track, voicing=voicing, **cb)
     total = sum(int(t.shape[1]) for t in parts)
     step = total if max_frames is None else int(max_frames)
     if compact and pool.largest_hole < min(step, total) <= pool.free_rows:
@@ -931,7 +953,7 @@ def enrol_steps(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
 
 
 def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_frames=None, compact=False, f0_estimator=None,
-                world_pitch=False, codebook=None, codebook_iters=10, codebook_seed=0, pitch_track=None):
+                world_pitch=False, codebook=None, codebook_iters=10, codebook_seed=0, pitch_track=None, voicing=None):
     """Enrol a voice into a reserved pool from audio, while sessions run on the pool's other voices: the recipe of voice_parts
     (multistream_inference.voice_tokens', under ops.Fp16Guard), appended through the strided alive_pool_append -- the encoder's
     output is never copied or concatenated.  The voice's rows are bitwise those of voice_tokens followed by `add`.
@@ -941,13 +963,13 @@ def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
     is encoded once and its tokens are appended piece by piece, which is bitwise one call for any max_frames (a row and its norm
     depend on the row's own token alone).  compact=True: compact the pool first when the first piece fits its free rows but none
     of its holes.  f0_estimator= (auto pitch): the voice also gets its register, measured on the same audio (voice_parts; with
-    pitch_track= on the tracked contour).
+    pitch_track= on the tracked contour, with voicing= on the voiced frames).
     codebook=SIZE (with codebook_iters, codebook_seed): the voice goes in as its SIZE-row codebook (module/codebook.py), bitwise
     `add(name, build_codebook(tokens, SIZE))`; `compact=` is about the pool's holes and has nothing to do with it.
     Returns the voice's row count."""
     rows = 0
     for rows in enrol_steps(pool, name, content_encoder, wav, sr, lib, every, max_frames, compact, f0_estimator, world_pitch,
-                            codebook, codebook_iters, codebook_seed, pitch_track):
+                            codebook, codebook_iters, codebook_seed, pitch_track, voicing):
         pass
     return rows
 
@@ -1941,7 +1963,7 @@ def db_scale(db):
 
 _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold",
            "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope", "conceal", "intonation", "auto_range",
-           "pitch_track", "track_weight", "track_jump", "lufs")
+           "pitch_track", "track_weight", "track_jump", "lufs", "voicing", "voicing_on", "voicing_off", "voicing_floor_db")
 
 
 class MultiStreamConverter:
@@ -1955,6 +1977,7 @@ class MultiStreamConverter:
     conceal = False                    # (likewise: whether lost chunks are concealed in front of the ring push; needs sparse)
     pitch_track = False                # (likewise: whether the f0 branch stores the class scores and carries the tracker kernel)
     loud = False                       # (likewise: whether the tick carries the loudness kernel; loudness() is the read-back)
+    voicing = False                    # (likewise: whether the f0 branch carries the voicing kernels; voicing_state() is the read-back)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
@@ -1963,7 +1986,14 @@ class MultiStreamConverter:
                  envelope_range_db=12.0, envelope_radius=1, conceal=False, conceal_hold_ms=10.0, conceal_fade_ms=50.0,
                  conceal_recover_ms=5.0, pitch_range=False, pitch_range_max=2.0, pitch_track=False, track_lo=50, track_hi=1100,
                  track_band=2.0, loudness=False, loudness_half_life=3.0, loudness_prior=1.0, loudness_gate_lufs=LOUDNESS_GATE_LUFS,
-                 loudness_max_db=12.0, loudness_slew_db=6.0):
+                 loudness_max_db=12.0, loudness_slew_db=6.0, voicing=False, voicing_lo=common.VOICING_LO, voicing_hi=common.VOICING_HI,
+                 voicing_window_ms=common.VOICING_WINDOW_MS, voicing_bridge=common.VOICING_BRIDGE,
+                 voicing_min_run=common.VOICING_MIN_RUN):
+        if not isinstance(voicing, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: voicing must be a bool, got {voicing!r}")
+        if voicing:                        # (checked before anything is built)
+            voicing_opts = common.voicing_options(dict(lo=voicing_lo, hi=voicing_hi, window_ms=voicing_window_ms, bridge=voicing_bridge,
+                                                       min_run=voicing_min_run), "MultiStreamConverter")
         if not isinstance(loudness, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: loudness must be a bool, got {loudness!r}")
         if loudness:                       # (checked before anything is built)
@@ -2152,6 +2182,19 @@ class MultiStreamConverter:
             self.track_jump = torch.full((B,), common.TRACK_JUMP, dtype=torch.float64, device=dev)
             self.track_changed = torch.zeros(B, dtype=torch.int32, device=dev)
             self._track_bufs = {}
+        # voicing: the two voicing kernels are part of the f0 branch (captured once); per row, voicing_on switches the decision and
+        # the thresholds are the session's.  No state: the detector looks at the whole ring again every tick
+        self.voicing = bool(voicing)
+        if self.voicing:
+            self._voicing = voicing_opts
+            f64 = dict(dtype=torch.float64, device=dev)
+            self.voicing_on = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.voicing_thr_on = torch.full((B,), common.VOICING_ON, **f64)
+            self.voicing_thr_off = torch.full((B,), common.VOICING_OFF, **f64)
+            self.voicing_floor_e = torch.full((B,), common.voicing_floor_e(common.VOICING_FLOOR_DB), **f64)
+            self._voicing_out = dict(r=torch.zeros(B, self.frames, **f64),
+                                     voiced=torch.zeros(B, self.frames, dtype=torch.int32, device=dev),
+                                     changed=torch.zeros(B, dtype=torch.int32, device=dev))
         # gate: the two gate kernels are part of the tick (captured once); per row, gate_on switches the session's gate, and the tick
         # reads seg_len_eff / world_eff / follow where it read seg_len / world_on / emit.  gate_state is the session's, like phi
         self.gate = bool(gate)
@@ -2462,6 +2505,30 @@ class MultiStreamConverter:
                              "class scores")
         return int(bool(on)), w, j
 
+    def _session_voicing(self, slot, p):
+        """a session's voicing settings -> (on, thr_on, thr_off, floor_e), checked against the converter"""
+        on = p.get("voicing", False)
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"slot {slot}: voicing must be a bool, got {on!r}")
+        o = common.voicing_options(dict(on=p.get("voicing_on", common.VOICING_ON), off=p.get("voicing_off", common.VOICING_OFF),
+                                        floor_db=p.get("voicing_floor_db", common.VOICING_FLOOR_DB)), f"slot {slot}")
+        if on and not self.voicing:
+            raise ValueError(f"slot {slot}: voicing=True needs a converter built with MultiStreamConverter(..., voicing=True)")
+        if on and p.get("world_pitch", False):
+            raise ValueError(f"slot {slot}: voicing cannot be combined with world_pitch: WORLD makes its own voicing decision")
+        return int(bool(on)), o["on"], o["off"], o["floor_e"]
+
+    def voicing_state(self):
+        """the voicing decision of the latest tick, a list of B triples (voiced frames of the ring, frames whose f0 was set to 0, r of
+        the centre frame of the emitted span); (0, 0, 0.0) for a slot that does not decide (or is closed).  One host read"""
+        if not self.voicing:
+            raise ValueError("voicing_state needs a converter built with MultiStreamConverter(..., voicing=True)")
+        o = self._voicing_out
+        centre = min((self.begin_of_output + self.end_of_output) // 2 // 320, self.frames - 1)      # (the span is in 16 kHz samples)
+        rows = torch.stack([o["voiced"].sum(dim=1).double(), o["changed"].double(), o["r"][:, centre]], dim=1).tolist()
+        return [(int(v), int(c), r) if self.is_open[b] and self.params[b].get("voicing", False) else (0, 0, 0.0)
+                for b, (v, c, r) in enumerate(rows)]
+
     def pitch_track_changed(self):
         """how many frames of each slot's ring the tracker moved off the per-frame argmax in the latest tick, a list of B ints; 0 for
         a slot that does not track (or is closed).  One host read"""
@@ -2492,6 +2559,7 @@ class MultiStreamConverter:
         env = self._session_envelope(slot, p)
         con = self._session_conceal(slot, p, rate)
         track = self._session_track(slot, p)
+        voicing = self._session_voicing(slot, p)
         loud = self._session_loudness(slot, p, rate)
         names, weights = blend_spec(p["voice"], self.pool, k, self.S)
         world = p["world_pitch"]
@@ -2544,6 +2612,10 @@ class MultiStreamConverter:
             self.track_on[slot], self.track_weight[slot], self.track_jump[slot] = track
             if not track[0]:
                 self.track_changed[slot] = 0
+        if self.voicing:
+            self.voicing_on[slot], self.voicing_thr_on[slot], self.voicing_thr_off[slot], self.voicing_floor_e[slot] = voicing
+            if not voicing[0]:
+                self._voicing_clear(slot)
         if self.auto_pitch:
             self.auto_on[slot] = int(bool(auto))
             self.target[slot] = target if auto else 0.0
@@ -2568,6 +2640,11 @@ class MultiStreamConverter:
         if self.conceal:
             self.conceal_on[slot], self._conceal_host[slot] = con[0], con[0]
             self._conceal_consts[:, slot] = torch.tensor(con[1], dtype=torch.int32)
+
+    def _voicing_clear(self, slot):
+        """the read-back rows of a slot that does not decide (the kernels leave the rows of such a slot untouched)"""
+        o = self._voicing_out
+        o["r"][slot], o["voiced"][slot], o["changed"][slot] = 0.0, 0, 0
 
     def _write_segments(self, slot, names):
         """the slot's rows of seg_lo / seg_len from where its voices lie in the pool now"""
@@ -2635,7 +2712,8 @@ class MultiStreamConverter:
     def open(self, slot, voice, pitch=0.0, f0_rate=1.0, alpha=0.0, gain=0.0, input_gain=0.0, rate=None, world_pitch=False, k=None,
              auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0,
              limit_hold_ms=20.0, envelope=0.0, conceal=None, intonation=1.0, auto_range=False, pitch_track=False, track_weight=1.0,
-             track_jump=12.0, lufs=None):
+             track_jump=12.0, lufs=None, voicing=False, voicing_on=common.VOICING_ON, voicing_off=common.VOICING_OFF,
+             voicing_floor_db=common.VOICING_FLOOR_DB):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
@@ -2662,6 +2740,10 @@ class MultiStreamConverter:
         the estimator's class scores of its ring instead of their per-frame argmax, at track_weight per semitone moved inside the
         converter's band and track_jump for any other move (both >= 0, in the units of the scores); the followers and the transform see
         the tracked contour.
+        voicing=True (needs a voicing=True converter; not together with world_pitch): the f0 of the frames of the session's ring that
+        are not periodic becomes 0, after the estimator or the tracker and before the followers and the transform: a frame turns voiced
+        when its best normalised correlation reaches voicing_on and unvoiced under voicing_off (0 < off <= on <= 1), and a frame under
+        voicing_floor_db dBFS is unvoiced whatever its correlation.
         lufs (needs a loudness=True converter): the session's loudness target in LUFS, -70 < lufs <= 0 (None: the session's level is
         left alone): what the session emits is brought to it by a running BS.1770 loudness and a slewed gain, ahead of the limiter"""
         slot = self._slot(slot)
@@ -2673,7 +2755,8 @@ class MultiStreamConverter:
                  k=k, auto_pitch=auto_pitch, gate_db=gate_db, gate_hold=gate_hold, crossfade_ms=crossfade_ms, limit_db=limit_db,
                  limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms, envelope=envelope, conceal=conceal,
                  intonation=intonation, auto_range=auto_range, pitch_track=pitch_track, track_weight=track_weight,
-                 track_jump=track_jump, lufs=lufs)
+                 track_jump=track_jump, lufs=lufs, voicing=voicing, voicing_on=voicing_on, voicing_off=voicing_off,
+                 voicing_floor_db=voicing_floor_db)
         self._apply(slot, p, rate)                            # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -2696,7 +2779,7 @@ class MultiStreamConverter:
 
     def set(self, slot, **params):
         """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
-        intonation, auto_range, pitch_track, track_weight, track_jump, gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms,
+        intonation, auto_range, pitch_track, track_weight, track_jump, voicing, voicing_on, voicing_off, voicing_floor_db, gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms,
         limit_hold_ms, envelope, conceal, lufs; the gate's state, the saved tail, the running loudness with its gain and the
         limiter's history are kept: a longer crossfade fades over what the tail holds this tick and in full from the next, and a
         limiter switched on or retuned sees the required gains of the samples already emitted).
@@ -2733,6 +2816,11 @@ class MultiStreamConverter:
         if self.pitch_track:
             self.track_on[slot], self.track_changed[slot] = 0, 0
             self.track_weight[slot], self.track_jump[slot] = common.TRACK_WEIGHT, common.TRACK_JUMP
+        if self.voicing:
+            self.voicing_on[slot] = 0
+            self.voicing_thr_on[slot], self.voicing_thr_off[slot] = common.VOICING_ON, common.VOICING_OFF
+            self.voicing_floor_e[slot] = common.voicing_floor_e(common.VOICING_FLOOR_DB)
+            self._voicing_clear(slot)
         if self.auto_pitch:
             self.auto_on[slot] = 0
             self.target[slot] = 0.0
@@ -2844,7 +2932,8 @@ class MultiStreamConverter:
         """realtime.f0_on_side_stream with the per-row pitch transform.  world_pitch: after the estimator, the masked WORLD f0 of
         the 16-kHz rings `data` (rows off: no work), selected per row, then the transform at the effective rates.  pitch_track: the
         estimator stores its class scores, their argmax goes to the buffer as without it, and the tracker overwrites the rows that are
-        on -- before the WORLD select, the followers and the transform"""
+        on -- before the WORLD select, the followers and the transform.  voicing: after the estimator or the tracker, the f0 of the
+        unvoiced frames of the rows that are on becomes 0, again before the WORLD select, the followers and the transform"""
         def body(buf):
             if self.pitch_track:
                 f0 = self.pe.estimate(spec, out=buf, track=self._track, track_on=self.track_on, track_weight=self.track_weight,
@@ -2852,6 +2941,9 @@ class MultiStreamConverter:
                                       changed=self.track_changed)
             else:
                 f0 = self.pe.estimate(spec, out=buf)
+            if self.voicing:                                  # the rows that are on: f0 = 0 where their ring is not periodic
+                ops.voicing_rows_(f0, data, self._voicing, self.voicing_on, self.voicing_thr_on, self.voicing_thr_off,
+                                  self.voicing_floor_e, self._voicing_out)
             rate = self.f0_rate
             if self.world_pitch:
                 world_on = self.world_eff if self.gate else (self.world_tick if self.sparse else self.world_on)

@@ -265,6 +265,47 @@ def pitch_transform_(f0, mode, f0_rate=1.0, pitch_shift=0.0, intonation=1.0):
     return f0
 
 
+_voicing_ws = nat.Workspace()
+
+
+def voicing_rows_(f0, x, opts, on=None, thr_on=None, thr_off=None, floor_e=None, out=None, length=None, hop=320):
+    """alive_voicing_rows in place on f0 [N, 1, T] (or [N, T]): +0 on the frames of x [N, ld] (the 16 kHz rows the networks see, valid
+    up to `length`, default ld) that the correlation detector of csrc/voicing.hip finds unvoiced.  opts: common.voicing_options(...).
+    on: device int32 [N] (None: every row); thr_on / thr_off / floor_e: device float64 [N] (None: opts' on / off / floor_db for every
+    row); out: a dict that may hold the device arrays "r" (float64 [N, T]), "lag", "voiced" (int32 [N, T]) and "changed" (int32 [N]).
+    No host synchronisation and, with device arrays, no allocation once the stream's workspace exists: capturable"""
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"voicing: x must be a contiguous fp32 [N, ld] tensor, got {tuple(x.shape)}")
+    n, ld = x.shape
+    t = f0.shape[-1]
+    if f0.dtype != torch.float32 or not f0.is_contiguous() or f0.shape[0] != n or f0.numel() != n * t:
+        raise ValueError(f"voicing: f0 must be a contiguous fp32 [{n}, 1, T] tensor, got {tuple(f0.shape)}")
+    per_row = []
+    for name, v, key in (("thr_on", thr_on, "on"), ("thr_off", thr_off, "off"), ("floor_e", floor_e, "floor_e")):
+        if v is None:
+            v = torch.full((n,), float(opts[key]), dtype=torch.float64, device=x.device)
+        elif v.dtype != torch.float64 or v.numel() != n or not v.is_contiguous():
+            raise ValueError(f"voicing: {name} must be a contiguous float64 [{n}] device array")
+        per_row.append(v)
+    out = out or {}
+    unknown = set(out) - {"r", "lag", "voiced", "changed"}
+    if unknown:
+        raise ValueError(f"voicing: unknown outputs {sorted(unknown)} (r, lag, voiced, changed)")
+    for name, v, dtype, count in (("on", on, torch.int32, n), ("r", out.get("r"), torch.float64, n * t),
+                                  ("lag", out.get("lag"), torch.int32, n * t), ("voiced", out.get("voiced"), torch.int32, n * t),
+                                  ("changed", out.get("changed"), torch.int32, n)):
+        if v is not None and (v.dtype != dtype or v.numel() != count or not v.is_contiguous()):
+            raise ValueError(f"voicing: {name} must be a contiguous {dtype} device array of {count} elements")
+    L = nat.lib()
+    ws = _voicing_ws.get(L.alive_voicing_workspace_bytes(n, t), x.device)
+    nat.check(L.alive_voicing_rows(nat.ptr(x), n, ld, ld if length is None else int(length), int(hop), t, opts["lag_lo"],
+                                   opts["lag_hi"], opts["W"], opts["min_run"], opts["bridge"], nat.ptr(on), nat.ptr(per_row[0]),
+                                   nat.ptr(per_row[1]), nat.ptr(per_row[2]), nat.ptr(f0), t, nat.ptr(out.get("r")),
+                                   nat.ptr(out.get("lag")), nat.ptr(out.get("voiced")), nat.ptr(out.get("changed")), nat.ptr(ws),
+                                   nat.stream()), "alive_voicing_rows")
+    return f0
+
+
 def _out_like(x, out):
     """the output of a FilterBlock call: a new tensor, or the caller's (a test's, pre-filled)"""
     if out is None:

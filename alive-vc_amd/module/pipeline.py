@@ -138,7 +138,7 @@ class Converter:
         return cache[key]
 
     def features(self, windows, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, frames=None, out=None, world_pitch=False,
-                 pitch_track=None):
+                 pitch_track=None, voicing=None):
         """spectrogram -> f0 (+ per-window pitch transform) and content features   (inference.py:112-128).
         frames = (lo, hi): content features are only needed on [lo, hi) (context trimming): the encoder runs on that range
         plus its own receptive field; the other frames come back as zeros.  f0 always covers the whole window (the pitch
@@ -146,7 +146,13 @@ class Converter:
         world_pitch: f0 is WORLD's DIO + StoneMask of each whole window (common.compute_f0, reference inference.py:113-114) and the
         f0 estimator does not run.
         pitch_track (common.track_options): the f0 of each whole window is the Viterbi path over the estimator's class scores
-        (F0Estimator.estimate(track=), csrc/f0_track.hip) instead of their per-frame argmax, before the pitch transform."""
+        (F0Estimator.estimate(track=), csrc/f0_track.hip) instead of their per-frame argmax, before the pitch transform.
+        voicing (common.voicing_options): the f0 of the frames of each whole window that the correlation detector finds unvoiced
+        becomes 0 (ops.voicing_rows_, csrc/voicing.hip), after the estimator or the tracker and before the pitch transform, whose
+        window mean is then taken over the voiced frames alone."""
+        if voicing is not None and world_pitch:
+            raise ValueError("voicing cannot be combined with world_pitch: WORLD makes its own voicing decision")
+        voice = (lambda f0: f0) if voicing is None else (lambda f0: ops.voicing_rows_(f0, windows, voicing))
         if pitch_track is not None:
             if world_pitch:
                 raise ValueError("pitch_track cannot be combined with world_pitch: the tracker decodes the estimator's class scores")
@@ -154,7 +160,7 @@ class Converter:
             spec = spectrogram(windows)
             f0 = self.pe.estimate(spec, out=None if out is None else out[1], track=self._pitch_track(o["lo"], o["hi"], o["band"]),
                                   track_weight=o["weight"], track_jump=o["jump"])
-            f0 = ops.pitch_transform_(f0, 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
+            f0 = ops.pitch_transform_(voice(f0), 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
             feat = self._encode(spec, frames)
             if out is not None:
                 out[0].copy_(feat)
@@ -168,10 +174,10 @@ class Converter:
             return feat, f0
         if frames is None:                 # the whole window: one fused call, no fp32 spectrogram (ops.front_end)
             feat, f0 = ops.front_end(windows, self.ce, self.pe, out=out)     # out = (feat, f0) batch slices to write into
-            return feat, ops.pitch_transform_(f0, 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
+            return feat, ops.pitch_transform_(voice(f0), 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
         spec = spectrogram(windows)
         f0 = self.pe.estimate(spec, out=None if out is None else out[1])
-        f0 = ops.pitch_transform_(f0, 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
+        f0 = ops.pitch_transform_(voice(f0), 0, f0_rate=f0_rate, pitch_shift=pitch_shift, intonation=intonation)
         return self._encode(spec, frames), f0
 
     def _encode(self, spec, frames=None):
@@ -284,7 +290,7 @@ class Converter:
         return None                       # one process, one decision (ShardedConverter: max over the ranks)
 
     def _convert_windows(self, windows, k=4, alpha=0.0, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, window_batch=64,
-                         keep_frames=None, share_overlap=None, world_pitch=False, pitch_track=None):
+                         keep_frames=None, share_overlap=None, world_pitch=False, pitch_track=None, voicing=None):
         """windows [n, L] on the device -> waveforms [n, L]; L a multiple of 320.
         Networks run in batches of `window_batch` windows (bounded scratch); the kNN match runs ONCE over the frames
         of all windows, so every library tile streamed from L2 is used by as many frames as possible.
@@ -296,7 +302,12 @@ class Converter:
         sharing is not used with it (the per-window path gives the same samples) and trimming applies to the content only.
         pitch_track=True | dict(weight=, jump=, lo=, hi=, band=): the f0 of every whole window is the Viterbi path over the
         estimator's class scores (features); it rides where world_pitch does -- per-window front end, no overlap sharing, f0
-        over the whole window also with keep_frames -- and cannot be combined with it."""
+        over the whole window also with keep_frames -- and cannot be combined with it.
+        voicing=True | dict(on=, off=, floor_db=, lo=, hi=, window_ms=, bridge=, min_run=): the f0 of the frames of every whole window
+        that are not periodic becomes 0 (features); it rides where pitch_track does and cannot be combined with world_pitch."""
+        voicing = common.voicing_options(voicing)
+        if voicing is not None and world_pitch:
+            raise ValueError("voicing cannot be combined with world_pitch: WORLD makes its own voicing decision")
         pitch_track = common.track_options(pitch_track)
         if pitch_track is not None and world_pitch:
             raise ValueError("pitch_track cannot be combined with world_pitch: the tracker decodes the estimator's class scores")
@@ -310,7 +321,7 @@ class Converter:
         rng = _decoded_range(keep_frames, lf)
         # sharing and trimming together need the trimmed range to consist of interior frames of the signal (it does for the
         # centre third of a 3-chunk window from 46 frames per chunk on); otherwise trimming alone is used -- same samples
-        share_ok = bool(share_overlap) and n * (EDGE + NET_MARGIN) >= 96 and not world_pitch and pitch_track is None
+        share_ok = bool(share_overlap) and n * (EDGE + NET_MARGIN) >= 96 and not world_pitch and pitch_track is None and voicing is None
         if share_ok and (rng is None or (EDGE <= rng[0] and rng[1] <= lf - EDGE and rng[1] - rng[0] >= 5)):
             # share_overlap = windows per signal (make_windows order): front end once per signal, decoder per window
             feat, f0 = self.features_shared(windows, int(share_overlap), k, alpha, frames=rng)
@@ -321,10 +332,10 @@ class Converter:
             b = slice(i, i + window_batch)
             if rng is None:                                 # the networks write straight into the batch's slices
                 self.features(windows[b], pitch_shift, intonation, f0_rate, out=(feat[b], f0[b]), world_pitch=world_pitch,
-                              pitch_track=pitch_track)
+                              pitch_track=pitch_track, voicing=voicing)
             else:
                 feat[b], f0[b] = self.features(windows[b], pitch_shift, intonation, f0_rate, frames=rng, world_pitch=world_pitch,
-                                               pitch_track=pitch_track)
+                                               pitch_track=pitch_track, voicing=voicing)
 
         def match(feat):                                    # (ShardedConverter overrides self.match)
             if rng is None:
@@ -409,7 +420,7 @@ class Converter:
 
     def convert_many(self, utterances, pool, voices, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, alpha=0.0, chunk=48000, k=4,
                      window_batch=64, trim_context=False, world_pitch=False, auto_pitch=False, auto_range=False,
-                     pitch_range_max=2.0, pitch_track=None):
+                     pitch_range_max=2.0, pitch_track=None, voicing=None):
         """Many-to-many batch conversion: utterance i (16 kHz, [L] or [1, L], any length) to voice voices[i] of `pool`
         (module/multistream.py: VoicePool), with per-utterance pitch_shift / intonation / f0_rate / alpha / world_pitch (a scalar
         applies to every utterance; world_pitch: WORLD's f0 of each whole window, as convert(world_pitch=True)).  Returns one [1, L_i] waveform per utterance.  The windows of ALL utterances form one batch (a network
@@ -444,7 +455,13 @@ class Converter:
         the tracked utterances must agree on them; not together with world_pitch).  Per window batch, the class scores of the tracked
         windows are stored (F0Estimator.logits) and alive_f0_track_rows overwrites their f0 rows, each with its utterance's weight
         and jump, before the transform -- auto pitch and auto range measure the tracked contour.  A row's path depends on its own
-        scores only; a corpus without a tracked utterance launches the present path."""
+        scores only; a corpus without a tracked utterance launches the present path.
+        voicing (None / a bool / dict(on=, off=, floor_db=), or one per utterance): the f0 of utterance i's frames that are not
+        periodic becomes 0, as convert(voicing=...) of it alone (lo, hi, window_ms, bridge and min_run are call-wide: the deciding
+        utterances must agree on them; not together with world_pitch).  One alive_voicing_rows call per window batch over the rows
+        that are on, each with its utterance's thresholds, after the tracker and before the transform -- auto pitch and auto range
+        measure the voiced contour.  A row's decision depends on its own window only; a corpus without a deciding utterance launches
+        the present path."""
         from . import multistream as MS
         m = len(utterances)
         voices = list(voices)
@@ -483,6 +500,19 @@ class Converter:
             if len(wide) != 1:
                 raise ValueError(f"pitch_track: lo, hi and band are call-wide, the tracked utterances ask for {sorted(wide)}")
             tracker = self._pitch_track(*wide.pop())
+        voicings = list(voicing) if isinstance(voicing, (list, tuple)) else [voicing] * m
+        if len(voicings) != m:
+            raise ValueError(f"voicing: {len(voicings)} values for {m} utterances")
+        voicings = [common.voicing_options(v, f"convert_many: utterance {i}") for i, v in enumerate(voicings)]
+        if any(v is not None and w for v, w in zip(voicings, worlds)):
+            raise ValueError("voicing cannot be combined with world_pitch on the same utterance")
+        voicing_wide = None
+        if any(v is not None for v in voicings):
+            wide = {tuple(v[key] for key in ("lo", "hi", "window_ms", "bridge", "min_run")) for v in voicings if v is not None}
+            if len(wide) != 1:
+                raise ValueError("voicing: lo, hi, window_ms, bridge and min_run are call-wide, the deciding utterances ask for "
+                                 f"{sorted(wide)}")
+            voicing_wide = next(v for v in voicings if v is not None)
         autos = list(auto_pitch) if isinstance(auto_pitch, (list, tuple)) else [auto_pitch] * m
         if len(autos) != m:
             raise ValueError(f"auto_pitch: {len(autos)} values for {m} utterances")
@@ -566,6 +596,19 @@ class Converter:
                     on=torch.tensor([int(part[j] is not None) for j in sel], dtype=torch.int32, device=self.device),
                     weight=torch.tensor([part[j]["weight"] if part[j] else 0.0 for j in sel], dtype=torch.float64, device=self.device),
                     jump=torch.tensor([part[j]["jump"] if part[j] else 0.0 for j in sel], dtype=torch.float64, device=self.device))
+        # the deciding windows of every window batch: the mask and their rows' thresholds
+        params["voicing"] = {}
+        if voicing_wide is not None:
+            per_win = [v for v, c in zip(voicings, counts) for _ in range(c)]
+            f64 = dict(dtype=torch.float64, device=self.device)
+            for i in range(0, len(per_win), window_batch):
+                part = per_win[i:i + window_batch]
+                if any(v is not None for v in part):
+                    params["voicing"][i] = dict(
+                        mask=torch.tensor([int(v is not None) for v in part], dtype=torch.int32, device=self.device),
+                        thr_on=torch.tensor([v["on"] if v else voicing_wide["on"] for v in part], **f64),
+                        thr_off=torch.tensor([v["off"] if v else voicing_wide["off"] for v in part], **f64),
+                        floor_e=torch.tensor([v["floor_e"] if v else voicing_wide["floor_e"] for v in part], **f64))
         rng = _decoded_range((chunk // 320, 2 * chunk // 320) if trim_context else None, windows.shape[1] // 320)
 
         def encode(i, feat, f0):
@@ -584,6 +627,9 @@ class Converter:
                 sub = f0[b].index_select(0, tr["sel"])
                 tracker.rows(self.pe.logits(spectrogram(windows[b].index_select(0, tr["sel"]))), sub, tr["on"], tr["weight"], tr["jump"])
                 f0[b].index_copy_(0, tr["sel"], sub)
+            vo = params["voicing"].get(i)
+            if vo is not None:              # the deciding windows' unvoiced frames become 0 (same stream: after the tracker)
+                ops.voicing_rows_(f0[b], windows[b], voicing_wide, vo["mask"], vo["thr_on"], vo["thr_off"], vo["floor_e"])
 
         def transform(f0):                  # each utterance's pitch, intonation and f0 rate (features(world_pitch=True))
             shift, au, rg = params["shift"], params.get("auto"), params.get("range")

@@ -149,14 +149,22 @@ class RealtimeConverter:
     envelope = False                   # (likewise: whether the step carries the envelope kernel)
     pitch_range = False                # (likewise: whether the f0 branch runs the pitch-range follower and the centred transform)
     pitch_track = False                # (likewise: whether the f0 branch stores the class scores and runs the tracker kernel)
+    voicing = False                    # (likewise: whether the f0 branch runs the voicing kernels; voicing_state() is the read-back)
 
     def __init__(self, content_encoder, f0_estimator, decoder, library_tokens, device="cuda", chunk=960, buffersize=8,
                  input_sr=16000, output_sr=16000, f0_rate=1.0, pitch=0.0, k=4, alpha=0.0, gain=0.0, input_gain=0.0,
                  reuse_interior="auto", world_pitch=False, gate_db=None, gate_hold=0.2, gate_lookahead=None,
                  crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0, limit_hold_ms=20.0, limit_history=0.05,
                  envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0, envelope_radius=1, intonation=1.0,
-                 intonation_half_life=10.0, intonation_prior=0.5, pitch_track=None):
+                 intonation_half_life=10.0, intonation_prior=0.5, pitch_track=None, voicing=None):
         self.device = torch.device(device)
+        voicing = common.voicing_options(voicing, "RealtimeConverter")
+        self.voicing = voicing is not None                  # (checked before anything is built)
+        if self.voicing:
+            if world_pitch:
+                raise ValueError("RealtimeConverter: voicing cannot be combined with world_pitch: WORLD makes its own voicing decision")
+            if reuse_interior is True:
+                raise ValueError("interior reuse cannot be combined with voicing: a frame's decision depends on the frames around it")
         track = common.track_options(pitch_track, "RealtimeConverter: pitch_track")
         self.pitch_track = track is not None                # (checked before anything is built)
         if self.pitch_track:
@@ -290,6 +298,14 @@ class RealtimeConverter:
             self._track_jump = torch.tensor([track["jump"]], dtype=torch.float64, device=dev)
             self._track_changed = torch.zeros(1, dtype=torch.int32, device=dev)
             self._track_bufs = {}
+        if self.voicing:
+            # the multi-session detector at one row; no state: it looks at the whole ring again every step
+            dev = self.device
+            self._voicing = voicing
+            self._voicing_rows = [torch.tensor([voicing[key]], dtype=torch.float64, device=dev) for key in ("on", "off", "floor_e")]
+            self._voicing_out = dict(r=torch.zeros(1, frames, dtype=torch.float64, device=dev),
+                                     voiced=torch.zeros(1, frames, dtype=torch.int32, device=dev),
+                                     changed=torch.zeros(1, dtype=torch.int32, device=dev))
         self._side = None                  # side stream of the f0 estimator (see _f0_on_side_stream)
         self._f0_bufs = {}
         # interior reuse: only where it is exact -- no resampling in front (the ring IS the 16 kHz signal), a shift of whole
@@ -314,6 +330,9 @@ class RealtimeConverter:
             fits = False
         # pitch_track: a frame's tracked class depends on the whole ring (the path is decoded again every step) -- interior reuse is off
         if self.pitch_track:
+            fits = False
+        # voicing: hysteresis, bridge and minimum run make a frame's decision depend on the ring around it -- interior reuse is off
+        if self.voicing:
             fits = False
         if reuse_interior is True and not fits:
             raise ValueError("interior reuse needs input_sr 16000, chunk a multiple of 320 and a ring of at least 70 + chunk / 320 "
@@ -411,6 +430,15 @@ class RealtimeConverter:
             raise ValueError("pitch_track_changed needs a converter built with RealtimeConverter(..., pitch_track=True)")
         return int(self._track_changed.tolist()[0])
 
+    def voicing_state(self):
+        """the voicing decision of the latest step: (voiced frames of the ring, frames whose f0 was set to 0, r of the centre frame of
+        the emitted span), read back from the device"""
+        if not self.voicing:
+            raise ValueError("voicing_state needs a converter built with RealtimeConverter(..., voicing=True)")
+        o = self._voicing_out
+        centre = min((self.begin_of_output + self.end_of_output) // 2 // 320, self.frames - 1)      # (the span is in 16 kHz samples)
+        return int(o["voiced"].sum()), int(o["changed"][0]), float(o["r"][0, centre])
+
     def _f0_on_side_stream(self, spec, data=None):
         """f0_on_side_stream with the estimator's f0 and the pitch transform.  With world_pitch the branch is WORLD's f0 of the
         16-kHz ring `data` instead, and the pitch transform leaves out f0_rate: the reference multiplies only the estimator's f0
@@ -436,6 +464,8 @@ class RealtimeConverter:
                                       changed=self._track_changed)
             else:
                 f0 = self.pe.estimate(spec, out=buf)
+            if self.voicing:                   # f0 = 0 where the ring is not periodic, before the follower and the transform
+                ops.voicing_rows_(f0, data.contiguous(), self._voicing, None, *self._voicing_rows, self._voicing_out)
             if self.pitch_range:
                 return ranged(f0)
             return ops.pitch_transform_(f0, 1, f0_rate=self.f0_rate, pitch_shift=self.pitch)

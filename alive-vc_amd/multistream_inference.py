@@ -23,6 +23,10 @@ The sessions file is a JSON list; each entry:
                                           (module/multistream.py "Pitch tracking"); not with "world_pitch"
    "track_weight": 1, "track_jump": 12,   optional, numbers >= 0 (defaults: --track-weight / --track-jump): the tracker's cost per
                                           semitone moved inside the band and its flat cost of any other move
+   "voicing": true,                       optional, a JSON bool (default: -vd): the session's f0 is 0 on the frames of its ring that are
+                                          not periodic (module/multistream.py "Voicing"); not with "world_pitch"
+   "voicing_on": 0.6, "voicing_off": 0.45, "voicing_floor_db": -60,      optional (defaults: --voicing-on / --voicing-off /
+                                          --voicing-floor): the session's two thresholds on the normalised correlation and its silence floor
    "gate_db": -40, "gate_hold": 0.2,      optional: the session's input gate (module/multistream.py "Input gate"): a threshold in
                                           dBFS on its 16 kHz ring after the input gain (null: no gate; default -thr) and the
                                           seconds it stays open after the last loud tick (default --gate-hold)
@@ -71,6 +75,8 @@ only if some session is on auto pitch: a file without "auto_pitch", run without 
 The converter is built with pitch_range=True, and the voices are given registers and ranges, only if some session ends up at an
 "intonation" other than 1 or on "auto_range" (or under -int / --auto-range): a file without the keys, run without the flags, runs as
 before.
+The converter carries the voicing kernels only if some session ends up deciding ("voicing", or -vd): a file without the key, run
+without the flag, runs as before.  --voicing-lo / --voicing-hi hold for the whole converter.
 The converter stores the class scores and carries the tracker kernel only if some session ends up tracking ("pitch_track", or -pt): a
 file without the key, run without the flag, runs as before.  --track-lo / --track-hi / --track-band hold for the whole converter.
 The converter carries the two gate kernels only if some session ends up gated ("gate_db", or -thr): a file without the keys, run
@@ -139,6 +145,7 @@ LOSE_KEYS = ("lose",)                    # likewise (the converter is then spars
 CONCEAL_KEYS = ("conceal",)              # likewise: the session's own switch
 RANGE_KEYS = ("intonation", "auto_range")    # a loaded session carries "intonation" only when it is not 1, "auto_range" only when on
 TRACK_KEYS = ("pitch_track", "track_weight", "track_jump")      # a loaded session carries them only when it tracks
+VOICING_KEYS = ("voicing", "voicing_on", "voicing_off", "voicing_floor_db")      # likewise: only when it decides
 RANGE_ST_KEYS = ("range_st",)            # a loaded session carries it only when its entry has the key
 
 
@@ -223,6 +230,7 @@ def build_parser():
     parser.add_argument('--no-graph', action='store_true',
                         help="launch the per-tick device pipeline kernel by kernel instead of replaying one captured hipGraph")
     common.add_track_arguments(parser)      # (-pt: sessions track unless their "pitch_track" says otherwise)
+    common.add_voicing_arguments(parser)    # (-vd: sessions decide unless their "voicing" says otherwise)
     return parser
 
 
@@ -294,6 +302,22 @@ def session_track(s, where, pitch_track=False, weight=common.TRACK_WEIGHT, jump=
     if s.get("world_pitch", False):
         raise ValueError(f"{where}: \"pitch_track\" cannot be combined with \"world_pitch\"")
     return w, j
+
+
+def session_voicing(s, where, voicing=False, on=common.VOICING_ON, off=common.VOICING_OFF, floor_db=common.VOICING_FLOOR_DB):
+    """an entry's voicing settings -> (on, off, floor_db) as floats, or None for a session that does not decide: "voicing" (default
+    `voicing`) a JSON bool, "voicing_on" / "voicing_off" / "voicing_floor_db" (defaults `on`, `off`, `floor_db`) numbers with
+    0 < off <= on <= 1; ValueError otherwise, and together with "world_pitch" """
+    v = s.get("voicing", bool(voicing))
+    if not isinstance(v, bool):
+        raise ValueError(f"{where}: \"voicing\" must be true or false, got {v!r}")
+    o = common.voicing_options(dict(on=s.get("voicing_on", on), off=s.get("voicing_off", off),
+                                    floor_db=s.get("voicing_floor_db", floor_db)), where)
+    if not v:
+        return None
+    if s.get("world_pitch", False):
+        raise ValueError(f"{where}: \"voicing\" cannot be combined with \"world_pitch\"")
+    return o["on"], o["off"], o["floor_db"]
 
 
 def declared_registers(entries, name_of):
@@ -425,7 +449,8 @@ def supply_ticks(start, n_chunks, stall=None):
 def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, codebook=None, crossfade_ms=None, limit_db=None,
                   limit_lookahead_ms=5.0, limit_hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0,
                   envelope_radius=1, conceal_hold_ms=10.0, conceal_fade_ms=50.0, conceal_recover_ms=5.0, intonation=1.0,
-                  auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT, track_jump=common.TRACK_JUMP, lufs=None):
+                  auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT, track_jump=common.TRACK_JUMP, lufs=None,
+                  voicing=False, voicing_on=common.VOICING_ON, voicing_off=common.VOICING_OFF, voicing_floor_db=common.VOICING_FLOOR_DB):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
@@ -436,7 +461,9 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     (default `intonation`) only on a session whose factor is not 1, "auto_range" (default `auto_range`) only on one that is on, and
     "range_st" only where the entry has it; "pitch_track" (true), "track_weight" and "track_jump" (defaults `pitch_track`,
     `track_weight`, `track_jump`) only on a session that tracks; "lufs" (default `lufs`) only on a session that is normalised;
-    ValueError on a malformed entry"""
+    "voicing" (true), "voicing_on", "voicing_off" and "voicing_floor_db" (defaults `voicing`, `voicing_on`, `voicing_off`,
+    `voicing_floor_db`) only on a session that decides; ValueError on a malformed entry"""
+    session_voicing({}, "-vd / --voicing-on / --voicing-off / --voicing-floor", voicing, voicing_on, voicing_off, voicing_floor_db)
     session_track({}, "-pt / --track-weight / --track-jump", pitch_track, track_weight, track_jump)
     try:
         check_conceal_ms(conceal_hold_ms, conceal_fade_ms, conceal_recover_ms)
@@ -461,11 +488,11 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
         if not isinstance(s, dict) or "input" not in s:
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
         unknown = (set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(CODEBOOK_KEYS)
-                   - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS) - set(RANGE_KEYS) - set(RANGE_ST_KEYS) - set(TRACK_KEYS)
+                   - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS) - set(RANGE_KEYS) - set(RANGE_ST_KEYS) - set(TRACK_KEYS) - set(VOICING_KEYS)
                    - set(LOUDNESS_KEYS))
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS + TRACK_KEYS + LOUDNESS_KEYS})")
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS + TRACK_KEYS + LOUDNESS_KEYS + VOICING_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
@@ -486,6 +513,7 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
         inton, ranged = session_range(s, f"session {i}", intonation, auto_range)
         range_st = range_st_of(s, f"session {i}")
         track = session_track(s, f"session {i}", pitch_track, track_weight, track_jump)
+        decide = session_voicing(s, f"session {i}", voicing, voicing_on, voicing_off, voicing_floor_db)
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
                  gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
@@ -521,6 +549,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             e["range_st"] = range_st
         if track is not None:
             e["pitch_track"], (e["track_weight"], e["track_jump"]) = True, track
+        if decide is not None:
+            e["voicing"], (e["voicing_on"], e["voicing_off"], e["voicing_floor_db"]) = True, decide
         out.append(e)
     return out
 
@@ -673,12 +703,14 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
         tw, tj, lo, hi, band = common.track_arguments(args)             # (before anything is loaded)
+        voicing_opts = common.voicing_options(dict(lo=args.voicing_lo, hi=args.voicing_hi), "--voicing-lo / --voicing-hi")
     except ValueError as e:
         raise SystemExit(str(e)) from None
     sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook,
                              args.crossfade, args.limit, args.limit_lookahead, args.limit_hold, args.envelope, args.envelope_floor,
                              args.envelope_range, args.envelope_radius, args.conceal_hold, args.conceal_fade, args.conceal_recover,
-                             args.intonation, args.auto_range, args.pitch_track, tw, tj, args.lufs)
+                             args.intonation, args.auto_range, args.pitch_track, tw, tj, args.lufs, args.voicing, args.voicing_on,
+                             args.voicing_off, args.voicing_floor)
     loud = dict(loudness_half_life=args.loudness_half_life, loudness_prior=args.loudness_prior, loudness_gate_lufs=args.loudness_gate,
                 loudness_max_db=args.loudness_max_db, loudness_slew_db=args.loudness_slew)
     try:
@@ -728,6 +760,8 @@ def main(argv=None):
                                 **(dict(pitch_range=True) if wants_range else {}),
                                 **(dict(pitch_track=True, track_lo=lo, track_hi=hi, track_band=band)
                                    if any("pitch_track" in s for s in sessions) else {}),
+                                **(dict(voicing=True, voicing_lo=voicing_opts["lo"], voicing_hi=voicing_opts["hi"])
+                                   if any("voicing" in s for s in sessions) else {}),
                                 **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}),
                                 **(dict(crossfade=True) if any("crossfade_ms" in s for s in sessions) else {}),
                                 **(dict(limiter=True) if any("limit_db" in s for s in sessions) else {}),
@@ -740,7 +774,7 @@ def main(argv=None):
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
                    **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CONCEAL_KEYS + RANGE_KEYS + TRACK_KEYS
-                      + LOUDNESS_KEYS if g in s})
+                      + LOUDNESS_KEYS + VOICING_KEYS if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()

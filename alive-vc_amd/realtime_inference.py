@@ -79,6 +79,7 @@ def build_parser():
                         help="scale the pitch excursions around the stream's running mean pitch by this factor, as inference.py's -int "
                              "does around a window's mean (default 1: off; module/multistream.py \"Pitch range\"; this build only)")
     common.add_track_arguments(parser)
+    common.add_voicing_arguments(parser)
     parser.add_argument('-isr', '--input-sr', default=16000, type=int)
     parser.add_argument('-osr', '--output-sr', default=16000, type=int)
     parser.add_argument('-lsr', '--loopback-sr', default=16000, type=int)
@@ -93,6 +94,12 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.knn_strict:
         os.environ["ALIVE_KNN_STRICT"] = "1"              # read by module/common.py when the library is packed
+    try:
+        voicing = common.voicing_arguments(args)                             # (before the device is looked for)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if voicing is not None and args.world_pitch_estimation:
+        raise SystemExit("-vd cannot be combined with -wpe: WORLD makes its own voicing decision")
     if args.device != 'cuda' or not torch.cuda.is_available():
         raise SystemExit("Error: this build needs a ROCm device: pass -d cuda on an MI355X host.")
     if args.fp16:
@@ -133,7 +140,8 @@ def main(argv=None):
                            **(dict(envelope=args.envelope, envelope_floor_db=args.envelope_floor, envelope_range_db=args.envelope_range,
                                    envelope_radius=args.envelope_radius) if args.envelope else {}),
                            **(dict(intonation=args.intonation) if args.intonation != 1.0 else {}),
-                           **({} if track is None else dict(pitch_track=track)))
+                           **({} if track is None else dict(pitch_track=track)),
+                           **({} if voicing is None else dict(voicing={k: voicing[k] for k in common.VOICING_KEYS})))
     if not args.no_graph:
         rt.enable_graph()        # the whole per-chunk device pipeline (~150 launches) captured once, replayed per chunk: same samples
     print("streaming: conversion running (Ctrl-C stops)")

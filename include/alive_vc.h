@@ -803,6 +803,34 @@ int alive_f0_track_rows(const float* logits, int N, int C, int T, int lo, int S,
                         const int32_t* band_hi, const int32_t* on, const double* weight, const double* jump, float* f0,
                         int32_t* changed, void* ws, void* stream);
 
+/* Voicing: f0 = 0 on the frames of a row whose source is not periodic (tools/voicing_ref.py is the NumPy restatement, bit for bit).
+ * The detector is a normalised cross-correlation of the 16 kHz signal x[N][ld] (valid length L <= ld, zero beyond it) and does not
+ * look at the f0 estimator.  q[i] = clamp(rintf(x[i] * 32768.0f), -32768, 32767) as an integer (NaN -> 0; 0 outside [0, L)), so every
+ * sum below is an exact integer (int64) and no summation order can matter.  Per frame t of `hop` samples and lag tau in
+ * [lag_lo, lag_hi], with c = hop t + hop / 2 and s = c - floor((W + tau) / 2):
+ *   Sxy = sum q[i] q[i + tau], Sxx = sum q[i]^2, Syy = sum q[i + tau]^2 over i in [s, s + W)
+ *   rho(tau) = (double)Sxy / sqrt((double)Sxx * (double)Syy) when all three sums are > 0, else 0.0 (each operation rounded on its own)
+ *   r[t] = max over tau of rho, lag[t] the lowest tau attaining it (lag_lo when r[t] == 0)
+ *   silent[t] = (double)(sum of q[i]^2 over [hop t, hop t + hop)) < floor_e[n]     (host: floor_e = 10^(dB / 10) * hop * 2^30)
+ * then per row, in frame order: (a) hysteresis from s = 0: silent -> 0; else r >= thr_on[n] -> 1; else r < thr_off[n] -> 0; else s
+ * stays; (b) an unvoiced run of at most `bridge` frames with a voiced frame on both sides and no silent frame in it becomes voiced;
+ * (c) a voiced run shorter than `min_run` frames that touches neither end of the row becomes unvoiced.  f0[n][t] (row stride ld_f0)
+ * keeps its value on a voiced frame and becomes +0.0f on every other one.
+ *   on          DEVICE int32 [N] or NULL (every row): a row with on[n] == 0 does nothing; its f0 row and outputs are untouched
+ *   thr_on, thr_off, floor_e   DEVICE double [N], read when the kernels run
+ *   r_out (double [N][T]), lag_out, voiced_out (int32 [N][T]), changed (int32 [N]: the frames that were not 0 and were set to 0):
+ *               DEVICE or NULL
+ *   ws          alive_voicing_workspace_bytes(N, T) bytes (0: bad args)
+ * Limits: W <= ALIVE_VOICING_MAX_WINDOW, lag_hi <= ALIVE_VOICING_MAX_LAG (a frame's samples and the int64 prefix sum of their squares
+ * lie in 64 KB of LDS).  Two launches whose grids depend on N, T, hop, W and lag_hi alone; no host synchronisation, no allocation,
+ * no atomics. */
+#define ALIVE_VOICING_MAX_WINDOW 4096
+#define ALIVE_VOICING_MAX_LAG 1600
+size_t alive_voicing_workspace_bytes(int N, int T);
+int alive_voicing_rows(const float* x, int N, int ld, int L, int hop, int T, int lag_lo, int lag_hi, int W, int min_run, int bridge,
+                       const int32_t* on, const double* thr_on, const double* thr_off, const double* floor_e, float* f0, int ld_f0,
+                       double* r_out, int32_t* lag_out, int32_t* voiced_out, int32_t* changed, void* ws, void* stream);
+
 /* Arithmetic of the decoder's two largest groups of GEMMs on the batch path (more than 96 columns; the streaming kernels are not
  * affected): (a) the six k = 5 convs of the 256-channel FilterBlock (decoder.py:128-134 at the Filter's coarsest scale), (b) the two
  * pointwise convs of the feature extractor's four AdaptiveConvNeXt1d layers (common.py:74-82), (c) the norm-FiLM projection, the two

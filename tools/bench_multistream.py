@@ -53,6 +53,12 @@ scores stored, their argmax, and the tracker's blocks returning at once) and wit
 all three alive in the one process and timed in alternating rounds (the medians over the rounds; the spread of track_off's rounds is
 the yardstick), the tracker call alone by device events around 200 back-to-back eager calls on the last tick's scores
 (track_call_us), and how many frames it moved in the last tick (track_changed_mean, on SYNTHETIC weights and input).
+--voicing adds the graph tick p50 / p99 of a voicing=True converter with no session deciding (voicing_none_tick_*: the two kernels'
+blocks returning at once) and with every session deciding at the defaults (voicing_all_tick_*: alive_voicing_rows over every ring,
+csrc/voicing.hip) beside the converter built without it (voicing_off_tick_*), all three alive in the one process and timed in
+alternating rounds as --pitch-track's are, the call alone by device events around 200 back-to-back eager calls on the last tick's
+rings (voicing_call_us), and how many frames it set to 0 in the last tick (voicing_changed_mean, on SYNTHETIC weights and input).
+--voicing-offline runs the bare call ALONE over 384 windows of 450 frames (144 000 samples each), by device events around 20 calls.
 --enrol runs the live-enrolment leg ALONE: B = 64 sessions on distinct 50 000-row voices at -c 160 -b 16, graph mode, and
 one more 50 000-row voice added between two ticks, once on a default pool (the add re-packs the pool and the next tick
 re-captures) and once on a reserved pool of 65 x 50 000 rows (VoicePool(capacity=...): alive_pool_append into the table in
@@ -80,9 +86,10 @@ alive_ring_push_rows with every row present (push_call_us).
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch] [--pitch-range]
-                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--loudness] [--pitch-track]
+                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--loudness] [--pitch-track] [--voicing]
                                       [--out multistream.json]
     python tools/bench_multistream.py --loudness-offline [--out loudness_offline.json]
+    python tools/bench_multistream.py --voicing-offline [--out voicing_offline.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
     python tools/bench_multistream.py --sparse [--batches 128,1024] [--ticks 40] [--out profiles/multistream_sparse_bench.json]
     python tools/bench_multistream.py --conceal [--batches 128,1024] [--ticks 40] [--out profiles/multistream_conceal_bench.json]
@@ -173,6 +180,20 @@ def loudness_offline_leg(shapes=((64, 10.0), (8, 60.0)), rate=48000):
         recs.append(rec)
         del y
     return recs
+
+
+def voicing_offline_leg(windows=384, frames=450):
+    """the bare voicing call over `windows` windows of `frames` frames of make_voiced speech at the defaults"""
+    from module import common, ops
+    o = common.voicing_options(True)
+    x = synthetic.make_voiced(320 * frames, 3)[0].cuda().repeat(windows, 1).contiguous()
+    f0 = torch.full((windows, 1, frames), 120.0, device="cuda")
+    per_row = [torch.full((windows,), o[key], dtype=torch.float64, device="cuda") for key in ("on", "off", "floor_e")]
+    us = time_calls(lambda: ops.voicing_rows_(f0, x, o, None, *per_row), reps=20)
+    rec = {"windows": windows, "frames": frames, "lags": [o["lag_lo"], o["lag_hi"]], "W": o["W"], "voicing_call_us": round(us, 1),
+           "us_per_frame": round(us / (windows * frames), 4)}
+    print(json.dumps(rec), flush=True)
+    return [rec]
 
 
 def conceal_leg(nets, batches=(128, 1024), ticks=40, warmup=6):
@@ -405,6 +426,9 @@ def main():
                     "normalize_loudness over 64 rows of 10 s at 48 kHz, and over 8 rows of 60 s")
     ap.add_argument("--pitch-track", action="store_true", help="also time a pitch_track=True converter with no session and with "
                     "every session tracking, beside the plain converter in alternating rounds")
+    ap.add_argument("--voicing", action="store_true", help="also time a voicing=True converter with no session and with every session "
+                    "deciding, beside the plain converter in alternating rounds")
+    ap.add_argument("--voicing-offline", action="store_true", help="the bare voicing call alone over 384 windows of 450 frames")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
                                                          "default and on a reserved pool")
     ap.add_argument("--sparse", action="store_true", help="the sparse-ticks leg alone: dense against sparse(=True) converters, "
@@ -437,6 +461,12 @@ def main():
         return
     if args.loudness_offline:
         rows = loudness_offline_leg()
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(rows, open(args.out, "w"), indent=1)
+        return
+    if args.voicing_offline:
+        rows = voicing_offline_leg()
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             json.dump(rows, open(args.out, "w"), indent=1)
@@ -682,6 +712,32 @@ def main():
                     rec["track_frames"], rec["track_states"] = int(lg.shape[2]), tc._track.states
                     rec["track_call_us"] = round(time_calls(lambda: tc._track.rows(lg, f0, tc.track_on, tc.track_weight, tc.track_jump)), 2)
                     del three, tc
+                if args.voicing:
+                    three = {}
+                    for name, kw, sess in (("voicing_off", {}, {}), ("voicing_none", dict(voicing=True), {}),
+                                           ("voicing_all", dict(voicing=True), dict(voicing=True))):
+                        c = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, **kw)
+                        for s in range(B):
+                            c.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, **sess)
+                        c.enable_graph()
+                        three[name] = c
+                    times = {name: [] for name in three}
+                    for _ in range(5):                         # alternating rounds in the one process
+                        for name, c in three.items():
+                            times[name].append(time_ticks(c, B, chunk, args.ticks, args.warmup + bs + 1, 300))
+                    for name, ts in times.items():
+                        rec[f"{name}_tick_p50_ms"] = round(float(np.median([t[0] for t in ts])), 3)
+                        rec[f"{name}_tick_p99_ms"] = round(float(np.median([t[1] for t in ts])), 3)
+                        rec[f"{name}_tick_p50_rounds_ms"] = [round(t[0], 3) for t in ts]
+                    vc = three["voicing_all"]
+                    assert vc.captures == 1 and three["voicing_none"].voicing_state() == [(0, 0, 0.0)] * B
+                    rec["voicing_changed_mean"] = round(float(np.mean([st[1] for st in vc.voicing_state()])), 2)
+                    x = torch.from_numpy(vc.ring.astype(np.float32) / 32768.0).cuda() if not vc.sparse else None
+                    f0 = torch.full((B, 1, vc.frames), 120.0, device="cuda")
+                    rec["voicing_frames"] = vc.frames
+                    rec["voicing_call_us"] = round(time_calls(lambda: MS.ops.voicing_rows_(f0, x, vc._voicing, vc.voicing_on, vc.voicing_thr_on,
+                                                                                       vc.voicing_thr_off, vc.voicing_floor_e)), 2)
+                    del three, vc
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
                 rows.append(rec)
