@@ -51,6 +51,10 @@ The jobs file is a JSON list; each entry:
                                                             inference.py's -vd).  Not with "world_pitch".  --voicing-lo /
                                                             --voicing-hi hold for the whole run.  A jobs file without it, run
                                                             without -vd, runs as before
+   "match_path": true,                                      optional, a JSON bool or {"weight": 1} (default: -mp with --path-weight):
+                                                            each frame's matched feature is ONE of its k nearest rows, chosen by a
+                                                            Viterbi path over each window (convert_many(match_path=); inference.py's
+                                                            -mp).  A jobs file without it, run without -mp, runs as before
    "blend": [{"target": "a.wav", "weight": 2},              instead of "target" / "lib": a weighted mix of 1 to 4 voices, each
              {"lib": "b.pt", "weight": 1}],                 component a voice source as above (module/multistream.py blend_spec)
    "output": "a_out.wav"}                                   optional: default <outdir>/<index>_<input name>.wav
@@ -79,6 +83,7 @@ LIMIT_KEYS = ("limit_db",)               # taken per job too; a loaded job carri
 LOUDNESS_KEYS = ("lufs",)                # likewise; a loaded job carries it only when it is normalised
 TRACK_KEYS = ("pitch_track",)            # a loaded job carries it only when it tracks: {"weight": W, "jump": J}
 VOICING_KEYS = ("voicing",)              # a loaded job carries it only when it decides: {"on": R, "off": R, "floor_db": DB}
+PATH_KEYS = ("match_path",)              # a loaded job carries it only when its match takes a path: {"weight": W}
 RANGE_KEYS = ("auto_range", "range_st")  # a loaded job carries "auto_range" only when it is on, "range_st" only when its entry has it
 
 
@@ -125,6 +130,7 @@ def build_parser():
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV")
     common.add_track_arguments(parser)      # (-pt: jobs track unless their "pitch_track" says otherwise)
     common.add_voicing_arguments(parser)    # (-vd: jobs decide unless their "voicing" says otherwise)
+    common.add_path_arguments(parser)       # (-mp: jobs take the match path unless their "match_path" says otherwise)
     return parser
 
 
@@ -237,6 +243,21 @@ def job_track(j, where, pitch_track=False, weight=common.TRACK_WEIGHT, jump=comm
     return base
 
 
+def job_path(j, where, match_path=False, weight=common.PATH_WEIGHT):
+    """an entry's "match_path" (default `match_path`): true, false or {"weight": W} (default `weight`) -> {"weight": W} as a float, or
+    None for a job whose match takes no path; ValueError otherwise"""
+    v = j.get("match_path", bool(match_path))
+    try:
+        base = dict(weight=common.path_param(weight))
+        if isinstance(v, dict):
+            base = common.path_options(dict(base, **v), "\"match_path\"")
+        elif not isinstance(v, bool):
+            raise ValueError(f"\"match_path\" must be true, false or an object with weight, got {v!r}")
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return None if v is False else base
+
+
 def job_voicing(j, where, voicing=False, on=common.VOICING_ON, off=common.VOICING_OFF, floor_db=common.VOICING_FLOOR_DB):
     """an entry's "voicing" (default `voicing`): true, false or {"on": R, "off": R, "floor_db": DB} (defaults `on`, `off`, `floor_db`)
     -> {"on": R, "off": R, "floor_db": DB} as floats, or None for a job that does not decide; ValueError otherwise, and together with
@@ -261,16 +282,19 @@ def job_voicing(j, where, voicing=False, on=common.VOICING_ON, off=common.VOICIN
 def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0,
               envelope_range_db=12.0, envelope_radius=1, auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT,
               track_jump=common.TRACK_JUMP, lufs=None, loudness_max_db=12.0, voicing=False, voicing_on=common.VOICING_ON,
-              voicing_off=common.VOICING_OFF, voicing_floor_db=common.VOICING_FLOOR_DB):
+              voicing_off=common.VOICING_OFF, voicing_floor_db=common.VOICING_FLOOR_DB, match_path=False,
+              path_weight=common.PATH_WEIGHT):
     """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder; "auto_pitch": default
     `auto_pitch`); a limited job ("limit_db", default `limit_db`) also carries "limit_db", a job without a limiter does not, so a
     file without the key loads to what it did; likewise "envelope" (default `envelope`) only on a job that follows at an amount above
     0, "auto_range" (default `auto_range`) only on a job that is on, "range_st" only where the entry has it and "pitch_track"
     (default `pitch_track` at `track_weight` / `track_jump`) only on a job that tracks and "lufs" (default `lufs`) only on a job that
-    is normalised and "voicing" (default `voicing` at `voicing_on` / `voicing_off` / `voicing_floor_db`) only on a job that decides;
+    is normalised and "voicing" (default `voicing` at `voicing_on` / `voicing_off` / `voicing_floor_db`) only on a job that decides and
+    "match_path" (default `match_path` at `path_weight`) only on a job whose match takes a path;
     ValueError on a malformed job, before anything runs on the device"""
     job_voicing({}, "-vd / --voicing-on / --voicing-off / --voicing-floor", voicing, voicing_on, voicing_off, voicing_floor_db)
     job_track({}, "-pt / --track-weight / --track-jump", pitch_track, track_weight, track_jump)
+    job_path({}, "-mp / --path-weight", match_path, path_weight)
     job_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, lookahead_ms, hold_ms)
     job_loudness({}, "-lufs / --loudness-max-db", lufs, loudness_max_db)
     env = (envelope_floor_db, envelope_range_db, envelope_radius)
@@ -288,10 +312,10 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
         if not isinstance(j, dict) or "input" not in j:
             raise ValueError(f"job {i}: an object with an \"input\" wav is required")
         unknown = (set(j) - set(JOB_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(RANGE_KEYS) - set(TRACK_KEYS)
-                   - set(LOUDNESS_KEYS) - set(VOICING_KEYS))
+                   - set(LOUDNESS_KEYS) - set(VOICING_KEYS) - set(PATH_KEYS))
         if unknown:
             raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS + TRACK_KEYS + LOUDNESS_KEYS + VOICING_KEYS})")
+                             f"{JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS + TRACK_KEYS + LOUDNESS_KEYS + VOICING_KEYS + PATH_KEYS})")
         blend = blend_sources(j, f"job {i}", rel) if "blend" in j else None
         if blend is None and j.get("target") is None and j.get("lib") is None:
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
@@ -324,6 +348,9 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
         decide = job_voicing(j, f"job {i}", voicing, voicing_on, voicing_off, voicing_floor_db)
         if decide is not None:
             e["voicing"] = decide
+        path_ = job_path(j, f"job {i}", match_path, path_weight)
+        if path_ is not None:
+            e["match_path"] = path_
         range_st = range_st_of(j, f"job {i}")
         if range_st is not None:
             e["range_st"] = range_st
@@ -384,11 +411,14 @@ def main(argv=None):
     try:
         tw, tj, lo, hi, band = common.track_arguments(args)             # (before anything is loaded)
         common.voicing_arguments(args)                                  # (likewise: --voicing-lo / --voicing-hi and the defaults)
+        common.path_arguments(args)
     except ValueError as e:
         raise SystemExit(str(e)) from None
     jobs = load_jobs(args.jobs, args.k, args.auto_pitch, args.limit, args.limit_lookahead, args.limit_hold, args.envelope,
                      args.envelope_floor, args.envelope_range, args.envelope_radius, args.auto_range, args.pitch_track, tw, tj,
-                     args.lufs, args.loudness_max_db, args.voicing, args.voicing_on, args.voicing_off, args.voicing_floor)
+                     args.lufs, args.loudness_max_db, args.voicing, args.voicing_on, args.voicing_off, args.voicing_floor,
+                     args.match_path, args.path_weight)
+    pathed = any("match_path" in j for j in jobs)
     tracked = any("pitch_track" in j for j in jobs)
     deciding = any("voicing" in j for j in jobs)
     on_auto = any(j["auto_pitch"] for j in jobs)
@@ -454,7 +484,8 @@ def main(argv=None):
                              **(dict(pitch_track=[dict(j["pitch_track"], lo=lo, hi=hi, band=band) if "pitch_track" in j else None
                                                   for j in jobs]) if tracked else {}),
                              **(dict(voicing=[dict(j["voicing"], lo=args.voicing_lo, hi=args.voicing_hi) if "voicing" in j else None
-                                              for j in jobs]) if deciding else {}), chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
+                                              for j in jobs]) if deciding else {}),
+                             **(dict(match_path=[j.get("match_path") for j in jobs]) if pathed else {}), chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)
     for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
         if job.get("envelope"):                                         # at 16 kHz, against the source the converter saw

@@ -88,6 +88,7 @@ def build_parser():
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV (this build only)")
     common.add_track_arguments(parser)
     common.add_voicing_arguments(parser)
+    common.add_path_arguments(parser)
     return parser
 
 
@@ -119,6 +120,10 @@ def main(argv=None):
         raise SystemExit(str(e))
     if voicing is not None and args.world_pitch_estimation:
         raise SystemExit("-vd cannot be combined with -wpe: WORLD makes its own voicing decision")
+    try:
+        match_path = common.path_arguments(args)                             # (before anything is loaded)
+    except ValueError as e:
+        raise SystemExit(str(e))
 
     PE, CE, Dec = F0Estimator().to(device), ContentEncoder().to(device), Decoder().to(device)
     PE.load_state_dict(torch.load(args.f0_estimator_path, map_location=device))
@@ -153,7 +158,8 @@ def main(argv=None):
                            world_pitch=bool(args.world_pitch_estimation), intonation=args.intonation, f0_rate=args.f0_rate, window_batch=args.window_batch,
                            trim_context=not args.no_trim_context,
                            share_overlap=None if args.no_share_overlap else "auto", **({} if track is None else dict(pitch_track=track)),
-                           **({} if voicing is None else dict(voicing={k: voicing[k] for k in common.VOICING_KEYS})))
+                           **({} if voicing is None else dict(voicing={k: voicing[k] for k in common.VOICING_KEYS})),
+                           **({} if match_path is None else dict(match_path=match_path)))
         if args.envelope > 0:                     # at 16 kHz, against the normalised mono source the converter saw
             out = follow_envelope(out, wf, None, args.envelope, *env)
         out = audio_io.resample(out, 16000, sr, post_gain_db=args.gain)            # resample, then gain (:136-137)

@@ -176,6 +176,9 @@ PROTOTYPES = {
     "alive_f0_track_rows": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_voicing_workspace_bytes": (_SZ, [_I, _I]),
     "alive_voicing_rows": (_I, [_VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "alive_knn_path_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "alive_knn_path_layout": (_I, [_I, _I, _I, _VP]),
+    "alive_knn_path_rows": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I64, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "alive_decoder_workspace_bytes": (_SZ, [_I, _I]),
     "alive_decoder_forward": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "alive_decoder_forward_range": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP]),

@@ -6,6 +6,7 @@
   compute_f0_rows(wf, row_on)                         compute_f0 of the rows a device mask switches on (the batched paths)
   pitch_track(lo=50, hi=1100, band=2.0, device=)      the tables of the pitch tracker (F0Estimator.estimate(track=); no counterpart)
   voicing_options(v, where="")                        the checked settings of the voicing decision (ops.voicing_rows_; no counterpart)
+  path_options(v, what="match_path")                  the checked settings of the match path (ops.knn_path_rows; no counterpart)
 
 runs on the MI355X through libalive_vc.so: fp6- (or fp8- / bf16-) MFMA candidate scoring with
 LDS-staged top-k' lists, exact fp32 rescoring, gather-mean-blend.  The library
@@ -689,6 +690,75 @@ def voicing_arguments(args):
     o = voicing_options(dict(on=args.voicing_on, off=args.voicing_off, floor_db=args.voicing_floor, lo=args.voicing_lo,
                              hi=args.voicing_hi), "-vd")
     return o if args.voicing else None
+
+
+# ---- match path: one library row per frame by a Viterbi path over the top-k lists (csrc/match_path.hip, DESIGN.md "Match path") -----
+PATH_WEIGHT = 1.0                               # in cosine units, like the target cost: a design choice, not tuned
+PATH_MAX_K = 8                                  # ALIVE_KNN_PATH_MAX_K
+PATH_MAX_FRAMES = 1 << 20                       # ALIVE_KNN_PATH_MAX_FRAMES: list rows x frames of one call
+PATH_CHUNK_BYTES = 256 << 20                    # Converter.match: the most workspace one call may take
+
+
+def path_param(v, name="weight"):
+    """the path's join weight from the host: a finite float >= 0"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (v >= 0.0 and v < float("inf")):
+        raise ValueError(f"match path: {name} must be a finite number >= 0 (in cosine units), got {v!r}")
+    return float(v)
+
+
+def path_options(v, what="match_path"):
+    """match_path=None | False | True | dict(weight=) -> None, or dict(weight=) filled in and checked"""
+    if v is None or v is False:
+        return None
+    if v is True:
+        v = {}
+    if not isinstance(v, dict):
+        raise ValueError(f"{what}: expected None, a bool or a dict of weight, got {v!r}")
+    unknown = set(v) - {"weight"}
+    if unknown:
+        raise ValueError(f"{what}: unknown keys {sorted(unknown)} (weight)")
+    return dict(weight=path_param(v.get("weight", PATH_WEIGHT)))
+
+
+def add_path_arguments(parser):
+    """the match path's flags, the same in every CLI that takes them: -mp and --path-weight"""
+    parser.add_argument('-mp', '--match-path', action='store_true',
+                        help="match path: one library row per frame, chosen out of the frame's k nearest by a Viterbi path that keeps "
+                             "consecutive rows close in the library's own feature space, instead of their mean (default: off; this "
+                             "build only)")
+    parser.add_argument('--path-weight', default=PATH_WEIGHT, type=float, metavar="W",
+                        help="match path: weight of the cosine between consecutive chosen rows against a candidate's cosine below the "
+                             f"frame's best one; 0 is the k = 1 match (default {PATH_WEIGHT})")
+
+
+def path_arguments(args):
+    """the parsed flags -> the checked options (path_options) when -mp is set, else None; refuses before anything is loaded"""
+    o = dict(weight=path_param(args.path_weight, "--path-weight"))
+    return o if args.match_path else None
+
+
+def knn_path_chunks(val, idx, k_row, k_max, on, weight, rows, norms):
+    """ops.knn_path_rows over any number of list rows: the call goes in chunks of rows whose workspace stays under PATH_CHUNK_BYTES
+    and whose frames stay within the call's limit (rows are independent: the chunking does not show) -> (val, idx, moved)"""
+    from . import ops
+    r = int(k_row.numel())
+    t = val.shape[0] // r
+    per = max(1, min(PATH_CHUNK_BYTES // (t * (8 * k_max * k_max + k_max) + 512), PATH_MAX_FRAMES // t))
+    if per >= r:
+        return ops.knn_path_rows(val, idx, k_row, k_max, on, weight, rows, norms)
+    parts = [ops.knn_path_rows(val[a * t:(a + per) * t], idx[a * t:(a + per) * t], k_row[a:a + per], k_max, on[a:a + per],
+                               weight[a:a + per], rows, norms) for a in range(0, r, per)]
+    return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
+
+
+def match_path(val, idx, n, k, weight, rows, norms):
+    """the path over the lists [n * T, k] of one search, every one of the n rows on at one weight -> (val, idx) [n * T, 1], the lists
+    of a k = 1 match, and moved [n]"""
+    dev = val.device
+    val, idx, moved = knn_path_chunks(val, idx, torch.full((n,), k, dtype=torch.int32, device=dev), k,
+                                      torch.ones(n, dtype=torch.int32, device=dev),
+                                      torch.full((n,), weight, dtype=torch.float64, device=dev), rows, norms)
+    return val[:, :1].contiguous(), idx[:, :1].contiguous(), moved
 
 
 def linear_resize(x, size):

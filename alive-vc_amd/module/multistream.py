@@ -201,6 +201,19 @@ world_pitch on one session (WORLD decides for itself).  voicing_state() reads ba
 frames set to 0 and r of the emitted centre frame.  The defaults (0.6, 0.45, -60 dB, 50 .. 500 Hz, 40 ms, 1, 2) are design choices:
 with no trained weights, what the decision does to perceived quality is unmeasured.
 
+Match path: every frame is matched on its own, and the mean of its k nearest rows is all the continuity the match has -- none at the
+k = 1 or 2 that a small voice or a codebook wants.  A converter built with match_path=True (csrc/match_path.hip) always runs the
+per-row-k entry points (k_max defaults to k) and puts ONE call between the grouped search and the gather: for the sessions opened or
+set with match_path=True it chooses, out of each frame's k candidates, one row per frame by a Viterbi path over the ring's frames --
+a candidate costs its cosine below the frame's best one, a step earns path_weight times the cosine between the two chosen rows, in
+fp64 (tools/match_path_ref.py restates it bit for bit) -- and the gather reads gather_k, 1 on those slots and the slot's k on the
+others, beside k_rows.  A blend's lists each take their own path.  path_weight = 0 is the k = 1 match.  The call is stateless over
+the ring, like the tracker: nothing is carried across ticks, the bf16 repeat or a capture; a gated row has no match and passes
+through, and a sparse converter's row that sits a tick out keeps its count.  on and weight are device arrays: toggling and retuning
+never re-capture; a converter built without match_path allocates nothing, launches exactly what it did and refuses match_path=True.
+path_moved() reads back how many frames of each ring the path moved off the nearest row.  The default weight (1.0, in cosine units)
+is a design choice: with no trained weights, what the path does to perceived quality is unmeasured.
+
 Loudness: every path leaves the converted voice at the level of the library rows it selected.  measure_loudness / normalize_loudness
 (csrc/loudness.hip) are the integrated loudness of ITU-R BS.1770-4 / EBU R 128 for one channel -- K-weighting, 400-ms blocks every 100
 ms, the absolute gate at -70 LUFS and the relative one 10 LU below the gated mean -- and the one gain per row that brings it to a
@@ -1093,6 +1106,9 @@ def blend_gather_rows_k(val, idx, k_row, k_max, first, weight, alpha, rows, sour
     return out
 
 
+knn_path_rows = ops.knn_path_rows       # the path between a per-row-k search and its gather (csrc/match_path.hip)
+
+
 def check_k(k, what="k", hi=MAX_K):
     """a k of the batched paths: an int (not a bool) in [1, hi] -> int; ValueError otherwise"""
     if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= hi:
@@ -1963,7 +1979,8 @@ def db_scale(db):
 
 _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold",
            "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope", "conceal", "intonation", "auto_range",
-           "pitch_track", "track_weight", "track_jump", "lufs", "voicing", "voicing_on", "voicing_off", "voicing_floor_db")
+           "pitch_track", "track_weight", "track_jump", "lufs", "voicing", "voicing_on", "voicing_off", "voicing_floor_db",
+           "match_path", "path_weight")
 
 
 class MultiStreamConverter:
@@ -1978,6 +1995,7 @@ class MultiStreamConverter:
     pitch_track = False                # (likewise: whether the f0 branch stores the class scores and carries the tracker kernel)
     loud = False                       # (likewise: whether the tick carries the loudness kernel; loudness() is the read-back)
     voicing = False                    # (likewise: whether the f0 branch carries the voicing kernels; voicing_state() is the read-back)
+    match_path = False                 # (likewise: whether the path call sits between the search and the gather; path_moved() reads back)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
@@ -1988,7 +2006,9 @@ class MultiStreamConverter:
                  track_band=2.0, loudness=False, loudness_half_life=3.0, loudness_prior=1.0, loudness_gate_lufs=LOUDNESS_GATE_LUFS,
                  loudness_max_db=12.0, loudness_slew_db=6.0, voicing=False, voicing_lo=common.VOICING_LO, voicing_hi=common.VOICING_HI,
                  voicing_window_ms=common.VOICING_WINDOW_MS, voicing_bridge=common.VOICING_BRIDGE,
-                 voicing_min_run=common.VOICING_MIN_RUN):
+                 voicing_min_run=common.VOICING_MIN_RUN, match_path=False):
+        if not isinstance(match_path, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: match_path must be a bool, got {match_path!r}")
         if not isinstance(voicing, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: voicing must be a bool, got {voicing!r}")
         if voicing:                        # (checked before anything is built)
@@ -2059,6 +2079,8 @@ class MultiStreamConverter:
             raise ValueError(f"MultiStreamConverter: auto_pitch_prior={auto_pitch_prior!r} must be >= 0 seconds")
         if not 1 <= int(k) <= MAX_K:
             raise ValueError(f"MultiStreamConverter: k={k} outside [1, {MAX_K}] (the grouped search keeps k <= 8)")
+        if match_path and k_max is None:   # the path call reads and the gathers after it take a k per row: the per-row-k entry points
+            k_max = int(k)
         if k_max is not None:
             k_max = check_k(k_max, "MultiStreamConverter: k_max")
             if k_max < int(k):
@@ -2133,6 +2155,17 @@ class MultiStreamConverter:
         if self.k_max is not None:         # the slot's k, and (blend) the same on each of its list rows for the search
             self.k_rows = torch.full((B,), self.k, dtype=torch.int32, device=dev)
             self.k_lists = self.k_rows if self.S == 1 else torch.full((B * self.S,), self.k, dtype=torch.int32, device=dev)
+        # match_path: the path call (csrc/match_path.hip) sits between the search and the gather and is part of the tick (captured
+        # once); per list row, path_on selects ONE of the frame's k_rows candidates per frame by a Viterbi path over the ring's frames,
+        # at the session's weight, and gather_k -- 1 where the path is on, the slot's k otherwise -- is what the gather reads beside
+        # k_rows.  No state: the call is a function of the tick's lists.
+        self.match_path = bool(match_path)
+        if self.match_path:
+            self.gather_k = torch.full((B,), self.k, dtype=torch.int32, device=dev)
+            self.path_on = torch.zeros(B * self.S, dtype=torch.int32, device=dev)
+            self.path_weight = torch.full((B * self.S,), common.PATH_WEIGHT, dtype=torch.float64, device=dev)
+            self.path_moved_rows = torch.zeros(B * self.S, dtype=torch.int32, device=dev)
+            self._path_moved_tick = torch.zeros(B * self.S, dtype=torch.int32, device=dev)      # (a sparse converter's: the call's own)
         self.alpha = torch.zeros(B, dtype=torch.float64, device=dev)
         self.f0_rate = torch.ones(B, dtype=torch.float32, device=dev)
         self.pitch = torch.zeros(B, dtype=torch.float32, device=dev)
@@ -2505,6 +2538,34 @@ class MultiStreamConverter:
                              "class scores")
         return int(bool(on)), w, j
 
+    def _session_path(self, slot, p):
+        """a session's match path settings -> (on, weight), checked against the converter"""
+        on = p.get("match_path", False)
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"slot {slot}: match_path must be a bool, got {on!r}")
+        try:
+            w = common.path_param(p.get("path_weight", common.PATH_WEIGHT), "path_weight")
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+        if on and not self.match_path:
+            raise ValueError(f"slot {slot}: match_path=True needs a converter built with MultiStreamConverter(..., match_path=True)")
+        return int(bool(on)), w
+
+    def path_moved(self):
+        """how many frames of each slot's ring the path moved off the frame's nearest row in the latest tick (a blend: over all its
+        lists), a list of B ints; 0 for a slot without the path (or closed).  One host read"""
+        if not self.match_path:
+            raise ValueError("path_moved needs a converter built with MultiStreamConverter(..., match_path=True)")
+        moved = self.path_moved_rows.view(self.B, self.S).sum(dim=1).tolist()
+        return [moved[b] if self.is_open[b] and self.params[b].get("match_path", False) else 0 for b in range(self.B)]
+
+    def _set_path(self, slot, on, weight, k):
+        rows = slice(slot * self.S, (slot + 1) * self.S)
+        self.path_on[rows], self.path_weight[rows] = on, weight
+        self.gather_k[slot] = 1 if on else k
+        if not on:
+            self.path_moved_rows[rows] = 0
+
     def _session_voicing(self, slot, p):
         """a session's voicing settings -> (on, thr_on, thr_off, floor_e), checked against the converter"""
         on = p.get("voicing", False)
@@ -2560,6 +2621,7 @@ class MultiStreamConverter:
         con = self._session_conceal(slot, p, rate)
         track = self._session_track(slot, p)
         voicing = self._session_voicing(slot, p)
+        path = self._session_path(slot, p)
         loud = self._session_loudness(slot, p, rate)
         names, weights = blend_spec(p["voice"], self.pool, k, self.S)
         world = p["world_pitch"]
@@ -2601,6 +2663,8 @@ class MultiStreamConverter:
             self.k_rows[slot] = k
             if self.S > 1:
                 self.k_lists[slot * self.S:(slot + 1) * self.S] = k
+        if self.match_path:
+            self._set_path(slot, path[0], path[1], k)
         self.alpha[slot] = float(p["alpha"])
         self.f0_rate[slot] = float(p["f0_rate"])
         self.pitch[slot] = float(p["pitch"])
@@ -2713,7 +2777,7 @@ class MultiStreamConverter:
              auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0,
              limit_hold_ms=20.0, envelope=0.0, conceal=None, intonation=1.0, auto_range=False, pitch_track=False, track_weight=1.0,
              track_jump=12.0, lufs=None, voicing=False, voicing_on=common.VOICING_ON, voicing_off=common.VOICING_OFF,
-             voicing_floor_db=common.VOICING_FLOOR_DB):
+             voicing_floor_db=common.VOICING_FLOOR_DB, match_path=False, path_weight=common.PATH_WEIGHT):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
@@ -2745,7 +2809,10 @@ class MultiStreamConverter:
         when its best normalised correlation reaches voicing_on and unvoiced under voicing_off (0 < off <= on <= 1), and a frame under
         voicing_floor_db dBFS is unvoiced whatever its correlation.
         lufs (needs a loudness=True converter): the session's loudness target in LUFS, -70 < lufs <= 0 (None: the session's level is
-        left alone): what the session emits is brought to it by a running BS.1770 loudness and a slewed gain, ahead of the limiter"""
+        left alone): what the session emits is brought to it by a running BS.1770 loudness and a slewed gain, ahead of the limiter.
+        match_path=True (needs a match_path=True converter): each frame's matched feature is ONE of its k nearest rows, chosen by a
+        Viterbi path over the ring's frames that weighs the cosine between consecutive chosen rows by path_weight (>= 0; 0 is the
+        k = 1 match) against a candidate's cosine below the frame's best one; a blend: every voice's list takes its own path"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
@@ -2756,7 +2823,7 @@ class MultiStreamConverter:
                  limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms, envelope=envelope, conceal=conceal,
                  intonation=intonation, auto_range=auto_range, pitch_track=pitch_track, track_weight=track_weight,
                  track_jump=track_jump, lufs=lufs, voicing=voicing, voicing_on=voicing_on, voicing_off=voicing_off,
-                 voicing_floor_db=voicing_floor_db)
+                 voicing_floor_db=voicing_floor_db, match_path=match_path, path_weight=path_weight)
         self._apply(slot, p, rate)                            # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -2779,7 +2846,7 @@ class MultiStreamConverter:
 
     def set(self, slot, **params):
         """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
-        intonation, auto_range, pitch_track, track_weight, track_jump, voicing, voicing_on, voicing_off, voicing_floor_db, gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms,
+        intonation, auto_range, pitch_track, track_weight, track_jump, voicing, voicing_on, voicing_off, voicing_floor_db, match_path, path_weight, gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms,
         limit_hold_ms, envelope, conceal, lufs; the gate's state, the saved tail, the running loudness with its gain and the
         limiter's history are kept: a longer crossfade fades over what the tail holds this tick and in full from the next, and a
         limiter switched on or retuned sees the required gains of the samples already emitted).
@@ -2809,6 +2876,8 @@ class MultiStreamConverter:
             self.k_rows[slot] = self.k
             if self.S > 1:
                 self.k_lists[slot * self.S:(slot + 1) * self.S] = self.k
+        if self.match_path:
+            self._set_path(slot, 0, common.PATH_WEIGHT, self.k)
         self._hold(slot, ())
         self.phi[slot] = 0.0
         if self.world_pitch:
@@ -2988,7 +3057,21 @@ class MultiStreamConverter:
             # -c 960 -b 8, for a tracker call of 0.6 ms; DESIGN.md 5.4 "Pitch tracking")
             join()
         K = self.k_max
-        if self.S == 1:
+        if self.match_path:                                   # the per-row-k search, the path over its lists, the gather at gather_k
+            b, d, t = content.shape
+            rep = content if self.S == 1 else content.unsqueeze(1).expand(b, self.S, d, t).reshape(b * self.S, d, t).contiguous()
+            val, idx = knn_search_grouped_k(rep, self.pool.rows, self.pool.norms, self.seg_lo, seg_len, self.k_lists, K)
+            # (a sparse converter's rows that do not emit this tick -- filling, stalled -- search nothing: their count stands)
+            val, idx, moved = knn_path_rows(val, idx, self.k_lists, K, self.path_on, self.path_weight, self.pool.rows, self.pool.norms,
+                                            moved=self._path_moved_tick if self.sparse else self.path_moved_rows)
+            if self.sparse:
+                emit = self.emit.expand(b, self.S).reshape(b * self.S)
+                self.path_moved_rows.copy_(torch.where(emit, moved, self.path_moved_rows))
+            if self.S == 1:
+                content = merge_gather_rows_k(val, idx, self.gather_k, K, self.alpha, self.pool.rows, content)
+            else:
+                content = blend_gather_rows_k(val, idx, self.gather_k, K, self.first, self.weight, self.alpha, self.pool.rows, content)
+        elif self.S == 1:
             if K is None:
                 val, idx = knn_search_grouped(content, self.pool.rows, self.pool.norms, self.seg_lo, seg_len, self.k)
                 content = merge_gather_rows(val, idx, self.k, self.alpha, self.pool.rows, content)

@@ -306,6 +306,42 @@ def voicing_rows_(f0, x, opts, on=None, thr_on=None, thr_off=None, floor_e=None,
     return f0
 
 
+# ---- match path (csrc/match_path.hip) --------------------------------------------------------------------------------------------
+PATH_MAX_K, PATH_MAX_FRAMES = 8, 1 << 20         # ALIVE_KNN_PATH_MAX_K, ALIVE_KNN_PATH_MAX_FRAMES
+_path_ws = nat.Workspace()
+
+
+def knn_path_rows(val, idx, k_row, k_max, on, weight, rows, norms, moved=None):
+    """alive_knn_path_rows: top-k lists val fp32 / idx int32 [R * T, k_max] (R = len(k_row) list rows of T frames, as every search form
+    returns them) -> (out_val, out_idx) of the same shape with ONE entry per frame, the path's (csrc/match_path.hip), ready for any
+    gather at k = 1.  k_row, on: device int32 [R]; weight: device float64 [R]; moved: device int32 [R] or None (allocated), returned
+    third.  rows fp32 [P, 768] / norms fp32 [P]: the table the indices point into.  No host synchronisation and no allocation beyond
+    the outputs once the stream's workspace exists: capturable."""
+    if val.dtype != torch.float32 or idx.dtype != torch.int32 or val.dim() != 2 or val.shape != idx.shape or val.shape[1] != int(k_max):
+        raise ValueError(f"match path: lists must be fp32 / int32 [R * T, {k_max}] tensors, got {tuple(val.shape)} / {tuple(idx.shape)}")
+    r = int(k_row.numel())
+    if r < 1 or val.shape[0] % r:
+        raise ValueError(f"match path: {val.shape[0]} list frames do not divide into {r} rows")
+    t = val.shape[0] // r
+    if not (1 <= int(k_max) <= PATH_MAX_K) or r * t > PATH_MAX_FRAMES:
+        raise ValueError(f"match path: k_max {k_max} outside [1, {PATH_MAX_K}] or {r} x {t} frames exceed {PATH_MAX_FRAMES}")
+    if moved is None:
+        moved = torch.empty(r, dtype=torch.int32, device=val.device)
+    for name, v, dtype in (("k_row", k_row, torch.int32), ("on", on, torch.int32), ("weight", weight, torch.float64),
+                           ("moved", moved, torch.int32)):
+        if not torch.is_tensor(v) or v.dtype != dtype or v.numel() != r or not v.is_contiguous():
+            raise ValueError(f"match path: {name} must be a contiguous {dtype} [{r}] device array")
+    if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != 768 or norms.dtype != torch.float32 or norms.numel() != rows.shape[0]:
+        raise ValueError(f"match path: rows must be fp32 [P, 768] with norms fp32 [P], got {tuple(rows.shape)} / {tuple(norms.shape)}")
+    L = nat.lib()
+    out_val, out_idx = torch.empty_like(val), torch.empty_like(idx)
+    ws = _path_ws.get(L.alive_knn_path_workspace_bytes(r, t, int(k_max)), val.device)
+    nat.check(L.alive_knn_path_rows(nat.ptr(val), nat.ptr(idx), nat.ptr(k_row), int(k_max), nat.ptr(on), nat.ptr(weight), nat.ptr(rows),
+                                    nat.ptr(norms), int(rows.shape[0]), r, t, nat.ptr(out_val), nat.ptr(out_idx), nat.ptr(moved),
+                                    nat.ptr(ws), nat.stream()), "alive_knn_path_rows")
+    return out_val, out_idx, moved
+
+
 def _out_like(x, out):
     """the output of a FilterBlock call: a new tensor, or the caller's (a test's, pre-filled)"""
     if out is None:

@@ -274,10 +274,15 @@ class Converter:
         self.last_front_end_frames = m * nu                     # frames that went through the match
         return feat, f0
 
-    def match(self, feat, k=4, alpha=0.0):
+    def match(self, feat, k=4, alpha=0.0, path=None):
+        """path (common.path_options): instead of the mean of each frame's k nearest rows, ONE of them per frame, chosen by a Viterbi
+        path over every window's lists (common.match_path, csrc/match_path.hip), gathered as a k = 1 match"""
         self._subspace()
         val, idx = self.library.search(feat, k)
-        return merge_gather(val, idx, 1, k, alpha, self.library.rows, feat)
+        if path is None:
+            return merge_gather(val, idx, 1, k, alpha, self.library.rows, feat)
+        val, idx, self.last_path_moved = common.match_path(val, idx, feat.shape[0], k, path["weight"], self.library.rows, self.library.norms)
+        return merge_gather(val, idx, 1, 1, alpha, self.library.rows, feat)
 
     def convert_windows(self, windows, *a, **kw):
         """`_convert_windows` (below: same arguments) under the fp16 range guard (ops.Fp16Guard): the saturation counters of the fp16
@@ -289,8 +294,12 @@ class Converter:
     def _agree_on_saturations(self):
         return None                       # one process, one decision (ShardedConverter: max over the ranks)
 
+    def _path_options(self, match_path):
+        """the checked match_path option of a call (ShardedConverter refuses it)"""
+        return common.path_options(match_path)
+
     def _convert_windows(self, windows, k=4, alpha=0.0, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, window_batch=64,
-                         keep_frames=None, share_overlap=None, world_pitch=False, pitch_track=None, voicing=None):
+                         keep_frames=None, share_overlap=None, world_pitch=False, pitch_track=None, voicing=None, match_path=None):
         """windows [n, L] on the device -> waveforms [n, L]; L a multiple of 320.
         Networks run in batches of `window_batch` windows (bounded scratch); the kNN match runs ONCE over the frames
         of all windows, so every library tile streamed from L2 is used by as many frames as possible.
@@ -304,7 +313,12 @@ class Converter:
         estimator's class scores (features); it rides where world_pitch does -- per-window front end, no overlap sharing, f0
         over the whole window also with keep_frames -- and cannot be combined with it.
         voicing=True | dict(on=, off=, floor_db=, lo=, hi=, window_ms=, bridge=, min_run=): the f0 of the frames of every whole window
-        that are not periodic becomes 0 (features); it rides where pitch_track does and cannot be combined with world_pitch."""
+        that are not periodic becomes 0 (features); it rides where pitch_track does and cannot be combined with world_pitch.
+        match_path=True | dict(weight=): the matched feature of a frame is ONE of its k nearest library rows, chosen by a Viterbi path
+        over the window (match(path=)) -- per-window front end, no overlap sharing.  The path depends on every frame of its window, so
+        with keep_frames the match still covers the whole window and trimming applies to the decoder alone: the kept samples are
+        bitwise the same with and without it."""
+        match_path = self._path_options(match_path)
         voicing = common.voicing_options(voicing)
         if voicing is not None and world_pitch:
             raise ValueError("voicing cannot be combined with world_pitch: WORLD makes its own voicing decision")
@@ -321,7 +335,8 @@ class Converter:
         rng = _decoded_range(keep_frames, lf)
         # sharing and trimming together need the trimmed range to consist of interior frames of the signal (it does for the
         # centre third of a 3-chunk window from 46 frames per chunk on); otherwise trimming alone is used -- same samples
-        share_ok = bool(share_overlap) and n * (EDGE + NET_MARGIN) >= 96 and not world_pitch and pitch_track is None and voicing is None
+        share_ok = (bool(share_overlap) and n * (EDGE + NET_MARGIN) >= 96 and not world_pitch and pitch_track is None and voicing is None
+                    and match_path is None)
         if share_ok and (rng is None or (EDGE <= rng[0] and rng[1] <= lf - EDGE and rng[1] - rng[0] >= 5)):
             # share_overlap = windows per signal (make_windows order): front end once per signal, decoder per window
             feat, f0 = self.features_shared(windows, int(share_overlap), k, alpha, frames=rng)
@@ -330,7 +345,7 @@ class Converter:
 
         def encode(i, feat, f0):                            # the pitch transform included (features)
             b = slice(i, i + window_batch)
-            if rng is None:                                 # the networks write straight into the batch's slices
+            if rng is None or match_path is not None:       # the networks write straight into the batch's slices
                 self.features(windows[b], pitch_shift, intonation, f0_rate, out=(feat[b], f0[b]), world_pitch=world_pitch,
                               pitch_track=pitch_track, voicing=voicing)
             else:
@@ -338,6 +353,9 @@ class Converter:
                                                pitch_track=pitch_track, voicing=voicing)
 
         def match(feat):                                    # (ShardedConverter overrides self.match)
+            if match_path is not None:                      # the path runs over the whole window; the decoder takes its range of it
+                out = self.match(feat, k, alpha, path=match_path)
+                return out if rng is None else out[:, :, rng[0]:rng[1]]
             if rng is None:
                 return self.match(feat, k, alpha)
             feat[:, :, rng[0]:rng[1]] = self.match(feat[:, :, rng[0]:rng[1]].contiguous(), k, alpha)
@@ -420,7 +438,7 @@ class Converter:
 
     def convert_many(self, utterances, pool, voices, pitch_shift=0.0, intonation=1.0, f0_rate=1.0, alpha=0.0, chunk=48000, k=4,
                      window_batch=64, trim_context=False, world_pitch=False, auto_pitch=False, auto_range=False,
-                     pitch_range_max=2.0, pitch_track=None, voicing=None):
+                     pitch_range_max=2.0, pitch_track=None, voicing=None, match_path=None):
         """Many-to-many batch conversion: utterance i (16 kHz, [L] or [1, L], any length) to voice voices[i] of `pool`
         (module/multistream.py: VoicePool), with per-utterance pitch_shift / intonation / f0_rate / alpha / world_pitch (a scalar
         applies to every utterance; world_pitch: WORLD's f0 of each whole window, as convert(world_pitch=True)).  Returns one [1, L_i] waveform per utterance.  The windows of ALL utterances form one batch (a network
@@ -461,7 +479,13 @@ class Converter:
         utterances must agree on them; not together with world_pitch).  One alive_voicing_rows call per window batch over the rows
         that are on, each with its utterance's thresholds, after the tracker and before the transform -- auto pitch and auto range
         measure the voiced contour.  A row's decision depends on its own window only; a corpus without a deciding utterance launches
-        the present path."""
+        the present path.
+        match_path (None / a bool / dict(weight=), or one per utterance): the matched feature of utterance i's frames is ONE of their
+        k_i nearest rows, chosen by a Viterbi path over each of its whole windows, as convert(match_path=...) of it alone.  The pool
+        search runs as it does; ONE path call (alive_knn_path_rows) then takes every list row with its utterance's switch and weight
+        (a blend: every list of a window its own path), and the per-row-k gathers run at a gather-k of 1 on the path's rows.  With
+        trim_context the match covers the whole windows and trimming applies to the decoder alone.  A row's path depends on its own
+        lists only; a corpus without such an utterance launches the present path."""
         from . import multistream as MS
         m = len(utterances)
         voices = list(voices)
@@ -513,6 +537,11 @@ class Converter:
                 raise ValueError("voicing: lo, hi, window_ms, bridge and min_run are call-wide, the deciding utterances ask for "
                                  f"{sorted(wide)}")
             voicing_wide = next(v for v in voicings if v is not None)
+        paths = list(match_path) if isinstance(match_path, (list, tuple)) else [match_path] * m
+        if len(paths) != m:
+            raise ValueError(f"match_path: {len(paths)} values for {m} utterances")
+        paths = [common.path_options(v, f"convert_many: match_path[{i}]") for i, v in enumerate(paths)]
+        pathed = any(v is not None for v in paths)
         autos = list(auto_pitch) if isinstance(auto_pitch, (list, tuple)) else [auto_pitch] * m
         if len(autos) != m:
             raise ValueError(f"auto_pitch: {len(autos)} values for {m} utterances")
@@ -573,6 +602,16 @@ class Converter:
                           weight=torch.tensor(lweights, dtype=torch.float64, device=self.device))
             if ks is not None:
                 params["k_lists"] = params["k"].index_select(0, params["owner"]).contiguous()
+        if pathed:                          # per window: its search k, whether its lists take a path and at what weight, its gather k
+            ku = [k] * m if ks is None else ks
+            k_win = rows(ku, torch.int32)
+            on_win = rows([int(v is not None) for v in paths], torch.int32)
+            w_win = rows([v["weight"] if v is not None else 0.0 for v in paths], torch.float64)
+            params["path"] = dict(k=k_win, on=on_win, weight=w_win,
+                                  gather_k=rows([1 if v is not None else kk for v, kk in zip(paths, ku)], torch.int32))
+            if blended:                     # every list row of a window: its owner's
+                params["path"].update({key: params["path"][key].index_select(0, params["owner"]).contiguous()
+                                       for key in ("k", "on", "weight")})
         # the WORLD windows of every window batch (batch-local row indices, on the device before the batches start)
         on = [bool(w) for w, c in zip(worlds, counts) for _ in range(c)]
         params["world"] = {i: torch.tensor([j - i for j in range(i, min(i + window_batch, len(on))) if on[j]], dtype=torch.int64,
@@ -613,7 +652,7 @@ class Converter:
 
         def encode(i, feat, f0):
             b = slice(i, i + window_batch)
-            if rng is None:
+            if rng is None or pathed:       # (a path runs over the whole window: every frame's features)
                 ops.front_end(windows[b], self.ce, self.pe, out=(feat[b], f0[b]))
             else:
                 spec = spectrogram(windows[b])
@@ -647,14 +686,11 @@ class Converter:
                 shift = MS.pitch_shift_groups(stats, au["first"], f0.shape[0], au["offset"], au["on"], au["target"])
             MS.pitch_transform_rows_(f0, 0, params["rate"], shift, params["inton"])
 
-        def match(feat):
-            src = feat if rng is None else feat[:, :, rng[0]:rng[1]].contiguous()
+        def search(src):                    # every window's lists, at stride k (a blend: one list row per voice of the window)
             if not blended:
                 if ks is None:
-                    val, idx = MS.knn_search_pool(src, pool, params["ids"], k)
-                    return MS.merge_gather_rows(val, idx, k, params["alpha"], pool.rows, src)
-                val, idx = MS.knn_search_pool_k(src, pool, params["ids"], params["k"], k)
-                return MS.merge_gather_rows_k(val, idx, params["k"], k, params["alpha"], pool.rows, src)
+                    return MS.knn_search_pool(src, pool, params["ids"], k)
+                return MS.knn_search_pool_k(src, pool, params["ids"], params["k"], k)
             src_v = src.index_select(0, params["owner"])
             R, _, t = src_v.shape
             step = max(1, min(MS.POOL_PIECE_ROWS, MS.POOL_PIECE_FRAMES // t))
@@ -663,8 +699,27 @@ class Converter:
             else:
                 pieces = [MS.knn_search_pool_k(src_v[a:a + step], pool, params["ids"][a:a + step],
                                                params["k_lists"][a:a + step].contiguous(), k) for a in range(0, R, step)]
-            val = pieces[0][0] if len(pieces) == 1 else torch.cat([p[0] for p in pieces])
-            idx = pieces[0][1] if len(pieces) == 1 else torch.cat([p[1] for p in pieces])
+            if len(pieces) == 1:
+                return pieces[0]
+            return torch.cat([p[0] for p in pieces]), torch.cat([p[1] for p in pieces])
+
+        def match(feat):
+            if pathed:                      # over the whole windows: the path call on the lists, the per-row-k gathers at the gather k
+                pa = params["path"]
+                val, idx = search(feat)
+                val, idx, _ = common.knn_path_chunks(val, idx, pa["k"], k, pa["on"], pa["weight"], pool.rows, pool.norms)
+                if not blended:
+                    out = MS.merge_gather_rows_k(val, idx, pa["gather_k"], k, params["alpha"], pool.rows, feat)
+                else:
+                    out = MS.blend_gather_rows_k(val, idx, pa["gather_k"], k, params["first"], params["weight"], params["alpha"],
+                                                 pool.rows, feat)
+                return out if rng is None else out[:, :, rng[0]:rng[1]]
+            src = feat if rng is None else feat[:, :, rng[0]:rng[1]].contiguous()
+            val, idx = search(src)
+            if not blended:
+                if ks is None:
+                    return MS.merge_gather_rows(val, idx, k, params["alpha"], pool.rows, src)
+                return MS.merge_gather_rows_k(val, idx, params["k"], k, params["alpha"], pool.rows, src)
             if ks is None:
                 return MS.blend_gather_rows(val, idx, k, params["first"], params["weight"], params["alpha"], pool.rows, src)
             return MS.blend_gather_rows_k(val, idx, params["k"], k, params["first"], params["weight"], params["alpha"], pool.rows,

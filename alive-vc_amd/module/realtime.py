@@ -150,14 +150,19 @@ class RealtimeConverter:
     pitch_range = False                # (likewise: whether the f0 branch runs the pitch-range follower and the centred transform)
     pitch_track = False                # (likewise: whether the f0 branch stores the class scores and runs the tracker kernel)
     voicing = False                    # (likewise: whether the f0 branch runs the voicing kernels; voicing_state() is the read-back)
+    match_path = False                 # (likewise: whether the path call sits between the search and the gather; path_moved() reads back)
 
     def __init__(self, content_encoder, f0_estimator, decoder, library_tokens, device="cuda", chunk=960, buffersize=8,
                  input_sr=16000, output_sr=16000, f0_rate=1.0, pitch=0.0, k=4, alpha=0.0, gain=0.0, input_gain=0.0,
                  reuse_interior="auto", world_pitch=False, gate_db=None, gate_hold=0.2, gate_lookahead=None,
                  crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0, limit_hold_ms=20.0, limit_history=0.05,
                  envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0, envelope_radius=1, intonation=1.0,
-                 intonation_half_life=10.0, intonation_prior=0.5, pitch_track=None, voicing=None):
+                 intonation_half_life=10.0, intonation_prior=0.5, pitch_track=None, voicing=None, match_path=None):
         self.device = torch.device(device)
+        path = common.path_options(match_path, "RealtimeConverter: match_path")
+        self.match_path = path is not None                  # (checked before anything is built)
+        if self.match_path and reuse_interior is True:
+            raise ValueError("interior reuse cannot be combined with match_path: a frame's chosen row depends on the whole ring")
         voicing = common.voicing_options(voicing, "RealtimeConverter")
         self.voicing = voicing is not None                  # (checked before anything is built)
         if self.voicing:
@@ -298,6 +303,14 @@ class RealtimeConverter:
             self._track_jump = torch.tensor([track["jump"]], dtype=torch.float64, device=dev)
             self._track_changed = torch.zeros(1, dtype=torch.int32, device=dev)
             self._track_bufs = {}
+        if self.match_path:
+            # the multi-session path call at one row, between the search and the gather; no state: the whole ring's path every step
+            dev = self.device
+            self.path_weight = path["weight"]
+            self._path_k = torch.full((1,), int(k), dtype=torch.int32, device=dev)
+            self._path_on = torch.ones(1, dtype=torch.int32, device=dev)
+            self._path_weight = torch.tensor([path["weight"]], dtype=torch.float64, device=dev)
+            self._path_moved = torch.zeros(1, dtype=torch.int32, device=dev)
         if self.voicing:
             # the multi-session detector at one row; no state: it looks at the whole ring again every step
             dev = self.device
@@ -333,6 +346,9 @@ class RealtimeConverter:
             fits = False
         # voicing: hysteresis, bridge and minimum run make a frame's decision depend on the ring around it -- interior reuse is off
         if self.voicing:
+            fits = False
+        # match_path: a frame's chosen row depends on the whole ring (the path is decoded again every step) -- interior reuse is off
+        if self.match_path:
             fits = False
         if reuse_interior is True and not fits:
             raise ValueError("interior reuse needs input_sr 16000, chunk a multiple of 320 and a ring of at least 70 + chunk / 320 "
@@ -430,6 +446,12 @@ class RealtimeConverter:
             raise ValueError("pitch_track_changed needs a converter built with RealtimeConverter(..., pitch_track=True)")
         return int(self._track_changed.tolist()[0])
 
+    def path_moved(self):
+        """how many frames of the ring the match path moved off the frame's nearest row in the latest step (one host read)"""
+        if not self.match_path:
+            raise ValueError("path_moved needs a converter built with RealtimeConverter(..., match_path=True)")
+        return int(self._path_moved.tolist()[0])
+
     def voicing_state(self):
         """the voicing decision of the latest step: (voiced frames of the ring, frames whose f0 was set to 0, r of the centre frame of
         the emitted span), read back from the device"""
@@ -476,7 +498,12 @@ class RealtimeConverter:
         f0, join = self._f0_on_side_stream(spec, data)
         content = self.ce(spec)
         val, idx = self.lib.search(content, self.k)
-        out = merge_gather(val, idx, 1, self.k, self.alpha, self.lib.rows, content)
+        if self.match_path:                # one row per frame, chosen by the path over the ring's lists, gathered as a k = 1 match
+            val, idx, _ = ops.knn_path_rows(val, idx, self._path_k, self.k, self._path_on, self._path_weight, self.lib.rows,
+                                            self.lib.norms, moved=self._path_moved)
+            out = merge_gather(val[:, :1].contiguous(), idx[:, :1].contiguous(), 1, 1, self.alpha, self.lib.rows, content)
+        else:
+            out = merge_gather(val, idx, 1, self.k, self.alpha, self.lib.rows, content)
         join()
         return out, f0
 

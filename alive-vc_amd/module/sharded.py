@@ -159,6 +159,12 @@ class ShardedConverter(Converter):
                              "share_overlap=None")
         return super().convert_windows(windows, *a, share_overlap=None, **kw)
 
+    def _path_options(self, match_path):
+        # the path needs the rows and norms of every candidate of a window on one device; the slabs hold their own rows only
+        if match_path is not None and match_path is not False:
+            raise ValueError("match_path is not available with a sharded library: use the replicated Converter")
+        return None
+
     def _agree_on_saturations(self):
         # the fp16 range guard (ops.Fp16Guard) repeats a saturated batch -- through the exchange collectives: all ranks or none
         def agree(n):

@@ -21,6 +21,9 @@ The sessions file is a JSON list; each entry:
    "pitch_track": true,                   optional, a JSON bool (default: -pt): the session's f0 is the Viterbi path over the f0
                                           estimator's class scores of its ring instead of their per-frame argmax
                                           (module/multistream.py "Pitch tracking"); not with "world_pitch"
+   "match_path": true, "path_weight": 1,  optional, a JSON bool (default: -mp) and a number >= 0 (default: --path-weight): each frame's
+                                          matched feature is ONE of its k nearest rows, chosen by a Viterbi path over the ring
+                                          (MultiStreamConverter.open(match_path=, path_weight=))
    "track_weight": 1, "track_jump": 12,   optional, numbers >= 0 (defaults: --track-weight / --track-jump): the tracker's cost per
                                           semitone moved inside the band and its flat cost of any other move
    "voicing": true,                       optional, a JSON bool (default: -vd): the session's f0 is 0 on the frames of its ring that are
@@ -145,6 +148,7 @@ LOSE_KEYS = ("lose",)                    # likewise (the converter is then spars
 CONCEAL_KEYS = ("conceal",)              # likewise: the session's own switch
 RANGE_KEYS = ("intonation", "auto_range")    # a loaded session carries "intonation" only when it is not 1, "auto_range" only when on
 TRACK_KEYS = ("pitch_track", "track_weight", "track_jump")      # a loaded session carries them only when it tracks
+PATH_KEYS = ("match_path", "path_weight")                       # a loaded session carries them only when its match takes the path
 VOICING_KEYS = ("voicing", "voicing_on", "voicing_off", "voicing_floor_db")      # likewise: only when it decides
 RANGE_ST_KEYS = ("range_st",)            # a loaded session carries it only when its entry has the key
 
@@ -230,6 +234,7 @@ def build_parser():
     parser.add_argument('--no-graph', action='store_true',
                         help="launch the per-tick device pipeline kernel by kernel instead of replaying one captured hipGraph")
     common.add_track_arguments(parser)      # (-pt: sessions track unless their "pitch_track" says otherwise)
+    common.add_path_arguments(parser)       # (-mp: sessions take the match path unless their "match_path" says otherwise)
     common.add_voicing_arguments(parser)    # (-vd: sessions decide unless their "voicing" says otherwise)
     return parser
 
@@ -283,6 +288,19 @@ def session_range(s, where, intonation=1.0, auto_range=False):
         return check_intonation(it, "\"intonation\""), on
     except ValueError as e:
         raise ValueError(f"{where}: {e}") from None
+
+
+def session_path(s, where, match_path=False, weight=common.PATH_WEIGHT):
+    """an entry's match path settings -> the weight as a float, or None for a session whose match takes no path: "match_path" (default
+    `match_path`) a JSON bool, "path_weight" (default `weight`) a number >= 0; ValueError otherwise"""
+    on = s.get("match_path", bool(match_path))
+    if not isinstance(on, bool):
+        raise ValueError(f"{where}: \"match_path\" must be true or false, got {on!r}")
+    try:
+        w = common.path_param(s.get("path_weight", weight), "\"path_weight\"")
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return w if on else None
 
 
 def session_track(s, where, pitch_track=False, weight=common.TRACK_WEIGHT, jump=common.TRACK_JUMP):
@@ -450,7 +468,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
                   limit_lookahead_ms=5.0, limit_hold_ms=20.0, envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0,
                   envelope_radius=1, conceal_hold_ms=10.0, conceal_fade_ms=50.0, conceal_recover_ms=5.0, intonation=1.0,
                   auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT, track_jump=common.TRACK_JUMP, lufs=None,
-                  voicing=False, voicing_on=common.VOICING_ON, voicing_off=common.VOICING_OFF, voicing_floor_db=common.VOICING_FLOOR_DB):
+                  voicing=False, voicing_on=common.VOICING_ON, voicing_off=common.VOICING_OFF, voicing_floor_db=common.VOICING_FLOOR_DB,
+                  match_path=False, path_weight=common.PATH_WEIGHT):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
@@ -462,7 +481,9 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     "range_st" only where the entry has it; "pitch_track" (true), "track_weight" and "track_jump" (defaults `pitch_track`,
     `track_weight`, `track_jump`) only on a session that tracks; "lufs" (default `lufs`) only on a session that is normalised;
     "voicing" (true), "voicing_on", "voicing_off" and "voicing_floor_db" (defaults `voicing`, `voicing_on`, `voicing_off`,
-    `voicing_floor_db`) only on a session that decides; ValueError on a malformed entry"""
+    `voicing_floor_db`) only on a session that decides; "match_path" (true) and "path_weight" (defaults `match_path`, `path_weight`)
+    only on a session whose match takes the path; ValueError on a malformed entry"""
+    session_path({}, "-mp / --path-weight", match_path, path_weight)
     session_voicing({}, "-vd / --voicing-on / --voicing-off / --voicing-floor", voicing, voicing_on, voicing_off, voicing_floor_db)
     session_track({}, "-pt / --track-weight / --track-jump", pitch_track, track_weight, track_jump)
     try:
@@ -489,10 +510,10 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
         unknown = (set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(CODEBOOK_KEYS)
                    - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS) - set(RANGE_KEYS) - set(RANGE_ST_KEYS) - set(TRACK_KEYS) - set(VOICING_KEYS)
-                   - set(LOUDNESS_KEYS))
+                   - set(LOUDNESS_KEYS) - set(PATH_KEYS))
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS + TRACK_KEYS + LOUDNESS_KEYS + VOICING_KEYS})")
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS + TRACK_KEYS + LOUDNESS_KEYS + VOICING_KEYS + PATH_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
@@ -514,6 +535,7 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
         range_st = range_st_of(s, f"session {i}")
         track = session_track(s, f"session {i}", pitch_track, track_weight, track_jump)
         decide = session_voicing(s, f"session {i}", voicing, voicing_on, voicing_off, voicing_floor_db)
+        path_w = session_path(s, f"session {i}", match_path, path_weight)
         e = dict(input=rel(s["input"]), target=rel(s.get("target")), lib=rel(s.get("lib")), output=rel(s.get("output")),
                  pitch=float(s.get("pitch", 0.0)), f0_rate=float(s.get("f0_rate", 1.0)), alpha=float(s.get("alpha", 0.0)),
                  gain=float(s.get("gain", 0.0)), input_gain=float(s.get("input_gain", 0.0)), start=int(s.get("start", 0)),
@@ -551,6 +573,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             e["pitch_track"], (e["track_weight"], e["track_jump"]) = True, track
         if decide is not None:
             e["voicing"], (e["voicing_on"], e["voicing_off"], e["voicing_floor_db"]) = True, decide
+        if path_w is not None:
+            e["match_path"], e["path_weight"] = True, path_w
         out.append(e)
     return out
 
@@ -704,13 +728,14 @@ def main(argv=None):
     try:
         tw, tj, lo, hi, band = common.track_arguments(args)             # (before anything is loaded)
         voicing_opts = common.voicing_options(dict(lo=args.voicing_lo, hi=args.voicing_hi), "--voicing-lo / --voicing-hi")
+        common.path_arguments(args)
     except ValueError as e:
         raise SystemExit(str(e)) from None
     sessions = load_sessions(args.sessions, args.k, args.auto_pitch, args.gate_db, args.gate_hold, args.codebook,
                              args.crossfade, args.limit, args.limit_lookahead, args.limit_hold, args.envelope, args.envelope_floor,
                              args.envelope_range, args.envelope_radius, args.conceal_hold, args.conceal_fade, args.conceal_recover,
                              args.intonation, args.auto_range, args.pitch_track, tw, tj, args.lufs, args.voicing, args.voicing_on,
-                             args.voicing_off, args.voicing_floor)
+                             args.voicing_off, args.voicing_floor, args.match_path, args.path_weight)
     loud = dict(loudness_half_life=args.loudness_half_life, loudness_prior=args.loudness_prior, loudness_gate_lufs=args.loudness_gate,
                 loudness_max_db=args.loudness_max_db, loudness_slew_db=args.loudness_slew)
     try:
@@ -762,6 +787,7 @@ def main(argv=None):
                                    if any("pitch_track" in s for s in sessions) else {}),
                                 **(dict(voicing=True, voicing_lo=voicing_opts["lo"], voicing_hi=voicing_opts["hi"])
                                    if any("voicing" in s for s in sessions) else {}),
+                                **(dict(match_path=True) if any("match_path" in s for s in sessions) else {}),
                                 **(dict(gate=True) if any("gate_db" in s for s in sessions) else {}),
                                 **(dict(crossfade=True) if any("crossfade_ms" in s for s in sessions) else {}),
                                 **(dict(limiter=True) if any("limit_db" in s for s in sessions) else {}),
@@ -774,7 +800,7 @@ def main(argv=None):
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
                    **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CONCEAL_KEYS + RANGE_KEYS + TRACK_KEYS
-                      + LOUDNESS_KEYS + VOICING_KEYS if g in s})
+                      + LOUDNESS_KEYS + VOICING_KEYS + PATH_KEYS if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()

@@ -80,6 +80,7 @@ def build_parser():
                              "does around a window's mean (default 1: off; module/multistream.py \"Pitch range\"; this build only)")
     common.add_track_arguments(parser)
     common.add_voicing_arguments(parser)
+    common.add_path_arguments(parser)
     parser.add_argument('-isr', '--input-sr', default=16000, type=int)
     parser.add_argument('-osr', '--output-sr', default=16000, type=int)
     parser.add_argument('-lsr', '--loopback-sr', default=16000, type=int)
@@ -104,6 +105,10 @@ def main(argv=None):
         raise SystemExit("Error: this build needs a ROCm device: pass -d cuda on an MI355X host.")
     if args.fp16:
         raise SystemExit("-fp16 (documented deprecated upstream) is outside this build's scope")
+    try:
+        match_path = common.path_arguments(args)                             # (before anything is loaded)
+    except ValueError as e:
+        raise SystemExit(str(e))
     track = None
     if args.pitch_track:
         if args.world_pitch_estimation:
@@ -141,7 +146,8 @@ def main(argv=None):
                                    envelope_radius=args.envelope_radius) if args.envelope else {}),
                            **(dict(intonation=args.intonation) if args.intonation != 1.0 else {}),
                            **({} if track is None else dict(pitch_track=track)),
-                           **({} if voicing is None else dict(voicing={k: voicing[k] for k in common.VOICING_KEYS})))
+                           **({} if voicing is None else dict(voicing={k: voicing[k] for k in common.VOICING_KEYS})),
+                           **({} if match_path is None else dict(match_path=match_path)))
     if not args.no_graph:
         rt.enable_graph()        # the whole per-chunk device pipeline (~150 launches) captured once, replayed per chunk: same samples
     print("streaming: conversion running (Ctrl-C stops)")

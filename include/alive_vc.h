@@ -831,6 +831,34 @@ int alive_voicing_rows(const float* x, int N, int ld, int L, int hop, int T, int
                        const int32_t* on, const double* thr_on, const double* thr_off, const double* floor_e, float* f0, int ld_f0,
                        double* r_out, int32_t* lag_out, int32_t* voiced_out, int32_t* changed, void* ws, void* stream);
 
+/* Match path: out of each frame's candidates of a top-k list, ONE library row per frame by a Viterbi path, between a search and its
+ * gather (tools/match_path_ref.py is the NumPy restatement, bit for bit).  R list rows of T frames: val / idx [R][T][k_max] as every
+ * search form writes them (best first, -1 behind the last valid entry), k_row[r] entries of a frame in use; rows_f32 [P][768] and
+ * norms [P] are the table the indices point into.  A frame is active when idx[t][0] >= 0 and no idx[t][i], i < k_row, is >= P (such an
+ * index is never dereferenced); state i of an active frame exists when i < k_row and idx[t][i] >= 0.  In fp64, every operation rounded
+ * on its own:
+ *   e[t][i] = val[t][i] - val[t][0];   c[t][i][j] = dot(a, b) / (norms[a] * norms[b]) with a = idx[t][i], b = idx[t-1][j]
+ *   D[t][i] = e[t][i] at t = 0 and after an inactive frame, else e[t][i] + max_j (D[t-1][j] + weight * c[t][i][j])   (lowest j on ties)
+ * dot in one fixed order (lane l of 64: products l + 64 q, q ascending from 0.0; then p[l] += p[l + o], o = 32 .. 1).  Each segment of
+ * consecutive active frames is traced back from the lowest argmax of D at its end.  Output lists [R][T][k_max]: entry 0 of frame t is
+ * the chosen (val, idx), every other entry and every entry of an inactive frame (-inf, -1), so that every gather serves at k = 1; they
+ * must not overlap the input lists.  weight = 0 chooses entry 0 everywhere.
+ *   k_row, on   DEVICE int32 [R]: a row with on[r] == 0 or k_row[r] outside [1, k_max] is off: its lists are copied, moved[r] = 0
+ *   weight      DEVICE double [R], >= 0, in cosine units (the units of e)
+ *   moved       DEVICE int32 [R]: the frames whose chosen entry is not entry 0
+ *   ws          alive_knn_path_workspace_bytes(R, T, k_max) bytes (0: bad sizes); alive_knn_path_layout: off[0] the byte offset of
+ *               J = c as double [R][T][k_max][k_max] (written for existing states of consecutive active frames only), off[1] that of
+ *               the back pointers, uint8 [R][T][k_max]
+ * Limits: k_max <= ALIVE_KNN_PATH_MAX_K, R * T <= ALIVE_KNN_PATH_MAX_FRAMES.  Two launches (one when T = 1) whose grids depend on R, T
+ * and k_max alone; every per-row array is read when the kernels run; no host synchronisation, no allocation, no atomics. */
+#define ALIVE_KNN_PATH_MAX_K 8
+#define ALIVE_KNN_PATH_MAX_FRAMES 1048576
+size_t alive_knn_path_workspace_bytes(int R, int T, int k_max);
+int alive_knn_path_layout(int R, int T, int k_max, int64_t* off);
+int alive_knn_path_rows(const float* val, const int32_t* idx, const int32_t* k_row, int k_max, const int32_t* on, const double* weight,
+                        const float* rows_f32, const float* norms, int64_t P, int R, int T, float* out_val, int32_t* out_idx,
+                        int32_t* moved, void* ws, void* stream);
+
 /* Arithmetic of the decoder's two largest groups of GEMMs on the batch path (more than 96 columns; the streaming kernels are not
  * affected): (a) the six k = 5 convs of the 256-channel FilterBlock (decoder.py:128-134 at the Filter's coarsest scale), (b) the two
  * pointwise convs of the feature extractor's four AdaptiveConvNeXt1d layers (common.py:74-82), (c) the norm-FiLM projection, the two

@@ -86,10 +86,11 @@ alive_ring_push_rows with every row present (push_call_us).
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch] [--pitch-range]
-                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--loudness] [--pitch-track] [--voicing]
+                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--loudness] [--pitch-track] [--voicing] [--match-path]
                                       [--out multistream.json]
     python tools/bench_multistream.py --loudness-offline [--out loudness_offline.json]
     python tools/bench_multistream.py --voicing-offline [--out voicing_offline.json]
+    python tools/bench_multistream.py --match-path-offline [--out match_path_call.json]
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
     python tools/bench_multistream.py --sparse [--batches 128,1024] [--ticks 40] [--out profiles/multistream_sparse_bench.json]
     python tools/bench_multistream.py --conceal [--batches 128,1024] [--ticks 40] [--out profiles/multistream_conceal_bench.json]
@@ -194,6 +195,23 @@ def voicing_offline_leg(windows=384, frames=450):
            "us_per_frame": round(us / (windows * frames), 4)}
     print(json.dumps(rec), flush=True)
     return [rec]
+
+
+def match_path_offline_leg(shapes=((1, 24), (16, 24), (128, 24), (384, 450)), rows_n=4096):
+    """the bare path call (alive_knn_path_rows: join + path) on R list rows of T frames at k_max = 4 and 8, every row on"""
+    g = torch.Generator(device="cuda").manual_seed(9)
+    rows = torch.randn(rows_n, 768, device="cuda", generator=g)
+    norms = rows.double().pow(2).sum(dim=1).sqrt().float()
+    recs = []
+    for R, T in shapes:
+        rec = {"leg": "match_path_call", "R": R, "T": T, "table_rows": rows_n}
+        for k in (4, 8):
+            us = path_call_us(R, T, k, rows, norms)
+            rec[f"path_call_k{k}_us"] = round(us, 2)
+            rec[f"k{k}_us_per_frame"] = round(us / (R * T), 4)
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+    return recs
 
 
 def conceal_leg(nets, batches=(128, 1024), ticks=40, warmup=6):
@@ -395,6 +413,23 @@ def time_search(conv, B, reps=20, seg_len=None):
     return a.elapsed_time(b) / reps, sum(ln for _, ln in segs) * (768 + 1) * 4
 
 
+def path_call_us(R, T, k, rows, norms, seed=5):
+    """alive_knn_path_rows alone on R list rows of T frames at k_max = k: random descending cosines, indices that repeat a third of
+    the frame before's (as neighbouring frames of speech do), every row on at weight 1; device events around 200 back-to-back calls"""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    val = torch.sort(torch.rand(R * T, k, device="cuda", generator=g) * 0.3 + 0.6, dim=1, descending=True)[0].contiguous()
+    idx = torch.randint(0, rows.shape[0], (R, T, k), device="cuda", generator=g, dtype=torch.int32)
+    keep = torch.rand(R, T, k, device="cuda", generator=g) < 0.35
+    for t in range(1, T):
+        idx[:, t] = torch.where(keep[:, t], idx[:, t - 1], idx[:, t])
+    idx = idx.view(R * T, k).contiguous()
+    k_row = torch.full((R,), k, dtype=torch.int32, device="cuda")
+    on = torch.ones(R, dtype=torch.int32, device="cuda")
+    w = torch.ones(R, dtype=torch.float64, device="cuda")
+    moved = torch.zeros(R, dtype=torch.int32, device="cuda")
+    return time_calls(lambda: MS.knn_path_rows(val, idx, k_row, k, on, w, rows, norms, moved=moved))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default=None, help="comma-separated batch sizes (default 1,8,32,64,128; with --sparse 128,1024)")
@@ -428,6 +463,10 @@ def main():
                     "every session tracking, beside the plain converter in alternating rounds")
     ap.add_argument("--voicing", action="store_true", help="also time a voicing=True converter with no session and with every session "
                     "deciding, beside the plain converter in alternating rounds")
+    ap.add_argument("--match-path", action="store_true", help="also time a match_path=True converter with no session and with every "
+                                                              "session on the path, against a plain one in alternating rounds, and "
+                                                              "the path call alone at k_max = 4 and 8")
+    ap.add_argument("--match-path-offline", action="store_true", help="the bare path call alone over 384 windows of 450 frames")
     ap.add_argument("--voicing-offline", action="store_true", help="the bare voicing call alone over 384 windows of 450 frames")
     ap.add_argument("--enrol", action="store_true", help="the live-enrolment leg alone: one more voice between two ticks, on a "
                                                          "default and on a reserved pool")
@@ -467,6 +506,12 @@ def main():
         return
     if args.voicing_offline:
         rows = voicing_offline_leg()
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(rows, open(args.out, "w"), indent=1)
+        return
+    if args.match_path_offline:
+        rows = match_path_offline_leg()
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             json.dump(rows, open(args.out, "w"), indent=1)
@@ -738,6 +783,30 @@ def main():
                     rec["voicing_call_us"] = round(time_calls(lambda: MS.ops.voicing_rows_(f0, x, vc._voicing, vc.voicing_on, vc.voicing_thr_on,
                                                                                        vc.voicing_thr_off, vc.voicing_floor_e)), 2)
                     del three, vc
+                if args.match_path:
+                    three = {}
+                    for name, kw, sess in (("path_off", {}, {}), ("path_none", dict(match_path=True), {}),
+                                           ("path_all", dict(match_path=True), dict(match_path=True))):
+                        c = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, **kw)
+                        for s in range(B):
+                            c.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, **sess)
+                        c.enable_graph()
+                        three[name] = c
+                    times = {name: [] for name in three}
+                    for _ in range(5):                         # alternating rounds in the one process
+                        for name, c in three.items():
+                            times[name].append(time_ticks(c, B, chunk, args.ticks, args.warmup + bs + 1, 300))
+                    for name, ts in times.items():
+                        rec[f"{name}_tick_p50_ms"] = round(float(np.median([t[0] for t in ts])), 3)
+                        rec[f"{name}_tick_p99_ms"] = round(float(np.median([t[1] for t in ts])), 3)
+                        rec[f"{name}_tick_p50_rounds_ms"] = [round(t[0], 3) for t in ts]
+                    pc = three["path_all"]
+                    assert pc.captures == 1 and three["path_none"].path_moved() == [0] * B
+                    rec["path_moved_mean"] = round(float(np.mean(pc.path_moved())), 2)
+                    rec["path_frames"] = pc.frames
+                    for kk in (4, 8):
+                        rec[f"path_call_k{kk}_us"] = round(path_call_us(B, pc.frames, kk, pool.rows, pool.norms), 2)
+                    del three, pc
                 rec.update(search_ms=round(ms, 4), search_bytes=nbytes, search_GBps=round(nbytes / ms / 1e6, 1))
                 print(json.dumps(rec), flush=True)
                 rows.append(rec)
