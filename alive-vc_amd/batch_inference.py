@@ -39,6 +39,10 @@ The jobs file is a JSON list; each entry:
                                                             follow_envelope), at 16 kHz before the output resample and the gain; 0 or
                                                             null: the decoder's own level.  A jobs file without it, run without -env,
                                                             runs as before
+   "post_filter": 0.8,                                      optional, a number in [0, 0.85] or null (default: -pf): the alpha of the
+                                                            adaptive formant post filter (module/multistream.py post_filter) on the
+                                                            converted wave at 16 kHz, ahead of "envelope"; 0 or null: no filter.  A
+                                                            jobs file without it, run without -pf, runs as before
    "pitch_track": true,                                     optional, a JSON bool or {"weight": 1, "jump": 12} (default: -pt with
                                                             --track-weight / --track-jump): the file's f0 is the Viterbi path over
                                                             the f0 estimator's class scores of each window instead of their argmax
@@ -79,6 +83,7 @@ from module.multistream import MAX_K, blend_sources, check_k     # noqa: E402
 JOB_KEYS = ("input", "target", "lib", "pitch", "intonation", "f0_rate", "alpha", "gain", "normalize", "world_pitch", "output",
             "blend", "k", "auto_pitch", "register_hz")
 ENVELOPE_KEYS = ("envelope",)            # likewise; a loaded job carries it only when it follows (an amount above 0)
+POSTFILTER_KEYS = ("post_filter",)       # likewise; a loaded job carries it only when it is filtered (an alpha above 0)
 LIMIT_KEYS = ("limit_db",)               # taken per job too; a loaded job carries it only when it is limited
 LOUDNESS_KEYS = ("lufs",)                # likewise; a loaded job carries it only when it is normalised
 TRACK_KEYS = ("pitch_track",)            # a loaded job carries it only when it tracks: {"weight": W, "jump": J}
@@ -127,6 +132,13 @@ def build_parser():
                         help="the most the envelope follow turns a frame up or down (default 12)")
     parser.add_argument('--envelope-radius', default=1, type=int, metavar="FRAMES",
                         help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
+    parser.add_argument('-pf', '--post-filter-alpha', default=0.0, type=float, metavar="A",
+                        help="adaptive formant post filter on the converted waves at 16 kHz, ahead of -env: the alpha of the denominator, "
+                             "0 (off, the default) to 0.85, unless a job's \"post_filter\" says otherwise (module/multistream.py post_filter)")
+    parser.add_argument('--post-filter-ratio', default=0.625, type=float, metavar="R",
+                        help="the post filter's numerator alpha as a share of the denominator's, 0 to 1 (default 0.625)")
+    parser.add_argument('--post-filter-tilt', default=0.5, type=float, metavar="T",
+                        help="the share of the post filter's spectral tilt that is taken out again, 0 to 1 (default 0.5)")
     parser.add_argument('--pcm16', action='store_true', help="write 16-bit PCM instead of float32 WAV")
     common.add_track_arguments(parser)      # (-pt: jobs track unless their "pitch_track" says otherwise)
     common.add_voicing_arguments(parser)    # (-vd: jobs decide unless their "voicing" says otherwise)
@@ -220,6 +232,18 @@ def job_envelope(j, where, envelope=0.0, floor_db=-60.0, range_db=12.0, radius=1
     return a if a > 0 else None
 
 
+def job_post_filter(j, where, alpha=0.0, ratio=0.625, tilt=0.5):
+    """an entry's "post_filter" (default `alpha`; a JSON null or 0 switches the default off) -> the alpha as a float in (0, 0.85], or
+    None for a job that is not filtered; ValueError otherwise (ratio and tilt are those of the flags, checked with it)"""
+    from module.multistream import check_post_filter
+    a = j.get("post_filter", alpha)
+    try:
+        a = check_post_filter(0.0 if a is None else a, ratio, tilt)[0]
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return a if a > 0 else None
+
+
 def job_track(j, where, pitch_track=False, weight=common.TRACK_WEIGHT, jump=common.TRACK_JUMP):
     """an entry's "pitch_track" (default `pitch_track`): true, false or {"weight": W, "jump": J} (defaults `weight`, `jump`) ->
     {"weight": W, "jump": J} as floats, or None for a job that does not track; ValueError otherwise, and together with
@@ -283,14 +307,15 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
               envelope_range_db=12.0, envelope_radius=1, auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT,
               track_jump=common.TRACK_JUMP, lufs=None, loudness_max_db=12.0, voicing=False, voicing_on=common.VOICING_ON,
               voicing_off=common.VOICING_OFF, voicing_floor_db=common.VOICING_FLOOR_DB, match_path=False,
-              path_weight=common.PATH_WEIGHT):
+              path_weight=common.PATH_WEIGHT, post_filter=0.0, post_filter_ratio=0.625, post_filter_tilt=0.5):
     """the jobs file -> list of dicts with every key filled in (paths relative to the file's folder; "auto_pitch": default
     `auto_pitch`); a limited job ("limit_db", default `limit_db`) also carries "limit_db", a job without a limiter does not, so a
     file without the key loads to what it did; likewise "envelope" (default `envelope`) only on a job that follows at an amount above
     0, "auto_range" (default `auto_range`) only on a job that is on, "range_st" only where the entry has it and "pitch_track"
     (default `pitch_track` at `track_weight` / `track_jump`) only on a job that tracks and "lufs" (default `lufs`) only on a job that
     is normalised and "voicing" (default `voicing` at `voicing_on` / `voicing_off` / `voicing_floor_db`) only on a job that decides and
-    "match_path" (default `match_path` at `path_weight`) only on a job whose match takes a path;
+    "match_path" (default `match_path` at `path_weight`) only on a job whose match takes a path and "post_filter" (default
+    `post_filter`) only on a job that is filtered at an alpha above 0;
     ValueError on a malformed job, before anything runs on the device"""
     job_voicing({}, "-vd / --voicing-on / --voicing-off / --voicing-floor", voicing, voicing_on, voicing_off, voicing_floor_db)
     job_track({}, "-pt / --track-weight / --track-jump", pitch_track, track_weight, track_jump)
@@ -299,6 +324,7 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
     job_loudness({}, "-lufs / --loudness-max-db", lufs, loudness_max_db)
     env = (envelope_floor_db, envelope_range_db, envelope_radius)
     job_envelope({}, "-env / --envelope-floor / --envelope-range / --envelope-radius", envelope, *env)
+    job_post_filter({}, "-pf / --post-filter-ratio / --post-filter-tilt", post_filter, post_filter_ratio, post_filter_tilt)
     if not 1 <= k <= MAX_K:
         raise ValueError(f"k={k} outside [1, {MAX_K}] (the pool search's limit)")
     with open(path) as f:
@@ -312,10 +338,10 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
         if not isinstance(j, dict) or "input" not in j:
             raise ValueError(f"job {i}: an object with an \"input\" wav is required")
         unknown = (set(j) - set(JOB_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(RANGE_KEYS) - set(TRACK_KEYS)
-                   - set(LOUDNESS_KEYS) - set(VOICING_KEYS) - set(PATH_KEYS))
+                   - set(LOUDNESS_KEYS) - set(VOICING_KEYS) - set(PATH_KEYS) - set(POSTFILTER_KEYS))
         if unknown:
             raise ValueError(f"job {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS + TRACK_KEYS + LOUDNESS_KEYS + VOICING_KEYS + PATH_KEYS})")
+                             f"{JOB_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + RANGE_KEYS + TRACK_KEYS + LOUDNESS_KEYS + VOICING_KEYS + PATH_KEYS + POSTFILTER_KEYS})")
         blend = blend_sources(j, f"job {i}", rel) if "blend" in j else None
         if blend is None and j.get("target") is None and j.get("lib") is None:
             raise ValueError(f"job {i}: needs a \"target\" wav and / or a \"lib\" voice library")
@@ -340,6 +366,9 @@ def load_jobs(path, k=4, auto_pitch=False, limit_db=None, lookahead_ms=5.0, hold
         amount = job_envelope(j, f"job {i}", envelope, *env)
         if amount is not None:
             e["envelope"] = amount
+        pfa = job_post_filter(j, f"job {i}", post_filter, post_filter_ratio, post_filter_tilt)
+        if pfa is not None:
+            e["post_filter"] = pfa
         if j.get("auto_range", bool(auto_range)):
             e["auto_range"] = True
         track = job_track(j, f"job {i}", pitch_track, track_weight, track_jump)
@@ -417,7 +446,7 @@ def main(argv=None):
     jobs = load_jobs(args.jobs, args.k, args.auto_pitch, args.limit, args.limit_lookahead, args.limit_hold, args.envelope,
                      args.envelope_floor, args.envelope_range, args.envelope_radius, args.auto_range, args.pitch_track, tw, tj,
                      args.lufs, args.loudness_max_db, args.voicing, args.voicing_on, args.voicing_off, args.voicing_floor,
-                     args.match_path, args.path_weight)
+                     args.match_path, args.path_weight, args.post_filter_alpha, args.post_filter_ratio, args.post_filter_tilt)
     pathed = any("match_path" in j for j in jobs)
     tracked = any("pitch_track" in j for j in jobs)
     deciding = any("voicing" in j for j in jobs)
@@ -430,7 +459,8 @@ def main(argv=None):
     from module.content_encoder import ContentEncoder
     from module.decoder import Decoder
     from module.f0_estimator import F0Estimator
-    from module.multistream import VoicePool, follow_envelope, limit_waves, measure_register, normalize_loudness, pitch_hz
+    from module.multistream import (VoicePool, follow_envelope, limit_waves, measure_register, normalize_loudness, pitch_hz,
+                                    post_filter)
     from module.pipeline import Converter
     from module.spectrogram import spectrogram
     from module.voice_library import VoiceLibrary
@@ -488,6 +518,8 @@ def main(argv=None):
                              **(dict(match_path=[j.get("match_path") for j in jobs]) if pathed else {}), chunk=args.chunk, k=jobs_k(jobs, args.k), window_batch=args.window_batch,
                              trim_context=not args.no_trim_context)
     for i, (job, out, sr) in enumerate(zip(jobs, outs, rates)):
+        if job.get("post_filter"):                                      # at 16 kHz, first: the envelope sets the level of the filtered wave
+            out = post_filter(out, None, job["post_filter"], args.post_filter_ratio, args.post_filter_tilt)
         if job.get("envelope"):                                         # at 16 kHz, against the source the converter saw
             out = follow_envelope(out, utts[i], None, job["envelope"], args.envelope_floor, args.envelope_range, args.envelope_radius)
         out = audio_io.resample(out, 16000, sr, post_gain_db=job["gain"])

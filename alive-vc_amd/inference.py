@@ -48,7 +48,14 @@ def build_parser():
     parser.add_argument('-lib', '--voice-library-path', default="NONE")
     parser.add_argument('-noise', '--noise-amp', default=1.0, type=float)        # parsed and unused, as in the reference
     parser.add_argument('-harmonics', '--harmonics-amp', default=1.0, type=float)
-    parser.add_argument('-pf', '--post-filter-alpha', default=0.0, type=float)
+    parser.add_argument('-pf', '--post-filter-alpha', default=0.0, type=float, metavar="A",
+                        help="adaptive formant post filter on the converted wave at 16 kHz, ahead of -env: the alpha of the denominator, "
+                             "0 (off, the default) to 0.85; 0.8 is the classic setting (module/multistream.py post_filter; the reference "
+                             "parses the flag and never reads it)")
+    parser.add_argument('--post-filter-ratio', default=0.625, type=float, metavar="R",
+                        help="the post filter's numerator alpha as a share of -pf, 0 to 1 (default 0.625: 0.5 against 0.8)")
+    parser.add_argument('--post-filter-tilt', default=0.5, type=float, metavar="T",
+                        help="the share of the post filter's spectral tilt that is taken out again, 0 to 1 (default 0.5)")
     parser.add_argument('-wpe', '--world-pitch-estimation', default=False)
     parser.add_argument('-norm', '--normalize', default=False, type=bool)
     parser.add_argument('--window-batch', default=64, type=int, help="windows per device batch (this build only)")
@@ -109,6 +116,10 @@ def main(argv=None):
     if args.envelope != 0:
         from module.multistream import check_envelope, follow_envelope
         check_envelope(args.envelope, *env)                                  # (before anything is loaded)
+    pf = (args.post_filter_ratio, args.post_filter_tilt)
+    if args.post_filter_alpha != 0:
+        from module.multistream import check_post_filter, post_filter
+        check_post_filter(args.post_filter_alpha, *pf)                       # (before anything is loaded)
     track = None
     if args.pitch_track:
         if args.world_pitch_estimation:
@@ -160,6 +171,8 @@ def main(argv=None):
                            share_overlap=None if args.no_share_overlap else "auto", **({} if track is None else dict(pitch_track=track)),
                            **({} if voicing is None else dict(voicing={k: voicing[k] for k in common.VOICING_KEYS})),
                            **({} if match_path is None else dict(match_path=match_path)))
+        if args.post_filter_alpha > 0:            # at 16 kHz, first: the envelope follow sets the level of the filtered wave
+            out = post_filter(out, None, args.post_filter_alpha, *pf)
         if args.envelope > 0:                     # at 16 kHz, against the normalised mono source the converter saw
             out = follow_envelope(out, wf, None, args.envelope, *env)
         out = audio_io.resample(out, 16000, sr, post_gain_db=args.gain)            # resample, then gain (:136-137)

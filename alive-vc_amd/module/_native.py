@@ -201,6 +201,7 @@ PROTOTYPES = {
     "alive_loudness_apply_waves": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _D, _VP, _VP]),
     "alive_loudness_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_envelope_waves": (_I,[_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _D, _D, _D, _VP, _VP]),
+    "alive_postfilter_waves": (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _VP, _VP, _D, _D, _D, _D, _D, _VP, _VP]),
     "alive_ring_push_rows": (_I, [_VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "alive_emit_rows": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I, _VP]),
     "alive_conceal_rows": (_I, [_VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP]),

@@ -152,6 +152,20 @@ faded by crossfade.  The gain can lift a sample above 1.0: use the limiter besid
 and largest frame gain per slot back.  follow_envelope is the offline form (the same call over whole utterances).  The defaults (R = 1:
 60 ms, floor -60 dB, range 12 dB) are design choices: with no trained weights, how they sound is unmeasured.
 
+Post filter: every stage behind the decoder shapes the level of the converted wave; none shapes its spectrum, and a kNN match that
+averages k library rows flattens formants.  A converter built with post_filter=True (csrc/postfilter.hip) runs alive_postfilter_waves
+right after the decoder and before the envelope follow, which so sets the level of the filtered wave: for the sessions opened or set
+with post_filter=A (0 < A <= 0.85; 0.8 is the classic setting) each 320-sample frame of the decoder's 16 kHz wave gets an LPC analysis
+(40 ms Hamming window on the int16 grid, order 16, Levinson-Durbin in fp64), the filter A(z / (A ratio)) / A(z / A) with a first-order
+tilt compensation as a 128-tap response, and a frame gain that restores the frame's level; between the frame centres the output moves
+linearly from one frame's filtered wave to the next's (tools/postfilter_ref.py restates it bit for bit).  Like the envelope follow it
+is a stateless function of the tick's wave: nothing is carried across ticks, the bf16 repeat or a capture, the result goes to a buffer
+allocated once, the alphas are a device array (toggling and retuning never re-capture), a converter built without it launches exactly
+what it did and one whose sessions are all at 0 emits byte-identical streams.  Its frame grid is ring-relative too, exactly as the
+envelope follow's: with chunks that are no multiple of 320 samples two successive decodes analyse slightly different frames at a seam.
+post_filter_db() reads the latest tick's smallest and largest frame gain per slot back; post_filter is the offline form.  With no trained
+weights, what the filter does to perceived quality is unmeasured.
+
 Lost chunks: a stall costs nothing, but a server meets another event more often: a chunk that never arrives while the session's clock
 must go on.  Pushing zeros for it puts 10 ms of digital silence with two hard edges into voiced speech, and the hole is re-encoded on
 every one of the buffersize ticks it spends in the ring.  A sparse converter built with conceal=True (csrc/conceal.hip) fills the hole
@@ -1820,6 +1834,100 @@ def follow_envelope(wave, source, lens=None, amount=1.0, floor_db=-60.0, range_d
     return out[0] if one else out
 
 
+POSTFILTER_TAPS, POSTFILTER_MAX_ORDER, POSTFILTER_TILE = 128, 32, 16     # ALIVE_POSTFILTER_* (include/alive_vc.h)
+POSTFILTER_HOP = 320                            # the decoder's frame at 16 kHz
+POSTFILTER_MAX_ALPHA = 0.85                     # the poles lie inside radius alpha: beyond it 128 taps are no longer the whole response
+
+
+def postfilter_window(window):
+    """the analysis window alive_postfilter_waves takes, int16 [window] on the host: a Hamming window on the half-sample grid in
+    units of 1/64 (tools/postfilter_ref.py window_table)"""
+    i = np.arange(int(window), dtype=np.float64)
+    return np.rint(64.0 * (0.54 - 0.46 * np.cos(2.0 * np.pi * (i + 0.5) / float(window)))).astype(np.int16)
+
+
+def postfilter_lag(order):
+    """the lag window alive_postfilter_waves takes, float64 [order + 1] on the host: a 60 Hz Gaussian at 16 kHz
+    (tools/postfilter_ref.py lag_table)"""
+    k = np.arange(int(order) + 1, dtype=np.float64)
+    return np.exp(-0.5 * (2.0 * np.pi * 60.0 * k / 16000.0) ** 2)
+
+
+def postfilter_tables(window, order, device):
+    """(win int16 [window], lag float64 [order + 1]) on the device"""
+    return (torch.from_numpy(postfilter_window(window)).to(device), torch.from_numpy(postfilter_lag(order)).to(device))
+
+
+def postfilter_waves_(out, y, lens, alpha, hop, window, order, win, lag, ratio, tilt, floor_ms, g_lo, g_hi, gain_minmax=None):
+    """alive_postfilter_waves into out [N, ld]: y float32 [N, ld] through the adaptive formant post filter, row n over its first lens[n]
+    samples (device int32 [N], or None: the whole row) at alpha[n] (device float32 [N]; a row whose alpha is not in (0, 0.85] is
+    copied).  win int16 [window] and lag float64 [order + 1]: postfilter_tables.  gain_minmax: float32 [N, 2] or None.  out must not
+    overlap y"""
+    for name, t in (("out", out), ("y", y)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2:
+            raise ValueError(f"postfilter_waves_: {name} must be contiguous float32 [N, ld]")
+    if out.shape != y.shape:
+        raise ValueError(f"postfilter_waves_: out {tuple(out.shape)} and y {tuple(y.shape)} do not belong together")
+    if win.dtype != torch.int16 or win.numel() != int(window) or lag.dtype != torch.float64 or lag.numel() != int(order) + 1:
+        raise ValueError(f"postfilter_waves_: win must be int16 [{window}] and lag float64 [{int(order) + 1}]")
+    n, ld = y.shape
+    nat.check(nat.lib().alive_postfilter_waves(nat.ptr(out), nat.ptr(y), ld, n, nat.ptr(lens), nat.ptr(alpha), int(hop), int(window),
+                                               int(order), nat.ptr(win), nat.ptr(lag), float(ratio), float(tilt), float(floor_ms),
+                                               float(g_lo), float(g_hi), nat.ptr(gain_minmax), nat.stream()), "alive_postfilter_waves")
+    return out
+
+
+def check_post_filter(alpha, ratio=0.625, tilt=0.5, order=16, window_ms=40.0, floor_db=-100.0, range_db=12.0):
+    """a post filter's settings -> (alpha, ratio, tilt, order, window, floor_ms, g_lo, g_hi): alpha, ratio and tilt as floats, the
+    window in samples at 16 kHz, the floor as a mean square 10^(floor_db / 10) and the range 10^(-+range_db / 20) in float64.
+    ValueError unless alpha is a finite number in [0, 0.85] (not a bool; 0: off), ratio and tilt finite numbers in [0, 1], order an
+    integer in [1, POSTFILTER_MAX_ORDER], window_ms a number whose 16 samples per millisecond are a whole even number in [320, 1024]
+    (the frame of 320 plus an even excess), floor_db a finite number in [-3000, 3000] and range_db one in [0, 6000]"""
+    if not _number(alpha) or not (np.isfinite(alpha) and 0 <= alpha <= POSTFILTER_MAX_ALPHA):
+        raise ValueError(f"post_filter={alpha!r} must be a finite number in [0, {POSTFILTER_MAX_ALPHA}] (0: the converted wave as it is)")
+    if not _number(ratio) or not (np.isfinite(ratio) and 0 <= ratio <= 1):
+        raise ValueError(f"post_filter_ratio={ratio!r} must be a finite number in [0, 1] (the numerator's alpha over the denominator's)")
+    if not _number(tilt) or not (np.isfinite(tilt) and 0 <= tilt <= 1):
+        raise ValueError(f"post_filter_tilt={tilt!r} must be a finite number in [0, 1] (the share of the tilt taken out)")
+    if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)) or not 1 <= order <= POSTFILTER_MAX_ORDER:
+        raise ValueError(f"post_filter_order={order!r} must be an integer in [1, {POSTFILTER_MAX_ORDER}]")
+    window = float(window_ms) * 16.0 if _number(window_ms) and np.isfinite(window_ms) else -1.0
+    if window != int(window) or not POSTFILTER_HOP <= window <= 1024 or int(window) % 2:
+        raise ValueError(f"post_filter_window_ms={window_ms!r} must be a number of milliseconds in [20, 64] that is a whole even number "
+                         "of samples at 16 kHz")
+    if not _number(floor_db) or not (np.isfinite(floor_db) and -3000 <= floor_db <= 3000):
+        raise ValueError(f"post_filter_floor_db={floor_db!r} must be a finite number of dB in [-3000, 3000] (its mean square is above 0)")
+    if not _number(range_db) or not (np.isfinite(range_db) and 0 <= range_db <= 6000):
+        raise ValueError(f"post_filter_range_db={range_db!r} must be a finite number of dB >= 0 (at most 6000)")
+    return (float(alpha), float(ratio), float(tilt), int(order), int(window), float(10.0 ** (float(floor_db) / 10.0)),
+            float(10.0 ** (-float(range_db) / 20.0)), float(10.0 ** (float(range_db) / 20.0)))
+
+
+def post_filter(wave, lens=None, alpha=0.8, ratio=0.625, tilt=0.5, order=16, window_ms=40.0, floor_db=-100.0, range_db=12.0):
+    """The offline post filter: wave float32 [N, ld] (or [ld]) on the device at 16 kHz -> a new tensor of wave's shape, row n's first
+    lens[n] samples (default: the whole row) through the adaptive formant post filter, the rest copied (alive_postfilter_waves).
+    alpha: a number in [0, 0.85], or one per row (0: the row is copied).  ValueError as check_post_filter"""
+    one = wave.dim() == 1
+    y = (wave[None] if one else wave).contiguous()
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError(f"post_filter: wave must be float32 [N, ld] or [ld], got {tuple(wave.shape)} {wave.dtype}")
+    n, ld = y.shape
+    alphas = list(alpha) if isinstance(alpha, (list, tuple)) else [alpha] * n
+    if len(alphas) != n:
+        raise ValueError(f"post_filter: {len(alphas)} alphas for {n} rows")
+    checked = [check_post_filter(a, ratio, tilt, order, window_ms, floor_db, range_db) for a in alphas]
+    _, ratio, tilt, order, window, floor_ms, g_lo, g_hi = checked[0]
+    lens = [ld] * n if lens is None else [int(v) for v in lens]
+    if len(lens) != n:
+        raise ValueError(f"post_filter: {len(lens)} lens for {n} rows")
+    dev = y.device
+    win, lag = postfilter_tables(window, order, dev)
+    out = postfilter_waves_(torch.empty_like(y), y, torch.tensor(lens, dtype=torch.int32, device=dev),
+                            torch.tensor([c[0] for c in checked], dtype=torch.float32, device=dev), POSTFILTER_HOP, window, order, win,
+                            lag, ratio, tilt, floor_ms, g_lo, g_hi)
+    return out[0] if one else out
+
+
 def wave_length(frames, rate):
     """the samples of a converter's final wave: the decoder's 320 per frame at 16 kHz, resampled to `rate`"""
     orig, new = audio_io._reduced(16000, rate)
@@ -1980,7 +2088,7 @@ def db_scale(db):
 _PARAMS = ("voice", "pitch", "f0_rate", "alpha", "gain", "input_gain", "world_pitch", "k", "auto_pitch", "gate_db", "gate_hold",
            "crossfade_ms", "limit_db", "limit_lookahead_ms", "limit_hold_ms", "envelope", "conceal", "intonation", "auto_range",
            "pitch_track", "track_weight", "track_jump", "lufs", "voicing", "voicing_on", "voicing_off", "voicing_floor_db",
-           "match_path", "path_weight")
+           "match_path", "path_weight", "post_filter")
 
 
 class MultiStreamConverter:
@@ -1996,6 +2104,7 @@ class MultiStreamConverter:
     loud = False                       # (likewise: whether the tick carries the loudness kernel; loudness() is the read-back)
     voicing = False                    # (likewise: whether the f0 branch carries the voicing kernels; voicing_state() is the read-back)
     match_path = False                 # (likewise: whether the path call sits between the search and the gather; path_moved() reads back)
+    post_filter = False                # (likewise: whether the tick carries the post filter kernel; post_filter_db() is the read-back)
 
     def __init__(self, content_encoder, f0_estimator, decoder, pool, slots, chunk=960, buffersize=8, input_sr=16000,
                  output_sr=16000, k=4, device="cuda", rates=None, world_pitch=False, blend=1, k_max=None, auto_pitch=False,
@@ -2006,7 +2115,15 @@ class MultiStreamConverter:
                  track_band=2.0, loudness=False, loudness_half_life=3.0, loudness_prior=1.0, loudness_gate_lufs=LOUDNESS_GATE_LUFS,
                  loudness_max_db=12.0, loudness_slew_db=6.0, voicing=False, voicing_lo=common.VOICING_LO, voicing_hi=common.VOICING_HI,
                  voicing_window_ms=common.VOICING_WINDOW_MS, voicing_bridge=common.VOICING_BRIDGE,
-                 voicing_min_run=common.VOICING_MIN_RUN, match_path=False):
+                 voicing_min_run=common.VOICING_MIN_RUN, match_path=False, post_filter=False, post_filter_ratio=0.625,
+                 post_filter_tilt=0.5, post_filter_order=16, post_filter_window_ms=40.0):
+        if not isinstance(post_filter, (bool, np.bool_)):
+            raise ValueError(f"MultiStreamConverter: post_filter must be a bool, got {post_filter!r}")
+        if post_filter:                    # (checked before anything is built)
+            try:
+                pf = check_post_filter(0.0, post_filter_ratio, post_filter_tilt, post_filter_order, post_filter_window_ms)
+            except ValueError as e:
+                raise ValueError(f"MultiStreamConverter: {e}") from None
         if not isinstance(match_path, (bool, np.bool_)):
             raise ValueError(f"MultiStreamConverter: match_path must be a bool, got {match_path!r}")
         if not isinstance(voicing, (bool, np.bool_)):
@@ -2289,6 +2406,16 @@ class MultiStreamConverter:
             self.env_amount = torch.zeros(B, dtype=torch.float32, device=dev)
             self.env_minmax = torch.ones(B, 2, dtype=torch.float32, device=dev)
             self._env_out = None
+        # post filter: the post filter kernel is part of the tick (captured once), right after the decoder and before the envelope
+        # follow; per row, pf_alpha is the session's amount (0: copied).  No state: a function of the tick's wave.  _pf_out is
+        # allocated once, by the first tick
+        self.post_filter = bool(post_filter)
+        if self.post_filter:
+            self._pf = pf[1:]                                  # (ratio, tilt, order, window, floor_ms, g_lo, g_hi)
+            self._pf_win, self._pf_lag = postfilter_tables(pf[4], pf[3], dev)
+            self.pf_alpha = torch.zeros(B, dtype=torch.float32, device=dev)
+            self.pf_minmax = torch.ones(B, 2, dtype=torch.float32, device=dev)
+            self._pf_out = None
         self.phi = torch.zeros(B, 64, device=dev)
         self._in = torch.zeros(B, ld_in, device=dev)
         # sparse: the rings live on the device in time order (ring_dev; `ring` is gone, rings() reads them back), one push per tick
@@ -2489,6 +2616,17 @@ class MultiStreamConverter:
             raise ValueError(f"slot {slot}: envelope={a!r} needs a converter built with MultiStreamConverter(..., envelope=True)")
         return a
 
+    def _session_post_filter(self, slot, p):
+        """a session's post filter amount (None: 0), checked against the converter"""
+        a = p.get("post_filter", 0.0)
+        try:
+            a = check_post_filter(0.0 if a is None else a)[0]
+        except ValueError as e:
+            raise ValueError(f"slot {slot}: {e}") from None
+        if a > 0 and not self.post_filter:
+            raise ValueError(f"slot {slot}: post_filter={a!r} needs a converter built with MultiStreamConverter(..., post_filter=True)")
+        return a
+
     def _session_conceal(self, slot, p, rate=None):
         """a session's concealment -> (on, consts) at its rate, None in a converter without conceal; checked against the converter.
         conceal None: the converter's (on in a conceal=True converter)"""
@@ -2618,6 +2756,7 @@ class MultiStreamConverter:
         xlen = self._session_seam(slot, p, rate)
         limit = self._session_limit(slot, p, rate)
         env = self._session_envelope(slot, p)
+        pfa = self._session_post_filter(slot, p)
         con = self._session_conceal(slot, p, rate)
         track = self._session_track(slot, p)
         voicing = self._session_voicing(slot, p)
@@ -2695,6 +2834,8 @@ class MultiStreamConverter:
             self.look[slot], self.hold[slot], self.ceil[slot] = limit
         if self.envelope:
             self.env_amount[slot] = env
+        if self.post_filter:
+            self.pf_alpha[slot] = pfa
         if self.loud:
             self.loud_on[slot] = loud[0]
             if loud[0]:
@@ -2777,7 +2918,7 @@ class MultiStreamConverter:
              auto_pitch=False, gate_db=None, gate_hold=0.2, crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0,
              limit_hold_ms=20.0, envelope=0.0, conceal=None, intonation=1.0, auto_range=False, pitch_track=False, track_weight=1.0,
              track_jump=12.0, lufs=None, voicing=False, voicing_on=common.VOICING_ON, voicing_off=common.VOICING_OFF,
-             voicing_floor_db=common.VOICING_FLOOR_DB, match_path=False, path_weight=common.PATH_WEIGHT):
+             voicing_floor_db=common.VOICING_FLOOR_DB, match_path=False, path_weight=common.PATH_WEIGHT, post_filter=0.0):
         """start a session in `slot`: empty ring, phase 0.  k (default: the converter's): the session's own k, 1 <= k <= k_max, in
         a converter built with k_max= (every voice of the session needs at least k vectors); without k_max only the converter's k.  `rate` (default: the converter's input_sr) is one of the declared
         `rates`: the session sends and receives chunk * rate / input_sr samples per tick, for its whole life.  world_pitch=True:
@@ -2812,7 +2953,9 @@ class MultiStreamConverter:
         left alone): what the session emits is brought to it by a running BS.1770 loudness and a slewed gain, ahead of the limiter.
         match_path=True (needs a match_path=True converter): each frame's matched feature is ONE of its k nearest rows, chosen by a
         Viterbi path over the ring's frames that weighs the cosine between consecutive chosen rows by path_weight (>= 0; 0 is the
-        k = 1 match) against a candidate's cosine below the frame's best one; a blend: every voice's list takes its own path"""
+        k = 1 match) against a candidate's cosine below the frame's best one; a blend: every voice's list takes its own path.
+        post_filter (above 0: needs a post_filter=True converter): the alpha of the session's adaptive formant post filter, at most
+        0.85 (0.8 is the classic setting): the valleys between the formants of the converted wave are deepened, its level kept"""
         slot = self._slot(slot)
         rate = int(self.input_sr if rate is None else rate)
         if rate not in self.rates:
@@ -2823,7 +2966,7 @@ class MultiStreamConverter:
                  limit_lookahead_ms=limit_lookahead_ms, limit_hold_ms=limit_hold_ms, envelope=envelope, conceal=conceal,
                  intonation=intonation, auto_range=auto_range, pitch_track=pitch_track, track_weight=track_weight,
                  track_jump=track_jump, lufs=lufs, voicing=voicing, voicing_on=voicing_on, voicing_off=voicing_off,
-                 voicing_floor_db=voicing_floor_db, match_path=match_path, path_weight=path_weight)
+                 voicing_floor_db=voicing_floor_db, match_path=match_path, path_weight=path_weight, post_filter=post_filter)
         self._apply(slot, p, rate)                            # (validates the voice before anything changes)
         self._set_rate(slot, rate)
         self.params[slot] = p
@@ -2847,7 +2990,7 @@ class MultiStreamConverter:
     def set(self, slot, **params):
         """change a session's settings between ticks (voice, pitch, f0_rate, alpha, gain, input_gain, world_pitch, k, auto_pitch,
         intonation, auto_range, pitch_track, track_weight, track_jump, voicing, voicing_on, voicing_off, voicing_floor_db, match_path, path_weight, gate_db, gate_hold, crossfade_ms, limit_db, limit_lookahead_ms,
-        limit_hold_ms, envelope, conceal, lufs; the gate's state, the saved tail, the running loudness with its gain and the
+        limit_hold_ms, envelope, post_filter, conceal, lufs; the gate's state, the saved tail, the running loudness with its gain and the
         limiter's history are kept: a longer crossfade fades over what the tail holds this tick and in full from the next, and a
         limiter switched on or retuned sees the required gains of the samples already emitted).
         The running source register is kept: a new voice changes the target only, and auto_pitch=True after False resumes from
@@ -2914,6 +3057,9 @@ class MultiStreamConverter:
         if self.envelope:
             self.env_amount[slot] = 0.0
             self.env_minmax[slot] = 1.0
+        if self.post_filter:
+            self.pf_alpha[slot] = 0.0
+            self.pf_minmax[slot] = 1.0
         if self.loud:
             self.loud_on[slot] = False
             self._loud_reset(slot)
@@ -2972,6 +3118,23 @@ class MultiStreamConverter:
         floor_ms, g_lo, g_hi, radius = self._env
         return envelope_waves_(self._env_out, wave, data, None, self.env_amount, ENVELOPE_HOP, radius, floor_ms, g_lo, g_hi,
                                self.env_minmax)
+
+    def post_filter_db(self):
+        """the level correction of the post filter in the latest tick, a list of B pairs: 20 log10 of the smallest and of the largest
+        frame gain over the slot's whole wave; (0.0, 0.0) for a slot that is not filtered.  One host read"""
+        if not self.post_filter:
+            raise ValueError("post_filter_db needs a converter built with MultiStreamConverter(..., post_filter=True)")
+        return minmax_db(self.pf_minmax.tolist())
+
+    def _postfilter(self, wave):
+        """the decoder's 16 kHz waves [B, L] through the post filter, row by row at the sessions' alphas, into the buffer allocated
+        once"""
+        wave = wave.contiguous()
+        if self._pf_out is None or self._pf_out.shape != wave.shape:
+            self._pf_out = torch.empty_like(wave)
+        ratio, tilt, order, window, floor_ms, g_lo, g_hi = self._pf
+        return postfilter_waves_(self._pf_out, wave, None, self.pf_alpha, POSTFILTER_HOP, window, order, self._pf_win, self._pf_lag,
+                                 ratio, tilt, floor_ms, g_lo, g_hi, self.pf_minmax)
 
     def seam_db(self):
         """the seam statistic of the latest tick, a list of B floats: 10 log10(sum (c - t)^2 / sum c^2) over the faded head of each
@@ -3091,6 +3254,8 @@ class MultiStreamConverter:
         join()
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0
+        if self.post_filter:                                  # the decoder's spectrum first: the envelope sets the level of the filtered wave
+            wave = self._postfilter(wave)
         if self.envelope:                                     # the decoder's level -> the source's contour, before all downstream
             wave = self._follow(wave, data)
         if self._rt is None:

@@ -25,6 +25,11 @@ Envelope follow (`-env`): RealtimeConverter(envelope=A, envelope_floor_db=, enve
 alive_envelope_waves (csrc/envelope.hip, module/multistream.py "Envelope follow") at one row right after the decoder, on both step forms:
 the decoder's 16 kHz wave takes on the loudness contour of the 16 kHz ring the gate also sees, by the amount A in (0, 1].  It is a
 stateless function of the step's ring and wave: nothing is kept between steps.  Without it (A = 0) the converter launches what it did.
+
+Post filter (`-pf`): RealtimeConverter(post_filter=A, post_filter_ratio=, post_filter_tilt=, post_filter_order=, post_filter_window_ms=)
+runs alive_postfilter_waves (csrc/postfilter.hip, module/multistream.py "Post filter") at one row right after the decoder and before the
+envelope follow, on both step forms: the adaptive formant post filter at alpha A in (0, 0.85] on the decoder's 16 kHz wave.  Stateless
+likewise; without it (A = 0) the converter launches what it did.
 """
 import numpy as np
 import torch
@@ -147,6 +152,7 @@ def capture_step(device, step, phi):
 class RealtimeConverter:
     limiter = False                    # (set per converter in __init__: whether the step carries the limiter kernel)
     envelope = False                   # (likewise: whether the step carries the envelope kernel)
+    post_filter = False                # (likewise: whether the step carries the post filter kernel)
     pitch_range = False                # (likewise: whether the f0 branch runs the pitch-range follower and the centred transform)
     pitch_track = False                # (likewise: whether the f0 branch stores the class scores and runs the tracker kernel)
     voicing = False                    # (likewise: whether the f0 branch runs the voicing kernels; voicing_state() is the read-back)
@@ -157,7 +163,8 @@ class RealtimeConverter:
                  reuse_interior="auto", world_pitch=False, gate_db=None, gate_hold=0.2, gate_lookahead=None,
                  crossfade_ms=None, limit_db=None, limit_lookahead_ms=5.0, limit_hold_ms=20.0, limit_history=0.05,
                  envelope=0.0, envelope_floor_db=-60.0, envelope_range_db=12.0, envelope_radius=1, intonation=1.0,
-                 intonation_half_life=10.0, intonation_prior=0.5, pitch_track=None, voicing=None, match_path=None):
+                 intonation_half_life=10.0, intonation_prior=0.5, pitch_track=None, voicing=None, match_path=None,
+                 post_filter=0.0, post_filter_ratio=0.625, post_filter_tilt=0.5, post_filter_order=16, post_filter_window_ms=40.0):
         self.device = torch.device(device)
         path = common.path_options(match_path, "RealtimeConverter: match_path")
         self.match_path = path is not None                  # (checked before anything is built)
@@ -190,6 +197,10 @@ class RealtimeConverter:
         from .multistream import check_envelope
         env = check_envelope(0.0 if envelope is None else envelope, envelope_floor_db, envelope_range_db, envelope_radius)
         self.envelope = env[0] > 0         # (checked before anything is built)
+        from .multistream import check_post_filter
+        pf = check_post_filter(0.0 if post_filter is None else post_filter, post_filter_ratio, post_filter_tilt, post_filter_order,
+                               post_filter_window_ms)
+        self.post_filter = pf[0] > 0       # (checked before anything is built)
         self.limiter = limit_db is not None
         if self.limiter:                   # (checked before anything is built)
             from .multistream import check_limit, limit_history_width
@@ -275,6 +286,14 @@ class RealtimeConverter:
             self._env = env[1:]                # (floor_ms, g_lo, g_hi, radius)
             self._env_amount = torch.tensor([env[0]], dtype=torch.float32, device=self.device)
             self._env_out = None
+        if self.post_filter:
+            # the multi-session post filter at one row; no state: a function of the step's wave.  _pf_out is allocated once, by the
+            # first step
+            from .multistream import postfilter_tables
+            self._pf = pf[1:]                  # (ratio, tilt, order, window, floor_ms, g_lo, g_hi)
+            self._pf_win, self._pf_lag = postfilter_tables(pf[4], pf[3], self.device)
+            self._pf_alpha = torch.tensor([pf[0]], dtype=torch.float32, device=self.device)
+            self._pf_out = None
         if self.pitch_range:
             # the multi-session pitch range at one row: an always-emitting session without auto pitch or auto range (there is no
             # pool); _reg_state = (S, W, Q) is the stream's, like the phase
@@ -372,7 +391,7 @@ class RealtimeConverter:
         content, f0 = self._front_end(spectrogram(data), data)
         wave, phi_out = self.dec(content, f0=f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = f0                  # (a view of the per-shape side-stream buffer: valid until the next step)
-        wave = self._follow(wave, data)
+        wave = self._follow(self._postfilter(wave), data)
         wave = self._limit(self._gate_edge(self._seam(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain))))[0]   # gain, then resample
         return wave, phi_out[:, :, self.end_of_output]
 
@@ -402,6 +421,19 @@ class RealtimeConverter:
             wave = seam_rows_(wave.contiguous(), self._seam_lo, self._seam_shift, self._seam_x, self._seam_emit, self._seam_tail,
                               self._seam_stored, self._g0 if self.gate else None, self._g1 if self.gate else None,
                               self._seam_stats)
+        return wave
+
+    def _postfilter(self, wave):
+        """post filter on: the decoder's 16 kHz wave [1, L] through alive_postfilter_waves at one row, into the buffer allocated once
+        (right after the decoder, before the envelope follow)"""
+        if self.post_filter:
+            from .multistream import POSTFILTER_HOP, postfilter_waves_
+            wave = wave.contiguous()
+            if self._pf_out is None or self._pf_out.shape != wave.shape:
+                self._pf_out = torch.empty_like(wave)
+            ratio, tilt, order, window, floor_ms, g_lo, g_hi = self._pf
+            wave = postfilter_waves_(self._pf_out, wave, None, self._pf_alpha, POSTFILTER_HOP, window, order, self._pf_win,
+                                     self._pf_lag, ratio, tilt, floor_ms, g_lo, g_hi)
         return wave
 
     def _follow(self, wave, data):
@@ -534,7 +566,7 @@ class RealtimeConverter:
             self._c_f0[:, :, a:].copy_(f0[:, :, margin:])
         wave, phi_out = self.dec(self._c_feat, f0=self._c_f0, phi=phi, crop=(self.begin_of_output, self.end_of_output))
         self.last_f0 = self._c_f0
-        wave = self._follow(wave, data)
+        wave = self._follow(self._postfilter(wave), data)
         wave = self._limit(self._gate_edge(self._seam(audio_io.resample(wave, 16000, self.output_sr, pre_gain_db=self.gain))))[0]
         return wave, phi_out[:, :, self.end_of_output]
 

@@ -47,6 +47,9 @@ The sessions file is a JSON list; each entry:
    "envelope": 0.7,                       optional, a number in [0, 1] or null (default: -env): how far the session's converted voice
                                           follows the loudness contour of its input (module/multistream.py "Envelope follow"); 0 or
                                           null: the decoder's own level
+   "post_filter": 0.8,                    optional, a number in [0, 0.85] or null (default: -pf): the alpha of the session's adaptive
+                                          formant post filter, right after the decoder and ahead of "envelope" (module/multistream.py
+                                          "Post filter"); 0 or null: no filter
    "codebook": 4096,                      optional, an integer >= 1 or null (default: --codebook): the session's voice is condensed to
                                           that many centroid rows by k-means when it is packed or enrolled (module/codebook.py); a
                                           voice of that many rows or fewer stays as it is.  A codebook's rows are means: use k 1 or 2
@@ -92,7 +95,8 @@ The converter carries the loudness kernel only if some session ends up normalise
 without the flag, runs as before.  --loudness-half-life / --loudness-prior / --loudness-gate / --loudness-max-db / --loudness-slew hold
 for the whole converter.
 The converter carries the envelope kernel only if some session ends up following ("envelope" above 0, or -env): a file without the
-key, run without the flag, runs as before.
+key, run without the flag, runs as before.  Likewise the post filter kernel ("post_filter" above 0, or -pf; --post-filter-ratio /
+--post-filter-tilt hold for the whole converter).
 The voices are condensed only for sessions with a "codebook" (or under --codebook): a file without the key, run without the flag, runs
 as before.  The size is part of the voice's pool name: sessions on the same sources at different sizes get different voices; a blend's
 components are each condensed to the session's size.
@@ -129,7 +133,7 @@ from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
 from module.multistream import (MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
-                                check_conceal_ms, check_crossfade_ms, check_envelope, check_intonation, check_limit,
+                                check_conceal_ms, check_crossfade_ms, check_envelope, check_intonation, check_limit, check_post_filter,
                                 check_loudness, check_loudness_stream,
                                 gate_hold_ticks, gate_thr_ms, measure_register)
 from module.spectrogram import spectrogram                       # noqa: E402
@@ -140,6 +144,7 @@ SESSION_KEYS = ("input", "target", "lib", "pitch", "f0_rate", "alpha", "gain", "
 GATE_KEYS = ("gate_db", "gate_hold")     # taken per session too; a loaded session carries them only when it is gated
 SEAM_KEYS = ("crossfade_ms",)            # taken per session too; a loaded session carries it only when it crossfades
 LIMIT_KEYS = ("limit_db", "limit_lookahead_ms", "limit_hold_ms")      # likewise; a loaded session carries them only when it limits
+POSTFILTER_KEYS = ("post_filter",)       # likewise; a loaded session carries it only when it is filtered (an alpha above 0)
 ENVELOPE_KEYS = ("envelope",)            # likewise; a loaded session carries it only when it follows (an amount above 0)
 LOUDNESS_KEYS = ("lufs",)                # likewise; a loaded session carries it only when it is normalised
 CODEBOOK_KEYS = ("codebook",)            # taken per session too; a loaded session carries it only when its voice is condensed
@@ -206,6 +211,13 @@ def build_parser():
                         help="the most the loudness gain turns a session up or down (default 12)")
     parser.add_argument('--loudness-slew', default=6.0, type=float, metavar="DB",
                         help="the most the loudness gain moves per second, in dB (default 6)")
+    parser.add_argument('-pf', '--post-filter-alpha', default=0.0, type=float, metavar="A",
+                        help="adaptive formant post filter on the sessions' converted waves, ahead of -env: the alpha of the denominator, 0 "
+                             "(off, the default) to 0.85, unless their \"post_filter\" says otherwise (module/multistream.py \"Post filter\")")
+    parser.add_argument('--post-filter-ratio', default=0.625, type=float, metavar="R",
+                        help="the post filter's numerator alpha as a share of the denominator's, 0 to 1 (default 0.625)")
+    parser.add_argument('--post-filter-tilt', default=0.5, type=float, metavar="T",
+                        help="the share of the post filter's spectral tilt that is taken out again, 0 to 1 (default 0.5)")
     parser.add_argument('-env', '--envelope', default=0.0, type=float, metavar="A",
                         help="envelope follow: the sessions' converted voices take on their inputs' loudness contours by this amount, 0 (off, the "
                              "default) to 1, unless their \"envelope\" says otherwise (module/multistream.py \"Envelope follow\").  It can "
@@ -405,6 +417,17 @@ def session_envelope(s, where, envelope=0.0, floor_db=-60.0, range_db=12.0, radi
     return a if a > 0 else None
 
 
+def session_post_filter(s, where, alpha=0.0, ratio=0.625, tilt=0.5):
+    """an entry's "post_filter" (default `alpha`; a JSON null or 0 switches the default off) -> the alpha as a float in (0, 0.85], or
+    None for a session that is not filtered; ValueError otherwise (ratio and tilt are those of the flags, checked with it)"""
+    a = s.get("post_filter", alpha)
+    try:
+        a = check_post_filter(0.0 if a is None else a, ratio, tilt)[0]
+    except ValueError as e:
+        raise ValueError(f"{where}: {e}") from None
+    return a if a > 0 else None
+
+
 def session_codebook(s, where, codebook=None):
     """an entry's "codebook" (default `codebook`) -> an integer >= 1, or None for a voice that stays as it is (a JSON null switches
     the default off); ValueError otherwise"""
@@ -469,7 +492,7 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
                   envelope_radius=1, conceal_hold_ms=10.0, conceal_fade_ms=50.0, conceal_recover_ms=5.0, intonation=1.0,
                   auto_range=False, pitch_track=False, track_weight=common.TRACK_WEIGHT, track_jump=common.TRACK_JUMP, lufs=None,
                   voicing=False, voicing_on=common.VOICING_ON, voicing_off=common.VOICING_OFF, voicing_floor_db=common.VOICING_FLOOR_DB,
-                  match_path=False, path_weight=common.PATH_WEIGHT):
+                  match_path=False, path_weight=common.PATH_WEIGHT, post_filter=0.0, post_filter_ratio=0.625, post_filter_tilt=0.5):
     """the sessions file -> list of dicts with every key filled in ("k": the session's own, default `k`; "auto_pitch": default
     `auto_pitch`); a gated session ("gate_db", default `gate_db`) also carries "gate_db" and "gate_hold", a session without a gate
     neither, so a file without the keys loads to what it did; likewise "codebook" (default `codebook`) only on a session whose voice is
@@ -482,7 +505,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     `track_weight`, `track_jump`) only on a session that tracks; "lufs" (default `lufs`) only on a session that is normalised;
     "voicing" (true), "voicing_on", "voicing_off" and "voicing_floor_db" (defaults `voicing`, `voicing_on`, `voicing_off`,
     `voicing_floor_db`) only on a session that decides; "match_path" (true) and "path_weight" (defaults `match_path`, `path_weight`)
-    only on a session whose match takes the path; ValueError on a malformed entry"""
+    only on a session whose match takes the path; "post_filter" (default `post_filter`) only on a session that is filtered at an
+    alpha above 0; ValueError on a malformed entry"""
     session_path({}, "-mp / --path-weight", match_path, path_weight)
     session_voicing({}, "-vd / --voicing-on / --voicing-off / --voicing-floor", voicing, voicing_on, voicing_off, voicing_floor_db)
     session_track({}, "-pt / --track-weight / --track-jump", pitch_track, track_weight, track_jump)
@@ -497,6 +521,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
     session_limit({}, "-lim / --limit-lookahead / --limit-hold", limit_db, limit_lookahead_ms, limit_hold_ms)
     env = (envelope_floor_db, envelope_range_db, envelope_radius)
     session_envelope({}, "-env / --envelope-floor / --envelope-range / --envelope-radius", envelope, *env)
+    pf = (post_filter_ratio, post_filter_tilt)
+    session_post_filter({}, "-pf / --post-filter-ratio / --post-filter-tilt", post_filter, *pf)
     session_range({}, "-int / --auto-range", intonation, auto_range)
     session_loudness({}, "-lufs", lufs)
     with open(path) as f:
@@ -510,15 +536,16 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             raise ValueError(f"session {i}: an object with an \"input\" wav is required")
         unknown = (set(s) - set(SESSION_KEYS) - set(GATE_KEYS) - set(SEAM_KEYS) - set(LIMIT_KEYS) - set(ENVELOPE_KEYS) - set(CODEBOOK_KEYS)
                    - set(STALL_KEYS) - set(LOSE_KEYS) - set(CONCEAL_KEYS) - set(RANGE_KEYS) - set(RANGE_ST_KEYS) - set(TRACK_KEYS) - set(VOICING_KEYS)
-                   - set(LOUDNESS_KEYS) - set(PATH_KEYS))
+                   - set(LOUDNESS_KEYS) - set(PATH_KEYS) - set(POSTFILTER_KEYS))
         if unknown:
             raise ValueError(f"session {i}: unknown keys {sorted(unknown)} (known: "
-                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS + TRACK_KEYS + LOUDNESS_KEYS + VOICING_KEYS + PATH_KEYS})")
+                             f"{SESSION_KEYS + GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CODEBOOK_KEYS + STALL_KEYS + LOSE_KEYS + CONCEAL_KEYS + RANGE_KEYS + RANGE_ST_KEYS + TRACK_KEYS + LOUDNESS_KEYS + VOICING_KEYS + PATH_KEYS + POSTFILTER_KEYS})")
         gate = session_gate(s, f"session {i}", gate_db, gate_hold)
         xf = session_crossfade(s, f"session {i}", crossfade_ms)
         size = session_codebook(s, f"session {i}", codebook)
         lim = session_limit(s, f"session {i}", limit_db, limit_lookahead_ms, limit_hold_ms)
         amount = session_envelope(s, f"session {i}", envelope, *env)
+        pfa = session_post_filter(s, f"session {i}", post_filter, *pf)
         target = session_loudness(s, f"session {i}", lufs)
         rel = lambda p: None if p is None else (p if os.path.isabs(p) else os.path.join(base, p))      # noqa: E731
         blend = blend_sources(s, f"session {i}", rel) if "blend" in s else None
@@ -553,6 +580,8 @@ def load_sessions(path, k=4, auto_pitch=False, gate_db=None, gate_hold=0.2, code
             e["limit_db"], e["limit_lookahead_ms"], e["limit_hold_ms"] = lim
         if amount is not None:
             e["envelope"] = amount
+        if pfa is not None:
+            e["post_filter"] = pfa
         if target is not None:
             e["lufs"] = target
         if size is not None:
@@ -735,7 +764,8 @@ def main(argv=None):
                              args.crossfade, args.limit, args.limit_lookahead, args.limit_hold, args.envelope, args.envelope_floor,
                              args.envelope_range, args.envelope_radius, args.conceal_hold, args.conceal_fade, args.conceal_recover,
                              args.intonation, args.auto_range, args.pitch_track, tw, tj, args.lufs, args.voicing, args.voicing_on,
-                             args.voicing_off, args.voicing_floor, args.match_path, args.path_weight)
+                             args.voicing_off, args.voicing_floor, args.match_path, args.path_weight, args.post_filter_alpha,
+                             args.post_filter_ratio, args.post_filter_tilt)
     loud = dict(loudness_half_life=args.loudness_half_life, loudness_prior=args.loudness_prior, loudness_gate_lufs=args.loudness_gate,
                 loudness_max_db=args.loudness_max_db, loudness_slew_db=args.loudness_slew)
     try:
@@ -794,13 +824,15 @@ def main(argv=None):
                                 **(dict(loudness=True, **loud) if any("lufs" in s for s in sessions) else {}),
                                 **(dict(envelope=True, envelope_floor_db=args.envelope_floor, envelope_range_db=args.envelope_range,
                                         envelope_radius=args.envelope_radius) if any("envelope" in s for s in sessions) else {}),
+                                **(dict(post_filter=True, post_filter_ratio=args.post_filter_ratio, post_filter_tilt=args.post_filter_tilt)
+                                   if any("post_filter" in s for s in sessions) else {}),
                                 **(dict(sparse=True) if args.sparse or conceal or any("stall" in s for s in sessions) else {}),
                                 **(dict(conceal=True, conceal_hold_ms=args.conceal_hold, conceal_fade_ms=args.conceal_fade,
                                         conceal_recover_ms=args.conceal_recover) if conceal else {}))
     params = [dict(voice=n, pitch=s["pitch"], f0_rate=s["f0_rate"], alpha=s["alpha"], gain=s["gain"],
                    input_gain=s["input_gain"], rate=r, world_pitch=s["world_pitch"], k=s["k"], auto_pitch=s["auto_pitch"],
                    **{g: s[g] for g in GATE_KEYS + SEAM_KEYS + LIMIT_KEYS + ENVELOPE_KEYS + CONCEAL_KEYS + RANGE_KEYS + TRACK_KEYS
-                      + LOUDNESS_KEYS + VOICING_KEYS + PATH_KEYS if g in s})
+                      + LOUDNESS_KEYS + VOICING_KEYS + PATH_KEYS + POSTFILTER_KEYS if g in s})
               for n, s, r in zip(names, sessions, in_sr)]
     if not args.no_graph:
         conv.enable_graph()

@@ -75,6 +75,13 @@ def build_parser():
                         help="the most the envelope follow turns a frame up or down (default 12)")
     parser.add_argument('--envelope-radius', default=1, type=int, metavar="FRAMES",
                         help="20 ms frames on each side over which the envelope follow smooths both levels, 0 to 4 (default 1: 60 ms)")
+    parser.add_argument('-pf', '--post-filter-alpha', default=0.0, type=float, metavar="A",
+                        help="adaptive formant post filter on the converted wave, right after the decoder and ahead of -env: the alpha of "
+                             "the denominator, 0 (off, the default) to 0.85 (module/multistream.py \"Post filter\"; this build only)")
+    parser.add_argument('--post-filter-ratio', default=0.625, type=float, metavar="R",
+                        help="the post filter's numerator alpha as a share of -pf, 0 to 1 (default 0.625)")
+    parser.add_argument('--post-filter-tilt', default=0.5, type=float, metavar="T",
+                        help="the share of the post filter's spectral tilt that is taken out again, 0 to 1 (default 0.5)")
     parser.add_argument('-int', '--intonation', default=1.0, type=float,
                         help="scale the pitch excursions around the stream's running mean pitch by this factor, as inference.py's -int "
                              "does around a window's mean (default 1: off; module/multistream.py \"Pitch range\"; this build only)")
@@ -144,6 +151,8 @@ def main(argv=None):
                               if args.limit is not None else {}),
                            **(dict(envelope=args.envelope, envelope_floor_db=args.envelope_floor, envelope_range_db=args.envelope_range,
                                    envelope_radius=args.envelope_radius) if args.envelope else {}),
+                           **(dict(post_filter=args.post_filter_alpha, post_filter_ratio=args.post_filter_ratio,
+                                   post_filter_tilt=args.post_filter_tilt) if args.post_filter_alpha else {}),
                            **(dict(intonation=args.intonation) if args.intonation != 1.0 else {}),
                            **({} if track is None else dict(pitch_track=track)),
                            **({} if voicing is None else dict(voicing={k: voicing[k] for k in common.VOICING_KEYS})),

@@ -1221,6 +1221,49 @@ int alive_conceal_rows(const int16_t* ring, int N, int ld, const int* ring_len, 
 int alive_envelope_waves(float* out, const float* y, int ld_y, const float* x, int ld_x, int N, const int* len, const float* amount,
                          int hop, int radius, double floor_ms, double g_lo, double g_hi, float* gain_minmax, void* stream);
 
+/* Post filter (csrc/postfilter.hip): an adaptive formant post filter (Chen and Gersho 1995; G.729 4.2) on the converted 16 kHz wave:
+ * per frame an LPC analysis gives A(z), the frame's filter is A(z / b) / A(z / a) with a tilt compensation, and a frame gain restores
+ * the level.  Stateless and OUT OF PLACE: out[N][ld] from y[N][ld].  All pointers are DEVICE pointers; the call allocates nothing,
+ * synchronises nothing and reads nothing on the host; the grid depends on N, ld and hop alone (graph-capturable: a captured call serves
+ * any alphas and lengths).  No floating-point atomics; every store is a plain vector store.
+ * Per row, n = len[row] clamped to [0, ld] (len NULL: ld), frames of `hop` samples, F = ceil(n / hop), a = (double)alpha[row],
+ * b = a * ratio, e = floor_ms (a mean square).  Per frame f:
+ *     q[i]      the int16 grid: clamp(rintf(32768 y[i]), +-32767), a NaN 0, 0 outside [0, n)
+ *     s[i]      q[f hop - (window - hop) / 2 + i] * win[i] for i < window          (win: `window` integers, 64 = unity)
+ *     R[k]      sum_i s[i] s[i + k] for k = 0 .. order: exact integers (below 2^53 for win <= 64), so their order cannot show
+ *     r[k]      (double)R[k] * lag[k]; r[0] = r[0] * 1.0001                         (lag: order + 1 doubles)
+ *     Levinson-Durbin in fp64, err = r[0], for m = 1 .. order: acc = r[m], acc = acc + A[j] * r[m - j] for j = 1 .. m - 1 ascending;
+ *               k = -acc / err; A'[j] = A[j] + k * A[m - j] for j < m, A'[m] = k; err = err * (1 - k * k)
+ *     den[j]    A[j] * a^j, num[j] = A[j] * b^j, A[0] = 1, the powers by repeated multiplication
+ *     h0[k]     (k <= order ? num[k] : 0) - acc for k < ALIVE_POSTFILTER_TAPS, acc = 0.0, acc = acc + den[j] * h0[k - j] for
+ *               j = 1 .. min(k, order) ascending
+ *     t         tilt * (c1 / c0), c0 = sum_k h0[k]^2 and c1 = sum_k h0[k] h0[k + 1], both ascending from 0.0
+ *     h[k]      h0[k] - t * h0[k - 1], h[0] = h0[0]
+ *     U(f, i)   sum_k h[k] * (double)y[i - k] for k ascending from 0.0, y = 0 before the row's start
+ *     g[f]      min(max(sqrt(q), g_lo), g_hi) if q = (Ein + e c) / (Eout + e c) and its denominator are finite (an infinite Eout
+ *               would give q = 0), else 1: Ein = sum y[i]^2 and Eout = sum U(f, i)^2 over the frame's own c samples, both in the
+ *               order of the envelope follow's frame sums
+ * A frame is the identity (h = delta, so g = 1) when R[0] <= 0, when a k is not finite or |k| >= 1, or when err stops being > 0.
+ *     out[i]    (float)(g[0] U(0, i)) for i < hop / 2; (float)(g[F - 1] U(F - 1, i)) for i >= hop / 2 + (F - 1) hop; otherwise
+ *               (float)(Z0 + (Z1 - Z0) * w) with f = (i - hop / 2) / hop, w = (double)((i - hop / 2) - f hop) / (double)hop,
+ *               Z0 = g[f] U(f, i) and Z1 = g[f + 1] U(f + 1, i);  y[i] for i >= n
+ * A row whose alpha (the float) is not in (0, 0.85] -- 0, a NaN, 0.9 -- or whose n is 0 is copied bit for bit: the poles lie inside
+ * radius a, and at 0.85 the 128 taps leave less than 1e-9 of full scale.  A NaN or an infinite sample makes up to 127 samples behind it
+ * non-finite and leaves the gains of the frames those lie in at 1.  A row's result does not depend on N, on the other rows or on the
+ * tiling.  Everything after R is fp64 with only + - * / and sqrt, each rounded on its own: bitwise tools/postfilter_ref.py.
+ *   The grid is tiles of ALIVE_POSTFILTER_TILE centre-to-centre units x rows, 256 threads; a tile recomputes the filters and gains of
+ *   the frames it shares with its neighbours and reads the samples around its own, so an `out` that overlaps y is refused.
+ *   gain_minmax float [N][2] or NULL: the row's smallest and largest g[f] as floats, (1, 1) for a copied row (filled with (+inf, 0)
+ *   first, then integer atomic min / max on the floats' bits: every g is > 0).
+ *   0 < N <= 65535; ld > 0; hop even in [2, 1024]; hop <= window <= 1024 with window - hop even; 1 <= order <=
+ *   ALIVE_POSTFILTER_MAX_ORDER and < window; ratio and tilt finite in [0, 1]; floor_ms > 0; 0 < g_lo <= 1 <= g_hi; all finite. */
+#define ALIVE_POSTFILTER_TAPS 128
+#define ALIVE_POSTFILTER_MAX_ORDER 32
+#define ALIVE_POSTFILTER_TILE 16
+int alive_postfilter_waves(float* out, const float* y, int ld, int N, const int* len, const float* alpha, int hop, int window,
+                           int order, const int16_t* win, const double* lag, double ratio, double tilt, double floor_ms, double g_lo,
+                           double g_hi, float* gain_minmax, void* stream);
+
 /* Voice codebooks (csrc/codebook.hip; module/codebook.py build_codebook): the device passes of one k-means iteration over a voice's
  * rows that are not the search.  The assignment of a row is the strict search's top-1 against the centroids (alive_knn_search_strict)
  * and the inverted index a stable sort of the assignment; both are the caller's.  All pointers are DEVICE pointers; no call allocates,

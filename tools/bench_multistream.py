@@ -39,6 +39,9 @@ more launch pair after the decoder, alive_envelope_waves, csrc/envelope.hip) bes
 and timed in alternating rounds (envelope_off_tick_*; the medians over the rounds, and the spread of the plain converter's rounds as the
 yardstick), the call's own time by device events around 200 back-to-back eager calls at the tick's shapes (envelope_call_us, its fill
 launch included) with the 12 B L bytes it moves (envelope_call_bytes), and the gains of the last tick (envelope_db_min / _max).
+--post-filter does the same for a post_filter=True converter with every session at alpha 0.8 (post_filter_tick_* beside
+post_filter_off_tick_*, post_filter_call_us for alive_postfilter_waves at the tick's shapes, csrc/postfilter.hip; post_filter_db_min /
+_max).  --post-filter-offline times the offline call alone at 384 rows of 144 000 samples (post_filter_offline_ms).
 --loudness adds the graph tick p50 / p99 of a loudness=True converter with every session normalised to -23 LUFS (loudness_tick_*: one
 more launch between the gate's edge and the limiter, alive_loudness_rows, csrc/loudness.hip) beside the plain converter, both alive in
 the one process and timed in alternating rounds (loudness_off_tick_*; the medians over the rounds, and the spread of the plain
@@ -86,7 +89,7 @@ alive_ring_push_rows with every row present (push_call_us).
 
     python tools/bench_multistream.py [--batches 1,8,32,64,128] [--ticks 40] [--warmup 6] [--rates 8000,16000,44100,48000]
                                       [--world off,0,0.5,1] [--voices shared,distinct] [--blend] [--mixed-k] [--auto-pitch] [--pitch-range]
-                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--loudness] [--pitch-track] [--voicing] [--match-path]
+                                      [--gated 0,0.5,1] [--crossfade] [--limit] [--envelope] [--post-filter] [--loudness] [--pitch-track] [--voicing] [--match-path]
                                       [--out multistream.json]
     python tools/bench_multistream.py --loudness-offline [--out loudness_offline.json]
     python tools/bench_multistream.py --voicing-offline [--out voicing_offline.json]
@@ -181,6 +184,18 @@ def loudness_offline_leg(shapes=((64, 10.0), (8, 60.0)), rate=48000):
         recs.append(rec)
         del y
     return recs
+
+
+def post_filter_offline_leg(rows=384, samples=144000):
+    """the offline post_filter call (its two small tensors and the output allocation included) over `rows` rows of `samples` samples of
+    make_voiced speech at alpha 0.8 and the defaults; a copy of the same rows by the same call at alpha 0 beside it"""
+    y = synthetic.make_voiced(samples, 3)[0].cuda().repeat(rows, 1).contiguous()
+    us = time_calls(lambda: MS.post_filter(y, None, 0.8), reps=10)
+    us0 = time_calls(lambda: MS.post_filter(y, None, 0.0), reps=10)
+    rec = {"leg": "post_filter_offline", "rows": rows, "samples": samples, "post_filter_offline_ms": round(us / 1e3, 3),
+           "post_filter_offline_copy_ms": round(us0 / 1e3, 3), "ns_per_sample": round(us * 1e3 / (rows * samples), 4)}
+    print(json.dumps(rec), flush=True)
+    return [rec]
 
 
 def voicing_offline_leg(windows=384, frames=450):
@@ -453,6 +468,9 @@ def main():
                                                              "10 ms, and the plain converter a second time")
     ap.add_argument("--limit", action="store_true", help="also time a limiter=True converter, every session limiting at -12 dBFS, "
                                                          "and the plain converter a second time")
+    ap.add_argument("--post-filter", action="store_true", help="also time a post_filter=True converter, every session at alpha 0.8, "
+                    "beside the plain one in alternating rounds, and the call alone")
+    ap.add_argument("--post-filter-offline", action="store_true", help="only time the offline post_filter call at 384 x 144000")
     ap.add_argument("--envelope", action="store_true", help="also time an envelope=True converter, every session following at amount "
                                                             "1, against the plain converter in alternating rounds, and the call alone")
     ap.add_argument("--loudness", action="store_true", help="also time a loudness=True converter, every session normalised to -23 LUFS, "
@@ -500,6 +518,12 @@ def main():
         return
     if args.loudness_offline:
         rows = loudness_offline_leg()
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(rows, open(args.out, "w"), indent=1)
+        return
+    if args.post_filter_offline:
+        rows = post_filter_offline_leg()
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             json.dump(rows, open(args.out, "w"), indent=1)
@@ -703,6 +727,40 @@ def main():
                     rec["envelope_call_us"] = round(a.elapsed_time(b) * 1e3 / 200, 2)
                     rec["envelope_call_bytes"] = 12 * B * ld
                     del both, ec
+                if args.post_filter:
+                    both = {}
+                    for name, kw, sess in (("post_filter_off", {}, {}), ("post_filter", dict(post_filter=True), dict(post_filter=0.8))):
+                        c = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4, **kw)
+                        for s in range(B):
+                            c.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5, **sess)
+                        c.enable_graph()
+                        both[name] = c
+                    times = {name: [] for name in both}
+                    for _ in range(5):                         # alternating rounds in the one process
+                        for name, c in both.items():
+                            times[name].append(time_ticks(c, B, chunk, args.ticks, args.warmup + bs + 1, 300))
+                    for name, ts in times.items():
+                        rec[f"{name}_tick_p50_ms"] = round(float(np.median([t[0] for t in ts])), 3)
+                        rec[f"{name}_tick_p99_ms"] = round(float(np.median([t[1] for t in ts])), 3)
+                        rec[f"{name}_tick_p50_rounds_ms"] = [round(t[0], 3) for t in ts]
+                    pc = both["post_filter"]
+                    db = np.array(pc.post_filter_db())
+                    assert np.isfinite(db).all() and pc.captures == 1, (db, pc.captures)
+                    rec["post_filter_db_min"], rec["post_filter_db_max"] = round(float(db[:, 0].min()), 2), round(float(db[:, 1].max()), 2)
+                    ld = pc._pf_out.shape[1]
+                    g = torch.Generator(device="cuda").manual_seed(5)
+                    y = torch.randn(B, ld, device="cuda", generator=g) * 0.1
+                    for _ in range(10):
+                        pc._postfilter(y)
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    for _ in range(200):
+                        pc._postfilter(y)
+                    b.record()
+                    torch.cuda.synchronize()
+                    rec["post_filter_call_us"] = round(a.elapsed_time(b) * 1e3 / 200, 2)
+                    rec["post_filter_call_samples"] = B * ld
+                    del both, pc
                 if args.loudness:
                     both = {}
                     for name, kw, sess in (("loudness_off", {}, {}), ("loudness", dict(loudness=True), dict(lufs=-23.0))):
