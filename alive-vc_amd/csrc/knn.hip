@@ -196,8 +196,14 @@ __device__ __forceinline__ unsigned fp6_e2m3(float y) {
 // bf16[n32][32] -> [n32][32 bytes]: 32 codes in the first 24 bytes, 8 bytes of zeros.  Groups at or beyond n_valid (frame rows
 // past the bf16 image's padded end) are written as zeros without reading.
 // clip (optional, [rows]): set to 1 for every row (24 groups) with an element beyond e2m3's largest value.
+// when (the subspace search's lazy image: the steady state never reads it) -- 0: always; 1: only if *g_probe != 0 (a probe is due and
+// samples the image); 2: only if *g_sub == 2 (the gate sent the batch to the plain stage) and no probe built the image already
+// (g_probe null, or *g_probe == 0).  Blocks of a closed launch return at once, as in the other gated kernels.
 __global__ __launch_bounds__(256) void to_fp6_kernel(const unsigned short* __restrict__ in, int64_t n32, int64_t n_valid, u32x4* __restrict__ out,
-                                                     unsigned char* __restrict__ clip = nullptr) {
+                                                     unsigned char* __restrict__ clip = nullptr, int when = 0,
+                                                     const int* __restrict__ g_probe = nullptr, const int* __restrict__ g_sub = nullptr) {
+    if (when == 1 && *g_probe == 0) return;
+    if (when == 2 && (*g_sub != 2 || (g_probe != nullptr && *g_probe != 0))) return;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n32) return;
     if (i >= n_valid) {
@@ -220,6 +226,16 @@ __global__ __launch_bounds__(256) void to_fp6_kernel(const unsigned short* __res
     out[2 * i] = u32x4{wd[0], wd[1], wd[2], wd[3]};
     out[2 * i + 1] = u32x4{wd[4], wd[5], 0u, 0u};
     if (clip != nullptr && clipped) clip[i / (D / 32)] = 1;
+}
+// rows[M][D], norms[M] -> hat[M][D] = fl(rows / norms): the quotients the exact tiers form on every call (div_by: bit for bit this IEEE
+// division on a packed library's operands), stored once per library for knn_rescore_kernel.  One float4 per thread.
+__global__ __launch_bounds__(256) void lib_unit_rows_kernel(const f32x4* __restrict__ rows, const float* __restrict__ norms, int64_t n4,
+                                                            f32x4* __restrict__ hat) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const f32x4 r = rows[i];
+    const float n = norms[i / (D / 4)];
+    hat[i] = f32x4{r[0] / n, r[1] / n, r[2] / n, r[3] / n};
 }
 __device__ __forceinline__ unsigned char to_fp8(float v) {
     return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(v * F8_SCALE, 0.0f, 0, false) & 0xff);
@@ -1661,10 +1677,11 @@ struct PoolRescore {
 };
 enum { PG_VOICE = 0, PG_MSTART, PG_SIZE, PG_BLK0, PG_NBLK, PG_CHUNKS, PG_NSLAB, PG_BASE, PG_FBASE, PG_K, PG_FIELDS };
 
-template <int PER, bool POOL = false>
-__global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_idx,
+template <int PER, bool POOL = false, bool HAT = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HAT && PER < 16 ? 8 : 1))) void knn_rescore_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_idx,
                                                           int P, int kp, const float* __restrict__ s_f32,
                                                           const float* __restrict__ rows, const float* __restrict__ norms,
+                                                          const float* __restrict__ rows_hat,
                                                           int64_t Tt, int64_t idx_base, int k, float* __restrict__ out_val,
                                                           int* __restrict__ out_idx, const int* __restrict__ frame_list,
                                                           const int* __restrict__ gate_cnt, int gate_lo, int gate_hi,
@@ -1883,6 +1900,10 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
     // gather latency per candidate); lanes past the last candidate are not visited
     const unsigned long long have = __builtin_amdgcn_ballot_w64(my_idx >= 0);
     const int hi = have == 0 ? 0 : 64 - (int)__builtin_clzll(have);
+    // HAT: the rows come from rows_hat (alive_library_pack_unit_rows: the quotients below, formed once per library) -- no norm gather,
+    // no division, the same bits in the same fmaf chain
+    // (a template parameter, not a branch: the two loops in one kernel cost both of them a third of their occupancy)
+    const float* table = HAT ? rows_hat : rows;
     for (int c0 = 0; c0 < hi; c0 += 4) {
         int idx[4];
         bool any = false;
@@ -1893,27 +1914,36 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
         }
         if (!any) continue;                              // wave-uniform
         f32x4 r0[4], r1[4], r2[4];
-        float nn[4];
+        [[maybe_unused]] float nn[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int ii = idx[u] >= 0 ? idx[u] : 0;
-            const f32x4* rp = (const f32x4*)(rows + (size_t)ii * D);
+            const f32x4* rp = (const f32x4*)(table + (size_t)ii * D);
             r0[u] = rp[lane];
             r1[u] = rp[lane + 64];
             r2[u] = rp[lane + 128];
-            nn[u] = norms[ii];
+            if constexpr (!HAT) nn[u] = norms[ii];
         }
         float d4[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const NormDiv nd = norm_div(nn[u]);
             float p = 0.0f;
+            if constexpr (HAT) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) p = fmaf(s0[j], div_by(r0[u][j], nd), p);
+                for (int j = 0; j < 4; ++j) p = fmaf(s0[j], r0[u][j], p);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) p = fmaf(s1[j], div_by(r1[u][j], nd), p);
+                for (int j = 0; j < 4; ++j) p = fmaf(s1[j], r1[u][j], p);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) p = fmaf(s2[j], div_by(r2[u][j], nd), p);
+                for (int j = 0; j < 4; ++j) p = fmaf(s2[j], r2[u][j], p);
+            } else {
+                const NormDiv nd = norm_div(nn[u]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) p = fmaf(s0[j], div_by(r0[u][j], nd), p);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) p = fmaf(s1[j], div_by(r1[u][j], nd), p);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) p = fmaf(s2[j], div_by(r2[u][j], nd), p);
+            }
             d4[u] = p;
         }
         const int tot = __builtin_bit_cast(int, wave_sum_frames<4>(d4, lane));     // candidate u's sum in lanes 16 u .. 16 u + 15
@@ -1998,14 +2028,21 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
 }
 
 // PER from the candidate count of a launch: R = P * kp <= 64 PER
-template <typename... A>
-static void rescore_launch(unsigned grid, hipStream_t s, const float* cv, const int* ci, int P, int kp, A... rest) {
+template <bool HAT, typename... A>
+static void rescore_launch_form(unsigned grid, hipStream_t s, const float* cv, const int* ci, int P, int kp, A... rest) {
     const int R = P * kp;
-    if (R <= 64) knn_rescore_kernel<0><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else if (R <= 192) knn_rescore_kernel<3><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else if (R <= 256) knn_rescore_kernel<4><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else if (R <= 512) knn_rescore_kernel<8><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else knn_rescore_kernel<16><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+    if (R <= 64) knn_rescore_kernel<0, false, HAT><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+    else if (R <= 192) knn_rescore_kernel<3, false, HAT><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+    else if (R <= 256) knn_rescore_kernel<4, false, HAT><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+    else if (R <= 512) knn_rescore_kernel<8, false, HAT><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+    else knn_rescore_kernel<16, false, HAT><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
+}
+// rows_hat given: the form that reads the unit rows
+template <typename... A>
+static void rescore_launch(unsigned grid, hipStream_t s, const float* cv, const int* ci, int P, int kp, const float* s_f32, const float* rows,
+                           const float* norms, const float* rows_hat, A... rest) {
+    if (rows_hat != nullptr) rescore_launch_form<true>(grid, s, cv, ci, P, kp, s_f32, rows, norms, rows_hat, rest...);
+    else rescore_launch_form<false>(grid, s, cv, ci, P, kp, s_f32, rows, norms, rows_hat, rest...);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -3058,12 +3095,14 @@ struct SearchWs {
     unsigned char* clip6;                  // fp6 stage: 1 = the frame's fp6 image clipped an element (-> it fails the certificate)
     unsigned char* sub_f6; float* sub_g; unsigned char* sub_flag;   // subspace stage (its workspace only): frame codes [Tp8][512], g_f,
     float* sub_nrm;                                                  // 1 = flagged, |q| of each frame
+    unsigned short* sub_planes; float* sub_y;   // alive_knn_search_unit: the frames as two k-blocked bf16 planes, [U | u]^T src [N][576][T]
     unsigned short* s_c2h; unsigned short* s_c2l;   // split tier (strict search): both planes of the frames that failed the deterministic certificate
     float* c2v; int* c2i;                  // candidate lists of the collect tiers: [slot][split][caps]
     int rows_t, rows_b;                    // rows per frame they may fill: tier-1 launches (<= fcap frames) / bulk launches
     const unsigned short* lib_lo;          // set by the strict search when the library carries its lo plane
     float* tau; int* tau_flag;             // fp8 stage: per-frame admission seeds handed from split to split, and the hand-off flags
     const float* det_q; const float* det_lib;   // set by the strict search only: frame / library share of the deterministic bound
+    const float* rows_hat;                 // set by alive_knn_search_unit: the library's unit rows (knn_rescore_kernel: no division)
     size_t bytes;
 };
 
@@ -3123,6 +3162,7 @@ static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split =
     w.tau_flag = a.take<int>((size_t)(Tp / FT) * (MAX_SPLIT > MAX_SPLIT8 ? MAX_SPLIT : MAX_SPLIT8));
     w.det_q = nullptr;
     w.det_lib = nullptr;
+    w.rows_hat = nullptr;
     // the two frame planes of the split tier (1.5 KB per frame each) exist only in the strict search's workspace
     // (alive_knn_workspace_bytes_strict); they come last, so every other address is the same in both layouts
     w.s_c2h = split ? a.take<unsigned short>((size_t)Tp * D) : nullptr;
@@ -3132,6 +3172,8 @@ static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split =
     w.sub_g = sub ? a.take<float>((size_t)Tp8) : nullptr;
     w.sub_nrm = sub ? a.take<float>((size_t)Tp8) : nullptr;
     w.sub_flag = sub ? a.take<unsigned char>((size_t)Tp8) : nullptr;
+    w.sub_planes = sub ? a.take<unsigned short>(alive_planes_bytes(Tt, D, 2) / 2) : nullptr;
+    w.sub_y = sub ? a.take<float>((size_t)Tt * SUB_C) : nullptr;
     w.bytes = a.used() + 1024;
     return w;
 }
@@ -3616,7 +3658,7 @@ static void collect_tier_launch(const SearchWs& w, const void* lib_bf16, const f
         knn_collect_split_kernel<<<dim3(Tp / FT2, w.p16.split), 256, SPLIT_LDS, s>>>(
             w.s_c2h, w.s_c2l, (const unsigned short*)lib_bf16, w.lib_lo, M, w.p16.tiles_total, w.p16.tiles_per_split, w.p16.P, caps,
             w.c2v, w.c2i, cnt1, COLLECT_MIN, w.thr1);
-        rescore_launch((unsigned)((Tt + 3) / 4), s, w.c2v, w.c2i, w.p16.P, caps, w.s_f32, rows_f32, norms, Tt, idx_base, k,
+        rescore_launch((unsigned)((Tt + 3) / 4), s, w.c2v, w.c2i, w.p16.P, caps, w.s_f32, rows_f32, norms, w.rows_hat, Tt, idx_base, k,
                                                                    out_val, out_idx, w.list1, cnt1, COLLECT_MIN, 0x7fffffff, w.list2, cnt2,
                                                                    CERT_Z, KH, 1.0f, SD_PRIOR16, nullptr, nullptr, nullptr, 1, 0.0f);
         knn_exact_launch(w, rows_f32, norms, M, Tt, idx_base, k, w.list2, cnt2, out_val, out_idx, s);
@@ -3630,7 +3672,7 @@ static void collect_tier_launch(const SearchWs& w, const void* lib_bf16, const f
     knn_score_kernel<true><<<dim3((unsigned)(fcap / FT), w.pt.split), 256, SCORE_LDS, s>>>(
         w.s_c, (const unsigned short*)lib_bf16, M, w.pt.tiles_total, w.pt.tiles_per_split, w.pt.P, w.c2v, w.c2i, cnt1, COLLECT_MIN, fcap, 1,
         w.thr1, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, caps_t);
-    rescore_launch((unsigned)((fcap + 3) / 4), s, w.c2v, w.c2i, w.pt.P, caps_t, w.s_f32, rows_f32, norms, fcap, idx_base, k,
+    rescore_launch((unsigned)((fcap + 3) / 4), s, w.c2v, w.c2i, w.pt.P, caps_t, w.s_f32, rows_f32, norms, w.rows_hat, fcap, idx_base, k,
                                                                  out_val, out_idx, w.list1, cnt1, COLLECT_MIN, fcap, w.list2, cnt2, CERT_Z,
                                                                  KH, 1.0f, SD_PRIOR16, nullptr, nullptr, nullptr, 1, 0.0f);
     if (w.p16.Tt_pad > fcap) {
@@ -3638,7 +3680,7 @@ static void collect_tier_launch(const SearchWs& w, const void* lib_bf16, const f
         knn_score_kernel<true><<<dim3((unsigned)(w.p16.Tt_pad / FT), w.p16.split), 256, SCORE_LDS, s>>>(
             w.s_c, (const unsigned short*)lib_bf16, M, w.p16.tiles_total, w.p16.tiles_per_split, w.p16.P, w.c2v, w.c2i, cnt1, fcap,
             0x7fffffff, 1, w.thr1, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, caps_b);
-        rescore_launch((unsigned)((Tt + 3) / 4), s, w.c2v, w.c2i, w.p16.P, caps_b, w.s_f32, rows_f32, norms, Tt, idx_base, k,
+        rescore_launch((unsigned)((Tt + 3) / 4), s, w.c2v, w.c2i, w.p16.P, caps_b, w.s_f32, rows_f32, norms, w.rows_hat, Tt, idx_base, k,
                                                                    out_val, out_idx, w.list1, cnt1, fcap, 0x7fffffff, w.list2, cnt2,
                                                                    CERT_Z, KH, 1.0f, SD_PRIOR16, nullptr, nullptr, nullptr, 1, 0.0f);
     }
@@ -3665,13 +3707,13 @@ static void bf16_tiers_launch(const SearchWs& w, const void* lib_bf16, const flo
     gather_frames_kernel<<<(unsigned)t1a, 128, 0, s>>>(w.s_bf16, w.list0, cnt0, RESEARCH_MIN, t1a, w.s_c);
     knn_score_kernel<false><<<dim3(1, w.pa.split), 256, SCORE_LDS, s>>>(
         w.s_c, (const unsigned short*)lib_bf16, M, w.pa.tiles_total, w.pa.tiles_per_split, w.pa.P, w.cv1, w.ci1, cnt0, RESEARCH_MIN, t1a, 1, nullptr, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, 0);
-    rescore_launch((unsigned)((t1a + 3) / 4), s, w.cv1, w.ci1, w.pa.P, KP, w.s_f32, rows_f32, norms, t1a, idx_base, k,
+    rescore_launch((unsigned)((t1a + 3) / 4), s, w.cv1, w.ci1, w.pa.P, KP, w.s_f32, rows_f32, norms, w.rows_hat, t1a, idx_base, k,
                                                                 out_val, out_idx, w.list0, cnt0, RESEARCH_MIN, t1a, w.list1, cnt1, CERT_Z, KH, 1.0f, SD_PRIOR16, w.det_q, w.det_lib, w.thr1, 0, w.lib_lo != nullptr ? SPLIT_BOUND : 0.0f);
     if (fcap > t1a) {
     gather_frames_kernel<<<(unsigned)fcap, 128, 0, s>>>(w.s_bf16, w.list0, cnt0, t1a, fcap, w.s_c);
     knn_score_kernel<false><<<dim3((unsigned)(fcap / FT), w.pt.split), 256, SCORE_LDS, s>>>(
         w.s_c, (const unsigned short*)lib_bf16, M, w.pt.tiles_total, w.pt.tiles_per_split, w.pt.P, w.cv1, w.ci1, cnt0, t1a, fcap, 1, nullptr, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, 0);
-    rescore_launch((unsigned)((fcap + 3) / 4), s, w.cv1, w.ci1, w.pt.P, KP, w.s_f32, rows_f32, norms, fcap, idx_base, k,
+    rescore_launch((unsigned)((fcap + 3) / 4), s, w.cv1, w.ci1, w.pt.P, KP, w.s_f32, rows_f32, norms, w.rows_hat, fcap, idx_base, k,
                                                                  out_val, out_idx, w.list0, cnt0, t1a, fcap, w.list1, cnt1, CERT_Z, KH, 1.0f, SD_PRIOR16, w.det_q, w.det_lib, w.thr1, 0, w.lib_lo != nullptr ? SPLIT_BOUND : 0.0f);
     }
     if (w.p16.Tt_pad > fcap) {
@@ -3682,7 +3724,7 @@ static void bf16_tiers_launch(const SearchWs& w, const void* lib_bf16, const flo
         knn_score_kernel<false><<<dim3((unsigned)(w.p16.Tt_pad / FT), w.p16.split), 256, SCORE_LDS, s>>>(
             w.s_c, (const unsigned short*)lib_bf16, M, w.p16.tiles_total, w.p16.tiles_per_split, w.p16.P, w.cv, w.ci, cnt0, fcap,
             0x7fffffff, 1, nullptr, sa, 0);
-        rescore_launch((unsigned)((Tt + 3) / 4), s, w.cv, w.ci, w.p16.P, KP, w.s_f32, rows_f32, norms, Tt, idx_base, k,
+        rescore_launch((unsigned)((Tt + 3) / 4), s, w.cv, w.ci, w.p16.P, KP, w.s_f32, rows_f32, norms, w.rows_hat, Tt, idx_base, k,
                                                                    out_val, out_idx, w.list0, cnt0, fcap, 0x7fffffff, w.list1, cnt1,
                                                                    CERT_Z, KH, 1.0f, SD_PRIOR16, w.det_q, w.det_lib, w.thr1, 0, w.lib_lo != nullptr ? SPLIT_BOUND : 0.0f);
     }
@@ -3695,11 +3737,12 @@ static void bf16_tiers_launch(const SearchWs& w, const void* lib_bf16, const flo
 static int knn_search_impl(const float* src, int N, int T, const void* lib_bf16, const float* rows_f32,
                            const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
                            void* ws, void* stream, hipEvent_t g_ev_start, hipEvent_t g_ev_stop, const float* strict_bound = nullptr,
-                           const void* lib_lo = nullptr) {
+                           const void* lib_lo = nullptr, const float* rows_hat = nullptr) {
     ALIVE_CHECK_ARG(src && lib_bf16 && rows_f32 && norms && out_val && out_idx && ws, "alive_knn_search: null pointer");
     if (int rc = check_search_args("alive_knn_search", src, ws, N, T, k, M)) return rc;
     const int64_t Tt = (int64_t)N * T;
     SearchWs w = ws_layout(ws, Tt, M, k, strict_bound != nullptr && lib_lo != nullptr);
+    w.rows_hat = rows_hat;
     if (strict_bound != nullptr) {         // deterministic certificate: per-frame rounding error + the library's (alive_library_rounding_bound)
         w.det_q = w.dq;
         w.det_lib = strict_bound;
@@ -3724,7 +3767,7 @@ static int knn_search_impl(const float* src, int N, int T, const void* lib_bf16,
     knn_score_kernel<false><<<dim3((unsigned)(p.Tt_pad / FT), p.split), 256, SCORE_LDS, s>>>(
         w.s_bf16, (const unsigned short*)lib_bf16, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, nullptr, 0, 0, 0, nullptr, sa, 0);
     if (g_ev_stop) (void)hipEventRecord(g_ev_stop, s);
-    rescore_launch((unsigned)((Tt + 3) / 4), s, w.cv, w.ci, p.P, KP, w.s_f32, rows_f32, norms, Tt, idx_base, k,
+    rescore_launch((unsigned)((Tt + 3) / 4), s, w.cv, w.ci, p.P, KP, w.s_f32, rows_f32, norms, w.rows_hat, Tt, idx_base, k,
                                                                out_val, out_idx, nullptr, nullptr, 0, 0, w.list1, w.stats + ST_FLAG16,
                                                                CERT_Z, KH, 1.0f, SD_PRIOR16, w.det_q, w.det_lib, w.thr1, 0, w.lib_lo != nullptr ? SPLIT_BOUND : 0.0f);
     collect_tier_launch(w, lib_bf16, rows_f32, norms, M, Tt, idx_base, k, out_val, out_idx, s);
@@ -3789,7 +3832,8 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
                                const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
                                void* ws, void* stream, hipEvent_t g_ev_start, hipEvent_t g_ev_stop, int fmt = 0,
                                const float* y_rot = nullptr, float rot_c0 = 0.0f, const float* y_sub = nullptr,
-                               const void* lib_sub = nullptr, const float* rho = nullptr) {
+                               const void* lib_sub = nullptr, const float* rho = nullptr, const float* rows_hat = nullptr,
+                               bool lazy_plain = false) {
     // y_rot != NULL (fp8 only): lib_f8 holds the ROTATED codes of the rows (alive_library_pack_fp8_rot) and y_rot the frames' rotated
     // coordinates [N][576][T]: the frames' codes come from rot_codes_kernel, the stage's error prior is SD_PRIOR8R; everything else --
     // exact rescoring on the original rows, certificates, the bf16 tiers on lib_bf16 -- is the plain search's
@@ -3798,7 +3842,11 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
     const int64_t Tt = (int64_t)N * T;
     if (k > KH)
         return knn_search_impl(src, N, T, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream, g_ev_start, g_ev_stop);
-    const SearchWs w = ws_layout(ws, Tt, M, k, false, y_sub != nullptr);
+    SearchWs w = ws_layout(ws, Tt, M, k, false, y_sub != nullptr);
+    w.rows_hat = rows_hat;
+    // lazy_plain (alive_knn_search_unit, subspace form): the plain fp6 image of the frames is built only where it is read -- by a due
+    // probe, or by the plain stage when the gate sends the batch there.  clip6 keeps its meaning: cleared first, bytes are only ever set.
+    const bool lazy = lazy_plain && y_sub != nullptr;
     const bool f6 = fmt == 2;
     const SearchPlan& p = f6 ? w.p6 : w.p8;
     const SearchPlan& pp = f6 ? w.pp6 : w.pp;
@@ -3817,7 +3865,9 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
     if (f6) {
         const int64_t n32 = p.Tt_pad * D / 32;
         (void)hipMemsetAsync(w.clip6, 0, (size_t)p.Tt_pad, s);
-        to_fp6_kernel<<<(unsigned)((n32 + 255) / 256), 256, 0, s>>>(w.s_bf16, n32, w.p16.Tt_pad * D / 32, (u32x4*)w.s_f8, w.clip6);
+        if (!lazy || w.probe_n > 0)
+            to_fp6_kernel<<<(unsigned)((n32 + 255) / 256), 256, 0, s>>>(w.s_bf16, n32, w.p16.Tt_pad * D / 32, (u32x4*)w.s_f8, w.clip6, lazy ? 1 : 0,
+                                                                        w.stats + ST_PROBE_GATE);
         if (y_sub != nullptr)
             sub_codes_kernel<<<(unsigned)(p.Tt_pad / 32), 256, 0, s>>>(y_sub, w.sub_nrm, T, Tt, p.Tt_pad, w.sub_f6, w.sub_g, w.sub_flag, w.stats);
     } else if (y_rot != nullptr) {
@@ -3839,13 +3889,18 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
         // the sample's own rescoring.  The kernel writes a frame's result to the frame's own output rows (out[frame]), so
         // the sample's exact lists land in the caller's outputs and are overwritten by the pass over the batch; its flagged
         // frames (second half of p_list) are only counted
-        rescore_launch((unsigned)((w.probe_n + 3) / 4), s, w.cvp, w.cip, pp.P, KP8, w.s_f32, rows_f32, norms, w.probe_n,
+        rescore_launch((unsigned)((w.probe_n + 3) / 4), s, w.cvp, w.cip, pp.P, KP8, w.s_f32, rows_f32, norms, w.rows_hat, w.probe_n,
                                                                           idx_base, k, out_val, out_idx, w.p_list, pgate, GATE_BOOL, 0,
                                                                           w.p_list + probe_pad, w.stats + ST_PROBE_CNT, CERT_Z, KH8,
                                                                           pre, prior, nullptr, nullptr, nullptr, 0, 0.0f, f6 ? w.clip6 : nullptr);
         probe_decide_kernel<<<1, 1, 0, s>>>(w.stats, w.probe_n, PROBE_NUM, PROBE_DEN);
     }
     if (y_sub != nullptr) sub_select_kernel<<<(unsigned)((p.Tt_pad + 255) / 256), 256, 0, s>>>(w.sub_flag, w.clip6, p.Tt_pad, w.stats);
+    if (lazy) {
+        const int64_t n32 = p.Tt_pad * D / 32;
+        to_fp6_kernel<<<(unsigned)((n32 + 255) / 256), 256, 0, s>>>(w.s_bf16, n32, w.p16.Tt_pad * D / 32, (u32x4*)w.s_f8, w.clip6, 2,
+                                                                    w.probe_n > 0 ? w.stats + ST_PROBE_GATE : nullptr, w.stats + ST_SUB_GATE);
+    }
     // ---- mode 0: the fp8 / fp6 stage first ----
     const SeedArgs sa8 = seeds_for(w, p.Tt_pad / ft, p.split, k, f6 ? SEED_MARGIN6 : SEED_MARGIN8, ST_SEEDED, s, f6 ? SEED_MIN_FB6 : SEED_MIN_FB);
     if (g_ev_start) (void)hipEventRecord(g_ev_start, s);             // behind the memset of the seed flags: the events bracket the kernel alone
@@ -3862,7 +3917,7 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
         knn_score8_kernel<<<dim3((unsigned)(p.Tt_pad / ft), p.split), 256, lds, s>>>(
             w.s_f8, (const unsigned char*)lib_f8, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, mode, -1, 0, sa8);
     if (g_ev_stop) (void)hipEventRecord(g_ev_stop, s);
-    rescore_launch((unsigned)((Tt + 3) / 4), s, w.cv, w.ci, p.P, KP8, w.s_f32, rows_f32, norms, Tt, idx_base, k,
+    rescore_launch((unsigned)((Tt + 3) / 4), s, w.cv, w.ci, p.P, KP8, w.s_f32, rows_f32, norms, w.rows_hat, Tt, idx_base, k,
                                                                out_val, out_idx, nullptr, mode, -1, 0, w.list0, w.stats + ST_FLAG8,
                                                                CERT_Z, KH8, pre, prior, nullptr, nullptr, nullptr, 0, 0.0f, f6 ? w.clip6 : nullptr);
     // ---- mode 1: bf16 first (every frame into list0) ----
@@ -3933,6 +3988,65 @@ extern "C" int alive_knn_search_fp6_sub_timed(const float* src, const float* y_s
     return knn_search_fp8_impl(src, N, T, lib_f6, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream,
                                (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 2, nullptr, 0.0f, y_sub, lib_sub, rho);
 }
+// Unit rows of a packed library, once per library: rows_hat[M][768] = fl(rows_f32 / norms), the quotients knn_rescore_kernel, knn_exact_kernel
+// and knn_scan_kernel form on every call (div_by above: the same bits).  3 KB per row beside the rows themselves, which stay: the gather
+// returns the ORIGINAL rows, and fl(fl(x / n) n) != x.
+extern "C" int alive_library_pack_unit_rows(const float* rows_f32, const float* norms, int64_t M, float* rows_hat, void* stream) {
+    ALIVE_CHECK_ARG(rows_f32 && norms && rows_hat, "alive_library_pack_unit_rows: null pointer");
+    ALIVE_CHECK_ARG(M >= 1 && M < (int64_t)1 << 31, "alive_library_pack_unit_rows: M out of range");
+    const int64_t n4 = M * (D / 4);
+    lib_unit_rows_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, (hipStream_t)stream>>>((const f32x4*)rows_f32, norms, n4, (f32x4*)rows_hat);
+    ALIVE_CHECK_LAUNCH("alive_library_pack_unit_rows");
+    return ALIVE_OK;
+}
+
+// Every tiered search above behind one entry, with the library's unit rows: the rescoring passes (main, probe, bf16 tiers, collect tiers)
+// read rows_hat instead of dividing rows_f32 by norms -- the same bits, so every list is bitwise the list of the entry it stands for --
+// and the subspace form builds the frames' plain fp6 image only when a due probe or the plain stage reads it.  rows_hat null: the
+// named entry's own arithmetic.
+extern "C" int alive_knn_search_unit(const AliveKnnSearch* a, void* stream) {
+    ALIVE_CHECK_ARG(a != nullptr, "alive_knn_search_unit: null arguments");
+    hipEvent_t e0 = (hipEvent_t)a->ev_start, e1 = (hipEvent_t)a->ev_stop;
+    switch (a->form) {
+        case ALIVE_KNN_BF16:
+            return knn_search_impl(a->src, a->N, a->T, a->lib_bf16, a->rows_f32, a->norms, a->M, a->idx_base, a->k, a->out_val, a->out_idx, a->ws,
+                                   stream, e0, e1, nullptr, nullptr, a->rows_hat);
+        case ALIVE_KNN_STRICT:
+            ALIVE_CHECK_ARG(a->bound != nullptr, "alive_knn_search_unit: strict form without a bound (alive_library_rounding_bound)");
+            return knn_search_impl(a->src, a->N, a->T, a->lib_bf16, a->rows_f32, a->norms, a->M, a->idx_base, a->k, a->out_val, a->out_idx, a->ws,
+                                   stream, e0, e1, a->bound, a->lib_lo, a->rows_hat);
+        case ALIVE_KNN_FP8:
+        case ALIVE_KNN_FP6:
+            return knn_search_fp8_impl(a->src, a->N, a->T, a->lib_stage, a->lib_bf16, a->rows_f32, a->norms, a->M, a->idx_base, a->k, a->out_val,
+                                       a->out_idx, a->ws, stream, e0, e1, a->form == ALIVE_KNN_FP6 ? 2 : 0, nullptr, 0.0f, nullptr, nullptr,
+                                       nullptr, a->rows_hat);
+        case ALIVE_KNN_FP8_ROT:
+            ALIVE_CHECK_ARG(a->y != nullptr, "alive_knn_search_unit: rotated form without the rotated frames");
+            return knn_search_fp8_impl(a->src, a->N, a->T, a->lib_stage, a->lib_bf16, a->rows_f32, a->norms, a->M, a->idx_base, a->k, a->out_val,
+                                       a->out_idx, a->ws, stream, e0, e1, 0, a->y, a->rot_c0, nullptr, nullptr, nullptr, a->rows_hat);
+        case ALIVE_KNN_FP6_SUB: {
+            ALIVE_CHECK_ARG((a->y || a->sub_w) && a->lib_sub && a->rho, "alive_knn_search_unit: null subspace operand");
+            const float* y = a->y;
+            const int64_t Tt = (int64_t)a->N * a->T;
+            if (y == nullptr && a->src && a->ws && a->N > 0 && a->T > 0 && a->k >= 1 && a->k <= KH && !(Tt * a->k <= 64 && a->M <= SCAN_ROWS_MAX)) {
+                // the frames' change of basis as a plane GEMM (three bf16 MFMAs per product, as alive_conv1d's split form, without its
+                // fp32 loads and in-loop splits): src -> two k-blocked bf16 planes -> [U | u]^T src, both in the subspace workspace
+                ALIVE_CHECK_ARG(Tt * SUB_C < (1ll << 30), "alive_knn_search_unit: %lld frames exceed the plane GEMM's 32-bit offsets (pass y)", (long long)Tt);
+                const SearchWs w = ws_layout(a->ws, Tt, a->M, a->k, false, true);
+                if (int rc = alive_to_planes(a->src, a->N, D, a->T, 2, w.sub_planes, stream)) return rc;
+                AliveGemm g{};
+                g.W = a->sub_w; g.P = w.sub_planes; g.N = a->N; g.T = a->T; g.Ci = D; g.Co = SUB_C; g.planes = 2; g.Y = w.sub_y;
+                if (int rc = alive_gemm_planes(&g, stream)) return rc;
+                y = w.sub_y;
+            }
+            return knn_search_fp8_impl(a->src, a->N, a->T, a->lib_stage, a->lib_bf16, a->rows_f32, a->norms, a->M, a->idx_base, a->k, a->out_val,
+                                       a->out_idx, a->ws, stream, e0, e1, 2, nullptr, 0.0f, y, a->lib_sub, a->rho, a->rows_hat, true);
+        }
+        default:
+            ALIVE_CHECK_ARG(false, "alive_knn_search_unit: form %d", a->form);
+    }
+    return ALIVE_OK;
+}
 extern "C" int alive_knn_sub_coordinates(void) { return SUB_C; }
 extern "C" size_t alive_library_fp6_sub_bytes(int64_t M) { return (size_t)alive_library_padded_rows(M) * SUB_K; }
 // y_rows: [count][576] fp32 coordinates of the unit rows m0 .. m0 + count - 1 (U^T r^ in 0 .. 511, u . r^ in 512); lib_sub: alive_library_fp6_sub_bytes(M),
@@ -3983,6 +4097,7 @@ extern "C" int alive_debug_knn_stage_view(int64_t Tt, int64_t M, int k, int sub,
         out[11 + 4 * i] = plans[i]->P;
     }
     out[20] = KP; out[21] = KP8; out[22] = FT; out[23] = FT6; out[24] = LT;
+    if (n_out >= 27) { out[25] = off(w.sub_planes); out[26] = off(w.sub_y); }
     return ALIVE_OK;
 }
 
@@ -4013,7 +4128,7 @@ static int debug_rescore_check(const char* who, const AliveRescoreArgs* a, bool 
 
 extern "C" int alive_debug_knn_rescore(const AliveRescoreArgs* a, void* stream) {
     if (int rc = debug_rescore_check("alive_debug_knn_rescore", a, false)) return rc;
-    rescore_launch((unsigned)((a->Tt + 3) / 4), (hipStream_t)stream, a->cand_val, a->cand_idx, a->P, a->kp, a->s_f32, a->rows, a->norms, a->Tt,
+    rescore_launch((unsigned)((a->Tt + 3) / 4), (hipStream_t)stream, a->cand_val, a->cand_idx, a->P, a->kp, a->s_f32, a->rows, a->norms, nullptr, a->Tt,
                    a->idx_base, a->k, a->out_val, a->out_idx, a->frame_list, a->gate_cnt, a->gate_lo, a->gate_hi, a->flag_list, a->flag_cnt,
                    a->zsig, a->list_len, a->pre_scale, a->sd_prior, a->det_q, a->det_lib, a->thr_list, a->collect, a->overflow_slack,
                    a->force_fail);
@@ -4269,7 +4384,7 @@ static int search_pool(const char* who, const float* src, int N, int T, const vo
         pb);
     const PoolRescore pr{w.slot_grp, w.grp, w.gfail, w.fb};
     // (the kernel takes each frame's k from its group; the k argument is the stride of the lists)
-    pool_rescore_launch((unsigned)(w.S / 4), s, w.cv, w.ci, w.P, KP, w.s_f32, rows_f32, norms, w.S, 0, k, out_val, out_idx, w.slot_frame,
+    pool_rescore_launch((unsigned)(w.S / 4), s, w.cv, w.ci, w.P, KP, w.s_f32, rows_f32, norms, nullptr, w.S, 0, k, out_val, out_idx, w.slot_frame,
                         nullptr, 0, 0, w.fb, w.stats, CERT_Z, KH, 1.0f, SD_PRIOR16, w.dq, bounds, nullptr, 0, 0.0f, nullptr, pr);
     knn_pool_fallback_plan_kernel<<<1, 64, 0, s>>>(seg_len, w);
     knn_pool_scan_kernel<<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, seg_lo, seg_len, w);
@@ -4303,7 +4418,7 @@ extern "C" int alive_debug_knn_rescore_pool(const AliveRescoreArgs* a, const int
     ALIVE_CHECK_ARG(slot_grp && grp && gfail && fb && groups >= 1, "alive_debug_knn_rescore_pool: null pointer or no group");
     const PoolRescore pr{slot_grp, grp, gfail, fb};
     pool_rescore_launch((unsigned)((a->Tt + 3) / 4), (hipStream_t)stream, a->cand_val, a->cand_idx, a->P, a->kp, a->s_f32, a->rows, a->norms,
-                        a->Tt, a->idx_base, a->k, a->out_val, a->out_idx, a->frame_list, a->gate_cnt, a->gate_lo, a->gate_hi, a->flag_list,
+                        nullptr, a->Tt, a->idx_base, a->k, a->out_val, a->out_idx, a->frame_list, a->gate_cnt, a->gate_lo, a->gate_hi, a->flag_list,
                         a->flag_cnt, a->zsig, a->list_len, a->pre_scale, a->sd_prior, a->det_q, a->det_lib, a->thr_list, a->collect,
                         a->overflow_slack, a->force_fail, pr);
     ALIVE_CHECK_LAUNCH("alive_debug_knn_rescore_pool");

@@ -55,6 +55,19 @@ class AliveRescoreArgs(C.Structure):     # test only (alive_debug_knn_rescore)
     ]
 
 
+class AliveKnnSearch(C.Structure):       # alive_knn_search_unit
+    _fields_ = [
+        ("form", C.c_int), ("N", C.c_int), ("T", C.c_int), ("k", C.c_int),
+        ("src", C.c_void_p), ("lib_stage", C.c_void_p), ("lib_bf16", C.c_void_p), ("lib_lo", C.c_void_p),
+        ("rows_f32", C.c_void_p), ("norms", C.c_void_p), ("rows_hat", C.c_void_p), ("bound", C.c_void_p),
+        ("y", C.c_void_p), ("lib_sub", C.c_void_p), ("rho", C.c_void_p), ("sub_w", C.c_void_p), ("rot_c0", C.c_float),
+        ("M", C.c_int64), ("idx_base", C.c_int64),
+        ("out_val", C.c_void_p), ("out_idx", C.c_void_p), ("ws", C.c_void_p), ("ev_start", C.c_void_p), ("ev_stop", C.c_void_p),
+    ]
+
+
+KNN_BF16, KNN_STRICT, KNN_FP8, KNN_FP6, KNN_FP8_ROT, KNN_FP6_SUB = range(6)       # AliveKnnSearch.form (include/alive_vc.h)
+
 _VP, _I, _I64, _F, _D, _SZ = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); mirrors include/alive_vc.h one to one
@@ -86,6 +99,8 @@ PROTOTYPES = {
     "alive_library_fp6_sub_bytes": (_SZ, [_I64]),
     "alive_library_pack_fp6_sub": (_I, [_VP, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
     "alive_knn_search_fp6_sub_timed": (_I, [_VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "alive_library_pack_unit_rows": (_I, [_VP, _VP, _I64, _VP, _VP]),
+    "alive_knn_search_unit": (_I, [C.POINTER(AliveKnnSearch), _VP]),
     "alive_knn_rot_coordinates": (_I, []),
     "alive_knn_rot_leading": (_I, []),
     "alive_knn_rot_mixed": (_I, []),

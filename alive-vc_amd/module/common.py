@@ -13,6 +13,7 @@ LDS-staged top-k' lists, exact fp32 rescoring, gather-mean-blend.  The library
 is packed (normalised fp6 / fp8 / bf16 rows + fp32 rows + norms) once per reference tensor
 and cached, so the per-window calls of inference.py:129 only pay for the search.
 """
+import ctypes
 import os
 import weakref
 
@@ -55,7 +56,8 @@ class PackedLibrary:
     """Device-resident search form of a voice library tokens[768, M] (one shard).
 
     lib_bf16[M_pad,768] normalised rows (MFMA operand), rows[M,768] fp32 raw rows,
-    norms[M].  `idx_base` is the global index of row 0 when the library is sharded."""
+    norms[M], rows_hat[M,768] = rows / norms (the rescoring passes read the quotients instead of
+    forming them on every call; 3 KB per row).  `idx_base` is the global index of row 0 when the library is sharded."""
 
     def __init__(self, tokens_DxM: torch.Tensor, idx_base: int = 0, prefilter: str = None, strict: bool = None):
         self.strict = _strict() if strict is None else bool(strict)
@@ -83,6 +85,11 @@ class PackedLibrary:
             first = int(torch.nonzero(bad)[0])
             raise ValueError(f"voice library row {first + self.idx_base} has zero or non-finite norm ({int(bad.sum())} such rows): "
                              f"remove them (the reference would match every frame to them through NaN cosines)")
+        # unit rows, once per library (the copies of with_prefilter / with_strict share them); `rows` stays: merge_gather returns the
+        # original rows, and fl(fl(x / n) n) != x
+        self.rows_hat = torch.empty_like(self.rows)
+        nat.check(L.alive_library_pack_unit_rows(nat.ptr(self.rows), nat.ptr(self.norms), self.M, nat.ptr(self.rows_hat), nat.stream()),
+                  "alive_library_pack_unit_rows")
         self.lib_f8 = None                 # the fp8 OR the fp6 image of the rows (same size and tile layout), per self.prefilter
         self.fp6_declined = False
         self.rot = None                    # rotated fp8 stage: {"W": packed 1x1 conv weights of the basis, "spectrum": ...}
@@ -207,7 +214,8 @@ class PackedLibrary:
         if int(clip.item()) != 0:                  # a row coordinate beyond e2m3's range: keep the plain stage (as _fp6_would_clip)
             self.sub = None
             return self
-        self.sub = {"W": pack_conv_split(B.t().contiguous().unsqueeze(2), 2), "co": co, "lib": lib, "rho": rho}
+        # "W": [U | u]^T as two k-blocked bf16 planes -- the weight operand of alive_gemm_planes and of alive_conv1d's split form alike
+        self.sub = {"W": pack_conv_split(B.t().contiguous().unsqueeze(2), 2), "co": co, "lib": lib, "rho": rho, "basis": B}
         return self
 
     def _rotate_frames(self, source, form=None):
@@ -250,31 +258,34 @@ class PackedLibrary:
         sub = self.sub is not None and self.prefilter == "fp6" and not self.strict and self.rot is None
         wsb = L.alive_knn_workspace_bytes_strict if split else (L.alive_knn_workspace_bytes_sub if sub else L.alive_knn_workspace_bytes_fast)
         ws = self._ws.get(wsb(n * t, self.M), source.device)
-        ev = (None, None) if events is None else (events[0].cuda_event, events[1].cuda_event)
+        a = nat.AliveKnnSearch()
+        a.N, a.T, a.k, a.M, a.idx_base = n, t, k, self.M, self.idx_base
+        a.src, a.lib_bf16, a.rows_f32, a.norms = nat.ptr(source), nat.ptr(self.lib_bf16), nat.ptr(self.rows), nat.ptr(self.norms)
+        a.rows_hat = nat.ptr(getattr(self, "rows_hat", None))
+        a.out_val, a.out_idx, a.ws = nat.ptr(val), nat.ptr(idx), nat.ptr(ws)
+        if events is not None:
+            a.ev_start, a.ev_stop = events[0].cuda_event, events[1].cuda_event
         if self.strict:
-            nat.check(L.alive_knn_search_strict(nat.ptr(source), n, t, nat.ptr(self.lib_bf16), nat.ptr(self.lib_lo), nat.ptr(self.rows), nat.ptr(self.norms),
-                                                nat.ptr(self.bound), self.M, self.idx_base, k, nat.ptr(val), nat.ptr(idx),
-                                                nat.ptr(ws), nat.stream(), *ev), "alive_knn_search_strict")
+            a.form, what = nat.KNN_STRICT, "alive_knn_search_strict"
+            a.lib_lo, a.bound = nat.ptr(self.lib_lo), nat.ptr(self.bound)
         elif self.rot is not None:
             y = self._rotate_frames(source)
-            nat.check(L.alive_knn_search_fp8_rot_timed(nat.ptr(source), nat.ptr(y), self.rot["c0"], n, t, nat.ptr(self.lib_f8), nat.ptr(self.lib_bf16),
-                                                       nat.ptr(self.rows), nat.ptr(self.norms), self.M, self.idx_base, k,
-                                                       nat.ptr(val), nat.ptr(idx), nat.ptr(ws), nat.stream(), *ev), "alive_knn_search_fp8_rot")
+            a.form, what = nat.KNN_FP8_ROT, "alive_knn_search_fp8_rot"
+            a.lib_stage, a.y, a.rot_c0 = nat.ptr(self.lib_f8), nat.ptr(y), self.rot["c0"]
         elif sub:
-            y = self._rotate_frames(source, self.sub)
-            nat.check(L.alive_knn_search_fp6_sub_timed(nat.ptr(source), nat.ptr(y), n, t, nat.ptr(self.sub["lib"]), nat.ptr(self.sub["rho"]),
-                                                       nat.ptr(self.lib_f8), nat.ptr(self.lib_bf16), nat.ptr(self.rows), nat.ptr(self.norms),
-                                                       self.M, self.idx_base, k, nat.ptr(val), nat.ptr(idx), nat.ptr(ws), nat.stream(), *ev),
-                      "alive_knn_search_fp6_sub")
+            a.form, what = nat.KNN_FP6_SUB, "alive_knn_search_fp6_sub"
+            a.lib_stage, a.lib_sub, a.rho = nat.ptr(self.lib_f8), nat.ptr(self.sub["lib"]), nat.ptr(self.sub["rho"])
+            if n * t * self.sub["co"] < 1 << 30:       # the search rotates the frames itself (plane GEMM on the form's two-plane weights)
+                a.sub_w = nat.ptr(self.sub["W"])
+            else:                                      # beyond the plane GEMM's 32-bit offsets: the conv, as the rotated fp8 stage
+                y = self._rotate_frames(source, self.sub)
+                a.y = nat.ptr(y)
         elif self.lib_f8 is not None:
-            fn = L.alive_knn_search_fp6_timed if self.prefilter == "fp6" else L.alive_knn_search_fp8_timed
-            nat.check(fn(nat.ptr(source), n, t, nat.ptr(self.lib_f8), nat.ptr(self.lib_bf16),
-                         nat.ptr(self.rows), nat.ptr(self.norms), self.M, self.idx_base, k,
-                         nat.ptr(val), nat.ptr(idx), nat.ptr(ws), nat.stream(), *ev), "alive_knn_search_" + self.prefilter)
+            a.form, what = (nat.KNN_FP6 if self.prefilter == "fp6" else nat.KNN_FP8), "alive_knn_search_" + self.prefilter
+            a.lib_stage = nat.ptr(self.lib_f8)
         else:
-            nat.check(L.alive_knn_search_timed(nat.ptr(source), n, t, nat.ptr(self.lib_bf16), nat.ptr(self.rows),
-                                               nat.ptr(self.norms), self.M, self.idx_base, k, nat.ptr(val), nat.ptr(idx),
-                                               nat.ptr(ws), nat.stream(), *ev), "alive_knn_search")
+            a.form, what = nat.KNN_BF16, "alive_knn_search"
+        nat.check(L.alive_knn_search_unit(ctypes.byref(a), nat.stream()), what)
         self._last = (n, t, k, ws, sub)
         return val, idx
 

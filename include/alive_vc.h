@@ -144,7 +144,9 @@ const int* alive_knn_search_stats(int N, int T, int64_t M, void* ws);
  *                 clip flags, the subspace codes [.][512] and g (-1 without sub), candidate values, candidate indices;  out[7] bytes
  *   out[8 .. 19]  Tt_pad, tiles_total, tiles_per_split, P (library splits) of the bf16, the fp8 and the fp6 / subspace stage
  *   out[20 .. 24] candidates per frame and split (bf16 stage, block-scaled stages), frames per block (256-frame kernels, fp6
- *                 kernels), library rows per tile.  Candidates are [frame][P][candidates per split].  n_out >= 25. */
+ *                 kernels), library rows per tile.  Candidates are [frame][P][candidates per split].  n_out >= 25.
+ *   out[25 .. 26] (n_out >= 27; -1 without sub) byte offsets of alive_knn_search_unit's change of basis: the frames' two k-blocked bf16
+ *                 planes [2][24][cols_pad][32] and y_sub [N][576][T] fp32. */
 int alive_debug_knn_stage_view(int64_t Tt, int64_t M, int k, int sub, int64_t* out, int n_out);
 
 /* TEST ONLY (tests/test_gpu_knn_cert.py): the rescoring kernel that ends every search, launched by the searches' own dispatcher on
@@ -264,6 +266,44 @@ int alive_knn_search_fp6_sub_timed(const float* src, const float* y_sub, int N, 
                                    const void* lib_f6, const void* lib_bf16, const float* rows_f32, const float* norms, int64_t M,
                                    int64_t idx_base, int k, float* out_val, int32_t* out_idx, void* ws, void* stream,
                                    void* ev_start, void* ev_stop);
+
+/* Unit rows, packed once per library: rows_hat[M][768] = fl(rows_f32[r][d] / norms[r]), the quotient every exact tier forms on every
+ * call (IEEE fp32 division).  alive_knn_search_unit is every tiered search above behind one entry -- `form` names the entry it stands
+ * for, the members are that entry's arguments under their names there -- whose rescoring passes read rows_hat instead of dividing:
+ * (val, idx) are bitwise the named entry's.  rows_f32 and norms are still needed (exact scan tiers; the gather returns the original
+ * rows).  rows_hat NULL: the named entry's own arithmetic.  In the ALIVE_KNN_FP6_SUB form the frames' plain fp6 image is built only
+ * when it is read (a due probe, or the device-side gate sending the batch to the plain stage): frames whose plain image clips while
+ * their subspace image does not are no longer forced to the bf16 tier.  Workspace and counters as for the named entry.
+ *   lib_stage: lib_f8 / lib_f6 / lib_f8_rot of the form (unused by BF16 and STRICT); y: y_rot (FP8_ROT) or y_sub (FP6_SUB);
+ *   sub_w (FP6_SUB, with y NULL): [U | u]^T as two-plane weights [2][768 / 32][576][32] (module/_pack.py::pack_conv_split of the
+ *   1x1 conv) -- the search forms y_sub itself: alive_to_planes of src and alive_gemm_planes (2 planes) into the subspace workspace;
+ *   bound / lib_lo: STRICT only; ev_start / ev_stop may be NULL. */
+enum { ALIVE_KNN_BF16 = 0, ALIVE_KNN_STRICT = 1, ALIVE_KNN_FP8 = 2, ALIVE_KNN_FP6 = 3, ALIVE_KNN_FP8_ROT = 4, ALIVE_KNN_FP6_SUB = 5 };
+typedef struct AliveKnnSearch {
+    int form;
+    int N, T, k;
+    const float* src;
+    const void* lib_stage;
+    const void* lib_bf16;
+    const void* lib_lo;
+    const float* rows_f32;
+    const float* norms;
+    const float* rows_hat;
+    const float* bound;
+    const float* y;
+    const void* lib_sub;
+    const float* rho;
+    const void* sub_w;
+    float rot_c0;
+    int64_t M, idx_base;
+    float* out_val;
+    int32_t* out_idx;
+    void* ws;
+    void* ev_start;
+    void* ev_stop;
+} AliveKnnSearch;
+int alive_library_pack_unit_rows(const float* rows_f32, const float* norms, int64_t M, float* rows_hat, void* stream);
+int alive_knn_search_unit(const AliveKnnSearch* a, void* stream);
 
 /* alive_knn_merge_gather: merge n_shards exact top-k lists ([S][Tt][k], e.g.
  * after an RCCL all-gather), pick the global top-k, gather those rows from the
