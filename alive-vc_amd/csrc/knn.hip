@@ -563,8 +563,9 @@ __device__ __forceinline__ bool seeds_look(const SeedArgs& sa, int split) {
 // end of a block (after the barrier behind its last tile): thread = frame; the k-th largest score among the REAL entries of the
 // frame's two half-lists (KH_ entries each, entry-major [KH_][512 lane-columns]) -> tau, then release + flag
 // (WF_ frames per wave, FRAMES_ = 4 WF_ per block: 64 / 256 in the bf16 and the shipped fp8 kernel)
-template <int KH_, int WF_ = 64, int FRAMES_ = 256>
-__device__ __forceinline__ void seeds_publish(const SeedArgs& sa, const float* Lv, const int* Li, int64_t frame0, int split, bool seeded) {
+// (LI: int entries hold a row index, -1 in a seed entry; 16-bit entries -- knn_sub6w_kernel -- a tile offset, 0xFFFF in a seed entry)
+template <int KH_, int WF_ = 64, int FRAMES_ = 256, typename LI = int>
+__device__ __forceinline__ void seeds_publish(const SeedArgs& sa, const float* Lv, const LI* Li, int64_t frame0, int split, bool seeded) {
     constexpr int LW_ = 4 * 2 * WF_;
     for (int col = threadIdx.x; col < FRAMES_; col += 256) {
         const int lcb = (col / WF_) * (2 * WF_) + ((col % WF_) >> 5) * 64 + (col & 31);
@@ -574,7 +575,9 @@ __device__ __forceinline__ void seeds_publish(const SeedArgs& sa, const float* L
             for (int e = 0; e < 2 * KH_; ++e) {
                 const int o = (e % KH_) * LW_ + lcb + (e / KH_) * 32;
                 const float v = Lv[o];
-                if (Li[o] >= 0 && v < prev) m = fmaxf(m, v);
+                bool real;
+                if constexpr (sizeof(LI) == 2) real = Li[o] != (LI)0xFFFF; else real = Li[o] >= 0;
+                if (real && v < prev) m = fmaxf(m, v);
             }
             prev = m;
         }
@@ -1101,6 +1104,10 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* Lv = (float*)(smem + 2 * ABUF_);
     int* Li = (int*)(Lv + FT8 * KP8);          // both entry-major: [KH8][LW8 lane-columns]
+    // WIDE (four column tiles, knn_sub6w_kernel): 16-bit entries in Li's place, tile - tile_begin of the admitted row (0xFFFF: a seed
+    // entry); the row inside the tile is in the score's low mantissa bits (fold_rare) and the half-list, see the write-out
+    constexpr bool WIDE = NCT8 == 4;
+    unsigned short* Lt = (unsigned short*)(Lv + FT8 * KP8);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1125,7 +1132,11 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
 #pragma unroll
     for (int ni = 0; ni < NCT8; ++ni)
 #pragma unroll
-        for (int q = 0; q < KH8; ++q) { Lv[q * LW8 + w * (2 * WF8) + ni * 64 + lane] = seed[ni]; Li[q * LW8 + w * (2 * WF8) + ni * 64 + lane] = -1; }
+        for (int q = 0; q < KH8; ++q) {
+            Lv[q * LW8 + w * (2 * WF8) + ni * 64 + lane] = seed[ni];
+            if constexpr (WIDE) Lt[q * LW8 + w * (2 * WF8) + ni * 64 + lane] = 0xFFFFu;
+            else Li[q * LW8 + w * (2 * WF8) + ni * 64 + lane] = -1;
+        }
 
     // DMA: wave w copies rows 8 w .. 8 w + 7 of the tile, 6 pieces of 8 rows x 128 B; chunk order swizzled on the source
     const int dma_row = 8 * w + (lane >> 3);
@@ -1141,6 +1152,7 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
 
     // stationary B fragments: frame = frame0 + 64 w + 32 ni + lr, features 64 ks + 32 lh .. + 31 (32 bytes)
     v8i bq[NCT8][NK];
+    constexpr int WIDE_AGPR_NI = 2;
 #pragma unroll
     for (int ni = 0; ni < NCT8; ++ni) {
         const unsigned char* fp = s_f8 + (size_t)(frame0 + WF8 * w + 32 * ni + lr) * KD + 32 * lh;
@@ -1149,7 +1161,16 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             if constexpr (FMT == 2) {           // 24 of the 32 bytes carry the 32 six-bit codes: no 8-register temporaries
                 const u32x4 lo = *(const u32x4*)(fp + 64 * ks);
                 const uint2 hi = *(const uint2*)(fp + 64 * ks + 16);
-                bq[ni][ks] = v8i{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi.x, (int)hi.y, 0, 0};
+                if constexpr (NCT8 == 4) {
+                    // the wide form: column tiles WIDE_AGPR_NI .. 3 keep their fragments in AGPRs (an MFMA reads its B operand from
+                    // either file), beside the 128 accumulator registers, so that the VALU side of the fold has VGPRs to work in
+                    typedef int v6i __attribute__((ext_vector_type(6)));
+                    v6i t = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi.x, (int)hi.y};
+                    if (ni >= WIDE_AGPR_NI) asm volatile("" : "+a"(t));
+                    bq[ni][ks] = v8i{t[0], t[1], t[2], t[3], t[4], t[5], 0, 0};
+                } else {
+                    bq[ni][ks] = v8i{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi.x, (int)hi.y, 0, 0};
+                }
             } else {
                 const u32x4 lo = *(const u32x4*)(fp + 64 * ks), hi = *(const u32x4*)(fp + 64 * ks + 16);
                 bq[ni][ks] = v8i{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
@@ -1259,7 +1280,8 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             const int tq = tpos >> 2;                            // its quarter
             if (has) {
                 lv[tpos * LW8] = mx;
-                li[tpos * LW8] = (int)(row0 + ((__float_as_uint(mx) & 3u) + 8u * ((__float_as_uint(mx) >> 2) & 3u)) + 4 * lh);
+                if constexpr (WIDE) Lt[lc0 + ni * 64 + tpos * LW8] = (unsigned short)(tile - tile_begin);
+                else li[tpos * LW8] = (int)(row0 + ((__float_as_uint(mx) & 3u) + 8u * ((__float_as_uint(mx) >> 2) & 3u)) + 4 * lh);
             }
             // rescan that quarter (after the write: LDS operations of a wave complete in order)
             const float* qb = lv + (tq * 4) * LW8;
@@ -1325,7 +1347,8 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         if (has) {
             const unsigned u = __float_as_uint(m1);
             lv[tpos * LW8] = m1;
-            li[tpos * LW8] = (int)(row0 + ((u & 3u) + 8u * ((u >> 2) & 3u)) + 4 * lh);
+            if constexpr (WIDE) Lt[lc0 + ni * 64 + tpos * LW8] = (unsigned short)(tile - tile_begin);
+            else li[tpos * LW8] = (int)(row0 + ((u & 3u) + 8u * ((u >> 2) & 3u)) + 4 * lh);
         }
         // the quarter as it stands after the write: the new entry in place of the old minimum
         x0 = (has && te == 0) ? m1 : x0;
@@ -1453,6 +1476,107 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             fold_now3(B0, B1, B2, tile_end - 1, RB);
         }
     }
+    } else if constexpr (NCT8 == 4) {
+    // Four column tiles per wave (knn_sub6w_kernel, the subspace stage only: 4 x 8 x 6 = 192 stationary registers): one A fragment,
+    // one DMA piece and the block barrier feed four MFMAs instead of three, and dependent MFMAs sit four issues apart.  32 MFMAs per
+    // tile into (c0 .. c3); the 4 DMA pieces ride in the first gap of steps 0 .. 3, the previous tile's fold (the five pieces per column
+    // tile of the three-tile form, 20 in all) takes the gaps without a DMA piece from step 0 on; rho rides one tile ahead as there.
+    static_assert(NK == 8 && FMT == 2, "the four-tile form exists for the subspace stage");
+    auto do_tile4 = [&](int tile, f32x16& c0, f32x16& c1, f32x16& c2, f32x16& c3, f32x16& p0, f32x16& p1, f32x16& p2, f32x16& p3,
+                        float* rv, float* rn) {
+        const int buf = (tile - tile_begin) & 1;
+        const int next_tile = tile + 1 < tile_end ? tile + 1 : tile;
+        const unsigned char* gnext = lib + ((size_t)next_tile * LT + dma_row) * KD + dma_chunk * 16;
+        unsigned char* lnext = smem + (buf ^ 1) * ABUF_ + w * PIECE;
+        const unsigned char* Ab = smem + buf * ABUF_;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; c2[r] = 0.0f; c3[r] = 0.0f; }
+        load_rho(tile, rn);
+        v8i a[2];
+        a[0] = load_a(Ab, 0);
+        float pm0 = -INFINITY, pm1 = -INFINITY, pm2 = -INFINITY, pm3 = -INFINITY;
+        ALIVE_CHAIN_GAP(7);
+#define K8_STEP4(ks, AFTER0, AFTER1, AFTER2, AFTER3)                                                                             \
+        {                                                                                                                        \
+            __builtin_amdgcn_sched_barrier(0);                                                                                   \
+            c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[(ks) & 1], bq[0][ks], c0, FMT, FMT, 0, 127, 0, 127);          \
+            __builtin_amdgcn_sched_barrier(0);                                                                                   \
+            if ((ks) + 1 < NK) a[((ks) + 1) & 1] = load_a(Ab, (ks) + 1);                                                         \
+            if ((ks) < NSEG)                                                                                                     \
+                __builtin_amdgcn_global_load_lds((gptr_t)(gnext + (ks) * 128), (lptr_t)(lnext + (ks) * 4 * PIECE), 16, 0, 0);    \
+            AFTER0;                                                                                                              \
+            __builtin_amdgcn_sched_barrier(0);                                                                                   \
+            c1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[(ks) & 1], bq[1][ks], c1, FMT, FMT, 0, 127, 0, 127);          \
+            __builtin_amdgcn_sched_barrier(0);                                                                                   \
+            AFTER1;                                                                                                              \
+            __builtin_amdgcn_sched_barrier(0);                                                                                   \
+            c2 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[(ks) & 1], bq[2][ks], c2, FMT, FMT, 0, 127, 0, 127);          \
+            __builtin_amdgcn_sched_barrier(0);                                                                                   \
+            AFTER2;                                                                                                              \
+            __builtin_amdgcn_sched_barrier(0);                                                                                   \
+            c3 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[(ks) & 1], bq[3][ks], c3, FMT, FMT, 0, 127, 0, 127);          \
+            __builtin_amdgcn_sched_barrier(0);                                                                                   \
+            AFTER3;                                                                                                              \
+        }
+        f32x16 v0, v1, v2, v3;
+        auto acc_read = [&](const f32x16& a_, int lo, int hi, f32x16& v) {
+#pragma unroll
+            for (int r = lo; r < hi; ++r) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v[r]) : "a"(a_[r]));
+        };
+        auto acc_pin = [&]() { asm volatile("" : "+a"(c0), "+a"(c1), "+a"(c2), "+a"(c3)); };
+        auto acc_pin2 = [&]() { asm volatile("" : "+a"(c0), "+a"(c1)); };
+        auto acc_pin3 = [&]() { asm volatile("" : "+a"(c0), "+a"(c1), "+a"(c2)); };
+        // (each column tile's copy is folded before the next one is read: one 16-register copy live at a time)
+        // (step 0 pins only the chains that have begun: naming c2 / c3 before their first MFMA, which takes C = 0, would make hipcc write
+        // 32 zeros into them)
+        K8_STEP4(0, (void)0, (acc_pin2(), acc_read(p0, 0, 8, v0)), (acc_pin3(), acc_read(p0, 8, 16, v0), mask_ragged(v0, tile - 1)),
+                 (acc_pin(), pm0 = max8g(v0, 0, pm0, 0, rv)))
+        K8_STEP4(1, (void)0, pm0 = max8g(v0, 8, pm0, 0, rv), fold_rare(v0, 0, tile - 1, pm0), (acc_pin(), acc_read(p1, 0, 8, v1)))
+        K8_STEP4(2, (void)0, (acc_pin(), acc_read(p1, 8, 16, v1), mask_ragged(v1, tile - 1)), (acc_pin(), pm1 = max8g(v1, 0, pm1, 1, rv)),
+                 pm1 = max8g(v1, 8, pm1, 1, rv))
+        K8_STEP4(3, (void)0, fold_rare(v1, 1, tile - 1, pm1), (acc_pin(), acc_read(p2, 0, 8, v2)),
+                 (acc_pin(), acc_read(p2, 8, 16, v2), mask_ragged(v2, tile - 1)))
+        K8_STEP4(4, (acc_pin(), pm2 = max8g(v2, 0, pm2, 2, rv)), pm2 = max8g(v2, 8, pm2, 2, rv), fold_rare(v2, 2, tile - 1, pm2),
+                 (acc_pin(), acc_read(p3, 0, 8, v3)))
+        K8_STEP4(5, (acc_pin(), acc_read(p3, 8, 16, v3), mask_ragged(v3, tile - 1)), (acc_pin(), pm3 = max8g(v3, 0, pm3, 3, rv)),
+                 pm3 = max8g(v3, 8, pm3, 3, rv), fold_rare(v3, 3, tile - 1, pm3))
+        K8_STEP4(6, (void)0, (void)0, (void)0, (void)0)
+        K8_STEP4(7, (void)0, (void)0, (void)0, (void)0)
+#undef K8_STEP4
+        acc_pin();
+        __syncthreads();
+    };
+    auto fold_now4 = [&](f32x16& p0, f32x16& p1, f32x16& p2, f32x16& p3, int tile, float* rv) {
+        mask_ragged(p0, tile);
+        mask_ragged(p1, tile);
+        mask_ragged(p2, tile);
+        mask_ragged(p3, tile);
+        (void)max8g(p0, 0, max8g(p0, 8, -INFINITY, 0, rv), 0, rv);
+        (void)max8g(p1, 0, max8g(p1, 8, -INFINITY, 1, rv), 1, rv);
+        (void)max8g(p2, 0, max8g(p2, 8, -INFINITY, 2, rv), 2, rv);
+        (void)max8g(p3, 0, max8g(p3, 8, -INFINITY, 3, rv), 3, rv);
+        fold_rare(p0, 0, tile, max8(p0, 8, max8(p0, 0, -INFINITY)));
+        fold_rare(p1, 1, tile, max8(p1, 8, max8(p1, 0, -INFINITY)));
+        fold_rare(p2, 2, tile, max8(p2, 8, max8(p2, 0, -INFINITY)));
+        fold_rare(p3, 3, tile, max8(p3, 8, max8(p3, 0, -INFINITY)));
+    };
+    {
+        f32x16 A0, A1, A2, A3, B0, B1, B2, B3;
+        float RA[16], RB[16];                  // rho of the tiles in A / B
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { B0[r] = -INFINITY; B1[r] = -INFINITY; B2[r] = -INFINITY; B3[r] = -INFINITY; RA[r] = 0.0f; RB[r] = 0.0f; }
+        int tile = tile_begin;
+        for (; tile + 1 < tile_end; tile += 2) {
+            do_tile4(tile, A0, A1, A2, A3, B0, B1, B2, B3, RB, RA);
+            do_tile4(tile + 1, B0, B1, B2, B3, A0, A1, A2, A3, RA, RB);
+        }
+        if (tile < tile_end) {
+            do_tile4(tile, A0, A1, A2, A3, B0, B1, B2, B3, RB, RA);
+            fold_now4(A0, A1, A2, A3, tile, RA);
+        } else if (tile_begin < tile_end) {
+            fold_now4(B0, B1, B2, B3, tile_end - 1, RB);
+        }
+    }
     } else {
     auto do_tile = [&](int tile, f32x16& c0, f32x16& c1, f32x16& p0, f32x16& p1) {
         const int buf = (tile - tile_begin) & 1;
@@ -1553,9 +1677,18 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         const int lc = (col / WF8) * (2 * WF8) + ((col % WF8) >> 5) * 64 + (k / KH8) * 32 + (col & 31);
         const size_t o = (((size_t)(frame0 + col)) * P + split) * KP8 + k;
         cand_val[o] = Lv[(k % KH8) * LW8 + lc];
-        cand_idx[o] = Li[(k % KH8) * LW8 + lc];
+        if constexpr (WIDE) {
+            const unsigned t = Lt[(k % KH8) * LW8 + lc], u = __float_as_uint(Lv[(k % KH8) * LW8 + lc]);
+            cand_idx[o] = t == 0xFFFFu ? -1 : (int)((tile_begin + (int)t) * LT + (u & 3u) + 8u * ((u >> 2) & 3u) + 4 * (k / KH8));
+        } else {
+            cand_idx[o] = Li[(k % KH8) * LW8 + lc];
+        }
     }
-    if (sa.tau != nullptr) seeds_publish<KH8, WF8, FT8>(sa, Lv, Li, frame0, split, seeded);
+    if constexpr (WIDE) {
+        if (sa.tau != nullptr) seeds_publish<KH8, WF8, FT8>(sa, Lv, Lt, frame0, split, seeded);
+    } else {
+        if (sa.tau != nullptr) seeds_publish<KH8, WF8, FT8>(sa, Lv, Li, frame0, split, seeded);
+    }
 }
 
 // two entry points of the same body, so that a kernel trace tells the pass over the batch from the 1 024-frame probe
@@ -1596,6 +1729,21 @@ __global__ __launch_bounds__(256, 1) void knn_sub6_kernel(const unsigned char* _
                                                           float* __restrict__ cand_val, int* __restrict__ cand_idx,
                                                           const int* __restrict__ gate_cnt, int gate_lo, int gate_hi, SeedArgs sa) {
     knn_score8_body<2, 3, NK_SUB>(s_sub, lib_sub, M, tiles_total, tiles_per_split, P, cand_val, cand_idx, gate_cnt, gate_lo, gate_hi, sa,
+                                  rho, gq);
+}
+// The wide form of the same stage: four column tiles per wave, 512 frames per block.  Its lists hold 6 bytes per entry (fp32 score +
+// 16-bit tile offset, knn_score8_body WIDE), so the LDS total is SUB6_LDS again: 2 x 18 432 + 512 x 32 x 6.  The host takes it only
+// when a split has at most SUB6W_MAX_TILES tiles (alive_knn_sub_frames).
+constexpr int FT6W = 4 * 32 * 4;                                 // frames per block
+constexpr int SUB6W_LDS = 2 * 4 * (SUB_K / 128) * PIECE + FT6W * KP8 * 6;
+constexpr int SUB6W_MAX_TILES = 65535;                           // 0xFFFF marks a seed entry
+static_assert(SUB6W_LDS == SUB6_LDS && SUB6W_LDS <= 163840, "the wide subspace kernel's LDS");
+__global__ __launch_bounds__(256, 1) void knn_sub6w_kernel(const unsigned char* __restrict__ s_sub, const unsigned char* __restrict__ lib_sub,
+                                                           const float* __restrict__ rho, const float* __restrict__ gq,
+                                                           int64_t M, int tiles_total, int tiles_per_split, int P,
+                                                           float* __restrict__ cand_val, int* __restrict__ cand_idx,
+                                                           const int* __restrict__ gate_cnt, int gate_lo, int gate_hi, SeedArgs sa) {
+    knn_score8_body<2, 4, NK_SUB>(s_sub, lib_sub, M, tiles_total, tiles_per_split, P, cand_val, cand_idx, gate_cnt, gate_lo, gate_hi, sa,
                                   rho, gq);
 }
 
@@ -2826,6 +2974,7 @@ enum { ST_FLAG8 = 0, ST_FLAG16 = 1, ST_PROBE_N = 2, ST_PROBE_FAIL = 3, ST_MODE =
        // subspace stage (alive_knn_search_fp6_sub): frames flagged by sub_codes_kernel (out of the subspace or clipped) / of them clipped;
        // ST_SUB_FORM (written by every subspace search): 1 = the subspace kernel ran, 2 = the plain fp6 kernel (too many flagged frames)
        ST_SUB_FLAG = 14, ST_SUB_CLIP = 15, ST_SUB_FORM = 20, ST_SUB_GATE = 21,
+       ST_SUB_FRAMES = 22,    // frames per block of the subspace kernel this search launched: 384 (knn_sub6_kernel) or 512 (knn_sub6w_kernel)
        // Probe history (round 6), kept in the CALLER'S workspace across calls and never reset by a search: the probe costs 1.8 ms per
        // 172 800-frame search and says the same thing every time a library is searched with frames of one kind.  After two consecutive
        // searches on this workspace (same library size, same frame count: ST_HIST_TAG) in which the probe chose the low-precision stage
@@ -2928,12 +3077,13 @@ __global__ __launch_bounds__(256) void sub_codes_kernel(const float* __restrict_
 // after the probe (ST_MODE final): the gate word of the two fp6 kernels -- 0 none (bf16 first), 1 the subspace kernel, 2 the plain one
 // (more than RESEARCH_MIN flagged frames) -- and, for the subspace kernel, its flagged frames join the forced failures
 __global__ __launch_bounds__(256) void sub_select_kernel(const unsigned char* __restrict__ flag, unsigned char* __restrict__ clip6,
-                                                         int64_t n, int* __restrict__ stats) {
+                                                         int64_t n, int* __restrict__ stats, int stage_frames) {
     const bool sub = stats[ST_SUB_FLAG] <= RESEARCH_MIN;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (sub && i < n && flag[i] != 0) clip6[i] = 1;
     if (i == 0) {
         stats[ST_SUB_FORM] = sub ? 1 : 2;
+        stats[ST_SUB_FRAMES] = stage_frames;
         stats[ST_SUB_GATE] = stats[ST_MODE] != 0 ? 0 : (sub ? 1 : 2);
     }
 }
@@ -3081,6 +3231,7 @@ static SeedArgs seeds_for(const struct SearchWs& w, int64_t fb, int split, int k
 struct SearchWs {
     SearchPlan p16, p8, pt, pp;            // bf16 main / fp8 main / tier-1 re-search / probe
     SearchPlan p6, pp6;                    // fp6 main / probe (384-frame blocks)
+    SearchPlan p6w;                        // the wide subspace kernel (512-frame blocks)
     SearchPlan pa;                         // tier 1a of the bf16 re-search: ONE frame block, as many library splits as the rescoring takes
     int fcap, probe_n, probe_pad, probe_pad6;
     float* s_f32; unsigned short* s_bf16; unsigned char* s_f8;
@@ -3111,8 +3262,10 @@ static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split =
     w.p16 = make_plan(Tt, M);
     w.p8 = make_plan(Tt, M, MAX_SPLIT8);
     w.p6 = make_plan(Tt, M, MAX_SPLIT8, FT6);
+    w.p6w = make_plan(Tt, M, MAX_SPLIT8, FT6W);
     const int64_t Tp = w.p16.Tt_pad;
-    const int64_t Tp8 = w.p6.Tt_pad > Tp ? w.p6.Tt_pad : Tp;      // (the fp6 stage pads the frames to blocks of 384)
+    // (the fp6 stage pads the frames to blocks of 384, the wide subspace kernel to blocks of 512)
+    const int64_t Tp8 = std::max(std::max(w.p6.Tt_pad, w.p6w.Tt_pad), Tp);
     w.fcap = Tp < FCAP ? (int)Tp : FCAP;
     w.pt = make_plan(w.fcap < FPLAN ? w.fcap : FPLAN, M);
     w.pa = make_plan(FT, M);
@@ -3126,7 +3279,8 @@ static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split =
     w.s_f32 = a.take<float>((size_t)Tt * D);
     w.s_bf16 = a.take<unsigned short>((size_t)Tp * D);
     w.s_f8 = a.take<unsigned char>((size_t)Tp8 * D);
-    const size_t c8a = (size_t)Tp * w.p8.P * KP8, c8b = (size_t)w.p6.Tt_pad * w.p6.P * KP8;
+    // (the plain fp6 kernel may run on the wide plan's splits: the subspace search's device-side fall-back)
+    const size_t c8a = (size_t)Tp * w.p8.P * KP8, c8b = (size_t)Tp8 * std::max(w.p6.P, w.p6w.P) * KP8;
     const size_t c16 = (size_t)Tp * w.p16.P * KP, c8 = c8a > c8b ? c8a : c8b;
     w.cv = a.take<float>(c16 > c8 ? c16 : c8);
     w.ci = a.take<int>(c16 > c8 ? c16 : c8);
@@ -3159,7 +3313,7 @@ static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split =
     w.rows_b = (int)(c2n / (size_t)Tp < 1024 ? c2n / (size_t)Tp : 1024);
     w.lib_lo = nullptr;
     w.tau = a.take<float>((size_t)Tp8);
-    w.tau_flag = a.take<int>((size_t)(Tp / FT) * (MAX_SPLIT > MAX_SPLIT8 ? MAX_SPLIT : MAX_SPLIT8));
+    w.tau_flag = a.take<int>((size_t)(Tp8 / FT) * (MAX_SPLIT > MAX_SPLIT8 ? MAX_SPLIT : MAX_SPLIT8));
     w.det_q = nullptr;
     w.det_lib = nullptr;
     w.rows_hat = nullptr;
@@ -3581,13 +3735,36 @@ static int check_search_args(const char* what, const void* a, const void* b, int
     return ALIVE_OK;
 }
 
+// Which subspace kernel a search launches (alive_knn_sub_frames): 0 = by the rule below, 384 = always knn_sub6_kernel, 512 = knn_sub6w_kernel
+// whenever its 16-bit tile offsets can hold a split.  The rule reads the frame count and M only (through the 512-frame plan): the wide
+// form runs when that plan has at least SEED_MIN_FB6 frame blocks, so that seeded admission stays on.
+static int g_sub_frames = -1;             // -1: not decided yet (environment ALIVE_KNN_SUB_FRAMES = 384 / 512, else 0)
+static int sub_frames_mode() {
+    if (g_sub_frames < 0) {
+        const char* e = getenv("ALIVE_KNN_SUB_FRAMES");
+        const int v = e != nullptr ? atoi(e) : 0;
+        g_sub_frames = v == FT6 || v == FT6W ? v : 0;
+    }
+    return g_sub_frames;
+}
+extern "C" int alive_knn_sub_frames(int mode) {
+    if (mode == FT6 || mode == FT6W) g_sub_frames = mode;
+    else if (mode < 0) g_sub_frames = 0;
+    return sub_frames_mode();
+}
+static bool sub_wide(const SearchPlan& pw) {
+    const int mode = sub_frames_mode();
+    if (mode == FT6 || pw.tiles_per_split > SUB6W_MAX_TILES) return false;
+    return mode == FT6W || pw.Tt_pad / FT6W >= SEED_MIN_FB6;
+}
+
 static int lds_optin(const char* what) {
     static LdsOptIn optin8, optin6, optin16, optin_split, optin_sub;
     hipError_t e = optin8.ensure({(const void*)knn_score8_kernel, (const void*)knn_probe8_kernel}, SCORE8_LDS);
     if (e == hipSuccess) e = optin6.ensure({(const void*)knn_score6_kernel, (const void*)knn_probe6_kernel}, SCORE6_LDS);
     if (e == hipSuccess) e = optin16.ensure({(const void*)knn_score_kernel<false>, (const void*)knn_score_kernel<true>}, SCORE_LDS);
     if (e == hipSuccess) e = optin_split.ensure({(const void*)knn_collect_split_kernel}, SPLIT_LDS);
-    if (e == hipSuccess) e = optin_sub.ensure({(const void*)knn_sub6_kernel}, SUB6_LDS);
+    if (e == hipSuccess) e = optin_sub.ensure({(const void*)knn_sub6_kernel, (const void*)knn_sub6w_kernel}, SUB6_LDS);
     if (e != hipSuccess) {
         alive_set_error("%s: cannot reserve %d B of LDS: %s", what, SCORE_LDS, hipGetErrorString(e));
         return ALIVE_ERR_LAUNCH;
@@ -3848,8 +4025,13 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
     // probe, or by the plain stage when the gate sends the batch there.  clip6 keeps its meaning: cleared first, bytes are only ever set.
     const bool lazy = lazy_plain && y_sub != nullptr;
     const bool f6 = fmt == 2;
-    const SearchPlan& p = f6 ? w.p6 : w.p8;
+    // wide: the subspace kernel runs in its 512-frame form, on the 512-frame plan -- and so does, on the same library splits, the plain
+    // fp6 kernel behind the same gate word (384-frame blocks over the frames padded to 512: both write cand[frame][P][KP8])
+    const bool wide = f6 && y_sub != nullptr && sub_wide(w.p6w);
+    const SearchPlan& p = f6 ? (wide ? w.p6w : w.p6) : w.p8;
     const SearchPlan& pp = f6 ? w.pp6 : w.pp;
+    // frames the operand kernels cover: the plan's blocks -- of both block sizes when the wide form may hand over to the plain kernel
+    const int64_t Tpad = wide ? std::max(w.p6.Tt_pad, w.p6w.Tt_pad) : p.Tt_pad;
     const int ft = f6 ? FT6 : FT, probe_pad = f6 ? w.probe_pad6 : w.probe_pad, lds = f6 ? SCORE6_LDS : SCORE8_LDS;
     const float pre = f6 ? 1.0f / (F6_SCALE * F6_SCALE) : 1.0f / (F8_SCALE * F8_SCALE),
                 prior = f6 ? SD_PRIOR6 : (y_rot != nullptr ? SD_PRIOR8R : SD_PRIOR8);
@@ -3863,13 +4045,13 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
     stats_init_kernel<<<1, 64, 0, s>>>(w.stats, f6 ? TIER_FP6 : TIER_FP8, w.probe_n > 0 ? hist_tag : 0);
     src_prep_launch(w, src, T, Tt, s);
     if (f6) {
-        const int64_t n32 = p.Tt_pad * D / 32;
-        (void)hipMemsetAsync(w.clip6, 0, (size_t)p.Tt_pad, s);
+        const int64_t n32 = Tpad * D / 32;
+        (void)hipMemsetAsync(w.clip6, 0, (size_t)Tpad, s);
         if (!lazy || w.probe_n > 0)
             to_fp6_kernel<<<(unsigned)((n32 + 255) / 256), 256, 0, s>>>(w.s_bf16, n32, w.p16.Tt_pad * D / 32, (u32x4*)w.s_f8, w.clip6, lazy ? 1 : 0,
                                                                         w.stats + ST_PROBE_GATE);
         if (y_sub != nullptr)
-            sub_codes_kernel<<<(unsigned)(p.Tt_pad / 32), 256, 0, s>>>(y_sub, w.sub_nrm, T, Tt, p.Tt_pad, w.sub_f6, w.sub_g, w.sub_flag, w.stats);
+            sub_codes_kernel<<<(unsigned)(Tpad / 32), 256, 0, s>>>(y_sub, w.sub_nrm, T, Tt, Tpad, w.sub_f6, w.sub_g, w.sub_flag, w.stats);
     } else if (y_rot != nullptr) {
         rot_codes_kernel<<<(unsigned)(p.Tt_pad / 32), 256, 0, s>>>(y_rot, Tt, p.Tt_pad, T, 1, rot_c0, w.s_f8);
     } else {
@@ -3895,20 +4077,28 @@ static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f
                                                                           pre, prior, nullptr, nullptr, nullptr, 0, 0.0f, f6 ? w.clip6 : nullptr);
         probe_decide_kernel<<<1, 1, 0, s>>>(w.stats, w.probe_n, PROBE_NUM, PROBE_DEN);
     }
-    if (y_sub != nullptr) sub_select_kernel<<<(unsigned)((p.Tt_pad + 255) / 256), 256, 0, s>>>(w.sub_flag, w.clip6, p.Tt_pad, w.stats);
+    if (y_sub != nullptr)
+        sub_select_kernel<<<(unsigned)((Tpad + 255) / 256), 256, 0, s>>>(w.sub_flag, w.clip6, Tpad, w.stats, wide ? FT6W : FT6);
     if (lazy) {
-        const int64_t n32 = p.Tt_pad * D / 32;
+        const int64_t n32 = Tpad * D / 32;
         to_fp6_kernel<<<(unsigned)((n32 + 255) / 256), 256, 0, s>>>(w.s_bf16, n32, w.p16.Tt_pad * D / 32, (u32x4*)w.s_f8, w.clip6, 2,
                                                                     w.probe_n > 0 ? w.stats + ST_PROBE_GATE : nullptr, w.stats + ST_SUB_GATE);
     }
     // ---- mode 0: the fp8 / fp6 stage first ----
-    const SeedArgs sa8 = seeds_for(w, p.Tt_pad / ft, p.split, k, f6 ? SEED_MARGIN6 : SEED_MARGIN8, ST_SEEDED, s, f6 ? SEED_MIN_FB6 : SEED_MIN_FB);
+    const int64_t fb = wide ? p.Tt_pad / FT6W : p.Tt_pad / ft, fb6 = w.p6.Tt_pad / FT6;
+    const SeedArgs sa8 = seeds_for(w, fb, p.split, k, f6 ? SEED_MARGIN6 : SEED_MARGIN8, ST_SEEDED, s, f6 ? SEED_MIN_FB6 : SEED_MIN_FB);
+    if (wide && sa8.flag != nullptr && fb6 > fb)       // the plain kernel's 384-frame blocks are more: their flags too
+        (void)hipMemsetAsync(w.tau_flag, 0, (size_t)fb6 * p.split * sizeof(int), s);
     if (g_ev_start) (void)hipEventRecord(g_ev_start, s);             // behind the memset of the seed flags: the events bracket the kernel alone
     if (y_sub != nullptr) {            // one of the two runs: the gate word of sub_select_kernel (1 subspace, 2 plain, 0 neither)
         const int* gate = w.stats + ST_SUB_GATE;
-        knn_sub6_kernel<<<dim3((unsigned)(p.Tt_pad / ft), p.split), 256, SUB6_LDS, s>>>(
-            w.sub_f6, (const unsigned char*)lib_sub, rho, w.sub_g, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, gate, 0, 1, sa8);
-        knn_score6_kernel<<<dim3((unsigned)(p.Tt_pad / ft), p.split), 256, lds, s>>>(
+        if (wide)
+            knn_sub6w_kernel<<<dim3((unsigned)fb, p.split), 256, SUB6W_LDS, s>>>(
+                w.sub_f6, (const unsigned char*)lib_sub, rho, w.sub_g, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, gate, 0, 1, sa8);
+        else
+            knn_sub6_kernel<<<dim3((unsigned)fb, p.split), 256, SUB6_LDS, s>>>(
+                w.sub_f6, (const unsigned char*)lib_sub, rho, w.sub_g, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, gate, 0, 1, sa8);
+        knn_score6_kernel<<<dim3((unsigned)fb6, p.split), 256, lds, s>>>(
             w.s_f8, (const unsigned char*)lib_f8, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, gate, 1, 2, sa8);
     } else if (f6)
         knn_score6_kernel<<<dim3((unsigned)(p.Tt_pad / ft), p.split), 256, lds, s>>>(
@@ -4064,7 +4254,7 @@ extern "C" int alive_library_pack_fp6_sub(const float* y_rows, int64_t m0, int64
     return ALIVE_OK;
 }
 
-// device pointer (inside ws) to the counters of the last search on this workspace, int[32] (ST_WORDS; slots used today: 0-4, 7-21):
+// device pointer (inside ws) to the counters of the last search on this workspace, int[32] (ST_WORDS; slots used today: 0-4, 7-22):
 //   [0] frames the fp8 certificate sent to the bf16 stage (all frames when the probe chose bf16 first)
 //   [1] frames the bf16 certificate sent on (to the collect tier; [8] of them end in the exact scan)
 //   [2] frames of the probe sample, [3] of which failed the fp8 certificate, [4] 1 = the probe chose bf16 first
@@ -4073,6 +4263,7 @@ extern "C" int alive_library_pack_fp6_sub(const float* y_rows, int64_t m0, int64
 //       (strict search with a lo-plane library: the collect tier IS the split-bf16 pass)
 //   [14] / [15] subspace search: frames flagged by sub_codes_kernel (out of the subspace or clipped) / of them clipped;
 //   [20] / [21] its form and gate word: 1 the subspace kernel, 2 the plain fp6 kernel; [21] = 0: neither ran (bf16 first)
+//   [22] frames per block of the subspace kernel it launched: 384 (knn_sub6_kernel) / 512 (knn_sub6w_kernel, alive_knn_sub_frames)
 // (the counters are the first thing in the workspace: their address depends on neither the batch nor k)
 extern "C" const int* alive_knn_search_stats(int N, int T, int64_t M, void* ws) {
     return ws_layout(ws, (int64_t)N * T, M, 4).stats;
@@ -4098,6 +4289,43 @@ extern "C" int alive_debug_knn_stage_view(int64_t Tt, int64_t M, int k, int sub,
     }
     out[20] = KP; out[21] = KP8; out[22] = FT; out[23] = FT6; out[24] = LT;
     if (n_out >= 27) { out[25] = off(w.sub_planes); out[26] = off(w.sub_y); }
+    if (n_out >= 32) {                     // the wide subspace kernel's plan (512-frame blocks) and its frames per block
+        out[27] = w.p6w.Tt_pad; out[28] = w.p6w.tiles_total; out[29] = w.p6w.tiles_per_split; out[30] = w.p6w.P; out[31] = FT6W;
+    }
+    return ALIVE_OK;
+}
+
+// debug (tests/test_gpu_knn_sub_wide.py): the subspace stage alone on the caller's operands, the library cut into `split` ranges of the
+// caller's choosing (a search never leaves a small batch with few splits, so the 16-bit tile offsets of knn_sub6w_kernel are out of its
+// reach at any library a test can hold).  The kernel is chosen as in the search: alive_knn_sub_frames and the 65 535-tile limit; the
+// block-count threshold of the rule does not apply (mode 0 counts as 512).  frames: Tt_pad codes [Tt_pad][512] and g [Tt_pad], Tt_pad a
+// multiple of 1536; lib_sub / rho as alive_library_pack_fp6_sub leaves them; cand [Tt_pad][split][32].  Unseeded, ungated.  Returns the
+// frames per block of the kernel launched (384 / 512) in *frames_out.
+extern "C" int alive_debug_knn_sub_stage(const void* s_sub, const float* g, int64_t Tt_pad, const void* lib_sub, const float* rho, int64_t M,
+                                         int split, float* cand_val, int32_t* cand_idx, int* frames_out, void* stream) {
+    ALIVE_CHECK_ARG(s_sub && g && lib_sub && rho && cand_val && cand_idx && frames_out, "alive_debug_knn_sub_stage: null pointer");
+    ALIVE_CHECK_ARG(Tt_pad >= 1 && Tt_pad % (3 * FT6W) == 0 && Tt_pad < ((int64_t)1 << 24), "alive_debug_knn_sub_stage: Tt_pad must be a multiple of %d", 3 * FT6W);
+    ALIVE_CHECK_ARG(M >= 1 && M < ((int64_t)1 << 31) - TILE && split >= 1 && split <= MAX_SPLIT8, "alive_debug_knn_sub_stage: M or split out of range");
+    if (int rc = lds_optin("alive_debug_knn_sub_stage")) return rc;
+    SearchPlan p;
+    p.Tt = p.Tt_pad = Tt_pad;
+    p.tiles_total = (int)(((M + TILE - 1) / TILE * TILE) / LT);
+    p.split = p.P = split;
+    p.tiles_per_split = (p.tiles_total + split - 1) / split;
+    const int mode = sub_frames_mode();
+    const bool wide = mode != FT6 && p.tiles_per_split <= SUB6W_MAX_TILES;
+    const SeedArgs none{nullptr, nullptr, 0, 0.0f, nullptr};
+    hipStream_t s = (hipStream_t)stream;
+    if (wide)
+        knn_sub6w_kernel<<<dim3((unsigned)(Tt_pad / FT6W), split), 256, SUB6W_LDS, s>>>(
+            (const unsigned char*)s_sub, (const unsigned char*)lib_sub, rho, g, M, p.tiles_total, p.tiles_per_split, p.P, cand_val, cand_idx,
+            nullptr, 0, 1, none);
+    else
+        knn_sub6_kernel<<<dim3((unsigned)(Tt_pad / FT6), split), 256, SUB6_LDS, s>>>(
+            (const unsigned char*)s_sub, (const unsigned char*)lib_sub, rho, g, M, p.tiles_total, p.tiles_per_split, p.P, cand_val, cand_idx,
+            nullptr, 0, 1, none);
+    ALIVE_CHECK_LAUNCH("alive_debug_knn_sub_stage");
+    *frames_out = wide ? FT6W : FT6;
     return ALIVE_OK;
 }
 

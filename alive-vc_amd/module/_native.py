@@ -88,6 +88,7 @@ PROTOTYPES = {
     "alive_knn_search_fp8": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP]),
     "alive_knn_search_stats": (_VP, [_I, _I, _I64, _VP]),
     "alive_debug_knn_stage_view": (_I, [_I64, _I64, _I, _I, _VP, _I]),
+    "alive_debug_knn_sub_stage": (_I, [_VP, _VP, _I64, _VP, _VP, _I64, _I, _VP, _VP, _VP, _VP]),
     "alive_debug_knn_rescore": (_I, [C.POINTER(AliveRescoreArgs), _VP]),                              # test only
     "alive_debug_knn_rescore_pool": (_I, [C.POINTER(AliveRescoreArgs), _VP, _VP, _VP, _VP, _I, _VP]),  # test only
     "alive_debug_knn_pool_fields": (_I, [_VP, _I]),                                                   # test only
@@ -95,6 +96,7 @@ PROTOTYPES = {
     "alive_knn_search_fp8_timed": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I64, _I64, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "alive_library_pack_fp6": (_I, [_VP, _I64, _VP, _VP]),
     "alive_knn_sub_coordinates": (_I, []),
+    "alive_knn_sub_frames": (_I, [_I]),
     "alive_knn_workspace_bytes_sub": (_SZ, [_I64, _I64]),
     "alive_library_fp6_sub_bytes": (_SZ, [_I64]),
     "alive_library_pack_fp6_sub": (_I, [_VP, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),

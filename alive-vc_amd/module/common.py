@@ -339,7 +339,8 @@ class PackedLibrary:
         c = ws[off:off + 128].view(torch.int32).tolist()      # int[32]: knn.hip ST_*
         tier = c[7]                                     # written by the C side on every path (knn.hip: ST_TIER)
         if sub and tier == 5:                           # subspace form (knn.hip ST_SUB_*): which kernel scored, frames flagged / clipped
-            st.update(stage_form={1: "subspace", 2: "plain"}.get(c[21], "none"), frames_left_subspace=c[14] - c[15], frames_clipped=c[15])
+            st.update(stage_form={1: "subspace", 2: "plain"}.get(c[21], "none"), frames_left_subspace=c[14] - c[15], frames_clipped=c[15],
+                      stage_frames=c[22])         # frames per block of the subspace kernel launched: 384 / 512 (alive_knn_sub_frames)
         if tier == 1:
             return dict(st, tier="exact scan of every row (streaming)")
         if tier == 2:

@@ -146,8 +146,15 @@ const int* alive_knn_search_stats(int N, int T, int64_t M, void* ws);
  *   out[20 .. 24] candidates per frame and split (bf16 stage, block-scaled stages), frames per block (256-frame kernels, fp6
  *                 kernels), library rows per tile.  Candidates are [frame][P][candidates per split].  n_out >= 25.
  *   out[25 .. 26] (n_out >= 27; -1 without sub) byte offsets of alive_knn_search_unit's change of basis: the frames' two k-blocked bf16
- *                 planes [2][24][cols_pad][32] and y_sub [N][576][T] fp32. */
+ *                 planes [2][24][cols_pad][32] and y_sub [N][576][T] fp32.
+ *   out[27 .. 31] (n_out >= 32) Tt_pad, tiles_total, tiles_per_split, P of the wide subspace kernel's plan and its frames per block (512). */
 int alive_debug_knn_stage_view(int64_t Tt, int64_t M, int k, int sub, int64_t* out, int n_out);
+/* Debug (tests/test_gpu_knn_sub_wide.py): the subspace candidate stage alone, the library cut into `split` ranges of the caller's choosing.
+ * s_sub [Tt_pad][512] frame codes and g [Tt_pad] (Tt_pad a multiple of 1536), lib_sub / rho from alive_library_pack_fp6_sub, cand_val /
+ * cand_idx [Tt_pad][split][32].  The kernel is chosen as in the search (alive_knn_sub_frames, at most 65 535 tiles per split for the
+ * 512-frame kernel; mode 0 counts as 512); *frames_out (host) receives its frames per block, 384 or 512.  Unseeded. */
+int alive_debug_knn_sub_stage(const void* s_sub, const float* g, int64_t Tt_pad, const void* lib_sub, const float* rho, int64_t M, int split,
+                              float* cand_val, int32_t* cand_idx, int* frames_out, void* stream);
 
 /* TEST ONLY (tests/test_gpu_knn_cert.py): the rescoring kernel that ends every search, launched by the searches' own dispatcher on
  * the caller's device buffers -- every argument the searches forward, under the names of knn_rescore_kernel (csrc/knn.hip), plus the
@@ -258,6 +265,17 @@ int alive_knn_search_fp6_timed(const float* src, int N, int T,
  *     scoring launches.  Counters (alive_knn_search_stats): [14] frames flagged, [15] of them clipped, [21] which kernel scored
  *     (1 subspace, 2 plain fp6, 0 neither: the probe chose bf16 first). */
 int alive_knn_sub_coordinates(void);
+/* Which kernel scores the subspace stage (process-wide; not to be changed while a search is in flight):
+ *   mode 384: knn_sub6_kernel, 96 stationary frames per wave, 384-frame blocks;
+ *   mode 512: knn_sub6w_kernel, 128 stationary frames per wave, 512-frame blocks, whenever a library split has at most 65 535 tiles
+ *             (its lists hold 16-bit tile offsets; beyond that the 384-frame kernel runs);
+ *   mode < 0: back to the rule: the 512-frame kernel when the batch fills at least 300 of its frame blocks (seeded admission on) and a
+ *             split has at most 65 535 tiles.  The rule reads the frame count and M only.  The initial state, unless
+ *             ALIVE_KNN_SUB_FRAMES is 384 or 512;
+ *   mode 0:   query.  Returns the mode in force: 384, 512, or 0 for the rule.
+ * Either kernel leaves the same candidate layout; the search's results are the exact top-k in both.  Counter [22] of
+ * alive_knn_search_stats tells which one the last subspace search launched (384 / 512). */
+int alive_knn_sub_frames(int mode);
 size_t alive_knn_workspace_bytes_sub(int64_t Tt, int64_t M);      /* the workspace of alive_knn_search_fp6_sub_timed */
 size_t alive_library_fp6_sub_bytes(int64_t M);
 int alive_library_pack_fp6_sub(const float* y_rows, int64_t m0, int64_t count, int64_t M, void* lib_sub, float* rho, int* clip,

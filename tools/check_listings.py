@@ -42,7 +42,7 @@ def main():
             print(f"check_listings: {tag}: {r['mfma']} MFMAs, {len(r['switches'])} chain switches beside an unread accumulator, {len(short)} without the gap")
             if r["mfma"] < least.get(tag, 100) or short:
                 bad.append((tag, "chain gap", short[:3]))
-        for kern, want in (("knn_score6_kernel", 36), ("knn_probe6_kernel", 36), ("knn_sub6_kernel", 24)):
+        for kern, want in (("knn_score6_kernel", 36), ("knn_probe6_kernel", 36), ("knn_sub6_kernel", 24), ("knn_sub6w_kernel", 24)):
             n_asm, unwaited = hz.asm_lds_reads_are_waited_for(lst["knn"], kern)
             print(f"check_listings: {kern}: {n_asm} asm LDS reads, {unwaited} touched before an lgkmcnt wait")
             if n_asm != want or unwaited:
