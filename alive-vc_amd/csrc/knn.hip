@@ -1082,6 +1082,9 @@ constexpr int SEED_MIN_FB = 512;
 constexpr int SEED_MIN_FB6 = 300;                                // fp6 kernel, 384-frame blocks: a little over one round of the chip is enough --
                                                                  // the look at the predecessor's flag never waits, an unfinished one means an unseeded block
 
+// a compile-time int as a lambda argument (the tile buffer, the k-step: knn_score8_body load_a)
+template <int V> struct IntC { static constexpr int value = V; };
+
 template <int FMT, int NCT8, int NK = NK64>
 __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict__ s_f8,
                                                 const unsigned char* __restrict__ lib, int64_t M, int tiles_total,
@@ -1208,8 +1211,19 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
     const int lc0 = w * (2 * WF8) + lane;
     __syncthreads();
 
-    auto load_a = [&](const unsigned char* Ab, int ks) {
-        const unsigned char* q = Ab + (ks >> 1) * 4 * PIECE;
+    // The tile buffer and the k-step are compile-time values (IntC): buffer and segment are then ONE constant, K, that rides in the
+    // offset field of both reads instead of a v_add_u32 per address in front of them (26 per two tiles of the wide kernel).  The lane's
+    // part of the address, ab[j][c] = LDS address of smem + a_off[j][c], lives in four registers for the whole kernel; the asm read
+    // "modifies" ab[j][0] in place (the tie below), so the chain of reads goes through the same register and no copy is made.
+    unsigned ab[2][2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) ab[j][c] = (unsigned)(uintptr_t)(lptr_t)(smem + a_off[j][c]);
+    auto load_a = [&](auto bufc, auto ksc) {
+        constexpr int ks = decltype(ksc)::value;
+        constexpr int K = decltype(bufc)::value * ABUF_ + (ks >> 1) * 4 * PIECE;
+        static_assert(2 * ABUF_ < 65536, "buffer and segment must fit the 16-bit offset field of a ds_read");
         if constexpr (FMT == 2) {
             // Only the 24 code bytes of the 32-byte slot leave the LDS (the kernel moves 120 KB through the LDS per 1 152 MFMA cycles:
             // 61.0 -> 57.7 ms per launch against two b128 reads).  A compiler-visible ds_read_b64 of the tile
@@ -1218,20 +1232,25 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             // hipcc places in front of the fragment's first use (the MFMA takes both halves) covers the asm read too; an unknown
             // extra read in flight can only make hipcc's counted waits stricter.  tests/test_host_logic.py checks on the listing
             // that no instruction touches an asm read's registers before an lgkmcnt wait.
-            unsigned off0 = (unsigned)(uintptr_t)(lptr_t)(q + a_off[ks & 1][0]);
-            const unsigned off1 = (unsigned)(uintptr_t)(lptr_t)(q + a_off[ks & 1][1]);
             uint2 h8;
-            asm volatile("ds_read_b64 %0, %2" : "=v"(h8), "+v"(off0) : "v"(off1));
-            const u32x4 lo = *(const __attribute__((address_space(3))) u32x4*)(uintptr_t)off0;
+            asm volatile("ds_read_b64 %0, %2 offset:%3" : "=v"(h8), "+v"(ab[ks & 1][0]) : "v"(ab[ks & 1][1]), "n"(K));
+            const u32x4 lo = *(const __attribute__((address_space(3))) u32x4*)(uintptr_t)(ab[ks & 1][0] + K);
             return v8i{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)h8.x, (int)h8.y, 0, 0};
         }
+        const unsigned char* q = smem + K;
         const u32x4 lo = *(const u32x4*)(q + a_off[ks & 1][0]);
         const u32x4 hi = *(const u32x4*)(q + a_off[ks & 1][1]);
         return v8i{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
     };
 
     // ---- folding a 32 x 32 accumulator tile (column group ni) into the per-frame candidate lists, in pieces ----
-    // rows beyond M (only in the library's last tiles: a real, wave-uniform branch)
+    // rows beyond M (only in the library's last tiles: a real, wave-uniform branch).  Called by fold_now* alone, on the last tile of a
+    // split; the tile bodies (do_tile*) fold the PREVIOUS tile without it.  Rows come padded to TILE = 128 = 4 tiles, so up to three
+    // ragged or all-pad tiles (every tile with row0 + LT > M but the library's last) ARE folded inside a tile body: there the running
+    // maximum may carry a pad row's score (zero codes: 0, or g rho of a pad row), which can only open fold_rare for nothing --
+    // fold_rare puts the rows beyond M back to -inf before it picks (below), so no pad row is admitted, the lists are entry for
+    // entry what they were, and the price is the out-of-line block on at most three tiles per search.  What it buys: eight
+    // compare / branch sets and ~50 instructions of masking each out of the span of the loop, which one wave per SIMD fetches alone.
     auto mask_ragged = [&](f32x16& acc, int tile) {
         const int64_t row0 = (int64_t)tile * LT;
         if (row0 + LT > M) {
@@ -1309,7 +1328,9 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
     };
 
     auto fold_rare = [&](f32x16& acc, int ni, int tile, float mx) {
-        if (__builtin_amdgcn_ballot_w64(mx > thr[ni]) == 0) return;
+        // (expected: hipcc then places everything below behind the loop, and the tile bodies run with no taken branch but the back edge;
+        // tests/test_host_knn_loop_layout.py checks the branch targets on the listing)
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(mx > thr[ni]) == 0, 1)) return;
         // Rare path (wave-uniform; by ablation ~1500 cycles with the matrix pipe idle, 15 % of the kernel on the bench batch and
         // 30 % on uncorrelated frames), cut for the common case of ONE admitted row per lane:
         //  * every lane's list minimum and its quarter are known from the register caches, so the quarter is read from LDS
@@ -1380,19 +1401,18 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
     // rv: rho of the previous tile's rows (the subspace stage; ready: loaded one tile earlier), rn: rho of this tile's rows, requested
     // here and waited for by the barrier at the end of the tile (vmcnt(0) there for the DMA anyway) -- a plain load consumed inside the
     // tile would make hipcc drain vmcnt, the LDS-DMA pieces just issued included, in the middle of it
-    auto do_tile3 = [&](int tile, f32x16& c0, f32x16& c1, f32x16& c2, f32x16& p0, f32x16& p1, f32x16& p2, float* rv, float* rn) {
-        const int buf = (tile - tile_begin) & 1;
+    auto do_tile3 = [&](auto bufc, int tile, f32x16& c0, f32x16& c1, f32x16& c2, f32x16& p0, f32x16& p1, f32x16& p2, float* rv, float* rn) {
+        constexpr int buf = decltype(bufc)::value;      // (tile - tile_begin) & 1: the callers alternate 0, 1 from tile_begin on
         const int next_tile = tile + 1 < tile_end ? tile + 1 : tile;
         const unsigned char* gnext = lib + ((size_t)next_tile * LT + dma_row) * KD + dma_chunk * 16;
         unsigned char* lnext = smem + (buf ^ 1) * ABUF_ + w * PIECE;
-        const unsigned char* Ab = smem + buf * ABUF_;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; c2[r] = 0.0f; }
         if constexpr (NK != NK64) load_rho(tile, rn);
         constexpr int PD6 = 1, NA6 = PD6 + 1;     // A fragments requested this many k-steps ahead of their MFMAs
         v8i a[NA6];
-#pragma unroll
-        for (int i = 0; i < PD6; ++i) a[i] = load_a(Ab, i);
+        static_assert(PD6 == 1, "one fragment in flight in front of the first k-step");
+        a[0] = load_a(bufc, IntC<0>{});
         float pm0 = -INFINITY, pm1 = -INFINITY, pm2 = -INFINITY;
         ALIVE_CHAIN_GAP(7);
 #define K8_STEP3(ks, AFTER0, AFTER1, AFTER2)                                                                                     \
@@ -1400,7 +1420,7 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
             c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[(ks) % NA6], bq[0][ks], c0, FMT, FMT, 0, 127, 0, 127); \
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
-            if ((ks) + PD6 < NK) a[((ks) + PD6) % NA6] = load_a(Ab, (ks) + PD6);                                                 \
+            if ((ks) + PD6 < NK) a[((ks) + PD6) % NA6] = load_a(bufc, IntC<(ks) + PD6>{});                                                 \
             if ((ks) < NSEG)                                                                                                     \
                 __builtin_amdgcn_global_load_lds((gptr_t)(gnext + (ks) * 128), (lptr_t)(lnext + (ks) * 4 * PIECE), 16, 0, 0);    \
             AFTER0;                                                                                                              \
@@ -1425,21 +1445,21 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         }
         if constexpr (NK == NK64) {
         // (each column tile's copy is folded before the next one is read: one 16-register copy live at a time)
-        K8_STEP3(6, acc_read(p0, 0, 8, v0), (acc_pin(), acc_read(p0, 8, 16, v0), mask_ragged(v0, tile - 1)), (acc_pin(), pm0 = max8(v0, 0, pm0)))
+        K8_STEP3(6, acc_read(p0, 0, 8, v0), (acc_pin(), acc_read(p0, 8, 16, v0)), (acc_pin(), pm0 = max8(v0, 0, pm0)))
         K8_STEP3(7, pm0 = max8(v0, 8, pm0), fold_rare(v0, 0, tile - 1, pm0), (acc_pin(), acc_read(p1, 0, 8, v1)))
-        K8_STEP3(8, (acc_pin(), acc_read(p1, 8, 16, v1), mask_ragged(v1, tile - 1)), (acc_pin(), pm1 = max8(v1, 0, pm1)), pm1 = max8(v1, 8, pm1))
-        K8_STEP3(9, fold_rare(v1, 1, tile - 1, pm1), (acc_pin(), acc_read(p2, 0, 8, v2)), (acc_pin(), acc_read(p2, 8, 16, v2), mask_ragged(v2, tile - 1)))
+        K8_STEP3(8, (acc_pin(), acc_read(p1, 8, 16, v1)), (acc_pin(), pm1 = max8(v1, 0, pm1)), pm1 = max8(v1, 8, pm1))
+        K8_STEP3(9, fold_rare(v1, 1, tile - 1, pm1), (acc_pin(), acc_read(p2, 0, 8, v2)), (acc_pin(), acc_read(p2, 8, 16, v2)))
         K8_STEP3(10, (acc_pin(), pm2 = max8(v2, 0, pm2)), pm2 = max8(v2, 8, pm2), fold_rare(v2, 2, tile - 1, pm2))
         K8_STEP3(11, (void)0, (void)0, (void)0)
         } else {
         // the subspace stage: 8 k-steps, the 4 DMA pieces in steps 0 .. 3; the previous tile's fold (the same 15 pieces as above) takes
         // the slots from the second MFMA of step 3 on, its rho (4 x 16 B per lane, requested in front of this tile's DMA pieces) has
         // had three steps to arrive
-        K8_STEP3(3, acc_pin(), (acc_pin(), acc_read(p0, 0, 8, v0)), (acc_pin(), acc_read(p0, 8, 16, v0), mask_ragged(v0, tile - 1)))
+        K8_STEP3(3, acc_pin(), (acc_pin(), acc_read(p0, 0, 8, v0)), (acc_pin(), acc_read(p0, 8, 16, v0)))
         K8_STEP3(4, (acc_pin(), pm0 = max8g(v0, 0, pm0, 0, rv)), pm0 = max8g(v0, 8, pm0, 0, rv), fold_rare(v0, 0, tile - 1, pm0))
-        K8_STEP3(5, (acc_pin(), acc_read(p1, 0, 8, v1)), (acc_pin(), acc_read(p1, 8, 16, v1), mask_ragged(v1, tile - 1)), (acc_pin(), pm1 = max8g(v1, 0, pm1, 1, rv)))
+        K8_STEP3(5, (acc_pin(), acc_read(p1, 0, 8, v1)), (acc_pin(), acc_read(p1, 8, 16, v1)), (acc_pin(), pm1 = max8g(v1, 0, pm1, 1, rv)))
         K8_STEP3(6, pm1 = max8g(v1, 8, pm1, 1, rv), fold_rare(v1, 1, tile - 1, pm1), (acc_pin(), acc_read(p2, 0, 8, v2)))
-        K8_STEP3(7, (acc_pin(), acc_read(p2, 8, 16, v2), mask_ragged(v2, tile - 1)), (acc_pin(), pm2 = max8g(v2, 0, pm2, 2, rv)),
+        K8_STEP3(7, (acc_pin(), acc_read(p2, 8, 16, v2)), (acc_pin(), pm2 = max8g(v2, 0, pm2, 2, rv)),
                  (pm2 = max8g(v2, 8, pm2, 2, rv), fold_rare(v2, 2, tile - 1, pm2)))
         }
 #undef K8_STEP3
@@ -1466,11 +1486,11 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         for (int r = 0; r < 16; ++r) { B0[r] = -INFINITY; B1[r] = -INFINITY; B2[r] = -INFINITY; RA[r] = 0.0f; RB[r] = 0.0f; }
         int tile = tile_begin;
         for (; tile + 1 < tile_end; tile += 2) {
-            do_tile3(tile, A0, A1, A2, B0, B1, B2, RB, RA);
-            do_tile3(tile + 1, B0, B1, B2, A0, A1, A2, RA, RB);
+            do_tile3(IntC<0>{}, tile, A0, A1, A2, B0, B1, B2, RB, RA);
+            do_tile3(IntC<1>{}, tile + 1, B0, B1, B2, A0, A1, A2, RA, RB);
         }
         if (tile < tile_end) {
-            do_tile3(tile, A0, A1, A2, B0, B1, B2, RB, RA);
+            do_tile3(IntC<0>{}, tile, A0, A1, A2, B0, B1, B2, RB, RA);
             fold_now3(A0, A1, A2, tile, RA);
         } else if (tile_begin < tile_end) {
             fold_now3(B0, B1, B2, tile_end - 1, RB);
@@ -1482,18 +1502,17 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
     // tile into (c0 .. c3); the 4 DMA pieces ride in the first gap of steps 0 .. 3, the previous tile's fold (the five pieces per column
     // tile of the three-tile form, 20 in all) takes the gaps without a DMA piece from step 0 on; rho rides one tile ahead as there.
     static_assert(NK == 8 && FMT == 2, "the four-tile form exists for the subspace stage");
-    auto do_tile4 = [&](int tile, f32x16& c0, f32x16& c1, f32x16& c2, f32x16& c3, f32x16& p0, f32x16& p1, f32x16& p2, f32x16& p3,
+    auto do_tile4 = [&](auto bufc, int tile, f32x16& c0, f32x16& c1, f32x16& c2, f32x16& c3, f32x16& p0, f32x16& p1, f32x16& p2, f32x16& p3,
                         float* rv, float* rn) {
-        const int buf = (tile - tile_begin) & 1;
+        constexpr int buf = decltype(bufc)::value;      // (tile - tile_begin) & 1: the callers alternate 0, 1 from tile_begin on
         const int next_tile = tile + 1 < tile_end ? tile + 1 : tile;
         const unsigned char* gnext = lib + ((size_t)next_tile * LT + dma_row) * KD + dma_chunk * 16;
         unsigned char* lnext = smem + (buf ^ 1) * ABUF_ + w * PIECE;
-        const unsigned char* Ab = smem + buf * ABUF_;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; c2[r] = 0.0f; c3[r] = 0.0f; }
         load_rho(tile, rn);
         v8i a[2];
-        a[0] = load_a(Ab, 0);
+        a[0] = load_a(bufc, IntC<0>{});
         float pm0 = -INFINITY, pm1 = -INFINITY, pm2 = -INFINITY, pm3 = -INFINITY;
         ALIVE_CHAIN_GAP(7);
 #define K8_STEP4(ks, AFTER0, AFTER1, AFTER2, AFTER3)                                                                             \
@@ -1501,7 +1520,7 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
             c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[(ks) & 1], bq[0][ks], c0, FMT, FMT, 0, 127, 0, 127);          \
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
-            if ((ks) + 1 < NK) a[((ks) + 1) & 1] = load_a(Ab, (ks) + 1);                                                         \
+            if ((ks) + 1 < NK) a[((ks) + 1) & 1] = load_a(bufc, IntC<(ks) + 1>{});                                                         \
             if ((ks) < NSEG)                                                                                                     \
                 __builtin_amdgcn_global_load_lds((gptr_t)(gnext + (ks) * 128), (lptr_t)(lnext + (ks) * 4 * PIECE), 16, 0, 0);    \
             AFTER0;                                                                                                              \
@@ -1529,16 +1548,16 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         // (each column tile's copy is folded before the next one is read: one 16-register copy live at a time)
         // (step 0 pins only the chains that have begun: naming c2 / c3 before their first MFMA, which takes C = 0, would make hipcc write
         // 32 zeros into them)
-        K8_STEP4(0, (void)0, (acc_pin2(), acc_read(p0, 0, 8, v0)), (acc_pin3(), acc_read(p0, 8, 16, v0), mask_ragged(v0, tile - 1)),
+        K8_STEP4(0, (void)0, (acc_pin2(), acc_read(p0, 0, 8, v0)), (acc_pin3(), acc_read(p0, 8, 16, v0)),
                  (acc_pin(), pm0 = max8g(v0, 0, pm0, 0, rv)))
         K8_STEP4(1, (void)0, pm0 = max8g(v0, 8, pm0, 0, rv), fold_rare(v0, 0, tile - 1, pm0), (acc_pin(), acc_read(p1, 0, 8, v1)))
-        K8_STEP4(2, (void)0, (acc_pin(), acc_read(p1, 8, 16, v1), mask_ragged(v1, tile - 1)), (acc_pin(), pm1 = max8g(v1, 0, pm1, 1, rv)),
+        K8_STEP4(2, (void)0, (acc_pin(), acc_read(p1, 8, 16, v1)), (acc_pin(), pm1 = max8g(v1, 0, pm1, 1, rv)),
                  pm1 = max8g(v1, 8, pm1, 1, rv))
         K8_STEP4(3, (void)0, fold_rare(v1, 1, tile - 1, pm1), (acc_pin(), acc_read(p2, 0, 8, v2)),
-                 (acc_pin(), acc_read(p2, 8, 16, v2), mask_ragged(v2, tile - 1)))
+                 (acc_pin(), acc_read(p2, 8, 16, v2)))
         K8_STEP4(4, (acc_pin(), pm2 = max8g(v2, 0, pm2, 2, rv)), pm2 = max8g(v2, 8, pm2, 2, rv), fold_rare(v2, 2, tile - 1, pm2),
                  (acc_pin(), acc_read(p3, 0, 8, v3)))
-        K8_STEP4(5, (acc_pin(), acc_read(p3, 8, 16, v3), mask_ragged(v3, tile - 1)), (acc_pin(), pm3 = max8g(v3, 0, pm3, 3, rv)),
+        K8_STEP4(5, (acc_pin(), acc_read(p3, 8, 16, v3)), (acc_pin(), pm3 = max8g(v3, 0, pm3, 3, rv)),
                  pm3 = max8g(v3, 8, pm3, 3, rv), fold_rare(v3, 3, tile - 1, pm3))
         K8_STEP4(6, (void)0, (void)0, (void)0, (void)0)
         K8_STEP4(7, (void)0, (void)0, (void)0, (void)0)
@@ -1567,23 +1586,22 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         for (int r = 0; r < 16; ++r) { B0[r] = -INFINITY; B1[r] = -INFINITY; B2[r] = -INFINITY; B3[r] = -INFINITY; RA[r] = 0.0f; RB[r] = 0.0f; }
         int tile = tile_begin;
         for (; tile + 1 < tile_end; tile += 2) {
-            do_tile4(tile, A0, A1, A2, A3, B0, B1, B2, B3, RB, RA);
-            do_tile4(tile + 1, B0, B1, B2, B3, A0, A1, A2, A3, RA, RB);
+            do_tile4(IntC<0>{}, tile, A0, A1, A2, A3, B0, B1, B2, B3, RB, RA);
+            do_tile4(IntC<1>{}, tile + 1, B0, B1, B2, B3, A0, A1, A2, A3, RA, RB);
         }
         if (tile < tile_end) {
-            do_tile4(tile, A0, A1, A2, A3, B0, B1, B2, B3, RB, RA);
+            do_tile4(IntC<0>{}, tile, A0, A1, A2, A3, B0, B1, B2, B3, RB, RA);
             fold_now4(A0, A1, A2, A3, tile, RA);
         } else if (tile_begin < tile_end) {
             fold_now4(B0, B1, B2, B3, tile_end - 1, RB);
         }
     }
     } else {
-    auto do_tile = [&](int tile, f32x16& c0, f32x16& c1, f32x16& p0, f32x16& p1) {
-        const int buf = (tile - tile_begin) & 1;
+    auto do_tile = [&](auto bufc, int tile, f32x16& c0, f32x16& c1, f32x16& p0, f32x16& p1) {
+        constexpr int buf = decltype(bufc)::value;      // (tile - tile_begin) & 1: the callers alternate 0, 1 from tile_begin on
         const int next_tile = tile + 1 < tile_end ? tile + 1 : tile;
         const unsigned char* gnext = lib + ((size_t)next_tile * LT + dma_row) * KD + dma_chunk * 16;
         unsigned char* lnext = smem + (buf ^ 1) * ABUF_ + w * PIECE;
-        const unsigned char* Ab = smem + buf * ABUF_;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { c0[r] = 0.0f; c1[r] = 0.0f; }
         // hipcc waits lgkmcnt(0) in front of every MFMA that takes an LDS fragment, i.e. for EVERYTHING in flight -- a
@@ -1591,7 +1609,7 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         // fragment of step ks + 1 is requested between the two MFMAs of step ks: the wait then falls in front of the next
         // step's first MFMA, ~120 cycles later, behind this step's second MFMA in the matrix pipe.
         v8i a[2];
-        a[0] = load_a(Ab, 0);
+        a[0] = load_a(bufc, IntC<0>{});
         float pm0 = -INFINITY, pm1 = -INFINITY;
 #ifndef ALIVE_KNN8_NO_CHAIN_GAP
         // (p0, p1) are read in steps 6 .. 9, beside this tile's chains: the shape of the accumulation-chain hazard of the fused
@@ -1605,7 +1623,7 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
             c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[(ks) & 1], bq[0][ks], c0, FMT, FMT, 0, 127, 0, 127);              \
             __builtin_amdgcn_sched_barrier(0);                                                                                   \
-            if ((ks) + 1 < NK) a[((ks) + 1) & 1] = load_a(Ab, (ks) + 1);                                                         \
+            if ((ks) + 1 < NK) a[((ks) + 1) & 1] = load_a(bufc, IntC<(ks) + 1>{});                                                         \
             if ((ks) < NSEG)    /* the 6 DMA pieces of the next tile go out in the FIRST half of this one: the barrier at its */  \
                                 /* end waits vmcnt(0), and a piece issued in the last step exposes a whole L2 / HBM round trip */ \
                 __builtin_amdgcn_global_load_lds((gptr_t)(gnext + (ks) * 128), (lptr_t)(lnext + (ks) * 4 * PIECE), 16, 0, 0);    \
@@ -1634,9 +1652,9 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
         auto acc_pin = [&]() { asm volatile("" : "+a"(c0), "+a"(c1)); };
         K8_STEP(0, (void)0, (void)0) K8_STEP(1, (void)0, (void)0) K8_STEP(2, (void)0, (void)0) K8_STEP(3, (void)0, (void)0)
         K8_STEP(4, (void)0, (void)0) K8_STEP(5, (void)0, acc_pin())
-        K8_STEP(6, acc_read(p0, 0, 8, v0), (acc_pin(), acc_read(p0, 8, 16, v0), mask_ragged(v0, tile - 1)))
+        K8_STEP(6, acc_read(p0, 0, 8, v0), (acc_pin(), acc_read(p0, 8, 16, v0)))
         K8_STEP(7, (acc_pin(), pm0 = max8(v0, 0, pm0)), pm0 = max8(v0, 8, pm0))
-        K8_STEP(8, (acc_pin(), acc_read(p1, 0, 8, v1)), (acc_pin(), acc_read(p1, 8, 16, v1), mask_ragged(v1, tile - 1)))
+        K8_STEP(8, (acc_pin(), acc_read(p1, 0, 8, v1)), (acc_pin(), acc_read(p1, 8, 16, v1)))
         K8_STEP(9, (acc_pin(), pm1 = max8(v1, 0, pm1)), pm1 = max8(v1, 8, pm1))
         K8_STEP(10, (void)0, fold_rare(v0, 0, tile - 1, pm0))
         K8_STEP(11, (void)0, fold_rare(v1, 1, tile - 1, pm1))
@@ -1659,11 +1677,11 @@ __device__ __forceinline__ void knn_score8_body(const unsigned char* __restrict_
     for (int r = 0; r < 16; ++r) { B0[r] = -INFINITY; B1[r] = -INFINITY; }
     int tile = tile_begin;
     for (; tile + 1 < tile_end; tile += 2) {
-        do_tile(tile, A0, A1, B0, B1);
-        do_tile(tile + 1, B0, B1, A0, A1);
+        do_tile(IntC<0>{}, tile, A0, A1, B0, B1);
+        do_tile(IntC<1>{}, tile + 1, B0, B1, A0, A1);
     }
     if (tile < tile_end) {                 // odd count: one more tile into A, then its own fold
-        do_tile(tile, A0, A1, B0, B1);
+        do_tile(IntC<0>{}, tile, A0, A1, B0, B1);
         fold_now(A0, A1, tile);
     } else if (tile_begin < tile_end) {    // even count: the last tile's accumulators are in B
         fold_now(B0, B1, tile_end - 1);
