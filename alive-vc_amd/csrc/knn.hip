@@ -2526,9 +2526,26 @@ __global__ __launch_bounds__(256) void knn_grouped_plan_kernel(const int* __rest
     }
 }
 
+// The element type of a pool's row table (float, or _Float16 for a half pool): four consecutive elements of a row as they lie in
+// memory (16 or 8 bytes, one load) and as the arithmetic takes them.  fp16 -> fp32 is exact, so a kernel on a half table H is
+// bitwise the same kernel on the fp32 table of H's widened values; the float form is the identity and leaves its code as it was.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <typename RT> struct PoolRow;
+template <> struct PoolRow<float> {
+    typedef f32x4 quad;
+    static __device__ __forceinline__ f32x4 widen(f32x4 q) { return q; }
+};
+template <> struct PoolRow<_Float16> {
+    typedef f16x4 quad;
+    static __device__ __forceinline__ f32x4 widen(f16x4 q) { return f32x4{(float)q[0], (float)q[1], (float)q[2], (float)q[3]}; }
+};
+
 // one wave per item (wave-stride loop): the rows of one slab scored against the frames of one chunk, knn_scan_kernel's loop
-__global__ __launch_bounds__(64 * SCAN_WAVES) void knn_grouped_scan_kernel(const float* __restrict__ rows, const float* __restrict__ norms,
+// (RT: PoolRow -- a lane holds elements 4 lane .. 4 lane + 3 of each third of the row whatever their width)
+template <typename RT>
+__global__ __launch_bounds__(64 * SCAN_WAVES) void knn_grouped_scan_kernel(const RT* __restrict__ rows, const float* __restrict__ norms,
                                                                            int T, GroupedWs w) {
+    typedef typename PoolRow<RT>::quad quad;
     const int lane = threadIdx.x & 63;
     const int nw = gridDim.x * SCAN_WAVES;
     const int G = w.hdr[0], items = w.hdr[1];
@@ -2556,18 +2573,18 @@ __global__ __launch_bounds__(64 * SCAN_WAVES) void knn_grouped_scan_kernel(const
         const bool live = lane < nf * k;
         float lv = -INFINITY;
         int li = 0x7fffffff;
-        f32x4 n0 = {}, n1 = {}, n2 = {};
+        quad n0 = {}, n1 = {}, n2 = {};
         float nnx = 1.0f;
         if (r0 < r1) {
-            const f32x4* rp = (const f32x4*)(rows + (size_t)r0 * D);
+            const quad* rp = (const quad*)(rows + (size_t)r0 * D);
             n0 = rp[lane]; n1 = rp[lane + 64]; n2 = rp[lane + 128];
             nnx = norms[r0];
         }
         for (int64_t rr = r0; rr < r1; ++rr) {
-            f32x4 q0 = n0, q1 = n1, q2 = n2;
+            f32x4 q0 = PoolRow<RT>::widen(n0), q1 = PoolRow<RT>::widen(n1), q2 = PoolRow<RT>::widen(n2);
             const float nn = nnx;
             if (rr + 1 < r1) {
-                const f32x4* rp = (const f32x4*)(rows + (size_t)(rr + 1) * D);
+                const quad* rp = (const quad*)(rows + (size_t)(rr + 1) * D);
                 n0 = rp[lane]; n1 = rp[lane + 64]; n2 = rp[lane + 128];
                 nnx = norms[rr + 1];
             }
@@ -2651,10 +2668,11 @@ __global__ __launch_bounds__(256) void knn_grouped_merge_kernel(int T, int k, Gr
 // forms each active list's mean as the one-list form does and sums them weighted, in list order, before the alpha blend.
 // k_rows (with ROWS; alive_knn_merge_gather_rows_k / alive_knn_blend_gather_rows_k): output row n's own k = k_rows[n], its lists
 // (a blend's lists all use their owner's k) read at stride k = k_max; a k_rows[n] outside [1, k_max] passes the row's source through.
-template <int NPER, int KMAX, bool ROWS = false, int LISTS = 1>
+// RT: the row table's element type (float, or _Float16 widened as it is read: PoolRow)
+template <int NPER, int KMAX, bool ROWS = false, int LISTS = 1, typename RT = float>
 __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __restrict__ cand_val,
                                                                const int* __restrict__ cand_idx, int S, int k, float alpha,
-                                                               float one_minus, const float* __restrict__ rows, const float* __restrict__ src,
+                                                               float one_minus, const RT* __restrict__ rows, const float* __restrict__ src,
                                                                int T, int64_t Tt, float* __restrict__ out,
                                                                int* __restrict__ final_idx, const double* __restrict__ alpha_rows = nullptr,
                                                                const int* __restrict__ first = nullptr, const double* __restrict__ weight = nullptr,
@@ -2710,7 +2728,7 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
                     float acc = 0.0f;
                     for (int j = 0; j < k; ++j) {
                         int idx = sel[s][f][j];
-                        float r = (idx >= 0) ? rows[(size_t)idx * D + d0 + lane] : __builtin_nanf("");
+                        float r = (idx >= 0) ? (float)rows[(size_t)idx * D + d0 + lane] : __builtin_nanf("");
                         acc = (j == 0) ? r : acc + r;
                     }
                     const float c = wgt[s] * (acc / (float)k);
@@ -2791,7 +2809,7 @@ __global__ __launch_bounds__(256) void knn_merge_gather_kernel(const float* __re
             float acc = 0.0f;
             for (int j = 0; j < k; ++j) {
                 int idx = sel[0][f][j];
-                float r = (idx >= 0) ? rows[(size_t)idx * D + d0 + lane] : __builtin_nanf("");
+                float r = (idx >= 0) ? (float)rows[(size_t)idx * D + d0 + lane] : __builtin_nanf("");
                 acc = (j == 0) ? r : acc + r;
             }
             tile[f][lane] = acc / (float)k;
@@ -4435,7 +4453,9 @@ extern "C" size_t alive_knn_grouped_workspace_bytes(int N, int T, int k) {
 }
 
 // both grouped entry points: k_row null = every row at k (alive_knn_search_grouped), else k = k_max and row n at k_row[n]
-static int search_grouped(const char* who, const float* src, int N, int T, const float* rows_f32, const float* norms, int64_t P,
+// (RT: the row table's element type -- the _f16 entry points pass _Float16; everything but the scan kernel is shared)
+template <typename RT>
+static int search_grouped(const char* who, const float* src, int N, int T, const RT* rows_f32, const float* norms, int64_t P,
                           const int32_t* seg_lo, const int32_t* seg_len, const int32_t* k_row, int k, float* out_val, int32_t* out_idx,
                           void* ws, void* stream) {
     ALIVE_CHECK_ARG(src && rows_f32 && norms && seg_lo && seg_len && out_val && out_idx && ws, "%s: null pointer", who);
@@ -4448,7 +4468,7 @@ static int search_grouped(const char* who, const float* src, int N, int T, const
     hipStream_t s = (hipStream_t)stream;
     src_prep_small_kernel<<<(unsigned)Tt, 256, 0, s>>>(src, T, Tt, w.s_f32, w.s_bf16, nullptr);
     knn_grouped_plan_kernel<<<1, 256, 0, s>>>(seg_lo, seg_len, k_row, N, T, P, k, w);
-    knn_grouped_scan_kernel<<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, T, w);
+    knn_grouped_scan_kernel<RT><<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, T, w);
     if (k_row != nullptr) knn_grouped_merge_kernel<MERGE_ROW><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
     else if (k <= 4) knn_grouped_merge_kernel<MERGE_K4><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
     else knn_grouped_merge_kernel<MERGE_GEN><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
@@ -4473,16 +4493,33 @@ extern "C" int alive_knn_search_grouped_k(const float* src, int N, int T, const 
                           stream);
 }
 
+// half pool: the row table as fp16 [P][768]; val and idx bitwise those of the fp32 call on the widened table
+extern "C" int alive_knn_search_grouped_f16(const float* src, int N, int T, const void* rows_f16, const float* norms, int64_t P,
+                                            const int32_t* seg_lo, const int32_t* seg_len, int k, float* out_val, int32_t* out_idx,
+                                            void* ws, void* stream) {
+    return search_grouped("alive_knn_search_grouped_f16", src, N, T, (const _Float16*)rows_f16, norms, P, seg_lo, seg_len, nullptr, k, out_val,
+                          out_idx, ws, stream);
+}
+
+extern "C" int alive_knn_search_grouped_k_f16(const float* src, int N, int T, const void* rows_f16, const float* norms, int64_t P,
+                                              const int32_t* seg_lo, const int32_t* seg_len, const int32_t* k_row, int k_max,
+                                              float* out_val, int32_t* out_idx, void* ws, void* stream) {
+    ALIVE_CHECK_ARG(k_row, "alive_knn_search_grouped_k_f16: null pointer");
+    return search_grouped("alive_knn_search_grouped_k_f16", src, N, T, (const _Float16*)rows_f16, norms, P, seg_lo, seg_len, k_row, k_max,
+                          out_val, out_idx, ws, stream);
+}
+
 // both one-shard row gathers: k_row null = every row at k (alive_knn_merge_gather_rows), else lists at stride k = k_max, row n at k_row[n]
+template <typename RT>
 static int merge_gather_rows(const char* who, const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k, const double* alpha,
-                             const float* rows_f32_full, const float* src, int N, int T, float* out, int32_t* final_idx, void* stream) {
+                             const RT* rows_f32_full, const float* src, int N, int T, float* out, int32_t* final_idx, void* stream) {
     ALIVE_CHECK_ARG(cand_val && cand_idx && alpha && rows_f32_full && src && out, "%s: null pointer", who);
     ALIVE_CHECK_ARG(k >= 1 && k <= 8, "%s: k=%d outside [1,8]", who, k);
     ALIVE_CHECK_ARG(N > 0 && T > 0, "%s: empty source", who);
     const int zs = (int64_t)cdiv(T, 32) * N < 64 ? D / 64 : 1;       // as alive_knn_merge_gather
     const dim3 g(cdiv(T, 32), N, zs);
-    knn_merge_gather_kernel<2, 8, true><<<g, 256, 0, (hipStream_t)stream>>>(cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T,
-                                                                         (int64_t)N * T, out, final_idx, alpha, nullptr, nullptr, k_row);
+    knn_merge_gather_kernel<2, 8, true, 1, RT><<<g, 256, 0, (hipStream_t)stream>>>(cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T,
+                                                                                (int64_t)N * T, out, final_idx, alpha, nullptr, nullptr, k_row);
     ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
 }
@@ -4502,17 +4539,33 @@ extern "C" int alive_knn_merge_gather_rows_k(const float* cand_val, const int32_
                              final_idx, stream);
 }
 
+extern "C" int alive_knn_merge_gather_rows_f16(const float* cand_val, const int32_t* cand_idx, int k, const double* alpha,
+                                               const void* rows_f16_full, const float* src, int N, int T, float* out,
+                                               int32_t* final_idx, void* stream) {
+    return merge_gather_rows("alive_knn_merge_gather_rows_f16", cand_val, cand_idx, nullptr, k, alpha, (const _Float16*)rows_f16_full, src, N,
+                             T, out, final_idx, stream);
+}
+
+extern "C" int alive_knn_merge_gather_rows_k_f16(const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k_max,
+                                                 const double* alpha, const void* rows_f16_full, const float* src, int N, int T,
+                                                 float* out, int32_t* final_idx, void* stream) {
+    ALIVE_CHECK_ARG(k_row, "alive_knn_merge_gather_rows_k_f16: null pointer");
+    return merge_gather_rows("alive_knn_merge_gather_rows_k_f16", cand_val, cand_idx, k_row, k_max, alpha, (const _Float16*)rows_f16_full,
+                             src, N, T, out, final_idx, stream);
+}
+
 // Voice blending: output row n mixes the means of its list rows first[n] .. first[n+1]-1 with their weights (the blend form of
 // knn_merge_gather_kernel: same grid forms as alive_knn_merge_gather_rows, a per-list table in LDS).  No allocation, no sync.
+template <typename RT>
 static int blend_gather_rows(const char* who, const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k,
-                             const int32_t* first, const double* weight, const double* alpha, const float* rows_f32_full, const float* src,
+                             const int32_t* first, const double* weight, const double* alpha, const RT* rows_f32_full, const float* src,
                              int N, int T, float* out, void* stream) {
     ALIVE_CHECK_ARG(cand_val && cand_idx && first && weight && alpha && rows_f32_full && src && out, "%s: null pointer", who);
     ALIVE_CHECK_ARG(k >= 1 && k <= 8, "%s: k=%d outside [1,8]", who, k);
     ALIVE_CHECK_ARG(N >= 1 && T >= 1, "%s: N=%d, T=%d: empty source", who, N, T);
     const int zs = (int64_t)cdiv(T, 32) * N < 64 ? D / 64 : 1;       // as alive_knn_merge_gather_rows
     const dim3 g(cdiv(T, 32), N, zs);
-    knn_merge_gather_kernel<2, 8, true, ALIVE_MAX_BLEND><<<g, 256, 0, (hipStream_t)stream>>>(
+    knn_merge_gather_kernel<2, 8, true, ALIVE_MAX_BLEND, RT><<<g, 256, 0, (hipStream_t)stream>>>(
         cand_val, cand_idx, 1, k, 0.0f, 0.0f, rows_f32_full, src, T, (int64_t)N * T, out, nullptr, alpha, first, weight, k_row);
     ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
@@ -4531,6 +4584,21 @@ extern "C" int alive_knn_blend_gather_rows_k(const float* cand_val, const int32_
     ALIVE_CHECK_ARG(k_row, "alive_knn_blend_gather_rows_k: null pointer");
     return blend_gather_rows("alive_knn_blend_gather_rows_k", cand_val, cand_idx, k_row, k_max, first, weight, alpha, rows_f32_full, src, N,
                              T, out, stream);
+}
+
+extern "C" int alive_knn_blend_gather_rows_f16(const float* cand_val, const int32_t* cand_idx, int k, const int32_t* first,
+                                               const double* weight, const double* alpha, const void* rows_f16_full, const float* src,
+                                               int N, int T, float* out, void* stream) {
+    return blend_gather_rows("alive_knn_blend_gather_rows_f16", cand_val, cand_idx, nullptr, k, first, weight, alpha,
+                             (const _Float16*)rows_f16_full, src, N, T, out, stream);
+}
+
+extern "C" int alive_knn_blend_gather_rows_k_f16(const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k_max,
+                                                 const int32_t* first, const double* weight, const double* alpha, const void* rows_f16_full,
+                                                 const float* src, int N, int T, float* out, void* stream) {
+    ALIVE_CHECK_ARG(k_row, "alive_knn_blend_gather_rows_k_f16: null pointer");
+    return blend_gather_rows("alive_knn_blend_gather_rows_k_f16", cand_val, cand_idx, k_row, k_max, first, weight, alpha,
+                             (const _Float16*)rows_f16_full, src, N, T, out, stream);
 }
 
 // ---- pool search (many-to-many batch conversion) ----
@@ -4682,8 +4750,11 @@ __global__ void pool_report_init_kernel(int32_t* __restrict__ report) {
     report[1] = INT32_MAX;
 }
 
+// RT = _Float16 (a half pool): every element is rounded to fp16 first (round to nearest even, subnormals kept, beyond 65504 -> inf)
+// and the norm is taken over the rounded values widened again, in the same order: bitwise the float form on tok.half().float().
+template <typename RT>
 __global__ __launch_bounds__(256) void pool_append_kernel(const float* __restrict__ tok, int64_t rs, int64_t cs, int64_t M, int64_t at,
-                                                          float* __restrict__ rows, float* __restrict__ norms,
+                                                          RT* __restrict__ rows, float* __restrict__ norms,
                                                           int32_t* __restrict__ report) {
     __shared__ float red[4][64];
     __shared__ float tile[64][65];
@@ -4695,6 +4766,7 @@ __global__ __launch_bounds__(256) void pool_append_kernel(const float* __restric
     float ss = 0.0f;
     for (int d = wv; d < D; d += 4) {
         float v = ok ? col[(int64_t)d * rs] : 0.0f;
+        v = (float)(RT)v;                                       // (the identity for float)
         ss = fmaf(v, v, ss);
     }
     red[wv][lane] = ss;
@@ -4712,7 +4784,7 @@ __global__ __launch_bounds__(256) void pool_append_kernel(const float* __restric
         __syncthreads();
         for (int r = wv; r < 64; r += 4) {      // r = token inside the block, lane = feature
             const int64_t mm = m0 + r;
-            if (mm < M) rows[(size_t)(at + mm) * D + d0 + lane] = tile[lane][r];
+            if (mm < M) rows[(size_t)(at + mm) * D + d0 + lane] = (RT)tile[lane][r];
         }
         __syncthreads();
     }
@@ -4761,34 +4833,54 @@ static void pool_move_launch(T* base, int64_t src, int64_t dst, int64_t n, hipSt
     pool_move_kernel<T><<<(unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)), 256, 0, s>>>(base, src, dst, n);
 }
 
-extern "C" int alive_pool_append(const float* tokens, int64_t row_stride, int64_t col_stride, int64_t M, int Dd, float* rows_f32,
-                                 float* norms, int64_t capacity, int64_t at, int32_t* report, void* stream) {
-    ALIVE_CHECK_ARG(tokens && rows_f32 && norms && report, "alive_pool_append: null pointer");
-    ALIVE_CHECK_ARG(Dd == D, "alive_pool_append: feature dim %d, expected %d", Dd, D);
-    ALIVE_CHECK_ARG(capacity >= 1 && capacity < (int64_t)1 << 31, "alive_pool_append: capacity %lld out of range", (long long)capacity);
-    ALIVE_CHECK_ARG(M >= 1 && at >= 0 && M <= capacity && at <= capacity - M,
-                    "alive_pool_append: rows [%lld, +%lld) outside the table of %lld rows", (long long)at, (long long)M, (long long)capacity);
-    ALIVE_CHECK_ARG(row_stride >= 0 && col_stride >= 0, "alive_pool_append: negative stride (%lld, %lld)", (long long)row_stride,
-                    (long long)col_stride);
+// both appends (RT = float: alive_pool_append; _Float16: alive_pool_append_f16, the table as fp16 [capacity][768])
+template <typename RT>
+static int pool_append(const char* who, const float* tokens, int64_t row_stride, int64_t col_stride, int64_t M, int Dd, RT* rows, float* norms,
+                       int64_t capacity, int64_t at, int32_t* report, void* stream) {
+    ALIVE_CHECK_ARG(tokens && rows && norms && report, "%s: null pointer", who);
+    ALIVE_CHECK_ARG(Dd == D, "%s: feature dim %d, expected %d", who, Dd, D);
+    ALIVE_CHECK_ARG(capacity >= 1 && capacity < (int64_t)1 << 31, "%s: capacity %lld out of range", who, (long long)capacity);
+    ALIVE_CHECK_ARG(M >= 1 && at >= 0 && M <= capacity && at <= capacity - M, "%s: rows [%lld, +%lld) outside the table of %lld rows", who,
+                    (long long)at, (long long)M, (long long)capacity);
+    ALIVE_CHECK_ARG(row_stride >= 0 && col_stride >= 0, "%s: negative stride (%lld, %lld)", who, (long long)row_stride, (long long)col_stride);
     hipStream_t s = (hipStream_t)stream;
     pool_report_init_kernel<<<1, 1, 0, s>>>(report);
-    pool_append_kernel<<<(unsigned)((M + 63) / 64), 256, 0, s>>>(tokens, row_stride, col_stride, M, at, rows_f32, norms, report);
-    ALIVE_CHECK_LAUNCH("alive_pool_append");
+    pool_append_kernel<RT><<<(unsigned)((M + 63) / 64), 256, 0, s>>>(tokens, row_stride, col_stride, M, at, rows, norms, report);
+    ALIVE_CHECK_LAUNCH(who);
+    return ALIVE_OK;
+}
+
+extern "C" int alive_pool_append(const float* tokens, int64_t row_stride, int64_t col_stride, int64_t M, int Dd, float* rows_f32,
+                                 float* norms, int64_t capacity, int64_t at, int32_t* report, void* stream) {
+    return pool_append("alive_pool_append", tokens, row_stride, col_stride, M, Dd, rows_f32, norms, capacity, at, report, stream);
+}
+
+extern "C" int alive_pool_append_f16(const float* tokens, int64_t row_stride, int64_t col_stride, int64_t M, int Dd, void* rows_f16,
+                                     float* norms, int64_t capacity, int64_t at, int32_t* report, void* stream) {
+    return pool_append("alive_pool_append_f16", tokens, row_stride, col_stride, M, Dd, (_Float16*)rows_f16, norms, capacity, at, report, stream);
+}
+
+// both movers: a row is `quads` sixteen-byte quads (192 of fp32, 96 of fp16); bytes, not numbers: bitwise by construction
+static int pool_move_rows(const char* who, void* rows, int64_t quads, float* norms, int64_t capacity, int64_t src, int64_t dst, int64_t n,
+                          void* stream) {
+    ALIVE_CHECK_ARG(rows && norms, "%s: null pointer", who);
+    ALIVE_CHECK_ARG(((uintptr_t)rows & 15) == 0, "%s: the row table must be 16-byte aligned", who);
+    ALIVE_CHECK_ARG(capacity >= 1 && capacity < (int64_t)1 << 31, "%s: capacity %lld out of range", who, (long long)capacity);
+    ALIVE_CHECK_ARG(n >= 1 && n <= capacity && src >= 0 && dst >= 0 && src <= capacity - n && dst <= capacity - n,
+                    "%s: %lld rows from %lld to %lld outside the table of %lld rows", who, (long long)n, (long long)src, (long long)dst,
+                    (long long)capacity);
+    if (src == dst) return ALIVE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    pool_move_launch<pool_u32x4>((pool_u32x4*)rows, src * quads, dst * quads, n * quads, s);
+    pool_move_launch<unsigned int>((unsigned int*)norms, src, dst, n, s);
+    ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
 }
 
 extern "C" int alive_pool_move_rows(float* rows_f32, float* norms, int64_t capacity, int64_t src, int64_t dst, int64_t n, void* stream) {
-    ALIVE_CHECK_ARG(rows_f32 && norms, "alive_pool_move_rows: null pointer");
-    ALIVE_CHECK_ARG(((uintptr_t)rows_f32 & 15) == 0, "alive_pool_move_rows: the row table must be 16-byte aligned");
-    ALIVE_CHECK_ARG(capacity >= 1 && capacity < (int64_t)1 << 31, "alive_pool_move_rows: capacity %lld out of range", (long long)capacity);
-    ALIVE_CHECK_ARG(n >= 1 && n <= capacity && src >= 0 && dst >= 0 && src <= capacity - n && dst <= capacity - n,
-                    "alive_pool_move_rows: %lld rows from %lld to %lld outside the table of %lld rows", (long long)n, (long long)src,
-                    (long long)dst, (long long)capacity);
-    if (src == dst) return ALIVE_OK;
-    hipStream_t s = (hipStream_t)stream;
-    constexpr int64_t Q = D / 4;                                 // a row is 192 quads
-    pool_move_launch<pool_u32x4>((pool_u32x4*)rows_f32, src * Q, dst * Q, n * Q, s);      // bytes, not floats: bitwise by construction
-    pool_move_launch<unsigned int>((unsigned int*)norms, src, dst, n, s);
-    ALIVE_CHECK_LAUNCH("alive_pool_move_rows");
-    return ALIVE_OK;
+    return pool_move_rows("alive_pool_move_rows", rows_f32, D / 4, norms, capacity, src, dst, n, stream);
+}
+
+extern "C" int alive_pool_move_rows_f16(void* rows_f16, float* norms, int64_t capacity, int64_t src, int64_t dst, int64_t n, void* stream) {
+    return pool_move_rows("alive_pool_move_rows_f16", rows_f16, D / 8, norms, capacity, src, dst, n, stream);
 }

@@ -51,8 +51,11 @@ __device__ __forceinline__ bool frame_active(const int32_t* __restrict__ ix, int
     return ok;
 }
 
+// RT: the row table's element type (float, or _Float16 of a half pool widened as it is read -- exact, so the dots are those of the
+// fp32 table of the widened values)
+template <typename RT>
 __global__ __launch_bounds__(64 * KP) void path_join_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ k_row, int k_max,
-                                                            const int32_t* __restrict__ on, const float* __restrict__ rows,
+                                                            const int32_t* __restrict__ on, const RT* __restrict__ rows,
                                                             const float* __restrict__ norms, int64_t P, int T, double* __restrict__ J) {
     __shared__ float prev[KP][D];
     const int r = blockIdx.x / (T - 1), t = blockIdx.x % (T - 1) + 1;
@@ -64,15 +67,15 @@ __global__ __launch_bounds__(64 * KP) void path_join_kernel(const int32_t* __res
     const int mine = wave < K ? it[wave] : -1;              // state `wave` of frame t (< P: the frame is active)
     const int theirs = wave < K ? it[wave - k_max] : -1;    // state `wave` of frame t - 1
     if (theirs >= 0) {
-        const float* y = rows + (size_t)theirs * D;
+        const RT* y = rows + (size_t)theirs * D;
 #pragma unroll
-        for (int q = 0; q < QS; ++q) prev[wave][lane + 64 * q] = y[lane + 64 * q];
+        for (int q = 0; q < QS; ++q) prev[wave][lane + 64 * q] = (float)y[lane + 64 * q];
     }
     float x[QS];
     if (mine >= 0) {
-        const float* xr = rows + (size_t)mine * D;
+        const RT* xr = rows + (size_t)mine * D;
 #pragma unroll
-        for (int q = 0; q < QS; ++q) x[q] = xr[lane + 64 * q];
+        for (int q = 0; q < QS; ++q) x[q] = (float)xr[lane + 64 * q];
     }
     __syncthreads();
     if (mine < 0) return;
@@ -205,28 +208,46 @@ extern "C" size_t alive_knn_path_workspace_bytes(int R, int T, int k_max) {
     return align_up((size_t)R * T * k_max * k_max * sizeof(double), 256) + align_up((size_t)R * T * k_max, 256);
 }
 
-extern "C" int alive_knn_path_rows(const float* val, const int32_t* idx, const int32_t* k_row, int k_max, const int32_t* on,
-                                   const double* weight, const float* rows_f32, const float* norms, int64_t P, int R, int T,
-                                   float* out_val, int32_t* out_idx, int32_t* moved, void* ws, void* stream) {
-    ALIVE_CHECK_ARG(val && idx && out_val && out_idx, "alive_knn_path_rows: null lists");
-    ALIVE_CHECK_ARG(k_row && on && weight && moved, "alive_knn_path_rows: null per-row array");
-    ALIVE_CHECK_ARG(rows_f32 && norms && ws, "alive_knn_path_rows: null pointer");
-    ALIVE_CHECK_ARG(k_max >= 1 && k_max <= ALIVE_KNN_PATH_MAX_K, "alive_knn_path_rows: k_max %d outside [1, %d]", k_max,
-                    ALIVE_KNN_PATH_MAX_K);
-    ALIVE_CHECK_ARG(R >= 1 && T >= 1, "alive_knn_path_rows: empty lists");
-    ALIVE_CHECK_ARG((int64_t)R * T <= ALIVE_KNN_PATH_MAX_FRAMES, "alive_knn_path_rows: R * T = %lld exceeds 2^20 frames",
-                    (long long)R * T);
-    ALIVE_CHECK_ARG(P > 0 && P <= 0x7fffffffLL, "alive_knn_path_rows: P outside [1, 2^31)");
-    ALIVE_CHECK_ARG(val != out_val && idx != out_idx, "alive_knn_path_rows: the output lists must not be the input lists");
+namespace {
+
+// both entry points (RT = float: alive_knn_path_rows; _Float16: alive_knn_path_rows_f16)
+template <typename RT>
+int path_rows(const char* who, const float* val, const int32_t* idx, const int32_t* k_row, int k_max, const int32_t* on, const double* weight,
+              const RT* rows, const float* norms, int64_t P, int R, int T, float* out_val, int32_t* out_idx, int32_t* moved, void* ws,
+              void* stream) {
+    ALIVE_CHECK_ARG(val && idx && out_val && out_idx, "%s: null lists", who);
+    ALIVE_CHECK_ARG(k_row && on && weight && moved, "%s: null per-row array", who);
+    ALIVE_CHECK_ARG(rows && norms && ws, "%s: null pointer", who);
+    ALIVE_CHECK_ARG(k_max >= 1 && k_max <= ALIVE_KNN_PATH_MAX_K, "%s: k_max %d outside [1, %d]", who, k_max, ALIVE_KNN_PATH_MAX_K);
+    ALIVE_CHECK_ARG(R >= 1 && T >= 1, "%s: empty lists", who);
+    ALIVE_CHECK_ARG((int64_t)R * T <= ALIVE_KNN_PATH_MAX_FRAMES, "%s: R * T = %lld exceeds 2^20 frames", who, (long long)R * T);
+    ALIVE_CHECK_ARG(P > 0 && P <= 0x7fffffffLL, "%s: P outside [1, 2^31)", who);
+    ALIVE_CHECK_ARG(val != out_val && idx != out_idx, "%s: the output lists must not be the input lists", who);
     int64_t off[2];
     alive_knn_path_layout(R, T, k_max, off);
     double* J = (double*)((char*)ws + off[0]);
     unsigned char* back = (unsigned char*)ws + off[1];
     if (T > 1) {                                            // (a one-frame list has no join: one launch)
-        path_join_kernel<<<R * (T - 1), 64 * k_max, 0, (hipStream_t)stream>>>(idx, k_row, k_max, on, rows_f32, norms, P, T, J);
-        ALIVE_CHECK_LAUNCH("alive_knn_path_rows (join)");
+        path_join_kernel<RT><<<R * (T - 1), 64 * k_max, 0, (hipStream_t)stream>>>(idx, k_row, k_max, on, rows, norms, P, T, J);
+        ALIVE_CHECK_LAUNCH(who);
     }
     path_kernel<<<R, 64, 0, (hipStream_t)stream>>>(val, idx, k_row, k_max, on, weight, P, T, J, out_val, out_idx, moved, back);
-    ALIVE_CHECK_LAUNCH("alive_knn_path_rows (path)");
+    ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
+}
+
+}  // namespace
+
+extern "C" int alive_knn_path_rows(const float* val, const int32_t* idx, const int32_t* k_row, int k_max, const int32_t* on,
+                                   const double* weight, const float* rows_f32, const float* norms, int64_t P, int R, int T,
+                                   float* out_val, int32_t* out_idx, int32_t* moved, void* ws, void* stream) {
+    return path_rows("alive_knn_path_rows", val, idx, k_row, k_max, on, weight, rows_f32, norms, P, R, T, out_val, out_idx, moved, ws, stream);
+}
+
+// half pool: the row table as fp16 [P][768]; bitwise alive_knn_path_rows on the widened table
+extern "C" int alive_knn_path_rows_f16(const float* val, const int32_t* idx, const int32_t* k_row, int k_max, const int32_t* on,
+                                       const double* weight, const void* rows_f16, const float* norms, int64_t P, int R, int T,
+                                       float* out_val, int32_t* out_idx, int32_t* moved, void* ws, void* stream) {
+    return path_rows("alive_knn_path_rows_f16", val, idx, k_row, k_max, on, weight, (const _Float16*)rows_f16, norms, P, R, T, out_val, out_idx,
+                     moved, ws, stream);
 }

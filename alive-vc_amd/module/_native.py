@@ -121,6 +121,16 @@ PROTOTYPES = {
     "alive_knn_blend_gather_rows_k": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
     "alive_pool_append": (_I, [_VP, _I64, _I64, _I64, _I, _VP, _VP, _I64, _I64, _VP, _VP]),
     "alive_pool_move_rows": (_I, [_VP, _VP, _I64, _I64, _I64, _I64, _VP]),
+    # half pool: the fp32 twins' signatures, the row table as fp16 [P][768]
+    "alive_pool_append_f16": (_I, [_VP, _I64, _I64, _I64, _I, _VP, _VP, _I64, _I64, _VP, _VP]),
+    "alive_pool_move_rows_f16": (_I, [_VP, _VP, _I64, _I64, _I64, _I64, _VP]),
+    "alive_knn_search_grouped_f16": (_I, [_VP, _I, _I, _VP, _VP, _I64, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "alive_knn_search_grouped_k_f16": (_I, [_VP, _I, _I, _VP, _VP, _I64, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "alive_knn_merge_gather_rows_f16": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP]),
+    "alive_knn_merge_gather_rows_k_f16": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP]),
+    "alive_knn_blend_gather_rows_f16": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
+    "alive_knn_blend_gather_rows_k_f16": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP]),
+    "alive_knn_path_rows_f16": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I64, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "alive_pool_image_bytes": (_SZ, [_VP, _I, _VP]),
     "alive_pool_pack_images": (_I, [_VP, _VP, _I64, _VP, _VP, _I, _VP, _VP, _VP]),
     "alive_knn_pool_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I64, _I64]),

@@ -493,6 +493,26 @@ class Register(tuple):
         return self[0], self[1], self.sumsq
 
 
+POOL_DTYPES = {"fp32": torch.float32, "fp16": torch.float16}     # (the names of --pool-dtype)
+
+
+def pool_dtype(dtype):
+    """the element type of a pool's row table: torch.float32 or torch.float16 (or their names "fp32" / "fp16"); ValueError otherwise"""
+    dtype = POOL_DTYPES.get(dtype, dtype) if isinstance(dtype, str) else dtype
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"a voice pool stores torch.float32 or torch.float16 rows, got dtype={dtype!r}")
+    return dtype
+
+
+def _rows_call(name, rows):
+    """the entry point `name` for a row table of rows.dtype: itself for fp32, its _f16 twin for fp16; ValueError for any other dtype"""
+    if rows.dtype == torch.float32:
+        return getattr(nat.lib(), name), name
+    if rows.dtype == torch.float16:
+        return getattr(nat.lib(), name + "_f16"), name + "_f16"
+    raise ValueError(f"{name}: the row table must be torch.float32 or torch.float16, got {rows.dtype}")
+
+
 class VoicePool:
     """Named voices tokens[768, M] packed into one fp32 row table rows[P, 768] with norms[P] (the norms bitwise those of
     PackedLibrary) and a name -> (seg_lo, M) map.
@@ -523,10 +543,19 @@ class VoicePool:
     Ranges (pitch range): beside its register a voice may carry the sum of its squared voiced pitch (`ranges`), from which
     `pitch_range(name)` is the standard deviation in semitones.  A register given as (sum, count, sumsq) -- or as the Register that
     measure_register returns -- carries it, a 2-tuple does not; a voice keeps a range only while every piece merged into its
-    register brought one.  It travels and goes with the register."""
+    register brought one.  It travels and goes with the register.
 
-    def __init__(self, voices=None, device="cuda", capacity=None, registers=None):
+    Half pool (dtype=torch.float16, either kind): `rows` is fp16 [P, 768] -- 1536 bytes per row (`row_bytes`) instead of 3072 -- and
+    `norms` stays fp32.  Every token element is rounded to fp16 on the way in (alive_pool_append_f16: round to nearest even; a row
+    with an element beyond fp16's range, or one that rounds to all zeros, is refused like any row without a usable norm), and the
+    norms are those of the rounded rows.  fp16 -> fp32 is exact and the kernels widen in registers, so the streaming search, the
+    gathers and the match path on a half pool are bitwise what they are on an fp32 pool of `tokens.half().float()`.  `tokens(name)`
+    returns the rounded tokens as fp32.  The offline pool search (`search_images`, `voice_ids`: Converter.convert_many) rescans fp32
+    rows and refuses a half pool."""
+
+    def __init__(self, voices=None, device="cuda", capacity=None, registers=None, dtype=torch.float32):
         self.device = torch.device(device)
+        self.dtype = pool_dtype(dtype)
         self.segments = {}
         self.registers = {}                    # name -> (sum of voiced pitch, voiced frames), host floats
         self.ranges = {}                       # name -> sum of squared voiced pitch, for the voices that carry a second moment
@@ -537,7 +566,7 @@ class VoicePool:
             self._alloc = RowAllocator(capacity)
             self.capacity = self.P = self._alloc.capacity
             self.segments = self._alloc.segments
-            self.rows = torch.empty(self.P, DIM, dtype=torch.float32, device=self.device)
+            self.rows = torch.empty(self.P, DIM, dtype=self.dtype, device=self.device)
             self.norms = torch.empty(self.P, dtype=torch.float32, device=self.device)
             self._report = torch.zeros(2, dtype=torch.int32, device=self.device)
             self.mutations = 0                 # every operation; `order` is the event recorded after the latest one
@@ -548,12 +577,24 @@ class VoicePool:
         self._tokens = {}
         self.rows = self.norms = None
         self.P = 0
+        if self.dtype == torch.float16:                        # (a default half pool packs through the half append)
+            self._report = torch.zeros(2, dtype=torch.int32, device=self.device)
         if voices:
             for name, tok in voices.items():
                 self._tokens[str(name)] = _tokens_2d(tok).to(self.device, torch.float32).contiguous()
             self._pack()
             for name, reg in (registers or {}).items():
                 self.set_register(str(name), register=reg)
+
+    @property
+    def row_bytes(self):
+        """bytes one row of the table takes: 3072 (fp32) or 1536 (fp16)"""
+        return DIM * self.rows.element_size() if self.rows is not None else DIM * torch.empty(0, dtype=self.dtype).element_size()
+
+    def _need_f32(self, what):
+        if self.dtype != torch.float32:
+            raise ValueError(f"{what} needs an fp32 voice pool and this one stores {self.dtype} rows: the offline pool search rescans "
+                             "fp32 rows (a half pool serves MultiStreamConverter)")
 
     # ------------------------------------------------------------------ registers (auto pitch)
     @staticmethod
@@ -696,22 +737,27 @@ class VoicePool:
     def _append(self, at, parts):
         """pack the parts at consecutive rows from `at` (the rows are the caller's to write); ValueError if a new row's norm is zero
         or not finite -- read from the device's two-word report, not from the norms"""
-        L = nat.lib()
         for t in parts:
-            if t.device != self.device or t.dtype != torch.float32:
-                t = t.to(self.device, torch.float32)
             m = int(t.shape[1])
-            nat.check(L.alive_pool_append(t.data_ptr(), t.stride(0), t.stride(1), m, DIM, nat.ptr(self.rows), nat.ptr(self.norms),
-                                          self.P, at, nat.ptr(self._report), nat.stream()), "alive_pool_append")
-            bad, first = self._report.tolist()
-            if bad:
-                raise ValueError(f"voice pool row {first} has zero or non-finite norm ({bad} such row(s) among the new ones): "
-                                 "remove it")
+            self._append_into(self.rows, self.norms, self.P, at, t)
             at += m
 
+    def _append_into(self, rows, norms, P, at, t):
+        """one part t [768, m] packed at rows [at, at + m) of a table of this pool's dtype (alive_pool_append / _f16)"""
+        if t.device != self.device or t.dtype != torch.float32:
+            t = t.to(self.device, torch.float32)
+        half = self.dtype == torch.float16
+        name = "alive_pool_append_f16" if half else "alive_pool_append"
+        nat.check(getattr(nat.lib(), name)(t.data_ptr(), t.stride(0), t.stride(1), int(t.shape[1]), DIM, nat.ptr(rows), nat.ptr(norms),
+                                           P, at, nat.ptr(self._report), nat.stream()), name)
+        bad, first = self._report.tolist()
+        if bad:
+            raise ValueError(f"voice pool row {first} has zero or non-finite norm ({bad} such row(s) among the new ones): "
+                             "remove it" + (" (as fp16: an element beyond 65504 is inf, a tiny row rounds to zero)" if half else ""))
+
     def _move(self, src, dst, n):
-        nat.check(nat.lib().alive_pool_move_rows(nat.ptr(self.rows), nat.ptr(self.norms), self.P, src, dst, n, nat.stream()),
-                  "alive_pool_move_rows")
+        name = "alive_pool_move_rows_f16" if self.dtype == torch.float16 else "alive_pool_move_rows"
+        nat.check(getattr(nat.lib(), name)(nat.ptr(self.rows), nat.ptr(self.norms), self.P, src, dst, n, nat.stream()), name)
 
     def extend(self, name, tokens, register=None):
         """append rows to a live voice (old rows first): in place when the hole behind it is large enough, else the voice moves to
@@ -782,8 +828,11 @@ class VoicePool:
         return self._alloc.largest_hole
 
     def tokens(self, name):
-        """the voice's tokens [768, M], bitwise those that went in (a reserved pool keeps no copy: rebuilt from its rows)"""
+        """the voice's tokens [768, M], bitwise those that went in (a reserved pool keeps no copy: rebuilt from its rows); of a half
+        pool the rounded tokens, widened to fp32: what was stored"""
         lo, m = self.segment(name)
+        if self.dtype != torch.float32:
+            return self.rows[lo:lo + m].float().t().contiguous()
         if self.capacity is None:
             return self._tokens[name]
         return self.rows[lo:lo + m].t().contiguous()
@@ -796,19 +845,22 @@ class VoicePool:
     def _pack(self):
         L = nat.lib()
         P = sum(int(t.shape[1]) for t in self._tokens.values())
-        rows = torch.empty(P, DIM, dtype=torch.float32, device=self.device)
+        rows = torch.empty(P, DIM, dtype=self.dtype, device=self.device)
         norms = torch.empty(P, dtype=torch.float32, device=self.device)
+        if P >= 2 ** 31:
+            raise ValueError(f"a voice pool holds fewer than 2^31 rows (got {P})")
         segs, lo = {}, 0
         for name, t in self._tokens.items():
             m = int(t.shape[1])
             if m < 1:
                 raise ValueError(f"voice {name!r} is empty")
-            nat.check(L.alive_library_pack_rows(nat.ptr(t), m, DIM, rows[lo].data_ptr(), norms[lo].data_ptr(), nat.stream()),
-                      "alive_library_pack_rows")
+            if self.dtype == torch.float16:                   # the half append: the bits a reserved half pool holds
+                self._append_into(rows, norms, P, lo, t)
+            else:
+                nat.check(L.alive_library_pack_rows(nat.ptr(t), m, DIM, rows[lo].data_ptr(), norms[lo].data_ptr(), nat.stream()),
+                          "alive_library_pack_rows")
             segs[name] = (lo, m)
             lo += m
-        if P >= 2 ** 31:
-            raise ValueError(f"a voice pool holds fewer than 2^31 rows (got {P})")
         bad = ~(torch.isfinite(norms) & (norms > 0))          # as PackedLibrary: a zero-norm row would match every frame
         if bool(bad.any()):
             raise ValueError(f"voice pool row {int(torch.nonzero(bad)[0])} has zero or non-finite norm: remove it")
@@ -821,6 +873,7 @@ class VoicePool:
         passes its live voices only, with P its capacity):
         a dict of the bf16 image buffer, device int64 img_off [V], int32 seg_lo / seg_len [V], float32 bounds [V] (the
         deterministic certificate's per-voice rounding bound), the voice names in table order, and the longest voice."""
+        self._need_f32("VoicePool.search_images")
         if self._images is not None:
             return self._images
         L = nat.lib()
@@ -846,6 +899,7 @@ class VoicePool:
 
     def voice_ids(self, names):
         """voice names (None: an inactive row) -> device int32 [N] indices of the pool search's table"""
+        self._need_f32("VoicePool.voice_ids")
         index = self.search_images()["index"]
         ids = []
         for n in names:
@@ -1002,7 +1056,8 @@ def enrol_voice(pool, name, content_encoder, wav, sr, lib=None, every=4, max_fra
 
 
 def knn_search_grouped(source, rows, norms, seg_lo, seg_len, k):
-    """source [N, 768, T], pool rows / norms, device int32 seg_lo / seg_len [N] -> (val [N*T, k], idx [N*T, k] pool indices)"""
+    """source [N, 768, T], pool rows (fp32, or the fp16 rows of a half pool: alive_knn_search_grouped_f16) / norms, device int32
+    seg_lo / seg_len [N] -> (val [N*T, k], idx [N*T, k] pool indices)"""
     n, d, t = source.shape
     L = nat.lib()
     if not 1 <= k <= MAX_K:
@@ -1010,12 +1065,12 @@ def knn_search_grouped(source, rows, norms, seg_lo, seg_len, k):
     nbytes = L.alive_knn_grouped_workspace_bytes(n, t, k)
     if nbytes == 0:                                         # (before anything is allocated)
         raise ValueError(f"grouped search: {n} rows x {t} frames (k={k}) out of range")
+    fn, name = _rows_call("alive_knn_search_grouped", rows)
     val = torch.empty(n * t, k, dtype=torch.float32, device=source.device)
     idx = torch.empty(n * t, k, dtype=torch.int32, device=source.device)
     ws = _ws.get(nbytes, source.device)
-    nat.check(L.alive_knn_search_grouped(nat.ptr(source), n, t, nat.ptr(rows), nat.ptr(norms), rows.shape[0], nat.ptr(seg_lo),
-                                         nat.ptr(seg_len), k, nat.ptr(val), nat.ptr(idx), nat.ptr(ws), nat.stream()),
-              "alive_knn_search_grouped")
+    nat.check(fn(nat.ptr(source), n, t, nat.ptr(rows), nat.ptr(norms), rows.shape[0], nat.ptr(seg_lo), nat.ptr(seg_len), k, nat.ptr(val),
+                 nat.ptr(idx), nat.ptr(ws), nat.stream()), name)
     return val, idx
 
 
@@ -1031,12 +1086,12 @@ def knn_search_grouped_k(source, rows, norms, seg_lo, seg_len, k_row, k_max):
     nbytes = L.alive_knn_grouped_k_workspace_bytes(n, t, k_max)
     if nbytes == 0:                                         # (before anything is allocated)
         raise ValueError(f"grouped search: {n} rows x {t} frames (k_max={k_max}) out of range")
+    fn, name = _rows_call("alive_knn_search_grouped_k", rows)
     val = torch.empty(n * t, k_max, dtype=torch.float32, device=source.device)
     idx = torch.empty(n * t, k_max, dtype=torch.int32, device=source.device)
     ws = _ws.get(nbytes, source.device)
-    nat.check(L.alive_knn_search_grouped_k(nat.ptr(source), n, t, nat.ptr(rows), nat.ptr(norms), rows.shape[0], nat.ptr(seg_lo),
-                                           nat.ptr(seg_len), nat.ptr(k_row), k_max, nat.ptr(val), nat.ptr(idx), nat.ptr(ws),
-                                           nat.stream()), "alive_knn_search_grouped_k")
+    nat.check(fn(nat.ptr(source), n, t, nat.ptr(rows), nat.ptr(norms), rows.shape[0], nat.ptr(seg_lo), nat.ptr(seg_len), nat.ptr(k_row),
+                 k_max, nat.ptr(val), nat.ptr(idx), nat.ptr(ws), nat.stream()), name)
     return val, idx
 
 
@@ -1102,10 +1157,10 @@ def knn_search_pool_k(source, pool, voice_ids, k_row, k_max):
 def merge_gather_rows_k(val, idx, k_row, k_max, alpha, rows, source):
     """merge_gather_rows with a k per row (device int32 k_row [N]); val / idx [N*T, k_max] from a per-row-k search"""
     n, d, t = source.shape
+    fn, name = _rows_call("alive_knn_merge_gather_rows_k", rows)
     out = torch.empty_like(source)
-    nat.check(nat.lib().alive_knn_merge_gather_rows_k(nat.ptr(val), nat.ptr(idx), nat.ptr(k_row), k_max, nat.ptr(alpha), nat.ptr(rows),
-                                                      nat.ptr(source), n, t, nat.ptr(out), None, nat.stream()),
-              "alive_knn_merge_gather_rows_k")
+    nat.check(fn(nat.ptr(val), nat.ptr(idx), nat.ptr(k_row), k_max, nat.ptr(alpha), nat.ptr(rows), nat.ptr(source), n, t, nat.ptr(out),
+                 None, nat.stream()), name)
     return out
 
 
@@ -1113,10 +1168,10 @@ def blend_gather_rows_k(val, idx, k_row, k_max, first, weight, alpha, rows, sour
     """blend_gather_rows with a k per OUTPUT row (device int32 k_row [N]): every list of a blend uses its owner's k; val / idx
     [first[N] * T, k_max] from a per-row-k search whose k_row repeats the owner's k on each of its list rows"""
     n, d, t = source.shape
+    fn, name = _rows_call("alive_knn_blend_gather_rows_k", rows)
     out = torch.empty_like(source)
-    nat.check(nat.lib().alive_knn_blend_gather_rows_k(nat.ptr(val), nat.ptr(idx), nat.ptr(k_row), k_max, nat.ptr(first),
-                                                      nat.ptr(weight), nat.ptr(alpha), nat.ptr(rows), nat.ptr(source), n, t,
-                                                      nat.ptr(out), nat.stream()), "alive_knn_blend_gather_rows_k")
+    nat.check(fn(nat.ptr(val), nat.ptr(idx), nat.ptr(k_row), k_max, nat.ptr(first), nat.ptr(weight), nat.ptr(alpha), nat.ptr(rows),
+                 nat.ptr(source), n, t, nat.ptr(out), nat.stream()), name)
     return out
 
 
@@ -1133,9 +1188,10 @@ def check_k(k, what="k", hi=MAX_K):
 def merge_gather_rows(val, idx, k, alpha, rows, source):
     """merge_gather with one shard and a per-window alpha (device float64 [N])"""
     n, d, t = source.shape
+    fn, name = _rows_call("alive_knn_merge_gather_rows", rows)
     out = torch.empty_like(source)
-    nat.check(nat.lib().alive_knn_merge_gather_rows(nat.ptr(val), nat.ptr(idx), k, nat.ptr(alpha), nat.ptr(rows), nat.ptr(source),
-                                                    n, t, nat.ptr(out), None, nat.stream()), "alive_knn_merge_gather_rows")
+    nat.check(fn(nat.ptr(val), nat.ptr(idx), k, nat.ptr(alpha), nat.ptr(rows), nat.ptr(source), n, t, nat.ptr(out), None, nat.stream()),
+              name)
     return out
 
 
@@ -1144,10 +1200,10 @@ def blend_gather_rows(val, idx, k, first, weight, alpha, rows, source):
     weight: device float64 [first[N]]; val / idx: [first[N] * T, k] from a grouped or pool search of the list rows), then the
     per-row alpha (device float64 [N]) as merge_gather_rows (csrc/knn.hip: alive_knn_blend_gather_rows)"""
     n, d, t = source.shape
+    fn, name = _rows_call("alive_knn_blend_gather_rows", rows)
     out = torch.empty_like(source)
-    nat.check(nat.lib().alive_knn_blend_gather_rows(nat.ptr(val), nat.ptr(idx), k, nat.ptr(first), nat.ptr(weight), nat.ptr(alpha),
-                                                    nat.ptr(rows), nat.ptr(source), n, t, nat.ptr(out), nat.stream()),
-              "alive_knn_blend_gather_rows")
+    nat.check(fn(nat.ptr(val), nat.ptr(idx), k, nat.ptr(first), nat.ptr(weight), nat.ptr(alpha), nat.ptr(rows), nat.ptr(source), n, t,
+                 nat.ptr(out), nat.stream()), name)
     return out
 
 

@@ -315,7 +315,7 @@ def knn_path_rows(val, idx, k_row, k_max, on, weight, rows, norms, moved=None):
     """alive_knn_path_rows: top-k lists val fp32 / idx int32 [R * T, k_max] (R = len(k_row) list rows of T frames, as every search form
     returns them) -> (out_val, out_idx) of the same shape with ONE entry per frame, the path's (csrc/match_path.hip), ready for any
     gather at k = 1.  k_row, on: device int32 [R]; weight: device float64 [R]; moved: device int32 [R] or None (allocated), returned
-    third.  rows fp32 [P, 768] / norms fp32 [P]: the table the indices point into.  No host synchronisation and no allocation beyond
+    third.  rows fp32 (or fp16, a half pool's: alive_knn_path_rows_f16) [P, 768] / norms fp32 [P]: the table the indices point into.  No host synchronisation and no allocation beyond
     the outputs once the stream's workspace exists: capturable."""
     if val.dtype != torch.float32 or idx.dtype != torch.int32 or val.dim() != 2 or val.shape != idx.shape or val.shape[1] != int(k_max):
         raise ValueError(f"match path: lists must be fp32 / int32 [R * T, {k_max}] tensors, got {tuple(val.shape)} / {tuple(idx.shape)}")
@@ -331,14 +331,17 @@ def knn_path_rows(val, idx, k_row, k_max, on, weight, rows, norms, moved=None):
                            ("moved", moved, torch.int32)):
         if not torch.is_tensor(v) or v.dtype != dtype or v.numel() != r or not v.is_contiguous():
             raise ValueError(f"match path: {name} must be a contiguous {dtype} [{r}] device array")
-    if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != 768 or norms.dtype != torch.float32 or norms.numel() != rows.shape[0]:
+    if rows.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"match path: the row table must be torch.float32 or torch.float16, got {rows.dtype}")
+    if rows.dim() != 2 or rows.shape[1] != 768 or norms.dtype != torch.float32 or norms.numel() != rows.shape[0]:
         raise ValueError(f"match path: rows must be fp32 [P, 768] with norms fp32 [P], got {tuple(rows.shape)} / {tuple(norms.shape)}")
     L = nat.lib()
+    name = "alive_knn_path_rows" if rows.dtype == torch.float32 else "alive_knn_path_rows_f16"
     out_val, out_idx = torch.empty_like(val), torch.empty_like(idx)
     ws = _path_ws.get(L.alive_knn_path_workspace_bytes(r, t, int(k_max)), val.device)
-    nat.check(L.alive_knn_path_rows(nat.ptr(val), nat.ptr(idx), nat.ptr(k_row), int(k_max), nat.ptr(on), nat.ptr(weight), nat.ptr(rows),
-                                    nat.ptr(norms), int(rows.shape[0]), r, t, nat.ptr(out_val), nat.ptr(out_idx), nat.ptr(moved),
-                                    nat.ptr(ws), nat.stream()), "alive_knn_path_rows")
+    nat.check(getattr(L, name)(nat.ptr(val), nat.ptr(idx), nat.ptr(k_row), int(k_max), nat.ptr(on), nat.ptr(weight), nat.ptr(rows),
+                               nat.ptr(norms), int(rows.shape[0]), r, t, nat.ptr(out_val), nat.ptr(out_idx), nat.ptr(moved), nat.ptr(ws),
+                               nat.stream()), name)
     return out_val, out_idx, moved
 
 

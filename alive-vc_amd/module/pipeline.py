@@ -487,6 +487,8 @@ class Converter:
         trim_context the match covers the whole windows and trimming applies to the decoder alone.  A row's path depends on its own
         lists only; a corpus without such an utterance launches the present path."""
         from . import multistream as MS
+        if getattr(pool, "dtype", torch.float32) != torch.float32:         # (a half pool: the pool search rescans fp32 rows)
+            pool._need_f32(f"{type(self).__name__}.convert_many")
         m = len(utterances)
         voices = list(voices)
         if len(voices) != m:

@@ -117,6 +117,10 @@ run) and removed after the last session on it closes, so N need only cover the v
 enrolments, the removals and the peak).  The pool is compacted when a voice fits its free rows but none of its holes; a voice
 that does not fit ends the run with the pool's `add` error before any audio is written.  The outputs are byte for byte those
 without the flag.
+
+--pool-dtype fp16: the pool stores its rows in half precision (VoicePool(dtype=torch.float16); 1536 bytes per row instead of 3072),
+with or without --pool-rows; the sessions file is the same.  Every voice's tokens are rounded to fp16 as they are enrolled, and the
+run writes byte for byte what an fp32 pool of the rounded tokens writes.  Default fp32: the pool and the run are what they were.
 """
 import argparse
 import json
@@ -132,7 +136,7 @@ from module import audio_io, common                             # noqa: E402
 from module.content_encoder import ContentEncoder                # noqa: E402
 from module.decoder import Decoder                               # noqa: E402
 from module.f0_estimator import F0Estimator                      # noqa: E402
-from module.multistream import (MultiStreamConverter, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
+from module.multistream import (MultiStreamConverter, POOL_DTYPES, VoicePool, blend_sources, check_k, enrol_voice,   # noqa: E402
                                 check_conceal_ms, check_crossfade_ms, check_envelope, check_intonation, check_limit, check_post_filter,
                                 check_loudness, check_loudness_stream,
                                 gate_hold_ticks, gate_thr_ms, measure_register)
@@ -175,6 +179,9 @@ def build_parser():
     parser.add_argument('--pool-rows', default=None, type=int,
                         help="a reserved voice pool of this many rows: voices are enrolled at the first tick that needs them and "
                              "removed after their last session (default: every voice is packed before tick 0)")
+    parser.add_argument('--pool-dtype', default="fp32", choices=sorted(POOL_DTYPES),
+                        help="the element type of the pool's row table: fp16 halves its bytes, the tokens are rounded as they are "
+                             "enrolled (default fp32)")
     parser.add_argument('--auto-pitch', action='store_true',
                         help="sessions follow their target voice's register unless their \"auto_pitch\" says otherwise")
     parser.add_argument('-int', '--intonation', default=1.0, type=float,
@@ -752,6 +759,11 @@ def run(conv, pcms, starts, chunk, params, before=None, after=None, stalls=None,
     return [np.concatenate(o) if o else np.zeros(0, np.int16) for o in outs]
 
 
+def make_pool(args, device):
+    """the run's (still empty) voice pool: reserved under --pool-rows, of --pool-dtype"""
+    return VoicePool(device=device, capacity=args.pool_rows, dtype=POOL_DTYPES[args.pool_dtype])
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
@@ -791,7 +803,7 @@ def main(argv=None):
     name_of = lambda s: voice_name(s["target"], s["lib"], s.get("codebook"))      # noqa: E731
     declared = declared_registers(sessions, name_of) if auto else {}
     declared_st = declared_ranges(sessions, name_of) if ranged else {}
-    pool, names = VoicePool(device=device, capacity=args.pool_rows), []
+    pool, names = make_pool(args, device), []
     for s in sessions:
         for target, lib in session_sources(s):
             name = voice_name(target, lib, s.get("codebook"))

@@ -415,6 +415,38 @@ int alive_pool_append(const float* tokens, int64_t row_stride, int64_t col_strid
                       float* norms, int64_t capacity, int64_t at, int32_t* report, void* stream);
 int alive_pool_move_rows(float* rows_f32, float* norms, int64_t capacity, int64_t src, int64_t dst, int64_t n, void* stream);
 
+/* ---------------------------------------------- half-precision voice pool (fp16 rows) ----
+ * The row table of a voice pool stored as IEEE fp16, rows_f16[P][768] (1536 bytes per row); the norms stay fp32.  Every call is its
+ * fp32 twin above with `_f16` appended: the same arguments (the table pointer is to fp16), the same checks and grids, and kernels
+ * that widen each element in registers and then run the twin's arithmetic in the twin's order.  fp16 -> fp32 is exact, so on a
+ * table H every call returns BITWISE what its twin returns on the fp32 table of H's widened values (same norms).
+ * alive_pool_append_f16: rounds each token element to fp16 (round to nearest even, subnormals kept, beyond fp16's range -> inf) and
+ *   takes the norm over the rounded values widened again: rows are the fp16 rounding of the tokens, norms bitwise those of
+ *   alive_pool_append on the rounded tokens.  The report therefore counts a row that overflowed fp16 (its norm is inf) and a row
+ *   that rounded to all zeros, besides the rows alive_pool_append counts.
+ * alive_pool_move_rows_f16: the same mover on rows of 96 sixteen-byte quads; the table must be 16-byte aligned. */
+int alive_pool_append_f16(const float* tokens, int64_t row_stride, int64_t col_stride, int64_t M, int Dd, void* rows_f16,
+                          float* norms, int64_t capacity, int64_t at, int32_t* report, void* stream);
+int alive_pool_move_rows_f16(void* rows_f16, float* norms, int64_t capacity, int64_t src, int64_t dst, int64_t n, void* stream);
+int alive_knn_search_grouped_f16(const float* src, int N, int T, const void* rows_f16, const float* norms, int64_t P,
+                                 const int32_t* seg_lo, const int32_t* seg_len, int k, float* out_val, int32_t* out_idx,
+                                 void* ws, void* stream);
+int alive_knn_search_grouped_k_f16(const float* src, int N, int T, const void* rows_f16, const float* norms, int64_t P,
+                                   const int32_t* seg_lo, const int32_t* seg_len, const int32_t* k_row, int k_max, float* out_val,
+                                   int32_t* out_idx, void* ws, void* stream);
+int alive_knn_merge_gather_rows_f16(const float* cand_val, const int32_t* cand_idx, int k, const double* alpha,
+                                    const void* rows_f16_full, const float* src, int N, int T, float* out,
+                                    int32_t* final_idx, void* stream);
+int alive_knn_merge_gather_rows_k_f16(const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k_max,
+                                      const double* alpha, const void* rows_f16_full, const float* src, int N, int T, float* out,
+                                      int32_t* final_idx, void* stream);
+int alive_knn_blend_gather_rows_f16(const float* cand_val, const int32_t* cand_idx, int k, const int32_t* first,
+                                    const double* weight, const double* alpha, const void* rows_f16_full, const float* src,
+                                    int N, int T, float* out, void* stream);
+int alive_knn_blend_gather_rows_k_f16(const float* cand_val, const int32_t* cand_idx, const int32_t* k_row, int k_max,
+                                      const int32_t* first, const double* weight, const double* alpha, const void* rows_f16_full,
+                                      const float* src, int N, int T, float* out, void* stream);
+
 /* ---------------------------------------------- pool search (many-to-many batch conversion) ----
  * A pool of V voices: fp32 rows_f32[P][768] / norms[P] from alive_library_pack_rows (voice v = rows [seg_lo[v], seg_lo[v] +
  * seg_len[v])), plus one bf16 IMAGE per voice in the layout of alive_library_pack (padded to alive_library_padded_rows rows),
@@ -916,6 +948,11 @@ int alive_knn_path_layout(int R, int T, int k_max, int64_t* off);
 int alive_knn_path_rows(const float* val, const int32_t* idx, const int32_t* k_row, int k_max, const int32_t* on, const double* weight,
                         const float* rows_f32, const float* norms, int64_t P, int R, int T, float* out_val, int32_t* out_idx,
                         int32_t* moved, void* ws, void* stream);
+/* the same on a half pool's table rows_f16 [P][768] (see "half-precision voice pool"): the join cost's dot over the widened values in
+ * the same order, bitwise alive_knn_path_rows on the fp32 table of the widened values */
+int alive_knn_path_rows_f16(const float* val, const int32_t* idx, const int32_t* k_row, int k_max, const int32_t* on,
+                            const double* weight, const void* rows_f16, const float* norms, int64_t P, int R, int T, float* out_val,
+                            int32_t* out_idx, int32_t* moved, void* ws, void* stream);
 
 /* Arithmetic of the decoder's two largest groups of GEMMs on the batch path (more than 96 columns; the streaming kernels are not
  * affected): (a) the six k = 5 convs of the 256-channel FilterBlock (decoder.py:128-134 at the Filter's coarsest scale), (b) the two

@@ -97,6 +97,11 @@ alive_ring_push_rows with every row present (push_call_us).
     python tools/bench_multistream.py --enrol [--out profiles/multistream_enrol.json]
     python tools/bench_multistream.py --sparse [--batches 128,1024] [--ticks 40] [--out profiles/multistream_sparse_bench.json]
     python tools/bench_multistream.py --conceal [--batches 128,1024] [--ticks 40] [--out profiles/multistream_conceal_bench.json]
+    python tools/bench_multistream.py --pool-dtype fp16 [--batches 64,128] [--out profiles/pool_f16_bench.json]
+
+--pool-dtype fp16 (pool_dtype_leg): the half-precision pool (VoicePool(dtype=torch.float16)) beside the fp32 pool of the same voices,
+the two alternated run by run in one process, three runs each: tick p50 / p99, the event-timed grouped search alone, the spread
+between runs and the search's read rate, then two fidelity figures on a synthetic voice (pool_dtype_fidelity).
 """
 import argparse
 import json
@@ -411,6 +416,97 @@ def sparse_leg(nets, batches=(128, 1024), ticks=40, warmup=6):
     return recs
 
 
+def pool_dtype_leg(nets, batches, configs, mixes, ticks, warmup, runs=3):
+    """--pool-dtype fp16: the shared / distinct legs on an fp32 and on a half pool of the same voices (two reserved pools filled voice
+    by voice, so no second copy of the tokens is kept), the two ALTERNATED run by run inside this one process, `runs` runs each.  Per
+    leg and dtype: the graph tick's p50 / p99 and the event-timed grouped search alone (time_search) of every run, their medians,
+    the spread between runs ((max - min) / median of the runs' p50s and search times), and the search's read rate in TB/s: the
+    bytes of the distinct segments, rows and norms, read once, over the median search time.  Then the fidelity figures."""
+    n_voices = max(batches) if "distinct" in mixes else 1
+    pools = {"fp32": MS.VoicePool(capacity=n_voices * VOICE_ROWS), "fp16": MS.VoicePool(capacity=n_voices * VOICE_ROWS, dtype=torch.float16)}
+    g = torch.Generator(device="cuda").manual_seed(2)
+    for i in range(n_voices):
+        tok = torch.randn(768, VOICE_ROWS, device="cuda", generator=g)
+        for pool in pools.values():
+            pool.add(f"v{i}", tok)
+        del tok
+    recs = []
+    for chunk, bs in configs:
+        for mix in mixes:
+            for B in batches:
+                rec = {"leg": "pool_dtype", "chunk": chunk, "buffersize": bs, "B": B, "voices": mix, "voice_rows": VOICE_ROWS,
+                       "chunk_period_ms": chunk / 16.0, "runs": runs}
+                per = {name: {"tick_p50_ms": [], "tick_p99_ms": [], "search_ms": []} for name in pools}
+                nbytes = {}
+                for run in range(runs):
+                    for name, pool in pools.items():           # alternated: fp32, fp16, fp32, fp16, ...
+                        conv = MS.MultiStreamConverter(*nets, pool, B, chunk=chunk, buffersize=bs, k=4)
+                        for s in range(B):
+                            conv.open(s, "v0" if mix == "shared" else f"v{s}", pitch=float(s % 5), f0_rate=0.5)
+                        conv.enable_graph()
+                        p50, p99 = time_ticks(conv, B, chunk, ticks, warmup + bs + 1, 300)
+                        ms, _ = time_search(conv, B, reps=60)
+                        segs = {(int(lo), int(ln)) for lo, ln in zip(conv.seg_lo.tolist(), conv.seg_len.tolist()) if ln > 0}
+                        nbytes[name] = sum(ln for _, ln in segs) * (pool.row_bytes + 4)
+                        per[name]["tick_p50_ms"].append(round(p50, 3))
+                        per[name]["tick_p99_ms"].append(round(p99, 3))
+                        per[name]["search_ms"].append(round(ms, 4))
+                        for s in range(B):
+                            conv.close(s)
+                        del conv
+                for name, d in per.items():
+                    med = {key: float(np.median(v)) for key, v in d.items()}
+                    rec[name] = dict(d, tick_p50_ms_median=round(med["tick_p50_ms"], 3), tick_p99_ms_median=round(med["tick_p99_ms"], 3),
+                                     search_ms_median=round(med["search_ms"], 4),
+                                     tick_p50_spread=round((max(d["tick_p50_ms"]) - min(d["tick_p50_ms"])) / med["tick_p50_ms"], 4),
+                                     search_spread=round((max(d["search_ms"]) - min(d["search_ms"])) / med["search_ms"], 4),
+                                     search_bytes=nbytes[name], search_TB_per_s=round(nbytes[name] / (med["search_ms"] * 1e-3) / 1e12, 3),
+                                     pool_table_bytes=pools[name].rows.numel() * pools[name].rows.element_size())
+                rec["search_fp16_over_fp32"] = round(rec["fp16"]["search_ms_median"] / rec["fp32"]["search_ms_median"], 4)
+                rec["tick_p50_fp16_over_fp32"] = round(rec["fp16"]["tick_p50_ms_median"] / rec["fp32"]["tick_p50_ms_median"], 4)
+                rec["real_time"] = {name: rec[name]["tick_p99_ms_median"] < rec["chunk_period_ms"] for name in pools}
+                print(json.dumps(rec), flush=True)
+                recs.append(rec)
+    del pools
+    recs.append(pool_dtype_fidelity(nets))
+    print(json.dumps(recs[-1]), flush=True)
+    return recs
+
+
+def pool_dtype_fidelity(nets, rows_n=5000, k=4, chunk=960, bs=8, ticks=350):
+    """Two figures, no bar: a half pool against an fp32 pool of the UNROUNDED tokens of a synthetic voice (synthetic.make_library, the
+    voices of the tests).  (a) the share of frames whose top-k SET differs, over the content encoder's frames of 350 s / 10 of
+    synthetic audio (>= 1000 frames), each pool searched by its own kernel; (b) one session streamed through a converter on each
+    pool in lockstep: the RMS of the difference of the two emitted int16 streams over 32768, beside the stream's own RMS."""
+    from module.spectrogram import spectrogram
+    tok = synthetic.make_library(rows_n, 31)[0].to("cuda")
+    pools = [MS.VoicePool({"v": tok}, dtype=torch.float16), MS.VoicePool({"v": tok})]
+    wav = synthetic.make_waveform(320 * 1100, 77).to("cuda")
+    ce = nets[0].to("cuda")
+    feat = torch.cat([ce(spectrogram(wav[:, i:i + 320 * 110])) for i in range(0, 320 * 1100, 320 * 110)], dim=2).contiguous()
+    n_frames = feat.shape[2]
+    lo = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ln = torch.full((1,), rows_n, dtype=torch.int32, device="cuda")
+    sets = [MS.knn_search_grouped(feat, p.rows, p.norms, lo, ln, k)[1].sort(dim=1).values for p in pools]
+    differ = int((sets[0] != sets[1]).any(dim=1).sum())
+    convs = [MS.MultiStreamConverter(*nets, p, 1, chunk=chunk, buffersize=bs, k=k) for p in pools]
+    for c in convs:
+        c.open(0, "v")
+        c.enable_graph()
+    pcm = (synthetic.make_waveform(chunk * ticks, 78)[0].numpy() * 12000).astype(np.int16)
+    out = [[], []]
+    for t in range(ticks):
+        for c, o in zip(convs, out):
+            y = c.step({0: pcm[t * chunk:(t + 1) * chunk]})[0]
+            if y is not None:
+                o.append(y.astype(np.float64))
+    a, b = (np.concatenate(o) for o in out)
+    return {"leg": "pool_dtype_fidelity", "voice_rows": rows_n, "k": k, "frames_searched": n_frames, "frames_topk_set_differs": differ,
+            "share_topk_set_differs": round(differ / n_frames, 5), "stream_samples": int(a.size), "stream_frames": int(a.size // 320),
+            "stream_rms_diff_over_32768": float(np.sqrt(np.mean((a - b) ** 2)) / 32768),
+            "stream_rms_over_32768": float(np.sqrt(np.mean(b ** 2)) / 32768), "stream_samples_differing": int((a != b).sum())}
+
+
 def time_search(conv, B, reps=20, seg_len=None):
     """the grouped search alone on the tick's shape: (ms per call, bytes of distinct segments read once).  seg_len: the segment
     lengths to search with (default: the converter's; a gated converter's seg_len_eff has its closed rows at 0)"""
@@ -493,6 +589,8 @@ def main():
     ap.add_argument("--conceal", action="store_true", help="the lost-chunk leg alone: a conceal=False sparse converter against "
                                                            "conceal=True ones with 0, 5 and 100 %% of the sessions losing every tick, "
                                                            "alternated, and the conceal call and the push alone")
+    ap.add_argument("--pool-dtype", default=None, choices=["fp16"], help="the half-pool leg alone: the shared / distinct legs (default "
+                    "B = 64,128) on an fp32 and on an fp16 pool, alternated, three runs each, and the fidelity figures")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     batches = [int(b) for b in (args.batches or ("128,1024" if args.sparse or args.conceal else "1,8,32,64,128")).split(",")]
@@ -504,6 +602,12 @@ def main():
     if args.quick:
         batches, configs, mixes = [64], [(160, 16)], ("distinct",)
     nets = (ContentEncoder(seed=2), F0Estimator(seed=2), Decoder(seed=2))
+    if args.pool_dtype:
+        rows = pool_dtype_leg(nets, [int(b) for b in (args.batches or "64,128").split(",")], configs, mixes, args.ticks, args.warmup)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            json.dump(rows, open(args.out, "w"), indent=1)
+        return
     if args.conceal:
         rows = conceal_leg(nets, batches, args.ticks, args.warmup)
         if args.out:
