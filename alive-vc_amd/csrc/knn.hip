@@ -2193,24 +2193,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HAT && PER 
     }
 }
 
-// PER from the candidate count of a launch: R = P * kp <= 64 PER
-template <bool HAT, typename... A>
-static void rescore_launch_form(unsigned grid, hipStream_t s, const float* cv, const int* ci, int P, int kp, A... rest) {
-    const int R = P * kp;
-    if (R <= 64) knn_rescore_kernel<0, false, HAT><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else if (R <= 192) knn_rescore_kernel<3, false, HAT><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else if (R <= 256) knn_rescore_kernel<4, false, HAT><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else if (R <= 512) knn_rescore_kernel<8, false, HAT><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else knn_rescore_kernel<16, false, HAT><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-}
-// rows_hat given: the form that reads the unit rows
-template <typename... A>
-static void rescore_launch(unsigned grid, hipStream_t s, const float* cv, const int* ci, int P, int kp, const float* s_f32, const float* rows,
-                           const float* norms, const float* rows_hat, A... rest) {
-    if (rows_hat != nullptr) rescore_launch_form<true>(grid, s, cv, ci, P, kp, s_f32, rows, norms, rows_hat, rest...);
-    else rescore_launch_form<false>(grid, s, cv, ci, P, kp, s_f32, rows, norms, rows_hat, rest...);
-}
-
 // ----------------------------------------------------------------------------------------------
 // a handful of frames (streaming): exact fp32 scan, no candidate stage
 // ----------------------------------------------------------------------------------------------
@@ -3210,7 +3192,7 @@ struct SearchPlan {
 
 // Grid = (Tt_pad / 256 frame blocks) x (split library ranges), one block per CU at a time (1 wave / SIMD).
 // The split is chosen so that the last round of blocks over the 256 CUs is as full as possible.
-static SearchPlan make_plan(int64_t Tt, int64_t M, int split_cap = MAX_SPLIT, int ft = FT) {
+static SearchPlan make_plan(int64_t Tt, int64_t M, int split_cap, int ft) {
     SearchPlan p;
     p.Tt = Tt;
     p.Tt_pad = (Tt + ft - 1) / ft * ft;
@@ -3260,10 +3242,9 @@ constexpr int PROBE_NUM = 11, PROBE_DEN = 20; // bf16 first when more than 55 % 
                                               // kernel's late accumulator copies; it was 40 % at t16 = 2.3 t8).  Measured on the dense
                                               // library, 49 % failing: fp8 first 216.9 ms per search, bf16 first 227.9 ms
 
-// seeds for a launch of `fb` frame blocks x `split` library splits (nullptr members: no seeding); zeroes the flags on the stream
-static SeedArgs seeds_for(const struct SearchWs& w, int64_t fb, int split, int k, float margin, int counter, hipStream_t s, int min_fb = SEED_MIN_FB);
-
 // ---- workspace: ONE layout function for the size query, the searches and the stats pointer ----
+// (a pure function of its arguments: what a call adds -- certificate operands, unit rows -- lives in SearchRun)
+enum WsKind { WS_FAST, WS_STRICT, WS_SUB };       // WS_STRICT: + the split tier's frame planes; WS_SUB: + the subspace stage's operands
 struct SearchWs {
     SearchPlan p16, p8, pt, pp;            // bf16 main / fp8 main / tier-1 re-search / probe
     SearchPlan p6, pp6;                    // fp6 main / probe (384-frame blocks)
@@ -3286,29 +3267,27 @@ struct SearchWs {
     unsigned short* s_c2h; unsigned short* s_c2l;   // split tier (strict search): both planes of the frames that failed the deterministic certificate
     float* c2v; int* c2i;                  // candidate lists of the collect tiers: [slot][split][caps]
     int rows_t, rows_b;                    // rows per frame they may fill: tier-1 launches (<= fcap frames) / bulk launches
-    const unsigned short* lib_lo;          // set by the strict search when the library carries its lo plane
     float* tau; int* tau_flag;             // fp8 stage: per-frame admission seeds handed from split to split, and the hand-off flags
-    const float* det_q; const float* det_lib;   // set by the strict search only: frame / library share of the deterministic bound
-    const float* rows_hat;                 // set by alive_knn_search_unit: the library's unit rows (knn_rescore_kernel: no division)
     size_t bytes;
 };
 
-static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split = false, bool sub = false) {
+static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, WsKind kind) {
     SearchWs w;
-    w.p16 = make_plan(Tt, M);
-    w.p8 = make_plan(Tt, M, MAX_SPLIT8);
+    const bool split = kind == WS_STRICT, sub = kind == WS_SUB;
+    w.p16 = make_plan(Tt, M, MAX_SPLIT, FT);
+    w.p8 = make_plan(Tt, M, MAX_SPLIT8, FT);
     w.p6 = make_plan(Tt, M, MAX_SPLIT8, FT6);
     w.p6w = make_plan(Tt, M, MAX_SPLIT8, FT6W);
     const int64_t Tp = w.p16.Tt_pad;
     // (the fp6 stage pads the frames to blocks of 384, the wide subspace kernel to blocks of 512)
     const int64_t Tp8 = std::max(std::max(w.p6.Tt_pad, w.p6w.Tt_pad), Tp);
     w.fcap = Tp < FCAP ? (int)Tp : FCAP;
-    w.pt = make_plan(w.fcap < FPLAN ? w.fcap : FPLAN, M);
-    w.pa = make_plan(FT, M);
+    w.pt = make_plan(w.fcap < FPLAN ? w.fcap : FPLAN, M, MAX_SPLIT, FT);
+    w.pa = make_plan(FT, M, MAX_SPLIT, FT);
     w.probe_n = Tt >= PROBE_MIN_T ? PROBE_N : 0;
     w.probe_pad = (w.probe_n + FT - 1) / FT * FT;
     w.probe_pad6 = (w.probe_n + FT6 - 1) / FT6 * FT6;
-    w.pp = make_plan(w.probe_n > 0 ? w.probe_n : 1, M, MAX_SPLIT8);
+    w.pp = make_plan(w.probe_n > 0 ? w.probe_n : 1, M, MAX_SPLIT8, FT);
     w.pp6 = make_plan(w.probe_n > 0 ? w.probe_n : 1, M, MAX_SPLIT8, FT6);
     Arena a(base);
     w.stats = a.take<int>(ST_WORDS);       // first: its address must not depend on k (alive_knn_search_stats has no k)
@@ -3347,12 +3326,8 @@ static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split =
     w.c2i = a.take<int>(c2n);
     w.rows_t = (int)(c2n / (size_t)w.fcap < 1024 ? c2n / (size_t)w.fcap : 1024);
     w.rows_b = (int)(c2n / (size_t)Tp < 1024 ? c2n / (size_t)Tp : 1024);
-    w.lib_lo = nullptr;
     w.tau = a.take<float>((size_t)Tp8);
     w.tau_flag = a.take<int>((size_t)(Tp8 / FT) * (MAX_SPLIT > MAX_SPLIT8 ? MAX_SPLIT : MAX_SPLIT8));
-    w.det_q = nullptr;
-    w.det_lib = nullptr;
-    w.rows_hat = nullptr;
     // the two frame planes of the split tier (1.5 KB per frame each) exist only in the strict search's workspace
     // (alive_knn_workspace_bytes_strict); they come last, so every other address is the same in both layouts
     w.s_c2h = split ? a.take<unsigned short>((size_t)Tp * D) : nullptr;
@@ -3368,8 +3343,11 @@ static SearchWs ws_layout(void* base, int64_t Tt, int64_t M, int k, bool split =
     return w;
 }
 
+constexpr SeedArgs NO_SEEDS{nullptr, nullptr, 0, 0.0f, nullptr};
+
+// seeds for a launch of `fb` >= min_fb frame blocks x `split` library splits (else NO_SEEDS); zeroes the flags on the stream
 static SeedArgs seeds_for(const SearchWs& w, int64_t fb, int split, int k, float margin, int counter, hipStream_t s, int min_fb) {
-    if (fb < min_fb || split < 2) return SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr};
+    if (fb < min_fb || split < 2) return NO_SEEDS;
     (void)hipMemsetAsync(w.tau_flag, 0, (size_t)fb * split * sizeof(int), s);
     return SeedArgs{w.tau, w.tau_flag, k, margin, w.stats + counter};
 }
@@ -3416,12 +3394,12 @@ struct PoolWs {
 };
 
 // kinds: the values of k one voice may be searched at in one call (1: every row at k; k: rows at their own k in [1, k])
-static PoolWs pool_ws_layout(void* base, int N, int T, int k, int V, int64_t max_len, int kinds = 1) {
+static PoolWs pool_ws_layout(void* base, int N, int T, int k, int V, int64_t max_len, int kinds) {
     PoolWs w{};
     const int64_t Tt = (int64_t)N * T;
     const int64_t gmax = N < (int64_t)V * kinds ? N : (int64_t)V * kinds;   // groups: each adds at most one partial frame block
     w.S = ((Tt + FT - 1) / FT + gmax) * FT;
-    w.P = make_plan(Tt, max_len).split;
+    w.P = make_plan(Tt, max_len, MAX_SPLIT, FT).split;
     const int F = 64 / k;                                               // (a group at k' <= k has chunks of 64 / k' >= F frames)
     const int64_t chunks = (Tt + F - 1) / F + gmax;
     w.items = chunks > GR_ITEMS ? chunks : GR_ITEMS;
@@ -3720,54 +3698,208 @@ extern "C" int alive_library_pack(const float* tokens, int64_t M, int Dd, void* 
     return ALIVE_OK;
 }
 
-static int knn_scan_launch(const float* src, int T, int64_t Tt, const float* rows_f32, const float* norms, int64_t M,
-                           int64_t idx_base, int k, float* s_f32, unsigned short* s_bf16, float* pv, int* pi, float* out_val,
-                           int32_t* out_idx, int* stats, hipStream_t s, hipEvent_t g_ev_start, hipEvent_t g_ev_stop) {
-    stats_init_kernel<<<1, 64, 0, s>>>(stats, TIER_SCAN);
-    src_prep_small_kernel<<<(unsigned)Tt, 256, 0, s>>>(src, T, Tt, s_f32, s_bf16, nullptr);
-    int blocks = (int)((M + 4 * SCAN_WAVES - 1) / (4 * SCAN_WAVES));          // >= 4 rows per wave
+// ---- the host side of a search: one call record in, named records to the tier launchers ----
+// A tiered search runs from the caller's AliveKnnSearch (the named entry points fill one, alive_knn_search_unit is handed one).  What the
+// search derives from it once -- frame count, workspace layout, the strict form's certificate operands -- travels beside it in a SearchRun.
+struct SearchRun {
+    const AliveKnnSearch& a;
+    const SearchWs& w;
+    int64_t Tt;
+    hipStream_t s;
+    const float* det_q = nullptr; const float* det_lib = nullptr;   // strict form only: frame / library share of the deterministic bound
+    const unsigned short* lib_lo = nullptr;                         // strict form whose library carries its lo plane (else: no split tier)
+};
+
+// a launch runs when the device-side count *cnt lies in (lo, hi]; cnt null: always
+struct Gate { const int* cnt; int lo, hi; };
+constexpr int GATE_ALL = 0x7fffffff;
+
+// knn_rescore_kernel's parameters under their names, in its order.  Call sites start from rescore16 / certify16 / certify8 below and
+// write out what differs.
+struct Rescore {
+    const float* cand_val; const int* cand_idx; int P, kp;
+    const float* s_f32; const float* rows; const float* norms; const float* rows_hat;
+    int64_t Tt, idx_base; int k;
+    float* out_val; int* out_idx;
+    const int* frame_list; Gate gate;
+    int* flag_list; int* flag_cnt;
+    float zsig; int list_len; float pre_scale, sd_prior;
+    const float* det_q = nullptr; const float* det_lib = nullptr;
+    float* thr_list = nullptr; int collect = 0; float overflow_slack = 0.0f;
+    const unsigned char* force_fail = nullptr;
+    PoolRescore pool{};                    // slot_grp set: the pool search's form
+};
+
+// PER from the candidate count of the launch (R = P * kp <= 64 PER), HAT with unit rows, POOL with a pool plan (which reads no unit rows)
+static void rescore_launch(unsigned grid, hipStream_t s, const Rescore& r) {
+    const auto per = [&](auto n) {
+        constexpr int PER = decltype(n)::value;
+        const auto go = [&](auto kernel) {
+            kernel<<<grid, 256, 0, s>>>(r.cand_val, r.cand_idx, r.P, r.kp, r.s_f32, r.rows, r.norms, r.rows_hat, r.Tt, r.idx_base, r.k, r.out_val,
+                                        r.out_idx, r.frame_list, r.gate.cnt, r.gate.lo, r.gate.hi, r.flag_list, r.flag_cnt, r.zsig, r.list_len,
+                                        r.pre_scale, r.sd_prior, r.det_q, r.det_lib, r.thr_list, r.collect, r.overflow_slack, r.force_fail, r.pool);
+        };
+        if (r.pool.slot_grp != nullptr) go(knn_rescore_kernel<PER, true, false>);
+        else if (r.rows_hat != nullptr) go(knn_rescore_kernel<PER, false, true>);
+        else go(knn_rescore_kernel<PER, false, false>);
+    };
+    const int R = r.P * r.kp;
+    if (R <= 64) per(IntC<0>{});
+    else if (R <= 192) per(IntC<3>{});
+    else if (R <= 256) per(IntC<4>{});
+    else if (R <= 512) per(IntC<8>{});
+    else per(IntC<16>{});
+}
+
+// the rescoring of all Tt frames of a search from the main candidate lists, at the bf16 stage's scale and error prior; flagged frames ->
+// `list` / the counter stats[counter]
+static Rescore rescore16(const SearchRun& r, int* list, int counter) {
+    const AliveKnnSearch& a = r.a;
+    return Rescore{r.w.cv, r.w.ci, r.w.p16.P, KP, r.w.s_f32, a.rows_f32, a.norms, a.rows_hat, r.Tt, a.idx_base, a.k, a.out_val, a.out_idx,
+                   nullptr, Gate{nullptr, 0, 0}, list, r.w.stats + counter, CERT_Z, KH, 1.0f, SD_PRIOR16};
+}
+// certify behind the bf16 stage (strict: the deterministic bound): failures -> list1, with the thresholds the collect tier takes them at
+static Rescore certify16(const SearchRun& r) {
+    Rescore c = rescore16(r, r.w.list1, ST_FLAG16);
+    c.det_q = r.det_q; c.det_lib = r.det_lib;
+    c.thr_list = r.w.thr1;
+    c.overflow_slack = r.lib_lo != nullptr ? SPLIT_BOUND : 0.0f;
+    return c;
+}
+// certify behind a block-scaled stage (scores in units of 1 / pre, the stage's error prior): failures -> list0
+static Rescore certify8(const SearchRun& r, const SearchPlan& p, float pre, float prior, const unsigned char* force_fail) {
+    Rescore c = rescore16(r, r.w.list0, ST_FLAG8);
+    c.P = p.P; c.kp = KP8;
+    c.list_len = KH8; c.pre_scale = pre; c.sd_prior = prior;
+    c.force_fail = force_fail;
+    return c;
+}
+// collected rows (nothing to certify): frames whose rows did not fit -> list2
+static Rescore collect16(const SearchRun& r) {
+    Rescore c = rescore16(r, r.w.list2, ST_FLAGC);
+    c.cand_val = r.w.c2v; c.cand_idx = r.w.c2i;
+    c.collect = 1;
+    return c;
+}
+
+// seeds of a bf16 scoring launch of `fb` frame blocks x `split` library splits (the strict form admits with a wider margin)
+static SeedArgs seeds16(const SearchRun& r, int64_t fb, int split) {
+    return seeds_for(r.w, fb, split, r.a.k, r.det_q != nullptr ? SEED_MARGIN16_STRICT : SEED_MARGIN16, ST_SEEDED16, r.s, SEED_MIN_FB);
+}
+
+// One pass of the bf16 stage over the listed frames list[0 .. *gate.cnt), launched up front and run when the count lies in the gate's
+// window: compact the frames, score them (COLLECT: keep every row at or above the frame's threshold thr1, `caps` per split), rescore.
+// `rs` says what the rescoring does with them; the pass fills in its candidates, frames and gate.
+struct Bf16Pass {
+    const SearchPlan& plan;                // library splits of the scoring launch
+    int64_t slots, frames;                 // compacted slots the gather and the scoring cover (whole frame blocks) / the rescoring covers
+    const int* list; Gate gate;
+    float* cv; int* ci;                    // candidate lists [slot][P][KP or caps]
+    int caps;
+    bool seeded;                           // seeded admission (seeds16), when the launch is large enough for it
+};
+template <bool COLLECT>
+static void bf16_pass_launch(const SearchRun& r, const Bf16Pass& b, Rescore rs) {
+    const SearchWs& w = r.w;
+    const SearchPlan& p = b.plan;
+    gather_frames_kernel<<<(unsigned)b.slots, 128, 0, r.s>>>(w.s_bf16, b.list, b.gate.cnt, b.gate.lo, b.gate.hi, w.s_c);
+    const SeedArgs sa = b.seeded ? seeds16(r, b.slots / FT, p.split) : NO_SEEDS;          // (its memset of the flags: behind the gather)
+    knn_score_kernel<COLLECT><<<dim3((unsigned)(b.slots / FT), p.split), 256, SCORE_LDS, r.s>>>(
+        w.s_c, (const unsigned short*)r.a.lib_bf16, r.a.M, p.tiles_total, p.tiles_per_split, p.P, b.cv, b.ci, b.gate.cnt, b.gate.lo, b.gate.hi, 1,
+        COLLECT ? w.thr1 : nullptr, sa, COLLECT ? b.caps : 0);
+    rs.cand_val = b.cv; rs.cand_idx = b.ci; rs.P = p.P; rs.kp = COLLECT ? b.caps : KP;
+    rs.Tt = b.frames; rs.frame_list = b.list; rs.gate = b.gate;
+    rescore_launch((unsigned)((b.frames + 3) / 4), r.s, rs);
+}
+
+// One launcher for the block-scaled scoring kernels: which kernel, its grid and dynamic LDS, the operands, the gate and the seeds
+// (rho / g: the subspace kernels' fp32 term; the probes are unseeded and read the gate as an on / off word)
+enum StageKernel { STAGE_SCORE8, STAGE_PROBE8, STAGE_SCORE6, STAGE_PROBE6, STAGE_SUB6, STAGE_SUB6W };
+struct StageOps {
+    const unsigned char* frames; const unsigned char* lib;
+    const float* rho; const float* g;
+    int64_t M; const SearchPlan& p;
+    float* cv; int* ci;
+};
+static void stage_launch(StageKernel which, dim3 grid, int lds, hipStream_t s, const StageOps& o, Gate gate, SeedArgs sa) {
+    const SearchPlan& p = o.p;
+    const auto score = [&](auto kernel) {
+        kernel<<<grid, 256, lds, s>>>(o.frames, o.lib, o.M, p.tiles_total, p.tiles_per_split, p.P, o.cv, o.ci, gate.cnt, gate.lo, gate.hi, sa);
+    };
+    const auto probe = [&](auto kernel) {
+        kernel<<<grid, 256, lds, s>>>(o.frames, o.lib, o.M, p.tiles_total, p.tiles_per_split, p.P, o.cv, o.ci, gate.cnt);
+    };
+    const auto sub = [&](auto kernel) {
+        kernel<<<grid, 256, lds, s>>>(o.frames, o.lib, o.rho, o.g, o.M, p.tiles_total, p.tiles_per_split, p.P, o.cv, o.ci, gate.cnt, gate.lo, gate.hi, sa);
+    };
+    switch (which) {
+        case STAGE_SCORE8: score(knn_score8_kernel); break;
+        case STAGE_PROBE8: probe(knn_probe8_kernel); break;
+        case STAGE_SCORE6: score(knn_score6_kernel); break;
+        case STAGE_PROBE6: probe(knn_probe6_kernel); break;
+        case STAGE_SUB6: sub(knn_sub6_kernel); break;
+        case STAGE_SUB6W: sub(knn_sub6w_kernel); break;
+    }
+}
+
+// the merge form of a grouped / pool search: a k per row, or the call's k (up to 4: the one-register form)
+template <typename F>
+static void with_merge_form(const int32_t* k_row, int k, F&& launch) {
+    if (k_row != nullptr) launch(IntC<MERGE_ROW>{});
+    else if (k <= 4) launch(IntC<MERGE_K4>{});
+    else launch(IntC<MERGE_GEN>{});
+}
+
+// a handful of frames (Tt * k <= 64): the exact fp32 scan of the rows, no candidate stage; the events bracket the scan kernel
+static int knn_scan_launch(const char* who, const SearchRun& r) {
+    const AliveKnnSearch& a = r.a;
+    const SearchWs& w = r.w;
+    hipStream_t s = r.s;
+    stats_init_kernel<<<1, 64, 0, s>>>(w.stats, TIER_SCAN);
+    src_prep_small_kernel<<<(unsigned)r.Tt, 256, 0, s>>>(a.src, a.T, r.Tt, w.s_f32, w.s_bf16, nullptr);
+    int blocks = (int)((a.M + 4 * SCAN_WAVES - 1) / (4 * SCAN_WAVES));          // >= 4 rows per wave
     if (blocks > SCAN_MAX_LISTS / SCAN_WAVES) blocks = SCAN_MAX_LISTS / SCAN_WAVES;
     if (blocks < 1) blocks = 1;
-    if (g_ev_start) (void)hipEventRecord(g_ev_start, s);
-    knn_scan_kernel<true><<<blocks, 64 * SCAN_WAVES, 0, s>>>(s_f32, rows_f32, norms, M, (int)Tt, k, pv, pi);
-    if (g_ev_stop) (void)hipEventRecord(g_ev_stop, s);
-    if (k <= 4) knn_scan_merge_kernel<true><<<(unsigned)Tt, 256, 0, s>>>(pv, pi, blocks * SCAN_WAVES, k, idx_base, out_val, out_idx);
-    else knn_scan_merge_kernel<false><<<(unsigned)Tt, 256, 0, s>>>(pv, pi, blocks * SCAN_WAVES, k, idx_base, out_val, out_idx);
-    ALIVE_CHECK_LAUNCH("alive_knn_search(scan)");
+    if (a.ev_start) (void)hipEventRecord((hipEvent_t)a.ev_start, s);
+    knn_scan_kernel<true><<<blocks, 64 * SCAN_WAVES, 0, s>>>(w.s_f32, a.rows_f32, a.norms, a.M, (int)r.Tt, a.k, w.pv, w.pi);
+    if (a.ev_stop) (void)hipEventRecord((hipEvent_t)a.ev_stop, s);
+    if (a.k <= 4) knn_scan_merge_kernel<true><<<(unsigned)r.Tt, 256, 0, s>>>(w.pv, w.pi, blocks * SCAN_WAVES, a.k, a.idx_base, a.out_val, a.out_idx);
+    else knn_scan_merge_kernel<false><<<(unsigned)r.Tt, 256, 0, s>>>(w.pv, w.pi, blocks * SCAN_WAVES, a.k, a.idx_base, a.out_val, a.out_idx);
+    ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
 }
 
-// exact tier over a frame list with a device-side count (list == nullptr: all Tt frames)
-static void knn_exact_launch(const SearchWs& w, const float* rows_f32, const float* norms, int64_t M, int64_t Tt, int64_t idx_base,
-                             int k, const int* list, const int* cnt, float* out_val, int32_t* out_idx, hipStream_t s,
-                             int max_count = 0x7fffffff) {
-#define ALIVE_EXACT(G_)                                                                                                        \
-    {                                                                                                                          \
-        knn_exact_kernel<G_><<<EX_BLOCKS, 256, 0, s>>>(w.s_f32, rows_f32, norms, M, Tt, k, list, cnt, w.pv, w.pi, max_count);   \
-        knn_exact_merge_kernel<G_><<<1024, 256, 0, s>>>(w.pv, w.pi, Tt, k, idx_base, list, cnt, out_val, out_idx, max_count);  \
+// exact tier over a frame list with a device-side count of at most max_count (list == nullptr: all Tt frames)
+static void knn_exact_launch(const SearchRun& r, const int* list, const int* cnt, int max_count) {
+    const AliveKnnSearch& a = r.a;
+    const SearchWs& w = r.w;
+    const auto group = [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        knn_exact_kernel<G><<<EX_BLOCKS, 256, 0, r.s>>>(w.s_f32, a.rows_f32, a.norms, a.M, r.Tt, a.k, list, cnt, w.pv, w.pi, max_count);
+        knn_exact_merge_kernel<G><<<1024, 256, 0, r.s>>>(w.pv, w.pi, r.Tt, a.k, a.idx_base, list, cnt, a.out_val, a.out_idx, max_count);
+    };
+    switch (exact_group(a.k)) {
+        case 16: group(IntC<16>{}); break;
+        case 8: group(IntC<8>{}); break;
+        case 4: group(IntC<4>{}); break;
+        case 2: group(IntC<2>{}); break;
+        default: group(IntC<1>{}); break;
     }
-    switch (exact_group(k)) {
-        case 16: ALIVE_EXACT(16) break;
-        case 8: ALIVE_EXACT(8) break;
-        case 4: ALIVE_EXACT(4) break;
-        case 2: ALIVE_EXACT(2) break;
-        default: ALIVE_EXACT(1) break;
-    }
-#undef ALIVE_EXACT
 }
 
-static void src_prep_launch(const SearchWs& w, const float* src, int T, int64_t Tt, hipStream_t s) {
-    float* dq = w.det_q != nullptr ? w.dq : nullptr;
-    if (Tt <= 512) src_prep_small_kernel<<<(unsigned)w.p16.Tt_pad, 256, 0, s>>>(src, T, Tt, w.s_f32, w.s_bf16, dq, w.sub_nrm);
-    else src_prep_kernel<<<(unsigned)(w.p16.Tt_pad / 64), 256, 0, s>>>(src, T, Tt, w.p16.Tt_pad, w.s_f32, w.s_bf16, dq, w.sub_nrm);
+static void src_prep_launch(const SearchRun& r) {
+    const SearchWs& w = r.w;
+    float* dq = r.det_q != nullptr ? w.dq : nullptr;
+    if (r.Tt <= 512) src_prep_small_kernel<<<(unsigned)w.p16.Tt_pad, 256, 0, r.s>>>(r.a.src, r.a.T, r.Tt, w.s_f32, w.s_bf16, dq, w.sub_nrm);
+    else src_prep_kernel<<<(unsigned)(w.p16.Tt_pad / 64), 256, 0, r.s>>>(r.a.src, r.a.T, r.Tt, w.p16.Tt_pad, w.s_f32, w.s_bf16, dq, w.sub_nrm);
 }
 
-static int check_search_args(const char* what, const void* a, const void* b, int N, int T, int k, int64_t M) {
-    ALIVE_CHECK_ARG(a && b, "%s: null pointer", what);
-    ALIVE_CHECK_ARG(N > 0 && T > 0, "%s: empty source", what);
-    ALIVE_CHECK_ARG(k >= 1 && k <= ALIVE_MAX_K, "%s: k=%d outside [1,%d]", what, k, ALIVE_MAX_K);
-    ALIVE_CHECK_ARG(M >= k, "%s: library shard has %lld vectors, fewer than k=%d", what, (long long)M, k);
-    ALIVE_CHECK_ARG((int64_t)N * T < ((int64_t)1 << 31) - FT6, "%s: %lld frames in one call", what, (long long)N * T);
+// what every tiered search checks behind its own null checks (who: the entry that was called)
+static int check_search_args(const char* who, const AliveKnnSearch& a) {
+    ALIVE_CHECK_ARG(a.N > 0 && a.T > 0, "%s: empty source", who);
+    ALIVE_CHECK_ARG(a.k >= 1 && a.k <= ALIVE_MAX_K, "%s: k=%d outside [1,%d]", who, a.k, ALIVE_MAX_K);
+    ALIVE_CHECK_ARG(a.M >= a.k, "%s: library shard has %lld vectors, fewer than k=%d", who, (long long)a.M, a.k);
+    ALIVE_CHECK_ARG((int64_t)a.N * a.T < ((int64_t)1 << 31) - FT6, "%s: %lld frames in one call", who, (long long)a.N * a.T);
     return ALIVE_OK;
 }
 
@@ -3832,20 +3964,14 @@ extern "C" int alive_library_pack_fp6(const void* lib_bf16, int64_t M, void* lib
 // the layout).  alive_knn_workspace_bytes is the bound that is safe for EVERY search entry point (a caller built against an older header
 // sizes one buffer with it and may hand it to the strict search, which takes no size argument); the searches without a lo plane need
 // only alive_knn_workspace_bytes_fast (3 KB per frame less).
-extern "C" size_t alive_knn_workspace_bytes_fast(int64_t Tt, int64_t M) {
-    // sized for any k the entry points accept (the exact tier's partial lists grow with ceil(Tt / G(k)))
-    const size_t a = ws_layout(nullptr, Tt, M, 4).bytes, b = ws_layout(nullptr, Tt, M, ALIVE_MAX_K).bytes;
-    return a > b ? a : b;
+// Each is sized for any k the entry points accept (the exact tier's partial lists grow with ceil(Tt / G(k))).
+static size_t ws_bytes_any_k(int64_t Tt, int64_t M, WsKind kind) {
+    return std::max(ws_layout(nullptr, Tt, M, 4, kind).bytes, ws_layout(nullptr, Tt, M, ALIVE_MAX_K, kind).bytes);
 }
-extern "C" size_t alive_knn_workspace_bytes_strict(int64_t Tt, int64_t M) {
-    const size_t a = ws_layout(nullptr, Tt, M, 4, true).bytes, b = ws_layout(nullptr, Tt, M, ALIVE_MAX_K, true).bytes;
-    return a > b ? a : b;
-}
+extern "C" size_t alive_knn_workspace_bytes_fast(int64_t Tt, int64_t M) { return ws_bytes_any_k(Tt, M, WS_FAST); }
+extern "C" size_t alive_knn_workspace_bytes_strict(int64_t Tt, int64_t M) { return ws_bytes_any_k(Tt, M, WS_STRICT); }
 extern "C" size_t alive_knn_workspace_bytes(int64_t Tt, int64_t M) { return alive_knn_workspace_bytes_strict(Tt, M); }
-extern "C" size_t alive_knn_workspace_bytes_sub(int64_t Tt, int64_t M) {       // alive_knn_search_fp6_sub_timed
-    const size_t a = ws_layout(nullptr, Tt, M, 4, false, true).bytes, b = ws_layout(nullptr, Tt, M, ALIVE_MAX_K, false, true).bytes;
-    return a > b ? a : b;
-}
+extern "C" size_t alive_knn_workspace_bytes_sub(int64_t Tt, int64_t M) { return ws_bytes_any_k(Tt, M, WS_SUB); }   // alive_knn_search_fp6_sub_timed
 
 // The collect tier: the frames whose bf16 certificate failed (list1, with the thresholds thr1 the rescoring kernel recorded
 // for them) go through the bf16 scoring kernel once more, in its COLLECT form -- every row whose stage score reaches the
@@ -3854,153 +3980,246 @@ extern "C" size_t alive_knn_workspace_bytes_sub(int64_t Tt, int64_t M) {       /
 // the deterministic bound of the strict search), so the result is final; frames with more rows above the threshold than
 // the lists hold (dense clusters: more rows inside the stage's error than any candidate list can keep) are the only ones
 // left for the exact scan.  Same two launch plans as the re-search: few frames (<= fcap) / the whole batch.
-static void collect_tier_launch(const SearchWs& w, const void* lib_bf16, const float* rows_f32, const float* norms, int64_t M,
-                                int64_t Tt, int64_t idx_base, int k, float* out_val, int32_t* out_idx, hipStream_t s) {
+static void collect_tier_launch(const SearchRun& r) {
+    const SearchWs& w = r.w;
     int* cnt1 = w.stats + ST_FLAG16;
     int* cnt2 = w.stats + ST_FLAGC;
     const int fcap = w.fcap;
-    if (w.lib_lo != nullptr) {
+    const Gate past_min{cnt1, COLLECT_MIN, GATE_ALL}, few{cnt1, COLLECT_MIN, fcap}, bulk{cnt1, fcap, GATE_ALL};
+    // a handful of frames: the exact scan costs less than the fixed cost of one more scoring pass over the library (~8 ms at 1 M
+    // rows against ~20 us per frame of exact scan)
+    knn_exact_launch(r, w.list1, cnt1, COLLECT_MIN);
+    if (r.lib_lo != nullptr) {
         // Strict search with a lo-plane library: the frames that failed the deterministic certificate (list1, thresholds
         // thr1 = v_k - SPLIT_BOUND) go STRAIGHT to the split-bf16 collect pass -- on a dense library 95 % of them overflow the
         // single-plane collect tier (its band is the certificate's 1.8e-3), which would be a wasted pass over the library -- its
         // rows are rescored exactly, and only what overflows it (clusters of near-copies) reaches the exact scan.
-        const unsigned Tp = (unsigned)w.p16.Tt_pad;
-        knn_exact_launch(w, rows_f32, norms, M, Tt, idx_base, k, w.list1, cnt1, out_val, out_idx, s, COLLECT_MIN);
-        gather_frames_split_kernel<<<Tp, 128, 0, s>>>(w.s_bf16, w.s_f32, w.list1, cnt1, COLLECT_MIN, w.s_c2h, w.s_c2l);
-        const int caps = w.rows_b / w.p16.P < 64 ? w.rows_b / w.p16.P : 64;              // P <= MAX_SPLIT = 64: at least 4
-        knn_collect_split_kernel<<<dim3(Tp / FT2, w.p16.split), 256, SPLIT_LDS, s>>>(
-            w.s_c2h, w.s_c2l, (const unsigned short*)lib_bf16, w.lib_lo, M, w.p16.tiles_total, w.p16.tiles_per_split, w.p16.P, caps,
-            w.c2v, w.c2i, cnt1, COLLECT_MIN, w.thr1);
-        rescore_launch((unsigned)((Tt + 3) / 4), s, w.c2v, w.c2i, w.p16.P, caps, w.s_f32, rows_f32, norms, w.rows_hat, Tt, idx_base, k,
-                                                                   out_val, out_idx, w.list1, cnt1, COLLECT_MIN, 0x7fffffff, w.list2, cnt2,
-                                                                   CERT_Z, KH, 1.0f, SD_PRIOR16, nullptr, nullptr, nullptr, 1, 0.0f);
-        knn_exact_launch(w, rows_f32, norms, M, Tt, idx_base, k, w.list2, cnt2, out_val, out_idx, s);
-        return;
+        const SearchPlan& p = w.p16;
+        const unsigned Tp = (unsigned)p.Tt_pad;
+        const int caps = w.rows_b / p.P < 64 ? w.rows_b / p.P : 64;                      // P <= MAX_SPLIT = 64: at least 4
+        gather_frames_split_kernel<<<Tp, 128, 0, r.s>>>(w.s_bf16, w.s_f32, w.list1, past_min.cnt, past_min.lo, w.s_c2h, w.s_c2l);
+        knn_collect_split_kernel<<<dim3(Tp / FT2, p.split), 256, SPLIT_LDS, r.s>>>(
+            w.s_c2h, w.s_c2l, (const unsigned short*)r.a.lib_bf16, r.lib_lo, r.a.M, p.tiles_total, p.tiles_per_split, p.P, caps, w.c2v, w.c2i,
+            past_min.cnt, past_min.lo, w.thr1);
+        Rescore rs = collect16(r);
+        rs.P = p.P; rs.kp = caps;
+        rs.frame_list = w.list1; rs.gate = past_min;
+        rescore_launch((unsigned)((r.Tt + 3) / 4), r.s, rs);
+    } else {
+        // the same two launch plans as the re-search: few frames (<= fcap) / the whole batch
+        const int caps_t = w.rows_t / w.pt.P < 64 ? w.rows_t / w.pt.P : 64, caps_b = w.rows_b / w.p16.P < 64 ? w.rows_b / w.p16.P : 64;
+        bf16_pass_launch<true>(r, Bf16Pass{w.pt, fcap, fcap, w.list1, few, w.c2v, w.c2i, caps_t, false}, collect16(r));
+        if (w.p16.Tt_pad > fcap)
+            bf16_pass_launch<true>(r, Bf16Pass{w.p16, w.p16.Tt_pad, r.Tt, w.list1, bulk, w.c2v, w.c2i, caps_b, false}, collect16(r));
     }
-    // a handful of frames: the exact scan costs less than the fixed cost of one more scoring pass over the library (~8 ms at 1 M
-    // rows against ~20 us per frame of exact scan)
-    const int caps_t = w.rows_t / w.pt.P < 64 ? w.rows_t / w.pt.P : 64, caps_b = w.rows_b / w.p16.P < 64 ? w.rows_b / w.p16.P : 64;
-    knn_exact_launch(w, rows_f32, norms, M, Tt, idx_base, k, w.list1, cnt1, out_val, out_idx, s, COLLECT_MIN);
-    gather_frames_kernel<<<(unsigned)fcap, 128, 0, s>>>(w.s_bf16, w.list1, cnt1, COLLECT_MIN, fcap, w.s_c);
-    knn_score_kernel<true><<<dim3((unsigned)(fcap / FT), w.pt.split), 256, SCORE_LDS, s>>>(
-        w.s_c, (const unsigned short*)lib_bf16, M, w.pt.tiles_total, w.pt.tiles_per_split, w.pt.P, w.c2v, w.c2i, cnt1, COLLECT_MIN, fcap, 1,
-        w.thr1, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, caps_t);
-    rescore_launch((unsigned)((fcap + 3) / 4), s, w.c2v, w.c2i, w.pt.P, caps_t, w.s_f32, rows_f32, norms, w.rows_hat, fcap, idx_base, k,
-                                                                 out_val, out_idx, w.list1, cnt1, COLLECT_MIN, fcap, w.list2, cnt2, CERT_Z,
-                                                                 KH, 1.0f, SD_PRIOR16, nullptr, nullptr, nullptr, 1, 0.0f);
-    if (w.p16.Tt_pad > fcap) {
-        gather_frames_kernel<<<(unsigned)w.p16.Tt_pad, 128, 0, s>>>(w.s_bf16, w.list1, cnt1, fcap, 0x7fffffff, w.s_c);
-        knn_score_kernel<true><<<dim3((unsigned)(w.p16.Tt_pad / FT), w.p16.split), 256, SCORE_LDS, s>>>(
-            w.s_c, (const unsigned short*)lib_bf16, M, w.p16.tiles_total, w.p16.tiles_per_split, w.p16.P, w.c2v, w.c2i, cnt1, fcap,
-            0x7fffffff, 1, w.thr1, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, caps_b);
-        rescore_launch((unsigned)((Tt + 3) / 4), s, w.c2v, w.c2i, w.p16.P, caps_b, w.s_f32, rows_f32, norms, w.rows_hat, Tt, idx_base, k,
-                                                                   out_val, out_idx, w.list1, cnt1, fcap, 0x7fffffff, w.list2, cnt2,
-                                                                   CERT_Z, KH, 1.0f, SD_PRIOR16, nullptr, nullptr, nullptr, 1, 0.0f);
-    }
-    knn_exact_launch(w, rows_f32, norms, M, Tt, idx_base, k, w.list2, cnt2, out_val, out_idx, s);
+    knn_exact_launch(r, w.list2, cnt2, GATE_ALL);
 }
 
-// The bf16 re-search of the frames in list[0 .. *cnt) (compacted), certified, behind either first stage:
+// The bf16 re-search of the frames in list0[0 .. *cnt) (compacted), certified, behind either first stage, by their count:
 //   up to RESEARCH_MIN frames: straight to the exact scan;
+//   tier 1a (.. one frame block): tier 1's split is chosen for 4096 frames (16 frame blocks x 16 splits): a hundred flagged frames keep
+//       ONE of its frame blocks busy, i.e. 16 CUs walk the whole library -- 9 ms at 1 M rows, which is what the 73 frames the fp6 stage
+//       leaves uncertified on the bench batch cost.  Here the one block's library is cut MAX_SPLIT ways (64 CUs, 1024 candidates per
+//       frame = what the rescoring kernel takes).  Same buffers as tier 1: the windows exclude each other;
 //   tier 1 (.. fcap frames): library split chosen for few frames;
-//   tier 2 (more): the split of the whole batch; blocks past the count exit at once.
-// Frames that fail the bf16 certificate land in list1 and go through the exact scan.
-static void bf16_tiers_launch(const SearchWs& w, const void* lib_bf16, const float* rows_f32, const float* norms, int64_t M,
-                              int64_t Tt, int64_t idx_base, int k, float* out_val, int32_t* out_idx, hipStream_t s) {
+//   bulk (more): the split of the whole batch, seeded (the frames are compacted: a block's 256 slots are the same in every split, so
+//       the seeds are indexed by slot); blocks past the count exit at once.
+// Frames that fail the bf16 certificate land in list1 and go through the collect tier.
+static void bf16_tiers_launch(const SearchRun& r) {
+    const SearchWs& w = r.w;
     int* cnt0 = w.stats + ST_FLAG8;
-    int* cnt1 = w.stats + ST_FLAG16;
-    const int fcap = w.fcap;
-    knn_exact_launch(w, rows_f32, norms, M, Tt, idx_base, k, w.list0, cnt0, out_val, out_idx, s, RESEARCH_MIN);
-    // tier 1a (round 5): RESEARCH_MIN < count <= one frame block.  Tier 1's split is chosen for 4096 frames (16 frame blocks x 16
-    // splits): a hundred flagged frames keep ONE of its frame blocks busy, i.e. 16 CUs walk the whole library -- 9 ms at 1 M rows,
-    // which is what the 73 frames the fp6 stage leaves uncertified on the bench batch cost.  Here the one block's library is cut
-    // MAX_SPLIT ways (64 CUs, 1024 candidates per frame = what the rescoring kernel takes).  Same buffers as tier 1: the gates
-    // (RESEARCH_MIN, TIER1A] / (TIER1A, fcap] exclude each other.
-    const int t1a = fcap < TIER1A ? fcap : TIER1A;
-    gather_frames_kernel<<<(unsigned)t1a, 128, 0, s>>>(w.s_bf16, w.list0, cnt0, RESEARCH_MIN, t1a, w.s_c);
-    knn_score_kernel<false><<<dim3(1, w.pa.split), 256, SCORE_LDS, s>>>(
-        w.s_c, (const unsigned short*)lib_bf16, M, w.pa.tiles_total, w.pa.tiles_per_split, w.pa.P, w.cv1, w.ci1, cnt0, RESEARCH_MIN, t1a, 1, nullptr, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, 0);
-    rescore_launch((unsigned)((t1a + 3) / 4), s, w.cv1, w.ci1, w.pa.P, KP, w.s_f32, rows_f32, norms, w.rows_hat, t1a, idx_base, k,
-                                                                out_val, out_idx, w.list0, cnt0, RESEARCH_MIN, t1a, w.list1, cnt1, CERT_Z, KH, 1.0f, SD_PRIOR16, w.det_q, w.det_lib, w.thr1, 0, w.lib_lo != nullptr ? SPLIT_BOUND : 0.0f);
-    if (fcap > t1a) {
-    gather_frames_kernel<<<(unsigned)fcap, 128, 0, s>>>(w.s_bf16, w.list0, cnt0, t1a, fcap, w.s_c);
-    knn_score_kernel<false><<<dim3((unsigned)(fcap / FT), w.pt.split), 256, SCORE_LDS, s>>>(
-        w.s_c, (const unsigned short*)lib_bf16, M, w.pt.tiles_total, w.pt.tiles_per_split, w.pt.P, w.cv1, w.ci1, cnt0, t1a, fcap, 1, nullptr, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, 0);
-    rescore_launch((unsigned)((fcap + 3) / 4), s, w.cv1, w.ci1, w.pt.P, KP, w.s_f32, rows_f32, norms, w.rows_hat, fcap, idx_base, k,
-                                                                 out_val, out_idx, w.list0, cnt0, t1a, fcap, w.list1, cnt1, CERT_Z, KH, 1.0f, SD_PRIOR16, w.det_q, w.det_lib, w.thr1, 0, w.lib_lo != nullptr ? SPLIT_BOUND : 0.0f);
-    }
-    if (w.p16.Tt_pad > fcap) {
-        gather_frames_kernel<<<(unsigned)w.p16.Tt_pad, 128, 0, s>>>(w.s_bf16, w.list0, cnt0, fcap, 0x7fffffff, w.s_c);
-        // (the frames are compacted: a block's 256 slots are the same in every split, so the seeds are indexed by slot)
-        const SeedArgs sa = seeds_for(w, w.p16.Tt_pad / FT, w.p16.split, k, w.det_q != nullptr ? SEED_MARGIN16_STRICT : SEED_MARGIN16,
-                                      ST_SEEDED16, s);
-        knn_score_kernel<false><<<dim3((unsigned)(w.p16.Tt_pad / FT), w.p16.split), 256, SCORE_LDS, s>>>(
-            w.s_c, (const unsigned short*)lib_bf16, M, w.p16.tiles_total, w.p16.tiles_per_split, w.p16.P, w.cv, w.ci, cnt0, fcap,
-            0x7fffffff, 1, nullptr, sa, 0);
-        rescore_launch((unsigned)((Tt + 3) / 4), s, w.cv, w.ci, w.p16.P, KP, w.s_f32, rows_f32, norms, w.rows_hat, Tt, idx_base, k,
-                                                                   out_val, out_idx, w.list0, cnt0, fcap, 0x7fffffff, w.list1, cnt1,
-                                                                   CERT_Z, KH, 1.0f, SD_PRIOR16, w.det_q, w.det_lib, w.thr1, 0, w.lib_lo != nullptr ? SPLIT_BOUND : 0.0f);
-    }
-    collect_tier_launch(w, lib_bf16, rows_f32, norms, M, Tt, idx_base, k, out_val, out_idx, s);
+    const int fcap = w.fcap, t1a = fcap < TIER1A ? fcap : TIER1A;
+    const Gate one_block{cnt0, RESEARCH_MIN, t1a}, few{cnt0, t1a, fcap}, bulk{cnt0, fcap, GATE_ALL};
+    knn_exact_launch(r, w.list0, cnt0, RESEARCH_MIN);
+    bf16_pass_launch<false>(r, Bf16Pass{w.pa, t1a, t1a, w.list0, one_block, w.cv1, w.ci1, 0, false}, certify16(r));
+    if (fcap > t1a) bf16_pass_launch<false>(r, Bf16Pass{w.pt, fcap, fcap, w.list0, few, w.cv1, w.ci1, 0, false}, certify16(r));
+    if (w.p16.Tt_pad > fcap)
+        bf16_pass_launch<false>(r, Bf16Pass{w.p16, w.p16.Tt_pad, r.Tt, w.list0, bulk, w.cv, w.ci, 0, true}, certify16(r));
+    collect_tier_launch(r);
 }
 
-// Search with the bf16 MFMA as the first candidate stage: every frame's candidate set is certified against the bf16 score
-// error measured on its own rescored candidates; frames that fail go through the exact fp32 scan.  k > 8 (deeper than a
-// half-list of the candidate stage): the exact scan for every frame.
-static int knn_search_impl(const float* src, int N, int T, const void* lib_bf16, const float* rows_f32,
-                           const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
-                           void* ws, void* stream, hipEvent_t g_ev_start, hipEvent_t g_ev_stop, const float* strict_bound = nullptr,
-                           const void* lib_lo = nullptr, const float* rows_hat = nullptr) {
-    ALIVE_CHECK_ARG(src && lib_bf16 && rows_f32 && norms && out_val && out_idx && ws, "alive_knn_search: null pointer");
-    if (int rc = check_search_args("alive_knn_search", src, ws, N, T, k, M)) return rc;
-    const int64_t Tt = (int64_t)N * T;
-    SearchWs w = ws_layout(ws, Tt, M, k, strict_bound != nullptr && lib_lo != nullptr);
-    w.rows_hat = rows_hat;
-    if (strict_bound != nullptr) {         // deterministic certificate: per-frame rounding error + the library's (alive_library_rounding_bound)
-        w.det_q = w.dq;
-        w.det_lib = strict_bound;
-        w.lib_lo = (const unsigned short*)lib_lo;      // nullptr: no split tier, collect-tier overflow goes straight to the exact scan
+// Search with the bf16 MFMA as the first candidate stage (forms ALIVE_KNN_BF16 and ALIVE_KNN_STRICT): every frame's candidate set is
+// certified against the bf16 score error measured on its own rescored candidates -- strict: against the deterministic bound, per-frame
+// rounding error + the library's (alive_library_rounding_bound) -- and frames that fail go through the collect tier and the exact fp32
+// scan.  k > 8 (deeper than a half-list of the candidate stage): the exact scan for every frame.
+static int knn_search_bf16(const char* who, const AliveKnnSearch& a, hipStream_t s) {
+    ALIVE_CHECK_ARG(a.src && a.lib_bf16 && a.rows_f32 && a.norms && a.out_val && a.out_idx && a.ws, "%s: null pointer", who);
+    if (int rc = check_search_args(who, a)) return rc;
+    const bool strict = a.form == ALIVE_KNN_STRICT;
+    const int64_t Tt = (int64_t)a.N * a.T;
+    const SearchWs w = ws_layout(a.ws, Tt, a.M, a.k, strict && a.lib_lo != nullptr ? WS_STRICT : WS_FAST);
+    SearchRun r{a, w, Tt, s};
+    if (strict) {
+        r.det_q = w.dq;
+        r.det_lib = a.bound;
+        r.lib_lo = (const unsigned short*)a.lib_lo;    // nullptr: no split tier, collect-tier overflow goes straight to the exact scan
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (Tt * k <= 64 && M <= SCAN_ROWS_MAX)            // a handful of frames: exact fp32 scan of the rows, no candidate stage
-        return knn_scan_launch(src, T, Tt, rows_f32, norms, M, idx_base, k, w.s_f32, w.s_bf16, w.pv, w.pi, out_val, out_idx, w.stats, s, g_ev_start, g_ev_stop);
-    if (int rc = lds_optin("alive_knn_search")) return rc;
-    stats_init_kernel<<<1, 64, 0, s>>>(w.stats, k > KH ? TIER_EXACT_ALL : TIER_BF16);
-    src_prep_launch(w, src, T, Tt, s);
-    if (k > KH) {
-        if (g_ev_start) (void)hipEventRecord(g_ev_start, s);
-        knn_exact_launch(w, rows_f32, norms, M, Tt, idx_base, k, nullptr, nullptr, out_val, out_idx, s);
-        if (g_ev_stop) (void)hipEventRecord(g_ev_stop, s);
-        ALIVE_CHECK_LAUNCH("alive_knn_search(exact)");
+    hipEvent_t ev_start = (hipEvent_t)a.ev_start, ev_stop = (hipEvent_t)a.ev_stop;
+    if (Tt * a.k <= 64 && a.M <= SCAN_ROWS_MAX) return knn_scan_launch(who, r);
+    if (int rc = lds_optin(who)) return rc;
+    stats_init_kernel<<<1, 64, 0, s>>>(w.stats, a.k > KH ? TIER_EXACT_ALL : TIER_BF16);
+    src_prep_launch(r);
+    if (a.k > KH) {
+        if (ev_start) (void)hipEventRecord(ev_start, s);
+        knn_exact_launch(r, nullptr, nullptr, GATE_ALL);
+        if (ev_stop) (void)hipEventRecord(ev_stop, s);
+        ALIVE_CHECK_LAUNCH(who);
         return ALIVE_OK;
     }
     const SearchPlan& p = w.p16;
-    const SeedArgs sa = seeds_for(w, p.Tt_pad / FT, p.split, k, w.det_q != nullptr ? SEED_MARGIN16_STRICT : SEED_MARGIN16, ST_SEEDED16, s);
-    if (g_ev_start) (void)hipEventRecord(g_ev_start, s);             // behind the memset of the seed flags: the events bracket the kernel alone
+    const SeedArgs sa = seeds16(r, p.Tt_pad / FT, p.split);
+    if (ev_start) (void)hipEventRecord(ev_start, s);                 // behind the memset of the seed flags: the events bracket the kernel alone
     knn_score_kernel<false><<<dim3((unsigned)(p.Tt_pad / FT), p.split), 256, SCORE_LDS, s>>>(
-        w.s_bf16, (const unsigned short*)lib_bf16, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, nullptr, 0, 0, 0, nullptr, sa, 0);
-    if (g_ev_stop) (void)hipEventRecord(g_ev_stop, s);
-    rescore_launch((unsigned)((Tt + 3) / 4), s, w.cv, w.ci, p.P, KP, w.s_f32, rows_f32, norms, w.rows_hat, Tt, idx_base, k,
-                                                               out_val, out_idx, nullptr, nullptr, 0, 0, w.list1, w.stats + ST_FLAG16,
-                                                               CERT_Z, KH, 1.0f, SD_PRIOR16, w.det_q, w.det_lib, w.thr1, 0, w.lib_lo != nullptr ? SPLIT_BOUND : 0.0f);
-    collect_tier_launch(w, lib_bf16, rows_f32, norms, M, Tt, idx_base, k, out_val, out_idx, s);
-    ALIVE_CHECK_LAUNCH("alive_knn_search");
+        w.s_bf16, (const unsigned short*)a.lib_bf16, a.M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, nullptr, 0, 0, 0, nullptr, sa, 0);
+    if (ev_stop) (void)hipEventRecord(ev_stop, s);
+    rescore_launch((unsigned)((Tt + 3) / 4), s, certify16(r));
+    collect_tier_launch(r);
+    ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
 }
 
-// The same search with the candidate stage on the fp8 MFMA (knn_score8_kernel); lib_f8 from alive_library_pack_fp8.
-//   probe   (batches of >= 16384 frames) the fp8 stage + its certificate on a sample of 1024 frames; when more than 40 % of
-//           them fail -- a library whose best cosines lie closer together than the fp8 error -- the fp8 pass over the
-//           batch is skipped (mode 1) and every frame goes straight to the bf16 stage;
-//   fp8     (mode 0) candidate stage on the fp8 MFMA, exact rescoring, certificate -> list0;
-//   bf16    the frames of list0 (all of them in mode 1) through the bf16 candidate stage, exact rescoring, certificate
-//           with the bf16 error statistics -> list1;
-//   exact   the frames of list1 through the brute-force fp32 scan.
+// The same search with a block-scaled first stage (forms ALIVE_KNN_FP8, _FP6, _FP8_ROT, _FP6_SUB); a.lib_stage from alive_library_pack_fp8
+// / _fp6 / _fp8_rot.
+//   probe   (batches of >= 16384 frames) the stage + its certificate on a sample of 1024 frames; when more than 55 % of them fail -- a
+//           library whose best cosines lie closer together than the stage's error -- the pass over the batch is skipped (mode 1) and
+//           every frame goes straight to the bf16 stage;
+//   stage   (mode 0) candidate stage on the fp8 / fp6 MFMA, exact rescoring, certificate -> list0;
+//   bf16    the frames of list0 (all of them in mode 1) through the bf16 candidate stage, exact rescoring, certificate with the bf16
+//           error statistics -> list1;
+//   exact   the frames of list1 through the collect tier and the brute-force fp32 scan.
 // All of it is launched up front -- the kernels read the counters on the device and return at once when a tier is empty.
+//   rotated: lib_stage holds the ROTATED codes of the rows and a.y the frames' rotated coordinates [N][576][T]: the frames' codes come from
+//           rot_codes_kernel, the stage's error prior is SD_PRIOR8R; everything else is the plain search's, on the original rows;
+//   subspace: a.y = [U | u]^T src -- or, a.y null, formed here from a.sub_w as a plane GEMM (three bf16 MFMAs per product, as alive_conv1d's
+//           split form, without its fp32 loads and in-loop splits): src -> two k-blocked bf16 planes -> y, both in the subspace workspace;
+//   lazy_plain (subspace form through alive_knn_search_unit): the plain fp6 image of the frames is built only where it is read -- by a due
+//           probe, or by the plain stage when the gate sends the batch there.  clip6 keeps its meaning: cleared first, bytes are only ever set.
+static int knn_search_scaled(const char* who, const AliveKnnSearch& a, bool lazy_plain, hipStream_t s) {
+    ALIVE_CHECK_ARG(a.src && a.lib_stage && a.lib_bf16 && a.rows_f32 && a.norms && a.out_val && a.out_idx && a.ws, "%s: null pointer", who);
+    if (int rc = check_search_args(who, a)) return rc;
+    if (a.k > KH) {                        // deeper than the stage's lists: the bf16 form's exact scan of every frame
+        AliveKnnSearch b = a;
+        b.form = ALIVE_KNN_BF16;
+        return knn_search_bf16(who, b, s);
+    }
+    const bool sub = a.form == ALIVE_KNN_FP6_SUB, rot = a.form == ALIVE_KNN_FP8_ROT, f6 = sub || a.form == ALIVE_KNN_FP6;
+    const int k = a.k;
+    const int64_t Tt = (int64_t)a.N * a.T, M = a.M;
+    const SearchWs w = ws_layout(a.ws, Tt, M, k, sub ? WS_SUB : WS_FAST);       // one layout: the plane GEMM's operands and the search
+    const SearchRun r{a, w, Tt, s};
+    if (Tt * k <= 64 && M <= SCAN_ROWS_MAX) return knn_scan_launch(who, r);     // streaming ring: the exact scan, no candidate stage at all
+    if (int rc = lds_optin(who)) return rc;
+    const float* y_sub = sub ? a.y : nullptr;
+    if (sub && y_sub == nullptr) {
+        ALIVE_CHECK_ARG(Tt * SUB_C < (1ll << 30), "%s: %lld frames exceed the plane GEMM's 32-bit offsets (pass y)", who, (long long)Tt);
+        if (int rc = alive_to_planes(a.src, a.N, D, a.T, 2, w.sub_planes, s)) return rc;
+        AliveGemm g{};
+        g.W = a.sub_w; g.P = w.sub_planes; g.N = a.N; g.T = a.T; g.Ci = D; g.Co = SUB_C; g.planes = 2; g.Y = w.sub_y;
+        if (int rc = alive_gemm_planes(&g, s)) return rc;
+        y_sub = w.sub_y;
+    }
+    const bool lazy = lazy_plain && sub;
+    // wide: the subspace kernel runs in its 512-frame form, on the 512-frame plan -- and so does, on the same library splits, the plain
+    // fp6 kernel behind the same gate word (384-frame blocks over the frames padded to 512: both write cand[frame][P][KP8])
+    const bool wide = sub && sub_wide(w.p6w);
+    const SearchPlan& p = f6 ? (wide ? w.p6w : w.p6) : w.p8;
+    const SearchPlan& pp = f6 ? w.pp6 : w.pp;
+    // frames the operand kernels cover: the plan's blocks -- of both block sizes when the wide form may hand over to the plain kernel
+    const int64_t Tpad = wide ? std::max(w.p6.Tt_pad, w.p6w.Tt_pad) : p.Tt_pad;
+    const int ft = f6 ? FT6 : FT, probe_pad = f6 ? w.probe_pad6 : w.probe_pad, lds = f6 ? SCORE6_LDS : SCORE8_LDS;
+    const float pre = f6 ? 1.0f / (F6_SCALE * F6_SCALE) : 1.0f / (F8_SCALE * F8_SCALE),
+                prior = f6 ? SD_PRIOR6 : (rot ? SD_PRIOR8R : SD_PRIOR8);
+    const unsigned char* lib_stage = (const unsigned char*)a.lib_stage;
+    hipEvent_t ev_start = (hipEvent_t)a.ev_start, ev_stop = (hipEvent_t)a.ev_stop;
+    // (history tag: library size, frame count and stage -- a workspace that was last used for another search starts over)
+    const int hist_tag = (int)(((uint64_t)M * 0x9E3779B1u) ^ ((uint64_t)Tt * 0x85EBCA77u) ^
+                               (f6 ? (sub ? 0x36u : 0x6u) : (rot ? 0x18u : 0x8u))) | 1;
+    stats_init_kernel<<<1, 64, 0, s>>>(w.stats, f6 ? TIER_FP6 : TIER_FP8, w.probe_n > 0 ? hist_tag : 0);
+    src_prep_launch(r);
+    if (f6) {
+        const int64_t n32 = Tpad * D / 32;
+        (void)hipMemsetAsync(w.clip6, 0, (size_t)Tpad, s);
+        if (!lazy || w.probe_n > 0)
+            to_fp6_kernel<<<(unsigned)((n32 + 255) / 256), 256, 0, s>>>(w.s_bf16, n32, w.p16.Tt_pad * D / 32, (u32x4*)w.s_f8, w.clip6, lazy ? 1 : 0,
+                                                                        w.stats + ST_PROBE_GATE);
+        if (sub)
+            sub_codes_kernel<<<(unsigned)(Tpad / 32), 256, 0, s>>>(y_sub, w.sub_nrm, a.T, Tt, Tpad, w.sub_f6, w.sub_g, w.sub_flag, w.stats);
+    } else if (rot) {
+        rot_codes_kernel<<<(unsigned)(p.Tt_pad / 32), 256, 0, s>>>(a.y, Tt, p.Tt_pad, a.T, 1, a.rot_c0, w.s_f8);
+    } else {
+        const int64_t n8 = p.Tt_pad * D / 8;
+        src_to_fp8_kernel<<<(unsigned)((n8 + 255) / 256), 256, 0, s>>>(w.s_bf16, n8, (uint2*)w.s_f8);
+    }
+    int* mode = w.stats + ST_MODE;
+    const unsigned char* force_fail = f6 ? w.clip6 : nullptr;
+    if (w.probe_n > 0) {
+        const int* pgate = w.stats + ST_PROBE_GATE;      // 0: the history of this workspace says no probe is needed (all five launches return at once)
+        probe_gather_kernel<<<(unsigned)probe_pad, 64, 0, s>>>(w.s_f8, Tt, w.probe_n, probe_pad, w.s_p8, w.p_list, pgate);
+        stage_launch(f6 ? STAGE_PROBE6 : STAGE_PROBE8, dim3((unsigned)(probe_pad / ft), pp.split), lds, s,
+                     StageOps{w.s_p8, lib_stage, nullptr, nullptr, M, pp, w.cvp, w.cip}, Gate{pgate, 0, 1}, NO_SEEDS);
+        // the sample's own rescoring.  The kernel writes a frame's result to the frame's own output rows (out[frame]), so
+        // the sample's exact lists land in the caller's outputs and are overwritten by the pass over the batch; its flagged
+        // frames (second half of p_list) are only counted
+        Rescore rs = certify8(r, pp, pre, prior, force_fail);
+        rs.cand_val = w.cvp; rs.cand_idx = w.cip;
+        rs.Tt = w.probe_n; rs.frame_list = w.p_list; rs.gate = Gate{pgate, GATE_BOOL, 0};
+        rs.flag_list = w.p_list + probe_pad; rs.flag_cnt = w.stats + ST_PROBE_CNT;
+        rescore_launch((unsigned)((w.probe_n + 3) / 4), s, rs);
+        probe_decide_kernel<<<1, 1, 0, s>>>(w.stats, w.probe_n, PROBE_NUM, PROBE_DEN);
+    }
+    if (sub) sub_select_kernel<<<(unsigned)((Tpad + 255) / 256), 256, 0, s>>>(w.sub_flag, w.clip6, Tpad, w.stats, wide ? FT6W : FT6);
+    if (lazy) {
+        const int64_t n32 = Tpad * D / 32;
+        to_fp6_kernel<<<(unsigned)((n32 + 255) / 256), 256, 0, s>>>(w.s_bf16, n32, w.p16.Tt_pad * D / 32, (u32x4*)w.s_f8, w.clip6, 2,
+                                                                    w.probe_n > 0 ? w.stats + ST_PROBE_GATE : nullptr, w.stats + ST_SUB_GATE);
+    }
+    // ---- mode 0: the fp8 / fp6 stage first ----
+    const int64_t fb = wide ? p.Tt_pad / FT6W : p.Tt_pad / ft, fb6 = w.p6.Tt_pad / FT6;
+    const SeedArgs sa8 = seeds_for(w, fb, p.split, k, f6 ? SEED_MARGIN6 : SEED_MARGIN8, ST_SEEDED, s, f6 ? SEED_MIN_FB6 : SEED_MIN_FB);
+    if (wide && sa8.flag != nullptr && fb6 > fb)       // the plain kernel's 384-frame blocks are more: their flags too
+        (void)hipMemsetAsync(w.tau_flag, 0, (size_t)fb6 * p.split * sizeof(int), s);
+    if (ev_start) (void)hipEventRecord(ev_start, s);                 // behind the memset of the seed flags: the events bracket the kernel alone
+    const StageOps plain{w.s_f8, lib_stage, nullptr, nullptr, M, p, w.cv, w.ci};
+    if (sub) {                         // one of the two runs: the gate word of sub_select_kernel (1 subspace, 2 plain, 0 neither)
+        const int* gate = w.stats + ST_SUB_GATE;
+        stage_launch(wide ? STAGE_SUB6W : STAGE_SUB6, dim3((unsigned)fb, p.split), wide ? SUB6W_LDS : SUB6_LDS, s,
+                     StageOps{w.sub_f6, (const unsigned char*)a.lib_sub, a.rho, w.sub_g, M, p, w.cv, w.ci}, Gate{gate, 0, 1}, sa8);
+        stage_launch(STAGE_SCORE6, dim3((unsigned)fb6, p.split), lds, s, plain, Gate{gate, 1, 2}, sa8);
+    } else {
+        stage_launch(f6 ? STAGE_SCORE6 : STAGE_SCORE8, dim3((unsigned)(p.Tt_pad / ft), p.split), lds, s, plain, Gate{mode, -1, 0}, sa8);
+    }
+    if (ev_stop) (void)hipEventRecord(ev_stop, s);
+    Rescore rs = certify8(r, p, pre, prior, force_fail);
+    rs.gate = Gate{mode, -1, 0};
+    rescore_launch((unsigned)((Tt + 3) / 4), s, rs);
+    // ---- mode 1: bf16 first (every frame into list0) ----
+    if (w.probe_n > 0) flag_all_kernel<<<(unsigned)((Tt + 255) / 256), 256, 0, s>>>(w.list0, w.stats + ST_FLAG8, Tt, mode, 0, 1);
+    if (w.probe_n > 0) probe_history_kernel<<<1, 1, 0, s>>>(w.stats, Tt);        // (ST_FLAG8 is final here: the tiers below only read it)
+    bf16_tiers_launch(r);
+    ALIVE_CHECK_LAUNCH(who);
+    return ALIVE_OK;
+}
+
+// Every entry point of the tiered searches ends here: the form's own operands are checked, then the form's search runs from the record.
+// unit: through alive_knn_search_unit (the subspace form then builds the plain fp6 image lazily); a named entry checks its operands
+// itself, under its own wording, before it comes here.
+static int knn_search_dispatch(const char* who, const AliveKnnSearch& a, bool unit, hipStream_t s) {
+    const int f = a.form;
+    ALIVE_CHECK_ARG(f >= ALIVE_KNN_BF16 && f <= ALIVE_KNN_FP6_SUB, "%s: form %d", who, f);
+    ALIVE_CHECK_ARG(f != ALIVE_KNN_STRICT || a.bound != nullptr, "%s: strict form without a bound (alive_library_rounding_bound)", who);
+    ALIVE_CHECK_ARG(f != ALIVE_KNN_FP8_ROT || a.y != nullptr, "%s: rotated form without the rotated frames", who);
+    ALIVE_CHECK_ARG(f != ALIVE_KNN_FP6_SUB || ((a.y || a.sub_w) && a.lib_sub && a.rho), "%s: null subspace operand", who);
+    if (f == ALIVE_KNN_BF16 || f == ALIVE_KNN_STRICT) return knn_search_bf16(who, a, s);
+    return knn_search_scaled(who, a, unit && f == ALIVE_KNN_FP6_SUB, s);
+}
+
+// (a named entry point leaves rows_hat NULL in its record, so its arithmetic is the named entry's own)
 extern "C" int alive_knn_search(const float* src, int N, int T, const void* lib_bf16, const float* rows_f32,
                                 const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
                                 void* ws, void* stream) {
-    return knn_search_impl(src, N, T, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream, nullptr, nullptr);
+    const AliveKnnSearch a{.form = ALIVE_KNN_BF16, .N = N, .T = T, .k = k, .src = src, .lib_bf16 = lib_bf16, .rows_f32 = rows_f32, .norms = norms,
+                           .M = M, .idx_base = idx_base, .out_val = out_val, .out_idx = out_idx, .ws = ws};
+    return knn_search_dispatch("alive_knn_search", a, false, (hipStream_t)stream);
 }
 // Strict search: the bf16 candidate stage with a DETERMINISTIC certificate (knn_rescore_kernel: det_bound), frames that
 // fail it through the exact fp32 scan.  No statistical assumption anywhere: the result is the exact top-k of the rescoring
@@ -4009,9 +4228,12 @@ extern "C" int alive_knn_search_strict(const float* src, int N, int T, const voi
                                        const float* norms, const float* bound, int64_t M, int64_t idx_base, int k, float* out_val,
                                        int32_t* out_idx, void* ws, void* stream, void* ev_start, void* ev_stop) {
     ALIVE_CHECK_ARG(bound != nullptr, "alive_knn_search_strict: null bound (alive_library_rounding_bound)");
-    return knn_search_impl(src, N, T, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream,
-                           (hipEvent_t)ev_start, (hipEvent_t)ev_stop, bound, lib_lo);
+    const AliveKnnSearch a{.form = ALIVE_KNN_STRICT, .N = N, .T = T, .k = k, .src = src, .lib_bf16 = lib_bf16, .lib_lo = lib_lo, .rows_f32 = rows_f32,
+                           .norms = norms, .bound = bound, .M = M, .idx_base = idx_base, .out_val = out_val, .out_idx = out_idx, .ws = ws,
+                           .ev_start = ev_start, .ev_stop = ev_stop};
+    return knn_search_dispatch("alive_knn_search_strict", a, false, (hipStream_t)stream);
 }
+
 
 // lo plane of a packed library (strict searches): lib_lo[M_pad][768] = bf16(r^ - lib_bf16), 2 * 768 * alive_library_padded_rows(M) bytes
 extern "C" int alive_library_pack_lo(const void* lib_bf16, const float* rows_f32, const float* norms, int64_t M, void* lib_lo,
@@ -4037,133 +4259,26 @@ extern "C" int alive_library_rounding_bound(const void* lib_bf16, const float* r
 extern "C" int alive_knn_search_timed(const float* src, int N, int T, const void* lib_bf16, const float* rows_f32,
                                       const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
                                       void* ws, void* stream, void* ev_start, void* ev_stop) {
-    return knn_search_impl(src, N, T, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream,
-                           (hipEvent_t)ev_start, (hipEvent_t)ev_stop);
+    const AliveKnnSearch a{.form = ALIVE_KNN_BF16, .N = N, .T = T, .k = k, .src = src, .lib_bf16 = lib_bf16, .rows_f32 = rows_f32, .norms = norms,
+                           .M = M, .idx_base = idx_base, .out_val = out_val, .out_idx = out_idx, .ws = ws, .ev_start = ev_start, .ev_stop = ev_stop};
+    return knn_search_dispatch("alive_knn_search_timed", a, false, (hipStream_t)stream);
 }
 
-static int knn_search_fp8_impl(const float* src, int N, int T, const void* lib_f8, const void* lib_bf16, const float* rows_f32,
-                               const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
-                               void* ws, void* stream, hipEvent_t g_ev_start, hipEvent_t g_ev_stop, int fmt = 0,
-                               const float* y_rot = nullptr, float rot_c0 = 0.0f, const float* y_sub = nullptr,
-                               const void* lib_sub = nullptr, const float* rho = nullptr, const float* rows_hat = nullptr,
-                               bool lazy_plain = false) {
-    // y_rot != NULL (fp8 only): lib_f8 holds the ROTATED codes of the rows (alive_library_pack_fp8_rot) and y_rot the frames' rotated
-    // coordinates [N][576][T]: the frames' codes come from rot_codes_kernel, the stage's error prior is SD_PRIOR8R; everything else --
-    // exact rescoring on the original rows, certificates, the bf16 tiers on lib_bf16 -- is the plain search's
-    ALIVE_CHECK_ARG(src && lib_f8 && lib_bf16 && rows_f32 && norms && out_val && out_idx && ws, "alive_knn_search_fp8: null pointer");
-    if (int rc = check_search_args("alive_knn_search_fp8", src, ws, N, T, k, M)) return rc;
-    const int64_t Tt = (int64_t)N * T;
-    if (k > KH)
-        return knn_search_impl(src, N, T, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream, g_ev_start, g_ev_stop);
-    SearchWs w = ws_layout(ws, Tt, M, k, false, y_sub != nullptr);
-    w.rows_hat = rows_hat;
-    // lazy_plain (alive_knn_search_unit, subspace form): the plain fp6 image of the frames is built only where it is read -- by a due
-    // probe, or by the plain stage when the gate sends the batch there.  clip6 keeps its meaning: cleared first, bytes are only ever set.
-    const bool lazy = lazy_plain && y_sub != nullptr;
-    const bool f6 = fmt == 2;
-    // wide: the subspace kernel runs in its 512-frame form, on the 512-frame plan -- and so does, on the same library splits, the plain
-    // fp6 kernel behind the same gate word (384-frame blocks over the frames padded to 512: both write cand[frame][P][KP8])
-    const bool wide = f6 && y_sub != nullptr && sub_wide(w.p6w);
-    const SearchPlan& p = f6 ? (wide ? w.p6w : w.p6) : w.p8;
-    const SearchPlan& pp = f6 ? w.pp6 : w.pp;
-    // frames the operand kernels cover: the plan's blocks -- of both block sizes when the wide form may hand over to the plain kernel
-    const int64_t Tpad = wide ? std::max(w.p6.Tt_pad, w.p6w.Tt_pad) : p.Tt_pad;
-    const int ft = f6 ? FT6 : FT, probe_pad = f6 ? w.probe_pad6 : w.probe_pad, lds = f6 ? SCORE6_LDS : SCORE8_LDS;
-    const float pre = f6 ? 1.0f / (F6_SCALE * F6_SCALE) : 1.0f / (F8_SCALE * F8_SCALE),
-                prior = f6 ? SD_PRIOR6 : (y_rot != nullptr ? SD_PRIOR8R : SD_PRIOR8);
-    hipStream_t s = (hipStream_t)stream;
-    if (Tt * k <= 64 && M <= SCAN_ROWS_MAX)            // streaming ring: the exact scan, no candidate stage at all
-        return knn_scan_launch(src, T, Tt, rows_f32, norms, M, idx_base, k, w.s_f32, w.s_bf16, w.pv, w.pi, out_val, out_idx, w.stats, s, g_ev_start, g_ev_stop);
-    if (int rc = lds_optin("alive_knn_search_fp8")) return rc;
-    // (history tag: library size, frame count and stage -- a workspace that was last used for another search starts over)
-    const int hist_tag = (int)(((uint64_t)M * 0x9E3779B1u) ^ ((uint64_t)Tt * 0x85EBCA77u) ^
-                               (f6 ? (y_sub != nullptr ? 0x36u : 0x6u) : (y_rot != nullptr ? 0x18u : 0x8u))) | 1;
-    stats_init_kernel<<<1, 64, 0, s>>>(w.stats, f6 ? TIER_FP6 : TIER_FP8, w.probe_n > 0 ? hist_tag : 0);
-    src_prep_launch(w, src, T, Tt, s);
-    if (f6) {
-        const int64_t n32 = Tpad * D / 32;
-        (void)hipMemsetAsync(w.clip6, 0, (size_t)Tpad, s);
-        if (!lazy || w.probe_n > 0)
-            to_fp6_kernel<<<(unsigned)((n32 + 255) / 256), 256, 0, s>>>(w.s_bf16, n32, w.p16.Tt_pad * D / 32, (u32x4*)w.s_f8, w.clip6, lazy ? 1 : 0,
-                                                                        w.stats + ST_PROBE_GATE);
-        if (y_sub != nullptr)
-            sub_codes_kernel<<<(unsigned)(Tpad / 32), 256, 0, s>>>(y_sub, w.sub_nrm, T, Tt, Tpad, w.sub_f6, w.sub_g, w.sub_flag, w.stats);
-    } else if (y_rot != nullptr) {
-        rot_codes_kernel<<<(unsigned)(p.Tt_pad / 32), 256, 0, s>>>(y_rot, Tt, p.Tt_pad, T, 1, rot_c0, w.s_f8);
-    } else {
-        const int64_t n8 = p.Tt_pad * D / 8;
-        src_to_fp8_kernel<<<(unsigned)((n8 + 255) / 256), 256, 0, s>>>(w.s_bf16, n8, (uint2*)w.s_f8);
-    }
-    int* mode = w.stats + ST_MODE;
-    if (w.probe_n > 0) {
-        const int* pgate = w.stats + ST_PROBE_GATE;      // 0: the history of this workspace says no probe is needed (all five launches return at once)
-        probe_gather_kernel<<<(unsigned)probe_pad, 64, 0, s>>>(w.s_f8, Tt, w.probe_n, probe_pad, w.s_p8, w.p_list, pgate);
-        if (f6)
-            knn_probe6_kernel<<<dim3((unsigned)(probe_pad / ft), pp.split), 256, lds, s>>>(
-                w.s_p8, (const unsigned char*)lib_f8, M, pp.tiles_total, pp.tiles_per_split, pp.P, w.cvp, w.cip, pgate);
-        else
-            knn_probe8_kernel<<<dim3((unsigned)(probe_pad / ft), pp.split), 256, lds, s>>>(
-                w.s_p8, (const unsigned char*)lib_f8, M, pp.tiles_total, pp.tiles_per_split, pp.P, w.cvp, w.cip, pgate);
-        // the sample's own rescoring.  The kernel writes a frame's result to the frame's own output rows (out[frame]), so
-        // the sample's exact lists land in the caller's outputs and are overwritten by the pass over the batch; its flagged
-        // frames (second half of p_list) are only counted
-        rescore_launch((unsigned)((w.probe_n + 3) / 4), s, w.cvp, w.cip, pp.P, KP8, w.s_f32, rows_f32, norms, w.rows_hat, w.probe_n,
-                                                                          idx_base, k, out_val, out_idx, w.p_list, pgate, GATE_BOOL, 0,
-                                                                          w.p_list + probe_pad, w.stats + ST_PROBE_CNT, CERT_Z, KH8,
-                                                                          pre, prior, nullptr, nullptr, nullptr, 0, 0.0f, f6 ? w.clip6 : nullptr);
-        probe_decide_kernel<<<1, 1, 0, s>>>(w.stats, w.probe_n, PROBE_NUM, PROBE_DEN);
-    }
-    if (y_sub != nullptr)
-        sub_select_kernel<<<(unsigned)((Tpad + 255) / 256), 256, 0, s>>>(w.sub_flag, w.clip6, Tpad, w.stats, wide ? FT6W : FT6);
-    if (lazy) {
-        const int64_t n32 = Tpad * D / 32;
-        to_fp6_kernel<<<(unsigned)((n32 + 255) / 256), 256, 0, s>>>(w.s_bf16, n32, w.p16.Tt_pad * D / 32, (u32x4*)w.s_f8, w.clip6, 2,
-                                                                    w.probe_n > 0 ? w.stats + ST_PROBE_GATE : nullptr, w.stats + ST_SUB_GATE);
-    }
-    // ---- mode 0: the fp8 / fp6 stage first ----
-    const int64_t fb = wide ? p.Tt_pad / FT6W : p.Tt_pad / ft, fb6 = w.p6.Tt_pad / FT6;
-    const SeedArgs sa8 = seeds_for(w, fb, p.split, k, f6 ? SEED_MARGIN6 : SEED_MARGIN8, ST_SEEDED, s, f6 ? SEED_MIN_FB6 : SEED_MIN_FB);
-    if (wide && sa8.flag != nullptr && fb6 > fb)       // the plain kernel's 384-frame blocks are more: their flags too
-        (void)hipMemsetAsync(w.tau_flag, 0, (size_t)fb6 * p.split * sizeof(int), s);
-    if (g_ev_start) (void)hipEventRecord(g_ev_start, s);             // behind the memset of the seed flags: the events bracket the kernel alone
-    if (y_sub != nullptr) {            // one of the two runs: the gate word of sub_select_kernel (1 subspace, 2 plain, 0 neither)
-        const int* gate = w.stats + ST_SUB_GATE;
-        if (wide)
-            knn_sub6w_kernel<<<dim3((unsigned)fb, p.split), 256, SUB6W_LDS, s>>>(
-                w.sub_f6, (const unsigned char*)lib_sub, rho, w.sub_g, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, gate, 0, 1, sa8);
-        else
-            knn_sub6_kernel<<<dim3((unsigned)fb, p.split), 256, SUB6_LDS, s>>>(
-                w.sub_f6, (const unsigned char*)lib_sub, rho, w.sub_g, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, gate, 0, 1, sa8);
-        knn_score6_kernel<<<dim3((unsigned)fb6, p.split), 256, lds, s>>>(
-            w.s_f8, (const unsigned char*)lib_f8, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, gate, 1, 2, sa8);
-    } else if (f6)
-        knn_score6_kernel<<<dim3((unsigned)(p.Tt_pad / ft), p.split), 256, lds, s>>>(
-            w.s_f8, (const unsigned char*)lib_f8, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, mode, -1, 0, sa8);
-    else
-        knn_score8_kernel<<<dim3((unsigned)(p.Tt_pad / ft), p.split), 256, lds, s>>>(
-            w.s_f8, (const unsigned char*)lib_f8, M, p.tiles_total, p.tiles_per_split, p.P, w.cv, w.ci, mode, -1, 0, sa8);
-    if (g_ev_stop) (void)hipEventRecord(g_ev_stop, s);
-    rescore_launch((unsigned)((Tt + 3) / 4), s, w.cv, w.ci, p.P, KP8, w.s_f32, rows_f32, norms, w.rows_hat, Tt, idx_base, k,
-                                                               out_val, out_idx, nullptr, mode, -1, 0, w.list0, w.stats + ST_FLAG8,
-                                                               CERT_Z, KH8, pre, prior, nullptr, nullptr, nullptr, 0, 0.0f, f6 ? w.clip6 : nullptr);
-    // ---- mode 1: bf16 first (every frame into list0) ----
-    if (w.probe_n > 0) flag_all_kernel<<<(unsigned)((Tt + 255) / 256), 256, 0, s>>>(w.list0, w.stats + ST_FLAG8, Tt, mode, 0, 1);
-    if (w.probe_n > 0) probe_history_kernel<<<1, 1, 0, s>>>(w.stats, Tt);        // (ST_FLAG8 is final here: the tiers below only read it)
-    bf16_tiers_launch(w, lib_bf16, rows_f32, norms, M, Tt, idx_base, k, out_val, out_idx, s);
-    ALIVE_CHECK_LAUNCH("alive_knn_search_fp8");
-    return ALIVE_OK;
-}
-
+// The same search with the candidate stage on the fp8 MFMA (knn_score8_kernel); lib_f8 from alive_library_pack_fp8.
 extern "C" int alive_knn_search_fp8(const float* src, int N, int T, const void* lib_f8, const void* lib_bf16, const float* rows_f32,
                                     const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
                                     void* ws, void* stream) {
-    return knn_search_fp8_impl(src, N, T, lib_f8, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream, nullptr, nullptr);
+    const AliveKnnSearch a{.form = ALIVE_KNN_FP8, .N = N, .T = T, .k = k, .src = src, .lib_stage = lib_f8, .lib_bf16 = lib_bf16, .rows_f32 = rows_f32,
+                           .norms = norms, .M = M, .idx_base = idx_base, .out_val = out_val, .out_idx = out_idx, .ws = ws};
+    return knn_search_dispatch("alive_knn_search_fp8", a, false, (hipStream_t)stream);
 }
 extern "C" int alive_knn_search_fp8_timed(const float* src, int N, int T, const void* lib_f8, const void* lib_bf16, const float* rows_f32,
                                           const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
                                           void* ws, void* stream, void* ev_start, void* ev_stop) {
-    return knn_search_fp8_impl(src, N, T, lib_f8, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream,
-                               (hipEvent_t)ev_start, (hipEvent_t)ev_stop);
+    const AliveKnnSearch a{.form = ALIVE_KNN_FP8, .N = N, .T = T, .k = k, .src = src, .lib_stage = lib_f8, .lib_bf16 = lib_bf16, .rows_f32 = rows_f32,
+                           .norms = norms, .M = M, .idx_base = idx_base, .out_val = out_val, .out_idx = out_idx, .ws = ws, .ev_start = ev_start,
+                           .ev_stop = ev_stop};
+    return knn_search_dispatch("alive_knn_search_fp8_timed", a, false, (hipStream_t)stream);
 }
 
 // The fp8 search on ROTATED operands (dense banks; rot_codes_kernel above).  y_rows: [count][576] fp32 coordinates of the unit rows
@@ -4184,22 +4299,28 @@ extern "C" int alive_library_pack_fp8_rot(const float* y_rows, int64_t m0, int64
 extern "C" int alive_knn_search_fp8_rot_timed(const float* src, const float* y_rot, float c0, int N, int T, const void* lib_f8_rot, const void* lib_bf16,
                                               const float* rows_f32, const float* norms, int64_t M, int64_t idx_base, int k, float* out_val,
                                               int32_t* out_idx, void* ws, void* stream, void* ev_start, void* ev_stop) {
-    ALIVE_CHECK_ARG(y_rot != nullptr, "alive_knn_search_fp8_rot: null rotated frames");
-    return knn_search_fp8_impl(src, N, T, lib_f8_rot, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream,
-                               (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 0, y_rot, c0);
+    ALIVE_CHECK_ARG(y_rot != nullptr, "alive_knn_search_fp8_rot_timed: null rotated frames");
+    const AliveKnnSearch a{.form = ALIVE_KNN_FP8_ROT, .N = N, .T = T, .k = k, .src = src, .lib_stage = lib_f8_rot, .lib_bf16 = lib_bf16,
+                           .rows_f32 = rows_f32, .norms = norms, .y = y_rot, .rot_c0 = c0, .M = M, .idx_base = idx_base, .out_val = out_val,
+                           .out_idx = out_idx, .ws = ws, .ev_start = ev_start, .ev_stop = ev_stop};
+    return knn_search_dispatch("alive_knn_search_fp8_rot_timed", a, false, (hipStream_t)stream);
 }
 
 // The same search with the candidate stage on the fp6 MFMA (knn_score6_kernel); lib_f6 from alive_library_pack_fp6.
 extern "C" int alive_knn_search_fp6(const float* src, int N, int T, const void* lib_f6, const void* lib_bf16, const float* rows_f32,
                                     const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
                                     void* ws, void* stream) {
-    return knn_search_fp8_impl(src, N, T, lib_f6, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream, nullptr, nullptr, 2);
+    const AliveKnnSearch a{.form = ALIVE_KNN_FP6, .N = N, .T = T, .k = k, .src = src, .lib_stage = lib_f6, .lib_bf16 = lib_bf16, .rows_f32 = rows_f32,
+                           .norms = norms, .M = M, .idx_base = idx_base, .out_val = out_val, .out_idx = out_idx, .ws = ws};
+    return knn_search_dispatch("alive_knn_search_fp6", a, false, (hipStream_t)stream);
 }
 extern "C" int alive_knn_search_fp6_timed(const float* src, int N, int T, const void* lib_f6, const void* lib_bf16, const float* rows_f32,
                                           const float* norms, int64_t M, int64_t idx_base, int k, float* out_val, int32_t* out_idx,
                                           void* ws, void* stream, void* ev_start, void* ev_stop) {
-    return knn_search_fp8_impl(src, N, T, lib_f6, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream,
-                               (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 2);
+    const AliveKnnSearch a{.form = ALIVE_KNN_FP6, .N = N, .T = T, .k = k, .src = src, .lib_stage = lib_f6, .lib_bf16 = lib_bf16, .rows_f32 = rows_f32,
+                           .norms = norms, .M = M, .idx_base = idx_base, .out_val = out_val, .out_idx = out_idx, .ws = ws, .ev_start = ev_start,
+                           .ev_stop = ev_stop};
+    return knn_search_dispatch("alive_knn_search_fp6_timed", a, false, (hipStream_t)stream);
 }
 
 // The subspace form of the fp6 search (knn_sub6_kernel): y_sub = [U | u]^T src [N][576][T] (alive_conv1d of the frames, unnormalised),
@@ -4210,10 +4331,13 @@ extern "C" int alive_knn_search_fp6_sub_timed(const float* src, const float* y_s
                                               const void* lib_f6, const void* lib_bf16, const float* rows_f32, const float* norms, int64_t M,
                                               int64_t idx_base, int k, float* out_val, int32_t* out_idx, void* ws, void* stream,
                                               void* ev_start, void* ev_stop) {
-    ALIVE_CHECK_ARG(y_sub && lib_sub && rho, "alive_knn_search_fp6_sub: null subspace operand");
-    return knn_search_fp8_impl(src, N, T, lib_f6, lib_bf16, rows_f32, norms, M, idx_base, k, out_val, out_idx, ws, stream,
-                               (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 2, nullptr, 0.0f, y_sub, lib_sub, rho);
+    ALIVE_CHECK_ARG(y_sub && lib_sub && rho, "alive_knn_search_fp6_sub_timed: null subspace operand");
+    const AliveKnnSearch a{.form = ALIVE_KNN_FP6_SUB, .N = N, .T = T, .k = k, .src = src, .lib_stage = lib_f6, .lib_bf16 = lib_bf16,
+                           .rows_f32 = rows_f32, .norms = norms, .y = y_sub, .lib_sub = lib_sub, .rho = rho, .M = M, .idx_base = idx_base,
+                           .out_val = out_val, .out_idx = out_idx, .ws = ws, .ev_start = ev_start, .ev_stop = ev_stop};
+    return knn_search_dispatch("alive_knn_search_fp6_sub_timed", a, false, (hipStream_t)stream);
 }
+
 // Unit rows of a packed library, once per library: rows_hat[M][768] = fl(rows_f32 / norms), the quotients knn_rescore_kernel, knn_exact_kernel
 // and knn_scan_kernel form on every call (div_by above: the same bits).  3 KB per row beside the rows themselves, which stay: the gather
 // returns the ORIGINAL rows, and fl(fl(x / n) n) != x.
@@ -4232,47 +4356,9 @@ extern "C" int alive_library_pack_unit_rows(const float* rows_f32, const float* 
 // named entry's own arithmetic.
 extern "C" int alive_knn_search_unit(const AliveKnnSearch* a, void* stream) {
     ALIVE_CHECK_ARG(a != nullptr, "alive_knn_search_unit: null arguments");
-    hipEvent_t e0 = (hipEvent_t)a->ev_start, e1 = (hipEvent_t)a->ev_stop;
-    switch (a->form) {
-        case ALIVE_KNN_BF16:
-            return knn_search_impl(a->src, a->N, a->T, a->lib_bf16, a->rows_f32, a->norms, a->M, a->idx_base, a->k, a->out_val, a->out_idx, a->ws,
-                                   stream, e0, e1, nullptr, nullptr, a->rows_hat);
-        case ALIVE_KNN_STRICT:
-            ALIVE_CHECK_ARG(a->bound != nullptr, "alive_knn_search_unit: strict form without a bound (alive_library_rounding_bound)");
-            return knn_search_impl(a->src, a->N, a->T, a->lib_bf16, a->rows_f32, a->norms, a->M, a->idx_base, a->k, a->out_val, a->out_idx, a->ws,
-                                   stream, e0, e1, a->bound, a->lib_lo, a->rows_hat);
-        case ALIVE_KNN_FP8:
-        case ALIVE_KNN_FP6:
-            return knn_search_fp8_impl(a->src, a->N, a->T, a->lib_stage, a->lib_bf16, a->rows_f32, a->norms, a->M, a->idx_base, a->k, a->out_val,
-                                       a->out_idx, a->ws, stream, e0, e1, a->form == ALIVE_KNN_FP6 ? 2 : 0, nullptr, 0.0f, nullptr, nullptr,
-                                       nullptr, a->rows_hat);
-        case ALIVE_KNN_FP8_ROT:
-            ALIVE_CHECK_ARG(a->y != nullptr, "alive_knn_search_unit: rotated form without the rotated frames");
-            return knn_search_fp8_impl(a->src, a->N, a->T, a->lib_stage, a->lib_bf16, a->rows_f32, a->norms, a->M, a->idx_base, a->k, a->out_val,
-                                       a->out_idx, a->ws, stream, e0, e1, 0, a->y, a->rot_c0, nullptr, nullptr, nullptr, a->rows_hat);
-        case ALIVE_KNN_FP6_SUB: {
-            ALIVE_CHECK_ARG((a->y || a->sub_w) && a->lib_sub && a->rho, "alive_knn_search_unit: null subspace operand");
-            const float* y = a->y;
-            const int64_t Tt = (int64_t)a->N * a->T;
-            if (y == nullptr && a->src && a->ws && a->N > 0 && a->T > 0 && a->k >= 1 && a->k <= KH && !(Tt * a->k <= 64 && a->M <= SCAN_ROWS_MAX)) {
-                // the frames' change of basis as a plane GEMM (three bf16 MFMAs per product, as alive_conv1d's split form, without its
-                // fp32 loads and in-loop splits): src -> two k-blocked bf16 planes -> [U | u]^T src, both in the subspace workspace
-                ALIVE_CHECK_ARG(Tt * SUB_C < (1ll << 30), "alive_knn_search_unit: %lld frames exceed the plane GEMM's 32-bit offsets (pass y)", (long long)Tt);
-                const SearchWs w = ws_layout(a->ws, Tt, a->M, a->k, false, true);
-                if (int rc = alive_to_planes(a->src, a->N, D, a->T, 2, w.sub_planes, stream)) return rc;
-                AliveGemm g{};
-                g.W = a->sub_w; g.P = w.sub_planes; g.N = a->N; g.T = a->T; g.Ci = D; g.Co = SUB_C; g.planes = 2; g.Y = w.sub_y;
-                if (int rc = alive_gemm_planes(&g, stream)) return rc;
-                y = w.sub_y;
-            }
-            return knn_search_fp8_impl(a->src, a->N, a->T, a->lib_stage, a->lib_bf16, a->rows_f32, a->norms, a->M, a->idx_base, a->k, a->out_val,
-                                       a->out_idx, a->ws, stream, e0, e1, 2, nullptr, 0.0f, y, a->lib_sub, a->rho, a->rows_hat, true);
-        }
-        default:
-            ALIVE_CHECK_ARG(false, "alive_knn_search_unit: form %d", a->form);
-    }
-    return ALIVE_OK;
+    return knn_search_dispatch("alive_knn_search_unit", *a, true, (hipStream_t)stream);
 }
+
 extern "C" int alive_knn_sub_coordinates(void) { return SUB_C; }
 extern "C" size_t alive_library_fp6_sub_bytes(int64_t M) { return (size_t)alive_library_padded_rows(M) * SUB_K; }
 // y_rows: [count][576] fp32 coordinates of the unit rows m0 .. m0 + count - 1 (U^T r^ in 0 .. 511, u . r^ in 512); lib_sub: alive_library_fp6_sub_bytes(M),
@@ -4302,7 +4388,7 @@ extern "C" int alive_library_pack_fp6_sub(const float* y_rows, int64_t m0, int64
 //   [22] frames per block of the subspace kernel it launched: 384 (knn_sub6_kernel) / 512 (knn_sub6w_kernel, alive_knn_sub_frames)
 // (the counters are the first thing in the workspace: their address depends on neither the batch nor k)
 extern "C" const int* alive_knn_search_stats(int N, int T, int64_t M, void* ws) {
-    return ws_layout(ws, (int64_t)N * T, M, 4).stats;
+    return ws_layout(ws, (int64_t)N * T, M, 4, WS_FAST).stats;
 }
 
 // debug (tests/test_gpu_knn_stage.py): where the first stage's buffers sit in the workspace of a search of Tt frames against M rows at
@@ -4312,7 +4398,7 @@ extern "C" const int* alive_knn_search_stats(int N, int T, int64_t M, void* ws) 
 //   out[20 .. 24] KP, KP8 (candidates per frame and split: bf16 / block-scaled), FT, FT6 (frames per block), LT (rows per tile)
 extern "C" int alive_debug_knn_stage_view(int64_t Tt, int64_t M, int k, int sub, int64_t* out, int n_out) {
     ALIVE_CHECK_ARG(out && n_out >= 25 && Tt >= 1 && M >= 1 && k >= 1 && k <= ALIVE_MAX_K, "alive_debug_knn_stage_view: bad args");
-    const SearchWs w = ws_layout(nullptr, Tt, M, k, false, sub != 0);
+    const SearchWs w = ws_layout(nullptr, Tt, M, k, sub != 0 ? WS_SUB : WS_FAST);
     auto off = [](const void* p) { return p != nullptr ? (int64_t)(intptr_t)p : (int64_t)-1; };
     const int64_t head[8] = {off(w.s_bf16), off(w.s_f8), off(w.clip6), off(w.sub_f6), off(w.sub_g), off(w.cv), off(w.ci), (int64_t)w.bytes};
     for (int i = 0; i < 8; ++i) out[i] = head[i];
@@ -4350,22 +4436,15 @@ extern "C" int alive_debug_knn_sub_stage(const void* s_sub, const float* g, int6
     p.tiles_per_split = (p.tiles_total + split - 1) / split;
     const int mode = sub_frames_mode();
     const bool wide = mode != FT6 && p.tiles_per_split <= SUB6W_MAX_TILES;
-    const SeedArgs none{nullptr, nullptr, 0, 0.0f, nullptr};
-    hipStream_t s = (hipStream_t)stream;
-    if (wide)
-        knn_sub6w_kernel<<<dim3((unsigned)(Tt_pad / FT6W), split), 256, SUB6W_LDS, s>>>(
-            (const unsigned char*)s_sub, (const unsigned char*)lib_sub, rho, g, M, p.tiles_total, p.tiles_per_split, p.P, cand_val, cand_idx,
-            nullptr, 0, 1, none);
-    else
-        knn_sub6_kernel<<<dim3((unsigned)(Tt_pad / FT6), split), 256, SUB6_LDS, s>>>(
-            (const unsigned char*)s_sub, (const unsigned char*)lib_sub, rho, g, M, p.tiles_total, p.tiles_per_split, p.P, cand_val, cand_idx,
-            nullptr, 0, 1, none);
+    stage_launch(wide ? STAGE_SUB6W : STAGE_SUB6, dim3((unsigned)(Tt_pad / (wide ? FT6W : FT6)), split), wide ? SUB6W_LDS : SUB6_LDS,
+                 (hipStream_t)stream, StageOps{(const unsigned char*)s_sub, (const unsigned char*)lib_sub, rho, g, M, p, cand_val, cand_idx},
+                 Gate{nullptr, 0, 1}, NO_SEEDS);
     ALIVE_CHECK_LAUNCH("alive_debug_knn_sub_stage");
     *frames_out = wide ? FT6W : FT6;
     return ALIVE_OK;
 }
 
-// debug (tests/test_gpu_knn_cert.py): knn_rescore_kernel through rescore_launch / pool_rescore_launch on the caller's buffers.  What
+// debug (tests/test_gpu_knn_cert.py): knn_rescore_kernel through rescore_launch, the searches' own launcher, on the caller's buffers.  What
 // the kernel indexes with is checked here as far as the host can see it (sizes and pointers); the contents of cand_idx, frame_list,
 // out_idx and the pool plan stay on the device and are the caller's to check.
 static int debug_rescore_check(const char* who, const AliveRescoreArgs* a, bool pool) {
@@ -4390,17 +4469,22 @@ static int debug_rescore_check(const char* who, const AliveRescoreArgs* a, bool 
     return ALIVE_OK;
 }
 
+// the caller's record as the searches' own (no unit rows; the pool form adds its plan)
+static Rescore debug_rescore_record(const AliveRescoreArgs& a) {
+    Rescore r{a.cand_val, a.cand_idx, a.P, a.kp, a.s_f32, a.rows, a.norms, nullptr, a.Tt, a.idx_base, a.k, a.out_val, a.out_idx, a.frame_list,
+              Gate{a.gate_cnt, a.gate_lo, a.gate_hi}, a.flag_list, a.flag_cnt, a.zsig, a.list_len, a.pre_scale, a.sd_prior};
+    r.det_q = a.det_q; r.det_lib = a.det_lib;
+    r.thr_list = a.thr_list; r.collect = a.collect; r.overflow_slack = a.overflow_slack;
+    r.force_fail = a.force_fail;
+    return r;
+}
+
 extern "C" int alive_debug_knn_rescore(const AliveRescoreArgs* a, void* stream) {
     if (int rc = debug_rescore_check("alive_debug_knn_rescore", a, false)) return rc;
-    rescore_launch((unsigned)((a->Tt + 3) / 4), (hipStream_t)stream, a->cand_val, a->cand_idx, a->P, a->kp, a->s_f32, a->rows, a->norms, nullptr, a->Tt,
-                   a->idx_base, a->k, a->out_val, a->out_idx, a->frame_list, a->gate_cnt, a->gate_lo, a->gate_hi, a->flag_list, a->flag_cnt,
-                   a->zsig, a->list_len, a->pre_scale, a->sd_prior, a->det_q, a->det_lib, a->thr_list, a->collect, a->overflow_slack,
-                   a->force_fail);
+    rescore_launch((unsigned)((a->Tt + 3) / 4), (hipStream_t)stream, debug_rescore_record(*a));
     ALIVE_CHECK_LAUNCH("alive_debug_knn_rescore");
     return ALIVE_OK;
 }
-
-// (alive_debug_knn_rescore_pool stands behind the pool search, whose launcher it shares)
 
 extern "C" int alive_debug_knn_pool_fields(int32_t* out, int n_out) {
     ALIVE_CHECK_ARG(out && n_out >= 4, "alive_debug_knn_pool_fields: bad args");
@@ -4469,9 +4553,7 @@ static int search_grouped(const char* who, const float* src, int N, int T, const
     src_prep_small_kernel<<<(unsigned)Tt, 256, 0, s>>>(src, T, Tt, w.s_f32, w.s_bf16, nullptr);
     knn_grouped_plan_kernel<<<1, 256, 0, s>>>(seg_lo, seg_len, k_row, N, T, P, k, w);
     knn_grouped_scan_kernel<RT><<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, T, w);
-    if (k_row != nullptr) knn_grouped_merge_kernel<MERGE_ROW><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
-    else if (k <= 4) knn_grouped_merge_kernel<MERGE_K4><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
-    else knn_grouped_merge_kernel<MERGE_GEN><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx);
+    with_merge_form(k_row, k, [&](auto m) { knn_grouped_merge_kernel<decltype(m)::value><<<(unsigned)Tt, 256, 0, s>>>(T, k, w, out_val, out_idx); });
     ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
 }
@@ -4642,7 +4724,7 @@ static bool pool_args_ok(int N, int T, int k, int V, int64_t P, int64_t max_len)
 
 extern "C" size_t alive_knn_pool_workspace_bytes(int N, int T, int k, int V, int64_t P, int64_t max_len) {
     if (!pool_args_ok(N, T, k, V, P, max_len)) return 0;
-    return pool_ws_layout(nullptr, N, T, k, V, max_len).bytes;
+    return pool_ws_layout(nullptr, N, T, k, V, max_len, 1).bytes;
 }
 
 // per-row k: a voice may be searched at up to k_max values of k, each a group of its own (at most min(N, k_max V) groups)
@@ -4652,17 +4734,6 @@ extern "C" size_t alive_knn_pool_k_workspace_bytes(int N, int T, int k_max, int 
 }
 
 extern "C" const int* alive_knn_pool_stats(void* ws) { return (const int*)ws; }
-
-// the pool form of rescore_launch: the same choice of PER; `rest` ends in the PoolRescore
-template <typename... A>
-static void pool_rescore_launch(unsigned grid, hipStream_t s, const float* cv, const int* ci, int P, int kp, A... rest) {
-    const int R = P * kp;
-    if (R <= 64) knn_rescore_kernel<0, true><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else if (R <= 192) knn_rescore_kernel<3, true><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else if (R <= 256) knn_rescore_kernel<4, true><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else if (R <= 512) knn_rescore_kernel<8, true><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-    else knn_rescore_kernel<16, true><<<grid, 256, 0, s>>>(cv, ci, P, kp, rest...);
-}
 
 // both pool entry points: k_row null = every row at k (alive_knn_search_pool), else k = k_max and row n at k_row[n]
 static int search_pool(const char* who, const float* src, int N, int T, const void* images, const int64_t* img_off, const float* rows_f32,
@@ -4694,17 +4765,17 @@ static int search_pool(const char* who, const float* src, int N, int T, const vo
     knn_pool_gather_kernel<<<(unsigned)w.S, 128, 0, s>>>(T, w);
     const PoolBlocks pb{w.hdr, w.blk_voice, img_off, seg_lo, seg_len};
     knn_score_kernel<false, true><<<dim3((unsigned)(w.S / FT), w.P), 256, SCORE_LDS, s>>>(
-        w.s_c, (const unsigned short*)images, 0, 0, 0, w.P, w.cv, w.ci, nullptr, 0, 0, 0, nullptr, SeedArgs{nullptr, nullptr, 0, 0.0f, nullptr}, 0,
-        pb);
-    const PoolRescore pr{w.slot_grp, w.grp, w.gfail, w.fb};
-    // (the kernel takes each frame's k from its group; the k argument is the stride of the lists)
-    pool_rescore_launch((unsigned)(w.S / 4), s, w.cv, w.ci, w.P, KP, w.s_f32, rows_f32, norms, nullptr, w.S, 0, k, out_val, out_idx, w.slot_frame,
-                        nullptr, 0, 0, w.fb, w.stats, CERT_Z, KH, 1.0f, SD_PRIOR16, w.dq, bounds, nullptr, 0, 0.0f, nullptr, pr);
+        w.s_c, (const unsigned short*)images, 0, 0, 0, w.P, w.cv, w.ci, nullptr, 0, 0, 0, nullptr, NO_SEEDS, 0, pb);
+    // the strict search's certificate on the slots of the plan, every voice under its own bound (the kernel takes each frame's k from
+    // its group; the k member is the stride of the lists)
+    Rescore rs{w.cv, w.ci, w.P, KP, w.s_f32, rows_f32, norms, nullptr, w.S, 0, k, out_val, out_idx, w.slot_frame, Gate{nullptr, 0, 0},
+               w.fb, w.stats, CERT_Z, KH, 1.0f, SD_PRIOR16};
+    rs.det_q = w.dq; rs.det_lib = bounds;
+    rs.pool = PoolRescore{w.slot_grp, w.grp, w.gfail, w.fb};
+    rescore_launch((unsigned)(w.S / 4), s, rs);
     knn_pool_fallback_plan_kernel<<<1, 64, 0, s>>>(seg_len, w);
     knn_pool_scan_kernel<<<GR_BLOCKS, 64 * SCAN_WAVES, 0, s>>>(rows_f32, norms, seg_lo, seg_len, w);
-    if (k_row != nullptr) knn_pool_merge_kernel<MERGE_ROW><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
-    else if (k <= 4) knn_pool_merge_kernel<MERGE_K4><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
-    else knn_pool_merge_kernel<MERGE_GEN><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx);
+    with_merge_form(k_row, k, [&](auto m) { knn_pool_merge_kernel<decltype(m)::value><<<POOL_MERGE_BLOCKS, 256, 0, s>>>(k, w, out_val, out_idx); });
     ALIVE_CHECK_LAUNCH(who);
     return ALIVE_OK;
 }
@@ -4730,11 +4801,9 @@ extern "C" int alive_debug_knn_rescore_pool(const AliveRescoreArgs* a, const int
                                             int32_t* fb, int groups, void* stream) {
     if (int rc = debug_rescore_check("alive_debug_knn_rescore_pool", a, true)) return rc;
     ALIVE_CHECK_ARG(slot_grp && grp && gfail && fb && groups >= 1, "alive_debug_knn_rescore_pool: null pointer or no group");
-    const PoolRescore pr{slot_grp, grp, gfail, fb};
-    pool_rescore_launch((unsigned)((a->Tt + 3) / 4), (hipStream_t)stream, a->cand_val, a->cand_idx, a->P, a->kp, a->s_f32, a->rows, a->norms,
-                        nullptr, a->Tt, a->idx_base, a->k, a->out_val, a->out_idx, a->frame_list, a->gate_cnt, a->gate_lo, a->gate_hi, a->flag_list,
-                        a->flag_cnt, a->zsig, a->list_len, a->pre_scale, a->sd_prior, a->det_q, a->det_lib, a->thr_list, a->collect,
-                        a->overflow_slack, a->force_fail, pr);
+    Rescore rs = debug_rescore_record(*a);
+    rs.pool = PoolRescore{slot_grp, grp, gfail, fb};
+    rescore_launch((unsigned)((a->Tt + 3) / 4), (hipStream_t)stream, rs);
     ALIVE_CHECK_LAUNCH("alive_debug_knn_rescore_pool");
     return ALIVE_OK;
 }
